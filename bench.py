@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""bench.py — full-pipeline MUSICA throughput on N MI355X GPUs + roofline of the metric kernel.
+"""bench.py — full-pipeline MUSICA throughput on N MI355X GPUs (+ with --full: roofline of the metric kernel and the rest).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C2|C3|C5|REF]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C2|C3|C5|REF] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole hot path (minmax -> pyramid reduce -> analysis -> contrast /
 noise-reduction + expand -> gradation) over one batch of synthetic raw images already resident in
 HBM. Steps alternate over --in-flight contexts (default 3, the C ABI's musica_pipeline_*: step s is enqueued on context s mod 3, each
 context with its own copy of the input, its own buffers and ONE in-order stream, so the chip-filling kernels of a step
-run in the part-idle phases of the two steps beside it); `one_context` in the JSON line is the same K steps on a single
+run in the part-idle phases of the two steps beside it); `one_context` in the JSON line of --full is the same K steps on a single
 context with the library's default dispatch for that batch (its `what` names it), each step behind the previous one. After the W warm-up steps the whole job (the same K steps + its
 tail) is rehearsed once, untimed; the timed region is then EXACTLY K steps between a barrier + device synchronize on both
 sides. Default workload C4 is BASELINE.json configs[3] seen from one GPU:
@@ -20,7 +20,16 @@ timed region, to all-gather the per-image summary statistics (musica_stats) of t
 `python -m torch.distributed.run` before anything touches the GPU, relays rank 0's JSON line and fails if
 the ranks do not all join; under an external launcher (WORLD_SIZE set) it is one rank of that job.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = megapixels/s of the whole job, plus
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step when --dump-outputs is given
+and prints ONE JSON line on rank 0: value = megapixels/s of the whole job, ms_per_step = milliseconds of one timed step.
+
+--dump-outputs DIR: what the timed path hands its caller for its last step, as DIR/<name>.npy (float32 / float64, under 20 MB):
+  stats.npy           : the all-gathered per-image summary rows (musica_stats), one float64 column per 32-bit field, by image id;
+  graded.npy          : rank 0's graded images (float32) at a fixed, seeded sample of DUMP_SAMPLE positions (all of them if fewer);
+  out_pixels.npy      : rank 0's 8-bit output images (saveOutImage's cropped pixels, as float32) at a fixed, seeded sample.
+The inputs are seeded phantoms, so the same arguments give the same inputs in every run.
+
+--full measures everything else after the headline figure and adds it to the line:
   roofline            : the metric kernel BASELINE.json names — fused 5-tap smooth + 2x downsample
                         (k_reduce_dma) on 4096 x 4096 f32 — timed with HIP events on the library's stream
                         over back-to-back launches that ROTATE over 8 distinct input / output planes (640 MB,
@@ -33,7 +42,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement): value = megapix
   kernels             : per-kernel-family mean duration, algorithmic GB/s and share of the step;
   cpu_baseline        : the CPU oracle (a port: the reference has no CPU path) on a bounded sample;
   reference_3072_L12  : one 3072 x 3072 image per execute with the reference's 12 levels, one context (the reference's call shape);
-  cli                 : wall time of `musica-standalone image.raw out.bmp` at that size, 5 fresh processes, and its own timing line.
+  cli                 : wall time of `musica-standalone image.raw out.bmp` at that size, 5 fresh processes, and its own timing line;
+  one_context, e2e_host_MPps, job_one_pass, e2e_host_overlapped, single_image: the same pipeline in one-context and host-input call shapes.
 """
 import argparse
 import json
@@ -105,7 +115,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="C4", type=str.upper, choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and report everything else: one-context and host-input call shapes, per-kernel "
+                         "figures, the stand-alone metric kernel (roofline), the reference's configuration and CLI, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64; see the module docstring)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of the CPU baseline sample of --full (0 = skip)")
     ap.add_argument("--in-flight", type=int, default=3,
                     help="contexts whose steps alternate (musica_pipeline_*): step s runs on context s mod D, so the head of a step fills the "
                          "part-idle tail of the one before; 1 = one context, every step behind the previous one")
@@ -116,11 +131,11 @@ def parse_args():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend; gloo + MUSICA_BENCH_ONE_DEVICE=1 rehearses the multi-rank flow on a one-GPU box (every rank on cuda:0, "
                          "the stats rows travel through host memory)")
-    ap.add_argument("--no-single-image", action="store_true", help="skip the one-image-per-execute measurement (keeps a kernel trace of the run pure)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip the per-kernel event passes after the timed region")
-    ap.add_argument("--no-standalone", action="store_true", help="skip the stand-alone 4096^2 metric-kernel measurements (roofline becomes the in-pipeline launch)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not collect the metric kernel's HBM traffic with rocprofv3 --pmc (roofline.traffic then comes from profiles/pmc_traffic.json)")
-    ap.add_argument("--no-cli", action="store_true", help="skip the drop-in measurement (musica-standalone <raw> <bmp> in fresh processes at 3072^2 / L12)")
+    ap.add_argument("--no-single-image", action="store_true", help="--full: skip the one-image-per-execute measurement (keeps a kernel trace of the run pure)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip the per-kernel event passes after the timed region")
+    ap.add_argument("--no-standalone", action="store_true", help="--full: skip the stand-alone 4096^2 metric-kernel measurements (roofline becomes the in-pipeline launch)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not collect the metric kernel's HBM traffic with rocprofv3 --pmc (roofline.traffic then comes from profiles/pmc_traffic.json)")
+    ap.add_argument("--no-cli", action="store_true", help="--full: skip the drop-in measurement (musica-standalone <raw> <bmp> in fresh processes at 3072^2 / L12)")
     return ap.parse_args()
 
 
@@ -203,144 +218,73 @@ def cpu_model():
     return "unknown"
 
 
-def main():
-    args = parse_args()
-    if args.gpus < 1:
-        raise SystemExit("--gpus must be >= 1")
-    if "WORLD_SIZE" not in os.environ:
-        if args.gpus > 1:
-            return self_launch(args)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        raise SystemExit("WORLD_SIZE (%d) != --gpus (%d): start %d ranks, or run `python bench.py --gpus %d` without a launcher" % (world, args.gpus, args.gpus, args.gpus))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = 0 if os.environ.get("MUSICA_BENCH_ONE_DEVICE") == "1" else int(os.environ.get("LOCAL_RANK", "0"))
+DUMP_SAMPLE = 1 << 21     # positions sampled from each dumped image array (8 MB of float32)
+DUMP_SEED = 20240229      # fixed: the same positions in every run, so two builds compare output for output
+
+
+def make_inputs(n, image_ids, bits):
+    """The rank's shard of seeded phantoms (C4 uses default_rng(100 + k)), generated on a few host threads. Each phantom
+    depends on its seed alone, so the batch is the same whatever the number of threads."""
+    from concurrent.futures import ThreadPoolExecutor
 
     import numpy as np
-    import torch  # first: libmusica_hip.so then binds to the HIP runtime torch already loaded
-    import torch.distributed as dist
+
+    from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd.phantom import phantom
+    try:
+        cores = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cores = os.cpu_count() or 1
+    with ThreadPoolExecutor(max(1, min(len(image_ids), cores, 16))) as ex:
+        return np.stack(list(ex.map(lambda k: phantom(n, 100 + k, bits=bits), image_ids)))
+
+
+def stats_columns(rows, stats_type):
+    """int32 musica_stats rows -> float64 [rows, words], each 32-bit word read as the field it holds (uint32 or float32), by image id."""
+    import ctypes
+
+    import numpy as np
+    is_float = []
+    for _, t in stats_type._fields_:
+        base, count = (t._type_, t._length_) if issubclass(t, ctypes.Array) else (t, 1)
+        is_float += [base is ctypes.c_float] * count
+    r = np.ascontiguousarray(rows, dtype=np.int32)
+    assert r.shape[1] == len(is_float)
+    f, u = r.view(np.float32), r.view(np.uint32)
+    cols = np.stack([(f if fl else u)[:, j].astype(np.float64) for j, fl in enumerate(is_float)], axis=1)
+    return cols[np.argsort(cols[:, 0], kind="stable")]
+
+
+def dump_outputs(out_dir, ctx, rows, stats_type):
+    """--dump-outputs: what the caller of the timed path receives for its last step (module docstring), read from the context that ran it."""
+    import numpy as np
+
+    def sample(a):
+        a = a.reshape(-1)
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=DUMP_SAMPLE, replace=False))]
+        return a.astype(np.float32)
+
+    out = {"stats": stats_columns(rows, stats_type),
+           "graded": sample(ctx.graded()),
+           "out_pixels": sample(np.stack([ctx.out_pixels(k) for k in range(ctx.batch)]))}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
+def measure_full(args, pipe, proc, px, n, levels, batch, flags, depth, world, rank, local_rank, kernel_events, elapsed):
+    """--full: everything the line reports beside the headline figure, measured after the timed region (module docstring).
+    The one-context and per-kernel passes run on every rank; the rest on rank 0, which gets the extra fields of the line."""
+    import torch
 
     from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import batch as mb
     from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp
     from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd.phantom import phantom
 
-    if not torch.cuda.is_available() or mp.device_count() < 1:
-        raise SystemExit("bench.py needs a HIP device: the MUSICA path has no CPU fallback")
-    if torch.cuda.device_count() < local_rank + 1:
-        raise SystemExit("rank %d wants cuda:%d but only %d device(s) are visible" % (rank, local_rank, torch.cuda.device_count()))
-    torch.cuda.set_device(local_rank)
-    distributed = world > 1
-    if distributed:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if args.backend == "nccl":
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-        else:
-            dist.init_process_group("gloo", rank=rank, world_size=world)
-        if dist.get_world_size() != args.gpus:
-            raise SystemExit("process group has %d ranks, --gpus asked for %d" % (dist.get_world_size(), args.gpus))
-
-    n, levels, batch, bits, flags, desc = WORKLOADS[args.workload]
-    if args.batch > 0:
-        batch = args.batch
-        desc += " [--batch %d override]" % batch
-    image_ids = mb.assign_images(world * batch, world)[rank]      # image k -> rank k mod world (SURVEY 8e)
-    assert len(image_ids) == batch
-    px = np.stack([phantom(n, 100 + k, bits=bits) for k in image_ids])   # C4 uses default_rng(100 + k)
-
-    depth = 1 if args.kernel_events else max(1, args.in_flight)   # events inside the timed steps need the one profiled context
-    try:
-        pipe = mp.MusicaPipeline(n, levels=levels, batch=batch, depth=depth, flags=flags, device=local_rank)   # the C ABI's musica_pipeline_*
-    except RuntimeError as e:
-        raise SystemExit(str(e))
-    pipe.upload(px)                                                # inputs resident in HBM (one copy per context) before the timed region
-    pipe.prime()                                                   # every context has captured its graph; the best set of hardware queues is kept
-    queue_calibration = {str(k): round(v, 4) for k, v in pipe.calibration().items()} or None
-    sdev_in_expand = bool(pipe.context(0).fuses_sdev())              # the timed contexts compute sdev inside the expand launches of levels 0 .. 2 (no stored sdev images there)
-    if depth == 1:
-        proc = pipe.context(0)
-    else:                                                          # the per-kernel passes and the other measurements: one context alone, default dispatch
-        proc = mp.MusicaProcessing(device=local_rank)
-        if not proc.init(n, levels=levels, batch=batch, flags=flags):
-            raise SystemExit("musica_create failed: " + mp.last_error())
-        proc.upload(px)
-        for _ in range(2):
-            proc.execute_device()
-        proc.sync()
-
-    d_stats = torch.zeros((batch, mb.STATS_WORDS), dtype=torch.int32, device="cuda")
-
-    def barrier():
-        if distributed:
-            dist.barrier()
-
-    def step():
-        try:
-            pipe.step()
-        except RuntimeError as e:
-            raise SystemExit(str(e))
-
     def step_one():
         if not proc.execute_device():
             raise SystemExit("musica_execute_device failed: " + mp.last_error())
-
-    def finish_job():
-        """End of a job: per-image stats rows of the last step on the device (image ids job-wide: rank + index * world,
-        batch.assign_images), every context drained, one all-gather."""
-        pipe.last().stats_device(d_stats.data_ptr(), image_id_base=rank, image_id_stride=world)
-        pipe.sync()
-        return mb.gather_rows(d_stats, world, dist if distributed else None)   # RCCL over xGMI: the only inter-GPU traffic
-
-    for _ in range(args.warmup):
-        step()
-    finish_job()                                                   # untimed rehearsal: loads torch's / RCCL's kernels, connects the ranks
-
-    # The timed region replays the captured hipGraph (the product's default dispatch). ROCm 7.2 stream capture
-    # drops hipEventRecord calls (devtools/graph_events.hip), so HIP events around a kernel need eager launches:
-    # the level-0 metric kernel is bracketed in a second pass over the same K steps right after the timed region
-    # (2 records per step), and all launches in a third pass (costs ~18 % of the step) for the "kernels" table.
-    # --kernel-events moves the level-0 events into the timed region itself (eager launches, ~4 % slower).
-    kernel_events = args.kernel_events
-    proc.profile_reset()
-    proc.profile_enable(["reduce_l0"] if kernel_events else False)
-
-    # One untimed rehearsal of the whole job (the same K steps + the tail) right before the timed one: the first K-step run
-    # after start-up is 3 - 5 % slower than every later one (7.86 ms against 7.52 - 7.59 for 20 steps, same process: clocks
-    # and caches settle over more than the W = 5 warm-up steps the driver asks for). MUSICA_BENCH_REHEARSALS=0 turns it off.
-    rehearsals = int(os.environ.get("MUSICA_BENCH_REHEARSALS", "1"))
-    for rep in range(rehearsals):
-        torch.cuda.synchronize()
-        tr = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        tq = time.perf_counter()
-        finish_job()
-        torch.cuda.synchronize()
-        if os.environ.get("MUSICA_BENCH_TRACE") == "1":
-            sys.stderr.write("rehearsal %d: %d steps enqueued %.3f ms, job done %.3f ms\n" % (rep, args.steps, (tq - tr) * 1e3, (time.perf_counter() - tr) * 1e3))
-    barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    t_enq = time.perf_counter()
-    gathered = finish_job()
-    t_fin = time.perf_counter()
-    torch.cuda.synchronize()
-    barrier()
-    t1 = time.perf_counter()
-    if os.environ.get("MUSICA_BENCH_TRACE") == "1":
-        sys.stderr.write("timed region: %d steps enqueued after %.3f ms, finish_job returned after %.3f ms, end %.3f ms\n"
-                         % (args.steps, (t_enq - t0) * 1e3, (t_fin - t0) * 1e3, (t1 - t0) * 1e3))
-
-    elapsed = t1 - t0
-    if distributed:
-        tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
-    st = gathered.cpu().numpy()
-    got_ids = sorted(int(r[0]) for r in st)
-    if st.shape[0] != world * batch or got_ids != list(range(world * batch)):
-        raise SystemExit("stats gather incomplete: %d rows, ids %s (expected %d images from %d ranks)" % (st.shape[0], got_ids[:8], world * batch, world))
 
     proc.profile_enable(False)
     prof_timed = proc.profile()
@@ -376,10 +320,8 @@ def main():
     if prof_timed.get("reduce_l0", (0, 0))[1]:
         prof["reduce_l0"] = prof_timed["reduce_l0"]              # the metric-kernel-only measurement wins
 
-    result = None
     if rank == 0:
         mpix = world * batch * n * n * args.steps / 1e6
-        ms_per_step = elapsed / args.steps * 1e3
         fused = n % 8 == 0
         rb_mode = 2 if proc.fuses_reduce_band() else 0
         le090 = bool(proc.fuses_gradhist() and rb_mode >= 1)
@@ -605,26 +547,7 @@ def main():
                    "host_cpus": os.cpu_count(), "configs0_single_thread": configs0,
                    "sample": "%d x %dx%d images, %d-level pyramid, oracle MUSICA_ORDER_FAST with OpenMP on %d threads, %.1f s"
                              % (done, n, n, levels, cores, tc)}
-        result = {
-            "metric": "megapixels/sec full MUSICA pipeline", "value": round(mpix / elapsed, 1), "unit": "MP/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "value_is": "whole-job MP/s of %d steps enqueued round-robin on %d one-stream contexts of each GPU (steps in flight), every context replaying its own HBM-resident copy "
-                        "of the rank's %d-image shard (inputs do not change between steps; H2D excluded); `one_context`, `single_image`, `reference_3072_L12`, `e2e_host_*` "
-                        "and `cli` are the same pipeline in the reference's one-frame-at-a-time call shapes" % (args.steps, depth, batch),
-            "config": {"workload": desc, "image_size": n, "levels": levels, "images_per_gpu_per_step": batch, "contexts_in_flight": depth, "untimed_rehearsals_of_the_job": rehearsals,
-                       "queue_calibration_ms": queue_calibration,
-                       "sdev_in_expand_launches": sdev_in_expand,
-                       "input": "seeded phantoms, %d-bit" % bits, "dispatch": "eager launches" if (kernel_events or os.environ.get("MUSICA_GRAPH", "1") == "0") else "hipGraph replay",
-                       "kernel_events_in_timed_region": kernel_events, "sharding": "image k -> rank k mod N, no data-path collective",
-                       "stats_gathered": int(st.shape[0]), "ranks_joined": world,
-                       "collective": ("%s all_gather_into_tensor of %d stats rows per rank" % ("RCCL (torch backend nccl)" if args.backend == "nccl" else "gloo", batch)) if distributed else "none (one rank)"},
-            "parity": "timed path = default (separable) order: bit-identical to the build's CPU oracle in that order; with MUSICA_FLAG_REFERENCE_ORDER the GPU runs the "
-                      "shaders' literal 25-tap order, bit-identical to the oracle's literal restatement on every BASELINE config and 3072/L12 (tests/test_gpu_reference_order.py). "
-                      "Default vs literal order, measured at full size on every config (profiles/r03_literal_order_*.json): stencil outputs within 6e-7 / 1e-6, every "
-                      "noise-histogram argmax equal, reconstruction within 4e-6 on all but <= 0.003 % of the texels (max 2.1e-2: blocks under cnr texels at the "
-                      "noise-reduction thresholds 3 / 9), <= 0.011 % of the 8-bit pixels differ (isolated 0 <-> 255 flips at getY's x > 1 -> 0 edge). "
-                      "Parity with the reference itself is unpinned (no vectors in the reference, GLSL not buildable here)",
+        return {
             "roofline": roofline, "roofline_4096_warm": warm, "roofline_pipeline_l0": pipeline_l0, "cpu_baseline": cpu, "kernels": kernels,
             "one_context": {"ms_per_step": round(one_ctx_ms, 4), "value": round(batch * n * n / 1e6 / (one_ctx_ms * 1e-3), 1), "unit": "MP/s per GPU",
                             "what": "the same %d steps on one context alone (%s), each step behind the previous one (rank 0)" % (args.steps, proc.dispatch_text())},
@@ -640,7 +563,179 @@ def main():
             "reference_3072_L12": ref,
             "cli": cli,
         }
-    if depth > 1:
+    return None
+
+
+def main():
+    args = parse_args()
+    if args.gpus < 1:
+        raise SystemExit("--gpus must be >= 1")
+    if "WORLD_SIZE" not in os.environ:
+        if args.gpus > 1:
+            return self_launch(args)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        raise SystemExit("WORLD_SIZE (%d) != --gpus (%d): start %d ranks, or run `python bench.py --gpus %d` without a launcher" % (world, args.gpus, args.gpus, args.gpus))
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = 0 if os.environ.get("MUSICA_BENCH_ONE_DEVICE") == "1" else int(os.environ.get("LOCAL_RANK", "0"))
+
+    import torch  # first: libmusica_hip.so then binds to the HIP runtime torch already loaded
+    import torch.distributed as dist
+
+    from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import batch as mb
+    from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp
+
+    if not torch.cuda.is_available() or mp.device_count() < 1:
+        raise SystemExit("bench.py needs a HIP device: the MUSICA path has no CPU fallback")
+    if torch.cuda.device_count() < local_rank + 1:
+        raise SystemExit("rank %d wants cuda:%d but only %d device(s) are visible" % (rank, local_rank, torch.cuda.device_count()))
+    torch.cuda.set_device(local_rank)
+    distributed = world > 1
+    if distributed:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if args.backend == "nccl":
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
+        else:
+            dist.init_process_group("gloo", rank=rank, world_size=world)
+        if dist.get_world_size() != args.gpus:
+            raise SystemExit("process group has %d ranks, --gpus asked for %d" % (dist.get_world_size(), args.gpus))
+
+    n, levels, batch, bits, flags, desc = WORKLOADS[args.workload]
+    if args.batch > 0:
+        batch = args.batch
+        desc += " [--batch %d override]" % batch
+    image_ids = mb.assign_images(world * batch, world)[rank]      # image k -> rank k mod world (SURVEY 8e)
+    assert len(image_ids) == batch
+    px = make_inputs(n, image_ids, bits)
+
+    depth = 1 if args.kernel_events else max(1, args.in_flight)   # events inside the timed steps need the one profiled context
+    try:
+        pipe = mp.MusicaPipeline(n, levels=levels, batch=batch, depth=depth, flags=flags, device=local_rank)   # the C ABI's musica_pipeline_*
+    except RuntimeError as e:
+        raise SystemExit(str(e))
+    pipe.upload(px)                                                # inputs resident in HBM (one copy per context) before the timed region
+    pipe.prime()                                                   # every context has captured its graph; the best set of hardware queues is kept
+    queue_calibration = {str(k): round(v, 4) for k, v in pipe.calibration().items()} or None
+    sdev_in_expand = bool(pipe.context(0).fuses_sdev())              # the timed contexts compute sdev inside the expand launches of levels 0 .. 2 (no stored sdev images there)
+    if depth == 1:
+        proc = pipe.context(0)
+    elif args.full:                                                # the per-kernel passes and the other measurements: one context alone, default dispatch
+        proc = mp.MusicaProcessing(device=local_rank)
+        if not proc.init(n, levels=levels, batch=batch, flags=flags):
+            raise SystemExit("musica_create failed: " + mp.last_error())
+        proc.upload(px)
+        for _ in range(2):
+            proc.execute_device()
+        proc.sync()
+    else:
+        proc = None                                                # a plain run measures the timed pipeline alone
+
+    d_stats = torch.zeros((batch, mb.STATS_WORDS), dtype=torch.int32, device="cuda")
+
+    def barrier():
+        if distributed:
+            dist.barrier()
+
+    def step():
+        try:
+            pipe.step()
+        except RuntimeError as e:
+            raise SystemExit(str(e))
+
+    def finish_job():
+        """End of a job: per-image stats rows of the last step on the device (image ids job-wide: rank + index * world,
+        batch.assign_images), every context drained, one all-gather."""
+        pipe.last().stats_device(d_stats.data_ptr(), image_id_base=rank, image_id_stride=world)
+        pipe.sync()
+        return mb.gather_rows(d_stats, world, dist if distributed else None)   # RCCL over xGMI: the only inter-GPU traffic
+
+    for _ in range(args.warmup):
+        step()
+    finish_job()                                                   # untimed rehearsal: loads torch's / RCCL's kernels, connects the ranks
+
+    # The timed region replays the captured hipGraph (the product's default dispatch). ROCm 7.2 stream capture
+    # drops hipEventRecord calls (devtools/graph_events.hip), so HIP events around a kernel need eager launches: with --full,
+    # the level-0 metric kernel is bracketed in a second pass over the same K steps right after the timed region
+    # (2 records per step), and all launches in a third pass (costs ~18 % of the step) for the "kernels" table.
+    # --kernel-events moves the level-0 events into the timed region itself (eager launches, ~4 % slower).
+    kernel_events = args.kernel_events
+    if proc is not None:
+        proc.profile_reset()
+        proc.profile_enable(["reduce_l0"] if kernel_events else False)
+
+    # One untimed rehearsal of the whole job (the same K steps + the tail) right before the timed one: the first K-step run
+    # after start-up is 3 - 5 % slower than every later one (7.86 ms against 7.52 - 7.59 for 20 steps, same process: clocks
+    # and caches settle over more than the W = 5 warm-up steps the driver asks for). MUSICA_BENCH_REHEARSALS=0 turns it off.
+    rehearsals = int(os.environ.get("MUSICA_BENCH_REHEARSALS", "1"))
+    for rep in range(rehearsals):
+        torch.cuda.synchronize()
+        tr = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        tq = time.perf_counter()
+        finish_job()
+        torch.cuda.synchronize()
+        if os.environ.get("MUSICA_BENCH_TRACE") == "1":
+            sys.stderr.write("rehearsal %d: %d steps enqueued %.3f ms, job done %.3f ms\n" % (rep, args.steps, (tq - tr) * 1e3, (time.perf_counter() - tr) * 1e3))
+    barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    t_enq = time.perf_counter()
+    gathered = finish_job()
+    t_fin = time.perf_counter()
+    torch.cuda.synchronize()
+    barrier()
+    t1 = time.perf_counter()
+    if os.environ.get("MUSICA_BENCH_TRACE") == "1":
+        sys.stderr.write("timed region: %d steps enqueued after %.3f ms, finish_job returned after %.3f ms, end %.3f ms\n"
+                         % (args.steps, (t_enq - t0) * 1e3, (t_fin - t0) * 1e3, (t1 - t0) * 1e3))
+
+    elapsed = t1 - t0
+    if distributed:
+        tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+    st = gathered.cpu().numpy()
+    got_ids = sorted(int(r[0]) for r in st)
+    if st.shape[0] != world * batch or got_ids != list(range(world * batch)):
+        raise SystemExit("stats gather incomplete: %d rows, ids %s (expected %d images from %d ranks)" % (st.shape[0], got_ids[:8], world * batch, world))
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, pipe.last(), st, mp.Stats)
+        sys.stderr.write("outputs of the last timed step: %s under %s\n" % (", ".join(k + ".npy" for k in names), args.dump_outputs))
+
+    full = measure_full(args, pipe, proc, px, n, levels, batch, flags, depth, world, rank, local_rank, kernel_events, elapsed) if args.full else None
+    result = None
+    if rank == 0:
+        mpix = world * batch * n * n * args.steps / 1e6
+        ms_per_step = elapsed / args.steps * 1e3
+        result = {
+            "metric": "megapixels/sec full MUSICA pipeline", "value": round(mpix / elapsed, 1), "unit": "MP/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "value_is": "whole-job MP/s of %d steps enqueued round-robin on %d one-stream contexts of each GPU (steps in flight), every context replaying its own HBM-resident copy "
+                        "of the rank's %d-image shard (inputs do not change between steps; H2D excluded); with --full, `one_context`, `single_image`, `reference_3072_L12`, "
+                        "`e2e_host_*` and `cli` are the same pipeline in the reference's one-frame-at-a-time call shapes" % (args.steps, depth, batch),
+            "config": {"workload": desc, "image_size": n, "levels": levels, "images_per_gpu_per_step": batch, "contexts_in_flight": depth, "untimed_rehearsals_of_the_job": rehearsals,
+                       "queue_calibration_ms": queue_calibration,
+                       "sdev_in_expand_launches": sdev_in_expand,
+                       "input": "seeded phantoms, %d-bit" % bits, "dispatch": "eager launches" if (kernel_events or os.environ.get("MUSICA_GRAPH", "1") == "0") else "hipGraph replay",
+                       "kernel_events_in_timed_region": kernel_events, "sharding": "image k -> rank k mod N, no data-path collective",
+                       "stats_gathered": int(st.shape[0]), "ranks_joined": world,
+                       "collective": ("%s all_gather_into_tensor of %d stats rows per rank" % ("RCCL (torch backend nccl)" if args.backend == "nccl" else "gloo", batch)) if distributed else "none (one rank)"},
+            "parity": "timed path = default (separable) order: bit-identical to the build's CPU oracle in that order; with MUSICA_FLAG_REFERENCE_ORDER the GPU runs the "
+                      "shaders' literal 25-tap order, bit-identical to the oracle's literal restatement on every BASELINE config and 3072/L12 (tests/test_gpu_reference_order.py). "
+                      "Default vs literal order, measured at full size on every config (profiles/r03_literal_order_*.json): stencil outputs within 6e-7 / 1e-6, every "
+                      "noise-histogram argmax equal, reconstruction within 4e-6 on all but <= 0.003 % of the texels (max 2.1e-2: blocks under cnr texels at the "
+                      "noise-reduction thresholds 3 / 9), <= 0.011 % of the 8-bit pixels differ (isolated 0 <-> 255 flips at getY's x > 1 -> 0 edge). "
+                      "Parity with the reference itself is unpinned (no vectors in the reference, GLSL not buildable here)",
+        }
+        if full is not None:
+            result.update(full)
+    if proc is not None and depth > 1:
         proc.cleanup()
     pipe.cleanup()
     if distributed:
@@ -653,3 +748,4 @@ def main():
 
 if __name__ == "__main__":
     main()
+

@@ -15,7 +15,7 @@ for a in sys.argv[3:]:   # NAME=path[,ENV=VAL,...]
     envs[name] = dict(kv.split("=", 1) for kv in parts[1:])
 res = {n: [] for n, _ in libs}
 one = {n: [] for n, _ in libs}
-code = ("import sys, os; sys.path.insert(0, %r); sys.argv = ['bench.py', '--workload', %r, '--cpu-seconds', '0', '--no-single-image', '--no-standalone', '--no-cli', '--no-pmc', '--no-kernel-events'];"
+code = ("import sys, os; sys.path.insert(0, %r); sys.argv = ['bench.py', '--full', '--workload', %r, '--cpu-seconds', '0', '--no-single-image', '--no-standalone', '--no-cli', '--no-pmc', '--no-kernel-events'];"
         "from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp; mp.LIB_PATH = os.path.join(%r, os.environ['AB_LIB']);"
         "import runpy; runpy.run_path(os.path.join(%r, 'bench.py'), run_name='__main__')") % (ROOT, wl, ROOT, ROOT)
 for r in range(rounds):

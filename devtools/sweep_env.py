@@ -8,7 +8,7 @@ for combo in itertools.product(*[v for _, v in vars_]):
     env = dict(os.environ)
     for (k, _), val in zip(vars_, combo):
         env[k] = val
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "2", "--cpu-seconds", "0"], env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--cpu-seconds", "0"], env=env, capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])
         ks = " ".join("%s=%.1f" % (k, d["kernels"][k]["mean_us"]) for k in kernels)

@@ -1,7 +1,11 @@
 """Helpers shared by the golden-fixture tests: the stage dictionary of one executed back end and its digests."""
 import hashlib
+import json
+import os
 
 import numpy as np
+
+REF_BMP_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_bmp_digests.json")
 
 
 def stages(get_image, x, levels, clahe, kinds):
@@ -42,3 +46,21 @@ def check_digest(got, want):
     assert set(want) == set(got)
     bad = [k for k in want if digest(got[k]) != want[k]]
     assert not bad, "stages differing from the committed digests: %s" % bad
+
+
+def ref_bmp_key(data):
+    """Key of one writer input in tests/golden/ref_bmp_digests.json: components, width x height and a digest of the pixels."""
+    d = np.ascontiguousarray(data, dtype=np.uint8)
+    return "%s_%dx%d_%s" % ("rgba" if d.ndim == 3 else "gray", d.shape[1], d.shape[0], hashlib.sha256(d.tobytes()).hexdigest()[:16])
+
+
+def ref_bmp_digest(data):
+    """SHA-256 of the file the reference's stbi_write_bmp writes for `data`, as recorded by tests/golden/make_ref_bmp_digests.py."""
+    with open(REF_BMP_DIGESTS) as f:
+        want = json.load(f)
+    return want[ref_bmp_key(data)]
+
+
+def file_digest(path):
+    with open(path, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()

@@ -185,7 +185,7 @@ def test_bench_launches_its_own_ranks_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MUSICA_BENCH_ONE_DEVICE="1")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--backend", "gloo",
-           "--workload", "C2", "--batch", "2", "--no-kernel-events", "--no-standalone", "--cpu-seconds", "0"]
+           "--workload", "C2", "--batch", "2", "--full", "--no-kernel-events", "--no-standalone", "--cpu-seconds", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     _check_bench_line(r.stdout, 2, 4)
@@ -201,7 +201,7 @@ def test_bench_under_an_external_launcher_and_rank_count_mismatch():
     env = dict(os.environ, MUSICA_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
             "--master-port", str(_free_port()), os.path.join(root, "bench.py")]
-    tail = ["--steps", "4", "--warmup", "1", "--backend", "gloo", "--workload", "C2", "--no-kernel-events", "--no-standalone", "--cpu-seconds", "0"]
+    tail = ["--steps", "4", "--warmup", "1", "--backend", "gloo", "--workload", "C2", "--full", "--no-kernel-events", "--no-standalone", "--cpu-seconds", "0"]
     r = subprocess.run(base + ["--gpus", "2"] + tail, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     _check_bench_line(r.stdout, 2, 4)
