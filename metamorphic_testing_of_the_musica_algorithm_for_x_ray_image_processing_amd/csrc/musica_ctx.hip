@@ -58,84 +58,92 @@ struct ProfSpan {
 
 // Captured graphs kept per context, one per distinct input pointer (include/musica.h, musica_execute_device).
 constexpr int kGraphSlots = 4;
+constexpr int kLaneStreams = 1;   // streams of the image lanes (musica_ctx::lanes). One: a one-image chain (0.14 - 0.19 ms) is as long as an image's copy,
+                                  // so chains on several streams would barely overlap, and which hardware queue a further stream lands on (4 queues,
+                                  // round-robin over every stream of the process) decided whether three lanes were faster or slower than none
 
-struct musica_ctx {
+// Every device buffer that holds one slice per image: B slices, image k's at k x its elements per image. for_each_buffer names each
+// member once with that count; allocation, the image lanes and the getters all go through it.
+struct DeviceBuffers {
+    uint16_t* d_input = nullptr;
+    uint32_t* d_minmax = nullptr;
+    uint32_t* d_mm_slots = nullptr;    // [B][kMinMaxSlots]: per-block {min | max << 16} of k_minmax_u16
+    uint32_t* d_mm_ticket = nullptr;   // [B]: its arrival counters (self-resetting)
+    uint32_t* d_gr_ticket = nullptr;   // [B][kGradTicketStride]: the tickets of the one-launch recount + tone curve
+    float* d_norm = nullptr;
+    float* d_down[MUSICA_MAX_LEVELS] = {};
+    float* d_band[MUSICA_MAX_LEVELS] = {};
+    float* d_recon[MUSICA_MAX_LEVELS] = {};
+    float* d_sdev[4] = {};
+    uint32_t* d_noise_hist = nullptr;
+    musica_hist_max_point* d_noise_max = nullptr;
+    DevCurve* d_curves = nullptr;
+    DevCurveLut* d_luts = nullptr;
+    float* d_cnr = nullptr;
+    uint32_t* d_grad_hist = nullptr;
+    uint32_t* d_grad_hist_b = nullptr;   // the literal recount of images whose reconstruction holds an exact zero (fused gradation histogram)
+    uint32_t* d_gzero = nullptr;         // [B]: that condition
+    int* d_thr090 = nullptr;             // [B]: raw-pixel form of `normalized <= 0.9`
+    double* d_stats_partial = nullptr;   // [B][kStatsMaxBlocks]: partial sums of the cnr image (k_stats_partial -> k_stats)
+    uint16_t* d_le090 = nullptr;         // [B][S1][S0 / 8] or null: its bit image, written by the level-0 reduce + band launch for the level-0 expand launch
+    musica_hist_max_point* d_grad_max = nullptr;
+    DevCurve* d_gcurve = nullptr;
+    float* d_graded = nullptr;
+    float* d_scratch = nullptr;
+    musica_stats* d_stats = nullptr;
+    uint32_t* d_clahe_hist = nullptr;
+    musica_point* d_clahe_pts = nullptr;
+    float* d_clahe_graded = nullptr;
+};
+
+struct musica_ctx : DeviceBuffers {
     musica_params p;
     musica_tunables tun;     // the constants of the host parameter formulas (musica_create_ex; default: the reference's)
     int N, L, B;
     bool generic;
     int ref_order;           // MUSICA_FLAG_REFERENCE_ORDER: generic kernels in the shaders' literal 25-tap accumulation order
-    bool tuning;  // inside autotune(): launches are tagged so profilers keep them apart
+    bool tuning = false;     // inside autotune(): launches are tagged so profilers keep them apart
     LevelDesc lv[MUSICA_MAX_LEVELS + 1];
     int min_chain_exact;
     int hist_cov;  // (N / 512) * 512
-    hipStream_t stream;
+    hipStream_t stream = nullptr;
     hipStream_t cur;         // stream the run_*_level helpers launch on (stream or side)
-    hipStream_t side;        // coarse-level chain runs here, concurrently with the level-0 kernels on `stream`
-    hipEvent_t ev_fork, ev_join;
+    hipStream_t side = nullptr;   // coarse-level chain runs here, concurrently with the level-0 kernels on `stream`
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool fuse_u16;           // level-0 kernels read the raw uint16 pixels; the normalized image is produced on demand only
     bool grad_one_launch;    // recount + tone curve in one launch behind the fused expand launch (MUSICA_GRAD_ONE_LAUNCH=0: two)
-    uint32_t* d_gr_ticket;   // its tickets: [B][kGradTicketStride]
     bool tiny_tail;          // levels of side <= kTailSide in one launch (MUSICA_TINY_TAIL=0: one launch per level and stage)
     bool clahe_one_apply;    // ... and whose two apply passes are one launch (MUSICA_CLAHE_ONE_APPLY=0: k_grad_apply and k_clahe_apply4)
     bool clahe_in_expand;    // ... and whose histogram the level-0 expand launch counts (MUSICA_CLAHE_IN_EXPAND=0: k_clahe_hist)
     bool clahe_raw;          // CLAHE context whose relevant image is computed from the raw pixels (no stored normalized image)
-    bool norm_valid;         // d_norm holds the normalized image of the current input
+    bool norm_valid = false; // d_norm holds the normalized image of the current input
     // hipGraph replay of the two-stream dispatch (captured once per input pointer; MUSICA_FLAG_NO_GRAPH /
     // MUSICA_GRAPH=0 / per-kernel profiling fall back to eager launches)
     bool use_graph;
-    hipGraphExec_t graph_exec[kGraphSlots];      // one captured graph per input pointer, the kGraphSlots most recently used (the streaming
-    const uint16_t* graph_input[kGraphSlots];    // path alternates between two device input buffers; callers may rotate a few of their own)
-    uint64_t graph_used[kGraphSlots];            // launch counter at the slot's last use (least recently used slot is recaptured)
-    uint64_t graph_clock;
+    hipGraphExec_t graph_exec[kGraphSlots] = {};      // one captured graph per input pointer, the kGraphSlots most recently used (the streaming
+    const uint16_t* graph_input[kGraphSlots] = {};    // path alternates between two device input buffers; callers may rotate a few of their own)
+    uint64_t graph_used[kGraphSlots] = {};            // launch counter at the slot's last use (least recently used slot is recaptured)
+    uint64_t graph_clock = 0;
     int dag;                 // 0: one in-order stream (enqueue_linear); 2: two streams (enqueue_fork: the analysis beside the reduce tail)
-    // device state
-    uint16_t* d_input;
-    uint16_t* d_input2;      // second input buffer of the streaming path (musica_execute_stream), allocated on first use
-    hipStream_t copy_stream; // its H2D copies run here, under the previous batch's kernels
-    hipEvent_t ev_copied[2], ev_consumed[2];
-    const uint16_t* cur_input;
-    uint32_t* d_minmax;
-    uint32_t* d_mm_slots;      // [B][kMinMaxSlots]: per-block {min | max << 16} of k_minmax_u16
-    uint32_t* d_mm_ticket;     // [B]: its arrival counters (self-resetting)
-    float* d_norm;
-    float* d_down[MUSICA_MAX_LEVELS];
-    float* d_band[MUSICA_MAX_LEVELS];
-    float* d_recon[MUSICA_MAX_LEVELS];
-    float* d_sdev[4];
-    uint32_t* d_noise_hist;
-    musica_hist_max_point* d_noise_max;
-    DevCurve* d_curves;
-    DevCurveLut* d_luts;
-    musica_contrast_params* d_cparams;
-    float* d_cnr;
-    uint32_t* d_grad_hist;
-    uint32_t* d_grad_hist_b;   // the literal recount of images whose reconstruction holds an exact zero (fused gradation histogram)
-    uint32_t* d_gzero;         // [B]: that condition
-    int* d_thr090;             // [B]: raw-pixel form of `normalized <= 0.9`
-    uint32_t* d_plot;          // one MUSICA_HIST_RENDER_WIDTH x MUSICA_HIST_RENDER_HEIGHT rgba8 image (the RENDER_HISTS plots, on demand)
-    double* d_stats_partial;   // [B][kStatsMaxBlocks]: partial sums of the cnr image (k_stats_partial -> k_stats)
-    uint16_t* d_le090;         // [B][S1][S0 / 8] or null: its bit image, written by the level-0 reduce + band launch for the level-0 expand launch
+    // device state shared by the whole context (the per-image buffers are the DeviceBuffers base)
+    uint16_t* d_input2 = nullptr;      // second input buffer of the streaming path (musica_execute_stream), allocated on first use
+    hipStream_t copy_stream = nullptr; // its H2D copies run here, under the previous batch's kernels
+    hipEvent_t ev_copied[2] = {}, ev_consumed[2] = {};
+    const uint16_t* cur_input = nullptr;
+    musica_contrast_params* d_cparams = nullptr;
+    uint32_t* d_plot = nullptr;        // one MUSICA_HIST_RENDER_WIDTH x MUSICA_HIST_RENDER_HEIGHT rgba8 image (the RENDER_HISTS plots, on demand)
     bool fuse_gh;              // the level-0 expand launch accumulates the gradation histogram
     // The expand launches of levels 0 .. 2 compute the 5 x 5 RMS of their band image themselves (k_expand_fast<.., SD>) and the sdev +
     // noise-histogram launches of those levels store nothing: 8 of a step's 48 bytes per input pixel. The whole-step scripts run that way
     // (sd_active); the stage entry points, getters and dumps want the stored images: ensure_sdev() writes them on demand.
-    bool sd_fused, sd_active, sdev_stored;
+    bool sd_fused, sd_active = false, sdev_stored = true;
     bool pair_rb_sdev;         // the one-stream script pairs the sdev pass of level i with reduce + band of level i + 1 in one launch (k_rb_sdev); MUSICA_PAIR_RB_SDEV
     bool sdev_one_launch;      // the sdev + noise-histogram passes of levels 0 .. 3 as ONE launch (k_sdev_hist_levels); MUSICA_SDEV_ONE_LAUNCH=0: one launch per marching level + one for the runs
     int rows_rb[MUSICA_MAX_LEVELS];   // its coarse rows per wavefront
-    musica_hist_max_point* d_grad_max;
-    DevCurve* d_gcurve;
-    float* d_graded;
-    float* d_scratch;
-    musica_stats* d_stats;
-    uint32_t* d_clahe_hist;
-    musica_point* d_clahe_pts;
-    float* d_clahe_graded;
-    uint8_t* d_out8;           // saveOutImage's cropped 8-bit pixels of one image (device) and their pinned host copy, allocated on first use
-    uint8_t* h_out8;
-    uint8_t* h_bmp;            // saveOutImage's whole file image in page-locked memory: 2 bytes of padding, the 54-byte header, then the pixel array the
-                               // device writes itself (k_out_bmp24: the array starts on a 4-byte boundary); allocated on first use
+    uint8_t* d_out8 = nullptr;   // saveOutImage's cropped 8-bit pixels of one image (device) and their pinned host copy, allocated on first use
+    uint8_t* h_out8 = nullptr;
+    uint8_t* h_bmp = nullptr;    // saveOutImage's whole file image in page-locked memory: 2 bytes of padding, the 54-byte header, then the pixel array the
+                                 // device writes itself (k_out_bmp24: the array starts on a 4-byte boundary); allocated on first use
     // host parameters (src/vk_processing.cpp:259-297, 321-325)
     musica_contrast_params h_cparams[MUSICA_MAX_LEVELS];
     musica_nr_params h_nr[3];
@@ -144,24 +152,75 @@ struct musica_ctx {
     // tunables
     int expand_rows, sdev_rows, grad_groups, min_waves;
     // profiling
-    uint32_t profiling;  // bit i set: bracket kernel family i with HIP events
+    uint32_t profiling = 0;  // bit i set: bracket kernel family i with HIP events
     std::vector<ProfSpan> spans;
-    size_t spans_used;
-    double prof_total_us[MUSICA_KERNEL_COUNT];
-    uint64_t prof_count[MUSICA_KERNEL_COUNT];
-    bool needs_reset;        // a step failed (launch / sync error): the self-resetting tickets of k_minmax_u16 and k_grad_recount_curve may hold a
-                             // partial count, which would leave every later launch without a last-ticket block — zeroed before the next step
+    size_t spans_used = 0;
+    double prof_total_us[MUSICA_KERNEL_COUNT] = {};
+    uint64_t prof_count[MUSICA_KERNEL_COUNT] = {};
+    bool needs_reset = false;  // a step failed (launch / sync error): the self-resetting tickets of k_minmax_u16 and k_grad_recount_curve may hold a
+                               // partial count, which would leave every later launch without a last-ticket block — zeroed before the next step
     std::vector<void*> allocations;
     // Image lanes (musica_execute of a context with a batch, from page-locked host memory): shallow copies of the context for one or
     // two images each — device pointers moved to those images — whose one-stream script is enqueued behind the host-to-device copy of
     // just those images. Every stage of the path is per image, so nothing changes in the results; the first images' kernels run under
     // the remaining copies. Created on first use.
     std::vector<musica_ctx*> lanes;
-    hipStream_t lane_stream[3];
-    hipStream_t lane_copy[2];        // the images' copies ([1]: unused; two alternating copy streams made every copy twice as long)
-    hipEvent_t lane_done[3], lane_start;
+    hipStream_t lane_stream[kLaneStreams] = {};
+    hipStream_t lane_copy[2] = {};   // the images' copies ([1]: unused; two alternating copy streams made every copy twice as long)
+    hipEvent_t lane_done[kLaneStreams] = {}, lane_start = nullptr;
     std::vector<hipEvent_t> img_copied;   // one per image
 };
+
+// Calls f(member, elements per image) for every member of DeviceBuffers, in allocation order; 0 elements: a buffer this context does
+// not have. Returns the number of pointers visited (create_impl checks it against the size of DeviceBuffers).
+template <typename D, typename F>
+static size_t for_each_buffer(D& d, const musica_ctx& c, F f) {
+    size_t visited = 0;
+    auto v = [&](auto& ptr, size_t count) { f(ptr, count); visited++; };
+    const bool clahe = (c.p.flags & MUSICA_FLAG_CLAHE) != 0;
+    const size_t plane0 = c.lv[0].plane, tiles = (size_t)MUSICA_CLAHE_TILES * MUSICA_CLAHE_TILES * MUSICA_CLAHE_BINS;
+    v(d.d_input, (size_t)c.N * c.N);
+    v(d.d_minmax, kMinMaxStride);
+    v(d.d_mm_slots, kMinMaxSlots);
+    v(d.d_mm_ticket, kMinMaxStride);   // one 128-byte line per image
+    v(d.d_gr_ticket, kGradTicketStride);
+    v(d.d_norm, plane0);
+    for (int i = 0; i < MUSICA_MAX_LEVELS; i++) {
+        v(d.d_down[i], i < c.L ? c.lv[i + 1].plane : 0);
+        v(d.d_band[i], i < c.L ? c.lv[i].plane : 0);
+        v(d.d_recon[i], i < c.L ? c.lv[i].plane : 0);
+        if (i <= MUSICA_CNR_LEVEL) v(d.d_sdev[i], i < c.L ? c.lv[i].plane : 0);
+    }
+    v(d.d_noise_hist, 4 * MUSICA_NOISE_BINS);
+    v(d.d_noise_max, c.L);
+    v(d.d_curves, c.L);
+    v(d.d_luts, MUSICA_COARSER_LEVELS_START);
+    v(d.d_cnr, c.lv[MUSICA_CNR_LEVEL].plane);
+    v(d.d_grad_hist, MUSICA_GRAD_BINS);
+    v(d.d_grad_hist_b, MUSICA_GRAD_BINS);
+    v(d.d_gzero, 1);
+    v(d.d_thr090, 1);
+    v(d.d_stats_partial, kStatsMaxBlocks);
+    v(d.d_le090, c.fuse_gh ? (size_t)c.lv[1].S * (c.lv[0].S / 8) : 0);
+    v(d.d_grad_max, 1);
+    v(d.d_gcurve, 1);
+    v(d.d_graded, plane0);
+    v(d.d_scratch, plane0);
+    v(d.d_stats, 1);
+    v(d.d_clahe_hist, clahe ? tiles : 0);
+    v(d.d_clahe_pts, clahe ? tiles : 0);
+    v(d.d_clahe_graded, clahe ? plane0 : 0);
+    return visited;
+}
+// Elements per image of `buf`, a member of c's DeviceBuffers, and image idx's slice of it.
+template <typename T>
+static size_t per_image(const musica_ctx* c, T* const& buf) {
+    size_t count = 0;
+    for_each_buffer(*c, *c, [&](auto& ptr, size_t n) { if ((const void*)&ptr == (const void*)&buf) count = n; });
+    return count;
+}
+template <typename T>
+static T* image_slice(const musica_ctx* c, T* const& buf, uint32_t idx) { return buf + (size_t)idx * per_image(c, buf); }
 
 static int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -265,6 +324,15 @@ static int sdev_rows_default(const musica_ctx* c, int i, int batch) {
     if (mode == 1 || (mode < 0 && marches < 1024)) return 0;
     return pick_rows(c->sdev_rows, 16, c->lv[i].S, c->lv[i].S, batch);
 }
+// Launch geometry of a step of `batch` images before autotune: rows per wavefront of the expand, sdev and reduce + band launches
+// (results never depend on it).
+static void default_rows(musica_ctx* c, int batch) {
+    for (int i = 0; i < c->L; i++) {
+        c->rows_expand[i] = pick_rows(c->expand_rows, 1, c->lv[i].S, c->lv[i + 1].S, batch);
+        if (i <= MUSICA_CNR_LEVEL) c->rows_sdev[i] = sdev_rows_default(c, i, batch);
+        c->rows_rb[i] = pick_rows(env_int("MUSICA_RB_ROWS", 16), 1, c->lv[i].S, c->lv[i + 1].S, batch);
+    }
+}
 
 extern "C" {
 
@@ -281,13 +349,13 @@ void musica_destroy(musica_ctx* c) {
     if (!c) return;
     hipSetDevice(c->p.device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (int k = 0; k < 3; k++) if (c->lane_stream[k]) hipStreamSynchronize(c->lane_stream[k]);
+    for (int k = 0; k < kLaneStreams; k++) if (c->lane_stream[k]) hipStreamSynchronize(c->lane_stream[k]);
     for (musica_ctx* v : c->lanes) {
         for (auto& sp : v->spans) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
         for (int k = 0; k < kGraphSlots; k++) if (v->graph_exec[k]) hipGraphExecDestroy(v->graph_exec[k]);
         delete v;
     }
-    for (int k = 0; k < 3; k++) {
+    for (int k = 0; k < kLaneStreams; k++) {
         if (c->lane_stream[k]) { hipStreamSynchronize(c->lane_stream[k]); hipStreamDestroy(c->lane_stream[k]); }
         if (c->lane_done[k]) hipEventDestroy(c->lane_done[k]);
     }
@@ -337,6 +405,13 @@ musica_ctx* musica_create_ex(const musica_params* params, const musica_tunables*
 
 static musica_ctx* create_impl(const musica_params* params, const musica_tunables* tunables) {
     if (!params) { fail("musica_create: params is NULL"); return nullptr; }
+    {   // a per-image buffer the visitor does not name would be neither allocated nor moved to a lane's images
+        musica_ctx probe{};
+        if (for_each_buffer(probe, probe, [](auto&, size_t) {}) != sizeof(DeviceBuffers) / sizeof(void*)) {
+            fail("musica_create: for_each_buffer does not visit every member of DeviceBuffers");
+            return nullptr;
+        }
+    }
     musica_tunables tun;
     musica_tunables_default(&tun);
     if (tunables) {
@@ -374,14 +449,6 @@ static musica_ctx* create_impl(const musica_params* params, const musica_tunable
     c->p.levels = L; c->p.batch = (uint32_t)c->B;
     c->ref_order = (params->flags & MUSICA_FLAG_REFERENCE_ORDER) ? 1 : 0;
     c->generic = (params->flags & MUSICA_FLAG_GENERIC_KERNELS) != 0 || c->ref_order;   // the literal order lives in the one-thread-per-texel kernels
-    c->tuning = false;
-    c->stream = nullptr; c->side = nullptr; c->ev_fork = nullptr; c->ev_join = nullptr; c->profiling = 0; c->spans_used = 0; c->cur_input = nullptr;
-    c->d_out8 = nullptr; c->h_out8 = nullptr; c->h_bmp = nullptr; c->needs_reset = false;
-    for (int k = 0; k < 3; k++) { c->lane_stream[k] = nullptr; c->lane_done[k] = nullptr; }
-    c->lane_start = nullptr; c->lane_copy[0] = c->lane_copy[1] = nullptr;
-    c->d_input2 = nullptr; c->copy_stream = nullptr; c->ev_copied[0] = c->ev_copied[1] = c->ev_consumed[0] = c->ev_consumed[1] = nullptr;
-    memset(c->prof_total_us, 0, sizeof(c->prof_total_us));
-    memset(c->prof_count, 0, sizeof(c->prof_count));
     int s = (int)N;
     for (int i = 0; i <= c->L; i++) {
         c->lv[i].S = s;
@@ -428,10 +495,7 @@ static musica_ctx* create_impl(const musica_params* params, const musica_tunable
         ok = ok && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
     }
-    for (int k = 0; k < kGraphSlots; k++) { c->graph_exec[k] = nullptr; c->graph_input[k] = nullptr; c->graph_used[k] = 0; }
-    c->graph_clock = 0;
     c->fuse_u16 = (N % 8) == 0 && !c->generic;
-    c->norm_valid = false;
     // fused gradation histogram: streaming level-0 kernels on raw pixels, cnr scale 8 (every N >= 57 with N % 8 == 0), no CLAHE
     // block (it wants the stored relevant image anyway)
     // (a CLAHE context fuses too since its relevant image comes from the raw pixels, k_relevant4<true>; MUSICA_CLAHE_FUSE=0: as before)
@@ -451,7 +515,6 @@ static musica_ctx* create_impl(const musica_params* params, const musica_tunable
         const bool pays = texels >= ((params->flags & MUSICA_FLAG_LINEAR) ? (size_t)2 : (size_t)8) * 2048 * 2048;
         c->sd_fused = env_int("MUSICA_SDEV_IN_EXPAND", pays ? 1 : 0) != 0 && !c->generic;
     }
-    c->sd_active = false; c->sdev_stored = true;
     // every level's sdev pass in one launch for batches and for the contexts of a pipeline (same-box A/B: a lone 8 x 2048^2 context -3.5 %, 8192^2 -1.1 %;
     // three steps in flight 8 x 2048^2 -1 %, 8192^2 -1.5 %, 3072^2 L12 -3.5 %); a lone context with one image keeps one launch per marching level:
     // beside the reduce tail of its two-stream script the merged launch slows the tail's small launches (3072^2 L12 +4 %, 2048^2 +0.7 %)
@@ -463,44 +526,9 @@ static musica_ctx* create_impl(const musica_params* params, const musica_tunable
     c->fuse_gh = env_int("MUSICA_FUSE_GH", 1) != 0 && c->fuse_u16 && (!(params->flags & MUSICA_FLAG_CLAHE) || c->clahe_raw) &&
                  cnr_scale(c->lv[0].S, c->lv[MUSICA_CNR_LEVEL].S) == 8;
     tick.lap("streams + events");
-    ok = ok && dalloc(c, &c->d_input, B * N * N);
-    ok = ok && dalloc(c, &c->d_minmax, B * kMinMaxStride);
-    ok = ok && dalloc(c, &c->d_mm_slots, B * kMinMaxSlots);
-    ok = ok && dalloc(c, &c->d_mm_ticket, B * kMinMaxStride);   // one 128-byte line per image
-    ok = ok && dalloc(c, &c->d_gr_ticket, B * kGradTicketStride);
-    ok = ok && dalloc(c, &c->d_norm, B * c->lv[0].plane);
-    for (int i = 0; i < c->L && ok; i++) {
-        ok = ok && dalloc(c, &c->d_down[i], B * c->lv[i + 1].plane);
-        ok = ok && dalloc(c, &c->d_band[i], B * c->lv[i].plane);
-        ok = ok && dalloc(c, &c->d_recon[i], B * c->lv[i].plane);
-        if (i <= MUSICA_CNR_LEVEL) ok = ok && dalloc(c, &c->d_sdev[i], B * c->lv[i].plane);
-    }
-    ok = ok && dalloc(c, &c->d_noise_hist, B * 4 * MUSICA_NOISE_BINS);
-    ok = ok && dalloc(c, &c->d_noise_max, B * L);
-    ok = ok && dalloc(c, &c->d_curves, B * L);
-    ok = ok && dalloc(c, &c->d_luts, B * MUSICA_COARSER_LEVELS_START);
+    for_each_buffer(*c, *c, [&](auto& ptr, size_t count) { if (count) ok = ok && dalloc(c, &ptr, B * count); });
     ok = ok && dalloc(c, &c->d_cparams, (size_t)L);
-    ok = ok && dalloc(c, &c->d_cnr, B * c->lv[MUSICA_CNR_LEVEL].plane);
-    ok = ok && dalloc(c, &c->d_grad_hist, B * MUSICA_GRAD_BINS);
-    ok = ok && dalloc(c, &c->d_grad_hist_b, B * MUSICA_GRAD_BINS);
-    ok = ok && dalloc(c, &c->d_gzero, B);
-    ok = ok && dalloc(c, &c->d_thr090, B);
-    ok = ok && dalloc(c, &c->d_stats_partial, B * kStatsMaxBlocks);
     ok = ok && dalloc(c, &c->d_plot, (size_t)MUSICA_HIST_RENDER_WIDTH * MUSICA_HIST_RENDER_HEIGHT);
-    c->d_le090 = nullptr;
-    if (c->fuse_gh) ok = ok && dalloc(c, &c->d_le090, B * (size_t)c->lv[1].S * (c->lv[0].S / 8));
-    ok = ok && dalloc(c, &c->d_grad_max, B);
-    ok = ok && dalloc(c, &c->d_gcurve, B);
-    ok = ok && dalloc(c, &c->d_graded, B * c->lv[0].plane);
-    ok = ok && dalloc(c, &c->d_scratch, B * c->lv[0].plane);
-    ok = ok && dalloc(c, &c->d_stats, B);
-    c->d_clahe_hist = nullptr; c->d_clahe_pts = nullptr; c->d_clahe_graded = nullptr;
-    if (ok && (params->flags & MUSICA_FLAG_CLAHE)) {
-        const size_t tb = MUSICA_CLAHE_TILES * MUSICA_CLAHE_TILES * MUSICA_CLAHE_BINS;
-        ok = ok && dalloc(c, &c->d_clahe_hist, B * tb);
-        ok = ok && dalloc(c, &c->d_clahe_pts, B * tb);
-        ok = ok && dalloc(c, &c->d_clahe_graded, B * c->lv[0].plane);
-    }
     tick.lap("device buffers");
     ok = ok && hipMemcpy(c->d_cparams, c->h_cparams, sizeof(musica_contrast_params) * L, hipMemcpyHostToDevice) == hipSuccess;
     tick.lap("parameter upload");
@@ -511,11 +539,7 @@ static musica_ctx* create_impl(const musica_params* params, const musica_tunable
     }
     c->cur_input = c->d_input;
     c->cur = c->stream;
-    for (int i = 0; i < c->L; i++) {
-        c->rows_expand[i] = pick_rows(c->expand_rows, 1, c->lv[i].S, c->lv[i + 1].S, c->B);
-        if (i <= MUSICA_CNR_LEVEL) c->rows_sdev[i] = sdev_rows_default(c, i, c->B);
-        c->rows_rb[i] = pick_rows(env_int("MUSICA_RB_ROWS", 16), 1, c->lv[i].S, c->lv[i + 1].S, c->B);
-    }
+    default_rows(c, c->B);
     const bool tune = !(params->flags & MUSICA_FLAG_NO_AUTOTUNE) && env_int("MUSICA_AUTOTUNE", 1) && !c->generic;
     if (tune) autotune(c);
     return c;
@@ -946,8 +970,8 @@ static void reset_tickets_if_needed(musica_ctx* c) {
     if (!c->needs_reset) return;
     hipStreamSynchronize(c->stream);
     (void)hipGetLastError();
-    hipMemsetAsync(c->d_mm_ticket, 0, (size_t)c->B * kMinMaxStride * sizeof(uint32_t), c->stream);
-    hipMemsetAsync(c->d_gr_ticket, 0, (size_t)c->B * kGradTicketStride * sizeof(uint32_t), c->stream);
+    hipMemsetAsync(c->d_mm_ticket, 0, c->B * per_image(c, c->d_mm_ticket) * sizeof(uint32_t), c->stream);
+    hipMemsetAsync(c->d_gr_ticket, 0, c->B * per_image(c, c->d_gr_ticket) * sizeof(uint32_t), c->stream);
     c->needs_reset = false;
 }
 static int enqueue_all_impl(musica_ctx* c);
@@ -1080,9 +1104,6 @@ static int download_small(musica_ctx* c, const T* d_src, T* dst, size_t count) {
 extern "C" {
 
 // ---- image lanes (see musica_ctx::lanes) ----------------------------------------------------------------------------------
-constexpr int kLaneStreams = 1;   // one: a one-image chain (0.14 - 0.19 ms) is as long as an image's copy, so chains on several streams would barely
-                                  // overlap, and which hardware queue a further stream lands on (4 queues, round-robin over every stream of the
-                                  // process) decided whether three lanes were faster or slower than none
 // Shallow copy of the context restricted to image i0: same buffers, every per-image pointer moved to that image, batch 1, one stream,
 // its script replayed as a graph of its own.
 static musica_ctx* make_lane(const musica_ctx* c, int i0, int nb) {
@@ -1100,47 +1121,10 @@ static musica_ctx* make_lane(const musica_ctx* c, int i0, int nb) {
     v->profiling = 0;
     v->B = nb;
     v->p.batch = (uint32_t)nb;
-    const size_t o = (size_t)i0, NN = (size_t)c->N * c->N;
-    v->d_input += o * NN;
+    const size_t o = (size_t)i0;
+    for_each_buffer(*v, *c, [o](auto& ptr, size_t count) { ptr += o * count; });
     v->cur_input = v->d_input;
-    v->d_minmax += o * kMinMaxStride;
-    v->d_mm_slots += o * kMinMaxSlots;
-    v->d_mm_ticket += o * kMinMaxStride;
-    v->d_gr_ticket += o * kGradTicketStride;
-    v->d_norm += o * c->lv[0].plane;
-    for (int i = 0; i < c->L; i++) {
-        v->d_down[i] += o * c->lv[i + 1].plane;
-        v->d_band[i] += o * c->lv[i].plane;
-        v->d_recon[i] += o * c->lv[i].plane;
-        if (i <= MUSICA_CNR_LEVEL) v->d_sdev[i] += o * c->lv[i].plane;
-    }
-    v->d_noise_hist += o * 4 * MUSICA_NOISE_BINS;
-    v->d_noise_max += o * c->L;
-    v->d_curves += o * c->L;
-    v->d_luts += o * MUSICA_COARSER_LEVELS_START;
-    v->d_cnr += o * c->lv[MUSICA_CNR_LEVEL].plane;
-    v->d_grad_hist += o * MUSICA_GRAD_BINS;
-    v->d_grad_hist_b += o * MUSICA_GRAD_BINS;
-    v->d_gzero += o;
-    v->d_thr090 += o;
-    v->d_stats_partial += o * kStatsMaxBlocks;
-    if (v->d_le090) v->d_le090 += o * (size_t)c->lv[1].S * (c->lv[0].S / 8);
-    v->d_grad_max += o;
-    v->d_gcurve += o;
-    v->d_graded += o * c->lv[0].plane;
-    v->d_scratch += o * c->lv[0].plane;
-    v->d_stats += o;
-    if (c->d_clahe_hist) {
-        const size_t tb = (size_t)MUSICA_CLAHE_TILES * MUSICA_CLAHE_TILES * MUSICA_CLAHE_BINS;
-        v->d_clahe_hist += o * tb;
-        v->d_clahe_pts += o * tb;
-        v->d_clahe_graded += o * c->lv[0].plane;
-    }
-    for (int i = 0; i < c->L; i++) {   // launch geometry of a one-image step (results never depend on it)
-        v->rows_expand[i] = pick_rows(c->expand_rows, 1, c->lv[i].S, c->lv[i + 1].S, nb);
-        if (i <= MUSICA_CNR_LEVEL) v->rows_sdev[i] = sdev_rows_default(c, i, nb);
-        v->rows_rb[i] = pick_rows(16, 1, c->lv[i].S, c->lv[i + 1].S, nb);
-    }
+    default_rows(v, nb);   // launch geometry of a step of nb images
     return v;
 }
 // Only for page-locked host memory (musica_host_alloc, hipHostMalloc, hipHostRegister): a copy from pageable memory is staged by the
@@ -1200,19 +1184,22 @@ static int enqueue_images_from_host(musica_ctx* c, uint16_t* d_dst, const uint16
         first += nb;
     }
     first = 0;
-    for (size_t l = 0; l < c->lanes.size(); l++) {
+    int ok = 1;
+    for (size_t l = 0; l < c->lanes.size() && ok; l++) {
         musica_ctx* v = c->lanes[l];
         const int k = first;
         first += v->B;
         hipStreamWaitEvent(v->stream, c->img_copied[l], 0);
         v->cur_input = d_dst + (size_t)k * NN;
         v->cur = v->stream;
-        if (!enqueue_all_impl(v)) { c->needs_reset = true; return 0; }
+        ok = enqueue_all_impl(v);
     }
+    // also after a failed lane: what the lanes before it enqueued still writes the planes, and musica_sync waits on c->stream only
     for (int k = 0; k < kLaneStreams; k++) {
         hipEventRecord(c->lane_done[k], c->lane_stream[k]);
         hipStreamWaitEvent(c->stream, c->lane_done[k], 0);
     }
+    if (!ok) { c->needs_reset = true; return 0; }
     c->cur_input = d_dst;
     c->norm_valid = c->lanes[0]->norm_valid;
     if (c->sd_fused) c->sdev_stored = false;
@@ -1380,25 +1367,36 @@ uint32_t musica_image_side(const musica_ctx* c, musica_image_kind kind, uint32_t
     }
 }
 
+// The plane of image idx that a step stores for (kind, level), and its level; null for the kinds computed on demand and for a buffer
+// this context does not have. The caller has checked (kind, level) with musica_image_side.
+static float* stored_plane(musica_ctx* c, uint32_t idx, musica_image_kind kind, uint32_t level, const LevelDesc** desc) {
+    float* const* buf = nullptr;
+    switch (kind) {
+        case MUSICA_IMG_NORMALIZED: buf = &c->d_norm; level = 0; break;
+        case MUSICA_IMG_GRADED: buf = &c->d_graded; level = 0; break;
+        case MUSICA_IMG_CLAHE_GRADED: buf = &c->d_clahe_graded; level = 0; break;
+        case MUSICA_IMG_CNR: buf = &c->d_cnr; level = MUSICA_CNR_LEVEL; break;
+        case MUSICA_IMG_DOWNSAMPLED: buf = &c->d_down[level]; level++; break;
+        case MUSICA_IMG_BANDPASS: buf = &c->d_band[level]; break;
+        case MUSICA_IMG_EXPAND: buf = &c->d_recon[level]; break;
+        case MUSICA_IMG_SDEV: if (level <= MUSICA_CNR_LEVEL) buf = &c->d_sdev[level]; break;
+        default: break;
+    }
+    *desc = &c->lv[level];
+    return buf && *buf ? image_slice(c, *buf, idx) : nullptr;
+}
+
 // Resolves (kind, level) to a device plane of image `idx`; on-demand kinds are computed into d_scratch.
 static int resolve_image(musica_ctx* c, uint32_t idx, musica_image_kind kind, uint32_t level, const float** plane, const LevelDesc** desc) {
     if (musica_image_side(c, kind, level) == 0) return fail("musica_get_image: no image kind=%d level=%u", (int)kind, level);
+    if (kind == MUSICA_IMG_NORMALIZED) ensure_normalized(c);
+    if (kind == MUSICA_IMG_SDEV) ensure_sdev(c);
+    if ((*plane = stored_plane(c, idx, kind, level, desc))) return 1;
     const LevelDesc& l0 = c->lv[0];
     const LevelDesc& l3 = c->lv[MUSICA_CNR_LEVEL];
     switch (kind) {
-        case MUSICA_IMG_NORMALIZED: ensure_normalized(c); *plane = c->d_norm + idx * l0.plane; *desc = &c->lv[0]; return 1;
-        case MUSICA_IMG_GRADED: *plane = c->d_graded + idx * l0.plane; *desc = &c->lv[0]; return 1;
-        case MUSICA_IMG_CLAHE_GRADED:
-            if (!c->d_clahe_graded) return fail("musica_get_image: ctx was created without MUSICA_FLAG_CLAHE");
-            *plane = c->d_clahe_graded + idx * l0.plane; *desc = &c->lv[0]; return 1;
-        case MUSICA_IMG_CNR: *plane = c->d_cnr + idx * l3.plane; *desc = &c->lv[MUSICA_CNR_LEVEL]; return 1;
-        case MUSICA_IMG_DOWNSAMPLED: *plane = c->d_down[level] + idx * c->lv[level + 1].plane; *desc = &c->lv[level + 1]; return 1;
-        case MUSICA_IMG_BANDPASS: *plane = c->d_band[level] + idx * c->lv[level].plane; *desc = &c->lv[level]; return 1;
-        case MUSICA_IMG_EXPAND: *plane = c->d_recon[level] + idx * c->lv[level].plane; *desc = &c->lv[level]; return 1;
+        case MUSICA_IMG_CLAHE_GRADED: return fail("musica_get_image: ctx was created without MUSICA_FLAG_CLAHE");
         case MUSICA_IMG_SDEV:
-            *desc = &c->lv[level];
-            ensure_sdev(c);
-            if (level <= MUSICA_CNR_LEVEL) { *plane = c->d_sdev[level] + idx * c->lv[level].plane; return 1; }
             // levels >= 4: the reference never writes these images (src/vk_processing.cpp:2285) -> zeros (Q2)
             HIP_OK(hipMemsetAsync(c->d_scratch, 0, c->lv[level].plane * sizeof(float), c->stream));
             *plane = c->d_scratch; return 1;
@@ -1435,28 +1433,21 @@ int musica_debug_set_image(musica_ctx* c, uint32_t idx, musica_image_kind kind, 
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if (!src) return fail("musica_debug_set_image: src is NULL");
     if (musica_image_side(c, kind, level) == 0) return fail("musica_debug_set_image: no image kind=%d level=%u", (int)kind, level);
-    switch (kind) {
-        case MUSICA_IMG_NORMALIZED:
-            if (c->fuse_u16) return fail("musica_debug_set_image: the normalized image is not stored on the hot path (level 0 reads the raw pixels)");
-            return upload_plane(c, c->d_norm + idx * c->lv[0].plane, c->lv[0], src);
-        case MUSICA_IMG_GRADED: return upload_plane(c, c->d_graded + idx * c->lv[0].plane, c->lv[0], src);
-        case MUSICA_IMG_CNR: return upload_plane(c, c->d_cnr + idx * c->lv[MUSICA_CNR_LEVEL].plane, c->lv[MUSICA_CNR_LEVEL], src);
-        case MUSICA_IMG_DOWNSAMPLED: return upload_plane(c, c->d_down[level] + idx * c->lv[level + 1].plane, c->lv[level + 1], src);
-        case MUSICA_IMG_BANDPASS: return upload_plane(c, c->d_band[level] + idx * c->lv[level].plane, c->lv[level], src);
-        case MUSICA_IMG_EXPAND: return upload_plane(c, c->d_recon[level] + idx * c->lv[level].plane, c->lv[level], src);
-        case MUSICA_IMG_SDEV:
-            if (level > MUSICA_CNR_LEVEL) return fail("musica_debug_set_image: sdev exists only for levels 0..3");
-            ensure_sdev(c);   // the other levels' stored images first: a later getter must not overwrite what the caller sets here
-            return upload_plane(c, c->d_sdev[level] + idx * c->lv[level].plane, c->lv[level], src);
-        default: return fail("musica_debug_set_image: kind %d is not stored on the hot path", (int)kind);
-    }
+    if (kind == MUSICA_IMG_NORMALIZED && c->fuse_u16)
+        return fail("musica_debug_set_image: the normalized image is not stored on the hot path (level 0 reads the raw pixels)");
+    if (kind == MUSICA_IMG_SDEV && level > MUSICA_CNR_LEVEL) return fail("musica_debug_set_image: sdev exists only for levels 0..3");
+    const LevelDesc* d = nullptr;
+    float* plane = kind == MUSICA_IMG_CLAHE_GRADED ? nullptr : stored_plane(c, idx, kind, level, &d);   // the CLAHE output is never set
+    if (!plane) return fail("musica_debug_set_image: kind %d is not stored on the hot path", (int)kind);
+    if (kind == MUSICA_IMG_SDEV) ensure_sdev(c);   // the other levels' stored images first: a later getter must not overwrite what the caller sets here
+    return upload_plane(c, plane, *d, src);
 }
 
 int musica_get_graded(musica_ctx* c, float* dst) {
     CHECK_CTX(c);
     if (!dst) return fail("musica_get_graded: dst is NULL");
     for (int b = 0; b < c->B; b++)
-        if (!download_plane(c, c->d_graded + (size_t)b * c->lv[0].plane, c->lv[0], dst + (size_t)b * c->N * c->N)) return 0;
+        if (!download_plane(c, image_slice(c, c->d_graded, b), c->lv[0], dst + (size_t)b * c->N * c->N)) return 0;
     return 1;
 }
 
@@ -1473,7 +1464,7 @@ static const uint8_t* out_pixels_pinned(musica_ctx* c, uint32_t idx) {
         if (hipHostMalloc((void**)&c->h_out8, bytes, hipHostMallocDefault) != hipSuccess) { c->h_out8 = nullptr; fail("saveOutImage: pinned allocation failed"); return nullptr; }
     }
     tick.lap("device + pinned buffers");
-    launch_out_pixels(c->stream, c->d_graded + (size_t)idx * c->lv[0].plane, c->lv[0], (int)margin, c->d_out8);
+    launch_out_pixels(c->stream, image_slice(c, c->d_graded, idx), c->lv[0], (int)margin, c->d_out8);
     hipError_t e = hipMemcpyAsync(c->h_out8, c->d_out8, bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { fail("saveOutImage: read-back failed: %s", hipGetErrorString(e)); return nullptr; }
@@ -1512,7 +1503,7 @@ int musica_save_out_image(musica_ctx* c, uint32_t idx, const char* path) {
         if (c->h_bmp && hipHostGetDevicePointer(&dev, c->h_bmp, 0) == hipSuccess && dev) {
             tick.lap("page-locked file image");
             memcpy(c->h_bmp + 2, hdr, 54);
-            launch_out_bmp24(c->stream, c->d_graded + (size_t)idx * c->lv[0].plane, c->lv[0], (int)margin, reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(dev) + 56));
+            launch_out_bmp24(c->stream, image_slice(c, c->d_graded, idx), c->lv[0], (int)margin, reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(dev) + 56));
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) return fail("saveOutImage: pixel kernel failed: %s", hipGetErrorString(e));
@@ -1535,26 +1526,26 @@ int musica_get_noise_hist(musica_ctx* c, uint32_t idx, uint32_t level, uint32_t*
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if ((int)level >= c->L) return fail("musica_get_noise_hist: level %u >= %d", level, c->L);
     if (level > MUSICA_CNR_LEVEL) { memset(dst, 0, MUSICA_NOISE_BINS * sizeof(uint32_t)); return 1; }  // cleared, never filled
-    return download_small(c, c->d_noise_hist + ((size_t)idx * 4 + level) * MUSICA_NOISE_BINS, dst, MUSICA_NOISE_BINS);
+    return download_small(c, image_slice(c, c->d_noise_hist, idx) + (size_t)level * MUSICA_NOISE_BINS, dst, MUSICA_NOISE_BINS);
 }
 int musica_get_grad_hist(musica_ctx* c, uint32_t idx, uint32_t* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
-    return download_small(c, c->d_grad_hist + (size_t)idx * MUSICA_GRAD_BINS, dst, MUSICA_GRAD_BINS);
+    return download_small(c, image_slice(c, c->d_grad_hist, idx), dst, MUSICA_GRAD_BINS);
 }
 int musica_get_noise_hist_max(musica_ctx* c, uint32_t idx, uint32_t level, musica_hist_max_point* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if ((int)level >= c->L) return fail("musica_get_noise_hist_max: level %u >= %d", level, c->L);
-    return download_small(c, c->d_noise_max + (size_t)idx * c->L + level, dst, 1);
+    return download_small(c, image_slice(c, c->d_noise_max, idx) + level, dst, 1);
 }
 int musica_get_grad_hist_max(musica_ctx* c, uint32_t idx, musica_hist_max_point* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
-    return download_small(c, c->d_grad_max + idx, dst, 1);
+    return download_small(c, image_slice(c, c->d_grad_max, idx), dst, 1);
 }
 int musica_get_contrast_curve(musica_ctx* c, uint32_t idx, uint32_t level, musica_contrast_curve* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if ((int)level >= c->L) return fail("musica_get_contrast_curve: level %u >= %d", level, c->L);
     DevCurve dc;
-    if (!download_small(c, c->d_curves + (size_t)idx * c->L + level, &dc, 1)) return 0;
+    if (!download_small(c, image_slice(c, c->d_curves, idx) + level, &dc, 1)) return 0;
     memset(dst, 0, sizeof(*dst));
     for (uint32_t i = 0; i < dc.count && i < MUSICA_MAX_POINTS; i++) { dst->points[i].x = dc.x[i]; dst->points[i].y = dc.y[i]; }
     dst->pointsCount = dc.count;
@@ -1563,7 +1554,7 @@ int musica_get_contrast_curve(musica_ctx* c, uint32_t idx, uint32_t level, music
 int musica_get_grad_curve(musica_ctx* c, uint32_t idx, musica_grad_curve* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     DevCurve dc;
-    if (!download_small(c, c->d_gcurve + idx, &dc, 1)) return 0;
+    if (!download_small(c, image_slice(c, c->d_gcurve, idx), &dc, 1)) return 0;
     memset(dst, 0, sizeof(*dst));
     for (uint32_t i = 0; i < dc.count && i < MUSICA_MAX_POINTS; i++) { dst->points[i].x = dc.x[i]; dst->points[i].y = dc.y[i]; }
     dst->pointsCount = dc.count;
@@ -1581,14 +1572,14 @@ static int plot_out(musica_ctx* c, uint8_t* rgba) {
 int musica_render_noise_hist(musica_ctx* c, uint32_t idx, uint8_t* rgba) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if (!rgba) return fail("musica_render_noise_hist: rgba is NULL");
-    launch_render_noise_hist(c->stream, c->d_noise_hist + ((size_t)idx * 4 + MUSICA_CNR_LEVEL) * MUSICA_NOISE_BINS,
-                             c->d_noise_max + (size_t)idx * c->L + MUSICA_CNR_LEVEL, c->d_plot);   // src/vk_processing.cpp:1260-1266
+    launch_render_noise_hist(c->stream, image_slice(c, c->d_noise_hist, idx) + MUSICA_CNR_LEVEL * MUSICA_NOISE_BINS,
+                             image_slice(c, c->d_noise_max, idx) + MUSICA_CNR_LEVEL, c->d_plot);   // src/vk_processing.cpp:1260-1266
     return plot_out(c, rgba);
 }
 int musica_render_grad_hist(musica_ctx* c, uint32_t idx, uint8_t* rgba) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if (!rgba) return fail("musica_render_grad_hist: rgba is NULL");
-    launch_render_grad_hist(c->stream, c->d_grad_hist + (size_t)idx * MUSICA_GRAD_BINS, c->d_grad_max + idx, c->d_gcurve + idx, c->d_plot);   // :1668-1675
+    launch_render_grad_hist(c->stream, image_slice(c, c->d_grad_hist, idx), image_slice(c, c->d_grad_max, idx), image_slice(c, c->d_gcurve, idx), c->d_plot);   // :1668-1675
     return plot_out(c, rgba);
 }
 int musica_get_contrast_params(musica_ctx* c, uint32_t level, musica_contrast_params* dst) {
@@ -1604,8 +1595,9 @@ int musica_get_nr_params(musica_ctx* c, uint32_t level, musica_nr_params* dst) {
 int musica_get_minmax(musica_ctx* c, uint32_t idx, float* min_sqrt, float* max_sqrt) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     uint32_t mm[2];
-    if (!download_small(c, c->d_minmax + kMinMaxStride * (size_t)idx, &mm[0], 1)) return 0;
-    if (!download_small(c, c->d_minmax + kMinMaxStride * (size_t)idx + kMaxWord, &mm[1], 1)) return 0;
+    const uint32_t* minmax = image_slice(c, c->d_minmax, idx);
+    if (!download_small(c, minmax, &mm[0], 1)) return 0;
+    if (!download_small(c, minmax + kMaxWord, &mm[1], 1)) return 0;
     // same scalars the normalize kernel derives (kernels_analysis.hip chain_scalars)
     const float mx = sqrtf((float)mm[1]), mn = sqrtf((float)mm[0]);
     *max_sqrt = (float)(uint32_t)mx;
@@ -1625,19 +1617,17 @@ int musica_stats_device(musica_ctx* c, void* d_dst, uint32_t image_id_base) { re
 int musica_get_stats(musica_ctx* c, uint32_t idx, musica_stats* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if (!musica_stats_device(c, c->d_stats, 0)) return 0;
-    return download_small(c, c->d_stats + idx, dst, 1);
+    return download_small(c, image_slice(c, c->d_stats, idx), dst, 1);
 }
 int musica_get_clahe_hist(musica_ctx* c, uint32_t idx, uint32_t* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if (!c->d_clahe_hist) return fail("musica_get_clahe_hist: ctx was created without MUSICA_FLAG_CLAHE");
-    const size_t tb = MUSICA_CLAHE_TILES * MUSICA_CLAHE_TILES * MUSICA_CLAHE_BINS;
-    return download_small(c, c->d_clahe_hist + idx * tb, dst, tb);
+    return download_small(c, image_slice(c, c->d_clahe_hist, idx), dst, per_image(c, c->d_clahe_hist));
 }
 int musica_get_clahe_curves(musica_ctx* c, uint32_t idx, musica_point* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if (!c->d_clahe_pts) return fail("musica_get_clahe_curves: ctx was created without MUSICA_FLAG_CLAHE");
-    const size_t tb = MUSICA_CLAHE_TILES * MUSICA_CLAHE_TILES * MUSICA_CLAHE_BINS;
-    return download_small(c, c->d_clahe_pts + idx * tb, dst, tb);
+    return download_small(c, image_slice(c, c->d_clahe_pts, idx), dst, per_image(c, c->d_clahe_pts));
 }
 
 // VulkanState::downloadAndSaveImage (src/vk_state.cpp:809-855): (uint8_t)(255 * (v - min) / (max - min)), full image.

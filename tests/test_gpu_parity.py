@@ -263,6 +263,70 @@ def test_streaming_execute_overlaps_copies_and_keeps_every_batch_exact(ob):
     p.cleanup()
 
 
+@pytest.mark.parametrize("n,levels,batch,clahe,env", [
+    (520, 5, 5, False, {"MUSICA_GRAPH": "0"}),             # lanes of 2 + 2 + 1 images
+    (520, 5, 5, False, {"MUSICA_GRAPH": "1"}),
+    (1040, 6, 3, False, {"MUSICA_GRAPH": "0"}),            # lanes of 1 + 1 + 1 images
+    (1040, 6, 3, False, {"MUSICA_GRAPH": "1"}),
+    (520, 5, 5, False, {"MUSICA_SDEV_IN_EXPAND": "1"}),
+    (1024, 5, 3, True, {}),
+])
+def test_execute_from_pinned_batch_takes_the_image_lanes(ob, n, levels, batch, clahe, env, monkeypatch):
+    """musica_execute of a batch in page-locked memory runs the image lanes: per-image shallow copies of the context whose pointers
+    are moved to their images. A batch of different phantoms, then the same pinned buffer with the images rotated (a lane that read
+    or wrote another image's slice, or kept the previous call's, shows up): every image equals the oracle. The whole-batch path
+    (MUSICA_HOST_LANES=0) gives the same arrays, and a pageable execute and upload + execute_device on the same context still work."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.delenv("MUSICA_HOST_LANES", raising=False)
+    px = np.stack([phantom(n, 60 + k) for k in range(batch)])
+    oflags = [ob.FLAG_CLAHE] if clahe else []
+    oracles = [ob.Oracle(n, levels, ob.ORDER_FAST, *oflags).execute(px[k]) for k in range(batch)]
+    p = _proc(n, levels, batch=batch, flags=mp.FLAG_CLAHE if clahe else 0)
+
+    def check(order, tag):
+        for k in range(batch):
+            o = oracles[order[k]]
+            _compare_all(p, o, ob, idx=k, tag="%s image %d: " % (tag, k))
+            if clahe:
+                assert np.array_equal(p.clahe_hist(k), o.clahe_hist()), tag + "clahe_hist %d" % k
+                a, b = p.clahe_curves(k), o.clahe_curves()
+                assert ((a == b) | (np.isnan(a) & np.isnan(b))).all(), tag + "clahe_curves %d" % k
+                _same(p.image(mp.IMG_CLAHE_GRADED, 0, k), o.image(ob.IMG_CLAHE_GRADED), tag + "clahe graded %d" % k)
+
+    def snapshot():
+        s = [p.graded().copy()]
+        for k in range(batch):
+            s += [p.out_pixels(k), p.grad_hist(k), p.image(mp.IMG_CNR, 3, k)] + [p.noise_hist(i, k) for i in range(4)]
+            if clahe:
+                s += [p.clahe_hist(k), p.clahe_curves(k), p.image(mp.IMG_CLAHE_GRADED, 0, k)]
+        return s
+
+    # The lane path's preconditions hold for every execute(pinned) below: B > 1, input in page-locked memory (musica_host_alloc),
+    # profiling off (musica_execute then copies and computes image by image).
+    pinned = p.host_alloc(px.shape)
+    orders = [list(range(batch)), [(k + 1) % batch for k in range(batch)]]
+    for rep, order in enumerate(orders):
+        pinned[...] = px[order]
+        assert p.execute(pinned), mp.last_error()
+        check(order, "lanes, call %d," % rep)
+    lanes = snapshot()
+    monkeypatch.setenv("MUSICA_HOST_LANES", "0")
+    assert p.execute(pinned), mp.last_error()
+    whole = snapshot()
+    monkeypatch.delenv("MUSICA_HOST_LANES")
+    for a, b in zip(lanes, whole):
+        assert np.array_equal(a, b, equal_nan=True), "image lanes against the whole batch"
+    p.host_free(pinned)
+    assert p.execute(px), mp.last_error()                  # pageable input: the whole-batch path
+    _compare_all(p, oracles[batch - 1], ob, idx=batch - 1, tag="pageable execute: ")
+    p.upload(px[orders[1]])
+    assert p.execute_device(), mp.last_error()
+    p.sync()
+    _compare_all(p, oracles[orders[1][batch - 1]], ob, idx=batch - 1, tag="execute_device: ")
+    p.cleanup()
+
+
 def _random_cases(count, seed):
     """(N, levels, phantom seed, bits, noise) drawn once from a fixed generator: odd sizes, sizes around the strip
     (512) and vector (8) boundaries, the smallest accepted sides, reference-rule and explicit level counts."""
