@@ -329,6 +329,35 @@ int musica_pipeline_step(musica_pipeline* p, const uint16_t* d_pixels);
 musica_ctx* musica_pipeline_last(musica_pipeline* p);
 int musica_pipeline_sync(musica_pipeline* p);
 
+/* ---- similarity metrics of the metamorphic study (new, not in the reference) ---- */
+
+/* The reference's study scores each processed altered image against the processed unaltered one with 1 - RMSE / 255, SSIM (7 x 7
+ * uniform window, K1 = 0.01, K2 = 0.03, data range 255, sample covariance, borders cropped) and three 256-bin histogram distances
+ * (test/metamorphic_test/script.py:143-198; harness.py mse_similarity / ssim_similarity / hist_similarity). These entry points
+ * compute them on the device: side a is the 8-bit output of a batch image (exactly what musica_get_out_pixels returns, quantised
+ * while it is read), side b one of MUSICA_SIM_SLOTS context-owned reference planes of side N - 20. A region is given in
+ * output-pixel coordinates: (ax, ay) in a, (bx, by) in b, w x h (w, h >= 7). All three run on the context's stream after whatever
+ * was enqueued there (a step, musica_execute_device, a pipeline step of this context) and add nothing to a step. */
+#define MUSICA_SIM_SLOTS 8
+#define MUSICA_SIM_MAX_QUERIES 64
+typedef struct musica_sim_query {
+    uint32_t image_index, slot, ax, ay, bx, by, w, h;
+} musica_sim_query;
+typedef struct musica_sim_result {
+    double mse, ssim, hist_intersection, hist_distance, hist_bhattacharyya;   /* harness.similarities' five numbers */
+    uint64_t sq_diff_sum, pixels;                                             /* exact: sum of (a - b)^2 over the region, w * h */
+    uint32_t bins_a[256], bins_b[256];                                        /* == np.histogram(a or b, bins=256)[0] */
+    uint32_t min_a, max_a, min_b, max_b;                                      /* the values np.histogram's range spans */
+} musica_sim_result;
+/* The current 8-bit output of image `image_index` into `slot` (device to device). */
+int musica_sim_capture(musica_ctx* ctx, uint32_t slot, uint32_t image_index);
+/* (N - 20)^2 host bytes, top-down rows, into `slot` (synchronous). */
+int musica_sim_set_reference(musica_ctx* ctx, uint32_t slot, const uint8_t* pixels);
+/* `count` (1 .. MUSICA_SIM_MAX_QUERIES) comparisons in one launch; synchronous. Refused (0, musica_last_error) before any device work:
+ * NULL pointers, a count out of range, a slot out of range or never written, image_index >= batch, a region that leaves either
+ * plane, w < 7 or h < 7. */
+int musica_sim_compare(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_result* results);
+
 /* ---- test / profiling hooks ------------------------------------------ */
 
 /* A sequence of `count` batches (pixels[j]: batch x N x N uint16 in host memory), pipelined: two device input buffers and a

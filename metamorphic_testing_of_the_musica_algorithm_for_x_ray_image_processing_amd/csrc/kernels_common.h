@@ -143,6 +143,16 @@ __device__ __forceinline__ uint32_t f2u(float v) {
     return (uint32_t)v;
 }
 
+// saveOutImage's quantisation of one graded texel, (uint8_t)(255.0f * (v - 0) / (1 - 0)) (src/vk_processing.cpp:2624-2634). The C cast
+// is undefined outside [0, 256): restated as the x86 lowering the reference's build gets (cvttss2si to int32, low byte kept; NaN and
+// values outside int32 give 0x80000000 -> 0), the same statement as the oracle's and dump_image's. Shared by k_out_pixels, k_out_bmp24
+// and the similarity kernel (kernels_similarity.hip), which quantise while they load.
+__device__ __forceinline__ uint32_t out_u8(float v) {
+    const float maxValue = 1.0f, minValue = 0.0f;
+    const float q = 255.0f * (v - minValue) / (maxValue - minValue);
+    return (q == q && q > -2147483648.0f && q < 2147483648.0f) ? (uint32_t)(uint8_t)(int32_t)q : 0u;
+}
+
 // The two scalars img_normalize.comp:17-18 reads from the 1x1 ends of the min / max chains, from the
 // integer extrema k_minmax_u16 left in `minmax` (see kernels_analysis.hip).
 __device__ __forceinline__ void chain_scalars(const uint32_t* __restrict__ minmax, int img, int min_chain_exact, float& minv, float& maxv) {

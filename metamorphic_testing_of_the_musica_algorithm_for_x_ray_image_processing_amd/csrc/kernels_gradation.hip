@@ -575,17 +575,13 @@ void launch_grad_curve(hipStream_t st, uint32_t* hist, musica_hist_max_point* gm
     hipLaunchKernelGGL(k_grad_curve, dim3(batch), dim3(1024), 0, st, hist, gmax, curves, hist_b, gzero);
 }
 
-// saveOutImage (src/vk_processing.cpp:2624-2634): crop `margin` texels on every side and quantise, (uint8_t)(255.0f * (v - 0) / (1 - 0)),
-// on the device, so that the read-back is 1 byte per output pixel instead of 4 bytes per input pixel. The C cast is undefined
-// outside [0, 256): restated as the x86 lowering the reference's build gets (cvttss2si to int32, low byte kept; NaN and
-// values outside int32 give 0x80000000 -> 0), the same statement as the oracle's and dump_image's.
+// saveOutImage (src/vk_processing.cpp:2624-2634): crop `margin` texels on every side and quantise (out_u8, kernels_common.h) on the
+// device, so that the read-back is 1 byte per output pixel instead of 4 bytes per input pixel.
 __global__ __launch_bounds__(256) void k_out_pixels(const float* __restrict__ graded, int pitch, int margin, int nw, uint8_t* __restrict__ out) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
     if (x >= nw) return;
-    const float maxValue = 1.0f, minValue = 0.0f;
-    const float q = 255.0f * (graded[(size_t)(y + margin) * pitch + x + margin] - minValue) / (maxValue - minValue);
-    out[(size_t)y * nw + x] = (q == q && q > -2147483648.0f && q < 2147483648.0f) ? (uint8_t)(int32_t)q : (uint8_t)0;
+    out[(size_t)y * nw + x] = (uint8_t)out_u8(graded[(size_t)(y + margin) * pitch + x + margin]);
 }
 void launch_out_pixels(hipStream_t st, const float* graded, const LevelDesc& l0, int margin, uint8_t* out) {
     const int nw = l0.S - 2 * margin;
@@ -601,16 +597,11 @@ __global__ __launch_bounds__(256) void k_out_bmp24(const float* __restrict__ gra
     const int r = blockIdx.y;              // file row: 0 is the bottom row of the image
     if (k >= row_words) return;
     const float* src = graded + (size_t)(nw - 1 - r + margin) * pitch + margin;
-    const float maxValue = 1.0f, minValue = 0.0f;
     uint32_t word = 0u;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int px = (4 * k + j) / 3;
-        uint32_t v = 0u;
-        if (px < nw) {
-            const float q = 255.0f * (src[px] - minValue) / (maxValue - minValue);
-            v = (q == q && q > -2147483648.0f && q < 2147483648.0f) ? (uint32_t)(uint8_t)(int32_t)q : 0u;   // k_out_pixels' statement of the cast
-        }
+        const uint32_t v = px < nw ? out_u8(src[px]) : 0u;
         word |= v << (8 * j);
     }
     out[(size_t)r * row_words + k] = word;

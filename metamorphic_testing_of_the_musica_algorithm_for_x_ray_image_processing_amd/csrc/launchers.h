@@ -133,6 +133,26 @@ void launch_grad_apply(hipStream_t st, const float* in, float* out, const LevelD
 // crop + quantise of saveOutImage for ONE image plane: out = (S - 2 margin)^2 bytes, dense
 void launch_out_pixels(hipStream_t st, const float* graded, const LevelDesc& l0, int margin, uint8_t* out);
 void launch_out_bmp24(hipStream_t st, const float* graded, const LevelDesc& l0, int margin, uint32_t* out);   // the BMP file's pixel array (24 bpp, bottom-up, padded rows)
+// kernels_similarity.hip: one comparison of musica_sim_compare. a: the graded f32 plane at the region's origin (margin included),
+// b: the reference slot's u8 plane at its origin; strips / segs / seg_rows: launch geometry (sim_geometry).
+struct SimQueryDev {
+    const float* a;
+    const uint8_t* b;
+    int a_pitch, b_pitch;   // elements
+    int w, h;
+    int strips, segs, seg_rows;
+};
+struct SimPart {
+    double ssim;              // sum of the per-pixel SSIM over the interior the workgroup computes
+    unsigned long long ssd;   // sum of squared differences over the pixels it owns
+};
+struct SimConsts {
+    double c1, c2, cov_norm;  // (0.01 * 255)^2, (0.03 * 255)^2, 49 / 48 as harness.ssim_similarity computes them
+};
+constexpr int kSimMaxBlocks = 1024;   // workgroups per query (partials slots)
+void sim_geometry(SimQueryDev& q);
+// k_sim over `count` queries (grid.x = the largest strips * segs), then k_sim_fold; hist: count x [a 256 | b 256] u32, zeroed by the caller
+void launch_sim(hipStream_t st, const SimQueryDev* d_qs, int count, int max_blocks, SimPart* part, uint32_t* hist, SimPart* out, const SimConsts& k);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <exception>
 #include <string>
@@ -144,6 +145,14 @@ struct musica_ctx : DeviceBuffers {
     uint8_t* h_out8 = nullptr;
     uint8_t* h_bmp = nullptr;    // saveOutImage's whole file image in page-locked memory: 2 bytes of padding, the 54-byte header, then the pixel array the
                                  // device writes itself (k_out_bmp24: the array starts on a 4-byte boundary); allocated on first use
+    // musica_sim_*: the reference slots (u8, side N - 20) and the scratch of musica_sim_compare, context-level and allocated on first use
+    uint8_t* d_sim_slot[MUSICA_SIM_SLOTS] = {};
+    bool sim_written[MUSICA_SIM_SLOTS] = {};
+    SimQueryDev* d_sim_q = nullptr;
+    SimPart* d_sim_part = nullptr;   // [MUSICA_SIM_MAX_QUERIES][kSimMaxBlocks]
+    SimPart* d_sim_out = nullptr;    // [MUSICA_SIM_MAX_QUERIES]
+    uint32_t* d_sim_hist = nullptr;  // [MUSICA_SIM_MAX_QUERIES][512]: value counts of a, then b
+    std::vector<SimQueryDev> h_sim_q;
     // host parameters (src/vk_processing.cpp:259-297, 321-325)
     musica_contrast_params h_cparams[MUSICA_MAX_LEVELS];
     musica_nr_params h_nr[3];
@@ -1520,6 +1529,139 @@ int musica_save_out_image(musica_ctx* c, uint32_t idx, const char* path) {
     tick.lap("bmp file");
     return 1;
     ABI_CATCH("musica_save_out_image")
+}
+
+// ---- similarity metrics (musica_sim_*, include/musica.h; kernels_similarity.hip) ----------------------------------------------------
+static uint8_t* sim_slot(musica_ctx* c, uint32_t slot) {
+    const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
+    if (!c->d_sim_slot[slot] && !dalloc(c, &c->d_sim_slot[slot], nw * nw)) { fail("musica_sim: device allocation of slot %u failed", slot); return nullptr; }
+    return c->d_sim_slot[slot];
+}
+
+int musica_sim_capture(musica_ctx* c, uint32_t slot, uint32_t idx) {
+    if (!c) return fail("musica_sim_capture: ctx is NULL");
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_capture: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    CHECK_IMG(c, idx);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_capture: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    CHECK_CTX(c);
+    uint8_t* dst = sim_slot(c, slot);
+    if (!dst) return 0;
+    launch_out_pixels(c->stream, image_slice(c, c->d_graded, idx), c->lv[0], MUSICA_OUT_MARGIN, dst);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("musica_sim_capture: launch failed: %s", hipGetErrorString(e));
+    c->sim_written[slot] = true;
+    return 1;
+}
+
+int musica_sim_set_reference(musica_ctx* c, uint32_t slot, const uint8_t* pixels) {
+    if (!c) return fail("musica_sim_set_reference: ctx is NULL");
+    if (!pixels) return fail("musica_sim_set_reference: pixels is NULL");
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_set_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_set_reference: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    CHECK_CTX(c);
+    uint8_t* dst = sim_slot(c, slot);
+    if (!dst) return 0;
+    const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
+    HIP_OK(hipMemcpyAsync(dst, pixels, nw * nw, hipMemcpyHostToDevice, c->stream));   // after what the stream holds (a compare reading the slot)
+    HIP_OK(hipStreamSynchronize(c->stream));                                             // `pixels` is borrowed for the call
+    c->sim_written[slot] = true;
+    return 1;
+}
+
+// harness.hist_similarity from the exact value counts: np.histogram(v, bins=256) of u8 data spans [lo, hi] = [min, max] and puts v
+// into bin min(255, (v - lo) * 256 // (hi - lo)) — exactly, for every (lo, hi) — and everything into bin 128 when lo == hi
+// (numpy widens the range by +-0.5).
+static void sim_bins(const uint32_t* counts, uint32_t* bins, uint32_t* lo_out, uint32_t* hi_out) {
+    int lo = 0, hi = 255;
+    while (lo < 255 && counts[lo] == 0) lo++;
+    while (hi > 0 && counts[hi] == 0) hi--;
+    memset(bins, 0, 256 * sizeof(uint32_t));
+    for (int v = lo; v <= hi; v++) {
+        if (!counts[v]) continue;
+        const int b = hi == lo ? 128 : std::min(255, (v - lo) * 256 / (hi - lo));
+        bins[b] += counts[v];
+    }
+    *lo_out = (uint32_t)lo;
+    *hi_out = (uint32_t)hi;
+}
+
+static void sim_finish(const uint32_t* counts /* a 256 | b 256 */, const SimPart& r, const musica_sim_query& q, musica_sim_result* o) {
+    const uint64_t n = (uint64_t)q.w * q.h;
+    o->sq_diff_sum = r.ssd;
+    o->pixels = n;
+    sim_bins(counts, o->bins_a, &o->min_a, &o->max_a);
+    sim_bins(counts + 256, o->bins_b, &o->min_b, &o->max_b);
+    o->mse = 1.0 - sqrt((double)r.ssd / (65025.0 * (double)n));                 // 1 - sqrt(mean(((a - b) / 255)^2))
+    o->ssim = r.ssim / ((double)(q.w - 6) * (double)(q.h - 6));                // mean over the interior (borders of 3 cropped)
+    uint64_t inter = 0;
+    double e2 = 0.0, bc = 0.0;
+    for (int i = 0; i < 256; i++) {
+        inter += std::min(o->bins_a[i], o->bins_b[i]);
+        const double na = (double)o->bins_a[i] / (double)n, nb = (double)o->bins_b[i] / (double)n;
+        e2 += (na - nb) * (na - nb);
+        bc += sqrt(na * nb);
+    }
+    o->hist_intersection = (double)inter / (double)n;
+    o->hist_distance = sqrt(e2) / sqrt(2.0);
+    o->hist_bhattacharyya = bc;
+}
+
+int musica_sim_compare(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_result* out) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_compare: ctx is NULL");
+    if (!qs || !out) return fail("musica_sim_compare: queries or results is NULL");
+    if (count == 0 || count > MUSICA_SIM_MAX_QUERIES) return fail("musica_sim_compare: count %u out of range [1, %d]", count, MUSICA_SIM_MAX_QUERIES);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_compare: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        if (q.slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_compare: query %u: slot %u >= %d", i, q.slot, MUSICA_SIM_SLOTS);
+        if (!c->sim_written[q.slot]) return fail("musica_sim_compare: query %u: slot %u was never written", i, q.slot);
+        if ((int)q.image_index >= c->B) return fail("musica_sim_compare: query %u: image_index %u >= batch %d", i, q.image_index, c->B);
+        if (q.w < 7 || q.h < 7) return fail("musica_sim_compare: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", i, q.w, q.h);
+        if ((uint64_t)q.ax + q.w > nw || (uint64_t)q.ay + q.h > nw || (uint64_t)q.bx + q.w > nw || (uint64_t)q.by + q.h > nw)
+            return fail("musica_sim_compare: query %u: region (%u, %u) / (%u, %u) + %u x %u leaves the %llu x %llu planes", i, q.ax, q.ay, q.bx, q.by,
+                        q.w, q.h, (unsigned long long)nw, (unsigned long long)nw);
+    }
+    CHECK_CTX(c);
+    if (!c->d_sim_hist) {   // keyed on the LAST allocation of the block
+        const bool ok = (c->d_sim_q || dalloc(c, &c->d_sim_q, MUSICA_SIM_MAX_QUERIES)) &&
+                        (c->d_sim_part || dalloc(c, &c->d_sim_part, (size_t)MUSICA_SIM_MAX_QUERIES * kSimMaxBlocks)) &&
+                        (c->d_sim_out || dalloc(c, &c->d_sim_out, MUSICA_SIM_MAX_QUERIES)) &&
+                        dalloc(c, &c->d_sim_hist, (size_t)MUSICA_SIM_MAX_QUERIES * 512);
+        if (!ok) return fail("musica_sim_compare: device allocation failed");
+    }
+    c->h_sim_q.assign(count, SimQueryDev{});
+    int max_blocks = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        SimQueryDev& d = c->h_sim_q[i];
+        d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
+        d.b = c->d_sim_slot[q.slot] + (size_t)q.by * nw + q.bx;
+        d.a_pitch = c->lv[0].pitch;
+        d.b_pitch = (int)nw;
+        d.w = (int)q.w;
+        d.h = (int)q.h;
+        sim_geometry(d);
+        max_blocks = std::max(max_blocks, d.strips * d.segs);
+    }
+    SimConsts k;
+    const double k1 = 0.01 * 255, k2 = 0.03 * 255;   // harness.ssim_similarity: c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2 (float ** is C pow)
+    k.c1 = pow(k1, 2.0);
+    k.c2 = pow(k2, 2.0);
+    k.cov_norm = 49.0 / 48.0;                         // npx / (npx - 1)
+    HIP_OK(hipMemcpyAsync(c->d_sim_q, c->h_sim_q.data(), count * sizeof(SimQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(c->d_sim_hist, 0, (size_t)count * 512 * sizeof(uint32_t), c->stream));
+    launch_sim(c->stream, c->d_sim_q, (int)count, max_blocks, c->d_sim_part, c->d_sim_hist, c->d_sim_out, k);
+    HIP_OK(hipGetLastError());
+    std::vector<uint32_t> hist((size_t)count * 512);
+    std::vector<SimPart> parts(count);
+    HIP_OK(hipMemcpyAsync(hist.data(), c->d_sim_hist, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(parts.data(), c->d_sim_out, count * sizeof(SimPart), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < count; i++) sim_finish(hist.data() + (size_t)i * 512, parts[i], qs[i], out + i);
+    return 1;
+    ABI_CATCH("musica_sim_compare")
 }
 
 int musica_get_noise_hist(musica_ctx* c, uint32_t idx, uint32_t level, uint32_t* dst) {

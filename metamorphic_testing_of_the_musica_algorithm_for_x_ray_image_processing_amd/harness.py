@@ -138,24 +138,49 @@ def similarities(a, b):
 
 
 # ---- registration of the altered result onto the unaltered one (script.py:442-456, 484-508, 586-608) ----
+# The geometry lives in the *_rects functions: one rectangle (x, y, w, h) per side, exactly what the reference's slices select (Python's
+# clamping of slice bounds included). register_* slice with them; roi_* state them as the (ax, ay, bx, by, w, h) region of a device-side
+# comparison (musica_sim_compare), or None when the two slices differ in shape (the study then has no registered comparison).
 
-def register_collimator(alt, unalt, shutter):
+def _span(start, stop, n):
+    """What a[start:stop] selects along an axis of length n: (first index, length)."""
+    first, end, _ = slice(start, stop).indices(n)
+    return first, max(0, end - first)
+
+
+def _rect(shape, y0, y1, x0, x1):
+    y, h = _span(y0, y1, shape[0])
+    x, w = _span(x0, x1, shape[1])
+    return x, y, w, h
+
+
+def _crop(alt, unalt, rects):
+    (ax, ay, aw, ah), (bx, by, bw, bh) = rects
+    return alt[ay:ay + ah, ax:ax + aw], unalt[by:by + bh, bx:bx + bw]
+
+
+def _roi(rects):
+    (ax, ay, aw, ah), (bx, by, bw, bh) = rects
+    return (ax, ay, bx, by, aw, ah) if (aw, ah) == (bw, bh) else None
+
+
+def collimator_rects(a_shape, b_shape, shutter):
     x = y = shutter + PROCESSING_MARGIN
-    w = alt.shape[1] - (2 * shutter + 2 * PROCESSING_MARGIN)
-    h = alt.shape[0] - (2 * shutter + 2 * PROCESSING_MARGIN)
-    return alt[y:y + h, x:x + w], unalt[y:y + h, x:x + w]
+    w = a_shape[1] - (2 * shutter + 2 * PROCESSING_MARGIN)
+    h = a_shape[0] - (2 * shutter + 2 * PROCESSING_MARGIN)
+    return _rect(a_shape, y, y + h, x, x + w), _rect(b_shape, y, y + h, x, x + w)
 
 
-def register_translation_x(alt, unalt, tx):
-    return alt[:, tx:], unalt[:, PROCESSING_MARGIN:alt.shape[1] - tx + PROCESSING_MARGIN]
+def translation_x_rects(a_shape, b_shape, tx):
+    return _rect(a_shape, None, None, tx, None), _rect(b_shape, None, None, PROCESSING_MARGIN, a_shape[1] - tx + PROCESSING_MARGIN)
 
 
-def register_translation_y(alt, unalt, ty):
-    return alt[ty:, :], unalt[PROCESSING_MARGIN:alt.shape[0] - ty + PROCESSING_MARGIN, :]
+def translation_y_rects(a_shape, b_shape, ty):
+    return _rect(a_shape, ty, None, None, None), _rect(b_shape, PROCESSING_MARGIN, a_shape[0] - ty + PROCESSING_MARGIN, None, None)
 
 
-def register_rotation(alt, unalt, degree):
-    h, w = unalt.shape
+def rotation_rects(a_shape, b_shape, degree):
+    h, w = b_shape
     ang = math.radians(degree)
     new_w = w * abs(math.cos(ang)) + h * abs(math.sin(ang))
     new_h = h * abs(math.cos(ang)) + w * abs(math.sin(ang))
@@ -163,8 +188,44 @@ def register_rotation(alt, unalt, degree):
     inner_h = h * w / new_w if w < h else w * h / new_h
     left, top = int((w - inner_w) / 2), int((h - inner_h) / 2)
     right, bottom = int((w + inner_w) / 2), int((h + inner_h) / 2)
-    rot = ndimage.rotate(unalt, degree, reshape=False, order=0, mode="constant", cval=0)
-    return alt[top:bottom, left:right], rot[top:bottom, left:right]
+    return _rect(a_shape, top, bottom, left, right), _rect(b_shape, top, bottom, left, right)
+
+
+def roi_collimator(shape, shutter, b_shape=None):
+    return _roi(collimator_rects(shape, b_shape or shape, shutter))
+
+
+def roi_translation_x(shape, tx, b_shape=None):
+    return _roi(translation_x_rects(shape, b_shape or shape, tx))
+
+
+def roi_translation_y(shape, ty, b_shape=None):
+    return _roi(translation_y_rects(shape, b_shape or shape, ty))
+
+
+def roi_rotation(shape, degree, b_shape=None):
+    return _roi(rotation_rects(shape, b_shape or shape, degree))
+
+
+def register_collimator(alt, unalt, shutter):
+    return _crop(alt, unalt, collimator_rects(alt.shape, unalt.shape, shutter))
+
+
+def register_translation_x(alt, unalt, tx):
+    return _crop(alt, unalt, translation_x_rects(alt.shape, unalt.shape, tx))
+
+
+def register_translation_y(alt, unalt, ty):
+    return _crop(alt, unalt, translation_y_rects(alt.shape, unalt.shape, ty))
+
+
+def rotated_reference(unalt, degree):
+    """The unaltered result rotated like the alteration (nearest neighbour, zero fill), what register_rotation compares against."""
+    return ndimage.rotate(unalt, degree, reshape=False, order=0, mode="constant", cval=0)
+
+
+def register_rotation(alt, unalt, degree):
+    return _crop(alt, rotated_reference(unalt, degree), rotation_rects(alt.shape, unalt.shape, degree))
 
 
 # ---- running the pipeline -------------------------------------------------------------------------
@@ -172,8 +233,11 @@ def register_rotation(alt, unalt, degree):
 class Runner:
     """Processes raw images to the 8-bit output the reference's saveOutImage writes (margin cropped)."""
 
-    def __init__(self, image_size, levels=0, device=0, use_cli=False):
+    def __init__(self, image_size, levels=0, device=0, use_cli=False, device_metrics=False):
+        if use_cli and device_metrics:
+            raise ValueError("device metrics score the library's device output: the CLI path has none")
         self.n, self.levels, self.device, self.use_cli = image_size, levels, device, use_cli
+        self.device_metrics = device_metrics   # run_study scores on the device (musica_sim_compare) instead of with numpy
         self.proc = None
         if not use_cli:
             self.proc = mp.MusicaProcessing(device=device)
@@ -187,6 +251,11 @@ class Runner:
         if not self.proc.execute(raw):
             raise RuntimeError("musica_execute failed: " + mp.last_error())
         return self.proc.out_pixels()
+
+    def run_device(self, raw):
+        """The same step, its output left on the device (for sim_capture / sim_compare)."""
+        if not self.proc.execute(raw):
+            raise RuntimeError("musica_execute failed: " + mp.last_error())
 
     def mean_cnr(self):
         """mean(cnr image) * 256 of the last run — what test/mean_cnr/script.py prints for a cnr.bmp dump."""
@@ -220,7 +289,8 @@ def read_bmp_gray(path):
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
-    {alteration, direct: {...}, registered: {...} or None, mean_cnr}."""
+    {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
+    on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1)."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     shutters = scaled(SHUTTERS, n) if shutters is None else shutters
@@ -228,27 +298,60 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     rotations = ROTATIONS if rotations is None else rotations
     sigmas = GAUSS_SIGMAS if sigmas is None else sigmas
     factors = POISSON_FACTORS if factors is None else factors
+    device = getattr(runner, "device_metrics", False)
     unalt = runner.run(raw)
-    rows = [{"alteration": "unaltered", "direct": similarities(unalt, unalt), "registered": None, "mean_cnr": runner.mean_cnr() if runner.proc else None}]
+    shape = unalt.shape
+    full = (0, 0, 0, 0, shape[1], shape[0])
 
-    def add(name, altered_raw, reg=None):
-        alt = runner.run(altered_raw)
-        row = {"alteration": name, "direct": similarities(alt, unalt), "registered": None,
-               "mean_cnr": runner.mean_cnr() if runner.proc else None}
-        if reg is not None:
-            a, u = reg(alt, unalt)
-            if a.size and a.shape == u.shape and min(a.shape) >= 8:
-                row["registered"] = similarities(a, u)
-        rows.append(row)
+    def on_device(queries):
+        return [{k: r[k] for k in mp.SIM_METRICS} for r in runner.proc.sim_compare(queries)]
+
+    if device:
+        runner.proc.sim_capture(0)
+        direct = on_device([(0, 0) + full])[0]
+    else:
+        direct = similarities(unalt, unalt)
+    rows = [{"alteration": "unaltered", "direct": direct, "registered": None, "mean_cnr": runner.mean_cnr() if runner.proc else None}]
+
+    def add(name, altered_raw, reg=None, roi=None):
+        """reg: the host crop; roi: () -> (region, slot) of the same comparison on the device (region None: no registration)."""
+        row = {"alteration": name, "registered": None}
+        if device:
+            runner.run_device(altered_raw)
+            queries = [(0, 0) + full]
+            if roi is not None:
+                region, slot = roi()
+                if region is not None and min(region[4], region[5]) >= 8:
+                    queries.append((0, slot) + region)
+            res = on_device(queries)
+            row["direct"] = res[0]
+            if len(res) > 1:
+                row["registered"] = res[1]
+        else:
+            alt = runner.run(altered_raw)
+            row["direct"] = similarities(alt, unalt)
+            if reg is not None:
+                a, u = reg(alt, unalt)
+                if a.size and a.shape == u.shape and min(a.shape) >= 8:
+                    row["registered"] = similarities(a, u)
+        row["mean_cnr"] = runner.mean_cnr() if runner.proc else None
+        rows.append({k: row[k] for k in ("alteration", "direct", "registered", "mean_cnr")})
+
+    def rotated_slot(d):
+        runner.proc.sim_set_reference(1, rotated_reference(unalt, d))
+        return roi_rotation(shape, d), 1
 
     for s in shutters:
-        add("c_sh_%d" % s, apply_collimator(raw, s, s, rng), lambda a, u, s=s: register_collimator(a, u, s))
+        add("c_sh_%d" % s, apply_collimator(raw, s, s, rng), lambda a, u, s=s: register_collimator(a, u, s),
+            lambda s=s: (roi_collimator(shape, s), 0))
     for t in translations:
-        add("t_x_%d" % t, clamp_translation(raw, t, 0), lambda a, u, t=t: register_translation_x(a, u, t))
+        add("t_x_%d" % t, clamp_translation(raw, t, 0), lambda a, u, t=t: register_translation_x(a, u, t),
+            lambda t=t: (roi_translation_x(shape, t), 0))
     for t in translations:
-        add("t_y_%d" % t, clamp_translation(raw, 0, t), lambda a, u, t=t: register_translation_y(a, u, t))
+        add("t_y_%d" % t, clamp_translation(raw, 0, t), lambda a, u, t=t: register_translation_y(a, u, t),
+            lambda t=t: (roi_translation_y(shape, t), 0))
     for d in rotations:
-        add("r_%d" % d, clamp_rotate(raw, d), lambda a, u, d=d: register_rotation(a, u, d))
+        add("r_%d" % d, clamp_rotate(raw, d), lambda a, u, d=d: register_rotation(a, u, d), lambda d=d: rotated_slot(d))
     for sg in sigmas:
         add("gn_%s" % sg, add_gaussian_noise(raw, 0.0, sg, rng))
     for f in factors:
@@ -298,7 +401,10 @@ def main(argv=None):
     ap.add_argument("--levels", type=int, default=0)
     ap.add_argument("--out", default="out", help="directory of the CSV files")
     ap.add_argument("--cli", action="store_true", help="run every image through the musica-standalone process (run_process, script.py:200-214)")
+    ap.add_argument("--device-metrics", action="store_true", help="compute MSE, SSIM and the histogram distances on the GPU (musica_sim_compare)")
     args = ap.parse_args(argv)
+    if args.cli and args.device_metrics:
+        ap.error("--device-metrics scores the in-process library's device output: it cannot be combined with --cli")
     if args.raw:
         from .processing import read_raw
         raw = read_raw(args.raw, args.size)
@@ -307,7 +413,7 @@ def main(argv=None):
         from .phantom import phantom
         raw = phantom(args.size, args.phantom_seed, noise=4.0)
         name = "phantom_%d_seed%d" % (args.size, args.phantom_seed)
-    runner = Runner(args.size, args.levels, use_cli=args.cli)
+    runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics)
     rows = run_study(raw, runner, rng=np.random.default_rng(0))
     runner.close()
     write_study_csvs(rows, args.out, name, mean_cnr=not args.cli)

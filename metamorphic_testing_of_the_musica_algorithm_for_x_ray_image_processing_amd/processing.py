@@ -111,6 +111,29 @@ class Stats(C.Structure):
                [float(self.grad_max_bin), self.mean_cnr, self.t0, self.ta, self.t1, float(self.grad_max_value)]
 
 
+SIM_SLOTS = 8               # MUSICA_SIM_SLOTS
+SIM_MAX_QUERIES = 64        # MUSICA_SIM_MAX_QUERIES
+SIM_METRICS = ("mse", "ssim", "hist_intersection", "hist_distance", "hist_bhattacharyya")   # harness.similarities' keys
+
+
+class SimQuery(C.Structure):
+    """musica_sim_query: image `image_index`'s output at (ax, ay) against reference slot `slot` at (bx, by), w x h output pixels."""
+    _fields_ = [(n, C.c_uint32) for n in ("image_index", "slot", "ax", "ay", "bx", "by", "w", "h")]
+
+
+class SimResult(C.Structure):
+    _fields_ = [(n, C.c_double) for n in SIM_METRICS] + \
+               [("sq_diff_sum", C.c_uint64), ("pixels", C.c_uint64), ("bins_a", C.c_uint32 * 256), ("bins_b", C.c_uint32 * 256),
+                ("min_a", C.c_uint32), ("max_a", C.c_uint32), ("min_b", C.c_uint32), ("max_b", C.c_uint32)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n in SIM_METRICS}
+        d.update(sq_diff_sum=int(self.sq_diff_sum), pixels=int(self.pixels),
+                 bins_a=np.ctypeslib.as_array(self.bins_a).astype(np.int64), bins_b=np.ctypeslib.as_array(self.bins_b).astype(np.int64),
+                 min_a=int(self.min_a), max_a=int(self.max_a), min_b=int(self.min_b), max_b=int(self.max_b))
+        return d
+
+
 # Every symbol include/musica.h declares: (restype, argtypes). tests/test_abi.py checks the
 # shared object exports exactly these.
 _VP = C.c_void_p
@@ -190,6 +213,9 @@ ABI = {
     "musica_get_tunables": (C.c_int, [_VP, C.POINTER(Tunables)]),
     "musica_pipeline_create_ex": (_VP, [C.POINTER(Params), C.c_uint32, C.POINTER(Tunables)]),
     "musica_device_count": (C.c_int, []),
+    "musica_sim_capture": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
+    "musica_sim_set_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
+    "musica_sim_compare": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimResult)]),
 }
 
 _lib = None
@@ -479,6 +505,28 @@ class MusicaProcessing:
     def fuses_reduce_band(self):
         """True when level 0's reduce and band kernels are one launch (profile family `reduce_l0` covers both)."""
         return self._lib.musica_fuses_reduce_band(self._h) == 1
+
+    # ---- similarity metrics of the metamorphic study (musica_sim_*) ---------------------------
+    def sim_capture(self, slot, image_index=0):
+        """The current 8-bit output of `image_index` into reference slot `slot` (on the device)."""
+        self._ok(self._lib.musica_sim_capture(self._h, int(slot), int(image_index)), "musica_sim_capture")
+
+    def sim_set_reference(self, slot, pixels):
+        """(N - 20, N - 20) uint8 into reference slot `slot`."""
+        n = self.imageSize - 2 * OUT_MARGIN
+        a = np.ascontiguousarray(pixels, dtype=np.uint8)
+        if a.shape != (n, n):
+            raise ValueError("expected a %d x %d uint8 plane, got %r" % (n, n, a.shape))
+        self._ok(self._lib.musica_sim_set_reference(self._h, int(slot), a.ctypes.data_as(_U8P)), "musica_sim_set_reference")
+
+    def sim_compare(self, queries):
+        """queries: (image_index, slot, ax, ay, bx, by, w, h) tuples (or SimQuery), all in one launch. Returns one dict per query:
+        harness.similarities()' five numbers plus the exact sq_diff_sum, pixels, bins_a / bins_b (== np.histogram(..., bins=256)[0])
+        and the min / max of each side."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimResult * max(len(qs), 1))()
+        self._ok(self._lib.musica_sim_compare(self._h, len(qs), arr, res), "musica_sim_compare")
+        return [res[i].as_dict() for i in range(len(qs))]
 
     # ---- profiling ----------------------------------------------------------------------
     def profile_enable(self, which=True):
