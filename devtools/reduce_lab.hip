@@ -259,7 +259,7 @@ static void l_lds(hipStream_t st, const float* in, float* out, int S) {
 template <int RPW>
 static void l_prod(hipStream_t st, const float* in, float* out, int S) {
     LevelDesc li{S, S, (size_t)S * S}, lo{S / 2, S / 2, (size_t)(S / 2) * (S / 2)};
-    launch_reduce(st, in, li, out, lo, 1, false, 4);   // the production kernel (k_reduce_dma); RPW is unused since round 3
+    launch_reduce(st, in, li, out, lo, 1, false, 4, 1, 1);   // the production kernel (k_reduce_dma); RPW is unused since round 3
 }
 static void l_copy41(hipStream_t st, const float* in, float* out, int S) { launch_copy41(st, in, out, S); }
 static void l_copy41nt(hipStream_t st, const float* in, float* out, int S) {

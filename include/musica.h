@@ -208,6 +208,12 @@ int musica_fuses_reduce_band(const musica_ctx* ctx);
  * images on demand, bit-identical); chosen per workload by musica_create, MUSICA_SDEV_IN_EXPAND=0|1 overrides. bench.py prices
  * the launches accordingly. */
 int musica_fuses_sdev(const musica_ctx* ctx);
+/* How many paired launches (k_rb_sdev: the sdev + noise-histogram pass of level i and the smooth + downsample and band-pass launch of
+ * level i + 1 as one launch, for i = 0, 1, ..) one whole step of this context runs; 0 when its steps run no pair (two streams, the
+ * generic kernels, MUSICA_FLAG_REFERENCE_ORDER, pairing off: musica_create chooses it per workload, MUSICA_PAIR_RB_SDEV=0|1
+ * overrides) or when no level qualifies (levels i and i + 1 need sides that are multiples of 8, and level i + 1 must lie above the
+ * one-launch tail of small levels). Returns 0 for a NULL context. */
+int musica_get_paired_levels(const musica_ctx* ctx);
 uint32_t musica_get_level_size(const musica_ctx* ctx, uint32_t level);
 /* How this context dispatches a step (chosen by musica_create from the batch, the image side, the depth of the pyramid and the
  * flags): *streams = 1 (the reference's one in-order queue), 2 (the analysis launches on a second stream

@@ -685,18 +685,18 @@ void launch_sqrt(hipStream_t st, const uint16_t* px, float* out, const LevelDesc
 }
 
 void launch_sdev_hist(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov,
-                      int batch, int rows_per_wave) {
+                      int batch, int rows_per_wave, int swz) {
     const int strips = (l.S + kStripCols - 1) / kStripCols;
     if (rows_per_wave <= 0) {   // one 16-row run per workgroup (k_sdev_hist_run)
         const dim3 grid(strips, (l.S + kHistArea - 1) / kHistArea, batch);
-        if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_run<true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, xcd_swizzle_on());
-        else hipLaunchKernelGGL((k_sdev_hist_run<false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, xcd_swizzle_on());
+        if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_run<true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, swz);
+        else hipLaunchKernelGGL((k_sdev_hist_run<false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, swz);
         return;
     }
     const int segs = (l.S + rows_per_wave - 1) / rows_per_wave;
     const dim3 grid(strips, (segs + kWavesPerBlock - 1) / kWavesPerBlock, batch);
-    if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_pf<true, true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, rows_per_wave, xcd_swizzle_on());
-    else hipLaunchKernelGGL((k_sdev_hist_pf<true, false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, rows_per_wave, xcd_swizzle_on());
+    if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_pf<true, true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, rows_per_wave, swz);
+    else hipLaunchKernelGGL((k_sdev_hist_pf<true, false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, rows_per_wave, swz);
 }
 
 void launch_sdev_hist_runs(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
@@ -720,7 +720,7 @@ void launch_sdev_hist_runs(hipStream_t st, int n, const float* const* band, floa
 }
 
 void launch_sdev_hist_levels(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
-                             const int* rows, size_t hist_stride, int cov, int batch) {
+                             const int* rows, size_t hist_stride, int cov, int batch, int swz) {
     SdevRunLevels a;
     a.n = n;
     int first = 0;
@@ -736,19 +736,19 @@ void launch_sdev_hist_levels(hipStream_t st, int n, const float* const* band, fl
         a8 = a8 && (l.S & 7) == 0;
     }
     for (int k = n; k < kSdevRunLevelsMax; k++) a.l[k] = a.l[0];
-    a.swz = xcd_swizzle_on();
+    a.swz = swz;
     const dim3 grid(first, 1, batch);
     if (a8) hipLaunchKernelGGL((k_sdev_hist_levels<true>), grid, dim3(kBlockThreads), 0, st, a, hist_stride, cov);
     else hipLaunchKernelGGL((k_sdev_hist_levels<false>), grid, dim3(kBlockThreads), 0, st, a, hist_stride, cov);
 }
 
 // sdev alone (no histogram): the stored image of a level whose hot path does not store it, for getters / dumps / the stage entry points
-void launch_sdev_only(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch) {
+void launch_sdev_only(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch, int swz) {
     const int strips = (l.S + kStripCols - 1) / kStripCols, rows = 16;
     const int segs = (l.S + rows - 1) / rows;
     const dim3 grid(strips, (segs + kWavesPerBlock - 1) / kWavesPerBlock, batch);
-    if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_pf<false, true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, (uint32_t*)nullptr, (size_t)0, 0, rows, xcd_swizzle_on());
-    else hipLaunchKernelGGL((k_sdev_hist_pf<false, false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, (uint32_t*)nullptr, (size_t)0, 0, rows, xcd_swizzle_on());
+    if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_pf<false, true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, (uint32_t*)nullptr, (size_t)0, 0, rows, swz);
+    else hipLaunchKernelGGL((k_sdev_hist_pf<false, false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, (uint32_t*)nullptr, (size_t)0, 0, rows, swz);
 }
 
 void launch_sdev_literal(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch) {

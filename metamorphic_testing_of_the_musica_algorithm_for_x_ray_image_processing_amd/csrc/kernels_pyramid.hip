@@ -1273,7 +1273,6 @@ void launch_rb_sdev(hipStream_t st, RbSdevArgs a, const LevelDesc& ls, int batch
     a.rb_strips = (a.S + kStripCols - 1) / kStripCols;
     const int segs = (a.Sc + a.rows_rb - 1) / a.rows_rb;
     a.rb_blocks = (segs + kWavesPerBlock - 1) / kWavesPerBlock;
-    a.swz = xcd_swizzle_on();
     const int total = a.rb_first + ((a.rb_strips * a.rb_blocks + 7) & ~7);
     hipLaunchKernelGGL(k_rb_sdev, dim3(total, 1, batch), dim3(kBlockThreads), 0, st, a);
 }
@@ -1294,34 +1293,27 @@ void launch_tiny_tail(hipStream_t st, const TailArgs& a, int batch) {
     hipLaunchKernelGGL(k_tiny_tail, dim3(batch), dim3(1024), 0, st, a);
 }
 
-int xcd_swizzle_on() {
-    static const int on = getenv("MUSICA_XCD_SWIZZLE") ? atoi(getenv("MUSICA_XCD_SWIZZLE")) : 1;
-    return on;
-}
-
-static int region_map_on() {   // MUSICA_XCD_REGIONS=0: the round-3 tile mapping of the metric kernel
-    static const int on = getenv("MUSICA_XCD_REGIONS") ? atoi(getenv("MUSICA_XCD_REGIONS")) : 1;
-    return on;
-}
 static inline dim3 generic_grid(int S, int batch) { return dim3((S + 31) / 32, (S + 7) / 8, batch); }
 static const dim3 kGenericBlock(32, 8, 1);
 
 static inline bool fast_ok(int S) { return S >= 8 && (S % 8) == 0; }
 
 // tag: launch site (see k_reduce_dma)
-void launch_reduce(hipStream_t st, const float* in, const LevelDesc& li, float* out, const LevelDesc& lo, int batch, bool force_generic, int tag, int ref) {
+// regions = 0 (MUSICA_XCD_REGIONS=0): the round-3 tile mapping of the metric kernel
+void launch_reduce(hipStream_t st, const float* in, const LevelDesc& li, float* out, const LevelDesc& lo, int batch, bool force_generic, int tag,
+                   int swz_on, int regions, int ref) {
     if (fast_ok(li.S) && !force_generic) {
         const int strips = (li.S + kStripCols - 1) / kStripCols;
         const dim3 grid(strips, (lo.S + kDmaRows - 1) / kDmaRows, batch);
         // 8 k strips: workgroup id % 8 == strip % 8 already gives every strip one XCD, tile above tile in dispatch order; otherwise
         // the XCD-aware mapping does (2048^2: 6.0 -> 5.05 us; it costs 1.5 us at 4096^2 where the plain mapping has that property).
         // Round 4: where the geometry allows, 2-D regions per XCD (xcd_region_tile): horizontal neighbours share an L2 as well.
-        int swz = (strips % 8) != 0 ? xcd_swizzle_on() : 0;
+        int swz = (strips % 8) != 0 ? swz_on : 0;
         {
             const unsigned gx = (unsigned)strips, gy = grid.y;
             const bool pow2 = gx >= 2 && (gx & (gx - 1)) == 0 && gx <= 32;
             const unsigned w = region_width(gx), across = pow2 ? gx / w : 1u, v = pow2 ? 8u / across : 1u;
-            if (pow2 && across * v == 8u && gy % v == 0 && xcd_swizzle_on() && region_map_on()) swz = 2;
+            if (pow2 && across * v == 8u && gy % v == 0 && swz_on && regions) swz = 2;
         }
         auto* kern = tag == 0 ? k_reduce_dma<0> : tag == 1 ? k_reduce_dma<1> : tag == 2 ? k_reduce_dma<2> : tag == 4 ? k_reduce_dma<4> : k_reduce_dma<5>;
         hipLaunchKernelGGL(kern, grid, dim3(kBlockThreads), 0, st, in, out, li.S, li.pitch, li.plane, lo.S, lo.pitch, lo.plane, swz);
@@ -1332,14 +1324,14 @@ void launch_reduce(hipStream_t st, const float* in, const LevelDesc& li, float* 
 }
 
 void launch_reduce_band_u16(hipStream_t st, const uint16_t* px, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch,
-                            int rows_per_wave, const uint32_t* minmax, int min_chain_exact, uint16_t* le090) {
+                            int rows_per_wave, const uint32_t* minmax, int min_chain_exact, uint16_t* le090, int swz) {
     hipLaunchKernelGGL(k_reduce_band<true>, stream_grid(lf.S, lc.S, rows_per_wave, batch), dim3(kBlockThreads), 0, st, (const void*)px, down, band, lf.S,
-                       lf.pitch, lf.plane, lc.S, lc.pitch, lc.plane, rows_per_wave, minmax, min_chain_exact, le090, xcd_swizzle_on());
+                       lf.pitch, lf.plane, lc.S, lc.pitch, lc.plane, rows_per_wave, minmax, min_chain_exact, le090, swz);
 }
 // levels >= 1 (f32 fine image); the side must be a multiple of 8 and at least 16 (the caller checks)
-void launch_reduce_band(hipStream_t st, const float* fine, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch, int rows_per_wave) {
+void launch_reduce_band(hipStream_t st, const float* fine, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch, int rows_per_wave, int swz) {
     hipLaunchKernelGGL(k_reduce_band<false>, stream_grid(lf.S, lc.S, rows_per_wave, batch), dim3(kBlockThreads), 0, st, (const void*)fine, down, band, lf.S,
-                       lf.pitch, lf.plane, lc.S, lc.pitch, lc.plane, rows_per_wave, (const uint32_t*)nullptr, 0, (uint16_t*)nullptr, xcd_swizzle_on());
+                       lf.pitch, lf.plane, lc.S, lc.pitch, lc.plane, rows_per_wave, (const uint32_t*)nullptr, 0, (uint16_t*)nullptr, swz);
 }
 // band of a level that does not take the fused reduce + band march (sides that are not a multiple of 8, generic / literal-order contexts)
 void launch_band(hipStream_t st, const float* fine, const float* coarse, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch, int ref) {

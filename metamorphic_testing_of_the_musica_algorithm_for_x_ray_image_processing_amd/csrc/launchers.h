@@ -61,12 +61,17 @@ struct GradArgs {
 };
 
 // kernels_pyramid.hip
+// swz: the XCD-aware workgroup -> tile mapping of the marching kernels (kernels_common.h xcd_tile, role_tile), 0 or 1; regions: the
+// metric kernel's 2-D regions per XCD (xcd_region_tile) where its geometry allows, 0 or 1. A context reads both once, in create_impl
+// (MUSICA_XCD_SWIZZLE, MUSICA_XCD_REGIONS), and hands them to every launch (ExpandArgs::swz, RbSdevArgs::swz likewise).
 // ref != 0 (generic kernels only): the shaders' literal 25-tap accumulation order (MUSICA_FLAG_REFERENCE_ORDER)
-void launch_reduce(hipStream_t st, const float* in, const LevelDesc& li, float* out, const LevelDesc& lo, int batch, bool force_generic, int tag, int ref = 0);
+void launch_reduce(hipStream_t st, const float* in, const LevelDesc& li, float* out, const LevelDesc& lo, int batch, bool force_generic, int tag,
+                   int swz, int regions, int ref = 0);
 void launch_band(hipStream_t st, const float* fine, const float* coarse, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch, int ref = 0);
 void launch_reduce_band_u16(hipStream_t st, const uint16_t* px, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch,
-                            int rows_per_wave, const uint32_t* minmax, int min_chain_exact, uint16_t* le090);
-void launch_reduce_band(hipStream_t st, const float* fine, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch, int rows_per_wave);
+                            int rows_per_wave, const uint32_t* minmax, int min_chain_exact, uint16_t* le090, int swz);
+void launch_reduce_band(hipStream_t st, const float* fine, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch, int rows_per_wave,
+                        int swz);
 void launch_lowpass(hipStream_t st, const float* coarse, float* low, const LevelDesc& lf, const LevelDesc& lc, int batch, int ref = 0);
 void launch_expand(hipStream_t st, const ExpandArgs& a, int gain_mode, bool nr, int batch, bool force_generic);
 // reduce + band of level i + 1 AND the sdev + noise-histogram pass of level i in one launch (both read what the reduce + band launch of level i wrote
@@ -93,18 +98,18 @@ void launch_minmax(hipStream_t st, const uint16_t* px, int N, uint32_t* minmax, 
                    uint32_t* clahe_hist = nullptr);
 void launch_normalize(hipStream_t st, const uint16_t* px, float* out, const LevelDesc& l0, const uint32_t* minmax, int min_chain_exact, int batch);
 void launch_sqrt(hipStream_t st, const uint16_t* px, float* out, const LevelDesc& l0, int batch);
-void launch_sdev_hist(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov, int batch, int rows_per_wave);
+void launch_sdev_hist(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov, int batch, int rows_per_wave, int swz);
 // the 16-row-run form of launch_sdev_hist for n <= kSdevRunLevelsMax levels in ONE launch (hist[k]: image 0's histogram of level k)
 void launch_sdev_hist_runs(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
                            size_t hist_stride, int cov, int batch);
 // every level's sdev + noise-histogram pass in ONE launch, each level in its own form (rows[k] > 0: the march with that many rows per
 // wavefront, 0: one 16-row run per workgroup); sdev[k] == nullptr: histogram only
 void launch_sdev_hist_levels(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
-                             const int* rows, size_t hist_stride, int cov, int batch);
+                             const int* rows, size_t hist_stride, int cov, int batch, int swz);
 void launch_noise_hist_only(hipStream_t st, const float* sdev, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov, int batch);
 // img_sdev.comp:10-35 with the 25 squares accumulated in the shader's order (one thread per texel; MUSICA_FLAG_REFERENCE_ORDER)
 void launch_sdev_literal(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch);
-void launch_sdev_only(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch);   // the fast order's sdev image alone (no histogram)
+void launch_sdev_only(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch, int swz);   // the fast order's sdev image alone (no histogram)
 void launch_noise_curves(hipStream_t st, const uint32_t* hist, size_t hist_stride, musica_hist_max_point* maxpts, DevCurve* curves, const musica_contrast_params* cparams, int levels, int batch, DevCurveLut* luts, const uint32_t* minmax, int min_chain_exact, int* thr090, int lev0 = 0, int nlev = 0);
 void launch_curves_cnr(hipStream_t st, const uint32_t* hist, size_t hist_stride, musica_hist_max_point* maxpts, DevCurve* curves,
                        const musica_contrast_params* cparams, int levels, int batch, DevCurveLut* luts, const float* sdev, float* cnr,
@@ -115,8 +120,6 @@ void launch_selftest_exact_math(hipStream_t st, unsigned long long* d_bad4);
 void launch_render_noise_hist(hipStream_t st, const uint32_t* hist, const musica_hist_max_point* maxpt, uint32_t* out);
 void launch_render_grad_hist(hipStream_t st, const uint32_t* hist, const musica_hist_max_point* maxpt, const DevCurve* curve, uint32_t* out);
 constexpr int kStatsMaxBlocks = 64;
-// XCD-aware workgroup -> tile mapping of the marching kernels (kernels_common.h xcd_tile); MUSICA_XCD_SWIZZLE=0 turns it off
-int xcd_swizzle_on();
 void launch_stats(hipStream_t st, const float* cnr, const LevelDesc& l3, const uint32_t* minmax, int min_chain_exact,
                   const musica_hist_max_point* noise_max, int levels, const musica_hist_max_point* grad_max, const DevCurve* gcurve,
                   musica_stats* out, uint32_t image_id_base, uint32_t image_id_stride, int batch, double* partial);

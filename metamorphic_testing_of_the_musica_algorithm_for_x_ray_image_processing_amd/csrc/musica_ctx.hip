@@ -141,6 +141,8 @@ struct musica_ctx : DeviceBuffers {
     bool pair_rb_sdev;         // the one-stream script pairs the sdev pass of level i with reduce + band of level i + 1 in one launch (k_rb_sdev); MUSICA_PAIR_RB_SDEV
     bool sdev_one_launch;      // the sdev + noise-histogram passes of levels 0 .. 3 as ONE launch (k_sdev_hist_levels); MUSICA_SDEV_ONE_LAUNCH=0: one launch per marching level + one for the runs
     int rows_rb[MUSICA_MAX_LEVELS];   // its coarse rows per wavefront
+    int xcd_swizzle;           // XCD-aware workgroup -> tile mapping of the marching kernels (launchers.h); MUSICA_XCD_SWIZZLE=0: the plain mapping
+    int xcd_regions;           // the metric kernel's 2-D regions per XCD where its geometry allows; MUSICA_XCD_REGIONS=0: the round-3 mapping
     uint8_t* d_out8 = nullptr;   // saveOutImage's cropped 8-bit pixels of one image (device) and their pinned host copy, allocated on first use
     uint8_t* h_out8 = nullptr;
     uint8_t* h_bmp = nullptr;    // saveOutImage's whole file image in page-locked memory: 2 bytes of padding, the 54-byte header, then the pixel array the
@@ -301,6 +303,8 @@ static musica_nr_params host_nr_params(uint32_t i, const musica_tunables& t) {
 
 static void autotune(musica_ctx* c);
 static bool rb_level(const musica_ctx* c, int i);
+static int tail_first(const musica_ctx* c);
+static int rb_sdev_pairs(const musica_ctx* c, int T);
 static void copy_rows(musica_ctx* dst, const musica_ctx* src) {
     if (dst == src) return;
     memcpy(dst->rows_expand, src->rows_expand, sizeof(src->rows_expand));
@@ -514,6 +518,8 @@ static musica_ctx* create_impl(const musica_params* params, const musica_tunable
     c->clahe_one_apply = env_int("MUSICA_CLAHE_ONE_APPLY", 1) != 0;
     c->tiny_tail = env_int("MUSICA_TINY_TAIL", 1) != 0;
     c->grad_one_launch = env_int("MUSICA_GRAD_ONE_LAUNCH", 1) != 0;
+    c->xcd_swizzle = env_int("MUSICA_XCD_SWIZZLE", 1) != 0 ? 1 : 0;
+    c->xcd_regions = env_int("MUSICA_XCD_REGIONS", 1) != 0 ? 1 : 0;
     {
         // sdev computed inside the expand launches of levels 0 .. 2 (k_expand_fast<.., SD>) instead of stored by the sdev launch and read back:
         // 8 of a step's 48 bytes per input pixel against ~35 % more vector work in those expand launches. It pays where a step is bound by its
@@ -566,6 +572,7 @@ int musica_get_dispatch(const musica_ctx* c, int* streams, int* graph) {
 int musica_fuses_gradation_histogram(const musica_ctx* c) { return (c && c->fuse_gh && !c->generic) ? 1 : 0; }
 int musica_fuses_reduce_band(const musica_ctx* c) { return (c && rb_level(c, 0)) ? 1 : 0; }
 int musica_fuses_sdev(const musica_ctx* c) { return (c && c->sd_fused && rb_level(c, 0)) ? 1 : 0; }
+int musica_get_paired_levels(const musica_ctx* c) { return (c && c->dag == 0) ? rb_sdev_pairs(c, tail_first(c)) : 0; }
 uint32_t musica_get_level_size(const musica_ctx* c, uint32_t level) { return (c && (int)level <= c->L) ? (uint32_t)c->lv[level].S : 0; }
 
 }  // extern "C"
@@ -633,14 +640,15 @@ static void ensure_normalized(musica_ctx* c) {
 static bool rb_level(const musica_ctx* c, int i) { return !c->generic && c->lv[i].S >= 8 && (c->lv[i].S % 8) == 0; }
 static void run_reduce_band(musica_ctx* c, int i, int rows) {
     if (i == 0)
-        launch_reduce_band_u16(c->cur, c->cur_input, c->d_down[0], c->d_band[0], c->lv[0], c->lv[1], c->B, rows, c->d_minmax, c->min_chain_exact, c->d_le090);
+        launch_reduce_band_u16(c->cur, c->cur_input, c->d_down[0], c->d_band[0], c->lv[0], c->lv[1], c->B, rows, c->d_minmax, c->min_chain_exact, c->d_le090,
+                               c->xcd_swizzle);
     else
-        launch_reduce_band(c->cur, level_input(c, i), c->d_down[i], c->d_band[i], c->lv[i], c->lv[i + 1], c->B, rows);
+        launch_reduce_band(c->cur, level_input(c, i), c->d_down[i], c->d_band[i], c->lv[i], c->lv[i + 1], c->B, rows, c->xcd_swizzle);
 }
 // reduce and band of level i, as one launch where that form applies, else the one-thread-per-texel kernels
 static void run_reduce_and_band(musica_ctx* c, int i) {
     if (rb_level(c, i)) { Span sp(c, i == 0 ? MUSICA_KERNEL_REDUCE_L0 : MUSICA_KERNEL_REDUCE_REST); run_reduce_band(c, i, c->rows_rb[i]); return; }
-    { Span sp(c, i == 0 ? MUSICA_KERNEL_REDUCE_L0 : MUSICA_KERNEL_REDUCE_REST); launch_reduce(c->cur, level_input(c, i), c->lv[i], c->d_down[i], c->lv[i + 1], c->B, true, i == 0 ? 0 : 1, c->ref_order); }
+    { Span sp(c, i == 0 ? MUSICA_KERNEL_REDUCE_L0 : MUSICA_KERNEL_REDUCE_REST); launch_reduce(c->cur, level_input(c, i), c->lv[i], c->d_down[i], c->lv[i + 1], c->B, true, i == 0 ? 0 : 1, c->xcd_swizzle, c->xcd_regions, c->ref_order); }
     { Span sp(c, i == 0 ? MUSICA_KERNEL_BAND_L0 : MUSICA_KERNEL_BAND_REST); launch_band(c->cur, level_input(c, i), c->d_down[i], c->d_band[i], c->lv[i], c->lv[i + 1], c->B, c->ref_order); }
 }
 // level i's sdev image is neither stored nor read by this step: its expand launch computes it (levels below the cnr level whose side
@@ -653,13 +661,13 @@ static void run_sdev_level(musica_ctx* c, int i, int rows) {
         return;
     }
     launch_sdev_hist(c->cur, c->d_band[i], sd_level(c, i) ? nullptr : c->d_sdev[i], c->lv[i], c->d_noise_hist + (size_t)i * MUSICA_NOISE_BINS,
-                     (size_t)4 * MUSICA_NOISE_BINS, c->hist_cov, c->B, rows);
+                     (size_t)4 * MUSICA_NOISE_BINS, c->hist_cov, c->B, rows, c->xcd_swizzle);
 }
 // The stored sdev images of levels whose hot path does not store them (getters, dumps, stage entry points, the generic kernels).
 static void ensure_sdev(musica_ctx* c) {
     if (c->sdev_stored) return;
     for (int i = 0; i < MUSICA_CNR_LEVEL && i < c->L; i++)
-        if (rb_level(c, i)) launch_sdev_only(c->stream, c->d_band[i], c->d_sdev[i], c->lv[i], c->B);
+        if (rb_level(c, i)) launch_sdev_only(c->stream, c->d_band[i], c->d_sdev[i], c->lv[i], c->B, c->xcd_swizzle);
     c->sdev_stored = true;
 }
 
@@ -736,7 +744,7 @@ static void run_sdev_all_levels(musica_ctx* c, int first = 0) {
         hist[n] = c->d_noise_hist + (size_t)i * MUSICA_NOISE_BINS;
         rows[n] = c->rows_sdev[i] > 0 ? c->rows_sdev[i] : 0;
     }
-    launch_sdev_hist_levels(c->cur, n, band, sdev, lv, hist, rows, (size_t)4 * MUSICA_NOISE_BINS, c->hist_cov, c->B);
+    launch_sdev_hist_levels(c->cur, n, band, sdev, lv, hist, rows, (size_t)4 * MUSICA_NOISE_BINS, c->hist_cov, c->B, c->xcd_swizzle);
 }
 static void enqueue_analysis(musica_ctx* c, hipStream_t st = nullptr) {
     if (!st) st = c->stream;
@@ -786,7 +794,7 @@ static ExpandArgs expand_args(musica_ctx* c, int lvl, float* dst) {
     a.lowCnr = q.lowCnr; a.lowFactor = q.lowFactor; a.highCnr = q.highCnr; a.highFactor = q.highFactor;
     a.rows_per_wave = c->rows_expand[lvl];
     a.raw = nullptr; a.ghist = nullptr; a.gzero = nullptr; a.thr090 = nullptr; a.le090 = nullptr; a.chist = nullptr;
-    a.swz = xcd_swizzle_on();
+    a.swz = c->xcd_swizzle;
     a.ref_order = c->ref_order;
     return a;
 }
@@ -878,8 +886,18 @@ static void run_rb_sdev_pair(musica_ctx* c, int i) {
     a.sl.band = c->d_band[i]; a.sl.sdev = sd_level(c, i) ? nullptr : c->d_sdev[i];
     a.sl.hist = c->d_noise_hist + (size_t)i * MUSICA_NOISE_BINS;
     a.sl.rows = c->rows_sdev[i] > 0 ? c->rows_sdev[i] : 0;
-    a.hist_stride = (size_t)4 * MUSICA_NOISE_BINS; a.cov = c->hist_cov;
+    a.hist_stride = (size_t)4 * MUSICA_NOISE_BINS; a.cov = c->hist_cov; a.swz = c->xcd_swizzle;
     launch_rb_sdev(c->cur, a, c->lv[i], c->B);
+}
+// Whether the one-stream script pairs at all, and how many pairs it launches: level i's sdev pass with reduce + band of level i + 1 for
+// i = 0, 1, .. while both levels take the streaming reduce + band launch and level i + 1 lies above the tiny tail (T: tail_first).
+// enqueue_linear_paired runs exactly these pairs and musica_get_paired_levels reports them.
+static bool pairs_rb_sdev(const musica_ctx* c) { return c->pair_rb_sdev && !c->ref_order && !c->generic && !c->tuning; }
+static int rb_sdev_pairs(const musica_ctx* c, int T) {
+    if (!pairs_rb_sdev(c)) return 0;
+    int n = 0;
+    while (n <= MUSICA_CNR_LEVEL && n + 1 < T && rb_level(c, n) && rb_level(c, n + 1)) n++;
+    return n;
 }
 // One in-order stream with the pairs: minmax RB0 [RB1 | S0] [RB2 | S1] [RB3 | S2] [RB4 | S3] RB5 .. [tail] curves+cnr E .. gradation — the pyramid's
 // dependent chain of ever smaller launches in the shadow of the sdev passes instead of in front of them.
@@ -888,11 +906,11 @@ static void enqueue_linear_paired(musica_ctx* c) {
     enqueue_norm(c, true);
     const int T = tail_first(c);
     run_reduce_and_band(c, 0);
+    const int pairs = rb_sdev_pairs(c, T);
     int i = 0;   // the first level whose sdev pass is still to run
-    while (i <= MUSICA_CNR_LEVEL && i + 1 < T && rb_level(c, i) && rb_level(c, i + 1)) {
+    for (; i < pairs; i++) {
         Span sp(c, MUSICA_KERNEL_SDEV_HIST);
         run_rb_sdev_pair(c, i);
-        i++;
     }
     for (int r = i + 1; r < T; r++) run_reduce_and_band(c, r);
     if (T < c->L) run_tiny_tail(c, T);
@@ -906,7 +924,7 @@ static void enqueue_linear_paired(musica_ctx* c) {
     enqueue_gradation(c, true);
 }
 static void enqueue_linear(musica_ctx* c) {
-    if (c->pair_rb_sdev && !c->ref_order && !c->generic && !c->tuning) { enqueue_linear_paired(c); return; }
+    if (pairs_rb_sdev(c)) { enqueue_linear_paired(c); return; }
     c->cur = c->stream;
     enqueue_norm(c, true);   // with the clears of :2153-2162
     const int T = enqueue_reduce_from(c, 0);
@@ -1448,7 +1466,9 @@ int musica_debug_set_image(musica_ctx* c, uint32_t idx, musica_image_kind kind, 
     const LevelDesc* d = nullptr;
     float* plane = kind == MUSICA_IMG_CLAHE_GRADED ? nullptr : stored_plane(c, idx, kind, level, &d);   // the CLAHE output is never set
     if (!plane) return fail("musica_debug_set_image: kind %d is not stored on the hot path", (int)kind);
-    if (kind == MUSICA_IMG_SDEV) ensure_sdev(c);   // the other levels' stored images first: a later getter must not overwrite what the caller sets here
+    // the stored sdev images first (every level: the step's, computed from the step's band images): a later getter must not overwrite
+    // an sdev image the caller sets here, nor rebuild the step's sdev images from a band image the caller sets here
+    if (kind == MUSICA_IMG_SDEV || kind == MUSICA_IMG_BANDPASS) ensure_sdev(c);
     return upload_plane(c, plane, *d, src);
 }
 
@@ -1895,7 +1915,7 @@ int musica_k_reduce(musica_ctx* c, const float* d_in, uint32_t side, uint32_t in
     CHECK_CTX(c);
     LevelDesc li, lo;
     if (!reduce_descs(side, in_pitch, out_pitch, &li, &lo)) return 0;
-    launch_reduce(c->stream, d_in, li, d_out, lo, (int)batch, c->generic, 2);
+    launch_reduce(c->stream, d_in, li, d_out, lo, (int)batch, c->generic, 2, c->xcd_swizzle, c->xcd_regions);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("kernel launch failed: %s", hipGetErrorString(e));
     return 1;
@@ -1929,7 +1949,7 @@ int musica_k_reduce_timed(musica_ctx* c, const float* d_in, uint32_t side, uint3
     HIP_OK(hipEventCreate(&a));
     HIP_OK(hipEventCreate(&b));
     HIP_OK(hipEventRecord(a, c->stream));
-    for (uint32_t i = 0; i < iters; i++) launch_reduce(c->stream, d_in, li, d_out, lo, (int)batch, c->generic, 2);
+    for (uint32_t i = 0; i < iters; i++) launch_reduce(c->stream, d_in, li, d_out, lo, (int)batch, c->generic, 2, c->xcd_swizzle, c->xcd_regions);
     HIP_OK(hipEventRecord(b, c->stream));
     HIP_OK(hipEventSynchronize(b));
     float ms = 0.f;
@@ -1952,7 +1972,7 @@ int musica_k_reduce_timed_rot(musica_ctx* c, const float* d_in, uint32_t side, u
     HIP_OK(hipEventCreate(&b));
     HIP_OK(hipEventRecord(a, c->stream));
     for (uint32_t i = 0; i < iters; i++)
-        launch_reduce(c->stream, d_in + (size_t)(i % nbuf) * li.plane, li, d_out + (size_t)(i % nbuf) * lo.plane, lo, 1, c->generic, side <= 4096 ? 4 : 5);
+        launch_reduce(c->stream, d_in + (size_t)(i % nbuf) * li.plane, li, d_out + (size_t)(i % nbuf) * lo.plane, lo, 1, c->generic, side <= 4096 ? 4 : 5, c->xcd_swizzle, c->xcd_regions);
     HIP_OK(hipEventRecord(b, c->stream));
     HIP_OK(hipEventSynchronize(b));
     float ms = 0.f;

@@ -148,6 +148,7 @@ ABI = {
     "musica_fuses_gradation_histogram": (C.c_int, [_VP]),
     "musica_fuses_reduce_band": (C.c_int, [_VP]),
     "musica_fuses_sdev": (C.c_int, [_VP]),
+    "musica_get_paired_levels": (C.c_int, [_VP]),
     "musica_get_dispatch": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "musica_execute": (C.c_int, [_VP, _U16P]),
     "musica_execute_device": (C.c_int, [_VP, _VP]),
@@ -501,6 +502,10 @@ class MusicaProcessing:
     def fuses_sdev(self):
         """True when the expand launches of levels 0 .. 2 compute sdev themselves and the sdev launches of those levels store nothing."""
         return self._lib.musica_fuses_sdev(self._h) == 1
+
+    def paired_levels(self):
+        """How many k_rb_sdev launches (the sdev pass of level i paired with reduce + band of level i + 1) one whole step runs; 0: no pair."""
+        return self._lib.musica_get_paired_levels(self._h)
 
     def fuses_reduce_band(self):
         """True when level 0's reduce and band kernels are one launch (profile family `reduce_l0` covers both)."""

@@ -37,6 +37,39 @@ def test_exports_every_declared_symbol():
     assert sorted(mp.ABI.keys()) == declared
 
 
+def test_launch_form_getters_take_a_null_context():
+    lib = mp.load_library()
+    for name in ("musica_fuses_gradation_histogram", "musica_fuses_reduce_band", "musica_fuses_sdev", "musica_get_paired_levels"):
+        assert name in mp.ABI
+        assert getattr(lib, name)(None) == 0, name
+
+
+def _static_environment_reads(text):
+    """`static` variables initialised from the environment (getenv / env_int) in C / C++ / HIP source, comments and strings removed."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r'"(?:\\.|[^"\\\n])*"', '""', text)
+    return re.findall(r"\bstatic\b[^;{}()]*=[^;{}]*\b(?:getenv|env_int)\s*\(", text)
+
+
+def test_no_source_caches_an_environment_knob():
+    """Every MUSICA_* knob is read when a context is created and kept on the context (create_impl). A function-local `static` initialised
+    from getenv fixes the value at the first call in the process, so a later context (a test that sets the knob, say) silently gets the
+    first one's."""
+    assert _static_environment_reads('int f() { static const int on = getenv("X") ? atoi(getenv("X")) : 1; return on; }')
+    assert _static_environment_reads("static int k =\n    env_int(\"X\", 1);")
+    assert not _static_environment_reads('static int env_int(const char* name, int dflt) { const char* v = getenv(name); return 0; }')
+    assert not _static_environment_reads('int f() { const int on = env_int("X", 1); /* static int c = getenv("Y"); */ return on; }')
+    csrc = os.path.join(os.path.dirname(pkg.__file__), "csrc")
+    bad = {}
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".h", ".cpp")):
+            found = _static_environment_reads(open(os.path.join(csrc, name)).read())
+            if found:
+                bad[name] = found
+    assert not bad, bad
+
+
 def test_struct_sizes_match_reference_layouts():
     # ContrastCurveObj 2052 B, GradCurveObj 2064 B, HistogramMaxPoint 8 B (SURVEY §8a T1-T5)
     assert ctypes.sizeof(mp.ContrastCurve) == 2052

@@ -475,7 +475,9 @@ def test_streaming_kernels_equal_generic_kernels(n, levels):
     b.cleanup()
 
 
-@pytest.mark.parametrize("side", [8, 16, 24, 64, 100, 257, 512, 520, 1024, 1032, 2048, 3080, 3, 2, 1, 5, 7, 12])
+# k_reduce_dma's three tile mappings (launch_reduce): 2, 4, 8, 16 strips of 512 columns (1024 .. 8192): 2-D regions per XCD; 3, 5, 6 strips
+# with grid rows % 8 == 0 (1536, 2560, 3072): the swizzled xcd_tile; the rest: the plain mapping
+@pytest.mark.parametrize("side", [8, 16, 24, 64, 100, 257, 512, 520, 1024, 1032, 1536, 2048, 2560, 3072, 3080, 3, 2, 1, 5, 7, 12])
 def test_metric_kernel_vs_oracle(ob, side):
     rng = np.random.default_rng(side)
     img = rng.random((2, side, side), dtype=np.float32)
@@ -490,9 +492,10 @@ def test_metric_kernel_vs_oracle(ob, side):
 
 
 @pytest.mark.parametrize("side", [4096, 8192])
-def test_metric_kernel_properties_full_size(side):
+def test_metric_kernel_properties_full_size(ob, side):
     # size-independent properties at BASELINE's 4096 x 4096 and at the 8192 x 8192 bench.py also times: a constant stays
-    # constant (sum w = 1), and the operator is linear: R(a + b) ~= R(a) + R(b)
+    # constant (sum w = 1), and the operator is linear: R(a + b) ~= R(a) + R(b); then every texel against the oracle
+    # (two images at 4096: the second image's tiles too)
     p = _proc(64, 4)
     const = np.full((1, side, side), 0.75, dtype=np.float32)
     out = p.k_reduce_host(const)
@@ -503,6 +506,12 @@ def test_metric_kernel_properties_full_size(side):
     b = rng.random((1, side, side), dtype=np.float32)
     ra, rb, rab = p.k_reduce_host(a), p.k_reduce_host(b), p.k_reduce_host(a + b)
     assert np.abs(rab - (ra + rb)).max() <= 1e-6
+    _same(ra[0], ob.k_downsample(ob.k_smooth(a[0], ob.ORDER_FAST)), "smooth+downsample side %d" % side)
+    if side <= 4096:
+        ab = np.concatenate([b, a])
+        got = p.k_reduce_host(ab)
+        for k in range(2):
+            _same(got[k], ob.k_downsample(ob.k_smooth(ab[k], ob.ORDER_FAST)), "smooth+downsample side %d image %d of 2" % (side, k))
     p.cleanup()
 
 
@@ -763,12 +772,15 @@ def test_steps_in_flight_on_three_contexts_are_the_lone_contexts_steps(ob, sd, m
     context is bit-identical to the oracle after 7 overlapping steps, and the strided image ids of a rank's stats
     rows (rank + index * world) come from the stats kernel itself."""
     from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import batch as mb
-    n, levels, b, depth = 520, 5, 2, 3
+    pairs = sd.endswith("pairs")
+    # 1056 / L5: levels 1056, 528, 264 take the paired launches (sides that are multiples of 8), two pairs; at 520 level 1 (260) ends the chain before it starts
+    n, levels, b, depth = (1056 if pairs else 520), 5, 2, 3
     monkeypatch.setenv("MUSICA_SDEV_IN_EXPAND", sd[0])
-    monkeypatch.setenv("MUSICA_PAIR_RB_SDEV", "1" if sd.endswith("pairs") else "0")   # the pairs of the one-stream script (k_rb_sdev): what byte-bound pipeline contexts run
+    monkeypatch.setenv("MUSICA_PAIR_RB_SDEV", "1" if pairs else "0")   # the pairs of the one-stream script (k_rb_sdev): what byte-bound pipeline contexts run
     px = [np.stack([phantom(n, 1000 + 10 * c + k) for k in range(b)]) for c in range(depth)]
     pipe = mp.MusicaPipeline(n, levels=levels, batch=b, depth=depth)
     assert pipe.context(0).fuses_sdev() == (sd[0] == "1")
+    assert pipe.context(0).paired_levels() == (2 if pairs else 0)
     pipe.upload(px[0])
     stale = pipe.context(0)
     pipe.prime()
