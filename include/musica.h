@@ -363,6 +363,63 @@ int musica_sim_set_reference(musica_ctx* ctx, uint32_t slot, const uint8_t* pixe
  * NULL pointers, a count out of range, a slot out of range or never written, image_index >= batch, a region that leaves either
  * plane, w < 7 or h < 7. */
 int musica_sim_compare(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_result* results);
+/* Rotates reference slot `src_slot` into `dst_slot` (device to device, on the ctx stream) as ndimage.rotate(order=0, reshape=False,
+ * mode="constant", cval=0) does with the 2 x 2 `matrix` (row-major) and `offset` it computes for a plane of side N - 20
+ * (harness.rotated_reference). dst_slot != src_slot; src_slot must have been written. */
+int musica_sim_rotate_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, const double matrix[4], const double offset[2]);
+/* (N - 20)^2 bytes of reference slot `slot` to the host (synchronous); the slot must have been written. */
+int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
+
+/* ---- alterations of the metamorphic study (new, not in the reference) ---- */
+
+/* The study's alteration generators (harness.py apply_collimator, clamp_translation, clamp_rotate, add_gaussian_noise,
+ * apply_quantum_noise; test/metamorphic_test/script.py:49-141) on the device: they read a context-owned N x N u16 source plane and
+ * write one image of the resident input buffer (musica_input_device_ptr), so a study needs one upload per raw image.
+ *   NONE        the source, bit-exact.
+ *   TRANSLATE   clamp_translation(src, dx, dy), bit-exact, the 99th-percentile fill of its 2-pixel strip included.
+ *   ROTATE      clamp_rotate: the (N - 2 margin)^2 crop rotated with `matrix` / `offset` exactly as ndimage.rotate(order=0,
+ *               reshape=False, mode="constant") maps it, filled with int(np.percentile(crop, 95)); bit-exact.
+ *   COLLIMATOR  apply_collimator(src, shutter_h, shutter_v): the source inside the inclusive rectangle [shutter_v, N - shutter_v] x
+ *               [shutter_h, N - shutter_h], outside it min(k, 65535) with k ~ Poisson(v / 100).
+ *   GAUSSIAN    add_gaussian_noise(src, mean, sigma): clip(v + trunc(N(mean, sigma)), 0, 65535).
+ *   POISSON     apply_quantum_noise(src, factor): k ~ Poisson(v * factor), then float(k) / float(factor) in f32, clipped, truncated.
+ * The noise draws come from Philox4x32-10 keyed by (seed, stream) with the pixel index as the counter: a pixel's value depends on
+ * the spec, its source value and its index only. They follow numpy's distributions (inversion below lambda = 10, PTRS above; Box-Muller
+ * for the normal) but not numpy's stream. */
+typedef enum musica_alteration_kind {
+    MUSICA_ALTER_NONE = 0,
+    MUSICA_ALTER_TRANSLATE = 1,
+    MUSICA_ALTER_ROTATE = 2,
+    MUSICA_ALTER_COLLIMATOR = 3,
+    MUSICA_ALTER_GAUSSIAN = 4,
+    MUSICA_ALTER_POISSON = 5,
+    MUSICA_ALTER_KIND_COUNT = 6
+} musica_alteration_kind;
+typedef struct musica_alteration {
+    uint32_t kind;                  /* musica_alteration_kind */
+    int32_t dx, dy;                 /* TRANSLATE: x_shift, y_shift (|shift| < N) */
+    int32_t margin;                 /* ROTATE: the crop's margin, 0 <= 2 margin < N */
+    int32_t shutter_h, shutter_v;   /* COLLIMATOR: 0 <= 2 shutter <= N */
+    double mean, sigma;             /* GAUSSIAN: sigma finite and > 0, mean finite */
+    double factor;                  /* POISSON: finite, > 0, 65535 * factor < 2^30 */
+    uint64_t seed;                  /* noise kinds: Philox key (with stream) */
+    uint32_t stream;
+    double matrix[4];               /* ROTATE: rot_matrix of ndimage.rotate, row-major */
+    double offset[2];               /* ROTATE: its offset */
+} musica_alteration;
+/* N x N host pixels into the source plane (allocated on first use; synchronous). */
+int musica_alter_set_source(musica_ctx* ctx, const uint16_t* pixels);
+/* The alteration of the source into image `image_index` of the input buffer, enqueued on the ctx stream (follow it with
+ * musica_execute_device(ctx, musica_input_device_ptr(ctx))). Refused before any device work: no source, a kind out of range,
+ * image_index >= batch, shifts or shutters that leave nothing, a margin that leaves no crop, a non-finite or non-positive sigma or factor,
+ * a non-finite matrix or offset. It changes no other image of the input buffer, no result of the last step and no reference slot. */
+int musica_alter(musica_ctx* ctx, uint32_t image_index, const musica_alteration* spec);
+/* Test hook: the N x N integer draws of a noise alteration (k of COLLIMATOR / POISSON, for every pixel; the truncated noise of GAUSSIAN),
+ * the same numbers musica_alter uses. Synchronous. */
+int musica_alter_draws(musica_ctx* ctx, const musica_alteration* spec, int32_t* dst);
+/* np.percentile(src[y:y + h, x:x + w], q) (numpy's default 'linear' method) of the source plane, computed on the device
+ * as the fills are; synchronous. */
+int musica_alter_percentile(musica_ctx* ctx, uint32_t x, uint32_t y, uint32_t w, uint32_t h, double q, double* out);
 
 /* ---- test / profiling hooks ------------------------------------------ */
 

@@ -156,6 +156,31 @@ constexpr int kSimMaxBlocks = 1024;   // workgroups per query (partials slots)
 void sim_geometry(SimQueryDev& q);
 // k_sim over `count` queries (grid.x = the largest strips * segs), then k_sim_fold; hist: count x [a 256 | b 256] u32, zeroed by the caller
 void launch_sim(hipStream_t st, const SimQueryDev* d_qs, int count, int max_blocks, SimPart* part, uint32_t* hist, SimPart* out, const SimConsts& k);
+// kernels_alteration.hip: one alteration of musica_alter (or the draws of musica_alter_draws) over an n x n plane.
+struct AlterDev {
+    int kind;                  // MUSICA_ALTER_*
+    int n;                     // side of the source and output planes
+    int ys, xs, hh, ww;        // TRANSLATE: out[ys .. ys + hh) x [xs .. xs + ww) = src[top .., left ..], the rest the fill
+    int top, left;
+    int margin, crop;          // ROTATE: the crop [margin, margin + crop)^2 is rotated, the rest the fill
+    int sh, sv;                // COLLIMATOR: shutters
+    double mean, sigma;        // GAUSSIAN
+    double factor;             // POISSON
+    uint32_t key0, key1, stream;
+    double m[4], off[2];       // ROTATE
+};
+// a region of a u16 plane and the percentile q (0 .. 100) of it to find
+struct PctRegion {
+    const uint16_t* src;
+    int pitch, x, y, w, h;
+    double q;
+};
+// out: the output plane (NULL: none), draws: n * n int32 of the noise kinds (NULL: none); fill: the device double of the geometric kinds
+void launch_alter(hipStream_t st, const uint16_t* src, uint16_t* out, int32_t* draws, const AlterDev& a, const double* fill);
+// ROTATE with margin 0, crop n and fill 0 over a u8 plane (a reference slot)
+void launch_rotate_u8(hipStream_t st, const uint8_t* src, uint8_t* out, const AlterDev& a);
+// np.percentile of the region into *out (device); hist: 768 u32 of scratch, zeroed by the caller
+void launch_percentile(hipStream_t st, const PctRegion& g, uint32_t* hist, double* out);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

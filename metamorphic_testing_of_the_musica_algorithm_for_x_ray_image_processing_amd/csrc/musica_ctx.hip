@@ -155,6 +155,12 @@ struct musica_ctx : DeviceBuffers {
     SimPart* d_sim_out = nullptr;    // [MUSICA_SIM_MAX_QUERIES]
     uint32_t* d_sim_hist = nullptr;  // [MUSICA_SIM_MAX_QUERIES][512]: value counts of a, then b
     std::vector<SimQueryDev> h_sim_q;
+    // musica_alter_*: the source plane (N x N u16), the radix-select counts and the fill, allocated on first use
+    uint16_t* d_alter_src = nullptr;
+    uint32_t* d_alter_hist = nullptr;    // [768]
+    double* d_alter_fill = nullptr;      // [1]
+    int32_t* d_alter_draws = nullptr;    // [N * N], musica_alter_draws only
+    uint16_t* d_input_kept = nullptr;    // the last step's input when an alteration overwrites d_input after it (the on-demand getters read it)
     // host parameters (src/vk_processing.cpp:259-297, 321-325)
     musica_contrast_params h_cparams[MUSICA_MAX_LEVELS];
     musica_nr_params h_nr[3];
@@ -1682,6 +1688,186 @@ int musica_sim_compare(musica_ctx* c, uint32_t count, const musica_sim_query* qs
     for (uint32_t i = 0; i < count; i++) sim_finish(hist.data() + (size_t)i * 512, parts[i], qs[i], out + i);
     return 1;
     ABI_CATCH("musica_sim_compare")
+}
+
+static bool finite_all(const double* v, int n) {
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+int musica_sim_rotate_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const double matrix[4], const double offset[2]) {
+    if (!c) return fail("musica_sim_rotate_reference: ctx is NULL");
+    if (!matrix || !offset) return fail("musica_sim_rotate_reference: matrix or offset is NULL");
+    if (dst_slot >= MUSICA_SIM_SLOTS || src_slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_rotate_reference: slot %u / %u >= %d", dst_slot, src_slot, MUSICA_SIM_SLOTS);
+    if (dst_slot == src_slot) return fail("musica_sim_rotate_reference: dst_slot == src_slot (%u)", dst_slot);
+    if (!c->sim_written[src_slot]) return fail("musica_sim_rotate_reference: slot %u was never written", src_slot);
+    if (!finite_all(matrix, 4) || !finite_all(offset, 2)) return fail("musica_sim_rotate_reference: matrix or offset is not finite");
+    CHECK_CTX(c);
+    uint8_t* dst = sim_slot(c, dst_slot);
+    if (!dst) return 0;
+    AlterDev a{};
+    a.n = c->N - 2 * MUSICA_OUT_MARGIN;
+    memcpy(a.m, matrix, sizeof(a.m));
+    memcpy(a.off, offset, sizeof(a.off));
+    launch_rotate_u8(c->stream, c->d_sim_slot[src_slot], dst, a);
+    HIP_OK(hipGetLastError());
+    c->sim_written[dst_slot] = true;
+    return 1;
+}
+
+int musica_sim_get_reference(musica_ctx* c, uint32_t slot, uint8_t* dst) {
+    if (!c) return fail("musica_sim_get_reference: ctx is NULL");
+    if (!dst) return fail("musica_sim_get_reference: dst is NULL");
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_get_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    if (!c->sim_written[slot]) return fail("musica_sim_get_reference: slot %u was never written", slot);
+    CHECK_CTX(c);
+    const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
+    HIP_OK(hipMemcpyAsync(dst, c->d_sim_slot[slot], nw * nw, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+// ---- alterations of the study (musica_alter_*, include/musica.h; kernels_alteration.hip) ----------------------------------------------
+int musica_alter_set_source(musica_ctx* c, const uint16_t* pixels) {
+    if (!c) return fail("musica_alter_set_source: ctx is NULL");
+    if (!pixels) return fail("musica_alter_set_source: pixels is NULL");
+    CHECK_CTX(c);
+    const size_t nn = (size_t)c->N * c->N;
+    if (!c->d_alter_src && !dalloc(c, &c->d_alter_src, nn)) return fail("musica_alter_set_source: device allocation failed");
+    HIP_OK(hipMemcpyAsync(c->d_alter_src, pixels, nn * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));   // after alterations that read it
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+static bool alter_scratch(musica_ctx* c) {
+    if (c->d_alter_fill) return true;   // keyed on the LAST allocation of the block
+    return (c->d_alter_hist || dalloc(c, &c->d_alter_hist, 768)) && dalloc(c, &c->d_alter_fill, 1);
+}
+
+// The region's percentile into d_alter_fill, on the stream.
+static int enqueue_percentile(musica_ctx* c, int x, int y, int w, int h, double q) {
+    PctRegion g{c->d_alter_src, c->N, x, y, w, h, q};
+    HIP_OK(hipMemsetAsync(c->d_alter_hist, 0, 768 * sizeof(uint32_t), c->stream));
+    launch_percentile(c->stream, g, c->d_alter_hist, c->d_alter_fill);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+// Checks `s` and restates its geometry (harness.clamp_translation / clamp_rotate / apply_collimator) as the kernel's arguments. No device work.
+static int alter_args(musica_ctx* c, const char* fn, const musica_alteration* s, AlterDev& a) {
+    if (!s) return fail("%s: spec is NULL", fn);
+    if (!c->d_alter_src) return fail("%s: no source plane (musica_alter_set_source)", fn);
+    if (s->kind >= MUSICA_ALTER_KIND_COUNT) return fail("%s: kind %u out of range", fn, s->kind);
+    const int n = c->N;
+    a = AlterDev{};
+    a.kind = (int)s->kind;
+    a.n = n;
+    a.key0 = (uint32_t)s->seed;
+    a.key1 = (uint32_t)(s->seed >> 32);
+    a.stream = s->stream;
+    switch (s->kind) {
+        case MUSICA_ALTER_TRANSLATE: {
+            const int dx = s->dx, dy = s->dy;
+            if (dx >= n || dx <= -n || dy >= n || dy <= -n) return fail("%s: shift (%d, %d) leaves nothing of a %d-pixel image", fn, dx, dy, n);
+            const int margin = 10;   // clamp_translation's bright = 2, margin = 10
+            a.left = dx > 0 ? margin : 0;
+            a.top = dy > 0 ? margin : 0;
+            const int right = dx < 0 ? n - margin : n, bottom = dy < 0 ? n - margin : n;
+            a.xs = std::max(dx, 0);
+            a.ys = std::max(dy, 0);
+            a.ww = std::min(right - a.left, n - a.xs);
+            a.hh = std::min(bottom - a.top, n - a.ys);
+            break;
+        }
+        case MUSICA_ALTER_ROTATE:
+            if (s->margin < 0 || 2 * (int64_t)s->margin >= n) return fail("%s: margin %d leaves no crop of a %d-pixel image", fn, s->margin, n);
+            if (!finite_all(s->matrix, 4) || !finite_all(s->offset, 2)) return fail("%s: matrix or offset is not finite", fn);
+            a.margin = s->margin;
+            a.crop = n - 2 * s->margin;
+            memcpy(a.m, s->matrix, sizeof(a.m));
+            memcpy(a.off, s->offset, sizeof(a.off));
+            break;
+        case MUSICA_ALTER_COLLIMATOR:
+            if (s->shutter_h < 0 || s->shutter_v < 0 || 2 * (int64_t)s->shutter_h > n || 2 * (int64_t)s->shutter_v > n)
+                return fail("%s: shutters (%d, %d) leave nothing of a %d-pixel image", fn, s->shutter_h, s->shutter_v, n);
+            a.sh = s->shutter_h;
+            a.sv = s->shutter_v;
+            break;
+        case MUSICA_ALTER_GAUSSIAN:
+            if (!std::isfinite(s->mean) || !std::isfinite(s->sigma) || !(s->sigma > 0.0)) return fail("%s: mean %g / sigma %g: need finite values, sigma > 0", fn, s->mean, s->sigma);
+            a.mean = s->mean;
+            a.sigma = s->sigma;
+            break;
+        case MUSICA_ALTER_POISSON:
+            if (!std::isfinite(s->factor) || !(s->factor > 0.0) || 65535.0 * s->factor >= 1073741824.0)
+                return fail("%s: factor %g: need a finite factor > 0 with 65535 * factor < 2^30", fn, s->factor);
+            a.factor = s->factor;
+            break;
+        default: break;
+    }
+    return 1;
+}
+
+int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
+    if (!c) return fail("musica_alter: ctx is NULL");
+    AlterDev a;
+    if (!alter_args(c, "musica_alter", s, a)) return 0;
+    CHECK_IMG(c, idx);
+    CHECK_CTX(c);
+    if (!alter_scratch(c)) return fail("musica_alter: device allocation failed");
+    const size_t nn = (size_t)c->N * c->N;
+    if (c->cur_input == c->d_input) {   // the last step read d_input: keep it for the getters that recompute from the input
+        if (!c->d_input_kept && !dalloc(c, &c->d_input_kept, (size_t)c->B * nn)) return fail("musica_alter: device allocation failed");
+        HIP_OK(hipMemcpyAsync(c->d_input_kept, c->d_input, (size_t)c->B * nn * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
+        c->cur_input = c->d_input_kept;
+    }
+    const double* fill = nullptr;
+    if (s->kind == MUSICA_ALTER_TRANSLATE) {   // clamp_translation: the 99th percentile of image[top:b_bottom, left:b_right]
+        const int n = c->N, b_right = s->dx > 0 ? 12 : n, b_bottom = s->dy > 0 ? 12 : n;
+        if (!enqueue_percentile(c, a.left, a.top, b_right - a.left, b_bottom - a.top, 99.0)) return 0;
+        fill = c->d_alter_fill;
+    } else if (s->kind == MUSICA_ALTER_ROTATE) {   // clamp_rotate: the 95th percentile of the crop
+        if (!enqueue_percentile(c, a.margin, a.margin, a.crop, a.crop, 95.0)) return 0;
+        fill = c->d_alter_fill;
+    }
+    launch_alter(c->stream, c->d_alter_src, c->d_input + idx * nn, nullptr, a, fill);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+int musica_alter_draws(musica_ctx* c, const musica_alteration* s, int32_t* dst) {
+    ABI_TRY
+    if (!c) return fail("musica_alter_draws: ctx is NULL");
+    if (!dst) return fail("musica_alter_draws: dst is NULL");
+    AlterDev a;
+    if (!alter_args(c, "musica_alter_draws", s, a)) return 0;
+    if (s->kind != MUSICA_ALTER_COLLIMATOR && s->kind != MUSICA_ALTER_GAUSSIAN && s->kind != MUSICA_ALTER_POISSON)
+        return fail("musica_alter_draws: kind %u draws no noise", s->kind);
+    CHECK_CTX(c);
+    const size_t nn = (size_t)c->N * c->N;
+    if (!c->d_alter_draws && !dalloc(c, &c->d_alter_draws, nn)) return fail("musica_alter_draws: device allocation failed");
+    launch_alter(c->stream, c->d_alter_src, nullptr, c->d_alter_draws, a, nullptr);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(dst, c->d_alter_draws, nn * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+    ABI_CATCH("musica_alter_draws")
+}
+
+int musica_alter_percentile(musica_ctx* c, uint32_t x, uint32_t y, uint32_t w, uint32_t h, double q, double* out) {
+    if (!c) return fail("musica_alter_percentile: ctx is NULL");
+    if (!out) return fail("musica_alter_percentile: out is NULL");
+    if (!c->d_alter_src) return fail("musica_alter_percentile: no source plane (musica_alter_set_source)");
+    if (w == 0 || h == 0 || (uint64_t)x + w > (uint64_t)c->N || (uint64_t)y + h > (uint64_t)c->N)
+        return fail("musica_alter_percentile: region (%u, %u) + %u x %u is empty or leaves the %d-pixel plane", x, y, w, h, c->N);
+    if (!(q >= 0.0 && q <= 100.0)) return fail("musica_alter_percentile: q %g outside [0, 100]", q);
+    CHECK_CTX(c);
+    if (!alter_scratch(c)) return fail("musica_alter_percentile: device allocation failed");
+    if (!enqueue_percentile(c, (int)x, (int)y, (int)w, (int)h, q)) return 0;
+    HIP_OK(hipMemcpyAsync(out, c->d_alter_fill, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
 }
 
 int musica_get_noise_hist(musica_ctx* c, uint32_t idx, uint32_t level, uint32_t* dst) {

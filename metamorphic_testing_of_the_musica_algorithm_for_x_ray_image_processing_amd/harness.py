@@ -233,11 +233,14 @@ def register_rotation(alt, unalt, degree):
 class Runner:
     """Processes raw images to the 8-bit output the reference's saveOutImage writes (margin cropped)."""
 
-    def __init__(self, image_size, levels=0, device=0, use_cli=False, device_metrics=False):
+    def __init__(self, image_size, levels=0, device=0, use_cli=False, device_metrics=False, device_alterations=False):
+        if use_cli and device_alterations:
+            raise ValueError("device alterations write the library's resident input buffer: the CLI path has none")
         if use_cli and device_metrics:
             raise ValueError("device metrics score the library's device output: the CLI path has none")
         self.n, self.levels, self.device, self.use_cli = image_size, levels, device, use_cli
-        self.device_metrics = device_metrics   # run_study scores on the device (musica_sim_compare) instead of with numpy
+        self.device_alterations = device_alterations   # run_study generates the alterations on the device (musica_alter); implies device_metrics
+        self.device_metrics = device_metrics or device_alterations   # run_study scores on the device (musica_sim_compare) instead of with numpy
         self.proc = None
         if not use_cli:
             self.proc = mp.MusicaProcessing(device=device)
@@ -256,6 +259,12 @@ class Runner:
         """The same step, its output left on the device (for sim_capture / sim_compare)."""
         if not self.proc.execute(raw):
             raise RuntimeError("musica_execute failed: " + mp.last_error())
+
+    def run_resident(self):
+        """The step on the resident input buffer (what an alter_* call wrote), its output left on the device."""
+        if not self.proc.execute_device():
+            raise RuntimeError("musica_execute_device failed: " + mp.last_error())
+        self.proc.sync()
 
     def mean_cnr(self):
         """mean(cnr image) * 256 of the last run — what test/mean_cnr/script.py prints for a cnr.bmp dump."""
@@ -290,7 +299,12 @@ def read_bmp_gray(path):
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
-    on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1)."""
+    on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
+
+    With runner.device_alterations the raw image is uploaded once and every alteration is generated on the device (musica_alter),
+    the rotated unaltered result comes from musica_sim_rotate_reference, and the seed of the noise alterations is drawn from `rng`, their
+    ordinal in the study being the stream. The geometric alterations are bit-identical to the host's, so their rows equal a device-metrics
+    study's; the noise rows (c_sh_*, gn_*, pn_*) come from a different, reproducible, stream than the host study's numpy draws."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     shutters = scaled(SHUTTERS, n) if shutters is None else shutters
@@ -299,6 +313,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     sigmas = GAUSS_SIGMAS if sigmas is None else sigmas
     factors = POISSON_FACTORS if factors is None else factors
     device = getattr(runner, "device_metrics", False)
+    alter_on_device = getattr(runner, "device_alterations", False)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -313,11 +328,27 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         direct = similarities(unalt, unalt)
     rows = [{"alteration": "unaltered", "direct": direct, "registered": None, "mean_cnr": runner.mean_cnr() if runner.proc else None}]
 
+    if alter_on_device:
+        runner.proc.alter_set_source(raw)
+        seed = int(rng.integers(0, 2 ** 63))
+        ordinal = [0]
+
+        def dev(make):
+            """An alteration as a no-argument call: make(seed, stream) enqueues it on the device, with the study ordinal as stream."""
+            ordinal[0] += 1
+            k = ordinal[0]
+            return lambda: make(seed, k)
+
     def add(name, altered_raw, reg=None, roi=None):
-        """reg: the host crop; roi: () -> (region, slot) of the same comparison on the device (region None: no registration)."""
+        """altered_raw: the altered image, or (device alterations) a call that writes it into the resident input buffer.
+        reg: the host crop; roi: () -> (region, slot) of the same comparison on the device (region None: no registration)."""
         row = {"alteration": name, "registered": None}
-        if device:
+        if callable(altered_raw):
+            altered_raw()
+            runner.run_resident()
+        elif device:
             runner.run_device(altered_raw)
+        if device:
             queries = [(0, 0) + full]
             if roi is not None:
                 region, slot = roi()
@@ -338,8 +369,27 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         rows.append({k: row[k] for k in ("alteration", "direct", "registered", "mean_cnr")})
 
     def rotated_slot(d):
-        runner.proc.sim_set_reference(1, rotated_reference(unalt, d))
+        if alter_on_device:
+            runner.proc.sim_rotate_reference(1, 0, d)
+        else:
+            runner.proc.sim_set_reference(1, rotated_reference(unalt, d))
         return roi_rotation(shape, d), 1
+
+    if alter_on_device:
+        p = runner.proc
+        for s in shutters:
+            add("c_sh_%d" % s, dev(lambda seed, k, s=s: p.alter_collimator(s, s, seed, k)), None, lambda s=s: (roi_collimator(shape, s), 0))
+        for t in translations:
+            add("t_x_%d" % t, dev(lambda seed, k, t=t: p.alter_translate(t, 0)), None, lambda t=t: (roi_translation_x(shape, t), 0))
+        for t in translations:
+            add("t_y_%d" % t, dev(lambda seed, k, t=t: p.alter_translate(0, t)), None, lambda t=t: (roi_translation_y(shape, t), 0))
+        for d in rotations:
+            add("r_%d" % d, dev(lambda seed, k, d=d: p.alter_rotate(d)), None, lambda d=d: rotated_slot(d))
+        for sg in sigmas:
+            add("gn_%s" % sg, dev(lambda seed, k, sg=sg: p.alter_gaussian(0.0, sg, seed, k)))
+        for f in factors:
+            add("pn_%s" % f, dev(lambda seed, k, f=f: p.alter_poisson(f, seed, k)))
+        return rows
 
     for s in shutters:
         add("c_sh_%d" % s, apply_collimator(raw, s, s, rng), lambda a, u, s=s: register_collimator(a, u, s),
@@ -402,7 +452,12 @@ def main(argv=None):
     ap.add_argument("--out", default="out", help="directory of the CSV files")
     ap.add_argument("--cli", action="store_true", help="run every image through the musica-standalone process (run_process, script.py:200-214)")
     ap.add_argument("--device-metrics", action="store_true", help="compute MSE, SSIM and the histogram distances on the GPU (musica_sim_compare)")
+    ap.add_argument("--device-alterations", action="store_true",
+                    help="generate the alterations on the GPU (musica_alter; implies --device-metrics); the noise rows then come from a "
+                         "different, reproducible, random stream than the host study's")
     args = ap.parse_args(argv)
+    if args.cli and args.device_alterations:
+        ap.error("--device-alterations writes the in-process library's input buffer: it cannot be combined with --cli")
     if args.cli and args.device_metrics:
         ap.error("--device-metrics scores the in-process library's device output: it cannot be combined with --cli")
     if args.raw:
@@ -413,7 +468,7 @@ def main(argv=None):
         from .phantom import phantom
         raw = phantom(args.size, args.phantom_seed, noise=4.0)
         name = "phantom_%d_seed%d" % (args.size, args.phantom_seed)
-    runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics)
+    runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics, device_alterations=args.device_alterations)
     rows = run_study(raw, runner, rng=np.random.default_rng(0))
     runner.close()
     write_study_csvs(rows, args.out, name, mean_cnr=not args.cli)

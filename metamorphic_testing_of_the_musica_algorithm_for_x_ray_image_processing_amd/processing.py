@@ -134,6 +134,30 @@ class SimResult(C.Structure):
         return d
 
 
+# musica_alteration_kind
+ALTER_NONE, ALTER_TRANSLATE, ALTER_ROTATE, ALTER_COLLIMATOR, ALTER_GAUSSIAN, ALTER_POISSON = range(6)
+ALTER_KIND_COUNT = 6
+
+
+class Alteration(C.Structure):
+    """musica_alteration: one of the study's alterations (include/musica.h)."""
+    _fields_ = [("kind", C.c_uint32), ("dx", C.c_int32), ("dy", C.c_int32), ("margin", C.c_int32), ("shutter_h", C.c_int32),
+                ("shutter_v", C.c_int32), ("mean", C.c_double), ("sigma", C.c_double), ("factor", C.c_double), ("seed", C.c_uint64),
+                ("stream", C.c_uint32), ("matrix", C.c_double * 4), ("offset", C.c_double * 2)]
+
+
+def rotation_params(side, degree):
+    """(matrix, offset) of ndimage.rotate(reshape=False) for a side x side plane, computed the way scipy computes them (special.cosdg /
+    sindg, offset = in_center - rot_matrix @ out_center, in numpy), so the device mapping sees the same doubles."""
+    from scipy import special
+    c, s = special.cosdg(degree), special.sindg(degree)
+    rot_matrix = np.array([[c, s], [-s, c]])
+    shape = np.asarray((side, side))
+    out_center = rot_matrix @ ((shape - 1) / 2)
+    in_center = (shape - 1) / 2
+    return rot_matrix, in_center - out_center
+
+
 # Every symbol include/musica.h declares: (restype, argtypes). tests/test_abi.py checks the
 # shared object exports exactly these.
 _VP = C.c_void_p
@@ -217,6 +241,12 @@ ABI = {
     "musica_sim_capture": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "musica_sim_set_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
     "musica_sim_compare": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimResult)]),
+    "musica_sim_rotate_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "musica_sim_get_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
+    "musica_alter_set_source": (C.c_int, [_VP, _U16P]),
+    "musica_alter": (C.c_int, [_VP, C.c_uint32, C.POINTER(Alteration)]),
+    "musica_alter_draws": (C.c_int, [_VP, C.POINTER(Alteration), C.POINTER(C.c_int32)]),
+    "musica_alter_percentile": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_double)]),
 }
 
 _lib = None
@@ -532,6 +562,85 @@ class MusicaProcessing:
         arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimResult * max(len(qs), 1))()
         self._ok(self._lib.musica_sim_compare(self._h, len(qs), arr, res), "musica_sim_compare")
         return [res[i].as_dict() for i in range(len(qs))]
+
+    def sim_rotate_reference(self, dst_slot, src_slot, degree):
+        """Reference slot `src_slot` rotated like harness.rotated_reference(slot, degree) into `dst_slot`, on the device."""
+        m, off = rotation_params(self.imageSize - 2 * OUT_MARGIN, degree)
+        mm, oo = (C.c_double * 4)(*[float(v) for v in m.ravel()]), (C.c_double * 2)(*[float(v) for v in off])
+        self._ok(self._lib.musica_sim_rotate_reference(self._h, int(dst_slot), int(src_slot), mm, oo), "musica_sim_rotate_reference")
+
+    def sim_get_reference(self, slot):
+        """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
+        n = self.imageSize - 2 * OUT_MARGIN
+        out = np.empty((n, n), dtype=np.uint8)
+        self._ok(self._lib.musica_sim_get_reference(self._h, int(slot), out.ctypes.data_as(_U8P)), "musica_sim_get_reference")
+        return out
+
+    # ---- alterations of the metamorphic study (musica_alter_*) ---------------------------------
+    # Each alter_* writes image `image_index` of the resident input buffer (follow it with execute_device()); the arguments mirror
+    # harness.py's generators. Noise kinds draw from Philox4x32-10 keyed by (seed, stream): the same distribution as numpy's, not its stream.
+    def alter_set_source(self, raw):
+        """One (N, N) uint16 image into the source plane every alteration reads."""
+        n = self.imageSize
+        a = np.ascontiguousarray(raw, dtype=np.uint16)
+        if a.shape != (n, n):
+            raise ValueError("expected a %d x %d uint16 image, got %r" % (n, n, a.shape))
+        self._ok(self._lib.musica_alter_set_source(self._h, a.ctypes.data_as(_U16P)), "musica_alter_set_source")
+
+    def alter(self, spec, image_index=0):
+        self._ok(self._lib.musica_alter(self._h, int(image_index), C.byref(spec)), "musica_alter")
+
+    def alter_none(self, image_index=0):
+        self.alter(Alteration(kind=ALTER_NONE), image_index)
+
+    def alter_translate(self, dx, dy=0, image_index=0):
+        """harness.clamp_translation(src, dx, dy)."""
+        self.alter(Alteration(kind=ALTER_TRANSLATE, dx=int(dx), dy=int(dy)), image_index)
+
+    @staticmethod
+    def rotate_spec(side, degree):
+        """The Alteration of harness.clamp_rotate(src, degree) for a side x side image."""
+        margin = min(100, side // 8)
+        m, off = rotation_params(side - 2 * margin, degree)
+        return Alteration(kind=ALTER_ROTATE, margin=margin, matrix=(C.c_double * 4)(*[float(v) for v in m.ravel()]),
+                          offset=(C.c_double * 2)(*[float(v) for v in off]))
+
+    def alter_rotate(self, degree, image_index=0):
+        """harness.clamp_rotate(src, degree)."""
+        self.alter(self.rotate_spec(self.imageSize, degree), image_index)
+
+    def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
+        """harness.apply_collimator(src, shutter_h, shutter_v)."""
+        self.alter(Alteration(kind=ALTER_COLLIMATOR, shutter_h=int(shutter_h), shutter_v=int(shutter_v), seed=int(seed), stream=int(stream)),
+                   image_index)
+
+    def alter_gaussian(self, mean, sigma, seed=0, stream=0, image_index=0):
+        """harness.add_gaussian_noise(src, mean, sigma)."""
+        self.alter(Alteration(kind=ALTER_GAUSSIAN, mean=float(mean), sigma=float(sigma), seed=int(seed), stream=int(stream)), image_index)
+
+    def alter_poisson(self, factor, seed=0, stream=0, image_index=0):
+        """harness.apply_quantum_noise(src, factor)."""
+        self.alter(Alteration(kind=ALTER_POISSON, factor=float(factor), seed=int(seed), stream=int(stream)), image_index)
+
+    def alter_draws(self, spec):
+        """The (N, N) int32 draws of a noise alteration: k (collimator, Poisson) or the truncated Gaussian noise."""
+        n = self.imageSize
+        out = np.empty((n, n), dtype=np.int32)
+        self._ok(self._lib.musica_alter_draws(self._h, C.byref(spec), out.ctypes.data_as(C.POINTER(C.c_int32))), "musica_alter_draws")
+        return out
+
+    def alter_percentile(self, x, y, w, h, q):
+        """np.percentile(src[y:y + h, x:x + w], q) of the source plane, computed on the device."""
+        out = C.c_double()
+        self._ok(self._lib.musica_alter_percentile(self._h, int(x), int(y), int(w), int(h), float(q), C.byref(out)), "musica_alter_percentile")
+        return out.value
+
+    def input_pixels(self):
+        """The resident input buffer (what musica_upload / musica_alter wrote) as a (batch, N, N) uint16 array."""
+        n = self.imageSize
+        out = np.empty((self.batch, n, n), dtype=np.uint16)
+        self._ok(self._lib.musica_memcpy_d2h(self._h, out.ctypes.data, self.input_device_ptr(), out.nbytes), "musica_memcpy_d2h")
+        return out
 
     # ---- profiling ----------------------------------------------------------------------
     def profile_enable(self, which=True):
