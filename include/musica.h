@@ -359,6 +359,13 @@ typedef struct musica_sim_result {
 int musica_sim_capture(musica_ctx* ctx, uint32_t slot, uint32_t image_index);
 /* (N - 20)^2 host bytes, top-down rows, into `slot` (synchronous). */
 int musica_sim_set_reference(musica_ctx* ctx, uint32_t slot, const uint8_t* pixels);
+/* The vendor-processed image of the raw one ((N - 20)^2 host values, top-down rows, as stored in its DICOM file: u16 when
+ * bits_allocated is 16, u8 when it is 8) into `slot`, converted on the device into the 8-bit image the reference's study compares
+ * against (test/metamorphic_test/script.py:396-405: Pillow's point(i * 1/256).convert('L') truncates, ImageOps.invert whatever the
+ * PhotometricInterpretation): 255 - (v >> 8) for u16, 255 - v for u8 (harness.vendor_to_u8). Uploads through a context-owned staging
+ * plane (allocated on first use); synchronous. Refused before any device work: NULL pointers, a slot out of range, bits_allocated
+ * other than 8 or 16, an image too small for the margin. */
+int musica_sim_set_vendor_reference(musica_ctx* ctx, uint32_t slot, const void* pixels, uint32_t bits_allocated /* 8 or 16 */);
 /* `count` (1 .. MUSICA_SIM_MAX_QUERIES) comparisons in one launch; synchronous. Refused (0, musica_last_error) before any device work:
  * NULL pointers, a count out of range, a slot out of range or never written, image_index >= batch, a region that leaves either
  * plane, w < 7 or h < 7. */

@@ -181,4 +181,45 @@ void launch_sim(hipStream_t st, const SimQueryDev* d_qs, int count, int max_bloc
     hipLaunchKernelGGL(k_sim_fold, dim3(count), dim3(kSimThreads), 0, st, d_qs, part, out);
 }
 
+// musica_sim_set_vendor_reference: the vendor-processed image into a reference slot, as the reference's script turns it into the 8-bit
+// image it compares against (test/metamorphic_test/script.py:397-405: Image.point(i * 1/256).convert('L') for 16-bit data, then
+// ImageOps.invert): 255 - (v >> 8) for u16, 255 - v for u8, truncating. Eight pixels per thread: 16 B (u16) or 8 B (u8) in, 8 B out,
+// all aligned (both planes are dense from a hipMalloc base and a thread starts at a multiple of 8 pixels); the thread that holds the
+// end of a plane whose size is not a multiple of 8 converts its tail one pixel at a time.
+constexpr int kVendorThreads = 256;
+constexpr int kVendorPx = 8;
+
+// bytes 1 and 3 of a, then of b: the high bytes of four little-endian u16
+__device__ __forceinline__ uint32_t high_bytes(uint32_t a, uint32_t b) {
+    return ((a >> 8) & 0xFFu) | ((a >> 16) & 0xFF00u) | ((b << 8) & 0xFF0000u) | (b & 0xFF000000u);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kVendorThreads) void k_sim_vendor(const T* __restrict__ src, uint8_t* __restrict__ out, long long total) {
+    const long long p0 = ((long long)blockIdx.x * kVendorThreads + threadIdx.x) * kVendorPx;
+    if (p0 >= total) return;
+    if (p0 + kVendorPx > total) {
+        for (long long p = p0; p < total; p++) out[p] = (uint8_t)(255u - ((uint32_t)src[p] >> (8 * (sizeof(T) - 1))));
+        return;
+    }
+    uint2 o;
+    if constexpr (sizeof(T) == 2) {
+        const uint4 v = *reinterpret_cast<const uint4*>(src + p0);
+        o = make_uint2(~high_bytes(v.x, v.y), ~high_bytes(v.z, v.w));   // ~b == 255 - b for every byte b
+    } else {
+        const uint2 v = *reinterpret_cast<const uint2*>(src + p0);
+        o = make_uint2(~v.x, ~v.y);
+    }
+    *reinterpret_cast<uint2*>(out + p0) = o;
+}
+
+void launch_sim_vendor(hipStream_t st, const void* src, int bits, uint8_t* out, long long total) {
+    const long long threads = (total + kVendorPx - 1) / kVendorPx;
+    const unsigned blocks = (unsigned)((threads + kVendorThreads - 1) / kVendorThreads);
+    if (bits == 16)
+        hipLaunchKernelGGL(k_sim_vendor<uint16_t>, dim3(blocks), dim3(kVendorThreads), 0, st, static_cast<const uint16_t*>(src), out, total);
+    else
+        hipLaunchKernelGGL(k_sim_vendor<uint8_t>, dim3(blocks), dim3(kVendorThreads), 0, st, static_cast<const uint8_t*>(src), out, total);
+}
+
 }  // namespace musica

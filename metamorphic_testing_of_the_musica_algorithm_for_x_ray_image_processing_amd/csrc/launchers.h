@@ -156,6 +156,9 @@ constexpr int kSimMaxBlocks = 1024;   // workgroups per query (partials slots)
 void sim_geometry(SimQueryDev& q);
 // k_sim over `count` queries (grid.x = the largest strips * segs), then k_sim_fold; hist: count x [a 256 | b 256] u32, zeroed by the caller
 void launch_sim(hipStream_t st, const SimQueryDev* d_qs, int count, int max_blocks, SimPart* part, uint32_t* hist, SimPart* out, const SimConsts& k);
+// k_sim_vendor: `total` vendor values (u16 when bits == 16, else u8; dense, from an allocation's base) into `out` (u8, dense, from an
+// allocation's base) as 255 - (v >> 8) or 255 - v
+void launch_sim_vendor(hipStream_t st, const void* src, int bits, uint8_t* out, long long total);
 // kernels_alteration.hip: one alteration of musica_alter (or the draws of musica_alter_draws) over an n x n plane.
 struct AlterDev {
     int kind;                  // MUSICA_ALTER_*

@@ -155,6 +155,7 @@ struct musica_ctx : DeviceBuffers {
     SimPart* d_sim_out = nullptr;    // [MUSICA_SIM_MAX_QUERIES]
     uint32_t* d_sim_hist = nullptr;  // [MUSICA_SIM_MAX_QUERIES][512]: value counts of a, then b
     std::vector<SimQueryDev> h_sim_q;
+    uint16_t* d_sim_vendor = nullptr;   // musica_sim_set_vendor_reference's staging plane: (N - 20)^2 u16 (u8 data uses its first half)
     // musica_alter_*: the source plane (N x N u16), the radix-select counts and the fill, allocated on first use
     uint16_t* d_alter_src = nullptr;
     uint32_t* d_alter_hist = nullptr;    // [768]
@@ -1590,6 +1591,26 @@ int musica_sim_set_reference(musica_ctx* c, uint32_t slot, const uint8_t* pixels
     const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
     HIP_OK(hipMemcpyAsync(dst, pixels, nw * nw, hipMemcpyHostToDevice, c->stream));   // after what the stream holds (a compare reading the slot)
     HIP_OK(hipStreamSynchronize(c->stream));                                             // `pixels` is borrowed for the call
+    c->sim_written[slot] = true;
+    return 1;
+}
+
+int musica_sim_set_vendor_reference(musica_ctx* c, uint32_t slot, const void* pixels, uint32_t bits_allocated) {
+    if (!c) return fail("musica_sim_set_vendor_reference: ctx is NULL");
+    if (!pixels) return fail("musica_sim_set_vendor_reference: pixels is NULL");
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_set_vendor_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    if (bits_allocated != 8 && bits_allocated != 16) return fail("musica_sim_set_vendor_reference: bits_allocated %u is neither 8 nor 16", bits_allocated);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_set_vendor_reference: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    CHECK_CTX(c);
+    uint8_t* dst = sim_slot(c, slot);
+    if (!dst) return 0;
+    const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
+    if (!c->d_sim_vendor && !dalloc(c, &c->d_sim_vendor, nw * nw)) return fail("musica_sim_set_vendor_reference: device allocation of the staging plane failed");
+    // after what the stream holds (a compare reading the slot); `pixels` is borrowed for the call
+    HIP_OK(hipMemcpyAsync(c->d_sim_vendor, pixels, nw * nw * (bits_allocated / 8), hipMemcpyHostToDevice, c->stream));
+    launch_sim_vendor(c->stream, c->d_sim_vendor, (int)bits_allocated, dst, (long long)(nw * nw));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(c->stream));
     c->sim_written[slot] = true;
     return 1;
 }

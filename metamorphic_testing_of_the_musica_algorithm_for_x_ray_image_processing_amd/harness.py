@@ -137,6 +137,20 @@ def similarities(a, b):
             "hist_distance": e_dist, "hist_bhattacharyya": b_coef}
 
 
+# ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
+
+def vendor_to_u8(pixels):
+    """The 8-bit image the reference compares against, from the vendor image's stored values (dicom.read_dicom_gray): for 16-bit data
+    Image.point(i * 1/256).convert('L') truncates to v >> 8, and ImageOps.invert is 255 - v, whatever the DICOM's
+    PhotometricInterpretation says. So 255 - (v >> 8) for uint16, 255 - v for uint8 (checked against Pillow for every value)."""
+    a = np.asarray(pixels)
+    if a.dtype == np.uint16:
+        return (255 - (a >> 8)).astype(np.uint8)
+    if a.dtype == np.uint8:
+        return 255 - a
+    raise ValueError("vendor image must be uint8 or uint16, got %s" % a.dtype)
+
+
 # ---- registration of the altered result onto the unaltered one (script.py:442-456, 484-508, 586-608) ----
 # The geometry lives in the *_rects functions: one rectangle (x, y, w, h) per side, exactly what the reference's slices select (Python's
 # clamping of slice bounds included). register_* slice with them; roi_* state them as the (ax, ay, bx, by, w, h) region of a device-side
@@ -296,7 +310,13 @@ def read_bmp_gray(path):
     return a[::-1].copy()
 
 
-def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None):
+# reference slots of a device study: the unaltered result, it rotated, the vendor image, it rotated (VENDOR_SLOT: the vendor slot that
+# stands beside an unaltered one)
+SLOT_UNALTERED, SLOT_ROTATED, SLOT_VENDOR, SLOT_VENDOR_ROTATED = 0, 1, 2, 3
+VENDOR_SLOT = {SLOT_UNALTERED: SLOT_VENDOR, SLOT_ROTATED: SLOT_VENDOR_ROTATED}
+
+
+def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -304,9 +324,22 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     With runner.device_alterations the raw image is uploaded once and every alteration is generated on the device (musica_alter),
     the rotated unaltered result comes from musica_sim_rotate_reference, and the seed of the noise alterations is drawn from `rng`, their
     ordinal in the study being the stream. The geometric alterations are bit-identical to the host's, so their rows equal a device-metrics
-    study's; the noise rows (c_sh_*, gn_*, pn_*) come from a different, reproducible, stream than the host study's numpy draws."""
+    study's; the noise rows (c_sh_*, gn_*, pn_*) come from a different, reproducible, stream than the host study's numpy draws.
+
+    vendor: the vendor-processed image of `raw` ((N - 20, N - 20) uint8 or uint16, as dicom.read_dicom_gray returns it), compared as
+    vendor_to_u8 converts it. Row 0 then gains "reference" (the unaltered result vs the vendor image: the reference's m_sim_ovd), every
+    other row "reference" (the altered result vs the vendor image) and "registered_reference" (the registered crop vs the same crop of
+    the vendor image, rotations: of the vendor image rotated as rotated_reference rotates; None exactly where "registered" is None).
+    On the device the vendor image sits in slot 2 (musica_sim_set_vendor_reference), rotated in slot 3, and its queries join the
+    row's own launch. Without it the rows are exactly as before."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
+    if vendor is not None:
+        vendor = np.asarray(vendor)
+        want = (n - 2 * PROCESSING_MARGIN,) * 2
+        if vendor.shape != want or vendor.dtype not in (np.uint8, np.uint16):
+            raise ValueError("vendor image must be a %d x %d uint8 or uint16 array, got %r %s" % (want + (vendor.shape, vendor.dtype)))
+    keys = ("alteration", "direct", "registered", "mean_cnr") + (() if vendor is None else ("reference", "registered_reference"))
     shutters = scaled(SHUTTERS, n) if shutters is None else shutters
     translations = scaled(TRANSLATIONS, n) if translations is None else translations
     rotations = ROTATIONS if rotations is None else rotations
@@ -314,6 +347,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     factors = POISSON_FACTORS if factors is None else factors
     device = getattr(runner, "device_metrics", False)
     alter_on_device = getattr(runner, "device_alterations", False)
+    ref8 = vendor_to_u8(vendor) if vendor is not None and not device else None   # the host metrics' vendor image
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -321,12 +355,23 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     def on_device(queries):
         return [{k: r[k] for k in mp.SIM_METRICS} for r in runner.proc.sim_compare(queries)]
 
+    first = {"alteration": "unaltered", "registered": None}
     if device:
-        runner.proc.sim_capture(0)
-        direct = on_device([(0, 0) + full])[0]
+        runner.proc.sim_capture(SLOT_UNALTERED)
+        queries = [(0, SLOT_UNALTERED) + full]
+        if vendor is not None:
+            runner.proc.sim_set_vendor_reference(SLOT_VENDOR, vendor)
+            queries.append((0, SLOT_VENDOR) + full)
+        res = on_device(queries)
+        first["direct"] = res[0]
+        if vendor is not None:
+            first["reference"] = res[1]
     else:
-        direct = similarities(unalt, unalt)
-    rows = [{"alteration": "unaltered", "direct": direct, "registered": None, "mean_cnr": runner.mean_cnr() if runner.proc else None}]
+        first["direct"] = similarities(unalt, unalt)
+        if vendor is not None:
+            first["reference"] = similarities(unalt, ref8)
+    first["mean_cnr"] = runner.mean_cnr() if runner.proc else None
+    rows = [{k: first[k] for k in keys if k in first}]
 
     if alter_on_device:
         runner.proc.alter_set_source(raw)
@@ -342,47 +387,62 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     def add(name, altered_raw, reg=None, roi=None):
         """altered_raw: the altered image, or (device alterations) a call that writes it into the resident input buffer.
         reg: the host crop; roi: () -> (region, slot) of the same comparison on the device (region None: no registration)."""
-        row = {"alteration": name, "registered": None}
+        row = {"alteration": name, "registered": None, "registered_reference": None}
         if callable(altered_raw):
             altered_raw()
             runner.run_resident()
         elif device:
             runner.run_device(altered_raw)
         if device:
-            queries = [(0, 0) + full]
+            queries = [(0, SLOT_UNALTERED) + full]
+            if vendor is not None:
+                queries.append((0, SLOT_VENDOR) + full)
             if roi is not None:
                 region, slot = roi()
                 if region is not None and min(region[4], region[5]) >= 8:
                     queries.append((0, slot) + region)
+                    if vendor is not None:
+                        queries.append((0, VENDOR_SLOT[slot]) + region)
             res = on_device(queries)
-            row["direct"] = res[0]
-            if len(res) > 1:
-                row["registered"] = res[1]
+            row["direct"] = res.pop(0)
+            if vendor is not None:
+                row["reference"] = res.pop(0)
+            if res:
+                row["registered"] = res.pop(0)
+                if vendor is not None:
+                    row["registered_reference"] = res.pop(0)
         else:
             alt = runner.run(altered_raw)
             row["direct"] = similarities(alt, unalt)
+            if vendor is not None:
+                row["reference"] = similarities(alt, ref8)
             if reg is not None:
                 a, u = reg(alt, unalt)
                 if a.size and a.shape == u.shape and min(a.shape) >= 8:
                     row["registered"] = similarities(a, u)
+                    if vendor is not None:
+                        row["registered_reference"] = similarities(*reg(alt, ref8))   # the same rectangles: ref8 has unalt's shape
         row["mean_cnr"] = runner.mean_cnr() if runner.proc else None
-        rows.append({k: row[k] for k in ("alteration", "direct", "registered", "mean_cnr")})
+        rows.append({k: row[k] for k in keys})
 
     def rotated_slot(d):
         if alter_on_device:
-            runner.proc.sim_rotate_reference(1, 0, d)
+            runner.proc.sim_rotate_reference(SLOT_ROTATED, SLOT_UNALTERED, d)
         else:
-            runner.proc.sim_set_reference(1, rotated_reference(unalt, d))
-        return roi_rotation(shape, d), 1
+            runner.proc.sim_set_reference(SLOT_ROTATED, rotated_reference(unalt, d))
+        if vendor is not None:
+            runner.proc.sim_rotate_reference(SLOT_VENDOR_ROTATED, SLOT_VENDOR, d)
+        return roi_rotation(shape, d), SLOT_ROTATED
 
     if alter_on_device:
         p = runner.proc
         for s in shutters:
-            add("c_sh_%d" % s, dev(lambda seed, k, s=s: p.alter_collimator(s, s, seed, k)), None, lambda s=s: (roi_collimator(shape, s), 0))
+            add("c_sh_%d" % s, dev(lambda seed, k, s=s: p.alter_collimator(s, s, seed, k)), None,
+                lambda s=s: (roi_collimator(shape, s), SLOT_UNALTERED))
         for t in translations:
-            add("t_x_%d" % t, dev(lambda seed, k, t=t: p.alter_translate(t, 0)), None, lambda t=t: (roi_translation_x(shape, t), 0))
+            add("t_x_%d" % t, dev(lambda seed, k, t=t: p.alter_translate(t, 0)), None, lambda t=t: (roi_translation_x(shape, t), SLOT_UNALTERED))
         for t in translations:
-            add("t_y_%d" % t, dev(lambda seed, k, t=t: p.alter_translate(0, t)), None, lambda t=t: (roi_translation_y(shape, t), 0))
+            add("t_y_%d" % t, dev(lambda seed, k, t=t: p.alter_translate(0, t)), None, lambda t=t: (roi_translation_y(shape, t), SLOT_UNALTERED))
         for d in rotations:
             add("r_%d" % d, dev(lambda seed, k, d=d: p.alter_rotate(d)), None, lambda d=d: rotated_slot(d))
         for sg in sigmas:
@@ -393,13 +453,13 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
 
     for s in shutters:
         add("c_sh_%d" % s, apply_collimator(raw, s, s, rng), lambda a, u, s=s: register_collimator(a, u, s),
-            lambda s=s: (roi_collimator(shape, s), 0))
+            lambda s=s: (roi_collimator(shape, s), SLOT_UNALTERED))
     for t in translations:
         add("t_x_%d" % t, clamp_translation(raw, t, 0), lambda a, u, t=t: register_translation_x(a, u, t),
-            lambda t=t: (roi_translation_x(shape, t), 0))
+            lambda t=t: (roi_translation_x(shape, t), SLOT_UNALTERED))
     for t in translations:
         add("t_y_%d" % t, clamp_translation(raw, 0, t), lambda a, u, t=t: register_translation_y(a, u, t),
-            lambda t=t: (roi_translation_y(shape, t), 0))
+            lambda t=t: (roi_translation_y(shape, t), SLOT_UNALTERED))
     for d in rotations:
         add("r_%d" % d, clamp_rotate(raw, d), lambda a, u, d=d: register_rotation(a, u, d), lambda d=d: rotated_slot(d))
     for sg in sigmas:
@@ -416,36 +476,121 @@ CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs 
               'normalized altered vs reference histogram distance']
 
 
-def write_study_csvs(rows, out_dir, raw_name, mean_cnr=True):
-    """direct_robustness.csv / reg_based_robustness.csv with the reference's column layout. The six "vs reference"
-    columns compare with the vendor-processed image, which the reference tree does not ship (missing blobs): they
-    stay empty. mean_cnr.csv adds what test/mean_cnr/script.py reports per alteration."""
+REF_CSV_HEADER = ['raw file', 'mse similarity', 'ssim similarity', 'histogram distance']   # ref_similarities.csv (script.py:285-290)
+
+
+def normalized_vs_reference(ref, ovd):
+    """m_sim_alt's three normalised values (script.py:272-274): ref_mse / ovd_mse, ref_ssim / ovd_ssim and
+    (ref_hist - ovd_hist) / (1 - ovd_hist), with ovd the unaltered result vs the vendor image. IEEE f64 division: a zero denominator
+    gives inf or nan (the reference would raise ZeroDivisionError and stop the study)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return [float(np.float64(ref["mse"]) / np.float64(ovd["mse"])), float(np.float64(ref["ssim"]) / np.float64(ovd["ssim"])),
+                float((np.float64(ref["hist_distance"]) - ovd["hist_distance"]) / (1.0 - np.float64(ovd["hist_distance"])))]
+
+
+def write_studies_csvs(studies, out_dir, mean_cnr=True):
+    """The reference's output files for several raw images: `studies` is a list of (raw_name, rows) pairs (run_study's rows), written
+    in order into one direct_robustness.csv / reg_based_robustness.csv with the reference's column layout (script.py:223-330), plus
+    mean_cnr.csv (what test/mean_cnr/script.py reports per alteration).
+
+    The six "vs reference" columns compare with the vendor-processed image. For a study run with one (rows[0] has "reference"): the
+    altered result vs that image (reg_based_robustness.csv: the registered crops), then normalized_vs_reference against the study's
+    full-image unaltered-vs-vendor values, as m_sim_alt and m_sim_norm_alt do; ref_similarities.csv gets one row of those values per
+    such study and is written only when there is one. Studies without a vendor image leave the six columns empty."""
     os.makedirs(out_dir, exist_ok=True)
+    ovds = []
+
+    def ref_columns(ref, ovd):
+        if ovd is None:
+            return [""] * 6
+        return [ref["mse"], ref["ssim"], ref["hist_distance"]] + normalized_vs_reference(ref, ovd)
+
     with open(os.path.join(out_dir, "direct_robustness.csv"), "w", newline="") as fd, \
             open(os.path.join(out_dir, "reg_based_robustness.csv"), "w", newline="") as fr:
         wd, wr = csv.writer(fd), csv.writer(fr)
         wd.writerow(CSV_HEADER)
         wr.writerow(CSV_HEADER)
-        for r in rows:
-            if r["alteration"] == "unaltered":
-                continue
-            d = r["direct"]
-            wd.writerow([raw_name, r["alteration"], d["mse"], d["ssim"], d["hist_distance"]] + [""] * 6)
-            if r["registered"] is not None:
-                g = r["registered"]
-                wr.writerow([raw_name, r["alteration"], g["mse"], g["ssim"], g["hist_distance"]] + [""] * 6)
+        for raw_name, rows in studies:
+            ovd = next((r.get("reference") for r in rows if r["alteration"] == "unaltered"), None)
+            if ovd is not None:
+                ovds.append([raw_name, ovd["mse"], ovd["ssim"], ovd["hist_distance"]])
+            for r in rows:
+                if r["alteration"] == "unaltered":
+                    continue
+                d = r["direct"]
+                wd.writerow([raw_name, r["alteration"], d["mse"], d["ssim"], d["hist_distance"]] + ref_columns(r.get("reference"), ovd))
+                if r["registered"] is not None:
+                    g = r["registered"]
+                    wr.writerow([raw_name, r["alteration"], g["mse"], g["ssim"], g["hist_distance"]] +
+                                ref_columns(r.get("registered_reference"), ovd))
     if mean_cnr:
         with open(os.path.join(out_dir, "mean_cnr.csv"), "w", newline="") as fc:
             wc = csv.writer(fc)
             wc.writerow(["raw file", "alteration", "mean cnr"])
-            for r in rows:
-                wc.writerow([raw_name, r["alteration"], r["mean_cnr"]])
+            for raw_name, rows in studies:
+                for r in rows:
+                    wc.writerow([raw_name, r["alteration"], r["mean_cnr"]])
+    if ovds:
+        with open(os.path.join(out_dir, "ref_similarities.csv"), "w", newline="") as fs:
+            ws = csv.writer(fs)
+            ws.writerow(REF_CSV_HEADER)
+            ws.writerows(ovds)
+
+
+def write_study_csvs(rows, out_dir, raw_name, mean_cnr=True):
+    """write_studies_csvs for one raw image: direct_robustness.csv / reg_based_robustness.csv with the reference's column layout,
+    mean_cnr.csv, and (rows of a study with a vendor image) the "vs reference" columns and ref_similarities.csv."""
+    write_studies_csvs([(raw_name, rows)], out_dir, mean_cnr=mean_cnr)
+
+
+def read_manifest(path):
+    """The images of a --manifest file: one `raw[,reference]` per line, `#` starts a comment, blank lines are skipped. Paths are
+    relative to the manifest's directory (either slash separates directories, so the reference's `foot\\image.raw` works as written).
+    Returns [(raw as written, raw path, reference path or None)]."""
+    base = os.path.dirname(os.path.abspath(path))
+
+    def resolve(p):
+        return os.path.join(base, *[s for s in p.replace("\\", "/").split("/") if s]) if not os.path.isabs(p) else p
+
+    entries = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            line = line.split("#", 1)[0].strip()
+            if not line:
+                continue
+            parts = [s.strip() for s in line.split(",")]
+            if len(parts) > 2 or not all(parts):
+                raise ValueError("%s:%d: expected `raw[,reference]`, got %r" % (path, ln, line))
+            entries.append((parts[0], resolve(parts[0]), resolve(parts[1]) if len(parts) == 2 else None))
+    if not entries:
+        raise ValueError("%s: no images" % path)
+    return entries
+
+
+def run_studies(entries, runner, **study_args):
+    """run_study over several raw images through one runner: `entries` as read_manifest returns them (raw paths of the runner's size;
+    a reference: the vendor DICOM, read with dicom.read_dicom_gray). Every image gets a fresh np.random.default_rng(0), so its rows are
+    those of a study of that image alone. Returns [(raw as written, rows)], for write_studies_csvs."""
+    from .dicom import read_dicom_gray
+    from .processing import read_raw
+    studies = []
+    for name, raw_path, ref_path in entries:
+        raw = read_raw(raw_path, runner.n)
+        if raw is None:
+            raise ValueError("%s: not a raw file of %d x %d pixels (256-byte header + N*N uint16)" % (raw_path, runner.n, runner.n))
+        vendor = read_dicom_gray(ref_path) if ref_path else None
+        studies.append((name, run_study(raw, runner, rng=np.random.default_rng(0), vendor=vendor, **study_args)))
+    return studies
 
 
 def main(argv=None):
     import argparse
-    ap = argparse.ArgumentParser(description="Metamorphic study of one raw image (or a seeded phantom) on the HIP MUSICA path")
+    ap = argparse.ArgumentParser(description="Metamorphic study of raw images (or a seeded phantom) on the HIP MUSICA path")
     ap.add_argument("--raw", help="raw file: 256-byte header + N*N little-endian uint16 (test/standalone/main.cpp:54-75)")
+    ap.add_argument("--reference", help="the vendor-processed DICOM of --raw (or of the phantom): fills the \"vs reference\" columns and "
+                                        "writes ref_similarities.csv (script.py:370-411)")
+    ap.add_argument("--manifest", help="text file with one `raw[,reference]` per line (paths relative to it, # comments): every image "
+                                       "through one runner into the same CSV files; excludes --raw and --reference")
     ap.add_argument("--phantom-seed", type=int, default=1, help="seed of the synthetic phantom used when --raw is absent")
     ap.add_argument("--size", type=int, default=3072, help="image side N (the reference's CLI fixes 3072)")
     ap.add_argument("--levels", type=int, default=0)
@@ -460,7 +605,11 @@ def main(argv=None):
         ap.error("--device-alterations writes the in-process library's input buffer: it cannot be combined with --cli")
     if args.cli and args.device_metrics:
         ap.error("--device-metrics scores the in-process library's device output: it cannot be combined with --cli")
-    if args.raw:
+    if args.manifest and (args.raw or args.reference):
+        ap.error("--manifest names every raw image and its reference: it cannot be combined with --raw or --reference")
+    if args.manifest:
+        entries = read_manifest(args.manifest)
+    elif args.raw:
         from .processing import read_raw
         raw = read_raw(args.raw, args.size)
         name = os.path.basename(args.raw)
@@ -468,11 +617,19 @@ def main(argv=None):
         from .phantom import phantom
         raw = phantom(args.size, args.phantom_seed, noise=4.0)
         name = "phantom_%d_seed%d" % (args.size, args.phantom_seed)
+    if args.reference:
+        from .dicom import read_dicom_gray
+        vendor = read_dicom_gray(args.reference)
     runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics, device_alterations=args.device_alterations)
-    rows = run_study(raw, runner, rng=np.random.default_rng(0))
-    runner.close()
-    write_study_csvs(rows, args.out, name, mean_cnr=not args.cli)
-    print("wrote %d alterations to %s" % (len(rows) - 1, args.out))
+    try:
+        if args.manifest:
+            studies = run_studies(entries, runner)
+        else:
+            studies = [(name, run_study(raw, runner, rng=np.random.default_rng(0), vendor=vendor if args.reference else None))]
+    finally:
+        runner.close()
+    write_studies_csvs(studies, args.out, mean_cnr=not args.cli)
+    print("wrote %d alterations to %s" % (sum(len(rows) - 1 for _, rows in studies), args.out))
     return 0
 
 

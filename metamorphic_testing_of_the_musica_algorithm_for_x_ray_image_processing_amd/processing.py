@@ -240,6 +240,7 @@ ABI = {
     "musica_device_count": (C.c_int, []),
     "musica_sim_capture": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "musica_sim_set_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
+    "musica_sim_set_vendor_reference": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32]),
     "musica_sim_compare": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimResult)]),
     "musica_sim_rotate_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "musica_sim_get_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
@@ -553,6 +554,17 @@ class MusicaProcessing:
         if a.shape != (n, n):
             raise ValueError("expected a %d x %d uint8 plane, got %r" % (n, n, a.shape))
         self._ok(self._lib.musica_sim_set_reference(self._h, int(slot), a.ctypes.data_as(_U8P)), "musica_sim_set_reference")
+
+    def sim_set_vendor_reference(self, slot, pixels):
+        """The vendor-processed image ((N - 20, N - 20) uint16 or uint8, the values its DICOM file stores) into reference slot `slot`,
+        converted on the device as harness.vendor_to_u8 converts it; 16 or 8 bits from the array's dtype."""
+        n = self.imageSize - 2 * OUT_MARGIN
+        a = np.asarray(pixels)
+        if a.dtype not in (np.uint16, np.uint8) or a.shape != (n, n):
+            raise ValueError("expected a %d x %d uint16 or uint8 plane, got %r %s" % (n, n, a.shape, a.dtype))
+        a = np.ascontiguousarray(a)
+        self._ok(self._lib.musica_sim_set_vendor_reference(self._h, int(slot), a.ctypes.data_as(_VP), 8 * a.itemsize),
+                 "musica_sim_set_vendor_reference")
 
     def sim_compare(self, queries):
         """queries: (image_index, slot, ax, ay, bx, by, w, h) tuples (or SimQuery), all in one launch. Returns one dict per query:
