@@ -428,6 +428,35 @@ int musica_alter_draws(musica_ctx* ctx, const musica_alteration* spec, int32_t* 
  * as the fills are; synchronous. */
 int musica_alter_percentile(musica_ctx* ctx, uint32_t x, uint32_t y, uint32_t w, uint32_t h, double q, double* out);
 
+/* ---- device-resident output and stream ordering (new, not in the reference) ---- */
+
+/* What musica_export_out writes per image. */
+typedef enum musica_out_format {
+    MUSICA_OUT_U8 = 0,          /* (N - 20) rows of N - 20 bytes: exactly musica_get_out_pixels' bytes (crop MUSICA_OUT_MARGIN, (uint8_t)(255 v)) */
+    MUSICA_OUT_GRADED_F32 = 1,  /* N rows of N floats: exactly musica_get_graded's values */
+    MUSICA_OUT_FORMAT_COUNT = 2
+} musica_out_format;
+
+/* Writes images first .. first + count - 1 of the last step into caller-owned DEVICE memory of the context's device: row r of image
+ * first + k at d_dst + k * image_pitch_bytes + r * row_pitch_bytes; the bytes between rows and between images are left alone.
+ * Enqueued on the context's stream behind whatever is there (a step, musica_execute_device, a pipeline step of this context, the last
+ * batch of musica_execute_stream); returns without waiting. Changes no result of the step and no other buffer. Refused before
+ * anything is enqueued when ctx or d_dst is NULL, the format is out of range, count is 0 or first + count exceeds the batch, a pitch
+ * is smaller than a row (row_pitch < width bytes) or an image (image_pitch < row_pitch * rows), with MUSICA_OUT_GRADED_F32 when
+ * d_dst or a pitch is not a multiple of 4, with MUSICA_OUT_U8 when N <= 20, when no step has run on the context, when d_dst is not
+ * device memory of the context's device (pinned and pageable host memory are refused) and when the last byte written lies beyond
+ * the allocation that holds d_dst. */
+int musica_export_out(musica_ctx* ctx, uint32_t first, uint32_t count, uint32_t format, void* d_dst, size_t row_pitch_bytes,
+                      size_t image_pitch_bytes);
+
+/* Stream ordering with a caller's stream (a hipStream_t of the context's device; NULL = the null stream). musica_stream_wait: all
+ * that the context enqueues from now on (steps, exports, stats, similarity, alterations) starts after the work already on `stream`.
+ * musica_stream_signal: the work enqueued on `stream` from now on starts after everything enqueued on the context so far (the side
+ * stream of a two-stream context rejoins the context's stream inside every step, eager or replayed). Neither waits on the host.
+ * Refused for a stream of another device and for a stream that is capturing a graph. */
+int musica_stream_wait(musica_ctx* ctx, void* stream);
+int musica_stream_signal(musica_ctx* ctx, void* stream);
+
 /* ---- test / profiling hooks ------------------------------------------ */
 
 /* A sequence of `count` batches (pixels[j]: batch x N x N uint16 in host memory), pipelined: two device input buffers and a

@@ -81,3 +81,43 @@ def process_shard(proc, images, image_ids):
             st.image_id = image_ids[start + k]
             rows[start + k] = stats_to_row(st)
     return rows
+
+
+def process_shard_device(proc, images, image_ids):
+    """process_shard on a GPU tensor: `images` is a (n, N, N) torch.uint16 tensor on the context's device (a MusicaProcessing or a
+    tensors.TensorProcessor). Returns (rows, outputs) as GPU tensors — int32 (n, STATS_WORDS), the rows process_shard returns, and uint8
+    (n, N - 20, N - 20), musica_get_out_pixels' bytes — ordered on the current torch stream, with no host synchronisation and no copy
+    to the host. Every chunk goes through one staging batch, so the context replays one captured graph; the last chunk is padded by
+    repeating its final image, as process_shard pads it."""
+    import torch
+    from . import processing as mp
+    p = getattr(proc, "proc", proc)
+    b, side = p.batch, p.imageSize
+    n = len(image_ids)
+    if tuple(images.shape) != (n, side, side) or images.dtype != torch.uint16 or images.device.type != "cuda":
+        raise ValueError("expected a (%d, %d, %d) torch.uint16 tensor on the GPU, got %r %s on %s" % (n, side, side, tuple(images.shape),
+                                                                                                        images.dtype, images.device))
+    dev = images.device
+    nw = side - 2 * mp.OUT_MARGIN
+    chunks = (n + b - 1) // b
+    rows = torch.empty((chunks * b, STATS_WORDS), dtype=torch.int32, device=dev)
+    outputs = torch.empty((n, nw, nw), dtype=torch.uint8, device=dev)
+    stage = torch.empty((b, side, side), dtype=torch.uint16, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    src, dst = images.view(torch.int16), stage.view(torch.int16)   # plain copies, whatever kernels torch has for uint16
+    for start in range(0, n, b):
+        m = min(b, n - start)
+        dst[:m].copy_(src[start:start + m])
+        if m < b:  # pad the last chunk by repeating its final image; padded rows are dropped
+            dst[m:].copy_(src[start + m - 1:start + m].expand(b - m, side, side))
+        p.stream_wait(stream)
+        try:
+            if not p.execute_device(stage.data_ptr()):
+                raise RuntimeError("musica_execute_device failed: " + mp.last_error())
+            p.export_out(outputs[start].data_ptr(), 0, m, mp.OUT_U8)
+            p.stats_device(rows[start].data_ptr())
+        finally:
+            p.stream_signal(stream)   # the next chunk's copy into `stage` waits for this step
+    rows = rows[:n]
+    rows[:, 0] = torch.as_tensor(list(image_ids), dtype=torch.int32).to(dev, non_blocking=True)
+    return rows, outputs

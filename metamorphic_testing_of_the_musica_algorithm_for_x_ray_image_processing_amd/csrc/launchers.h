@@ -136,6 +136,9 @@ void launch_grad_apply(hipStream_t st, const float* in, float* out, const LevelD
 // crop + quantise of saveOutImage for ONE image plane: out = (S - 2 margin)^2 bytes, dense
 void launch_out_pixels(hipStream_t st, const float* graded, const LevelDesc& l0, int margin, uint8_t* out);
 void launch_out_bmp24(hipStream_t st, const float* graded, const LevelDesc& l0, int margin, uint32_t* out);   // the BMP file's pixel array (24 bpp, bottom-up, padded rows)
+// kernels_export.hip: the same crop + quantise for `count` image planes from `graded` on (stride l0.plane) in one launch; image k's row r at
+// dst + k * image_pitch + r * row_pitch (bytes), nothing else written
+void launch_export_u8(hipStream_t st, const float* graded, const LevelDesc& l0, int count, uint8_t* dst, size_t row_pitch, size_t image_pitch);
 // kernels_similarity.hip: one comparison of musica_sim_compare. a: the graded f32 plane at the region's origin (margin included),
 // b: the reference slot's u8 plane at its origin; strips / segs / seg_rows: launch geometry (sim_geometry).
 struct SimQueryDev {

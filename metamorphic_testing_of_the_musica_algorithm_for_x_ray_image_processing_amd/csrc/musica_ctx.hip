@@ -162,6 +162,10 @@ struct musica_ctx : DeviceBuffers {
     double* d_alter_fill = nullptr;      // [1]
     int32_t* d_alter_draws = nullptr;    // [N * N], musica_alter_draws only
     uint16_t* d_input_kept = nullptr;    // the last step's input when an alteration overwrites d_input after it (the on-demand getters read it)
+    // musica_export_out / musica_stream_wait / musica_stream_signal: a step has been enqueued (the export refuses a context without one), and
+    // the two events that order the context's stream against a caller's stream, created on first use
+    bool stepped = false;
+    hipEvent_t ev_caller = nullptr, ev_signal = nullptr;
     // host parameters (src/vk_processing.cpp:259-297, 321-325)
     musica_contrast_params h_cparams[MUSICA_MAX_LEVELS];
     musica_nr_params h_nr[3];
@@ -395,6 +399,8 @@ void musica_destroy(musica_ctx* c) {
     if (c->side) { hipStreamSynchronize(c->side); hipStreamDestroy(c->side); }
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->ev_join) hipEventDestroy(c->ev_join);
+    if (c->ev_caller) hipEventDestroy(c->ev_caller);
+    if (c->ev_signal) hipEventDestroy(c->ev_signal);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1148,6 +1154,7 @@ static musica_ctx* make_lane(const musica_ctx* c, int i0, int nb) {
     v->lanes.clear();
     v->img_copied.clear();
     v->side = nullptr; v->ev_fork = nullptr; v->ev_join = nullptr; v->copy_stream = nullptr;
+    v->ev_caller = nullptr; v->ev_signal = nullptr;
     for (int k = 0; k < kGraphSlots; k++) { v->graph_exec[k] = nullptr; v->graph_input[k] = nullptr; v->graph_used[k] = 0; }
     v->use_graph = !(c->p.flags & MUSICA_FLAG_NO_GRAPH) && env_int("MUSICA_GRAPH", 1) != 0;   // one graph per lane and input buffer: the host
                                                                                              // enqueues 8 replays per batch instead of ~136 launches
@@ -1267,7 +1274,9 @@ int musica_execute_device(musica_ctx* c, const uint16_t* d_pixels) {
     if (!d_pixels) return fail("musica_execute_device: d_pixels is NULL");
     if (((uintptr_t)d_pixels & 15u) != 0) return fail("musica_execute_device: d_pixels must be 16-byte aligned");
     c->cur_input = d_pixels;
-    return enqueue_all(c);
+    if (!enqueue_all(c)) return 0;
+    c->stepped = true;
+    return 1;
 }
 
 int musica_execute(musica_ctx* c, const uint16_t* pixels) {
@@ -1277,11 +1286,13 @@ int musica_execute(musica_ctx* c, const uint16_t* pixels) {
     if (lanes_wanted(c, pixels)) {   // a batch in pinned memory: image k's chain starts when image k has landed (the copy of a batch takes 2 - 3 x its kernels)
         if (!ensure_lanes(c)) return fail("musica_execute: stream / event creation for the image lanes failed");
         if (!enqueue_images_from_host(c, c->d_input, pixels, true)) return 0;
+        c->stepped = true;
         return musica_sync(c);
     }
     HIP_OK(hipMemcpyAsync(c->d_input, pixels, (size_t)c->B * c->N * c->N * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));  // vk_state.cpp:313-342
     c->cur_input = c->d_input;
     if (!enqueue_all(c)) return 0;
+    c->stepped = true;
     return musica_sync(c);  // vkWaitForFences, src/vk_processing.cpp:2535-2536
     ABI_CATCH("musica_execute")
 }
@@ -1333,6 +1344,7 @@ int musica_execute_stream(musica_ctx* c, const uint16_t* const* pixels, uint32_t
         hipStreamWaitEvent(c->stream, c->ev_copied[k], 0);
         c->cur_input = bufs[k];
         ok = enqueue_all(c);
+        if (ok) c->stepped = true;
         if (ok && stats) {
             launch_stats(c->stream, c->d_cnr, c->lv[MUSICA_CNR_LEVEL], c->d_minmax, c->min_chain_exact, c->d_noise_max, c->L, c->d_grad_max, c->d_gcurve,
                          d_rows + (size_t)j * c->B, j * (uint32_t)c->B, 1u, c->B, c->d_stats_partial);
@@ -1983,6 +1995,105 @@ int musica_stats_device_strided(musica_ctx* c, void* d_dst, uint32_t image_id_ba
     return 1;
 }
 int musica_stats_device(musica_ctx* c, void* d_dst, uint32_t image_id_base) { return musica_stats_device_strided(c, d_dst, image_id_base, 1u); }
+
+// ---- device-resident output and stream ordering (musica_export_out, musica_stream_wait / _signal) ----------------------------------------
+// Everything about the destination is checked on the host before anything is enqueued: a kernel store to pageable host memory faults the
+// GPU, and a store past the end of the caller's allocation lands in whatever the runtime placed behind it.
+int musica_export_out(musica_ctx* c, uint32_t first, uint32_t count, uint32_t format, void* d_dst, size_t row_pitch, size_t image_pitch) {
+    CHECK_CTX(c);
+    if (!d_dst) return fail("musica_export_out: d_dst is NULL");
+    {
+        hipPointerAttribute_t a;
+        if (hipPointerGetAttributes(&a, d_dst) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("musica_export_out: d_dst is not device memory (the HIP runtime does not know it: pageable host memory?)");
+        }
+        if (a.type != hipMemoryTypeDevice) return fail("musica_export_out: d_dst is not device memory (memory type %d)", (int)a.type);
+        if (a.device != c->p.device) return fail("musica_export_out: d_dst is memory of device %d, the context runs on device %d", a.device, c->p.device);
+    }
+    if (format >= MUSICA_OUT_FORMAT_COUNT) return fail("musica_export_out: format %u out of range", format);
+    if (count == 0) return fail("musica_export_out: count is 0");
+    if ((uint64_t)first + count > (uint64_t)c->B) return fail("musica_export_out: images %u .. %u + %u exceed the batch of %d", first, first, count, c->B);
+    const bool u8 = format == MUSICA_OUT_U8;
+    if (u8 && c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_export_out: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    const size_t rows = u8 ? (size_t)c->N - 2 * MUSICA_OUT_MARGIN : (size_t)c->N;
+    const size_t width = u8 ? rows : (size_t)c->N * sizeof(float);
+    size_t image_bytes = 0, last = 0;
+    if (row_pitch < width) return fail("musica_export_out: row pitch %zu below the %zu bytes of a row", row_pitch, width);
+    if (__builtin_mul_overflow(row_pitch, rows, &image_bytes) || image_pitch < image_bytes)
+        return fail("musica_export_out: image pitch %zu below the %zu rows of pitch %zu", image_pitch, rows, row_pitch);
+    if (!u8 && (((uintptr_t)d_dst | row_pitch | image_pitch) & 3u) != 0)
+        return fail("musica_export_out: MUSICA_OUT_GRADED_F32 wants d_dst and both pitches on a multiple of 4 bytes");
+    if (!c->stepped) return fail("musica_export_out: no step has run on this context");
+    {
+        // the last byte written: image count - 1, row rows - 1, byte width - 1
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, d_dst) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("musica_export_out: the allocation that holds d_dst is unknown");
+        }
+        const size_t room = (size_t)((uintptr_t)base + size - (uintptr_t)d_dst);   // bytes from d_dst to the end of its allocation
+        if (__builtin_mul_overflow((size_t)(count - 1), image_pitch, &last) || __builtin_add_overflow(last, image_bytes - row_pitch + width, &last) ||
+            last > room)
+            return fail("musica_export_out: %u images of pitch %zu (rows of pitch %zu) reach beyond the allocation that holds d_dst (%zu bytes from d_dst)",
+                        count, image_pitch, row_pitch, room);
+    }
+    const float* src = image_slice(c, c->d_graded, first);
+    if (u8) {
+        launch_export_u8(c->stream, src, c->lv[0], (int)count, (uint8_t*)d_dst, row_pitch, image_pitch);
+    } else {
+        // a pitched device-to-device copy; one over every image when the destination's images follow each other at its row pitch (the
+        // graded planes do: a plane is exactly N rows of the level-0 pitch)
+        const size_t spitch = (size_t)c->lv[0].pitch * sizeof(float);
+        if (image_pitch == image_bytes && per_image(c, c->d_graded) == c->lv[0].plane) {
+            HIP_OK(hipMemcpy2DAsync(d_dst, row_pitch, src, spitch, width, rows * count, hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            for (uint32_t k = 0; k < count; k++)
+                HIP_OK(hipMemcpy2DAsync((uint8_t*)d_dst + (size_t)k * image_pitch, row_pitch, image_slice(c, c->d_graded, first + k), spitch, width, rows,
+                                        hipMemcpyDeviceToDevice, c->stream));
+        }
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("musica_export_out: launch failed: %s", hipGetErrorString(e));
+    return 1;
+}
+
+// A caller's stream: of the context's device and not capturing (a graph captured from the caller's side must not take in the context's
+// stream, and the events below are recorded eagerly).
+static int check_caller_stream(musica_ctx* c, hipStream_t s, const char* fn) {
+    hipDevice_t dev = -1;
+    if (hipStreamGetDevice(s, &dev) != hipSuccess) { (void)hipGetLastError(); return fail("%s: not a stream of this process", fn); }
+    if (dev != c->p.device) return fail("%s: the stream belongs to device %d, the context runs on device %d", fn, (int)dev, c->p.device);
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return fail("%s: the stream's capture status is unknown", fn); }
+    if (st != hipStreamCaptureStatusNone) return fail("%s: the stream is capturing a graph (capturing these calls is not supported)", fn);
+    return 1;
+}
+static int caller_events(musica_ctx* c) {
+    if (c->ev_signal) return 1;   // keyed on the LAST resource of the block: a call that failed half-way is retried, never half-initialised
+    if (!c->ev_caller) HIP_OK(hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags(&c->ev_signal, hipEventDisableTiming));
+    return 1;
+}
+int musica_stream_wait(musica_ctx* c, void* stream) {
+    CHECK_CTX(c);
+    const hipStream_t s = (hipStream_t)stream;
+    if (!check_caller_stream(c, s, "musica_stream_wait") || !caller_events(c)) return 0;
+    HIP_OK(hipEventRecord(c->ev_caller, s));
+    HIP_OK(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
+    return 1;
+}
+int musica_stream_signal(musica_ctx* c, void* stream) {
+    CHECK_CTX(c);
+    const hipStream_t s = (hipStream_t)stream;
+    if (!check_caller_stream(c, s, "musica_stream_signal") || !caller_events(c)) return 0;
+    // a two-stream step's side stream has rejoined c->stream (ev_join) before its last launches, and a replayed graph completes as a whole
+    // before anything behind it on c->stream: this event covers all of it
+    HIP_OK(hipEventRecord(c->ev_signal, c->stream));
+    HIP_OK(hipStreamWaitEvent(s, c->ev_signal, 0));
+    return 1;
+}
 int musica_get_stats(musica_ctx* c, uint32_t idx, musica_stats* dst) {
     CHECK_CTX(c); CHECK_IMG(c, idx);
     if (!musica_stats_device(c, c->d_stats, 0)) return 0;

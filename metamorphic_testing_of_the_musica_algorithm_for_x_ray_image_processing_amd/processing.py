@@ -134,6 +134,19 @@ class SimResult(C.Structure):
         return d
 
 
+# musica_out_format: what export_out writes per image
+OUT_U8, OUT_GRADED_F32 = 0, 1
+OUT_FORMAT_COUNT = 2
+
+
+def out_geometry(image_size, fmt):
+    """(rows, bytes per row) of one image of export_out: (N - 20, N - 20) for OUT_U8, (N, 4 N) for OUT_GRADED_F32."""
+    if fmt == OUT_U8:
+        side = max(image_size - 2 * OUT_MARGIN, 0)
+        return side, side
+    return image_size, 4 * image_size
+
+
 # musica_alteration_kind
 ALTER_NONE, ALTER_TRANSLATE, ALTER_ROTATE, ALTER_COLLIMATOR, ALTER_GAUSSIAN, ALTER_POISSON = range(6)
 ALTER_KIND_COUNT = 6
@@ -248,6 +261,9 @@ ABI = {
     "musica_alter": (C.c_int, [_VP, C.c_uint32, C.POINTER(Alteration)]),
     "musica_alter_draws": (C.c_int, [_VP, C.POINTER(Alteration), C.POINTER(C.c_int32)]),
     "musica_alter_percentile": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_double)]),
+    "musica_export_out": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, _VP, C.c_size_t, C.c_size_t]),
+    "musica_stream_wait": (C.c_int, [_VP, _VP]),
+    "musica_stream_signal": (C.c_int, [_VP, _VP]),
 }
 
 _lib = None
@@ -541,6 +557,24 @@ class MusicaProcessing:
     def fuses_reduce_band(self):
         """True when level 0's reduce and band kernels are one launch (profile family `reduce_l0` covers both)."""
         return self._lib.musica_fuses_reduce_band(self._h) == 1
+
+    # ---- device-resident output and stream ordering (musica_export_out, musica_stream_*) ---------
+    def export_out(self, d_dst, first=0, count=None, fmt=OUT_U8, row_pitch=0, image_pitch=0):
+        """Images first .. first + count - 1 (default: the rest of the batch) of the last step into caller-owned device memory at d_dst,
+        enqueued on the context's stream. Pitches in bytes; 0: dense (a row's bytes, rows x row_pitch)."""
+        count = self.batch - int(first) if count is None else int(count)
+        rows, width = out_geometry(self.imageSize, fmt)
+        row_pitch = int(row_pitch) or width
+        image_pitch = int(image_pitch) or row_pitch * rows
+        self._ok(self._lib.musica_export_out(self._h, int(first), count, int(fmt), d_dst, row_pitch, image_pitch), "musica_export_out")
+
+    def stream_wait(self, stream=None):
+        """What the context enqueues from now on starts after the work already on `stream` (a hipStream_t handle; None / 0: the null stream)."""
+        self._ok(self._lib.musica_stream_wait(self._h, stream or None), "musica_stream_wait")
+
+    def stream_signal(self, stream=None):
+        """Work enqueued on `stream` from now on starts after everything enqueued on the context so far."""
+        self._ok(self._lib.musica_stream_signal(self._h, stream or None), "musica_stream_signal")
 
     # ---- similarity metrics of the metamorphic study (musica_sim_*) ---------------------------
     def sim_capture(self, slot, image_index=0):

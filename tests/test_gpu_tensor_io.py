@@ -1,0 +1,323 @@
+"""Device-resident output and stream ordering with torch (musica_export_out, musica_stream_wait / _signal, k_export_u8, tensors.py,
+batch.process_shard_device): the exported bytes against musica_get_out_pixels / musica_get_graded and the oracle, pitched destinations
+whose padding must survive, the ordering against a torch stream made deterministic with a sleeping kernel, and every refusal."""
+import numpy as np
+import pytest
+import torch
+
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import batch as BD
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import tensors as T
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd.phantom import phantom_batch
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+SENT = 0xA5
+SLEEP_CYCLES = 50_000_000     # torch.cuda._sleep: tens of milliseconds, far longer than any step below
+
+
+def _ctx(n, batch=1, flags=0):
+    p = mp.MusicaProcessing()
+    assert p.init(n, batch=batch, flags=flags | mp.FLAG_NO_AUTOTUNE), mp.last_error()
+    return p
+
+
+def _to_np(t):
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+def _stepped(kind, n, px):
+    """A context whose last step processed `px`: a plain context, a MUSICA_FLAG_CLAHE one, or musica_pipeline_last() of a depth-1 pipeline.
+    Returns (context, owner to keep alive)."""
+    b = px.shape[0]
+    if kind == "pipeline":
+        pl = mp.MusicaPipeline(n, batch=b, depth=1)
+        pl.upload(px)
+        pl.prime()
+        pl.step()
+        pl.sync()
+        return pl.last(), pl
+    c = _ctx(n, b, mp.FLAG_CLAHE if kind == "clahe" else 0)
+    assert c.execute(px), mp.last_error()
+    return c, c
+
+
+def _export_u8(c, buf, first=0, count=None, row_pitch=0, image_pitch=0, offset=0):
+    torch.cuda.synchronize()          # the sentinel fill has landed
+    c.export_out(buf.data_ptr() + offset, first, count, mp.OUT_U8, row_pitch, image_pitch)
+    c.sync()
+    return _to_np(buf)
+
+
+@pytest.mark.parametrize("kind", ["plain", "clahe", "pipeline"])
+@pytest.mark.parametrize("n", [520, 1016])
+def test_u8_export_equals_out_pixels(ob, n, kind):
+    b, w = 3, n - 20
+    px = phantom_batch(n, [21, 22, 23])
+    c, keep = _stepped(kind, n, px)
+    want = np.stack([c.out_pixels(k) for k in range(b)])
+    if kind != "clahe":
+        o = ob.Oracle(n, c.pyramidLevels, ob.ORDER_FAST).execute(px[0])
+        assert np.array_equal(want[0], o.out_pixels())
+    # dense
+    got = _export_u8(c, torch.full((b, w, w), SENT, dtype=torch.uint8, device=DEV))
+    assert np.array_equal(got, want)
+    # pitched rows (w + 13: no store wider than a byte lines up) and three padding rows per image, all of it sentinel
+    rp, ip = w + 13, (w + 13) * (w + 3)
+    got = _export_u8(c, torch.full((b * ip,), SENT, dtype=torch.uint8, device=DEV), row_pitch=rp, image_pitch=ip)
+    mask = np.zeros(b * ip, dtype=bool)
+    for k in range(b):
+        img = got[k * ip:(k + 1) * ip][:w * rp].reshape(w, rp)
+        assert np.array_equal(img[:, :w], want[k]), k
+        for r in range(w):
+            mask[k * ip + r * rp:k * ip + r * rp + w] = True
+    assert np.all(got[~mask] == SENT)
+    # images 1 and 2 only, into slots 1 and 2 of a dense three-image buffer: slot 0 keeps the sentinel
+    got = _export_u8(c, torch.full((b, w, w), SENT, dtype=torch.uint8, device=DEV), first=1, count=2, offset=w * w)
+    assert np.all(got[0] == SENT)
+    assert np.array_equal(got[1:], want[1:])
+    del keep
+
+
+@pytest.mark.parametrize("kind", ["plain", "pipeline"])
+def test_f32_export_equals_graded_bit_for_bit(kind):
+    n, b = 520, 3
+    px = phantom_batch(n, [31, 32, 33])
+    c, keep = _stepped(kind, n, px)
+    want = c.graded().view(np.uint32)
+    out = torch.full((b, n, n), float("nan"), dtype=torch.float32, device=DEV)
+    torch.cuda.synchronize()
+    c.export_out(out.data_ptr(), 0, b, mp.OUT_GRADED_F32)            # one copy over every image
+    c.sync()
+    assert np.array_equal(_to_np(out).view(np.uint32), want)
+    # pitched: rows of n + 4 floats, images n + 1 rows apart (one copy per image), images 1 .. 2 into slots 1 .. 2
+    rp, ip = (n + 4) * 4, (n + 4) * 4 * (n + 1)
+    buf = torch.full((b * ip // 4,), -7.0, dtype=torch.float32, device=DEV)
+    torch.cuda.synchronize()
+    c.export_out(buf.data_ptr() + ip, 1, 2, mp.OUT_GRADED_F32, rp, ip)
+    c.sync()
+    got = _to_np(buf).view(np.uint32)
+    sent = np.float32(-7.0).view(np.uint32)
+    assert np.all(got[:ip // 4] == sent)
+    for k in (1, 2):
+        img = got[k * ip // 4:(k + 1) * ip // 4].reshape(n + 1, n + 4)
+        assert np.array_equal(img[:n, :n], want[k]), k
+        assert np.all(img[:n, n:] == sent) and np.all(img[n] == sent)
+    del keep
+
+
+def _snapshot(c):
+    return [c.graded()] + [c.out_pixels(k) for k in range(c.batch)] + [np.array(c.stats(k).as_row()) for k in range(c.batch)] + \
+           [c.grad_hist(k) for k in range(c.batch)] + [c.noise_hist(0, k) for k in range(c.batch)] + [c.input_pixels()]
+
+
+def test_export_changes_nothing_and_follows_the_next_step():
+    n, b, w = 520, 3, 500
+    px, px2 = phantom_batch(n, [41, 42, 43]), phantom_batch(n, [44, 45, 46])
+    c = _ctx(n, b)
+    assert c.execute(px)
+    before = _snapshot(c)
+    u8 = torch.empty((b, w, w), dtype=torch.uint8, device=DEV)
+    f32 = torch.empty((b, n, n), dtype=torch.float32, device=DEV)
+    c.export_out(u8.data_ptr())
+    c.export_out(f32.data_ptr(), fmt=mp.OUT_GRADED_F32)
+    c.sync()
+    after = _snapshot(c)
+    for a, z in zip(before, after):
+        assert np.array_equal(a.view(np.uint8), z.view(np.uint8))
+    assert np.array_equal(_to_np(u8), np.stack(before[1:1 + b]))
+    assert c.execute(px2)
+    c.export_out(u8.data_ptr())
+    c.sync()
+    want2 = np.stack([c.out_pixels(k) for k in range(b)])
+    assert np.array_equal(_to_np(u8), want2)
+    assert not np.array_equal(want2, np.stack(before[1:1 + b]))
+
+
+@pytest.fixture(params=["default", "two_streams_graph"])
+def ordering_env(request, monkeypatch):
+    """The default dispatch of the size below (one stream, eager) and a two-stream context replaying a graph (its side stream must have
+    rejoined before musica_stream_signal's event)."""
+    if request.param == "two_streams_graph":
+        monkeypatch.setenv("MUSICA_STREAMS", "2")
+        monkeypatch.setenv("MUSICA_GRAPH", "1")
+    return request.param
+
+
+def _streams():
+    """Four torch streams. The HIP runtime maps streams round-robin onto a few hardware queues, and two streams that share a queue run in
+    submission order whatever their events say: over four consecutive streams, most are on a queue of their own against the context's."""
+    return [torch.cuda.Stream(DEV) for _ in range(4)]
+
+
+def test_input_ordering_waits_for_the_torch_stream(ob, ordering_env):
+    n = 520
+    px = phantom_batch(n, [51])
+    tp = T.TensorProcessor(n, batch=1, device=DEV)
+    if ordering_env == "two_streams_graph":
+        assert tp.proc.dispatch() == (2, True)
+    want = ob.Oracle(n, tp.proc.pyramidLevels, ob.ORDER_FAST).execute(px[0]).out_pixels()
+    src = torch.from_numpy(px).to(DEV)
+    x = torch.empty_like(src)
+    for k, s in enumerate(_streams()):
+        x.view(torch.int16).zero_()                   # stale content: zeros
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s):
+            torch.cuda._sleep(SLEEP_CYCLES)
+            x.view(torch.int16).copy_(src.view(torch.int16))   # lands only after the sleep
+            out = tp(x)
+            got = out.clone()
+        assert np.array_equal(_to_np(got)[0], want), k
+
+
+def test_output_ordering_signals_the_torch_stream(ordering_env):
+    n = 520
+    px = phantom_batch(n, [52])
+    tp = T.TensorProcessor(n, batch=1, device=DEV)
+    if ordering_env == "two_streams_graph":
+        assert tp.proc.dispatch() == (2, True)
+    x = torch.from_numpy(px).to(DEV)
+    out = tp(x)
+    want = _to_np(out)
+    busy = torch.cuda.Stream(DEV)
+    for k, s in enumerate(_streams()):
+        torch.cuda.synchronize()
+        with torch.cuda.stream(busy):
+            torch.cuda._sleep(SLEEP_CYCLES)
+        tp.proc.stream_wait(busy.cuda_stream)     # the library's stream is held up by the sleeping stream, `s` is not
+        with torch.cuda.stream(s):
+            out.fill_(SENT)
+            tp(x, out=out)
+            got = out.clone()                     # without musica_stream_signal this copy overtakes the export
+        assert np.array_equal(_to_np(got), want), k
+
+
+def test_tensor_processor_outputs_and_stats():
+    n, b = 520, 2
+    px = phantom_batch(n, [61, 62])
+    tp = T.TensorProcessor(n, batch=b, device=DEV)
+    x = torch.from_numpy(px).to(DEV)
+    out8 = tp(x)
+    graded = tp(x, output="graded")
+    rows = tp.stats(image_id_base=7, image_id_stride=3)
+    assert out8.shape == (b, n - 20, n - 20) and out8.dtype == torch.uint8
+    assert graded.shape == (b, n, n) and graded.dtype == torch.float32
+    torch.cuda.synchronize()
+    assert np.array_equal(_to_np(out8), np.stack([tp.proc.out_pixels(k) for k in range(b)]))
+    assert np.array_equal(_to_np(graded).view(np.uint32), tp.proc.graded().view(np.uint32))
+    for k in range(b):
+        st = tp.proc.stats(k)
+        st.image_id = 7 + 3 * k
+        assert np.array_equal(_to_np(rows)[k], BD.stats_to_row(st))
+    # a strided caller tensor: its rows keep their padding
+    big = torch.full((b, n - 10, n - 7), SENT, dtype=torch.uint8, device=DEV)
+    view = big[:, 3:3 + n - 20, 5:5 + n - 20]
+    tp(x, out=view)
+    got = _to_np(big)
+    assert np.array_equal(got[:, 3:3 + n - 20, 5:5 + n - 20], _to_np(out8))
+    got[:, 3:3 + n - 20, 5:5 + n - 20] = SENT
+    assert np.all(got == SENT)
+    # batch 1 takes and returns two-dimensional tensors
+    t1 = T.TensorProcessor(n, batch=1, device=DEV)
+    o1 = t1(x[1])
+    assert o1.shape == (n - 20, n - 20)
+    assert np.array_equal(_to_np(o1), _to_np(out8)[1])
+
+
+def _refused(fn, *args, match=None):
+    with pytest.raises(RuntimeError) as e:
+        fn(*args)
+    if match:
+        assert match in str(e.value), str(e.value)
+
+
+def test_refusals_leave_the_context_working():
+    n, b, w = 520, 3, 500
+    px = phantom_batch(n, [71, 72, 73])
+    lib = mp.load_library()
+    fresh = _ctx(n, b)
+    dst = torch.full((b, n, n), 0.0, dtype=torch.float32, device=DEV)     # large enough for every format
+    _refused(fresh.export_out, dst.data_ptr(), match="no step")
+    c = _ctx(n, b)
+    assert c.execute(px)
+    want = np.stack([c.out_pixels(k) for k in range(b)])
+    d = dst.data_ptr()
+    assert lib.musica_export_out(None, 0, 1, mp.OUT_U8, d, w, w * w) == 0 and "ctx is NULL" in mp.last_error()
+    _refused(c.export_out, None, match="d_dst is NULL")
+    _refused(c.export_out, d, 0, b, mp.OUT_FORMAT_COUNT, match="format")
+    _refused(c.export_out, d, 0, b, 99, match="format")
+    assert lib.musica_export_out(c._h, 0, 0, mp.OUT_U8, d, w, w * w) == 0 and "count is 0" in mp.last_error()
+    _refused(c.export_out, d, 2, 2, match="exceed the batch")
+    _refused(c.export_out, d, 0, b, mp.OUT_U8, w - 1, match="row pitch")
+    _refused(c.export_out, d, 0, b, mp.OUT_U8, w, w * w - 1, match="image pitch")
+    _refused(c.export_out, d, 0, b, mp.OUT_GRADED_F32, 4 * n - 4, match="row pitch")
+    _refused(c.export_out, d, 0, b, mp.OUT_GRADED_F32, 4 * n, 4 * n * n - 4, match="image pitch")
+    _refused(c.export_out, d + 2, 0, 1, mp.OUT_GRADED_F32, match="multiple of 4")
+    _refused(c.export_out, d, 0, 1, mp.OUT_GRADED_F32, 4 * n + 2, match="multiple of 4")
+    # pinned host memory: refused before anything is enqueued
+    h = lib.musica_host_alloc(c._h, b * n * n * 4)
+    assert h
+    try:
+        _refused(c.export_out, h, match="not device memory")
+    finally:
+        lib.musica_host_free(c._h, h)
+    # a device allocation exactly one byte short of what the export writes, for each format
+    for fmt, need in ((mp.OUT_U8, b * w * w), (mp.OUT_GRADED_F32, b * n * n * 4)):
+        p = c.device_alloc(need - 1)
+        try:
+            _refused(c.export_out, p, 0, b, fmt, match="beyond the allocation")
+            if fmt == mp.OUT_U8:
+                c.export_out(p, 0, b - 1, fmt)     # two images fit
+        finally:
+            c.sync()
+            c.device_free(p)
+    # N <= 20: no 8-bit output exists
+    tiny = _ctx(16)
+    assert tiny.execute(phantom_batch(16, [1]))
+    _refused(tiny.export_out, d, 0, 1, mp.OUT_U8, 4, 0, match="margin")
+    tiny.export_out(d, 0, 1, mp.OUT_GRADED_F32)
+    tiny.sync()
+    assert np.array_equal(_to_np(dst).reshape(-1)[:256].view(np.uint32), tiny.graded().reshape(-1).view(np.uint32))
+    # a capturing torch stream is refused by both ordering calls and the capture stays usable
+    s = torch.cuda.Stream(DEV)
+    y = torch.zeros(16, device=DEV)
+    g = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
+        _refused(c.stream_wait, s.cuda_stream, match="capturing")
+        _refused(c.stream_signal, s.cuda_stream, match="capturing")
+        y.add_(1.0)
+    torch.cuda.synchronize()
+    # the context still works
+    out = torch.full((b, w, w), SENT, dtype=torch.uint8, device=DEV)
+    assert np.array_equal(_export_u8(c, out), want)
+    c.stream_wait(None)
+    c.stream_signal(None)
+    c.sync()
+
+
+def test_process_shard_device_matches_process_shard():
+    n, b = 520, 2
+    ids = [100, 103, 106, 109, 112]
+    px = phantom_batch(n, [81, 82, 83, 84, 85])
+    host = _ctx(n, b)
+    rows_want = BD.process_shard(host, px, ids)
+    outs_want = []
+    for start in range(0, len(ids), b):
+        chunk = px[start:start + b]
+        if len(chunk) < b:
+            chunk = np.concatenate([chunk, np.repeat(chunk[-1:], b - len(chunk), axis=0)])
+        assert host.execute(chunk)
+        outs_want += [host.out_pixels(k) for k in range(min(b, len(ids) - start))]
+    dev = _ctx(n, b)
+    rows, outs = BD.process_shard_device(dev, torch.from_numpy(px).to(DEV), ids)
+    assert rows.is_cuda and outs.is_cuda and rows.dtype == torch.int32 and outs.dtype == torch.uint8
+    assert np.array_equal(_to_np(rows), rows_want)
+    assert np.array_equal(_to_np(outs), np.stack(outs_want))
+
+
+def test_one_hip_runtime_is_mapped():
+    T.TensorProcessor(64, batch=1, device=DEV)
+    assert len(T.mapped_hip_runtimes()) == 1, T.mapped_hip_runtimes()
