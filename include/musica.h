@@ -374,6 +374,11 @@ int musica_sim_compare(musica_ctx* ctx, uint32_t count, const musica_sim_query* 
  * mode="constant", cval=0) does with the 2 x 2 `matrix` (row-major) and `offset` it computes for a plane of side N - 20
  * (harness.rotated_reference). dst_slot != src_slot; src_slot must have been written. */
 int musica_sim_rotate_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, const double matrix[4], const double offset[2]);
+/* Reference slot `src_slot` under element `element` (0 .. 7) of the square's symmetry group into `dst_slot` (device to device, on the
+ * ctx stream): np.rot90(b if element < 4 else b.T, element & 3) of the (N - 20)^2 plane, the index table of MUSICA_ALTER_SYMMETRY with
+ * side N - 20 (harness.apply_symmetry). Refused before any device work: a NULL context, a slot out of range, dst_slot == src_slot, a
+ * source slot never written, element > 7, an image too small for the margin. Marks dst_slot written. */
+int musica_sim_transform_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t element);
 /* (N - 20)^2 bytes of reference slot `slot` to the host (synchronous); the slot must have been written. */
 int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
 
@@ -392,7 +397,10 @@ int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
  *   POISSON     apply_quantum_noise(src, factor): k ~ Poisson(v * factor), then float(k) / float(factor) in f32, clipped, truncated.
  * The noise draws come from Philox4x32-10 keyed by (seed, stream) with the pixel index as the counter: a pixel's value depends on
  * the spec, its source value and its index only. They follow numpy's distributions (inversion below lambda = 10, PTRS above; Box-Muller
- * for the normal) but not numpy's stream. */
+ * for the normal) but not numpy's stream.
+ *   SYMMETRY    element `dx` (0 .. 7) of the square's symmetry group (D4), np.rot90(src if dx < 4 else src.T, dx & 3), bit-exact: a
+ *               permutation of the source, no fill and no resampling (harness.apply_symmetry). Output pixel (i, j) is source pixel
+ *               0: [i, j]   1: [j, N-1-i]   2: [N-1-i, N-1-j]   3: [N-1-j, i]   4: [j, i]   5: [N-1-i, j]   6: [N-1-j, N-1-i]   7: [i, N-1-j]. */
 typedef enum musica_alteration_kind {
     MUSICA_ALTER_NONE = 0,
     MUSICA_ALTER_TRANSLATE = 1,
@@ -400,11 +408,12 @@ typedef enum musica_alteration_kind {
     MUSICA_ALTER_COLLIMATOR = 3,
     MUSICA_ALTER_GAUSSIAN = 4,
     MUSICA_ALTER_POISSON = 5,
-    MUSICA_ALTER_KIND_COUNT = 6
+    MUSICA_ALTER_SYMMETRY = 6,
+    MUSICA_ALTER_KIND_COUNT = 7
 } musica_alteration_kind;
 typedef struct musica_alteration {
     uint32_t kind;                  /* musica_alteration_kind */
-    int32_t dx, dy;                 /* TRANSLATE: x_shift, y_shift (|shift| < N) */
+    int32_t dx, dy;                 /* TRANSLATE: x_shift, y_shift (|shift| < N); SYMMETRY: dx is the element, 0 .. 7 */
     int32_t margin;                 /* ROTATE: the crop's margin, 0 <= 2 margin < N */
     int32_t shutter_h, shutter_v;   /* COLLIMATOR: 0 <= 2 shutter <= N */
     double mean, sigma;             /* GAUSSIAN: sigma finite and > 0, mean finite */
@@ -419,7 +428,7 @@ int musica_alter_set_source(musica_ctx* ctx, const uint16_t* pixels);
 /* The alteration of the source into image `image_index` of the input buffer, enqueued on the ctx stream (follow it with
  * musica_execute_device(ctx, musica_input_device_ptr(ctx))). Refused before any device work: no source, a kind out of range,
  * image_index >= batch, shifts or shutters that leave nothing, a margin that leaves no crop, a non-finite or non-positive sigma or factor,
- * a non-finite matrix or offset. It changes no other image of the input buffer, no result of the last step and no reference slot. */
+ * a non-finite matrix or offset, a symmetry element outside 0 .. 7. It changes no other image of the input buffer, no result of the last step and no reference slot. */
 int musica_alter(musica_ctx* ctx, uint32_t image_index, const musica_alteration* spec);
 /* Test hook: the N x N integer draws of a noise alteration (k of COLLIMATOR / POISSON, for every pixel; the truncated noise of GAUSSIAN),
  * the same numbers musica_alter uses. Synchronous. */

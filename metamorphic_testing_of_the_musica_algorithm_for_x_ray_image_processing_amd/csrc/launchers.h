@@ -187,6 +187,10 @@ void launch_alter(hipStream_t st, const uint16_t* src, uint16_t* out, int32_t* d
 void launch_rotate_u8(hipStream_t st, const uint8_t* src, uint8_t* out, const AlterDev& a);
 // np.percentile of the region into *out (device); hist: 768 u32 of scratch, zeroed by the caller
 void launch_percentile(hipStream_t st, const PctRegion& g, uint32_t* hist, double* out);
+// kernels_symmetry.hip: element 0 .. 7 of the square's symmetry group, np.rot90(x if element < 4 else x.T, element & 3), of a dense n x n
+// plane into another (the planes must not overlap); any n >= 1
+void launch_symmetry_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, int element);
+void launch_symmetry_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int element);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -1749,6 +1749,22 @@ int musica_sim_rotate_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_s
     return 1;
 }
 
+int musica_sim_transform_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t element) {
+    if (!c) return fail("musica_sim_transform_reference: ctx is NULL");
+    if (dst_slot >= MUSICA_SIM_SLOTS || src_slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_transform_reference: slot %u / %u >= %d", dst_slot, src_slot, MUSICA_SIM_SLOTS);
+    if (dst_slot == src_slot) return fail("musica_sim_transform_reference: dst_slot == src_slot (%u)", dst_slot);
+    if (!c->sim_written[src_slot]) return fail("musica_sim_transform_reference: slot %u was never written", src_slot);
+    if (element > 7) return fail("musica_sim_transform_reference: element %u is not one of the square's 8 symmetries (0 .. 7)", element);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_transform_reference: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    CHECK_CTX(c);
+    uint8_t* dst = sim_slot(c, dst_slot);
+    if (!dst) return 0;
+    launch_symmetry_u8(c->stream, c->d_sim_slot[src_slot], dst, c->N - 2 * MUSICA_OUT_MARGIN, (int)element);
+    HIP_OK(hipGetLastError());
+    c->sim_written[dst_slot] = true;
+    return 1;
+}
+
 int musica_sim_get_reference(musica_ctx* c, uint32_t slot, uint8_t* dst) {
     if (!c) return fail("musica_sim_get_reference: ctx is NULL");
     if (!dst) return fail("musica_sim_get_reference: dst is NULL");
@@ -1837,6 +1853,9 @@ static int alter_args(musica_ctx* c, const char* fn, const musica_alteration* s,
                 return fail("%s: factor %g: need a finite factor > 0 with 65535 * factor < 2^30", fn, s->factor);
             a.factor = s->factor;
             break;
+        case MUSICA_ALTER_SYMMETRY:
+            if (s->dx < 0 || s->dx > 7) return fail("%s: element %d is not one of the square's 8 symmetries (0 .. 7)", fn, s->dx);
+            break;
         default: break;
     }
     return 1;
@@ -1864,7 +1883,8 @@ int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
         if (!enqueue_percentile(c, a.margin, a.margin, a.crop, a.crop, 95.0)) return 0;
         fill = c->d_alter_fill;
     }
-    launch_alter(c->stream, c->d_alter_src, c->d_input + idx * nn, nullptr, a, fill);
+    if (s->kind == MUSICA_ALTER_SYMMETRY) launch_symmetry_u16(c->stream, c->d_alter_src, c->d_input + idx * nn, c->N, s->dx);   // a permutation: kernels_symmetry.hip
+    else launch_alter(c->stream, c->d_alter_src, c->d_input + idx * nn, nullptr, a, fill);
     HIP_OK(hipGetLastError());
     return 1;
 }

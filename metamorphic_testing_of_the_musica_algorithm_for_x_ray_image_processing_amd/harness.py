@@ -30,6 +30,8 @@ TRANSLATIONS = [300, 600, 900, 1200, 1500]
 ROTATIONS = [9, 18, 27, 36, 45]
 GAUSS_SIGMAS = [4.0, 16.0, 64.0, 256.0, 1024.0]
 POISSON_FACTORS = [0.1, 0.05, 0.025, 0.0125, 0.00625]
+# not in the reference: the non-identity symmetries of the square (apply_symmetry), rows d4_<e> of a study run with `symmetries`
+SYMMETRIES = (1, 2, 3, 4, 5, 6, 7)
 
 
 def scaled(values, image_size):
@@ -93,6 +95,20 @@ def clamp_rotate(image, degree):
     out = np.full((h, w), fill, dtype=np.uint16)
     out[margin:h - margin, margin:w - margin] = rot
     return out
+
+
+def apply_symmetry(image, element):
+    """Element 0 .. 7 of the symmetry group of the square (D4): np.rot90(x if element < 4 else x.T, element & 3). Output pixel (i, j) of
+    a side-n plane is input pixel 0: [i, j], 1: [j, n-1-i], 2: [n-1-i, n-1-j], 3: [n-1-j, i], 4: [j, i] (transpose), 5: [n-1-i, j]
+    (flipud), 6: [n-1-j, n-1-i] (anti-transpose), 7: [i, n-1-j] (fliplr): a permutation of the pixels, no fill and no resampling
+    (not in the reference's script). Inverses: 1 <-> 3, every other element is its own."""
+    element = int(element)
+    if not 0 <= element <= 7:
+        raise ValueError("symmetry element %d is not in 0 .. 7" % element)
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1]:
+        raise ValueError("the symmetries of the square need a square image, got %r" % (image.shape,))
+    return np.ascontiguousarray(np.rot90(image if element < 4 else image.T, element & 3))
 
 
 # ---- similarity metrics (script.py:143-198) ----------------------------------------------------------
@@ -242,6 +258,16 @@ def register_rotation(alt, unalt, degree):
     return _crop(alt, rotated_reference(unalt, degree), rotation_rects(alt.shape, unalt.shape, degree))
 
 
+def register_symmetry(alt, unalt, element):
+    """The whole altered result against the unaltered result transformed like the alteration: the margin is symmetric, so nothing is cropped."""
+    return alt, apply_symmetry(unalt, element)
+
+
+def roi_symmetry(shape):
+    """The full frame, as the region of a device-side comparison."""
+    return (0, 0, 0, 0, shape[1], shape[0])
+
+
 # ---- running the pipeline -------------------------------------------------------------------------
 
 class Runner:
@@ -316,7 +342,7 @@ SLOT_UNALTERED, SLOT_ROTATED, SLOT_VENDOR, SLOT_VENDOR_ROTATED = 0, 1, 2, 3
 VENDOR_SLOT = {SLOT_UNALTERED: SLOT_VENDOR, SLOT_ROTATED: SLOT_VENDOR_ROTATED}
 
 
-def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None):
+def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -331,7 +357,14 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     other row "reference" (the altered result vs the vendor image) and "registered_reference" (the registered crop vs the same crop of
     the vendor image, rotations: of the vendor image rotated as rotated_reference rotates; None exactly where "registered" is None).
     On the device the vendor image sits in slot 2 (musica_sim_set_vendor_reference), rotated in slot 3, and its queries join the
-    row's own launch. Without it the rows are exactly as before."""
+    row's own launch. Without it the rows are exactly as before.
+
+    symmetries: elements of the square's symmetry group (apply_symmetry; SYMMETRIES for the seven non-trivial ones). None or empty adds
+    nothing. Otherwise rows d4_<e> follow the pn_* rows: the raw image under element e (on the device: alter_symmetry), "direct" against
+    the unaltered result, "registered" over the WHOLE frame against the unaltered result under the same element, which an exactly
+    equivariant pipeline would reproduce bit for bit. On the device that reference goes into slot 1 and the transformed vendor image into
+    slot 3 (musica_sim_transform_reference; the rotation rows are done with them by then). These rows draw nothing from `rng` and do not
+    advance the noise ordinal."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     if vendor is not None:
@@ -345,6 +378,10 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     rotations = ROTATIONS if rotations is None else rotations
     sigmas = GAUSS_SIGMAS if sigmas is None else sigmas
     factors = POISSON_FACTORS if factors is None else factors
+    symmetries = [int(e) for e in (symmetries or ())]
+    for e in symmetries:
+        if not 0 <= e <= 7:
+            raise ValueError("symmetry element %d is not in 0 .. 7" % e)
     device = getattr(runner, "device_metrics", False)
     alter_on_device = getattr(runner, "device_alterations", False)
     ref8 = vendor_to_u8(vendor) if vendor is not None and not device else None   # the host metrics' vendor image
@@ -434,6 +471,20 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             runner.proc.sim_rotate_reference(SLOT_VENDOR_ROTATED, SLOT_VENDOR, d)
         return roi_rotation(shape, d), SLOT_ROTATED
 
+    def symmetry_slot(e):
+        if alter_on_device:
+            runner.proc.sim_transform_reference(SLOT_ROTATED, SLOT_UNALTERED, e)
+        else:
+            runner.proc.sim_set_reference(SLOT_ROTATED, apply_symmetry(unalt, e))
+        if vendor is not None:
+            runner.proc.sim_transform_reference(SLOT_VENDOR_ROTATED, SLOT_VENDOR, e)
+        return roi_symmetry(shape), SLOT_ROTATED
+
+    def add_symmetries(make):
+        """The d4_<e> rows; make(e): the altered raw image, or (device alterations) the call that writes it."""
+        for e in symmetries:
+            add("d4_%d" % e, make(e), lambda a, u, e=e: register_symmetry(a, u, e), lambda e=e: symmetry_slot(e))
+
     if alter_on_device:
         p = runner.proc
         for s in shutters:
@@ -449,6 +500,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             add("gn_%s" % sg, dev(lambda seed, k, sg=sg: p.alter_gaussian(0.0, sg, seed, k)))
         for f in factors:
             add("pn_%s" % f, dev(lambda seed, k, f=f: p.alter_poisson(f, seed, k)))
+        add_symmetries(lambda e: (lambda: p.alter_symmetry(e)))   # not through dev(): no draws, no ordinal
         return rows
 
     for s in shutters:
@@ -466,6 +518,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         add("gn_%s" % sg, add_gaussian_noise(raw, 0.0, sg, rng))
     for f in factors:
         add("pn_%s" % f, apply_quantum_noise(raw, f, rng))
+    add_symmetries(lambda e: apply_symmetry(raw, e))
     return rows
 
 
@@ -583,6 +636,18 @@ def run_studies(entries, runner, **study_args):
     return studies
 
 
+def symmetry_list(text):
+    """--symmetries' comma list of elements 0 .. 7."""
+    import argparse
+    try:
+        elements = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a comma-separated list of elements 0 .. 7, got %r" % text)
+    if not elements or any(not 0 <= e <= 7 for e in elements):
+        raise argparse.ArgumentTypeError("symmetry elements are 0 .. 7, got %r" % text)
+    return elements
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Metamorphic study of raw images (or a seeded phantom) on the HIP MUSICA path")
@@ -600,6 +665,9 @@ def main(argv=None):
     ap.add_argument("--device-alterations", action="store_true",
                     help="generate the alterations on the GPU (musica_alter; implies --device-metrics); the noise rows then come from a "
                          "different, reproducible, random stream than the host study's")
+    ap.add_argument("--symmetries", nargs="?", const=SYMMETRIES, default=None, type=symmetry_list, metavar="E,E,...",
+                    help="add the rows d4_<e>: the raw image under elements of the square's symmetry group (1, 3: quarter turns, 2: half turn, "
+                         "4: transpose, 5, 7: flips, 6: anti-transpose), compared over the whole frame; without a list, all seven")
     args = ap.parse_args(argv)
     if args.cli and args.device_alterations:
         ap.error("--device-alterations writes the in-process library's input buffer: it cannot be combined with --cli")
@@ -623,9 +691,10 @@ def main(argv=None):
     runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics, device_alterations=args.device_alterations)
     try:
         if args.manifest:
-            studies = run_studies(entries, runner)
+            studies = run_studies(entries, runner, symmetries=args.symmetries)
         else:
-            studies = [(name, run_study(raw, runner, rng=np.random.default_rng(0), vendor=vendor if args.reference else None))]
+            studies = [(name, run_study(raw, runner, rng=np.random.default_rng(0), vendor=vendor if args.reference else None,
+                                        symmetries=args.symmetries))]
     finally:
         runner.close()
     write_studies_csvs(studies, args.out, mean_cnr=not args.cli)

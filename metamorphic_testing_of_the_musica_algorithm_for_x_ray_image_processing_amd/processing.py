@@ -148,8 +148,8 @@ def out_geometry(image_size, fmt):
 
 
 # musica_alteration_kind
-ALTER_NONE, ALTER_TRANSLATE, ALTER_ROTATE, ALTER_COLLIMATOR, ALTER_GAUSSIAN, ALTER_POISSON = range(6)
-ALTER_KIND_COUNT = 6
+ALTER_NONE, ALTER_TRANSLATE, ALTER_ROTATE, ALTER_COLLIMATOR, ALTER_GAUSSIAN, ALTER_POISSON, ALTER_SYMMETRY = range(7)
+ALTER_KIND_COUNT = 7
 
 
 class Alteration(C.Structure):
@@ -257,6 +257,7 @@ ABI = {
     "musica_sim_compare": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimResult)]),
     "musica_sim_rotate_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "musica_sim_get_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
+    "musica_sim_transform_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_set_source": (C.c_int, [_VP, _U16P]),
     "musica_alter": (C.c_int, [_VP, C.c_uint32, C.POINTER(Alteration)]),
     "musica_alter_draws": (C.c_int, [_VP, C.POINTER(Alteration), C.POINTER(C.c_int32)]),
@@ -615,6 +616,13 @@ class MusicaProcessing:
         mm, oo = (C.c_double * 4)(*[float(v) for v in m.ravel()]), (C.c_double * 2)(*[float(v) for v in off])
         self._ok(self._lib.musica_sim_rotate_reference(self._h, int(dst_slot), int(src_slot), mm, oo), "musica_sim_rotate_reference")
 
+    def sim_transform_reference(self, dst_slot, src_slot, element):
+        """Reference slot `src_slot` as harness.apply_symmetry(slot, element) (element 0 .. 7 of the square's symmetries) into `dst_slot`,
+        on the device."""
+        if int(element) < 0:
+            raise ValueError("symmetry element %d is not in 0 .. 7" % element)
+        self._ok(self._lib.musica_sim_transform_reference(self._h, int(dst_slot), int(src_slot), int(element)), "musica_sim_transform_reference")
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -654,6 +662,10 @@ class MusicaProcessing:
     def alter_rotate(self, degree, image_index=0):
         """harness.clamp_rotate(src, degree)."""
         self.alter(self.rotate_spec(self.imageSize, degree), image_index)
+
+    def alter_symmetry(self, element, image_index=0):
+        """harness.apply_symmetry(src, element): np.rot90(src if element < 4 else src.T, element & 3), element 0 .. 7."""
+        self.alter(Alteration(kind=ALTER_SYMMETRY, dx=int(element)), image_index)
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""

@@ -1,0 +1,223 @@
+"""The square's eight symmetries on the device (kernels_symmetry.hip): musica_alter's MUSICA_ALTER_SYMMETRY and
+musica_sim_transform_reference against harness.apply_symmetry bit for bit on every path of the kernels (row words of 16, 4 and 1 or
+2 bytes; dword tiles, edge tiles, planes smaller than a tile), what they must leave alone, their refusals, and the d4_* rows of a study
+on its three paths.
+
+Nothing here asserts how symmetric the pipeline is: the registered similarity of a d4_* row is a finding, not a
+premise. Only the identity's row has a known value."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import harness as H
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd.phantom import phantom
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-12   # what the similarity tests hold between the device metrics and numpy's
+
+
+def _ctx(n, levels=4, batch=1):
+    p = mp.MusicaProcessing(device=0)
+    assert p.init(n, levels=levels, batch=batch), mp.last_error()
+    return p
+
+
+def _full_range_u16(n, seed):
+    a = np.random.default_rng(seed).integers(0, 65536, (n, n), dtype=np.uint16)
+    a[0, 0], a[-1, -1] = 0, 65535
+    a[0, -1], a[-1, 0] = 65535, 0          # the corners tell the eight elements apart even at a glance
+    assert a.min() == 0 and a.max() == 65535
+    return a
+
+
+# 44: below the 64-pixel tile; 137: odd (pixel by pixel everywhere); 136, 1000: multiples of 8 but not of the tile (dword tiles inside,
+# edge tiles around; 272- and 2000-byte rows: 16-byte words); 138: even, rows of 276 bytes (4-byte words); 2048, 3072: whole tiles
+@pytest.mark.parametrize("n", [44, 137, 136, 138, 1000, 2048, 3072])
+def test_alter_symmetry_is_bit_identical(n):
+    raw = _full_range_u16(n, n)
+    p = _ctx(n)
+    p.alter_set_source(raw)
+    for e in range(8):
+        p.alter_symmetry(e)
+        got = p.input_pixels()[0]
+        assert np.array_equal(got, H.apply_symmetry(raw, e)), (n, e)
+    p.cleanup()
+
+
+def test_only_the_named_image_is_written():
+    n = 200
+    raw = _full_range_u16(n, 1)
+    p = _ctx(n, batch=3)
+    base = np.stack([_full_range_u16(n, 10 + k) for k in range(3)])
+    p.upload(base)
+    p.alter_set_source(raw)
+    for e in range(8):
+        p.alter_symmetry(e, image_index=1)
+        got = p.input_pixels()
+        assert np.array_equal(got[0], base[0]) and np.array_equal(got[2], base[2]), e
+        assert np.array_equal(got[1], H.apply_symmetry(raw, e)), e
+    p.cleanup()
+
+
+# sides 44, 137, 1000 (4-byte row words, dword tiles), 3052 (the same at the study's size); 137: bytes
+@pytest.mark.parametrize("n", [64, 157, 1020, 3072])
+def test_transform_reference_is_bit_identical(n):
+    nw = n - 2 * mp.OUT_MARGIN
+    rng = np.random.default_rng(n)
+    plane = rng.integers(0, 256, (nw, nw), dtype=np.uint8)
+    other = rng.integers(0, 256, (nw, nw), dtype=np.uint8)
+    p = _ctx(n)
+    p.sim_set_reference(0, plane)
+    p.sim_set_reference(7, other)
+    for e in range(8):
+        dst = 1 + e % 6
+        p.sim_transform_reference(dst, 0, e)
+        assert np.array_equal(p.sim_get_reference(dst), H.apply_symmetry(plane, e)), (n, e)
+        assert np.array_equal(p.sim_get_reference(0), plane) and np.array_equal(p.sim_get_reference(7), other), (n, e)
+    # slots 1 .. 6 hold elements 6, 7, 2, 3, 4, 5: a later transform changed none of the earlier ones
+    for dst, e in ((1, 6), (2, 7), (3, 2), (4, 3), (5, 4), (6, 5)):
+        assert np.array_equal(p.sim_get_reference(dst), H.apply_symmetry(plane, e)), (n, dst)
+    p.sim_transform_reference(0, 1, 6)      # a transformed slot is a source like any other: the anti-transpose is its own inverse
+    assert np.array_equal(p.sim_get_reference(0), plane)
+    p.cleanup()
+
+
+def test_refusals_leave_the_context_usable():
+    n, levels = 264, 4
+    raw = phantom(n, 25, noise=4.0)
+    p = _ctx(n, levels)
+    lib = mp.load_library()
+    assert p.execute(raw)
+    p.sim_capture(0)
+    p.alter_set_source(raw)
+    p.alter_none()
+    graded, slot0, inp = p.graded().copy(), p.sim_get_reference(0), p.input_pixels().copy()
+
+    def refused(rc, words):
+        assert rc == 0
+        msg = mp.last_error()
+        assert words in msg, msg
+
+    for bad in (8, -1, 1 << 20):
+        refused(lib.musica_alter(p._h, 0, C.byref(mp.Alteration(kind=mp.ALTER_SYMMETRY, dx=bad))), "element")
+    refused(lib.musica_alter(p._h, 1, C.byref(mp.Alteration(kind=mp.ALTER_SYMMETRY, dx=1))), "image_index")
+    refused(lib.musica_alter(p._h, 0, C.byref(mp.Alteration(kind=mp.ALTER_KIND_COUNT))), "kind")
+    draws = np.empty((n, n), np.int32)
+    refused(lib.musica_alter_draws(p._h, C.byref(mp.Alteration(kind=mp.ALTER_SYMMETRY, dx=1)), draws.ctypes.data_as(C.POINTER(C.c_int32))), "draws no noise")
+    refused(lib.musica_sim_transform_reference(None, 1, 0, 1), "NULL")
+    refused(lib.musica_sim_transform_reference(p._h, 1, 0, 8), "element")
+    refused(lib.musica_sim_transform_reference(p._h, 0, 0, 1), "dst_slot == src_slot")
+    refused(lib.musica_sim_transform_reference(p._h, 1, 5, 1), "never written")
+    refused(lib.musica_sim_transform_reference(p._h, mp.SIM_SLOTS, 0, 1), "slot")
+    refused(lib.musica_sim_transform_reference(p._h, 1, mp.SIM_SLOTS, 1), "slot")
+    with pytest.raises(RuntimeError):
+        p.alter_symmetry(8)
+    with pytest.raises(RuntimeError):
+        p.sim_transform_reference(1, 0, 8)
+    with pytest.raises(RuntimeError):
+        p.alter_draws(mp.Alteration(kind=mp.ALTER_SYMMETRY, dx=3))
+    fresh = _ctx(n, levels)
+    refused(lib.musica_alter(fresh._h, 0, C.byref(mp.Alteration(kind=mp.ALTER_SYMMETRY, dx=1))), "no source")
+    small = _ctx(2 * mp.OUT_MARGIN)
+    refused(lib.musica_sim_transform_reference(small._h, 1, 0, 1), "never written")
+    small.cleanup()
+    # nothing was touched by the refused calls: no image, no result, no slot; slot 1 is still unwritten
+    assert np.array_equal(p.input_pixels(), inp) and np.array_equal(p.graded(), graded) and np.array_equal(p.sim_get_reference(0), slot0)
+    with pytest.raises(RuntimeError):
+        p.sim_get_reference(1)
+    # a successful alteration and transform change neither the last step's results nor the source slot ...
+    p.alter_symmetry(3)
+    p.sim_transform_reference(1, 0, 3)
+    assert np.array_equal(p.graded(), graded) and np.array_equal(p.sim_get_reference(0), slot0)
+    assert np.array_equal(p.sim_get_reference(1), H.apply_symmetry(slot0, 3))
+    # ... and the step on the resident buffer processes what the alteration wrote
+    assert p.execute_device()
+    p.sync()
+    assert fresh.execute(H.apply_symmetry(raw, 3))
+    assert np.array_equal(p.graded(), fresh.graded())
+    assert np.array_equal(p.input_pixels()[0], H.apply_symmetry(raw, 3))
+    # the whole frame is the region of a registered comparison
+    res = p.sim_compare([(0, 1) + H.roi_symmetry(slot0.shape)])[0]
+    assert res["pixels"] == (n - 20) ** 2
+    p.cleanup()
+    fresh.cleanup()
+
+
+def _grids(n):
+    return dict(shutters=H.scaled(H.SHUTTERS, n)[:1], translations=H.scaled(H.TRANSLATIONS, n)[:1], rotations=[9, 45],
+                sigmas=[16.0], factors=[0.05])
+
+
+def _vendor(n, levels, seed):
+    """A synthetic vendor image: the phantom of another seed processed here, as 16-bit stored values with noise in the low byte."""
+    p = _ctx(n, levels)
+    assert p.execute(phantom(n, seed + 100, noise=4.0)), mp.last_error()
+    u = p.out_pixels()
+    p.cleanup()
+    low = np.random.default_rng(seed).integers(0, 256, size=u.shape, dtype=np.uint16)
+    return ((255 - u.astype(np.uint16)) << 8) | low
+
+
+def _study(n, levels, vendor, symmetries, **runner_args):
+    runner = H.Runner(n, levels, **runner_args)
+    rows = H.run_study(phantom(n, 11, noise=4.0), runner, rng=np.random.default_rng(5), vendor=vendor, symmetries=symmetries, **_grids(n))
+    runner.close()
+    return rows
+
+
+@pytest.mark.parametrize("with_vendor", [False, True])
+@pytest.mark.parametrize("n, levels", [(264, 4), (520, 0)])
+def test_study_rows_agree_on_the_three_paths(n, levels, with_vendor):
+    vendor = _vendor(n, levels, 7) if with_vendor else None
+    parts = ("direct", "registered") + (("reference", "registered_reference") if with_vendor else ())
+    studies = {}
+    for name, args in (("host", {}), ("metrics", dict(device_metrics=True)), ("alterations", dict(device_alterations=True))):
+        rows = _study(n, levels, vendor, H.SYMMETRIES, **args)
+        plain = _study(n, levels, vendor, None, **args)
+        names = [r["alteration"] for r in rows]
+        assert names[len(plain):] == ["d4_%d" % e for e in H.SYMMETRIES], name
+        assert rows[:len(plain)] == plain, name           # every other row is the row of the study without symmetries
+        studies[name] = rows[len(plain):]
+        for r in studies[name]:
+            assert set(r) == {"alteration", "mean_cnr"} | set(parts), (name, r["alteration"])
+            assert all(r[part] is not None for part in parts), (name, r["alteration"])   # the whole frame is always registered
+    assert studies["alterations"] == studies["metrics"]   # all five numbers of every part, and mean_cnr, exactly
+    for h, d in zip(studies["host"], studies["metrics"]):
+        assert h["alteration"] == d["alteration"] and h["mean_cnr"] == d["mean_cnr"]
+        for part in parts:
+            for k in mp.SIM_METRICS:
+                assert abs(h[part][k] - d[part][k]) <= TOL, (h["alteration"], part, k, h[part][k], d[part][k])
+
+
+@pytest.mark.parametrize("runner_args", [{}, dict(device_metrics=True), dict(device_alterations=True)])
+def test_the_identity_row_is_the_unaltered_row(runner_args):
+    n, levels = 264, 4
+    runner = H.Runner(n, levels, **runner_args)
+    rows = H.run_study(phantom(n, 11, noise=4.0), runner, rng=np.random.default_rng(5), symmetries=(0,), **_grids(n))
+    runner.close()
+    first, last = rows[0], rows[-1]
+    assert first["alteration"] == "unaltered" and last["alteration"] == "d4_0"
+    assert last["direct"] == first["direct"] and last["registered"] == first["direct"]
+    assert last["mean_cnr"] == first["mean_cnr"]
+
+
+def test_cli_symmetries_writes_the_rows(tmp_path):
+    import csv
+    import os
+    out = str(tmp_path / "out")
+    assert H.main(["--device-alterations", "--symmetries", "--size", "512", "--levels", "5", "--out", out]) == 0
+    d4 = ["d4_%d" % e for e in H.SYMMETRIES]
+    direct = list(csv.reader(open(os.path.join(out, "direct_robustness.csv"))))
+    reg = list(csv.reader(open(os.path.join(out, "reg_based_robustness.csv"))))
+    cnr = list(csv.reader(open(os.path.join(out, "mean_cnr.csv"))))
+    assert direct[0] == H.CSV_HEADER and reg[0] == H.CSV_HEADER
+    assert [r[1] for r in direct[-7:]] == d4 and [r[1] for r in reg[-7:]] == d4 and [r[1] for r in cnr[-7:]] == d4
+    assert len(direct) == 1 + 30 + 7 and len(cnr) == 1 + 1 + 30 + 7
+    plain = str(tmp_path / "plain")
+    assert H.main(["--device-alterations", "--size", "512", "--levels", "5", "--out", plain]) == 0
+    for name in ("direct_robustness.csv", "reg_based_robustness.csv", "mean_cnr.csv"):
+        with_rows, without = open(os.path.join(out, name)).read(), open(os.path.join(plain, name)).read()
+        assert with_rows.startswith(without) and with_rows.count("\n") == without.count("\n") + 7, name
