@@ -153,6 +153,10 @@ def lib():
     L.musica_oracle_render_noise_hist.argtypes = [vp, u8p]
     L.musica_oracle_render_grad_hist.restype = None
     L.musica_oracle_render_grad_hist.argtypes = [vp, u8p]
+    L.musica_oracle_k_render_noise_hist.restype = None
+    L.musica_oracle_k_render_noise_hist.argtypes = [u32p, HistMaxPoint, u8p]
+    L.musica_oracle_k_render_grad_hist.restype = None
+    L.musica_oracle_k_render_grad_hist.argtypes = [u32p, HistMaxPoint, C.POINTER(GradCurve), u8p]
     L.musica_oracle_read_raw.restype = C.c_int
     L.musica_oracle_read_raw.argtypes = [C.c_char_p, C.c_uint32, u16p]
     # single-shader entry points
@@ -385,6 +389,21 @@ def k_upsample(a, out_side):
     return out
 
 
+def _k_two_to_one(fn, a, b):
+    a, b = _sq(a), _sq(b)
+    out = np.empty_like(a)
+    fn(_f32p(a), _f32p(b), a.shape[0], _f32p(out))
+    return out
+
+
+def k_difference(a, b):
+    return _k_two_to_one(lib().musica_oracle_k_difference, a, b)
+
+
+def k_addition(a, b):
+    return _k_two_to_one(lib().musica_oracle_k_addition, a, b)
+
+
 def k_sdev(a, order=ORDER_REFERENCE):
     a = _sq(a)
     out = np.empty_like(a)
@@ -406,8 +425,9 @@ def k_histogram_max(hist):
     return (p.maxValue, p.maxBin)
 
 
-def k_contrast_curve_generate(max_bin, low, high):
-    c = ContrastCurve()
+def k_contrast_curve_generate(max_bin, low, high, curve=None):
+    """curve: the buffer as it is before the dispatch (stale points stay); a fresh zeroed one when None."""
+    c = ContrastCurve() if curve is None else curve
     lib().musica_oracle_k_contrast_curve_generate(HistMaxPoint(0, max_bin), ContrastParams(low, high), C.byref(c))
     return c
 
@@ -452,9 +472,9 @@ def k_gradation_histogram(img, relevant, groups):
     return h
 
 
-def k_gradation_curve_generate(hist):
+def k_gradation_curve_generate(hist, curve=None):
     h = np.ascontiguousarray(hist, dtype=np.uint32)
-    c = GradCurve()
+    c = GradCurve() if curve is None else curve
     lib().musica_oracle_k_gradation_curve_generate(h.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(c))
     return c
 
@@ -463,6 +483,21 @@ def k_apply_gradation_curve(img, curve):
     a = _sq(img)
     out = np.empty_like(a)
     lib().musica_oracle_k_apply_gradation_curve(_f32p(a), a.shape[0], C.byref(curve), _f32p(out))
+    return out
+
+
+def k_render_noise_hist(hist, max_value, max_bin):
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    out = np.empty((128, 512, 4), dtype=np.uint8)
+    lib().musica_oracle_k_render_noise_hist(h.ctypes.data_as(C.POINTER(C.c_uint32)), HistMaxPoint(max_value, max_bin), out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out
+
+
+def k_render_grad_hist(hist, max_value, max_bin, curve):
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    out = np.empty((128, 512, 4), dtype=np.uint8)
+    lib().musica_oracle_k_render_grad_hist(h.ctypes.data_as(C.POINTER(C.c_uint32)), HistMaxPoint(max_value, max_bin), C.byref(curve),
+                                           out.ctypes.data_as(C.POINTER(C.c_uint8)))
     return out
 
 
@@ -548,3 +583,229 @@ def ref_write_bmp_rgba(path, data):
     h, w, c = d.shape
     assert c == 4
     assert L.ref_write_bmp_rgba(os.fsencode(path), w, h, d.ctypes.data_as(C.POINTER(C.c_uint8))) != 0
+
+
+# ---- the reference's compute shaders, compiled for the host (oracle/ref_shaders.cpp) ----------------------------
+# Same argument conventions as the k_* helpers above, so a test can call both with the same arrays. Only
+# oracle/_ref/libref_shaders.so is loaded: neither the oracle library nor the reference tree is needed.
+
+REF_SHADERS_PATH = os.path.join(_HERE, "_ref", "libref_shaders.so")
+_ref_lib = None
+
+
+def ref_shaders_available():
+    return os.path.exists(REF_SHADERS_PATH)
+
+
+def reference_present():
+    """Whether the reference tree the Makefile builds oracle/_ref/ from is there."""
+    return subprocess.run(["make", "-s", "-C", _HERE, "ref_present"], capture_output=True).returncode == 0
+
+
+def ensure_ref_shaders():
+    """Build oracle/_ref/libref_shaders.so when it is missing and the reference tree is present. Returns whether the library
+    exists afterwards; raises when the tree is present and the build fails. False means both are absent."""
+    if not ref_shaders_available() and reference_present():
+        subprocess.run(["make", "-C", _HERE, "ref_shaders"], check=True, capture_output=True)
+        if not ref_shaders_available():
+            raise RuntimeError("make -C oracle ref_shaders left no _ref/libref_shaders.so although the reference tree is present")
+    return ref_shaders_available()
+
+
+def ref_lib():
+    global _ref_lib
+    if _ref_lib is not None:
+        return _ref_lib
+    L = C.CDLL(REF_SHADERS_PATH)
+    fp, u32p, u16p, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+    u32 = C.c_uint32
+    sigs = {
+        "ref_img_sqrt": [u16p, u32, fp],
+        "ref_img_max_reduce": [fp, u32, fp],
+        "ref_min_reduce": [fp, u32, fp],
+        "ref_img_normalize": [fp, u32, fp, fp, fp],
+        "ref_img_smooth": [fp, u32, fp],
+        "ref_img_smooth_upsampled": [fp, u32, fp],
+        "ref_img_downsample": [fp, u32, fp],
+        "ref_img_upsample": [fp, u32, fp, u32, u32],
+        "ref_img_difference": [fp, fp, u32, fp],
+        "ref_img_addition": [fp, fp, u32, fp],
+        "ref_img_sdev": [fp, u32, fp],
+        "ref_noise_hist": [fp, u32, u32, u32p],
+        "ref_img_histogram_max": [u32p, u32, C.POINTER(HistMaxPoint)],
+        "ref_contrast_curve_generate": [HistMaxPoint, ContrastParams, C.POINTER(ContrastCurve)],
+        "ref_contrast_curve_apply": [fp, fp, u32, C.POINTER(ContrastCurve), fp],
+        "ref_img_cnr": [fp, u32, HistMaxPoint, fp],
+        "ref_noise_reduction": [fp, u32, fp, u32, NrParams, fp],
+        "ref_img_relevant": [fp, u32, fp, u32, fp],
+        "ref_gradation_histogram": [fp, fp, u32, u32, u32p],
+        "ref_gradation_curve_generate": [u32p, C.POINTER(GradCurve)],
+        "ref_img_apply_gradation_curve": [fp, u32, C.POINTER(GradCurve), fp],
+        "ref_noise_hist_render": [u32p, HistMaxPoint, u8p, u32, u32],
+        "ref_gradation_curve_debug_render": [u32p, HistMaxPoint, C.POINTER(GradCurve), u8p, u32, u32],
+    }
+    for name, args in sigs.items():
+        fn = getattr(L, name)
+        fn.restype = None
+        fn.argtypes = args
+    _ref_lib = L
+    return L
+
+
+def _u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _img_to_img(name, a, out_side=None):
+    a = _sq(a)
+    s = a.shape[0] if out_side is None else out_side
+    out = np.zeros((s, s), dtype=np.float32)
+    getattr(ref_lib(), name)(_f32p(a), a.shape[0], _f32p(out))
+    return out
+
+
+def ref_sqrt(px):
+    px = np.ascontiguousarray(px, dtype=np.uint16)
+    out = np.zeros(px.shape, dtype=np.float32)
+    ref_lib().ref_img_sqrt(px.ctypes.data_as(C.POINTER(C.c_uint16)), px.shape[0], _f32p(out))
+    return out
+
+
+def ref_max_reduce(a):
+    return _img_to_img("ref_img_max_reduce", a, (np.shape(a)[0] + 7) // 8)
+
+
+def ref_min_reduce(a):
+    return _img_to_img("ref_min_reduce", a, (np.shape(a)[0] + 7) // 8)
+
+
+def ref_normalize(a, minv, maxv):
+    a = _sq(a)
+    out = np.zeros_like(a)
+    mx, mn = np.array([[maxv]], dtype=np.float32), np.array([[minv]], dtype=np.float32)
+    ref_lib().ref_img_normalize(_f32p(a), a.shape[0], _f32p(mx), _f32p(mn), _f32p(out))
+    return out
+
+
+def ref_smooth(a):
+    return _img_to_img("ref_img_smooth", a)
+
+
+def ref_smooth_upsampled(a):
+    return _img_to_img("ref_img_smooth_upsampled", a)
+
+
+def ref_downsample(a):
+    return _img_to_img("ref_img_downsample", a, (np.shape(a)[0] + 1) // 2)
+
+
+def ref_upsample(a, out_side, dispatch_side=None, out=None):
+    """out: the output image as it is before the dispatch (zeros when None); returns a new array."""
+    a = _sq(a)
+    out = np.zeros((out_side, out_side), dtype=np.float32) if out is None else np.array(out, dtype=np.float32, order="C")
+    ref_lib().ref_img_upsample(_f32p(a), a.shape[0], _f32p(out), out_side, a.shape[0] if dispatch_side is None else dispatch_side)
+    return out
+
+
+def _two_to_one(name, a, b):
+    a, b = _sq(a), _sq(b)
+    out = np.zeros_like(a)
+    getattr(ref_lib(), name)(_f32p(a), _f32p(b), a.shape[0], _f32p(out))
+    return out
+
+
+def ref_difference(a, b):
+    return _two_to_one("ref_img_difference", a, b)
+
+
+def ref_addition(a, b):
+    return _two_to_one("ref_img_addition", a, b)
+
+
+def ref_sdev(a):
+    return _img_to_img("ref_img_sdev", a)
+
+
+def ref_noise_hist(sdev, groups):
+    a = _sq(sdev)
+    h = np.zeros(NOISE_BINS, dtype=np.uint32)
+    ref_lib().ref_noise_hist(_f32p(a), a.shape[0], groups, _u32p(h))
+    return h
+
+
+def ref_histogram_max(hist, before=(0xDEAD, 0xBEEF)):
+    """before: what the block holds before the dispatch (the shader must overwrite both members)."""
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    p = HistMaxPoint(*before)
+    ref_lib().ref_img_histogram_max(_u32p(h), h.size, C.byref(p))
+    return (p.maxValue, p.maxBin)
+
+
+def ref_contrast_curve_generate(max_bin, low, high, curve=None):
+    c = ContrastCurve() if curve is None else curve
+    ref_lib().ref_contrast_curve_generate(HistMaxPoint(0, max_bin), ContrastParams(low, high), C.byref(c))
+    return c
+
+
+def ref_contrast_curve_apply(band, sdev, curve):
+    b, s = _sq(band), _sq(sdev)
+    out = np.zeros_like(b)
+    ref_lib().ref_contrast_curve_apply(_f32p(b), _f32p(s), b.shape[0], C.byref(curve), _f32p(out))
+    return out
+
+
+def ref_cnr(sdev, max_bin):
+    s = _sq(sdev)
+    out = np.zeros_like(s)
+    ref_lib().ref_img_cnr(_f32p(s), s.shape[0], HistMaxPoint(0, max_bin), _f32p(out))
+    return out
+
+
+def ref_noise_reduction(band, cnr, params):
+    b, c = _sq(band), _sq(cnr)
+    out = np.zeros_like(b)
+    ref_lib().ref_noise_reduction(_f32p(b), b.shape[0], _f32p(c), c.shape[0], NrParams(*params), _f32p(out))
+    return out
+
+
+def ref_relevant(normalized, cnr):
+    a, c = _sq(normalized), _sq(cnr)
+    out = np.zeros_like(a)
+    ref_lib().ref_img_relevant(_f32p(a), a.shape[0], _f32p(c), c.shape[0], _f32p(out))
+    return out
+
+
+def ref_gradation_histogram(img, relevant, groups):
+    a, r = _sq(img), _sq(relevant)
+    h = np.zeros(GRAD_BINS, dtype=np.uint32)
+    ref_lib().ref_gradation_histogram(_f32p(a), _f32p(r), a.shape[0], groups, _u32p(h))
+    return h
+
+
+def ref_gradation_curve_generate(hist, curve=None):
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    c = GradCurve() if curve is None else curve
+    ref_lib().ref_gradation_curve_generate(_u32p(h), C.byref(c))
+    return c
+
+
+def ref_apply_gradation_curve(img, curve):
+    a = _sq(img)
+    out = np.zeros_like(a)
+    ref_lib().ref_img_apply_gradation_curve(_f32p(a), a.shape[0], C.byref(curve), _f32p(out))
+    return out
+
+
+def ref_render_noise_hist(hist, max_value, max_bin):
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    out = np.zeros((128, 512, 4), dtype=np.uint8)
+    ref_lib().ref_noise_hist_render(_u32p(h), HistMaxPoint(max_value, max_bin), out.ctypes.data_as(C.POINTER(C.c_uint8)), 512, 128)
+    return out
+
+
+def ref_render_grad_hist(hist, max_value, max_bin, curve):
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    out = np.zeros((128, 512, 4), dtype=np.uint8)
+    ref_lib().ref_gradation_curve_debug_render(_u32p(h), HistMaxPoint(max_value, max_bin), C.byref(curve),
+                                               out.ctypes.data_as(C.POINTER(C.c_uint8)), 512, 128)
+    return out

@@ -1,6 +1,6 @@
 /*
  * musica_oracle.c — CPU restatement of the reference's MUSICA path.
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see musica_oracle.h).
+ * TEST INFRASTRUCTURE ONLY; per-shader arithmetic pinned to the reference's shader text (see musica_oracle.h).
  *
  * Every function cites the reference file:line it follows (paths relative to
  * the reference root). Emulation rules fixed here:
@@ -1046,14 +1046,14 @@ static void plot_px(uint8_t* img, uint32_t x, uint32_t y, uint8_t r, uint8_t g, 
 
 /* noise_hist_render.comp:17-76 bound to the histogram and the argmax of cnrLevel (src/vk_processing.cpp:1260-1266):
  * positionConversionFactor is 1.0, so only bins 0..511 of the 2048 are drawn, one per column. */
-void musica_oracle_render_noise_hist(const musica_oracle* o, uint8_t* rgba) {
+void musica_oracle_k_render_noise_hist(const uint32_t* hist, musica_hist_max_point mp, uint8_t* rgba) {
     const uint32_t H = MUSICA_HIST_RENDER_H;
-    const uint32_t maxValue = o->noise_max[MUSICA_CNR_LEVEL].maxValue, maxBin = o->noise_max[MUSICA_CNR_LEVEL].maxBin;
+    const uint32_t maxValue = mp.maxValue, maxBin = mp.maxBin;
     memset(rgba, 0, (size_t)MUSICA_HIST_RENDER_W * H * 4);
     for (uint32_t pos = 0; pos < MUSICA_HIST_RENDER_W; pos++) {
         const float factor = 1.0f;                                                    /* :19 */
         const uint32_t bin = f2u((float)pos * factor);                                /* :23 */
-        const uint32_t value = bin < MUSICA_NOISE_BINS ? o->noise_hist[MUSICA_CNR_LEVEL][bin] : 0u;   /* :41 */
+        const uint32_t value = bin < MUSICA_NOISE_BINS ? hist[bin] : 0u;                  /* :41 */
         uint32_t barHeight = f2u((float)value * ((float)H / (float)(maxValue + 1u))); /* :49 */
         if (barHeight > H) barHeight = H - 1u;                                        /* :50 */
         const uint32_t startY = H - barHeight - 1u;                                   /* :58 (uint arithmetic) */
@@ -1081,15 +1081,14 @@ static float plot_get_y(const musica_point* pts, uint32_t count, float x) {
 
 /* gradation_curve_debug_render.comp:48-123 bound to the gradation histogram, its argmax and the tone curve
  * (src/vk_processing.cpp:1668-1675): every SECOND histogram bin (factor 1024 / 512 = 2), the t0 / ta / t1 columns, the curve. */
-void musica_oracle_render_grad_hist(const musica_oracle* o, uint8_t* rgba) {
+void musica_oracle_k_render_grad_hist(const uint32_t* hist, musica_hist_max_point mp, const musica_grad_curve* gc, uint8_t* rgba) {
     const uint32_t H = MUSICA_HIST_RENDER_H, W = MUSICA_HIST_RENDER_W;
-    const uint32_t maxValue = o->grad_max.maxValue, maxBin = o->grad_max.maxBin;
-    const musica_grad_curve* gc = &o->gcurve.c;
+    const uint32_t maxValue = mp.maxValue, maxBin = mp.maxBin;
     memset(rgba, 0, (size_t)W * H * 4);
     for (uint32_t pos = 0; pos < W; pos++) {
         const float factor = (float)MUSICA_GRAD_BINS / 512.0f;                        /* :52 */
         const uint32_t bin = f2u((float)pos * factor);                                /* :54 */
-        const uint32_t value = bin < MUSICA_GRAD_BINS ? o->grad_hist[bin] : 0u;       /* :56 */
+        const uint32_t value = bin < MUSICA_GRAD_BINS ? hist[bin] : 0u;               /* :56 */
         uint32_t barHeight = f2u((float)value * ((float)H / (float)(maxValue + 1u))); /* :64 */
         if (barHeight > H) barHeight = H - 1u;                                        /* :65 */
         const uint32_t startY = H - barHeight - 1u;                                   /* :73 */
@@ -1115,6 +1114,13 @@ void musica_oracle_render_grad_hist(const musica_oracle* o, uint8_t* rgba) {
             for (uint32_t i = 0; i < W; i++) plot_px(rgba, posX, i, 255, 0, 0);
         plot_px(rgba, posX, posY, 0, 0, 255);                                         /* :123 */
     }
+}
+
+void musica_oracle_render_noise_hist(const musica_oracle* o, uint8_t* rgba) {
+    musica_oracle_k_render_noise_hist(o->noise_hist[MUSICA_CNR_LEVEL], o->noise_max[MUSICA_CNR_LEVEL], rgba);
+}
+void musica_oracle_render_grad_hist(const musica_oracle* o, uint8_t* rgba) {
+    musica_oracle_k_render_grad_hist(o->grad_hist, o->grad_max, &o->gcurve.c, rgba);
 }
 
 int musica_oracle_save_out_image(const musica_oracle* o, const char* path) {

@@ -6,17 +6,21 @@
  * load it, and only as the checker / the CPU number reported beside the GPU
  * one. libmusica_hip.so never links, loads or calls it.
  *
- * PARITY UNPINNED for the pixel arithmetic: the reference is a Vulkan/SPIR-V
- * program that cannot be built or run here (no Vulkan SDK, no glslc, no GPU
- * ICD), it ships no golden vectors for this path (raw_images/ are
- * missing blobs), and it has no CPU implementation. This file therefore
+ * PARITY: the reference is a Vulkan/SPIR-V program that cannot be built or
+ * run here (no Vulkan SDK, no glslc, no GPU ICD), it ships no
+ * golden vectors for this path and it has no CPU implementation. This file
  * restates shaders/X.comp and the dispatch script of
- * src/vk_processing.cpp:2104-2601 line by line and is pinned only by analytic
- * known-answer tests derived from the shader text (tests/test_oracle_kat.py).
- * The one piece that IS pinned against real reference code is the BMP byte
- * layout: oracle/ref_bmp.c compiles the reference's vendored
- * dependencies/stb/stb_image_write.h into oracle/_ref/ and the tests compare
- * bytes.
+ * src/vk_processing.cpp:2104-2601 line by line.
+ *   PINNED: the per-shader arithmetic of every musica_oracle_k_* function but
+ *   the CLAHE trio, to the reference's own shader text compiled for the host
+ *   (ref_shaders.cpp behind glsl_host.h -> oracle/_ref/libref_shaders.so),
+ *   under rules Q1 to Q6 and the constant-folding rule stated in glsl_host.h;
+ *   bit for bit, tests/test_reference_shaders.py. Also the BMP byte layout
+ *   (ref_bmp.c compiles the reference's vendored stb_image_write.h).
+ *   STILL UNPINNED: the dispatch script (src/vk_processing.cpp, Vulkan host
+ *   code), whatever a GPU driver does where GLSL is undefined, and the vendor
+ *   outputs. Inputs on which the shaders themselves are undefined and the CLAHE
+ *   trio rest on the analytic known-answer tests (tests/test_oracle_kat.py).
  *
  * Two arithmetic orders:
  *   MUSICA_ORDER_REFERENCE  literal 25-tap loops, x-outer / y-inner, exactly
@@ -99,6 +103,10 @@ int musica_oracle_debug_process(const musica_oracle* o, const char* dir);
 #define MUSICA_HIST_RENDER_H 128u
 void musica_oracle_render_noise_hist(const musica_oracle* o, uint8_t* rgba);
 void musica_oracle_render_grad_hist(const musica_oracle* o, uint8_t* rgba);
+/* The same two plots from given blocks; `curve` must be followed by readable memory for points[pointsCount] when pointsCount
+ * is 256 (it never is: the curve shaders write at most 33 points). */
+void musica_oracle_k_render_noise_hist(const uint32_t* hist /*2048*/, musica_hist_max_point mp, uint8_t* rgba);             /* noise_hist_render.comp */
+void musica_oracle_k_render_grad_hist(const uint32_t* hist /*1024*/, musica_hist_max_point mp, const musica_grad_curve* curve, uint8_t* rgba); /* gradation_curve_debug_render.comp */
 /* stbi_write_bmp(path, w, h, 4, data) restated (stb_image_write.h:501-509). */
 int musica_oracle_write_bmp_rgba(const char* path, uint32_t w, uint32_t h, const uint8_t* data);
 /* stbi_write_bmp(path, w, h, 1, data) restated (stb_image_write.h:492-500). */

@@ -1,7 +1,7 @@
 """Generates tests/golden/stages_*.npz and stage_digests.json: the oracle's (MUSICA_ORDER_FAST) output at every
 stage for small seeded phantoms (full arrays) and, for the BASELINE-sized cases, SHA-256 digests of the same
 arrays. The reference ships no golden vectors for this path, so these are regression pins of the
-build's own oracle ("parity unpinned" still holds): they catch drift of the oracle between rounds, compiler /
+build's own oracle (its per-shader arithmetic is pinned by tests/test_reference_shaders.py, not by these): they catch drift of the oracle between rounds, compiler /
 libm differences between the build container and the GPU box's CPU, and they give the HIP path a committed target.
 
 Run from the repo root:  python tests/golden/make_stage_fixtures.py [--large]

@@ -9,7 +9,9 @@ scalar, 8-bit pixel and the BMP file — on every BASELINE configuration at its 
 The second half states what the DEFAULT (separable) order is worth against the literal one: both are now GPU contexts, the
 literal one proven equal to the oracle above, so the distribution of the differences is measured at full size on every
 configuration and the test asserts the bounds DESIGN.md section 2 quotes (and prints the measured numbers).
-PARITY UNPINNED: the oracle is the build's restatement of the shaders; the reference holds no vectors for this path.
+PARITY: the oracle is the build's restatement of the shaders; its per-shader arithmetic is pinned to the reference's shader text under rules Q1 to Q6
+and the constant-folding rule (oracle/glsl_host.h, tests/test_reference_shaders.py). Unpinned: the dispatch script (src/vk_processing.cpp), driver
+behaviour where GLSL is undefined, the vendor outputs; the reference holds no vectors for this path.
 """
 import json
 import os
