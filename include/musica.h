@@ -395,9 +395,17 @@ int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
  *               [shutter_h, N - shutter_h], outside it min(k, 65535) with k ~ Poisson(v / 100).
  *   GAUSSIAN    add_gaussian_noise(src, mean, sigma): clip(v + trunc(N(mean, sigma)), 0, 65535).
  *   POISSON     apply_quantum_noise(src, factor): k ~ Poisson(v * factor), then float(k) / float(factor) in f32, clipped, truncated.
- * The noise draws come from Philox4x32-10 keyed by (seed, stream) with the pixel index as the counter: a pixel's value depends on
- * the spec, its source value and its index only. They follow numpy's distributions (inversion below lambda = 10, PTRS above; Box-Muller
- * for the normal) but not numpy's stream.
+ * The noise draws come from Philox4x32-10 (Salmon et al., SC 2011): the key is (seed & 0xffffffff, seed >> 32), and block j = 0, 1, ..
+ * of pixel p (its row-major index y * N + x) is the output (x, y, z, w) of the counter (p, j, stream, 0). A block yields two uniform
+ * doubles in [0, 1), u53(x, y) first and then u53(z, w), with u53(a, b) = ((a >> 5) * 2^26 + (b >> 6)) / 2^53 (numpy's next_double); a
+ * pixel consumes its uniforms in that order, starting at block 0 for every call. So a pixel's value depends on the spec, its source
+ * value and its index only: not on N, image_index or the launch. The samplers follow numpy's distributions but not numpy's stream:
+ *   normal   Box-Muller in f64 on the pixel's first two uniforms, z = sqrt(-2 ln(1 - u0)) cos(2 pi u1); the draw is mean + sigma z
+ *            truncated toward zero and saturated to int32.
+ *   Poisson  0 when lambda is not > 0 (no uniform consumed); below lambda = 10 the number of uniforms multiplied together, one per
+ *            round, before the product is no longer > exp(-lambda), less one; from 10 on Hormann's PTRS (1993) with its constants, two
+ *            uniforms per round: U = u - 0.5 first, then V.
+ * tests/noise_restatement.py states this contract in numpy; the draws are compared with it pixel for pixel.
  *   SYMMETRY    element `dx` (0 .. 7) of the square's symmetry group (D4), np.rot90(src if dx < 4 else src.T, dx & 3), bit-exact: a
  *               permutation of the source, no fill and no resampling (harness.apply_symmetry). Output pixel (i, j) is source pixel
  *               0: [i, j]   1: [j, N-1-i]   2: [N-1-i, N-1-j]   3: [N-1-j, i]   4: [j, i]   5: [N-1-i, j]   6: [N-1-j, N-1-i]   7: [i, N-1-j]. */
@@ -418,8 +426,8 @@ typedef struct musica_alteration {
     int32_t shutter_h, shutter_v;   /* COLLIMATOR: 0 <= 2 shutter <= N */
     double mean, sigma;             /* GAUSSIAN: sigma finite and > 0, mean finite */
     double factor;                  /* POISSON: finite, > 0, 65535 * factor < 2^30 */
-    uint64_t seed;                  /* noise kinds: Philox key (with stream) */
-    uint32_t stream;
+    uint64_t seed;                  /* noise kinds: the Philox key (low word, high word) */
+    uint32_t stream;                /* noise kinds: word 2 of the Philox counter */
     double matrix[4];               /* ROTATE: rot_matrix of ndimage.rotate, row-major */
     double offset[2];               /* ROTATE: its offset */
 } musica_alteration;

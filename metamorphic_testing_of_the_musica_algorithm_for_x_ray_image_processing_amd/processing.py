@@ -632,7 +632,7 @@ class MusicaProcessing:
 
     # ---- alterations of the metamorphic study (musica_alter_*) ---------------------------------
     # Each alter_* writes image `image_index` of the resident input buffer (follow it with execute_device()); the arguments mirror
-    # harness.py's generators. Noise kinds draw from Philox4x32-10 keyed by (seed, stream): the same distribution as numpy's, not its stream.
+    # harness.py's generators. Noise kinds draw from Philox4x32-10 keyed by the seed, counter (pixel, block, stream, 0): the same distribution as numpy's, not its stream.
     def alter_set_source(self, raw):
         """One (N, N) uint16 image into the source plane every alteration reads."""
         n = self.imageSize

@@ -54,6 +54,44 @@ def test_geometric_alterations_bit_exact(n):
     p.cleanup()
 
 
+# Sides whose planes k_alter stores pixel by pixel (N^2 is not a multiple of 8: N odd, or N = 2 mod 4) and whose crops are odd (513 - 128,
+# 1001 - 200) or = 2 mod 4 (1002 - 200, 150 - 36): the crop's centre then falls on a pixel, and the floor(c + 0.5) ties of rotate_px
+# against ndimage.rotate land elsewhere than at the even crops above; the percentile regions and the collimator rectangle have odd extents.
+# Image 1 of an odd side starts on a 2-byte boundary only.
+@pytest.mark.parametrize("n", [513, 1001, 1002, 150])
+def test_geometric_alterations_bit_exact_at_ragged_sides(n):
+    assert (n * n) % 8 != 0
+    raw = phantom(n, 26, noise=4.0)
+    p = _ctx(n, batch=2)
+    held = np.stack([phantom(n, 27, noise=4.0), phantom(n, 28, noise=4.0)])
+    p.upload(held)
+    p.alter_set_source(raw)
+
+    def check(alter, want, what):
+        for idx in (0, 1):
+            alter(idx)
+            got = p.input_pixels()
+            assert np.array_equal(got[idx], want), (what, idx)
+            assert np.array_equal(got[1 - idx], held[1 - idx]), (what, idx, "the other image")   # nothing stored past a plane's end
+            held[idx] = got[idx]
+
+    check(lambda idx: p.alter_none(idx), raw, "none")
+    shifts = [(t, 0) for t in H.scaled(H.TRANSLATIONS, n) + [1, n - 11]] + [(0, t) for t in H.scaled(H.TRANSLATIONS, n) + [1, n - 11]] + \
+             [(-7, 0), (0, -30), (5, 9), (-3, 11)]
+    for dx, dy in shifts:
+        check(lambda idx: p.alter_translate(dx, dy, image_index=idx), H.clamp_translation(raw, dx, dy), ("translate", dx, dy))
+    for d in STUDY_ANGLES + TIE_ANGLES:
+        check(lambda idx: p.alter_rotate(d, image_index=idx), H.clamp_rotate(raw, d), ("rotate", d))
+    for s in H.scaled(H.SHUTTERS, n)[:3] + [0, n // 2]:
+        for idx in (0, 1):
+            p.alter_collimator(s, s, seed=3, stream=s, image_index=idx)
+            got = p.input_pixels()
+            assert np.array_equal(got[idx][s:n - s + 1, s:n - s + 1], raw[s:n - s + 1, s:n - s + 1]), ("collimator", s, idx)
+            assert np.array_equal(got[1 - idx], held[1 - idx]), ("collimator", s, idx, "the other image")
+            held[idx] = got[idx]
+    p.cleanup()
+
+
 def test_only_the_named_image_is_written():
     n = 512
     raw = phantom(n, 22, noise=4.0)
@@ -96,7 +134,27 @@ def test_percentiles_match_numpy():
     p.cleanup()
 
 
-@pytest.mark.parametrize("n", [512, 1000])
+def test_percentiles_of_a_region_larger_than_the_grid_and_of_one_pixel():
+    """k_pct_hi / k_pct_lo launch at most 1024 workgroups of 256 threads, 16 pixels per thread on the first pass: a region above
+    2048 x 2048 makes the grid-stride loops wrap. Odd extents, so the last pass is a partial one."""
+    n = 3072
+    rng = np.random.default_rng(10)
+    src = rng.integers(0, 65536, (n, n), dtype=np.uint16)
+    src[1000:1400] = rng.choice(np.array([500, 501, 65535], np.uint16), (400, n))     # heavy ties around the upper ranks
+    p = _ctx(n)
+    p.alter_set_source(src)
+    regions = [(5, 3, 3001, 2051), (0, 0, n, n), (n - 1, n - 1, 1, 1), (1234, 567, 1, 1)]
+    assert regions[0][2] * regions[0][3] > 1024 * 256 * 16
+    for (x, y, w, h) in regions:
+        region = src[y:y + h, x:x + w]
+        for q in (0, 50, 95, 99, 99.9, 100):
+            assert p.alter_percentile(x, y, w, h, q) == float(np.percentile(region, q)), ((x, y, w, h), q)
+    p.cleanup()
+
+
+# 512, 1000: N - 20 = 492, 980, (N - 20)^2 a multiple of 16 (one 16-byte store per thread); 513: N - 20 odd; 1002, 150: N - 20 = 2 mod 4:
+# (N - 20)^2 is no multiple of 16 and the slot is stored byte by byte
+@pytest.mark.parametrize("n", [512, 1000, 513, 1002, 150])
 def test_rotated_reference_matches_harness(n):
     raw = phantom(n, 23, noise=4.0)
     p = _ctx(n)

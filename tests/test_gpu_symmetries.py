@@ -62,8 +62,9 @@ def test_only_the_named_image_is_written():
     p.cleanup()
 
 
-# sides 44, 137, 1000 (4-byte row words, dword tiles), 3052 (the same at the study's size); 137: bytes
-@pytest.mark.parametrize("n", [64, 157, 1020, 3072])
+# slot sides N - 20: 44, 1000, 3052 (the study's size): rows that are multiples of 4 but not of 16 bytes (4-byte row words, dword tiles);
+# 137 (odd) and 130 (2 mod 4): byte row words, tiles pixel by pixel; 64 and 1024: multiples of 16 (k_sym_rows<uint8_t, 16>), whole tiles
+@pytest.mark.parametrize("n", [64, 157, 1020, 3072, 84, 1044, 150])
 def test_transform_reference_is_bit_identical(n):
     nw = n - 2 * mp.OUT_MARGIN
     rng = np.random.default_rng(n)
@@ -82,6 +83,25 @@ def test_transform_reference_is_bit_identical(n):
         assert np.array_equal(p.sim_get_reference(dst), H.apply_symmetry(plane, e)), (n, dst)
     p.sim_transform_reference(0, 1, 6)      # a transformed slot is a source like any other: the anti-transpose is its own inverse
     assert np.array_equal(p.sim_get_reference(0), plane)
+    p.cleanup()
+
+
+def test_only_the_named_image_is_written_at_an_odd_side():
+    """N^2 odd: image 1 of the input buffer starts on a 2-byte boundary only and image 2 on a 4-byte one, while the source plane is
+    256-byte aligned; the neighbours on both sides keep every pixel."""
+    n = 201
+    raw = _full_range_u16(n, 2)
+    p = _ctx(n, batch=3)
+    base = np.stack([_full_range_u16(n, 20 + k) for k in range(3)])
+    p.upload(base)
+    p.alter_set_source(raw)
+    for idx in (1, 2):
+        for e in range(8):
+            p.upload(base)
+            p.alter_symmetry(e, image_index=idx)
+            got = p.input_pixels()
+            for k in range(3):
+                assert np.array_equal(got[k], H.apply_symmetry(raw, e) if k == idx else base[k]), (idx, e, k)
     p.cleanup()
 
 

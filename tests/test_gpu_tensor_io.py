@@ -81,6 +81,104 @@ def test_u8_export_equals_out_pixels(ob, n, kind):
     del keep
 
 
+def _store_width(ptr, row_pitch, image_pitch, count):
+    """The bytes per store launch_export_u8 chooses: the widest of 16, 8, 4, 1 that divides the destination's address, its row pitch
+    and - with more than one image - its image pitch."""
+    bits = ptr | row_pitch | (image_pitch if count > 1 else 0)
+    return next(w for w in (16, 8, 4, 1) if bits % w == 0)
+
+
+# (N, row pitch or 0 for dense, bytes between images beyond the rows or None for dense, offset of the destination, count, store width).
+# The row is N - 20 bytes; a lane owns 16 of them, the last lane of a row the ragged rest.
+EXPORT_FORMS = [
+    (532, 0, None, 0, 2, 16),            # rows of 512: 16-byte stores, no ragged tail
+    (1044, 0, None, 0, 2, 16),           # rows of 1024
+    (524, 0, None, 0, 2, 8),             # rows of 504 = 8 mod 16: 8-byte stores, a tail of 8
+    (520, 512, 1024, 0, 2, 16),          # rows of 500 at pitch 512, two padding rows: 16-byte stores, a tail of 4, padding behind every row
+    (520, 512, 1024, 8, 2, 8),           # the same destination 8, 4 and 1 bytes further
+    (520, 512, 1024, 4, 2, 4),
+    (520, 512, 1024, 1, 2, 1),
+    (520, 512, 1024 + 8, 0, 2, 8),       # an image pitch = 8 mod 16 narrows the stores of two images ...
+    (520, 512, 1024 + 8, 0, 1, 16),      # ... and is ignored for one
+    (520, 504, 8, 0, 2, 8),              # pitch 504 = 8 mod 16, wider than the ragged row
+    (21, 0, None, 0, 2, 1), (27, 0, None, 0, 2, 1), (35, 0, None, 0, 2, 1),   # rows of 1, 7, 15: nothing but a tail
+    (21, 16, 32, 0, 2, 16), (27, 16, 0, 0, 2, 16), (35, 16, 16, 0, 2, 16),    # ... at an aligned pitch: the 16-byte form never stores 16 bytes
+    (36, 0, None, 0, 2, 16), (36, 24, 0, 0, 2, 8), (36, 20, 0, 0, 2, 4), (36, 17, 3, 0, 2, 1),   # one full lane per row, every width
+]
+
+
+def test_the_export_forms_cover_every_store_width():
+    assert {f[5] for f in EXPORT_FORMS} == {16, 8, 4, 1}
+    assert {f[5] for f in EXPORT_FORMS if (f[0] - 20) % 16 and f[0] - 20 > 16} == {16, 8, 4, 1}    # each with a full lane and a ragged tail
+
+
+@pytest.fixture(scope="module")
+def stepped_by_side():
+    """One plain context per side (batch 2), stepped once; image 0 checked against the oracle."""
+    made = {}
+
+    def get(ob, n):
+        if n not in made:
+            px = phantom_batch(n, [n, n + 1])
+            c = _ctx(n, 2)
+            assert c.execute(px), mp.last_error()
+            want = np.stack([c.out_pixels(k) for k in range(2)])
+            o = ob.Oracle(n, c.pyramidLevels, ob.ORDER_FAST).execute(px[0])
+            assert np.array_equal(want[0], o.out_pixels()), n
+            made[n] = (c, want)
+        return made[n]
+
+    yield get
+    for c, _ in made.values():
+        c.cleanup()
+
+
+@pytest.mark.parametrize("form", EXPORT_FORMS, ids=lambda f: "N%d-rp%d-ip%s-off%d-x%d-W%d" % f)
+def test_u8_export_in_every_store_width(ob, stepped_by_side, form):
+    """k_export_u8<16 / 8 / 4 / 1>: which one runs follows from the destination (stated here the way the launcher states it), the bytes
+    written are musica_get_out_pixels', and every other byte of the destination keeps the sentinel."""
+    n, row_pitch, extra, offset, count, width = form
+    c, want = stepped_by_side(ob, n)
+    w = n - 20
+    rp = row_pitch or w
+    ip = rp * w + (extra or 0)
+    size = offset + count * ip + 48
+    buf = torch.full((size,), SENT, dtype=torch.uint8, device=DEV)
+    assert buf.data_ptr() % 16 == 0
+    assert _store_width(buf.data_ptr() + offset, rp, ip, count) == width
+    got = _export_u8(c, buf, first=0, count=count, row_pitch=rp, image_pitch=ip, offset=offset)
+    expect = np.full(size, SENT, dtype=np.uint8)
+    for k in range(count):
+        for r in range(w):
+            at = offset + k * ip + r * rp
+            expect[at:at + w] = want[k][r]
+    assert np.any(want[:count] != SENT)
+    bad = np.flatnonzero(got != expect)
+    assert bad.size == 0, "%d bytes differ, first at %d (image pitch %d, row pitch %d): %d, expected %d" % (
+        bad.size, bad[0], ip, rp, got[bad[0]], expect[bad[0]])
+    # the second image alone, from the same destination: the store width may differ (count 1 ignores the image pitch)
+    buf.fill_(SENT)
+    got = _export_u8(c, buf, first=1, count=1, row_pitch=rp, image_pitch=ip, offset=offset)
+    expect[:] = SENT
+    for r in range(w):
+        expect[offset + r * rp:offset + r * rp + w] = want[1][r]
+    assert np.array_equal(got, expect)
+
+
+def test_tensor_processor_meets_the_16_byte_form():
+    n, b = 532, 2
+    px = phantom_batch(n, [n, n + 1])
+    tp = T.TensorProcessor(n, batch=b, device=DEV)
+    out = torch.full((b, n - 20, n - 20), SENT, dtype=torch.uint8, device=DEV)
+    assert _store_width(out.data_ptr(), n - 20, (n - 20) ** 2, b) == 16
+    tp(torch.from_numpy(px).to(DEV), out=out)
+    got = _to_np(out)
+    assert np.array_equal(got, np.stack([tp.proc.out_pixels(k) for k in range(b)]))
+    fresh = tp(torch.from_numpy(px).to(DEV))                 # a tensor the processor allocates itself
+    assert _store_width(fresh.data_ptr(), n - 20, (n - 20) ** 2, b) == 16
+    assert np.array_equal(_to_np(fresh), got)
+
+
 @pytest.mark.parametrize("kind", ["plain", "pipeline"])
 def test_f32_export_equals_graded_bit_for_bit(kind):
     n, b = 520, 3
