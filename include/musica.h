@@ -382,6 +382,37 @@ int musica_sim_transform_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t 
 /* (N - 20)^2 bytes of reference slot `slot` to the host (synchronous); the slot must have been written. */
 int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
 
+/* Tone metrics from the joint gray-level histogram of a comparison (harness.tone_similarities): J[a][b] counts the region pixels with
+ * the value a in the batch image's 8-bit output and b in the reference slot, exactly (integer atomics: the same from call to call). The
+ * numbers are computed on the host from J. With n = w * h, the marginals A_a and B_b, S_b = sum_a a J[a][b], Q_b = sum_a a^2 J[a][b],
+ * all sums in ascending a, then ascending b, zero counts skipped, natural logarithms:
+ *   h_a = -sum (A_a / n) ln(A_a / n), h_b and h_ab (over J) likewise;
+ *   mi = sum (J / n) ln(J n / (A_a B_b));  nmi = 2 mi / (h_a + h_b), 1 when h_a + h_b == 0;
+ *   SSW = sum over b with B_b > 0 of (B_b Q_b - S_b^2) / B_b and SST = (n sum_a a^2 A_a - (sum_a a A_a)^2) / n, each numerator an exact
+ *   integer (128 bits), one f64 division per term;
+ *   corr_ratio = 1 - SSW / SST, 1 when SST's numerator is 0 (Roche et al.: how much of a's variance a function of b explains);
+ *   tone_mse = 1 - sqrt(SSW / n) / 255: the mse of musica_sim_compare after the least-squares gray-level remap of b onto a, E[a | b];
+ *   tone_lut[b] = (2 S_b + B_b) / (2 B_b) in integer division (that remap, rounded half up) where B_b > 0, else b.
+ * mi, nmi and corr_ratio do not change under an invertible remap of b's gray levels. */
+typedef struct musica_sim_joint_result {
+    double mi, nmi, corr_ratio, tone_mse;
+    double h_a, h_b, h_ab;                  /* entropies, nats */
+    uint64_t pixels;                        /* w * h */
+    uint64_t sq_diff_sum;                   /* sum J (a - b)^2 == musica_sim_compare's */
+    uint8_t tone_lut[256];
+} musica_sim_joint_result;
+/* `count` (1 .. MUSICA_SIM_MAX_QUERIES) joint histograms in one launch; synchronous. `joint` (may be NULL): count * 65536 counts, table
+ * i at joint + i * 65536, row a, column b. The refusals of musica_sim_compare, so one query array serves both calls: refused (0,
+ * musica_last_error) before any device work: NULL pointers, a count out of range, a slot out of range or never written, image_index >=
+ * batch, a region that leaves either plane, w < 7 or h < 7. Changes no slot, no result of the step and no input image; its tables are
+ * allocated on first use. */
+int musica_sim_joint(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_joint_result* results, uint32_t* joint);
+/* dst[i] = lut[src[i]] over the (N - 20)^2 plane of reference slot `src_slot` into `dst_slot` (device to device, on the ctx stream);
+ * with a musica_sim_joint_result's tone_lut: the slot tone-matched to the image it was compared with. Refused before any device work: a
+ * NULL context or table, a slot out of range, dst_slot == src_slot, a source slot never written, an image too small for the margin.
+ * Marks dst_slot written. */
+int musica_sim_remap_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]);
+
 /* ---- alterations of the metamorphic study (new, not in the reference) ---- */
 
 /* The study's alteration generators (harness.py apply_collimator, clamp_translation, clamp_rotate, add_gaussian_noise,

@@ -162,6 +162,25 @@ void launch_sim(hipStream_t st, const SimQueryDev* d_qs, int count, int max_bloc
 // k_sim_vendor: `total` vendor values (u16 when bits == 16, else u8; dense, from an allocation's base) into `out` (u8, dense, from an
 // allocation's base) as 255 - (v >> 8) or 255 - v
 void launch_sim_vendor(hipStream_t st, const void* src, int bits, uint8_t* out, long long total);
+// kernels_joint.hip: one query of musica_sim_joint. a, b, pitches, w, h as SimQueryDev; chunk_rows / chunks: launch geometry
+// (joint_geometry): a workgroup counts chunk_rows whole region rows (at most 65535 pixels) between two flushes of its LDS table.
+struct JointQueryDev {
+    const float* a;
+    const uint8_t* b;
+    int a_pitch, b_pitch;
+    int w, h;
+    int chunk_rows, chunks;
+};
+constexpr int kJointMaxBlocks = 256;    // workgroups per launch, shared by its queries, but at least kJointMinBlocks per query; a
+constexpr int kJointMinBlocks = 8;      // workgroup strides over the chunks beyond that
+void joint_geometry(JointQueryDev& q, int count);   // count: the queries of the launch
+// k_joint over `count` queries (grid.x = min(max_chunks, max(kJointMinBlocks, kJointMaxBlocks / count))); joint: count x 65536 u32 (row a, column b), zeroed by the caller
+void launch_joint(hipStream_t st, const JointQueryDev* d_qs, int count, int max_chunks, uint32_t* joint);
+// k_sim_remap: out[i] = lut[src[i]] over `total` bytes (both dense, from an allocation's base; the planes must not overlap)
+struct RemapLut {
+    uint8_t v[256];
+};
+void launch_sim_remap(hipStream_t st, const uint8_t* src, uint8_t* out, const RemapLut& lut, long long total);
 // kernels_alteration.hip: one alteration of musica_alter (or the draws of musica_alter_draws) over an n x n plane.
 struct AlterDev {
     int kind;                  // MUSICA_ALTER_*

@@ -156,6 +156,8 @@ struct musica_ctx : DeviceBuffers {
     uint32_t* d_sim_hist = nullptr;  // [MUSICA_SIM_MAX_QUERIES][512]: value counts of a, then b
     std::vector<SimQueryDev> h_sim_q;
     uint16_t* d_sim_vendor = nullptr;   // musica_sim_set_vendor_reference's staging plane: (N - 20)^2 u16 (u8 data uses its first half)
+    JointQueryDev* d_joint_q = nullptr;   // musica_sim_joint's queries and tables, allocated on first use
+    uint32_t* d_joint = nullptr;          // [MUSICA_SIM_MAX_QUERIES][65536]: J[a][b], row a
     // musica_alter_*: the source plane (N x N u16), the radix-select counts and the fill, allocated on first use
     uint16_t* d_alter_src = nullptr;
     uint32_t* d_alter_hist = nullptr;    // [768]
@@ -1665,23 +1667,30 @@ static void sim_finish(const uint32_t* counts /* a 256 | b 256 */, const SimPart
     o->hist_bhattacharyya = bc;
 }
 
-int musica_sim_compare(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_result* out) {
-    ABI_TRY
-    if (!c) return fail("musica_sim_compare: ctx is NULL");
-    if (!qs || !out) return fail("musica_sim_compare: queries or results is NULL");
-    if (count == 0 || count > MUSICA_SIM_MAX_QUERIES) return fail("musica_sim_compare: count %u out of range [1, %d]", count, MUSICA_SIM_MAX_QUERIES);
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_compare: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+// What musica_sim_compare and musica_sim_joint refuse, in the same words (`what`: the entry point), before any device work.
+static int sim_check_queries(musica_ctx* c, const char* what, uint32_t count, const musica_sim_query* qs, const void* out) {
+    if (!c) return fail("%s: ctx is NULL", what);
+    if (!qs || !out) return fail("%s: queries or results is NULL", what);
+    if (count == 0 || count > MUSICA_SIM_MAX_QUERIES) return fail("%s: count %u out of range [1, %d]", what, count, MUSICA_SIM_MAX_QUERIES);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("%s: image too small for the %d-pixel margin", what, MUSICA_OUT_MARGIN);
     const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
     for (uint32_t i = 0; i < count; i++) {
         const musica_sim_query& q = qs[i];
-        if (q.slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_compare: query %u: slot %u >= %d", i, q.slot, MUSICA_SIM_SLOTS);
-        if (!c->sim_written[q.slot]) return fail("musica_sim_compare: query %u: slot %u was never written", i, q.slot);
-        if ((int)q.image_index >= c->B) return fail("musica_sim_compare: query %u: image_index %u >= batch %d", i, q.image_index, c->B);
-        if (q.w < 7 || q.h < 7) return fail("musica_sim_compare: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", i, q.w, q.h);
+        if (q.slot >= MUSICA_SIM_SLOTS) return fail("%s: query %u: slot %u >= %d", what, i, q.slot, MUSICA_SIM_SLOTS);
+        if (!c->sim_written[q.slot]) return fail("%s: query %u: slot %u was never written", what, i, q.slot);
+        if ((int)q.image_index >= c->B) return fail("%s: query %u: image_index %u >= batch %d", what, i, q.image_index, c->B);
+        if (q.w < 7 || q.h < 7) return fail("%s: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", what, i, q.w, q.h);
         if ((uint64_t)q.ax + q.w > nw || (uint64_t)q.ay + q.h > nw || (uint64_t)q.bx + q.w > nw || (uint64_t)q.by + q.h > nw)
-            return fail("musica_sim_compare: query %u: region (%u, %u) / (%u, %u) + %u x %u leaves the %llu x %llu planes", i, q.ax, q.ay, q.bx, q.by,
+            return fail("%s: query %u: region (%u, %u) / (%u, %u) + %u x %u leaves the %llu x %llu planes", what, i, q.ax, q.ay, q.bx, q.by,
                         q.w, q.h, (unsigned long long)nw, (unsigned long long)nw);
     }
+    return 1;
+}
+
+int musica_sim_compare(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_result* out) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_compare", count, qs, out)) return 0;
+    const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
     CHECK_CTX(c);
     if (!c->d_sim_hist) {   // keyed on the LAST allocation of the block
         const bool ok = (c->d_sim_q || dalloc(c, &c->d_sim_q, MUSICA_SIM_MAX_QUERIES)) &&
@@ -1774,6 +1783,121 @@ int musica_sim_get_reference(musica_ctx* c, uint32_t slot, uint8_t* dst) {
     const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
     HIP_OK(hipMemcpyAsync(dst, c->d_sim_slot[slot], nw * nw, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+// musica_sim_joint's numbers from one exact table (include/musica.h states them; harness.tone_similarities restates them): sums in
+// ascending a, then ascending b, zero counts skipped; the variance numerators as exact 128-bit integers, one f64 division per term.
+static void joint_finish(const uint32_t* J, const musica_sim_query& q, musica_sim_joint_result* o) {
+    typedef unsigned __int128 u128;
+    const uint64_t n = (uint64_t)q.w * q.h;
+    const double dn = (double)n;
+    uint64_t A[256] = {}, B[256] = {}, S[256] = {}, Q[256] = {};
+    uint64_t ssd = 0;
+    for (int a = 0; a < 256; a++)
+        for (int b = 0; b < 256; b++) {
+            const uint64_t j = J[a * 256 + b];
+            if (!j) continue;
+            A[a] += j;
+            B[b] += j;
+            S[b] += (uint64_t)a * j;
+            Q[b] += (uint64_t)(a * a) * j;
+            ssd += (uint64_t)((a - b) * (a - b)) * j;
+        }
+    double h_a = 0.0, h_b = 0.0, h_ab = 0.0, mi = 0.0;
+    for (int a = 0; a < 256; a++)
+        if (A[a]) { const double p = (double)A[a] / dn; h_a -= p * log(p); }
+    for (int b = 0; b < 256; b++)
+        if (B[b]) { const double p = (double)B[b] / dn; h_b -= p * log(p); }
+    for (int a = 0; a < 256; a++)
+        for (int b = 0; b < 256; b++) {
+            const uint64_t j = J[a * 256 + b];
+            if (!j) continue;
+            const double p = (double)j / dn;
+            h_ab -= p * log(p);
+            mi += p * log((double)(j * n) / (double)(A[a] * B[b]));   // both products < 2^57
+        }
+    double ssw = 0.0;
+    for (int b = 0; b < 256; b++) {
+        o->tone_lut[b] = (uint8_t)(B[b] ? (2 * S[b] + B[b]) / (2 * B[b]) : (uint64_t)b);
+        if (B[b]) ssw += (double)((u128)B[b] * Q[b] - (u128)S[b] * S[b]) / (double)B[b];   // B Q >= S^2 (Cauchy-Schwarz)
+    }
+    uint64_t sa = 0, saa = 0;
+    for (int a = 0; a < 256; a++) {
+        sa += (uint64_t)a * A[a];
+        saa += (uint64_t)(a * a) * A[a];
+    }
+    const u128 sst_num = (u128)n * saa - (u128)sa * sa;
+    o->mi = mi;
+    o->nmi = h_a + h_b == 0.0 ? 1.0 : 2.0 * mi / (h_a + h_b);
+    o->corr_ratio = sst_num == 0 ? 1.0 : 1.0 - ssw / ((double)sst_num / dn);
+    o->tone_mse = 1.0 - sqrt(ssw / dn) / 255.0;
+    o->h_a = h_a;
+    o->h_b = h_b;
+    o->h_ab = h_ab;
+    o->pixels = n;
+    o->sq_diff_sum = ssd;
+}
+
+int musica_sim_joint(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_joint_result* out, uint32_t* joint) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_joint", count, qs, out)) return 0;
+    const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
+    CHECK_CTX(c);
+    if (!c->d_joint) {   // keyed on the LAST allocation of the block
+        const bool ok = (c->d_joint_q || dalloc(c, &c->d_joint_q, MUSICA_SIM_MAX_QUERIES)) &&
+                        dalloc(c, &c->d_joint, (size_t)MUSICA_SIM_MAX_QUERIES * 65536);
+        if (!ok) return fail("musica_sim_joint: device allocation failed");
+    }
+    std::vector<JointQueryDev> hq(count);
+    int max_chunks = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        JointQueryDev& d = hq[i];
+        d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
+        d.b = c->d_sim_slot[q.slot] + (size_t)q.by * nw + q.bx;
+        d.a_pitch = c->lv[0].pitch;
+        d.b_pitch = (int)nw;
+        d.w = (int)q.w;
+        d.h = (int)q.h;
+        joint_geometry(d, (int)count);
+        max_chunks = std::max(max_chunks, d.chunks);
+    }
+    std::vector<uint32_t> own;
+    if (!joint) {
+        own.resize((size_t)count * 65536);
+        joint = own.data();
+    }
+    HIP_OK(hipMemcpyAsync(c->d_joint_q, hq.data(), count * sizeof(JointQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(c->d_joint, 0, (size_t)count * 65536 * sizeof(uint32_t), c->stream));
+    launch_joint(c->stream, c->d_joint_q, (int)count, max_chunks, c->d_joint);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(joint, c->d_joint, (size_t)count * 65536 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        memset(out + i, 0, sizeof(out[i]));
+        joint_finish(joint + (size_t)i * 65536, qs[i], out + i);
+    }
+    return 1;
+    ABI_CATCH("musica_sim_joint")
+}
+
+int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]) {
+    if (!c) return fail("musica_sim_remap_reference: ctx is NULL");
+    if (!lut) return fail("musica_sim_remap_reference: lut is NULL");
+    if (dst_slot >= MUSICA_SIM_SLOTS || src_slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_remap_reference: slot %u / %u >= %d", dst_slot, src_slot, MUSICA_SIM_SLOTS);
+    if (dst_slot == src_slot) return fail("musica_sim_remap_reference: dst_slot == src_slot (%u)", dst_slot);
+    if (!c->sim_written[src_slot]) return fail("musica_sim_remap_reference: slot %u was never written", src_slot);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_remap_reference: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    CHECK_CTX(c);
+    uint8_t* dst = sim_slot(c, dst_slot);
+    if (!dst) return 0;
+    RemapLut t;
+    memcpy(t.v, lut, sizeof(t.v));   // travels as a kernel argument: `lut` is free again when the call returns
+    const long long nw = c->N - 2 * MUSICA_OUT_MARGIN;
+    launch_sim_remap(c->stream, c->d_sim_slot[src_slot], dst, t, nw * nw);
+    HIP_OK(hipGetLastError());
+    c->sim_written[dst_slot] = true;
     return 1;
 }
 

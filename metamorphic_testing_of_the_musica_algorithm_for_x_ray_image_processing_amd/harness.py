@@ -153,6 +153,82 @@ def similarities(a, b):
             "hist_distance": e_dist, "hist_bhattacharyya": b_coef}
 
 
+# ---- tone metrics from the joint gray-level histogram (not in the reference's script) ----------------------
+# MUSICA's gradation follows the image's own histogram, so an alteration that changes the histogram moves the global tone curve of the
+# output, and mse / ssim charge that shift in full. The joint histogram J[a][b] of two aligned 8-bit images separates it: mutual
+# information (Viola & Wells; Maes et al.) and the correlation ratio (Roche et al.) do not change under an invertible remap of b's gray
+# levels, and the least-squares remap E[a | b] itself turns a comparison into a tone-matched one. These functions state the numbers of
+# musica_sim_joint (include/musica.h) in Python integers and f64, in its summation order.
+
+def joint_histogram(a, b):
+    """J[a][b]: how many pixels have the value a in `a` and b in `b` (two uint8 arrays of one shape); (256, 256) int64."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("joint_histogram needs two uint8 arrays of one shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    return np.bincount(a.ravel().astype(np.int64) * 256 + b.ravel(), minlength=65536).reshape(256, 256)
+
+
+def _joint_moments(J):
+    """Per value b of the second image, as Python integers: B_b (count), S_b = sum_a a J[a][b], Q_b = sum_a a^2 J[a][b]."""
+    J = np.asarray(J).astype(np.int64)
+    v = np.arange(256, dtype=np.int64)
+    return [int(x) for x in J.sum(axis=0)], [int(x) for x in v @ J], [int(x) for x in (v * v) @ J]
+
+
+def tone_lut(J):
+    """The least-squares gray-level remap of b onto a, E[a | b] rounded half up: (2 S_b + B_b) // (2 B_b) where b occurs, else b;
+    (256,) uint8."""
+    B, S, _ = _joint_moments(J)
+    return np.array([(2 * S[b] + B[b]) // (2 * B[b]) if B[b] else b for b in range(256)], dtype=np.uint8)
+
+
+def joint_similarities(J):
+    """mi, nmi, corr_ratio, tone_mse and the entropies h_a, h_b, h_ab (nats) of a joint histogram, as musica_sim_joint computes them:
+    sums in ascending a, then ascending b, zero counts skipped; the variance numerators as exact integers, one f64 division per term."""
+    J = np.asarray(J).astype(np.int64)
+    n = int(J.sum())
+    if n == 0:
+        raise ValueError("empty joint histogram")
+    A = [int(x) for x in J.sum(axis=1)]
+    B, S, Q = _joint_moments(J)
+    dn = float(n)
+
+    def entropy(counts):
+        h = 0.0
+        for c in counts:
+            if c:
+                p = float(c) / dn
+                h -= p * math.log(p)
+        return h
+
+    h_a, h_b = entropy(A), entropy(B)
+    h_ab = mi = 0.0
+    for a, b in zip(*np.nonzero(J)):          # row-major: ascending a, then ascending b
+        j = int(J[a, b])
+        p = float(j) / dn
+        h_ab -= p * math.log(p)
+        mi += p * math.log(float(j * n) / float(A[a] * B[b]))
+    ssw = 0.0
+    for b in range(256):
+        if B[b]:
+            ssw += float(B[b] * Q[b] - S[b] * S[b]) / float(B[b])
+    sst_num = n * sum(a * a * A[a] for a in range(256)) - sum(a * A[a] for a in range(256)) ** 2
+    return {"mi": mi, "nmi": 1.0 if h_a + h_b == 0.0 else 2.0 * mi / (h_a + h_b),
+            "corr_ratio": 1.0 if sst_num == 0 else 1.0 - ssw / (float(sst_num) / dn),
+            "tone_mse": 1.0 - math.sqrt(ssw / dn) / 255.0, "h_a": h_a, "h_b": h_b, "h_ab": h_ab}
+
+
+def tone_similarities(a, b):
+    """The five JOINT_METRICS of two uint8 images of one shape: mi (mutual information, nats), nmi (2 mi / (h_a + h_b)), corr_ratio
+    (1 - SSW / SST: the share of a's variance a function of b explains), tone_mse (mse_similarity after the best gray-level remap of b
+    onto a: 1 - sqrt(SSW / n) / 255) and tone_ssim (ssim_similarity of a and b remapped with tone_lut)."""
+    J = joint_histogram(a, b)
+    r = joint_similarities(J)
+    out = {k: r[k] for k in mp.JOINT_METRICS if k != "tone_ssim"}
+    out["tone_ssim"] = ssim_similarity(a, tone_lut(J)[b])
+    return out
+
+
 # ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
 
 def vendor_to_u8(pixels):
@@ -340,9 +416,13 @@ def read_bmp_gray(path):
 # stands beside an unaltered one)
 SLOT_UNALTERED, SLOT_ROTATED, SLOT_VENDOR, SLOT_VENDOR_ROTATED = 0, 1, 2, 3
 VENDOR_SLOT = {SLOT_UNALTERED: SLOT_VENDOR, SLOT_ROTATED: SLOT_VENDOR_ROTATED}
+SLOT_TONE = 4   # tone=True: slots 4 .. 7 hold the slots of a row's (at most four) comparisons remapped with their tone_lut (musica_sim_remap_reference)
+TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "reference": "reference_tone",
+             "registered_reference": "registered_reference_tone"}
 
 
-def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None):
+def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
+              tone=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -364,7 +444,13 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     the unaltered result, "registered" over the WHOLE frame against the unaltered result under the same element, which an exactly
     equivariant pipeline would reproduce bit for bit. On the device that reference goes into slot 1 and the transformed vendor image into
     slot 3 (musica_sim_transform_reference; the rotation rows are done with them by then). These rows draw nothing from `rng` and do not
-    advance the noise ordinal."""
+    advance the noise ordinal.
+
+    tone: every comparison dict of a row gains a sibling with the five JOINT_METRICS (tone_similarities): direct_tone, registered_tone
+    and, with a vendor image, reference_tone and registered_reference_tone; present exactly where the original is and None exactly
+    where it is None. On the device the row's queries go through musica_sim_joint in one call, each comparison's tone_lut remaps its
+    slot into one of the slots SLOT_TONE .. SLOT_TONE + 3 (musica_sim_remap_reference), and tone_ssim is musica_sim_compare's ssim
+    against those slots over the same regions, one call per row. Without it the rows and the launches are exactly as before."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     if vendor is not None:
@@ -373,6 +459,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         if vendor.shape != want or vendor.dtype not in (np.uint8, np.uint16):
             raise ValueError("vendor image must be a %d x %d uint8 or uint16 array, got %r %s" % (want + (vendor.shape, vendor.dtype)))
     keys = ("alteration", "direct", "registered", "mean_cnr") + (() if vendor is None else ("reference", "registered_reference"))
+    if tone:
+        keys += tuple(TONE_KEYS[k] for k in keys if k in TONE_KEYS)
     shutters = scaled(SHUTTERS, n) if shutters is None else shutters
     translations = scaled(TRANSLATIONS, n) if translations is None else translations
     rotations = ROTATIONS if rotations is None else rotations
@@ -392,7 +480,18 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     def on_device(queries):
         return [{k: r[k] for k in mp.SIM_METRICS} for r in runner.proc.sim_compare(queries)]
 
-    first = {"alteration": "unaltered", "registered": None}
+    def tone_on_device(queries):
+        """The JOINT_METRICS of a row's queries (at most four): one musica_sim_joint call, every query's slot remapped with its tone_lut
+        into a slot of its own from SLOT_TONE on, then one musica_sim_compare call over the same regions for tone_ssim."""
+        res = runner.proc.sim_joint(queries)
+        for i, (q, r) in enumerate(zip(queries, res)):
+            runner.proc.sim_remap_reference(SLOT_TONE + i, q[1], r["tone_lut"])
+        scored = runner.proc.sim_compare([(q[0], SLOT_TONE + i) + tuple(q[2:]) for i, q in enumerate(queries)])
+        for r, c in zip(res, scored):
+            r["tone_ssim"] = c["ssim"]
+        return [{k: r[k] for k in mp.JOINT_METRICS} for r in res]
+
+    first = {"alteration": "unaltered", "registered": None, "registered_tone": None}
     if device:
         runner.proc.sim_capture(SLOT_UNALTERED)
         queries = [(0, SLOT_UNALTERED) + full]
@@ -403,10 +502,19 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         first["direct"] = res[0]
         if vendor is not None:
             first["reference"] = res[1]
+        if tone:
+            res = tone_on_device(queries)
+            first["direct_tone"] = res[0]
+            if vendor is not None:
+                first["reference_tone"] = res[1]
     else:
         first["direct"] = similarities(unalt, unalt)
         if vendor is not None:
             first["reference"] = similarities(unalt, ref8)
+        if tone:
+            first["direct_tone"] = tone_similarities(unalt, unalt)
+            if vendor is not None:
+                first["reference_tone"] = tone_similarities(unalt, ref8)
     first["mean_cnr"] = runner.mean_cnr() if runner.proc else None
     rows = [{k: first[k] for k in keys if k in first}]
 
@@ -424,7 +532,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     def add(name, altered_raw, reg=None, roi=None):
         """altered_raw: the altered image, or (device alterations) a call that writes it into the resident input buffer.
         reg: the host crop; roi: () -> (region, slot) of the same comparison on the device (region None: no registration)."""
-        row = {"alteration": name, "registered": None, "registered_reference": None}
+        row = {"alteration": name, "registered": None, "registered_reference": None, "registered_tone": None, "registered_reference_tone": None}
         if callable(altered_raw):
             altered_raw()
             runner.run_resident()
@@ -440,25 +548,29 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
                     queries.append((0, slot) + region)
                     if vendor is not None:
                         queries.append((0, VENDOR_SLOT[slot]) + region)
-            res = on_device(queries)
-            row["direct"] = res.pop(0)
-            if vendor is not None:
-                row["reference"] = res.pop(0)
-            if res:
-                row["registered"] = res.pop(0)
+            for suffix, score in (("", on_device),) + ((("_tone", tone_on_device),) if tone else ()):
+                res = score(queries)
+                row["direct" + suffix] = res.pop(0)
                 if vendor is not None:
-                    row["registered_reference"] = res.pop(0)
+                    row["reference" + suffix] = res.pop(0)
+                if res:
+                    row["registered" + suffix] = res.pop(0)
+                    if vendor is not None:
+                        row["registered_reference" + suffix] = res.pop(0)
         else:
             alt = runner.run(altered_raw)
-            row["direct"] = similarities(alt, unalt)
-            if vendor is not None:
-                row["reference"] = similarities(alt, ref8)
-            if reg is not None:
-                a, u = reg(alt, unalt)
-                if a.size and a.shape == u.shape and min(a.shape) >= 8:
-                    row["registered"] = similarities(a, u)
+            crop = reg(alt, unalt) if reg is not None else None
+            if crop is not None and not (crop[0].size and crop[0].shape == crop[1].shape and min(crop[0].shape) >= 8):
+                crop = None
+            vcrop = reg(alt, ref8) if crop is not None and vendor is not None else None   # the same rectangles: ref8 has unalt's shape
+            for suffix, score in (("", similarities),) + ((("_tone", tone_similarities),) if tone else ()):
+                row["direct" + suffix] = score(alt, unalt)
+                if vendor is not None:
+                    row["reference" + suffix] = score(alt, ref8)
+                if crop is not None:
+                    row["registered" + suffix] = score(*crop)
                     if vendor is not None:
-                        row["registered_reference"] = similarities(*reg(alt, ref8))   # the same rectangles: ref8 has unalt's shape
+                        row["registered_reference" + suffix] = score(*vcrop)
         row["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         rows.append({k: row[k] for k in keys})
 
@@ -530,6 +642,14 @@ CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs 
 
 
 REF_CSV_HEADER = ['raw file', 'mse similarity', 'ssim similarity', 'histogram distance']   # ref_similarities.csv (script.py:285-290)
+TONE_CSV_NAMES = ('mutual information', 'normalized mutual information', 'correlation ratio', 'tone-matched mse', 'tone-matched ssim')   # JOINT_METRICS' order
+TONE_CSV_GROUPS = (('direct_tone', 'altered vs unaltered'), ('registered_tone', 'registered vs unaltered'),
+                   ('reference_tone', 'altered vs reference'), ('registered_reference_tone', 'registered vs reference'))
+
+
+def tone_csv_header(with_reference):
+    """tone_robustness.csv's columns: the five JOINT_METRICS per group, the two vendor groups only for studies that have a vendor image."""
+    return ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in TONE_CSV_GROUPS[:4 if with_reference else 2] for m in TONE_CSV_NAMES]
 
 
 def normalized_vs_reference(ref, ovd):
@@ -549,7 +669,12 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     The six "vs reference" columns compare with the vendor-processed image. For a study run with one (rows[0] has "reference"): the
     altered result vs that image (reg_based_robustness.csv: the registered crops), then normalized_vs_reference against the study's
     full-image unaltered-vs-vendor values, as m_sim_alt and m_sim_norm_alt do; ref_similarities.csv gets one row of those values per
-    such study and is written only when there is one. Studies without a vendor image leave the six columns empty."""
+    such study and is written only when there is one. Studies without a vendor image leave the six columns empty.
+
+    Studies run with tone=True (rows[0] has "direct_tone") also get tone_robustness.csv: one line per row, the unaltered one included
+    (with a vendor image it carries the unaltered-vs-vendor numbers), the five JOINT_METRICS of the direct and of the registered
+    comparison, then, when any study has a vendor image, of the two comparisons with it. Cells without a comparison are empty. The
+    other files are written as without it."""
     os.makedirs(out_dir, exist_ok=True)
     ovds = []
 
@@ -588,6 +713,19 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
             ws = csv.writer(fs)
             ws.writerow(REF_CSV_HEADER)
             ws.writerows(ovds)
+    toned = [(raw_name, rows) for raw_name, rows in studies if rows and "direct_tone" in rows[0]]
+    if toned:
+        groups = TONE_CSV_GROUPS[:4 if any("reference_tone" in rows[0] for _, rows in toned) else 2]
+        with open(os.path.join(out_dir, "tone_robustness.csv"), "w", newline="") as ft:
+            wt = csv.writer(ft)
+            wt.writerow(tone_csv_header(len(groups) == 4))
+            for raw_name, rows in toned:
+                for r in rows:
+                    cells = []
+                    for key, _ in groups:
+                        t = r.get(key)
+                        cells += [""] * len(mp.JOINT_METRICS) if t is None else [t[k] for k in mp.JOINT_METRICS]
+                    wt.writerow([raw_name, r["alteration"]] + cells)
 
 
 def write_study_csvs(rows, out_dir, raw_name, mean_cnr=True):
@@ -668,6 +806,9 @@ def main(argv=None):
     ap.add_argument("--symmetries", nargs="?", const=SYMMETRIES, default=None, type=symmetry_list, metavar="E,E,...",
                     help="add the rows d4_<e>: the raw image under elements of the square's symmetry group (1, 3: quarter turns, 2: half turn, "
                          "4: transpose, 5, 7: flips, 6: anti-transpose), compared over the whole frame; without a list, all seven")
+    ap.add_argument("--tone", action="store_true",
+                    help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
+                         "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
     args = ap.parse_args(argv)
     if args.cli and args.device_alterations:
         ap.error("--device-alterations writes the in-process library's input buffer: it cannot be combined with --cli")
@@ -691,10 +832,10 @@ def main(argv=None):
     runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics, device_alterations=args.device_alterations)
     try:
         if args.manifest:
-            studies = run_studies(entries, runner, symmetries=args.symmetries)
+            studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone)
         else:
             studies = [(name, run_study(raw, runner, rng=np.random.default_rng(0), vendor=vendor if args.reference else None,
-                                        symmetries=args.symmetries))]
+                                        symmetries=args.symmetries, tone=args.tone))]
     finally:
         runner.close()
     write_studies_csvs(studies, args.out, mean_cnr=not args.cli)

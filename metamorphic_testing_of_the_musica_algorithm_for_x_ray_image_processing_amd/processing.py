@@ -134,6 +134,20 @@ class SimResult(C.Structure):
         return d
 
 
+JOINT_METRICS = ("mi", "nmi", "corr_ratio", "tone_mse", "tone_ssim")   # harness.tone_similarities' keys (tone_ssim: not in SimJointResult)
+
+
+class SimJointResult(C.Structure):
+    """musica_sim_joint_result: the tone metrics of one comparison, from its exact joint histogram."""
+    _fields_ = [(n, C.c_double) for n in ("mi", "nmi", "corr_ratio", "tone_mse", "h_a", "h_b", "h_ab")] + \
+               [("pixels", C.c_uint64), ("sq_diff_sum", C.c_uint64), ("tone_lut", C.c_uint8 * 256)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n in ("mi", "nmi", "corr_ratio", "tone_mse", "h_a", "h_b", "h_ab")}
+        d.update(pixels=int(self.pixels), sq_diff_sum=int(self.sq_diff_sum), tone_lut=np.ctypeslib.as_array(self.tone_lut).copy())
+        return d
+
+
 # musica_out_format: what export_out writes per image
 OUT_U8, OUT_GRADED_F32 = 0, 1
 OUT_FORMAT_COUNT = 2
@@ -258,6 +272,8 @@ ABI = {
     "musica_sim_rotate_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "musica_sim_get_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
     "musica_sim_transform_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
+    "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
     "musica_alter_set_source": (C.c_int, [_VP, _U16P]),
     "musica_alter": (C.c_int, [_VP, C.c_uint32, C.POINTER(Alteration)]),
     "musica_alter_draws": (C.c_int, [_VP, C.POINTER(Alteration), C.POINTER(C.c_int32)]),
@@ -629,6 +645,28 @@ class MusicaProcessing:
         out = np.empty((n, n), dtype=np.uint8)
         self._ok(self._lib.musica_sim_get_reference(self._h, int(slot), out.ctypes.data_as(_U8P)), "musica_sim_get_reference")
         return out
+
+    def sim_joint(self, queries, tables=False):
+        """queries as sim_compare's, all in one launch. Returns one dict per query: mi, nmi, corr_ratio, tone_mse (harness.tone_similarities'
+        numbers but tone_ssim), the entropies h_a, h_b, h_ab, the exact pixels and sq_diff_sum, tone_lut ((256,) uint8: the least-squares
+        remap of the slot's gray levels onto the image's) and, with tables=True, "joint": the (256, 256) uint32 counts, row a, column b
+        (== harness.joint_histogram)."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimJointResult * max(len(qs), 1))()
+        joint = np.empty((max(len(qs), 1), 256, 256), dtype=np.uint32) if tables else None
+        self._ok(self._lib.musica_sim_joint(self._h, len(qs), arr, res, joint.ctypes.data_as(_U32P) if tables else None), "musica_sim_joint")
+        out = [res[i].as_dict() for i in range(len(qs))]
+        if tables:
+            for i, d in enumerate(out):
+                d["joint"] = joint[i]
+        return out
+
+    def sim_remap_reference(self, dst_slot, src_slot, lut):
+        """Reference slot `src_slot` through the 256-entry uint8 table `lut` (dst = lut[src]) into `dst_slot`, on the device."""
+        t = np.ascontiguousarray(lut, dtype=np.uint8)
+        if t.shape != (256,):
+            raise ValueError("expected a table of 256 uint8 values, got %r" % (t.shape,))
+        self._ok(self._lib.musica_sim_remap_reference(self._h, int(dst_slot), int(src_slot), t.ctypes.data_as(_U8P)), "musica_sim_remap_reference")
 
     # ---- alterations of the metamorphic study (musica_alter_*) ---------------------------------
     # Each alter_* writes image `image_index` of the resident input buffer (follow it with execute_device()); the arguments mirror
