@@ -407,6 +407,35 @@ typedef struct musica_sim_joint_result {
  * batch, a region that leaves either plane, w < 7 or h < 7. Changes no slot, no result of the step and no input image; its tables are
  * allocated on first use. */
 int musica_sim_joint(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_joint_result* results, uint32_t* joint);
+/* Where the output went: exact block matching of a comparison (harness.displacement_table). With S = 2 radius + 1, radius in
+ * 1 .. MUSICA_SIM_MAX_RADIUS, side a the 8-bit output of batch image image_index (quantised while it is read, as musica_sim_compare
+ * reads it) and side b the plane of reference slot `slot`, the table of a query is, for dy, dx in [-radius, radius],
+ *   T[dy + radius][dx + radius] = sum over y < h, x < w of (a[ay + y][ax + x] - b[by + y + dy][bx + x + dx])^2.
+ * Every candidate covers the same w * h pixels, so the b window grown by `radius` on every side must lie inside the plane: a query whose
+ * grown window leaves it is refused, the caller insets its region. Tile (ty, tx) owns the region pixels [64 ty, min(h, 64 ty + 64)) x
+ * [64 tx, min(w, 64 tx + 64)); its table is the same sum over those pixels and fits u32 (64 * 64 * 255^2 < 2^32). The query's table is
+ * the sum of its tile tables in u64. The argmin of a table, the query's and a tile's: the smallest value, then the smallest
+ * dx^2 + dy^2, then the smallest dy, then the smallest dx, so a flat tile reports (0, 0) and is not counted in tiles_off. All of it is
+ * integer arithmetic: exact, and the same from call to call. */
+#define MUSICA_SIM_MAX_RADIUS 16
+#define MUSICA_SIM_TILE 64
+typedef struct musica_sim_displace_result {
+    uint64_t pixels;          /* w * h */
+    uint64_t ssd_zero;        /* table entry (0, 0) == musica_sim_compare's sq_diff_sum of the same query */
+    uint64_t ssd_min;         /* smallest table entry */
+    int32_t  dx, dy;          /* its shift, by the tie rule above */
+    uint32_t tiles_x, tiles_y;/* ceil(w / 64), ceil(h / 64) */
+    uint32_t tiles_off;       /* tiles whose own argmin (same tie rule) is not (0, 0) */
+} musica_sim_displace_result;
+/* `count` (1 .. MUSICA_SIM_MAX_QUERIES) displacement tables in one launch; synchronous, on the context's stream after whatever was
+ * enqueued there. `tables` (may be NULL): count * S^2 u64 values, table i at tables + i * S^2, row dy, column dx. `tile_tables` (may be
+ * NULL): the queries' tile tables back to back in query order, tiles_y * tiles_x * S^2 u32 each, tile-row major. Refused (0,
+ * musica_last_error) before any device work: a NULL ctx, queries or results, a count out of range, a radius outside
+ * 1 .. MUSICA_SIM_MAX_RADIUS, a slot out of range or never written, image_index >= batch, w < 7 or h < 7, an a region that leaves the
+ * output plane, a b window that, grown by the radius, leaves the plane. Changes no slot, no result of the step and no input image; its
+ * device buffers are allocated on first use and sized for the call. */
+int musica_sim_displace(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, uint32_t radius,
+                        musica_sim_displace_result* results, uint64_t* tables, uint32_t* tile_tables);
 /* dst[i] = lut[src[i]] over the (N - 20)^2 plane of reference slot `src_slot` into `dst_slot` (device to device, on the ctx stream);
  * with a musica_sim_joint_result's tone_lut: the slot tone-matched to the image it was compared with. Refused before any device work: a
  * NULL context or table, a slot out of range, dst_slot == src_slot, a source slot never written, an image too small for the margin.

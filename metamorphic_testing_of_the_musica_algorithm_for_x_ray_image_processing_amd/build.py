@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmusica_hip.so")
 CLI = os.path.join(HERE, "musica-standalone")
 HIP_SOURCES = ["kernels_pyramid.hip", "kernels_expand_sd.hip", "kernels_analysis.hip", "kernels_gradation.hip", "kernels_clahe.hip", "kernels_bench.hip",
-               "kernels_similarity.hip", "kernels_joint.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_export.hip", "musica_ctx.hip"]
+               "kernels_similarity.hip", "kernels_joint.hip", "kernels_displace.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_export.hip", "musica_ctx.hip"]
 CPP_SOURCES = ["musica_io.cpp"]
 HEADERS = ["musica_device.h", "kernels_common.h", "exact_math.h", "sdev_parts.h", "grad_parts.h", "launchers.h", os.path.join("..", "..", "include", "musica.h")]
 NO_SLP = {"kernels_analysis.hip", "kernels_expand_sd.hip"}   # kernels_expand_sd.hip: kernels_pyramid.hip's expand march again, for the launches that compute sdev in registers
@@ -127,7 +127,46 @@ def check_isa():
     return found
 
 
+def check_isa_displace():
+    """k_displace's inner loop is written with __builtin_amdgcn_udot4 and __builtin_amdgcn_alignbyte (kernels_displace.hip): four pixels per
+    multiply-add instruction. Reads the kernel's body back from the built object as check_isa does and raises RuntimeError unless it holds
+    v_dot4_u32_u8: a compiler that scalarises the loop would otherwise only show as a slow kernel. Returns the counts it found."""
+    import glob
+    import shutil
+    import tempfile
+    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+    if not os.path.exists(objdump):
+        raise RuntimeError("llvm-objdump not found under /opt/rocm/lib/llvm/bin")
+    obj = os.path.join(HERE, "build", "kernels_displace.o")
+    if not os.path.exists(obj):
+        raise RuntimeError("%s is not built" % obj)
+    td = tempfile.mkdtemp(prefix="musica_isa_")
+    try:
+        copy = os.path.join(td, "kernels_displace.o")
+        shutil.copy(obj, copy)
+        subprocess.run([objdump, "--offloading", copy], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=td)
+        outs = glob.glob(copy + ".*gfx950")
+        if not outs:
+            raise RuntimeError("no gfx950 code object inside %s" % obj)
+        text = subprocess.run([objdump, "-d", outs[0]], check=True, stdout=subprocess.PIPE, text=True).stdout
+    finally:
+        shutil.rmtree(td, ignore_errors=True)
+    body, inside = [], False
+    for line in text.splitlines():
+        if line.endswith(">:"):
+            inside = "k_displace" in line and "k_displace_fold" not in line
+        elif inside:
+            body.append(line)
+    if not body:
+        raise RuntimeError("kernels_displace: no code found for k_displace")
+    found = {"dot4": sum(1 for l in body if "v_dot4_u32_u8" in l), "alignbyte": sum(1 for l in body if "v_alignbyte_b32" in l)}
+    if found["dot4"] < 1:
+        raise RuntimeError("k_displace lost its v_dot4_u32_u8: the inner loop no longer does four pixels per instruction: %r" % (found,))
+    return found
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     print(LIB)
     print(check_isa())
+    print(check_isa_displace())

@@ -181,6 +181,23 @@ struct RemapLut {
     uint8_t v[256];
 };
 void launch_sim_remap(hipStream_t st, const uint8_t* src, uint8_t* out, const RemapLut& lut, long long total);
+// kernels_displace.hip: one query of musica_sim_displace. a, b, pitches, w, h as SimQueryDev; the b window grown by the radius lies
+// inside the slot's plane (the caller checks). tiles_x / tiles_y: ceil(w / 64), ceil(h / 64); tile_base: where the query's tile tables
+// start in the launch's tile-table buffer, in u32 elements (tile-row major, S^2 values per tile, S = 2 radius + 1).
+struct DisplaceQueryDev {
+    const float* a;
+    const uint8_t* b;
+    int a_pitch, b_pitch;
+    int w, h;
+    int tiles_x, tiles_y;
+    unsigned long long tile_base;
+};
+constexpr int kDisplaceTile = 64;        // MUSICA_SIM_TILE
+constexpr int kDisplaceMaxRadius = 16;   // MUSICA_SIM_MAX_RADIUS
+// k_displace over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y), then k_displace_fold. tile_tables: every query's
+// tile tables (all written); tables: count x S^2 u64 and tiles_off: count u32, both zeroed by the caller.
+void launch_displace(hipStream_t st, const DisplaceQueryDev* d_qs, int count, int max_tiles, int radius, uint32_t* tile_tables,
+                     unsigned long long* tables, uint32_t* tiles_off);
 // kernels_alteration.hip: one alteration of musica_alter (or the draws of musica_alter_draws) over an n x n plane.
 struct AlterDev {
     int kind;                  // MUSICA_ALTER_*

@@ -158,6 +158,11 @@ struct musica_ctx : DeviceBuffers {
     uint16_t* d_sim_vendor = nullptr;   // musica_sim_set_vendor_reference's staging plane: (N - 20)^2 u16 (u8 data uses its first half)
     JointQueryDev* d_joint_q = nullptr;   // musica_sim_joint's queries and tables, allocated on first use
     uint32_t* d_joint = nullptr;          // [MUSICA_SIM_MAX_QUERIES][65536]: J[a][b], row a
+    DisplaceQueryDev* d_disp_q = nullptr;          // musica_sim_displace's queries, tables and counts, allocated on first use
+    unsigned long long* d_disp_tables = nullptr;   // [MUSICA_SIM_MAX_QUERIES][33 * 33]
+    uint32_t* d_disp_off = nullptr;                // [MUSICA_SIM_MAX_QUERIES]: tiles_off
+    uint32_t* d_disp_tiles = nullptr;              // the tile tables of one call: disp_tiles_cap u32, regrown when a call needs more
+    size_t disp_tiles_cap = 0;
     // musica_alter_*: the source plane (N x N u16), the radix-select counts and the fill, allocated on first use
     uint16_t* d_alter_src = nullptr;
     uint32_t* d_alter_hist = nullptr;    // [768]
@@ -1880,6 +1885,103 @@ int musica_sim_joint(musica_ctx* c, uint32_t count, const musica_sim_query* qs, 
     }
     return 1;
     ABI_CATCH("musica_sim_joint")
+}
+
+// The argmin of an S x S displacement table by include/musica.h's tie rule: smallest value, then smallest dx^2 + dy^2, then smallest dy,
+// then smallest dx (harness.displacement_from_table restates it).
+static void displace_finish(const uint64_t* T, int radius, musica_sim_displace_result* o) {
+    const int S = 2 * radius + 1;
+    int by = radius, bx = radius;
+    for (int y = 0; y < S; y++)
+        for (int x = 0; x < S; x++) {
+            const uint64_t v = T[y * S + x], m = T[by * S + bx];
+            const int d2 = (x - radius) * (x - radius) + (y - radius) * (y - radius);
+            const int m2 = (bx - radius) * (bx - radius) + (by - radius) * (by - radius);
+            if (v < m || (v == m && d2 < m2)) {   // equal value and distance: the scan order is ascending dy, then ascending dx
+                by = y;
+                bx = x;
+            }
+        }
+    o->ssd_zero = T[radius * S + radius];
+    o->ssd_min = T[by * S + bx];
+    o->dx = bx - radius;
+    o->dy = by - radius;
+}
+
+int musica_sim_displace(musica_ctx* c, uint32_t count, const musica_sim_query* qs, uint32_t radius, musica_sim_displace_result* out,
+                        uint64_t* tables, uint32_t* tile_tables) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_displace", count, qs, out)) return 0;
+    if (radius < 1 || radius > MUSICA_SIM_MAX_RADIUS) return fail("musica_sim_displace: radius %u out of range [1, %d]", radius, MUSICA_SIM_MAX_RADIUS);
+    const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        if (q.bx < radius || q.by < radius || (uint64_t)q.bx + q.w + radius > nw || (uint64_t)q.by + q.h + radius > nw)
+            return fail("musica_sim_displace: query %u: the b window (%u, %u) + %u x %u grown by the radius %u leaves the %llu x %llu plane", i, q.bx,
+                        q.by, q.w, q.h, radius, (unsigned long long)nw, (unsigned long long)nw);
+    }
+    const size_t S2 = (size_t)(2 * radius + 1) * (2 * radius + 1);
+    std::vector<DisplaceQueryDev> hq(count);
+    size_t tile_words = 0;
+    int max_tiles = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        DisplaceQueryDev& d = hq[i];
+        d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
+        d.b = c->d_sim_slot[q.slot] + (size_t)q.by * nw + q.bx;
+        d.a_pitch = c->lv[0].pitch;
+        d.b_pitch = (int)nw;
+        d.w = (int)q.w;
+        d.h = (int)q.h;
+        d.tiles_x = (d.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+        d.tiles_y = (d.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+        d.tile_base = tile_words;
+        tile_words += (size_t)d.tiles_x * d.tiles_y * S2;
+        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+    }
+    CHECK_CTX(c);
+    if (!c->d_disp_off) {   // keyed on the LAST allocation of the block
+        const bool ok = (c->d_disp_q || dalloc(c, &c->d_disp_q, MUSICA_SIM_MAX_QUERIES)) &&
+                        (c->d_disp_tables || dalloc(c, &c->d_disp_tables, (size_t)MUSICA_SIM_MAX_QUERIES * (2 * MUSICA_SIM_MAX_RADIUS + 1) * (2 * MUSICA_SIM_MAX_RADIUS + 1))) &&
+                        dalloc(c, &c->d_disp_off, MUSICA_SIM_MAX_QUERIES);
+        if (!ok) return fail("musica_sim_displace: device allocation failed");
+    }
+    if (tile_words > c->disp_tiles_cap) {   // sized for the call: the largest call so far
+        if (c->d_disp_tiles) {
+            HIP_OK(hipStreamSynchronize(c->stream));
+            c->allocations.erase(std::remove(c->allocations.begin(), c->allocations.end(), (void*)c->d_disp_tiles), c->allocations.end());
+            hipFree(c->d_disp_tiles);
+            c->d_disp_tiles = nullptr;
+            c->disp_tiles_cap = 0;
+        }
+        if (!dalloc(c, &c->d_disp_tiles, tile_words)) return fail("musica_sim_displace: device allocation of %zu tile-table words failed", tile_words);
+        c->disp_tiles_cap = tile_words;
+    }
+    HIP_OK(hipMemcpyAsync(c->d_disp_q, hq.data(), count * sizeof(DisplaceQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(c->d_disp_tables, 0, count * S2 * sizeof(unsigned long long), c->stream));
+    HIP_OK(hipMemsetAsync(c->d_disp_off, 0, count * sizeof(uint32_t), c->stream));
+    launch_displace(c->stream, c->d_disp_q, (int)count, max_tiles, (int)radius, c->d_disp_tiles, c->d_disp_tables, c->d_disp_off);
+    HIP_OK(hipGetLastError());
+    std::vector<uint64_t> own;
+    if (!tables) {
+        own.resize(count * S2);
+        tables = own.data();
+    }
+    std::vector<uint32_t> off(count);
+    HIP_OK(hipMemcpyAsync(tables, c->d_disp_tables, count * S2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(off.data(), c->d_disp_off, count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (tile_tables) HIP_OK(hipMemcpyAsync(tile_tables, c->d_disp_tiles, tile_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        memset(out + i, 0, sizeof(out[i]));
+        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
+        out[i].tiles_x = (uint32_t)hq[i].tiles_x;
+        out[i].tiles_y = (uint32_t)hq[i].tiles_y;
+        out[i].tiles_off = off[i];
+        displace_finish(tables + (size_t)i * S2, (int)radius, out + i);
+    }
+    return 1;
+    ABI_CATCH("musica_sim_displace")
 }
 
 int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]) {

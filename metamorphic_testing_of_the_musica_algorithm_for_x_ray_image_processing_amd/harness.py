@@ -229,6 +229,132 @@ def tone_similarities(a, b):
     return out
 
 
+# ---- where the output went: exact block matching (musica_sim_displace; not in the reference) ------------------
+
+def _displacement_geometry(a_shape, b_shape, region, radius):
+    """Raises ValueError exactly where musica_sim_displace refuses a query on geometry; returns the region and radius as ints."""
+    ax, ay, bx, by, w, h = (int(v) for v in region)
+    radius = int(radius)
+    if not 1 <= radius <= mp.SIM_MAX_RADIUS:
+        raise ValueError("radius %d out of range [1, %d]" % (radius, mp.SIM_MAX_RADIUS))
+    if w < 7 or h < 7:
+        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
+    if ax < 0 or ay < 0 or ax + w > a_shape[1] or ay + h > a_shape[0]:
+        raise ValueError("region (%d, %d) + %d x %d leaves the %d x %d output plane" % (ax, ay, w, h, a_shape[1], a_shape[0]))
+    if bx < radius or by < radius or bx + w + radius > b_shape[1] or by + h + radius > b_shape[0]:
+        raise ValueError("the b window (%d, %d) + %d x %d grown by the radius %d leaves the %d x %d plane" % (bx, by, w, h, radius, b_shape[1], b_shape[0]))
+    return (ax, ay, bx, by, w, h), radius
+
+
+def _displacement_squares(a, b, region, radius):
+    """((dy, dx), the h x w int64 squared differences of the region under that shift) for every candidate, one shifted crop each."""
+    ax, ay, bx, by, w, h = region
+    ca = np.asarray(a)[ay:ay + h, ax:ax + w].astype(np.int64)
+    b = np.asarray(b)
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            yield (dy, dx), (ca - b[by + dy:by + dy + h, bx + dx:bx + dx + w].astype(np.int64)) ** 2
+
+
+def displacement_table(a, b, region, radius):
+    """musica_sim_displace's table of one query, restated: a the output image, b the full reference plane, region = (ax, ay, bx, by, w, h).
+    T[dy + radius][dx + radius] = sum over the region of (a[ay + y][ax + x] - b[by + y + dy][bx + x + dx])^2 for dy, dx in
+    [-radius, radius], one shifted crop per candidate, in int64. ValueError where the C call refuses on geometry: a radius outside
+    1 .. 16, w < 7 or h < 7, an a region that leaves a, a b window that, grown by the radius, leaves b."""
+    region, radius = _displacement_geometry(np.shape(a), np.shape(b), region, radius)
+    T = np.empty((2 * radius + 1,) * 2, dtype=np.int64)
+    for (dy, dx), sq in _displacement_squares(a, b, region, radius):
+        T[dy + radius, dx + radius] = np.sum(sq)
+    return T
+
+
+def displacement_tile_tables(a, b, region, radius):
+    """The same per 64 x 64 tile of the region (the last tiles ragged): (tiles_y, tiles_x, S, S) uint32, tile-row major; their sum over
+    the tiles is displacement_table."""
+    region, radius = _displacement_geometry(np.shape(a), np.shape(b), region, radius)
+    w, h = region[4], region[5]
+    t = mp.SIM_TILE
+    ny, nx, s = (h + t - 1) // t, (w + t - 1) // t, 2 * radius + 1
+    out = np.empty((ny, nx, s, s), dtype=np.uint32)
+    for (dy, dx), sq in _displacement_squares(a, b, region, radius):
+        out[:, :, dy + radius, dx + radius] = np.add.reduceat(np.add.reduceat(sq, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
+    return out
+
+
+def _displacement_argmin(T):
+    """(row, column) of the table's argmin: smallest value, then smallest dx^2 + dy^2, then smallest dy, then smallest dx."""
+    T = np.asarray(T)
+    radius = T.shape[0] // 2
+    ys, xs = np.nonzero(T == T.min())
+    return min(zip(ys.tolist(), xs.tolist()), key=lambda p: ((p[1] - radius) ** 2 + (p[0] - radius) ** 2, p[0], p[1]))
+
+
+def displacement_from_table(T):
+    """{dx, dy, ssd_min, ssd_zero, sub_dx, sub_dy} of an (S, S) displacement table: the argmin by the tie rule, and the vertex of the
+    parabola through the argmin and its two neighbours along the row (sub_dx) and along the column (sub_dy):
+    sub = d + (T- - T+) / (2 (T- - 2 T0 + T+)), computed from the exact integers with one f64 division, where |d| < radius and the
+    denominator is positive, else sub = d. The device and the host studies both call this on exact integer tables."""
+    T = np.asarray(T)
+    if T.ndim != 2 or T.shape[0] != T.shape[1] or T.shape[0] % 2 != 1 or T.shape[0] < 3:
+        raise ValueError("expected an (S, S) table with S = 2 radius + 1, got %r" % (T.shape,))
+    radius = T.shape[0] // 2
+    y, x = _displacement_argmin(T)
+
+    def vertex(d, lo, mid, hi):
+        if abs(d) >= radius:
+            return float(d)
+        lo, mid, hi = int(lo()), int(mid), int(hi())
+        den = 2 * (lo - 2 * mid + hi)
+        return d + (lo - hi) / den if den > 0 else float(d)
+
+    dx, dy = x - radius, y - radius
+    return {"dx": dx, "dy": dy, "ssd_min": int(T[y, x]), "ssd_zero": int(T[radius, radius]),
+            "sub_dx": vertex(dx, lambda: T[y, x - 1], T[y, x], lambda: T[y, x + 1]),
+            "sub_dy": vertex(dy, lambda: T[y - 1, x], T[y, x], lambda: T[y + 1, x])}
+
+
+def displacement_tiles_off(tile_tables):
+    """How many tiles' own argmin (the same tie rule) is not (0, 0)."""
+    tt = np.asarray(tile_tables)
+    radius = tt.shape[2] // 2
+    return sum(1 for ty in range(tt.shape[0]) for tx in range(tt.shape[1]) if _displacement_argmin(tt[ty, tx]) != (radius, radius))
+
+
+SHIFT_KEYS = ("dx", "dy", "sub_dx", "sub_dy", "mse_at_zero", "mse_at_best", "tiles", "tiles_off")
+
+
+def displacement_summary(T, pixels, tiles, tiles_off):
+    """A study row's *_shift dict (SHIFT_KEYS) from an exact table: displacement_from_table's shift, 1 - sqrt(ssd / pixels) / 255 at the
+    zero shift and at the best one, the number of tiles and of those whose own best shift is not (0, 0)."""
+    d = displacement_from_table(T)
+    out = {k: d[k] for k in ("dx", "dy", "sub_dx", "sub_dy")}
+    out["mse_at_zero"] = 1.0 - math.sqrt(d["ssd_zero"] / int(pixels)) / 255.0
+    out["mse_at_best"] = 1.0 - math.sqrt(d["ssd_min"] / int(pixels)) / 255.0
+    out["tiles"], out["tiles_off"] = int(tiles), int(tiles_off)
+    return out
+
+
+def displacement_maps(tile_tables, w, h):
+    """Two (tiles_y, tiles_x) uint8 maps of a w x h region's tile tables, one pixel per tile: the RMSE at the zero shift, rounded, and the
+    length of the tile's best shift, scaled so that the table's corner (radius, radius) is 255."""
+    tt = np.asarray(tile_tables)
+    ny, nx, radius, t = tt.shape[0], tt.shape[1], tt.shape[2] // 2, mp.SIM_TILE
+    rmse, mag = np.zeros((ny, nx), dtype=np.uint8), np.zeros((ny, nx), dtype=np.uint8)
+    for ty in range(ny):
+        for tx in range(nx):
+            px = (min(h, t * ty + t) - t * ty) * (min(w, t * tx + t) - t * tx)
+            rmse[ty, tx] = int(round(math.sqrt(int(tt[ty, tx, radius, radius]) / px)))
+            y, x = _displacement_argmin(tt[ty, tx])
+            mag[ty, tx] = int(round(255.0 * math.hypot(x - radius, y - radius) / (math.sqrt(2.0) * radius)))
+    return rmse, mag
+
+
+def _inset(region, r):
+    """The region (ax, ay, bx, by, w, h) inset by r on every side, or None when a side falls under 7."""
+    ax, ay, bx, by, w, h = region
+    return (ax + r, ay + r, bx + r, by + r, w - 2 * r, h - 2 * r) if min(w, h) - 2 * r >= 7 else None
+
+
 # ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
 
 def vendor_to_u8(pixels):
@@ -422,7 +548,7 @@ TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "referenc
 
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
-              tone=False):
+              tone=False, displacement=0, displacement_tiles=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -450,7 +576,16 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     and, with a vendor image, reference_tone and registered_reference_tone; present exactly where the original is and None exactly
     where it is None. On the device the row's queries go through musica_sim_joint in one call, each comparison's tone_lut remaps its
     slot into one of the slots SLOT_TONE .. SLOT_TONE + 3 (musica_sim_remap_reference), and tone_ssim is musica_sim_compare's ssim
-    against those slots over the same regions, one call per row. Without it the rows and the launches are exactly as before."""
+    against those slots over the same regions, one call per row. Without it the rows and the launches are exactly as before.
+
+    displacement: a radius R > 0 measures where the output went by exact block matching (displacement_table). Every row gains
+    "direct_shift": the full frame inset by R on every side against the unaltered result; rows with a registered comparison gain
+    "registered_shift": that comparison's region inset by R against what it is compared with (None exactly where "registered" is None or
+    the inset region has a side under 7). Each is a dict of SHIFT_KEYS (displacement_summary): (0, 0) in a registered row says the
+    output moved as the input did. On the device the row's one or two queries go through one musica_sim_displace call; on the host the
+    restatement runs on the same planes; both summarise exact integer tables with one function, so the two agree to the last bit.
+    displacement_tiles: each *_shift dict also carries "tile_tables" ((tiles_y, tiles_x, S, S) uint32) and "size" ((w, h) of its
+    region), what displacement_maps draws. With displacement=0 the rows and the launches are exactly as before."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     if vendor is not None:
@@ -461,6 +596,11 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     keys = ("alteration", "direct", "registered", "mean_cnr") + (() if vendor is None else ("reference", "registered_reference"))
     if tone:
         keys += tuple(TONE_KEYS[k] for k in keys if k in TONE_KEYS)
+    displacement = int(displacement)
+    if displacement and not 1 <= displacement <= mp.SIM_MAX_RADIUS:
+        raise ValueError("displacement radius %d is not in 1 .. %d" % (displacement, mp.SIM_MAX_RADIUS))
+    if displacement:
+        keys += ("direct_shift", "registered_shift")
     shutters = scaled(SHUTTERS, n) if shutters is None else shutters
     translations = scaled(TRANSLATIONS, n) if translations is None else translations
     rotations = ROTATIONS if rotations is None else rotations
@@ -491,7 +631,31 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             r["tone_ssim"] = c["ssim"]
         return [{k: r[k] for k in mp.JOINT_METRICS} for r in res]
 
-    first = {"alteration": "unaltered", "registered": None, "registered_tone": None}
+    def shift_summary(table, region, tiles, tiles_off, tile_tables):
+        out = displacement_summary(table, region[4] * region[5], tiles, tiles_off)
+        if displacement_tiles:
+            out["tile_tables"], out["size"] = tile_tables, (region[4], region[5])
+        return out
+
+    def shifts_on_device(comparisons):
+        """comparisons: (slot, region) pairs, region already inset (None: no comparison). One musica_sim_displace call for those present."""
+        present = [(slot, region) for slot, region in comparisons if region is not None]
+        res = iter(runner.proc.sim_displace([(0, slot) + region for slot, region in present], displacement, tables=True,
+                                            tiles=displacement_tiles) if present else [])
+        out = []
+        for slot, region in comparisons:
+            r = next(res) if region is not None else None
+            out.append(None if r is None else shift_summary(r["table"], region, r["tiles_x"] * r["tiles_y"], r["tiles_off"], r.get("tile_tables")))
+        return out
+
+    def shift_on_host(a, b, region):
+        """The same from the restatement: a the output, b the full plane it is compared with, region already inset (None: no comparison)."""
+        if region is None:
+            return None
+        tt = displacement_tile_tables(a, b, region, displacement)
+        return shift_summary(tt.astype(np.int64).sum(axis=(0, 1)), region, tt.shape[0] * tt.shape[1], displacement_tiles_off(tt), tt)
+
+    first = {"alteration": "unaltered", "registered": None, "registered_tone": None, "registered_shift": None}
     if device:
         runner.proc.sim_capture(SLOT_UNALTERED)
         queries = [(0, SLOT_UNALTERED) + full]
@@ -507,7 +671,11 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             first["direct_tone"] = res[0]
             if vendor is not None:
                 first["reference_tone"] = res[1]
+        if displacement:
+            first["direct_shift"] = shifts_on_device([(SLOT_UNALTERED, _inset(full, displacement))])[0]
     else:
+        if displacement:
+            first["direct_shift"] = shift_on_host(unalt, unalt, _inset(full, displacement))
         first["direct"] = similarities(unalt, unalt)
         if vendor is not None:
             first["reference"] = similarities(unalt, ref8)
@@ -529,10 +697,12 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             k = ordinal[0]
             return lambda: make(seed, k)
 
-    def add(name, altered_raw, reg=None, roi=None):
+    def add(name, altered_raw, reg=None, roi=None, plane=None):
         """altered_raw: the altered image, or (device alterations) a call that writes it into the resident input buffer.
-        reg: the host crop; roi: () -> (region, slot) of the same comparison on the device (region None: no registration)."""
-        row = {"alteration": name, "registered": None, "registered_reference": None, "registered_tone": None, "registered_reference_tone": None}
+        reg: the host crop; roi: () -> (region, slot) of the same comparison on the device (region None: no registration); plane:
+        () -> (region, the full host plane the region's b side lies in), what the host's displacement restatement needs."""
+        row = {"alteration": name, "registered": None, "registered_reference": None, "registered_tone": None, "registered_reference_tone": None,
+               "registered_shift": None}
         if callable(altered_raw):
             altered_raw()
             runner.run_resident()
@@ -542,9 +712,11 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             queries = [(0, SLOT_UNALTERED) + full]
             if vendor is not None:
                 queries.append((0, SLOT_VENDOR) + full)
+            registered = None   # (slot, region) of the registered comparison
             if roi is not None:
                 region, slot = roi()
                 if region is not None and min(region[4], region[5]) >= 8:
+                    registered = (slot, region)
                     queries.append((0, slot) + region)
                     if vendor is not None:
                         queries.append((0, VENDOR_SLOT[slot]) + region)
@@ -557,6 +729,10 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
                     row["registered" + suffix] = res.pop(0)
                     if vendor is not None:
                         row["registered_reference" + suffix] = res.pop(0)
+            if displacement:
+                row["direct_shift"], row["registered_shift"] = shifts_on_device(
+                    [(SLOT_UNALTERED, _inset(full, displacement)),
+                     (registered[0], _inset(registered[1], displacement)) if registered else (None, None)])
         else:
             alt = runner.run(altered_raw)
             crop = reg(alt, unalt) if reg is not None else None
@@ -571,6 +747,11 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
                     row["registered" + suffix] = score(*crop)
                     if vendor is not None:
                         row["registered_reference" + suffix] = score(*vcrop)
+            if displacement:
+                row["direct_shift"] = shift_on_host(alt, unalt, _inset(full, displacement))
+                if crop is not None:
+                    region, b_plane = plane()
+                    row["registered_shift"] = shift_on_host(alt, b_plane, _inset(region, displacement))
         row["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         rows.append({k: row[k] for k in keys})
 
@@ -595,7 +776,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     def add_symmetries(make):
         """The d4_<e> rows; make(e): the altered raw image, or (device alterations) the call that writes it."""
         for e in symmetries:
-            add("d4_%d" % e, make(e), lambda a, u, e=e: register_symmetry(a, u, e), lambda e=e: symmetry_slot(e))
+            add("d4_%d" % e, make(e), lambda a, u, e=e: register_symmetry(a, u, e), lambda e=e: symmetry_slot(e),
+                lambda e=e: (roi_symmetry(shape), apply_symmetry(unalt, e)))
 
     if alter_on_device:
         p = runner.proc
@@ -617,15 +799,16 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
 
     for s in shutters:
         add("c_sh_%d" % s, apply_collimator(raw, s, s, rng), lambda a, u, s=s: register_collimator(a, u, s),
-            lambda s=s: (roi_collimator(shape, s), SLOT_UNALTERED))
+            lambda s=s: (roi_collimator(shape, s), SLOT_UNALTERED), lambda s=s: (roi_collimator(shape, s), unalt))
     for t in translations:
         add("t_x_%d" % t, clamp_translation(raw, t, 0), lambda a, u, t=t: register_translation_x(a, u, t),
-            lambda t=t: (roi_translation_x(shape, t), SLOT_UNALTERED))
+            lambda t=t: (roi_translation_x(shape, t), SLOT_UNALTERED), lambda t=t: (roi_translation_x(shape, t), unalt))
     for t in translations:
         add("t_y_%d" % t, clamp_translation(raw, 0, t), lambda a, u, t=t: register_translation_y(a, u, t),
-            lambda t=t: (roi_translation_y(shape, t), SLOT_UNALTERED))
+            lambda t=t: (roi_translation_y(shape, t), SLOT_UNALTERED), lambda t=t: (roi_translation_y(shape, t), unalt))
     for d in rotations:
-        add("r_%d" % d, clamp_rotate(raw, d), lambda a, u, d=d: register_rotation(a, u, d), lambda d=d: rotated_slot(d))
+        add("r_%d" % d, clamp_rotate(raw, d), lambda a, u, d=d: register_rotation(a, u, d), lambda d=d: rotated_slot(d),
+            lambda d=d: (roi_rotation(shape, d), rotated_reference(unalt, d)))
     for sg in sigmas:
         add("gn_%s" % sg, add_gaussian_noise(raw, 0.0, sg, rng))
     for f in factors:
@@ -645,6 +828,11 @@ REF_CSV_HEADER = ['raw file', 'mse similarity', 'ssim similarity', 'histogram di
 TONE_CSV_NAMES = ('mutual information', 'normalized mutual information', 'correlation ratio', 'tone-matched mse', 'tone-matched ssim')   # JOINT_METRICS' order
 TONE_CSV_GROUPS = (('direct_tone', 'altered vs unaltered'), ('registered_tone', 'registered vs unaltered'),
                    ('reference_tone', 'altered vs reference'), ('registered_reference_tone', 'registered vs reference'))
+
+
+SHIFT_CSV_NAMES = ('dx', 'dy', 'sub dx', 'sub dy', 'mse at zero', 'mse at best', 'tiles', 'tiles off')   # SHIFT_KEYS' order
+SHIFT_CSV_GROUPS = (('direct_shift', 'direct'), ('registered_shift', 'registered'))
+SHIFT_CSV_HEADER = ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in SHIFT_CSV_GROUPS for m in SHIFT_CSV_NAMES]   # displacement.csv
 
 
 def tone_csv_header(with_reference):
@@ -674,7 +862,10 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     Studies run with tone=True (rows[0] has "direct_tone") also get tone_robustness.csv: one line per row, the unaltered one included
     (with a vendor image it carries the unaltered-vs-vendor numbers), the five JOINT_METRICS of the direct and of the registered
     comparison, then, when any study has a vendor image, of the two comparisons with it. Cells without a comparison are empty. The
-    other files are written as without it."""
+    other files are written as without it.
+
+    Studies run with a displacement radius (rows[0] has "direct_shift") also get displacement.csv: one line per row, the unaltered one
+    included, the SHIFT_KEYS of the direct and of the registered comparison; cells without a comparison are empty."""
     os.makedirs(out_dir, exist_ok=True)
     ovds = []
 
@@ -726,6 +917,38 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
                         t = r.get(key)
                         cells += [""] * len(mp.JOINT_METRICS) if t is None else [t[k] for k in mp.JOINT_METRICS]
                     wt.writerow([raw_name, r["alteration"]] + cells)
+    shifted = [(raw_name, rows) for raw_name, rows in studies if rows and "direct_shift" in rows[0]]
+    if shifted:
+        with open(os.path.join(out_dir, "displacement.csv"), "w", newline="") as fs:
+            ws = csv.writer(fs)
+            ws.writerow(SHIFT_CSV_HEADER)
+            for raw_name, rows in shifted:
+                for r in rows:
+                    cells = []
+                    for key, _ in SHIFT_CSV_GROUPS:
+                        t = r.get(key)
+                        cells += [""] * len(SHIFT_KEYS) if t is None else [t[k] for k in SHIFT_KEYS]
+                    ws.writerow([raw_name, r["alteration"]] + cells)
+
+
+def write_displacement_maps(studies, out_dir):
+    """Two 8-bit BMPs per registered row of studies run with displacement_tiles (displacement_maps: one pixel per 64 x 64 tile):
+    <raw>_<alteration>_rmse.bmp, the tile RMSE at the zero shift, and <raw>_<alteration>_shift.bmp, the length of the tile's best shift.
+    Returns the paths written."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for raw_name, rows in studies:
+        stem = os.path.splitext(os.path.basename(raw_name.replace("\\", "/")))[0]
+        for r in rows:
+            t = r.get("registered_shift")
+            if t is None or "tile_tables" not in t:
+                continue
+            for what, img in zip(("rmse", "shift"), displacement_maps(t["tile_tables"], *t["size"])):
+                path = os.path.join(out_dir, "%s_%s_%s.bmp" % (stem, r["alteration"], what))
+                if not mp.write_bmp_gray(path, img):
+                    raise RuntimeError("writing %s failed: %s" % (path, mp.last_error()))
+                written.append(path)
+    return written
 
 
 def write_study_csvs(rows, out_dir, raw_name, mean_cnr=True):
@@ -809,7 +1032,18 @@ def main(argv=None):
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
+    ap.add_argument("--displacement", type=int, default=0, metavar="R",
+                    help="measure where the output went: exact block matching over all integer shifts within R (1 .. 16) pixels, per row the "
+                         "direct and the registered comparison, written to displacement.csv; on the GPU with --device-metrics / "
+                         "--device-alterations (musica_sim_displace)")
+    ap.add_argument("--displacement-maps", metavar="DIR",
+                    help="with --displacement: two 8-bit BMPs per registered row into DIR, one pixel per 64 x 64 tile: the tile RMSE at the zero "
+                         "shift and the length of the tile's best shift")
     args = ap.parse_args(argv)
+    if args.displacement and not 1 <= args.displacement <= mp.SIM_MAX_RADIUS:
+        ap.error("--displacement takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
+    if args.displacement_maps and not args.displacement:
+        ap.error("--displacement-maps draws what --displacement measures: give a radius")
     if args.cli and args.device_alterations:
         ap.error("--device-alterations writes the in-process library's input buffer: it cannot be combined with --cli")
     if args.cli and args.device_metrics:
@@ -830,15 +1064,19 @@ def main(argv=None):
         from .dicom import read_dicom_gray
         vendor = read_dicom_gray(args.reference)
     runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics, device_alterations=args.device_alterations)
+    shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
+                 {"displacement": args.displacement} if args.displacement else {}
     try:
         if args.manifest:
-            studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone)
+            studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)
         else:
             studies = [(name, run_study(raw, runner, rng=np.random.default_rng(0), vendor=vendor if args.reference else None,
-                                        symmetries=args.symmetries, tone=args.tone))]
+                                        symmetries=args.symmetries, tone=args.tone, **shift_args))]
     finally:
         runner.close()
     write_studies_csvs(studies, args.out, mean_cnr=not args.cli)
+    if args.displacement_maps:
+        write_displacement_maps(studies, args.displacement_maps)
     print("wrote %d alterations to %s" % (sum(len(rows) - 1 for _, rows in studies), args.out))
     return 0
 

@@ -148,6 +148,19 @@ class SimJointResult(C.Structure):
         return d
 
 
+SIM_MAX_RADIUS = 16         # MUSICA_SIM_MAX_RADIUS
+SIM_TILE = 64               # MUSICA_SIM_TILE
+
+
+class SimDisplaceResult(C.Structure):
+    """musica_sim_displace_result: where one comparison's exact block matching puts the output."""
+    _fields_ = [("pixels", C.c_uint64), ("ssd_zero", C.c_uint64), ("ssd_min", C.c_uint64), ("dx", C.c_int32), ("dy", C.c_int32),
+                ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("tiles_off", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 # musica_out_format: what export_out writes per image
 OUT_U8, OUT_GRADED_F32 = 0, 1
 OUT_FORMAT_COUNT = 2
@@ -273,6 +286,7 @@ ABI = {
     "musica_sim_get_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
     "musica_sim_transform_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
+    "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
     "musica_alter_set_source": (C.c_int, [_VP, _U16P]),
     "musica_alter": (C.c_int, [_VP, C.c_uint32, C.POINTER(Alteration)]),
@@ -659,6 +673,36 @@ class MusicaProcessing:
         if tables:
             for i, d in enumerate(out):
                 d["joint"] = joint[i]
+        return out
+
+    def sim_displace(self, queries, radius, tables=False, tiles=False):
+        """queries as sim_compare's, all in one launch: the exact sum of squared differences of every query under every integer shift
+        (dx, dy) of its slot within `radius` (1 .. SIM_MAX_RADIUS), == harness.displacement_table. Returns one dict per query: pixels,
+        ssd_zero (== sim_compare's sq_diff_sum), ssd_min and its shift dx, dy (smallest value, then smallest dx^2 + dy^2, then smallest dy,
+        then smallest dx), tiles_x, tiles_y and tiles_off (the 64 x 64 tiles whose own best shift is not (0, 0)); with tables=True "table":
+        the (S, S) uint64 sums, row dy, column dx, S = 2 radius + 1; with tiles=True "tile_tables": the (tiles_y, tiles_x, S, S) uint32 sums
+        of the tiles. The slot's window grown by `radius` must lie inside the plane."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        if not 0 <= int(radius) < 2 ** 32:
+            raise ValueError("radius %r is not in 1 .. %d" % (radius, SIM_MAX_RADIUS))
+        s = 2 * min(int(radius), SIM_MAX_RADIUS) + 1   # a radius beyond the range is refused by the call: the arrays only have to exist
+        arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimDisplaceResult * max(len(qs), 1))()
+        table = np.zeros((max(len(qs), 1), s, s), dtype=np.uint64) if tables else None
+        tile = None
+        if tiles:
+            per = [((q.h + SIM_TILE - 1) // SIM_TILE) * ((q.w + SIM_TILE - 1) // SIM_TILE) * s * s for q in qs]
+            tile = np.zeros(max(sum(per), 1), dtype=np.uint32)
+        self._ok(self._lib.musica_sim_displace(self._h, len(qs), arr, int(radius), res,
+                                               table.ctypes.data_as(C.POINTER(C.c_uint64)) if table is not None else None,
+                                               tile.ctypes.data_as(_U32P) if tile is not None else None), "musica_sim_displace")
+        out = [res[i].as_dict() for i in range(len(qs))]
+        first = 0
+        for i, d in enumerate(out):
+            if tables:
+                d["table"] = table[i]
+            if tiles:
+                d["tile_tables"] = tile[first:first + per[i]].reshape(d["tiles_y"], d["tiles_x"], s, s)
+                first += per[i]
         return out
 
     def sim_remap_reference(self, dst_slot, src_slot, lut):
