@@ -8,7 +8,7 @@ OBJ=$PKG/build/var_$NAME
 mkdir -p $OBJ
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function -Wno-unused-value -Wno-unused-result"
 pids=()
-for f in kernels_pyramid kernels_expand_sd kernels_analysis kernels_gradation kernels_clahe kernels_bench kernels_similarity kernels_joint kernels_alteration kernels_symmetry kernels_export musica_ctx; do   # build.py's HIP_SOURCES
+for f in $(python3 -c "import sys; sys.path.insert(0, '$PKG'); import build; print(' '.join(s[:-4] for s in build.HIP_SOURCES))"); do
     NOSLP=""; case $f in kernels_analysis|kernels_expand_sd) NOSLP="-fno-slp-vectorize";; esac   # as build.py's NO_SLP
     /opt/rocm/bin/hipcc $FLAGS $NOSLP $EXTRA -x hip -c $PKG/csrc/$f.hip -o $OBJ/$f.o &
     pids+=($!)

@@ -17,9 +17,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmusica_hip.so")
 CLI = os.path.join(HERE, "musica-standalone")
 HIP_SOURCES = ["kernels_pyramid.hip", "kernels_expand_sd.hip", "kernels_analysis.hip", "kernels_gradation.hip", "kernels_clahe.hip", "kernels_bench.hip",
-               "kernels_similarity.hip", "kernels_joint.hip", "kernels_displace.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_export.hip", "musica_ctx.hip"]
+               "kernels_similarity.hip", "kernels_joint.hip", "kernels_displace.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_export.hip", "musica_ctx.hip", "musica_study.hip"]
 CPP_SOURCES = ["musica_io.cpp"]
-HEADERS = ["musica_device.h", "kernels_common.h", "exact_math.h", "sdev_parts.h", "grad_parts.h", "launchers.h", os.path.join("..", "..", "include", "musica.h")]
+HEADERS = ["musica_device.h", "kernels_common.h", "exact_math.h", "sdev_parts.h", "grad_parts.h", "launchers.h", "musica_ctx.h", os.path.join("..", "..", "include", "musica.h")]
 NO_SLP = {"kernels_analysis.hip", "kernels_expand_sd.hip"}   # kernels_expand_sd.hip: kernels_pyramid.hip's expand march again, for the launches that compute sdev in registers
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -75,76 +75,23 @@ def build(force=False, verbose=False):
     return LIB
 
 
-def check_isa():
-    """What the kernels rely on in the generated code, read back from the built objects (llvm-objdump of the gfx950 code object):
-      * the cross-workgroup hand-offs of k_minmax_u16 and k_grad_recount_curve store their slot / read the slots with `sc1` (write-through
-        store, L1-bypassing load: kernels_analysis.hip / kernels_gradation.hip rely on that instead of an agent-scope fence);
-      * the ticket adds are returning agent-scope atomics (`sc0` = return value on gfx950's global_atomic_add).
-    Returns a dict of findings; raises RuntimeError when one is missing (tests/test_abi.py runs it: a compiler that weakens the relaxed
-    agent-scope accesses would otherwise only show up as a rare stale min / max)."""
+def _kernel_body(obj_name, wanted):
+    """The disassembly lines of the kernels of build/<obj_name>.o's gfx950 code object whose label line `wanted` accepts
+    (llvm-objdump --offloading, then -d). Raises RuntimeError when the tool, the object or the code object is missing."""
     import glob
     import shutil
     import tempfile
     objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
     if not os.path.exists(objdump):
         raise RuntimeError("llvm-objdump not found under /opt/rocm/lib/llvm/bin")
-    found = {}
-    td = tempfile.mkdtemp(prefix="musica_isa_")
-    try:
-        for src, kernel in (("kernels_analysis", "k_minmax_u16"), ("kernels_gradation", "k_grad_recount_curve")):
-            obj = os.path.join(HERE, "build", src + ".o")
-            if not os.path.exists(obj):
-                raise RuntimeError("%s is not built" % obj)
-            copy = os.path.join(td, src + ".o")
-            shutil.copy(obj, copy)
-            subprocess.run([objdump, "--offloading", copy], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=td)   # writes <copy>.0.hipv4-...gfx950
-            outs = glob.glob(copy + ".*gfx950")
-            if not outs:
-                raise RuntimeError("no gfx950 code object inside %s" % obj)
-            text = subprocess.run([objdump, "-d", outs[0]], check=True, stdout=subprocess.PIPE, text=True).stdout
-            body, inside = [], False
-            for line in text.splitlines():
-                if line.endswith(">:"):
-                    inside = kernel in line
-                elif inside:
-                    body.append(line)
-            code = "\n".join(body)
-            found[kernel] = {
-                "sc1_stores": sum(1 for l in body if "global_store_dword" in l and " sc1" in l),
-                "sc1_loads": sum(1 for l in body if "global_load_dword" in l and " sc1" in l),
-                "returning_atomic_adds": sum(1 for l in body if "global_atomic_add" in l and " sc0" in l),
-            }
-            if not code:
-                raise RuntimeError("%s: no code found for %s" % (src, kernel))
-        mm = found["k_minmax_u16"]
-        if mm["sc1_stores"] < 1 or mm["sc1_loads"] < 1 or mm["returning_atomic_adds"] < 1:
-            raise RuntimeError("k_minmax_u16's slot hand-off lost its sc1 store / sc1 load / returning ticket add: %r" % (mm,))
-        gr = found["k_grad_recount_curve"]
-        if gr["returning_atomic_adds"] < 1 or gr["sc1_loads"] < 1:
-            raise RuntimeError("k_grad_recount_curve's last-ticket hand-off lost its returning ticket add / sc1 histogram loads: %r" % (gr,))
-    finally:
-        shutil.rmtree(td, ignore_errors=True)
-    return found
-
-
-def check_isa_displace():
-    """k_displace's inner loop is written with __builtin_amdgcn_udot4 and __builtin_amdgcn_alignbyte (kernels_displace.hip): four pixels per
-    multiply-add instruction. Reads the kernel's body back from the built object as check_isa does and raises RuntimeError unless it holds
-    v_dot4_u32_u8: a compiler that scalarises the loop would otherwise only show as a slow kernel. Returns the counts it found."""
-    import glob
-    import shutil
-    import tempfile
-    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    if not os.path.exists(objdump):
-        raise RuntimeError("llvm-objdump not found under /opt/rocm/lib/llvm/bin")
-    obj = os.path.join(HERE, "build", "kernels_displace.o")
+    obj = os.path.join(HERE, "build", obj_name + ".o")
     if not os.path.exists(obj):
         raise RuntimeError("%s is not built" % obj)
     td = tempfile.mkdtemp(prefix="musica_isa_")
     try:
-        copy = os.path.join(td, "kernels_displace.o")
+        copy = os.path.join(td, obj_name + ".o")
         shutil.copy(obj, copy)
-        subprocess.run([objdump, "--offloading", copy], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=td)
+        subprocess.run([objdump, "--offloading", copy], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=td)   # writes <copy>.0.hipv4-...gfx950
         outs = glob.glob(copy + ".*gfx950")
         if not outs:
             raise RuntimeError("no gfx950 code object inside %s" % obj)
@@ -154,9 +101,43 @@ def check_isa_displace():
     body, inside = [], False
     for line in text.splitlines():
         if line.endswith(">:"):
-            inside = "k_displace" in line and "k_displace_fold" not in line
+            inside = wanted(line)
         elif inside:
             body.append(line)
+    return body
+
+
+def check_isa():
+    """What the kernels rely on in the generated code, read back from the built objects (llvm-objdump of the gfx950 code object):
+      * the cross-workgroup hand-offs of k_minmax_u16 and k_grad_recount_curve store their slot / read the slots with `sc1` (write-through
+        store, L1-bypassing load: kernels_analysis.hip / kernels_gradation.hip rely on that instead of an agent-scope fence);
+      * the ticket adds are returning agent-scope atomics (`sc0` = return value on gfx950's global_atomic_add).
+    Returns a dict of findings; raises RuntimeError when one is missing (tests/test_abi.py runs it: a compiler that weakens the relaxed
+    agent-scope accesses would otherwise only show up as a rare stale min / max)."""
+    found = {}
+    for src, kernel in (("kernels_analysis", "k_minmax_u16"), ("kernels_gradation", "k_grad_recount_curve")):
+        body = _kernel_body(src, lambda line: kernel in line)
+        if not body:
+            raise RuntimeError("%s: no code found for %s" % (src, kernel))
+        found[kernel] = {
+            "sc1_stores": sum(1 for l in body if "global_store_dword" in l and " sc1" in l),
+            "sc1_loads": sum(1 for l in body if "global_load_dword" in l and " sc1" in l),
+            "returning_atomic_adds": sum(1 for l in body if "global_atomic_add" in l and " sc0" in l),
+        }
+    mm = found["k_minmax_u16"]
+    if mm["sc1_stores"] < 1 or mm["sc1_loads"] < 1 or mm["returning_atomic_adds"] < 1:
+        raise RuntimeError("k_minmax_u16's slot hand-off lost its sc1 store / sc1 load / returning ticket add: %r" % (mm,))
+    gr = found["k_grad_recount_curve"]
+    if gr["returning_atomic_adds"] < 1 or gr["sc1_loads"] < 1:
+        raise RuntimeError("k_grad_recount_curve's last-ticket hand-off lost its returning ticket add / sc1 histogram loads: %r" % (gr,))
+    return found
+
+
+def check_isa_displace():
+    """k_displace's inner loop is written with __builtin_amdgcn_udot4 and __builtin_amdgcn_alignbyte (kernels_displace.hip): four pixels per
+    multiply-add instruction. Reads the kernel's body back from the built object as check_isa does and raises RuntimeError unless it holds
+    v_dot4_u32_u8: a compiler that scalarises the loop would otherwise only show as a slow kernel. Returns the counts it found."""
+    body = _kernel_body("kernels_displace", lambda line: "k_displace" in line and "k_displace_fold" not in line)
     if not body:
         raise RuntimeError("kernels_displace: no code found for k_displace")
     found = {"dot4": sum(1 for l in body if "v_dot4_u32_u8" in l), "alignbyte": sum(1 for l in body if "v_alignbyte_b32" in l)}

@@ -1,5 +1,5 @@
 // launchers.h — host-callable launch wrappers implemented in the kernel files, plus the
-// argument blocks they share with the dispatch script in musica_ctx.hip.
+// argument blocks they share with the host code: the dispatch script in musica_ctx.hip and the study's entry points in musica_study.hip.
 #pragma once
 
 #include <stdlib.h>
@@ -139,13 +139,16 @@ void launch_out_bmp24(hipStream_t st, const float* graded, const LevelDesc& l0, 
 // kernels_export.hip: the same crop + quantise for `count` image planes from `graded` on (stride l0.plane) in one launch; image k's row r at
 // dst + k * image_pitch + r * row_pitch (bytes), nothing else written
 void launch_export_u8(hipStream_t st, const float* graded, const LevelDesc& l0, int count, uint8_t* dst, size_t row_pitch, size_t image_pitch);
-// kernels_similarity.hip: one comparison of musica_sim_compare. a: the graded f32 plane at the region's origin (margin included),
-// b: the reference slot's u8 plane at its origin; strips / segs / seg_rows: launch geometry (sim_geometry).
-struct SimQueryDev {
+// The two w x h regions a query of the study compares (musica_study.hip sim_region). a: the graded f32 plane at the region's origin
+// (margin included), b: the reference slot's u8 plane at its origin.
+struct SimRegion {
     const float* a;
     const uint8_t* b;
     int a_pitch, b_pitch;   // elements
     int w, h;
+};
+// kernels_similarity.hip: one comparison of musica_sim_compare. strips / segs / seg_rows: launch geometry (sim_geometry).
+struct SimQueryDev : SimRegion {
     int strips, segs, seg_rows;
 };
 struct SimPart {
@@ -162,13 +165,9 @@ void launch_sim(hipStream_t st, const SimQueryDev* d_qs, int count, int max_bloc
 // k_sim_vendor: `total` vendor values (u16 when bits == 16, else u8; dense, from an allocation's base) into `out` (u8, dense, from an
 // allocation's base) as 255 - (v >> 8) or 255 - v
 void launch_sim_vendor(hipStream_t st, const void* src, int bits, uint8_t* out, long long total);
-// kernels_joint.hip: one query of musica_sim_joint. a, b, pitches, w, h as SimQueryDev; chunk_rows / chunks: launch geometry
-// (joint_geometry): a workgroup counts chunk_rows whole region rows (at most 65535 pixels) between two flushes of its LDS table.
-struct JointQueryDev {
-    const float* a;
-    const uint8_t* b;
-    int a_pitch, b_pitch;
-    int w, h;
+// kernels_joint.hip: one query of musica_sim_joint. chunk_rows / chunks: launch geometry (joint_geometry): a workgroup counts
+// chunk_rows whole region rows (at most 65535 pixels) between two flushes of its LDS table.
+struct JointQueryDev : SimRegion {
     int chunk_rows, chunks;
 };
 constexpr int kJointMaxBlocks = 256;    // workgroups per launch, shared by its queries, but at least kJointMinBlocks per query; a
@@ -181,14 +180,10 @@ struct RemapLut {
     uint8_t v[256];
 };
 void launch_sim_remap(hipStream_t st, const uint8_t* src, uint8_t* out, const RemapLut& lut, long long total);
-// kernels_displace.hip: one query of musica_sim_displace. a, b, pitches, w, h as SimQueryDev; the b window grown by the radius lies
-// inside the slot's plane (the caller checks). tiles_x / tiles_y: ceil(w / 64), ceil(h / 64); tile_base: where the query's tile tables
-// start in the launch's tile-table buffer, in u32 elements (tile-row major, S^2 values per tile, S = 2 radius + 1).
-struct DisplaceQueryDev {
-    const float* a;
-    const uint8_t* b;
-    int a_pitch, b_pitch;
-    int w, h;
+// kernels_displace.hip: one query of musica_sim_displace. The b window grown by the radius lies inside the slot's plane (the caller
+// checks). tiles_x / tiles_y: ceil(w / 64), ceil(h / 64); tile_base: where the query's tile tables start in the launch's tile-table
+// buffer, in u32 elements (tile-row major, S^2 values per tile, S = 2 radius + 1).
+struct DisplaceQueryDev : SimRegion {
     int tiles_x, tiles_y;
     unsigned long long tile_base;
 };

@@ -8,25 +8,20 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
 #include <chrono>
-#include <exception>
 #include <string>
-#include <vector>
 
-#include "launchers.h"
+#include "musica_ctx.h"
 
 // host-only helpers implemented in musica_io.cpp
 extern "C" int musica_write_bmp_gray(const char* path, uint32_t w, uint32_t h, const uint8_t* data);
 extern "C" uint32_t musica_bmp24_header(uint32_t w, uint32_t h, uint8_t hdr[54]);
 extern "C" int musica_write_file(const char* path, const uint8_t* bytes, size_t count);
 
-using namespace musica;
-
 // ---- errors ---------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-static int fail(const char* fmt, ...) {
+int fail(const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -36,220 +31,6 @@ static int fail(const char* fmt, ...) {
     fprintf(stderr, "MUSICA ERROR: %s\n", buf);  // cf. "VK STATE ERROR: %s" src/vk_processing.cpp:14-18
     return 0;
 }
-
-// No C++ exception may cross the extern "C" boundary (a ctypes / CLI caller would abort): entry points that allocate
-// host memory run their body under this guard and report through fail() like every other error.
-#define ABI_TRY try {
-#define ABI_CATCH(name_)                                                                             \
-    }                                                                                                \
-    catch (const std::exception& e_) { return fail("%s: %s", name_, e_.what()); }                   \
-    catch (...) { return fail("%s: unknown C++ exception", name_); }
-
-#define HIP_OK(call)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) return fail("%s failed: %s", #call, hipGetErrorString(e_));  \
-    } while (0)
-
-// ---- context --------------------------------------------------------------------------
-struct ProfSpan {
-    int id;
-    hipEvent_t a, b;
-};
-
-// Captured graphs kept per context, one per distinct input pointer (include/musica.h, musica_execute_device).
-constexpr int kGraphSlots = 4;
-constexpr int kLaneStreams = 1;   // streams of the image lanes (musica_ctx::lanes). One: a one-image chain (0.14 - 0.19 ms) is as long as an image's copy,
-                                  // so chains on several streams would barely overlap, and which hardware queue a further stream lands on (4 queues,
-                                  // round-robin over every stream of the process) decided whether three lanes were faster or slower than none
-
-// Every device buffer that holds one slice per image: B slices, image k's at k x its elements per image. for_each_buffer names each
-// member once with that count; allocation, the image lanes and the getters all go through it.
-struct DeviceBuffers {
-    uint16_t* d_input = nullptr;
-    uint32_t* d_minmax = nullptr;
-    uint32_t* d_mm_slots = nullptr;    // [B][kMinMaxSlots]: per-block {min | max << 16} of k_minmax_u16
-    uint32_t* d_mm_ticket = nullptr;   // [B]: its arrival counters (self-resetting)
-    uint32_t* d_gr_ticket = nullptr;   // [B][kGradTicketStride]: the tickets of the one-launch recount + tone curve
-    float* d_norm = nullptr;
-    float* d_down[MUSICA_MAX_LEVELS] = {};
-    float* d_band[MUSICA_MAX_LEVELS] = {};
-    float* d_recon[MUSICA_MAX_LEVELS] = {};
-    float* d_sdev[4] = {};
-    uint32_t* d_noise_hist = nullptr;
-    musica_hist_max_point* d_noise_max = nullptr;
-    DevCurve* d_curves = nullptr;
-    DevCurveLut* d_luts = nullptr;
-    float* d_cnr = nullptr;
-    uint32_t* d_grad_hist = nullptr;
-    uint32_t* d_grad_hist_b = nullptr;   // the literal recount of images whose reconstruction holds an exact zero (fused gradation histogram)
-    uint32_t* d_gzero = nullptr;         // [B]: that condition
-    int* d_thr090 = nullptr;             // [B]: raw-pixel form of `normalized <= 0.9`
-    double* d_stats_partial = nullptr;   // [B][kStatsMaxBlocks]: partial sums of the cnr image (k_stats_partial -> k_stats)
-    uint16_t* d_le090 = nullptr;         // [B][S1][S0 / 8] or null: its bit image, written by the level-0 reduce + band launch for the level-0 expand launch
-    musica_hist_max_point* d_grad_max = nullptr;
-    DevCurve* d_gcurve = nullptr;
-    float* d_graded = nullptr;
-    float* d_scratch = nullptr;
-    musica_stats* d_stats = nullptr;
-    uint32_t* d_clahe_hist = nullptr;
-    musica_point* d_clahe_pts = nullptr;
-    float* d_clahe_graded = nullptr;
-};
-
-struct musica_ctx : DeviceBuffers {
-    musica_params p;
-    musica_tunables tun;     // the constants of the host parameter formulas (musica_create_ex; default: the reference's)
-    int N, L, B;
-    bool generic;
-    int ref_order;           // MUSICA_FLAG_REFERENCE_ORDER: generic kernels in the shaders' literal 25-tap accumulation order
-    bool tuning = false;     // inside autotune(): launches are tagged so profilers keep them apart
-    LevelDesc lv[MUSICA_MAX_LEVELS + 1];
-    int min_chain_exact;
-    int hist_cov;  // (N / 512) * 512
-    hipStream_t stream = nullptr;
-    hipStream_t cur;         // stream the run_*_level helpers launch on (stream or side)
-    hipStream_t side = nullptr;   // coarse-level chain runs here, concurrently with the level-0 kernels on `stream`
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool fuse_u16;           // level-0 kernels read the raw uint16 pixels; the normalized image is produced on demand only
-    bool grad_one_launch;    // recount + tone curve in one launch behind the fused expand launch (MUSICA_GRAD_ONE_LAUNCH=0: two)
-    bool tiny_tail;          // levels of side <= kTailSide in one launch (MUSICA_TINY_TAIL=0: one launch per level and stage)
-    bool clahe_one_apply;    // ... and whose two apply passes are one launch (MUSICA_CLAHE_ONE_APPLY=0: k_grad_apply and k_clahe_apply4)
-    bool clahe_in_expand;    // ... and whose histogram the level-0 expand launch counts (MUSICA_CLAHE_IN_EXPAND=0: k_clahe_hist)
-    bool clahe_raw;          // CLAHE context whose relevant image is computed from the raw pixels (no stored normalized image)
-    bool norm_valid = false; // d_norm holds the normalized image of the current input
-    // hipGraph replay of the two-stream dispatch (captured once per input pointer; MUSICA_FLAG_NO_GRAPH /
-    // MUSICA_GRAPH=0 / per-kernel profiling fall back to eager launches)
-    bool use_graph;
-    hipGraphExec_t graph_exec[kGraphSlots] = {};      // one captured graph per input pointer, the kGraphSlots most recently used (the streaming
-    const uint16_t* graph_input[kGraphSlots] = {};    // path alternates between two device input buffers; callers may rotate a few of their own)
-    uint64_t graph_used[kGraphSlots] = {};            // launch counter at the slot's last use (least recently used slot is recaptured)
-    uint64_t graph_clock = 0;
-    int dag;                 // 0: one in-order stream (enqueue_linear); 2: two streams (enqueue_fork: the analysis beside the reduce tail)
-    // device state shared by the whole context (the per-image buffers are the DeviceBuffers base)
-    uint16_t* d_input2 = nullptr;      // second input buffer of the streaming path (musica_execute_stream), allocated on first use
-    hipStream_t copy_stream = nullptr; // its H2D copies run here, under the previous batch's kernels
-    hipEvent_t ev_copied[2] = {}, ev_consumed[2] = {};
-    const uint16_t* cur_input = nullptr;
-    musica_contrast_params* d_cparams = nullptr;
-    uint32_t* d_plot = nullptr;        // one MUSICA_HIST_RENDER_WIDTH x MUSICA_HIST_RENDER_HEIGHT rgba8 image (the RENDER_HISTS plots, on demand)
-    bool fuse_gh;              // the level-0 expand launch accumulates the gradation histogram
-    // The expand launches of levels 0 .. 2 compute the 5 x 5 RMS of their band image themselves (k_expand_fast<.., SD>) and the sdev +
-    // noise-histogram launches of those levels store nothing: 8 of a step's 48 bytes per input pixel. The whole-step scripts run that way
-    // (sd_active); the stage entry points, getters and dumps want the stored images: ensure_sdev() writes them on demand.
-    bool sd_fused, sd_active = false, sdev_stored = true;
-    bool pair_rb_sdev;         // the one-stream script pairs the sdev pass of level i with reduce + band of level i + 1 in one launch (k_rb_sdev); MUSICA_PAIR_RB_SDEV
-    bool sdev_one_launch;      // the sdev + noise-histogram passes of levels 0 .. 3 as ONE launch (k_sdev_hist_levels); MUSICA_SDEV_ONE_LAUNCH=0: one launch per marching level + one for the runs
-    int rows_rb[MUSICA_MAX_LEVELS];   // its coarse rows per wavefront
-    int xcd_swizzle;           // XCD-aware workgroup -> tile mapping of the marching kernels (launchers.h); MUSICA_XCD_SWIZZLE=0: the plain mapping
-    int xcd_regions;           // the metric kernel's 2-D regions per XCD where its geometry allows; MUSICA_XCD_REGIONS=0: the round-3 mapping
-    uint8_t* d_out8 = nullptr;   // saveOutImage's cropped 8-bit pixels of one image (device) and their pinned host copy, allocated on first use
-    uint8_t* h_out8 = nullptr;
-    uint8_t* h_bmp = nullptr;    // saveOutImage's whole file image in page-locked memory: 2 bytes of padding, the 54-byte header, then the pixel array the
-                                 // device writes itself (k_out_bmp24: the array starts on a 4-byte boundary); allocated on first use
-    // musica_sim_*: the reference slots (u8, side N - 20) and the scratch of musica_sim_compare, context-level and allocated on first use
-    uint8_t* d_sim_slot[MUSICA_SIM_SLOTS] = {};
-    bool sim_written[MUSICA_SIM_SLOTS] = {};
-    SimQueryDev* d_sim_q = nullptr;
-    SimPart* d_sim_part = nullptr;   // [MUSICA_SIM_MAX_QUERIES][kSimMaxBlocks]
-    SimPart* d_sim_out = nullptr;    // [MUSICA_SIM_MAX_QUERIES]
-    uint32_t* d_sim_hist = nullptr;  // [MUSICA_SIM_MAX_QUERIES][512]: value counts of a, then b
-    std::vector<SimQueryDev> h_sim_q;
-    uint16_t* d_sim_vendor = nullptr;   // musica_sim_set_vendor_reference's staging plane: (N - 20)^2 u16 (u8 data uses its first half)
-    JointQueryDev* d_joint_q = nullptr;   // musica_sim_joint's queries and tables, allocated on first use
-    uint32_t* d_joint = nullptr;          // [MUSICA_SIM_MAX_QUERIES][65536]: J[a][b], row a
-    DisplaceQueryDev* d_disp_q = nullptr;          // musica_sim_displace's queries, tables and counts, allocated on first use
-    unsigned long long* d_disp_tables = nullptr;   // [MUSICA_SIM_MAX_QUERIES][33 * 33]
-    uint32_t* d_disp_off = nullptr;                // [MUSICA_SIM_MAX_QUERIES]: tiles_off
-    uint32_t* d_disp_tiles = nullptr;              // the tile tables of one call: disp_tiles_cap u32, regrown when a call needs more
-    size_t disp_tiles_cap = 0;
-    // musica_alter_*: the source plane (N x N u16), the radix-select counts and the fill, allocated on first use
-    uint16_t* d_alter_src = nullptr;
-    uint32_t* d_alter_hist = nullptr;    // [768]
-    double* d_alter_fill = nullptr;      // [1]
-    int32_t* d_alter_draws = nullptr;    // [N * N], musica_alter_draws only
-    uint16_t* d_input_kept = nullptr;    // the last step's input when an alteration overwrites d_input after it (the on-demand getters read it)
-    // musica_export_out / musica_stream_wait / musica_stream_signal: a step has been enqueued (the export refuses a context without one), and
-    // the two events that order the context's stream against a caller's stream, created on first use
-    bool stepped = false;
-    hipEvent_t ev_caller = nullptr, ev_signal = nullptr;
-    // host parameters (src/vk_processing.cpp:259-297, 321-325)
-    musica_contrast_params h_cparams[MUSICA_MAX_LEVELS];
-    musica_nr_params h_nr[3];
-    // rows each wavefront marches per launch, per level (heuristic, then autotuned at create)
-    int rows_expand[MUSICA_MAX_LEVELS], rows_sdev[4];
-    // tunables
-    int expand_rows, sdev_rows, grad_groups, min_waves;
-    // profiling
-    uint32_t profiling = 0;  // bit i set: bracket kernel family i with HIP events
-    std::vector<ProfSpan> spans;
-    size_t spans_used = 0;
-    double prof_total_us[MUSICA_KERNEL_COUNT] = {};
-    uint64_t prof_count[MUSICA_KERNEL_COUNT] = {};
-    bool needs_reset = false;  // a step failed (launch / sync error): the self-resetting tickets of k_minmax_u16 and k_grad_recount_curve may hold a
-                               // partial count, which would leave every later launch without a last-ticket block — zeroed before the next step
-    std::vector<void*> allocations;
-    // Image lanes (musica_execute of a context with a batch, from page-locked host memory): shallow copies of the context for one or
-    // two images each — device pointers moved to those images — whose one-stream script is enqueued behind the host-to-device copy of
-    // just those images. Every stage of the path is per image, so nothing changes in the results; the first images' kernels run under
-    // the remaining copies. Created on first use.
-    std::vector<musica_ctx*> lanes;
-    hipStream_t lane_stream[kLaneStreams] = {};
-    hipStream_t lane_copy[2] = {};   // the images' copies ([1]: unused; two alternating copy streams made every copy twice as long)
-    hipEvent_t lane_done[kLaneStreams] = {}, lane_start = nullptr;
-    std::vector<hipEvent_t> img_copied;   // one per image
-};
-
-// Calls f(member, elements per image) for every member of DeviceBuffers, in allocation order; 0 elements: a buffer this context does
-// not have. Returns the number of pointers visited (create_impl checks it against the size of DeviceBuffers).
-template <typename D, typename F>
-static size_t for_each_buffer(D& d, const musica_ctx& c, F f) {
-    size_t visited = 0;
-    auto v = [&](auto& ptr, size_t count) { f(ptr, count); visited++; };
-    const bool clahe = (c.p.flags & MUSICA_FLAG_CLAHE) != 0;
-    const size_t plane0 = c.lv[0].plane, tiles = (size_t)MUSICA_CLAHE_TILES * MUSICA_CLAHE_TILES * MUSICA_CLAHE_BINS;
-    v(d.d_input, (size_t)c.N * c.N);
-    v(d.d_minmax, kMinMaxStride);
-    v(d.d_mm_slots, kMinMaxSlots);
-    v(d.d_mm_ticket, kMinMaxStride);   // one 128-byte line per image
-    v(d.d_gr_ticket, kGradTicketStride);
-    v(d.d_norm, plane0);
-    for (int i = 0; i < MUSICA_MAX_LEVELS; i++) {
-        v(d.d_down[i], i < c.L ? c.lv[i + 1].plane : 0);
-        v(d.d_band[i], i < c.L ? c.lv[i].plane : 0);
-        v(d.d_recon[i], i < c.L ? c.lv[i].plane : 0);
-        if (i <= MUSICA_CNR_LEVEL) v(d.d_sdev[i], i < c.L ? c.lv[i].plane : 0);
-    }
-    v(d.d_noise_hist, 4 * MUSICA_NOISE_BINS);
-    v(d.d_noise_max, c.L);
-    v(d.d_curves, c.L);
-    v(d.d_luts, MUSICA_COARSER_LEVELS_START);
-    v(d.d_cnr, c.lv[MUSICA_CNR_LEVEL].plane);
-    v(d.d_grad_hist, MUSICA_GRAD_BINS);
-    v(d.d_grad_hist_b, MUSICA_GRAD_BINS);
-    v(d.d_gzero, 1);
-    v(d.d_thr090, 1);
-    v(d.d_stats_partial, kStatsMaxBlocks);
-    v(d.d_le090, c.fuse_gh ? (size_t)c.lv[1].S * (c.lv[0].S / 8) : 0);
-    v(d.d_grad_max, 1);
-    v(d.d_gcurve, 1);
-    v(d.d_graded, plane0);
-    v(d.d_scratch, plane0);
-    v(d.d_stats, 1);
-    v(d.d_clahe_hist, clahe ? tiles : 0);
-    v(d.d_clahe_pts, clahe ? tiles : 0);
-    v(d.d_clahe_graded, clahe ? plane0 : 0);
-    return visited;
-}
-// Elements per image of `buf`, a member of c's DeviceBuffers, and image idx's slice of it.
-template <typename T>
-static size_t per_image(const musica_ctx* c, T* const& buf) {
-    size_t count = 0;
-    for_each_buffer(*c, *c, [&](auto& ptr, size_t n) { if ((const void*)&ptr == (const void*)&buf) count = n; });
-    return count;
-}
-template <typename T>
-static T* image_slice(const musica_ctx* c, T* const& buf, uint32_t idx) { return buf + (size_t)idx * per_image(c, buf); }
 
 static int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -270,20 +51,6 @@ struct Tick {
         t = n;
     }
 };
-
-template <typename T>
-static bool dalloc(musica_ctx* c, T** out, size_t count) {
-    void* p = nullptr;
-    if (count == 0) count = 1;
-    if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) return false;
-    // "never-written texels read as 0" (Q2). hipMemset runs on the null stream, which the context's non-blocking streams do not wait for:
-    // drain it here, or a buffer allocated on first use (the 8-bit output, the second input buffer) could be zeroed AFTER the first
-    // kernel or copy has written it (seen once as zero rows at the top of saveOutImage's pixels)
-    if (hipMemset(p, 0, count * sizeof(T)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { hipFree(p); return false; }
-    c->allocations.push_back(p);
-    *out = (T*)p;
-    return true;
-}
 
 // highContrastFactor / lowContrastFactor per level: src/vk_processing.cpp:259-293, both forms of each (the reference picks one per
 // #define LINEAR_*_CONTRAST_LEVELS_REDUCTION, include/vk_processing.h:16-17; musica_tunables carries the choice).
@@ -1145,9 +912,6 @@ static int download_small(musica_ctx* c, const T* d_src, T* dst, size_t count) {
     return 1;
 }
 
-#define CHECK_CTX(c) do { if (!(c)) return fail("%s: ctx is NULL", __func__); if (hipSetDevice((c)->p.device) != hipSuccess) return fail("%s: hipSetDevice failed", __func__); } while (0)
-#define CHECK_IMG(c, idx) do { if ((int)(idx) >= (c)->B) return fail("%s: image_index %u >= batch %d", __func__, (unsigned)(idx), (c)->B); } while (0)
-
 extern "C" {
 
 // ---- image lanes (see musica_ctx::lanes) ----------------------------------------------------------------------------------
@@ -1315,7 +1079,7 @@ int musica_execute_stream(musica_ctx* c, const uint16_t* const* pixels, uint32_t
     if (!pixels) return fail("musica_execute_stream: pixels is NULL");
     const size_t bytes = (size_t)c->B * c->N * c->N * sizeof(uint16_t);
     if (!c->ev_consumed[1]) {   // keyed on the LAST resource of the block: a call that failed half-way is retried, never half-initialised
-        if (!c->d_input2 && !dalloc(c, &c->d_input2, (size_t)c->B * c->N * c->N)) return fail("musica_execute_stream: device allocation failed");
+        if (!ensure(c, &c->d_input2, (size_t)c->B * c->N * c->N)) return fail("musica_execute_stream: device allocation failed");
         if (!c->copy_stream) HIP_OK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
         for (int k = 0; k < 2; k++) {
             if (!c->ev_copied[k]) HIP_OK(hipEventCreateWithFlags(&c->ev_copied[k], hipEventDisableTiming));
@@ -1515,7 +1279,7 @@ static const uint8_t* out_pixels_pinned(musica_ctx* c, uint32_t idx) {
     const size_t nw = N - 2 * margin, bytes = nw * nw;
     Tick tick("save");
     if (!c->h_out8) {   // keyed on the LAST resource of the block: a call that failed half-way is retried, never half-initialised
-        if (!c->d_out8 && !dalloc(c, &c->d_out8, bytes)) { fail("saveOutImage: device allocation failed"); return nullptr; }
+        if (!ensure(c, &c->d_out8, bytes)) { fail("saveOutImage: device allocation failed"); return nullptr; }
         if (hipHostMalloc((void**)&c->h_out8, bytes, hipHostMallocDefault) != hipSuccess) { c->h_out8 = nullptr; fail("saveOutImage: pinned allocation failed"); return nullptr; }
     }
     tick.lap("device + pinned buffers");
@@ -1575,578 +1339,6 @@ int musica_save_out_image(musica_ctx* c, uint32_t idx, const char* path) {
     tick.lap("bmp file");
     return 1;
     ABI_CATCH("musica_save_out_image")
-}
-
-// ---- similarity metrics (musica_sim_*, include/musica.h; kernels_similarity.hip) ----------------------------------------------------
-static uint8_t* sim_slot(musica_ctx* c, uint32_t slot) {
-    const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
-    if (!c->d_sim_slot[slot] && !dalloc(c, &c->d_sim_slot[slot], nw * nw)) { fail("musica_sim: device allocation of slot %u failed", slot); return nullptr; }
-    return c->d_sim_slot[slot];
-}
-
-int musica_sim_capture(musica_ctx* c, uint32_t slot, uint32_t idx) {
-    if (!c) return fail("musica_sim_capture: ctx is NULL");
-    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_capture: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
-    CHECK_IMG(c, idx);
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_capture: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
-    CHECK_CTX(c);
-    uint8_t* dst = sim_slot(c, slot);
-    if (!dst) return 0;
-    launch_out_pixels(c->stream, image_slice(c, c->d_graded, idx), c->lv[0], MUSICA_OUT_MARGIN, dst);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("musica_sim_capture: launch failed: %s", hipGetErrorString(e));
-    c->sim_written[slot] = true;
-    return 1;
-}
-
-int musica_sim_set_reference(musica_ctx* c, uint32_t slot, const uint8_t* pixels) {
-    if (!c) return fail("musica_sim_set_reference: ctx is NULL");
-    if (!pixels) return fail("musica_sim_set_reference: pixels is NULL");
-    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_set_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_set_reference: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
-    CHECK_CTX(c);
-    uint8_t* dst = sim_slot(c, slot);
-    if (!dst) return 0;
-    const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
-    HIP_OK(hipMemcpyAsync(dst, pixels, nw * nw, hipMemcpyHostToDevice, c->stream));   // after what the stream holds (a compare reading the slot)
-    HIP_OK(hipStreamSynchronize(c->stream));                                             // `pixels` is borrowed for the call
-    c->sim_written[slot] = true;
-    return 1;
-}
-
-int musica_sim_set_vendor_reference(musica_ctx* c, uint32_t slot, const void* pixels, uint32_t bits_allocated) {
-    if (!c) return fail("musica_sim_set_vendor_reference: ctx is NULL");
-    if (!pixels) return fail("musica_sim_set_vendor_reference: pixels is NULL");
-    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_set_vendor_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
-    if (bits_allocated != 8 && bits_allocated != 16) return fail("musica_sim_set_vendor_reference: bits_allocated %u is neither 8 nor 16", bits_allocated);
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_set_vendor_reference: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
-    CHECK_CTX(c);
-    uint8_t* dst = sim_slot(c, slot);
-    if (!dst) return 0;
-    const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
-    if (!c->d_sim_vendor && !dalloc(c, &c->d_sim_vendor, nw * nw)) return fail("musica_sim_set_vendor_reference: device allocation of the staging plane failed");
-    // after what the stream holds (a compare reading the slot); `pixels` is borrowed for the call
-    HIP_OK(hipMemcpyAsync(c->d_sim_vendor, pixels, nw * nw * (bits_allocated / 8), hipMemcpyHostToDevice, c->stream));
-    launch_sim_vendor(c->stream, c->d_sim_vendor, (int)bits_allocated, dst, (long long)(nw * nw));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(c->stream));
-    c->sim_written[slot] = true;
-    return 1;
-}
-
-// harness.hist_similarity from the exact value counts: np.histogram(v, bins=256) of u8 data spans [lo, hi] = [min, max] and puts v
-// into bin min(255, (v - lo) * 256 // (hi - lo)) — exactly, for every (lo, hi) — and everything into bin 128 when lo == hi
-// (numpy widens the range by +-0.5).
-static void sim_bins(const uint32_t* counts, uint32_t* bins, uint32_t* lo_out, uint32_t* hi_out) {
-    int lo = 0, hi = 255;
-    while (lo < 255 && counts[lo] == 0) lo++;
-    while (hi > 0 && counts[hi] == 0) hi--;
-    memset(bins, 0, 256 * sizeof(uint32_t));
-    for (int v = lo; v <= hi; v++) {
-        if (!counts[v]) continue;
-        const int b = hi == lo ? 128 : std::min(255, (v - lo) * 256 / (hi - lo));
-        bins[b] += counts[v];
-    }
-    *lo_out = (uint32_t)lo;
-    *hi_out = (uint32_t)hi;
-}
-
-static void sim_finish(const uint32_t* counts /* a 256 | b 256 */, const SimPart& r, const musica_sim_query& q, musica_sim_result* o) {
-    const uint64_t n = (uint64_t)q.w * q.h;
-    o->sq_diff_sum = r.ssd;
-    o->pixels = n;
-    sim_bins(counts, o->bins_a, &o->min_a, &o->max_a);
-    sim_bins(counts + 256, o->bins_b, &o->min_b, &o->max_b);
-    o->mse = 1.0 - sqrt((double)r.ssd / (65025.0 * (double)n));                 // 1 - sqrt(mean(((a - b) / 255)^2))
-    o->ssim = r.ssim / ((double)(q.w - 6) * (double)(q.h - 6));                // mean over the interior (borders of 3 cropped)
-    uint64_t inter = 0;
-    double e2 = 0.0, bc = 0.0;
-    for (int i = 0; i < 256; i++) {
-        inter += std::min(o->bins_a[i], o->bins_b[i]);
-        const double na = (double)o->bins_a[i] / (double)n, nb = (double)o->bins_b[i] / (double)n;
-        e2 += (na - nb) * (na - nb);
-        bc += sqrt(na * nb);
-    }
-    o->hist_intersection = (double)inter / (double)n;
-    o->hist_distance = sqrt(e2) / sqrt(2.0);
-    o->hist_bhattacharyya = bc;
-}
-
-// What musica_sim_compare and musica_sim_joint refuse, in the same words (`what`: the entry point), before any device work.
-static int sim_check_queries(musica_ctx* c, const char* what, uint32_t count, const musica_sim_query* qs, const void* out) {
-    if (!c) return fail("%s: ctx is NULL", what);
-    if (!qs || !out) return fail("%s: queries or results is NULL", what);
-    if (count == 0 || count > MUSICA_SIM_MAX_QUERIES) return fail("%s: count %u out of range [1, %d]", what, count, MUSICA_SIM_MAX_QUERIES);
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("%s: image too small for the %d-pixel margin", what, MUSICA_OUT_MARGIN);
-    const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
-    for (uint32_t i = 0; i < count; i++) {
-        const musica_sim_query& q = qs[i];
-        if (q.slot >= MUSICA_SIM_SLOTS) return fail("%s: query %u: slot %u >= %d", what, i, q.slot, MUSICA_SIM_SLOTS);
-        if (!c->sim_written[q.slot]) return fail("%s: query %u: slot %u was never written", what, i, q.slot);
-        if ((int)q.image_index >= c->B) return fail("%s: query %u: image_index %u >= batch %d", what, i, q.image_index, c->B);
-        if (q.w < 7 || q.h < 7) return fail("%s: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", what, i, q.w, q.h);
-        if ((uint64_t)q.ax + q.w > nw || (uint64_t)q.ay + q.h > nw || (uint64_t)q.bx + q.w > nw || (uint64_t)q.by + q.h > nw)
-            return fail("%s: query %u: region (%u, %u) / (%u, %u) + %u x %u leaves the %llu x %llu planes", what, i, q.ax, q.ay, q.bx, q.by,
-                        q.w, q.h, (unsigned long long)nw, (unsigned long long)nw);
-    }
-    return 1;
-}
-
-int musica_sim_compare(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_result* out) {
-    ABI_TRY
-    if (!sim_check_queries(c, "musica_sim_compare", count, qs, out)) return 0;
-    const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
-    CHECK_CTX(c);
-    if (!c->d_sim_hist) {   // keyed on the LAST allocation of the block
-        const bool ok = (c->d_sim_q || dalloc(c, &c->d_sim_q, MUSICA_SIM_MAX_QUERIES)) &&
-                        (c->d_sim_part || dalloc(c, &c->d_sim_part, (size_t)MUSICA_SIM_MAX_QUERIES * kSimMaxBlocks)) &&
-                        (c->d_sim_out || dalloc(c, &c->d_sim_out, MUSICA_SIM_MAX_QUERIES)) &&
-                        dalloc(c, &c->d_sim_hist, (size_t)MUSICA_SIM_MAX_QUERIES * 512);
-        if (!ok) return fail("musica_sim_compare: device allocation failed");
-    }
-    c->h_sim_q.assign(count, SimQueryDev{});
-    int max_blocks = 1;
-    for (uint32_t i = 0; i < count; i++) {
-        const musica_sim_query& q = qs[i];
-        SimQueryDev& d = c->h_sim_q[i];
-        d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
-        d.b = c->d_sim_slot[q.slot] + (size_t)q.by * nw + q.bx;
-        d.a_pitch = c->lv[0].pitch;
-        d.b_pitch = (int)nw;
-        d.w = (int)q.w;
-        d.h = (int)q.h;
-        sim_geometry(d);
-        max_blocks = std::max(max_blocks, d.strips * d.segs);
-    }
-    SimConsts k;
-    const double k1 = 0.01 * 255, k2 = 0.03 * 255;   // harness.ssim_similarity: c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2 (float ** is C pow)
-    k.c1 = pow(k1, 2.0);
-    k.c2 = pow(k2, 2.0);
-    k.cov_norm = 49.0 / 48.0;                         // npx / (npx - 1)
-    HIP_OK(hipMemcpyAsync(c->d_sim_q, c->h_sim_q.data(), count * sizeof(SimQueryDev), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemsetAsync(c->d_sim_hist, 0, (size_t)count * 512 * sizeof(uint32_t), c->stream));
-    launch_sim(c->stream, c->d_sim_q, (int)count, max_blocks, c->d_sim_part, c->d_sim_hist, c->d_sim_out, k);
-    HIP_OK(hipGetLastError());
-    std::vector<uint32_t> hist((size_t)count * 512);
-    std::vector<SimPart> parts(count);
-    HIP_OK(hipMemcpyAsync(hist.data(), c->d_sim_hist, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(parts.data(), c->d_sim_out, count * sizeof(SimPart), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < count; i++) sim_finish(hist.data() + (size_t)i * 512, parts[i], qs[i], out + i);
-    return 1;
-    ABI_CATCH("musica_sim_compare")
-}
-
-static bool finite_all(const double* v, int n) {
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-int musica_sim_rotate_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const double matrix[4], const double offset[2]) {
-    if (!c) return fail("musica_sim_rotate_reference: ctx is NULL");
-    if (!matrix || !offset) return fail("musica_sim_rotate_reference: matrix or offset is NULL");
-    if (dst_slot >= MUSICA_SIM_SLOTS || src_slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_rotate_reference: slot %u / %u >= %d", dst_slot, src_slot, MUSICA_SIM_SLOTS);
-    if (dst_slot == src_slot) return fail("musica_sim_rotate_reference: dst_slot == src_slot (%u)", dst_slot);
-    if (!c->sim_written[src_slot]) return fail("musica_sim_rotate_reference: slot %u was never written", src_slot);
-    if (!finite_all(matrix, 4) || !finite_all(offset, 2)) return fail("musica_sim_rotate_reference: matrix or offset is not finite");
-    CHECK_CTX(c);
-    uint8_t* dst = sim_slot(c, dst_slot);
-    if (!dst) return 0;
-    AlterDev a{};
-    a.n = c->N - 2 * MUSICA_OUT_MARGIN;
-    memcpy(a.m, matrix, sizeof(a.m));
-    memcpy(a.off, offset, sizeof(a.off));
-    launch_rotate_u8(c->stream, c->d_sim_slot[src_slot], dst, a);
-    HIP_OK(hipGetLastError());
-    c->sim_written[dst_slot] = true;
-    return 1;
-}
-
-int musica_sim_transform_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t element) {
-    if (!c) return fail("musica_sim_transform_reference: ctx is NULL");
-    if (dst_slot >= MUSICA_SIM_SLOTS || src_slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_transform_reference: slot %u / %u >= %d", dst_slot, src_slot, MUSICA_SIM_SLOTS);
-    if (dst_slot == src_slot) return fail("musica_sim_transform_reference: dst_slot == src_slot (%u)", dst_slot);
-    if (!c->sim_written[src_slot]) return fail("musica_sim_transform_reference: slot %u was never written", src_slot);
-    if (element > 7) return fail("musica_sim_transform_reference: element %u is not one of the square's 8 symmetries (0 .. 7)", element);
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_transform_reference: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
-    CHECK_CTX(c);
-    uint8_t* dst = sim_slot(c, dst_slot);
-    if (!dst) return 0;
-    launch_symmetry_u8(c->stream, c->d_sim_slot[src_slot], dst, c->N - 2 * MUSICA_OUT_MARGIN, (int)element);
-    HIP_OK(hipGetLastError());
-    c->sim_written[dst_slot] = true;
-    return 1;
-}
-
-int musica_sim_get_reference(musica_ctx* c, uint32_t slot, uint8_t* dst) {
-    if (!c) return fail("musica_sim_get_reference: ctx is NULL");
-    if (!dst) return fail("musica_sim_get_reference: dst is NULL");
-    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_get_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
-    if (!c->sim_written[slot]) return fail("musica_sim_get_reference: slot %u was never written", slot);
-    CHECK_CTX(c);
-    const size_t nw = (size_t)c->N - 2 * MUSICA_OUT_MARGIN;
-    HIP_OK(hipMemcpyAsync(dst, c->d_sim_slot[slot], nw * nw, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
-}
-
-// musica_sim_joint's numbers from one exact table (include/musica.h states them; harness.tone_similarities restates them): sums in
-// ascending a, then ascending b, zero counts skipped; the variance numerators as exact 128-bit integers, one f64 division per term.
-static void joint_finish(const uint32_t* J, const musica_sim_query& q, musica_sim_joint_result* o) {
-    typedef unsigned __int128 u128;
-    const uint64_t n = (uint64_t)q.w * q.h;
-    const double dn = (double)n;
-    uint64_t A[256] = {}, B[256] = {}, S[256] = {}, Q[256] = {};
-    uint64_t ssd = 0;
-    for (int a = 0; a < 256; a++)
-        for (int b = 0; b < 256; b++) {
-            const uint64_t j = J[a * 256 + b];
-            if (!j) continue;
-            A[a] += j;
-            B[b] += j;
-            S[b] += (uint64_t)a * j;
-            Q[b] += (uint64_t)(a * a) * j;
-            ssd += (uint64_t)((a - b) * (a - b)) * j;
-        }
-    double h_a = 0.0, h_b = 0.0, h_ab = 0.0, mi = 0.0;
-    for (int a = 0; a < 256; a++)
-        if (A[a]) { const double p = (double)A[a] / dn; h_a -= p * log(p); }
-    for (int b = 0; b < 256; b++)
-        if (B[b]) { const double p = (double)B[b] / dn; h_b -= p * log(p); }
-    for (int a = 0; a < 256; a++)
-        for (int b = 0; b < 256; b++) {
-            const uint64_t j = J[a * 256 + b];
-            if (!j) continue;
-            const double p = (double)j / dn;
-            h_ab -= p * log(p);
-            mi += p * log((double)(j * n) / (double)(A[a] * B[b]));   // both products < 2^57
-        }
-    double ssw = 0.0;
-    for (int b = 0; b < 256; b++) {
-        o->tone_lut[b] = (uint8_t)(B[b] ? (2 * S[b] + B[b]) / (2 * B[b]) : (uint64_t)b);
-        if (B[b]) ssw += (double)((u128)B[b] * Q[b] - (u128)S[b] * S[b]) / (double)B[b];   // B Q >= S^2 (Cauchy-Schwarz)
-    }
-    uint64_t sa = 0, saa = 0;
-    for (int a = 0; a < 256; a++) {
-        sa += (uint64_t)a * A[a];
-        saa += (uint64_t)(a * a) * A[a];
-    }
-    const u128 sst_num = (u128)n * saa - (u128)sa * sa;
-    o->mi = mi;
-    o->nmi = h_a + h_b == 0.0 ? 1.0 : 2.0 * mi / (h_a + h_b);
-    o->corr_ratio = sst_num == 0 ? 1.0 : 1.0 - ssw / ((double)sst_num / dn);
-    o->tone_mse = 1.0 - sqrt(ssw / dn) / 255.0;
-    o->h_a = h_a;
-    o->h_b = h_b;
-    o->h_ab = h_ab;
-    o->pixels = n;
-    o->sq_diff_sum = ssd;
-}
-
-int musica_sim_joint(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_joint_result* out, uint32_t* joint) {
-    ABI_TRY
-    if (!sim_check_queries(c, "musica_sim_joint", count, qs, out)) return 0;
-    const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
-    CHECK_CTX(c);
-    if (!c->d_joint) {   // keyed on the LAST allocation of the block
-        const bool ok = (c->d_joint_q || dalloc(c, &c->d_joint_q, MUSICA_SIM_MAX_QUERIES)) &&
-                        dalloc(c, &c->d_joint, (size_t)MUSICA_SIM_MAX_QUERIES * 65536);
-        if (!ok) return fail("musica_sim_joint: device allocation failed");
-    }
-    std::vector<JointQueryDev> hq(count);
-    int max_chunks = 1;
-    for (uint32_t i = 0; i < count; i++) {
-        const musica_sim_query& q = qs[i];
-        JointQueryDev& d = hq[i];
-        d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
-        d.b = c->d_sim_slot[q.slot] + (size_t)q.by * nw + q.bx;
-        d.a_pitch = c->lv[0].pitch;
-        d.b_pitch = (int)nw;
-        d.w = (int)q.w;
-        d.h = (int)q.h;
-        joint_geometry(d, (int)count);
-        max_chunks = std::max(max_chunks, d.chunks);
-    }
-    std::vector<uint32_t> own;
-    if (!joint) {
-        own.resize((size_t)count * 65536);
-        joint = own.data();
-    }
-    HIP_OK(hipMemcpyAsync(c->d_joint_q, hq.data(), count * sizeof(JointQueryDev), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemsetAsync(c->d_joint, 0, (size_t)count * 65536 * sizeof(uint32_t), c->stream));
-    launch_joint(c->stream, c->d_joint_q, (int)count, max_chunks, c->d_joint);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(joint, c->d_joint, (size_t)count * 65536 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
-    for (uint32_t i = 0; i < count; i++) {
-        memset(out + i, 0, sizeof(out[i]));
-        joint_finish(joint + (size_t)i * 65536, qs[i], out + i);
-    }
-    return 1;
-    ABI_CATCH("musica_sim_joint")
-}
-
-// The argmin of an S x S displacement table by include/musica.h's tie rule: smallest value, then smallest dx^2 + dy^2, then smallest dy,
-// then smallest dx (harness.displacement_from_table restates it).
-static void displace_finish(const uint64_t* T, int radius, musica_sim_displace_result* o) {
-    const int S = 2 * radius + 1;
-    int by = radius, bx = radius;
-    for (int y = 0; y < S; y++)
-        for (int x = 0; x < S; x++) {
-            const uint64_t v = T[y * S + x], m = T[by * S + bx];
-            const int d2 = (x - radius) * (x - radius) + (y - radius) * (y - radius);
-            const int m2 = (bx - radius) * (bx - radius) + (by - radius) * (by - radius);
-            if (v < m || (v == m && d2 < m2)) {   // equal value and distance: the scan order is ascending dy, then ascending dx
-                by = y;
-                bx = x;
-            }
-        }
-    o->ssd_zero = T[radius * S + radius];
-    o->ssd_min = T[by * S + bx];
-    o->dx = bx - radius;
-    o->dy = by - radius;
-}
-
-int musica_sim_displace(musica_ctx* c, uint32_t count, const musica_sim_query* qs, uint32_t radius, musica_sim_displace_result* out,
-                        uint64_t* tables, uint32_t* tile_tables) {
-    ABI_TRY
-    if (!sim_check_queries(c, "musica_sim_displace", count, qs, out)) return 0;
-    if (radius < 1 || radius > MUSICA_SIM_MAX_RADIUS) return fail("musica_sim_displace: radius %u out of range [1, %d]", radius, MUSICA_SIM_MAX_RADIUS);
-    const uint64_t nw = (uint64_t)c->N - 2 * MUSICA_OUT_MARGIN;
-    for (uint32_t i = 0; i < count; i++) {
-        const musica_sim_query& q = qs[i];
-        if (q.bx < radius || q.by < radius || (uint64_t)q.bx + q.w + radius > nw || (uint64_t)q.by + q.h + radius > nw)
-            return fail("musica_sim_displace: query %u: the b window (%u, %u) + %u x %u grown by the radius %u leaves the %llu x %llu plane", i, q.bx,
-                        q.by, q.w, q.h, radius, (unsigned long long)nw, (unsigned long long)nw);
-    }
-    const size_t S2 = (size_t)(2 * radius + 1) * (2 * radius + 1);
-    std::vector<DisplaceQueryDev> hq(count);
-    size_t tile_words = 0;
-    int max_tiles = 1;
-    for (uint32_t i = 0; i < count; i++) {
-        const musica_sim_query& q = qs[i];
-        DisplaceQueryDev& d = hq[i];
-        d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
-        d.b = c->d_sim_slot[q.slot] + (size_t)q.by * nw + q.bx;
-        d.a_pitch = c->lv[0].pitch;
-        d.b_pitch = (int)nw;
-        d.w = (int)q.w;
-        d.h = (int)q.h;
-        d.tiles_x = (d.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
-        d.tiles_y = (d.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
-        d.tile_base = tile_words;
-        tile_words += (size_t)d.tiles_x * d.tiles_y * S2;
-        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
-    }
-    CHECK_CTX(c);
-    if (!c->d_disp_off) {   // keyed on the LAST allocation of the block
-        const bool ok = (c->d_disp_q || dalloc(c, &c->d_disp_q, MUSICA_SIM_MAX_QUERIES)) &&
-                        (c->d_disp_tables || dalloc(c, &c->d_disp_tables, (size_t)MUSICA_SIM_MAX_QUERIES * (2 * MUSICA_SIM_MAX_RADIUS + 1) * (2 * MUSICA_SIM_MAX_RADIUS + 1))) &&
-                        dalloc(c, &c->d_disp_off, MUSICA_SIM_MAX_QUERIES);
-        if (!ok) return fail("musica_sim_displace: device allocation failed");
-    }
-    if (tile_words > c->disp_tiles_cap) {   // sized for the call: the largest call so far
-        if (c->d_disp_tiles) {
-            HIP_OK(hipStreamSynchronize(c->stream));
-            c->allocations.erase(std::remove(c->allocations.begin(), c->allocations.end(), (void*)c->d_disp_tiles), c->allocations.end());
-            hipFree(c->d_disp_tiles);
-            c->d_disp_tiles = nullptr;
-            c->disp_tiles_cap = 0;
-        }
-        if (!dalloc(c, &c->d_disp_tiles, tile_words)) return fail("musica_sim_displace: device allocation of %zu tile-table words failed", tile_words);
-        c->disp_tiles_cap = tile_words;
-    }
-    HIP_OK(hipMemcpyAsync(c->d_disp_q, hq.data(), count * sizeof(DisplaceQueryDev), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemsetAsync(c->d_disp_tables, 0, count * S2 * sizeof(unsigned long long), c->stream));
-    HIP_OK(hipMemsetAsync(c->d_disp_off, 0, count * sizeof(uint32_t), c->stream));
-    launch_displace(c->stream, c->d_disp_q, (int)count, max_tiles, (int)radius, c->d_disp_tiles, c->d_disp_tables, c->d_disp_off);
-    HIP_OK(hipGetLastError());
-    std::vector<uint64_t> own;
-    if (!tables) {
-        own.resize(count * S2);
-        tables = own.data();
-    }
-    std::vector<uint32_t> off(count);
-    HIP_OK(hipMemcpyAsync(tables, c->d_disp_tables, count * S2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(off.data(), c->d_disp_off, count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (tile_tables) HIP_OK(hipMemcpyAsync(tile_tables, c->d_disp_tiles, tile_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
-    for (uint32_t i = 0; i < count; i++) {
-        memset(out + i, 0, sizeof(out[i]));
-        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
-        out[i].tiles_x = (uint32_t)hq[i].tiles_x;
-        out[i].tiles_y = (uint32_t)hq[i].tiles_y;
-        out[i].tiles_off = off[i];
-        displace_finish(tables + (size_t)i * S2, (int)radius, out + i);
-    }
-    return 1;
-    ABI_CATCH("musica_sim_displace")
-}
-
-int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]) {
-    if (!c) return fail("musica_sim_remap_reference: ctx is NULL");
-    if (!lut) return fail("musica_sim_remap_reference: lut is NULL");
-    if (dst_slot >= MUSICA_SIM_SLOTS || src_slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_remap_reference: slot %u / %u >= %d", dst_slot, src_slot, MUSICA_SIM_SLOTS);
-    if (dst_slot == src_slot) return fail("musica_sim_remap_reference: dst_slot == src_slot (%u)", dst_slot);
-    if (!c->sim_written[src_slot]) return fail("musica_sim_remap_reference: slot %u was never written", src_slot);
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_remap_reference: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
-    CHECK_CTX(c);
-    uint8_t* dst = sim_slot(c, dst_slot);
-    if (!dst) return 0;
-    RemapLut t;
-    memcpy(t.v, lut, sizeof(t.v));   // travels as a kernel argument: `lut` is free again when the call returns
-    const long long nw = c->N - 2 * MUSICA_OUT_MARGIN;
-    launch_sim_remap(c->stream, c->d_sim_slot[src_slot], dst, t, nw * nw);
-    HIP_OK(hipGetLastError());
-    c->sim_written[dst_slot] = true;
-    return 1;
-}
-
-// ---- alterations of the study (musica_alter_*, include/musica.h; kernels_alteration.hip) ----------------------------------------------
-int musica_alter_set_source(musica_ctx* c, const uint16_t* pixels) {
-    if (!c) return fail("musica_alter_set_source: ctx is NULL");
-    if (!pixels) return fail("musica_alter_set_source: pixels is NULL");
-    CHECK_CTX(c);
-    const size_t nn = (size_t)c->N * c->N;
-    if (!c->d_alter_src && !dalloc(c, &c->d_alter_src, nn)) return fail("musica_alter_set_source: device allocation failed");
-    HIP_OK(hipMemcpyAsync(c->d_alter_src, pixels, nn * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));   // after alterations that read it
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
-}
-
-static bool alter_scratch(musica_ctx* c) {
-    if (c->d_alter_fill) return true;   // keyed on the LAST allocation of the block
-    return (c->d_alter_hist || dalloc(c, &c->d_alter_hist, 768)) && dalloc(c, &c->d_alter_fill, 1);
-}
-
-// The region's percentile into d_alter_fill, on the stream.
-static int enqueue_percentile(musica_ctx* c, int x, int y, int w, int h, double q) {
-    PctRegion g{c->d_alter_src, c->N, x, y, w, h, q};
-    HIP_OK(hipMemsetAsync(c->d_alter_hist, 0, 768 * sizeof(uint32_t), c->stream));
-    launch_percentile(c->stream, g, c->d_alter_hist, c->d_alter_fill);
-    HIP_OK(hipGetLastError());
-    return 1;
-}
-
-// Checks `s` and restates its geometry (harness.clamp_translation / clamp_rotate / apply_collimator) as the kernel's arguments. No device work.
-static int alter_args(musica_ctx* c, const char* fn, const musica_alteration* s, AlterDev& a) {
-    if (!s) return fail("%s: spec is NULL", fn);
-    if (!c->d_alter_src) return fail("%s: no source plane (musica_alter_set_source)", fn);
-    if (s->kind >= MUSICA_ALTER_KIND_COUNT) return fail("%s: kind %u out of range", fn, s->kind);
-    const int n = c->N;
-    a = AlterDev{};
-    a.kind = (int)s->kind;
-    a.n = n;
-    a.key0 = (uint32_t)s->seed;
-    a.key1 = (uint32_t)(s->seed >> 32);
-    a.stream = s->stream;
-    switch (s->kind) {
-        case MUSICA_ALTER_TRANSLATE: {
-            const int dx = s->dx, dy = s->dy;
-            if (dx >= n || dx <= -n || dy >= n || dy <= -n) return fail("%s: shift (%d, %d) leaves nothing of a %d-pixel image", fn, dx, dy, n);
-            const int margin = 10;   // clamp_translation's bright = 2, margin = 10
-            a.left = dx > 0 ? margin : 0;
-            a.top = dy > 0 ? margin : 0;
-            const int right = dx < 0 ? n - margin : n, bottom = dy < 0 ? n - margin : n;
-            a.xs = std::max(dx, 0);
-            a.ys = std::max(dy, 0);
-            a.ww = std::min(right - a.left, n - a.xs);
-            a.hh = std::min(bottom - a.top, n - a.ys);
-            break;
-        }
-        case MUSICA_ALTER_ROTATE:
-            if (s->margin < 0 || 2 * (int64_t)s->margin >= n) return fail("%s: margin %d leaves no crop of a %d-pixel image", fn, s->margin, n);
-            if (!finite_all(s->matrix, 4) || !finite_all(s->offset, 2)) return fail("%s: matrix or offset is not finite", fn);
-            a.margin = s->margin;
-            a.crop = n - 2 * s->margin;
-            memcpy(a.m, s->matrix, sizeof(a.m));
-            memcpy(a.off, s->offset, sizeof(a.off));
-            break;
-        case MUSICA_ALTER_COLLIMATOR:
-            if (s->shutter_h < 0 || s->shutter_v < 0 || 2 * (int64_t)s->shutter_h > n || 2 * (int64_t)s->shutter_v > n)
-                return fail("%s: shutters (%d, %d) leave nothing of a %d-pixel image", fn, s->shutter_h, s->shutter_v, n);
-            a.sh = s->shutter_h;
-            a.sv = s->shutter_v;
-            break;
-        case MUSICA_ALTER_GAUSSIAN:
-            if (!std::isfinite(s->mean) || !std::isfinite(s->sigma) || !(s->sigma > 0.0)) return fail("%s: mean %g / sigma %g: need finite values, sigma > 0", fn, s->mean, s->sigma);
-            a.mean = s->mean;
-            a.sigma = s->sigma;
-            break;
-        case MUSICA_ALTER_POISSON:
-            if (!std::isfinite(s->factor) || !(s->factor > 0.0) || 65535.0 * s->factor >= 1073741824.0)
-                return fail("%s: factor %g: need a finite factor > 0 with 65535 * factor < 2^30", fn, s->factor);
-            a.factor = s->factor;
-            break;
-        case MUSICA_ALTER_SYMMETRY:
-            if (s->dx < 0 || s->dx > 7) return fail("%s: element %d is not one of the square's 8 symmetries (0 .. 7)", fn, s->dx);
-            break;
-        default: break;
-    }
-    return 1;
-}
-
-int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
-    if (!c) return fail("musica_alter: ctx is NULL");
-    AlterDev a;
-    if (!alter_args(c, "musica_alter", s, a)) return 0;
-    CHECK_IMG(c, idx);
-    CHECK_CTX(c);
-    if (!alter_scratch(c)) return fail("musica_alter: device allocation failed");
-    const size_t nn = (size_t)c->N * c->N;
-    if (c->cur_input == c->d_input) {   // the last step read d_input: keep it for the getters that recompute from the input
-        if (!c->d_input_kept && !dalloc(c, &c->d_input_kept, (size_t)c->B * nn)) return fail("musica_alter: device allocation failed");
-        HIP_OK(hipMemcpyAsync(c->d_input_kept, c->d_input, (size_t)c->B * nn * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
-        c->cur_input = c->d_input_kept;
-    }
-    const double* fill = nullptr;
-    if (s->kind == MUSICA_ALTER_TRANSLATE) {   // clamp_translation: the 99th percentile of image[top:b_bottom, left:b_right]
-        const int n = c->N, b_right = s->dx > 0 ? 12 : n, b_bottom = s->dy > 0 ? 12 : n;
-        if (!enqueue_percentile(c, a.left, a.top, b_right - a.left, b_bottom - a.top, 99.0)) return 0;
-        fill = c->d_alter_fill;
-    } else if (s->kind == MUSICA_ALTER_ROTATE) {   // clamp_rotate: the 95th percentile of the crop
-        if (!enqueue_percentile(c, a.margin, a.margin, a.crop, a.crop, 95.0)) return 0;
-        fill = c->d_alter_fill;
-    }
-    if (s->kind == MUSICA_ALTER_SYMMETRY) launch_symmetry_u16(c->stream, c->d_alter_src, c->d_input + idx * nn, c->N, s->dx);   // a permutation: kernels_symmetry.hip
-    else launch_alter(c->stream, c->d_alter_src, c->d_input + idx * nn, nullptr, a, fill);
-    HIP_OK(hipGetLastError());
-    return 1;
-}
-
-int musica_alter_draws(musica_ctx* c, const musica_alteration* s, int32_t* dst) {
-    ABI_TRY
-    if (!c) return fail("musica_alter_draws: ctx is NULL");
-    if (!dst) return fail("musica_alter_draws: dst is NULL");
-    AlterDev a;
-    if (!alter_args(c, "musica_alter_draws", s, a)) return 0;
-    if (s->kind != MUSICA_ALTER_COLLIMATOR && s->kind != MUSICA_ALTER_GAUSSIAN && s->kind != MUSICA_ALTER_POISSON)
-        return fail("musica_alter_draws: kind %u draws no noise", s->kind);
-    CHECK_CTX(c);
-    const size_t nn = (size_t)c->N * c->N;
-    if (!c->d_alter_draws && !dalloc(c, &c->d_alter_draws, nn)) return fail("musica_alter_draws: device allocation failed");
-    launch_alter(c->stream, c->d_alter_src, nullptr, c->d_alter_draws, a, nullptr);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(dst, c->d_alter_draws, nn * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
-    ABI_CATCH("musica_alter_draws")
-}
-
-int musica_alter_percentile(musica_ctx* c, uint32_t x, uint32_t y, uint32_t w, uint32_t h, double q, double* out) {
-    if (!c) return fail("musica_alter_percentile: ctx is NULL");
-    if (!out) return fail("musica_alter_percentile: out is NULL");
-    if (!c->d_alter_src) return fail("musica_alter_percentile: no source plane (musica_alter_set_source)");
-    if (w == 0 || h == 0 || (uint64_t)x + w > (uint64_t)c->N || (uint64_t)y + h > (uint64_t)c->N)
-        return fail("musica_alter_percentile: region (%u, %u) + %u x %u is empty or leaves the %d-pixel plane", x, y, w, h, c->N);
-    if (!(q >= 0.0 && q <= 100.0)) return fail("musica_alter_percentile: q %g outside [0, 100]", q);
-    CHECK_CTX(c);
-    if (!alter_scratch(c)) return fail("musica_alter_percentile: device allocation failed");
-    if (!enqueue_percentile(c, (int)x, (int)y, (int)w, (int)h, q)) return 0;
-    HIP_OK(hipMemcpyAsync(out, c->d_alter_fill, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
 }
 
 int musica_get_noise_hist(musica_ctx* c, uint32_t idx, uint32_t level, uint32_t* dst) {

@@ -1,0 +1,552 @@
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the three query calls
+// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip) and the alterations of the input (musica_alter_*;
+// kernels_alteration.hip, kernels_symmetry.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
+#include <math.h>
+#include <string.h>
+
+#include "musica_ctx.h"
+
+extern "C" {
+
+// ---- reference slots (musica_sim_*, include/musica.h) -------------------------------------------------------------------------------
+static size_t sim_side(const musica_ctx* c) { return (size_t)c->N - 2 * MUSICA_OUT_MARGIN; }   // of a slot's plane: the cropped output
+
+// The plane of a slot that `fn` is about to write, allocated on first use, after the two refusals every writer shares.
+static uint8_t* sim_slot_for_write(musica_ctx* c, const char* fn, uint32_t slot) {
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) { fail("%s: image too small for the %d-pixel margin", fn, MUSICA_OUT_MARGIN); return nullptr; }
+    if (hipSetDevice(c->p.device) != hipSuccess) { fail("%s: hipSetDevice failed", fn); return nullptr; }
+    if (!ensure(c, &c->study.slot[slot], sim_side(c) * sim_side(c))) { fail("musica_sim: device allocation of slot %u failed", slot); return nullptr; }
+    return c->study.slot[slot];
+}
+
+// What the calls that make dst_slot from src_slot refuse about the pair. A written source implies a context larger than the margin
+// (only sim_slot_for_write's callers set `written`), so its margin refusal cannot fire behind this one.
+static int sim_check_pair(const musica_ctx* c, const char* fn, uint32_t dst_slot, uint32_t src_slot) {
+    if (dst_slot >= MUSICA_SIM_SLOTS || src_slot >= MUSICA_SIM_SLOTS) return fail("%s: slot %u / %u >= %d", fn, dst_slot, src_slot, MUSICA_SIM_SLOTS);
+    if (dst_slot == src_slot) return fail("%s: dst_slot == src_slot (%u)", fn, dst_slot);
+    if (!c->study.written[src_slot]) return fail("%s: slot %u was never written", fn, src_slot);
+    return 1;
+}
+
+int musica_sim_capture(musica_ctx* c, uint32_t slot, uint32_t idx) {
+    if (!c) return fail("musica_sim_capture: ctx is NULL");
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_capture: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    CHECK_IMG(c, idx);
+    uint8_t* dst = sim_slot_for_write(c, "musica_sim_capture", slot);
+    if (!dst) return 0;
+    launch_out_pixels(c->stream, image_slice(c, c->d_graded, idx), c->lv[0], MUSICA_OUT_MARGIN, dst);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("musica_sim_capture: launch failed: %s", hipGetErrorString(e));
+    c->study.written[slot] = true;
+    return 1;
+}
+
+int musica_sim_set_reference(musica_ctx* c, uint32_t slot, const uint8_t* pixels) {
+    if (!c) return fail("musica_sim_set_reference: ctx is NULL");
+    if (!pixels) return fail("musica_sim_set_reference: pixels is NULL");
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_set_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    uint8_t* dst = sim_slot_for_write(c, "musica_sim_set_reference", slot);
+    if (!dst) return 0;
+    HIP_OK(hipMemcpyAsync(dst, pixels, sim_side(c) * sim_side(c), hipMemcpyHostToDevice, c->stream));   // after what the stream holds (a compare reading the slot)
+    HIP_OK(hipStreamSynchronize(c->stream));                                                             // `pixels` is borrowed for the call
+    c->study.written[slot] = true;
+    return 1;
+}
+
+int musica_sim_set_vendor_reference(musica_ctx* c, uint32_t slot, const void* pixels, uint32_t bits_allocated) {
+    if (!c) return fail("musica_sim_set_vendor_reference: ctx is NULL");
+    if (!pixels) return fail("musica_sim_set_vendor_reference: pixels is NULL");
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_set_vendor_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    if (bits_allocated != 8 && bits_allocated != 16) return fail("musica_sim_set_vendor_reference: bits_allocated %u is neither 8 nor 16", bits_allocated);
+    uint8_t* dst = sim_slot_for_write(c, "musica_sim_set_vendor_reference", slot);
+    if (!dst) return 0;
+    const size_t count = sim_side(c) * sim_side(c);
+    if (!ensure(c, &c->study.d_vendor, count)) return fail("musica_sim_set_vendor_reference: device allocation of the staging plane failed");
+    // after what the stream holds (a compare reading the slot); `pixels` is borrowed for the call
+    HIP_OK(hipMemcpyAsync(c->study.d_vendor, pixels, count * (bits_allocated / 8), hipMemcpyHostToDevice, c->stream));
+    launch_sim_vendor(c->stream, c->study.d_vendor, (int)bits_allocated, dst, (long long)count);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(c->stream));
+    c->study.written[slot] = true;
+    return 1;
+}
+
+int musica_sim_get_reference(musica_ctx* c, uint32_t slot, uint8_t* dst) {
+    if (!c) return fail("musica_sim_get_reference: ctx is NULL");
+    if (!dst) return fail("musica_sim_get_reference: dst is NULL");
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_get_reference: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    if (!c->study.written[slot]) return fail("musica_sim_get_reference: slot %u was never written", slot);
+    CHECK_CTX(c);
+    const size_t nw = sim_side(c);
+    HIP_OK(hipMemcpyAsync(dst, c->study.slot[slot], nw * nw, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+static bool finite_all(const double* v, int n) {
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+int musica_sim_rotate_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const double matrix[4], const double offset[2]) {
+    if (!c) return fail("musica_sim_rotate_reference: ctx is NULL");
+    if (!matrix || !offset) return fail("musica_sim_rotate_reference: matrix or offset is NULL");
+    if (!sim_check_pair(c, "musica_sim_rotate_reference", dst_slot, src_slot)) return 0;
+    if (!finite_all(matrix, 4) || !finite_all(offset, 2)) return fail("musica_sim_rotate_reference: matrix or offset is not finite");
+    uint8_t* dst = sim_slot_for_write(c, "musica_sim_rotate_reference", dst_slot);
+    if (!dst) return 0;
+    AlterDev a{};
+    a.n = (int)sim_side(c);
+    memcpy(a.m, matrix, sizeof(a.m));
+    memcpy(a.off, offset, sizeof(a.off));
+    launch_rotate_u8(c->stream, c->study.slot[src_slot], dst, a);
+    HIP_OK(hipGetLastError());
+    c->study.written[dst_slot] = true;
+    return 1;
+}
+
+int musica_sim_transform_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t element) {
+    if (!c) return fail("musica_sim_transform_reference: ctx is NULL");
+    if (!sim_check_pair(c, "musica_sim_transform_reference", dst_slot, src_slot)) return 0;
+    if (element > 7) return fail("musica_sim_transform_reference: element %u is not one of the square's 8 symmetries (0 .. 7)", element);
+    uint8_t* dst = sim_slot_for_write(c, "musica_sim_transform_reference", dst_slot);
+    if (!dst) return 0;
+    launch_symmetry_u8(c->stream, c->study.slot[src_slot], dst, (int)sim_side(c), (int)element);
+    HIP_OK(hipGetLastError());
+    c->study.written[dst_slot] = true;
+    return 1;
+}
+
+int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]) {
+    if (!c) return fail("musica_sim_remap_reference: ctx is NULL");
+    if (!lut) return fail("musica_sim_remap_reference: lut is NULL");
+    if (!sim_check_pair(c, "musica_sim_remap_reference", dst_slot, src_slot)) return 0;
+    uint8_t* dst = sim_slot_for_write(c, "musica_sim_remap_reference", dst_slot);
+    if (!dst) return 0;
+    RemapLut t;
+    memcpy(t.v, lut, sizeof(t.v));   // travels as a kernel argument: `lut` is free again when the call returns
+    launch_sim_remap(c->stream, c->study.slot[src_slot], dst, t, (long long)(sim_side(c) * sim_side(c)));
+    HIP_OK(hipGetLastError());
+    c->study.written[dst_slot] = true;
+    return 1;
+}
+
+// ---- the query calls (musica_sim_compare / _joint / _displace) ----------------------------------------------------------------------
+// harness.hist_similarity from the exact value counts: np.histogram(v, bins=256) of u8 data spans [lo, hi] = [min, max] and puts v
+// into bin min(255, (v - lo) * 256 // (hi - lo)) — exactly, for every (lo, hi) — and everything into bin 128 when lo == hi
+// (numpy widens the range by +-0.5).
+static void sim_bins(const uint32_t* counts, uint32_t* bins, uint32_t* lo_out, uint32_t* hi_out) {
+    int lo = 0, hi = 255;
+    while (lo < 255 && counts[lo] == 0) lo++;
+    while (hi > 0 && counts[hi] == 0) hi--;
+    memset(bins, 0, 256 * sizeof(uint32_t));
+    for (int v = lo; v <= hi; v++) {
+        if (!counts[v]) continue;
+        const int b = hi == lo ? 128 : std::min(255, (v - lo) * 256 / (hi - lo));
+        bins[b] += counts[v];
+    }
+    *lo_out = (uint32_t)lo;
+    *hi_out = (uint32_t)hi;
+}
+
+static void sim_finish(const uint32_t* counts /* a 256 | b 256 */, const SimPart& r, const musica_sim_query& q, musica_sim_result* o) {
+    const uint64_t n = (uint64_t)q.w * q.h;
+    o->sq_diff_sum = r.ssd;
+    o->pixels = n;
+    sim_bins(counts, o->bins_a, &o->min_a, &o->max_a);
+    sim_bins(counts + 256, o->bins_b, &o->min_b, &o->max_b);
+    o->mse = 1.0 - sqrt((double)r.ssd / (65025.0 * (double)n));                 // 1 - sqrt(mean(((a - b) / 255)^2))
+    o->ssim = r.ssim / ((double)(q.w - 6) * (double)(q.h - 6));                // mean over the interior (borders of 3 cropped)
+    uint64_t inter = 0;
+    double e2 = 0.0, bc = 0.0;
+    for (int i = 0; i < 256; i++) {
+        inter += std::min(o->bins_a[i], o->bins_b[i]);
+        const double na = (double)o->bins_a[i] / (double)n, nb = (double)o->bins_b[i] / (double)n;
+        e2 += (na - nb) * (na - nb);
+        bc += sqrt(na * nb);
+    }
+    o->hist_intersection = (double)inter / (double)n;
+    o->hist_distance = sqrt(e2) / sqrt(2.0);
+    o->hist_bhattacharyya = bc;
+}
+
+// What musica_sim_compare and musica_sim_joint refuse, in the same words (`what`: the entry point), before any device work.
+static int sim_check_queries(musica_ctx* c, const char* what, uint32_t count, const musica_sim_query* qs, const void* out) {
+    if (!c) return fail("%s: ctx is NULL", what);
+    if (!qs || !out) return fail("%s: queries or results is NULL", what);
+    if (count == 0 || count > MUSICA_SIM_MAX_QUERIES) return fail("%s: count %u out of range [1, %d]", what, count, MUSICA_SIM_MAX_QUERIES);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("%s: image too small for the %d-pixel margin", what, MUSICA_OUT_MARGIN);
+    const uint64_t nw = sim_side(c);
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        if (q.slot >= MUSICA_SIM_SLOTS) return fail("%s: query %u: slot %u >= %d", what, i, q.slot, MUSICA_SIM_SLOTS);
+        if (!c->study.written[q.slot]) return fail("%s: query %u: slot %u was never written", what, i, q.slot);
+        if ((int)q.image_index >= c->B) return fail("%s: query %u: image_index %u >= batch %d", what, i, q.image_index, c->B);
+        if (q.w < 7 || q.h < 7) return fail("%s: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", what, i, q.w, q.h);
+        if ((uint64_t)q.ax + q.w > nw || (uint64_t)q.ay + q.h > nw || (uint64_t)q.bx + q.w > nw || (uint64_t)q.by + q.h > nw)
+            return fail("%s: query %u: region (%u, %u) / (%u, %u) + %u x %u leaves the %llu x %llu planes", what, i, q.ax, q.ay, q.bx, q.by,
+                        q.w, q.h, (unsigned long long)nw, (unsigned long long)nw);
+    }
+    return 1;
+}
+
+// Where a query's two regions lie: a in the graded plane of its image (margin included), b in its slot's plane.
+static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion& d) {
+    d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
+    d.b = c->study.slot[q.slot] + (size_t)q.by * sim_side(c) + q.bx;
+    d.a_pitch = c->lv[0].pitch;
+    d.b_pitch = (int)sim_side(c);
+    d.w = (int)q.w;
+    d.h = (int)q.h;
+}
+
+int musica_sim_compare(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_result* out) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_compare", count, qs, out)) return 0;
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_sim_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_sim_part, (size_t)MUSICA_SIM_MAX_QUERIES * kSimMaxBlocks) &&
+          ensure(c, &st.d_sim_out, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_sim_hist, (size_t)MUSICA_SIM_MAX_QUERIES * 512)))
+        return fail("musica_sim_compare: device allocation failed");
+    std::vector<SimQueryDev> hq(count);
+    int max_blocks = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        sim_region(c, qs[i], hq[i]);
+        sim_geometry(hq[i]);
+        max_blocks = std::max(max_blocks, hq[i].strips * hq[i].segs);
+    }
+    SimConsts k;
+    const double k1 = 0.01 * 255, k2 = 0.03 * 255;   // harness.ssim_similarity: c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2 (float ** is C pow)
+    k.c1 = pow(k1, 2.0);
+    k.c2 = pow(k2, 2.0);
+    k.cov_norm = 49.0 / 48.0;                         // npx / (npx - 1)
+    HIP_OK(hipMemcpyAsync(st.d_sim_q, hq.data(), count * sizeof(SimQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_sim_hist, 0, (size_t)count * 512 * sizeof(uint32_t), c->stream));
+    launch_sim(c->stream, st.d_sim_q, (int)count, max_blocks, st.d_sim_part, st.d_sim_hist, st.d_sim_out, k);
+    HIP_OK(hipGetLastError());
+    std::vector<uint32_t> hist((size_t)count * 512);
+    std::vector<SimPart> parts(count);
+    HIP_OK(hipMemcpyAsync(hist.data(), st.d_sim_hist, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(parts.data(), st.d_sim_out, count * sizeof(SimPart), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the results are read by then
+    for (uint32_t i = 0; i < count; i++) sim_finish(hist.data() + (size_t)i * 512, parts[i], qs[i], out + i);
+    return 1;
+    ABI_CATCH("musica_sim_compare")
+}
+
+// musica_sim_joint's numbers from one exact table (include/musica.h states them; harness.tone_similarities restates them): sums in
+// ascending a, then ascending b, zero counts skipped; the variance numerators as exact 128-bit integers, one f64 division per term.
+static void joint_finish(const uint32_t* J, const musica_sim_query& q, musica_sim_joint_result* o) {
+    typedef unsigned __int128 u128;
+    const uint64_t n = (uint64_t)q.w * q.h;
+    const double dn = (double)n;
+    uint64_t A[256] = {}, B[256] = {}, S[256] = {}, Q[256] = {};
+    uint64_t ssd = 0;
+    for (int a = 0; a < 256; a++)
+        for (int b = 0; b < 256; b++) {
+            const uint64_t j = J[a * 256 + b];
+            if (!j) continue;
+            A[a] += j;
+            B[b] += j;
+            S[b] += (uint64_t)a * j;
+            Q[b] += (uint64_t)(a * a) * j;
+            ssd += (uint64_t)((a - b) * (a - b)) * j;
+        }
+    double h_a = 0.0, h_b = 0.0, h_ab = 0.0, mi = 0.0;
+    for (int a = 0; a < 256; a++)
+        if (A[a]) { const double p = (double)A[a] / dn; h_a -= p * log(p); }
+    for (int b = 0; b < 256; b++)
+        if (B[b]) { const double p = (double)B[b] / dn; h_b -= p * log(p); }
+    for (int a = 0; a < 256; a++)
+        for (int b = 0; b < 256; b++) {
+            const uint64_t j = J[a * 256 + b];
+            if (!j) continue;
+            const double p = (double)j / dn;
+            h_ab -= p * log(p);
+            mi += p * log((double)(j * n) / (double)(A[a] * B[b]));   // both products < 2^57
+        }
+    double ssw = 0.0;
+    for (int b = 0; b < 256; b++) {
+        o->tone_lut[b] = (uint8_t)(B[b] ? (2 * S[b] + B[b]) / (2 * B[b]) : (uint64_t)b);
+        if (B[b]) ssw += (double)((u128)B[b] * Q[b] - (u128)S[b] * S[b]) / (double)B[b];   // B Q >= S^2 (Cauchy-Schwarz)
+    }
+    uint64_t sa = 0, saa = 0;
+    for (int a = 0; a < 256; a++) {
+        sa += (uint64_t)a * A[a];
+        saa += (uint64_t)(a * a) * A[a];
+    }
+    const u128 sst_num = (u128)n * saa - (u128)sa * sa;
+    o->mi = mi;
+    o->nmi = h_a + h_b == 0.0 ? 1.0 : 2.0 * mi / (h_a + h_b);
+    o->corr_ratio = sst_num == 0 ? 1.0 : 1.0 - ssw / ((double)sst_num / dn);
+    o->tone_mse = 1.0 - sqrt(ssw / dn) / 255.0;
+    o->h_a = h_a;
+    o->h_b = h_b;
+    o->h_ab = h_ab;
+    o->pixels = n;
+    o->sq_diff_sum = ssd;
+}
+
+int musica_sim_joint(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_joint_result* out, uint32_t* joint) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_joint", count, qs, out)) return 0;
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_joint_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_joint, (size_t)MUSICA_SIM_MAX_QUERIES * 65536)))
+        return fail("musica_sim_joint: device allocation failed");
+    std::vector<JointQueryDev> hq(count);
+    int max_chunks = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        sim_region(c, qs[i], hq[i]);
+        joint_geometry(hq[i], (int)count);
+        max_chunks = std::max(max_chunks, hq[i].chunks);
+    }
+    std::vector<uint32_t> own;
+    if (!joint) {
+        own.resize((size_t)count * 65536);
+        joint = own.data();
+    }
+    HIP_OK(hipMemcpyAsync(st.d_joint_q, hq.data(), count * sizeof(JointQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_joint, 0, (size_t)count * 65536 * sizeof(uint32_t), c->stream));
+    launch_joint(c->stream, st.d_joint_q, (int)count, max_chunks, st.d_joint);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(joint, st.d_joint, (size_t)count * 65536 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        memset(out + i, 0, sizeof(out[i]));
+        joint_finish(joint + (size_t)i * 65536, qs[i], out + i);
+    }
+    return 1;
+    ABI_CATCH("musica_sim_joint")
+}
+
+// The argmin of an S x S displacement table by include/musica.h's tie rule: smallest value, then smallest dx^2 + dy^2, then smallest dy,
+// then smallest dx (harness.displacement_from_table restates it).
+static void displace_finish(const uint64_t* T, int radius, musica_sim_displace_result* o) {
+    const int S = 2 * radius + 1;
+    int by = radius, bx = radius;
+    for (int y = 0; y < S; y++)
+        for (int x = 0; x < S; x++) {
+            const uint64_t v = T[y * S + x], m = T[by * S + bx];
+            const int d2 = (x - radius) * (x - radius) + (y - radius) * (y - radius);
+            const int m2 = (bx - radius) * (bx - radius) + (by - radius) * (by - radius);
+            if (v < m || (v == m && d2 < m2)) {   // equal value and distance: the scan order is ascending dy, then ascending dx
+                by = y;
+                bx = x;
+            }
+        }
+    o->ssd_zero = T[radius * S + radius];
+    o->ssd_min = T[by * S + bx];
+    o->dx = bx - radius;
+    o->dy = by - radius;
+}
+
+int musica_sim_displace(musica_ctx* c, uint32_t count, const musica_sim_query* qs, uint32_t radius, musica_sim_displace_result* out,
+                        uint64_t* tables, uint32_t* tile_tables) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_displace", count, qs, out)) return 0;
+    if (radius < 1 || radius > MUSICA_SIM_MAX_RADIUS) return fail("musica_sim_displace: radius %u out of range [1, %d]", radius, MUSICA_SIM_MAX_RADIUS);
+    const uint64_t nw = sim_side(c);
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        if (q.bx < radius || q.by < radius || (uint64_t)q.bx + q.w + radius > nw || (uint64_t)q.by + q.h + radius > nw)
+            return fail("musica_sim_displace: query %u: the b window (%u, %u) + %u x %u grown by the radius %u leaves the %llu x %llu plane", i, q.bx,
+                        q.by, q.w, q.h, radius, (unsigned long long)nw, (unsigned long long)nw);
+    }
+    const size_t S2 = (size_t)(2 * radius + 1) * (2 * radius + 1);
+    std::vector<DisplaceQueryDev> hq(count);
+    size_t tile_words = 0;
+    int max_tiles = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        DisplaceQueryDev& d = hq[i];
+        sim_region(c, qs[i], d);
+        d.tiles_x = (d.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+        d.tiles_y = (d.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+        d.tile_base = tile_words;
+        tile_words += (size_t)d.tiles_x * d.tiles_y * S2;
+        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+    }
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_disp_q, MUSICA_SIM_MAX_QUERIES) &&
+          ensure(c, &st.d_disp_tables, (size_t)MUSICA_SIM_MAX_QUERIES * (2 * MUSICA_SIM_MAX_RADIUS + 1) * (2 * MUSICA_SIM_MAX_RADIUS + 1)) &&
+          ensure(c, &st.d_disp_off, MUSICA_SIM_MAX_QUERIES)))
+        return fail("musica_sim_displace: device allocation failed");
+    if (tile_words > st.disp_tiles_cap) {   // sized for the call: the largest call so far
+        HIP_OK(drelease(c, &st.d_disp_tiles));
+        st.disp_tiles_cap = 0;
+        if (!dalloc(c, &st.d_disp_tiles, tile_words)) return fail("musica_sim_displace: device allocation of %zu tile-table words failed", tile_words);
+        st.disp_tiles_cap = tile_words;
+    }
+    HIP_OK(hipMemcpyAsync(st.d_disp_q, hq.data(), count * sizeof(DisplaceQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_disp_tables, 0, count * S2 * sizeof(unsigned long long), c->stream));
+    HIP_OK(hipMemsetAsync(st.d_disp_off, 0, count * sizeof(uint32_t), c->stream));
+    launch_displace(c->stream, st.d_disp_q, (int)count, max_tiles, (int)radius, st.d_disp_tiles, st.d_disp_tables, st.d_disp_off);
+    HIP_OK(hipGetLastError());
+    std::vector<uint64_t> own;
+    if (!tables) {
+        own.resize(count * S2);
+        tables = own.data();
+    }
+    std::vector<uint32_t> off(count);
+    HIP_OK(hipMemcpyAsync(tables, st.d_disp_tables, count * S2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(off.data(), st.d_disp_off, count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (tile_tables) HIP_OK(hipMemcpyAsync(tile_tables, st.d_disp_tiles, tile_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        memset(out + i, 0, sizeof(out[i]));
+        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
+        out[i].tiles_x = (uint32_t)hq[i].tiles_x;
+        out[i].tiles_y = (uint32_t)hq[i].tiles_y;
+        out[i].tiles_off = off[i];
+        displace_finish(tables + (size_t)i * S2, (int)radius, out + i);
+    }
+    return 1;
+    ABI_CATCH("musica_sim_displace")
+}
+
+// ---- alterations of the study (musica_alter_*, include/musica.h; kernels_alteration.hip) ----------------------------------------------
+int musica_alter_set_source(musica_ctx* c, const uint16_t* pixels) {
+    if (!c) return fail("musica_alter_set_source: ctx is NULL");
+    if (!pixels) return fail("musica_alter_set_source: pixels is NULL");
+    CHECK_CTX(c);
+    const size_t nn = (size_t)c->N * c->N;
+    if (!ensure(c, &c->study.d_alter_src, nn)) return fail("musica_alter_set_source: device allocation failed");
+    HIP_OK(hipMemcpyAsync(c->study.d_alter_src, pixels, nn * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));   // after alterations that read it
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+static bool alter_scratch(musica_ctx* c) { return ensure(c, &c->study.d_alter_hist, 768) && ensure(c, &c->study.d_alter_fill, 1); }
+
+// The region's percentile into d_alter_fill, on the stream.
+static int enqueue_percentile(musica_ctx* c, int x, int y, int w, int h, double q) {
+    PctRegion g{c->study.d_alter_src, c->N, x, y, w, h, q};
+    HIP_OK(hipMemsetAsync(c->study.d_alter_hist, 0, 768 * sizeof(uint32_t), c->stream));
+    launch_percentile(c->stream, g, c->study.d_alter_hist, c->study.d_alter_fill);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+// Checks `s` and restates its geometry (harness.clamp_translation / clamp_rotate / apply_collimator) as the kernel's arguments. No device work.
+static int alter_args(musica_ctx* c, const char* fn, const musica_alteration* s, AlterDev& a) {
+    if (!s) return fail("%s: spec is NULL", fn);
+    if (!c->study.d_alter_src) return fail("%s: no source plane (musica_alter_set_source)", fn);
+    if (s->kind >= MUSICA_ALTER_KIND_COUNT) return fail("%s: kind %u out of range", fn, s->kind);
+    const int n = c->N;
+    a = AlterDev{};
+    a.kind = (int)s->kind;
+    a.n = n;
+    a.key0 = (uint32_t)s->seed;
+    a.key1 = (uint32_t)(s->seed >> 32);
+    a.stream = s->stream;
+    switch (s->kind) {
+        case MUSICA_ALTER_TRANSLATE: {
+            const int dx = s->dx, dy = s->dy;
+            if (dx >= n || dx <= -n || dy >= n || dy <= -n) return fail("%s: shift (%d, %d) leaves nothing of a %d-pixel image", fn, dx, dy, n);
+            const int margin = 10;   // clamp_translation's bright = 2, margin = 10
+            a.left = dx > 0 ? margin : 0;
+            a.top = dy > 0 ? margin : 0;
+            const int right = dx < 0 ? n - margin : n, bottom = dy < 0 ? n - margin : n;
+            a.xs = std::max(dx, 0);
+            a.ys = std::max(dy, 0);
+            a.ww = std::min(right - a.left, n - a.xs);
+            a.hh = std::min(bottom - a.top, n - a.ys);
+            break;
+        }
+        case MUSICA_ALTER_ROTATE:
+            if (s->margin < 0 || 2 * (int64_t)s->margin >= n) return fail("%s: margin %d leaves no crop of a %d-pixel image", fn, s->margin, n);
+            if (!finite_all(s->matrix, 4) || !finite_all(s->offset, 2)) return fail("%s: matrix or offset is not finite", fn);
+            a.margin = s->margin;
+            a.crop = n - 2 * s->margin;
+            memcpy(a.m, s->matrix, sizeof(a.m));
+            memcpy(a.off, s->offset, sizeof(a.off));
+            break;
+        case MUSICA_ALTER_COLLIMATOR:
+            if (s->shutter_h < 0 || s->shutter_v < 0 || 2 * (int64_t)s->shutter_h > n || 2 * (int64_t)s->shutter_v > n)
+                return fail("%s: shutters (%d, %d) leave nothing of a %d-pixel image", fn, s->shutter_h, s->shutter_v, n);
+            a.sh = s->shutter_h;
+            a.sv = s->shutter_v;
+            break;
+        case MUSICA_ALTER_GAUSSIAN:
+            if (!std::isfinite(s->mean) || !std::isfinite(s->sigma) || !(s->sigma > 0.0)) return fail("%s: mean %g / sigma %g: need finite values, sigma > 0", fn, s->mean, s->sigma);
+            a.mean = s->mean;
+            a.sigma = s->sigma;
+            break;
+        case MUSICA_ALTER_POISSON:
+            if (!std::isfinite(s->factor) || !(s->factor > 0.0) || 65535.0 * s->factor >= 1073741824.0)
+                return fail("%s: factor %g: need a finite factor > 0 with 65535 * factor < 2^30", fn, s->factor);
+            a.factor = s->factor;
+            break;
+        case MUSICA_ALTER_SYMMETRY:
+            if (s->dx < 0 || s->dx > 7) return fail("%s: element %d is not one of the square's 8 symmetries (0 .. 7)", fn, s->dx);
+            break;
+        default: break;
+    }
+    return 1;
+}
+
+int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
+    if (!c) return fail("musica_alter: ctx is NULL");
+    AlterDev a;
+    if (!alter_args(c, "musica_alter", s, a)) return 0;
+    CHECK_IMG(c, idx);
+    CHECK_CTX(c);
+    if (!alter_scratch(c)) return fail("musica_alter: device allocation failed");
+    const size_t nn = (size_t)c->N * c->N;
+    if (c->cur_input == c->d_input) {   // the last step read d_input: keep it for the getters that recompute from the input
+        if (!ensure(c, &c->d_input_kept, (size_t)c->B * nn)) return fail("musica_alter: device allocation failed");
+        HIP_OK(hipMemcpyAsync(c->d_input_kept, c->d_input, (size_t)c->B * nn * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
+        c->cur_input = c->d_input_kept;
+    }
+    const double* fill = nullptr;
+    if (s->kind == MUSICA_ALTER_TRANSLATE) {   // clamp_translation: the 99th percentile of image[top:b_bottom, left:b_right]
+        const int n = c->N, b_right = s->dx > 0 ? 12 : n, b_bottom = s->dy > 0 ? 12 : n;
+        if (!enqueue_percentile(c, a.left, a.top, b_right - a.left, b_bottom - a.top, 99.0)) return 0;
+        fill = c->study.d_alter_fill;
+    } else if (s->kind == MUSICA_ALTER_ROTATE) {   // clamp_rotate: the 95th percentile of the crop
+        if (!enqueue_percentile(c, a.margin, a.margin, a.crop, a.crop, 95.0)) return 0;
+        fill = c->study.d_alter_fill;
+    }
+    if (s->kind == MUSICA_ALTER_SYMMETRY) launch_symmetry_u16(c->stream, c->study.d_alter_src, c->d_input + idx * nn, c->N, s->dx);   // a permutation: kernels_symmetry.hip
+    else launch_alter(c->stream, c->study.d_alter_src, c->d_input + idx * nn, nullptr, a, fill);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+int musica_alter_draws(musica_ctx* c, const musica_alteration* s, int32_t* dst) {
+    ABI_TRY
+    if (!c) return fail("musica_alter_draws: ctx is NULL");
+    if (!dst) return fail("musica_alter_draws: dst is NULL");
+    AlterDev a;
+    if (!alter_args(c, "musica_alter_draws", s, a)) return 0;
+    if (s->kind != MUSICA_ALTER_COLLIMATOR && s->kind != MUSICA_ALTER_GAUSSIAN && s->kind != MUSICA_ALTER_POISSON)
+        return fail("musica_alter_draws: kind %u draws no noise", s->kind);
+    CHECK_CTX(c);
+    const size_t nn = (size_t)c->N * c->N;
+    if (!ensure(c, &c->study.d_alter_draws, nn)) return fail("musica_alter_draws: device allocation failed");
+    launch_alter(c->stream, c->study.d_alter_src, nullptr, c->study.d_alter_draws, a, nullptr);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(dst, c->study.d_alter_draws, nn * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+    ABI_CATCH("musica_alter_draws")
+}
+
+int musica_alter_percentile(musica_ctx* c, uint32_t x, uint32_t y, uint32_t w, uint32_t h, double q, double* out) {
+    if (!c) return fail("musica_alter_percentile: ctx is NULL");
+    if (!out) return fail("musica_alter_percentile: out is NULL");
+    if (!c->study.d_alter_src) return fail("musica_alter_percentile: no source plane (musica_alter_set_source)");
+    if (w == 0 || h == 0 || (uint64_t)x + w > (uint64_t)c->N || (uint64_t)y + h > (uint64_t)c->N)
+        return fail("musica_alter_percentile: region (%u, %u) + %u x %u is empty or leaves the %d-pixel plane", x, y, w, h, c->N);
+    if (!(q >= 0.0 && q <= 100.0)) return fail("musica_alter_percentile: q %g outside [0, 100]", q);
+    CHECK_CTX(c);
+    if (!alter_scratch(c)) return fail("musica_alter_percentile: device allocation failed");
+    if (!enqueue_percentile(c, (int)x, (int)y, (int)w, (int)h, q)) return 0;
+    HIP_OK(hipMemcpyAsync(out, c->study.d_alter_fill, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@ exactly like `run_process` (:200-214), and exposes the relations as data so test
 phantoms (the reference's raw_images/ are missing blobs).
 """
 import csv
+import itertools
 import math
 import os
 import subprocess
@@ -689,37 +690,28 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     if alter_on_device:
         runner.proc.alter_set_source(raw)
         seed = int(rng.integers(0, 2 ** 63))
-        ordinal = [0]
 
-        def dev(make):
-            """An alteration as a no-argument call: make(seed, stream) enqueues it on the device, with the study ordinal as stream."""
-            ordinal[0] += 1
-            k = ordinal[0]
-            return lambda: make(seed, k)
-
-    def add(name, altered_raw, reg=None, roi=None, plane=None):
-        """altered_raw: the altered image, or (device alterations) a call that writes it into the resident input buffer.
-        reg: the host crop; roi: () -> (region, slot) of the same comparison on the device (region None: no registration); plane:
-        () -> (region, the full host plane the region's b side lies in), what the host's displacement restatement needs."""
+    def add(name, host, dev, reg=None, region=None, slot=None, plane=None):
+        """One row of study() below, scored the way the runner's mode asks for."""
         row = {"alteration": name, "registered": None, "registered_reference": None, "registered_tone": None, "registered_reference_tone": None,
                "registered_shift": None}
-        if callable(altered_raw):
-            altered_raw()
+        if alter_on_device:
+            dev()
             runner.run_resident()
         elif device:
-            runner.run_device(altered_raw)
+            runner.run_device(host())
         if device:
             queries = [(0, SLOT_UNALTERED) + full]
             if vendor is not None:
                 queries.append((0, SLOT_VENDOR) + full)
             registered = None   # (slot, region) of the registered comparison
-            if roi is not None:
-                region, slot = roi()
-                if region is not None and min(region[4], region[5]) >= 8:
-                    registered = (slot, region)
-                    queries.append((0, slot) + region)
+            if region is not None:
+                sl, r = slot(), region()
+                if r is not None and min(r[4], r[5]) >= 8:
+                    registered = (sl, r)
+                    queries.append((0, sl) + r)
                     if vendor is not None:
-                        queries.append((0, VENDOR_SLOT[slot]) + region)
+                        queries.append((0, VENDOR_SLOT[sl]) + r)
             for suffix, score in (("", on_device),) + ((("_tone", tone_on_device),) if tone else ()):
                 res = score(queries)
                 row["direct" + suffix] = res.pop(0)
@@ -734,7 +726,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
                     [(SLOT_UNALTERED, _inset(full, displacement)),
                      (registered[0], _inset(registered[1], displacement)) if registered else (None, None)])
         else:
-            alt = runner.run(altered_raw)
+            alt = runner.run(host())
             crop = reg(alt, unalt) if reg is not None else None
             if crop is not None and not (crop[0].size and crop[0].shape == crop[1].shape and min(crop[0].shape) >= 8):
                 crop = None
@@ -750,70 +742,50 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             if displacement:
                 row["direct_shift"] = shift_on_host(alt, unalt, _inset(full, displacement))
                 if crop is not None:
-                    region, b_plane = plane()
-                    row["registered_shift"] = shift_on_host(alt, b_plane, _inset(region, displacement))
+                    row["registered_shift"] = shift_on_host(alt, plane(), _inset(region(), displacement))
         row["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         rows.append({k: row[k] for k in keys})
 
-    def rotated_slot(d):
+    def moved_slot(d, move_reference, moved_unalt):
+        """The unaltered result (and the vendor image) moved as the row moves its input, into SLOT_ROTATED (SLOT_VENDOR_ROTATED)."""
         if alter_on_device:
-            runner.proc.sim_rotate_reference(SLOT_ROTATED, SLOT_UNALTERED, d)
+            move_reference(SLOT_ROTATED, SLOT_UNALTERED, d)
         else:
-            runner.proc.sim_set_reference(SLOT_ROTATED, rotated_reference(unalt, d))
+            runner.proc.sim_set_reference(SLOT_ROTATED, moved_unalt(unalt, d))
         if vendor is not None:
-            runner.proc.sim_rotate_reference(SLOT_VENDOR_ROTATED, SLOT_VENDOR, d)
-        return roi_rotation(shape, d), SLOT_ROTATED
+            move_reference(SLOT_VENDOR_ROTATED, SLOT_VENDOR, d)
+        return SLOT_ROTATED
 
-    def symmetry_slot(e):
-        if alter_on_device:
-            runner.proc.sim_transform_reference(SLOT_ROTATED, SLOT_UNALTERED, e)
-        else:
-            runner.proc.sim_set_reference(SLOT_ROTATED, apply_symmetry(unalt, e))
-        if vendor is not None:
-            runner.proc.sim_transform_reference(SLOT_VENDOR_ROTATED, SLOT_VENDOR, e)
-        return roi_symmetry(shape), SLOT_ROTATED
-
-    def add_symmetries(make):
-        """The d4_<e> rows; make(e): the altered raw image, or (device alterations) the call that writes it."""
-        for e in symmetries:
-            add("d4_%d" % e, make(e), lambda a, u, e=e: register_symmetry(a, u, e), lambda e=e: symmetry_slot(e),
-                lambda e=e: (roi_symmetry(shape), apply_symmetry(unalt, e)))
-
-    if alter_on_device:
-        p = runner.proc
+    def study():
+        """Every alteration of the study once, in the rows' order, as add()'s arguments: name; host() the altered raw image; dev() the
+        call that writes it into the resident input buffer; reg(alt, unalt) the host's registration crop; region() the region of the
+        same comparison (None: no registration); slot() the reference slot its b side lies in on the device, filled by that call where
+        it is not the unaltered result's; plane() the full host plane it lies in. The noise rows have only the first three. add() makes a
+        row's calls before the next row is built: the rows' order is the order of the `rng` draws. The device's noise draws take the
+        row's ordinal in the study as their stream; the d4 rows draw nothing and take no ordinal."""
+        p, ordinal = runner.proc, itertools.count(1)
         for s in shutters:
-            add("c_sh_%d" % s, dev(lambda seed, k, s=s: p.alter_collimator(s, s, seed, k)), None,
-                lambda s=s: (roi_collimator(shape, s), SLOT_UNALTERED))
-        for t in translations:
-            add("t_x_%d" % t, dev(lambda seed, k, t=t: p.alter_translate(t, 0)), None, lambda t=t: (roi_translation_x(shape, t), SLOT_UNALTERED))
-        for t in translations:
-            add("t_y_%d" % t, dev(lambda seed, k, t=t: p.alter_translate(0, t)), None, lambda t=t: (roi_translation_y(shape, t), SLOT_UNALTERED))
+            yield ("c_sh_%d" % s, lambda: apply_collimator(raw, s, s, rng), lambda k=next(ordinal): p.alter_collimator(s, s, seed, k),
+                   lambda a, u: register_collimator(a, u, s), lambda: roi_collimator(shape, s), lambda: SLOT_UNALTERED, lambda: unalt)
+        for name, tx, ty, register, roi in (("t_x_%d", 1, 0, register_translation_x, roi_translation_x), ("t_y_%d", 0, 1, register_translation_y, roi_translation_y)):
+            for t in translations:
+                next(ordinal)   # every row before the d4 rows takes one, drawing or not
+                yield (name % t, lambda: clamp_translation(raw, tx * t, ty * t), lambda: p.alter_translate(tx * t, ty * t),
+                       lambda a, u: register(a, u, t), lambda: roi(shape, t), lambda: SLOT_UNALTERED, lambda: unalt)
         for d in rotations:
-            add("r_%d" % d, dev(lambda seed, k, d=d: p.alter_rotate(d)), None, lambda d=d: rotated_slot(d))
+            next(ordinal)
+            yield ("r_%d" % d, lambda: clamp_rotate(raw, d), lambda: p.alter_rotate(d), lambda a, u: register_rotation(a, u, d),
+                   lambda: roi_rotation(shape, d), lambda: moved_slot(d, p.sim_rotate_reference, rotated_reference), lambda: rotated_reference(unalt, d))
         for sg in sigmas:
-            add("gn_%s" % sg, dev(lambda seed, k, sg=sg: p.alter_gaussian(0.0, sg, seed, k)))
+            yield ("gn_%s" % sg, lambda: add_gaussian_noise(raw, 0.0, sg, rng), lambda k=next(ordinal): p.alter_gaussian(0.0, sg, seed, k))
         for f in factors:
-            add("pn_%s" % f, dev(lambda seed, k, f=f: p.alter_poisson(f, seed, k)))
-        add_symmetries(lambda e: (lambda: p.alter_symmetry(e)))   # not through dev(): no draws, no ordinal
-        return rows
+            yield ("pn_%s" % f, lambda: apply_quantum_noise(raw, f, rng), lambda k=next(ordinal): p.alter_poisson(f, seed, k))
+        for e in symmetries:
+            yield ("d4_%d" % e, lambda: apply_symmetry(raw, e), lambda: p.alter_symmetry(e), lambda a, u: register_symmetry(a, u, e),
+                   lambda: roi_symmetry(shape), lambda: moved_slot(e, p.sim_transform_reference, apply_symmetry), lambda: apply_symmetry(unalt, e))
 
-    for s in shutters:
-        add("c_sh_%d" % s, apply_collimator(raw, s, s, rng), lambda a, u, s=s: register_collimator(a, u, s),
-            lambda s=s: (roi_collimator(shape, s), SLOT_UNALTERED), lambda s=s: (roi_collimator(shape, s), unalt))
-    for t in translations:
-        add("t_x_%d" % t, clamp_translation(raw, t, 0), lambda a, u, t=t: register_translation_x(a, u, t),
-            lambda t=t: (roi_translation_x(shape, t), SLOT_UNALTERED), lambda t=t: (roi_translation_x(shape, t), unalt))
-    for t in translations:
-        add("t_y_%d" % t, clamp_translation(raw, 0, t), lambda a, u, t=t: register_translation_y(a, u, t),
-            lambda t=t: (roi_translation_y(shape, t), SLOT_UNALTERED), lambda t=t: (roi_translation_y(shape, t), unalt))
-    for d in rotations:
-        add("r_%d" % d, clamp_rotate(raw, d), lambda a, u, d=d: register_rotation(a, u, d), lambda d=d: rotated_slot(d),
-            lambda d=d: (roi_rotation(shape, d), rotated_reference(unalt, d)))
-    for sg in sigmas:
-        add("gn_%s" % sg, add_gaussian_noise(raw, 0.0, sg, rng))
-    for f in factors:
-        add("pn_%s" % f, apply_quantum_noise(raw, f, rng))
-    add_symmetries(lambda e: apply_symmetry(raw, e))
+    for row in study():
+        add(*row)
     return rows
 
 
