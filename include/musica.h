@@ -436,6 +436,39 @@ typedef struct musica_sim_displace_result {
  * device buffers are allocated on first use and sized for the call. */
 int musica_sim_displace(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, uint32_t radius,
                         musica_sim_displace_result* results, uint64_t* tables, uint32_t* tile_tables);
+/* At which spatial scale the output changed: multi-scale SSIM of a comparison (Wang, Simoncelli, Bovik 2003) with the 7 x 7 uniform
+ * window of musica_sim_compare, in exact integers (harness.multiscale_similarities). Side a is the 8-bit output of batch image
+ * image_index (quantised while it is read, as musica_sim_compare reads it), side b the plane of reference slot `slot`. For
+ * s = 0 .. scales - 1, X_s[i][j] is the SUM of the 2^s x 2^s block of the a region whose top-left pixel is (i 2^s, j 2^s) of the region,
+ * Y_s the same of b: planes of (h >> s) x (w >> s) integers <= 255 * 4^s, rows and columns that do not fill a block dropped (iterated
+ * 2 x 2 mean pooling, times 4^s). Over all (h_s - 6)(w_s - 6) windows of 7 x 7 texels the sums Sx, Sy, Sxx, Syy, Sxy of X_s, Y_s,
+ * X_s^2, Y_s^2, X_s Y_s are exact integers; ux = Sx / (49 * 4^s), uxx = Sxx / (49 * 16^s) (likewise uy, uyy, uxy: one f64 division by
+ * an exact double each), vx = (49 / 48)(uxx - ux ux), vy, vxy likewise, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, and per window
+ *   lum = (2 ux uy + C1) / (ux ux + uy uy + C1),  cs = (2 vxy + C2) / (vx + vy + C2),
+ *   ssim = ((2 ux uy + C1)(2 vxy + C2)) / ((ux ux + uy uy + C1)(vx + vy + C2))     (scale 0: musica_sim_compare's per-pixel value).
+ * ssim[s], cs[s], lum[s] are their means over the windows (only the order of that last f64 summation is the device's own: fixed, the
+ * same from call to call); ssd[s] = sum (X_s - Y_s)^2 over plane s, exact (ssd[0] == musica_sim_compare's sq_diff_sum);
+ * mse[s] = 1 - sqrt(ssd[s] / (h_s w_s)) / (255 * 4^s). With W = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) and w_s = W[s] / (W[0] + ..
+ * + W[scales - 1]):  ms_ssim = prod over s < scales - 1 of max(cs[s], 0)^w_s, times max(ssim[scales - 1], 0)^w_(scales - 1), C pow, in
+ * ascending s. Identical sides give exactly 1 everywhere. */
+#define MUSICA_SIM_MAX_SCALES 5
+typedef struct musica_sim_scales_result {
+    uint32_t scales;                 /* as asked */
+    uint64_t pixels;                 /* w * h */
+    double   ms_ssim;
+    double   ssim[5], cs[5], lum[5], mse[5];
+    uint64_t ssd[5];                 /* exact */
+    uint32_t plane_w[5], plane_h[5]; /* w >> s, h >> s */
+} musica_sim_scales_result;
+/* `count` (1 .. MUSICA_SIM_MAX_QUERIES) comparisons at `scales` (1 .. MUSICA_SIM_MAX_SCALES) scales each; synchronous, on the context's
+ * stream after whatever was enqueued there. The full-resolution planes are read once, by a pooling launch that writes the planes of
+ * every scale into context-owned scratch (allocated on first use, sized for the call); one windowed launch covers all queries and
+ * scales, a fold launch sums its partials in a fixed order. Array entries at s >= scales are zero. The refusals of musica_sim_compare,
+ * so one query array serves both calls: refused (0, musica_last_error) before any device work: NULL pointers, a count out of range, a
+ * slot out of range or never written, image_index >= batch, a region that leaves either plane, w < 7 or h < 7; and scales outside
+ * 1 .. MUSICA_SIM_MAX_SCALES, a region with min(w, h) >> (scales - 1) < 7. Changes no slot, no result of the step and no input image. */
+int musica_sim_multiscale(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, uint32_t scales,
+                          musica_sim_scales_result* results);
 /* dst[i] = lut[src[i]] over the (N - 20)^2 plane of reference slot `src_slot` into `dst_slot` (device to device, on the ctx stream);
  * with a musica_sim_joint_result's tone_lut: the slot tone-matched to the image it was compared with. Refused before any device work: a
  * NULL context or table, a slot out of range, dst_slot == src_slot, a source slot never written, an image too small for the margin.

@@ -193,6 +193,42 @@ constexpr int kDisplaceMaxRadius = 16;   // MUSICA_SIM_MAX_RADIUS
 // tile tables (all written); tables: count x S^2 u64 and tiles_off: count u32, both zeroed by the caller.
 void launch_displace(hipStream_t st, const DisplaceQueryDev* d_qs, int count, int max_tiles, int radius, uint32_t* tile_tables,
                      unsigned long long* tables, uint32_t* tiles_off);
+// kernels_scales.hip: musica_sim_multiscale. One query of the pooling pass: its 64 x 16 tiles anchored at the region's origin, where its
+// planes start in the call's scratch (bytes, 16-byte aligned: scale 0 as x | y << 8 in u16, scales >= 1 as x | y << 16 in u32, plane s
+// dense (h >> s) x (w >> s)) and where its tiles' partials start.
+constexpr int kScaleMaxScales = 5;    // MUSICA_SIM_MAX_SCALES
+constexpr int kScalePoolW = 64, kScalePoolH = 16;
+constexpr int kScaleMaxBlocks = 512;  // workgroups per job of the windowed launch (partials slots)
+struct ScalePoolDev : SimRegion {
+    int scales, tiles_x, tiles_y;
+    unsigned long long plane_off[kScaleMaxScales];
+    unsigned long long part_base;     // ScalePoolPart elements
+};
+struct ScalePoolPart {
+    unsigned long long ssd[kScaleMaxScales];   // sum of (X_s - Y_s)^2 over the tile's cells of plane s
+};
+// One (query, scale) of the windowed launch: the plane (w x h texels at plane_off) and the launch geometry (scales_geometry).
+struct ScaleJobDev {
+    unsigned long long plane_off;
+    int w, h, scale, query;
+    int strips, segs, seg_rows;
+};
+struct ScaleWinPart {
+    double ssim, cs, lum;             // sums over the windows the workgroup computes
+};
+struct ScaleOut {
+    double ssim, cs, lum;             // sums over the job's windows
+    unsigned long long ssd;           // the query's exact sum of (X_s - Y_s)^2 at the job's scale
+};
+struct ScaleConsts {
+    double c1, c2, cov_norm;                               // as SimConsts
+    double div1[kScaleMaxScales], div2[kScaleMaxScales];   // 49 * 4^s, 49 * 16^s
+};
+void scales_geometry(ScaleJobDev& q);
+// k_scales_pool over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y), k_scales_win over `jobs` jobs (grid.x =
+// max_blocks, the largest strips * segs), then k_scales_fold: out[j] of job j. pool: the tiles' partials; part: jobs x kScaleMaxBlocks.
+void launch_scales(hipStream_t st, const ScalePoolDev* d_qs, int count, int max_tiles, const ScaleJobDev* d_jobs, int jobs, int max_blocks,
+                   uint8_t* scratch, ScalePoolPart* pool, ScaleWinPart* part, ScaleOut* out, const ScaleConsts& k);
 // kernels_alteration.hip: one alteration of musica_alter (or the draws of musica_alter_draws) over an n x n plane.
 struct AlterDev {
     int kind;                  // MUSICA_ALTER_*

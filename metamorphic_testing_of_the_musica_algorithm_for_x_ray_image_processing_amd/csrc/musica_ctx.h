@@ -93,6 +93,15 @@ struct StudyState {
     uint32_t* d_disp_off = nullptr;                // [MUSICA_SIM_MAX_QUERIES]: tiles_off
     uint32_t* d_disp_tiles = nullptr;              // the tile tables of one call: disp_tiles_cap u32, regrown when a call needs more
     size_t disp_tiles_cap = 0;
+    // musica_sim_multiscale
+    ScalePoolDev* d_scale_q = nullptr;             // [MUSICA_SIM_MAX_QUERIES]
+    ScaleJobDev* d_scale_jobs = nullptr;           // [MUSICA_SIM_MAX_QUERIES * MUSICA_SIM_MAX_SCALES]
+    ScaleWinPart* d_scale_part = nullptr;          // [jobs][kScaleMaxBlocks]
+    ScaleOut* d_scale_out = nullptr;               // [jobs]
+    uint8_t* d_scale_planes = nullptr;             // the pooled planes of one call: scale_planes_cap bytes, regrown when a call needs more
+    size_t scale_planes_cap = 0;
+    ScalePoolPart* d_scale_pool = nullptr;         // the tiles' partials of one call: scale_pool_cap elements, likewise
+    size_t scale_pool_cap = 0;
     // musica_alter_*: the source plane (N x N u16), the radix-select counts and the fill
     uint16_t* d_alter_src = nullptr;
     uint32_t* d_alter_hist = nullptr;    // [768]

@@ -1,10 +1,22 @@
-// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the three query calls
-// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip) and the alterations of the input (musica_alter_*;
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the four query calls
+// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip) and the alterations of the input (musica_alter_*;
 // kernels_alteration.hip, kernels_symmetry.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
 #include "musica_ctx.h"
+
+// musica_sim_multiscale: a device buffer of one call, regrown when a call needs more than the largest call so far (as
+// musica_sim_displace's tile tables). A template, so it stands outside the extern "C" block.
+template <typename T>
+static int scales_grow(musica_ctx* c, T** buf, size_t* cap, size_t want) {
+    if (want <= *cap) return 1;
+    HIP_OK(drelease(c, buf));
+    *cap = 0;
+    if (!dalloc(c, buf, want)) return fail("musica_sim_multiscale: device allocation of %zu bytes failed", want * sizeof(T));
+    *cap = want;
+    return 1;
+}
 
 extern "C" {
 
@@ -132,7 +144,7 @@ int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_sl
     return 1;
 }
 
-// ---- the query calls (musica_sim_compare / _joint / _displace) ----------------------------------------------------------------------
+// ---- the query calls (musica_sim_compare / _joint / _displace / _multiscale) ----------------------------------------------------------------------
 // harness.hist_similarity from the exact value counts: np.histogram(v, bins=256) of u8 data spans [lo, hi] = [min, max] and puts v
 // into bin min(255, (v - lo) * 256 // (hi - lo)) — exactly, for every (lo, hi) — and everything into bin 128 when lo == hi
 // (numpy widens the range by +-0.5).
@@ -404,6 +416,93 @@ int musica_sim_displace(musica_ctx* c, uint32_t count, const musica_sim_query* q
     }
     return 1;
     ABI_CATCH("musica_sim_displace")
+}
+
+// musica_sim_multiscale's numbers of one query from the folded sums (include/musica.h states them; harness.multiscale_similarities
+// restates them): the means, mse per scale, and the product of powers in ascending s with C pow.
+static void scales_finish(const ScaleOut* r, const musica_sim_query& q, uint32_t scales, musica_sim_scales_result* o) {
+    static const double W[MUSICA_SIM_MAX_SCALES] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};   // Wang, Simoncelli, Bovik 2003
+    memset(o, 0, sizeof(*o));
+    o->scales = scales;
+    o->pixels = (uint64_t)q.w * q.h;
+    double wsum = 0.0;
+    for (uint32_t s = 0; s < scales; s++) wsum += W[s];
+    double ms = 1.0;
+    for (uint32_t s = 0; s < scales; s++) {
+        const uint64_t ws = q.w >> s, hs = q.h >> s;
+        const double windows = (double)((ws - 6) * (hs - 6));
+        o->plane_w[s] = (uint32_t)ws;
+        o->plane_h[s] = (uint32_t)hs;
+        o->ssim[s] = r[s].ssim / windows;
+        o->cs[s] = r[s].cs / windows;
+        o->lum[s] = r[s].lum / windows;
+        o->ssd[s] = r[s].ssd;
+        o->mse[s] = 1.0 - sqrt((double)r[s].ssd / (double)(hs * ws)) / (double)(255ull << (2 * s));
+        ms *= pow(std::max(s + 1 < scales ? o->cs[s] : o->ssim[s], 0.0), W[s] / wsum);
+    }
+    o->ms_ssim = ms;
+}
+
+int musica_sim_multiscale(musica_ctx* c, uint32_t count, const musica_sim_query* qs, uint32_t scales, musica_sim_scales_result* out) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_multiscale", count, qs, out)) return 0;
+    if (scales < 1 || scales > MUSICA_SIM_MAX_SCALES) return fail("musica_sim_multiscale: scales %u out of range [1, %d]", scales, MUSICA_SIM_MAX_SCALES);
+    for (uint32_t i = 0; i < count; i++)
+        if ((std::min(qs[i].w, qs[i].h) >> (scales - 1)) < 7)
+            return fail("musica_sim_multiscale: query %u: region %u x %u is smaller than the 7 x 7 window at scale %u", i, qs[i].w, qs[i].h, scales - 1);
+    std::vector<ScalePoolDev> hq(count);
+    std::vector<ScaleJobDev> jobs((size_t)count * scales);
+    size_t bytes = 0, tiles = 0;
+    int max_tiles = 1, max_blocks = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        ScalePoolDev& d = hq[i];
+        sim_region(c, qs[i], d);
+        d.scales = (int)scales;
+        d.tiles_x = (d.w + kScalePoolW - 1) / kScalePoolW;
+        d.tiles_y = (d.h + kScalePoolH - 1) / kScalePoolH;
+        d.part_base = tiles;
+        tiles += (size_t)d.tiles_x * d.tiles_y;
+        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+        for (uint32_t s = 0; s < MUSICA_SIM_MAX_SCALES; s++) d.plane_off[s] = 0;
+        for (uint32_t s = 0; s < scales; s++) {
+            ScaleJobDev& j = jobs[(size_t)i * scales + s];
+            j.plane_off = d.plane_off[s] = bytes;
+            j.w = d.w >> s;
+            j.h = d.h >> s;
+            j.scale = (int)s;
+            j.query = (int)i;
+            scales_geometry(j);
+            max_blocks = std::max(max_blocks, j.strips * j.segs);
+            bytes += ((size_t)j.w * j.h * (s == 0 ? 2 : 4) + 15) & ~(size_t)15;
+        }
+    }
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    const size_t max_jobs = (size_t)MUSICA_SIM_MAX_QUERIES * MUSICA_SIM_MAX_SCALES;
+    if (!(ensure(c, &st.d_scale_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_scale_jobs, max_jobs) &&
+          ensure(c, &st.d_scale_part, max_jobs * kScaleMaxBlocks) && ensure(c, &st.d_scale_out, max_jobs)))
+        return fail("musica_sim_multiscale: device allocation failed");
+    if (!scales_grow(c, &st.d_scale_planes, &st.scale_planes_cap, bytes) || !scales_grow(c, &st.d_scale_pool, &st.scale_pool_cap, tiles)) return 0;
+    ScaleConsts k;
+    const double k1 = 0.01 * 255, k2 = 0.03 * 255;   // as musica_sim_compare
+    k.c1 = pow(k1, 2.0);
+    k.c2 = pow(k2, 2.0);
+    k.cov_norm = 49.0 / 48.0;
+    for (int s = 0; s < MUSICA_SIM_MAX_SCALES; s++) {
+        k.div1[s] = (double)(49ull << (2 * s));   // 49 * 4^s and 49 * 16^s: exact doubles
+        k.div2[s] = (double)(49ull << (4 * s));
+    }
+    HIP_OK(hipMemcpyAsync(st.d_scale_q, hq.data(), count * sizeof(ScalePoolDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(st.d_scale_jobs, jobs.data(), jobs.size() * sizeof(ScaleJobDev), hipMemcpyHostToDevice, c->stream));
+    launch_scales(c->stream, st.d_scale_q, (int)count, max_tiles, st.d_scale_jobs, (int)jobs.size(), max_blocks, st.d_scale_planes, st.d_scale_pool,
+                  st.d_scale_part, st.d_scale_out, k);
+    HIP_OK(hipGetLastError());
+    std::vector<ScaleOut> res(jobs.size());
+    HIP_OK(hipMemcpyAsync(res.data(), st.d_scale_out, res.size() * sizeof(ScaleOut), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq, jobs and the results are read by then
+    for (uint32_t i = 0; i < count; i++) scales_finish(res.data() + (size_t)i * scales, qs[i], scales, out + i);
+    return 1;
+    ABI_CATCH("musica_sim_multiscale")
 }
 
 // ---- alterations of the study (musica_alter_*, include/musica.h; kernels_alteration.hip) ----------------------------------------------

@@ -356,6 +356,101 @@ def _inset(region, r):
     return (ax + r, ay + r, bx + r, by + r, w - 2 * r, h - 2 * r) if min(w, h) - 2 * r >= 7 else None
 
 
+# ---- at which scale the output changed: multi-scale SSIM in exact integers (musica_sim_multiscale; not in the reference) ----
+# MUSICA is a Laplacian pyramid and each of its stages works at scales of its own (per-level contrast curves, noise reduction on levels
+# 0 .. 2, the CNR weighting from level 3, the coarser-levels gain); a single 7 x 7 SSIM cannot tell a loss in the finest bands from a
+# change of the coarse ones. Multi-scale SSIM (Wang, Simoncelli, Bovik 2003) with ssim_similarity's uniform 7 x 7 window has an exact
+# integer form: iterated 2 x 2 mean pooling is the 2^s x 2^s block mean, the block SUMS of u8 data are integers (<= 255 * 4^s), so every
+# window sum at every scale is an exact integer and only the last f64 summation is open to reordering. These functions are the contract
+# of musica_sim_multiscale (include/musica.h).
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # the 2003 paper's
+SCALES_KEYS = ("ms_ssim", "scales") + mp.SCALE_METRICS        # a study row's *_scales dict
+
+
+def block_sums(a, s):
+    """X_s of a 2-D integer array: [i][j] = the sum of the 2^s x 2^s block whose top-left is (i 2^s, j 2^s); (h >> s, w >> s) int64,
+    rows and columns that do not fill a block dropped."""
+    a = np.asarray(a)
+    k = 1 << s
+    hs, ws = a.shape[0] >> s, a.shape[1] >> s
+    return a[:hs * k, :ws * k].astype(np.int64).reshape(hs, k, ws, k).sum(axis=(1, 3))
+
+
+def _window_sums7(p):
+    """The sums of all 7 x 7 windows of an int64 plane, (h - 6, w - 6) int64: differences of its summed-area table (exact)."""
+    c = np.zeros((p.shape[0] + 1, p.shape[1] + 1), dtype=np.int64)
+    c[1:, 1:] = p.cumsum(axis=0).cumsum(axis=1)
+    return c[7:, 7:] - c[:-7, 7:] - c[7:, :-7] + c[:-7, :-7]
+
+
+def multiscale_terms(sx, sy, sxx, syy, sxy, s):
+    """(ssim, cs, lum) per window from the exact 7 x 7 window sums of X_s, Y_s, X_s^2, Y_s^2, X_s Y_s (int64 arrays or ints): the means
+    by one f64 division by the exact doubles 49 * 4^s and 49 * 16^s, then ssim_similarity's expression in its order."""
+    d1, d2 = float(49 * 4 ** s), float(49 * 16 ** s)
+    ux, uy = np.asarray(sx, dtype=np.int64) / d1, np.asarray(sy, dtype=np.int64) / d1
+    uxx, uyy, uxy = np.asarray(sxx, dtype=np.int64) / d2, np.asarray(syy, dtype=np.int64) / d2, np.asarray(sxy, dtype=np.int64) / d2
+    cov_norm = 49 / 48
+    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
+    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    a1, a2, b1, b2 = 2 * ux * uy + c1, 2 * vxy + c2, ux * ux + uy * uy + c1, vx + vy + c2
+    return (a1 * a2) / (b1 * b2), a2 / b2, a1 / b1
+
+
+def multiscale_windows(a, b, s):
+    """(ssim, cs, lum), each (h_s - 6, w_s - 6) f64: the per-window values of scale s of two uint8 arrays of one shape."""
+    x, y = block_sums(a, s), block_sums(b, s)
+    return multiscale_terms(_window_sums7(x), _window_sums7(y), _window_sums7(x * x), _window_sums7(y * y), _window_sums7(x * y), s)
+
+
+def ms_ssim_from_means(cs, ssim_last):
+    """The combined number from the per-scale means: prod over s < scales - 1 of max(cs[s], 0)^w_s, times max(ssim of the last scale,
+    0)^w_last, w_s = W[s] / sum(W[:scales]); math.pow, ascending s. cs: the means of scales 0 .. scales - 1 (the last is not used)."""
+    n = len(cs)
+    total = sum(MS_SSIM_WEIGHTS[:n])
+    out = 1.0
+    for s in range(n):
+        out *= math.pow(max(float(cs[s]) if s < n - 1 else float(ssim_last), 0.0), MS_SSIM_WEIGHTS[s] / total)
+    return out
+
+
+def max_scales(w, h):
+    """The largest scale count a w x h region admits: min(w, h) >> (count - 1) >= 7; 0 for a region under 7 x 7, at most SIM_MAX_SCALES."""
+    n = 0
+    while n < mp.SIM_MAX_SCALES and (min(int(w), int(h)) >> n) >= 7:
+        n += 1
+    return n
+
+
+def multiscale_similarities(a, b, scales):
+    """musica_sim_multiscale's numbers of two uint8 arrays of one shape (h, w), 1 <= scales <= 5, min(h, w) >> (scales - 1) >= 7 (else
+    ValueError): {ms_ssim, scales, pixels, ssim, cs, lum, mse, ssd, plane_w, plane_h}, the last seven lists of length `scales`.
+    ssim / cs / lum: the means of multiscale_windows over the windows; ssd[s] = sum (X_s - Y_s)^2 (exact);
+    mse[s] = 1 - sqrt(ssd[s] / (h_s w_s)) / (255 * 4^s); ms_ssim: ms_ssim_from_means."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or a.shape != b.shape or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("multiscale_similarities needs two uint8 arrays of one 2-D shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    scales = int(scales)
+    if not 1 <= scales <= mp.SIM_MAX_SCALES:
+        raise ValueError("scales %d out of range [1, %d]" % (scales, mp.SIM_MAX_SCALES))
+    h, w = a.shape
+    if (min(h, w) >> (scales - 1)) < 7:
+        raise ValueError("region %d x %d is smaller than the 7 x 7 window at scale %d" % (w, h, scales - 1))
+    out = {"scales": scales, "pixels": h * w, "ssim": [], "cs": [], "lum": [], "mse": [], "ssd": [], "plane_w": [], "plane_h": []}
+    for s in range(scales):
+        ssim, cs, lum = multiscale_windows(a, b, s)
+        hs, ws = h >> s, w >> s
+        ssd = int(np.sum((block_sums(a, s) - block_sums(b, s)) ** 2))
+        out["ssim"].append(float(ssim.mean()))
+        out["cs"].append(float(cs.mean()))
+        out["lum"].append(float(lum.mean()))
+        out["ssd"].append(ssd)
+        out["mse"].append(1.0 - math.sqrt(ssd / (hs * ws)) / (255 * 4 ** s))
+        out["plane_w"].append(ws)
+        out["plane_h"].append(hs)
+    out["ms_ssim"] = ms_ssim_from_means(out["cs"], out["ssim"][-1])
+    return out
+
+
 # ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
 
 def vendor_to_u8(pixels):
@@ -544,12 +639,14 @@ def read_bmp_gray(path):
 SLOT_UNALTERED, SLOT_ROTATED, SLOT_VENDOR, SLOT_VENDOR_ROTATED = 0, 1, 2, 3
 VENDOR_SLOT = {SLOT_UNALTERED: SLOT_VENDOR, SLOT_ROTATED: SLOT_VENDOR_ROTATED}
 SLOT_TONE = 4   # tone=True: slots 4 .. 7 hold the slots of a row's (at most four) comparisons remapped with their tone_lut (musica_sim_remap_reference)
+SCALE_ROW_KEYS = {"direct": "direct_scales", "registered": "registered_scales", "reference": "reference_scales",
+                  "registered_reference": "registered_reference_scales"}
 TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "reference": "reference_tone",
              "registered_reference": "registered_reference_tone"}
 
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
-              tone=False, displacement=0, displacement_tiles=False):
+              tone=False, displacement=0, displacement_tiles=False, scales=0):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -586,7 +683,14 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     output moved as the input did. On the device the row's one or two queries go through one musica_sim_displace call; on the host the
     restatement runs on the same planes; both summarise exact integer tables with one function, so the two agree to the last bit.
     displacement_tiles: each *_shift dict also carries "tile_tables" ((tiles_y, tiles_x, S, S) uint32) and "size" ((w, h) of its
-    region), what displacement_maps draws. With displacement=0 the rows and the launches are exactly as before."""
+    region), what displacement_maps draws. With displacement=0 the rows and the launches are exactly as before.
+
+    scales: S > 0 (at most SIM_MAX_SCALES) says at which spatial scale the output changed (multiscale_similarities). Every comparison
+    dict of a row gains a sibling: direct_scales, registered_scales and, with a vendor image, reference_scales and
+    registered_reference_scales; present exactly where the original is and None exactly where it is None. Each is a dict of SCALES_KEYS:
+    ms_ssim, scales and the lists ssim, cs, lum, mse of length `scales`, a comparison using min(S, max_scales of its region). On the
+    device the row's queries go through one musica_sim_multiscale call per distinct scale count; on the host the restatement scores
+    the same crops. With scales=0 the rows and the launches are exactly as before."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     if vendor is not None:
@@ -602,6 +706,11 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         raise ValueError("displacement radius %d is not in 1 .. %d" % (displacement, mp.SIM_MAX_RADIUS))
     if displacement:
         keys += ("direct_shift", "registered_shift")
+    scales = int(scales)
+    if scales and not 1 <= scales <= mp.SIM_MAX_SCALES:
+        raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
+    if scales:
+        keys += tuple(SCALE_ROW_KEYS[k] for k in keys if k in SCALE_ROW_KEYS)
     shutters = scaled(SHUTTERS, n) if shutters is None else shutters
     translations = scaled(TRANSLATIONS, n) if translations is None else translations
     rotations = ROTATIONS if rotations is None else rotations
@@ -632,6 +741,20 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             r["tone_ssim"] = c["ssim"]
         return [{k: r[k] for k in mp.JOINT_METRICS} for r in res]
 
+    def scales_on_device(queries):
+        """The SCALES_KEYS of a row's queries: one musica_sim_multiscale call per distinct scale count, results in the queries' order."""
+        counts = [min(scales, max_scales(q[6], q[7])) for q in queries]
+        out = [None] * len(queries)
+        for n in sorted(set(counts)):
+            idx = [i for i, c in enumerate(counts) if c == n]
+            for i, r in zip(idx, runner.proc.sim_multiscale([queries[i] for i in idx], n)):
+                out[i] = {k: r[k] for k in SCALES_KEYS}
+        return out
+
+    def scales_on_host(a, b):
+        r = multiscale_similarities(a, b, min(scales, max_scales(a.shape[1], a.shape[0])))
+        return {k: r[k] for k in SCALES_KEYS}
+
     def shift_summary(table, region, tiles, tiles_off, tile_tables):
         out = displacement_summary(table, region[4] * region[5], tiles, tiles_off)
         if displacement_tiles:
@@ -656,7 +779,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         tt = displacement_tile_tables(a, b, region, displacement)
         return shift_summary(tt.astype(np.int64).sum(axis=(0, 1)), region, tt.shape[0] * tt.shape[1], displacement_tiles_off(tt), tt)
 
-    first = {"alteration": "unaltered", "registered": None, "registered_tone": None, "registered_shift": None}
+    first = {"alteration": "unaltered", "registered": None, "registered_tone": None, "registered_shift": None, "registered_scales": None}
     if device:
         runner.proc.sim_capture(SLOT_UNALTERED)
         queries = [(0, SLOT_UNALTERED) + full]
@@ -674,6 +797,11 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
                 first["reference_tone"] = res[1]
         if displacement:
             first["direct_shift"] = shifts_on_device([(SLOT_UNALTERED, _inset(full, displacement))])[0]
+        if scales:
+            res = scales_on_device(queries)
+            first["direct_scales"] = res[0]
+            if vendor is not None:
+                first["reference_scales"] = res[1]
     else:
         if displacement:
             first["direct_shift"] = shift_on_host(unalt, unalt, _inset(full, displacement))
@@ -684,6 +812,10 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             first["direct_tone"] = tone_similarities(unalt, unalt)
             if vendor is not None:
                 first["reference_tone"] = tone_similarities(unalt, ref8)
+        if scales:
+            first["direct_scales"] = scales_on_host(unalt, unalt)
+            if vendor is not None:
+                first["reference_scales"] = scales_on_host(unalt, ref8)
     first["mean_cnr"] = runner.mean_cnr() if runner.proc else None
     rows = [{k: first[k] for k in keys if k in first}]
 
@@ -694,7 +826,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     def add(name, host, dev, reg=None, region=None, slot=None, plane=None):
         """One row of study() below, scored the way the runner's mode asks for."""
         row = {"alteration": name, "registered": None, "registered_reference": None, "registered_tone": None, "registered_reference_tone": None,
-               "registered_shift": None}
+               "registered_shift": None, "registered_scales": None, "registered_reference_scales": None}
         if alter_on_device:
             dev()
             runner.run_resident()
@@ -712,7 +844,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
                     queries.append((0, sl) + r)
                     if vendor is not None:
                         queries.append((0, VENDOR_SLOT[sl]) + r)
-            for suffix, score in (("", on_device),) + ((("_tone", tone_on_device),) if tone else ()):
+            for suffix, score in (("", on_device),) + ((("_tone", tone_on_device),) if tone else ()) + ((("_scales", scales_on_device),) if scales else ()):
                 res = score(queries)
                 row["direct" + suffix] = res.pop(0)
                 if vendor is not None:
@@ -731,7 +863,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             if crop is not None and not (crop[0].size and crop[0].shape == crop[1].shape and min(crop[0].shape) >= 8):
                 crop = None
             vcrop = reg(alt, ref8) if crop is not None and vendor is not None else None   # the same rectangles: ref8 has unalt's shape
-            for suffix, score in (("", similarities),) + ((("_tone", tone_similarities),) if tone else ()):
+            for suffix, score in (("", similarities),) + ((("_tone", tone_similarities),) if tone else ()) + ((("_scales", scales_on_host),) if scales else ()):
                 row["direct" + suffix] = score(alt, unalt)
                 if vendor is not None:
                     row["reference" + suffix] = score(alt, ref8)
@@ -807,6 +939,25 @@ SHIFT_CSV_GROUPS = (('direct_shift', 'direct'), ('registered_shift', 'registered
 SHIFT_CSV_HEADER = ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in SHIFT_CSV_GROUPS for m in SHIFT_CSV_NAMES]   # displacement.csv
 
 
+SCALE_CSV_GROUPS = tuple((SCALE_ROW_KEYS[k], g) for k, g in (("direct", "altered vs unaltered"), ("registered", "registered vs unaltered"),
+                                                               ("reference", "altered vs reference"), ("registered_reference", "registered vs reference")))
+SCALE_CSV_METRICS = ("ssim", "cs", "mse")   # per scale 0 .. 4, behind ms_ssim and scales
+
+
+def scale_csv_header(with_reference):
+    """scale_robustness.csv's columns: per group ms_ssim, scales, then ssim, cs and mse of scales 0 .. 4; the two vendor groups only for
+    studies that have a vendor image."""
+    return ['raw file', 'alteration'] + [c for _, g in SCALE_CSV_GROUPS[:4 if with_reference else 2] for c in
+                                         ['%s ms-ssim' % g, '%s scales' % g] +
+                                         ['%s %s scale %d' % (g, m, s) for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)]]
+
+
+def _scale_csv_cells(t):
+    if t is None:
+        return [""] * (2 + len(SCALE_CSV_METRICS) * mp.SIM_MAX_SCALES)
+    return [t["ms_ssim"], t["scales"]] + [t[m][s] if s < t["scales"] else "" for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)]
+
+
 def tone_csv_header(with_reference):
     """tone_robustness.csv's columns: the five JOINT_METRICS per group, the two vendor groups only for studies that have a vendor image."""
     return ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in TONE_CSV_GROUPS[:4 if with_reference else 2] for m in TONE_CSV_NAMES]
@@ -837,7 +988,10 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     other files are written as without it.
 
     Studies run with a displacement radius (rows[0] has "direct_shift") also get displacement.csv: one line per row, the unaltered one
-    included, the SHIFT_KEYS of the direct and of the registered comparison; cells without a comparison are empty."""
+    included, the SHIFT_KEYS of the direct and of the registered comparison; cells without a comparison are empty.
+
+    Studies run with scales (rows[0] has "direct_scales") also get scale_robustness.csv (scale_csv_header): one line per row, the
+    unaltered one included; cells without a comparison, and of scales beyond a comparison's count, are empty."""
     os.makedirs(out_dir, exist_ok=True)
     ovds = []
 
@@ -901,6 +1055,17 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
                         t = r.get(key)
                         cells += [""] * len(SHIFT_KEYS) if t is None else [t[k] for k in SHIFT_KEYS]
                     ws.writerow([raw_name, r["alteration"]] + cells)
+
+
+    scored = [(raw_name, rows) for raw_name, rows in studies if rows and "direct_scales" in rows[0]]
+    if scored:
+        groups = SCALE_CSV_GROUPS[:4 if any("reference_scales" in rows[0] for _, rows in scored) else 2]
+        with open(os.path.join(out_dir, "scale_robustness.csv"), "w", newline="") as fs:
+            ws = csv.writer(fs)
+            ws.writerow(scale_csv_header(len(groups) == 4))
+            for raw_name, rows in scored:
+                for r in rows:
+                    ws.writerow([raw_name, r["alteration"]] + [c for key, _ in groups for c in _scale_csv_cells(r.get(key))])
 
 
 def write_displacement_maps(studies, out_dir):
@@ -1011,7 +1176,13 @@ def main(argv=None):
     ap.add_argument("--displacement-maps", metavar="DIR",
                     help="with --displacement: two 8-bit BMPs per registered row into DIR, one pixel per 64 x 64 tile: the tile RMSE at the zero "
                          "shift and the length of the tile's best shift")
+    ap.add_argument("--scales", type=int, default=0, metavar="S",
+                    help="say at which spatial scale the output changed: SSIM, its contrast-structure factor and mse at S (1 .. 5) scales of "
+                         "2 x 2 pooling and their MS-SSIM product, per comparison, written to scale_robustness.csv; on the GPU with "
+                         "--device-metrics / --device-alterations (musica_sim_multiscale)")
     args = ap.parse_args(argv)
+    if args.scales and not 1 <= args.scales <= mp.SIM_MAX_SCALES:
+        ap.error("--scales takes a count of 1 .. %d" % mp.SIM_MAX_SCALES)
     if args.displacement and not 1 <= args.displacement <= mp.SIM_MAX_RADIUS:
         ap.error("--displacement takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
     if args.displacement_maps and not args.displacement:
@@ -1038,6 +1209,8 @@ def main(argv=None):
     runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics, device_alterations=args.device_alterations)
     shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
                  {"displacement": args.displacement} if args.displacement else {}
+    if args.scales:
+        shift_args["scales"] = args.scales
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

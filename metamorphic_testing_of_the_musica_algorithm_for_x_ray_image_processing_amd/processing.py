@@ -161,6 +161,28 @@ class SimDisplaceResult(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+SIM_MAX_SCALES = 5          # MUSICA_SIM_MAX_SCALES
+SCALE_METRICS = ("ssim", "cs", "lum", "mse")   # the per-scale lists of harness.multiscale_similarities (beside ms_ssim and scales)
+
+
+class SimScalesResult(C.Structure):
+    """musica_sim_scales_result: the scale-resolved SSIM of one comparison."""
+    _fields_ = [("scales", C.c_uint32), ("pixels", C.c_uint64), ("ms_ssim", C.c_double)] + \
+               [(n, C.c_double * SIM_MAX_SCALES) for n in SCALE_METRICS] + \
+               [("ssd", C.c_uint64 * SIM_MAX_SCALES), ("plane_w", C.c_uint32 * SIM_MAX_SCALES), ("plane_h", C.c_uint32 * SIM_MAX_SCALES)]
+
+    def as_dict(self):
+        """The entries of the scales asked for; "raw": every array at its full length (zero beyond them)."""
+        n = int(self.scales)
+        d = {"scales": n, "pixels": int(self.pixels), "ms_ssim": float(self.ms_ssim)}
+        for k in SCALE_METRICS:
+            d[k] = [float(v) for v in getattr(self, k)[:n]]
+        for k in ("ssd", "plane_w", "plane_h"):
+            d[k] = [int(v) for v in getattr(self, k)[:n]]
+        d["raw"] = {k: list(getattr(self, k)) for k in SCALE_METRICS + ("ssd", "plane_w", "plane_h")}
+        return d
+
+
 # musica_out_format: what export_out writes per image
 OUT_U8, OUT_GRADED_F32 = 0, 1
 OUT_FORMAT_COUNT = 2
@@ -288,6 +310,7 @@ ABI = {
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
+    "musica_sim_multiscale": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimScalesResult)]),
     "musica_alter_set_source": (C.c_int, [_VP, _U16P]),
     "musica_alter": (C.c_int, [_VP, C.c_uint32, C.POINTER(Alteration)]),
     "musica_alter_draws": (C.c_int, [_VP, C.POINTER(Alteration), C.POINTER(C.c_int32)]),
@@ -704,6 +727,18 @@ class MusicaProcessing:
                 d["tile_tables"] = tile[first:first + per[i]].reshape(d["tiles_y"], d["tiles_x"], s, s)
                 first += per[i]
         return out
+
+    def sim_multiscale(self, queries, scales):
+        """queries as sim_compare's, every one at `scales` (1 .. SIM_MAX_SCALES) scales, in one call: the 7 x 7 SSIM of the 2^s x 2^s
+        block sums of both sides, == harness.multiscale_similarities. Returns one dict per query: ms_ssim, scales, pixels, the lists
+        ssim, cs, lum, mse (SCALE_METRICS), ssd (exact), plane_w, plane_h of length `scales`, and "raw": those arrays at their full
+        length (zero beyond `scales`). min(w, h) >> (scales - 1) must be at least 7."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        if not 0 <= int(scales) < 2 ** 32:
+            raise ValueError("scales %r is not in 1 .. %d" % (scales, SIM_MAX_SCALES))
+        arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimScalesResult * max(len(qs), 1))()
+        self._ok(self._lib.musica_sim_multiscale(self._h, len(qs), arr, int(scales), res), "musica_sim_multiscale")
+        return [res[i].as_dict() for i in range(len(qs))]
 
     def sim_remap_reference(self, dst_slot, src_slot, lut):
         """Reference slot `src_slot` through the 256-entry uint8 table `lut` (dst = lut[src]) into `dst_slot`, on the device."""
