@@ -1,0 +1,235 @@
+"""The early-exit scan of the noise histogram (noise_hist.comp), in every launch form, on inputs where the `break` matters.
+
+A phantom's band images never break a column-run (no sdev value is 0, above 0.1 or in bin 0), so on them any scan that counts every
+texel inside the coverage passes. Here the band images (stage level) and the raw pixels (whole steps) come from
+tests/noise_hist_restatement.py: a lattice of small dead patches of all three causes that hits every row phase of a run, every one of
+a lane's 8 columns, the first and last lane of a strip and every row quarter of a run workgroup, plus bin-2048 texels (dropped, the
+run goes on). tests/test_noise_hist_restatement.py holds the generators and the restatement to the oracle on the CPU.
+
+Every comparison is bit-exact (test_gpu_parity.py states the bars): the device against the oracle, and the device's histograms
+against the restatement applied to the ORACLE's sdev images, whose message names the level, column, run, phase and cause of the first
+broken run that holds a differing bin. That what the inputs decide is a condition too, asserted here on the oracle's sdev images
+(R.full_coverage_problems / R.raw_coverage_problems), so a later edit of a generator cannot hollow the tests out.
+
+Non-finite band samples: the oracle's hosting rules define the bin of a NaN (oracle/glsl_host.h Q6: int(NaN) = 0, a bin-0 break) and
++inf breaks as `> 1`, so one case injects a +inf and a NaN sample (25 sdev texels each) at the stage level."""
+import os
+
+import numpy as np
+import pytest
+
+import noise_hist_restatement as R
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd.phantom import phantom
+from test_gpu_parity import _compare_all, _proc, _same
+
+pytestmark = pytest.mark.gpu
+
+
+def _library_defaults(monkeypatch):
+    for k in list(os.environ):
+        if k.startswith("MUSICA_"):
+            monkeypatch.delenv(k)
+
+
+def _assert_hist(got, want_oracle, want_scan, sdev_oracle, n, what):
+    """One histogram against the oracle's and against the restatement of the scan on the oracle's sdev image (want_scan)."""
+    assert np.array_equal(want_scan, want_oracle), what + ": the restatement and the oracle disagree: " + R.first_difference(sdev_oracle, n, want_oracle)
+    assert np.array_equal(got, want_oracle), what + ": " + R.first_difference(sdev_oracle, n, got)
+
+
+# ---- stage level: injected band images ----------------------------------------------------------------------------------------------
+# The smallest sides that still have the geometry that matters:
+#   1032 / L6  level 0 has three strips, the last 8 columns wide, and 1032 % 16 = 8 ragged rows; cov = 1024 leaves rows and columns
+#              1024 .. 1031 uncovered; level 1 = 516 is not a multiple of 8 (the per-column masks instead of A8)
+#   1000 / L6  cov = 512 cuts level 0 in the middle on both axes; levels 1 .. 3 (500, 250, 125) are wholly covered and ragged
+#   1536 / L6  three full strips; levels 768 / 384 / 192, all multiples of 8 and of 16
+#   520 / L4   cov = 512 on a two-strip level 0 whose second strip is one lane wide
+#   504 / L4   cov = 0: every histogram stays empty whatever the band holds, and the curves come from empty histograms
+_SIDES = [(1032, 6), (1000, 6), (1536, 6), (520, 4), (504, 4)]
+_FIXED = {"MUSICA_AUTOTUNE": "0"}
+# name -> (environment, context flags, oracle order). With a batch the analysis stage is one launch for all levels (k_sdev_hist_levels), each
+# level in the form MUSICA_SDEV_RUN / MUSICA_SDEV_ROWS give it; MUSICA_SDEV_ONE_LAUNCH=0 takes the per-level launches k_sdev_hist /
+# k_sdev_hist_run and the merged run launch of the small levels (k_sdev_hist_runs).
+_FORMS = {
+    "march16": (dict(_FIXED, MUSICA_SDEV_RUN="0", MUSICA_SDEV_ROWS="16"), 0, "fast"),
+    "march32": (dict(_FIXED, MUSICA_SDEV_RUN="0", MUSICA_SDEV_ROWS="32"), 0, "fast"),
+    "run": (dict(_FIXED, MUSICA_SDEV_RUN="1"), 0, "fast"),
+    "march16_per_level": (dict(_FIXED, MUSICA_SDEV_RUN="0", MUSICA_SDEV_ROWS="16", MUSICA_SDEV_ONE_LAUNCH="0"), 0, "fast"),
+    "run_per_level": (dict(_FIXED, MUSICA_SDEV_RUN="1", MUSICA_SDEV_ONE_LAUNCH="0"), 0, "fast"),
+    "default": ({}, 0, "fast"),
+    "default_per_level": ({"MUSICA_SDEV_ONE_LAUNCH": "0"}, 0, "fast"),
+    "reference_order": ({}, mp.FLAG_REFERENCE_ORDER, "reference"),       # k_sdev_literal + k_noise_hist_only
+}
+
+_STAGE_WANT = {}      # (n, levels, order, k, nonfinite) -> what the oracle's analysis stage gives for crafted_bands(n, k): built once, left alone
+_STAGE_ORACLE = {}    # (n, levels, order) -> the oracle that has executed the base phantom
+
+
+def _base_phantom(n):
+    return phantom(n, 9)
+
+
+def _stage_want(ob, n, levels, order, k, nonfinite=False):
+    key = (n, levels, order, k, nonfinite)
+    if key not in _STAGE_WANT:
+        okey = (n, levels, order)
+        if okey not in _STAGE_ORACLE:
+            _STAGE_ORACLE[okey] = ob.Oracle(n, levels, ob.ORDER_REFERENCE if order == "reference" else ob.ORDER_FAST).execute(_base_phantom(n))
+        o = _STAGE_ORACLE[okey]
+        for i, band in enumerate(R.crafted_bands(n, k, nonfinite)):
+            o.set_image(ob.IMG_BANDPASS, i, band)
+        o.run_stage(ob.STAGE_ANALYSIS)
+        sdev = [o.image(ob.IMG_SDEV, i) for i in range(4)]
+        _STAGE_WANT[key] = {
+            "sdev": sdev, "hist": [o.noise_hist(i) for i in range(4)], "hist_max": [o.noise_hist_max(i) for i in range(4)],
+            "curves": [o.contrast_curve(i) for i in range(levels)], "cnr": o.image(ob.IMG_CNR, 3),
+            "scan": [R.scan(sd, n)[0] for sd in sdev],
+            "problems": [R.full_coverage_problems(R.coverage(sd, n)) for sd in sdev] if R.coverage_side(n) else [[]] * 4,
+        }
+    return _STAGE_WANT[key]
+
+
+def _run_stage_case(ob, n, levels, env, flags, order, members, monkeypatch, nonfinite=False):
+    """A context of len(members) images executes the base phantom, takes the crafted band images of batch member members[slot] in
+    every slot, runs the analysis stage and is compared with the oracle that did the same."""
+    _library_defaults(monkeypatch)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    batch = len(members)
+    p = _proc(n, levels, batch=batch, flags=flags)
+    assert p.execute(np.stack([_base_phantom(n)] * batch)), mp.last_error()
+    for slot, k in enumerate(members):
+        for i, band in enumerate(R.crafted_bands(n, k, nonfinite)):
+            p.set_image(mp.IMG_BANDPASS, i, band, slot)
+    p.run_stage(mp.STAGE_ANALYSIS)
+    for slot, k in enumerate(members):
+        want = _stage_want(ob, n, levels, order, k, nonfinite)
+        tag = "%d / L%d slot %d (crafted image %d): " % (n, levels, slot, k)
+        for i in range(4):
+            assert want["problems"][i] == [], tag + "level %d: the crafted band no longer decides %s" % (i, want["problems"][i])
+            _same(p.image(mp.IMG_SDEV, i, slot), want["sdev"][i], tag + "sdev[%d]" % i)
+            _assert_hist(p.noise_hist(i, slot), want["hist"][i], want["scan"][i], want["sdev"][i], n, tag + "noise_hist, level %d" % i)
+            assert p.noise_hist_max(i, slot) == want["hist_max"][i], tag + "noise_hist_max[%d]" % i
+        for i in range(levels):
+            assert np.array_equal(p.contrast_curve(i, slot), want["curves"][i]), tag + "contrast_curve[%d]" % i
+        _same(p.image(mp.IMG_CNR, 3, slot), want["cnr"], tag + "cnr")
+        if R.coverage_side(n) == 0:
+            assert all(h.sum() == 0 for h in want["hist"])
+    p.cleanup()
+
+
+@pytest.mark.parametrize("form", list(_FORMS))
+@pytest.mark.parametrize("n,levels", _SIDES, ids=["%d_L%d" % s for s in _SIDES])
+def test_analysis_stage_on_crafted_band_images(ob, n, levels, form, monkeypatch):
+    """A batch of three, a different crafted image per slot (blockIdx.z indexing, the per-image histogram stride)."""
+    env, flags, order = _FORMS[form]
+    _run_stage_case(ob, n, levels, env, flags, order, (0, 1, 2), monkeypatch)
+
+
+def test_march_of_two_runs_per_wavefront(ob, monkeypatch):
+    """MUSICA_SDEV_ROWS=32 holds only where 32-row marches still give 2048 wavefronts; below that the context halves it to 16. At
+    1536 / L6 that takes 15 images (3 strips x 48 marches x 15 = 2160): level 0 then marches two runs per wavefront, the form whose
+    `alive` masks are re-armed in mid-march."""
+    env = dict(_FIXED, MUSICA_SDEV_RUN="0", MUSICA_SDEV_ROWS="32")
+    _run_stage_case(ob, 1536, 6, env, 0, "fast", tuple(k % 3 for k in range(15)), monkeypatch)
+
+
+@pytest.mark.parametrize("form", ["march16", "run", "reference_order"])
+def test_non_finite_band_samples(ob, form, monkeypatch):
+    """A +inf and a NaN band sample: 25 sdev texels of +inf (`> 1` break) and 25 of NaN (bin 0 by Q6), last and first lanes of level 0."""
+    env, flags, order = _FORMS[form]
+    _run_stage_case(ob, 1032, 6, env, flags, order, (1, 0), monkeypatch, nonfinite=True)
+
+
+# ---- whole steps: crafted raw images --------------------------------------------------------------------------------------------------
+_STEP_WANT = {}       # (n, levels, image name) -> (pixels, executed ORDER_FAST oracle, per level (restatement's histogram, coverage problems))
+
+
+def _raw_image(n, name):
+    if name == "phantom":
+        return phantom(n, 41)
+    if name == "constant":
+        return np.full((n, n), 30000, dtype=np.uint16)
+    return R.crafted_raw(phantom(n, 500 + name), name)     # name = 0, 1, 2: crafted images
+
+
+def _step_want(ob, n, levels, name):
+    key = (n, levels, name)
+    if key not in _STEP_WANT:
+        px = _raw_image(n, name)
+        o = ob.Oracle(n, levels, ob.ORDER_FAST).execute(px)
+        sdev = [o.image(ob.IMG_SDEV, i) for i in range(4)]
+        held = [(R.scan(sd, n)[0], R.raw_coverage_problems(R.coverage(sd, n), i) if isinstance(name, int) else []) for i, sd in enumerate(sdev)]
+        _STEP_WANT[key] = (px, o, held)       # built once, only read afterwards
+    return _STEP_WANT[key]
+
+
+def _compare_step(p, ob, n, levels, names, tag):
+    for slot, name in enumerate(names):
+        _, o, held = _step_want(ob, n, levels, name)
+        t = "%s%d / L%d slot %d (%s): " % (tag, n, levels, slot, name)
+        for i in range(4):
+            assert held[i][1] == [], t + "level %d: the crafted image no longer decides %s" % (i, held[i][1])
+            _assert_hist(p.noise_hist(i, slot), o.noise_hist(i), held[i][0], o.image(ob.IMG_SDEV, i), n, t + "noise_hist, level %d" % i)
+        _compare_all(p, o, ob, idx=slot, tag=t)
+
+
+def _step_case(ob, n, levels, env, flags, names, monkeypatch, executes=2):
+    _library_defaults(monkeypatch)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    p = _proc(n, levels, batch=len(names), flags=flags)
+    px = np.stack([_step_want(ob, n, levels, name)[0] for name in names])
+    for _ in range(executes):                                  # the second execute replays what the first set up
+        assert p.execute(px), mp.last_error()
+    return p
+
+
+@pytest.mark.parametrize("one_launch", ["1", "0"])
+@pytest.mark.parametrize("n,levels", [(1032, 6), (1536, 6)], ids=["1032_L6", "1536_L6"])
+def test_lone_context_steps(ob, n, levels, one_launch, monkeypatch):
+    """All levels in one launch (k_sdev_hist_levels) and the per-level launches with the merged run launch of the small levels."""
+    p = _step_case(ob, n, levels, {"MUSICA_SDEV_ONE_LAUNCH": one_launch}, 0, (0,), monkeypatch)
+    _compare_step(p, ob, n, levels, (0,), "one launch %s: " % one_launch)
+    p.cleanup()
+
+
+@pytest.mark.parametrize("n,levels", [(1032, 6), (2056, 7)], ids=["1032_L6", "2056_L7"])
+def test_histogram_only_role_when_the_expand_launches_compute_sdev(ob, n, levels, monkeypatch):
+    """MUSICA_SDEV_IN_EXPAND=1: the sdev launches of levels 0 .. 2 get sdev == nullptr, store nothing and only count."""
+    p = _step_case(ob, n, levels, {"MUSICA_SDEV_IN_EXPAND": "1"}, 0, (1,), monkeypatch)
+    assert p.fuses_sdev()
+    _compare_step(p, ob, n, levels, (1,), "sdev in expand: ")
+    p.cleanup()
+
+
+_RUN = {"MUSICA_AUTOTUNE": "0", "MUSICA_SDEV_RUN": "1"}
+_MARCH = {"MUSICA_AUTOTUNE": "0", "MUSICA_SDEV_RUN": "0", "MUSICA_SDEV_ROWS": "16"}
+
+
+@pytest.mark.parametrize("sd", ["0", "1"])
+@pytest.mark.parametrize("form", ["run", "march"])
+def test_sdev_role_of_the_paired_launches(ob, form, sd, monkeypatch):
+    """A MUSICA_FLAG_LINEAR context of three images at 1152 / L6 with the pairs on: four pairs per step (test_gpu_launch_forms.py's
+    _GEOMETRY), the sdev role of k_rb_sdev in both forms, storing sdev (sd = 0) and histogram only (sd = 1)."""
+    n, levels, names = 1152, 6, (0, 1, 2)
+    env = dict(_RUN if form == "run" else _MARCH, MUSICA_PAIR_RB_SDEV="1", MUSICA_SDEV_IN_EXPAND=sd)
+    p = _step_case(ob, n, levels, env, mp.FLAG_LINEAR, names, monkeypatch)
+    assert p.dispatch()[0] == 1
+    assert p.paired_levels() == 4
+    assert p.fuses_sdev() == (sd == "1")
+    _compare_step(p, ob, n, levels, names, "pairs, %s, sd %s: " % (form, sd))
+    p.cleanup()
+
+
+def test_per_image_state_does_not_leak_between_slots_or_executes(ob, monkeypatch):
+    """A crafted image, a plain phantom and an all-constant image (min == max: the oracle defines the outcome, _compare_all has the NaN
+    branch for mean_cnr) in one batch, executed twice, then in reverse order on the same context."""
+    n, levels, names = 1032, 6, (2, "phantom", "constant")
+    p = _step_case(ob, n, levels, {}, 0, names, monkeypatch)
+    _compare_step(p, ob, n, levels, names, "mixed batch: ")
+    back = names[::-1]
+    assert p.execute(np.stack([_step_want(ob, n, levels, name)[0] for name in back])), mp.last_error()
+    _compare_step(p, ob, n, levels, back, "mixed batch reversed: ")
+    p.cleanup()
