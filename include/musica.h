@@ -475,6 +475,50 @@ int musica_sim_multiscale(musica_ctx* ctx, uint32_t count, const musica_sim_quer
  * Marks dst_slot written. */
 int musica_sim_remap_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]);
 
+/* Ensemble noise statistics: per-pixel mean and variance of the output across many realisations of a noise alteration, split into bias
+ * against a reference slot and noise (harness.ensemble_statistics). One comparison scores one draw and cannot tell a systematic change of
+ * the output from amplified noise; the ensemble can. a_k(p), k = 1 .. K, is the 8-bit output of realisation k at output pixel p: exactly
+ * the bytes musica_get_out_pixels returns (cropped by MUSICA_OUT_MARGIN, quantised while it is read). Per pixel of the (N - 20)^2 plane
+ * the context keeps S1(p) = sum_k a_k(p) and S2(p) = sum_k a_k(p)^2; with K <= MUSICA_SIM_ENSEMBLE_MAX, S1 <= 261 120 and
+ * S2 <= 66 585 600 fit u32. With b(p) the plane of a reference slot and a query region of n = w h pixels, all exact integers:
+ *   D(p) = S1(p) - K b(p) (signed),  V(p) = K S2(p) - S1(p)^2 (>= 0),
+ *   sq_bias_sum = sum D^2,  var_sum = sum V,  bias_sum = sum D,  abs_bias_max = max |D|,  var_max = max V,
+ *   sq_err_sum = sum (S2 - 2 b S1 + K b^2) = sum_k sum_p (a_k - b)^2: musica_sim_compare's sq_diff_sum summed over the K realisations,
+ * and K sq_err_sum == sq_bias_sum + var_sum holds exactly. sq_bias_sum <= 255^2 K^2 n and every other sum is smaller: a query with
+ * 65025 K^2 w h >= 2^64 is refused (with K = 1024 that is a region of 2^44 / 65025 pixels or more, 16 448^2: beyond any plane the library accepts). The doubles are computed on the host from those integers, one
+ * IEEE operation each in this order (every integer converted to double first):
+ *   mean_shift = bias_sum / (K n);  bias_rms = sqrt(sq_bias_sum / (K K n));  noise_rms = sqrt(var_sum / (K (K - 1) n)), 0 when K == 1;
+ *   mse = 1 - sqrt(sq_err_sum / (K n)) / 255;  bias_fraction = sq_bias_sum / (sq_bias_sum + var_sum), 0 when both are 0.
+ * Tiles are musica_sim_displace's: tile (ty, tx) owns the region pixels [64 ty, min(h, 64 ty + 64)) x [64 tx, min(w, 64 tx + 64)); a tile
+ * table holds two u64 per tile, (sum D^2, sum V), tile-row major, and the tile entries of a query sum to its totals. All of it is integer
+ * arithmetic: exact, and the same from call to call. */
+#define MUSICA_SIM_ENSEMBLE_MAX 1024
+typedef struct musica_sim_ensemble_stats {
+    double mean_shift, bias_rms, noise_rms, mse, bias_fraction;
+    uint64_t sq_bias_sum, var_sum, sq_err_sum;
+    int64_t bias_sum;
+    uint64_t abs_bias_max, var_max;
+    uint64_t pixels;                          /* w * h */
+    uint32_t realisations;                    /* K */
+    uint32_t tiles_x, tiles_y;                /* ceil(w / 64), ceil(h / 64) */
+} musica_sim_ensemble_stats;
+/* Zeroes the accumulators and K, on the context's stream. The accumulators ((N - 20)^2 words of 8 bytes) are allocated by the first call. */
+int musica_sim_ensemble_reset(musica_ctx* ctx);
+/* Adds the current outputs of batch images first .. first + count - 1 and sets K += count. Enqueued on the context's stream behind whatever
+ * is there (a step, musica_execute_device); returns without waiting. Refused before anything is enqueued: a NULL context, count == 0 or
+ * first + count > batch, N <= 20, no step has run on the context, the ensemble was never reset, K + count > MUSICA_SIM_ENSEMBLE_MAX.
+ * Changes no result of the step, no input image and no slot. */
+int musica_sim_ensemble_add(musica_ctx* ctx, uint32_t first, uint32_t count);
+/* `count` (1 .. MUSICA_SIM_MAX_QUERIES) queries in one launch; synchronous. Side a is the ensemble: image_index is checked like the other
+ * calls and not used, so one query array serves all the musica_sim_* calls. `tile_tables` (may be NULL): the queries' tile tables back to
+ * back in query order, tiles_y * tiles_x * 2 u64 each. The refusals of musica_sim_compare, and: K == 0 (never reset, or nothing added since),
+ * the range condition above. Changes no accumulator, no slot, no result of the step and no input image. */
+int musica_sim_ensemble_result(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_ensemble_stats* results,
+                               uint64_t* tile_tables);
+/* The (N - 20)^2 accumulators S1 and S2 to the host, top-down rows, and K; synchronous. Any of the three pointers may be NULL. Refused when
+ * the ensemble was never reset. */
+int musica_sim_ensemble_get(musica_ctx* ctx, uint32_t* s1, uint32_t* s2, uint32_t* realisations);
+
 /* ---- alterations of the metamorphic study (new, not in the reference) ---- */
 
 /* The study's alteration generators (harness.py apply_collimator, clamp_translation, clamp_rotate, add_gaussian_noise,

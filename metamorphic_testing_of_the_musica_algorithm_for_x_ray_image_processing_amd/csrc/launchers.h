@@ -229,6 +229,25 @@ void scales_geometry(ScaleJobDev& q);
 // max_blocks, the largest strips * segs), then k_scales_fold: out[j] of job j. pool: the tiles' partials; part: jobs x kScaleMaxBlocks.
 void launch_scales(hipStream_t st, const ScalePoolDev* d_qs, int count, int max_tiles, const ScaleJobDev* d_jobs, int jobs, int max_blocks,
                    uint8_t* scratch, ScalePoolPart* pool, ScaleWinPart* part, ScaleOut* out, const ScaleConsts& k);
+// kernels_ensemble.hip: musica_sim_ensemble_*. The accumulators are one uint2 {S1, S2} per pixel of the cropped plane, dense rows.
+// One query of k_ens_stats: s the accumulators at the a region's origin, b the reference slot's plane at the b region's origin, w x h
+// pixels; tiles_x / tiles_y: ceil(w / 64), ceil(h / 64); tile_base: where the query's tile pairs start in the launch's tile table, in tiles.
+struct EnsQueryDev {
+    const uint2* s;
+    const uint8_t* b;
+    int s_pitch, b_pitch;   // elements
+    int w, h;
+    int tiles_x, tiles_y;
+    unsigned long long tile_base;
+};
+constexpr int kEnsTile = 64;     // MUSICA_SIM_TILE
+constexpr int kEnsTotals = 6;    // u64 per query: sum D^2, sum V, sum D (two's complement), sum E, max |D|, max V
+// k_ens_add: S1 += a, S2 += a^2 over the cropped plane for the `count` graded planes from `graded` on (stride l0.plane), one launch
+void launch_ens_add(hipStream_t st, const float* graded, const LevelDesc& l0, int count, uint2* acc);
+// k_ens_stats over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y) after K realisations. tile_tables: two u64 per tile
+// (all written); totals: count x kEnsTotals u64, zeroed by the caller.
+void launch_ens_stats(hipStream_t st, const EnsQueryDev* d_qs, int count, int max_tiles, uint32_t K, unsigned long long* tile_tables,
+                      unsigned long long* totals);
 // kernels_alteration.hip: one alteration of musica_alter (or the draws of musica_alter_draws) over an n x n plane.
 struct AlterDev {
     int kind;                  // MUSICA_ALTER_*

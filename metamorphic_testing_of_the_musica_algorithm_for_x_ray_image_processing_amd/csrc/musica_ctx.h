@@ -102,6 +102,14 @@ struct StudyState {
     size_t scale_planes_cap = 0;
     ScalePoolPart* d_scale_pool = nullptr;         // the tiles' partials of one call: scale_pool_cap elements, likewise
     size_t scale_pool_cap = 0;
+    // musica_sim_ensemble_*
+    uint2* d_ens = nullptr;                        // [(N - 20)^2]: {S1, S2} per output pixel, allocated by the first reset
+    uint32_t ens_k = 0;                            // realisations added since the last reset
+    bool ens_reset = false;                        // a reset has been enqueued: the accumulators exist and start from zero
+    EnsQueryDev* d_ens_q = nullptr;                // [MUSICA_SIM_MAX_QUERIES]
+    unsigned long long* d_ens_out = nullptr;       // [MUSICA_SIM_MAX_QUERIES][kEnsTotals]
+    unsigned long long* d_ens_tiles = nullptr;     // the tile pairs of one call: 2 * ens_tiles_cap u64, regrown when a call needs more
+    size_t ens_tiles_cap = 0;
     // musica_alter_*: the source plane (N x N u16), the radix-select counts and the fill
     uint16_t* d_alter_src = nullptr;
     uint32_t* d_alter_hist = nullptr;    // [768]

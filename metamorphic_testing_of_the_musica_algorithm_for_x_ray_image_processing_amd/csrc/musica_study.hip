@@ -1,5 +1,6 @@
 // musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the four query calls
-// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip) and the alterations of the input (musica_alter_*;
+// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip), the ensemble accumulators
+// (musica_sim_ensemble_*; kernels_ensemble.hip) and the alterations of the input (musica_alter_*;
 // kernels_alteration.hip, kernels_symmetry.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
 #include <math.h>
 #include <string.h>
@@ -503,6 +504,133 @@ int musica_sim_multiscale(musica_ctx* c, uint32_t count, const musica_sim_query*
     for (uint32_t i = 0; i < count; i++) scales_finish(res.data() + (size_t)i * scales, qs[i], scales, out + i);
     return 1;
     ABI_CATCH("musica_sim_multiscale")
+}
+
+// ---- ensemble statistics (musica_sim_ensemble_*, include/musica.h; kernels_ensemble.hip) ------------------------------------------------
+int musica_sim_ensemble_reset(musica_ctx* c) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_ensemble_reset: ctx is NULL");
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_ensemble_reset: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    const size_t px = sim_side(c) * sim_side(c);
+    if (!ensure(c, &st.d_ens, px)) return fail("musica_sim_ensemble_reset: device allocation of %zu bytes failed", px * sizeof(uint2));
+    HIP_OK(hipMemsetAsync(st.d_ens, 0, px * sizeof(uint2), c->stream));   // behind the adds and results the stream holds
+    st.ens_k = 0;
+    st.ens_reset = true;
+    return 1;
+    ABI_CATCH("musica_sim_ensemble_reset")
+}
+
+int musica_sim_ensemble_add(musica_ctx* c, uint32_t first, uint32_t count) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_ensemble_add: ctx is NULL");
+    if (count == 0) return fail("musica_sim_ensemble_add: count is 0");
+    if ((uint64_t)first + count > (uint64_t)c->B) return fail("musica_sim_ensemble_add: images %u .. %u + %u exceed the batch of %d", first, first, count, c->B);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_ensemble_add: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    if (!c->stepped) return fail("musica_sim_ensemble_add: no step has run on this context");
+    StudyState& st = c->study;
+    if (!st.ens_reset) return fail("musica_sim_ensemble_add: the ensemble was never reset (musica_sim_ensemble_reset)");
+    if ((uint64_t)st.ens_k + count > MUSICA_SIM_ENSEMBLE_MAX)
+        return fail("musica_sim_ensemble_add: %u + %u realisations exceed MUSICA_SIM_ENSEMBLE_MAX = %d", st.ens_k, count, MUSICA_SIM_ENSEMBLE_MAX);
+    CHECK_CTX(c);
+    launch_ens_add(c->stream, image_slice(c, c->d_graded, first), c->lv[0], (int)count, st.d_ens);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("musica_sim_ensemble_add: launch failed: %s", hipGetErrorString(e));
+    st.ens_k += count;
+    return 1;
+    ABI_CATCH("musica_sim_ensemble_add")
+}
+
+int musica_sim_ensemble_get(musica_ctx* c, uint32_t* s1, uint32_t* s2, uint32_t* realisations) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_ensemble_get: ctx is NULL");
+    StudyState& st = c->study;
+    if (!st.ens_reset) return fail("musica_sim_ensemble_get: the ensemble was never reset (musica_sim_ensemble_reset)");
+    CHECK_CTX(c);
+    const size_t px = sim_side(c) * sim_side(c);
+    std::vector<uint2> words(s1 || s2 ? px : 0);
+    if (!words.empty()) HIP_OK(hipMemcpyAsync(words.data(), st.d_ens, px * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < words.size(); i++) {
+        if (s1) s1[i] = words[i].x;
+        if (s2) s2[i] = words[i].y;
+    }
+    if (realisations) *realisations = st.ens_k;
+    return 1;
+    ABI_CATCH("musica_sim_ensemble_get")
+}
+
+// musica_sim_ensemble_result's doubles from the exact integers, one operation each in the order include/musica.h states
+// (harness.ensemble_summary restates them).
+static void ensemble_finish(const unsigned long long* r /* kEnsTotals */, uint32_t K, const musica_sim_query& q, musica_sim_ensemble_stats* o) {
+    const uint64_t n = (uint64_t)q.w * q.h, k = K;
+    memset(o, 0, sizeof(*o));
+    o->sq_bias_sum = r[0];
+    o->var_sum = r[1];
+    o->bias_sum = (int64_t)r[2];
+    o->sq_err_sum = r[3];
+    o->abs_bias_max = r[4];
+    o->var_max = r[5];
+    o->pixels = n;
+    o->realisations = K;
+    o->tiles_x = (q.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+    o->tiles_y = (q.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+    o->mean_shift = (double)o->bias_sum / (double)(k * n);
+    o->bias_rms = sqrt((double)o->sq_bias_sum / (double)(k * k * n));
+    o->noise_rms = K == 1 ? 0.0 : sqrt((double)o->var_sum / (double)(k * (k - 1) * n));
+    o->mse = 1.0 - sqrt((double)o->sq_err_sum / (double)(k * n)) / 255.0;
+    const uint64_t both = o->sq_bias_sum + o->var_sum;   // == K sq_err_sum < 2^64
+    o->bias_fraction = both == 0 ? 0.0 : (double)o->sq_bias_sum / (double)both;
+}
+
+int musica_sim_ensemble_result(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_ensemble_stats* out, uint64_t* tile_tables) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_ensemble_result", count, qs, out)) return 0;
+    StudyState& st = c->study;
+    if (!st.ens_reset || st.ens_k == 0) return fail("musica_sim_ensemble_result: the ensemble holds no realisation (musica_sim_ensemble_reset, _add)");
+    const uint32_t K = st.ens_k;
+    for (uint32_t i = 0; i < count; i++)   // sum D^2 <= 255^2 K^2 w h must fit u64; every other sum is smaller
+        if (((unsigned __int128)65025u * K * K * qs[i].w * qs[i].h) >> 64)
+            return fail("musica_sim_ensemble_result: query %u: 65025 * %u^2 * %u * %u does not fit 64 bits", i, K, qs[i].w, qs[i].h);
+    const size_t nw = sim_side(c);
+    std::vector<EnsQueryDev> hq(count);
+    size_t tiles = 0;
+    int max_tiles = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        EnsQueryDev& d = hq[i];
+        d.s = st.d_ens + (size_t)q.ay * nw + q.ax;
+        d.b = st.slot[q.slot] + (size_t)q.by * nw + q.bx;
+        d.s_pitch = d.b_pitch = (int)nw;
+        d.w = (int)q.w;
+        d.h = (int)q.h;
+        d.tiles_x = (d.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+        d.tiles_y = (d.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+        d.tile_base = tiles;
+        tiles += (size_t)d.tiles_x * d.tiles_y;
+        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+    }
+    CHECK_CTX(c);
+    if (!(ensure(c, &st.d_ens_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_ens_out, (size_t)MUSICA_SIM_MAX_QUERIES * kEnsTotals)))
+        return fail("musica_sim_ensemble_result: device allocation failed");
+    if (tiles > st.ens_tiles_cap) {   // sized for the call: the largest call so far
+        HIP_OK(drelease(c, &st.d_ens_tiles));
+        st.ens_tiles_cap = 0;
+        if (!dalloc(c, &st.d_ens_tiles, 2 * tiles)) return fail("musica_sim_ensemble_result: device allocation of %zu tile pairs failed", tiles);
+        st.ens_tiles_cap = tiles;
+    }
+    HIP_OK(hipMemcpyAsync(st.d_ens_q, hq.data(), count * sizeof(EnsQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_ens_out, 0, (size_t)count * kEnsTotals * sizeof(unsigned long long), c->stream));
+    launch_ens_stats(c->stream, st.d_ens_q, (int)count, max_tiles, K, st.d_ens_tiles, st.d_ens_out);
+    HIP_OK(hipGetLastError());
+    std::vector<unsigned long long> res((size_t)count * kEnsTotals);
+    HIP_OK(hipMemcpyAsync(res.data(), st.d_ens_out, res.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (tile_tables) HIP_OK(hipMemcpyAsync(tile_tables, st.d_ens_tiles, 2 * tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the results are read by then
+    for (uint32_t i = 0; i < count; i++) ensemble_finish(res.data() + (size_t)i * kEnsTotals, K, qs[i], out + i);
+    return 1;
+    ABI_CATCH("musica_sim_ensemble_result")
 }
 
 // ---- alterations of the study (musica_alter_*, include/musica.h; kernels_alteration.hip) ----------------------------------------------

@@ -451,6 +451,94 @@ def multiscale_similarities(a, b, scales):
     return out
 
 
+# ---- bias and noise over many realisations: ensemble statistics (musica_sim_ensemble_*; not in the reference) ----
+# A noise row scores ONE random draw, which cannot tell a systematic change of the output (a tone curve that moved with the gradation
+# histogram, lost detail) from amplified noise, nor say how far the score moves under another seed. Over K realisations a_k of the same
+# alteration the per-pixel sums S1 = sum a_k and S2 = sum a_k^2 give both: D = S1 - K b is K times the bias against the unaltered result
+# b, V = K S2 - S1^2 is K (K - 1) times the sample variance. All of it is integer arithmetic; these functions are the contract of
+# musica_sim_ensemble_result (include/musica.h).
+ENSEMBLE_KEYS = mp.ENSEMBLE_METRICS + mp.ENSEMBLE_INTEGERS   # a study row's ensemble dicts; ensemble_statistics adds "tile_tables"
+
+
+def ensemble_stream(ordinal, j):
+    """The Philox stream of realisation j < 1024 of the study row with that ordinal (1, 2, ..): 1024 ordinal + j. Ordinals start at 1,
+    so these streams never meet a row's own stream, its ordinal (a study has far fewer than 1024 rows)."""
+    ordinal, j = int(ordinal), int(j)
+    if ordinal < 1 or not 0 <= j < mp.SIM_ENSEMBLE_MAX:
+        raise ValueError("ensemble_stream: ordinal %d must be >= 1 and the realisation %d in 0 .. %d" % (ordinal, j, mp.SIM_ENSEMBLE_MAX - 1))
+    return mp.SIM_ENSEMBLE_MAX * ordinal + j
+
+
+def ensemble_summary(sq_bias_sum, var_sum, sq_err_sum, bias_sum, abs_bias_max, var_max, realisations, w, h):
+    """A query's ENSEMBLE_KEYS dict from its exact integers: the doubles one IEEE operation each in include/musica.h's order, every
+    integer converted to double first. The device and the host studies both call this, so they agree to the last bit."""
+    ints = [int(v) for v in (sq_bias_sum, var_sum, sq_err_sum, bias_sum, abs_bias_max, var_max)]
+    k, n = int(realisations), int(w) * int(h)
+    sq_bias, var, sq_err, bias = ints[:4]
+    if k * sq_err != sq_bias + var:
+        raise ValueError("ensemble_summary: K sq_err_sum != sq_bias_sum + var_sum (%d * %d, %d + %d)" % (k, sq_err, sq_bias, var))
+    t = mp.SIM_TILE
+    out = {"mean_shift": float(bias) / float(k * n),
+           "bias_rms": math.sqrt(float(sq_bias) / float(k * k * n)),
+           "noise_rms": 0.0 if k == 1 else math.sqrt(float(var) / float(k * (k - 1) * n)),
+           "mse": 1.0 - math.sqrt(float(sq_err) / float(k * n)) / 255.0,
+           "bias_fraction": 0.0 if sq_bias + var == 0 else float(sq_bias) / float(sq_bias + var)}
+    out.update(zip(mp.ENSEMBLE_INTEGERS, ints + [n, k, (int(w) + t - 1) // t, (int(h) + t - 1) // t]))
+    return out
+
+
+def ensemble_statistics(outs, b, region):
+    """musica_sim_ensemble_result's numbers of one query, restated: outs a (K, H, W) stack of uint8 outputs (the realisations), b the full
+    uint8 reference plane, region = (ax, ay, bx, by, w, h). Integer dtype throughout: S1, S2, D, V and the error term per pixel and the
+    tile sums in int64 (a tile's sum D^2 <= 64^2 * 261120^2 < 2^63), the totals as Python ints summed over the tiles. Returns the
+    ENSEMBLE_KEYS dict (ensemble_summary) plus "tile_tables": (tiles_y, tiles_x, 2) uint64, (sum D^2, sum V) per 64 x 64 tile. ValueError
+    where the C call refuses: no or more than SIM_ENSEMBLE_MAX realisations, w < 7 or h < 7, a region that leaves either plane,
+    65025 K^2 w h >= 2^64."""
+    outs, b = np.asarray(outs), np.asarray(b)
+    if outs.ndim != 3 or b.ndim != 2 or outs.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("ensemble_statistics needs a (K, H, W) uint8 stack and a 2-D uint8 plane, got %r %s and %r %s" % (outs.shape, outs.dtype, b.shape, b.dtype))
+    k = outs.shape[0]
+    if not 1 <= k <= mp.SIM_ENSEMBLE_MAX:
+        raise ValueError("%d realisations out of range [1, %d]" % (k, mp.SIM_ENSEMBLE_MAX))
+    ax, ay, bx, by, w, h = (int(v) for v in region)
+    if w < 7 or h < 7:
+        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
+    if min(ax, ay, bx, by) < 0 or ax + w > outs.shape[2] or ay + h > outs.shape[1] or bx + w > b.shape[1] or by + h > b.shape[0]:
+        raise ValueError("region (%d, %d) / (%d, %d) + %d x %d leaves the planes" % (ax, ay, bx, by, w, h))
+    if 65025 * k * k * w * h >= 2 ** 64:
+        raise ValueError("65025 * %d^2 * %d * %d does not fit 64 bits" % (k, w, h))
+    a = outs[:, ay:ay + h, ax:ax + w].astype(np.int64)
+    cb = b[by:by + h, bx:bx + w].astype(np.int64)
+    s1, s2 = a.sum(axis=0), (a * a).sum(axis=0)
+    d = s1 - k * cb
+    v = k * s2 - s1 * s1
+    e = s2 - 2 * cb * s1 + k * cb * cb
+    t = mp.SIM_TILE
+
+    def tiles(x):
+        return np.add.reduceat(np.add.reduceat(x, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
+
+    tile_tables = np.stack([tiles(d * d), tiles(v)], axis=-1).astype(np.uint64)
+    out = ensemble_summary(sum(int(x) for x in tile_tables[..., 0].ravel()), sum(int(x) for x in tile_tables[..., 1].ravel()),
+                           sum(int(x) for x in tiles(e).ravel()), sum(int(x) for x in tiles(d).ravel()), int(np.abs(d).max()), int(v.max()), k, w, h)
+    out["tile_tables"] = tile_tables
+    return out
+
+
+def ensemble_maps(tile_tables, w, h, realisations):
+    """Two (tiles_y, tiles_x) uint8 maps of a w x h region's ensemble tile table, one pixel per tile: the tile's bias rms,
+    sqrt(sum D^2 / (K^2 pixels)), and its noise rms, sqrt(sum V / (K (K - 1) pixels)) (0 for K == 1), in gray levels, rounded."""
+    tt = np.asarray(tile_tables)
+    ny, nx, t, k = tt.shape[0], tt.shape[1], mp.SIM_TILE, int(realisations)
+    bias, noise = np.zeros((ny, nx), dtype=np.uint8), np.zeros((ny, nx), dtype=np.uint8)
+    for ty in range(ny):
+        for tx in range(nx):
+            px = (min(h, t * ty + t) - t * ty) * (min(w, t * tx + t) - t * tx)
+            bias[ty, tx] = min(255, int(round(math.sqrt(int(tt[ty, tx, 0]) / (k * k * px)))))
+            noise[ty, tx] = min(255, int(round(math.sqrt(int(tt[ty, tx, 1]) / (k * (k - 1) * px))))) if k > 1 else 0
+    return bias, noise
+
+
 # ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
 
 def vendor_to_u8(pixels):
@@ -571,7 +659,7 @@ def roi_symmetry(shape):
 class Runner:
     """Processes raw images to the 8-bit output the reference's saveOutImage writes (margin cropped)."""
 
-    def __init__(self, image_size, levels=0, device=0, use_cli=False, device_metrics=False, device_alterations=False):
+    def __init__(self, image_size, levels=0, device=0, use_cli=False, device_metrics=False, device_alterations=False, ensemble_batch=8):
         if use_cli and device_alterations:
             raise ValueError("device alterations write the library's resident input buffer: the CLI path has none")
         if use_cli and device_metrics:
@@ -579,6 +667,10 @@ class Runner:
         self.n, self.levels, self.device, self.use_cli = image_size, levels, device, use_cli
         self.device_alterations = device_alterations   # run_study generates the alterations on the device (musica_alter); implies device_metrics
         self.device_metrics = device_metrics or device_alterations   # run_study scores on the device (musica_sim_compare) instead of with numpy
+        self.ensemble_batch = int(ensemble_batch)       # images per step of the ensemble context (run_study's ensemble=K)
+        if self.ensemble_batch < 1:
+            raise ValueError("ensemble_batch %d must be at least 1" % self.ensemble_batch)
+        self.ensemble_proc = None                       # a second context of the runner's size, levels and device, created on first use
         self.proc = None
         if not use_cli:
             self.proc = mp.MusicaProcessing(device=device)
@@ -619,9 +711,21 @@ class Runner:
         subprocess.run(cmd, check=True, capture_output=True)
         return read_bmp_gray(out_path)
 
+    def ensemble_context(self, realisations):
+        """The batch context run_study's ensembles run on, created on first use with a batch of min(ensemble_batch, realisations)."""
+        if self.ensemble_proc is None:
+            proc = mp.MusicaProcessing(device=self.device)
+            if not proc.init(self.n, levels=self.levels, batch=max(1, min(self.ensemble_batch, int(realisations)))):
+                raise RuntimeError("musica_create failed: " + mp.last_error())
+            self.ensemble_proc = proc
+        return self.ensemble_proc
+
     def close(self):
         if self.proc:
             self.proc.cleanup()
+        if self.ensemble_proc:
+            self.ensemble_proc.cleanup()
+            self.ensemble_proc = None
 
 
 def read_bmp_gray(path):
@@ -646,7 +750,7 @@ TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "referenc
 
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
-              tone=False, displacement=0, displacement_tiles=False, scales=0):
+              tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -690,7 +794,19 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     registered_reference_scales; present exactly where the original is and None exactly where it is None. Each is a dict of SCALES_KEYS:
     ms_ssim, scales and the lists ssim, cs, lum, mse of length `scales`, a comparison using min(S, max_scales of its region). On the
     device the row's queries go through one musica_sim_multiscale call per distinct scale count; on the host the restatement scores
-    the same crops. With scales=0 the rows and the launches are exactly as before."""
+    the same crops. With scales=0 the rows and the launches are exactly as before.
+
+    ensemble: K > 0 (at most SIM_ENSEMBLE_MAX; needs runner.device_alterations, else ValueError) repeats every noise alteration K times and
+    splits the change of the output into bias and noise (ensemble_statistics). Every row gains "ensemble": None for rows without noise,
+    for c_sh_*, gn_* and pn_* a dict of "direct" (the full frame against the unaltered result, ENSEMBLE_KEYS), "registered" (the
+    collimator's region; present exactly where the row's "registered" is, else None), "realisations" (K) and "per_realisation": "mean"
+    and "std" (ddof = 1, 0 for K = 1) over the K realisations of the five SIM_METRICS of the direct comparison. The row's own keys and
+    launches are untouched: the ensemble runs after the row is complete on a second context owned by the runner
+    (runner.ensemble_context, batch runner.ensemble_batch) that holds the raw image as its source and the unaltered result in its slot 0.
+    Realisation j of the row with ordinal o draws from the study's seed and the stream ensemble_stream(o, j); B realisations go through
+    one step, musica_sim_ensemble_add and one musica_sim_compare call, and one musica_sim_ensemble_result call ends the row.
+    ensemble_tiles: the "direct" dict also carries "tile_tables" ((tiles_y, tiles_x, 2) uint64) and "size", what ensemble_maps draws.
+    With ensemble=0 nothing is created and the rows are exactly as before."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     if vendor is not None:
@@ -711,6 +827,13 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
     if scales:
         keys += tuple(SCALE_ROW_KEYS[k] for k in keys if k in SCALE_ROW_KEYS)
+    ensemble = int(ensemble)
+    if ensemble and not 1 <= ensemble <= mp.SIM_ENSEMBLE_MAX:
+        raise ValueError("ensemble %d is not in 1 .. %d" % (ensemble, mp.SIM_ENSEMBLE_MAX))
+    if ensemble and not getattr(runner, "device_alterations", False):
+        raise ValueError("an ensemble repeats the device's noise alterations: it needs a runner with device_alterations")
+    if ensemble:
+        keys += ("ensemble",)
     shutters = scaled(SHUTTERS, n) if shutters is None else shutters
     translations = scaled(TRANSLATIONS, n) if translations is None else translations
     rotations = ROTATIONS if rotations is None else rotations
@@ -779,7 +902,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         tt = displacement_tile_tables(a, b, region, displacement)
         return shift_summary(tt.astype(np.int64).sum(axis=(0, 1)), region, tt.shape[0] * tt.shape[1], displacement_tiles_off(tt), tt)
 
-    first = {"alteration": "unaltered", "registered": None, "registered_tone": None, "registered_shift": None, "registered_scales": None}
+    first = {"alteration": "unaltered", "registered": None, "registered_tone": None, "registered_shift": None, "registered_scales": None,
+             "ensemble": None}
     if device:
         runner.proc.sim_capture(SLOT_UNALTERED)
         queries = [(0, SLOT_UNALTERED) + full]
@@ -822,6 +946,41 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     if alter_on_device:
         runner.proc.alter_set_source(raw)
         seed = int(rng.integers(0, 2 ** 63))
+    noisy = {}   # row name -> (ordinal, alter(proc, stream, image_index)): the noise rows, for their ensembles
+    if ensemble:
+        eproc = runner.ensemble_context(ensemble)
+        eproc.alter_set_source(raw)
+        for i in range(eproc.batch):     # every image of the batch holds a valid input, whatever the last chunk leaves unused
+            eproc.alter_none(i)
+        eproc.sim_set_reference(SLOT_UNALTERED, runner.proc.sim_get_reference(SLOT_UNALTERED))
+
+    def ensemble_of(name, registered):
+        """The "ensemble" value of a completed row: None unless it is a noise row. registered: the region of its registered comparison
+        (None: the row has none)."""
+        if name not in noisy:
+            return None
+        ordinal, alter = noisy[name]
+        regions = [full] + ([registered] if registered is not None else [])
+        per = {k: [] for k in mp.SIM_METRICS}
+        eproc.sim_ensemble_reset()
+        for j0 in range(0, ensemble, eproc.batch):
+            count = min(eproc.batch, ensemble - j0)
+            for i in range(count):
+                alter(eproc, ensemble_stream(ordinal, j0 + i), i)
+            if not eproc.execute_device():
+                raise RuntimeError("musica_execute_device failed: " + mp.last_error())
+            eproc.sim_ensemble_add(0, count)
+            for r in eproc.sim_compare([(i, SLOT_UNALTERED) + full for i in range(count)]):
+                for k in mp.SIM_METRICS:
+                    per[k].append(r[k])
+        res = eproc.sim_ensemble_result([(0, SLOT_UNALTERED) + r for r in regions], tiles=ensemble_tiles)
+        dicts = [ensemble_summary(*[r[k] for k in ("sq_bias_sum", "var_sum", "sq_err_sum", "bias_sum", "abs_bias_max", "var_max", "realisations")],
+                                  g[4], g[5]) for r, g in zip(res, regions)]
+        if ensemble_tiles:
+            dicts[0]["tile_tables"], dicts[0]["size"] = res[0]["tile_tables"], (full[4], full[5])
+        return {"direct": dicts[0], "registered": dicts[1] if registered is not None else None, "realisations": ensemble,
+                "per_realisation": {"mean": {k: float(np.mean(v)) for k, v in per.items()},
+                                    "std": {k: float(np.std(v, ddof=1)) if ensemble > 1 else 0.0 for k, v in per.items()}}}
 
     def add(name, host, dev, reg=None, region=None, slot=None, plane=None):
         """One row of study() below, scored the way the runner's mode asks for."""
@@ -876,6 +1035,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
                 if crop is not None:
                     row["registered_shift"] = shift_on_host(alt, plane(), _inset(region(), displacement))
         row["mean_cnr"] = runner.mean_cnr() if runner.proc else None
+        if ensemble:   # device path (an ensemble needs device alterations): `registered` is the row's own (slot, region)
+            row["ensemble"] = ensemble_of(name, registered[1] if registered else None)
         rows.append({k: row[k] for k in keys})
 
     def moved_slot(d, move_reference, moved_unalt):
@@ -897,7 +1058,9 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         row's ordinal in the study as their stream; the d4 rows draw nothing and take no ordinal."""
         p, ordinal = runner.proc, itertools.count(1)
         for s in shutters:
-            yield ("c_sh_%d" % s, lambda: apply_collimator(raw, s, s, rng), lambda k=next(ordinal): p.alter_collimator(s, s, seed, k),
+            k = next(ordinal)
+            noisy["c_sh_%d" % s] = (k, lambda q, stream, i: q.alter_collimator(s, s, seed, stream, i))
+            yield ("c_sh_%d" % s, lambda: apply_collimator(raw, s, s, rng), lambda k=k: p.alter_collimator(s, s, seed, k),
                    lambda a, u: register_collimator(a, u, s), lambda: roi_collimator(shape, s), lambda: SLOT_UNALTERED, lambda: unalt)
         for name, tx, ty, register, roi in (("t_x_%d", 1, 0, register_translation_x, roi_translation_x), ("t_y_%d", 0, 1, register_translation_y, roi_translation_y)):
             for t in translations:
@@ -909,9 +1072,13 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             yield ("r_%d" % d, lambda: clamp_rotate(raw, d), lambda: p.alter_rotate(d), lambda a, u: register_rotation(a, u, d),
                    lambda: roi_rotation(shape, d), lambda: moved_slot(d, p.sim_rotate_reference, rotated_reference), lambda: rotated_reference(unalt, d))
         for sg in sigmas:
-            yield ("gn_%s" % sg, lambda: add_gaussian_noise(raw, 0.0, sg, rng), lambda k=next(ordinal): p.alter_gaussian(0.0, sg, seed, k))
+            k = next(ordinal)
+            noisy["gn_%s" % sg] = (k, lambda q, stream, i: q.alter_gaussian(0.0, sg, seed, stream, i))
+            yield ("gn_%s" % sg, lambda: add_gaussian_noise(raw, 0.0, sg, rng), lambda k=k: p.alter_gaussian(0.0, sg, seed, k))
         for f in factors:
-            yield ("pn_%s" % f, lambda: apply_quantum_noise(raw, f, rng), lambda k=next(ordinal): p.alter_poisson(f, seed, k))
+            k = next(ordinal)
+            noisy["pn_%s" % f] = (k, lambda q, stream, i: q.alter_poisson(f, seed, stream, i))
+            yield ("pn_%s" % f, lambda: apply_quantum_noise(raw, f, rng), lambda k=k: p.alter_poisson(f, seed, k))
         for e in symmetries:
             yield ("d4_%d" % e, lambda: apply_symmetry(raw, e), lambda: p.alter_symmetry(e), lambda a, u: register_symmetry(a, u, e),
                    lambda: roi_symmetry(shape), lambda: moved_slot(e, p.sim_transform_reference, apply_symmetry), lambda: apply_symmetry(unalt, e))
@@ -942,6 +1109,12 @@ SHIFT_CSV_HEADER = ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in SH
 SCALE_CSV_GROUPS = tuple((SCALE_ROW_KEYS[k], g) for k, g in (("direct", "altered vs unaltered"), ("registered", "registered vs unaltered"),
                                                                ("reference", "altered vs reference"), ("registered_reference", "registered vs reference")))
 SCALE_CSV_METRICS = ("ssim", "cs", "mse")   # per scale 0 .. 4, behind ms_ssim and scales
+
+
+ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
+ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
+ENSEMBLE_CSV_HEADER = ['raw file', 'alteration', 'realisations'] + ['%s %s' % (g, m) for g in ("direct", "registered") for _, m in ENSEMBLE_CSV_NAMES] + \
+                      ['per-realisation %s %s' % (m, w) for m in ENSEMBLE_CSV_METRICS for w in ("mean", "std")]   # ensemble.csv
 
 
 def scale_csv_header(with_reference):
@@ -991,7 +1164,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     included, the SHIFT_KEYS of the direct and of the registered comparison; cells without a comparison are empty.
 
     Studies run with scales (rows[0] has "direct_scales") also get scale_robustness.csv (scale_csv_header): one line per row, the
-    unaltered one included; cells without a comparison, and of scales beyond a comparison's count, are empty."""
+    unaltered one included; cells without a comparison, and of scales beyond a comparison's count, are empty.
+
+    Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
+    mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
+    and standard deviation over the realisations of the five similarity metrics."""
     os.makedirs(out_dir, exist_ok=True)
     ovds = []
 
@@ -1066,6 +1243,41 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
             for raw_name, rows in scored:
                 for r in rows:
                     ws.writerow([raw_name, r["alteration"]] + [c for key, _ in groups for c in _scale_csv_cells(r.get(key))])
+    ensembles = [(raw_name, rows) for raw_name, rows in studies if rows and "ensemble" in rows[0]]
+    if ensembles:
+        with open(os.path.join(out_dir, "ensemble.csv"), "w", newline="") as fe:
+            we = csv.writer(fe)
+            we.writerow(ENSEMBLE_CSV_HEADER)
+            for raw_name, rows in ensembles:
+                for r in rows:
+                    e = r["ensemble"]
+                    if e is None:
+                        continue
+                    cells = []
+                    for key in ("direct", "registered"):
+                        cells += [""] * len(ENSEMBLE_CSV_NAMES) if e[key] is None else [e[key][k] for k, _ in ENSEMBLE_CSV_NAMES]
+                    per = e["per_realisation"]
+                    we.writerow([raw_name, r["alteration"], e["realisations"]] + cells + [per[w][k] for k in mp.SIM_METRICS for w in ("mean", "std")])
+
+
+def write_ensemble_maps(studies, out_dir):
+    """Two 8-bit BMPs per noise row of studies run with ensemble_tiles (ensemble_maps: one pixel per 64 x 64 tile of the full frame):
+    <raw>_<alteration>_bias.bmp, the tile's bias rms against the unaltered result, and <raw>_<alteration>_noise.bmp, its noise rms, in
+    gray levels. Returns the paths written."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for raw_name, rows in studies:
+        stem = os.path.splitext(os.path.basename(raw_name.replace("\\", "/")))[0]
+        for r in rows:
+            e = r.get("ensemble")
+            if e is None or "tile_tables" not in e["direct"]:
+                continue
+            for what, img in zip(("bias", "noise"), ensemble_maps(e["direct"]["tile_tables"], *e["direct"]["size"], e["realisations"])):
+                path = os.path.join(out_dir, "%s_%s_%s.bmp" % (stem, r["alteration"], what))
+                if not mp.write_bmp_gray(path, img):
+                    raise RuntimeError("writing %s failed: %s" % (path, mp.last_error()))
+                written.append(path)
+    return written
 
 
 def write_displacement_maps(studies, out_dir):
@@ -1180,7 +1392,21 @@ def main(argv=None):
                     help="say at which spatial scale the output changed: SSIM, its contrast-structure factor and mse at S (1 .. 5) scales of "
                          "2 x 2 pooling and their MS-SSIM product, per comparison, written to scale_robustness.csv; on the GPU with "
                          "--device-metrics / --device-alterations (musica_sim_multiscale)")
+    ap.add_argument("--ensemble", type=int, default=0, metavar="K",
+                    help="with --device-alterations: repeat every noise alteration K (1 .. 1024) times and split the change of the output into "
+                         "bias against the unaltered result and noise, per pixel, written to ensemble.csv (musica_sim_ensemble_*)")
+    ap.add_argument("--ensemble-batch", type=int, default=8, metavar="B", help="with --ensemble: realisations per step of the ensemble context")
+    ap.add_argument("--ensemble-maps", metavar="DIR",
+                    help="with --ensemble: two 8-bit BMPs per noise row into DIR, one pixel per 64 x 64 tile: the tile's bias rms and its noise rms")
     args = ap.parse_args(argv)
+    if args.ensemble and not 1 <= args.ensemble <= mp.SIM_ENSEMBLE_MAX:
+        ap.error("--ensemble takes a count of 1 .. %d realisations" % mp.SIM_ENSEMBLE_MAX)
+    if args.ensemble and not args.device_alterations:
+        ap.error("--ensemble repeats the device's noise alterations: give --device-alterations")
+    if args.ensemble_maps and not args.ensemble:
+        ap.error("--ensemble-maps draws what --ensemble measures: give a count")
+    if args.ensemble_batch < 1:
+        ap.error("--ensemble-batch takes at least 1")
     if args.scales and not 1 <= args.scales <= mp.SIM_MAX_SCALES:
         ap.error("--scales takes a count of 1 .. %d" % mp.SIM_MAX_SCALES)
     if args.displacement and not 1 <= args.displacement <= mp.SIM_MAX_RADIUS:
@@ -1206,11 +1432,14 @@ def main(argv=None):
     if args.reference:
         from .dicom import read_dicom_gray
         vendor = read_dicom_gray(args.reference)
-    runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics, device_alterations=args.device_alterations)
+    runner = Runner(args.size, args.levels, use_cli=args.cli, device_metrics=args.device_metrics, device_alterations=args.device_alterations,
+                    **({"ensemble_batch": args.ensemble_batch} if args.ensemble else {}))
     shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
                  {"displacement": args.displacement} if args.displacement else {}
     if args.scales:
         shift_args["scales"] = args.scales
+    if args.ensemble:
+        shift_args.update(ensemble=args.ensemble, ensemble_tiles=bool(args.ensemble_maps))
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)
@@ -1222,6 +1451,8 @@ def main(argv=None):
     write_studies_csvs(studies, args.out, mean_cnr=not args.cli)
     if args.displacement_maps:
         write_displacement_maps(studies, args.displacement_maps)
+    if args.ensemble_maps:
+        write_ensemble_maps(studies, args.ensemble_maps)
     print("wrote %d alterations to %s" % (sum(len(rows) - 1 for _, rows in studies), args.out))
     return 0
 

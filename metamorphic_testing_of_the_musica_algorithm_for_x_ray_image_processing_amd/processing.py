@@ -183,6 +183,25 @@ class SimScalesResult(C.Structure):
         return d
 
 
+SIM_ENSEMBLE_MAX = 1024     # MUSICA_SIM_ENSEMBLE_MAX
+ENSEMBLE_METRICS = ("mean_shift", "bias_rms", "noise_rms", "mse", "bias_fraction")                      # the doubles of an ensemble result
+ENSEMBLE_INTEGERS = ("sq_bias_sum", "var_sum", "sq_err_sum", "bias_sum", "abs_bias_max", "var_max",      # its exact integers
+                     "pixels", "realisations", "tiles_x", "tiles_y")
+
+
+class SimEnsembleResult(C.Structure):
+    """musica_sim_ensemble_stats: the ensemble statistics of one query (harness.ensemble_statistics' keys)."""
+    _fields_ = [(n, C.c_double) for n in ENSEMBLE_METRICS] + \
+               [("sq_bias_sum", C.c_uint64), ("var_sum", C.c_uint64), ("sq_err_sum", C.c_uint64), ("bias_sum", C.c_int64),
+                ("abs_bias_max", C.c_uint64), ("var_max", C.c_uint64), ("pixels", C.c_uint64),
+                ("realisations", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32)]
+
+    def as_dict(self):
+        d = {n: float(getattr(self, n)) for n in ENSEMBLE_METRICS}
+        d.update({n: int(getattr(self, n)) for n in ENSEMBLE_INTEGERS})
+        return d
+
+
 # musica_out_format: what export_out writes per image
 OUT_U8, OUT_GRADED_F32 = 0, 1
 OUT_FORMAT_COUNT = 2
@@ -311,6 +330,10 @@ ABI = {
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
     "musica_sim_multiscale": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimScalesResult)]),
+    "musica_sim_ensemble_reset": (C.c_int, [_VP]),
+    "musica_sim_ensemble_add": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
+    "musica_sim_ensemble_result": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimEnsembleResult), C.POINTER(C.c_uint64)]),
+    "musica_sim_ensemble_get": (C.c_int, [_VP, _U32P, _U32P, _U32P]),
     "musica_alter_set_source": (C.c_int, [_VP, _U16P]),
     "musica_alter": (C.c_int, [_VP, C.c_uint32, C.POINTER(Alteration)]),
     "musica_alter_draws": (C.c_int, [_VP, C.POINTER(Alteration), C.POINTER(C.c_int32)]),
@@ -746,6 +769,46 @@ class MusicaProcessing:
         if t.shape != (256,):
             raise ValueError("expected a table of 256 uint8 values, got %r" % (t.shape,))
         self._ok(self._lib.musica_sim_remap_reference(self._h, int(dst_slot), int(src_slot), t.ctypes.data_as(_U8P)), "musica_sim_remap_reference")
+
+    # ---- ensemble noise statistics (musica_sim_ensemble_*) --------------------------------------
+    def sim_ensemble_reset(self):
+        """Zeroes the per-pixel accumulators S1 = sum a, S2 = sum a^2 and the realisation count, on the context's stream."""
+        self._ok(self._lib.musica_sim_ensemble_reset(self._h), "musica_sim_ensemble_reset")
+
+    def sim_ensemble_add(self, first=0, count=None):
+        """Adds the current 8-bit outputs of images first .. first + count - 1 (default: the rest of the batch) as that many realisations;
+        enqueued on the context's stream, returns without waiting. At most SIM_ENSEMBLE_MAX realisations between two resets."""
+        count = self.batch - int(first) if count is None else int(count)
+        self._ok(self._lib.musica_sim_ensemble_add(self._h, int(first), count), "musica_sim_ensemble_add")
+
+    def sim_ensemble_result(self, queries, tiles=False):
+        """queries as sim_compare's (image_index is checked and not used: side a is the ensemble), all in one launch. Returns one dict per
+        query: the doubles ENSEMBLE_METRICS and the exact ENSEMBLE_INTEGERS (== harness.ensemble_statistics); with tiles=True
+        "tile_tables": the (tiles_y, tiles_x, 2) uint64 pairs (sum D^2, sum V) of the 64 x 64 tiles."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimEnsembleResult * max(len(qs), 1))()
+        tile = None
+        if tiles:
+            per = [((q.h + SIM_TILE - 1) // SIM_TILE) * ((q.w + SIM_TILE - 1) // SIM_TILE) * 2 for q in qs]
+            tile = np.zeros(max(sum(per), 1), dtype=np.uint64)
+        self._ok(self._lib.musica_sim_ensemble_result(self._h, len(qs), arr, res,
+                                                      tile.ctypes.data_as(C.POINTER(C.c_uint64)) if tile is not None else None),
+                 "musica_sim_ensemble_result")
+        out = [res[i].as_dict() for i in range(len(qs))]
+        first = 0
+        for i, d in enumerate(out):
+            if tiles:
+                d["tile_tables"] = tile[first:first + per[i]].reshape(d["tiles_y"], d["tiles_x"], 2)
+                first += per[i]
+        return out
+
+    def sim_ensemble_get(self):
+        """(S1, S2, K): the two (N - 20, N - 20) uint32 accumulator planes and the realisations added since the last reset. S1 / K is the
+        per-pixel mean image, (K S2 - S1^2) / (K (K - 1)) the per-pixel sample variance."""
+        n = self.imageSize - 2 * OUT_MARGIN
+        s1, s2, k = np.empty((n, n), dtype=np.uint32), np.empty((n, n), dtype=np.uint32), C.c_uint32()
+        self._ok(self._lib.musica_sim_ensemble_get(self._h, s1.ctypes.data_as(_U32P), s2.ctypes.data_as(_U32P), C.byref(k)), "musica_sim_ensemble_get")
+        return s1, s2, int(k.value)
 
     # ---- alterations of the metamorphic study (musica_alter_*) ---------------------------------
     # Each alter_* writes image `image_index` of the resident input buffer (follow it with execute_device()); the arguments mirror
