@@ -502,7 +502,8 @@ typedef struct musica_sim_ensemble_stats {
     uint32_t realisations;                    /* K */
     uint32_t tiles_x, tiles_y;                /* ceil(w / 64), ceil(h / 64) */
 } musica_sim_ensemble_stats;
-/* Zeroes the accumulators and K, on the context's stream. The accumulators ((N - 20)^2 words of 8 bytes) are allocated by the first call. */
+/* Zeroes the accumulators and K, on the context's stream, and drops any tracked regions (musica_sim_ensemble_track). The accumulators
+ * ((N - 20)^2 words of 8 bytes) are allocated by the first call. */
 int musica_sim_ensemble_reset(musica_ctx* ctx);
 /* Adds the current outputs of batch images first .. first + count - 1 and sets K += count. Enqueued on the context's stream behind whatever
  * is there (a step, musica_execute_device); returns without waiting. Refused before anything is enqueued: a NULL context, count == 0 or
@@ -518,6 +519,55 @@ int musica_sim_ensemble_result(musica_ctx* ctx, uint32_t count, const musica_sim
 /* The (N - 20)^2 accumulators S1 and S2 to the host, top-down rows, and K; synchronous. Any of the three pointers may be NULL. Refused when
  * the ensemble was never reset. */
 int musica_sim_ensemble_get(musica_ctx* ctx, uint32_t* s1, uint32_t* s2, uint32_t* realisations);
+
+/* The texture of the output noise: its spatial auto-covariance over integer lags, taken over the realisations of an ensemble
+ * (harness.ensemble_covariance). The per-pixel statistics above say how strong the noise is; neighbour correlations, the correlation area
+ * and the noise power spectrum (Wiener-Khinchin: harness.noise_power_spectrum) follow from this table. a_k(p), k = 1 .. K, is the 8-bit
+ * output of realisation k at pixel p of the (N - 20)^2 plane, exactly the bytes musica_sim_ensemble_add adds. R is the radius,
+ * 1 .. MUSICA_SIM_MAX_RADIUS, S = 2 R + 1. A tracked region is the a-side rectangle (ax, ay, w, h) of a musica_sim_query, n = w h. The lags
+ * are d = (dx, dy) with dy = 0 .. R and dx = -R .. R: a table has (R + 1) x S entries, row dy, column dx + R. The entries with dy = 0 and
+ * dx < 0 are computed by the same formula as the others; they differ from their mirror only by edge terms. All sums over p in the region;
+ * p + d may leave the region but not the plane:
+ *   P(d) = sum_k sum_p a_k(p) a_k(p + d)     accumulated while realisations are added
+ *   U(d) = sum_p S1(p) S1(p + d)             from the ensemble's accumulators, at result time
+ *   C(d) = K P(d) - U(d)                     signed 64-bit
+ *        = K^2 n x (the population covariance at lag d, about the per-pixel ensemble mean).
+ * Every lag covers the same n pixels, so the region grown by R to the left and to the right and by R downwards must lie inside the plane:
+ * a region whose grown window leaves it is refused, the caller insets. C(0, 0) == var_sum of musica_sim_ensemble_result for the same region,
+ * exactly. Tiles are musica_sim_displace's: 64 x 64, anchored at the region's origin, ragged last tiles; a tile's table is the same sum
+ * over its own pixels and the tile tables of a region sum to its table. Ranges: a tile's P of one realisation is <= 64 * 64 * 255^2 =
+ * 266 342 400 < 2^28, so 16 realisations fit a u32 and 17 do not (the device keeps u64 per tile); a tile's U is <= 4096 * 261 120^2 < 2^48;
+ * |C(d)| <= 65025 K^2 w h, and a region with 65025 K^2 w h >= 2^63 is refused, with K = MUSICA_SIM_ENSEMBLE_MAX, the count an ensemble
+ * may reach (a region of 2^43 / 65025 pixels or more, 11 630^2), so that no later add can leave the range. The doubles are computed on the
+ * host from those integers, one IEEE operation each in this order (every integer converted to double first):
+ *   noise_var = C(0,0) / (K (K - 1) n), 0 when K == 1;
+ *   rho_x = C(1,0) / C(0,0) and rho_y = C(0,1) / C(0,0), both 0 when C(0,0) == 0;
+ *   corr_area = (C(0,0) + 2 sum C(d)) / C(0,0), 1 when C(0,0) == 0: the sum over the half plane dy > 0, or dy == 0 and dx > 0, in ascending
+ *   dy, then ascending dx, in f64. This is the zero-frequency noise power over the variance: 1 for white noise.
+ * All the integers are exact, and the same from call to call. */
+#define MUSICA_SIM_COV_MAX_REGIONS 4
+typedef struct musica_sim_cov_result {
+    double noise_var, rho_x, rho_y, corr_area;
+    int64_t c00;                              /* C(0, 0) == musica_sim_ensemble_result's var_sum of the region */
+    uint64_t pixels;                          /* w * h */
+    uint32_t realisations;                    /* K */
+    uint32_t radius;                          /* R */
+    uint32_t tiles_x, tiles_y;                /* ceil(w / 64), ceil(h / 64) */
+} musica_sim_cov_result;
+/* Declares `count` (1 .. MUSICA_SIM_COV_MAX_REGIONS) tracked regions for the ensemble now starting: allowed only after
+ * musica_sim_ensemble_reset and before the first add (K == 0). Uses ax, ay, w and h of each query; the other fields are checked as
+ * musica_sim_ensemble_result checks them, so the study's query arrays serve. While regions are tracked, every musica_sim_ensemble_add also
+ * enqueues the product launch for the same images, on the same stream behind the accumulation. musica_sim_ensemble_reset drops the
+ * tracking. The u64 tile tables are allocated on first use, sized for the call, and zeroed. Refused (0, musica_last_error) before any
+ * device work: NULL pointers, a radius outside 1 .. MUSICA_SIM_MAX_RADIUS, a count out of range, an ensemble never reset or with K > 0,
+ * the refusals of musica_sim_compare (w < 7 or h < 7, a region that leaves the plane, ...), a grown window that leaves the plane, the
+ * range condition above. */
+int musica_sim_ensemble_track(musica_ctx* ctx, uint32_t radius, uint32_t count, const musica_sim_query* regions);
+/* One result per tracked region, in order; synchronous. `tables` (may be NULL): count * (R + 1) * S values C(d), table i at
+ * tables + i * (R + 1) * S, row dy, column dx + R. `tile_tables` (may be NULL): the regions' tile tables C(d) back to back in region
+ * order, tiles_y * tiles_x * (R + 1) * S values each, tile-row major. Refused when ctx or results is NULL, nothing is tracked or K == 0.
+ * Changes no accumulator, no slot, no result of a step and no input image; may be called again after more adds. */
+int musica_sim_ensemble_covariance(musica_ctx* ctx, musica_sim_cov_result* results, int64_t* tables, int64_t* tile_tables);
 
 /* ---- alterations of the metamorphic study (new, not in the reference) ---- */
 

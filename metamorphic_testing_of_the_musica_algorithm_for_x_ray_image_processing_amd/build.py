@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmusica_hip.so")
 CLI = os.path.join(HERE, "musica-standalone")
 HIP_SOURCES = ["kernels_pyramid.hip", "kernels_expand_sd.hip", "kernels_analysis.hip", "kernels_gradation.hip", "kernels_clahe.hip", "kernels_bench.hip",
-               "kernels_similarity.hip", "kernels_joint.hip", "kernels_displace.hip", "kernels_scales.hip", "kernels_ensemble.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_export.hip", "musica_ctx.hip", "musica_study.hip"]
+               "kernels_similarity.hip", "kernels_joint.hip", "kernels_displace.hip", "kernels_scales.hip", "kernels_ensemble.hip", "kernels_covariance.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_export.hip", "musica_ctx.hip", "musica_study.hip"]
 CPP_SOURCES = ["musica_io.cpp"]
 HEADERS = ["musica_device.h", "kernels_common.h", "exact_math.h", "sdev_parts.h", "grad_parts.h", "launchers.h", "musica_ctx.h", os.path.join("..", "..", "include", "musica.h")]
 NO_SLP = {"kernels_analysis.hip", "kernels_expand_sd.hip"}   # kernels_expand_sd.hip: kernels_pyramid.hip's expand march again, for the launches that compute sdev in registers
@@ -134,7 +134,7 @@ def check_isa():
 
 
 def check_isa_displace():
-    """k_displace's inner loop is written with __builtin_amdgcn_udot4 and __builtin_amdgcn_alignbyte (kernels_displace.hip): four pixels per
+    """k_displace's inner loop, and k_cov_add's (kernels_covariance.hip), is written with __builtin_amdgcn_udot4 and __builtin_amdgcn_alignbyte (kernels_displace.hip): four pixels per
     multiply-add instruction. Reads the kernel's body back from the built object as check_isa does and raises RuntimeError unless it holds
     v_dot4_u32_u8: a compiler that scalarises the loop would otherwise only show as a slow kernel. Returns the counts it found."""
     body = _kernel_body("kernels_displace", lambda line: "k_displace" in line and "k_displace_fold" not in line)
@@ -143,6 +143,13 @@ def check_isa_displace():
     found = {"dot4": sum(1 for l in body if "v_dot4_u32_u8" in l), "alignbyte": sum(1 for l in body if "v_alignbyte_b32" in l)}
     if found["dot4"] < 1:
         raise RuntimeError("k_displace lost its v_dot4_u32_u8: the inner loop no longer does four pixels per instruction: %r" % (found,))
+    body = _kernel_body("kernels_covariance", lambda line: "k_cov_add" in line)
+    if not body:
+        raise RuntimeError("kernels_covariance: no code found for k_cov_add")
+    found["cov_dot4"] = sum(1 for l in body if "v_dot4_u32_u8" in l)
+    found["cov_alignbyte"] = sum(1 for l in body if "v_alignbyte_b32" in l)
+    if found["cov_dot4"] < 1:
+        raise RuntimeError("k_cov_add lost its v_dot4_u32_u8: the inner loop no longer does four pixels per instruction: %r" % (found,))
     return found
 
 

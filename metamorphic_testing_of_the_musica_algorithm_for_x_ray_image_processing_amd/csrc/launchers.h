@@ -248,6 +248,24 @@ void launch_ens_add(hipStream_t st, const float* graded, const LevelDesc& l0, in
 // (all written); totals: count x kEnsTotals u64, zeroed by the caller.
 void launch_ens_stats(hipStream_t st, const EnsQueryDev* d_qs, int count, int max_tiles, uint32_t K, unsigned long long* tile_tables,
                       unsigned long long* totals);
+// kernels_covariance.hip: musica_sim_ensemble_track / _covariance. One tracked region: (ax, ay) + w x h of the cropped plane, its window
+// grown by the radius left, right and downwards inside the plane (the caller checks); tiles_x / tiles_y: ceil(w / 64), ceil(h / 64);
+// tile_base: where the region's tile tables start in the tile-table buffers, in u64 elements (tile-row major, (R + 1) (2 R + 1) per tile).
+struct CovRegionDev {
+    int ax, ay, w, h;
+    int tiles_x, tiles_y;
+    unsigned long long tile_base;
+};
+constexpr int kCovTile = 64;         // MUSICA_SIM_TILE
+constexpr int kCovMaxRadius = 16;    // MUSICA_SIM_MAX_RADIUS
+// k_cov_add: P(d) += sum over the tile of a(p) a(p + d) for the `count` graded planes from `graded` on (stride l0.plane), one launch over
+// `regions` regions (grid.x = max_tiles, the largest tiles_x * tiles_y); tile_tables: u64, zeroed when tracking starts.
+void launch_cov_add(hipStream_t st, const CovRegionDev* d_rs, int regions, int max_tiles, int radius, const float* graded, const LevelDesc& l0, int count,
+                    unsigned long long* tile_tables);
+// k_cov_mean after K realisations: tile_cov = K P - U per tile (all written), added into tables (regions x (R + 1) (2 R + 1) u64, zeroed by
+// the caller; two's complement). ens: the ensemble's accumulators, dense rows of nw words.
+void launch_cov_mean(hipStream_t st, const CovRegionDev* d_rs, int regions, int max_tiles, int radius, uint32_t K, const uint2* ens, int nw,
+                     const unsigned long long* tile_tables, long long* tile_cov, unsigned long long* tables);
 // kernels_alteration.hip: one alteration of musica_alter (or the draws of musica_alter_draws) over an n x n plane.
 struct AlterDev {
     int kind;                  // MUSICA_ALTER_*

@@ -110,6 +110,16 @@ struct StudyState {
     unsigned long long* d_ens_out = nullptr;       // [MUSICA_SIM_MAX_QUERIES][kEnsTotals]
     unsigned long long* d_ens_tiles = nullptr;     // the tile pairs of one call: 2 * ens_tiles_cap u64, regrown when a call needs more
     size_t ens_tiles_cap = 0;
+    // musica_sim_ensemble_track / _covariance: the tracked regions of the ensemble now running (none after a reset)
+    uint32_t cov_regions = 0, cov_radius = 0;      // cov_regions == 0: nothing is tracked and musica_sim_ensemble_add launches k_ens_add alone
+    int cov_max_tiles = 1;
+    size_t cov_words = 0;                          // u64 per tile-table buffer of the regions tracked now
+    musica_sim_query cov_q[MUSICA_SIM_COV_MAX_REGIONS] = {};
+    CovRegionDev* d_cov_r = nullptr;               // [MUSICA_SIM_COV_MAX_REGIONS]
+    unsigned long long* d_cov_tiles = nullptr;     // the tiles' P(d): cov_tiles_cap u64, regrown when a track call needs more
+    long long* d_cov_ctiles = nullptr;             // the tiles' C(d) of the last covariance call, the same size
+    size_t cov_tiles_cap = 0;
+    unsigned long long* d_cov_tables = nullptr;    // [MUSICA_SIM_COV_MAX_REGIONS][17 * 33]
     // musica_alter_*: the source plane (N x N u16), the radix-select counts and the fill
     uint16_t* d_alter_src = nullptr;
     uint32_t* d_alter_hist = nullptr;    // [768]

@@ -1,6 +1,6 @@
 // musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the four query calls
 // (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip), the ensemble accumulators
-// (musica_sim_ensemble_*; kernels_ensemble.hip) and the alterations of the input (musica_alter_*;
+// (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
 // kernels_alteration.hip, kernels_symmetry.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
 #include <math.h>
 #include <string.h>
@@ -518,6 +518,7 @@ int musica_sim_ensemble_reset(musica_ctx* c) {
     HIP_OK(hipMemsetAsync(st.d_ens, 0, px * sizeof(uint2), c->stream));   // behind the adds and results the stream holds
     st.ens_k = 0;
     st.ens_reset = true;
+    st.cov_regions = 0;   // tracking ends with the ensemble it was declared for
     return 1;
     ABI_CATCH("musica_sim_ensemble_reset")
 }
@@ -535,6 +536,9 @@ int musica_sim_ensemble_add(musica_ctx* c, uint32_t first, uint32_t count) {
         return fail("musica_sim_ensemble_add: %u + %u realisations exceed MUSICA_SIM_ENSEMBLE_MAX = %d", st.ens_k, count, MUSICA_SIM_ENSEMBLE_MAX);
     CHECK_CTX(c);
     launch_ens_add(c->stream, image_slice(c, c->d_graded, first), c->lv[0], (int)count, st.d_ens);
+    if (st.cov_regions)   // musica_sim_ensemble_track: the same images' lag products, behind the accumulation
+        launch_cov_add(c->stream, st.d_cov_r, (int)st.cov_regions, st.cov_max_tiles, (int)st.cov_radius, image_slice(c, c->d_graded, first), c->lv[0],
+                       (int)count, st.d_cov_tiles);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("musica_sim_ensemble_add: launch failed: %s", hipGetErrorString(e));
     st.ens_k += count;
@@ -631,6 +635,117 @@ int musica_sim_ensemble_result(musica_ctx* c, uint32_t count, const musica_sim_q
     for (uint32_t i = 0; i < count; i++) ensemble_finish(res.data() + (size_t)i * kEnsTotals, K, qs[i], out + i);
     return 1;
     ABI_CATCH("musica_sim_ensemble_result")
+}
+
+// ---- the noise's spatial covariance (musica_sim_ensemble_track / _covariance, include/musica.h; kernels_covariance.hip) ---------------
+static void cov_tiles(const musica_sim_query& q, int* tx, int* ty) {
+    *tx = (int)((q.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE);
+    *ty = (int)((q.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE);
+}
+
+int musica_sim_ensemble_track(musica_ctx* c, uint32_t radius, uint32_t count, const musica_sim_query* qs) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_ensemble_track: ctx is NULL");
+    if (!qs) return fail("musica_sim_ensemble_track: regions is NULL");
+    if (radius < 1 || radius > MUSICA_SIM_MAX_RADIUS) return fail("musica_sim_ensemble_track: radius %u out of range [1, %d]", radius, MUSICA_SIM_MAX_RADIUS);
+    if (count == 0 || count > MUSICA_SIM_COV_MAX_REGIONS) return fail("musica_sim_ensemble_track: count %u out of range [1, %d]", count, MUSICA_SIM_COV_MAX_REGIONS);
+    StudyState& st = c->study;
+    if (!st.ens_reset) return fail("musica_sim_ensemble_track: the ensemble was never reset (musica_sim_ensemble_reset)");
+    if (st.ens_k) return fail("musica_sim_ensemble_track: %u realisations were already added: track after the reset, before the first add", st.ens_k);
+    if (!sim_check_queries(c, "musica_sim_ensemble_track", count, qs, qs)) return 0;
+    const uint64_t nw = sim_side(c);
+    const size_t T = (size_t)(radius + 1) * (2 * radius + 1);
+    std::vector<CovRegionDev> hr(count);
+    size_t words = 0;
+    int max_tiles = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        if (q.ax < radius || (uint64_t)q.ax + q.w + radius > nw || (uint64_t)q.ay + q.h + radius > nw)
+            return fail("musica_sim_ensemble_track: region %u: the window (%u, %u) + %u x %u grown by the radius %u (left, right, down) leaves the %llu x %llu plane",
+                        i, q.ax, q.ay, q.w, q.h, radius, (unsigned long long)nw, (unsigned long long)nw);
+        if (((unsigned __int128)65025u * MUSICA_SIM_ENSEMBLE_MAX * MUSICA_SIM_ENSEMBLE_MAX * q.w * q.h) >> 63)
+            return fail("musica_sim_ensemble_track: region %u: 65025 * %d^2 * %u * %u does not fit 63 bits", i, MUSICA_SIM_ENSEMBLE_MAX, q.w, q.h);
+        CovRegionDev& d = hr[i];
+        d.ax = (int)q.ax;
+        d.ay = (int)q.ay;
+        d.w = (int)q.w;
+        d.h = (int)q.h;
+        cov_tiles(q, &d.tiles_x, &d.tiles_y);
+        d.tile_base = words;
+        words += (size_t)d.tiles_x * d.tiles_y * T;
+        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+    }
+    CHECK_CTX(c);
+    if (!(ensure(c, &st.d_cov_r, MUSICA_SIM_COV_MAX_REGIONS) &&
+          ensure(c, &st.d_cov_tables, (size_t)MUSICA_SIM_COV_MAX_REGIONS * (MUSICA_SIM_MAX_RADIUS + 1) * (2 * MUSICA_SIM_MAX_RADIUS + 1))))
+        return fail("musica_sim_ensemble_track: device allocation failed");
+    if (words > st.cov_tiles_cap) {   // sized for the call: the largest call so far
+        HIP_OK(drelease(c, &st.d_cov_tiles));
+        HIP_OK(drelease(c, &st.d_cov_ctiles));
+        st.cov_tiles_cap = 0;
+        if (!dalloc(c, &st.d_cov_tiles, words) || !dalloc(c, &st.d_cov_ctiles, words))
+            return fail("musica_sim_ensemble_track: device allocation of %zu tile-table words failed", words);
+        st.cov_tiles_cap = words;
+    }
+    HIP_OK(hipMemsetAsync(st.d_cov_tiles, 0, words * sizeof(unsigned long long), c->stream));   // behind what the stream holds
+    HIP_OK(hipMemcpyAsync(st.d_cov_r, hr.data(), count * sizeof(CovRegionDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hr is read by then
+    for (uint32_t i = 0; i < count; i++) st.cov_q[i] = qs[i];
+    st.cov_radius = radius;
+    st.cov_max_tiles = max_tiles;
+    st.cov_words = words;
+    st.cov_regions = count;
+    return 1;
+    ABI_CATCH("musica_sim_ensemble_track")
+}
+
+// musica_sim_ensemble_covariance's doubles from one exact table, one operation each in the order include/musica.h states
+// (harness.covariance_summary restates them).
+static void covariance_finish(const int64_t* Ct, uint32_t K, uint32_t radius, const musica_sim_query& q, musica_sim_cov_result* o) {
+    const uint64_t n = (uint64_t)q.w * q.h, k = K;
+    const int R = (int)radius, S = 2 * R + 1;
+    memset(o, 0, sizeof(*o));
+    const int64_t c00 = Ct[R];
+    o->c00 = c00;
+    o->pixels = n;
+    o->realisations = K;
+    o->radius = radius;
+    o->tiles_x = (q.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+    o->tiles_y = (q.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+    o->noise_var = K == 1 ? 0.0 : (double)c00 / (double)(k * (k - 1) * n);
+    o->rho_x = c00 == 0 ? 0.0 : (double)Ct[R + 1] / (double)c00;
+    o->rho_y = c00 == 0 ? 0.0 : (double)Ct[S + R] / (double)c00;
+    double half = 0.0;
+    for (int dy = 0; dy <= R; dy++)
+        for (int dx = dy ? -R : 1; dx <= R; dx++) half += (double)Ct[dy * S + dx + R];
+    o->corr_area = c00 == 0 ? 1.0 : ((double)c00 + 2.0 * half) / (double)c00;
+}
+
+int musica_sim_ensemble_covariance(musica_ctx* c, musica_sim_cov_result* out, int64_t* tables, int64_t* tile_tables) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_ensemble_covariance: ctx is NULL");
+    if (!out) return fail("musica_sim_ensemble_covariance: results is NULL");
+    StudyState& st = c->study;
+    if (!st.ens_reset || !st.cov_regions) return fail("musica_sim_ensemble_covariance: no region is tracked (musica_sim_ensemble_track)");
+    if (st.ens_k == 0) return fail("musica_sim_ensemble_covariance: the ensemble holds no realisation (musica_sim_ensemble_add)");
+    const uint32_t K = st.ens_k, count = st.cov_regions, radius = st.cov_radius;
+    const size_t T = (size_t)(radius + 1) * (2 * radius + 1);
+    CHECK_CTX(c);
+    HIP_OK(hipMemsetAsync(st.d_cov_tables, 0, count * T * sizeof(unsigned long long), c->stream));
+    launch_cov_mean(c->stream, st.d_cov_r, (int)count, st.cov_max_tiles, (int)radius, K, st.d_ens, (int)sim_side(c), st.d_cov_tiles, st.d_cov_ctiles,
+                    st.d_cov_tables);
+    HIP_OK(hipGetLastError());
+    std::vector<int64_t> own;
+    if (!tables) {
+        own.resize(count * T);
+        tables = own.data();
+    }
+    HIP_OK(hipMemcpyAsync(tables, st.d_cov_tables, count * T * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (tile_tables) HIP_OK(hipMemcpyAsync(tile_tables, st.d_cov_ctiles, st.cov_words * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < count; i++) covariance_finish(tables + (size_t)i * T, K, radius, st.cov_q[i], out + i);
+    return 1;
+    ABI_CATCH("musica_sim_ensemble_covariance")
 }
 
 // ---- alterations of the study (musica_alter_*, include/musica.h; kernels_alteration.hip) ----------------------------------------------

@@ -539,6 +539,162 @@ def ensemble_maps(tile_tables, w, h, realisations):
     return bias, noise
 
 
+# ---- the texture of the noise: spatial auto-covariance and power spectrum (musica_sim_ensemble_track / _covariance; not in the reference) ----
+# The per-pixel statistics say how strong the output noise is and nothing about its grain: MUSICA amplifies fine pyramid levels more than
+# coarse ones and its noise reduction works on 5 x 5 neighbourhoods, so the noise that leaves it is coloured. Over K realisations a_k,
+# with S1 = sum_k a_k, the lag products P(d) = sum_k sum_p a_k(p) a_k(p + d) and U(d) = sum_p S1(p) S1(p + d) over a region of n pixels
+# give C(d) = K P(d) - U(d) = K^2 n times the population covariance at lag d about the per-pixel ensemble mean, in exact integers; the
+# neighbour correlations, the correlation area and the noise power spectrum (Wiener-Khinchin) follow. These functions are the contract
+# of musica_sim_ensemble_covariance (include/musica.h).
+COV_KEYS = mp.COV_METRICS + mp.COV_INTEGERS   # ensemble_covariance adds "table" and "tile_tables"; a study row's dicts add "nps_radial" and "hf_fraction"
+
+
+def _covariance_geometry(shape, region, radius):
+    """Raises ValueError exactly where musica_sim_ensemble_track refuses a region on geometry; returns (ax, ay, w, h) and the radius as
+    ints. region: (ax, ay, w, h), or a query's (ax, ay, bx, by, w, h), whose bx, by only have to stay inside the plane."""
+    region = tuple(int(v) for v in region)
+    if len(region) == 6:
+        ax, ay, bx, by, w, h = region
+    else:
+        ax, ay, w, h = region
+        bx, by = ax, ay
+    radius = int(radius)
+    if not 1 <= radius <= mp.SIM_MAX_RADIUS:
+        raise ValueError("radius %d out of range [1, %d]" % (radius, mp.SIM_MAX_RADIUS))
+    if w < 7 or h < 7:
+        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
+    if min(ax, ay, bx, by) < 0 or max(ax, bx) + w > shape[1] or max(ay, by) + h > shape[0]:
+        raise ValueError("region (%d, %d) / (%d, %d) + %d x %d leaves the %d x %d plane" % (ax, ay, bx, by, w, h, shape[1], shape[0]))
+    if ax < radius or ax + w + radius > shape[1] or ay + h + radius > shape[0]:
+        raise ValueError("the window (%d, %d) + %d x %d grown by the radius %d (left, right, down) leaves the %d x %d plane" % (ax, ay, w, h, radius, shape[1], shape[0]))
+    if 65025 * mp.SIM_ENSEMBLE_MAX ** 2 * w * h >= 2 ** 63:
+        raise ValueError("65025 * %d^2 * %d * %d does not fit 63 bits" % (mp.SIM_ENSEMBLE_MAX, w, h))
+    return (ax, ay, w, h), radius
+
+
+def covariance_summary(table, realisations, pixels):
+    """The doubles of a covariance result from its exact (R + 1, 2 R + 1) table C(d) (row dy, column dx + R), one IEEE operation each in
+    include/musica.h's order, every integer converted to double first, with c00, pixels, realisations and radius. The device and the
+    host studies both call this, so they agree to the last bit."""
+    table = np.asarray(table)
+    if table.ndim != 2 or table.shape[0] < 2 or table.shape[1] != 2 * table.shape[0] - 1:
+        raise ValueError("expected an (R + 1, 2 R + 1) table, got %r" % (table.shape,))
+    r, k, n = table.shape[0] - 1, int(realisations), int(pixels)
+    c00 = int(table[0, r])
+    half = 0.0
+    for dy in range(r + 1):
+        for dx in range(-r if dy else 1, r + 1):
+            half += float(int(table[dy, dx + r]))
+    return {"noise_var": 0.0 if k == 1 else float(c00) / float(k * (k - 1) * n),
+            "rho_x": 0.0 if c00 == 0 else float(int(table[0, r + 1])) / float(c00),
+            "rho_y": 0.0 if c00 == 0 else float(int(table[1, r])) / float(c00),
+            "corr_area": 1.0 if c00 == 0 else (float(c00) + 2.0 * half) / float(c00),
+            "c00": c00, "pixels": n, "realisations": k, "radius": r}
+
+
+def ensemble_covariance(outs, region, radius):
+    """musica_sim_ensemble_covariance's numbers of one tracked region, restated: outs a (K, H, W) stack of uint8 outputs (the
+    realisations), region = (ax, ay, w, h) or a query's (ax, ay, bx, by, w, h). For dy = 0 .. R and dx = -R .. R, per region pixel in
+    int64, K sum_k a_k(p) a_k(p + d) - S1(p) S1(p + d), summed per 64 x 64 tile of the region (int64: a tile's |C| <= 4096 * 65025 K^2 <
+    2^58), the region's totals as Python ints over the tiles. Returns the COV_KEYS dict (covariance_summary) plus "table":
+    (R + 1, 2 R + 1) int64, row dy, column dx + R, and "tile_tables": (tiles_y, tiles_x, R + 1, 2 R + 1) int64. ValueError where the C
+    calls refuse: no or more than SIM_ENSEMBLE_MAX realisations, a radius outside 1 .. 16, w < 7 or h < 7, a region that leaves the
+    plane, a window that, grown by the radius to the left, to the right and downwards, leaves it, 65025 * 1024^2 w h >= 2^63."""
+    outs = np.asarray(outs)
+    if outs.ndim != 3 or outs.dtype != np.uint8:
+        raise ValueError("ensemble_covariance needs a (K, H, W) uint8 stack, got %r %s" % (outs.shape, outs.dtype))
+    k = outs.shape[0]
+    if not 1 <= k <= mp.SIM_ENSEMBLE_MAX:
+        raise ValueError("%d realisations out of range [1, %d]" % (k, mp.SIM_ENSEMBLE_MAX))
+    (ax, ay, w, h), r = _covariance_geometry(outs.shape[1:], region, radius)
+    t, s = mp.SIM_TILE, 2 * r + 1
+    ny, nx = (h + t - 1) // t, (w + t - 1) // t
+    a = outs.astype(np.int64)
+    s1 = a.sum(axis=0)
+    ca, c1 = a[:, ay:ay + h, ax:ax + w], s1[ay:ay + h, ax:ax + w]
+    tile_tables = np.empty((ny, nx, r + 1, s), dtype=np.int64)
+    for dy in range(r + 1):
+        for dx in range(-r, r + 1):
+            shifted = (slice(ay + dy, ay + dy + h), slice(ax + dx, ax + dx + w))
+            c = k * (ca * a[(slice(None),) + shifted]).sum(axis=0) - c1 * s1[shifted]
+            tile_tables[:, :, dy, dx + r] = np.add.reduceat(np.add.reduceat(c, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
+    table = np.array([[sum(int(x) for x in tile_tables[:, :, dy, j].ravel()) for j in range(s)] for dy in range(r + 1)], dtype=np.int64)
+    out = covariance_summary(table, k, w * h)
+    out.update(tiles_x=nx, tiles_y=ny, table=table, tile_tables=tile_tables)
+    return out
+
+
+def covariance_symmetric(table):
+    """The (S, S) float64 table over dy, dx = -R .. R (row dy + R, column dx + R) of a half-plane table: C(-d) = C(d), the row dy = 0
+    taken from its entries with dx >= 0."""
+    table = np.asarray(table)
+    r = table.shape[0] - 1
+    sym = np.empty((2 * r + 1,) * 2, dtype=np.float64)
+    sym[r + 1:] = table[1:]
+    sym[:r] = table[1:][::-1, ::-1]
+    sym[r, r:] = table[0, r:]
+    sym[r, :r] = table[0, r + 1:][::-1]
+    return sym
+
+
+def noise_power_spectrum(table, realisations, pixels):
+    """The noise power spectrum of a covariance table (Wiener-Khinchin), host only: N[v][u] = sum over d of C_sym(d)
+    cos(2 pi (u dx + v dy) / S) / (K (K - 1) n) for u, v = 0 .. S - 1, (S, S) float64, the zero frequency at [0][0]. The sum of
+    cosines is taken as cos cos - sin sin with the phases' integers reduced mod S first. All zero when K == 1."""
+    sym = covariance_symmetric(table)
+    s, k, n = sym.shape[0], int(realisations), int(pixels)
+    if k == 1:
+        return np.zeros((s, s), dtype=np.float64)
+    d = np.arange(s) - s // 2
+    phase = 2.0 * np.pi * ((np.arange(s)[:, None] * d[None, :]) % s) / s     # [frequency][lag]
+    co, si = np.cos(phase), np.sin(phase)
+    return (co @ sym @ co.T - si @ sym @ si.T) / float(k * (k - 1) * n)
+
+
+def _nps_radius(s):
+    d = np.arange(s) - s // 2
+    return np.hypot(d[:, None], d[None, :])
+
+
+def nps_radial(nps):
+    """The mean of the centred spectrum (np.fft.fftshift) over the frequencies of rounded integer radius 0 .. R: a list of R + 1 floats."""
+    nps = np.asarray(nps, dtype=np.float64)
+    rad = np.rint(_nps_radius(nps.shape[0])).astype(np.int64)
+    c = np.fft.fftshift(nps)
+    return [float(c[rad == i].mean()) for i in range(nps.shape[0] // 2 + 1)]
+
+
+def nps_hf_fraction(nps):
+    """The share of the spectrum's sum at radius > R / 2 of the centred spectrum (0 for a spectrum that sums to 0). White noise gives
+    the share of such frequencies among the S^2: nps_hf_fraction(np.ones((S, S)))."""
+    nps = np.asarray(nps, dtype=np.float64)
+    total = float(nps.sum())
+    if total == 0.0:
+        return 0.0
+    return float(np.fft.fftshift(nps)[_nps_radius(nps.shape[0]) > (nps.shape[0] // 2) / 2.0].sum()) / total
+
+
+hf_fraction = nps_hf_fraction
+
+
+def covariance_row(table, realisations, w, h):
+    """A study row's covariance dict of one region from its exact table: COV_KEYS, then "nps_radial" and "hf_fraction"."""
+    t = mp.SIM_TILE
+    d = covariance_summary(table, realisations, int(w) * int(h))
+    d.update(tiles_x=(int(w) + t - 1) // t, tiles_y=(int(h) + t - 1) // t)
+    out = {k: d[k] for k in COV_KEYS}
+    nps = noise_power_spectrum(table, realisations, int(w) * int(h))
+    out["nps_radial"], out["hf_fraction"] = nps_radial(nps), nps_hf_fraction(nps)
+    return out
+
+
+def nps_map(table, realisations, pixels):
+    """The centred spectrum as an (S, S) uint8 image: log(1 + max(N, 0)) scaled so that its largest value is 255, rounded."""
+    v = np.log1p(np.maximum(np.fft.fftshift(noise_power_spectrum(table, realisations, pixels)), 0.0))
+    top = float(v.max())
+    return np.zeros(v.shape, dtype=np.uint8) if top == 0.0 else np.rint(255.0 * v / top).astype(np.uint8)
+
+
 # ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
 
 def vendor_to_u8(pixels):
@@ -750,7 +906,7 @@ TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "referenc
 
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
-              tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False):
+              tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -806,7 +962,14 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     Realisation j of the row with ordinal o draws from the study's seed and the stream ensemble_stream(o, j); B realisations go through
     one step, musica_sim_ensemble_add and one musica_sim_compare call, and one musica_sim_ensemble_result call ends the row.
     ensemble_tiles: the "direct" dict also carries "tile_tables" ((tiles_y, tiles_x, 2) uint64) and "size", what ensemble_maps draws.
-    With ensemble=0 nothing is created and the rows are exactly as before."""
+    With ensemble=0 nothing is created and the rows are exactly as before.
+
+    covariance: a radius R > 0 (at most SIM_MAX_RADIUS; needs ensemble > 0, else ValueError) adds the texture of the noise: each noise
+    row's "ensemble" dict gains "covariance": {"direct": ..., "registered": ...}, each a dict of COV_KEYS plus "nps_radial" and
+    "hf_fraction" (covariance_row). The direct region is the full frame inset by R; the registered one the row's registered region inset
+    by R, None where the row has none or an inset side is under 7. One musica_sim_ensemble_track call follows the row's reset and one
+    musica_sim_ensemble_covariance call ends it. covariance_tiles: the dicts also carry "table" and "tile_tables". With covariance=0 the
+    rows, keys and launches are exactly as before."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     if vendor is not None:
@@ -834,6 +997,11 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         raise ValueError("an ensemble repeats the device's noise alterations: it needs a runner with device_alterations")
     if ensemble:
         keys += ("ensemble",)
+    covariance = int(covariance)
+    if covariance and not 1 <= covariance <= mp.SIM_MAX_RADIUS:
+        raise ValueError("covariance radius %d is not in 1 .. %d" % (covariance, mp.SIM_MAX_RADIUS))
+    if covariance and not ensemble:
+        raise ValueError("covariance is taken over the realisations of an ensemble: give ensemble > 0")
     shutters = scaled(SHUTTERS, n) if shutters is None else shutters
     translations = scaled(TRANSLATIONS, n) if translations is None else translations
     rotations = ROTATIONS if rotations is None else rotations
@@ -963,6 +1131,11 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         regions = [full] + ([registered] if registered is not None else [])
         per = {k: [] for k in mp.SIM_METRICS}
         eproc.sim_ensemble_reset()
+        if covariance:
+            tracked = [_inset(full, covariance), _inset(registered, covariance) if registered is not None else None]
+            if tracked[0] is None:
+                raise ValueError("covariance radius %d leaves no 7 x 7 region of the %d x %d output" % (covariance, full[4], full[5]))
+            eproc.sim_ensemble_track([(0, SLOT_UNALTERED) + r for r in tracked if r is not None], covariance)
         for j0 in range(0, ensemble, eproc.batch):
             count = min(eproc.batch, ensemble - j0)
             for i in range(count):
@@ -978,9 +1151,23 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
                                   g[4], g[5]) for r, g in zip(res, regions)]
         if ensemble_tiles:
             dicts[0]["tile_tables"], dicts[0]["size"] = res[0]["tile_tables"], (full[4], full[5])
-        return {"direct": dicts[0], "registered": dicts[1] if registered is not None else None, "realisations": ensemble,
-                "per_realisation": {"mean": {k: float(np.mean(v)) for k, v in per.items()},
-                                    "std": {k: float(np.std(v, ddof=1)) if ensemble > 1 else 0.0 for k, v in per.items()}}}
+        out = {"direct": dicts[0], "registered": dicts[1] if registered is not None else None, "realisations": ensemble,
+               "per_realisation": {"mean": {k: float(np.mean(v)) for k, v in per.items()},
+                                   "std": {k: float(np.std(v, ddof=1)) if ensemble > 1 else 0.0 for k, v in per.items()}}}
+        if covariance:
+            cov = iter(eproc.sim_ensemble_covariance(tables=True, tiles=covariance_tiles))
+            groups = []
+            for r in tracked:
+                if r is None:
+                    groups.append(None)
+                    continue
+                c = next(cov)
+                d = covariance_row(c["table"], c["realisations"], r[4], r[5])
+                if covariance_tiles:
+                    d["table"], d["tile_tables"] = c["table"], c["tile_tables"]
+                groups.append(d)
+            out["covariance"] = {"direct": groups[0], "registered": groups[1]}
+        return out
 
     def add(name, host, dev, reg=None, region=None, slot=None, plane=None):
         """One row of study() below, scored the way the runner's mode asks for."""
@@ -1117,6 +1304,15 @@ ENSEMBLE_CSV_HEADER = ['raw file', 'alteration', 'realisations'] + ['%s %s' % (g
                       ['per-realisation %s %s' % (m, w) for m in ENSEMBLE_CSV_METRICS for w in ("mean", "std")]   # ensemble.csv
 
 
+COV_CSV_NAMES = (("noise_var", "noise var"), ("rho_x", "rho x"), ("rho_y", "rho y"), ("corr_area", "correlation area"), ("hf_fraction", "hf fraction"))
+
+
+def covariance_csv_header(radius):
+    """noise_covariance.csv of a study with covariance=radius: the groups' numbers, then the radial spectrum of the direct group."""
+    return ['raw file', 'alteration', 'realisations', 'radius'] + ['%s %s' % (g, m) for g in ("direct", "registered") for _, m in COV_CSV_NAMES] + \
+           ['direct nps radius %d' % i for i in range(int(radius) + 1)]
+
+
 def scale_csv_header(with_reference):
     """scale_robustness.csv's columns: per group ms_ssim, scales, then ssim, cs and mse of scales 0 .. 4; the two vendor groups only for
     studies that have a vendor image."""
@@ -1168,7 +1364,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
 
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
-    and standard deviation over the realisations of the five similarity metrics."""
+    and standard deviation over the realisations of the five similarity metrics.
+
+    Studies run with covariance=R (their noise rows' "ensemble" has "covariance") also get noise_covariance.csv
+    (covariance_csv_header): one line per noise row, K, R, the noise variance, rho x, rho y, correlation area and high-frequency
+    fraction of the direct and of the registered region (empty without one), then the radial noise power spectrum of the direct one."""
     os.makedirs(out_dir, exist_ok=True)
     ovds = []
 
@@ -1258,6 +1458,21 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
                         cells += [""] * len(ENSEMBLE_CSV_NAMES) if e[key] is None else [e[key][k] for k, _ in ENSEMBLE_CSV_NAMES]
                     per = e["per_realisation"]
                     we.writerow([raw_name, r["alteration"], e["realisations"]] + cells + [per[w][k] for k in mp.SIM_METRICS for w in ("mean", "std")])
+    covs = [(raw_name, [r for r in rows if r.get("ensemble") and "covariance" in r["ensemble"]]) for raw_name, rows in ensembles]
+    covs = [(raw_name, rows) for raw_name, rows in covs if rows]
+    if covs:
+        radius = covs[0][1][0]["ensemble"]["covariance"]["direct"]["radius"]
+        with open(os.path.join(out_dir, "noise_covariance.csv"), "w", newline="") as fc:
+            wc = csv.writer(fc)
+            wc.writerow(covariance_csv_header(radius))
+            for raw_name, rows in covs:
+                for r in rows:
+                    e = r["ensemble"]
+                    cells = []
+                    for key in ("direct", "registered"):
+                        g = e["covariance"][key]
+                        cells += [""] * len(COV_CSV_NAMES) if g is None else [g[k] for k, _ in COV_CSV_NAMES]
+                    wc.writerow([raw_name, r["alteration"], e["realisations"], radius] + cells + list(e["covariance"]["direct"]["nps_radial"]))
 
 
 def write_ensemble_maps(studies, out_dir):
@@ -1277,6 +1492,25 @@ def write_ensemble_maps(studies, out_dir):
                 if not mp.write_bmp_gray(path, img):
                     raise RuntimeError("writing %s failed: %s" % (path, mp.last_error()))
                 written.append(path)
+    return written
+
+
+def write_covariance_maps(studies, out_dir):
+    """One 8-bit BMP per noise row of studies run with covariance_tiles: <raw>_<alteration>_nps.bmp, the centred noise power spectrum of
+    the direct region (nps_map: S x S pixels, the zero frequency in the middle, log-scaled). Returns the paths written."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for raw_name, rows in studies:
+        stem = os.path.splitext(os.path.basename(raw_name.replace("\\", "/")))[0]
+        for r in rows:
+            e = r.get("ensemble")
+            g = e["covariance"]["direct"] if e and "covariance" in e else None
+            if g is None or "table" not in g:
+                continue
+            path = os.path.join(out_dir, "%s_%s_nps.bmp" % (stem, r["alteration"]))
+            if not mp.write_bmp_gray(path, nps_map(g["table"], g["realisations"], g["pixels"])):
+                raise RuntimeError("writing %s failed: %s" % (path, mp.last_error()))
+            written.append(path)
     return written
 
 
@@ -1398,7 +1632,19 @@ def main(argv=None):
     ap.add_argument("--ensemble-batch", type=int, default=8, metavar="B", help="with --ensemble: realisations per step of the ensemble context")
     ap.add_argument("--ensemble-maps", metavar="DIR",
                     help="with --ensemble: two 8-bit BMPs per noise row into DIR, one pixel per 64 x 64 tile: the tile's bias rms and its noise rms")
+    ap.add_argument("--covariance", type=int, default=0, metavar="R",
+                    help="with --ensemble: the spatial auto-covariance of the output noise over the lags within R (1 .. 16) pixels, its "
+                         "neighbour correlations, correlation area and noise power spectrum, written to noise_covariance.csv "
+                         "(musica_sim_ensemble_track, musica_sim_ensemble_covariance)")
+    ap.add_argument("--covariance-maps", metavar="DIR",
+                    help="with --covariance: one 8-bit BMP per noise row into DIR: the centred noise power spectrum, log-scaled")
     args = ap.parse_args(argv)
+    if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
+        ap.error("--covariance takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
+    if args.covariance and not args.ensemble:
+        ap.error("--covariance is taken over the realisations of an ensemble: give --ensemble")
+    if args.covariance_maps and not args.covariance:
+        ap.error("--covariance-maps draws what --covariance measures: give a radius")
     if args.ensemble and not 1 <= args.ensemble <= mp.SIM_ENSEMBLE_MAX:
         ap.error("--ensemble takes a count of 1 .. %d realisations" % mp.SIM_ENSEMBLE_MAX)
     if args.ensemble and not args.device_alterations:
@@ -1440,6 +1686,8 @@ def main(argv=None):
         shift_args["scales"] = args.scales
     if args.ensemble:
         shift_args.update(ensemble=args.ensemble, ensemble_tiles=bool(args.ensemble_maps))
+    if args.covariance:
+        shift_args.update(covariance=args.covariance, covariance_tiles=bool(args.covariance_maps))
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)
@@ -1453,6 +1701,8 @@ def main(argv=None):
         write_displacement_maps(studies, args.displacement_maps)
     if args.ensemble_maps:
         write_ensemble_maps(studies, args.ensemble_maps)
+    if args.covariance_maps:
+        write_covariance_maps(studies, args.covariance_maps)
     print("wrote %d alterations to %s" % (sum(len(rows) - 1 for _, rows in studies), args.out))
     return 0
 

@@ -202,6 +202,23 @@ class SimEnsembleResult(C.Structure):
         return d
 
 
+SIM_COV_MAX_REGIONS = 4     # MUSICA_SIM_COV_MAX_REGIONS
+COV_METRICS = ("noise_var", "rho_x", "rho_y", "corr_area")                                  # the doubles of a covariance result
+COV_INTEGERS = ("c00", "pixels", "realisations", "radius", "tiles_x", "tiles_y")            # its exact integers
+
+
+class SimCovResult(C.Structure):
+    """musica_sim_cov_result: the noise covariance summary of one tracked region (harness.ensemble_covariance's keys)."""
+    _fields_ = [(n, C.c_double) for n in COV_METRICS] + \
+               [("c00", C.c_int64), ("pixels", C.c_uint64), ("realisations", C.c_uint32), ("radius", C.c_uint32),
+                ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32)]
+
+    def as_dict(self):
+        d = {n: float(getattr(self, n)) for n in COV_METRICS}
+        d.update({n: int(getattr(self, n)) for n in COV_INTEGERS})
+        return d
+
+
 # musica_out_format: what export_out writes per image
 OUT_U8, OUT_GRADED_F32 = 0, 1
 OUT_FORMAT_COUNT = 2
@@ -334,6 +351,8 @@ ABI = {
     "musica_sim_ensemble_add": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "musica_sim_ensemble_result": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimEnsembleResult), C.POINTER(C.c_uint64)]),
     "musica_sim_ensemble_get": (C.c_int, [_VP, _U32P, _U32P, _U32P]),
+    "musica_sim_ensemble_track": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(SimQuery)]),
+    "musica_sim_ensemble_covariance": (C.c_int, [_VP, C.POINTER(SimCovResult), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "musica_alter_set_source": (C.c_int, [_VP, _U16P]),
     "musica_alter": (C.c_int, [_VP, C.c_uint32, C.POINTER(Alteration)]),
     "musica_alter_draws": (C.c_int, [_VP, C.POINTER(Alteration), C.POINTER(C.c_int32)]),
@@ -774,6 +793,7 @@ class MusicaProcessing:
     def sim_ensemble_reset(self):
         """Zeroes the per-pixel accumulators S1 = sum a, S2 = sum a^2 and the realisation count, on the context's stream."""
         self._ok(self._lib.musica_sim_ensemble_reset(self._h), "musica_sim_ensemble_reset")
+        self._cov_tracked = None   # the reset drops sim_ensemble_track's regions
 
     def sim_ensemble_add(self, first=0, count=None):
         """Adds the current 8-bit outputs of images first .. first + count - 1 (default: the rest of the batch) as that many realisations;
@@ -809,6 +829,44 @@ class MusicaProcessing:
         s1, s2, k = np.empty((n, n), dtype=np.uint32), np.empty((n, n), dtype=np.uint32), C.c_uint32()
         self._ok(self._lib.musica_sim_ensemble_get(self._h, s1.ctypes.data_as(_U32P), s2.ctypes.data_as(_U32P), C.byref(k)), "musica_sim_ensemble_get")
         return s1, s2, int(k.value)
+
+    def sim_ensemble_track(self, regions, radius):
+        """Declares up to SIM_COV_MAX_REGIONS tracked regions (queries as sim_compare's: ax, ay, w, h are used, the rest is checked) for
+        the ensemble now starting, after sim_ensemble_reset and before the first add: every later sim_ensemble_add also accumulates the
+        lag products of those regions for the lags dy = 0 .. radius, dx = -radius .. radius. A region grown by `radius` to the left, to
+        the right and downwards must lie inside the plane. sim_ensemble_reset drops the tracking."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in regions]
+        if not 0 <= int(radius) < 2 ** 32:
+            raise ValueError("radius %r is not in 1 .. %d" % (radius, SIM_MAX_RADIUS))
+        arr = (SimQuery * max(len(qs), 1))(*qs)
+        self._ok(self._lib.musica_sim_ensemble_track(self._h, int(radius), len(qs), arr), "musica_sim_ensemble_track")
+        self._cov_tracked = (qs, int(radius))
+
+    def sim_ensemble_covariance(self, tables=True, tiles=False):
+        """One dict per tracked region, in order: the doubles COV_METRICS and the exact COV_INTEGERS (== harness.ensemble_covariance);
+        with tables=True "table": the (radius + 1, 2 radius + 1) int64 values C(d) = K P(d) - U(d), row dy, column dx + radius; with
+        tiles=True "tile_tables": the (tiles_y, tiles_x, radius + 1, 2 radius + 1) int64 tables of the 64 x 64 tiles. Synchronous;
+        changes nothing and may be called again after more adds."""
+        qs, radius = getattr(self, "_cov_tracked", None) or ([], 1)
+        rows, s = radius + 1, 2 * radius + 1
+        res = (SimCovResult * SIM_COV_MAX_REGIONS)()
+        table = np.zeros((SIM_COV_MAX_REGIONS, rows, s), dtype=np.int64) if tables else None
+        tile = None
+        if tiles:
+            per = [((q.h + SIM_TILE - 1) // SIM_TILE) * ((q.w + SIM_TILE - 1) // SIM_TILE) * rows * s for q in qs]
+            tile = np.zeros(max(sum(per), 1), dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._ok(self._lib.musica_sim_ensemble_covariance(self._h, res, table.ctypes.data_as(i64p) if table is not None else None,
+                                                          tile.ctypes.data_as(i64p) if tile is not None else None), "musica_sim_ensemble_covariance")
+        out = [res[i].as_dict() for i in range(len(qs))]
+        first = 0
+        for i, d in enumerate(out):
+            if tables:
+                d["table"] = table[i]
+            if tiles:
+                d["tile_tables"] = tile[first:first + per[i]].reshape(d["tiles_y"], d["tiles_x"], rows, s)
+                first += per[i]
+        return out
 
     # ---- alterations of the metamorphic study (musica_alter_*) ---------------------------------
     # Each alter_* writes image `image_index` of the resident input buffer (follow it with execute_device()); the arguments mirror
