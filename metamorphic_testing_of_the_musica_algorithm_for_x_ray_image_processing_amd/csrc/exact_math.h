@@ -94,6 +94,33 @@ __device__ __forceinline__ void musica_sqrt8(float s[8]) {
         for (int j = 0; j < 8; j++) s[j] = sqrtf(s[j]);
     }
 }
+// sqrtf(x / 25.0f) for eight 5 x 5 sums of squares (img_sdev.comp:30) with ONE range test for the group, on the sums. Fast path: every
+// sum is +0 or lies in [2^-95, FLT_MAX]. There the residual of musica_div25 is a number (it is NaN only for x = +inf or NaN), so its
+// `r == r` select is not needed, and the quotient is +0 or at least 2^-95 / 25 > 2^-100, where musica_sqrt_core is exact, so musica_sqrt8's
+// second test is not needed either. Any other group (a sum below 2^-95, +inf, NaN, a set sign bit) takes the literal expression for all eight.
+// The test is musica_sqrt8's: the largest pattern below +inf (NaN and negatives have larger ones), the smallest non-zero one at least
+// 2^-95 (pattern - 1 wraps for +0). Checked against sqrtf(x / 25.0f) over all 2^32 patterns on the GPU (musica_selftest_exact_math).
+__device__ __forceinline__ void musica_rms25_8(float s[8]) {
+    uint32_t mx = 0u, mn = 0xFFFFFFFFu;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t u = __float_as_uint(s[j]);
+        mx = max(mx, u);
+        mn = min(mn, u - 1u);
+    }
+    const bool ok = mx < 0x7F800000u && mn >= 0x10000000u - 1u;   // 0x10000000 = 2^-95
+    if (__builtin_expect(ok, 1)) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float q = s[j] * 0.04f;
+            const float r = fmaf(-25.0f, q, s[j]);
+            s[j] = musica_sqrt_core(fmaf(r, 0.04f, q));
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) s[j] = sqrtf(s[j] / 25.0f);
+    }
+}
 __device__ __forceinline__ float musica_sqrt(float x) {
     const float s = musica_sqrt_core(x);
     if (__builtin_expect(!musica_sqrt_core_ok(x), 0)) return sqrtf(x);

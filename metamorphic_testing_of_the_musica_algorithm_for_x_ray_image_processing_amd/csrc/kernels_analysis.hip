@@ -184,6 +184,29 @@ __global__ __launch_bounds__(256) void k_selftest_sqrt(unsigned long long* __res
             if (!same_float(s[j], want[j])) b1++;
             if (!same_float(z[j], j == (int)(grp & 7) ? 0.0f : want[j])) b2++;
         }
+        // musica_rms25_8 (the 5 x 5 RMS of the sdev passes and the sdev-computing expand launches) against the literal sqrtf(x / 25.0f):
+        // the group as it is (slot 1), and with one member replaced by +0, by a value below the fast path's threshold, by +inf (slot 2) —
+        // the replaced member and the seven around it must all come out as the literal expression, whichever path the group takes
+        const float repl[3] = {0.0f, __uint_as_float(0x03800000u) /* 2^-120 */, __uint_as_float(0x7F800000u)};
+        float want25[8], r[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            r[j] = __uint_as_float((uint32_t)(grp * 8 + j));
+            want25[j] = sqrtf(r[j] / 25.0f);
+        }
+        musica_rms25_8(r);
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            if (!same_float(r[j], want25[j])) b1++;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) r[j] = j == (int)(grp & 7) ? repl[k] : __uint_as_float((uint32_t)(grp * 8 + j));
+            musica_rms25_8(r);
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if (!same_float(r[j], j == (int)(grp & 7) ? sqrtf(repl[k] / 25.0f) : want25[j])) b2++;
+        }
     }
     if (b0) atomicAdd(&bad[0], b0);
     if (b1) atomicAdd(&bad[1], b1);
@@ -419,8 +442,6 @@ __device__ __forceinline__ void noise_curves_block(int level, int img, const uin
         chain_scalars(minmax, img, min_chain_exact, minv, maxv);
         thr090[img] = norm_threshold_090(minv, maxv - minv);
     }
-    __shared__ float sx[kCurveCap];
-    __shared__ int sbucket[kCurveCap];
     __shared__ int sok;
     musica_hist_max_point mp;
     mp.maxValue = 0; mp.maxBin = 0;
@@ -449,12 +470,8 @@ __device__ __forceinline__ void noise_curves_block(int level, int img, const uin
             if (i == 0) { x = 0.0f; y = high; }                                                 // :68
             if (i == 1) { x = 1.0f; y = high; }                                                 // :69
         } else if (i < 33) {
-            const float p = (float)mp.maxBin * (1.0f / (float)MUSICA_NOISE_BINS) * kMaxNoiseValue;  // :71
-            const int seg = i / 11;
-            const uint32_t k = (uint32_t)(i - seg * 11);
-            if (seg == 0) bezier_point(0.0f, 1.0f, p * 4.0f / 5.0f, low, p, low, k, x, y);                               // :72-76
-            else if (seg == 1) bezier_point(p, low, p * 6.0f / 5.0f, low, p * 7.0f / 5.0f, low * 4.0f / 5.0f, k, x, y);   // :77-81
-            else bezier_point(p * 7.0f / 5.0f, low * 4.0f / 5.0f, p * 2.0f, 1.0f, 1.0f, 1.0f, k, x, y);                   // :82-86
+            static_assert(MUSICA_NOISE_BINS == 2048 && kMaxNoiseValue == 0.1f, "musica_contrast_point spells the noise mode out");
+            musica_contrast_point(mp.maxBin, low, i, x, y);                                     // :71-86 (curve_lut.h)
         }
         cx[i] = x;
         cy[i] = y;
@@ -463,56 +480,31 @@ __device__ __forceinline__ void noise_curves_block(int level, int img, const uin
     curve_store_parallel(c, cx, cy, &s_mono, npts, 0.0f, 0.0f, 0.0f);
     if (level >= MUSICA_COARSER_LEVELS_START) return;   // only the 33-point curves get a lookup table (block-uniform)
     __syncthreads();
-    // ---- lookup tables for the expand kernel (see DevCurveLut) ----
+    // ---- lookup table for the expand kernel (see DevCurveLut; entries, segments and the lookup itself are curve_lut.h's) ----
     DevCurveLut* lut = luts + (size_t)img * MUSICA_COARSER_LEVELS_START + level;
     const int count = npts;
-    const float range = cx[kLutTailFirst - 1] * 1.25f;                // 1.75 p: above x[22] = 1.4 p, below x[23] >= 1.49 p + 0.01
-    const float inv_w = (float)kLutBuckets / range;
-    __shared__ int scoarse[kCurveCap];
-    if (threadIdx.x == 0) sok = (s_mono && count == kLutPoints && range > 0.0f && inv_w < 3.0e38f && cx[0] == 0.0f) ? 1 : 0;
-    if ((int)threadIdx.x < kCurveCap) {
-        const float x = cx[threadIdx.x];
-        sx[threadIdx.x] = x;
-        const float kf = x * inv_w;                                    // the expand kernel's expression for the fine bucket
-        sbucket[threadIdx.x] = ((int)threadIdx.x < count && kf < (float)kLutBuckets) ? (int)kf : kLutBuckets;
-        const float cf = fminf(x * 256.0f, (float)(kLutCoarse - 1));  // ... and for the coarse bucket
-        scoarse[threadIdx.x] = (int)cf;
-    }
+    const int base = musica_lut_base(cx);
+    const int n = (s_mono && count == kLutPoints && cx[0] == 0.0f) ? musica_lut_entries(base) : 0;   // block-uniform; 0: no table
+    __shared__ int sslot[kCurveCap];   // the abscissae's table slots, three sentinels behind them
+    if (threadIdx.x == 0) sok = n > 0 ? 1 : 0;
+    if ((int)threadIdx.x < kCurveCap) sslot[threadIdx.x] = (int)threadIdx.x < count ? musica_lut_slot(cx[threadIdx.x], base) : kLutSlotSentinel;
     __syncthreads();
-    if ((int)threadIdx.x < count) {   // the fine table covers exactly the abscissae 0..22
-        const bool inside = sbucket[threadIdx.x] < kLutBuckets;
-        if (inside != ((int)threadIdx.x < kLutTailFirst)) sok = 0;
+    for (int k = threadIdx.x; k < n; k += blockDim.x) {   // a 6-step search per entry: a scan over the 33 abscissae per entry made this launch 8 us longer
+        float4 e;
+        if (musica_lut_entry(cx, sslot, count, k, e) > 2) sok = 0;
+        lut->bucket[k] = e;
     }
-    for (int k = threadIdx.x; k < kLutBuckets + kLutCoarse; k += blockDim.x) {
-        const bool fine = k < kLutBuckets;
-        const int kb = fine ? k : k - kLutBuckets;
-        const int first = fine ? 0 : kLutTailFirst;                     // the coarse table only ever sees s above x[0..22]
-        int jlo = first, inb = 0;
-        float xa = __builtin_huge_valf(), xb = __builtin_huge_valf();
-        for (int i = first; i < count && i < kCurveCap; i++) {
-            const int b = fine ? sbucket[i] : scoarse[i];
-            if (b < kb) jlo++;
-            else if (b == kb) {
-                if (inb == 0) xa = sx[i];
-                else if (inb == 1) xb = sx[i];
-                inb++;
-            }
-        }
-        if (inb > 2) sok = 0;
-        lut->bucket[k] = make_float4(__int_as_float(jlo * 16), xa, xb, 0.0f);   // 16 * jlo: the byte offset of seg[jlo]
-    }
-    if ((int)threadIdx.x <= kLutPoints) {   // segment table: same slopes as DevCurve::m (linearFunction, contrast_curve_apply.comp:22-25)
-        const int j = threadIdx.x;
-        float4 sg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (j == 0) sg = make_float4(cx[0], cy[0], 0.0f, 0.0f);
-        else if (j < count) sg = make_float4(cx[j - 1], cy[j - 1], (cy[j] - cy[j - 1]) / (cx[j] - cx[j - 1]), 0.0f);
-        lut->seg[j] = sg;
+    if ((int)threadIdx.x <= kLutPoints) {
+        float4 sg;
+        musica_lut_segment(cx, cy, count, (int)threadIdx.x, sg);
+        lut->seg[threadIdx.x] = sg;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        lut->inv_w = inv_w;
+        lut->base = base;
         lut->ok = (uint32_t)sok;
-        lut->pad0 = lut->pad1 = 0;
+        lut->n = (uint32_t)n;
+        lut->pad0 = 0;
     }
 }
 

@@ -301,11 +301,7 @@ __device__ __forceinline__ void curve_finish(DevCurve* c) {
     c->monotone = mono;
 }
 
-// interpolate() of contrast_curve_generate.comp:28-31
-__device__ __forceinline__ float interpolate(float from, float to, float percent) {
-    float difference = to - from;
-    return from + (difference * percent);
-}
+// interpolate() and bezier_point(): curve_lut.h (shared with the host)
 
 // generateCurve(): contrast_curve_generate.comp:39-54 (steps 11) / gradation_curve_generate.comp:30-46 (steps 10)
 __device__ __forceinline__ void generate_curve(DevCurve* c, uint32_t& n, float sx, float sy, float mx, float my,
@@ -320,18 +316,6 @@ __device__ __forceinline__ void generate_curve(DevCurve* c, uint32_t& n, float s
         c->y[n] = interpolate(ya, yb, t);
         n++;
     }
-}
-
-// One point of generateCurve() (same arithmetic as generate_curve above): step k of the quadratic Bezier
-// (s, m, e), t = k / 10.
-__device__ __forceinline__ void bezier_point(float sx, float sy, float mx, float my, float ex, float ey, uint32_t k, float& x, float& y) {
-    const float t = (float)k / 10.0f;
-    const float xa = interpolate(sx, mx, t);
-    const float ya = interpolate(sy, my, t);
-    const float xb = interpolate(mx, ex, t);
-    const float yb = interpolate(my, ey, t);
-    x = interpolate(xa, xb, t);
-    y = interpolate(ya, yb, t);
 }
 
 // Block-parallel curve_finish(): threads 0 .. kCurveCap-1 hold point i in (x, y) (zeros at i >= count) and

@@ -678,38 +678,26 @@ __device__ __forceinline__ float gain_of(float s, float high, const CurveLds& t)
 }
 
 // The streaming kernel's form of getY() for the 33-point contrast polyline (DevCurveLut): two 16-byte LDS reads and
-// no branch. Exactly curve_eval()'s result for every float s:
+// no branch — musica_lut_eval (curve_lut.h). Exactly curve_eval()'s result for every float s:
 //   * s is first clamped with sf = min(s, 2): NaN becomes 2 (v_min_f32 returns the other operand), as do +inf and every
 //     s > 2; all of them lie above x[32] = 1, where getY() matches no interval and returns 0 — and so does the table
 //     (j = 33, segment {0, 0, 0});
-//   * j = #{x[i] < sf} from the fine or the coarse bucket (musica_device.h); j in 1..32 -> the interval [x[j-1], x[j]];
+//   * j = #{x[i] < sf} from the entry of sf's bit pattern (musica_device.h); j in 1..32 -> the interval [x[j-1], x[j]];
 //   * j = 0 means sf <= x[0] = 0: getY() returns y[0] for sf == 0 (also -0) and 0 for negative sf.
 // Degenerate curves (lut.ok == 0) take curve_eval()'s literal scan.
 struct LutLds {
-    float4 bucket[kLutBuckets + kLutCoarse];
+    float4 bucket[kLutCap];
     float4 seg[kLutPoints + 1];
-    float inv_w;
+    int32_t base;
     uint32_t ok;
 };
 // LUTOK is wave-uniform and decided once per wavefront (k_expand_fast picks the instantiation of the whole march): a per-texel
-// `if (!ok) slow()` put a divergent branch and a call sequence around each of the 16 lookups of a trip.
+// `if (!ok) slow()` put a divergent branch and a call sequence around each of the 16 lookups of a trip. `base` is lut.base in a
+// scalar register.
 template <bool LUTOK>
-__device__ __forceinline__ float curve_eval_lut(const CurveLds& t, const LutLds& lut, float s) {
+__device__ __forceinline__ float curve_eval_lut(const CurveLds& t, const LutLds& lut, int base, float s) {
     if (!LUTOK) return curve_eval(t, s);
-    const float sf = fminf(s, 2.0f);
-    const float kf = sf * lut.inv_w;
-    // bucket index without a branch: the fine bucket int(kf) when kf < 256, else the coarse bucket 256 + int(min(sf * 256, 257)).
-    // The selection happens on the floats (both are <= 257, so one conversion serves either) and the +256 on the integers —
-    // the same values as converting each on its own. A negative kf (s < 0) clamps to bucket 0; its result is replaced below.
-    const bool in_fine = kf < (float)kLutBuckets;
-    const float tsel = in_fine ? kf : fminf(sf * 256.0f, (float)(kLutCoarse - 1));
-    const int idx = max((int)tsel + (in_fine ? 0 : kLutBuckets), 0);
-    const float4 e = lut.bucket[idx];
-    // e.x holds 16 * jlo as an integer (the byte offset of seg[jlo]); each abscissa of the bucket below sf moves one entry on
-    const int joff = __float_as_int(e.x) + (e.y < sf ? 16 : 0) + (e.z < sf ? 16 : 0);
-    const float4 g = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(lut.seg) + joff);
-    const float r = g.z * (sf - g.x) + g.y;
-    return sf < 0.0f ? 0.0f : r;
+    return musica_lut_eval(lut.bucket, lut.seg, base, s);
 }
 
 // GH (level 0 only): the launch also accumulates the gradation histogram — img_relevant.comp + gradation_histogram.comp —
@@ -736,7 +724,7 @@ constexpr int kChSlots = 4, kChCopies = 2;
 #define MUSICA_SD_CH_W 2   // with the CLAHE histogram on board the launch wants 189 registers: 64 bytes of scratch at 3 wavefronts per SIMD
 #endif
 // SD (levels 0 .. 2 of a context that does not store their sdev images): the launch computes the 5 x 5 RMS of the band image itself, from a
-// window of six band rows it keeps in registers — the bits k_sdev_hist* would have stored (the same sum5 / musica_div25 / musica_sqrt8 on the same
+// window of six band rows it keeps in registers — the bits k_sdev_hist* would have stored (the same sum5 / musica_rms25_8 on the same
 // squares, sdev_parts.h) — instead of reading them: 4 B per texel less to read here and 4 B less for the sdev launch to write.
 struct BRow {
     float v[8];     // band columns c .. c+7
@@ -760,9 +748,7 @@ __device__ __forceinline__ void sdev_from_band(const BRow& r0, const BRow& r1, c
     s[5] = sum5(q[3], q[4], q[5], q[6], q[7]);
     s[6] = sum5(q[4], q[5], q[6], q[7], b0);
     s[7] = sum5(q[5], q[6], q[7], b0, b1);
-#pragma unroll
-    for (int j = 0; j < 8; j++) s[j] = musica_div25(s[j]);
-    musica_sqrt8(s);
+    musica_rms25_8(s);
 }
 template <int GAIN, bool NR, bool GH, bool LUTOK, bool CNR48, bool CH = false, bool SD = false>
 __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds& tab, const LutLds& lut, uint32_t* lh, int img, uint32_t* lc = nullptr,
@@ -775,6 +761,7 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
     const int seg = __builtin_amdgcn_readfirstlane((int)(tile.segblock * kWavesPerBlock + (threadIdx.x >> 6)));   // wave-uniform: row arithmetic stays on the scalar unit
     const int k0 = seg * a.rows_per_wave;
     bool saw_zero = false;
+    const int lut_base = (GAIN == GAIN_CURVE && LUTOK) ? __builtin_amdgcn_readfirstlane(lut.base) : 0;   // one LDS word: wave-uniform
     if (k0 < a.Sc) {   // wave-uniform
     const int k1 = min(k0 + a.rows_per_wave, a.Sc);
     const int S = a.S;
@@ -798,7 +785,7 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
         for (int j = 0; j < 8; j++)
             if (g.active && (uint32_t)(g.c + j) > border && (uint32_t)(g.c + j) < lim) colin |= 1u << j;
     }
-    uint32_t* lhc = lh + (GH ? (lane & (kGhCopies - 1)) * kGhStride : 0);
+    uint32_t* lhc = lh + (GH ? 1 + (lane & (kGhCopies - 1)) * kGhStride : 0);   // bin 0 of the lane's copy; the word below it is a spare one too
     // CLAHE tile column of each of the lane's 8 columns, relative to the workgroup's first one (clahe_histogram.comp:34)
     const float fS = (float)S;
     uint32_t chx = 0u;
@@ -816,7 +803,7 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             // contrast_curve_apply.comp:61
-            float p = src[j] * (GAIN == GAIN_CURVE ? curve_eval_lut<LUTOK>(tab, lut, sd[j]) : gain_of<GAIN>(GAIN != GAIN_CONST ? sd[j] : 0.0f, a.high, tab));
+            float p = src[j] * (GAIN == GAIN_CURVE ? curve_eval_lut<LUTOK>(tab, lut, lut_base, sd[j]) : gain_of<GAIN>(GAIN != GAIN_CONST ? sd[j] : 0.0f, a.high, tab));
             if (NR) p = p * f[j];   // noise_reduction.comp:57
             b[j] = low[j] + p;      // img_addition.comp:15
         }
@@ -831,9 +818,9 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
                 const float cur = b[j];
                 saw_zero = saw_zero || (cur == 0.0f);                        // gradation_histogram.comp:24
                 // :26 int(cur * 1024) with "NaN never indexes" (oracle Q6) and "bins outside [0, 1024) are dropped" (Q1) folded into
-                // one unsigned compare: max(NaN, -1) = -1 and every scaled <= -1 convert to a negative int, i.e. a huge unsigned;
-                // (-1, 0) truncates to bin 0 like the shader's int(); everything out of range lands on the spare word 1024
-                const uint32_t bin = min((uint32_t)(int)fminf(fmaxf(cur * (float)MUSICA_GRAD_BINS, -1.0f), 2048.0f), (uint32_t)MUSICA_GRAD_BINS);
+                // the clamp: max(NaN, -1) = -1 and every scaled <= -1 land on the spare word below bin 0, everything >= 1024 on the spare
+                // word above bin 1023 (neither is flushed); (-1, 0) truncates to bin 0 like the shader's int(). The clamped value indexes directly.
+                const int bin = (int)fminf(fmaxf(cur * (float)MUSICA_GRAD_BINS, -1.0f), (float)MUSICA_GRAD_BINS);
                 // :28-30 uint(relevant * 100): 0 outside the border; adding 0 leaves the histogram as it is
                 const bool le090 = ((dark >> j) & 1u) != 0u;
                 const uint32_t w = ((m >> j) & 1u) * (le090 ? w_dark_or_ramp : w_cnr);
@@ -1023,13 +1010,14 @@ __global__ __launch_bounds__(kBlockThreads, W) void k_expand_fast(ExpandArgs a) 
     __shared__ CurveLds tab;
     __shared__ __attribute__((aligned(16))) LutLds lut;
     // four bank-staggered copies of the histogram (lane l adds into copy l % 4, see sdev_parts.h: neighbouring texels share bins,
-    // and lanes of one ds_add that hit the same address are served one after the other); word 1024 of a copy takes what is out of range
+    // and lanes of one ds_add that hit the same address are served one after the other); the words below bin 0 and above bin 1023 of a copy
+    // take what is out of range (lh[0] is the first copy's lower one)
     constexpr int kGhCopies = 4, kGhStride = MUSICA_GRAD_BINS + 8;
-    __shared__ uint32_t lh[GH ? kGhCopies * kGhStride : 1];
+    __shared__ uint32_t lh[GH ? kGhCopies * kGhStride + 1 : 1];
     __shared__ uint32_t lc[CH ? kChCopies * kChSlots * MUSICA_CLAHE_BINS : 1];
     const int img = blockIdx.z;
     if (GH)
-        for (int i = threadIdx.x; i < kGhCopies * kGhStride; i += blockDim.x) lh[i] = 0u;
+        for (int i = threadIdx.x; i < kGhCopies * kGhStride + 1; i += blockDim.x) lh[i] = 0u;
     uint32_t tx0 = 0u, ty0 = 0u;   // CLAHE tile of the workgroup's first column / first row
     if (CH) {
         for (int i = threadIdx.x; i < kChCopies * kChSlots * MUSICA_CLAHE_BINS; i += blockDim.x) lc[i] = 0u;
@@ -1041,9 +1029,10 @@ __global__ __launch_bounds__(kBlockThreads, W) void k_expand_fast(ExpandArgs a) 
         const DevCurve* cv = a.curves + (size_t)img * a.curve_stride;
         const DevCurveLut* lv = a.luts + (size_t)img * MUSICA_COARSER_LEVELS_START;
         curve_to_lds(tab, cv);
-        for (int i = threadIdx.x; i < kLutBuckets + kLutCoarse; i += blockDim.x) lut.bucket[i] = lv->bucket[i];
+        const int nlut = lv->ok ? min((int)lv->n, kLutCap) : 0;   // only the entries in use (a few hundred for typical noise modes)
+        for (int i = threadIdx.x; i < nlut; i += blockDim.x) lut.bucket[i] = lv->bucket[i];
         for (int i = threadIdx.x; i <= kLutPoints; i += blockDim.x) lut.seg[i] = lv->seg[i];
-        if (threadIdx.x == 0) { lut.inv_w = lv->inv_w; lut.ok = lv->ok; }
+        if (threadIdx.x == 0) { lut.base = lv->base; lut.ok = lv->ok; }
         __syncthreads();
     }
     // wave-uniform (one LDS word): readfirstlane tells the compiler so, and the whole march is instantiated per case
@@ -1061,7 +1050,7 @@ __global__ __launch_bounds__(kBlockThreads, W) void k_expand_fast(ExpandArgs a) 
         for (int i = threadIdx.x; i < MUSICA_GRAD_BINS; i += blockDim.x) {
             uint32_t v = 0u;
 #pragma unroll
-            for (int k = 0; k < kGhCopies; k++) v += lh[k * kGhStride + i];
+            for (int k = 0; k < kGhCopies; k++) v += lh[1 + k * kGhStride + i];
             if (v) atomicAdd(&gh[i], v);
         }
         if (CH) {

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/musica.h"
+#include "curve_lut.h"
 
 namespace musica {
 
@@ -50,26 +51,25 @@ struct DevCurve {
 
 // Exact accelerator for getY() on a 33-point contrast curve (levels 0..2): j = #{x[i] < s} from ONE 16-byte table read
 // and two compares, then the segment (x[j-1], y[j-1], slope[j-1]) from a second 16-byte read — no branches.
-//   fine table   : s * inv_w < kLutBuckets (s below 1.75 p): uniform buckets over [0, 1.75 p); a bucket stores how many
-//                  abscissae lie in lower buckets (jlo) and the at most two inside it (xa <= xb, +inf when absent);
-//   coarse table : every other s: buckets of width 1 / 256 over [0, 1] (index min(int(s * 256), kLutCoarse - 1)); only the
-//                  10 abscissae of the last Bezier span (x[23..32], spaced >= 0.01 apart) can lie at or above 1.75 p, so
-//                  jlo = 23 + (tail abscissae in lower coarse buckets) and the bucket holds at most two of them;
+// One table keyed on the float's bit pattern (curve_lut.h has the functions, shared with the host test):
+//   key(s) = bits(min(s, 2)) >> 17 (arithmetic): 64 log-spaced buckets per octave; NaN, +inf and everything above 2 take the key of
+//            2.0 — above x[32] = 1, where getY() matches no interval —, a set sign bit a negative key;
+//   entry k (0 .. n - 1) stands for key base + k, entry 0 also for every key below (s = +-0, negative s, positive s below the
+//            bucket of x[1]: it holds x[0] = 0 alone); base = key(x[1]) - 1, n = key(2.0) - base + 1 <= kLutCap;
+//   an entry stores how many abscissae lie in lower entries (jlo) and the at most two inside it (xa <= xb, +inf when absent):
 //   #{x[i] < s} = jlo + (xa < s) + (xb < s).
-// Bucket membership is decided by the same float expressions when the table is built and when it is read, and both are
-// monotone in x, so the count is exact whatever the rounding: an abscissa in a lower bucket is < s, one in a higher bucket
-// is > s (proof in DESIGN.md, "Exactness notes"). The builder verifies that exactly abscissae 0..22 fall inside the fine
-// table, that no bucket holds three and that x[0] == 0; otherwise (e.g. maxBin == 0) ok = 0 and the level takes the
-// literal scan.
-constexpr int kLutBuckets = 256;    // fine buckets
-constexpr int kLutCoarse = 258;     // coarse buckets: int(s * 256) = 0 .. 256, and one for everything above
-constexpr int kLutTailFirst = 23;   // abscissae 0..22 are <= 1.4 p and always inside the fine table's range
-constexpr int kLutPoints = 33;      // 3 x generateCurve(i <= 10), contrast_curve_generate.comp:72-86
+// Membership is decided by the same function of the value when the table is built and when it is read, and that function is
+// monotone (the bit pattern of a non-negative float grows with its value; the minimum, the shift and the clamp at base keep that),
+// so the count is exact: an abscissa in a lower entry is < s, one in a higher entry is > s ("Exactness notes"). The
+// builder verifies that the curve is monotone with 33 points, that x[0] == 0 < x[1], that the table fits kLutCap and that no entry
+// holds three abscissae; otherwise (e.g. maxBin == 0) ok = 0 and the level takes the literal scan. The abscissae depend on the
+// noise mode alone: every maxBin 1 .. 2048 gets a table (tests/test_curve_lut_host.py).
 struct DevCurveLut {
-    float inv_w;
+    int32_t base;
     uint32_t ok;
-    uint32_t pad0, pad1;
-    float4 bucket[kLutBuckets + kLutCoarse];   // {16 * jlo (integer bits: byte offset of seg[jlo]), xa, xb, unused}
+    uint32_t n;          // entries in use
+    uint32_t pad0;
+    float4 bucket[kLutCap];                     // {16 * jlo (integer bits: byte offset of seg[jlo]), xa, xb, unused}
     float4 seg[kLutPoints + 1];                 // seg[j] = {x[j-1], y[j-1], slope[j-1], 0}; seg[0] = {x[0], y[0], 0, 0}; seg[33] = 0
 };
 

@@ -137,9 +137,7 @@ __device__ __forceinline__ void sdev_values(const SRow& r0, const SRow& r1, cons
     s[5] = sum5(q[3], q[4], q[5], q[6], q[7]);
     s[6] = sum5(q[4], q[5], q[6], q[7], b0);
     s[7] = sum5(q[5], q[6], q[7], b0, b1);
-#pragma unroll
-    for (int j = 0; j < 8; j++) s[j] = musica_div25(s[j]);  // img_sdev.comp:30 (exact x / 25, exact_math.h)
-    musica_sqrt8(s);                                         // img_sdev.comp:30 (exact sqrt, exact_math.h)
+    musica_rms25_8(s);   // img_sdev.comp:30, sqrt(sum / 25): exact quotient and exact sqrt behind one range test on the sums (exact_math.h)
 }
 template <bool A8>
 __device__ __forceinline__ void sdev_store(const float (&s)[8], const SCfg& g, float* __restrict__ drow, const Buf& db, uint32_t row_off) {
