@@ -379,6 +379,21 @@ int musica_sim_rotate_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src
  * side N - 20 (harness.apply_symmetry). Refused before any device work: a NULL context, a slot out of range, dst_slot == src_slot, a
  * source slot never written, element > 7, an image too small for the margin. Marks dst_slot written. */
 int musica_sim_transform_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t element);
+/* ---- resolution loss: the exact binomial blur (new, not in the reference) ----
+ * harness.binomial_blur(image, radius) is the contract: of a 2-D uint16 or uint8 plane, with a radius r in 1 .. MUSICA_BLUR_MAX_RADIUS,
+ *   weights   w_k = C(2r, k), k = 0 .. 2r; they sum to 4^r
+ *   borders   indices clamped (edge replicated), no fill value
+ *   out[y, x] = (sum_i sum_j w_i w_j in[clamp(y + i - r), clamp(x + j - r)] + 2^(4r - 1)) >> 4r
+ * ONE rounding, after the full 2-D sum, halves rounded up; no rounding between the two passes. The result has the input's type; a
+ * constant plane is preserved, so nothing saturates. Every intermediate is an exact integer, which is where the largest radius comes
+ * from: the row pass of u16 data needs 16 + 2r <= 32 bits, so it fits u32 exactly up to r = 8; the full sum needs 16 + 4r <= 48 bits
+ * (u64). At r = 8 the blur is a Gaussian of sigma = sqrt(r / 2) = 2 pixels. The device results are bit-identical to that statement and
+ * repeat from call to call (kernels_blur.hip). */
+#define MUSICA_BLUR_MAX_RADIUS 8
+/* binomial_blur(reference slot `src_slot`, radius) of the (N - 20)^2 u8 plane into `dst_slot` (device to device, on the ctx stream).
+ * Refused before any device work: a NULL context, a slot out of range, dst_slot == src_slot, a source slot never written, a radius outside
+ * 1 .. MUSICA_BLUR_MAX_RADIUS, an image too small for the margin. Marks dst_slot written; changes no other slot. */
+int musica_sim_blur_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t radius);
 /* (N - 20)^2 bytes of reference slot `slot` to the host (synchronous); the slot must have been written. */
 int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
 
@@ -625,6 +640,11 @@ int musica_alter_set_source(musica_ctx* ctx, const uint16_t* pixels);
  * image_index >= batch, shifts or shutters that leave nothing, a margin that leaves no crop, a non-finite or non-positive sigma or factor,
  * a non-finite matrix or offset, a symmetry element outside 0 .. 7. It changes no other image of the input buffer, no result of the last step and no reference slot. */
 int musica_alter(musica_ctx* ctx, uint32_t image_index, const musica_alteration* spec);
+/* binomial_blur(source plane, radius) (above, at musica_sim_blur_reference) into image `image_index` of the input buffer, enqueued on the
+ * ctx stream, with musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step and no reference
+ * slot. An entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT. Refused before any
+ * device work: no source, image_index >= batch, a radius outside 1 .. MUSICA_BLUR_MAX_RADIUS. */
+int musica_alter_blur(musica_ctx* ctx, uint32_t image_index, uint32_t radius);
 /* Test hook: the N x N integer draws of a noise alteration (k of COLLIMATOR / POISSON, for every pixel; the truncated noise of GAUSSIAN),
  * the same numbers musica_alter uses. Synchronous. */
 int musica_alter_draws(musica_ctx* ctx, const musica_alteration* spec, int32_t* dst);

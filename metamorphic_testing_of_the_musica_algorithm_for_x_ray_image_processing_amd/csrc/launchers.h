@@ -295,6 +295,11 @@ void launch_percentile(hipStream_t st, const PctRegion& g, uint32_t* hist, doubl
 // plane into another (the planes must not overlap); any n >= 1
 void launch_symmetry_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, int element);
 void launch_symmetry_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int element);
+// kernels_blur.hip: harness.binomial_blur(plane, radius), the exact binomial blur with weights C(2 radius, k) and clamped borders, of a
+// dense n x n plane into another (the planes must not overlap); any n >= 1, radius 1 .. kBlurMaxRadius
+constexpr int kBlurMaxRadius = 8;   // MUSICA_BLUR_MAX_RADIUS
+void launch_blur_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, int radius);
+void launch_blur_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int radius);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -1,7 +1,7 @@
 // musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the four query calls
 // (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip), the ensemble accumulators
 // (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
+// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
@@ -126,6 +126,20 @@ int musica_sim_transform_reference(musica_ctx* c, uint32_t dst_slot, uint32_t sr
     uint8_t* dst = sim_slot_for_write(c, "musica_sim_transform_reference", dst_slot);
     if (!dst) return 0;
     launch_symmetry_u8(c->stream, c->study.slot[src_slot], dst, (int)sim_side(c), (int)element);
+    HIP_OK(hipGetLastError());
+    c->study.written[dst_slot] = true;
+    return 1;
+}
+
+static_assert(kBlurMaxRadius == MUSICA_BLUR_MAX_RADIUS, "kernels_blur.hip instantiates the radii of include/musica.h");
+
+int musica_sim_blur_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t radius) {
+    if (!c) return fail("musica_sim_blur_reference: ctx is NULL");
+    if (!sim_check_pair(c, "musica_sim_blur_reference", dst_slot, src_slot)) return 0;
+    if (radius < 1 || radius > MUSICA_BLUR_MAX_RADIUS) return fail("musica_sim_blur_reference: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS);
+    uint8_t* dst = sim_slot_for_write(c, "musica_sim_blur_reference", dst_slot);
+    if (!dst) return 0;
+    launch_blur_u8(c->stream, c->study.slot[src_slot], dst, (int)sim_side(c), (int)radius);
     HIP_OK(hipGetLastError());
     c->study.written[dst_slot] = true;
     return 1;
@@ -829,6 +843,16 @@ static int alter_args(musica_ctx* c, const char* fn, const musica_alteration* s,
     return 1;
 }
 
+// Before an alteration writes into d_input: when the last step read d_input, keep it for the getters that recompute from the input.
+static int alter_keep_input(musica_ctx* c, const char* fn) {
+    if (c->cur_input != c->d_input) return 1;
+    const size_t nn = (size_t)c->N * c->N;
+    if (!ensure(c, &c->d_input_kept, (size_t)c->B * nn)) return fail("%s: device allocation failed", fn);
+    HIP_OK(hipMemcpyAsync(c->d_input_kept, c->d_input, (size_t)c->B * nn * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
+    c->cur_input = c->d_input_kept;
+    return 1;
+}
+
 int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
     if (!c) return fail("musica_alter: ctx is NULL");
     AlterDev a;
@@ -837,11 +861,7 @@ int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
     CHECK_CTX(c);
     if (!alter_scratch(c)) return fail("musica_alter: device allocation failed");
     const size_t nn = (size_t)c->N * c->N;
-    if (c->cur_input == c->d_input) {   // the last step read d_input: keep it for the getters that recompute from the input
-        if (!ensure(c, &c->d_input_kept, (size_t)c->B * nn)) return fail("musica_alter: device allocation failed");
-        HIP_OK(hipMemcpyAsync(c->d_input_kept, c->d_input, (size_t)c->B * nn * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
-        c->cur_input = c->d_input_kept;
-    }
+    if (!alter_keep_input(c, "musica_alter")) return 0;
     const double* fill = nullptr;
     if (s->kind == MUSICA_ALTER_TRANSLATE) {   // clamp_translation: the 99th percentile of image[top:b_bottom, left:b_right]
         const int n = c->N, b_right = s->dx > 0 ? 12 : n, b_bottom = s->dy > 0 ? 12 : n;
@@ -853,6 +873,18 @@ int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
     }
     if (s->kind == MUSICA_ALTER_SYMMETRY) launch_symmetry_u16(c->stream, c->study.d_alter_src, c->d_input + idx * nn, c->N, s->dx);   // a permutation: kernels_symmetry.hip
     else launch_alter(c->stream, c->study.d_alter_src, c->d_input + idx * nn, nullptr, a, fill);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+int musica_alter_blur(musica_ctx* c, uint32_t idx, uint32_t radius) {
+    if (!c) return fail("musica_alter_blur: ctx is NULL");
+    if (!c->study.d_alter_src) return fail("musica_alter_blur: no source plane (musica_alter_set_source)");
+    if (radius < 1 || radius > MUSICA_BLUR_MAX_RADIUS) return fail("musica_alter_blur: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS);
+    CHECK_IMG(c, idx);
+    CHECK_CTX(c);
+    if (!alter_keep_input(c, "musica_alter_blur")) return 0;
+    launch_blur_u16(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, (int)radius);   // kernels_blur.hip
     HIP_OK(hipGetLastError());
     return 1;
 }

@@ -33,6 +33,8 @@ GAUSS_SIGMAS = [4.0, 16.0, 64.0, 256.0, 1024.0]
 POISSON_FACTORS = [0.1, 0.05, 0.025, 0.0125, 0.00625]
 # not in the reference: the non-identity symmetries of the square (apply_symmetry), rows d4_<e> of a study run with `symmetries`
 SYMMETRIES = (1, 2, 3, 4, 5, 6, 7)
+# not in the reference: the radii of the resolution-loss rows (binomial_blur), rows blur_<r> of a study run with `blurs`
+BLURS = (1, 2, 4, 8)
 
 
 def scaled(values, image_size):
@@ -110,6 +112,30 @@ def apply_symmetry(image, element):
     if image.ndim != 2 or image.shape[0] != image.shape[1]:
         raise ValueError("the symmetries of the square need a square image, got %r" % (image.shape,))
     return np.ascontiguousarray(np.rot90(image if element < 4 else image.T, element & 3))
+
+
+def binomial_blur(image, radius):
+    """The exact binomial blur of a 2-D uint16 or uint8 plane (not in the reference's script): resolution loss in integers. With
+    r = radius in 1 .. BLUR_MAX_RADIUS and the weights w_k = C(2r, k), k = 0 .. 2r (their sum is 4^r),
+        out[y, x] = (sum_i sum_j w_i w_j in[clamp(y + i - r), clamp(x + j - r)] + 2^(4r - 1)) >> 4r
+    with indices clamped to the plane (edge replicated, no fill value). ONE rounding, after the full 2-D sum, halves rounded up; nothing
+    is rounded between the two passes. The result has the input's dtype; a constant plane is preserved, so nothing saturates. The largest
+    radius follows from the widths: the row pass of u16 data needs 16 + 2r <= 32 bits, the full sum 16 + 4r <= 48 (u64 here). At r = 8
+    the blur is a Gaussian of sigma = sqrt(r / 2) = 2 pixels. This is the contract of musica_alter_blur and musica_sim_blur_reference
+    (include/musica.h), which are bit-identical to it."""
+    r = int(radius)
+    if not 1 <= r <= mp.BLUR_MAX_RADIUS:
+        raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
+    image = np.asarray(image)
+    if image.ndim != 2 or image.dtype not in (np.uint16, np.uint8) or not image.size:
+        raise ValueError("binomial_blur needs a non-empty 2-D uint16 or uint8 plane, got %r %s" % (image.shape, image.dtype))
+    acc = image.astype(np.uint64)
+    for axis in (1, 0):           # rows, then columns: exact integers, so the order changes nothing
+        padded = np.pad(acc, [(r, r) if a == axis else (0, 0) for a in (0, 1)], mode="edge")   # the clamped indices
+        acc = np.zeros_like(acc)
+        for k in range(2 * r + 1):
+            acc += np.uint64(math.comb(2 * r, k)) * (padded[k:k + acc.shape[0]] if axis == 0 else padded[:, k:k + acc.shape[1]])
+    return ((acc + np.uint64(1 << (4 * r - 1))) >> np.uint64(4 * r)).astype(image.dtype)
 
 
 # ---- similarity metrics (script.py:143-198) ----------------------------------------------------------
@@ -810,6 +836,20 @@ def roi_symmetry(shape):
     return (0, 0, 0, 0, shape[1], shape[0])
 
 
+def register_blur(alt, unalt, radius):
+    """The altered result against the unaltered result blurred like the alteration, both inset by the radius: within `radius` pixels of
+    the output plane's border the blurred reference is built from clamped neighbours, while the altered output there came from real
+    neighbours in the processing margin."""
+    r = int(radius)
+    h, w = alt.shape
+    return alt[r:max(h - r, r), r:max(w - r, r)], binomial_blur(unalt, r)[r:max(h - r, r), r:max(w - r, r)]
+
+
+def roi_blur(shape, radius):
+    """The full frame inset by the radius, as the region of a device-side comparison; None when a side falls under 7."""
+    return _inset((0, 0, 0, 0, shape[1], shape[0]), int(radius))
+
+
 # ---- running the pipeline -------------------------------------------------------------------------
 
 class Runner:
@@ -906,7 +946,8 @@ TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "referenc
 
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
-              tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False):
+              tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
+              blurs=None):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -969,7 +1010,15 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     "hf_fraction" (covariance_row). The direct region is the full frame inset by R; the registered one the row's registered region inset
     by R, None where the row has none or an inset side is under 7. One musica_sim_ensemble_track call follows the row's reset and one
     musica_sim_ensemble_covariance call ends it. covariance_tiles: the dicts also carry "table" and "tile_tables". With covariance=0 the
-    rows, keys and launches are exactly as before."""
+    rows, keys and launches are exactly as before.
+
+    blurs: radii of the resolution-loss rows (binomial_blur; BLURS for 1, 2, 4, 8), each in 1 .. BLUR_MAX_RADIUS, else ValueError before
+    any work. None or empty adds nothing. Otherwise rows blur_<r> follow the d4_* rows: the raw image blurred with radius r (on the
+    device: alter_blur), "direct" against the unaltered result (how much of the input's resolution loss reaches the output),
+    "registered" over the frame inset by r (roi_blur) against the unaltered result blurred with the same radius (what a linear,
+    shift-invariant processor would not show; None when the inset frame has a side under 8). On the device that reference goes into
+    slot 1 and the blurred vendor image into slot 3 (musica_sim_blur_reference). Like the d4 rows they draw nothing from `rng` and take
+    no ordinal; vendor, tone, scales and displacement apply to them as to a d4 row."""
     rng = rng or np.random.default_rng(0)
     n = raw.shape[0]
     if vendor is not None:
@@ -1011,6 +1060,10 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     for e in symmetries:
         if not 0 <= e <= 7:
             raise ValueError("symmetry element %d is not in 0 .. 7" % e)
+    blurs = [int(r) for r in (blurs or ())]
+    for r in blurs:
+        if not 1 <= r <= mp.BLUR_MAX_RADIUS:
+            raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
     device = getattr(runner, "device_metrics", False)
     alter_on_device = getattr(runner, "device_alterations", False)
     ref8 = vendor_to_u8(vendor) if vendor is not None and not device else None   # the host metrics' vendor image
@@ -1242,7 +1295,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         same comparison (None: no registration); slot() the reference slot its b side lies in on the device, filled by that call where
         it is not the unaltered result's; plane() the full host plane it lies in. The noise rows have only the first three. add() makes a
         row's calls before the next row is built: the rows' order is the order of the `rng` draws. The device's noise draws take the
-        row's ordinal in the study as their stream; the d4 rows draw nothing and take no ordinal."""
+        row's ordinal in the study as their stream; the d4 and blur rows draw nothing and take no ordinal."""
         p, ordinal = runner.proc, itertools.count(1)
         for s in shutters:
             k = next(ordinal)
@@ -1269,6 +1322,9 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         for e in symmetries:
             yield ("d4_%d" % e, lambda: apply_symmetry(raw, e), lambda: p.alter_symmetry(e), lambda a, u: register_symmetry(a, u, e),
                    lambda: roi_symmetry(shape), lambda: moved_slot(e, p.sim_transform_reference, apply_symmetry), lambda: apply_symmetry(unalt, e))
+        for r in blurs:
+            yield ("blur_%d" % r, lambda: binomial_blur(raw, r), lambda: p.alter_blur(r), lambda a, u: register_blur(a, u, r),
+                   lambda: roi_blur(shape, r), lambda: moved_slot(r, p.sim_blur_reference, binomial_blur), lambda: binomial_blur(unalt, r))
 
     for row in study():
         add(*row)
@@ -1592,6 +1648,18 @@ def symmetry_list(text):
     return elements
 
 
+def blur_list(text):
+    """--blurs' comma list of radii 1 .. BLUR_MAX_RADIUS."""
+    import argparse
+    try:
+        radii = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a comma-separated list of radii 1 .. %d, got %r" % (mp.BLUR_MAX_RADIUS, text))
+    if not radii or any(not 1 <= r <= mp.BLUR_MAX_RADIUS for r in radii):
+        raise argparse.ArgumentTypeError("blur radii are 1 .. %d, got %r" % (mp.BLUR_MAX_RADIUS, text))
+    return radii
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Metamorphic study of raw images (or a seeded phantom) on the HIP MUSICA path")
@@ -1612,6 +1680,9 @@ def main(argv=None):
     ap.add_argument("--symmetries", nargs="?", const=SYMMETRIES, default=None, type=symmetry_list, metavar="E,E,...",
                     help="add the rows d4_<e>: the raw image under elements of the square's symmetry group (1, 3: quarter turns, 2: half turn, "
                          "4: transpose, 5, 7: flips, 6: anti-transpose), compared over the whole frame; without a list, all seven")
+    ap.add_argument("--blurs", nargs="?", const=BLURS, default=None, type=blur_list, metavar="R,R,...",
+                    help="add the rows blur_<r>: the raw image under the exact binomial blur of radius r (1 .. 8; sigma = sqrt(r / 2) pixels), "
+                         "compared directly and, inset by r, with the unaltered result blurred alike; without a list, 1,2,4,8")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -1688,6 +1759,8 @@ def main(argv=None):
         shift_args.update(ensemble=args.ensemble, ensemble_tiles=bool(args.ensemble_maps))
     if args.covariance:
         shift_args.update(covariance=args.covariance, covariance_tiles=bool(args.covariance_maps))
+    if args.blurs:
+        shift_args["blurs"] = args.blurs
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

@@ -149,6 +149,7 @@ class SimJointResult(C.Structure):
 
 
 SIM_MAX_RADIUS = 16         # MUSICA_SIM_MAX_RADIUS
+BLUR_MAX_RADIUS = 8         # MUSICA_BLUR_MAX_RADIUS
 SIM_TILE = 64               # MUSICA_SIM_TILE
 
 
@@ -343,6 +344,8 @@ ABI = {
     "musica_sim_rotate_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "musica_sim_get_reference": (C.c_int, [_VP, C.c_uint32, _U8P]),
     "musica_sim_transform_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_sim_blur_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_alter_blur": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -718,6 +721,12 @@ class MusicaProcessing:
             raise ValueError("symmetry element %d is not in 0 .. 7" % element)
         self._ok(self._lib.musica_sim_transform_reference(self._h, int(dst_slot), int(src_slot), int(element)), "musica_sim_transform_reference")
 
+    def sim_blur_reference(self, dst_slot, src_slot, radius):
+        """Reference slot `src_slot` as harness.binomial_blur(slot, radius) (radius 1 .. BLUR_MAX_RADIUS) into `dst_slot`, on the device."""
+        if int(radius) < 0:
+            raise ValueError("blur radius %d is not in 1 .. %d" % (radius, BLUR_MAX_RADIUS))
+        self._ok(self._lib.musica_sim_blur_reference(self._h, int(dst_slot), int(src_slot), int(radius)), "musica_sim_blur_reference")
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -904,6 +913,12 @@ class MusicaProcessing:
     def alter_symmetry(self, element, image_index=0):
         """harness.apply_symmetry(src, element): np.rot90(src if element < 4 else src.T, element & 3), element 0 .. 7."""
         self.alter(Alteration(kind=ALTER_SYMMETRY, dx=int(element)), image_index)
+
+    def alter_blur(self, radius, image_index=0):
+        """harness.binomial_blur(src, radius): the exact binomial blur with weights C(2 radius, k), radius 1 .. BLUR_MAX_RADIUS."""
+        if int(radius) < 0:
+            raise ValueError("blur radius %d is not in 1 .. %d" % (radius, BLUR_MAX_RADIUS))
+        self._ok(self._lib.musica_alter_blur(self._h, int(image_index), int(radius)), "musica_alter_blur")
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""
