@@ -486,6 +486,37 @@ def k_apply_gradation_curve(img, curve):
     return out
 
 
+CLAHE_TILES, CLAHE_BINS = 4, 256
+
+
+def k_clahe_histogram(img, relevant):
+    """hist[tx][ty][bin] of one dispatch over a cleared histogram image."""
+    a, r = _sq(img), _sq(relevant)
+    assert a.shape == r.shape
+    h = np.zeros((CLAHE_TILES, CLAHE_TILES, CLAHE_BINS), dtype=np.uint32)
+    lib().musica_oracle_k_clahe_histogram(_f32p(a), _f32p(r), a.shape[0], h.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return h
+
+
+def k_clahe_grad_curve(hist):
+    """points[tx][ty][i] = (x, y) as a (4, 4, 256, 2) float32 array."""
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    assert h.shape == (CLAHE_TILES, CLAHE_TILES, CLAHE_BINS)
+    pts = np.zeros((CLAHE_TILES, CLAHE_TILES, CLAHE_BINS, 2), dtype=np.float32)
+    lib().musica_oracle_k_clahe_grad_curve(h.ctypes.data_as(C.POINTER(C.c_uint32)), pts.ctypes.data_as(C.POINTER(Point)))
+    return pts
+
+
+def k_clahe_grad_curve_apply(img, points):
+    """points: (4, 4, 256, 2) float32, [tx][ty][i] = (x, y)."""
+    a = _sq(img)
+    pts = np.ascontiguousarray(points, dtype=np.float32)
+    assert pts.shape == (CLAHE_TILES, CLAHE_TILES, CLAHE_BINS, 2)
+    out = np.empty_like(a)
+    lib().musica_oracle_k_clahe_grad_curve_apply(_f32p(a), a.shape[0], pts.ctypes.data_as(C.POINTER(Point)), _f32p(out))
+    return out
+
+
 def k_render_noise_hist(hist, max_value, max_bin):
     h = np.ascontiguousarray(hist, dtype=np.uint32)
     out = np.empty((128, 512, 4), dtype=np.uint8)

@@ -19,8 +19,16 @@
  *   (ref_bmp.c compiles the reference's vendored stb_image_write.h).
  *   STILL UNPINNED: the dispatch script (src/vk_processing.cpp, Vulkan host
  *   code), whatever a GPU driver does where GLSL is undefined, and the vendor
- *   outputs. Inputs on which the shaders themselves are undefined and the CLAHE
- *   trio rest on the analytic known-answer tests (tests/test_oracle_kat.py).
+ *   outputs. Inputs on which the shaders themselves are undefined rest on the
+ *   analytic known-answer tests (tests/test_oracle_kat.py). The CLAHE trio
+ *   (musica_oracle_k_clahe_histogram / _grad_curve / _grad_curve_apply) is not
+ *   hosted against the reference's text (clahe_grad_curve_apply.comp reads one
+ *   past its array); it is pinned by tests/test_clahe_kat.py: 14 tests, 66
+ *   cases, each function called alone, expected values derived by hand from
+ *   the shader text in exact fractions. A misreading shared by those
+ *   derivations and this file would still pass, and the two choices GLSL
+ *   leaves open (uint() of a negative tile coordinate -> 0, points[256] ->
+ *   (0, 0)) are this project's.
  *
  * Two arithmetic orders:
  *   MUSICA_ORDER_REFERENCE  literal 25-tap loops, x-outer / y-inner, exactly

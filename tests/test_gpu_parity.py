@@ -9,7 +9,7 @@ Bars (stated here so the numbers live next to the assertions):
     final 8-bit image: at most 0.1 % of pixels differ (getY's x > 1 -> 0 discontinuity and bin
     flips at 1e-7-level differences are inherent to the reference's semantics).
 PARITY note: the oracle's per-shader arithmetic is pinned to the reference's own shader text (test_reference_shaders.py, rules Q1 to Q6 and
-the constant-folding rule of oracle/glsl_host.h) and by the analytic KATs in test_oracle_kat.py; the dispatch script, driver behaviour where GLSL
+the constant-folding rule of oracle/glsl_host.h) and by the analytic KATs in test_oracle_kat.py (the CLAHE trio: test_clahe_kat.py); the dispatch script, driver behaviour where GLSL
 is undefined and the vendor outputs stay unpinned
 (no golden vectors exist in the reference for this path).
 """
