@@ -1,0 +1,94 @@
+"""One sha256 per study entry point over everything it returns, for comparing two trees bit for bit: the check on the fixed f64
+summation order of the study's reductions (csrc/study_device.h), which the tolerance-based restatement tests cannot see. The inputs are
+seeded phantoms; the shapes are the smallest at which the kernels can still go wrong:
+  * compare, joint and multiscale (scales 1, 3, 5) at N = 532: 512 x 512 outputs, three 250-column strips with a ragged last one, every
+    scale up to 4 at least 7 wide; one full frame and one odd-sized offset region;
+  * displace, ensemble add / result and track / covariance at radii 3 and 16, 17 realisations in two adds, at N = 151: 131 x 131 outputs,
+    3 x 3 tiles with a 3-pixel ragged tail (a masked last chunk), and one region narrower than 16 pixels (a tile of the ragged chunk only);
+  * the four dst / src slot operations at N = 151, a symmetry with a transpose and a blur of radius 8 among them.
+Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
+(the ABI does not promise f64 bits), so they are not committed as goldens.
+  python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
+import argparse
+import hashlib
+import json
+import os
+import struct
+import sys
+
+import numpy as np
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.tree))
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd.phantom import phantom
+
+if mp.device_count() < 1:
+    raise SystemExit("study_digest: no HIP device")
+
+
+def raw(v):
+    """The bytes of a returned value: arrays as they lie in memory, floats as IEEE doubles, integers as 64 bits, containers in order."""
+    if isinstance(v, np.ndarray):
+        return np.ascontiguousarray(v).tobytes()
+    if isinstance(v, dict):
+        return b"".join(k.encode() + raw(v[k]) for k in sorted(v))
+    if isinstance(v, (list, tuple)):
+        return b"".join(raw(x) for x in v)
+    if isinstance(v, float):
+        return struct.pack("<d", v)
+    return struct.pack("<q" if v < 0 else "<Q", int(v))
+
+
+digests = {}
+
+
+def note(name, value):
+    digests[name] = hashlib.sha256(raw(value)).hexdigest()
+
+
+def stepped(n, batch):
+    p = mp.MusicaProcessing()
+    assert p.init(n, levels=0, batch=batch, flags=mp.FLAG_NO_AUTOTUNE), mp.last_error()
+    assert p.execute(np.stack([phantom(n, 1 + i, noise=4.0) for i in range(batch)])), mp.last_error()
+    p.sim_capture(0, 0)   # slot 0: image 0's output; the other images differ from it by their noise
+    return p
+
+
+# ---- strips: N = 532 --------------------------------------------------------------------------------------------------------------------
+N = 532
+NW = N - 2 * mp.OUT_MARGIN
+p = stepped(N, 2)
+qs = [(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 13, 7, 5, 11, 301, 173)]
+note("musica_sim_compare", p.sim_compare(qs))
+note("musica_sim_joint", p.sim_joint(qs, tables=True))   # kernels_joint.hip takes its typedefs from the shared header
+for scales in (1, 3, 5):
+    note("musica_sim_multiscale_%d" % scales, p.sim_multiscale(qs, scales))
+p.cleanup()
+
+# ---- tiles: N = 151 ---------------------------------------------------------------------------------------------------------------------
+N = 151
+NW = N - 2 * mp.OUT_MARGIN
+K = (9, 8)
+p = stepped(N, sum(K))
+for r in (3, 16):
+    # the largest region the radius admits, a ragged one from mid-tile, one narrower than a 16-pixel chunk
+    qs = [(1, 0, r, r, r, r, NW - 2 * r, NW - 2 * r), (2, 0, 40, 33, 38, 29, 70, 75), (3, 0, r + 20, 30, r + 1, r + 2, 11, 70)]
+    note("musica_sim_displace_r%d" % r, p.sim_displace(qs, r, tables=True, tiles=True))
+    p.sim_ensemble_reset()
+    p.sim_ensemble_track([(0, 0, r, 0, r, 0, NW - 2 * r, NW - r), (0, 0, 40, 33, 40, 33, 70, 75), (0, 0, r + 20, 30, 0, 0, 11, 70)], r)
+    p.sim_ensemble_add(0, K[0])
+    p.sim_ensemble_add(K[0], K[1])
+    note("musica_sim_ensemble_get_r%d" % r, p.sim_ensemble_get())
+    note("musica_sim_ensemble_result_r%d" % r, p.sim_ensemble_result([(0, 0, 0, 0, 0, 0, NW, NW)] + qs, tiles=True))
+    note("musica_sim_ensemble_covariance_r%d" % r, p.sim_ensemble_covariance(tables=True, tiles=True))
+p.sim_rotate_reference(1, 0, 7.0)
+p.sim_transform_reference(2, 0, 5)   # np.rot90(x.T, 1)
+p.sim_blur_reference(3, 0, 8)
+p.sim_remap_reference(4, 0, (np.arange(256) * 7 + 3).astype(np.uint8))
+for name, slot in (("rotate", 1), ("transform", 2), ("blur", 3), ("remap", 4)):
+    note("musica_sim_%s_reference" % name, p.sim_get_reference(slot))
+p.cleanup()
+print(json.dumps(digests))

@@ -9,22 +9,17 @@
 //   across the realisations of the launch. It loops over the `count` graded planes, keeps the tile's u64 sums in registers (T <= 561
 //   entries, at most 3 per thread) and ends with ONE plain read-modify-write of its tile table: no global atomics, a tile has one owner,
 //   launches on one stream follow each other.
-//   * Staging, per realisation. The window the tile's lags reach, (tile_w + 2 R) x (tile_h + R) pixels from (64 tx - R, 64 ty) of the
-//     region, goes into LDS as packed bytes from byte 0 of each row (25 words staged, row pitch 41 words), quantised once. Bytes past the
-//     window are 0 and never loaded: musica_sim_ensemble_track refuses a region whose grown window leaves the plane, so everything that is
-//     loaded lies inside it. The tile itself (the window from byte R of each row on) is then copied inside LDS into rows of 16 words at
-//     a 16-byte aligned pitch of 20 words with v_alignbyte_b32; pixels at x >= tile_w of a ragged tile are cleared there.
-//   * A work item is (lag, block of 8 tile rows): T * ceil(tile_h / 8) items, dealt to the threads round-robin with the lag fastest, so
-//     the lanes of a wavefront hold neighbouring dx of one or two dy and read the same 16 B of the tile row (an LDS broadcast). Per 16
-//     pixels an item reads those 16 B and four new words of the shifted row (the fifth is carried), forms the four shifted words with
-//     v_alignbyte_b32 (shift (dx + R) & 3 bytes, word offset (dx + R) >> 2: one alignment per lane for the whole item) and does four
-//     v_dot4_u32_u8: 0.25 instructions per pixel and lag, half of k_displace's.
+//   * Staging, per realisation (the layout, the work items and the bank argument: study_device.h, packed byte windows; they are
+//     k_displace's). The window the tile's lags reach, (tile_w + 2 R) x (tile_h + R) pixels from (64 tx - R, 64 ty) of the region, goes
+//     into LDS from byte 0 of each row, quantised once. Bytes past the window are 0 and never loaded: musica_sim_ensemble_track refuses
+//     a region whose grown window leaves the plane, so everything that is loaded lies inside it. The tile itself (the window from byte R
+//     of each row on) is then copied inside LDS into the tile's rows with v_alignbyte_b32; pixels at x >= tile_w of a ragged tile are
+//     cleared there.
+//   * There are T * ceil(tile_h / 8) work items. Per 16 pixels an item forms the four shifted words and does four v_dot4_u32_u8: 0.25
+//     instructions per pixel and lag, half of k_displace's.
 //   * Padding. Rows past tile_h are not visited. A pixel is masked by ITS position in the region (the tile copy holds 0 at x >= tile_w, so
 //     the products of a padded pixel are 0 for every lag), never by where its partner lies: a pixel inside the region does see partners
 //     beyond the region's edge.
-//   * Banks. ds_read_b32 banks are word % 32 over 32-lane groups. 32 neighbouring lags span at most 9 words of a window row (33 dx) and
-//     rows one apart are 41 % 32 = 9 banks apart, so the groups of R >= 3 are conflict-free; lanes with equal words broadcast
-//     (k_displace's argument: the window has its layout).
 //   * Ranges. An item's sum is <= 8 * 64 * 255^2 < 2^25 and goes to its lag's entry of an LDS table with one integer LDS atomic; an entry
 //     is at most 64 * 64 * 255^2 = 266 342 400 < 2^28 per realisation. The u32 table is flushed into the u64 registers after EVERY
 //     realisation (16 would still fit, 17 would not).
@@ -33,43 +28,30 @@
 //   <= 8 * 64 * 261120^2 < 2^46, into a u64 LDS table (a tile's U < 2^48). The tile's C(d) = K P(d) - U(d) is written as i64 and added to
 //   the region's table with one 64-bit integer atomic per lag: the wrapped two's-complement sum is the signed one (as k_ens_stats' bias_sum).
 // Everything is integer arithmetic: exact, and the same from call to call whatever the order. No f64.
-#include "kernels_common.h"
-#include "launchers.h"
+#include "study_device.h"
 
 namespace musica {
 
-static_assert(kCovTile == MUSICA_SIM_TILE && kCovMaxRadius == MUSICA_SIM_MAX_RADIUS, "k_cov_add's tiles and radii are musica_sim_displace's");
-
-constexpr int kCovThreads = 256;
-constexpr int kCovRows = 8;                                  // tile rows of a work item
-constexpr int kCovAPitch = 20;                               // words per LDS row of the tile (16 used; 16-byte aligned rows)
-constexpr int kCovWWords = 25;                               // words per LDS row of the window that are staged: 64 + 2 * 16 + 3 bytes, rounded up
-constexpr int kCovWPitch = 41;                               // words per LDS row of the window
-constexpr int kCovWinRows = kCovTile + kCovMaxRadius;        // 80
-constexpr int kCovMaxLags = (kCovMaxRadius + 1) * (2 * kCovMaxRadius + 1);   // 561
+constexpr int kCovThreads = kStudyThreads;
+constexpr int kCovWinRows = kSimTile + kSimMaxRadius;        // 80
+constexpr int kCovMaxLags = (kSimMaxRadius + 1) * (2 * kSimMaxRadius + 1);   // 561
 constexpr int kCovPerThread = (kCovMaxLags + kCovThreads - 1) / kCovThreads; // 3
-constexpr int kCovMeanCols = kCovTile + 2 * kCovMaxRadius;   // 96
+constexpr int kCovMeanCols = kSimTile + 2 * kSimMaxRadius;   // 96
 constexpr int kCovMeanPitch = 97;
-typedef __attribute__((address_space(1))) float GlobalF32;
-typedef __attribute__((address_space(1))) unsigned long long GlobalU64;
-
-__device__ __forceinline__ uint32_t cov_dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
 
 __global__ __launch_bounds__(kCovThreads) void k_cov_add(const CovRegionDev* __restrict__ rs, int radius, const float* __restrict__ graded, int pitch,
                                                          size_t plane, int count, unsigned long long* __restrict__ tile_tables) {
-    __shared__ __attribute__((aligned(16))) uint32_t sa[kCovTile * kCovAPitch];
-    __shared__ uint32_t sw[kCovWinRows * kCovWPitch];
+    __shared__ __attribute__((aligned(16))) uint32_t sa[kSimTile * kByteTilePitch];
+    __shared__ uint32_t sw[kCovWinRows * kByteWinPitch];
     __shared__ uint32_t tab[kCovMaxLags];
     const CovRegionDev q = rs[blockIdx.z];
     const int tile = blockIdx.x;
     if (tile >= q.tiles_x * q.tiles_y) return;   // whole workgroup: the grid is sized for the region with the most tiles
     const int t = threadIdx.x;
-    const int ty = tile / q.tiles_x, tx = tile - ty * q.tiles_x;
-    const int x0 = tx * kCovTile, y0 = ty * kCovTile;
-    const int tw = min(kCovTile, q.w - x0), th = min(kCovTile, q.h - y0);
+    const auto [x0, y0, tw, th] = tile_geom(tile, q.tiles_x, q.w, q.h);
     const int S = 2 * radius + 1, T = (radius + 1) * S;
     const int bw = tw + 2 * radius, bh = th + radius;   // the window in bytes and rows: inside the plane (the call's refusals)
-    const int blocks = (th + kCovRows - 1) / kCovRows;
+    const int blocks = (th + kByteRows - 1) / kByteRows;
     const int full = tw >> 4, rest = tw & 15;
     const uint32_t ash = (uint32_t)(radius & 3);
     const int aw = radius >> 2;
@@ -79,30 +61,18 @@ __global__ __launch_bounds__(kCovThreads) void k_cov_add(const CovRegionDev* __r
     const ptrdiff_t origin = (ptrdiff_t)(q.ay + y0 + MUSICA_OUT_MARGIN) * pitch + (q.ax + x0 - radius + MUSICA_OUT_MARGIN);
 
     for (int k = 0; k < count; k++) {
-        // the planes are device memory: say so, or the loads come out as flat_load
         const GlobalF32* __restrict__ pw = (const GlobalF32*)graded + (size_t)k * plane + origin;
-        for (int i = t; i < bh * kCovWWords; i += kCovThreads) {
-            const int r = i / kCovWWords, wd = i - r * kCovWWords, j = wd << 2;
-            uint32_t word = 0u;
-            if (j < bw) {
-                const GlobalF32* p = pw + (ptrdiff_t)r * pitch + j;
-                if (j + 4 <= bw) {
-                    float v[4];
-                    __builtin_memcpy(v, p, 16);   // 4-byte aligned
-                    word = out_u8(v[0]) | (out_u8(v[1]) << 8) | (out_u8(v[2]) << 16) | (out_u8(v[3]) << 24);
-                } else {
-                    for (int n = 0; n < bw - j; n++) word |= out_u8(p[n]) << (8 * n);
-                }
-            }
-            sw[r * kCovWPitch + wd] = word;
+        for (int i = t; i < bh * kByteWinWords; i += kCovThreads) {
+            const int r = i / kByteWinWords, wd = i - r * kByteWinWords, j = wd << 2;
+            sw[r * kByteWinPitch + wd] = j < bw ? load_quant4(pw + (ptrdiff_t)r * pitch + j, bw - j) : 0u;
         }
         __syncthreads();
         // the tile: the window from byte `radius` of each row on, 16 words per row; bytes at x >= tw cleared (words aw + wd + 1 <= 4 + 15 + 1 < 25)
         for (int i = t; i < th * 16; i += kCovThreads) {
             const int r = i >> 4, wd = i & 15, n = tw - (wd << 2);
-            const uint32_t* row = sw + r * kCovWPitch + aw + wd;
+            const uint32_t* row = sw + r * kByteWinPitch + aw + wd;
             const uint32_t v = __builtin_amdgcn_alignbyte(row[1], row[0], ash);
-            sa[r * kCovAPitch + wd] = n >= 4 ? v : n <= 0 ? 0u : v & ((1u << (8 * n)) - 1u);
+            sa[r * kByteTilePitch + wd] = n >= 4 ? v : n <= 0 ? 0u : v & ((1u << (8 * n)) - 1u);
         }
         __syncthreads();
 
@@ -110,20 +80,22 @@ __global__ __launch_bounds__(kCovThreads) void k_cov_add(const CovRegionDev* __r
             const int p = i / T, c = i - p * T;
             const int dy = c / S, dxi = c - dy * S;   // dy, dx + R
             const uint32_t sh = (uint32_t)(dxi & 3);
-            const int y1 = min(th, (p + 1) * kCovRows);
+            const int y1 = min(th, (p + 1) * kByteRows);
             uint32_t sab = 0u;   // <= 8 * 64 * 255^2 < 2^25
-            for (int y = p * kCovRows; y < y1; y++) {
-                const uint4* ar = reinterpret_cast<const uint4*>(sa + y * kCovAPitch);
-                const uint32_t* br = sw + (y + dy) * kCovWPitch + (dxi >> 2);
+            for (int y = p * kByteRows; y < y1; y++) {
+                const uint4* ar = reinterpret_cast<const uint4*>(sa + y * kByteTilePitch);
+                const uint32_t* br = sw + (y + dy) * kByteWinPitch + (dxi >> 2);
                 uint32_t lo = br[0];
                 const int chunks = full + (rest ? 1 : 0);   // the tile copy is 0 at x >= tw: a ragged chunk needs no mask of its own; words up to (dxi >> 2) + 16 <= 24
                 for (int ch = 0; ch < chunks; ch++) {
                     const uint4 av = ar[ch];
                     const uint32_t b1 = br[4 * ch + 1], b2 = br[4 * ch + 2], b3 = br[4 * ch + 3], b4 = br[4 * ch + 4];
-                    sab = cov_dot4(av.x, __builtin_amdgcn_alignbyte(b1, lo, sh), sab);
-                    sab = cov_dot4(av.y, __builtin_amdgcn_alignbyte(b2, b1, sh), sab);
-                    sab = cov_dot4(av.z, __builtin_amdgcn_alignbyte(b3, b2, sh), sab);
-                    sab = cov_dot4(av.w, __builtin_amdgcn_alignbyte(b4, b3, sh), sab);
+                    uint32_t v[4];
+                    shifted_words(lo, b1, b2, b3, b4, sh, v);
+                    sab = dot4(av.x, v[0], sab);
+                    sab = dot4(av.y, v[1], sab);
+                    sab = dot4(av.z, v[2], sab);
+                    sab = dot4(av.w, v[3], sab);
                     lo = b4;
                 }
             }
@@ -158,13 +130,11 @@ __global__ __launch_bounds__(kCovThreads) void k_cov_mean(const CovRegionDev* __
     const int tile = blockIdx.x;
     if (tile >= q.tiles_x * q.tiles_y) return;   // whole workgroup
     const int t = threadIdx.x;
-    const int ty = tile / q.tiles_x, tx = tile - ty * q.tiles_x;
-    const int x0 = tx * kCovTile, y0 = ty * kCovTile;
-    const int tw = min(kCovTile, q.w - x0), th = min(kCovTile, q.h - y0);
+    const auto [x0, y0, tw, th] = tile_geom(tile, q.tiles_x, q.w, q.h);
     const int S = 2 * radius + 1, T = (radius + 1) * S;
     const int bw = tw + 2 * radius, bh = th + radius;   // inside the plane (the call's refusals)
     for (int i = t; i < T; i += kCovThreads) tab[i] = 0ull;
-    // the accumulators are device memory: say so. One word is {S1, S2}: S1 is its low half.
+    // one accumulator word is {S1, S2}: S1 is its low half
     const GlobalU64* __restrict__ ps = (const GlobalU64*)ens + (ptrdiff_t)(q.ay + y0) * nw + (q.ax + x0 - radius);
     for (int i = t; i < bh * kCovMeanCols; i += kCovThreads) {
         const int r = i / kCovMeanCols, j = i - r * kCovMeanCols;
@@ -172,13 +142,13 @@ __global__ __launch_bounds__(kCovThreads) void k_cov_mean(const CovRegionDev* __
     }
     __syncthreads();
 
-    const int blocks = (th + kCovRows - 1) / kCovRows;
+    const int blocks = (th + kByteRows - 1) / kByteRows;
     for (int i = t; i < T * blocks; i += kCovThreads) {
         const int p = i / T, c = i - p * T;
         const int dy = c / S, dxi = c - dy * S;
-        const int y1 = min(th, (p + 1) * kCovRows);
+        const int y1 = min(th, (p + 1) * kByteRows);
         unsigned long long u = 0ull;   // <= 8 * 64 * 261120^2 < 2^46
-        for (int y = p * kCovRows; y < y1; y++) {
+        for (int y = p * kByteRows; y < y1; y++) {
             const uint32_t* ar = s1 + y * kCovMeanPitch + radius;
             const uint32_t* br = s1 + (y + dy) * kCovMeanPitch + dxi;
             for (int x = 0; x < tw; x++) u += (unsigned long long)ar[x] * br[x];

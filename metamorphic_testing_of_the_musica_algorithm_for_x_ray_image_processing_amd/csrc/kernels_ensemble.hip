@@ -16,17 +16,13 @@
 //   and the workgroup reduces sum D^2, sum V, sum D, sum E, max |D|, max V (shuffles inside a wavefront, LDS across the four). It writes
 //   the tile's pair (sum D^2, sum V) and adds its sums to the query's totals with 64-bit integer atomics (add, max): exact, and the same
 //   from call to call whatever the order. Every sum fits u64: musica_sim_ensemble_result refuses 65025 K^2 w h >= 2^64. No f64.
-#include "kernels_common.h"
-#include "launchers.h"
+#include "study_device.h"
 
 namespace musica {
 
 static_assert((MUSICA_OUT_MARGIN & 1) == 0, "k_ens_add reads the cropped rows as 8-byte pairs: the margin must be even");
-static_assert(kEnsTile == MUSICA_SIM_TILE, "k_ens_stats' tiles are musica_sim_displace's");
 
-constexpr int kEnsThreads = 256;
-typedef __attribute__((address_space(1))) unsigned long long GlobalU64;   // one accumulator word: S1 in the low half, S2 in the high one
-typedef __attribute__((address_space(1))) uint8_t GlobalU8;
+constexpr int kEnsThreads = kStudyThreads;
 
 __global__ __launch_bounds__(kEnsThreads) void k_ens_add(const float* __restrict__ graded, int pitch, size_t plane, int count, int nw, int lanes_per_row,
                                                          uint2* __restrict__ acc) {
@@ -75,35 +71,21 @@ __global__ __launch_bounds__(kEnsThreads) void k_ens_add(const float* __restrict
     }
 }
 
-__device__ __forceinline__ unsigned long long ens_wave_sum(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long ens_wave_max(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_down(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kEnsThreads) void k_ens_stats(const EnsQueryDev* __restrict__ qs, uint32_t K, unsigned long long* __restrict__ tile_tables,
                                                            unsigned long long* __restrict__ totals) {
-    __shared__ unsigned long long part[kEnsThreads / 64][kEnsTotals];
+    __shared__ WaveSlots<unsigned long long, kEnsTotals> part;
     const EnsQueryDev q = qs[blockIdx.z];
     const int tile = blockIdx.x;
     if (tile >= q.tiles_x * q.tiles_y) return;   // whole workgroup: the grid is sized for the query with the most tiles
     const int t = threadIdx.x;
-    const int ty = tile / q.tiles_x, tx = tile - ty * q.tiles_x;
-    const int x0 = tx * kEnsTile, y0 = ty * kEnsTile;
-    const int tw = min(kEnsTile, q.w - x0), th = min(kEnsTile, q.h - y0);
-    // the planes are device memory: say so, or the pointers read from the query are generic and the loads come out as flat_load
+    const auto [x0, y0, tw, th] = tile_geom(tile, q.tiles_x, q.w, q.h);
+    // one accumulator word: S1 in the low half, S2 in the high one
     const GlobalU64* __restrict__ ps = (const GlobalU64*)q.s + (ptrdiff_t)y0 * q.s_pitch + x0;
     const GlobalU8* __restrict__ pb = (const GlobalU8*)q.b + (ptrdiff_t)y0 * q.b_pitch + x0;
     const long long k = (long long)K;
     unsigned long long sq_bias = 0ull, var = 0ull, sq_err = 0ull, bias_max = 0ull, var_max = 0ull;
     long long bias = 0ll;
-    for (int i = t; i < kEnsTile * kEnsTile; i += kEnsThreads) {
+    for (int i = t; i < kSimTile * kSimTile; i += kEnsThreads) {
         const int r = i >> 6, x = i & 63;
         if (r >= th || x >= tw) continue;
         const unsigned long long s = ps[(ptrdiff_t)r * q.s_pitch + x];
@@ -118,24 +100,18 @@ __global__ __launch_bounds__(kEnsThreads) void k_ens_stats(const EnsQueryDev* __
         bias_max = ad > bias_max ? ad : bias_max;
         var_max = v > var_max ? v : var_max;
     }
-    sq_bias = ens_wave_sum(sq_bias);
-    var = ens_wave_sum(var);
-    const unsigned long long ubias = ens_wave_sum((unsigned long long)bias);   // two's complement: the wrapped sum is the signed one
-    sq_err = ens_wave_sum(sq_err);
-    bias_max = ens_wave_max(bias_max);
-    var_max = ens_wave_max(var_max);
-    if ((t & 63) == 0) {
-        unsigned long long* p = part[t >> 6];
-        p[0] = sq_bias; p[1] = var; p[2] = ubias; p[3] = sq_err; p[4] = bias_max; p[5] = var_max;
-    }
+    unsigned long long ubias = (unsigned long long)bias;   // two's complement: the wrapped sum is the signed one
+    wave_sum(sq_bias);
+    wave_sum(var);
+    wave_sum(ubias);
+    wave_sum(sq_err);
+    const unsigned long long wave[kEnsTotals] = {sq_bias, var, ubias, sq_err, wave_max(bias_max), wave_max(var_max)};
+    if (wave_leader()) part.put(wave);
     __syncthreads();
     if (t == 0) {
         unsigned long long r[kEnsTotals];
-        for (int j = 0; j < kEnsTotals; j++) r[j] = part[0][j];
-        for (int w = 1; w < kEnsThreads / 64; w++) {
-            for (int j = 0; j < 4; j++) r[j] += part[w][j];
-            for (int j = 4; j < kEnsTotals; j++) r[j] = part[w][j] > r[j] ? part[w][j] : r[j];
-        }
+        for (int j = 0; j < 4; j++) r[j] = part.sum(j);
+        for (int j = 4; j < kEnsTotals; j++) r[j] = part.max(j);
         unsigned long long* pair = tile_tables + 2 * (q.tile_base + (size_t)tile);
         pair[0] = r[0];
         pair[1] = r[1];

@@ -24,8 +24,7 @@
 // allocations' bases), the table in LDS.
 #include <algorithm>
 
-#include "kernels_common.h"
-#include "launchers.h"
+#include "study_device.h"
 
 namespace musica {
 
@@ -33,8 +32,6 @@ constexpr int kJointThreads = 1024;
 constexpr int kJointDwords = 32768;          // 65536 u16 counters
 constexpr int kJointChunkPixels = 65535;     // what a u16 half can count
 constexpr int kJointQuads = 4;               // 4-pixel groups a thread loads before it counts them
-typedef __attribute__((address_space(1))) float GlobalF32;
-typedef __attribute__((address_space(1))) uint8_t GlobalU8;
 
 __device__ __forceinline__ void joint_count(uint32_t* tab, uint32_t* __restrict__ out, uint32_t a, uint32_t b) {
     const uint32_t bin = (a << 8) | b;

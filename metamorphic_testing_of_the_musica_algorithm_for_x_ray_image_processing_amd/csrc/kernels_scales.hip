@@ -21,16 +21,15 @@
 // (49 * (255 * 256)^2 = 2.09e11); arithmetic mod 2^32 / 2^64 on values that fit is exact. The per-window value is then
 // harness.multiscale_similarities' f64 expression in its order (-ffp-contract=off, IEEE f64 division): one division per mean by the
 // exact doubles 49 * 4^s and 49 * 16^s, then ssim_similarity's terms. Three f64 accumulators per thread (ssim, cs, lum).
-// Per-workgroup partials are folded per job in a fixed order by k_scales_fold (with the tiles' integer partials): no f64 atomics,
-// results are bit-identical from call to call.
+// Per-workgroup partials are folded per job by k_scales_fold (with the tiles' integer partials), both in study_device.h's fixed order:
+// no f64 atomics, results are bit-identical from call to call.
 #include <algorithm>
 
-#include "kernels_common.h"
-#include "launchers.h"
+#include "study_device.h"
 
 namespace musica {
 
-constexpr int kScaleThreads = 256;
+constexpr int kScaleThreads = kStudyThreads;
 constexpr int kScaleHalo = 3;                              // (7 - 1) / 2
 constexpr int kScaleCols = kScaleThreads - 2 * kScaleHalo; // plane columns a strip owns
 
@@ -45,7 +44,7 @@ __global__ __launch_bounds__(kScaleThreads) void k_scales_pool(const ScalePoolDe
     __shared__ uint32_t l1[8][kScalePoolW / 2];        // scale-1 cells
     __shared__ uint32_t l2[4][kScalePoolW / 4];
     __shared__ uint32_t l3[2][kScalePoolW / 8];
-    __shared__ unsigned long long red[kScaleThreads / 64][kScaleMaxScales];
+    __shared__ WaveSlots<unsigned long long, kScaleMaxScales> red;
     const ScalePoolDev q = qs[blockIdx.z];
     const int blk = blockIdx.x;
     if (blk >= q.tiles_x * q.tiles_y) return;   // whole workgroup: the grid is sized for the query with the most tiles
@@ -114,19 +113,12 @@ __global__ __launch_bounds__(kScaleThreads) void k_scales_pool(const ScalePoolDe
             ssd[4] += sq_diff_packed(v);
         }
     }
-    // the tile's partial: wavefront tree, then the four wavefronts in order
+    // the tile's partial: thread s folds scale s
 #pragma unroll
-    for (int s = 0; s < kScaleMaxScales; s++)
-        for (int off = 32; off > 0; off >>= 1) ssd[s] += __shfl_down(ssd[s], off, 64);
-    if ((t & 63) == 0)
-#pragma unroll
-        for (int s = 0; s < kScaleMaxScales; s++) red[t >> 6][s] = ssd[s];
+    for (int s = 0; s < kScaleMaxScales; s++) wave_sum(ssd[s]);
+    if (wave_leader()) red.put(ssd);
     __syncthreads();
-    if (t < kScaleMaxScales) {
-        unsigned long long v = red[0][t];
-        for (int w = 1; w < kScaleThreads / 64; w++) v += red[w][t];
-        part[q.part_base + blk].ssd[t] = v;
-    }
+    if (t < kScaleMaxScales) part[q.part_base + blk].ssd[t] = red.sum(t);
 }
 
 // The march of one job. T: the window sums' integer type; TEXEL: u16 (x | y << 8, scale 0) or u32 (x | y << 16).
@@ -185,11 +177,10 @@ __device__ __forceinline__ void scales_march(const ScaleJobDev& q, const uint8_t
                     }
                     const double ux = (double)s[0] / d1, uy = (double)s[1] / d1;
                     const double uxx = (double)s[2] / d2, uyy = (double)s[3] / d2, uxy = (double)s[4] / d2;
-                    const double vx_ = k.cov_norm * (uxx - ux * ux), vy_ = k.cov_norm * (uyy - uy * uy), vxy_ = k.cov_norm * (uxy - ux * uy);
-                    const double a1 = 2.0 * ux * uy + k.c1, a2 = 2.0 * vxy_ + k.c2, b1 = ux * ux + uy * uy + k.c1, b2 = vx_ + vy_ + k.c2;
-                    a_ssim += (a1 * a2) / (b1 * b2);
-                    a_cs += a2 / b2;
-                    a_lum += a1 / b1;
+                    const SsimTerms m = ssim_terms(ux, uy, uxx, uyy, uxy, k);
+                    a_ssim += (m.a1 * m.a2) / (m.b1 * m.b2);
+                    a_cs += m.a2 / m.b2;
+                    a_lum += m.a1 / m.b1;
                 }
                 p ^= 1;
             }
@@ -200,7 +191,7 @@ __device__ __forceinline__ void scales_march(const ScaleJobDev& q, const uint8_t
 __global__ __launch_bounds__(kScaleThreads) void k_scales_win(const ScaleJobDev* __restrict__ jobs, const uint8_t* __restrict__ scratch,
                                                               ScaleWinPart* __restrict__ part, ScaleConsts k) {
     __shared__ unsigned long long row[2 * 5 * kScaleThreads];
-    __shared__ double red[kScaleThreads / 64][3];
+    __shared__ WaveSlots<double, 3> red;
     const ScaleJobDev q = jobs[blockIdx.y];
     const int blk = blockIdx.x;
     if (blk >= q.strips * q.segs) return;   // whole workgroup: the grid is sized for the job with the most workgroups
@@ -208,35 +199,19 @@ __global__ __launch_bounds__(kScaleThreads) void k_scales_win(const ScaleJobDev*
     if (q.scale == 0) scales_march<uint32_t, uint16_t>(q, scratch, reinterpret_cast<uint32_t*>(row), k, blk, acc[0], acc[1], acc[2]);
     else if (q.scale <= 2) scales_march<uint32_t, uint32_t>(q, scratch, reinterpret_cast<uint32_t*>(row), k, blk, acc[0], acc[1], acc[2]);
     else scales_march<unsigned long long, uint32_t>(q, scratch, row, k, blk, acc[0], acc[1], acc[2]);
-    // partials in a fixed order: wavefront tree, then the four wavefronts in order
-    const int t = threadIdx.x;
 #pragma unroll
-    for (int f = 0; f < 3; f++)
-        for (int off = 32; off > 0; off >>= 1) acc[f] += __shfl_down(acc[f], off, 64);
-    if ((t & 63) == 0)
-#pragma unroll
-        for (int f = 0; f < 3; f++) red[t >> 6][f] = acc[f];
+    for (int f = 0; f < 3; f++) wave_sum(acc[f]);
+    if (wave_leader()) red.put(acc);
     __syncthreads();
-    if (t == 0) {
-        ScaleWinPart r;
-        r.ssim = red[0][0];
-        r.cs = red[0][1];
-        r.lum = red[0][2];
-        for (int w = 1; w < kScaleThreads / 64; w++) {
-            r.ssim += red[w][0];
-            r.cs += red[w][1];
-            r.lum += red[w][2];
-        }
-        part[(size_t)blockIdx.y * kScaleMaxBlocks + blk] = r;
-    }
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * kScaleMaxBlocks + blk] = ScaleWinPart{red.sum(0), red.sum(1), red.sum(2)};
 }
 
 // One workgroup per job: the partials of its workgroups, and its scale's integer partials of its query's tiles, in a fixed order.
 __global__ __launch_bounds__(kScaleThreads) void k_scales_fold(const ScaleJobDev* __restrict__ jobs, const ScalePoolDev* __restrict__ qs,
                                                                const ScaleWinPart* __restrict__ part, const ScalePoolPart* __restrict__ pool,
                                                                ScaleOut* __restrict__ out) {
-    __shared__ double red_d[kScaleThreads / 64][3];
-    __shared__ unsigned long long red_u[kScaleThreads / 64];
+    __shared__ WaveSlots<double, 3> red_d;
+    __shared__ WaveSlots<unsigned long long> red_u;
     const int t = threadIdx.x;
     const ScaleJobDev q = jobs[blockIdx.x];
     const ScalePoolDev pq = qs[q.query];
@@ -250,41 +225,16 @@ __global__ __launch_bounds__(kScaleThreads) void k_scales_fold(const ScaleJobDev
         acc[2] += pp[i].lum;
     }
     for (int i = t; i < tiles; i += kScaleThreads) ssd += pool[pq.part_base + i].ssd[q.scale];
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int f = 0; f < 3; f++) acc[f] += __shfl_down(acc[f], off, 64);
-        ssd += __shfl_down(ssd, off, 64);
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int f = 0; f < 3; f++) red_d[t >> 6][f] = acc[f];
-        red_u[t >> 6] = ssd;
+    wave_sum(acc[0], acc[1], acc[2], ssd);
+    if (wave_leader()) {
+        red_d.put(acc);
+        red_u.put(ssd);
     }
     __syncthreads();
-    if (t == 0) {
-        ScaleOut r;
-        r.ssim = red_d[0][0];
-        r.cs = red_d[0][1];
-        r.lum = red_d[0][2];
-        r.ssd = red_u[0];
-        for (int w = 1; w < kScaleThreads / 64; w++) {
-            r.ssim += red_d[w][0];
-            r.cs += red_d[w][1];
-            r.lum += red_d[w][2];
-            r.ssd += red_u[w];
-        }
-        out[blockIdx.x] = r;
-    }
+    if (t == 0) out[blockIdx.x] = ScaleOut{red_d.sum(0), red_d.sum(1), red_d.sum(2), red_u.sum()};
 }
 
-void scales_geometry(ScaleJobDev& q) {
-    q.strips = (q.w + kScaleCols - 1) / kScaleCols;
-    // as sim_geometry: a few hundred workgroups for a large plane, segments of at least 32 rows so that the 6-row halo stays below 20 %
-    const int want = std::max(1, kScaleMaxBlocks / q.strips);
-    const int segs = std::max(1, std::min((q.h + 31) / 32, want));
-    q.seg_rows = (q.h + segs - 1) / segs;
-    q.segs = (q.h + q.seg_rows - 1) / q.seg_rows;
-}
+void scales_geometry(ScaleJobDev& q) { strip_geometry(q.w, q.h, kScaleCols, kScaleMaxBlocks, q.strips, q.segs, q.seg_rows); }
 
 void launch_scales(hipStream_t st, const ScalePoolDev* d_qs, int count, int max_tiles, const ScaleJobDev* d_jobs, int jobs, int max_blocks,
                    uint8_t* scratch, ScalePoolPart* pool, ScaleWinPart* part, ScaleOut* out, const ScaleConsts& k) {

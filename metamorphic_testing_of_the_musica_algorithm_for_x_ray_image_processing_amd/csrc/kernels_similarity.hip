@@ -14,19 +14,20 @@
 //     of u8 data are integers, so they are exact; the per-pixel value is then harness.ssim_similarity's f64 expression in its order
 //     (-ffp-contract=off, IEEE f64 division), and only the order of the final summation differs from numpy's. Strips overlap by the
 //     6-column halo, segments by the 6-row halo.
-// Per-workgroup SSIM and SSD partials are written to `part` and folded per query in a fixed order by k_sim_fold: results are
-// bit-identical from call to call (no f64 atomics).
+// Per-workgroup SSIM and SSD partials are written to `part` and folded per query by k_sim_fold, both in study_device.h's fixed order:
+// results are bit-identical from call to call (no f64 atomics).
 #include <algorithm>
 
-#include "kernels_common.h"
-#include "launchers.h"
+#include "study_device.h"
 
 namespace musica {
 
-constexpr int kSimThreads = 256;
+constexpr int kSimThreads = kStudyThreads;
 constexpr int kSimHalo = 3;                            // (7 - 1) / 2
 constexpr int kSimCols = kSimThreads - 2 * kSimHalo;   // region columns a strip owns
 
+// k_sim keeps its own reduction and SSIM text, not study_device.h's helpers: with them its median in devtools/sim_probe.py was 0.2 - 0.5 us
+// of 87 slower in two A/B jobs (profiles/study_helpers_ab.txt). The order is the header's rule: wavefront tree, then the wavefronts in order.
 __global__ __launch_bounds__(kSimThreads) void k_sim(const SimQueryDev* __restrict__ qs, SimPart* __restrict__ part, uint32_t* __restrict__ hist,
                                                      SimConsts k) {
     __shared__ uint32_t sh_a[256], sh_b[256];
@@ -133,8 +134,8 @@ __global__ __launch_bounds__(kSimThreads) void k_sim(const SimQueryDev* __restri
 
 // One workgroup per query: the partials of its workgroups in a fixed order.
 __global__ __launch_bounds__(kSimThreads) void k_sim_fold(const SimQueryDev* __restrict__ qs, const SimPart* __restrict__ part, SimPart* __restrict__ out) {
-    __shared__ double red_d[kSimThreads / 64];
-    __shared__ unsigned long long red_u[kSimThreads / 64];
+    __shared__ WaveSlots<double> red_d;
+    __shared__ WaveSlots<unsigned long long> red_u;
     const int t = threadIdx.x;
     const SimQueryDev q = qs[blockIdx.x];
     const int n = q.strips * q.segs;
@@ -145,36 +146,26 @@ __global__ __launch_bounds__(kSimThreads) void k_sim_fold(const SimQueryDev* __r
         acc += pp[i].ssim;
         ssd += pp[i].ssd;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_down(acc, off, 64);
-        ssd += __shfl_down(ssd, off, 64);
-    }
-    if ((t & 63) == 0) {
-        red_d[t >> 6] = acc;
-        red_u[t >> 6] = ssd;
+    wave_sum(acc, ssd);
+    if (wave_leader()) {
+        red_d.put(acc);
+        red_u.put(ssd);
     }
     __syncthreads();
-    if (t == 0) {
-        SimPart r;
-        r.ssim = red_d[0];
-        r.ssd = red_u[0];
-        for (int w = 1; w < kSimThreads / 64; w++) {
-            r.ssim += red_d[w];
-            r.ssd += red_u[w];
-        }
-        out[blockIdx.x] = r;
-    }
+    if (t == 0) out[blockIdx.x] = SimPart{red_d.sum(), red_u.sum()};
 }
 
-void sim_geometry(SimQueryDev& q) {
-    q.strips = (q.w + kSimCols - 1) / kSimCols;
-    // a few hundred workgroups per query: enough to fill the chip for one comparison, few enough that the value-count flushes
-    // (up to 512 same-address atomics per workgroup) stay short; segments of at least 32 rows keep the 6-row halo below 20 %
-    const int want = std::max(1, std::min(kSimMaxBlocks, 512) / q.strips);
-    const int segs = std::max(1, std::min((q.h + 31) / 32, want));
-    q.seg_rows = (q.h + segs - 1) / segs;
-    q.segs = (q.h + q.seg_rows - 1) / q.seg_rows;
+void strip_geometry(int w, int h, int cols, int cap, int& strips, int& segs, int& seg_rows) {
+    strips = (w + cols - 1) / cols;
+    const int want = std::max(1, cap / strips);
+    const int n = std::max(1, std::min((h + 31) / 32, want));
+    seg_rows = (h + n - 1) / n;
+    segs = (h + seg_rows - 1) / seg_rows;
 }
+
+// a few hundred workgroups per query: enough to fill the chip for one comparison, few enough that the value-count flushes (up to 512
+// same-address atomics per workgroup) stay short
+void sim_geometry(SimQueryDev& q) { strip_geometry(q.w, q.h, kSimCols, std::min(kSimMaxBlocks, 512), q.strips, q.segs, q.seg_rows); }
 
 void launch_sim(hipStream_t st, const SimQueryDev* d_qs, int count, int max_blocks, SimPart* part, uint32_t* hist, SimPart* out, const SimConsts& k) {
     hipLaunchKernelGGL(k_sim, dim3(max_blocks, 1, count), dim3(kSimThreads), 0, st, d_qs, part, hist, k);

@@ -159,6 +159,11 @@ struct SimConsts {
     double c1, c2, cov_norm;  // (0.01 * 255)^2, (0.03 * 255)^2, 49 / 48 as harness.ssim_similarity computes them
 };
 constexpr int kSimMaxBlocks = 1024;   // workgroups per query (partials slots)
+constexpr int kSimTile = 64;          // MUSICA_SIM_TILE: the tiles of k_displace, k_ens_stats, k_cov_add and k_cov_mean
+constexpr int kSimMaxRadius = 16;     // MUSICA_SIM_MAX_RADIUS: the largest shift of k_displace and lag of k_cov_add / k_cov_mean
+// The launch geometry of a strip march (k_sim, k_scales_win) over a w x h plane: strips of `cols` columns and, at most `cap`
+// workgroups in all, segments of at least 32 rows so that the 6-row halo stays below 20 %.
+void strip_geometry(int w, int h, int cols, int cap, int& strips, int& segs, int& seg_rows);
 void sim_geometry(SimQueryDev& q);
 // k_sim over `count` queries (grid.x = the largest strips * segs), then k_sim_fold; hist: count x [a 256 | b 256] u32, zeroed by the caller
 void launch_sim(hipStream_t st, const SimQueryDev* d_qs, int count, int max_blocks, SimPart* part, uint32_t* hist, SimPart* out, const SimConsts& k);
@@ -187,8 +192,6 @@ struct DisplaceQueryDev : SimRegion {
     int tiles_x, tiles_y;
     unsigned long long tile_base;
 };
-constexpr int kDisplaceTile = 64;        // MUSICA_SIM_TILE
-constexpr int kDisplaceMaxRadius = 16;   // MUSICA_SIM_MAX_RADIUS
 // k_displace over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y), then k_displace_fold. tile_tables: every query's
 // tile tables (all written); tables: count x S^2 u64 and tiles_off: count u32, both zeroed by the caller.
 void launch_displace(hipStream_t st, const DisplaceQueryDev* d_qs, int count, int max_tiles, int radius, uint32_t* tile_tables,
@@ -220,8 +223,7 @@ struct ScaleOut {
     double ssim, cs, lum;             // sums over the job's windows
     unsigned long long ssd;           // the query's exact sum of (X_s - Y_s)^2 at the job's scale
 };
-struct ScaleConsts {
-    double c1, c2, cov_norm;                               // as SimConsts
+struct ScaleConsts : SimConsts {
     double div1[kScaleMaxScales], div2[kScaleMaxScales];   // 49 * 4^s, 49 * 16^s
 };
 void scales_geometry(ScaleJobDev& q);
@@ -240,7 +242,6 @@ struct EnsQueryDev {
     int tiles_x, tiles_y;
     unsigned long long tile_base;
 };
-constexpr int kEnsTile = 64;     // MUSICA_SIM_TILE
 constexpr int kEnsTotals = 6;    // u64 per query: sum D^2, sum V, sum D (two's complement), sum E, max |D|, max V
 // k_ens_add: S1 += a, S2 += a^2 over the cropped plane for the `count` graded planes from `graded` on (stride l0.plane), one launch
 void launch_ens_add(hipStream_t st, const float* graded, const LevelDesc& l0, int count, uint2* acc);
@@ -256,8 +257,6 @@ struct CovRegionDev {
     int tiles_x, tiles_y;
     unsigned long long tile_base;
 };
-constexpr int kCovTile = 64;         // MUSICA_SIM_TILE
-constexpr int kCovMaxRadius = 16;    // MUSICA_SIM_MAX_RADIUS
 // k_cov_add: P(d) += sum over the tile of a(p) a(p + d) for the `count` graded planes from `graded` on (stride l0.plane), one launch over
 // `regions` regions (grid.x = max_tiles, the largest tiles_x * tiles_y); tile_tables: u64, zeroed when tracking starts.
 void launch_cov_add(hipStream_t st, const CovRegionDev* d_rs, int regions, int max_tiles, int radius, const float* graded, const LevelDesc& l0, int count,

@@ -7,21 +7,37 @@
 
 #include "musica_ctx.h"
 
-// musica_sim_multiscale: a device buffer of one call, regrown when a call needs more than the largest call so far (as
-// musica_sim_displace's tile tables). A template, so it stands outside the extern "C" block.
-template <typename T>
-static int scales_grow(musica_ctx* c, T** buf, size_t* cap, size_t want) {
+// ---- helpers (templates among them, so they stand outside the extern "C" block) -------------------------------------------------------
+// A device buffer sized for one call of `fn` (or a `twin` pair that grows together), regrown when a call needs more than the largest
+// call so far: *cap and `want` count units of `per` elements; a refusal names `want` in `unit`s (nullptr: in bytes).
+template <typename T, typename U = T>
+static int grow(musica_ctx* c, const char* fn, T** buf, size_t* cap, size_t want, const char* unit = nullptr, size_t per = 1, U** twin = nullptr) {
     if (want <= *cap) return 1;
     HIP_OK(drelease(c, buf));
+    if (twin) HIP_OK(drelease(c, twin));
     *cap = 0;
-    if (!dalloc(c, buf, want)) return fail("musica_sim_multiscale: device allocation of %zu bytes failed", want * sizeof(T));
+    if (!dalloc(c, buf, per * want) || (twin && !dalloc(c, twin, per * want)))
+        return unit ? fail("%s: device allocation of %zu %s failed", fn, want, unit) : fail("%s: device allocation of %zu bytes failed", fn, want * sizeof(T));
     *cap = want;
     return 1;
 }
 
-extern "C" {
+// The grid of MUSICA_SIM_TILE^2 tiles of the regions of one launch: each region's tiles_x x tiles_y, where its tiles' tables start in
+// the launch's tile-table buffer (`per_tile` elements per tile, region after region) and the largest grid (the launch's grid.x).
+static int tiles_along(uint32_t len) { return (int)((len + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE); }
+struct TileRun {
+    size_t next = 0;      // elements so far: the next region's tile_base
+    int max_tiles = 1;
+    template <typename D>
+    void place(D& d, size_t per_tile) {
+        d.tiles_x = tiles_along((uint32_t)d.w);
+        d.tiles_y = tiles_along((uint32_t)d.h);
+        d.tile_base = next;
+        next += (size_t)d.tiles_x * d.tiles_y * per_tile;
+        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+    }
+};
 
-// ---- reference slots (musica_sim_*, include/musica.h) -------------------------------------------------------------------------------
 static size_t sim_side(const musica_ctx* c) { return (size_t)c->N - 2 * MUSICA_OUT_MARGIN; }   // of a slot's plane: the cropped output
 
 // The plane of a slot that `fn` is about to write, allocated on first use, after the two refusals every writer shares.
@@ -32,15 +48,32 @@ static uint8_t* sim_slot_for_write(musica_ctx* c, const char* fn, uint32_t slot)
     return c->study.slot[slot];
 }
 
-// What the calls that make dst_slot from src_slot refuse about the pair. A written source implies a context larger than the margin
-// (only sim_slot_for_write's callers set `written`), so its margin refusal cannot fire behind this one.
-static int sim_check_pair(const musica_ctx* c, const char* fn, uint32_t dst_slot, uint32_t src_slot) {
+// The calls that make dst_slot from src_slot, behind their NULL refusals: what they refuse about the pair, then `check` (the call's
+// refusals about its other arguments: 1, or fail(...)), then launch(src, dst) into the destination's plane. A written source implies a
+// context larger than the margin (only sim_slot_for_write's callers set `written`), so its margin refusal cannot fire behind the pair's.
+template <typename Check, typename Launch>
+static int sim_derive_slot(musica_ctx* c, const char* fn, uint32_t dst_slot, uint32_t src_slot, Check check, Launch launch) {
     if (dst_slot >= MUSICA_SIM_SLOTS || src_slot >= MUSICA_SIM_SLOTS) return fail("%s: slot %u / %u >= %d", fn, dst_slot, src_slot, MUSICA_SIM_SLOTS);
     if (dst_slot == src_slot) return fail("%s: dst_slot == src_slot (%u)", fn, dst_slot);
     if (!c->study.written[src_slot]) return fail("%s: slot %u was never written", fn, src_slot);
+    if (!check()) return 0;
+    uint8_t* dst = sim_slot_for_write(c, fn, dst_slot);
+    if (!dst) return 0;
+    launch(c->study.slot[src_slot], dst);
+    HIP_OK(hipGetLastError());
+    c->study.written[dst_slot] = true;
     return 1;
 }
 
+// harness.ssim_similarity: c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2 (float ** is C pow); cov_norm = npx / (npx - 1)
+static SimConsts sim_consts() {
+    const double k1 = 0.01 * 255, k2 = 0.03 * 255;
+    return {pow(k1, 2.0), pow(k2, 2.0), 49.0 / 48.0};
+}
+
+extern "C" {
+
+// ---- reference slots (musica_sim_*, include/musica.h) -------------------------------------------------------------------------------
 int musica_sim_capture(musica_ctx* c, uint32_t slot, uint32_t idx) {
     if (!c) return fail("musica_sim_capture: ctx is NULL");
     if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_capture: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
@@ -105,58 +138,46 @@ static bool finite_all(const double* v, int n) {
 int musica_sim_rotate_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const double matrix[4], const double offset[2]) {
     if (!c) return fail("musica_sim_rotate_reference: ctx is NULL");
     if (!matrix || !offset) return fail("musica_sim_rotate_reference: matrix or offset is NULL");
-    if (!sim_check_pair(c, "musica_sim_rotate_reference", dst_slot, src_slot)) return 0;
-    if (!finite_all(matrix, 4) || !finite_all(offset, 2)) return fail("musica_sim_rotate_reference: matrix or offset is not finite");
-    uint8_t* dst = sim_slot_for_write(c, "musica_sim_rotate_reference", dst_slot);
-    if (!dst) return 0;
-    AlterDev a{};
-    a.n = (int)sim_side(c);
-    memcpy(a.m, matrix, sizeof(a.m));
-    memcpy(a.off, offset, sizeof(a.off));
-    launch_rotate_u8(c->stream, c->study.slot[src_slot], dst, a);
-    HIP_OK(hipGetLastError());
-    c->study.written[dst_slot] = true;
-    return 1;
+    return sim_derive_slot(
+        c, "musica_sim_rotate_reference", dst_slot, src_slot,
+        [&] { return finite_all(matrix, 4) && finite_all(offset, 2) ? 1 : fail("musica_sim_rotate_reference: matrix or offset is not finite"); },
+        [&](const uint8_t* src, uint8_t* dst) {
+            AlterDev a{};
+            a.n = (int)sim_side(c);
+            memcpy(a.m, matrix, sizeof(a.m));
+            memcpy(a.off, offset, sizeof(a.off));
+            launch_rotate_u8(c->stream, src, dst, a);
+        });
 }
 
 int musica_sim_transform_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t element) {
     if (!c) return fail("musica_sim_transform_reference: ctx is NULL");
-    if (!sim_check_pair(c, "musica_sim_transform_reference", dst_slot, src_slot)) return 0;
-    if (element > 7) return fail("musica_sim_transform_reference: element %u is not one of the square's 8 symmetries (0 .. 7)", element);
-    uint8_t* dst = sim_slot_for_write(c, "musica_sim_transform_reference", dst_slot);
-    if (!dst) return 0;
-    launch_symmetry_u8(c->stream, c->study.slot[src_slot], dst, (int)sim_side(c), (int)element);
-    HIP_OK(hipGetLastError());
-    c->study.written[dst_slot] = true;
-    return 1;
+    return sim_derive_slot(
+        c, "musica_sim_transform_reference", dst_slot, src_slot,
+        [&] { return element <= 7 ? 1 : fail("musica_sim_transform_reference: element %u is not one of the square's 8 symmetries (0 .. 7)", element); },
+        [&](const uint8_t* src, uint8_t* dst) { launch_symmetry_u8(c->stream, src, dst, (int)sim_side(c), (int)element); });
 }
 
 static_assert(kBlurMaxRadius == MUSICA_BLUR_MAX_RADIUS, "kernels_blur.hip instantiates the radii of include/musica.h");
 
 int musica_sim_blur_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t radius) {
     if (!c) return fail("musica_sim_blur_reference: ctx is NULL");
-    if (!sim_check_pair(c, "musica_sim_blur_reference", dst_slot, src_slot)) return 0;
-    if (radius < 1 || radius > MUSICA_BLUR_MAX_RADIUS) return fail("musica_sim_blur_reference: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS);
-    uint8_t* dst = sim_slot_for_write(c, "musica_sim_blur_reference", dst_slot);
-    if (!dst) return 0;
-    launch_blur_u8(c->stream, c->study.slot[src_slot], dst, (int)sim_side(c), (int)radius);
-    HIP_OK(hipGetLastError());
-    c->study.written[dst_slot] = true;
-    return 1;
+    return sim_derive_slot(
+        c, "musica_sim_blur_reference", dst_slot, src_slot,
+        [&] { return radius >= 1 && radius <= MUSICA_BLUR_MAX_RADIUS ? 1 : fail("musica_sim_blur_reference: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS); },
+        [&](const uint8_t* src, uint8_t* dst) { launch_blur_u8(c->stream, src, dst, (int)sim_side(c), (int)radius); });
 }
 
 int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]) {
     if (!c) return fail("musica_sim_remap_reference: ctx is NULL");
     if (!lut) return fail("musica_sim_remap_reference: lut is NULL");
-    if (!sim_check_pair(c, "musica_sim_remap_reference", dst_slot, src_slot)) return 0;
-    uint8_t* dst = sim_slot_for_write(c, "musica_sim_remap_reference", dst_slot);
-    if (!dst) return 0;
-    RemapLut t;
-    memcpy(t.v, lut, sizeof(t.v));   // travels as a kernel argument: `lut` is free again when the call returns
-    launch_sim_remap(c->stream, c->study.slot[src_slot], dst, t, (long long)(sim_side(c) * sim_side(c)));
-    HIP_OK(hipGetLastError());
-    c->study.written[dst_slot] = true;
-    return 1;
+    return sim_derive_slot(
+        c, "musica_sim_remap_reference", dst_slot, src_slot, [] { return 1; },   // nothing more to refuse
+        [&](const uint8_t* src, uint8_t* dst) {
+            RemapLut t;
+            memcpy(t.v, lut, sizeof(t.v));   // travels as a kernel argument: `lut` is free again when the call returns
+            launch_sim_remap(c->stream, src, dst, t, (long long)(sim_side(c) * sim_side(c)));
+        });
 }
 
 // ---- the query calls (musica_sim_compare / _joint / _displace / _multiscale) ----------------------------------------------------------------------
@@ -243,14 +264,9 @@ int musica_sim_compare(musica_ctx* c, uint32_t count, const musica_sim_query* qs
         sim_geometry(hq[i]);
         max_blocks = std::max(max_blocks, hq[i].strips * hq[i].segs);
     }
-    SimConsts k;
-    const double k1 = 0.01 * 255, k2 = 0.03 * 255;   // harness.ssim_similarity: c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2 (float ** is C pow)
-    k.c1 = pow(k1, 2.0);
-    k.c2 = pow(k2, 2.0);
-    k.cov_norm = 49.0 / 48.0;                         // npx / (npx - 1)
     HIP_OK(hipMemcpyAsync(st.d_sim_q, hq.data(), count * sizeof(SimQueryDev), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemsetAsync(st.d_sim_hist, 0, (size_t)count * 512 * sizeof(uint32_t), c->stream));
-    launch_sim(c->stream, st.d_sim_q, (int)count, max_blocks, st.d_sim_part, st.d_sim_hist, st.d_sim_out, k);
+    launch_sim(c->stream, st.d_sim_q, (int)count, max_blocks, st.d_sim_part, st.d_sim_hist, st.d_sim_out, sim_consts());
     HIP_OK(hipGetLastError());
     std::vector<uint32_t> hist((size_t)count * 512);
     std::vector<SimPart> parts(count);
@@ -383,33 +399,23 @@ int musica_sim_displace(musica_ctx* c, uint32_t count, const musica_sim_query* q
     }
     const size_t S2 = (size_t)(2 * radius + 1) * (2 * radius + 1);
     std::vector<DisplaceQueryDev> hq(count);
-    size_t tile_words = 0;
-    int max_tiles = 1;
+    TileRun run;
     for (uint32_t i = 0; i < count; i++) {
-        DisplaceQueryDev& d = hq[i];
-        sim_region(c, qs[i], d);
-        d.tiles_x = (d.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
-        d.tiles_y = (d.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
-        d.tile_base = tile_words;
-        tile_words += (size_t)d.tiles_x * d.tiles_y * S2;
-        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+        sim_region(c, qs[i], hq[i]);
+        run.place(hq[i], S2);
     }
+    const size_t tile_words = run.next;
     CHECK_CTX(c);
     StudyState& st = c->study;
     if (!(ensure(c, &st.d_disp_q, MUSICA_SIM_MAX_QUERIES) &&
           ensure(c, &st.d_disp_tables, (size_t)MUSICA_SIM_MAX_QUERIES * (2 * MUSICA_SIM_MAX_RADIUS + 1) * (2 * MUSICA_SIM_MAX_RADIUS + 1)) &&
           ensure(c, &st.d_disp_off, MUSICA_SIM_MAX_QUERIES)))
         return fail("musica_sim_displace: device allocation failed");
-    if (tile_words > st.disp_tiles_cap) {   // sized for the call: the largest call so far
-        HIP_OK(drelease(c, &st.d_disp_tiles));
-        st.disp_tiles_cap = 0;
-        if (!dalloc(c, &st.d_disp_tiles, tile_words)) return fail("musica_sim_displace: device allocation of %zu tile-table words failed", tile_words);
-        st.disp_tiles_cap = tile_words;
-    }
+    if (!grow(c, "musica_sim_displace", &st.d_disp_tiles, &st.disp_tiles_cap, tile_words, "tile-table words")) return 0;
     HIP_OK(hipMemcpyAsync(st.d_disp_q, hq.data(), count * sizeof(DisplaceQueryDev), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemsetAsync(st.d_disp_tables, 0, count * S2 * sizeof(unsigned long long), c->stream));
     HIP_OK(hipMemsetAsync(st.d_disp_off, 0, count * sizeof(uint32_t), c->stream));
-    launch_displace(c->stream, st.d_disp_q, (int)count, max_tiles, (int)radius, st.d_disp_tiles, st.d_disp_tables, st.d_disp_off);
+    launch_displace(c->stream, st.d_disp_q, (int)count, run.max_tiles, (int)radius, st.d_disp_tiles, st.d_disp_tables, st.d_disp_off);
     HIP_OK(hipGetLastError());
     std::vector<uint64_t> own;
     if (!tables) {
@@ -497,12 +503,11 @@ int musica_sim_multiscale(musica_ctx* c, uint32_t count, const musica_sim_query*
     if (!(ensure(c, &st.d_scale_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_scale_jobs, max_jobs) &&
           ensure(c, &st.d_scale_part, max_jobs * kScaleMaxBlocks) && ensure(c, &st.d_scale_out, max_jobs)))
         return fail("musica_sim_multiscale: device allocation failed");
-    if (!scales_grow(c, &st.d_scale_planes, &st.scale_planes_cap, bytes) || !scales_grow(c, &st.d_scale_pool, &st.scale_pool_cap, tiles)) return 0;
+    if (!grow(c, "musica_sim_multiscale", &st.d_scale_planes, &st.scale_planes_cap, bytes) ||
+        !grow(c, "musica_sim_multiscale", &st.d_scale_pool, &st.scale_pool_cap, tiles))
+        return 0;
     ScaleConsts k;
-    const double k1 = 0.01 * 255, k2 = 0.03 * 255;   // as musica_sim_compare
-    k.c1 = pow(k1, 2.0);
-    k.c2 = pow(k2, 2.0);
-    k.cov_norm = 49.0 / 48.0;
+    static_cast<SimConsts&>(k) = sim_consts();
     for (int s = 0; s < MUSICA_SIM_MAX_SCALES; s++) {
         k.div1[s] = (double)(49ull << (2 * s));   // 49 * 4^s and 49 * 16^s: exact doubles
         k.div2[s] = (double)(49ull << (4 * s));
@@ -592,8 +597,8 @@ static void ensemble_finish(const unsigned long long* r /* kEnsTotals */, uint32
     o->var_max = r[5];
     o->pixels = n;
     o->realisations = K;
-    o->tiles_x = (q.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
-    o->tiles_y = (q.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+    o->tiles_x = (uint32_t)tiles_along(q.w);
+    o->tiles_y = (uint32_t)tiles_along(q.h);
     o->mean_shift = (double)o->bias_sum / (double)(k * n);
     o->bias_rms = sqrt((double)o->sq_bias_sum / (double)(k * k * n));
     o->noise_rms = K == 1 ? 0.0 : sqrt((double)o->var_sum / (double)(k * (k - 1) * n));
@@ -613,8 +618,7 @@ int musica_sim_ensemble_result(musica_ctx* c, uint32_t count, const musica_sim_q
             return fail("musica_sim_ensemble_result: query %u: 65025 * %u^2 * %u * %u does not fit 64 bits", i, K, qs[i].w, qs[i].h);
     const size_t nw = sim_side(c);
     std::vector<EnsQueryDev> hq(count);
-    size_t tiles = 0;
-    int max_tiles = 1;
+    TileRun run;
     for (uint32_t i = 0; i < count; i++) {
         const musica_sim_query& q = qs[i];
         EnsQueryDev& d = hq[i];
@@ -623,24 +627,16 @@ int musica_sim_ensemble_result(musica_ctx* c, uint32_t count, const musica_sim_q
         d.s_pitch = d.b_pitch = (int)nw;
         d.w = (int)q.w;
         d.h = (int)q.h;
-        d.tiles_x = (d.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
-        d.tiles_y = (d.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
-        d.tile_base = tiles;
-        tiles += (size_t)d.tiles_x * d.tiles_y;
-        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+        run.place(d, 1);
     }
+    const size_t tiles = run.next;
     CHECK_CTX(c);
     if (!(ensure(c, &st.d_ens_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_ens_out, (size_t)MUSICA_SIM_MAX_QUERIES * kEnsTotals)))
         return fail("musica_sim_ensemble_result: device allocation failed");
-    if (tiles > st.ens_tiles_cap) {   // sized for the call: the largest call so far
-        HIP_OK(drelease(c, &st.d_ens_tiles));
-        st.ens_tiles_cap = 0;
-        if (!dalloc(c, &st.d_ens_tiles, 2 * tiles)) return fail("musica_sim_ensemble_result: device allocation of %zu tile pairs failed", tiles);
-        st.ens_tiles_cap = tiles;
-    }
+    if (!grow(c, "musica_sim_ensemble_result", &st.d_ens_tiles, &st.ens_tiles_cap, tiles, "tile pairs", 2)) return 0;
     HIP_OK(hipMemcpyAsync(st.d_ens_q, hq.data(), count * sizeof(EnsQueryDev), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemsetAsync(st.d_ens_out, 0, (size_t)count * kEnsTotals * sizeof(unsigned long long), c->stream));
-    launch_ens_stats(c->stream, st.d_ens_q, (int)count, max_tiles, K, st.d_ens_tiles, st.d_ens_out);
+    launch_ens_stats(c->stream, st.d_ens_q, (int)count, run.max_tiles, K, st.d_ens_tiles, st.d_ens_out);
     HIP_OK(hipGetLastError());
     std::vector<unsigned long long> res((size_t)count * kEnsTotals);
     HIP_OK(hipMemcpyAsync(res.data(), st.d_ens_out, res.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -652,11 +648,6 @@ int musica_sim_ensemble_result(musica_ctx* c, uint32_t count, const musica_sim_q
 }
 
 // ---- the noise's spatial covariance (musica_sim_ensemble_track / _covariance, include/musica.h; kernels_covariance.hip) ---------------
-static void cov_tiles(const musica_sim_query& q, int* tx, int* ty) {
-    *tx = (int)((q.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE);
-    *ty = (int)((q.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE);
-}
-
 int musica_sim_ensemble_track(musica_ctx* c, uint32_t radius, uint32_t count, const musica_sim_query* qs) {
     ABI_TRY
     if (!c) return fail("musica_sim_ensemble_track: ctx is NULL");
@@ -670,8 +661,7 @@ int musica_sim_ensemble_track(musica_ctx* c, uint32_t radius, uint32_t count, co
     const uint64_t nw = sim_side(c);
     const size_t T = (size_t)(radius + 1) * (2 * radius + 1);
     std::vector<CovRegionDev> hr(count);
-    size_t words = 0;
-    int max_tiles = 1;
+    TileRun run;
     for (uint32_t i = 0; i < count; i++) {
         const musica_sim_query& q = qs[i];
         if (q.ax < radius || (uint64_t)q.ax + q.w + radius > nw || (uint64_t)q.ay + q.h + radius > nw)
@@ -684,29 +674,20 @@ int musica_sim_ensemble_track(musica_ctx* c, uint32_t radius, uint32_t count, co
         d.ay = (int)q.ay;
         d.w = (int)q.w;
         d.h = (int)q.h;
-        cov_tiles(q, &d.tiles_x, &d.tiles_y);
-        d.tile_base = words;
-        words += (size_t)d.tiles_x * d.tiles_y * T;
-        max_tiles = std::max(max_tiles, d.tiles_x * d.tiles_y);
+        run.place(d, T);
     }
+    const size_t words = run.next;
     CHECK_CTX(c);
     if (!(ensure(c, &st.d_cov_r, MUSICA_SIM_COV_MAX_REGIONS) &&
           ensure(c, &st.d_cov_tables, (size_t)MUSICA_SIM_COV_MAX_REGIONS * (MUSICA_SIM_MAX_RADIUS + 1) * (2 * MUSICA_SIM_MAX_RADIUS + 1))))
         return fail("musica_sim_ensemble_track: device allocation failed");
-    if (words > st.cov_tiles_cap) {   // sized for the call: the largest call so far
-        HIP_OK(drelease(c, &st.d_cov_tiles));
-        HIP_OK(drelease(c, &st.d_cov_ctiles));
-        st.cov_tiles_cap = 0;
-        if (!dalloc(c, &st.d_cov_tiles, words) || !dalloc(c, &st.d_cov_ctiles, words))
-            return fail("musica_sim_ensemble_track: device allocation of %zu tile-table words failed", words);
-        st.cov_tiles_cap = words;
-    }
+    if (!grow(c, "musica_sim_ensemble_track", &st.d_cov_tiles, &st.cov_tiles_cap, words, "tile-table words", 1, &st.d_cov_ctiles)) return 0;
     HIP_OK(hipMemsetAsync(st.d_cov_tiles, 0, words * sizeof(unsigned long long), c->stream));   // behind what the stream holds
     HIP_OK(hipMemcpyAsync(st.d_cov_r, hr.data(), count * sizeof(CovRegionDev), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));   // hr is read by then
     for (uint32_t i = 0; i < count; i++) st.cov_q[i] = qs[i];
     st.cov_radius = radius;
-    st.cov_max_tiles = max_tiles;
+    st.cov_max_tiles = run.max_tiles;
     st.cov_words = words;
     st.cov_regions = count;
     return 1;
@@ -724,8 +705,8 @@ static void covariance_finish(const int64_t* Ct, uint32_t K, uint32_t radius, co
     o->pixels = n;
     o->realisations = K;
     o->radius = radius;
-    o->tiles_x = (q.w + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
-    o->tiles_y = (q.h + MUSICA_SIM_TILE - 1) / MUSICA_SIM_TILE;
+    o->tiles_x = (uint32_t)tiles_along(q.w);
+    o->tiles_y = (uint32_t)tiles_along(q.h);
     o->noise_var = K == 1 ? 0.0 : (double)c00 / (double)(k * (k - 1) * n);
     o->rho_x = c00 == 0 ? 0.0 : (double)Ct[R + 1] / (double)c00;
     o->rho_y = c00 == 0 ? 0.0 : (double)Ct[S + R] / (double)c00;
