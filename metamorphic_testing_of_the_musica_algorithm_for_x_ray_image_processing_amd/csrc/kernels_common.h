@@ -19,6 +19,27 @@ __device__ __forceinline__ float from_right_lane(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(s, s, 0x130, 0xF, 0xF, true));
 }
 
+// The same moves for a strip's edge lanes: the lane without a source (lane 0 of wave_shr, lane 63 of wave_shl) keeps `edge` — with
+// bound_ctrl = 0 the instruction leaves that lane's destination as it is, and `old` is what the destination holds. What was a DPP move
+// and a select per value is the move alone.
+__device__ __forceinline__ float from_left_lane_or(float v, float edge) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float from_right_lane_or(float v, float edge) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, false));
+}
+// quad_perm [I, I, I, I]: every lane receives the value lane I of its own group of four lanes holds.
+template <int I>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, I * 0x55, 0xF, 0xF, true);
+}
+template <int I>
+__device__ __forceinline__ float quad_bcast(float v) { return __uint_as_float(quad_bcast<I>(__float_as_uint(v))); }
+// A strip's edge lanes (0 and 63) hand a word they loaded to the four lanes of their quad: lane 0 is lane 0 of the first quad, lane 63 lane 3
+// of the last one, and the other three lanes of either quad hold 0 (they requested out of range), so the OR of the two broadcasts is the
+// edge lane's word in lanes 0 .. 3 and 60 .. 63 and 0 in between.
+__device__ __forceinline__ uint32_t edge_quad_word(uint32_t v) { return quad_bcast<0>(v) | quad_bcast<3>(v); }
+
 // ---- branch-free memory access through buffer descriptors ----
 // A raw buffer load whose byte offset lies outside the descriptor returns 0 and touches no memory;
 // a store there is dropped. Lanes that must not access memory therefore just carry kOob as their

@@ -21,6 +21,7 @@
 //
 // Both forms evaluate exactly the oracle's MUSICA_ORDER_FAST arithmetic.
 #include <stdlib.h>
+#include <type_traits>
 #include "kernels_common.h"
 #include "sdev_parts.h"
 #include "launchers.h"
@@ -412,12 +413,20 @@ __device__ __forceinline__ void lowpass_pair(const CRow& a, const CRow& b, const
 // (four raw halo pixels per row instead of two / one). Every value is produced by the expressions of reduce_row() and
 // lowpass_pair(), so both outputs are bit-identical to the two-kernel path (tested against the oracle and against it).
 // ======================================================================================
-// (Round 4 measured the halo columns spread over the lanes of the first and last quad, one column per lane, with quad-broadcast DPP moves:
-// 540 -> 503 vector instructions per trip and the same 49 - 53 us at 8 x 2048^2 — but 96 - 115 us instead of 89 - 91 us at 8192^2, eight 2-byte
-// halo requests per row instead of two 8-byte ones; the round-3 form below stays. profiles/r04_rb0_experiments.txt)
+// Level 0 (raw pixels, FRowQ): the four halo pixels are requested by the edge lane alone, one 8-byte request per row, and then spread over the
+// four lanes of its quad in registers (edge_quad_word): lane i of the first quad normalises column c0-4+i and runs its vertical chain, lane 60+i
+// of the last quad column c0+512+i — one norm_px and one chain5 per lane and row where every lane ran four — and coarse_row() gathers the
+// four chains back with quad broadcasts. (Round 4 had spread the columns by LOADING one per lane: eight 2-byte requests per row instead of two
+// 8-byte ones, the same 49 - 53 us at 8 x 2048^2 and 96 - 115 us instead of 89 - 91 us at 8192^2. profiles/r04_rb0_experiments.txt)
+// The f32 levels keep the four halo values on every lane (FRow): there is no normalisation to save, and spreading four whole words costs
+// more moves than the three chains it removes (319 -> 331 vector instructions per trip, profiles/r06_level0_lane_work.txt).
 struct FRow {
-    float v[8];   // normalized pixels c .. c+7
+    float v[8];   // pixels c .. c+7
     float h[4];   // c-4 .. c-1 on lane 0, c+8 .. c+11 on lane 63 (strips with a neighbour on that side; 0 elsewhere)
+};
+struct FRowQ {
+    float v[8];   // normalized pixels c .. c+7
+    float h;      // lane i of the strip's first quad: column c0-4+i; lane 60+i: column c0+512+i (strips with a neighbour on that side); unused elsewhere
 };
 struct RawF {
     float4 m;     // 8 raw uint16 (bit pattern)
@@ -427,21 +436,29 @@ __device__ __forceinline__ void load_raw_f(RawF& r, const Buf& b, uint32_t row_o
     r.m = bload4(b, off + row_off);
     r.h = bload2(b, off_h + row_off);
 }
-__device__ __forceinline__ void convert_f(FRow& r, const RawF& w, const NormK& nk) {
+// `qi` = lane % 4: which of the edge lane's four halo pixels this lane takes
+__device__ __forceinline__ void convert_f(FRowQ& r, const RawF& w, const NormK& nk, const uint32_t qi) {
     norm8(r.v, w.m, nk);
-    const uint32_t a = __float_as_uint(w.h.x), b = __float_as_uint(w.h.y);
-    r.h[0] = norm_px(a & 0xFFFFu, nk);
-    r.h[1] = norm_px(a >> 16, nk);
-    r.h[2] = norm_px(b & 0xFFFFu, nk);
-    r.h[3] = norm_px(b >> 16, nk);
+    const uint32_t a = edge_quad_word(__float_as_uint(w.h.x)), b = edge_quad_word(__float_as_uint(w.h.y));
+    r.h = norm_px(((qi & 2u) ? b : a) >> ((qi & 1u) * 16u) & 0xFFFFu, nk);
 }
 // One coarse row (the lane's 4 columns + the halo column of an edge lane) from its five fine rows: reduce_row()'s arithmetic.
-__device__ __forceinline__ void coarse_row(CRow& cr, const FRow& r0, const FRow& r1, const FRow& r2, const FRow& r3, const FRow& r4, const LaneCfg& g) {
+// the vertical chains of the four halo columns, as lane 0 / lane 63 use them
+__device__ __forceinline__ void halo_chains(float (&vh)[4], const FRow& r0, const FRow& r1, const FRow& r2, const FRow& r3, const FRow& r4) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) vh[j] = chain5(r0.h[j], r1.h[j], r2.h[j], r3.h[j], r4.h[j]);
+}
+// one chain per lane of the edge lane's quad (c-4 .. c-1 for lane 0, c+8 .. c+11 for lane 63), gathered with quad broadcasts
+__device__ __forceinline__ void halo_chains(float (&vh)[4], const FRowQ& r0, const FRowQ& r1, const FRowQ& r2, const FRowQ& r3, const FRowQ& r4) {
+    const float vq = chain5(r0.h, r1.h, r2.h, r3.h, r4.h);
+    vh[0] = quad_bcast<0>(vq); vh[1] = quad_bcast<1>(vq); vh[2] = quad_bcast<2>(vq); vh[3] = quad_bcast<3>(vq);
+}
+template <class R>
+__device__ __forceinline__ void coarse_row(CRow& cr, const R& r0, const R& r1, const R& r2, const R& r3, const R& r4, const LaneCfg& g) {
     float v[8], vh[4];
 #pragma unroll
     for (int j = 0; j < 8; j++) v[j] = chain5(r0.v[j], r1.v[j], r2.v[j], r3.v[j], r4.v[j]);
-#pragma unroll
-    for (int j = 0; j < 4; j++) vh[j] = chain5(r0.h[j], r1.h[j], r2.h[j], r3.h[j], r4.h[j]);
+    halo_chains(vh, r0, r1, r2, r3, r4);
     float vl6 = from_left_lane(v[6]);
     float vl7 = from_left_lane(v[7]);
     float vr0 = from_right_lane(v[0]);
@@ -462,7 +479,8 @@ __device__ __forceinline__ void coarse_row(CRow& cr, const FRow& r0, const FRow&
     cr.hl = ch;
     cr.hr = ch;
 }
-__device__ __forceinline__ void band_pair(const CRow& a, const CRow& b, const CRow& c, const FRow& fe, const FRow& fo, const LaneCfg& g,
+template <class R>
+__device__ __forceinline__ void band_pair(const CRow& a, const CRow& b, const CRow& c, const R& fe, const R& fo, const LaneCfg& g,
                                           const Buf& bb, uint32_t off_e, uint32_t off_o) {
     float lowE[8], lowO[8], be[8], bo[8];
     lowpass_pair(a, b, c, g, lowE, lowO);
@@ -476,7 +494,7 @@ __device__ __forceinline__ void band_pair(const CRow& a, const CRow& b, const CR
 }
 
 // bit j: fe.v[j] <= 0.9, bit 8 + j: fo.v[j] <= 0.9 — the shader's own comparison on the normalized value (NaN: false)
-__device__ __forceinline__ uint32_t le090_bits(const FRow& fe, const FRow& fo) {
+__device__ __forceinline__ uint32_t le090_bits(const FRowQ& fe, const FRowQ& fo) {
     uint32_t m = 0u;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -528,19 +546,20 @@ __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine,
     const uint32_t px_bytes = U16 ? 2u : 4u;
     const uint32_t foff = g.off == kOob ? kOob : (uint32_t)g.c * px_bytes;
     const uint32_t foff_h = g.off_l != kOob ? (uint32_t)(g.c - 4) * px_bytes : (g.off_r != kOob ? (uint32_t)(g.c + 8) * px_bytes : kOob);
+    const uint32_t qi = (uint32_t)lane & 3u;
     const int hi = S - 1;
     const uint32_t frb = U16 ? (uint32_t)S * 2u : (uint32_t)pitch * 4u, rb = (uint32_t)pitch * 4u, crb = (uint32_t)cpitch * 4u;
     const int ks = max(k0 - 1, 0), ke = min(k1, Sc - 1);   // coarse rows this wavefront computes (the first / last only feed its band rows)
 
-    FRow w0, w1, w2, w3, w4;
+    typename std::conditional<U16, FRowQ, FRow>::type w0, w1, w2, w3, w4;
     RawF ra, rc;
-    if (U16) {
+    if constexpr (U16) {
         load_raw_f(ra, ib, (uint32_t)mirror_idx(2 * ks - 2, hi) * frb, foff, foff_h);
-        convert_f(w0, ra, nk);
+        convert_f(w0, ra, nk, qi);
         load_raw_f(ra, ib, (uint32_t)mirror_idx(2 * ks - 1, hi) * frb, foff, foff_h);
-        convert_f(w1, ra, nk);
+        convert_f(w1, ra, nk, qi);
         load_raw_f(ra, ib, (uint32_t)(2 * ks) * frb, foff, foff_h);
-        convert_f(w2, ra, nk);
+        convert_f(w2, ra, nk, qi);
         load_raw_f(ra, ib, (uint32_t)mirror_idx(2 * ks + 1, hi) * frb, foff, foff_h);
         load_raw_f(rc, ib, (uint32_t)mirror_idx(2 * ks + 2, hi) * frb, foff, foff_h);
     } else {
@@ -551,9 +570,9 @@ __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine,
     CRow c0, cm1, cm2;
     cm1 = CRow(); cm2 = CRow();
     for (int k = ks; k <= ke; k++) {
-        if (U16) {
-            convert_f(w3, ra, nk);   // the pair requested one trip ago
-            convert_f(w4, rc, nk);
+        if constexpr (U16) {
+            convert_f(w3, ra, nk, qi);   // the pair requested one trip ago
+            convert_f(w4, rc, nk, qi);
             const int kn = min(k + 1, ke);
             load_raw_f(ra, ib, (uint32_t)mirror_idx(2 * kn + 1, hi) * frb, foff, foff_h);
             load_raw_f(rc, ib, (uint32_t)mirror_idx(2 * kn + 2, hi) * frb, foff, foff_h);
@@ -568,7 +587,7 @@ __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine,
         // km1(0) = coarse_of_fine(-2) = 1 (reflect-101 on the fine grid, img_smooth_upsampled.comp:10-16): row k itself.
         const int kp = k - 1;
         if (kp >= k0 && kp < k1) {  // wave-uniform
-            if (want_mask) bstore_u16(mb, moff + (uint32_t)kp * mrb, le090_bits(w0, w1));
+            if constexpr (U16) if (want_mask) bstore_u16(mb, moff + (uint32_t)kp * mrb, le090_bits(w0, w1));
             band_pair(kp == 0 ? c0 : cm2, cm1, c0, w0, w1, g, bb, (uint32_t)(2 * kp) * rb, (uint32_t)(2 * kp + 1) * rb);
         }
         cm2 = cm1; cm1 = c0;
@@ -576,7 +595,7 @@ __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine,
     }
     // the last row pair of the image: kp1(Sc-1) = coarse_of_fine(S) = Sc-1 (fine row S mirrors onto S-2)
     if (k1 == Sc) {
-        if (want_mask) bstore_u16(mb, moff + (uint32_t)(Sc - 1) * mrb, le090_bits(w0, w1));
+        if constexpr (U16) if (want_mask) bstore_u16(mb, moff + (uint32_t)(Sc - 1) * mrb, le090_bits(w0, w1));
         band_pair(cm2, cm1, cm1, w0, w1, g, bb, (uint32_t)(2 * (Sc - 1)) * rb, (uint32_t)(2 * (Sc - 1) + 1) * rb);
     }
 }
@@ -730,16 +749,14 @@ struct BRow {
     float v[8];     // band columns c .. c+7
     float e0, e1;   // lane 0: columns c-2, c-1; lane 63: columns c+8, c+9 (0 where the image ends); unused elsewhere
 };
-__device__ __forceinline__ void sdev_from_band(const BRow& r0, const BRow& r1, const BRow& r2, const BRow& r3, const BRow& r4, bool lane0, bool lane63, float (&s)[8]) {
+__device__ __forceinline__ void sdev_from_band(const BRow& r0, const BRow& r1, const BRow& r2, const BRow& r3, const BRow& r4, float (&s)[8]) {
     float q[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) q[j] = sum5(r0.v[j] * r0.v[j], r1.v[j] * r1.v[j], r2.v[j] * r2.v[j], r3.v[j] * r3.v[j], r4.v[j] * r4.v[j]);
     const float qe0 = sum5(r0.e0 * r0.e0, r1.e0 * r1.e0, r2.e0 * r2.e0, r3.e0 * r3.e0, r4.e0 * r4.e0);
     const float qe1 = sum5(r0.e1 * r0.e1, r1.e1 * r1.e1, r2.e1 * r2.e1, r3.e1 * r3.e1, r4.e1 * r4.e1);
-    float a6 = from_left_lane(q[6]), a7 = from_left_lane(q[7]);
-    float b0 = from_right_lane(q[0]), b1 = from_right_lane(q[1]);
-    if (lane0) { a6 = qe0; a7 = qe1; }
-    if (lane63) { b0 = qe0; b1 = qe1; }
+    const float a6 = from_left_lane_or(q[6], qe0), a7 = from_left_lane_or(q[7], qe1);   // lane 0 keeps its left pair, lane 63 its right one
+    const float b0 = from_right_lane_or(q[0], qe0), b1 = from_right_lane_or(q[1], qe1);
     s[0] = sum5(a6, a7, q[0], q[1], q[2]);
     s[1] = sum5(a7, q[0], q[1], q[2], q[3]);
     s[2] = sum5(q[0], q[1], q[2], q[3], q[4]);
@@ -900,13 +917,13 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
             const bool one_dark = CH && !kc.ramp && kc.high;
             {   // even row 2k: window rows 2k - 2 .. 2k + 2, its band values are the centre row's
                 float sd[8];
-                sdev_from_band(r0, r1, r2, r3, r4, g.lane0, g.lane63, sd);
+                sdev_from_band(r0, r1, r2, r3, r4, sd);
                 row_phase(0, lowE, r2.v, sd, lowE, fe, le, k, w_cnr, w_dark_or_ramp, one_ramp, one_dark);
             }
             load_brow(r0, 2 * k + 4, more);   // the slot of row 2k - 2 takes row 2k + 4 (the next trip's; nothing if there is none)
             {   // odd row 2k + 1: rows 2k - 1 .. 2k + 3
                 float sd[8];
-                sdev_from_band(r1, r2, r3, r4, r5, g.lane0, g.lane63, sd);
+                sdev_from_band(r1, r2, r3, r4, r5, sd);
                 row_phase(1, lowO, r3.v, sd, lowO, fo, le, k, w_cnr, w_dark_or_ramp, one_ramp, one_dark);
             }
             load_brow(r1, 2 * k + 5, more);

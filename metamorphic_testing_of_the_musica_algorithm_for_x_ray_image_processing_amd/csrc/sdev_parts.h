@@ -38,16 +38,14 @@ __device__ __forceinline__ void hist_lds_flush(const uint32_t* lh, uint32_t* __r
 
 struct SRow {
     float q[8];    // squares of columns c .. c+7
-    float l0, l1;  // squares of columns c-2, c-1   (lane 0 of a strip that is not the first)
-    float h0, h1;  // squares of columns c+8, c+9   (lane 63)
+    float e0, e1;  // lane 0: squares of columns c-2, c-1 (a strip that is not the first); lane 63: of columns c+8, c+9; 0 on every other lane
 };
 
 // Byte offsets of one lane inside a row; kOob where the access would leave the image (reads as 0: Q1).
 struct SCfg {
     int c;
     uint32_t off0, off1;  // 16-byte groups c .. c+3, c+4 .. c+7
-    uint32_t off_l;       // c-2, c-1 (lane 0)
-    uint32_t off_r;       // c+8, c+9 (lane 63)
+    uint32_t off_e;       // the edge pair: c-2, c-1 on lane 0, c+8, c+9 on lane 63, kOob on every other lane
     int valid;            // number of in-image columns among the lane's 8 (pad columns of a pitched row must read as 0)
     bool lane0, lane63;
 };
@@ -60,8 +58,9 @@ __device__ __forceinline__ SCfg make_scfg(int strip, int lane, int S) {
     g.valid = min(max(S - g.c, 0), 8);
     g.off0 = g.c < S ? (uint32_t)g.c * 4u : kOob;
     g.off1 = g.c + 4 < S ? (uint32_t)(g.c + 4) * 4u : kOob;
-    g.off_l = (g.lane0 && g.c >= 2 && g.c < S) ? (uint32_t)(g.c - 2) * 4u : kOob;
-    g.off_r = (g.lane63 && g.c + 8 < S) ? (uint32_t)(g.c + 8) * 4u : kOob;
+    const uint32_t off_l = (g.lane0 && g.c >= 2 && g.c < S) ? (uint32_t)(g.c - 2) * 4u : kOob;
+    const uint32_t off_r = (g.lane63 && g.c + 8 < S) ? (uint32_t)(g.c + 8) * 4u : kOob;
+    g.off_e = g.lane0 ? off_l : off_r;
     return g;
 }
 
@@ -69,14 +68,13 @@ __device__ __forceinline__ SCfg make_scfg(int strip, int lane, int S) {
 // right-halo column are masked to 0 by `valid` / the c+9 test when the row is squared.
 struct SRaw {
     float4 a, d;
-    float2 l, h;
+    float2 e;
 };
 __device__ __forceinline__ void load_sraw(SRaw& r, const Buf& b, uint32_t row_off, const SCfg& g) {
     // kOob has only bit 31 set and every in-image offset is < 2^31, so an OR keeps "either one out of range" out of range
     r.a = bload4(b, (g.off0 + row_off) | ((g.off0 | row_off) & kOob));
     r.d = bload4(b, (g.off1 + row_off) | ((g.off1 | row_off) & kOob));
-    r.l = bload2(b, (g.off_l + row_off) | ((g.off_l | row_off) & kOob));
-    r.h = bload2(b, (g.off_r + row_off) | ((g.off_r | row_off) & kOob));
+    r.e = bload2(b, (g.off_e + row_off) | ((g.off_e | row_off) & kOob));
 }
 // A8: the side is a multiple of 8, so a lane's 8 columns are all inside the image or all outside (then every load of the lane is
 // out of range and reads 0) and the right-halo pair c+8, c+9 likewise: no per-column masks.
@@ -88,10 +86,9 @@ __device__ __forceinline__ void square_srow(SRow& r, const SRaw& w, const SCfg& 
         const float t = (A8 || j < g.valid) ? v[j] : 0.0f;
         r.q[j] = t * t;
     }
-    r.l0 = w.l.x * w.l.x; r.l1 = w.l.y * w.l.y;
-    r.h0 = w.h.x * w.h.x;
-    const float h1 = (A8 || g.c + 9 < S) ? w.h.y : 0.0f;
-    r.h1 = h1 * h1;
+    r.e0 = w.e.x * w.e.x;
+    const float e1 = (A8 || g.lane0 || g.c + 9 < S) ? w.e.y : 0.0f;   // only the right pair can reach past the image (column c + 9 of a pitched row)
+    r.e1 = e1 * e1;
 }
 template <bool A8>
 __device__ __forceinline__ void load_srow(SRow& r, const Buf& b, uint32_t row_off, const SCfg& g, int S) {
@@ -122,12 +119,10 @@ __device__ __forceinline__ void sdev_values(const SRow& r0, const SRow& r1, cons
     float q[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) q[j] = sum5(r0.q[j], r1.q[j], r2.q[j], r3.q[j], r4.q[j]);
-    const float ql0 = sum5(r0.l0, r1.l0, r2.l0, r3.l0, r4.l0), ql1 = sum5(r0.l1, r1.l1, r2.l1, r3.l1, r4.l1);
-    const float qh0 = sum5(r0.h0, r1.h0, r2.h0, r3.h0, r4.h0), qh1 = sum5(r0.h1, r1.h1, r2.h1, r3.h1, r4.h1);
-    float a6 = from_left_lane(q[6]), a7 = from_left_lane(q[7]);
-    float b0 = from_right_lane(q[0]), b1 = from_right_lane(q[1]);
-    if (g.lane0) { a6 = ql0; a7 = ql1; }    // zeros at the image's left edge (loads out of range)
-    if (g.lane63) { b0 = qh0; b1 = qh1; }   // zeros beyond the right edge
+    const float qe0 = sum5(r0.e0, r1.e0, r2.e0, r3.e0, r4.e0), qe1 = sum5(r0.e1, r1.e1, r2.e1, r3.e1, r4.e1);
+    // lane 0 keeps its left pair, lane 63 its right one: zeros at the image's left edge and beyond its right edge (loads out of range)
+    const float a6 = from_left_lane_or(q[6], qe0), a7 = from_left_lane_or(q[7], qe1);
+    const float b0 = from_right_lane_or(q[0], qe0), b1 = from_right_lane_or(q[1], qe1);
     // lanes right of the image hold q == 0, so the last in-image lane reads zeros from its neighbour
     s[0] = sum5(a6, a7, q[0], q[1], q[2]);
     s[1] = sum5(a7, q[0], q[1], q[2], q[3]);
