@@ -10,17 +10,24 @@ script.py:143-145), SSIM (:147-152) and histogram distances (:154-198), both "di
 parameter grids and the metric definitions, can drive the library in-process or through the drop-in CLI
 exactly like `run_process` (:200-214), and exposes the relations as data so tests can assert them on
 phantoms (the reference's raw_images/ are missing blobs).
+
+The host restatements of the metrics live in metrics.py, the CSV and BMP writers in report.py; this module re-exports both, so
+harness.<name> reaches every one of them, and keeps the grids and generators, the registration, Runner, run_study and the command line.
 """
-import csv
+import collections
 import itertools
 import math
 import os
 import subprocess
+import types
 
 import numpy as np
 from scipy import ndimage
 
 from . import processing as mp
+from .metrics import *   # noqa: F401,F403 -- this module is the import surface: every restatement stays reachable as harness.<name>
+from .metrics import _covariance_geometry, _inset, _joint_moments   # noqa: F401 -- the underscored ones the tests and probes use
+from .report import *    # noqa: F401,F403
 
 PROCESSING_MARGIN = 10  # script.py:24 == MUSICA_OUT_MARGIN
 
@@ -136,589 +143,6 @@ def binomial_blur(image, radius):
         for k in range(2 * r + 1):
             acc += np.uint64(math.comb(2 * r, k)) * (padded[k:k + acc.shape[0]] if axis == 0 else padded[:, k:k + acc.shape[1]])
     return ((acc + np.uint64(1 << (4 * r - 1))) >> np.uint64(4 * r)).astype(image.dtype)
-
-
-# ---- similarity metrics (script.py:143-198) ----------------------------------------------------------
-
-def mse_similarity(a, b):
-    """1 - RMSE / 255 (script.py:143-145)."""
-    e = np.abs(a.astype(np.float64) - b.astype(np.float64)) / 255
-    return 1.0 - math.sqrt(np.mean(np.square(e)))
-
-
-def ssim_similarity(a, b):
-    """skimage.metrics.structural_similarity with its defaults for uint8 input (script.py:147-152):
-    7 x 7 uniform window, K1 = 0.01, K2 = 0.03, data range 255, sample covariance, borders cropped."""
-    x, y = a.astype(np.float64), b.astype(np.float64)
-    win = 7
-    npx = win * win
-    cov_norm = npx / (npx - 1)
-    ux, uy = ndimage.uniform_filter(x, win), ndimage.uniform_filter(y, win)
-    uxx, uyy, uxy = ndimage.uniform_filter(x * x, win), ndimage.uniform_filter(y * y, win), ndimage.uniform_filter(x * y, win)
-    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
-    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
-    s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
-    pad = (win - 1) // 2
-    return float(s[pad:-pad, pad:-pad].mean())
-
-
-def hist_similarity(a, b):
-    """(intersection, normalised Euclidean distance, Bhattacharyya coefficient) of the 256-bin histograms
-    (script.py:154-198; np.histogram(bins=256) spans [min, max] of each image, as there)."""
-    ha, _ = np.histogram(a.ravel(), bins=256)
-    hb, _ = np.histogram(b.ravel(), bins=256)
-    inter = np.sum(np.minimum(ha, hb)) / min(np.sum(ha), np.sum(hb))
-    na, nb = ha / np.sum(ha), hb / np.sum(hb)
-    e_dist = math.sqrt(np.sum((na - nb) ** 2)) / math.sqrt(2)
-    b_coef = float(np.sum(np.sqrt(na * nb)))
-    return float(inter), float(e_dist), b_coef
-
-
-def similarities(a, b):
-    inter, e_dist, b_coef = hist_similarity(a, b)
-    return {"mse": mse_similarity(a, b), "ssim": ssim_similarity(a, b), "hist_intersection": inter,
-            "hist_distance": e_dist, "hist_bhattacharyya": b_coef}
-
-
-# ---- tone metrics from the joint gray-level histogram (not in the reference's script) ----------------------
-# MUSICA's gradation follows the image's own histogram, so an alteration that changes the histogram moves the global tone curve of the
-# output, and mse / ssim charge that shift in full. The joint histogram J[a][b] of two aligned 8-bit images separates it: mutual
-# information (Viola & Wells; Maes et al.) and the correlation ratio (Roche et al.) do not change under an invertible remap of b's gray
-# levels, and the least-squares remap E[a | b] itself turns a comparison into a tone-matched one. These functions state the numbers of
-# musica_sim_joint (include/musica.h) in Python integers and f64, in its summation order.
-
-def joint_histogram(a, b):
-    """J[a][b]: how many pixels have the value a in `a` and b in `b` (two uint8 arrays of one shape); (256, 256) int64."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != np.uint8 or b.dtype != np.uint8:
-        raise ValueError("joint_histogram needs two uint8 arrays of one shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
-    return np.bincount(a.ravel().astype(np.int64) * 256 + b.ravel(), minlength=65536).reshape(256, 256)
-
-
-def _joint_moments(J):
-    """Per value b of the second image, as Python integers: B_b (count), S_b = sum_a a J[a][b], Q_b = sum_a a^2 J[a][b]."""
-    J = np.asarray(J).astype(np.int64)
-    v = np.arange(256, dtype=np.int64)
-    return [int(x) for x in J.sum(axis=0)], [int(x) for x in v @ J], [int(x) for x in (v * v) @ J]
-
-
-def tone_lut(J):
-    """The least-squares gray-level remap of b onto a, E[a | b] rounded half up: (2 S_b + B_b) // (2 B_b) where b occurs, else b;
-    (256,) uint8."""
-    B, S, _ = _joint_moments(J)
-    return np.array([(2 * S[b] + B[b]) // (2 * B[b]) if B[b] else b for b in range(256)], dtype=np.uint8)
-
-
-def joint_similarities(J):
-    """mi, nmi, corr_ratio, tone_mse and the entropies h_a, h_b, h_ab (nats) of a joint histogram, as musica_sim_joint computes them:
-    sums in ascending a, then ascending b, zero counts skipped; the variance numerators as exact integers, one f64 division per term."""
-    J = np.asarray(J).astype(np.int64)
-    n = int(J.sum())
-    if n == 0:
-        raise ValueError("empty joint histogram")
-    A = [int(x) for x in J.sum(axis=1)]
-    B, S, Q = _joint_moments(J)
-    dn = float(n)
-
-    def entropy(counts):
-        h = 0.0
-        for c in counts:
-            if c:
-                p = float(c) / dn
-                h -= p * math.log(p)
-        return h
-
-    h_a, h_b = entropy(A), entropy(B)
-    h_ab = mi = 0.0
-    for a, b in zip(*np.nonzero(J)):          # row-major: ascending a, then ascending b
-        j = int(J[a, b])
-        p = float(j) / dn
-        h_ab -= p * math.log(p)
-        mi += p * math.log(float(j * n) / float(A[a] * B[b]))
-    ssw = 0.0
-    for b in range(256):
-        if B[b]:
-            ssw += float(B[b] * Q[b] - S[b] * S[b]) / float(B[b])
-    sst_num = n * sum(a * a * A[a] for a in range(256)) - sum(a * A[a] for a in range(256)) ** 2
-    return {"mi": mi, "nmi": 1.0 if h_a + h_b == 0.0 else 2.0 * mi / (h_a + h_b),
-            "corr_ratio": 1.0 if sst_num == 0 else 1.0 - ssw / (float(sst_num) / dn),
-            "tone_mse": 1.0 - math.sqrt(ssw / dn) / 255.0, "h_a": h_a, "h_b": h_b, "h_ab": h_ab}
-
-
-def tone_similarities(a, b):
-    """The five JOINT_METRICS of two uint8 images of one shape: mi (mutual information, nats), nmi (2 mi / (h_a + h_b)), corr_ratio
-    (1 - SSW / SST: the share of a's variance a function of b explains), tone_mse (mse_similarity after the best gray-level remap of b
-    onto a: 1 - sqrt(SSW / n) / 255) and tone_ssim (ssim_similarity of a and b remapped with tone_lut)."""
-    J = joint_histogram(a, b)
-    r = joint_similarities(J)
-    out = {k: r[k] for k in mp.JOINT_METRICS if k != "tone_ssim"}
-    out["tone_ssim"] = ssim_similarity(a, tone_lut(J)[b])
-    return out
-
-
-# ---- where the output went: exact block matching (musica_sim_displace; not in the reference) ------------------
-
-def _displacement_geometry(a_shape, b_shape, region, radius):
-    """Raises ValueError exactly where musica_sim_displace refuses a query on geometry; returns the region and radius as ints."""
-    ax, ay, bx, by, w, h = (int(v) for v in region)
-    radius = int(radius)
-    if not 1 <= radius <= mp.SIM_MAX_RADIUS:
-        raise ValueError("radius %d out of range [1, %d]" % (radius, mp.SIM_MAX_RADIUS))
-    if w < 7 or h < 7:
-        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
-    if ax < 0 or ay < 0 or ax + w > a_shape[1] or ay + h > a_shape[0]:
-        raise ValueError("region (%d, %d) + %d x %d leaves the %d x %d output plane" % (ax, ay, w, h, a_shape[1], a_shape[0]))
-    if bx < radius or by < radius or bx + w + radius > b_shape[1] or by + h + radius > b_shape[0]:
-        raise ValueError("the b window (%d, %d) + %d x %d grown by the radius %d leaves the %d x %d plane" % (bx, by, w, h, radius, b_shape[1], b_shape[0]))
-    return (ax, ay, bx, by, w, h), radius
-
-
-def _displacement_squares(a, b, region, radius):
-    """((dy, dx), the h x w int64 squared differences of the region under that shift) for every candidate, one shifted crop each."""
-    ax, ay, bx, by, w, h = region
-    ca = np.asarray(a)[ay:ay + h, ax:ax + w].astype(np.int64)
-    b = np.asarray(b)
-    for dy in range(-radius, radius + 1):
-        for dx in range(-radius, radius + 1):
-            yield (dy, dx), (ca - b[by + dy:by + dy + h, bx + dx:bx + dx + w].astype(np.int64)) ** 2
-
-
-def displacement_table(a, b, region, radius):
-    """musica_sim_displace's table of one query, restated: a the output image, b the full reference plane, region = (ax, ay, bx, by, w, h).
-    T[dy + radius][dx + radius] = sum over the region of (a[ay + y][ax + x] - b[by + y + dy][bx + x + dx])^2 for dy, dx in
-    [-radius, radius], one shifted crop per candidate, in int64. ValueError where the C call refuses on geometry: a radius outside
-    1 .. 16, w < 7 or h < 7, an a region that leaves a, a b window that, grown by the radius, leaves b."""
-    region, radius = _displacement_geometry(np.shape(a), np.shape(b), region, radius)
-    T = np.empty((2 * radius + 1,) * 2, dtype=np.int64)
-    for (dy, dx), sq in _displacement_squares(a, b, region, radius):
-        T[dy + radius, dx + radius] = np.sum(sq)
-    return T
-
-
-def displacement_tile_tables(a, b, region, radius):
-    """The same per 64 x 64 tile of the region (the last tiles ragged): (tiles_y, tiles_x, S, S) uint32, tile-row major; their sum over
-    the tiles is displacement_table."""
-    region, radius = _displacement_geometry(np.shape(a), np.shape(b), region, radius)
-    w, h = region[4], region[5]
-    t = mp.SIM_TILE
-    ny, nx, s = (h + t - 1) // t, (w + t - 1) // t, 2 * radius + 1
-    out = np.empty((ny, nx, s, s), dtype=np.uint32)
-    for (dy, dx), sq in _displacement_squares(a, b, region, radius):
-        out[:, :, dy + radius, dx + radius] = np.add.reduceat(np.add.reduceat(sq, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
-    return out
-
-
-def _displacement_argmin(T):
-    """(row, column) of the table's argmin: smallest value, then smallest dx^2 + dy^2, then smallest dy, then smallest dx."""
-    T = np.asarray(T)
-    radius = T.shape[0] // 2
-    ys, xs = np.nonzero(T == T.min())
-    return min(zip(ys.tolist(), xs.tolist()), key=lambda p: ((p[1] - radius) ** 2 + (p[0] - radius) ** 2, p[0], p[1]))
-
-
-def displacement_from_table(T):
-    """{dx, dy, ssd_min, ssd_zero, sub_dx, sub_dy} of an (S, S) displacement table: the argmin by the tie rule, and the vertex of the
-    parabola through the argmin and its two neighbours along the row (sub_dx) and along the column (sub_dy):
-    sub = d + (T- - T+) / (2 (T- - 2 T0 + T+)), computed from the exact integers with one f64 division, where |d| < radius and the
-    denominator is positive, else sub = d. The device and the host studies both call this on exact integer tables."""
-    T = np.asarray(T)
-    if T.ndim != 2 or T.shape[0] != T.shape[1] or T.shape[0] % 2 != 1 or T.shape[0] < 3:
-        raise ValueError("expected an (S, S) table with S = 2 radius + 1, got %r" % (T.shape,))
-    radius = T.shape[0] // 2
-    y, x = _displacement_argmin(T)
-
-    def vertex(d, lo, mid, hi):
-        if abs(d) >= radius:
-            return float(d)
-        lo, mid, hi = int(lo()), int(mid), int(hi())
-        den = 2 * (lo - 2 * mid + hi)
-        return d + (lo - hi) / den if den > 0 else float(d)
-
-    dx, dy = x - radius, y - radius
-    return {"dx": dx, "dy": dy, "ssd_min": int(T[y, x]), "ssd_zero": int(T[radius, radius]),
-            "sub_dx": vertex(dx, lambda: T[y, x - 1], T[y, x], lambda: T[y, x + 1]),
-            "sub_dy": vertex(dy, lambda: T[y - 1, x], T[y, x], lambda: T[y + 1, x])}
-
-
-def displacement_tiles_off(tile_tables):
-    """How many tiles' own argmin (the same tie rule) is not (0, 0)."""
-    tt = np.asarray(tile_tables)
-    radius = tt.shape[2] // 2
-    return sum(1 for ty in range(tt.shape[0]) for tx in range(tt.shape[1]) if _displacement_argmin(tt[ty, tx]) != (radius, radius))
-
-
-SHIFT_KEYS = ("dx", "dy", "sub_dx", "sub_dy", "mse_at_zero", "mse_at_best", "tiles", "tiles_off")
-
-
-def displacement_summary(T, pixels, tiles, tiles_off):
-    """A study row's *_shift dict (SHIFT_KEYS) from an exact table: displacement_from_table's shift, 1 - sqrt(ssd / pixels) / 255 at the
-    zero shift and at the best one, the number of tiles and of those whose own best shift is not (0, 0)."""
-    d = displacement_from_table(T)
-    out = {k: d[k] for k in ("dx", "dy", "sub_dx", "sub_dy")}
-    out["mse_at_zero"] = 1.0 - math.sqrt(d["ssd_zero"] / int(pixels)) / 255.0
-    out["mse_at_best"] = 1.0 - math.sqrt(d["ssd_min"] / int(pixels)) / 255.0
-    out["tiles"], out["tiles_off"] = int(tiles), int(tiles_off)
-    return out
-
-
-def displacement_maps(tile_tables, w, h):
-    """Two (tiles_y, tiles_x) uint8 maps of a w x h region's tile tables, one pixel per tile: the RMSE at the zero shift, rounded, and the
-    length of the tile's best shift, scaled so that the table's corner (radius, radius) is 255."""
-    tt = np.asarray(tile_tables)
-    ny, nx, radius, t = tt.shape[0], tt.shape[1], tt.shape[2] // 2, mp.SIM_TILE
-    rmse, mag = np.zeros((ny, nx), dtype=np.uint8), np.zeros((ny, nx), dtype=np.uint8)
-    for ty in range(ny):
-        for tx in range(nx):
-            px = (min(h, t * ty + t) - t * ty) * (min(w, t * tx + t) - t * tx)
-            rmse[ty, tx] = int(round(math.sqrt(int(tt[ty, tx, radius, radius]) / px)))
-            y, x = _displacement_argmin(tt[ty, tx])
-            mag[ty, tx] = int(round(255.0 * math.hypot(x - radius, y - radius) / (math.sqrt(2.0) * radius)))
-    return rmse, mag
-
-
-def _inset(region, r):
-    """The region (ax, ay, bx, by, w, h) inset by r on every side, or None when a side falls under 7."""
-    ax, ay, bx, by, w, h = region
-    return (ax + r, ay + r, bx + r, by + r, w - 2 * r, h - 2 * r) if min(w, h) - 2 * r >= 7 else None
-
-
-# ---- at which scale the output changed: multi-scale SSIM in exact integers (musica_sim_multiscale; not in the reference) ----
-# MUSICA is a Laplacian pyramid and each of its stages works at scales of its own (per-level contrast curves, noise reduction on levels
-# 0 .. 2, the CNR weighting from level 3, the coarser-levels gain); a single 7 x 7 SSIM cannot tell a loss in the finest bands from a
-# change of the coarse ones. Multi-scale SSIM (Wang, Simoncelli, Bovik 2003) with ssim_similarity's uniform 7 x 7 window has an exact
-# integer form: iterated 2 x 2 mean pooling is the 2^s x 2^s block mean, the block SUMS of u8 data are integers (<= 255 * 4^s), so every
-# window sum at every scale is an exact integer and only the last f64 summation is open to reordering. These functions are the contract
-# of musica_sim_multiscale (include/musica.h).
-MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # the 2003 paper's
-SCALES_KEYS = ("ms_ssim", "scales") + mp.SCALE_METRICS        # a study row's *_scales dict
-
-
-def block_sums(a, s):
-    """X_s of a 2-D integer array: [i][j] = the sum of the 2^s x 2^s block whose top-left is (i 2^s, j 2^s); (h >> s, w >> s) int64,
-    rows and columns that do not fill a block dropped."""
-    a = np.asarray(a)
-    k = 1 << s
-    hs, ws = a.shape[0] >> s, a.shape[1] >> s
-    return a[:hs * k, :ws * k].astype(np.int64).reshape(hs, k, ws, k).sum(axis=(1, 3))
-
-
-def _window_sums7(p):
-    """The sums of all 7 x 7 windows of an int64 plane, (h - 6, w - 6) int64: differences of its summed-area table (exact)."""
-    c = np.zeros((p.shape[0] + 1, p.shape[1] + 1), dtype=np.int64)
-    c[1:, 1:] = p.cumsum(axis=0).cumsum(axis=1)
-    return c[7:, 7:] - c[:-7, 7:] - c[7:, :-7] + c[:-7, :-7]
-
-
-def multiscale_terms(sx, sy, sxx, syy, sxy, s):
-    """(ssim, cs, lum) per window from the exact 7 x 7 window sums of X_s, Y_s, X_s^2, Y_s^2, X_s Y_s (int64 arrays or ints): the means
-    by one f64 division by the exact doubles 49 * 4^s and 49 * 16^s, then ssim_similarity's expression in its order."""
-    d1, d2 = float(49 * 4 ** s), float(49 * 16 ** s)
-    ux, uy = np.asarray(sx, dtype=np.int64) / d1, np.asarray(sy, dtype=np.int64) / d1
-    uxx, uyy, uxy = np.asarray(sxx, dtype=np.int64) / d2, np.asarray(syy, dtype=np.int64) / d2, np.asarray(sxy, dtype=np.int64) / d2
-    cov_norm = 49 / 48
-    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
-    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
-    a1, a2, b1, b2 = 2 * ux * uy + c1, 2 * vxy + c2, ux * ux + uy * uy + c1, vx + vy + c2
-    return (a1 * a2) / (b1 * b2), a2 / b2, a1 / b1
-
-
-def multiscale_windows(a, b, s):
-    """(ssim, cs, lum), each (h_s - 6, w_s - 6) f64: the per-window values of scale s of two uint8 arrays of one shape."""
-    x, y = block_sums(a, s), block_sums(b, s)
-    return multiscale_terms(_window_sums7(x), _window_sums7(y), _window_sums7(x * x), _window_sums7(y * y), _window_sums7(x * y), s)
-
-
-def ms_ssim_from_means(cs, ssim_last):
-    """The combined number from the per-scale means: prod over s < scales - 1 of max(cs[s], 0)^w_s, times max(ssim of the last scale,
-    0)^w_last, w_s = W[s] / sum(W[:scales]); math.pow, ascending s. cs: the means of scales 0 .. scales - 1 (the last is not used)."""
-    n = len(cs)
-    total = sum(MS_SSIM_WEIGHTS[:n])
-    out = 1.0
-    for s in range(n):
-        out *= math.pow(max(float(cs[s]) if s < n - 1 else float(ssim_last), 0.0), MS_SSIM_WEIGHTS[s] / total)
-    return out
-
-
-def max_scales(w, h):
-    """The largest scale count a w x h region admits: min(w, h) >> (count - 1) >= 7; 0 for a region under 7 x 7, at most SIM_MAX_SCALES."""
-    n = 0
-    while n < mp.SIM_MAX_SCALES and (min(int(w), int(h)) >> n) >= 7:
-        n += 1
-    return n
-
-
-def multiscale_similarities(a, b, scales):
-    """musica_sim_multiscale's numbers of two uint8 arrays of one shape (h, w), 1 <= scales <= 5, min(h, w) >> (scales - 1) >= 7 (else
-    ValueError): {ms_ssim, scales, pixels, ssim, cs, lum, mse, ssd, plane_w, plane_h}, the last seven lists of length `scales`.
-    ssim / cs / lum: the means of multiscale_windows over the windows; ssd[s] = sum (X_s - Y_s)^2 (exact);
-    mse[s] = 1 - sqrt(ssd[s] / (h_s w_s)) / (255 * 4^s); ms_ssim: ms_ssim_from_means."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.ndim != 2 or a.shape != b.shape or a.dtype != np.uint8 or b.dtype != np.uint8:
-        raise ValueError("multiscale_similarities needs two uint8 arrays of one 2-D shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
-    scales = int(scales)
-    if not 1 <= scales <= mp.SIM_MAX_SCALES:
-        raise ValueError("scales %d out of range [1, %d]" % (scales, mp.SIM_MAX_SCALES))
-    h, w = a.shape
-    if (min(h, w) >> (scales - 1)) < 7:
-        raise ValueError("region %d x %d is smaller than the 7 x 7 window at scale %d" % (w, h, scales - 1))
-    out = {"scales": scales, "pixels": h * w, "ssim": [], "cs": [], "lum": [], "mse": [], "ssd": [], "plane_w": [], "plane_h": []}
-    for s in range(scales):
-        ssim, cs, lum = multiscale_windows(a, b, s)
-        hs, ws = h >> s, w >> s
-        ssd = int(np.sum((block_sums(a, s) - block_sums(b, s)) ** 2))
-        out["ssim"].append(float(ssim.mean()))
-        out["cs"].append(float(cs.mean()))
-        out["lum"].append(float(lum.mean()))
-        out["ssd"].append(ssd)
-        out["mse"].append(1.0 - math.sqrt(ssd / (hs * ws)) / (255 * 4 ** s))
-        out["plane_w"].append(ws)
-        out["plane_h"].append(hs)
-    out["ms_ssim"] = ms_ssim_from_means(out["cs"], out["ssim"][-1])
-    return out
-
-
-# ---- bias and noise over many realisations: ensemble statistics (musica_sim_ensemble_*; not in the reference) ----
-# A noise row scores ONE random draw, which cannot tell a systematic change of the output (a tone curve that moved with the gradation
-# histogram, lost detail) from amplified noise, nor say how far the score moves under another seed. Over K realisations a_k of the same
-# alteration the per-pixel sums S1 = sum a_k and S2 = sum a_k^2 give both: D = S1 - K b is K times the bias against the unaltered result
-# b, V = K S2 - S1^2 is K (K - 1) times the sample variance. All of it is integer arithmetic; these functions are the contract of
-# musica_sim_ensemble_result (include/musica.h).
-ENSEMBLE_KEYS = mp.ENSEMBLE_METRICS + mp.ENSEMBLE_INTEGERS   # a study row's ensemble dicts; ensemble_statistics adds "tile_tables"
-
-
-def ensemble_stream(ordinal, j):
-    """The Philox stream of realisation j < 1024 of the study row with that ordinal (1, 2, ..): 1024 ordinal + j. Ordinals start at 1,
-    so these streams never meet a row's own stream, its ordinal (a study has far fewer than 1024 rows)."""
-    ordinal, j = int(ordinal), int(j)
-    if ordinal < 1 or not 0 <= j < mp.SIM_ENSEMBLE_MAX:
-        raise ValueError("ensemble_stream: ordinal %d must be >= 1 and the realisation %d in 0 .. %d" % (ordinal, j, mp.SIM_ENSEMBLE_MAX - 1))
-    return mp.SIM_ENSEMBLE_MAX * ordinal + j
-
-
-def ensemble_summary(sq_bias_sum, var_sum, sq_err_sum, bias_sum, abs_bias_max, var_max, realisations, w, h):
-    """A query's ENSEMBLE_KEYS dict from its exact integers: the doubles one IEEE operation each in include/musica.h's order, every
-    integer converted to double first. The device and the host studies both call this, so they agree to the last bit."""
-    ints = [int(v) for v in (sq_bias_sum, var_sum, sq_err_sum, bias_sum, abs_bias_max, var_max)]
-    k, n = int(realisations), int(w) * int(h)
-    sq_bias, var, sq_err, bias = ints[:4]
-    if k * sq_err != sq_bias + var:
-        raise ValueError("ensemble_summary: K sq_err_sum != sq_bias_sum + var_sum (%d * %d, %d + %d)" % (k, sq_err, sq_bias, var))
-    t = mp.SIM_TILE
-    out = {"mean_shift": float(bias) / float(k * n),
-           "bias_rms": math.sqrt(float(sq_bias) / float(k * k * n)),
-           "noise_rms": 0.0 if k == 1 else math.sqrt(float(var) / float(k * (k - 1) * n)),
-           "mse": 1.0 - math.sqrt(float(sq_err) / float(k * n)) / 255.0,
-           "bias_fraction": 0.0 if sq_bias + var == 0 else float(sq_bias) / float(sq_bias + var)}
-    out.update(zip(mp.ENSEMBLE_INTEGERS, ints + [n, k, (int(w) + t - 1) // t, (int(h) + t - 1) // t]))
-    return out
-
-
-def ensemble_statistics(outs, b, region):
-    """musica_sim_ensemble_result's numbers of one query, restated: outs a (K, H, W) stack of uint8 outputs (the realisations), b the full
-    uint8 reference plane, region = (ax, ay, bx, by, w, h). Integer dtype throughout: S1, S2, D, V and the error term per pixel and the
-    tile sums in int64 (a tile's sum D^2 <= 64^2 * 261120^2 < 2^63), the totals as Python ints summed over the tiles. Returns the
-    ENSEMBLE_KEYS dict (ensemble_summary) plus "tile_tables": (tiles_y, tiles_x, 2) uint64, (sum D^2, sum V) per 64 x 64 tile. ValueError
-    where the C call refuses: no or more than SIM_ENSEMBLE_MAX realisations, w < 7 or h < 7, a region that leaves either plane,
-    65025 K^2 w h >= 2^64."""
-    outs, b = np.asarray(outs), np.asarray(b)
-    if outs.ndim != 3 or b.ndim != 2 or outs.dtype != np.uint8 or b.dtype != np.uint8:
-        raise ValueError("ensemble_statistics needs a (K, H, W) uint8 stack and a 2-D uint8 plane, got %r %s and %r %s" % (outs.shape, outs.dtype, b.shape, b.dtype))
-    k = outs.shape[0]
-    if not 1 <= k <= mp.SIM_ENSEMBLE_MAX:
-        raise ValueError("%d realisations out of range [1, %d]" % (k, mp.SIM_ENSEMBLE_MAX))
-    ax, ay, bx, by, w, h = (int(v) for v in region)
-    if w < 7 or h < 7:
-        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
-    if min(ax, ay, bx, by) < 0 or ax + w > outs.shape[2] or ay + h > outs.shape[1] or bx + w > b.shape[1] or by + h > b.shape[0]:
-        raise ValueError("region (%d, %d) / (%d, %d) + %d x %d leaves the planes" % (ax, ay, bx, by, w, h))
-    if 65025 * k * k * w * h >= 2 ** 64:
-        raise ValueError("65025 * %d^2 * %d * %d does not fit 64 bits" % (k, w, h))
-    a = outs[:, ay:ay + h, ax:ax + w].astype(np.int64)
-    cb = b[by:by + h, bx:bx + w].astype(np.int64)
-    s1, s2 = a.sum(axis=0), (a * a).sum(axis=0)
-    d = s1 - k * cb
-    v = k * s2 - s1 * s1
-    e = s2 - 2 * cb * s1 + k * cb * cb
-    t = mp.SIM_TILE
-
-    def tiles(x):
-        return np.add.reduceat(np.add.reduceat(x, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
-
-    tile_tables = np.stack([tiles(d * d), tiles(v)], axis=-1).astype(np.uint64)
-    out = ensemble_summary(sum(int(x) for x in tile_tables[..., 0].ravel()), sum(int(x) for x in tile_tables[..., 1].ravel()),
-                           sum(int(x) for x in tiles(e).ravel()), sum(int(x) for x in tiles(d).ravel()), int(np.abs(d).max()), int(v.max()), k, w, h)
-    out["tile_tables"] = tile_tables
-    return out
-
-
-def ensemble_maps(tile_tables, w, h, realisations):
-    """Two (tiles_y, tiles_x) uint8 maps of a w x h region's ensemble tile table, one pixel per tile: the tile's bias rms,
-    sqrt(sum D^2 / (K^2 pixels)), and its noise rms, sqrt(sum V / (K (K - 1) pixels)) (0 for K == 1), in gray levels, rounded."""
-    tt = np.asarray(tile_tables)
-    ny, nx, t, k = tt.shape[0], tt.shape[1], mp.SIM_TILE, int(realisations)
-    bias, noise = np.zeros((ny, nx), dtype=np.uint8), np.zeros((ny, nx), dtype=np.uint8)
-    for ty in range(ny):
-        for tx in range(nx):
-            px = (min(h, t * ty + t) - t * ty) * (min(w, t * tx + t) - t * tx)
-            bias[ty, tx] = min(255, int(round(math.sqrt(int(tt[ty, tx, 0]) / (k * k * px)))))
-            noise[ty, tx] = min(255, int(round(math.sqrt(int(tt[ty, tx, 1]) / (k * (k - 1) * px))))) if k > 1 else 0
-    return bias, noise
-
-
-# ---- the texture of the noise: spatial auto-covariance and power spectrum (musica_sim_ensemble_track / _covariance; not in the reference) ----
-# The per-pixel statistics say how strong the output noise is and nothing about its grain: MUSICA amplifies fine pyramid levels more than
-# coarse ones and its noise reduction works on 5 x 5 neighbourhoods, so the noise that leaves it is coloured. Over K realisations a_k,
-# with S1 = sum_k a_k, the lag products P(d) = sum_k sum_p a_k(p) a_k(p + d) and U(d) = sum_p S1(p) S1(p + d) over a region of n pixels
-# give C(d) = K P(d) - U(d) = K^2 n times the population covariance at lag d about the per-pixel ensemble mean, in exact integers; the
-# neighbour correlations, the correlation area and the noise power spectrum (Wiener-Khinchin) follow. These functions are the contract
-# of musica_sim_ensemble_covariance (include/musica.h).
-COV_KEYS = mp.COV_METRICS + mp.COV_INTEGERS   # ensemble_covariance adds "table" and "tile_tables"; a study row's dicts add "nps_radial" and "hf_fraction"
-
-
-def _covariance_geometry(shape, region, radius):
-    """Raises ValueError exactly where musica_sim_ensemble_track refuses a region on geometry; returns (ax, ay, w, h) and the radius as
-    ints. region: (ax, ay, w, h), or a query's (ax, ay, bx, by, w, h), whose bx, by only have to stay inside the plane."""
-    region = tuple(int(v) for v in region)
-    if len(region) == 6:
-        ax, ay, bx, by, w, h = region
-    else:
-        ax, ay, w, h = region
-        bx, by = ax, ay
-    radius = int(radius)
-    if not 1 <= radius <= mp.SIM_MAX_RADIUS:
-        raise ValueError("radius %d out of range [1, %d]" % (radius, mp.SIM_MAX_RADIUS))
-    if w < 7 or h < 7:
-        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
-    if min(ax, ay, bx, by) < 0 or max(ax, bx) + w > shape[1] or max(ay, by) + h > shape[0]:
-        raise ValueError("region (%d, %d) / (%d, %d) + %d x %d leaves the %d x %d plane" % (ax, ay, bx, by, w, h, shape[1], shape[0]))
-    if ax < radius or ax + w + radius > shape[1] or ay + h + radius > shape[0]:
-        raise ValueError("the window (%d, %d) + %d x %d grown by the radius %d (left, right, down) leaves the %d x %d plane" % (ax, ay, w, h, radius, shape[1], shape[0]))
-    if 65025 * mp.SIM_ENSEMBLE_MAX ** 2 * w * h >= 2 ** 63:
-        raise ValueError("65025 * %d^2 * %d * %d does not fit 63 bits" % (mp.SIM_ENSEMBLE_MAX, w, h))
-    return (ax, ay, w, h), radius
-
-
-def covariance_summary(table, realisations, pixels):
-    """The doubles of a covariance result from its exact (R + 1, 2 R + 1) table C(d) (row dy, column dx + R), one IEEE operation each in
-    include/musica.h's order, every integer converted to double first, with c00, pixels, realisations and radius. The device and the
-    host studies both call this, so they agree to the last bit."""
-    table = np.asarray(table)
-    if table.ndim != 2 or table.shape[0] < 2 or table.shape[1] != 2 * table.shape[0] - 1:
-        raise ValueError("expected an (R + 1, 2 R + 1) table, got %r" % (table.shape,))
-    r, k, n = table.shape[0] - 1, int(realisations), int(pixels)
-    c00 = int(table[0, r])
-    half = 0.0
-    for dy in range(r + 1):
-        for dx in range(-r if dy else 1, r + 1):
-            half += float(int(table[dy, dx + r]))
-    return {"noise_var": 0.0 if k == 1 else float(c00) / float(k * (k - 1) * n),
-            "rho_x": 0.0 if c00 == 0 else float(int(table[0, r + 1])) / float(c00),
-            "rho_y": 0.0 if c00 == 0 else float(int(table[1, r])) / float(c00),
-            "corr_area": 1.0 if c00 == 0 else (float(c00) + 2.0 * half) / float(c00),
-            "c00": c00, "pixels": n, "realisations": k, "radius": r}
-
-
-def ensemble_covariance(outs, region, radius):
-    """musica_sim_ensemble_covariance's numbers of one tracked region, restated: outs a (K, H, W) stack of uint8 outputs (the
-    realisations), region = (ax, ay, w, h) or a query's (ax, ay, bx, by, w, h). For dy = 0 .. R and dx = -R .. R, per region pixel in
-    int64, K sum_k a_k(p) a_k(p + d) - S1(p) S1(p + d), summed per 64 x 64 tile of the region (int64: a tile's |C| <= 4096 * 65025 K^2 <
-    2^58), the region's totals as Python ints over the tiles. Returns the COV_KEYS dict (covariance_summary) plus "table":
-    (R + 1, 2 R + 1) int64, row dy, column dx + R, and "tile_tables": (tiles_y, tiles_x, R + 1, 2 R + 1) int64. ValueError where the C
-    calls refuse: no or more than SIM_ENSEMBLE_MAX realisations, a radius outside 1 .. 16, w < 7 or h < 7, a region that leaves the
-    plane, a window that, grown by the radius to the left, to the right and downwards, leaves it, 65025 * 1024^2 w h >= 2^63."""
-    outs = np.asarray(outs)
-    if outs.ndim != 3 or outs.dtype != np.uint8:
-        raise ValueError("ensemble_covariance needs a (K, H, W) uint8 stack, got %r %s" % (outs.shape, outs.dtype))
-    k = outs.shape[0]
-    if not 1 <= k <= mp.SIM_ENSEMBLE_MAX:
-        raise ValueError("%d realisations out of range [1, %d]" % (k, mp.SIM_ENSEMBLE_MAX))
-    (ax, ay, w, h), r = _covariance_geometry(outs.shape[1:], region, radius)
-    t, s = mp.SIM_TILE, 2 * r + 1
-    ny, nx = (h + t - 1) // t, (w + t - 1) // t
-    a = outs.astype(np.int64)
-    s1 = a.sum(axis=0)
-    ca, c1 = a[:, ay:ay + h, ax:ax + w], s1[ay:ay + h, ax:ax + w]
-    tile_tables = np.empty((ny, nx, r + 1, s), dtype=np.int64)
-    for dy in range(r + 1):
-        for dx in range(-r, r + 1):
-            shifted = (slice(ay + dy, ay + dy + h), slice(ax + dx, ax + dx + w))
-            c = k * (ca * a[(slice(None),) + shifted]).sum(axis=0) - c1 * s1[shifted]
-            tile_tables[:, :, dy, dx + r] = np.add.reduceat(np.add.reduceat(c, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
-    table = np.array([[sum(int(x) for x in tile_tables[:, :, dy, j].ravel()) for j in range(s)] for dy in range(r + 1)], dtype=np.int64)
-    out = covariance_summary(table, k, w * h)
-    out.update(tiles_x=nx, tiles_y=ny, table=table, tile_tables=tile_tables)
-    return out
-
-
-def covariance_symmetric(table):
-    """The (S, S) float64 table over dy, dx = -R .. R (row dy + R, column dx + R) of a half-plane table: C(-d) = C(d), the row dy = 0
-    taken from its entries with dx >= 0."""
-    table = np.asarray(table)
-    r = table.shape[0] - 1
-    sym = np.empty((2 * r + 1,) * 2, dtype=np.float64)
-    sym[r + 1:] = table[1:]
-    sym[:r] = table[1:][::-1, ::-1]
-    sym[r, r:] = table[0, r:]
-    sym[r, :r] = table[0, r + 1:][::-1]
-    return sym
-
-
-def noise_power_spectrum(table, realisations, pixels):
-    """The noise power spectrum of a covariance table (Wiener-Khinchin), host only: N[v][u] = sum over d of C_sym(d)
-    cos(2 pi (u dx + v dy) / S) / (K (K - 1) n) for u, v = 0 .. S - 1, (S, S) float64, the zero frequency at [0][0]. The sum of
-    cosines is taken as cos cos - sin sin with the phases' integers reduced mod S first. All zero when K == 1."""
-    sym = covariance_symmetric(table)
-    s, k, n = sym.shape[0], int(realisations), int(pixels)
-    if k == 1:
-        return np.zeros((s, s), dtype=np.float64)
-    d = np.arange(s) - s // 2
-    phase = 2.0 * np.pi * ((np.arange(s)[:, None] * d[None, :]) % s) / s     # [frequency][lag]
-    co, si = np.cos(phase), np.sin(phase)
-    return (co @ sym @ co.T - si @ sym @ si.T) / float(k * (k - 1) * n)
-
-
-def _nps_radius(s):
-    d = np.arange(s) - s // 2
-    return np.hypot(d[:, None], d[None, :])
-
-
-def nps_radial(nps):
-    """The mean of the centred spectrum (np.fft.fftshift) over the frequencies of rounded integer radius 0 .. R: a list of R + 1 floats."""
-    nps = np.asarray(nps, dtype=np.float64)
-    rad = np.rint(_nps_radius(nps.shape[0])).astype(np.int64)
-    c = np.fft.fftshift(nps)
-    return [float(c[rad == i].mean()) for i in range(nps.shape[0] // 2 + 1)]
-
-
-def nps_hf_fraction(nps):
-    """The share of the spectrum's sum at radius > R / 2 of the centred spectrum (0 for a spectrum that sums to 0). White noise gives
-    the share of such frequencies among the S^2: nps_hf_fraction(np.ones((S, S)))."""
-    nps = np.asarray(nps, dtype=np.float64)
-    total = float(nps.sum())
-    if total == 0.0:
-        return 0.0
-    return float(np.fft.fftshift(nps)[_nps_radius(nps.shape[0]) > (nps.shape[0] // 2) / 2.0].sum()) / total
-
-
-hf_fraction = nps_hf_fraction
-
-
-def covariance_row(table, realisations, w, h):
-    """A study row's covariance dict of one region from its exact table: COV_KEYS, then "nps_radial" and "hf_fraction"."""
-    t = mp.SIM_TILE
-    d = covariance_summary(table, realisations, int(w) * int(h))
-    d.update(tiles_x=(int(w) + t - 1) // t, tiles_y=(int(h) + t - 1) // t)
-    out = {k: d[k] for k in COV_KEYS}
-    nps = noise_power_spectrum(table, realisations, int(w) * int(h))
-    out["nps_radial"], out["hf_fraction"] = nps_radial(nps), nps_hf_fraction(nps)
-    return out
-
-
-def nps_map(table, realisations, pixels):
-    """The centred spectrum as an (S, S) uint8 image: log(1 + max(N, 0)) scaled so that its largest value is 255, rounded."""
-    v = np.log1p(np.maximum(np.fft.fftshift(noise_power_spectrum(table, realisations, pixels)), 0.0))
-    top = float(v.max())
-    return np.zeros(v.shape, dtype=np.uint8) if top == 0.0 else np.rint(255.0 * v / top).astype(np.uint8)
 
 
 # ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
@@ -945,6 +369,259 @@ TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "referenc
              "registered_reference": "registered_reference_tone"}
 
 
+VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
+
+
+def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
+                  scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs):
+    """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
+    its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
+    order) and `device_alterations`."""
+    if vendor is not None:
+        vendor = np.asarray(vendor)
+        want = (n - 2 * PROCESSING_MARGIN,) * 2
+        if vendor.shape != want or vendor.dtype not in (np.uint8, np.uint16):
+            raise ValueError("vendor image must be a %d x %d uint8 or uint16 array, got %r %s" % (want + (vendor.shape, vendor.dtype)))
+    displacement = int(displacement)
+    if displacement and not 1 <= displacement <= mp.SIM_MAX_RADIUS:
+        raise ValueError("displacement radius %d is not in 1 .. %d" % (displacement, mp.SIM_MAX_RADIUS))
+    scales = int(scales)
+    if scales and not 1 <= scales <= mp.SIM_MAX_SCALES:
+        raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
+    ensemble = int(ensemble)
+    device_alterations = getattr(runner, "device_alterations", False)
+    if ensemble and not 1 <= ensemble <= mp.SIM_ENSEMBLE_MAX:
+        raise ValueError("ensemble %d is not in 1 .. %d" % (ensemble, mp.SIM_ENSEMBLE_MAX))
+    if ensemble and not device_alterations:
+        raise ValueError("an ensemble repeats the device's noise alterations: it needs a runner with device_alterations")
+    covariance = int(covariance)
+    if covariance and not 1 <= covariance <= mp.SIM_MAX_RADIUS:
+        raise ValueError("covariance radius %d is not in 1 .. %d" % (covariance, mp.SIM_MAX_RADIUS))
+    if covariance and not ensemble:
+        raise ValueError("covariance is taken over the realisations of an ensemble: give ensemble > 0")
+    symmetries = [int(e) for e in (symmetries or ())]
+    for e in symmetries:
+        if not 0 <= e <= 7:
+            raise ValueError("symmetry element %d is not in 0 .. 7" % e)
+    blurs = [int(r) for r in (blurs or ())]
+    for r in blurs:
+        if not 1 <= r <= mp.BLUR_MAX_RADIUS:
+            raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
+    compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
+    keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
+           (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
+           (("ensemble",) if ensemble else ())
+    return types.SimpleNamespace(
+        shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
+        rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
+        factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
+        displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
+        covariance_tiles=covariance_tiles, blurs=blurs, keys=keys, device_alterations=device_alterations)
+
+
+# One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
+# region() the region of the registered comparison (None, or no region at all as for the noise rows: no registration); move = (the
+# context's method, the host's function, their parameter), which both move a reference plane as the alteration moves the input: the
+# registered comparison is then against the moved plane; noise = (the row's ordinal, alter(context, stream, image_index)) for the rows
+# that draw, what their ensembles repeat.
+Alteration = collections.namedtuple("Alteration", "name host dev region move noise", defaults=(None, None, None))
+
+
+def study_alterations(raw, rng, p, seed, shape, opt):
+    """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
+    order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
+    as their stream; the d4 and blur rows draw nothing and take no ordinal."""
+    ordinal = itertools.count(1)
+    for s in opt.shutters:
+        k = next(ordinal)
+        yield Alteration("c_sh_%d" % s, lambda: apply_collimator(raw, s, s, rng), lambda k=k: p.alter_collimator(s, s, seed, k),
+                         lambda: roi_collimator(shape, s), noise=(k, lambda q, stream, i: q.alter_collimator(s, s, seed, stream, i)))
+    for name, tx, ty, roi in (("t_x_%d", 1, 0, roi_translation_x), ("t_y_%d", 0, 1, roi_translation_y)):
+        for t in opt.translations:
+            next(ordinal)   # every row before the d4 rows takes one, drawing or not
+            yield Alteration(name % t, lambda: clamp_translation(raw, tx * t, ty * t), lambda: p.alter_translate(tx * t, ty * t),
+                             lambda: roi(shape, t))
+    for d in opt.rotations:
+        next(ordinal)
+        yield Alteration("r_%d" % d, lambda: clamp_rotate(raw, d), lambda: p.alter_rotate(d), lambda: roi_rotation(shape, d),
+                         ("sim_rotate_reference", rotated_reference, d))
+    for sg in opt.sigmas:
+        k = next(ordinal)
+        yield Alteration("gn_%s" % sg, lambda: add_gaussian_noise(raw, 0.0, sg, rng), lambda k=k: p.alter_gaussian(0.0, sg, seed, k),
+                         noise=(k, lambda q, stream, i: q.alter_gaussian(0.0, sg, seed, stream, i)))
+    for f in opt.factors:
+        k = next(ordinal)
+        yield Alteration("pn_%s" % f, lambda: apply_quantum_noise(raw, f, rng), lambda k=k: p.alter_poisson(f, seed, k),
+                         noise=(k, lambda q, stream, i: q.alter_poisson(f, seed, stream, i)))
+    for e in opt.symmetries:
+        yield Alteration("d4_%d" % e, lambda: apply_symmetry(raw, e), lambda: p.alter_symmetry(e), lambda: roi_symmetry(shape),
+                         ("sim_transform_reference", apply_symmetry, e))
+    for r in opt.blurs:
+        yield Alteration("blur_%d" % r, lambda: binomial_blur(raw, r), lambda: p.alter_blur(r), lambda: roi_blur(shape, r),
+                         ("sim_blur_reference", binomial_blur, r))
+
+
+class Scorer:
+    """How run_study scores a row, on the host or on the device. produce(alteration) makes the altered output the one that is scored
+    (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
+    SLOT_ROTATED and SLOT_VENDOR_ROTATED; similarities, tone, scales and shifts take the row's comparisons, (reference key, region)
+    pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset)."""
+
+    def __init__(self, runner, opt, unalt):
+        self.runner, self.proc, self.opt, self.unalt = runner, runner.proc, opt, unalt
+
+    def shift_summary(self, table, region, tiles, tiles_off, tile_tables):
+        out = displacement_summary(table, region[4] * region[5], tiles, tiles_off)
+        if self.opt.displacement_tiles:
+            out["tile_tables"], out["size"] = tile_tables, (region[4], region[5])
+        return out
+
+
+class DeviceScorer(Scorer):
+    """The output is image 0 of the runner's context, a reference key the slot itself: every method is one or a few sim_* calls."""
+
+    def __init__(self, runner, opt, unalt):
+        super().__init__(runner, opt, unalt)
+        self.proc.sim_capture(SLOT_UNALTERED)
+        if opt.vendor is not None:
+            self.proc.sim_set_vendor_reference(SLOT_VENDOR, opt.vendor)
+
+    def produce(self, alteration):
+        if self.opt.device_alterations:
+            alteration.dev()
+            self.runner.run_resident()
+        else:
+            self.runner.run_device(alteration.host())
+
+    def move(self, method, function, parameter):
+        if self.opt.device_alterations:
+            getattr(self.proc, method)(SLOT_ROTATED, SLOT_UNALTERED, parameter)
+        else:
+            self.proc.sim_set_reference(SLOT_ROTATED, function(self.unalt, parameter))
+        if self.opt.vendor is not None:
+            getattr(self.proc, method)(SLOT_VENDOR_ROTATED, SLOT_VENDOR, parameter)
+
+    def similarities(self, comparisons):
+        return [{k: r[k] for k in mp.SIM_METRICS} for r in self.proc.sim_compare([(0, slot) + region for slot, region in comparisons])]
+
+    def tone(self, comparisons):
+        """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
+        has at most four), then one musica_sim_compare call over the same regions for tone_ssim."""
+        res = self.proc.sim_joint([(0, slot) + region for slot, region in comparisons])
+        for i, ((slot, _), r) in enumerate(zip(comparisons, res)):
+            self.proc.sim_remap_reference(SLOT_TONE + i, slot, r["tone_lut"])
+        scored = self.proc.sim_compare([(0, SLOT_TONE + i) + region for i, (_, region) in enumerate(comparisons)])
+        for r, c in zip(res, scored):
+            r["tone_ssim"] = c["ssim"]
+        return [{k: r[k] for k in mp.JOINT_METRICS} for r in res]
+
+    def scales(self, comparisons):
+        """One musica_sim_multiscale call per distinct scale count, ascending; the results in the comparisons' order."""
+        counts = [min(self.opt.scales, max_scales(region[4], region[5])) for _, region in comparisons]
+        out = [None] * len(comparisons)
+        for n in sorted(set(counts)):
+            idx = [i for i, c in enumerate(counts) if c == n]
+            for i, r in zip(idx, self.proc.sim_multiscale([(0, comparisons[i][0]) + comparisons[i][1] for i in idx], n)):
+                out[i] = {k: r[k] for k in SCALES_KEYS}
+        return out
+
+    def shifts(self, comparisons):
+        """One musica_sim_displace call, none without a comparison."""
+        res = self.proc.sim_displace([(0, slot) + region for slot, region in comparisons], self.opt.displacement, tables=True,
+                                     tiles=self.opt.displacement_tiles) if comparisons else []
+        return [self.shift_summary(r["table"], region, r["tiles_x"] * r["tiles_y"], r["tiles_off"], r.get("tile_tables"))
+                for (_, region), r in zip(comparisons, res)]
+
+
+class HostScorer(Scorer):
+    """The output is an array and a reference key looks up a full plane (the unaltered result, the vendor image as vendor_to_u8 converts
+    it, and what move() made of them): every comparison is the restatement on the output cropped by the region's a side and the plane
+    cropped by its b side."""
+
+    def __init__(self, runner, opt, unalt):
+        super().__init__(runner, opt, unalt)
+        self.out = unalt
+        self.planes = {SLOT_UNALTERED: unalt}
+        if opt.vendor is not None:
+            self.planes[SLOT_VENDOR] = vendor_to_u8(opt.vendor)
+
+    def produce(self, alteration):
+        self.out = self.runner.run(alteration.host())
+
+    def move(self, method, function, parameter):
+        for slot, moved in ((SLOT_UNALTERED, SLOT_ROTATED), (SLOT_VENDOR, SLOT_VENDOR_ROTATED)):
+            if slot in self.planes:
+                self.planes[moved] = function(self.planes[slot], parameter)
+
+    def sides(self, slot, region):
+        ax, ay, bx, by, w, h = region
+        return self.out[ay:ay + h, ax:ax + w], self.planes[slot][by:by + h, bx:bx + w]
+
+    def similarities(self, comparisons):
+        return [similarities(*self.sides(*c)) for c in comparisons]
+
+    def tone(self, comparisons):
+        return [tone_similarities(*self.sides(*c)) for c in comparisons]
+
+    def scales(self, comparisons):
+        res = [multiscale_similarities(*self.sides(slot, region), min(self.opt.scales, max_scales(region[4], region[5]))) for slot, region in comparisons]
+        return [{k: r[k] for k in SCALES_KEYS} for r in res]
+
+    def shifts(self, comparisons):
+        tables = [(region, displacement_tile_tables(self.out, self.planes[slot], region, self.opt.displacement)) for slot, region in comparisons]
+        return [self.shift_summary(tt.astype(np.int64).sum(axis=(0, 1)), region, tt.shape[0] * tt.shape[1], displacement_tiles_off(tt), tt)
+                for region, tt in tables]
+
+
+def ensemble_of(eproc, noise, registered, full, opt):
+    """The "ensemble" value of a completed row, on the ensemble context: None unless it is a noise row (noise: its Alteration's).
+    registered: the region of its registered comparison (None: the row has none)."""
+    if noise is None:
+        return None
+    ordinal, alter = noise
+    ensemble, covariance = opt.ensemble, opt.covariance
+    regions = [full] + ([registered] if registered is not None else [])
+    per = {k: [] for k in mp.SIM_METRICS}
+    eproc.sim_ensemble_reset()
+    if covariance:
+        tracked = [_inset(full, covariance), _inset(registered, covariance) if registered is not None else None]
+        if tracked[0] is None:
+            raise ValueError("covariance radius %d leaves no 7 x 7 region of the %d x %d output" % (covariance, full[4], full[5]))
+        eproc.sim_ensemble_track([(0, SLOT_UNALTERED) + r for r in tracked if r is not None], covariance)
+    for j0 in range(0, ensemble, eproc.batch):
+        count = min(eproc.batch, ensemble - j0)
+        for i in range(count):
+            alter(eproc, ensemble_stream(ordinal, j0 + i), i)
+        if not eproc.execute_device():
+            raise RuntimeError("musica_execute_device failed: " + mp.last_error())
+        eproc.sim_ensemble_add(0, count)
+        for r in eproc.sim_compare([(i, SLOT_UNALTERED) + full for i in range(count)]):
+            for k in mp.SIM_METRICS:
+                per[k].append(r[k])
+    res = eproc.sim_ensemble_result([(0, SLOT_UNALTERED) + r for r in regions], tiles=opt.ensemble_tiles)
+    dicts = [ensemble_summary(*[r[k] for k in ("sq_bias_sum", "var_sum", "sq_err_sum", "bias_sum", "abs_bias_max", "var_max", "realisations")],
+                              g[4], g[5]) for r, g in zip(res, regions)]
+    if opt.ensemble_tiles:
+        dicts[0]["tile_tables"], dicts[0]["size"] = res[0]["tile_tables"], (full[4], full[5])
+    out = {"direct": dicts[0], "registered": dicts[1] if registered is not None else None, "realisations": ensemble,
+           "per_realisation": {"mean": {k: float(np.mean(v)) for k, v in per.items()},
+                               "std": {k: float(np.std(v, ddof=1)) if ensemble > 1 else 0.0 for k, v in per.items()}}}
+    if covariance:
+        cov = iter(eproc.sim_ensemble_covariance(tables=True, tiles=opt.covariance_tiles))
+        groups = []
+        for r in tracked:
+            if r is None:
+                groups.append(None)
+                continue
+            c = next(cov)
+            d = covariance_row(c["table"], c["realisations"], r[4], r[5])
+            if opt.covariance_tiles:
+                d["table"], d["tile_tables"] = c["table"], c["tile_tables"]
+            groups.append(d)
+        out["covariance"] = {"direct": groups[0], "registered": groups[1]}
+    return out
+
+
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None):
@@ -1020,580 +697,59 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     slot 1 and the blurred vendor image into slot 3 (musica_sim_blur_reference). Like the d4 rows they draw nothing from `rng` and take
     no ordinal; vendor, tone, scales and displacement apply to them as to a d4 row."""
     rng = rng or np.random.default_rng(0)
-    n = raw.shape[0]
-    if vendor is not None:
-        vendor = np.asarray(vendor)
-        want = (n - 2 * PROCESSING_MARGIN,) * 2
-        if vendor.shape != want or vendor.dtype not in (np.uint8, np.uint16):
-            raise ValueError("vendor image must be a %d x %d uint8 or uint16 array, got %r %s" % (want + (vendor.shape, vendor.dtype)))
-    keys = ("alteration", "direct", "registered", "mean_cnr") + (() if vendor is None else ("reference", "registered_reference"))
-    if tone:
-        keys += tuple(TONE_KEYS[k] for k in keys if k in TONE_KEYS)
-    displacement = int(displacement)
-    if displacement and not 1 <= displacement <= mp.SIM_MAX_RADIUS:
-        raise ValueError("displacement radius %d is not in 1 .. %d" % (displacement, mp.SIM_MAX_RADIUS))
-    if displacement:
-        keys += ("direct_shift", "registered_shift")
-    scales = int(scales)
-    if scales and not 1 <= scales <= mp.SIM_MAX_SCALES:
-        raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
-    if scales:
-        keys += tuple(SCALE_ROW_KEYS[k] for k in keys if k in SCALE_ROW_KEYS)
-    ensemble = int(ensemble)
-    if ensemble and not 1 <= ensemble <= mp.SIM_ENSEMBLE_MAX:
-        raise ValueError("ensemble %d is not in 1 .. %d" % (ensemble, mp.SIM_ENSEMBLE_MAX))
-    if ensemble and not getattr(runner, "device_alterations", False):
-        raise ValueError("an ensemble repeats the device's noise alterations: it needs a runner with device_alterations")
-    if ensemble:
-        keys += ("ensemble",)
-    covariance = int(covariance)
-    if covariance and not 1 <= covariance <= mp.SIM_MAX_RADIUS:
-        raise ValueError("covariance radius %d is not in 1 .. %d" % (covariance, mp.SIM_MAX_RADIUS))
-    if covariance and not ensemble:
-        raise ValueError("covariance is taken over the realisations of an ensemble: give ensemble > 0")
-    shutters = scaled(SHUTTERS, n) if shutters is None else shutters
-    translations = scaled(TRANSLATIONS, n) if translations is None else translations
-    rotations = ROTATIONS if rotations is None else rotations
-    sigmas = GAUSS_SIGMAS if sigmas is None else sigmas
-    factors = POISSON_FACTORS if factors is None else factors
-    symmetries = [int(e) for e in (symmetries or ())]
-    for e in symmetries:
-        if not 0 <= e <= 7:
-            raise ValueError("symmetry element %d is not in 0 .. 7" % e)
-    blurs = [int(r) for r in (blurs or ())]
-    for r in blurs:
-        if not 1 <= r <= mp.BLUR_MAX_RADIUS:
-            raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
-    device = getattr(runner, "device_metrics", False)
-    alter_on_device = getattr(runner, "device_alterations", False)
-    ref8 = vendor_to_u8(vendor) if vendor is not None and not device else None   # the host metrics' vendor image
+    opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
+                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
+    scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
+    metrics = [("", scorer.similarities)] + ([("_tone", scorer.tone)] if opt.tone else []) + ([("_scales", scorer.scales)] if opt.scales else [])
+    rows = []
 
-    def on_device(queries):
-        return [{k: r[k] for k in mp.SIM_METRICS} for r in runner.proc.sim_compare(queries)]
+    def row(alteration=None, eproc=None):
+        """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
+        the study, in the order compare, tone, scales, displacement; then, with the ensemble's context, the row's ensemble."""
+        registered = None   # (reference key, region) of the registered comparison
+        if alteration is not None:
+            scorer.produce(alteration)
+            if alteration.move:
+                scorer.move(*alteration.move)
+            region = alteration.region() if alteration.region else None
+            if region is not None and min(region[4], region[5]) >= 8:
+                registered = (SLOT_ROTATED if alteration.move else SLOT_UNALTERED, region)
+        own = [("direct", (SLOT_UNALTERED, full))] + ([("registered", registered)] if registered else [])
+        compared = []   # (row key, comparison) in the queries' order: each of the row's own, then the same against the vendor image
+        for key, (slot, region) in own:
+            compared.append((key, (slot, region)))
+            if opt.vendor is not None:
+                compared.append((VENDOR_KEY[key], (VENDOR_SLOT[slot], region)))
+        out = dict.fromkeys(k for k in opt.keys if alteration is not None or not k.startswith("registered_reference"))
+        out["alteration"] = alteration.name if alteration is not None else "unaltered"
+        for suffix, score in metrics:
+            out.update(zip([key + suffix for key, _ in compared], score([c for _, c in compared])))
+        if opt.displacement:   # a *_shift stays None without its comparison, or where the inset leaves a side under 7
+            shifted = [(key + "_shift", (slot, _inset(region, opt.displacement))) for key, (slot, region) in own]
+            shifted = [(key, c) for key, c in shifted if c[1] is not None]
+            out.update(zip([key for key, _ in shifted], scorer.shifts([c for _, c in shifted])))
+        out["mean_cnr"] = runner.mean_cnr() if runner.proc else None
+        if eproc is not None:
+            out["ensemble"] = ensemble_of(eproc, alteration.noise, registered[1] if registered else None, full, opt)
+        rows.append(out)
 
-    def tone_on_device(queries):
-        """The JOINT_METRICS of a row's queries (at most four): one musica_sim_joint call, every query's slot remapped with its tone_lut
-        into a slot of its own from SLOT_TONE on, then one musica_sim_compare call over the same regions for tone_ssim."""
-        res = runner.proc.sim_joint(queries)
-        for i, (q, r) in enumerate(zip(queries, res)):
-            runner.proc.sim_remap_reference(SLOT_TONE + i, q[1], r["tone_lut"])
-        scored = runner.proc.sim_compare([(q[0], SLOT_TONE + i) + tuple(q[2:]) for i, q in enumerate(queries)])
-        for r, c in zip(res, scored):
-            r["tone_ssim"] = c["ssim"]
-        return [{k: r[k] for k in mp.JOINT_METRICS} for r in res]
-
-    def scales_on_device(queries):
-        """The SCALES_KEYS of a row's queries: one musica_sim_multiscale call per distinct scale count, results in the queries' order."""
-        counts = [min(scales, max_scales(q[6], q[7])) for q in queries]
-        out = [None] * len(queries)
-        for n in sorted(set(counts)):
-            idx = [i for i, c in enumerate(counts) if c == n]
-            for i, r in zip(idx, runner.proc.sim_multiscale([queries[i] for i in idx], n)):
-                out[i] = {k: r[k] for k in SCALES_KEYS}
-        return out
-
-    def scales_on_host(a, b):
-        r = multiscale_similarities(a, b, min(scales, max_scales(a.shape[1], a.shape[0])))
-        return {k: r[k] for k in SCALES_KEYS}
-
-    def shift_summary(table, region, tiles, tiles_off, tile_tables):
-        out = displacement_summary(table, region[4] * region[5], tiles, tiles_off)
-        if displacement_tiles:
-            out["tile_tables"], out["size"] = tile_tables, (region[4], region[5])
-        return out
-
-    def shifts_on_device(comparisons):
-        """comparisons: (slot, region) pairs, region already inset (None: no comparison). One musica_sim_displace call for those present."""
-        present = [(slot, region) for slot, region in comparisons if region is not None]
-        res = iter(runner.proc.sim_displace([(0, slot) + region for slot, region in present], displacement, tables=True,
-                                            tiles=displacement_tiles) if present else [])
-        out = []
-        for slot, region in comparisons:
-            r = next(res) if region is not None else None
-            out.append(None if r is None else shift_summary(r["table"], region, r["tiles_x"] * r["tiles_y"], r["tiles_off"], r.get("tile_tables")))
-        return out
-
-    def shift_on_host(a, b, region):
-        """The same from the restatement: a the output, b the full plane it is compared with, region already inset (None: no comparison)."""
-        if region is None:
-            return None
-        tt = displacement_tile_tables(a, b, region, displacement)
-        return shift_summary(tt.astype(np.int64).sum(axis=(0, 1)), region, tt.shape[0] * tt.shape[1], displacement_tiles_off(tt), tt)
-
-    first = {"alteration": "unaltered", "registered": None, "registered_tone": None, "registered_shift": None, "registered_scales": None,
-             "ensemble": None}
-    if device:
-        runner.proc.sim_capture(SLOT_UNALTERED)
-        queries = [(0, SLOT_UNALTERED) + full]
-        if vendor is not None:
-            runner.proc.sim_set_vendor_reference(SLOT_VENDOR, vendor)
-            queries.append((0, SLOT_VENDOR) + full)
-        res = on_device(queries)
-        first["direct"] = res[0]
-        if vendor is not None:
-            first["reference"] = res[1]
-        if tone:
-            res = tone_on_device(queries)
-            first["direct_tone"] = res[0]
-            if vendor is not None:
-                first["reference_tone"] = res[1]
-        if displacement:
-            first["direct_shift"] = shifts_on_device([(SLOT_UNALTERED, _inset(full, displacement))])[0]
-        if scales:
-            res = scales_on_device(queries)
-            first["direct_scales"] = res[0]
-            if vendor is not None:
-                first["reference_scales"] = res[1]
-    else:
-        if displacement:
-            first["direct_shift"] = shift_on_host(unalt, unalt, _inset(full, displacement))
-        first["direct"] = similarities(unalt, unalt)
-        if vendor is not None:
-            first["reference"] = similarities(unalt, ref8)
-        if tone:
-            first["direct_tone"] = tone_similarities(unalt, unalt)
-            if vendor is not None:
-                first["reference_tone"] = tone_similarities(unalt, ref8)
-        if scales:
-            first["direct_scales"] = scales_on_host(unalt, unalt)
-            if vendor is not None:
-                first["reference_scales"] = scales_on_host(unalt, ref8)
-    first["mean_cnr"] = runner.mean_cnr() if runner.proc else None
-    rows = [{k: first[k] for k in keys if k in first}]
-
-    if alter_on_device:
+    row()
+    seed = eproc = None
+    if opt.device_alterations:
         runner.proc.alter_set_source(raw)
         seed = int(rng.integers(0, 2 ** 63))
-    noisy = {}   # row name -> (ordinal, alter(proc, stream, image_index)): the noise rows, for their ensembles
-    if ensemble:
-        eproc = runner.ensemble_context(ensemble)
+    if opt.ensemble:
+        eproc = runner.ensemble_context(opt.ensemble)
         eproc.alter_set_source(raw)
         for i in range(eproc.batch):     # every image of the batch holds a valid input, whatever the last chunk leaves unused
             eproc.alter_none(i)
         eproc.sim_set_reference(SLOT_UNALTERED, runner.proc.sim_get_reference(SLOT_UNALTERED))
-
-    def ensemble_of(name, registered):
-        """The "ensemble" value of a completed row: None unless it is a noise row. registered: the region of its registered comparison
-        (None: the row has none)."""
-        if name not in noisy:
-            return None
-        ordinal, alter = noisy[name]
-        regions = [full] + ([registered] if registered is not None else [])
-        per = {k: [] for k in mp.SIM_METRICS}
-        eproc.sim_ensemble_reset()
-        if covariance:
-            tracked = [_inset(full, covariance), _inset(registered, covariance) if registered is not None else None]
-            if tracked[0] is None:
-                raise ValueError("covariance radius %d leaves no 7 x 7 region of the %d x %d output" % (covariance, full[4], full[5]))
-            eproc.sim_ensemble_track([(0, SLOT_UNALTERED) + r for r in tracked if r is not None], covariance)
-        for j0 in range(0, ensemble, eproc.batch):
-            count = min(eproc.batch, ensemble - j0)
-            for i in range(count):
-                alter(eproc, ensemble_stream(ordinal, j0 + i), i)
-            if not eproc.execute_device():
-                raise RuntimeError("musica_execute_device failed: " + mp.last_error())
-            eproc.sim_ensemble_add(0, count)
-            for r in eproc.sim_compare([(i, SLOT_UNALTERED) + full for i in range(count)]):
-                for k in mp.SIM_METRICS:
-                    per[k].append(r[k])
-        res = eproc.sim_ensemble_result([(0, SLOT_UNALTERED) + r for r in regions], tiles=ensemble_tiles)
-        dicts = [ensemble_summary(*[r[k] for k in ("sq_bias_sum", "var_sum", "sq_err_sum", "bias_sum", "abs_bias_max", "var_max", "realisations")],
-                                  g[4], g[5]) for r, g in zip(res, regions)]
-        if ensemble_tiles:
-            dicts[0]["tile_tables"], dicts[0]["size"] = res[0]["tile_tables"], (full[4], full[5])
-        out = {"direct": dicts[0], "registered": dicts[1] if registered is not None else None, "realisations": ensemble,
-               "per_realisation": {"mean": {k: float(np.mean(v)) for k, v in per.items()},
-                                   "std": {k: float(np.std(v, ddof=1)) if ensemble > 1 else 0.0 for k, v in per.items()}}}
-        if covariance:
-            cov = iter(eproc.sim_ensemble_covariance(tables=True, tiles=covariance_tiles))
-            groups = []
-            for r in tracked:
-                if r is None:
-                    groups.append(None)
-                    continue
-                c = next(cov)
-                d = covariance_row(c["table"], c["realisations"], r[4], r[5])
-                if covariance_tiles:
-                    d["table"], d["tile_tables"] = c["table"], c["tile_tables"]
-                groups.append(d)
-            out["covariance"] = {"direct": groups[0], "registered": groups[1]}
-        return out
-
-    def add(name, host, dev, reg=None, region=None, slot=None, plane=None):
-        """One row of study() below, scored the way the runner's mode asks for."""
-        row = {"alteration": name, "registered": None, "registered_reference": None, "registered_tone": None, "registered_reference_tone": None,
-               "registered_shift": None, "registered_scales": None, "registered_reference_scales": None}
-        if alter_on_device:
-            dev()
-            runner.run_resident()
-        elif device:
-            runner.run_device(host())
-        if device:
-            queries = [(0, SLOT_UNALTERED) + full]
-            if vendor is not None:
-                queries.append((0, SLOT_VENDOR) + full)
-            registered = None   # (slot, region) of the registered comparison
-            if region is not None:
-                sl, r = slot(), region()
-                if r is not None and min(r[4], r[5]) >= 8:
-                    registered = (sl, r)
-                    queries.append((0, sl) + r)
-                    if vendor is not None:
-                        queries.append((0, VENDOR_SLOT[sl]) + r)
-            for suffix, score in (("", on_device),) + ((("_tone", tone_on_device),) if tone else ()) + ((("_scales", scales_on_device),) if scales else ()):
-                res = score(queries)
-                row["direct" + suffix] = res.pop(0)
-                if vendor is not None:
-                    row["reference" + suffix] = res.pop(0)
-                if res:
-                    row["registered" + suffix] = res.pop(0)
-                    if vendor is not None:
-                        row["registered_reference" + suffix] = res.pop(0)
-            if displacement:
-                row["direct_shift"], row["registered_shift"] = shifts_on_device(
-                    [(SLOT_UNALTERED, _inset(full, displacement)),
-                     (registered[0], _inset(registered[1], displacement)) if registered else (None, None)])
-        else:
-            alt = runner.run(host())
-            crop = reg(alt, unalt) if reg is not None else None
-            if crop is not None and not (crop[0].size and crop[0].shape == crop[1].shape and min(crop[0].shape) >= 8):
-                crop = None
-            vcrop = reg(alt, ref8) if crop is not None and vendor is not None else None   # the same rectangles: ref8 has unalt's shape
-            for suffix, score in (("", similarities),) + ((("_tone", tone_similarities),) if tone else ()) + ((("_scales", scales_on_host),) if scales else ()):
-                row["direct" + suffix] = score(alt, unalt)
-                if vendor is not None:
-                    row["reference" + suffix] = score(alt, ref8)
-                if crop is not None:
-                    row["registered" + suffix] = score(*crop)
-                    if vendor is not None:
-                        row["registered_reference" + suffix] = score(*vcrop)
-            if displacement:
-                row["direct_shift"] = shift_on_host(alt, unalt, _inset(full, displacement))
-                if crop is not None:
-                    row["registered_shift"] = shift_on_host(alt, plane(), _inset(region(), displacement))
-        row["mean_cnr"] = runner.mean_cnr() if runner.proc else None
-        if ensemble:   # device path (an ensemble needs device alterations): `registered` is the row's own (slot, region)
-            row["ensemble"] = ensemble_of(name, registered[1] if registered else None)
-        rows.append({k: row[k] for k in keys})
-
-    def moved_slot(d, move_reference, moved_unalt):
-        """The unaltered result (and the vendor image) moved as the row moves its input, into SLOT_ROTATED (SLOT_VENDOR_ROTATED)."""
-        if alter_on_device:
-            move_reference(SLOT_ROTATED, SLOT_UNALTERED, d)
-        else:
-            runner.proc.sim_set_reference(SLOT_ROTATED, moved_unalt(unalt, d))
-        if vendor is not None:
-            move_reference(SLOT_VENDOR_ROTATED, SLOT_VENDOR, d)
-        return SLOT_ROTATED
-
-    def study():
-        """Every alteration of the study once, in the rows' order, as add()'s arguments: name; host() the altered raw image; dev() the
-        call that writes it into the resident input buffer; reg(alt, unalt) the host's registration crop; region() the region of the
-        same comparison (None: no registration); slot() the reference slot its b side lies in on the device, filled by that call where
-        it is not the unaltered result's; plane() the full host plane it lies in. The noise rows have only the first three. add() makes a
-        row's calls before the next row is built: the rows' order is the order of the `rng` draws. The device's noise draws take the
-        row's ordinal in the study as their stream; the d4 and blur rows draw nothing and take no ordinal."""
-        p, ordinal = runner.proc, itertools.count(1)
-        for s in shutters:
-            k = next(ordinal)
-            noisy["c_sh_%d" % s] = (k, lambda q, stream, i: q.alter_collimator(s, s, seed, stream, i))
-            yield ("c_sh_%d" % s, lambda: apply_collimator(raw, s, s, rng), lambda k=k: p.alter_collimator(s, s, seed, k),
-                   lambda a, u: register_collimator(a, u, s), lambda: roi_collimator(shape, s), lambda: SLOT_UNALTERED, lambda: unalt)
-        for name, tx, ty, register, roi in (("t_x_%d", 1, 0, register_translation_x, roi_translation_x), ("t_y_%d", 0, 1, register_translation_y, roi_translation_y)):
-            for t in translations:
-                next(ordinal)   # every row before the d4 rows takes one, drawing or not
-                yield (name % t, lambda: clamp_translation(raw, tx * t, ty * t), lambda: p.alter_translate(tx * t, ty * t),
-                       lambda a, u: register(a, u, t), lambda: roi(shape, t), lambda: SLOT_UNALTERED, lambda: unalt)
-        for d in rotations:
-            next(ordinal)
-            yield ("r_%d" % d, lambda: clamp_rotate(raw, d), lambda: p.alter_rotate(d), lambda a, u: register_rotation(a, u, d),
-                   lambda: roi_rotation(shape, d), lambda: moved_slot(d, p.sim_rotate_reference, rotated_reference), lambda: rotated_reference(unalt, d))
-        for sg in sigmas:
-            k = next(ordinal)
-            noisy["gn_%s" % sg] = (k, lambda q, stream, i: q.alter_gaussian(0.0, sg, seed, stream, i))
-            yield ("gn_%s" % sg, lambda: add_gaussian_noise(raw, 0.0, sg, rng), lambda k=k: p.alter_gaussian(0.0, sg, seed, k))
-        for f in factors:
-            k = next(ordinal)
-            noisy["pn_%s" % f] = (k, lambda q, stream, i: q.alter_poisson(f, seed, stream, i))
-            yield ("pn_%s" % f, lambda: apply_quantum_noise(raw, f, rng), lambda k=k: p.alter_poisson(f, seed, k))
-        for e in symmetries:
-            yield ("d4_%d" % e, lambda: apply_symmetry(raw, e), lambda: p.alter_symmetry(e), lambda a, u: register_symmetry(a, u, e),
-                   lambda: roi_symmetry(shape), lambda: moved_slot(e, p.sim_transform_reference, apply_symmetry), lambda: apply_symmetry(unalt, e))
-        for r in blurs:
-            yield ("blur_%d" % r, lambda: binomial_blur(raw, r), lambda: p.alter_blur(r), lambda a, u: register_blur(a, u, r),
-                   lambda: roi_blur(shape, r), lambda: moved_slot(r, p.sim_blur_reference, binomial_blur), lambda: binomial_blur(unalt, r))
-
-    for row in study():
-        add(*row)
+    for alteration in study_alterations(raw, rng, runner.proc, seed, shape, opt):
+        row(alteration, eproc)
     return rows
-
-
-# ---- command line: the reference's three CSV files (script.py:223-330) -------------------------
-CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
-              'altered vs reference mse', 'altered vs reference ssim', 'altered vs reference histogram distance',
-              'normalized altered vs reference mse', 'normalized altered vs reference ssim',
-              'normalized altered vs reference histogram distance']
-
-
-REF_CSV_HEADER = ['raw file', 'mse similarity', 'ssim similarity', 'histogram distance']   # ref_similarities.csv (script.py:285-290)
-TONE_CSV_NAMES = ('mutual information', 'normalized mutual information', 'correlation ratio', 'tone-matched mse', 'tone-matched ssim')   # JOINT_METRICS' order
-TONE_CSV_GROUPS = (('direct_tone', 'altered vs unaltered'), ('registered_tone', 'registered vs unaltered'),
-                   ('reference_tone', 'altered vs reference'), ('registered_reference_tone', 'registered vs reference'))
-
-
-SHIFT_CSV_NAMES = ('dx', 'dy', 'sub dx', 'sub dy', 'mse at zero', 'mse at best', 'tiles', 'tiles off')   # SHIFT_KEYS' order
-SHIFT_CSV_GROUPS = (('direct_shift', 'direct'), ('registered_shift', 'registered'))
-SHIFT_CSV_HEADER = ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in SHIFT_CSV_GROUPS for m in SHIFT_CSV_NAMES]   # displacement.csv
-
-
-SCALE_CSV_GROUPS = tuple((SCALE_ROW_KEYS[k], g) for k, g in (("direct", "altered vs unaltered"), ("registered", "registered vs unaltered"),
-                                                               ("reference", "altered vs reference"), ("registered_reference", "registered vs reference")))
-SCALE_CSV_METRICS = ("ssim", "cs", "mse")   # per scale 0 .. 4, behind ms_ssim and scales
-
-
-ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
-ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
-ENSEMBLE_CSV_HEADER = ['raw file', 'alteration', 'realisations'] + ['%s %s' % (g, m) for g in ("direct", "registered") for _, m in ENSEMBLE_CSV_NAMES] + \
-                      ['per-realisation %s %s' % (m, w) for m in ENSEMBLE_CSV_METRICS for w in ("mean", "std")]   # ensemble.csv
-
-
-COV_CSV_NAMES = (("noise_var", "noise var"), ("rho_x", "rho x"), ("rho_y", "rho y"), ("corr_area", "correlation area"), ("hf_fraction", "hf fraction"))
-
-
-def covariance_csv_header(radius):
-    """noise_covariance.csv of a study with covariance=radius: the groups' numbers, then the radial spectrum of the direct group."""
-    return ['raw file', 'alteration', 'realisations', 'radius'] + ['%s %s' % (g, m) for g in ("direct", "registered") for _, m in COV_CSV_NAMES] + \
-           ['direct nps radius %d' % i for i in range(int(radius) + 1)]
-
-
-def scale_csv_header(with_reference):
-    """scale_robustness.csv's columns: per group ms_ssim, scales, then ssim, cs and mse of scales 0 .. 4; the two vendor groups only for
-    studies that have a vendor image."""
-    return ['raw file', 'alteration'] + [c for _, g in SCALE_CSV_GROUPS[:4 if with_reference else 2] for c in
-                                         ['%s ms-ssim' % g, '%s scales' % g] +
-                                         ['%s %s scale %d' % (g, m, s) for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)]]
-
-
-def _scale_csv_cells(t):
-    if t is None:
-        return [""] * (2 + len(SCALE_CSV_METRICS) * mp.SIM_MAX_SCALES)
-    return [t["ms_ssim"], t["scales"]] + [t[m][s] if s < t["scales"] else "" for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)]
-
-
-def tone_csv_header(with_reference):
-    """tone_robustness.csv's columns: the five JOINT_METRICS per group, the two vendor groups only for studies that have a vendor image."""
-    return ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in TONE_CSV_GROUPS[:4 if with_reference else 2] for m in TONE_CSV_NAMES]
-
-
-def normalized_vs_reference(ref, ovd):
-    """m_sim_alt's three normalised values (script.py:272-274): ref_mse / ovd_mse, ref_ssim / ovd_ssim and
-    (ref_hist - ovd_hist) / (1 - ovd_hist), with ovd the unaltered result vs the vendor image. IEEE f64 division: a zero denominator
-    gives inf or nan (the reference would raise ZeroDivisionError and stop the study)."""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return [float(np.float64(ref["mse"]) / np.float64(ovd["mse"])), float(np.float64(ref["ssim"]) / np.float64(ovd["ssim"])),
-                float((np.float64(ref["hist_distance"]) - ovd["hist_distance"]) / (1.0 - np.float64(ovd["hist_distance"])))]
-
-
-def write_studies_csvs(studies, out_dir, mean_cnr=True):
-    """The reference's output files for several raw images: `studies` is a list of (raw_name, rows) pairs (run_study's rows), written
-    in order into one direct_robustness.csv / reg_based_robustness.csv with the reference's column layout (script.py:223-330), plus
-    mean_cnr.csv (what test/mean_cnr/script.py reports per alteration).
-
-    The six "vs reference" columns compare with the vendor-processed image. For a study run with one (rows[0] has "reference"): the
-    altered result vs that image (reg_based_robustness.csv: the registered crops), then normalized_vs_reference against the study's
-    full-image unaltered-vs-vendor values, as m_sim_alt and m_sim_norm_alt do; ref_similarities.csv gets one row of those values per
-    such study and is written only when there is one. Studies without a vendor image leave the six columns empty.
-
-    Studies run with tone=True (rows[0] has "direct_tone") also get tone_robustness.csv: one line per row, the unaltered one included
-    (with a vendor image it carries the unaltered-vs-vendor numbers), the five JOINT_METRICS of the direct and of the registered
-    comparison, then, when any study has a vendor image, of the two comparisons with it. Cells without a comparison are empty. The
-    other files are written as without it.
-
-    Studies run with a displacement radius (rows[0] has "direct_shift") also get displacement.csv: one line per row, the unaltered one
-    included, the SHIFT_KEYS of the direct and of the registered comparison; cells without a comparison are empty.
-
-    Studies run with scales (rows[0] has "direct_scales") also get scale_robustness.csv (scale_csv_header): one line per row, the
-    unaltered one included; cells without a comparison, and of scales beyond a comparison's count, are empty.
-
-    Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
-    mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
-    and standard deviation over the realisations of the five similarity metrics.
-
-    Studies run with covariance=R (their noise rows' "ensemble" has "covariance") also get noise_covariance.csv
-    (covariance_csv_header): one line per noise row, K, R, the noise variance, rho x, rho y, correlation area and high-frequency
-    fraction of the direct and of the registered region (empty without one), then the radial noise power spectrum of the direct one."""
-    os.makedirs(out_dir, exist_ok=True)
-    ovds = []
-
-    def ref_columns(ref, ovd):
-        if ovd is None:
-            return [""] * 6
-        return [ref["mse"], ref["ssim"], ref["hist_distance"]] + normalized_vs_reference(ref, ovd)
-
-    with open(os.path.join(out_dir, "direct_robustness.csv"), "w", newline="") as fd, \
-            open(os.path.join(out_dir, "reg_based_robustness.csv"), "w", newline="") as fr:
-        wd, wr = csv.writer(fd), csv.writer(fr)
-        wd.writerow(CSV_HEADER)
-        wr.writerow(CSV_HEADER)
-        for raw_name, rows in studies:
-            ovd = next((r.get("reference") for r in rows if r["alteration"] == "unaltered"), None)
-            if ovd is not None:
-                ovds.append([raw_name, ovd["mse"], ovd["ssim"], ovd["hist_distance"]])
-            for r in rows:
-                if r["alteration"] == "unaltered":
-                    continue
-                d = r["direct"]
-                wd.writerow([raw_name, r["alteration"], d["mse"], d["ssim"], d["hist_distance"]] + ref_columns(r.get("reference"), ovd))
-                if r["registered"] is not None:
-                    g = r["registered"]
-                    wr.writerow([raw_name, r["alteration"], g["mse"], g["ssim"], g["hist_distance"]] +
-                                ref_columns(r.get("registered_reference"), ovd))
-    if mean_cnr:
-        with open(os.path.join(out_dir, "mean_cnr.csv"), "w", newline="") as fc:
-            wc = csv.writer(fc)
-            wc.writerow(["raw file", "alteration", "mean cnr"])
-            for raw_name, rows in studies:
-                for r in rows:
-                    wc.writerow([raw_name, r["alteration"], r["mean_cnr"]])
-    if ovds:
-        with open(os.path.join(out_dir, "ref_similarities.csv"), "w", newline="") as fs:
-            ws = csv.writer(fs)
-            ws.writerow(REF_CSV_HEADER)
-            ws.writerows(ovds)
-    toned = [(raw_name, rows) for raw_name, rows in studies if rows and "direct_tone" in rows[0]]
-    if toned:
-        groups = TONE_CSV_GROUPS[:4 if any("reference_tone" in rows[0] for _, rows in toned) else 2]
-        with open(os.path.join(out_dir, "tone_robustness.csv"), "w", newline="") as ft:
-            wt = csv.writer(ft)
-            wt.writerow(tone_csv_header(len(groups) == 4))
-            for raw_name, rows in toned:
-                for r in rows:
-                    cells = []
-                    for key, _ in groups:
-                        t = r.get(key)
-                        cells += [""] * len(mp.JOINT_METRICS) if t is None else [t[k] for k in mp.JOINT_METRICS]
-                    wt.writerow([raw_name, r["alteration"]] + cells)
-    shifted = [(raw_name, rows) for raw_name, rows in studies if rows and "direct_shift" in rows[0]]
-    if shifted:
-        with open(os.path.join(out_dir, "displacement.csv"), "w", newline="") as fs:
-            ws = csv.writer(fs)
-            ws.writerow(SHIFT_CSV_HEADER)
-            for raw_name, rows in shifted:
-                for r in rows:
-                    cells = []
-                    for key, _ in SHIFT_CSV_GROUPS:
-                        t = r.get(key)
-                        cells += [""] * len(SHIFT_KEYS) if t is None else [t[k] for k in SHIFT_KEYS]
-                    ws.writerow([raw_name, r["alteration"]] + cells)
-
-
-    scored = [(raw_name, rows) for raw_name, rows in studies if rows and "direct_scales" in rows[0]]
-    if scored:
-        groups = SCALE_CSV_GROUPS[:4 if any("reference_scales" in rows[0] for _, rows in scored) else 2]
-        with open(os.path.join(out_dir, "scale_robustness.csv"), "w", newline="") as fs:
-            ws = csv.writer(fs)
-            ws.writerow(scale_csv_header(len(groups) == 4))
-            for raw_name, rows in scored:
-                for r in rows:
-                    ws.writerow([raw_name, r["alteration"]] + [c for key, _ in groups for c in _scale_csv_cells(r.get(key))])
-    ensembles = [(raw_name, rows) for raw_name, rows in studies if rows and "ensemble" in rows[0]]
-    if ensembles:
-        with open(os.path.join(out_dir, "ensemble.csv"), "w", newline="") as fe:
-            we = csv.writer(fe)
-            we.writerow(ENSEMBLE_CSV_HEADER)
-            for raw_name, rows in ensembles:
-                for r in rows:
-                    e = r["ensemble"]
-                    if e is None:
-                        continue
-                    cells = []
-                    for key in ("direct", "registered"):
-                        cells += [""] * len(ENSEMBLE_CSV_NAMES) if e[key] is None else [e[key][k] for k, _ in ENSEMBLE_CSV_NAMES]
-                    per = e["per_realisation"]
-                    we.writerow([raw_name, r["alteration"], e["realisations"]] + cells + [per[w][k] for k in mp.SIM_METRICS for w in ("mean", "std")])
-    covs = [(raw_name, [r for r in rows if r.get("ensemble") and "covariance" in r["ensemble"]]) for raw_name, rows in ensembles]
-    covs = [(raw_name, rows) for raw_name, rows in covs if rows]
-    if covs:
-        radius = covs[0][1][0]["ensemble"]["covariance"]["direct"]["radius"]
-        with open(os.path.join(out_dir, "noise_covariance.csv"), "w", newline="") as fc:
-            wc = csv.writer(fc)
-            wc.writerow(covariance_csv_header(radius))
-            for raw_name, rows in covs:
-                for r in rows:
-                    e = r["ensemble"]
-                    cells = []
-                    for key in ("direct", "registered"):
-                        g = e["covariance"][key]
-                        cells += [""] * len(COV_CSV_NAMES) if g is None else [g[k] for k, _ in COV_CSV_NAMES]
-                    wc.writerow([raw_name, r["alteration"], e["realisations"], radius] + cells + list(e["covariance"]["direct"]["nps_radial"]))
-
-
-def write_ensemble_maps(studies, out_dir):
-    """Two 8-bit BMPs per noise row of studies run with ensemble_tiles (ensemble_maps: one pixel per 64 x 64 tile of the full frame):
-    <raw>_<alteration>_bias.bmp, the tile's bias rms against the unaltered result, and <raw>_<alteration>_noise.bmp, its noise rms, in
-    gray levels. Returns the paths written."""
-    os.makedirs(out_dir, exist_ok=True)
-    written = []
-    for raw_name, rows in studies:
-        stem = os.path.splitext(os.path.basename(raw_name.replace("\\", "/")))[0]
-        for r in rows:
-            e = r.get("ensemble")
-            if e is None or "tile_tables" not in e["direct"]:
-                continue
-            for what, img in zip(("bias", "noise"), ensemble_maps(e["direct"]["tile_tables"], *e["direct"]["size"], e["realisations"])):
-                path = os.path.join(out_dir, "%s_%s_%s.bmp" % (stem, r["alteration"], what))
-                if not mp.write_bmp_gray(path, img):
-                    raise RuntimeError("writing %s failed: %s" % (path, mp.last_error()))
-                written.append(path)
-    return written
-
-
-def write_covariance_maps(studies, out_dir):
-    """One 8-bit BMP per noise row of studies run with covariance_tiles: <raw>_<alteration>_nps.bmp, the centred noise power spectrum of
-    the direct region (nps_map: S x S pixels, the zero frequency in the middle, log-scaled). Returns the paths written."""
-    os.makedirs(out_dir, exist_ok=True)
-    written = []
-    for raw_name, rows in studies:
-        stem = os.path.splitext(os.path.basename(raw_name.replace("\\", "/")))[0]
-        for r in rows:
-            e = r.get("ensemble")
-            g = e["covariance"]["direct"] if e and "covariance" in e else None
-            if g is None or "table" not in g:
-                continue
-            path = os.path.join(out_dir, "%s_%s_nps.bmp" % (stem, r["alteration"]))
-            if not mp.write_bmp_gray(path, nps_map(g["table"], g["realisations"], g["pixels"])):
-                raise RuntimeError("writing %s failed: %s" % (path, mp.last_error()))
-            written.append(path)
-    return written
-
-
-def write_displacement_maps(studies, out_dir):
-    """Two 8-bit BMPs per registered row of studies run with displacement_tiles (displacement_maps: one pixel per 64 x 64 tile):
-    <raw>_<alteration>_rmse.bmp, the tile RMSE at the zero shift, and <raw>_<alteration>_shift.bmp, the length of the tile's best shift.
-    Returns the paths written."""
-    os.makedirs(out_dir, exist_ok=True)
-    written = []
-    for raw_name, rows in studies:
-        stem = os.path.splitext(os.path.basename(raw_name.replace("\\", "/")))[0]
-        for r in rows:
-            t = r.get("registered_shift")
-            if t is None or "tile_tables" not in t:
-                continue
-            for what, img in zip(("rmse", "shift"), displacement_maps(t["tile_tables"], *t["size"])):
-                path = os.path.join(out_dir, "%s_%s_%s.bmp" % (stem, r["alteration"], what))
-                if not mp.write_bmp_gray(path, img):
-                    raise RuntimeError("writing %s failed: %s" % (path, mp.last_error()))
-                written.append(path)
-    return written
-
-
-def write_study_csvs(rows, out_dir, raw_name, mean_cnr=True):
-    """write_studies_csvs for one raw image: direct_robustness.csv / reg_based_robustness.csv with the reference's column layout,
-    mean_cnr.csv, and (rows of a study with a vendor image) the "vs reference" columns and ref_similarities.csv."""
-    write_studies_csvs([(raw_name, rows)], out_dir, mean_cnr=mean_cnr)
 
 
 def read_manifest(path):

@@ -1,0 +1,591 @@
+"""The host restatements of the study's metrics: numpy statements of what the musica_sim_* kernels compute (include/musica.h), which the
+host study scores with and the GPU tests compare the kernels against. harness re-exports every name."""
+import math
+
+import numpy as np
+from scipy import ndimage
+
+from . import processing as mp
+
+
+# ---- similarity metrics (script.py:143-198) ----------------------------------------------------------
+
+def mse_similarity(a, b):
+    """1 - RMSE / 255 (script.py:143-145)."""
+    e = np.abs(a.astype(np.float64) - b.astype(np.float64)) / 255
+    return 1.0 - math.sqrt(np.mean(np.square(e)))
+
+
+def ssim_similarity(a, b):
+    """skimage.metrics.structural_similarity with its defaults for uint8 input (script.py:147-152):
+    7 x 7 uniform window, K1 = 0.01, K2 = 0.03, data range 255, sample covariance, borders cropped."""
+    x, y = a.astype(np.float64), b.astype(np.float64)
+    win = 7
+    npx = win * win
+    cov_norm = npx / (npx - 1)
+    ux, uy = ndimage.uniform_filter(x, win), ndimage.uniform_filter(y, win)
+    uxx, uyy, uxy = ndimage.uniform_filter(x * x, win), ndimage.uniform_filter(y * y, win), ndimage.uniform_filter(x * y, win)
+    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
+    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
+    pad = (win - 1) // 2
+    return float(s[pad:-pad, pad:-pad].mean())
+
+
+def hist_similarity(a, b):
+    """(intersection, normalised Euclidean distance, Bhattacharyya coefficient) of the 256-bin histograms
+    (script.py:154-198; np.histogram(bins=256) spans [min, max] of each image, as there)."""
+    ha, _ = np.histogram(a.ravel(), bins=256)
+    hb, _ = np.histogram(b.ravel(), bins=256)
+    inter = np.sum(np.minimum(ha, hb)) / min(np.sum(ha), np.sum(hb))
+    na, nb = ha / np.sum(ha), hb / np.sum(hb)
+    e_dist = math.sqrt(np.sum((na - nb) ** 2)) / math.sqrt(2)
+    b_coef = float(np.sum(np.sqrt(na * nb)))
+    return float(inter), float(e_dist), b_coef
+
+
+def similarities(a, b):
+    inter, e_dist, b_coef = hist_similarity(a, b)
+    return {"mse": mse_similarity(a, b), "ssim": ssim_similarity(a, b), "hist_intersection": inter,
+            "hist_distance": e_dist, "hist_bhattacharyya": b_coef}
+
+
+# ---- tone metrics from the joint gray-level histogram (not in the reference's script) ----------------------
+# MUSICA's gradation follows the image's own histogram, so an alteration that changes the histogram moves the global tone curve of the
+# output, and mse / ssim charge that shift in full. The joint histogram J[a][b] of two aligned 8-bit images separates it: mutual
+# information (Viola & Wells; Maes et al.) and the correlation ratio (Roche et al.) do not change under an invertible remap of b's gray
+# levels, and the least-squares remap E[a | b] itself turns a comparison into a tone-matched one. These functions state the numbers of
+# musica_sim_joint (include/musica.h) in Python integers and f64, in its summation order.
+
+def joint_histogram(a, b):
+    """J[a][b]: how many pixels have the value a in `a` and b in `b` (two uint8 arrays of one shape); (256, 256) int64."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("joint_histogram needs two uint8 arrays of one shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    return np.bincount(a.ravel().astype(np.int64) * 256 + b.ravel(), minlength=65536).reshape(256, 256)
+
+
+def _joint_moments(J):
+    """Per value b of the second image, as Python integers: B_b (count), S_b = sum_a a J[a][b], Q_b = sum_a a^2 J[a][b]."""
+    J = np.asarray(J).astype(np.int64)
+    v = np.arange(256, dtype=np.int64)
+    return [int(x) for x in J.sum(axis=0)], [int(x) for x in v @ J], [int(x) for x in (v * v) @ J]
+
+
+def tone_lut(J):
+    """The least-squares gray-level remap of b onto a, E[a | b] rounded half up: (2 S_b + B_b) // (2 B_b) where b occurs, else b;
+    (256,) uint8."""
+    B, S, _ = _joint_moments(J)
+    return np.array([(2 * S[b] + B[b]) // (2 * B[b]) if B[b] else b for b in range(256)], dtype=np.uint8)
+
+
+def joint_similarities(J):
+    """mi, nmi, corr_ratio, tone_mse and the entropies h_a, h_b, h_ab (nats) of a joint histogram, as musica_sim_joint computes them:
+    sums in ascending a, then ascending b, zero counts skipped; the variance numerators as exact integers, one f64 division per term."""
+    J = np.asarray(J).astype(np.int64)
+    n = int(J.sum())
+    if n == 0:
+        raise ValueError("empty joint histogram")
+    A = [int(x) for x in J.sum(axis=1)]
+    B, S, Q = _joint_moments(J)
+    dn = float(n)
+
+    def entropy(counts):
+        h = 0.0
+        for c in counts:
+            if c:
+                p = float(c) / dn
+                h -= p * math.log(p)
+        return h
+
+    h_a, h_b = entropy(A), entropy(B)
+    h_ab = mi = 0.0
+    for a, b in zip(*np.nonzero(J)):          # row-major: ascending a, then ascending b
+        j = int(J[a, b])
+        p = float(j) / dn
+        h_ab -= p * math.log(p)
+        mi += p * math.log(float(j * n) / float(A[a] * B[b]))
+    ssw = 0.0
+    for b in range(256):
+        if B[b]:
+            ssw += float(B[b] * Q[b] - S[b] * S[b]) / float(B[b])
+    sst_num = n * sum(a * a * A[a] for a in range(256)) - sum(a * A[a] for a in range(256)) ** 2
+    return {"mi": mi, "nmi": 1.0 if h_a + h_b == 0.0 else 2.0 * mi / (h_a + h_b),
+            "corr_ratio": 1.0 if sst_num == 0 else 1.0 - ssw / (float(sst_num) / dn),
+            "tone_mse": 1.0 - math.sqrt(ssw / dn) / 255.0, "h_a": h_a, "h_b": h_b, "h_ab": h_ab}
+
+
+def tone_similarities(a, b):
+    """The five JOINT_METRICS of two uint8 images of one shape: mi (mutual information, nats), nmi (2 mi / (h_a + h_b)), corr_ratio
+    (1 - SSW / SST: the share of a's variance a function of b explains), tone_mse (mse_similarity after the best gray-level remap of b
+    onto a: 1 - sqrt(SSW / n) / 255) and tone_ssim (ssim_similarity of a and b remapped with tone_lut)."""
+    J = joint_histogram(a, b)
+    r = joint_similarities(J)
+    out = {k: r[k] for k in mp.JOINT_METRICS if k != "tone_ssim"}
+    out["tone_ssim"] = ssim_similarity(a, tone_lut(J)[b])
+    return out
+
+
+# ---- where the output went: exact block matching (musica_sim_displace; not in the reference) ------------------
+
+def _displacement_geometry(a_shape, b_shape, region, radius):
+    """Raises ValueError exactly where musica_sim_displace refuses a query on geometry; returns the region and radius as ints."""
+    ax, ay, bx, by, w, h = (int(v) for v in region)
+    radius = int(radius)
+    if not 1 <= radius <= mp.SIM_MAX_RADIUS:
+        raise ValueError("radius %d out of range [1, %d]" % (radius, mp.SIM_MAX_RADIUS))
+    if w < 7 or h < 7:
+        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
+    if ax < 0 or ay < 0 or ax + w > a_shape[1] or ay + h > a_shape[0]:
+        raise ValueError("region (%d, %d) + %d x %d leaves the %d x %d output plane" % (ax, ay, w, h, a_shape[1], a_shape[0]))
+    if bx < radius or by < radius or bx + w + radius > b_shape[1] or by + h + radius > b_shape[0]:
+        raise ValueError("the b window (%d, %d) + %d x %d grown by the radius %d leaves the %d x %d plane" % (bx, by, w, h, radius, b_shape[1], b_shape[0]))
+    return (ax, ay, bx, by, w, h), radius
+
+
+def _displacement_squares(a, b, region, radius):
+    """((dy, dx), the h x w int64 squared differences of the region under that shift) for every candidate, one shifted crop each."""
+    ax, ay, bx, by, w, h = region
+    ca = np.asarray(a)[ay:ay + h, ax:ax + w].astype(np.int64)
+    b = np.asarray(b)
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            yield (dy, dx), (ca - b[by + dy:by + dy + h, bx + dx:bx + dx + w].astype(np.int64)) ** 2
+
+
+def displacement_table(a, b, region, radius):
+    """musica_sim_displace's table of one query, restated: a the output image, b the full reference plane, region = (ax, ay, bx, by, w, h).
+    T[dy + radius][dx + radius] = sum over the region of (a[ay + y][ax + x] - b[by + y + dy][bx + x + dx])^2 for dy, dx in
+    [-radius, radius], one shifted crop per candidate, in int64. ValueError where the C call refuses on geometry: a radius outside
+    1 .. 16, w < 7 or h < 7, an a region that leaves a, a b window that, grown by the radius, leaves b."""
+    region, radius = _displacement_geometry(np.shape(a), np.shape(b), region, radius)
+    T = np.empty((2 * radius + 1,) * 2, dtype=np.int64)
+    for (dy, dx), sq in _displacement_squares(a, b, region, radius):
+        T[dy + radius, dx + radius] = np.sum(sq)
+    return T
+
+
+def displacement_tile_tables(a, b, region, radius):
+    """The same per 64 x 64 tile of the region (the last tiles ragged): (tiles_y, tiles_x, S, S) uint32, tile-row major; their sum over
+    the tiles is displacement_table."""
+    region, radius = _displacement_geometry(np.shape(a), np.shape(b), region, radius)
+    w, h = region[4], region[5]
+    t = mp.SIM_TILE
+    ny, nx, s = (h + t - 1) // t, (w + t - 1) // t, 2 * radius + 1
+    out = np.empty((ny, nx, s, s), dtype=np.uint32)
+    for (dy, dx), sq in _displacement_squares(a, b, region, radius):
+        out[:, :, dy + radius, dx + radius] = np.add.reduceat(np.add.reduceat(sq, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
+    return out
+
+
+def _displacement_argmin(T):
+    """(row, column) of the table's argmin: smallest value, then smallest dx^2 + dy^2, then smallest dy, then smallest dx."""
+    T = np.asarray(T)
+    radius = T.shape[0] // 2
+    ys, xs = np.nonzero(T == T.min())
+    return min(zip(ys.tolist(), xs.tolist()), key=lambda p: ((p[1] - radius) ** 2 + (p[0] - radius) ** 2, p[0], p[1]))
+
+
+def displacement_from_table(T):
+    """{dx, dy, ssd_min, ssd_zero, sub_dx, sub_dy} of an (S, S) displacement table: the argmin by the tie rule, and the vertex of the
+    parabola through the argmin and its two neighbours along the row (sub_dx) and along the column (sub_dy):
+    sub = d + (T- - T+) / (2 (T- - 2 T0 + T+)), computed from the exact integers with one f64 division, where |d| < radius and the
+    denominator is positive, else sub = d. The device and the host studies both call this on exact integer tables."""
+    T = np.asarray(T)
+    if T.ndim != 2 or T.shape[0] != T.shape[1] or T.shape[0] % 2 != 1 or T.shape[0] < 3:
+        raise ValueError("expected an (S, S) table with S = 2 radius + 1, got %r" % (T.shape,))
+    radius = T.shape[0] // 2
+    y, x = _displacement_argmin(T)
+
+    def vertex(d, lo, mid, hi):
+        if abs(d) >= radius:
+            return float(d)
+        lo, mid, hi = int(lo()), int(mid), int(hi())
+        den = 2 * (lo - 2 * mid + hi)
+        return d + (lo - hi) / den if den > 0 else float(d)
+
+    dx, dy = x - radius, y - radius
+    return {"dx": dx, "dy": dy, "ssd_min": int(T[y, x]), "ssd_zero": int(T[radius, radius]),
+            "sub_dx": vertex(dx, lambda: T[y, x - 1], T[y, x], lambda: T[y, x + 1]),
+            "sub_dy": vertex(dy, lambda: T[y - 1, x], T[y, x], lambda: T[y + 1, x])}
+
+
+def displacement_tiles_off(tile_tables):
+    """How many tiles' own argmin (the same tie rule) is not (0, 0)."""
+    tt = np.asarray(tile_tables)
+    radius = tt.shape[2] // 2
+    return sum(1 for ty in range(tt.shape[0]) for tx in range(tt.shape[1]) if _displacement_argmin(tt[ty, tx]) != (radius, radius))
+
+
+SHIFT_KEYS = ("dx", "dy", "sub_dx", "sub_dy", "mse_at_zero", "mse_at_best", "tiles", "tiles_off")
+
+
+def displacement_summary(T, pixels, tiles, tiles_off):
+    """A study row's *_shift dict (SHIFT_KEYS) from an exact table: displacement_from_table's shift, 1 - sqrt(ssd / pixels) / 255 at the
+    zero shift and at the best one, the number of tiles and of those whose own best shift is not (0, 0)."""
+    d = displacement_from_table(T)
+    out = {k: d[k] for k in ("dx", "dy", "sub_dx", "sub_dy")}
+    out["mse_at_zero"] = 1.0 - math.sqrt(d["ssd_zero"] / int(pixels)) / 255.0
+    out["mse_at_best"] = 1.0 - math.sqrt(d["ssd_min"] / int(pixels)) / 255.0
+    out["tiles"], out["tiles_off"] = int(tiles), int(tiles_off)
+    return out
+
+
+def displacement_maps(tile_tables, w, h):
+    """Two (tiles_y, tiles_x) uint8 maps of a w x h region's tile tables, one pixel per tile: the RMSE at the zero shift, rounded, and the
+    length of the tile's best shift, scaled so that the table's corner (radius, radius) is 255."""
+    tt = np.asarray(tile_tables)
+    ny, nx, radius, t = tt.shape[0], tt.shape[1], tt.shape[2] // 2, mp.SIM_TILE
+    rmse, mag = np.zeros((ny, nx), dtype=np.uint8), np.zeros((ny, nx), dtype=np.uint8)
+    for ty in range(ny):
+        for tx in range(nx):
+            px = (min(h, t * ty + t) - t * ty) * (min(w, t * tx + t) - t * tx)
+            rmse[ty, tx] = int(round(math.sqrt(int(tt[ty, tx, radius, radius]) / px)))
+            y, x = _displacement_argmin(tt[ty, tx])
+            mag[ty, tx] = int(round(255.0 * math.hypot(x - radius, y - radius) / (math.sqrt(2.0) * radius)))
+    return rmse, mag
+
+
+def _inset(region, r):
+    """The region (ax, ay, bx, by, w, h) inset by r on every side, or None when a side falls under 7."""
+    ax, ay, bx, by, w, h = region
+    return (ax + r, ay + r, bx + r, by + r, w - 2 * r, h - 2 * r) if min(w, h) - 2 * r >= 7 else None
+
+
+# ---- at which scale the output changed: multi-scale SSIM in exact integers (musica_sim_multiscale; not in the reference) ----
+# MUSICA is a Laplacian pyramid and each of its stages works at scales of its own (per-level contrast curves, noise reduction on levels
+# 0 .. 2, the CNR weighting from level 3, the coarser-levels gain); a single 7 x 7 SSIM cannot tell a loss in the finest bands from a
+# change of the coarse ones. Multi-scale SSIM (Wang, Simoncelli, Bovik 2003) with ssim_similarity's uniform 7 x 7 window has an exact
+# integer form: iterated 2 x 2 mean pooling is the 2^s x 2^s block mean, the block SUMS of u8 data are integers (<= 255 * 4^s), so every
+# window sum at every scale is an exact integer and only the last f64 summation is open to reordering. These functions are the contract
+# of musica_sim_multiscale (include/musica.h).
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # the 2003 paper's
+SCALES_KEYS = ("ms_ssim", "scales") + mp.SCALE_METRICS        # a study row's *_scales dict
+
+
+def block_sums(a, s):
+    """X_s of a 2-D integer array: [i][j] = the sum of the 2^s x 2^s block whose top-left is (i 2^s, j 2^s); (h >> s, w >> s) int64,
+    rows and columns that do not fill a block dropped."""
+    a = np.asarray(a)
+    k = 1 << s
+    hs, ws = a.shape[0] >> s, a.shape[1] >> s
+    return a[:hs * k, :ws * k].astype(np.int64).reshape(hs, k, ws, k).sum(axis=(1, 3))
+
+
+def _window_sums7(p):
+    """The sums of all 7 x 7 windows of an int64 plane, (h - 6, w - 6) int64: differences of its summed-area table (exact)."""
+    c = np.zeros((p.shape[0] + 1, p.shape[1] + 1), dtype=np.int64)
+    c[1:, 1:] = p.cumsum(axis=0).cumsum(axis=1)
+    return c[7:, 7:] - c[:-7, 7:] - c[7:, :-7] + c[:-7, :-7]
+
+
+def multiscale_terms(sx, sy, sxx, syy, sxy, s):
+    """(ssim, cs, lum) per window from the exact 7 x 7 window sums of X_s, Y_s, X_s^2, Y_s^2, X_s Y_s (int64 arrays or ints): the means
+    by one f64 division by the exact doubles 49 * 4^s and 49 * 16^s, then ssim_similarity's expression in its order."""
+    d1, d2 = float(49 * 4 ** s), float(49 * 16 ** s)
+    ux, uy = np.asarray(sx, dtype=np.int64) / d1, np.asarray(sy, dtype=np.int64) / d1
+    uxx, uyy, uxy = np.asarray(sxx, dtype=np.int64) / d2, np.asarray(syy, dtype=np.int64) / d2, np.asarray(sxy, dtype=np.int64) / d2
+    cov_norm = 49 / 48
+    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
+    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    a1, a2, b1, b2 = 2 * ux * uy + c1, 2 * vxy + c2, ux * ux + uy * uy + c1, vx + vy + c2
+    return (a1 * a2) / (b1 * b2), a2 / b2, a1 / b1
+
+
+def multiscale_windows(a, b, s):
+    """(ssim, cs, lum), each (h_s - 6, w_s - 6) f64: the per-window values of scale s of two uint8 arrays of one shape."""
+    x, y = block_sums(a, s), block_sums(b, s)
+    return multiscale_terms(_window_sums7(x), _window_sums7(y), _window_sums7(x * x), _window_sums7(y * y), _window_sums7(x * y), s)
+
+
+def ms_ssim_from_means(cs, ssim_last):
+    """The combined number from the per-scale means: prod over s < scales - 1 of max(cs[s], 0)^w_s, times max(ssim of the last scale,
+    0)^w_last, w_s = W[s] / sum(W[:scales]); math.pow, ascending s. cs: the means of scales 0 .. scales - 1 (the last is not used)."""
+    n = len(cs)
+    total = sum(MS_SSIM_WEIGHTS[:n])
+    out = 1.0
+    for s in range(n):
+        out *= math.pow(max(float(cs[s]) if s < n - 1 else float(ssim_last), 0.0), MS_SSIM_WEIGHTS[s] / total)
+    return out
+
+
+def max_scales(w, h):
+    """The largest scale count a w x h region admits: min(w, h) >> (count - 1) >= 7; 0 for a region under 7 x 7, at most SIM_MAX_SCALES."""
+    n = 0
+    while n < mp.SIM_MAX_SCALES and (min(int(w), int(h)) >> n) >= 7:
+        n += 1
+    return n
+
+
+def multiscale_similarities(a, b, scales):
+    """musica_sim_multiscale's numbers of two uint8 arrays of one shape (h, w), 1 <= scales <= 5, min(h, w) >> (scales - 1) >= 7 (else
+    ValueError): {ms_ssim, scales, pixels, ssim, cs, lum, mse, ssd, plane_w, plane_h}, the last seven lists of length `scales`.
+    ssim / cs / lum: the means of multiscale_windows over the windows; ssd[s] = sum (X_s - Y_s)^2 (exact);
+    mse[s] = 1 - sqrt(ssd[s] / (h_s w_s)) / (255 * 4^s); ms_ssim: ms_ssim_from_means."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or a.shape != b.shape or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("multiscale_similarities needs two uint8 arrays of one 2-D shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    scales = int(scales)
+    if not 1 <= scales <= mp.SIM_MAX_SCALES:
+        raise ValueError("scales %d out of range [1, %d]" % (scales, mp.SIM_MAX_SCALES))
+    h, w = a.shape
+    if (min(h, w) >> (scales - 1)) < 7:
+        raise ValueError("region %d x %d is smaller than the 7 x 7 window at scale %d" % (w, h, scales - 1))
+    out = {"scales": scales, "pixels": h * w, "ssim": [], "cs": [], "lum": [], "mse": [], "ssd": [], "plane_w": [], "plane_h": []}
+    for s in range(scales):
+        ssim, cs, lum = multiscale_windows(a, b, s)
+        hs, ws = h >> s, w >> s
+        ssd = int(np.sum((block_sums(a, s) - block_sums(b, s)) ** 2))
+        out["ssim"].append(float(ssim.mean()))
+        out["cs"].append(float(cs.mean()))
+        out["lum"].append(float(lum.mean()))
+        out["ssd"].append(ssd)
+        out["mse"].append(1.0 - math.sqrt(ssd / (hs * ws)) / (255 * 4 ** s))
+        out["plane_w"].append(ws)
+        out["plane_h"].append(hs)
+    out["ms_ssim"] = ms_ssim_from_means(out["cs"], out["ssim"][-1])
+    return out
+
+
+# ---- bias and noise over many realisations: ensemble statistics (musica_sim_ensemble_*; not in the reference) ----
+# A noise row scores ONE random draw, which cannot tell a systematic change of the output (a tone curve that moved with the gradation
+# histogram, lost detail) from amplified noise, nor say how far the score moves under another seed. Over K realisations a_k of the same
+# alteration the per-pixel sums S1 = sum a_k and S2 = sum a_k^2 give both: D = S1 - K b is K times the bias against the unaltered result
+# b, V = K S2 - S1^2 is K (K - 1) times the sample variance. All of it is integer arithmetic; these functions are the contract of
+# musica_sim_ensemble_result (include/musica.h).
+ENSEMBLE_KEYS = mp.ENSEMBLE_METRICS + mp.ENSEMBLE_INTEGERS   # a study row's ensemble dicts; ensemble_statistics adds "tile_tables"
+
+
+def ensemble_stream(ordinal, j):
+    """The Philox stream of realisation j < 1024 of the study row with that ordinal (1, 2, ..): 1024 ordinal + j. Ordinals start at 1,
+    so these streams never meet a row's own stream, its ordinal (a study has far fewer than 1024 rows)."""
+    ordinal, j = int(ordinal), int(j)
+    if ordinal < 1 or not 0 <= j < mp.SIM_ENSEMBLE_MAX:
+        raise ValueError("ensemble_stream: ordinal %d must be >= 1 and the realisation %d in 0 .. %d" % (ordinal, j, mp.SIM_ENSEMBLE_MAX - 1))
+    return mp.SIM_ENSEMBLE_MAX * ordinal + j
+
+
+def ensemble_summary(sq_bias_sum, var_sum, sq_err_sum, bias_sum, abs_bias_max, var_max, realisations, w, h):
+    """A query's ENSEMBLE_KEYS dict from its exact integers: the doubles one IEEE operation each in include/musica.h's order, every
+    integer converted to double first. The device and the host studies both call this, so they agree to the last bit."""
+    ints = [int(v) for v in (sq_bias_sum, var_sum, sq_err_sum, bias_sum, abs_bias_max, var_max)]
+    k, n = int(realisations), int(w) * int(h)
+    sq_bias, var, sq_err, bias = ints[:4]
+    if k * sq_err != sq_bias + var:
+        raise ValueError("ensemble_summary: K sq_err_sum != sq_bias_sum + var_sum (%d * %d, %d + %d)" % (k, sq_err, sq_bias, var))
+    t = mp.SIM_TILE
+    out = {"mean_shift": float(bias) / float(k * n),
+           "bias_rms": math.sqrt(float(sq_bias) / float(k * k * n)),
+           "noise_rms": 0.0 if k == 1 else math.sqrt(float(var) / float(k * (k - 1) * n)),
+           "mse": 1.0 - math.sqrt(float(sq_err) / float(k * n)) / 255.0,
+           "bias_fraction": 0.0 if sq_bias + var == 0 else float(sq_bias) / float(sq_bias + var)}
+    out.update(zip(mp.ENSEMBLE_INTEGERS, ints + [n, k, (int(w) + t - 1) // t, (int(h) + t - 1) // t]))
+    return out
+
+
+def ensemble_statistics(outs, b, region):
+    """musica_sim_ensemble_result's numbers of one query, restated: outs a (K, H, W) stack of uint8 outputs (the realisations), b the full
+    uint8 reference plane, region = (ax, ay, bx, by, w, h). Integer dtype throughout: S1, S2, D, V and the error term per pixel and the
+    tile sums in int64 (a tile's sum D^2 <= 64^2 * 261120^2 < 2^63), the totals as Python ints summed over the tiles. Returns the
+    ENSEMBLE_KEYS dict (ensemble_summary) plus "tile_tables": (tiles_y, tiles_x, 2) uint64, (sum D^2, sum V) per 64 x 64 tile. ValueError
+    where the C call refuses: no or more than SIM_ENSEMBLE_MAX realisations, w < 7 or h < 7, a region that leaves either plane,
+    65025 K^2 w h >= 2^64."""
+    outs, b = np.asarray(outs), np.asarray(b)
+    if outs.ndim != 3 or b.ndim != 2 or outs.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("ensemble_statistics needs a (K, H, W) uint8 stack and a 2-D uint8 plane, got %r %s and %r %s" % (outs.shape, outs.dtype, b.shape, b.dtype))
+    k = outs.shape[0]
+    if not 1 <= k <= mp.SIM_ENSEMBLE_MAX:
+        raise ValueError("%d realisations out of range [1, %d]" % (k, mp.SIM_ENSEMBLE_MAX))
+    ax, ay, bx, by, w, h = (int(v) for v in region)
+    if w < 7 or h < 7:
+        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
+    if min(ax, ay, bx, by) < 0 or ax + w > outs.shape[2] or ay + h > outs.shape[1] or bx + w > b.shape[1] or by + h > b.shape[0]:
+        raise ValueError("region (%d, %d) / (%d, %d) + %d x %d leaves the planes" % (ax, ay, bx, by, w, h))
+    if 65025 * k * k * w * h >= 2 ** 64:
+        raise ValueError("65025 * %d^2 * %d * %d does not fit 64 bits" % (k, w, h))
+    a = outs[:, ay:ay + h, ax:ax + w].astype(np.int64)
+    cb = b[by:by + h, bx:bx + w].astype(np.int64)
+    s1, s2 = a.sum(axis=0), (a * a).sum(axis=0)
+    d = s1 - k * cb
+    v = k * s2 - s1 * s1
+    e = s2 - 2 * cb * s1 + k * cb * cb
+    t = mp.SIM_TILE
+
+    def tiles(x):
+        return np.add.reduceat(np.add.reduceat(x, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
+
+    tile_tables = np.stack([tiles(d * d), tiles(v)], axis=-1).astype(np.uint64)
+    out = ensemble_summary(sum(int(x) for x in tile_tables[..., 0].ravel()), sum(int(x) for x in tile_tables[..., 1].ravel()),
+                           sum(int(x) for x in tiles(e).ravel()), sum(int(x) for x in tiles(d).ravel()), int(np.abs(d).max()), int(v.max()), k, w, h)
+    out["tile_tables"] = tile_tables
+    return out
+
+
+def ensemble_maps(tile_tables, w, h, realisations):
+    """Two (tiles_y, tiles_x) uint8 maps of a w x h region's ensemble tile table, one pixel per tile: the tile's bias rms,
+    sqrt(sum D^2 / (K^2 pixels)), and its noise rms, sqrt(sum V / (K (K - 1) pixels)) (0 for K == 1), in gray levels, rounded."""
+    tt = np.asarray(tile_tables)
+    ny, nx, t, k = tt.shape[0], tt.shape[1], mp.SIM_TILE, int(realisations)
+    bias, noise = np.zeros((ny, nx), dtype=np.uint8), np.zeros((ny, nx), dtype=np.uint8)
+    for ty in range(ny):
+        for tx in range(nx):
+            px = (min(h, t * ty + t) - t * ty) * (min(w, t * tx + t) - t * tx)
+            bias[ty, tx] = min(255, int(round(math.sqrt(int(tt[ty, tx, 0]) / (k * k * px)))))
+            noise[ty, tx] = min(255, int(round(math.sqrt(int(tt[ty, tx, 1]) / (k * (k - 1) * px))))) if k > 1 else 0
+    return bias, noise
+
+
+# ---- the texture of the noise: spatial auto-covariance and power spectrum (musica_sim_ensemble_track / _covariance; not in the reference) ----
+# The per-pixel statistics say how strong the output noise is and nothing about its grain: MUSICA amplifies fine pyramid levels more than
+# coarse ones and its noise reduction works on 5 x 5 neighbourhoods, so the noise that leaves it is coloured. Over K realisations a_k,
+# with S1 = sum_k a_k, the lag products P(d) = sum_k sum_p a_k(p) a_k(p + d) and U(d) = sum_p S1(p) S1(p + d) over a region of n pixels
+# give C(d) = K P(d) - U(d) = K^2 n times the population covariance at lag d about the per-pixel ensemble mean, in exact integers; the
+# neighbour correlations, the correlation area and the noise power spectrum (Wiener-Khinchin) follow. These functions are the contract
+# of musica_sim_ensemble_covariance (include/musica.h).
+COV_KEYS = mp.COV_METRICS + mp.COV_INTEGERS   # ensemble_covariance adds "table" and "tile_tables"; a study row's dicts add "nps_radial" and "hf_fraction"
+
+
+def _covariance_geometry(shape, region, radius):
+    """Raises ValueError exactly where musica_sim_ensemble_track refuses a region on geometry; returns (ax, ay, w, h) and the radius as
+    ints. region: (ax, ay, w, h), or a query's (ax, ay, bx, by, w, h), whose bx, by only have to stay inside the plane."""
+    region = tuple(int(v) for v in region)
+    if len(region) == 6:
+        ax, ay, bx, by, w, h = region
+    else:
+        ax, ay, w, h = region
+        bx, by = ax, ay
+    radius = int(radius)
+    if not 1 <= radius <= mp.SIM_MAX_RADIUS:
+        raise ValueError("radius %d out of range [1, %d]" % (radius, mp.SIM_MAX_RADIUS))
+    if w < 7 or h < 7:
+        raise ValueError("region %d x %d is smaller than 7 x 7" % (w, h))
+    if min(ax, ay, bx, by) < 0 or max(ax, bx) + w > shape[1] or max(ay, by) + h > shape[0]:
+        raise ValueError("region (%d, %d) / (%d, %d) + %d x %d leaves the %d x %d plane" % (ax, ay, bx, by, w, h, shape[1], shape[0]))
+    if ax < radius or ax + w + radius > shape[1] or ay + h + radius > shape[0]:
+        raise ValueError("the window (%d, %d) + %d x %d grown by the radius %d (left, right, down) leaves the %d x %d plane" % (ax, ay, w, h, radius, shape[1], shape[0]))
+    if 65025 * mp.SIM_ENSEMBLE_MAX ** 2 * w * h >= 2 ** 63:
+        raise ValueError("65025 * %d^2 * %d * %d does not fit 63 bits" % (mp.SIM_ENSEMBLE_MAX, w, h))
+    return (ax, ay, w, h), radius
+
+
+def covariance_summary(table, realisations, pixels):
+    """The doubles of a covariance result from its exact (R + 1, 2 R + 1) table C(d) (row dy, column dx + R), one IEEE operation each in
+    include/musica.h's order, every integer converted to double first, with c00, pixels, realisations and radius. The device and the
+    host studies both call this, so they agree to the last bit."""
+    table = np.asarray(table)
+    if table.ndim != 2 or table.shape[0] < 2 or table.shape[1] != 2 * table.shape[0] - 1:
+        raise ValueError("expected an (R + 1, 2 R + 1) table, got %r" % (table.shape,))
+    r, k, n = table.shape[0] - 1, int(realisations), int(pixels)
+    c00 = int(table[0, r])
+    half = 0.0
+    for dy in range(r + 1):
+        for dx in range(-r if dy else 1, r + 1):
+            half += float(int(table[dy, dx + r]))
+    return {"noise_var": 0.0 if k == 1 else float(c00) / float(k * (k - 1) * n),
+            "rho_x": 0.0 if c00 == 0 else float(int(table[0, r + 1])) / float(c00),
+            "rho_y": 0.0 if c00 == 0 else float(int(table[1, r])) / float(c00),
+            "corr_area": 1.0 if c00 == 0 else (float(c00) + 2.0 * half) / float(c00),
+            "c00": c00, "pixels": n, "realisations": k, "radius": r}
+
+
+def ensemble_covariance(outs, region, radius):
+    """musica_sim_ensemble_covariance's numbers of one tracked region, restated: outs a (K, H, W) stack of uint8 outputs (the
+    realisations), region = (ax, ay, w, h) or a query's (ax, ay, bx, by, w, h). For dy = 0 .. R and dx = -R .. R, per region pixel in
+    int64, K sum_k a_k(p) a_k(p + d) - S1(p) S1(p + d), summed per 64 x 64 tile of the region (int64: a tile's |C| <= 4096 * 65025 K^2 <
+    2^58), the region's totals as Python ints over the tiles. Returns the COV_KEYS dict (covariance_summary) plus "table":
+    (R + 1, 2 R + 1) int64, row dy, column dx + R, and "tile_tables": (tiles_y, tiles_x, R + 1, 2 R + 1) int64. ValueError where the C
+    calls refuse: no or more than SIM_ENSEMBLE_MAX realisations, a radius outside 1 .. 16, w < 7 or h < 7, a region that leaves the
+    plane, a window that, grown by the radius to the left, to the right and downwards, leaves it, 65025 * 1024^2 w h >= 2^63."""
+    outs = np.asarray(outs)
+    if outs.ndim != 3 or outs.dtype != np.uint8:
+        raise ValueError("ensemble_covariance needs a (K, H, W) uint8 stack, got %r %s" % (outs.shape, outs.dtype))
+    k = outs.shape[0]
+    if not 1 <= k <= mp.SIM_ENSEMBLE_MAX:
+        raise ValueError("%d realisations out of range [1, %d]" % (k, mp.SIM_ENSEMBLE_MAX))
+    (ax, ay, w, h), r = _covariance_geometry(outs.shape[1:], region, radius)
+    t, s = mp.SIM_TILE, 2 * r + 1
+    ny, nx = (h + t - 1) // t, (w + t - 1) // t
+    a = outs.astype(np.int64)
+    s1 = a.sum(axis=0)
+    ca, c1 = a[:, ay:ay + h, ax:ax + w], s1[ay:ay + h, ax:ax + w]
+    tile_tables = np.empty((ny, nx, r + 1, s), dtype=np.int64)
+    for dy in range(r + 1):
+        for dx in range(-r, r + 1):
+            shifted = (slice(ay + dy, ay + dy + h), slice(ax + dx, ax + dx + w))
+            c = k * (ca * a[(slice(None),) + shifted]).sum(axis=0) - c1 * s1[shifted]
+            tile_tables[:, :, dy, dx + r] = np.add.reduceat(np.add.reduceat(c, np.arange(0, h, t), axis=0), np.arange(0, w, t), axis=1)
+    table = np.array([[sum(int(x) for x in tile_tables[:, :, dy, j].ravel()) for j in range(s)] for dy in range(r + 1)], dtype=np.int64)
+    out = covariance_summary(table, k, w * h)
+    out.update(tiles_x=nx, tiles_y=ny, table=table, tile_tables=tile_tables)
+    return out
+
+
+def covariance_symmetric(table):
+    """The (S, S) float64 table over dy, dx = -R .. R (row dy + R, column dx + R) of a half-plane table: C(-d) = C(d), the row dy = 0
+    taken from its entries with dx >= 0."""
+    table = np.asarray(table)
+    r = table.shape[0] - 1
+    sym = np.empty((2 * r + 1,) * 2, dtype=np.float64)
+    sym[r + 1:] = table[1:]
+    sym[:r] = table[1:][::-1, ::-1]
+    sym[r, r:] = table[0, r:]
+    sym[r, :r] = table[0, r + 1:][::-1]
+    return sym
+
+
+def noise_power_spectrum(table, realisations, pixels):
+    """The noise power spectrum of a covariance table (Wiener-Khinchin), host only: N[v][u] = sum over d of C_sym(d)
+    cos(2 pi (u dx + v dy) / S) / (K (K - 1) n) for u, v = 0 .. S - 1, (S, S) float64, the zero frequency at [0][0]. The sum of
+    cosines is taken as cos cos - sin sin with the phases' integers reduced mod S first. All zero when K == 1."""
+    sym = covariance_symmetric(table)
+    s, k, n = sym.shape[0], int(realisations), int(pixels)
+    if k == 1:
+        return np.zeros((s, s), dtype=np.float64)
+    d = np.arange(s) - s // 2
+    phase = 2.0 * np.pi * ((np.arange(s)[:, None] * d[None, :]) % s) / s     # [frequency][lag]
+    co, si = np.cos(phase), np.sin(phase)
+    return (co @ sym @ co.T - si @ sym @ si.T) / float(k * (k - 1) * n)
+
+
+def _nps_radius(s):
+    d = np.arange(s) - s // 2
+    return np.hypot(d[:, None], d[None, :])
+
+
+def nps_radial(nps):
+    """The mean of the centred spectrum (np.fft.fftshift) over the frequencies of rounded integer radius 0 .. R: a list of R + 1 floats."""
+    nps = np.asarray(nps, dtype=np.float64)
+    rad = np.rint(_nps_radius(nps.shape[0])).astype(np.int64)
+    c = np.fft.fftshift(nps)
+    return [float(c[rad == i].mean()) for i in range(nps.shape[0] // 2 + 1)]
+
+
+def nps_hf_fraction(nps):
+    """The share of the spectrum's sum at radius > R / 2 of the centred spectrum (0 for a spectrum that sums to 0). White noise gives
+    the share of such frequencies among the S^2: nps_hf_fraction(np.ones((S, S)))."""
+    nps = np.asarray(nps, dtype=np.float64)
+    total = float(nps.sum())
+    if total == 0.0:
+        return 0.0
+    return float(np.fft.fftshift(nps)[_nps_radius(nps.shape[0]) > (nps.shape[0] // 2) / 2.0].sum()) / total
+
+
+hf_fraction = nps_hf_fraction
+
+
+def covariance_row(table, realisations, w, h):
+    """A study row's covariance dict of one region from its exact table: COV_KEYS, then "nps_radial" and "hf_fraction"."""
+    t = mp.SIM_TILE
+    d = covariance_summary(table, realisations, int(w) * int(h))
+    d.update(tiles_x=(int(w) + t - 1) // t, tiles_y=(int(h) + t - 1) // t)
+    out = {k: d[k] for k in COV_KEYS}
+    nps = noise_power_spectrum(table, realisations, int(w) * int(h))
+    out["nps_radial"], out["hf_fraction"] = nps_radial(nps), nps_hf_fraction(nps)
+    return out
+
+
+def nps_map(table, realisations, pixels):
+    """The centred spectrum as an (S, S) uint8 image: log(1 + max(N, 0)) scaled so that its largest value is 255, rounded."""
+    v = np.log1p(np.maximum(np.fft.fftshift(noise_power_spectrum(table, realisations, pixels)), 0.0))
+    top = float(v.max())
+    return np.zeros(v.shape, dtype=np.uint8) if top == 0.0 else np.rint(255.0 * v / top).astype(np.uint8)

@@ -1,0 +1,243 @@
+"""What a study leaves on disk: the reference's CSV files (script.py:223-330) and the files of the study's later options, one table
+entry each, and the 8-bit BMP maps of the tile tables. harness re-exports every name."""
+import csv
+import os
+
+import numpy as np
+
+from . import processing as mp
+from .metrics import SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
+
+# ---- the CSV files' headers ---------------------------------------------------------------------
+CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
+              'altered vs reference mse', 'altered vs reference ssim', 'altered vs reference histogram distance',
+              'normalized altered vs reference mse', 'normalized altered vs reference ssim',
+              'normalized altered vs reference histogram distance']
+
+REF_CSV_HEADER = ['raw file', 'mse similarity', 'ssim similarity', 'histogram distance']   # ref_similarities.csv (script.py:285-290)
+TONE_CSV_NAMES = ('mutual information', 'normalized mutual information', 'correlation ratio', 'tone-matched mse', 'tone-matched ssim')   # JOINT_METRICS' order
+TONE_CSV_GROUPS = (('direct_tone', 'altered vs unaltered'), ('registered_tone', 'registered vs unaltered'),
+                   ('reference_tone', 'altered vs reference'), ('registered_reference_tone', 'registered vs reference'))
+
+SHIFT_CSV_NAMES = ('dx', 'dy', 'sub dx', 'sub dy', 'mse at zero', 'mse at best', 'tiles', 'tiles off')   # SHIFT_KEYS' order
+SHIFT_CSV_GROUPS = (('direct_shift', 'direct'), ('registered_shift', 'registered'))
+SHIFT_CSV_HEADER = ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in SHIFT_CSV_GROUPS for m in SHIFT_CSV_NAMES]   # displacement.csv
+
+SCALE_CSV_GROUPS = (('direct_scales', 'altered vs unaltered'), ('registered_scales', 'registered vs unaltered'),
+                    ('reference_scales', 'altered vs reference'), ('registered_reference_scales', 'registered vs reference'))
+SCALE_CSV_METRICS = ("ssim", "cs", "mse")   # per scale 0 .. 4, behind ms_ssim and scales
+
+ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
+ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
+ENSEMBLE_CSV_HEADER = ['raw file', 'alteration', 'realisations'] + ['%s %s' % (g, m) for g in ("direct", "registered") for _, m in ENSEMBLE_CSV_NAMES] + \
+                      ['per-realisation %s %s' % (m, w) for m in ENSEMBLE_CSV_METRICS for w in ("mean", "std")]   # ensemble.csv
+
+COV_CSV_NAMES = (("noise_var", "noise var"), ("rho_x", "rho x"), ("rho_y", "rho y"), ("corr_area", "correlation area"), ("hf_fraction", "hf fraction"))
+
+
+def covariance_csv_header(radius):
+    """noise_covariance.csv of a study with covariance=radius: the groups' numbers, then the radial spectrum of the direct group."""
+    return ['raw file', 'alteration', 'realisations', 'radius'] + ['%s %s' % (g, m) for g in ("direct", "registered") for _, m in COV_CSV_NAMES] + \
+           ['direct nps radius %d' % i for i in range(int(radius) + 1)]
+
+
+def scale_csv_header(with_reference):
+    """scale_robustness.csv's columns: per group ms_ssim, scales, then ssim, cs and mse of scales 0 .. 4; the two vendor groups only for
+    studies that have a vendor image."""
+    return ['raw file', 'alteration'] + [c for _, g in SCALE_CSV_GROUPS[:4 if with_reference else 2] for c in
+                                         ['%s ms-ssim' % g, '%s scales' % g] +
+                                         ['%s %s scale %d' % (g, m, s) for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)]]
+
+
+def _scale_csv_cells(t):
+    if t is None:
+        return [""] * (2 + len(SCALE_CSV_METRICS) * mp.SIM_MAX_SCALES)
+    return [t["ms_ssim"], t["scales"]] + [t[m][s] if s < t["scales"] else "" for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)]
+
+
+def tone_csv_header(with_reference):
+    """tone_robustness.csv's columns: the five JOINT_METRICS per group, the two vendor groups only for studies that have a vendor image."""
+    return ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in TONE_CSV_GROUPS[:4 if with_reference else 2] for m in TONE_CSV_NAMES]
+
+
+def normalized_vs_reference(ref, ovd):
+    """m_sim_alt's three normalised values (script.py:272-274): ref_mse / ovd_mse, ref_ssim / ovd_ssim and
+    (ref_hist - ovd_hist) / (1 - ovd_hist), with ovd the unaltered result vs the vendor image. IEEE f64 division: a zero denominator
+    gives inf or nan (the reference would raise ZeroDivisionError and stop the study)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return [float(np.float64(ref["mse"]) / np.float64(ovd["mse"])), float(np.float64(ref["ssim"]) / np.float64(ovd["ssim"])),
+                float((np.float64(ref["hist_distance"]) - ovd["hist_distance"]) / (1.0 - np.float64(ovd["hist_distance"])))]
+
+
+# ---- the tables' parts ----------------------------------------------------------------------------
+SIM_CSV_KEYS = ("mse", "ssim", "hist_distance")   # the reference's three similarities
+
+
+def _cells(d, keys):
+    """The cells of an optional dict: its values under `keys`, or as many empty cells."""
+    return [""] * len(keys) if d is None else [d[k] for k in keys]
+
+
+def _write_csv(out_dir, name, header, lines):
+    with open(os.path.join(out_dir, name), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(header)
+        w.writerows(lines)
+
+
+def _unaltered(r):
+    return r["alteration"] == "unaltered"
+
+
+def _ovd(rows):
+    """The study's unaltered result vs the vendor image (the reference's m_sim_ovd), None for a study without one."""
+    return next((r.get("reference") for r in rows if _unaltered(r)), None)
+
+
+def _lines(studies, cells):
+    """One CSV line per row of the studies: the raw file, the alteration, then cells(row, the study's _ovd); none where that is None."""
+    for raw_name, rows in studies:
+        ovd = _ovd(rows)
+        for r in rows:
+            c = cells(r, ovd)
+            if c is not None:
+                yield [raw_name, r["alteration"]] + c
+
+
+def _ref_columns(ref, ovd):
+    return [""] * 6 if ovd is None else _cells(ref, SIM_CSV_KEYS) + normalized_vs_reference(ref, ovd)
+
+
+def _ensemble_cells(e):
+    if e is None:
+        return None
+    return [e["realisations"]] + [c for key in ("direct", "registered") for c in _cells(e[key], [k for k, _ in ENSEMBLE_CSV_NAMES])] + \
+           [e["per_realisation"][w][k] for k in mp.SIM_METRICS for w in ("mean", "std")]
+
+
+def _covariance_cells(e, radius):
+    cov = e["covariance"]
+    return [e["realisations"], radius] + [c for key in ("direct", "registered") for c in _cells(cov[key], [k for k, _ in COV_CSV_NAMES])] + \
+           list(cov["direct"]["nps_radial"])
+
+
+def write_studies_csvs(studies, out_dir, mean_cnr=True):
+    """The reference's output files for several raw images: `studies` is a list of (raw_name, rows) pairs (run_study's rows), written
+    in order into one direct_robustness.csv / reg_based_robustness.csv with the reference's column layout (script.py:223-330), plus
+    mean_cnr.csv (what test/mean_cnr/script.py reports per alteration).
+
+    The six "vs reference" columns compare with the vendor-processed image. For a study run with one (rows[0] has "reference"): the
+    altered result vs that image (reg_based_robustness.csv: the registered crops), then normalized_vs_reference against the study's
+    full-image unaltered-vs-vendor values, as m_sim_alt and m_sim_norm_alt do; ref_similarities.csv gets one row of those values per
+    such study and is written only when there is one. Studies without a vendor image leave the six columns empty.
+
+    Studies run with tone=True (rows[0] has "direct_tone") also get tone_robustness.csv: one line per row, the unaltered one included
+    (with a vendor image it carries the unaltered-vs-vendor numbers), the five JOINT_METRICS of the direct and of the registered
+    comparison, then, when any study has a vendor image, of the two comparisons with it. Cells without a comparison are empty. The
+    other files are written as without it.
+
+    Studies run with a displacement radius (rows[0] has "direct_shift") also get displacement.csv: one line per row, the unaltered one
+    included, the SHIFT_KEYS of the direct and of the registered comparison; cells without a comparison are empty.
+
+    Studies run with scales (rows[0] has "direct_scales") also get scale_robustness.csv (scale_csv_header): one line per row, the
+    unaltered one included; cells without a comparison, and of scales beyond a comparison's count, are empty.
+
+    Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
+    mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
+    and standard deviation over the realisations of the five similarity metrics.
+
+    Studies run with covariance=R (their noise rows' "ensemble" has "covariance") also get noise_covariance.csv
+    (covariance_csv_header): one line per noise row, K, R, the noise variance, rho x, rho y, correlation area and high-frequency
+    fraction of the direct and of the registered region (empty without one), then the radial noise power spectrum of the direct one."""
+    os.makedirs(out_dir, exist_ok=True)
+    having = lambda key: [(raw_name, rows) for raw_name, rows in studies if rows and key in rows[0]]   # noqa: E731
+    toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
+    tone_groups = TONE_CSV_GROUPS[:4 if any("reference_tone" in rows[0] for _, rows in toned) else 2]
+    scale_groups = SCALE_CSV_GROUPS[:4 if any("reference_scales" in rows[0] for _, rows in scored) else 2]
+    covs = [(raw_name, [r for r in rows if r.get("ensemble") and "covariance" in r["ensemble"]]) for raw_name, rows in ensembles]
+    covs = [(raw_name, rows) for raw_name, rows in covs if rows]
+    radius = covs[0][1][0]["ensemble"]["covariance"]["direct"]["radius"] if covs else 0
+    # file name, header, the studies it covers, cells(row, ovd) behind the raw file and the alteration (None: no line for this row)
+    tables = [
+        ("direct_robustness.csv", CSV_HEADER, studies,
+         lambda r, ovd: None if _unaltered(r) else _cells(r["direct"], SIM_CSV_KEYS) + _ref_columns(r.get("reference"), ovd)),
+        ("reg_based_robustness.csv", CSV_HEADER, studies,
+         lambda r, ovd: None if _unaltered(r) or r["registered"] is None else
+         _cells(r["registered"], SIM_CSV_KEYS) + _ref_columns(r.get("registered_reference"), ovd)),
+        ("mean_cnr.csv", ["raw file", "alteration", "mean cnr"], studies if mean_cnr else None, lambda r, ovd: [r["mean_cnr"]]),
+        ("tone_robustness.csv", tone_csv_header(len(tone_groups) == 4), toned or None,
+         lambda r, ovd: [c for key, _ in tone_groups for c in _cells(r.get(key), mp.JOINT_METRICS)]),
+        ("displacement.csv", SHIFT_CSV_HEADER, having("direct_shift") or None,
+         lambda r, ovd: [c for key, _ in SHIFT_CSV_GROUPS for c in _cells(r.get(key), SHIFT_KEYS)]),
+        ("scale_robustness.csv", scale_csv_header(len(scale_groups) == 4), scored or None,
+         lambda r, ovd: [c for key, _ in scale_groups for c in _scale_csv_cells(r.get(key))]),
+        ("ensemble.csv", ENSEMBLE_CSV_HEADER, ensembles or None, lambda r, ovd: _ensemble_cells(r["ensemble"])),
+        ("noise_covariance.csv", covariance_csv_header(radius), covs or None, lambda r, ovd: _covariance_cells(r["ensemble"], radius)),
+    ]
+    for name, header, covered, cells in tables:
+        if covered is not None:
+            _write_csv(out_dir, name, header, _lines(covered, cells))
+    ovds = [[raw_name] + _cells(_ovd(rows), SIM_CSV_KEYS) for raw_name, rows in studies if _ovd(rows) is not None]
+    if ovds:
+        _write_csv(out_dir, "ref_similarities.csv", REF_CSV_HEADER, ovds)
+
+
+def _write_maps(studies, out_dir, images):
+    """images(row): the (name, uint8 image) pairs of a row, none for a row without them. Writes <raw>_<alteration>_<name>.bmp for each and
+    returns the paths."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for raw_name, rows in studies:
+        stem = os.path.splitext(os.path.basename(raw_name.replace("\\", "/")))[0]
+        for r in rows:
+            for what, img in images(r):
+                path = os.path.join(out_dir, "%s_%s_%s.bmp" % (stem, r["alteration"], what))
+                if not mp.write_bmp_gray(path, img):
+                    raise RuntimeError("writing %s failed: %s" % (path, mp.last_error()))
+                written.append(path)
+    return written
+
+
+def _ensemble_images(r):
+    e = r.get("ensemble")
+    if e is None or "tile_tables" not in e["direct"]:
+        return ()
+    return zip(("bias", "noise"), ensemble_maps(e["direct"]["tile_tables"], *e["direct"]["size"], e["realisations"]))
+
+
+def _covariance_images(r):
+    e = r.get("ensemble")
+    g = e["covariance"]["direct"] if e and "covariance" in e else None
+    return () if g is None or "table" not in g else (("nps", nps_map(g["table"], g["realisations"], g["pixels"])),)
+
+
+def _displacement_images(r):
+    t = r.get("registered_shift")
+    return () if t is None or "tile_tables" not in t else zip(("rmse", "shift"), displacement_maps(t["tile_tables"], *t["size"]))
+
+
+def write_ensemble_maps(studies, out_dir):
+    """Two 8-bit BMPs per noise row of studies run with ensemble_tiles (ensemble_maps: one pixel per 64 x 64 tile of the full frame):
+    <raw>_<alteration>_bias.bmp, the tile's bias rms against the unaltered result, and <raw>_<alteration>_noise.bmp, its noise rms, in
+    gray levels. Returns the paths written."""
+    return _write_maps(studies, out_dir, _ensemble_images)
+
+
+def write_covariance_maps(studies, out_dir):
+    """One 8-bit BMP per noise row of studies run with covariance_tiles: <raw>_<alteration>_nps.bmp, the centred noise power spectrum of
+    the direct region (nps_map: S x S pixels, the zero frequency in the middle, log-scaled). Returns the paths written."""
+    return _write_maps(studies, out_dir, _covariance_images)
+
+
+def write_displacement_maps(studies, out_dir):
+    """Two 8-bit BMPs per registered row of studies run with displacement_tiles (displacement_maps: one pixel per 64 x 64 tile):
+    <raw>_<alteration>_rmse.bmp, the tile RMSE at the zero shift, and <raw>_<alteration>_shift.bmp, the length of the tile's best shift.
+    Returns the paths written."""
+    return _write_maps(studies, out_dir, _displacement_images)
+
+
+
+def write_study_csvs(rows, out_dir, raw_name, mean_cnr=True):
+    """write_studies_csvs for one raw image: direct_robustness.csv / reg_based_robustness.csv with the reference's column layout,
+    mean_cnr.csv, and (rows of a study with a vendor image) the "vs reference" columns and ref_similarities.csv."""
+    write_studies_csvs([(raw_name, rows)], out_dir, mean_cnr=mean_cnr)

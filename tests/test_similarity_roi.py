@@ -1,5 +1,7 @@
 """The registration geometry stated as device-side comparison regions (harness.roi_*): each region selects exactly what the
-reference's crops (harness.register_*) return, so a registered comparison on the device scores the same pixels as on the host."""
+reference's crops (harness.register_*) return, so a registered comparison on the device scores the same pixels as on the host. The
+host study itself scores by region (the output cropped by the a side, the reference plane, moved where the row moves it, by the b
+side), so it rests on this equivalence for every kind of row."""
 import numpy as np
 import pytest
 
@@ -70,6 +72,37 @@ def test_rotation_roi_selects_the_register_rotation_crop(shape):
         assert (ax, ay) == (bx, by) and (h, w) == ca.shape == cu.shape
         assert np.array_equal(a[ay:ay + h, ax:ax + w], ca)
         assert np.array_equal(H.rotated_reference(u, d)[by:by + h, bx:bx + w], cu)
+
+
+@pytest.mark.parametrize("n", [12, 64, 101])
+def test_symmetry_roi_selects_the_register_symmetry_planes(n):
+    rng = np.random.default_rng(4)
+    a = rng.integers(0, 256, size=(n, n)).astype(np.uint8)
+    u = rng.integers(0, 256, size=(n, n)).astype(np.uint8)
+    roi = H.roi_symmetry(a.shape)
+    assert roi == (0, 0, 0, 0, n, n)
+    for e in range(8):
+        _check(roi, a, H.apply_symmetry(u, e), H.register_symmetry(a, u, e))
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
+@pytest.mark.parametrize("n", [12, 22, 23, 24, 64, 101])
+def test_blur_roi_selects_the_register_blur_crop(n, dtype):
+    """Radius 8 leaves sides of 6, 7 and 8 at n = 22, 23 and 24: no region under 7, and the study's guard (8) between the other two."""
+    rng = np.random.default_rng(6)
+    a = rng.integers(0, 256, size=(n, n)).astype(dtype)
+    u = rng.integers(0, 256, size=(n, n)).astype(dtype)
+    for r in range(1, 9):
+        got = H.register_blur(a, u, r)
+        roi = H.roi_blur(a.shape, r)
+        side = max(n - 2 * r, 0)
+        assert got[0].shape == got[1].shape == (side, side)
+        assert (roi is None) == (side < 7)
+        if roi is not None:
+            assert roi == (r, r, r, r, side, side)
+            _check(roi, a, H.binomial_blur(u, r), got)
+        host = bool(got[0].size and min(got[0].shape) >= 8)
+        assert host == (roi is not None and min(roi[4], roi[5]) >= 8), (n, r)
 
 
 def test_study_guard_agrees_with_roi():

@@ -1,0 +1,186 @@
+"""The device branch of harness.run_study, on a CPU: a recording stand-in for runner.proc and for the ensemble context logs every
+sim_* / alter_* / execute* call (arrays reduced to shape and dtype) and answers with canned results of the right shape, each number
+different from every other, so the rows also say which result went under which key. Three studies at side 84 (a 64 x 64 output), one
+value per grid, are compared with tests/golden/study_calls.json.
+
+The golden file was recorded with record() below driving the harness.py of the commit BEFORE run_study was split into a row routine
+and two scorers (never the code under test), with one edit by hand: in row 0 the sim_displace call was moved behind the
+sim_multiscale calls, the order every other row already had."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import harness as H
+from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "study_calls.json")
+SIDE = 84
+OUT = SIDE - 2 * H.PROCESSING_MARGIN
+ENSEMBLE_INPUTS = ("sq_bias_sum", "var_sum", "sq_err_sum", "bias_sum", "abs_bias_max", "var_max", "realisations")
+
+
+def _plain(v):
+    """JSON's view of a call's arguments or of a row: arrays as their shape and dtype, tuples as lists, numpy scalars as Python's."""
+    if isinstance(v, np.ndarray):
+        return {"shape": list(v.shape), "dtype": str(v.dtype)}
+    if isinstance(v, dict):
+        return {str(k): _plain(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    if isinstance(v, np.generic):
+        return v.item()
+    return v
+
+
+KINDS = ("stats", "compare", "joint", "multiscale")
+
+
+class RecordingProc:
+    """Stands in for a MusicaProcessing context: `name` tells the runner's context ("proc") from the ensemble's ("eproc") in the log."""
+
+    def __init__(self, log, name, batch=1):
+        self.log, self.name, self.batch = log, name, batch
+        self.plane = np.random.default_rng(5).integers(0, 256, size=(OUT, OUT)).astype(np.uint8)
+        self.counts = {}      # per kind of call, the source of the canned numbers: they do not depend on the order of unlike calls
+        self.tracked = 0      # regions of the last sim_ensemble_track
+
+    def ordinal(self, kind):
+        self.counts[kind] = self.counts.get(kind, 0) + 1
+        return self.counts[kind]
+
+    def number(self, kind):
+        return KINDS.index(kind) + self.ordinal(kind) / 4096.0   # exact in binary and in JSON; no two alike
+
+    def __getattr__(self, call):
+        if not call.startswith(("sim_", "alter_", "execute")):
+            raise AttributeError(call)
+
+        def method(*args, **kwargs):
+            self.log.append([self.name, call, _plain(args), _plain(kwargs)])
+            return getattr(self, "_" + call, lambda *a, **k: True)(*args, **kwargs)
+        return method
+
+    def out_pixels(self, image_index=0):
+        return self.plane.copy()
+
+    def sync(self):
+        pass
+
+    def stats(self, image_index=0):
+        class Stats:
+            mean_cnr = self.number("stats")
+        return Stats
+
+    def _sim_get_reference(self, slot):
+        return self.plane.copy()
+
+    def _sim_compare(self, queries):
+        return [dict({k: self.number("compare") for k in mp.SIM_METRICS}, pixels=q[6] * q[7]) for q in queries]
+
+    def _sim_joint(self, queries, tables=False):
+        return [dict({k: self.number("joint") for k in mp.JOINT_METRICS if k != "tone_ssim"}, tone_lut=np.arange(256, dtype=np.uint8)) for _ in queries]
+
+    def _sim_multiscale(self, queries, scales):
+        return [dict({k: [self.number("multiscale") for _ in range(scales)] for k in mp.SCALE_METRICS}, ms_ssim=self.number("multiscale"), scales=scales) for _ in queries]
+
+    def _sim_displace(self, queries, radius, tables=False, tiles=False):
+        s = 2 * radius + 1
+        out = []
+        for q in queries:
+            n = self.ordinal("displace")
+            table = np.arange(s * s, dtype=np.uint64).reshape(s, s) * 7 + n    # the best shift is (-radius, -radius)
+            tx, ty = (q[6] + mp.SIM_TILE - 1) // mp.SIM_TILE, (q[7] + mp.SIM_TILE - 1) // mp.SIM_TILE
+            out.append({"table": table, "tiles_x": tx, "tiles_y": ty, "tiles_off": n % 3})
+            if tiles:
+                out[-1]["tile_tables"] = np.zeros((ty, tx, s, s), dtype=np.uint32)
+        return out
+
+    def _sim_ensemble_track(self, regions, radius):
+        self.tracked, self.radius = len(regions), radius
+
+    def _sim_ensemble_result(self, queries, tiles=False):
+        out = []
+        for q in queries:
+            n = self.ordinal("ensemble")
+            out.append(dict(zip(ENSEMBLE_INPUTS, (6 * n, 12 * n, 6 * n, n, 5, 9, 3))))    # K sq_err_sum == sq_bias_sum + var_sum, as ensemble_summary demands
+            if tiles:
+                out[-1]["tile_tables"] = np.zeros(((q[7] + mp.SIM_TILE - 1) // mp.SIM_TILE, (q[6] + mp.SIM_TILE - 1) // mp.SIM_TILE, 2), dtype=np.uint64)
+        return out
+
+    def _sim_ensemble_covariance(self, tables=True, tiles=False):
+        out = []
+        for _ in range(self.tracked):
+            table = np.zeros((self.radius + 1, 2 * self.radius + 1), dtype=np.int64)
+            table[0, self.radius] = 6 * self.ordinal("covariance")    # white noise: its spectrum is flat, whatever the platform's cosines
+            out.append({"table": table, "realisations": 3})
+            if tiles:
+                out[-1]["tile_tables"] = np.zeros((1, 1) + table.shape, dtype=np.int64)
+        return out
+
+
+def _runner(log, device_alterations, batch=2):
+    """A harness.Runner around two recording contexts: its own methods run, nothing of the library is loaded."""
+    r = H.Runner.__new__(H.Runner)
+    r.n, r.levels, r.device, r.use_cli = SIDE, 0, 0, False
+    r.device_alterations, r.device_metrics, r.ensemble_batch = device_alterations, True, batch
+    r.proc, r.ensemble_proc = RecordingProc(log, "proc"), RecordingProc(log, "eproc", batch)
+    return r
+
+
+GRIDS = dict(shutters=[8], translations=[52], rotations=[9], sigmas=[16.0], factors=[0.05])   # t = 52 leaves a registered side of 12: one scale
+STUDIES = {
+    "everything": (True, dict(GRIDS, vendor=True, tone=True, scales=2, displacement=2, displacement_tiles=True, symmetries=[1], blurs=[2],
+                              ensemble=3, ensemble_tiles=True, covariance=2, covariance_tiles=True)),
+    "device_metrics": (False, dict(GRIDS, vendor=True, symmetries=[4], blurs=[1])),
+    "no_region": (True, dict(GRIDS, translations=[60], vendor=True, tone=True, scales=2, displacement=2)),   # 60 > 64 - 8: nothing to register
+}
+
+
+def record(name, harness=H):
+    """{"calls": the log, "rows": run_study's rows} of one of STUDIES, both as JSON holds them."""
+    device_alterations, args = STUDIES[name]
+    rng = np.random.default_rng(11)
+    raw = rng.integers(0, 4096, size=(SIDE, SIDE)).astype(np.uint16)
+    if args.get("vendor"):
+        args = dict(args, vendor=rng.integers(0, 65536, size=(OUT, OUT)).astype(np.uint16))
+    log = []
+    rows = harness.run_study(raw, _runner(log, device_alterations), rng=np.random.default_rng(0), **args)
+    return json.loads(json.dumps({"calls": log, "rows": [[[k, _plain(v)] for k, v in row.items()] for row in rows]}))
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("name", sorted(STUDIES))
+def test_the_device_study_makes_the_recorded_calls(name, golden):
+    got, want = record(name), golden[name]
+    for i, (g, w) in enumerate(zip(got["calls"], want["calls"])):
+        assert g == w, "call %d of %s" % (i, name)
+    assert len(got["calls"]) == len(want["calls"])
+    assert [[k for k, _ in row] for row in got["rows"]] == [[k for k, _ in row] for row in want["rows"]]   # the keys and their order
+    assert got["rows"] == want["rows"]
+
+
+def test_the_studies_cover_what_they_are_meant_to(golden):
+    calls = {name: [(c[0], c[1]) for c in golden[name]["calls"]] for name in STUDIES}
+    every = calls["everything"]
+    for call in ("sim_capture", "sim_set_vendor_reference", "sim_compare", "sim_joint", "sim_remap_reference", "sim_multiscale", "sim_displace",
+                 "sim_rotate_reference", "sim_transform_reference", "sim_blur_reference", "alter_symmetry", "alter_blur", "execute_device"):
+        assert ("proc", call) in every, call
+    for call in ("sim_ensemble_reset", "sim_ensemble_track", "sim_ensemble_add", "sim_ensemble_result", "sim_ensemble_covariance", "execute_device"):
+        assert ("eproc", call) in every, call
+    adds = [c[2] for c in golden["everything"]["calls"] if c[1] == "sim_ensemble_add"]
+    assert adds[:2] == [[0, 2], [0, 1]]                                       # K = 3 on a batch of 2: chunks of 2 and 1
+    counts = [c[2][1] for c in golden["everything"]["calls"] if c[1] == "sim_multiscale"]
+    assert [1, 2] in [counts[i:i + 2] for i in range(len(counts))]            # a row with two scale counts: ascending
+    assert [c for _, c in calls["device_metrics"] if c == "sim_set_reference"] == ["sim_set_reference"] * 3   # the rotation, d4 and blur rows
+    assert not any(c.startswith("alter_") or c == "execute_device" for _, c in calls["device_metrics"])
+    t_x = [row for row in golden["no_region"]["rows"] if dict(row)["alteration"] == "t_x_60"][0]
+    assert all(v is None for k, v in t_x if k.startswith("registered"))
+    queries = [len(c[2][0]) for c in golden["no_region"]["calls"] if c[1] == "sim_compare"]
+    assert queries[2] == 4 and queries[4] == 2                                # t_x_60: direct and vendor only; c_sh_8: all four
