@@ -394,6 +394,24 @@ int musica_sim_transform_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t 
  * Refused before any device work: a NULL context, a slot out of range, dst_slot == src_slot, a source slot never written, a radius outside
  * 1 .. MUSICA_BLUR_MAX_RADIUS, an image too small for the margin. Marks dst_slot written; changes no other slot. */
 int musica_sim_blur_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t radius);
+/* ---- magnification: the exact rational zoom (new, not in the reference) ----
+ * harness.zoom(image, (p, q)) is the contract: a square 2-D uint16 or uint8 plane of side n magnified by p / q about its centre,
+ * bilinearly, in integers, with 1 <= q < p <= MUSICA_ZOOM_MAX_P and gcd(p, q) = 1. With D = 2p, for an output index x
+ *   n_x = (2x - (n - 1)) q + (n - 1) p        (>= 0; the source coordinate is n_x / D)
+ *   i_x = n_x div D,   f_x = n_x mod D,   g_x = D - f_x,   i+ = min(i + 1, n - 1)
+ *   out[y, x] = (g_y g_x in[i_y, i_x] + g_y f_x in[i_y, i_x+] + f_y g_x in[i_y+, i_x] + f_y f_x in[i_y+, i_x+] + D^2 / 2) div D^2
+ * ONE rounding, after the full 2-D sum, halves rounded up. The result has the input's type. The weights sum to D^2 <= 4096 and the sum
+ * is at most 65535 * 4096 + 2048 < 2^32, so every intermediate fits u32 and a constant plane is preserved. A zoom above 1 about the
+ * centre reads only inside the plane, so there is no fill value: i_x <= n - 2 except where f_x = 0, and there the clamped neighbour's
+ * weight is 0. Mirroring x -> n - 1 - x maps n_x -> 2p (n - 1) - n_x, so the map commutes exactly with the eight symmetries of the
+ * square; and because 2 (x + 10) - (N - 1) = 2x - (M - 1) for M = N - 20, the zoom of the cropped output plane is the crop of the zoom
+ * of the full frame. The device results are bit-identical to that statement and repeat from call to call (kernels_zoom.hip; DESIGN.md
+ * section 4). */
+#define MUSICA_ZOOM_MAX_P 32
+/* zoom(reference slot `src_slot`, (p, q)) of the (N - 20)^2 u8 plane into `dst_slot` (device to device, on the ctx stream). Refused
+ * before any device work: a NULL context, q = 0, p <= q, p > MUSICA_ZOOM_MAX_P, gcd(p, q) != 1, a slot out of range, dst_slot ==
+ * src_slot, a source slot never written, an image too small for the margin. Marks dst_slot written; changes no other slot. */
+int musica_sim_zoom_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t p, uint32_t q);
 /* (N - 20)^2 bytes of reference slot `slot` to the host (synchronous); the slot must have been written. */
 int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
 
@@ -645,6 +663,11 @@ int musica_alter(musica_ctx* ctx, uint32_t image_index, const musica_alteration*
  * slot. An entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT. Refused before any
  * device work: no source, image_index >= batch, a radius outside 1 .. MUSICA_BLUR_MAX_RADIUS. */
 int musica_alter_blur(musica_ctx* ctx, uint32_t image_index, uint32_t radius);
+/* zoom(source plane, (p, q)) (above, at musica_sim_zoom_reference) into image `image_index` of the input buffer, enqueued on the ctx
+ * stream, with musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step and no reference
+ * slot. An entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT. Refused before any
+ * device work: a NULL context, no source, q = 0, p <= q, p > MUSICA_ZOOM_MAX_P, gcd(p, q) != 1, image_index >= batch. */
+int musica_alter_zoom(musica_ctx* ctx, uint32_t image_index, uint32_t p, uint32_t q);
 /* Test hook: the N x N integer draws of a noise alteration (k of COLLIMATOR / POISSON, for every pixel; the truncated noise of GAUSSIAN),
  * the same numbers musica_alter uses. Synchronous. */
 int musica_alter_draws(musica_ctx* ctx, const musica_alteration* spec, int32_t* dst);

@@ -299,6 +299,11 @@ void launch_symmetry_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n,
 constexpr int kBlurMaxRadius = 8;   // MUSICA_BLUR_MAX_RADIUS
 void launch_blur_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, int radius);
 void launch_blur_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int radius);
+// kernels_zoom.hip: harness.zoom(plane, (p, q)), the exact bilinear magnification by p / q about the centre, of a dense n x n plane into
+// another (the planes must not overlap); any n >= 1, 1 <= q < p <= kZoomMaxP with gcd(p, q) = 1
+constexpr int kZoomMaxP = 32;   // MUSICA_ZOOM_MAX_P
+void launch_zoom_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, int p, int q);
+void launch_zoom_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int p, int q);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -1,7 +1,7 @@
 // musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the four query calls
 // (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip), the ensemble accumulators
 // (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
+// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
@@ -62,6 +62,17 @@ static int sim_derive_slot(musica_ctx* c, const char* fn, uint32_t dst_slot, uin
     launch(c->study.slot[src_slot], dst);
     HIP_OK(hipGetLastError());
     c->study.written[dst_slot] = true;
+    return 1;
+}
+
+static_assert(kZoomMaxP == MUSICA_ZOOM_MAX_P, "kernels_zoom.hip's u32 sums hold for the zooms of include/musica.h");
+
+// What both zoom calls refuse about p / q: harness.zoom's 1 <= q < p <= MUSICA_ZOOM_MAX_P in lowest terms.
+static int zoom_check(const char* fn, uint32_t p, uint32_t q) {
+    if (q == 0 || p <= q || p > MUSICA_ZOOM_MAX_P) return fail("%s: zoom %u / %u is not 1 <= q < p <= %d", fn, p, q, MUSICA_ZOOM_MAX_P);
+    uint32_t a = p, b = q;
+    while (b) { const uint32_t r = a % b; a = b; b = r; }
+    if (a != 1) return fail("%s: zoom %u / %u is not in lowest terms (gcd %u)", fn, p, q, a);
     return 1;
 }
 
@@ -166,6 +177,14 @@ int musica_sim_blur_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slo
         c, "musica_sim_blur_reference", dst_slot, src_slot,
         [&] { return radius >= 1 && radius <= MUSICA_BLUR_MAX_RADIUS ? 1 : fail("musica_sim_blur_reference: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS); },
         [&](const uint8_t* src, uint8_t* dst) { launch_blur_u8(c->stream, src, dst, (int)sim_side(c), (int)radius); });
+}
+
+int musica_sim_zoom_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t p, uint32_t q) {
+    if (!c) return fail("musica_sim_zoom_reference: ctx is NULL");
+    if (!zoom_check("musica_sim_zoom_reference", p, q)) return 0;
+    return sim_derive_slot(
+        c, "musica_sim_zoom_reference", dst_slot, src_slot, [] { return 1; },   // nothing more to refuse
+        [&](const uint8_t* src, uint8_t* dst) { launch_zoom_u8(c->stream, src, dst, (int)sim_side(c), (int)p, (int)q); });
 }
 
 int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]) {
@@ -866,6 +885,18 @@ int musica_alter_blur(musica_ctx* c, uint32_t idx, uint32_t radius) {
     CHECK_CTX(c);
     if (!alter_keep_input(c, "musica_alter_blur")) return 0;
     launch_blur_u16(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, (int)radius);   // kernels_blur.hip
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+int musica_alter_zoom(musica_ctx* c, uint32_t idx, uint32_t p, uint32_t q) {
+    if (!c) return fail("musica_alter_zoom: ctx is NULL");
+    if (!c->study.d_alter_src) return fail("musica_alter_zoom: no source plane (musica_alter_set_source)");
+    if (!zoom_check("musica_alter_zoom", p, q)) return 0;
+    CHECK_IMG(c, idx);
+    CHECK_CTX(c);
+    if (!alter_keep_input(c, "musica_alter_zoom")) return 0;
+    launch_zoom_u16(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, (int)p, (int)q);   // kernels_zoom.hip
     HIP_OK(hipGetLastError());
     return 1;
 }

@@ -42,6 +42,9 @@ POISSON_FACTORS = [0.1, 0.05, 0.025, 0.0125, 0.00625]
 SYMMETRIES = (1, 2, 3, 4, 5, 6, 7)
 # not in the reference: the radii of the resolution-loss rows (binomial_blur), rows blur_<r> of a study run with `blurs`
 BLURS = (1, 2, 4, 8)
+# not in the reference: the magnifications p / q of the scale rows (zoom), rows zoom_<p>_<q> of a study run with `zooms`: 1.05, 1.1,
+# 1.25, 1.5 and 2, five strengths as every alteration of the reference's script has
+ZOOMS = ((21, 20), (11, 10), (5, 4), (3, 2), (2, 1))
 
 
 def scaled(values, image_size):
@@ -143,6 +146,33 @@ def binomial_blur(image, radius):
         for k in range(2 * r + 1):
             acc += np.uint64(math.comb(2 * r, k)) * (padded[k:k + acc.shape[0]] if axis == 0 else padded[:, k:k + acc.shape[1]])
     return ((acc + np.uint64(1 << (4 * r - 1))) >> np.uint64(4 * r)).astype(image.dtype)
+
+
+def zoom(image, ratio):
+    """The exact rational zoom of a square 2-D uint16 or uint8 plane of side n (not in the reference's script): magnification by p / q
+    about the plane's centre, bilinear, in integers. ratio = (p, q), integers 1 <= q < p <= ZOOM_MAX_P = 32 with gcd(p, q) = 1, else
+    ValueError before any work. With D = 2p, for an output index x
+        n_x = (2x - (n - 1)) q + (n - 1) p        (>= 0; the source coordinate is n_x / D = (x - c) q / p + c, c = (n - 1) / 2)
+        i_x = n_x div D,   f_x = n_x mod D,   g_x = D - f_x,   i+ = min(i + 1, n - 1)
+        out[y, x] = (g_y g_x in[i_y, i_x] + g_y f_x in[i_y, i_x+] + f_y g_x in[i_y+, i_x] + f_y f_x in[i_y+, i_x+] + D^2 / 2) div D^2
+    ONE rounding, after the full 2-D sum, halves rounded up. The result has the input's dtype. The weights sum to D^2 <= 4096 and the
+    sum is at most 65535 * 4096 + 2048 < 2^32: every intermediate fits u32, and a constant plane is preserved. A zoom above 1 about the
+    centre reads only inside the plane, so there is no fill value: i_x <= n - 2 everywhere except where f_x = 0, and there the clamped
+    neighbour's weight is 0. Mirroring x -> n - 1 - x maps n_x -> 2p (n - 1) - n_x, so the map commutes exactly with all eight
+    apply_symmetry elements. And 2 (x + 10) - (N - 1) = 2x - (M - 1) for M = N - 20: the zoom of the output plane (the full frame
+    cropped by PROCESSING_MARGIN on every side) is the crop of the zoom of the full frame, which is what makes register_zoom meaningful.
+    This is the contract of musica_alter_zoom and musica_sim_zoom_reference (include/musica.h), which are bit-identical to it."""
+    p, q = mp.zoom_ratio(ratio)
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype not in (np.uint16, np.uint8) or not image.size:
+        raise ValueError("zoom needs a non-empty square 2-D uint16 or uint8 plane, got %r %s" % (image.shape, image.dtype))
+    n, d = image.shape[0], 2 * p
+    num = (2 * np.arange(n, dtype=np.int64) - (n - 1)) * q + (n - 1) * p
+    i, f = num // d, (num % d).astype(np.uint64)
+    g, i1 = np.uint64(d) - f, np.minimum(i + 1, n - 1)
+    a = image.astype(np.uint64)
+    top, bottom = (a[r][:, i] * g + a[r][:, i1] * f for r in (i, i1))       # the rows i_y and i_y+, folded along x
+    return ((g[:, None] * top + f[:, None] * bottom + np.uint64(d * d // 2)) // np.uint64(d * d)).astype(image.dtype)
 
 
 # ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
@@ -274,6 +304,17 @@ def roi_blur(shape, radius):
     return _inset((0, 0, 0, 0, shape[1], shape[0]), int(radius))
 
 
+def register_zoom(alt, unalt, ratio):
+    """The whole altered result against the unaltered result magnified like the alteration: a zoom above 1 about the centre needs no
+    fill and crop and zoom commute (zoom), so nothing is cropped."""
+    return alt, zoom(unalt, ratio)
+
+
+def roi_zoom(shape):
+    """The full frame, as the region of a device-side comparison (as roi_symmetry)."""
+    return (0, 0, 0, 0, shape[1], shape[0])
+
+
 # ---- running the pipeline -------------------------------------------------------------------------
 
 class Runner:
@@ -373,7 +414,7 @@ VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a
 
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
-                  scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs):
+                  scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -407,6 +448,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     for r in blurs:
         if not 1 <= r <= mp.BLUR_MAX_RADIUS:
             raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
+    zooms = [mp.zoom_ratio(z) for z in (zooms or ())]
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
@@ -416,7 +458,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
-        covariance_tiles=covariance_tiles, blurs=blurs, keys=keys, device_alterations=device_alterations)
+        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, keys=keys, device_alterations=device_alterations)
 
 
 # One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
@@ -430,7 +472,7 @@ Alteration = collections.namedtuple("Alteration", "name host dev region move noi
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4 and blur rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur and zoom rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -459,6 +501,9 @@ def study_alterations(raw, rng, p, seed, shape, opt):
     for r in opt.blurs:
         yield Alteration("blur_%d" % r, lambda: binomial_blur(raw, r), lambda: p.alter_blur(r), lambda: roi_blur(shape, r),
                          ("sim_blur_reference", binomial_blur, r))
+    for z in opt.zooms:
+        yield Alteration("zoom_%d_%d" % z, lambda: zoom(raw, z), lambda: p.alter_zoom(z), lambda: roi_zoom(shape),
+                         ("sim_zoom_reference", zoom, z))
 
 
 class Scorer:
@@ -624,7 +669,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
-              blurs=None):
+              blurs=None, zooms=None):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -695,10 +740,18 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     "registered" over the frame inset by r (roi_blur) against the unaltered result blurred with the same radius (what a linear,
     shift-invariant processor would not show; None when the inset frame has a side under 8). On the device that reference goes into
     slot 1 and the blurred vendor image into slot 3 (musica_sim_blur_reference). Like the d4 rows they draw nothing from `rng` and take
-    no ordinal; vendor, tone, scales and displacement apply to them as to a d4 row."""
+    no ordinal; vendor, tone, scales and displacement apply to them as to a d4 row.
+
+    zooms: magnifications (p, q) of the scale rows (zoom; ZOOMS for 1.05, 1.1, 1.25, 1.5 and 2), each 1 <= q < p <= ZOOM_MAX_P in lowest
+    terms, else ValueError before any work. None or empty adds nothing. Otherwise rows zoom_<p>_<q> follow the blur_* rows: the raw image
+    magnified by p / q about its centre (on the device: alter_zoom), "direct" against the unaltered result, "registered" over the WHOLE
+    frame (roi_zoom: no fill, nothing to crop) against the unaltered result magnified alike, which a processor that commutes with
+    magnification would reproduce. On the device that reference goes into slot 1 and the magnified vendor image into slot 3
+    (musica_sim_zoom_reference). They draw nothing from `rng` and take no ordinal; vendor, tone, scales and displacement apply to them
+    as to a d4 row."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
-                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs)
+                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -816,6 +869,19 @@ def blur_list(text):
     return radii
 
 
+def zoom_list(text):
+    """--zooms' comma list of magnifications P/Q: 1 <= Q < P <= ZOOM_MAX_P in lowest terms."""
+    import argparse
+    try:
+        zooms = tuple(tuple(int(v) for v in t.split("/")) for t in text.split(","))
+        if not zooms or any(len(z) != 2 for z in zooms):
+            raise ValueError
+        return tuple(mp.zoom_ratio(z) for z in zooms)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError("expected a comma-separated list of magnifications P/Q (1 <= Q < P <= %d, lowest terms), got %r%s"
+                                         % (mp.ZOOM_MAX_P, text, ": %s" % e if str(e) else ""))
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Metamorphic study of raw images (or a seeded phantom) on the HIP MUSICA path")
@@ -839,6 +905,10 @@ def main(argv=None):
     ap.add_argument("--blurs", nargs="?", const=BLURS, default=None, type=blur_list, metavar="R,R,...",
                     help="add the rows blur_<r>: the raw image under the exact binomial blur of radius r (1 .. 8; sigma = sqrt(r / 2) pixels), "
                          "compared directly and, inset by r, with the unaltered result blurred alike; without a list, 1,2,4,8")
+    ap.add_argument("--zooms", nargs="?", const=ZOOMS, default=None, type=zoom_list, metavar="P/Q,P/Q,...",
+                    help="add the rows zoom_<p>_<q>: the raw image magnified by P/Q about its centre (exact integer bilinear; 1 <= Q < P <= 32 "
+                         "in lowest terms), compared directly and, over the whole frame, with the unaltered result magnified alike; without "
+                         "a list, 21/20,11/10,5/4,3/2,2/1")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -917,6 +987,8 @@ def main(argv=None):
         shift_args.update(covariance=args.covariance, covariance_tiles=bool(args.covariance_maps))
     if args.blurs:
         shift_args["blurs"] = args.blurs
+    if args.zooms:
+        shift_args["zooms"] = args.zooms
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

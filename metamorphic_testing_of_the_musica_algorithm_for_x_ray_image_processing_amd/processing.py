@@ -11,6 +11,7 @@ There is no CPU fallback: the shared library is HIP-only and every call fails
 loudly when the extension or a GPU is missing.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -150,7 +151,25 @@ class SimJointResult(C.Structure):
 
 SIM_MAX_RADIUS = 16         # MUSICA_SIM_MAX_RADIUS
 BLUR_MAX_RADIUS = 8         # MUSICA_BLUR_MAX_RADIUS
+ZOOM_MAX_P = 32             # MUSICA_ZOOM_MAX_P
 SIM_TILE = 64               # MUSICA_SIM_TILE
+
+
+def zoom_ratio(zoom):
+    """(p, q) of a magnification p / q as harness.zoom and the library take it: integers 1 <= q < p <= ZOOM_MAX_P in lowest terms, else
+    ValueError."""
+    try:
+        p, q = zoom
+        if p != int(p) or q != int(q):
+            raise TypeError
+        p, q = int(p), int(q)
+    except (TypeError, ValueError):
+        raise ValueError("a zoom is a pair of integers (p, q), got %r" % (zoom,))
+    if not 1 <= q < p <= ZOOM_MAX_P:
+        raise ValueError("zoom %d / %d is not 1 <= q < p <= %d" % (p, q, ZOOM_MAX_P))
+    if math.gcd(p, q) != 1:
+        raise ValueError("zoom %d / %d is not in lowest terms" % (p, q))
+    return p, q
 
 
 class SimDisplaceResult(C.Structure):
@@ -346,6 +365,8 @@ ABI = {
     "musica_sim_transform_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_blur_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_blur": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
+    "musica_sim_zoom_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_alter_zoom": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -727,6 +748,11 @@ class MusicaProcessing:
             raise ValueError("blur radius %d is not in 1 .. %d" % (radius, BLUR_MAX_RADIUS))
         self._ok(self._lib.musica_sim_blur_reference(self._h, int(dst_slot), int(src_slot), int(radius)), "musica_sim_blur_reference")
 
+    def sim_zoom_reference(self, dst_slot, src_slot, zoom):
+        """Reference slot `src_slot` as harness.zoom(slot, zoom) (zoom = (p, q): zoom_ratio) into `dst_slot`, on the device."""
+        p, q = zoom_ratio(zoom)
+        self._ok(self._lib.musica_sim_zoom_reference(self._h, int(dst_slot), int(src_slot), p, q), "musica_sim_zoom_reference")
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -919,6 +945,11 @@ class MusicaProcessing:
         if int(radius) < 0:
             raise ValueError("blur radius %d is not in 1 .. %d" % (radius, BLUR_MAX_RADIUS))
         self._ok(self._lib.musica_alter_blur(self._h, int(image_index), int(radius)), "musica_alter_blur")
+
+    def alter_zoom(self, zoom, image_index=0):
+        """harness.zoom(src, zoom): the exact bilinear magnification by p / q about the centre, zoom = (p, q) (zoom_ratio)."""
+        p, q = zoom_ratio(zoom)
+        self._ok(self._lib.musica_alter_zoom(self._h, int(image_index), p, q), "musica_alter_zoom")
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""
