@@ -15,7 +15,7 @@ import test_gpu_parity as tp
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
 ob.set_threads(min(16, os.cpu_count() or 1))
-knobs = ["MUSICA_SDEV_IN_EXPAND", "MUSICA_PAIR_RB_SDEV", "MUSICA_SDEV_ONE_LAUNCH", "MUSICA_GRAPH", "MUSICA_AUTOTUNE", "MUSICA_TINY_TAIL"]
+knobs = ["MUSICA_SDEV_IN_EXPAND", "MUSICA_HIST_IN_RB", "MUSICA_PAIR_RB_SDEV", "MUSICA_SDEV_ONE_LAUNCH", "MUSICA_GRAPH", "MUSICA_AUTOTUNE", "MUSICA_TINY_TAIL"]
 for case in range(cases):
     n = int(rng.choice([8 * int(rng.integers(8, 190)), int(rng.integers(64, 1500))]))   # a multiple of 8 (streaming kernels) or any side (generic ones)
     lmax = int(np.ceil(np.log2(n)))

@@ -214,6 +214,13 @@ int musica_fuses_sdev(const musica_ctx* ctx);
  * overrides) or when no level qualifies (levels i and i + 1 need sides that are multiples of 8, and level i + 1 must lie above the
  * one-launch tail of small levels). Returns 0 for a NULL context. */
 int musica_get_paired_levels(const musica_ctx* ctx);
+/* 1 when level 0's smooth + downsample and band-pass launch of a whole step also counts the level's noise histogram from the band
+ * values it has in registers (k_reduce_band_hist) and what is left of the level-0 sdev pass is the seam: the two columns either side of
+ * every 512-column strip boundary, counted from the stored band image. Needs musica_fuses_sdev, raw-pixel level-0 launches and a side
+ * of at least 512; chosen by musica_create for one-stream contexts whose level-0 launch fills the chip with segments of 16 coarse rows
+ * (the contexts of a pipeline from 8 x 2048^2 or one 4096^2 image per step), MUSICA_HIST_IN_RB=0|1 overrides. Histograms, curves and
+ * images are the same bits either way. Returns 0 for a NULL context. */
+int musica_fuses_noise_hist(const musica_ctx* ctx);
 uint32_t musica_get_level_size(const musica_ctx* ctx, uint32_t level);
 /* How this context dispatches a step (chosen by musica_create from the batch, the image side, the depth of the pyramid and the
  * flags): *streams = 1 (the reference's one in-order queue), 2 (the analysis launches on a second stream

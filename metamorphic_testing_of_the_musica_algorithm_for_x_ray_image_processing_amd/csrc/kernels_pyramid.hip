@@ -493,6 +493,32 @@ __device__ __forceinline__ void band_pair(const CRow& a, const CRow& b, const CR
     store8_nt(bb, g.off + off_o, bo);
 }
 
+// band_pair() for the march that also counts the level's noise histogram (reduce_band_block<true, true>): the pair is stored only where
+// `store` (wave-uniform) says so — the pairs above and below a segment only feed the 5 x 5 sums — and its squares go into se / so. A lane
+// right of the image normalises pixels it never loaded: its squares are 0, what img_sdev.comp reads there.
+template <class R>
+__device__ __forceinline__ void band_pair_sq(const CRow& a, const CRow& b, const CRow& c, const R& fe, const R& fo, const LaneCfg& g,
+                                             const Buf& bb, uint32_t off_e, uint32_t off_o, bool store, SRow& se, SRow& so) {
+    float lowE[8], lowO[8], be[8], bo[8];
+    lowpass_pair(a, b, c, g, lowE, lowO);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        be[j] = fe.v[j] - lowE[j];   // img_difference.comp:15
+        bo[j] = fo.v[j] - lowO[j];
+    }
+    if (store) {
+        store8_nt(bb, g.off + off_e, be);
+        store8_nt(bb, g.off + off_o, bo);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const float te = g.active ? be[j] : 0.0f, to = g.active ? bo[j] : 0.0f;
+        se.q[j] = te * te;
+        so.q[j] = to * to;
+    }
+    se.e0 = se.e1 = so.e0 = so.e1 = 0.0f;   // the columns beside the strip are the seam pass's (hist_seam_block)
+}
+
 // bit j: fe.v[j] <= 0.9, bit 8 + j: fo.v[j] <= 0.9 — the shader's own comparison on the normalized value (NaN: false)
 __device__ __forceinline__ uint32_t le090_bits(const FRowQ& fe, const FRowQ& fo) {
     uint32_t m = 0u;
@@ -516,11 +542,21 @@ __device__ __forceinline__ void load_f(FRow& r, const Buf& b, uint32_t row_off, 
 // needed (a prefetch would cost 24 registers and a wavefront per SIMD; these levels are small and L2-resident).
 // one workgroup of the launch: `tile` = its strip and block of four segments, `img` = its image (k_reduce_band below; the paired launch of
 // kernels_expand_sd.hip gives some of its workgroups this role)
-template <bool U16>
+// NH (level 0 only): the march also counts the level's noise histogram (img_sdev.comp + noise_hist.comp) from the band values it has in
+// registers when it stores them, instead of a pass that reads the band image back. The wavefront keeps the squares of its last six band
+// rows and, when band rows 2 kp, 2 kp + 1 exist, scans rows 2 kp - 2, 2 kp - 1 with sdev_row() — the arithmetic and the bookkeeping of
+// every other form. It scans the rows of its own segment, so it computes one band pair more at either end than it stores (ks = k0 - 2,
+// ke = k1 + 1: two more trips), and a segment holds whole 16-row runs (rows_per_wave % 8 == 0, the caller checks). Rows outside the
+// image are zeros. The two columns either side of an interior strip boundary would need the neighbouring strip's band values: they
+// start every run dead here and hist_seam_block() counts them from the stored band image. lh: the workgroup's cleared LDS histogram
+// (the kernel flushes it); cov: the dispatch coverage of noise_hist.comp.
+template <bool U16, bool NH = false>
 __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine, float* __restrict__ down, float* __restrict__ band,
                                                   int S, int pitch, size_t plane, int Sc, int cpitch, size_t cplane,
                                                   int rows_per_wave, const uint32_t* __restrict__ minmax, int min_chain_exact,
-                                                  uint16_t* __restrict__ le090, const Tile tile, const int img) {
+                                                  uint16_t* __restrict__ le090, const Tile tile, const int img,
+                                                  uint32_t* lh = nullptr, int cov = 0) {
+    static_assert(!NH || U16, "the histogram form is level 0's");
     const int lane = threadIdx.x & 63;
     const int seg = __builtin_amdgcn_readfirstlane((int)(tile.segblock * kWavesPerBlock + (threadIdx.x >> 6)));   // wave-uniform: row arithmetic stays on the scalar unit
     const int k0 = seg * rows_per_wave;
@@ -549,7 +585,7 @@ __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine,
     const uint32_t qi = (uint32_t)lane & 3u;
     const int hi = S - 1;
     const uint32_t frb = U16 ? (uint32_t)S * 2u : (uint32_t)pitch * 4u, rb = (uint32_t)pitch * 4u, crb = (uint32_t)cpitch * 4u;
-    const int ks = max(k0 - 1, 0), ke = min(k1, Sc - 1);   // coarse rows this wavefront computes (the first / last only feed its band rows)
+    const int ks = max(k0 - (NH ? 2 : 1), 0), ke = min(k1 + (NH ? 1 : 0), Sc - 1);   // coarse rows this wavefront computes (the first / last only feed its band rows)
 
     typename std::conditional<U16, FRowQ, FRow>::type w0, w1, w2, w3, w4;
     RawF ra, rc;
@@ -569,6 +605,24 @@ __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine,
     }
     CRow c0, cm1, cm2;
     cm1 = CRow(); cm2 = CRow();
+    // NH: q0 .. q5 = the squares of band rows 2 kp - 4 .. 2 kp + 1 once pair kp is in (q4, q5); zeros above row 0
+    [[maybe_unused]] SRow q0 = SRow(), q1 = SRow(), q2 = SRow(), q3 = SRow(), q4 = SRow(), q5 = SRow();
+    [[maybe_unused]] unsigned long long alive[8], start[8];
+    [[maybe_unused]] const SCfg sg = make_scfg(tile.strip, lane, S);
+    if constexpr (NH) {
+        sdev_start_masks(start, alive, sg, cov);
+        // columns c0, c0 + 1 of a strip with a left neighbour and c0 + 510, c0 + 511 of one with a right neighbour: the seam pass's
+        const unsigned long long keep_l = tile.strip > 0 ? ~1ull : ~0ull, keep_r = (tile.strip + 1) * kStripCols < S ? ~(1ull << 63) : ~0ull;
+        start[0] &= keep_l; start[1] &= keep_l; start[6] &= keep_r; start[7] &= keep_r;
+    }
+    // band rows 2 kq, 2 kq + 1 (their five-row neighbourhoods are complete once pair kq + 1 is in) and the window's step of two rows
+    [[maybe_unused]] auto scan_pair = [&](int kq) {
+        if (kq >= k0 && kq < k1) {  // wave-uniform
+            sdev_row<true, true>(q0, q1, q2, q3, q4, sg, S, 2 * kq, cov, nullptr, bb, 0u, lh, alive, start, false);
+            sdev_row<true, true>(q1, q2, q3, q4, q5, sg, S, 2 * kq + 1, cov, nullptr, bb, 0u, lh, alive, start, false);
+        }
+        q0 = q2; q1 = q3; q2 = q4; q3 = q5;
+    };
     for (int k = ks; k <= ke; k++) {
         if constexpr (U16) {
             convert_f(w3, ra, nk, qi);   // the pair requested one trip ago
@@ -586,7 +640,14 @@ __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine,
         // coarse row k completes the neighbourhood of row k-1: band rows 2(k-1), 2(k-1)+1 are the two oldest rows of the window.
         // km1(0) = coarse_of_fine(-2) = 1 (reflect-101 on the fine grid, img_smooth_upsampled.comp:10-16): row k itself.
         const int kp = k - 1;
-        if (kp >= k0 && kp < k1) {  // wave-uniform
+        if constexpr (NH) {
+            if (kp >= max(k0 - 1, 0)) {  // wave-uniform; kp <= min(k1, Sc - 2) by ke
+                const bool mine = kp >= k0 && kp < k1;
+                if (want_mask && mine) bstore_u16(mb, moff + (uint32_t)kp * mrb, le090_bits(w0, w1));
+                band_pair_sq(kp == 0 ? c0 : cm2, cm1, c0, w0, w1, g, bb, (uint32_t)(2 * kp) * rb, (uint32_t)(2 * kp + 1) * rb, mine, q4, q5);
+                scan_pair(kp - 1);
+            }
+        } else if (kp >= k0 && kp < k1) {  // wave-uniform
             if constexpr (U16) if (want_mask) bstore_u16(mb, moff + (uint32_t)kp * mrb, le090_bits(w0, w1));
             band_pair(kp == 0 ? c0 : cm2, cm1, c0, w0, w1, g, bb, (uint32_t)(2 * kp) * rb, (uint32_t)(2 * kp + 1) * rb);
         }
@@ -596,7 +657,14 @@ __device__ __forceinline__ void reduce_band_block(const void* __restrict__ fine,
     // the last row pair of the image: kp1(Sc-1) = coarse_of_fine(S) = Sc-1 (fine row S mirrors onto S-2)
     if (k1 == Sc) {
         if constexpr (U16) if (want_mask) bstore_u16(mb, moff + (uint32_t)(Sc - 1) * mrb, le090_bits(w0, w1));
-        band_pair(cm2, cm1, cm1, w0, w1, g, bb, (uint32_t)(2 * (Sc - 1)) * rb, (uint32_t)(2 * (Sc - 1) + 1) * rb);
+        if constexpr (NH) {
+            band_pair_sq(cm2, cm1, cm1, w0, w1, g, bb, (uint32_t)(2 * (Sc - 1)) * rb, (uint32_t)(2 * (Sc - 1) + 1) * rb, true, q4, q5);
+            scan_pair(Sc - 2);
+            q4 = SRow(); q5 = SRow();   // rows S, S + 1: zeros
+            scan_pair(Sc - 1);
+        } else {
+            band_pair(cm2, cm1, cm1, w0, w1, g, bb, (uint32_t)(2 * (Sc - 1)) * rb, (uint32_t)(2 * (Sc - 1) + 1) * rb);
+        }
     }
 }
 template <bool U16>
@@ -1252,6 +1320,91 @@ __device__ __forceinline__ bool role_tile(int local, int strips, int blocks, int
     }
     return t.segblock < blocks;   // false: padding
 }
+// The seam of the level-0 march that counts its own noise histogram (reduce_band_block<true, true>): the two columns either side of every
+// interior strip boundary, which that march leaves uncounted, from the stored band image. noise_hist.comp scans every (column, 16-row run)
+// on its own (:20-47, m outer), so these runs are the shader's whatever launch counts them. One thread per column and run: 20 band rows x 5
+// columns, vertical then horizontal sums of squares in sdev_values()' order, the literal sqrt(sum / 25) (what musica_rms25_8 returns),
+// musica_noise_bin. Work item w of an image = (run, boundary, column): w % 4 = column 512 b - 2 + w % 4, so a boundary's four threads
+// read one 32-byte piece of a row. `first`: the workgroup's first item; items: 4 x (strips - 1) x runs.
+__device__ __forceinline__ void hist_seam_block(const float* __restrict__ band, int S, int pitch, uint32_t* __restrict__ hist, int cov,
+                                                int first, int items, uint32_t* lh) {
+    hist_lds_clear(lh);
+    __syncthreads();
+    const int w = first + (int)threadIdx.x;
+    const int bounds = (S + kStripCols - 1) / kStripCols - 1;
+    const int ci = w & 3, b = (w >> 2) % bounds + 1, run = (w >> 2) / bounds;
+    const int x = b * kStripCols - 2 + ci, y0 = run * kHistArea;
+    if (w < items && x < cov && y0 < cov) {   // columns and rows outside the dispatch coverage are not counted (cov is a multiple of 512)
+        float q[kHistArea + 4][5];
+#pragma unroll
+        for (int r = 0; r < kHistArea + 4; r++) {
+            const int y = y0 - 2 + r;
+            const bool in = y >= 0 && y < S;
+            const float* row = band + (size_t)(in ? y : 0) * pitch + (x - 2);   // columns x - 2 .. x + 2 lie inside the image: S >= 512 b + 8
+#pragma unroll
+            for (int m = 0; m < 5; m++) {
+                const float v = in ? row[m] : 0.0f;   // rows outside the image read 0 (img_sdev.comp)
+                q[r][m] = v * v;
+            }
+        }
+        const uint32_t copy = (uint32_t)((threadIdx.x % kHistCopies) * kHistCopyStride);
+        bool alive = true;
+#pragma unroll
+        for (int r = 0; r < kHistArea; r++) {
+            float c[5];
+#pragma unroll
+            for (int m = 0; m < 5; m++) c[m] = sum5(q[r][m], q[r + 1][m], q[r + 2][m], q[r + 3][m], q[r + 4][m]);
+            const float s = sqrtf(sum5(c[0], c[1], c[2], c[3], c[4]) / 25.0f);   // img_sdev.comp:30
+            const int bin = musica_noise_bin(s);                                 // 0 = break (noise_hist.comp:29, :33, :39)
+            alive = alive && bin != 0 && y0 + r < S;
+            if (alive) atomicAdd(&lh[copy + (uint32_t)bin], 1u);                 // :45; bin 2048 is the pad word behind the copy (dropped, no break)
+        }
+    }
+    __syncthreads();
+    hist_lds_flush(lh, hist);
+}
+// the seam pass as a launch of its own (the scripts without pairs); grid: x = workgroups of an image, z = batch
+__global__ __launch_bounds__(kBlockThreads) void k_hist_seam(const float* __restrict__ band, int S, int pitch, size_t plane, uint32_t* __restrict__ hist,
+                                                             size_t hist_stride, int cov, int items) {
+    __shared__ uint32_t lh[kHistLdsWords];
+    const int img = (int)blockIdx.z;
+    hist_seam_block(band + (size_t)img * plane, S, pitch, hist + (size_t)img * hist_stride, cov, (int)blockIdx.x * kBlockThreads, items, lh);
+}
+static inline int seam_items(int S, int cov) {
+    const int bounds = (S + kStripCols - 1) / kStripCols - 1, rows = S < cov ? S : cov;
+    return 4 * bounds * ((rows + kHistArea - 1) / kHistArea);
+}
+void launch_hist_seam(hipStream_t st, const float* band, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov, int batch) {
+    const int items = seam_items(l.S, cov);
+    if (items <= 0) return;   // one strip: no seam
+    hipLaunchKernelGGL(k_hist_seam, dim3((items + kBlockThreads - 1) / kBlockThreads, 1, batch), dim3(kBlockThreads), 0, st, band, l.S, l.pitch, l.plane,
+                       hist, hist_stride, cov, items);
+}
+
+#ifndef MUSICA_RB_HIST_W
+#define MUSICA_RB_HIST_W 2   // wavefronts per SIMD the register allocation is capped for
+#endif
+// Level 0's reduce + band launch counting the level's noise histogram itself (reduce_band_block<true, true>). Built here, without the SLP
+// vectoriser, like the expand launches that keep a window of squares in registers.
+__global__ __launch_bounds__(kBlockThreads, MUSICA_RB_HIST_W) void k_reduce_band_hist(const void* __restrict__ fine, float* __restrict__ down, float* __restrict__ band,
+                                                               int S, int pitch, size_t plane, int Sc, int cpitch, size_t cplane,
+                                                               int rows_per_wave, const uint32_t* __restrict__ minmax, int min_chain_exact,
+                                                               uint16_t* __restrict__ le090, int swz, uint32_t* __restrict__ hist, size_t hist_stride, int cov) {
+    __shared__ uint32_t lh[kHistLdsWords];
+    hist_lds_clear(lh);
+    __syncthreads();
+    reduce_band_block<true, true>(fine, down, band, S, pitch, plane, Sc, cpitch, cplane, rows_per_wave, minmax, min_chain_exact, le090, xcd_tile(swz),
+                                  (int)blockIdx.z, lh, cov);
+    __syncthreads();
+    hist_lds_flush(lh, hist + (size_t)blockIdx.z * hist_stride);
+}
+void launch_reduce_band_u16_hist(hipStream_t st, const uint16_t* px, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch,
+                                 int rows_per_wave, const uint32_t* minmax, int min_chain_exact, uint16_t* le090, int swz, uint32_t* hist,
+                                 size_t hist_stride, int cov) {
+    hipLaunchKernelGGL(k_reduce_band_hist, stream_grid(lf.S, lc.S, rows_per_wave, batch), dim3(kBlockThreads), 0, st, (const void*)px, down, band, lf.S,
+                       lf.pitch, lf.plane, lc.S, lc.pitch, lc.plane, rows_per_wave, minmax, min_chain_exact, le090, swz, hist, hist_stride, cov);
+}
+
 __global__ __launch_bounds__(kBlockThreads, 4) void k_rb_sdev(const RbSdevArgs a) {
     __shared__ uint32_t lh[kHistLdsWords];
     __shared__ unsigned long long nzw[kWavesPerBlock][8];
@@ -1263,6 +1416,11 @@ __global__ __launch_bounds__(kBlockThreads, 4) void k_rb_sdev(const RbSdevArgs a
         return;
     }
     const SdevRunLevel& l = a.sl;
+    if (l.rows < 0) {   // the level's march counted its own histogram: what is left of its pass is the seam (l.blocks workgroups)
+        if ((int)blockIdx.x < l.blocks)
+            hist_seam_block(l.band + (size_t)img * l.plane, l.S, l.pitch, l.hist + (size_t)img * a.hist_stride, a.cov, (int)blockIdx.x * kBlockThreads, a.seam_items, lh);
+        return;
+    }
     if (!role_tile((int)blockIdx.x, l.strips, l.blocks, a.swz, tile)) return;
     float* sd = l.sdev ? l.sdev + (size_t)img * l.plane : nullptr;
     if (l.rows > 0) sdev_march_block<true, true>(l.band + (size_t)img * l.plane, sd, l.S, l.pitch, l.plane, l.hist + (size_t)img * a.hist_stride, a.cov, l.rows, tile, lh);
@@ -1270,9 +1428,11 @@ __global__ __launch_bounds__(kBlockThreads, 4) void k_rb_sdev(const RbSdevArgs a
 }
 // `a`: the pointers, geometry of the reduce + band role and sl.{band, sdev, hist, rows} filled in by the caller; ls: the sdev level
 void launch_rb_sdev(hipStream_t st, RbSdevArgs a, const LevelDesc& ls, int batch) {
-    const int s_strips = (ls.S + kStripCols - 1) / kStripCols;
+    int s_strips = (ls.S + kStripCols - 1) / kStripCols;
     int s_blocks;
-    if (a.sl.rows > 0) { const int segs = (ls.S + a.sl.rows - 1) / a.sl.rows; s_blocks = (segs + kWavesPerBlock - 1) / kWavesPerBlock; }
+    a.seam_items = 0;
+    if (a.sl.rows < 0) { a.seam_items = seam_items(ls.S, a.cov); s_strips = 1; s_blocks = (a.seam_items + kBlockThreads - 1) / kBlockThreads; }
+    else if (a.sl.rows > 0) { const int segs = (ls.S + a.sl.rows - 1) / a.sl.rows; s_blocks = (segs + kWavesPerBlock - 1) / kWavesPerBlock; }
     else s_blocks = (ls.S + kHistArea - 1) / kHistArea;
     a.sl.plane = ls.plane; a.sl.S = ls.S; a.sl.pitch = ls.pitch; a.sl.strips = s_strips; a.sl.blocks = s_blocks; a.sl.first = 0;
     a.rb_first = (s_strips * s_blocks + 7) & ~7;

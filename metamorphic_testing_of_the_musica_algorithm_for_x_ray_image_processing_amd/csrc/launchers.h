@@ -80,10 +80,19 @@ struct RbSdevArgs {
     const float* fine; float* down; float* band;   // reduce + band of level i + 1: its fine image, coarse image, band image
     int S, pitch; size_t plane; int Sc, cpitch; size_t cplane; int rows_rb;
     int rb_strips, rb_blocks, rb_first;            // that role's workgroups: rb_strips * rb_blocks from rb_first on (a multiple of 8)
-    SdevRunLevel sl;                               // level i's pass: march (sl.rows > 0) or one run per workgroup; sl.sdev == nullptr: histogram only
+    SdevRunLevel sl;                               // level i's pass: march (sl.rows > 0) or one run per workgroup; sl.sdev == nullptr: histogram only;
+                                                   // sl.rows < 0 (level 0): its reduce + band launch counted the histogram, the role is the seam pass
     size_t hist_stride; int cov, swz;
+    int seam_items;                                // filled in by launch_rb_sdev
 };
 void launch_rb_sdev(hipStream_t st, RbSdevArgs a, const LevelDesc& ls, int batch);
+// launch_reduce_band_u16 that also counts level 0's noise histogram (k_reduce_band_hist, kernels_expand_sd.hip) except for the two columns
+// either side of every interior strip boundary: launch_hist_seam, or the sdev role of launch_rb_sdev with sl.rows < 0, counts those from
+// the stored band image. rows_per_wave % 8 == 0. hist: image 0's level-0 histogram.
+void launch_reduce_band_u16_hist(hipStream_t st, const uint16_t* px, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch,
+                                 int rows_per_wave, const uint32_t* minmax, int min_chain_exact, uint16_t* le090, int swz, uint32_t* hist,
+                                 size_t hist_stride, int cov);
+void launch_hist_seam(hipStream_t st, const float* band, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov, int batch);
 void launch_expand_sd(hipStream_t st, const ExpandArgs& a, bool nr, int batch);   // a.sdev == nullptr: sdev computed by the launch (kernels_expand_sd.hip)
 // reduce + band of the levels in `a`, then their expand slots, one workgroup per image (levels of side <= kTailSide)
 void launch_tiny_tail(hipStream_t st, const TailArgs& a, int batch);

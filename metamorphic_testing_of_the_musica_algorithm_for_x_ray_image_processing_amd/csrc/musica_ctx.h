@@ -171,6 +171,11 @@ struct musica_ctx : DeviceBuffers {
     bool pair_rb_sdev;         // the one-stream script pairs the sdev pass of level i with reduce + band of level i + 1 in one launch (k_rb_sdev); MUSICA_PAIR_RB_SDEV
     bool sdev_one_launch;      // the sdev + noise-histogram passes of levels 0 .. 3 as ONE launch (k_sdev_hist_levels); MUSICA_SDEV_ONE_LAUNCH=0: one launch per marching level + one for the runs
     int rows_rb[MUSICA_MAX_LEVELS];   // its coarse rows per wavefront
+    // Level 0's reduce + band launch of a whole-step script counts the level's noise histogram itself (k_reduce_band_hist) and the level-0
+    // sdev pass shrinks to the seam columns (musica_ctx.hip hist_in_rb). MUSICA_HIST_IN_RB: 0 never, 1 wherever the form exists, unset (-1):
+    // the one-stream steps large enough for segments of 16 coarse rows (hist_rb_rows()).
+    int hist_in_rb;
+    int hist_rb_rows;          // MUSICA_HIST_RB_ROWS: coarse rows per wavefront of that launch (a multiple of 8), 0: chosen from the step's size
     int xcd_swizzle;           // XCD-aware workgroup -> tile mapping of the marching kernels (launchers.h); MUSICA_XCD_SWIZZLE=0: the plain mapping
     int xcd_regions;           // the metric kernel's 2-D regions per XCD where its geometry allows; MUSICA_XCD_REGIONS=0: the round-3 mapping
     uint8_t* d_out8 = nullptr;   // saveOutImage's cropped 8-bit pixels of one image (device) and their pinned host copy, allocated on first use

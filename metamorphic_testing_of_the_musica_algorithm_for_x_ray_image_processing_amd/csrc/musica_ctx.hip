@@ -90,6 +90,7 @@ static void autotune(musica_ctx* c);
 static bool rb_level(const musica_ctx* c, int i);
 static int tail_first(const musica_ctx* c);
 static int rb_sdev_pairs(const musica_ctx* c, int T);
+static int hist_rb_rows(const musica_ctx* c);
 static void copy_rows(musica_ctx* dst, const musica_ctx* src) {
     if (dst == src) return;
     memcpy(dst->rows_expand, src->rows_expand, sizeof(src->rows_expand));
@@ -324,6 +325,8 @@ static musica_ctx* create_impl(const musica_params* params, const musica_tunable
     // 8 x 2048^2 -3.1 %, 8192^2 -2.0 %, 4096^2 + CLAHE -2.1 %, 3072^2 L12 +0.6 %, one 2048^2 image +2.8 %); a lone one-stream context is slower with them
     // (512^2 +17 %, 1024^2 +3 %, 1536^2 +7 %, 2 / 4 x 1024^2 +5 / +4 %): alone on the chip a pair costs what its two launches cost one after the other
     c->pair_rb_sdev = env_int("MUSICA_PAIR_RB_SDEV", ((params->flags & MUSICA_FLAG_LINEAR) && (size_t)c->B * N * N >= (size_t)2 * 2048 * 2048) ? 1 : 0) != 0;
+    c->hist_in_rb = env_int("MUSICA_HIST_IN_RB", -1);
+    c->hist_rb_rows = env_int("MUSICA_HIST_RB_ROWS", 0) & ~7;
     c->sdev_one_launch = env_int("MUSICA_SDEV_ONE_LAUNCH", ((params->flags & MUSICA_FLAG_LINEAR) || c->B > 1) ? 1 : 0) != 0;
     c->fuse_gh = env_int("MUSICA_FUSE_GH", 1) != 0 && c->fuse_u16 && (!(params->flags & MUSICA_FLAG_CLAHE) || c->clahe_raw) &&
                  cnr_scale(c->lv[0].S, c->lv[MUSICA_CNR_LEVEL].S) == 8;
@@ -359,6 +362,9 @@ int musica_get_dispatch(const musica_ctx* c, int* streams, int* graph) {
 int musica_fuses_gradation_histogram(const musica_ctx* c) { return (c && c->fuse_gh && !c->generic) ? 1 : 0; }
 int musica_fuses_reduce_band(const musica_ctx* c) { return (c && rb_level(c, 0)) ? 1 : 0; }
 int musica_fuses_sdev(const musica_ctx* c) { return (c && c->sd_fused && rb_level(c, 0)) ? 1 : 0; }
+int musica_fuses_noise_hist(const musica_ctx* c) {
+    return (c && c->sd_fused && !c->ref_order && !c->generic && c->fuse_u16 && rb_level(c, 0) && hist_rb_rows(c) > 0) ? 1 : 0;
+}
 int musica_get_paired_levels(const musica_ctx* c) { return (c && c->dag == 0) ? rb_sdev_pairs(c, tail_first(c)) : 0; }
 uint32_t musica_get_level_size(const musica_ctx* c, uint32_t level) { return (c && (int)level <= c->L) ? (uint32_t)c->lv[level].S : 0; }
 
@@ -425,8 +431,33 @@ static void ensure_normalized(musica_ctx* c) {
 
 // reduce + band of a level in one launch: every level whose side is a multiple of 8 (level 0 then reads the raw pixels)
 static bool rb_level(const musica_ctx* c, int i) { return !c->generic && c->lv[i].S >= 8 && (c->lv[i].S % 8) == 0; }
+// Coarse rows per wavefront of level 0's launch in the form that counts the noise histogram itself, 0 where the context does not take it.
+// A wavefront scans whole 16-row runs of its own segment: 8 k coarse rows (MUSICA_HIST_RB_ROWS sets k). By default the form is taken where
+// segments of 16 coarse rows fill the chip and the step runs on one stream (the contexts of a pipeline; the two-stream script of a
+// lone context has the level-0 sdev pass beside the reduce tail already, and a longer level-0 launch in front of it: profiles/r07);
+// MUSICA_HIST_IN_RB=1 takes it wherever it exists, down to segments of one run.
+static int hist_rb_rows(const musica_ctx* c) {
+    if (c->hist_in_rb == 0 || c->hist_cov <= 0) return 0;   // a side below 512 lies outside the dispatch coverage: nothing to count
+    // 16 coarse rows where that gives every SIMD a wavefront, else 8 (rows_rb[0] is tuned for the launch without the scan, and at init:
+    // its choice varies from process to process). Same-box A/B at 8 x 2048^2, three steps in flight: 16 rows -3.4 %, 32 rows -0.6 %.
+    const int r = pick_rows(16, 8, c->lv[0].S, c->lv[1].S, c->B, 1024);
+    if (c->hist_in_rb < 0 && !(r == 16 && c->dag == 0)) return 0;
+    return c->hist_rb_rows > 0 ? c->hist_rb_rows : r;
+}
+// whole-step scripts only (sd_active): the stage entry points, ensure_sdev(), the getters and the autotune pass see the launches they always saw
+static bool hist_in_rb(const musica_ctx* c) {
+    return c->sd_active && !c->tuning && !c->ref_order && !c->generic && c->fuse_u16 && rb_level(c, 0) && hist_rb_rows(c) > 0;
+}
+static uint32_t* noise_hist_of(const musica_ctx* c, int i) { return c->d_noise_hist + (size_t)i * MUSICA_NOISE_BINS; }
+// what is left of level 0's sdev pass then, as a launch of its own (the scripts without pairs)
+static void run_hist_seam(musica_ctx* c) {
+    launch_hist_seam(c->cur, c->d_band[0], c->lv[0], noise_hist_of(c, 0), (size_t)4 * MUSICA_NOISE_BINS, c->hist_cov, c->B);
+}
 static void run_reduce_band(musica_ctx* c, int i, int rows) {
-    if (i == 0)
+    if (i == 0 && hist_in_rb(c))
+        launch_reduce_band_u16_hist(c->cur, c->cur_input, c->d_down[0], c->d_band[0], c->lv[0], c->lv[1], c->B, hist_rb_rows(c), c->d_minmax, c->min_chain_exact,
+                                    c->d_le090, c->xcd_swizzle, noise_hist_of(c, 0), (size_t)4 * MUSICA_NOISE_BINS, c->hist_cov);
+    else if (i == 0)
         launch_reduce_band_u16(c->cur, c->cur_input, c->d_down[0], c->d_band[0], c->lv[0], c->lv[1], c->B, rows, c->d_minmax, c->min_chain_exact, c->d_le090,
                                c->xcd_swizzle);
     else
@@ -535,16 +566,19 @@ static void run_sdev_all_levels(musica_ctx* c, int first = 0) {
 }
 static void enqueue_analysis(musica_ctx* c, hipStream_t st = nullptr) {
     if (!st) st = c->stream;
+    const int s0 = hist_in_rb(c) ? 1 : 0;   // level 0's histogram came out of its reduce + band launch: the seam is what is left of its pass
+    if (s0) { Span sp(c, MUSICA_KERNEL_SDEV_HIST); run_hist_seam(c); }
     if (c->sdev_one_launch && !c->ref_order && !c->tuning) {
-        { Span sp(c, MUSICA_KERNEL_SDEV_HIST); run_sdev_all_levels(c); }
+        { Span sp(c, MUSICA_KERNEL_SDEV_HIST); run_sdev_all_levels(c, s0); }
         Span sp2(c, MUSICA_KERNEL_CURVES);
         launch_curves_cnr(st, c->d_noise_hist, (size_t)4 * MUSICA_NOISE_BINS, c->d_noise_max, c->d_curves, c->d_cparams, c->L, c->B, c->d_luts,
                           c->d_sdev[MUSICA_CNR_LEVEL], c->d_cnr, c->lv[MUSICA_CNR_LEVEL], c->d_minmax, c->min_chain_exact, c->d_thr090);
         return;
     }
     int merged = sdev_runs_from(c);
+    if (merged < s0) merged = s0;
     if (merged >= MUSICA_CNR_LEVEL) merged = MUSICA_CNR_LEVEL + 1;   // one level is its own launch
-    for (int i = 0; i < merged; i++) {  // i < coarserLevelsStart || i <= cnrLevel, :2285
+    for (int i = s0; i < merged; i++) {  // i < coarserLevelsStart || i <= cnrLevel, :2285
         Span sp(c, MUSICA_KERNEL_SDEV_HIST);
         run_sdev_level(c, i, c->rows_sdev[i]);
     }
@@ -673,6 +707,7 @@ static void run_rb_sdev_pair(musica_ctx* c, int i) {
     a.sl.band = c->d_band[i]; a.sl.sdev = sd_level(c, i) ? nullptr : c->d_sdev[i];
     a.sl.hist = c->d_noise_hist + (size_t)i * MUSICA_NOISE_BINS;
     a.sl.rows = c->rows_sdev[i] > 0 ? c->rows_sdev[i] : 0;
+    if (i == 0 && hist_in_rb(c)) a.sl.rows = -1;   // the seam pass in the sdev role
     a.hist_stride = (size_t)4 * MUSICA_NOISE_BINS; a.cov = c->hist_cov; a.swz = c->xcd_swizzle;
     launch_rb_sdev(c->cur, a, c->lv[i], c->B);
 }
@@ -701,6 +736,7 @@ static void enqueue_linear_paired(musica_ctx* c) {
     }
     for (int r = i + 1; r < T; r++) run_reduce_and_band(c, r);
     if (T < c->L) run_tiny_tail(c, T);
+    if (i == 0 && hist_in_rb(c)) { Span sp(c, MUSICA_KERNEL_SDEV_HIST); run_hist_seam(c); i = 1; }   // no pair: the seam as a launch of its own
     if (i <= MUSICA_CNR_LEVEL) { Span sp(c, MUSICA_KERNEL_SDEV_HIST); run_sdev_all_levels(c, i); }
     {
         Span sp(c, MUSICA_KERNEL_CURVES);

@@ -291,6 +291,7 @@ ABI = {
     "musica_fuses_reduce_band": (C.c_int, [_VP]),
     "musica_fuses_sdev": (C.c_int, [_VP]),
     "musica_get_paired_levels": (C.c_int, [_VP]),
+    "musica_fuses_noise_hist": (C.c_int, [_VP]),
     "musica_get_dispatch": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "musica_execute": (C.c_int, [_VP, _U16P]),
     "musica_execute_device": (C.c_int, [_VP, _VP]),
@@ -659,8 +660,11 @@ class MusicaProcessing:
 
     def dispatch_text(self):
         st, g = self.dispatch()
-        return "%s, %s" % ({1: "one stream", 2: "two streams (analysis beside the reduce tail)"}[st],
-                           "hipGraph replay" if g else "eager launches")
+        text = "%s, %s" % ({1: "one stream", 2: "two streams (analysis beside the reduce tail)"}[st],
+                             "hipGraph replay" if g else "eager launches")
+        if self.fuses_noise_hist():
+            text += ", level-0 noise histogram inside reduce + band"
+        return text
 
     def fuses_gradhist(self):
         """True when the level-0 expand kernel also accumulates the gradation histogram (no separate k_grad_hist launch)."""
@@ -669,6 +673,10 @@ class MusicaProcessing:
     def fuses_sdev(self):
         """True when the expand launches of levels 0 .. 2 compute sdev themselves and the sdev launches of those levels store nothing."""
         return self._lib.musica_fuses_sdev(self._h) == 1
+
+    def fuses_noise_hist(self):
+        """True when level 0's reduce + band launch also counts the level's noise histogram (the level-0 sdev pass is the seam columns only)."""
+        return self._lib.musica_fuses_noise_hist(self._h) == 1
 
     def paired_levels(self):
         """How many k_rb_sdev launches (the sdev pass of level i paired with reduce + band of level i + 1) one whole step runs; 0: no pair."""
