@@ -5,7 +5,8 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     scale up to 4 at least 7 wide; one full frame and one odd-sized offset region;
   * displace, ensemble add / result and track / covariance at radii 3 and 16, 17 realisations in two adds, at N = 151: 131 x 131 outputs,
     3 x 3 tiles with a 3-pixel ragged tail (a masked last chunk), and one region narrower than 16 pixels (a tile of the ragged chunk only);
-  * the five dst / src slot operations at N = 151, a symmetry with a transpose, a blur of radius 8 and a zoom of 32 / 31 among them.
+  * the six dst / src slot operations at N = 151, a symmetry with a transpose, a blur of radius 8, a zoom of 32 / 31 and a veil of radius
+    127 (wider than the slot) among them; and the same veil of the source plane into image 0 of the input buffer.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -89,7 +90,11 @@ p.sim_transform_reference(2, 0, 5)   # np.rot90(x.T, 1)
 p.sim_blur_reference(3, 0, 8)
 p.sim_remap_reference(4, 0, (np.arange(256) * 7 + 3).astype(np.uint8))
 p.sim_zoom_reference(5, 0, (32, 31))
-for name, slot in (("rotate", 1), ("transform", 2), ("blur", 3), ("remap", 4), ("zoom", 5)):
+p.sim_scatter_reference(6, 0, (127, 2, 3))
+for name, slot in (("rotate", 1), ("transform", 2), ("blur", 3), ("remap", 4), ("zoom", 5), ("scatter", 6)):
     note("musica_sim_%s_reference" % name, p.sim_get_reference(slot))
+p.alter_set_source(phantom(N, 3, noise=4.0))
+p.alter_scatter((127, 2, 3))
+note("musica_alter_scatter", p.input_pixels()[0])
 p.cleanup()
 print(json.dumps(digests))

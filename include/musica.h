@@ -419,6 +419,32 @@ int musica_sim_blur_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_s
  * before any device work: a NULL context, q = 0, p <= q, p > MUSICA_ZOOM_MAX_P, gcd(p, q) != 1, a slot out of range, dst_slot ==
  * src_slot, a source slot never written, an image too small for the margin. Marks dst_slot written; changes no other slot. */
 int musica_sim_zoom_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t p, uint32_t q);
+/* ---- scatter: the exact wide veiling glare (new, not in the reference) ----
+ * harness.scatter(image, (R, a, b)) is the contract: a square 2-D uint16 or uint8 plane mixed with a very wide blur of itself, the veil
+ * of scattered radiation under automatic exposure control, at the scatter fraction a / b. 1 <= R <= MUSICA_SCATTER_MAX_RADIUS,
+ * 1 <= a < b <= MUSICA_SCATTER_MAX_DEN, gcd(a, b) = 1. With box(A)[i] = sum_{k = -R .. R} A[clamp(i + k)] along one axis, clamped to the
+ * plane (edge replicated; each pass clamps its own input),
+ *   V   = box_y(box_y(box_x(box_x(image))))              tent x tent, total weight W = (2R + 1)^4
+ *   out = ((b - a) W image + a V + (b W) div 2) div (b W)
+ * ONE rounding, after the full sum, halves rounded up; nothing is rounded between the passes. The result has the input's type.
+ *   - the row and column operators commute: the order of the four passes changes nothing;
+ *   - after the two row passes a value is at most 255^2 * 65535 = 4 261 413 375 < 2^32: the row-pass plane is u32;
+ *   - W <= 255^4 = 4 228 250 625 < 2^32;
+ *   - the full numerator is at most 65535 * 64 * 255^4, about 1.77e16 < 2^64: the column passes and the mix are u64;
+ *   - the weights are a convex combination: a constant plane is preserved, nothing saturates, nothing is clipped;
+ *   - the operator commutes exactly with the eight symmetries of the square;
+ *   - it does NOT commute with cropping (the borders are clamped): a registered comparison is inset by 2R;
+ *   - the tent has sigma = sqrt(2R (R + 1) / 3) pixels, 104 at R = 127.
+ * The device results are bit-identical to that statement and repeat from call to call: integers only, no atomics, prefix sums along the
+ * rows and running sums down the columns (kernels_scatter.hip). The first call of either entry point allocates
+ * one N x N u32 plane, freed with the context. */
+#define MUSICA_SCATTER_MAX_RADIUS 127
+#define MUSICA_SCATTER_MAX_DEN 64
+/* scatter(reference slot `src_slot`, (radius, num, den)) of the (N - 20)^2 u8 plane into `dst_slot` (device to device, on the ctx
+ * stream). Refused before any device work: a NULL context, a radius outside 1 .. MUSICA_SCATTER_MAX_RADIUS, num = 0, num >= den, den >
+ * MUSICA_SCATTER_MAX_DEN, gcd(num, den) != 1, a slot out of range, dst_slot == src_slot, a source slot never written, an image too
+ * small for the margin, a failed allocation of the row plane. Marks dst_slot written; changes no other slot. */
+int musica_sim_scatter_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t radius, uint32_t num, uint32_t den);
 /* (N - 20)^2 bytes of reference slot `slot` to the host (synchronous); the slot must have been written. */
 int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
 
@@ -675,6 +701,12 @@ int musica_alter_blur(musica_ctx* ctx, uint32_t image_index, uint32_t radius);
  * slot. An entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT. Refused before any
  * device work: a NULL context, no source, q = 0, p <= q, p > MUSICA_ZOOM_MAX_P, gcd(p, q) != 1, image_index >= batch. */
 int musica_alter_zoom(musica_ctx* ctx, uint32_t image_index, uint32_t p, uint32_t q);
+/* scatter(source plane, (radius, num, den)) (above, at musica_sim_scatter_reference) into image `image_index` of the input buffer,
+ * enqueued on the ctx stream, with musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step
+ * and no reference slot. An entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT.
+ * Refused before any device work: a NULL context, no source, a radius outside 1 .. MUSICA_SCATTER_MAX_RADIUS, num = 0, num >= den,
+ * den > MUSICA_SCATTER_MAX_DEN, gcd(num, den) != 1, image_index >= batch, a failed allocation of the row plane. */
+int musica_alter_scatter(musica_ctx* ctx, uint32_t image_index, uint32_t radius, uint32_t num, uint32_t den);
 /* Test hook: the N x N integer draws of a noise alteration (k of COLLIMATOR / POISSON, for every pixel; the truncated noise of GAUSSIAN),
  * the same numbers musica_alter uses. Synchronous. */
 int musica_alter_draws(musica_ctx* ctx, const musica_alteration* spec, int32_t* dst);

@@ -313,6 +313,14 @@ void launch_blur_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int
 constexpr int kZoomMaxP = 32;   // MUSICA_ZOOM_MAX_P
 void launch_zoom_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, int p, int q);
 void launch_zoom_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int p, int q);
+// kernels_scatter.hip: harness.scatter(plane, (radius, num, den)), the exact veiling glare (the plane mixed with its tent x tent blur of
+// box radius `radius`, scatter fraction num / den), of a dense n x n plane into another through `plane32`, n x n u32 of scratch that the
+// row launch writes and the column launch reads (none of the three may overlap); any n in 1 .. 16384, 1 <= radius <= kScatterMaxRadius,
+// 1 <= num < den <= kScatterMaxDen
+constexpr int kScatterMaxRadius = 127;   // MUSICA_SCATTER_MAX_RADIUS
+constexpr int kScatterMaxDen = 64;       // MUSICA_SCATTER_MAX_DEN
+void launch_scatter_u16(hipStream_t st, const uint16_t* src, uint16_t* out, uint32_t* plane32, int n, int radius, int num, int den);
+void launch_scatter_u8(hipStream_t st, const uint8_t* src, uint8_t* out, uint32_t* plane32, int n, int radius, int num, int den);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -125,6 +125,8 @@ struct StudyState {
     uint32_t* d_alter_hist = nullptr;    // [768]
     double* d_alter_fill = nullptr;      // [1]
     int32_t* d_alter_draws = nullptr;    // [N * N], musica_alter_draws only
+    // musica_alter_scatter / musica_sim_scatter_reference: the row passes' plane between the two launches
+    uint32_t* d_scatter = nullptr;       // [N * N] (a slot's (N - 20)^2 use its start), allocated by the first scatter call
 };
 
 struct musica_ctx : DeviceBuffers {

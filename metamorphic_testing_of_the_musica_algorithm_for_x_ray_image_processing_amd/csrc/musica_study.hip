@@ -1,7 +1,7 @@
 // musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the four query calls
 // (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip), the ensemble accumulators
 // (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
+// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
@@ -73,6 +73,28 @@ static int zoom_check(const char* fn, uint32_t p, uint32_t q) {
     uint32_t a = p, b = q;
     while (b) { const uint32_t r = a % b; a = b; b = r; }
     if (a != 1) return fail("%s: zoom %u / %u is not in lowest terms (gcd %u)", fn, p, q, a);
+    return 1;
+}
+
+static_assert(kScatterMaxRadius == MUSICA_SCATTER_MAX_RADIUS && kScatterMaxDen == MUSICA_SCATTER_MAX_DEN,
+              "kernels_scatter.hip's u32 row plane and u64 numerator hold for the scatters of include/musica.h");
+
+// What both scatter calls refuse about (radius, num / den): harness.scatter's 1 <= radius <= MUSICA_SCATTER_MAX_RADIUS and
+// 1 <= num < den <= MUSICA_SCATTER_MAX_DEN in lowest terms.
+static int scatter_check(const char* fn, uint32_t radius, uint32_t num, uint32_t den) {
+    if (radius < 1 || radius > MUSICA_SCATTER_MAX_RADIUS) return fail("%s: radius %u out of range [1, %d]", fn, radius, MUSICA_SCATTER_MAX_RADIUS);
+    if (num == 0 || num >= den || den > MUSICA_SCATTER_MAX_DEN)
+        return fail("%s: scatter fraction %u / %u is not 1 <= num < den <= %d", fn, num, den, MUSICA_SCATTER_MAX_DEN);
+    uint32_t a = den, b = num;
+    while (b) { const uint32_t r = a % b; a = b; b = r; }
+    if (a != 1) return fail("%s: scatter fraction %u / %u is not in lowest terms (gcd %u)", fn, num, den, a);
+    return 1;
+}
+
+// The u32 plane between the two scatter launches, allocated on first use and freed with the context.
+static int scatter_plane(musica_ctx* c, const char* fn) {
+    const size_t nn = (size_t)c->N * c->N;
+    if (!ensure(c, &c->study.d_scatter, nn)) return fail("%s: device allocation of the %zu-byte row plane failed", fn, nn * sizeof(uint32_t));
     return 1;
 }
 
@@ -185,6 +207,17 @@ int musica_sim_zoom_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slo
     return sim_derive_slot(
         c, "musica_sim_zoom_reference", dst_slot, src_slot, [] { return 1; },   // nothing more to refuse
         [&](const uint8_t* src, uint8_t* dst) { launch_zoom_u8(c->stream, src, dst, (int)sim_side(c), (int)p, (int)q); });
+}
+
+int musica_sim_scatter_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t radius, uint32_t num, uint32_t den) {
+    if (!c) return fail("musica_sim_scatter_reference: ctx is NULL");
+    if (!scatter_check("musica_sim_scatter_reference", radius, num, den)) return 0;
+    return sim_derive_slot(
+        c, "musica_sim_scatter_reference", dst_slot, src_slot,
+        [&] { return hipSetDevice(c->p.device) == hipSuccess ? scatter_plane(c, "musica_sim_scatter_reference") : fail("musica_sim_scatter_reference: hipSetDevice failed"); },
+        [&](const uint8_t* src, uint8_t* dst) {
+            launch_scatter_u8(c->stream, src, dst, c->study.d_scatter, (int)sim_side(c), (int)radius, (int)num, (int)den);
+        });
 }
 
 int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]) {
@@ -897,6 +930,20 @@ int musica_alter_zoom(musica_ctx* c, uint32_t idx, uint32_t p, uint32_t q) {
     CHECK_CTX(c);
     if (!alter_keep_input(c, "musica_alter_zoom")) return 0;
     launch_zoom_u16(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, (int)p, (int)q);   // kernels_zoom.hip
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+int musica_alter_scatter(musica_ctx* c, uint32_t idx, uint32_t radius, uint32_t num, uint32_t den) {
+    if (!c) return fail("musica_alter_scatter: ctx is NULL");
+    if (!c->study.d_alter_src) return fail("musica_alter_scatter: no source plane (musica_alter_set_source)");
+    if (!scatter_check("musica_alter_scatter", radius, num, den)) return 0;
+    CHECK_IMG(c, idx);
+    CHECK_CTX(c);
+    if (!scatter_plane(c, "musica_alter_scatter")) return 0;
+    if (!alter_keep_input(c, "musica_alter_scatter")) return 0;
+    launch_scatter_u16(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->study.d_scatter, c->N, (int)radius, (int)num,
+                       (int)den);   // kernels_scatter.hip
     HIP_OK(hipGetLastError());
     return 1;
 }

@@ -45,6 +45,17 @@ BLURS = (1, 2, 4, 8)
 # not in the reference: the magnifications p / q of the scale rows (zoom), rows zoom_<p>_<q> of a study run with `zooms`: 1.05, 1.1,
 # 1.25, 1.5 and 2, five strengths as every alteration of the reference's script has
 ZOOMS = ((21, 20), (11, 10), (5, 4), (3, 2), (2, 1))
+# not in the reference: the scatter fractions a / b of the veiling-glare rows (scatter), rows scatter_<R>_<a>_<b> of a study run with
+# `scatters`: an extremity, 0.25, a chest (0.5 and 2 / 3) and an abdomen without a grid, five strengths as every alteration of the
+# reference's script has. SCATTERS(n) gives them the box radius of the image size.
+SCATTER_FRACTIONS = ((1, 10), (1, 4), (1, 2), (2, 3), (4, 5))
+
+
+def SCATTERS(n):
+    """The veils (R, a, b) of the scatter rows of a side-n image: SCATTER_FRACTIONS at R = clamp(round(127 n / 3072), 1, 127), the
+    tent of sigma 104 pixels at 3072 scaled with the image."""
+    r = min(max(int(round(127 * int(n) / 3072)), 1), mp.SCATTER_MAX_RADIUS)
+    return tuple((r, a, b) for a, b in SCATTER_FRACTIONS)
 
 
 def scaled(values, image_size):
@@ -173,6 +184,51 @@ def zoom(image, ratio):
     a = image.astype(np.uint64)
     top, bottom = (a[r][:, i] * g + a[r][:, i1] * f for r in (i, i1))       # the rows i_y and i_y+, folded along x
     return ((g[:, None] * top + f[:, None] * bottom + np.uint64(d * d // 2)) // np.uint64(d * d)).astype(image.dtype)
+
+
+def _box(acc, radius, axis):
+    """sum_{k = -R .. R} acc[clamp(i + k)] along `axis` of a uint64 array: np.pad(mode="edge"), then the (2R + 1)-window sum as the
+    difference of two entries of the padded array's cumulative sum."""
+    r = int(radius)
+    padded = np.pad(acc, [(r, r) if a == axis else (0, 0) for a in (0, 1)], mode="edge")   # the clamped indices
+    total = np.cumsum(padded, axis=axis, dtype=np.uint64)
+    total = np.concatenate([np.zeros_like(total[:1] if axis == 0 else total[:, :1]), total], axis=axis)
+    n = acc.shape[axis]
+    if axis == 0:
+        return total[2 * r + 1:2 * r + 1 + n] - total[:n]
+    return total[:, 2 * r + 1:2 * r + 1 + n] - total[:, :n]
+
+
+def scatter(image, spec):
+    """The exact wide veiling glare of a square 2-D uint16 or uint8 plane (not in the reference's script): scattered radiation under
+    automatic exposure control, a very wide, smooth veil that displaces primary signal at the scatter fraction SF = S / (S + P) = a / b.
+    spec = (R, a, b): the box radius 1 <= R <= SCATTER_MAX_RADIUS = 127 and integers 1 <= a < b <= SCATTER_MAX_DEN = 64 with
+    gcd(a, b) = 1, else ValueError before any work. With box_axis(A)[i] = sum_{k = -R .. R} A[clamp(i + k)], clamped to the plane (edge
+    replicated; each pass clamps its own input: np.pad(mode="edge") and a (2R + 1)-window sum), in uint64
+        V   = box_y(box_y(box_x(box_x(image))))          tent x tent, total weight W = (2R + 1)^4
+        out = ((b - a) W image + a V + (b W) // 2) // (b W)
+    ONE rounding, after the full sum, halves rounded up; nothing is rounded between the passes. The result has the input's dtype.
+      * The row and column operators commute: the order of the four passes changes nothing.
+      * After the two row passes a value is at most 255^2 * 65535 = 4 261 413 375 < 2^32 (the device's row-pass plane is u32).
+      * W <= 255^4 = 4 228 250 625 < 2^32.
+      * The full numerator is at most 65535 * 64 * 255^4, about 1.77e16 < 2^64: the column passes and the mix are u64. The cumulative
+        sums here stay below 255^3 * 65535 * (16384 + 254) < 2^64 for every side a context accepts.
+      * The weights are a convex combination: a constant plane is preserved, nothing saturates and nothing is clipped.
+      * The operator commutes exactly with all eight apply_symmetry elements.
+      * It does NOT commute with cropping, because the borders are clamped: within 2R pixels of the output plane's border the veiled
+        reference is built from clamped neighbours, so the registered region is inset by 2R (register_scatter, roi_scatter).
+      * The tent has sigma = sqrt(2R (R + 1) / 3) pixels: 104 at R = 127.
+    This is the contract of musica_alter_scatter and musica_sim_scatter_reference (include/musica.h), which are bit-identical to it."""
+    r, a, b = mp.scatter_spec(spec)
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype not in (np.uint16, np.uint8) or not image.size:
+        raise ValueError("scatter needs a non-empty square 2-D uint16 or uint8 plane, got %r %s" % (image.shape, image.dtype))
+    primary = image.astype(np.uint64)
+    veil = primary
+    for axis in (1, 1, 0, 0):     # rows twice, then columns twice: exact integers, so the order changes nothing
+        veil = _box(veil, r, axis)
+    w = (2 * r + 1) ** 4
+    return ((np.uint64((b - a) * w) * primary + np.uint64(a) * veil + np.uint64(b * w // 2)) // np.uint64(b * w)).astype(image.dtype)
 
 
 # ---- the vendor-processed reference image (script.py:395-411) ------------------------------------------
@@ -315,6 +371,20 @@ def roi_zoom(shape):
     return (0, 0, 0, 0, shape[1], shape[0])
 
 
+def register_scatter(alt, unalt, spec):
+    """The altered result against the unaltered result veiled like the alteration, both inset by 2R (as register_blur, carried to low
+    frequencies): within 2R pixels of the output plane's border the veiled reference is built from clamped neighbours, while the altered
+    output there came from real neighbours in the processing margin."""
+    r = 2 * mp.scatter_spec(spec)[0]
+    h, w = alt.shape
+    return alt[r:max(h - r, r), r:max(w - r, r)], scatter(unalt, spec)[r:max(h - r, r), r:max(w - r, r)]
+
+
+def roi_scatter(shape, spec):
+    """The full frame inset by 2R, as the region of a device-side comparison; None when a side falls under 7."""
+    return _inset((0, 0, 0, 0, shape[1], shape[0]), 2 * mp.scatter_spec(spec)[0])
+
+
 # ---- running the pipeline -------------------------------------------------------------------------
 
 class Runner:
@@ -414,7 +484,7 @@ VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a
 
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
-                  scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None):
+                  scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -449,6 +519,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         if not 1 <= r <= mp.BLUR_MAX_RADIUS:
             raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
     zooms = [mp.zoom_ratio(z) for z in (zooms or ())]
+    scatters = [mp.scatter_spec(s) for s in (scatters or ())]
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
@@ -458,7 +529,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
-        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, keys=keys, device_alterations=device_alterations)
+        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, keys=keys, device_alterations=device_alterations)
 
 
 # One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
@@ -472,7 +543,7 @@ Alteration = collections.namedtuple("Alteration", "name host dev region move noi
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4, blur and zoom rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur, zoom and scatter rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -504,6 +575,9 @@ def study_alterations(raw, rng, p, seed, shape, opt):
     for z in opt.zooms:
         yield Alteration("zoom_%d_%d" % z, lambda: zoom(raw, z), lambda: p.alter_zoom(z), lambda: roi_zoom(shape),
                          ("sim_zoom_reference", zoom, z))
+    for s in opt.scatters:
+        yield Alteration("scatter_%d_%d_%d" % s, lambda: scatter(raw, s), lambda: p.alter_scatter(s), lambda: roi_scatter(shape, s),
+                         ("sim_scatter_reference", scatter, s))
 
 
 class Scorer:
@@ -669,7 +743,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
-              blurs=None, zooms=None):
+              blurs=None, zooms=None, scatters=None):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -748,10 +822,19 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     frame (roi_zoom: no fill, nothing to crop) against the unaltered result magnified alike, which a processor that commutes with
     magnification would reproduce. On the device that reference goes into slot 1 and the magnified vendor image into slot 3
     (musica_sim_zoom_reference). They draw nothing from `rng` and take no ordinal; vendor, tone, scales and displacement apply to them
-    as to a d4 row."""
+    as to a d4 row.
+
+    scatters: veils (R, a, b) of the scatter rows (scatter; SCATTERS(n) for the fractions 1/10, 1/4, 1/2, 2/3 and 4/5 at the radius of
+    the image size), each 1 <= R <= SCATTER_MAX_RADIUS and 1 <= a < b <= SCATTER_MAX_DEN in lowest terms, else ValueError before any
+    work. None or empty adds nothing. Otherwise rows scatter_<R>_<a>_<b> follow the zoom_* rows: the raw image mixed with its tent x
+    tent blur of box radius R at the scatter fraction a / b (on the device: alter_scatter), "direct" against the unaltered result,
+    "registered" over the frame inset by 2R (roi_scatter) against the unaltered result veiled alike: blur's registered comparison
+    carried to low frequencies, what a linear, shift-invariant processor would not show (None when the inset frame has a side under
+    8). On the device that reference goes into slot 1 and the veiled vendor image into slot 3 (musica_sim_scatter_reference). They draw
+    nothing from `rng` and take no ordinal; vendor, tone, scales and displacement apply to them as to a d4 row."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
-                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms)
+                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -882,6 +965,21 @@ def zoom_list(text):
                                          % (mp.ZOOM_MAX_P, text, ": %s" % e if str(e) else ""))
 
 
+def scatter_list(text):
+    """--scatters' comma list of veils R:A/B: 1 <= R <= SCATTER_MAX_RADIUS, 1 <= A < B <= SCATTER_MAX_DEN in lowest terms."""
+    import argparse
+    try:
+        specs = []
+        for t in text.split(","):
+            radius, fraction = t.split(":")
+            a, b = fraction.split("/")
+            specs.append(mp.scatter_spec((int(radius), int(a), int(b))))
+        return tuple(specs)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError("expected a comma-separated list of veils R:A/B (1 <= R <= %d, 1 <= A < B <= %d, lowest terms), got %r%s"
+                                         % (mp.SCATTER_MAX_RADIUS, mp.SCATTER_MAX_DEN, text, ": %s" % e if str(e) else ""))
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Metamorphic study of raw images (or a seeded phantom) on the HIP MUSICA path")
@@ -909,6 +1007,11 @@ def main(argv=None):
                     help="add the rows zoom_<p>_<q>: the raw image magnified by P/Q about its centre (exact integer bilinear; 1 <= Q < P <= 32 "
                          "in lowest terms), compared directly and, over the whole frame, with the unaltered result magnified alike; without "
                          "a list, 21/20,11/10,5/4,3/2,2/1")
+    ap.add_argument("--scatters", nargs="?", const=True, default=None, type=scatter_list, metavar="R:A/B,R:A/B,...",
+                    help="add the rows scatter_<R>_<a>_<b>: the raw image under the exact veiling glare of scatter fraction A/B (1 <= A < B <= 64 "
+                         "in lowest terms) and box radius R (1 .. 127; the tent x tent veil has sigma = sqrt(2R(R+1)/3) pixels), compared "
+                         "directly and, inset by 2R, with the unaltered result veiled alike; without a list, 1/10,1/4,1/2,2/3,4/5 at "
+                         "R = round(127 * size / 3072)")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -989,6 +1092,8 @@ def main(argv=None):
         shift_args["blurs"] = args.blurs
     if args.zooms:
         shift_args["zooms"] = args.zooms
+    if args.scatters:
+        shift_args["scatters"] = SCATTERS(args.size) if args.scatters is True else args.scatters
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

@@ -152,6 +152,8 @@ class SimJointResult(C.Structure):
 SIM_MAX_RADIUS = 16         # MUSICA_SIM_MAX_RADIUS
 BLUR_MAX_RADIUS = 8         # MUSICA_BLUR_MAX_RADIUS
 ZOOM_MAX_P = 32             # MUSICA_ZOOM_MAX_P
+SCATTER_MAX_RADIUS = 127    # MUSICA_SCATTER_MAX_RADIUS
+SCATTER_MAX_DEN = 64        # MUSICA_SCATTER_MAX_DEN
 SIM_TILE = 64               # MUSICA_SIM_TILE
 
 
@@ -170,6 +172,25 @@ def zoom_ratio(zoom):
     if math.gcd(p, q) != 1:
         raise ValueError("zoom %d / %d is not in lowest terms" % (p, q))
     return p, q
+
+
+def scatter_spec(spec):
+    """(R, a, b) of a veil as harness.scatter and the library take it: the box radius 1 <= R <= SCATTER_MAX_RADIUS and the scatter
+    fraction a / b, integers 1 <= a < b <= SCATTER_MAX_DEN in lowest terms, else ValueError."""
+    try:
+        r, a, b = spec
+        if r != int(r) or a != int(a) or b != int(b):
+            raise TypeError
+        r, a, b = int(r), int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError("a scatter is a triple of integers (R, a, b), got %r" % (spec,))
+    if not 1 <= r <= SCATTER_MAX_RADIUS:
+        raise ValueError("scatter radius %d is not in 1 .. %d" % (r, SCATTER_MAX_RADIUS))
+    if not 1 <= a < b <= SCATTER_MAX_DEN:
+        raise ValueError("scatter fraction %d / %d is not 1 <= a < b <= %d" % (a, b, SCATTER_MAX_DEN))
+    if math.gcd(a, b) != 1:
+        raise ValueError("scatter fraction %d / %d is not in lowest terms" % (a, b))
+    return r, a, b
 
 
 class SimDisplaceResult(C.Structure):
@@ -368,6 +389,8 @@ ABI = {
     "musica_alter_blur": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "musica_sim_zoom_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_zoom": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_sim_scatter_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_alter_scatter": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -761,6 +784,11 @@ class MusicaProcessing:
         p, q = zoom_ratio(zoom)
         self._ok(self._lib.musica_sim_zoom_reference(self._h, int(dst_slot), int(src_slot), p, q), "musica_sim_zoom_reference")
 
+    def sim_scatter_reference(self, dst_slot, src_slot, spec):
+        """Reference slot `src_slot` as harness.scatter(slot, spec) (spec = (R, a, b): scatter_spec) into `dst_slot`, on the device."""
+        r, a, b = scatter_spec(spec)
+        self._ok(self._lib.musica_sim_scatter_reference(self._h, int(dst_slot), int(src_slot), r, a, b), "musica_sim_scatter_reference")
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -958,6 +986,12 @@ class MusicaProcessing:
         """harness.zoom(src, zoom): the exact bilinear magnification by p / q about the centre, zoom = (p, q) (zoom_ratio)."""
         p, q = zoom_ratio(zoom)
         self._ok(self._lib.musica_alter_zoom(self._h, int(image_index), p, q), "musica_alter_zoom")
+
+    def alter_scatter(self, spec, image_index=0):
+        """harness.scatter(src, spec): the source mixed with its tent x tent blur of box radius R at the scatter fraction a / b,
+        spec = (R, a, b) (scatter_spec)."""
+        r, a, b = scatter_spec(spec)
+        self._ok(self._lib.musica_alter_scatter(self._h, int(image_index), r, a, b), "musica_alter_scatter")
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""
