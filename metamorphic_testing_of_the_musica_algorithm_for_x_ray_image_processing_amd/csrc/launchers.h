@@ -1,5 +1,5 @@
 // launchers.h — host-callable launch wrappers implemented in the kernel files, plus the
-// argument blocks they share with the host code: the dispatch script in musica_ctx.hip and the study's entry points in musica_study.hip.
+// argument blocks they share with the host code: the step's launch sequence in musica_step.hip and the study's entry points in musica_study.hip.
 #pragma once
 
 #include <stdlib.h>

@@ -1,6 +1,10 @@
-// musica_ctx.h — the context behind include/musica.h's opaque musica_ctx and the helpers its two host files share: musica_ctx.hip
-// (create, the dispatch script, lanes, getters) and musica_study.hip (musica_sim_* / musica_alter_*). Internal: not installed.
+// musica_ctx.h — the context behind include/musica.h's opaque musica_ctx and what its host files share: musica_ctx.hip (create, queries,
+// getters, dumps), musica_step.hip (the form of a step and its launch sequence, graphs, autotune, lanes, the execute entry points),
+// musica_pipeline.hip (musica_pipeline_*) and musica_study.hip (musica_sim_* / musica_alter_*). Internal: not installed.
 #pragma once
+
+#include <math.h>
+#include <stdlib.h>
 
 #include <algorithm>
 #include <exception>
@@ -10,8 +14,13 @@
 
 using namespace musica;
 
+#define HIDDEN __attribute__((visibility("hidden")))
 // Records the message for musica_last_error, prints it and returns 0 (musica_ctx.hip).
-__attribute__((visibility("hidden"))) int fail(const char* fmt, ...);
+HIDDEN int fail(const char* fmt, ...);
+static inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return (v && *v) ? atoi(v) : dflt;
+}
 
 // No C++ exception may cross the extern "C" boundary (a ctypes / CLI caller would abort): entry points that allocate
 // host memory run their body under this guard and report through fail() like every other error.
@@ -135,7 +144,6 @@ struct musica_ctx : DeviceBuffers {
     int N, L, B;
     bool generic;
     int ref_order;           // MUSICA_FLAG_REFERENCE_ORDER: generic kernels in the shaders' literal 25-tap accumulation order
-    bool tuning = false;     // inside autotune(): launches are tagged so profilers keep them apart
     LevelDesc lv[MUSICA_MAX_LEVELS + 1];
     int min_chain_exact;
     int hist_cov;  // (N / 512) * 512
@@ -157,7 +165,7 @@ struct musica_ctx : DeviceBuffers {
     const uint16_t* graph_input[kGraphSlots] = {};    // path alternates between two device input buffers; callers may rotate a few of their own)
     uint64_t graph_used[kGraphSlots] = {};            // launch counter at the slot's last use (least recently used slot is recaptured)
     uint64_t graph_clock = 0;
-    int dag;                 // 0: one in-order stream (enqueue_linear); 2: two streams (enqueue_fork: the analysis beside the reduce tail)
+    int dag;                 // 0: one in-order stream (enqueue_one_stream); 2: two streams (enqueue_two_streams: the analysis beside the reduce tail)
     // device state shared by the whole context (the per-image buffers are the DeviceBuffers base)
     uint16_t* d_input2 = nullptr;      // second input buffer of the streaming path (musica_execute_stream), allocated on first use
     hipStream_t copy_stream = nullptr; // its H2D copies run here, under the previous batch's kernels
@@ -167,14 +175,14 @@ struct musica_ctx : DeviceBuffers {
     uint32_t* d_plot = nullptr;        // one MUSICA_HIST_RENDER_WIDTH x MUSICA_HIST_RENDER_HEIGHT rgba8 image (the RENDER_HISTS plots, on demand)
     bool fuse_gh;              // the level-0 expand launch accumulates the gradation histogram
     // The expand launches of levels 0 .. 2 compute the 5 x 5 RMS of their band image themselves (k_expand_fast<.., SD>) and the sdev +
-    // noise-histogram launches of those levels store nothing: 8 of a step's 48 bytes per input pixel. The whole-step scripts run that way
-    // (sd_active); the stage entry points, getters and dumps want the stored images: ensure_sdev() writes them on demand.
-    bool sd_fused, sd_active = false, sdev_stored = true;
+    // noise-histogram launches of those levels store nothing: 8 of a step's 48 bytes per input pixel. Whole steps run that way
+    // (StepForm::sd_levels); the stage entry points, getters and dumps want the stored images: ensure_sdev() writes them on demand.
+    bool sd_fused, sdev_stored = true;
     bool pair_rb_sdev;         // the one-stream script pairs the sdev pass of level i with reduce + band of level i + 1 in one launch (k_rb_sdev); MUSICA_PAIR_RB_SDEV
     bool sdev_one_launch;      // the sdev + noise-histogram passes of levels 0 .. 3 as ONE launch (k_sdev_hist_levels); MUSICA_SDEV_ONE_LAUNCH=0: one launch per marching level + one for the runs
     int rows_rb[MUSICA_MAX_LEVELS];   // its coarse rows per wavefront
     // Level 0's reduce + band launch of a whole-step script counts the level's noise histogram itself (k_reduce_band_hist) and the level-0
-    // sdev pass shrinks to the seam columns (musica_ctx.hip hist_in_rb). MUSICA_HIST_IN_RB: 0 never, 1 wherever the form exists, unset (-1):
+    // sdev pass shrinks to the seam columns (StepForm::hist_rows). MUSICA_HIST_IN_RB: 0 never, 1 wherever the form exists, unset (-1):
     // the one-stream steps large enough for segments of 16 coarse rows (hist_rb_rows()).
     int hist_in_rb;
     int hist_rb_rows;          // MUSICA_HIST_RB_ROWS: coarse rows per wavefront of that launch (a multiple of 8), 0: chosen from the step's size
@@ -196,7 +204,7 @@ struct musica_ctx : DeviceBuffers {
     // rows each wavefront marches per launch, per level (heuristic, then autotuned at create)
     int rows_expand[MUSICA_MAX_LEVELS], rows_sdev[4];
     // tunables
-    int expand_rows, sdev_rows, grad_groups, min_waves;
+    int expand_rows, sdev_rows, grad_groups;
     // profiling
     uint32_t profiling = 0;  // bit i set: bracket kernel family i with HIP events
     std::vector<ProfSpan> spans;
@@ -297,6 +305,39 @@ static hipError_t drelease(musica_ctx* c, T** buf) {
     *buf = nullptr;
     return hipSuccess;
 }
+
+// ---- the step (musica_step.hip) ----------------------------------------------------------------------------------------------
+// The form of the launches about to be enqueued: computed by step_form() at the top of whatever enqueues, never kept on the context
+// (rows_sdev changes under autotune, copy_rows and the image lanes).
+enum StepPurpose {
+    STEP_WHOLE,      // a whole step: the scripts, graph capture
+    STEP_STAGE,      // a single stage, ensure_sdev, the getters: one launch per level and stage, every sdev image stored and read
+    STEP_AUTOTUNE,   // the launches autotune times: a whole step's without the histogram-counting level-0 launch
+};
+struct StepForm {
+    uint32_t sd_levels = 0;   // bit i: level i's expand launch computes its sdev image itself, which this step neither stores nor reads
+    int hist_rows = 0;        // coarse rows per wavefront of the level-0 reduce + band launch that counts the noise histogram, 0: it does not
+    int tail;                 // the first level of the tiny tail, L: none
+    int pairs = 0;            // launches that pair level i's sdev pass with reduce + band of level i + 1 (one stream only)
+    bool sdev_one;            // the sdev passes still to run behind the pairs and the seam are one launch, else ...
+    int merged;               // ... one launch per level below this one and one for the 16-row-run levels from it on
+    bool sd(int i) const { return (sd_levels >> i) & 1u; }
+};
+HIDDEN StepForm step_form(const musica_ctx* c, StepPurpose purpose);
+HIDDEN bool rb_level(const musica_ctx* c, int i);
+// Launch geometry of a step of `batch` images before autotune: rows per wavefront of the expand, sdev and reduce + band launches
+// (results never depend on it); autotune() times candidates at create, copy_rows() hands its choice to an identical context.
+HIDDEN void default_rows(musica_ctx* c, int batch);
+HIDDEN void autotune(musica_ctx* c);
+HIDDEN void copy_rows(musica_ctx* dst, const musica_ctx* src);
+HIDDEN void collect_spans(musica_ctx* c);
+// The normalized image / the stored sdev images of levels whose hot path does not store them (getters, dumps, stage entry points).
+HIDDEN void ensure_normalized(musica_ctx* c);
+HIDDEN void ensure_sdev(musica_ctx* c);
+HIDDEN ExpandArgs expand_args(musica_ctx* c, const StepForm& f, int lvl, float* dst);
+static inline uint32_t cnr_scale(int S, int cnrS) { return (uint32_t)ceilf((float)S / (float)cnrS); }  // noise_reduction.comp:38
+static inline int gain_mode(int lvl) { return lvl > MUSICA_CNR_LEVEL ? GAIN_CONST : (lvl == MUSICA_CNR_LEVEL ? GAIN_RANGE : GAIN_CURVE); }
+static inline bool uses_nr(int lvl) { return lvl < MUSICA_CNR_LEVEL - 1; }  // currentLevel < cnrLevel - 1, src/vk_processing.cpp:1009-1016
 
 #define CHECK_CTX(c) do { if (!(c)) return fail("%s: ctx is NULL", __func__); if (hipSetDevice((c)->p.device) != hipSuccess) return fail("%s: hipSetDevice failed", __func__); } while (0)
 #define CHECK_IMG(c, idx) do { if ((int)(idx) >= (c)->B) return fail("%s: image_index %u >= batch %d", __func__, (unsigned)(idx), (c)->B); } while (0)

@@ -1,7 +1,7 @@
 // musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the four query calls
 // (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip), the ensemble accumulators
 // (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip) knows none of it.
+// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
