@@ -6,7 +6,9 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
   * displace, ensemble add / result and track / covariance at radii 3 and 16, 17 realisations in two adds, at N = 151: 131 x 131 outputs,
     3 x 3 tiles with a 3-pixel ragged tail (a masked last chunk), and one region narrower than 16 pixels (a tile of the ragged chunk only);
   * the six dst / src slot operations at N = 151, a symmetry with a transpose, a blur of radius 8, a zoom of 32 / 31 and a veil of radius
-    127 (wider than the slot) among them; and the same veil of the source plane into image 0 of the input buffer.
+    127 (wider than the slot) among them; and the same veil of the source plane into image 0 of the input buffer;
+  * the contrast-detail pair at N = 151: nine details of radius 1 .. 8 inserted into image 0 (a disc across a tile corner among them),
+    and the sums of the same details, shifted into the output plane, of image 1's output against slot 0.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -96,5 +98,9 @@ for name, slot in (("rotate", 1), ("transform", 2), ("blur", 3), ("remap", 4), (
 p.alter_set_source(phantom(N, 3, noise=4.0))
 p.alter_scatter((127, 2, 3))
 note("musica_alter_scatter", p.input_pixels()[0])
+details = [(30 + 40 * j - (7 if i == j else 0), 30 + 40 * i - (7 if i == j else 0), (1, 2, 4, 8, 1, 2, 4, 8, 1)[3 * i + j], (-512, 8, 128)[j]) for i in range(3) for j in range(3)]
+p.alter_details(details)
+note("musica_alter_details", p.input_pixels()[0])
+note("musica_sim_details", p.sim_details([(x - mp.OUT_MARGIN, y - mp.OUT_MARGIN, r, c) for x, y, r, c in details], 0, image_index=1))
 p.cleanup()
 print(json.dumps(digests))

@@ -714,6 +714,56 @@ int musica_alter_draws(musica_ctx* ctx, const musica_alteration* spec, int32_t* 
  * as the fills are; synchronous. */
 int musica_alter_percentile(musica_ctx* ctx, uint32_t x, uint32_t y, uint32_t w, uint32_t h, double q, double* out);
 
+/* ---- contrast-detail: inserted discs, measured where they lie (new, not in the reference) ----
+ * The one relation of the study that changes the input locally and measures the output locally: does a small low-contrast object come
+ * out visible, and equally so wherever it lies? harness.insert_details, harness.detail_statistics and harness.detail_summary are the
+ * contract; everything is integer and the device is bit-identical to them, from call to call as well (no atomics, one reduction order).
+ * A detail is (x, y, radius, contrast): an integer pixel centre, 1 <= radius <= MUSICA_DETAIL_MAX_RADIUS, 1 <= |contrast| <=
+ * MUSICA_DETAIL_MAX_CONTRAST. With d2 = (px - x)^2 + (py - y)^2 its zones are
+ *   disc   d2 <= r^2
+ *   ring   (r + 2)^2 <= d2 <= (2r + 2)^2
+ *   box    |px - x| <= 2r + 2 and |py - y| <= 2r + 2       (side 4r + 5)
+ * A list for a plane of side n holds 1 .. MUSICA_DETAIL_MAX details whose boxes lie inside [0, n)^2 and are pairwise disjoint
+ * (|xi - xj| > Roi + Roj or |yi - yj| > Roi + Roj with Ro = 2r + 2): a pixel belongs to at most one disc, so nothing depends on the
+ * list's order. Both entry points refuse every other list before any device work.
+ *   insertion   inside a disc out = min((v * (1024 - contrast) + 512) >> 10, 65535), every other pixel copied. contrast > 0 attenuates
+ *               as an absorbing object does, contrast < 0 brightens as a void does; ONE rounding, halves up; the largest intermediate is
+ *               65535 * 1536 + 512 < 2^32. With |contrast| <= 512 a non-zero pixel stays non-zero (v >= 1 gives (512 + 512) >> 10 = 1),
+ *               so an insertion never creates the zeros that the noise and gradation histograms treat specially.
+ *   statistics  per detail and for the disc and the ring: the pixel count n and the sums of a, b, a^2, b^2 and a b over the zone; over
+ *               the box the sum of (a - b)^2 and its pixel count (4r + 5)^2. `contrast` is not looked at.
+ * The attenuation is defined on detector counts, not on the graded 8-bit plane: there is no musica_sim_..._reference sibling that
+ * would insert details into a reference slot. */
+#define MUSICA_DETAIL_MAX_RADIUS 64
+#define MUSICA_DETAIL_MAX_CONTRAST 512
+#define MUSICA_DETAIL_MAX 1024
+typedef struct musica_detail {
+    int32_t x, y;                   /* the centre, in pixels of the plane the call names */
+    uint32_t radius;                /* 1 .. MUSICA_DETAIL_MAX_RADIUS */
+    int32_t contrast;               /* 1 <= |contrast| <= MUSICA_DETAIL_MAX_CONTRAST, in 1 / 1024 of the pixel's value */
+} musica_detail;
+typedef struct musica_sim_detail_result {   /* index 0: the disc, index 1: the ring */
+    uint64_t n[2];                  /* pixels of the zone */
+    uint64_t sum_a[2], sum_b[2];    /* sums over the zone of side a (the output) and side b (the slot) */
+    uint64_t sum_aa[2], sum_bb[2], sum_ab[2];
+    uint64_t box_ssd;               /* sum over the box of (a - b)^2 */
+    uint64_t box_pixels;            /* (4 radius + 5)^2 */
+} musica_sim_detail_result;
+/* insert_details(source plane, details) into image `image_index` of the input buffer: the details are in the N x N plane's
+ * coordinates. The kernel is enqueued on the ctx stream (the list is copied to the device first, which waits for what the stream
+ * holds), with musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step and no reference
+ * slot. One launch, 2 bytes read and 2 written per pixel (kernels_details.hip). Refused before any device work: a NULL context or list,
+ * no source, image_index >= batch, a count outside 1 .. MUSICA_DETAIL_MAX, a radius or contrast outside its limits, a box that leaves
+ * the plane, two boxes that are not disjoint. */
+int musica_alter_details(musica_ctx* ctx, uint32_t image_index, uint32_t count, const musica_detail* details);
+/* detail_statistics of side a, the 8-bit output of batch image `image_index` (quantised while read, exactly as musica_sim_compare
+ * reads it), against side b, reference slot `slot`: results[i] for details[i], in the coordinates of the (N - 20)^2 output plane.
+ * Synchronous. box_ssd equals musica_sim_compare's sq_diff_sum over the same (4r + 5)^2 region. Refused before any device work: a NULL
+ * context, list or results, a count outside 1 .. MUSICA_DETAIL_MAX, an image too small for the margin, a slot out of range or never
+ * written, image_index >= batch, a radius outside its limits, a box that leaves the plane, two boxes that are not disjoint. */
+int musica_sim_details(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t count, const musica_detail* details,
+                       musica_sim_detail_result* results);
+
 /* ---- device-resident output and stream ordering (new, not in the reference) ---- */
 
 /* What musica_export_out writes per image. */

@@ -321,6 +321,23 @@ constexpr int kScatterMaxRadius = 127;   // MUSICA_SCATTER_MAX_RADIUS
 constexpr int kScatterMaxDen = 64;       // MUSICA_SCATTER_MAX_DEN
 void launch_scatter_u16(hipStream_t st, const uint16_t* src, uint16_t* out, uint32_t* plane32, int n, int radius, int num, int den);
 void launch_scatter_u8(hipStream_t st, const uint8_t* src, uint8_t* out, uint32_t* plane32, int n, int radius, int num, int den);
+// kernels_details.hip: the contrast-detail relation. A detail (x, y, r, c) of a list that the caller has checked (limits, boxes inside
+// the plane and pairwise disjoint), packed: a plane side is at most 16384.
+constexpr int kDetailMaxRadius = 64;      // MUSICA_DETAIL_MAX_RADIUS
+constexpr int kDetailMaxContrast = 512;   // MUSICA_DETAIL_MAX_CONTRAST
+constexpr int kDetailMax = 1024;          // MUSICA_DETAIL_MAX
+constexpr int kDetailWords = 14;          // u64 of a musica_sim_detail_result
+struct PackedDetail {
+    uint32_t xy;   // x | y << 16
+    uint32_t rc;   // r | (c + 512) << 8
+};
+// harness.insert_details(src, details) of a dense n x n plane into another (the planes must not overlap); any n >= 1, `count` details
+// at d_details (device)
+void launch_alter_details(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const PackedDetail* d_details, int count);
+// harness.detail_statistics: one workgroup per detail. a_plane: the graded f32 plane at output pixel (0, 0), b_plane: the slot's u8
+// plane, pitches in elements, the details in the cropped output plane's coordinates; out: count x kDetailWords u64, all written
+void launch_sim_details(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedDetail* d_details, int count,
+                        unsigned long long* out);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

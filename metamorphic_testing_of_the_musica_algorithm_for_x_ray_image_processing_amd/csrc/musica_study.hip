@@ -1,7 +1,7 @@
-// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the four query calls
-// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip), the ensemble accumulators
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the five query calls
+// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_details.hip), the ensemble accumulators
 // (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
+// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_details.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
@@ -95,6 +95,44 @@ static int scatter_check(const char* fn, uint32_t radius, uint32_t num, uint32_t
 static int scatter_plane(musica_ctx* c, const char* fn) {
     const size_t nn = (size_t)c->N * c->N;
     if (!ensure(c, &c->study.d_scatter, nn)) return fail("%s: device allocation of the %zu-byte row plane failed", fn, nn * sizeof(uint32_t));
+    return 1;
+}
+
+static_assert(kDetailMaxRadius == MUSICA_DETAIL_MAX_RADIUS && kDetailMaxContrast == MUSICA_DETAIL_MAX_CONTRAST && kDetailMax == MUSICA_DETAIL_MAX,
+              "kernels_details.hip's tile list, u32 pixel and u32 partial sums hold for the details of include/musica.h");
+static_assert(sizeof(musica_sim_detail_result) == kDetailWords * sizeof(uint64_t), "k_sim_details writes a musica_sim_detail_result as its u64 words");
+
+// What both detail calls refuse about a list for a plane of side n (processing.detail_list): the count, each radius (and each contrast
+// when the call looks at it), boxes inside the plane, boxes pairwise disjoint. Fills `packed` for the device. No device work.
+static int details_check(const char* fn, uint32_t count, const musica_detail* ds, int n, bool with_contrast, std::vector<PackedDetail>& packed) {
+    if (count == 0 || count > MUSICA_DETAIL_MAX) return fail("%s: count %u out of range [1, %d]", fn, count, MUSICA_DETAIL_MAX);
+    packed.resize(count);
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_detail& d = ds[i];
+        if (d.radius < 1 || d.radius > MUSICA_DETAIL_MAX_RADIUS) return fail("%s: detail %u: radius %u out of range [1, %d]", fn, i, d.radius, MUSICA_DETAIL_MAX_RADIUS);
+        if (with_contrast && (d.contrast == 0 || d.contrast < -MUSICA_DETAIL_MAX_CONTRAST || d.contrast > MUSICA_DETAIL_MAX_CONTRAST))
+            return fail("%s: detail %u: contrast %d is not 1 <= |contrast| <= %d", fn, i, d.contrast, MUSICA_DETAIL_MAX_CONTRAST);
+        const int64_t ro = 2 * (int64_t)d.radius + 2;
+        if (d.x - ro < 0 || d.y - ro < 0 || d.x + ro >= n || d.y + ro >= n)
+            return fail("%s: detail %u: the box (%d, %d) +- %d leaves the %d x %d plane", fn, i, d.x, d.y, (int)ro, n, n);
+        const int c = with_contrast ? d.contrast : 0;
+        packed[i] = {(uint32_t)d.x | ((uint32_t)d.y << 16), d.radius | ((uint32_t)(c + 512) << 8)};
+    }
+    for (uint32_t i = 0; i < count; i++)
+        for (uint32_t j = i + 1; j < count; j++) {
+            const int64_t reach = 2 * ((int64_t)ds[i].radius + ds[j].radius) + 4;
+            if (std::abs((int64_t)ds[i].x - ds[j].x) <= reach && std::abs((int64_t)ds[i].y - ds[j].y) <= reach)
+                return fail("%s: the boxes of details %u and %u are not disjoint", fn, i, j);
+        }
+    return 1;
+}
+
+// The call's list on the device: copied on the stream, behind the kernels that still read the last call's, and `packed` is free again
+// when this returns.
+static int details_upload(musica_ctx* c, const char* fn, const std::vector<PackedDetail>& packed) {
+    if (!ensure(c, &c->study.d_details, MUSICA_DETAIL_MAX)) return fail("%s: device allocation of the detail list failed", fn);
+    HIP_OK(hipMemcpyAsync(c->study.d_details, packed.data(), packed.size() * sizeof(PackedDetail), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
     return 1;
 }
 
@@ -577,6 +615,31 @@ int musica_sim_multiscale(musica_ctx* c, uint32_t count, const musica_sim_query*
     ABI_CATCH("musica_sim_multiscale")
 }
 
+// ---- the contrast-detail measurement (musica_sim_details, include/musica.h; kernels_details.hip) ----------------------------------------
+int musica_sim_details(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count, const musica_detail* details, musica_sim_detail_result* out) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_details: ctx is NULL");
+    if (!details || !out) return fail("musica_sim_details: details or results is NULL");
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_details: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_details: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    if (!c->study.written[slot]) return fail("musica_sim_details: slot %u was never written", slot);
+    CHECK_IMG(c, idx);
+    std::vector<PackedDetail> packed;
+    if (!details_check("musica_sim_details", count, details, (int)sim_side(c), false, packed)) return 0;
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!ensure(c, &st.d_detail_out, (size_t)MUSICA_DETAIL_MAX * kDetailWords)) return fail("musica_sim_details: device allocation failed");
+    if (!details_upload(c, "musica_sim_details", packed)) return 0;
+    const int pitch = c->lv[0].pitch;
+    launch_sim_details(c->stream, image_slice(c, c->d_graded, idx) + (size_t)MUSICA_OUT_MARGIN * pitch + MUSICA_OUT_MARGIN, pitch, st.slot[slot],
+                       (int)sim_side(c), st.d_details, (int)count, st.d_detail_out);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out, st.d_detail_out, (size_t)count * sizeof(musica_sim_detail_result), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+    ABI_CATCH("musica_sim_details")
+}
+
 // ---- ensemble statistics (musica_sim_ensemble_*, include/musica.h; kernels_ensemble.hip) ------------------------------------------------
 int musica_sim_ensemble_reset(musica_ctx* c) {
     ABI_TRY
@@ -946,6 +1009,23 @@ int musica_alter_scatter(musica_ctx* c, uint32_t idx, uint32_t radius, uint32_t 
                        (int)den);   // kernels_scatter.hip
     HIP_OK(hipGetLastError());
     return 1;
+}
+
+int musica_alter_details(musica_ctx* c, uint32_t idx, uint32_t count, const musica_detail* details) {
+    ABI_TRY
+    if (!c) return fail("musica_alter_details: ctx is NULL");
+    if (!details) return fail("musica_alter_details: details is NULL");
+    if (!c->study.d_alter_src) return fail("musica_alter_details: no source plane (musica_alter_set_source)");
+    CHECK_IMG(c, idx);
+    std::vector<PackedDetail> packed;
+    if (!details_check("musica_alter_details", count, details, c->N, true, packed)) return 0;
+    CHECK_CTX(c);
+    if (!details_upload(c, "musica_alter_details", packed)) return 0;
+    if (!alter_keep_input(c, "musica_alter_details")) return 0;
+    launch_alter_details(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, c->study.d_details, (int)count);   // kernels_details.hip
+    HIP_OK(hipGetLastError());
+    return 1;
+    ABI_CATCH("musica_alter_details")
 }
 
 int musica_alter_draws(musica_ctx* c, const musica_alteration* s, int32_t* dst) {

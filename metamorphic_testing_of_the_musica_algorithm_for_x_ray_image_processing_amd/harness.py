@@ -58,6 +58,46 @@ def SCATTERS(n):
     return tuple((r, a, b) for a, b in SCATTER_FRACTIONS)
 
 
+# not in the reference: the contrast-detail rows (insert_details), rows cd_<c> of a study run with `details`: discs of the radii
+# DETAIL_RADII on a grid (detail_grid), one row per contrast c / 1024 = 0.8 % .. 12.5 %, five strengths as every alteration of the
+# reference's script has. DETAILS(n) gives the five grids of the image size.
+DETAIL_RADII = (1, 2, 4, 8, 16, 32)
+DETAIL_CONTRASTS = (8, 16, 32, 64, 128)
+
+
+def detail_grid(n, contrast, radii=None):
+    """The study's contrast-detail phantom for a raw image of side n: G x G details of one contrast on a square grid inside the output
+    plane's footprint. With B = PROCESSING_MARGIN and m = n - 2B, `radii` defaults to the longest prefix of DETAIL_RADII of length k
+    with m // (4 r_last + 5) >= k; G = min(m // (4 r_max + 5), 32) // k * k (ValueError if 0), the cell C = m // G, and detail (i, j),
+    i, j < G, row i first, is (B + j C + C // 2, B + i C + C // 2, radii[(i + j) % k], contrast): the diagonal assignment puts every
+    radius G / k times in every row and every column of the grid, so in every band of the frame. A box has side 4r + 5 <= C, so the
+    boxes are disjoint and lie inside [B, n - B)^2: shifted by -B (output_details) the list is valid for the output plane."""
+    n, b = int(n), PROCESSING_MARGIN
+    m = n - 2 * b
+    if radii is None:
+        k = 0
+        while k < len(DETAIL_RADII) and m // (4 * DETAIL_RADII[k] + 5) >= k + 1:
+            k += 1
+        radii = DETAIL_RADII[:k]
+    radii = tuple(int(r) for r in radii)
+    k = len(radii)
+    g = min(m // (4 * max(radii) + 5), 32) // k * k if k else 0
+    if g <= 0:
+        raise ValueError("a side of %d pixels holds no grid of the radii %r" % (n, radii))
+    c = m // g
+    return mp.detail_list([(b + j * c + c // 2, b + i * c + c // 2, radii[(i + j) % k], contrast) for i in range(g) for j in range(g)], n)
+
+
+def output_details(details):
+    """A raw plane's details in the coordinates of the output plane (the frame cropped by PROCESSING_MARGIN on every side)."""
+    return tuple((x - PROCESSING_MARGIN, y - PROCESSING_MARGIN, r, c) for x, y, r, c in details)
+
+
+def DETAILS(n):
+    """The five grids of the cd_ rows of a side-n image: detail_grid(n, c) for c in DETAIL_CONTRASTS."""
+    return tuple(detail_grid(n, c) for c in DETAIL_CONTRASTS)
+
+
 def scaled(values, image_size):
     """The reference's pixel-valued grids scaled from 3072 to `image_size`."""
     return [max(1, int(round(v * image_size / REF_IMAGE_SIZE))) for v in values]
@@ -484,7 +524,8 @@ VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a
 
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
-                  scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None):
+                  scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
+                  detail_tables=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -520,30 +561,35 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
             raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
     zooms = [mp.zoom_ratio(z) for z in (zooms or ())]
     scatters = [mp.scatter_spec(s) for s in (scatters or ())]
+    if details is not None:   # each grid is valid for the raw plane and, shifted, for the output plane
+        details = [mp.detail_list(g, n) for g in details]
+        for g in details:
+            mp.detail_list(output_details(g), n - 2 * PROCESSING_MARGIN)
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
-           (("ensemble",) if ensemble else ())
+           (("ensemble",) if ensemble else ()) + (("details",) if details is not None else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
-        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, keys=keys, device_alterations=device_alterations)
+        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, details=details or [], detail_tables=bool(detail_tables),
+        keys=keys, device_alterations=device_alterations)
 
 
 # One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
 # region() the region of the registered comparison (None, or no region at all as for the noise rows: no registration); move = (the
 # context's method, the host's function, their parameter), which both move a reference plane as the alteration moves the input: the
 # registered comparison is then against the moved plane; noise = (the row's ordinal, alter(context, stream, image_index)) for the rows
-# that draw, what their ensembles repeat.
-Alteration = collections.namedtuple("Alteration", "name host dev region move noise", defaults=(None, None, None))
+# that draw, what their ensembles repeat; details = the raw plane's detail list of a cd_ row, measured where the details lie.
+Alteration = collections.namedtuple("Alteration", "name host dev region move noise details", defaults=(None, None, None, None))
 
 
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4, blur, zoom and scatter rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur, zoom, scatter and cd rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -578,6 +624,8 @@ def study_alterations(raw, rng, p, seed, shape, opt):
     for s in opt.scatters:
         yield Alteration("scatter_%d_%d_%d" % s, lambda: scatter(raw, s), lambda: p.alter_scatter(s), lambda: roi_scatter(shape, s),
                          ("sim_scatter_reference", scatter, s))
+    for g in opt.details:
+        yield Alteration("cd_%d" % g[0][3], lambda: insert_details(raw, g), lambda: p.alter_details(g), details=g)
 
 
 class Scorer:
@@ -621,7 +669,13 @@ class DeviceScorer(Scorer):
             getattr(self.proc, method)(SLOT_VENDOR_ROTATED, SLOT_VENDOR, parameter)
 
     def similarities(self, comparisons):
-        return [{k: r[k] for k in mp.SIM_METRICS} for r in self.proc.sim_compare([(0, slot) + region for slot, region in comparisons])]
+        self.compared = self.proc.sim_compare([(0, slot) + region for slot, region in comparisons])   # details() reads the direct one's integers
+        return [{k: r[k] for k in mp.SIM_METRICS} for r in self.compared]
+
+    def details(self, details):
+        """One musica_sim_details call against the unaltered result; the full frame's integers are the row's direct comparison's."""
+        direct = self.compared[0]
+        return detail_row(details, self.proc.sim_details(details, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.detail_tables)
 
     def tone(self, comparisons):
         """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
@@ -678,6 +732,11 @@ class HostScorer(Scorer):
 
     def similarities(self, comparisons):
         return [similarities(*self.sides(*c)) for c in comparisons]
+
+    def details(self, details):
+        a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
+        return detail_row(details, detail_statistics(self.out, self.planes[SLOT_UNALTERED], details), int(((a - b) ** 2).sum()), a.size,
+                          self.opt.detail_tables)
 
     def tone(self, comparisons):
         return [tone_similarities(*self.sides(*c)) for c in comparisons]
@@ -743,7 +802,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
-              blurs=None, zooms=None, scatters=None):
+              blurs=None, zooms=None, scatters=None, details=None, detail_tables=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -831,10 +890,24 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     "registered" over the frame inset by 2R (roi_scatter) against the unaltered result veiled alike: blur's registered comparison
     carried to low frequencies, what a linear, shift-invariant processor would not show (None when the inset frame has a side under
     8). On the device that reference goes into slot 1 and the veiled vendor image into slot 3 (musica_sim_scatter_reference). They draw
-    nothing from `rng` and take no ordinal; vendor, tone, scales and displacement apply to them as to a d4 row."""
+    nothing from `rng` and take no ordinal; vendor, tone, scales and displacement apply to them as to a d4 row.
+
+    details: contrast-detail grids, each a detail list (x, y, r, c) for the raw plane (processing.detail_list; DETAILS(n) for the five
+    contrasts 0.8 % .. 12.5 % on detail_grid's phantom) that is also valid for the output plane when shifted by the margin
+    (output_details), else ValueError before any work. None adds nothing. Otherwise rows cd_<c> (c: the grid's first contrast) follow
+    the scatter_* rows: the raw image with the grid's discs inserted (insert_details; on the device: alter_details), "direct" scored
+    as for every row, "registered" None (nothing moved, as for the noise rows), and every row of the study gains "details": None
+    except in the cd_ rows, where it is detail_row's dict of the details measured where they lie against the unaltered result
+    (detail_statistics; on the device one musica_sim_details call behind the row's musica_sim_compare, whose exact sq_diff_sum of the
+    full frame gives outside_mse): per radius the count and the mean, min, max and population std over the positions of contrast,
+    cnr, rose and halo, and outside_mse. Host and device summarise exact integers with one function, so "details" is equal to the
+    last bit on every path. detail_tables: the dict also carries "per_detail". The rows draw nothing from `rng` and take no ordinal;
+    vendor, tone, scales and displacement apply to "direct" as elsewhere. Nothing is asserted about visibility: these are findings.
+    Three relations read off a cd_ study: locality (outside_mse near 0), monotonicity (more c, more contrast, at every radius) and
+    position invariance (a small std over the positions); where MUSICA's local gains break the last one is the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
-                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters)
+                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -867,6 +940,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             shifted = [(key + "_shift", (slot, _inset(region, opt.displacement))) for key, (slot, region) in own]
             shifted = [(key, c) for key, c in shifted if c[1] is not None]
             out.update(zip([key for key, _ in shifted], scorer.shifts([c for _, c in shifted])))
+        if alteration is not None and alteration.details:
+            out["details"] = scorer.details(output_details(alteration.details))
         out["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         if eproc is not None:
             out["ensemble"] = ensemble_of(eproc, alteration.noise, registered[1] if registered else None, full, opt)
@@ -1012,6 +1087,12 @@ def main(argv=None):
                          "in lowest terms) and box radius R (1 .. 127; the tent x tent veil has sigma = sqrt(2R(R+1)/3) pixels), compared "
                          "directly and, inset by 2R, with the unaltered result veiled alike; without a list, 1/10,1/4,1/2,2/3,4/5 at "
                          "R = round(127 * size / 3072)")
+    ap.add_argument("--details", action="store_true",
+                    help="add the rows cd_<c>: discs of radius 1 .. 32 inserted on a grid (detail_grid) at the contrasts c / 1024 = 0.8 %% .. "
+                         "12.5 %%, measured where they lie (contrast, cnr, halo per radius; the change away from them), written to "
+                         "contrast_detail.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_details, "
+                         "musica_alter_details)")
+    ap.add_argument("--detail-tables", action="store_true", help="with --details: keep every detail's numbers in the rows (\"per_detail\")")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -1039,6 +1120,8 @@ def main(argv=None):
     ap.add_argument("--covariance-maps", metavar="DIR",
                     help="with --covariance: one 8-bit BMP per noise row into DIR: the centred noise power spectrum, log-scaled")
     args = ap.parse_args(argv)
+    if args.detail_tables and not args.details:
+        ap.error("--detail-tables keeps what --details measures: give --details")
     if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
         ap.error("--covariance takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
     if args.covariance and not args.ensemble:
@@ -1094,6 +1177,8 @@ def main(argv=None):
         shift_args["zooms"] = args.zooms
     if args.scatters:
         shift_args["scatters"] = SCATTERS(args.size) if args.scatters is True else args.scatters
+    if args.details:
+        shift_args.update(details=DETAILS(args.size), detail_tables=args.detail_tables)
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

@@ -589,3 +589,120 @@ def nps_map(table, realisations, pixels):
     v = np.log1p(np.maximum(np.fft.fftshift(noise_power_spectrum(table, realisations, pixels)), 0.0))
     top = float(v.max())
     return np.zeros(v.shape, dtype=np.uint8) if top == 0.0 else np.rint(255.0 * v / top).astype(np.uint8)
+
+
+# ---- contrast-detail: inserted discs, measured where they lie (not in the reference's script) ------------------------------------------
+# Every other relation of the study perturbs the whole frame and asks how much the output changed. A contrast-detail phantom, discs of
+# graded size and contrast, asks what MUSICA exists to answer: does a small low-contrast object of the raw image come out visible, and
+# equally so wherever it lies? A detail is (x, y, r, c): an integer pixel centre, a radius 1 <= r <= DETAIL_MAX_RADIUS and a contrast
+# 1 <= |c| <= DETAIL_MAX_CONTRAST in 1 / 1024 of the pixel's value. With d2 = (px - x)^2 + (py - y)^2 its zones are the disc
+# d2 <= r^2, the ring (r + 2)^2 <= d2 <= (2r + 2)^2 and the box |px - x|, |py - y| <= Ro = 2r + 2 of side 4r + 5. The boxes of a list
+# lie inside the plane and are pairwise disjoint (processing.detail_list), so a pixel belongs to at most one disc and one box and
+# nothing depends on the list's order. These functions are the contract of musica_alter_details and musica_sim_details
+# (include/musica.h), which are bit-identical to them.
+
+def detail_zones(r):
+    """(disc, ring): the boolean masks of a radius-r detail's two zones over its (4r + 5)^2 box, from the integer d2."""
+    r = int(r)
+    ro = 2 * r + 2
+    d = np.arange(-ro, ro + 1, dtype=np.int64)
+    d2 = d[:, None] ** 2 + d[None, :] ** 2
+    return d2 <= r * r, (d2 >= (r + 2) ** 2) & (d2 <= ro * ro)
+
+
+def insert_details(image, details):
+    """The square 2-D uint16 plane with the discs of `details` (processing.detail_list for its side, else ValueError before any work)
+    inserted: inside each disc
+        out = min((v * (1024 - c) + 512) >> 10, 65535)
+    and every other pixel copied. c > 0 attenuates, as an absorbing object does; c < 0 brightens, as a void does. ONE rounding, halves
+    up; the largest intermediate is 65535 * 1536 + 512 < 2^32. With |c| <= 512 a non-zero pixel stays non-zero: v >= 1 gives at least
+    (512 + 512) >> 10 = 1. Zeros trigger the early exits of the noise and gradation histograms, so an insertion never creates one. The
+    boxes are disjoint, so a pixel belongs to at most one disc and the result does not depend on the list's order."""
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype != np.uint16 or not image.size:
+        raise ValueError("insert_details needs a non-empty square 2-D uint16 plane, got %r %s" % (image.shape, image.dtype))
+    details = mp.detail_list(details, image.shape[0])
+    out = image.copy()
+    for x, y, r, c in details:
+        ro = 2 * r + 2
+        disc = detail_zones(r)[0]
+        box = out[y - ro:y + ro + 1, x - ro:x + ro + 1]      # a view: the disc's pixels are rewritten in place
+        v = box[disc].astype(np.uint64)
+        box[disc] = np.minimum((v * np.uint64(1024 - c) + np.uint64(512)) >> np.uint64(10), np.uint64(65535)).astype(np.uint16)
+    return out
+
+
+def detail_statistics(a, b, details):
+    """The exact sums of every detail of `details` (in the planes' coordinates; c is not looked at) over two square uint8 planes of equal
+    shape: a list of dicts of Python ints, "disc" and "ring" each with n, sum_a, sum_b, sum_aa, sum_bb, sum_ab over the zone, and
+    box_ssd = sum over the box of (a - b)^2 with box_pixels = (4r + 5)^2: what musica_sim_details returns."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or a.shape != b.shape or a.shape[0] != a.shape[1] or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("detail_statistics needs two square 2-D uint8 planes of equal shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    details = mp.detail_list(details, a.shape[0], with_contrast=False)
+    out = []
+    for x, y, r, _ in details:
+        ro = 2 * r + 2
+        pa = a[y - ro:y + ro + 1, x - ro:x + ro + 1].astype(np.int64)
+        pb = b[y - ro:y + ro + 1, x - ro:x + ro + 1].astype(np.int64)
+        d = {}
+        for zone, mask in zip(mp.DETAIL_ZONES, detail_zones(r)):
+            za, zb = pa[mask], pb[mask]
+            d[zone] = {"n": int(mask.sum()), "sum_a": int(za.sum()), "sum_b": int(zb.sum()), "sum_aa": int((za * za).sum()),
+                       "sum_bb": int((zb * zb).sum()), "sum_ab": int((za * zb).sum())}
+        d["box_ssd"] = int(((pa - pb) ** 2).sum())
+        d["box_pixels"] = int(pa.size)
+        out.append(d)
+    return out
+
+
+DETAIL_KEYS = ("contrast", "halo", "texture", "cnr", "rose", "local_mse")   # detail_summary's numbers of one detail
+DETAIL_NOISE_FLOOR = 1.0 / math.sqrt(12.0)                                  # the rms of 8-bit quantisation
+
+
+def detail_summary(stats):
+    """What the study reports of each detail, from detail_statistics' (or musica_sim_details') exact integers: one function for every
+    study path, so the paths agree to the last bit. Per detail, in f64 (each quotient of two integers is one correctly rounded division):
+        contrast   (mean_disc a - mean_ring a) - (mean_disc b - mean_ring b): the anatomy's own disc - ring difference is removed
+        halo       mean_ring (a - b) = (sum_a - sum_b) / n over the ring: the rebound around the detail
+        texture    sqrt(max(var_ring b, 0)), the population variance (n sum_bb - sum_b^2) / n^2
+        cnr        contrast / max(texture, 1 / sqrt(12)): the floor is the 8-bit quantisation noise
+        rose       cnr * sqrt(n_disc)
+        local_mse  box_ssd / box_pixels
+    No visibility threshold is fixed here: these are findings."""
+    out = []
+    for s in stats:
+        d, g = s["disc"], s["ring"]
+        contrast = (d["sum_a"] / d["n"] - g["sum_a"] / g["n"]) - (d["sum_b"] / d["n"] - g["sum_b"] / g["n"])
+        texture = math.sqrt(max((g["n"] * g["sum_bb"] - g["sum_b"] * g["sum_b"]) / (g["n"] * g["n"]), 0.0))
+        cnr = contrast / max(texture, DETAIL_NOISE_FLOOR)
+        out.append({"contrast": contrast, "halo": (g["sum_a"] - g["sum_b"]) / g["n"], "texture": texture, "cnr": cnr,
+                    "rose": cnr * math.sqrt(d["n"]), "local_mse": s["box_ssd"] / s["box_pixels"]})
+    return out
+
+
+DETAIL_ROW_KEYS = ("contrast", "cnr", "rose", "halo")     # what a cd_ row's "details" gathers per radius
+DETAIL_ROW_STATS = ("mean", "min", "max", "std")
+
+
+def detail_row(details, stats, sq_diff_sum, pixels, tables=False):
+    """A cd_ row's "details" value from the row's details (their radii), their exact sums and the full frame's exact sum of squared
+    differences over `pixels` pixels: {"radii": {r: {"count", and for each of DETAIL_ROW_KEYS its mean, min, max and population std over
+    the positions of the radius-r details}}, in ascending r, "outside_mse": (sq_diff_sum - sum box_ssd) / (pixels - sum box_pixels), the
+    locality statistic (what changed away from every detail's neighbourhood)}, with tables=True also "per_detail": the (x, y, r, c) and
+    detail_summary's numbers of every detail, in the list's order."""
+    summary = detail_summary(stats)
+    radii = {}
+    for r in sorted(set(d[2] for d in details)):
+        group = [s for d, s in zip(details, summary) if d[2] == r]
+        radii[r] = {"count": len(group)}
+        for k in DETAIL_ROW_KEYS:
+            v = [s[k] for s in group]
+            mean = math.fsum(v) / len(v)
+            radii[r][k] = {"mean": mean, "min": min(v), "max": max(v), "std": math.sqrt(math.fsum((x - mean) * (x - mean) for x in v) / len(v))}
+    boxes, inside = sum(s["box_ssd"] for s in stats), sum(s["box_pixels"] for s in stats)
+    outside = int(pixels) - inside    # 0 only when one box is the whole plane
+    out = {"radii": radii, "outside_mse": (int(sq_diff_sum) - boxes) / outside if outside else 0.0}
+    if tables:
+        out["per_detail"] = [dict(s, x=d[0], y=d[1], r=d[2], c=d[3]) for d, s in zip(details, summary)]
+    return out

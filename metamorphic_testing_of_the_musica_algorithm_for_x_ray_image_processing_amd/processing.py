@@ -155,6 +155,9 @@ ZOOM_MAX_P = 32             # MUSICA_ZOOM_MAX_P
 SCATTER_MAX_RADIUS = 127    # MUSICA_SCATTER_MAX_RADIUS
 SCATTER_MAX_DEN = 64        # MUSICA_SCATTER_MAX_DEN
 SIM_TILE = 64               # MUSICA_SIM_TILE
+DETAIL_MAX_RADIUS = 64      # MUSICA_DETAIL_MAX_RADIUS
+DETAIL_MAX_CONTRAST = 512   # MUSICA_DETAIL_MAX_CONTRAST
+DETAIL_MAX = 1024           # MUSICA_DETAIL_MAX
 
 
 def zoom_ratio(zoom):
@@ -191,6 +194,60 @@ def scatter_spec(spec):
     if math.gcd(a, b) != 1:
         raise ValueError("scatter fraction %d / %d is not in lowest terms" % (a, b))
     return r, a, b
+
+
+def detail_list(details, n, with_contrast=True):
+    """The details (x, y, r, c) of a contrast-detail list for a plane of side n as harness.insert_details, harness.detail_statistics and
+    the library take it, a tuple of tuples of ints, else ValueError: 1 .. DETAIL_MAX details of integers, 1 <= r <= DETAIL_MAX_RADIUS,
+    1 <= |c| <= DETAIL_MAX_CONTRAST (with_contrast=False: c is not looked at, as the measurement does not), every box |px - x|,
+    |py - y| <= 2r + 2 inside [0, n)^2 and the boxes pairwise disjoint."""
+    try:
+        out = []
+        for d in details:
+            x, y, r, c = d
+            if x != int(x) or y != int(y) or r != int(r) or c != int(c):
+                raise TypeError
+            out.append((int(x), int(y), int(r), int(c)))
+    except (TypeError, ValueError):
+        raise ValueError("a detail list holds quadruples of integers (x, y, r, c), got %r" % (details,))
+    n = int(n)
+    if not 1 <= len(out) <= DETAIL_MAX:
+        raise ValueError("a detail list holds 1 .. %d details, got %d" % (DETAIL_MAX, len(out)))
+    for i, (x, y, r, c) in enumerate(out):
+        if not 1 <= r <= DETAIL_MAX_RADIUS:
+            raise ValueError("detail %d: radius %d is not in 1 .. %d" % (i, r, DETAIL_MAX_RADIUS))
+        if with_contrast and not 1 <= abs(c) <= DETAIL_MAX_CONTRAST:
+            raise ValueError("detail %d: contrast %d is not 1 <= |c| <= %d" % (i, c, DETAIL_MAX_CONTRAST))
+        ro = 2 * r + 2
+        if x - ro < 0 or y - ro < 0 or x + ro >= n or y + ro >= n:
+            raise ValueError("detail %d: the box (%d, %d) +- %d leaves the %d x %d plane" % (i, x, y, ro, n, n))
+    a = np.array(out, dtype=np.int64)
+    reach = (2 * a[:, 2] + 2)[:, None] + (2 * a[:, 2] + 2)[None, :]
+    meet = (np.abs(a[:, 0][:, None] - a[:, 0][None, :]) <= reach) & (np.abs(a[:, 1][:, None] - a[:, 1][None, :]) <= reach)
+    np.fill_diagonal(meet, False)
+    if meet.any():
+        i, j = np.argwhere(meet)[0]
+        raise ValueError("the boxes of details %d and %d are not disjoint" % (i, j))
+    return tuple(out)
+
+
+class Detail(C.Structure):
+    """musica_detail: a disc of `radius` about the integer pixel centre (x, y), of `contrast` / 1024."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("radius", C.c_uint32), ("contrast", C.c_int32)]
+
+
+DETAIL_ZONES = ("disc", "ring")   # index 0 and 1 of a musica_sim_detail_result's pairs
+DETAIL_SUMS = ("n", "sum_a", "sum_b", "sum_aa", "sum_bb", "sum_ab")
+
+
+class SimDetailResult(C.Structure):
+    """musica_sim_detail_result: the exact sums of one detail's disc, ring and box."""
+    _fields_ = [(k, C.c_uint64 * 2) for k in DETAIL_SUMS] + [("box_ssd", C.c_uint64), ("box_pixels", C.c_uint64)]
+
+    def as_dict(self):
+        d = {zone: {k: int(getattr(self, k)[i]) for k in DETAIL_SUMS} for i, zone in enumerate(DETAIL_ZONES)}
+        d.update(box_ssd=int(self.box_ssd), box_pixels=int(self.box_pixels))
+        return d
 
 
 class SimDisplaceResult(C.Structure):
@@ -391,6 +448,8 @@ ABI = {
     "musica_alter_zoom": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_scatter_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_scatter": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_alter_details": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Detail)]),
+    "musica_sim_details": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Detail), C.POINTER(SimDetailResult)]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -789,6 +848,15 @@ class MusicaProcessing:
         r, a, b = scatter_spec(spec)
         self._ok(self._lib.musica_sim_scatter_reference(self._h, int(dst_slot), int(src_slot), r, a, b), "musica_sim_scatter_reference")
 
+    def sim_details(self, details, slot, image_index=0):
+        """harness.detail_statistics(output of `image_index`, reference slot `slot`, details) on the device: the details (x, y, r, c) in
+        the (N - 20)^2 output plane's coordinates (detail_list; c is not looked at). Returns one dict per detail: "disc" and "ring", each
+        the Python ints n, sum_a, sum_b, sum_aa, sum_bb, sum_ab, and box_ssd, box_pixels."""
+        ds = detail_list(details, self.imageSize - 2 * OUT_MARGIN, with_contrast=False)
+        arr, res = (Detail * len(ds))(*[Detail(*d) for d in ds]), (SimDetailResult * len(ds))()
+        self._ok(self._lib.musica_sim_details(self._h, int(image_index), int(slot), len(ds), arr, res), "musica_sim_details")
+        return [res[i].as_dict() for i in range(len(ds))]
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -992,6 +1060,12 @@ class MusicaProcessing:
         spec = (R, a, b) (scatter_spec)."""
         r, a, b = scatter_spec(spec)
         self._ok(self._lib.musica_alter_scatter(self._h, int(image_index), r, a, b), "musica_alter_scatter")
+
+    def alter_details(self, details, image_index=0):
+        """harness.insert_details(src, details): the source with the discs (x, y, r, c) of a contrast-detail list (detail_list) inserted."""
+        ds = detail_list(details, self.imageSize)
+        arr = (Detail * len(ds))(*[Detail(*d) for d in ds])
+        self._ok(self._lib.musica_alter_details(self._h, int(image_index), len(ds), arr), "musica_alter_details")
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -33,6 +33,8 @@ ENSEMBLE_CSV_HEADER = ['raw file', 'alteration', 'realisations'] + ['%s %s' % (g
                       ['per-realisation %s %s' % (m, w) for m in ENSEMBLE_CSV_METRICS for w in ("mean", "std")]   # ensemble.csv
 
 COV_CSV_NAMES = (("noise_var", "noise var"), ("rho_x", "rho x"), ("rho_y", "rho y"), ("corr_area", "correlation area"), ("hf_fraction", "hf fraction"))
+DETAIL_CSV_HEADER = ['raw file', 'alteration', 'radius', 'details'] + ['%s %s' % (k, w) for k in DETAIL_ROW_KEYS for w in DETAIL_ROW_STATS] + \
+                    ['outside mse']   # contrast_detail.csv
 
 
 def covariance_csv_header(radius):
@@ -121,6 +123,15 @@ def _covariance_cells(e, radius):
            list(cov["direct"]["nps_radial"])
 
 
+def _detail_lines(studies):
+    """contrast_detail.csv's lines: one per cd_ row and radius, ascending."""
+    for raw_name, rows in studies:
+        for r in rows:
+            d = r.get("details")
+            for radius, g in (d["radii"].items() if d else ()):
+                yield [raw_name, r["alteration"], radius, g["count"]] + [g[k][w] for k in DETAIL_ROW_KEYS for w in DETAIL_ROW_STATS] + [d["outside_mse"]]
+
+
 def write_studies_csvs(studies, out_dir, mean_cnr=True):
     """The reference's output files for several raw images: `studies` is a list of (raw_name, rows) pairs (run_study's rows), written
     in order into one direct_robustness.csv / reg_based_robustness.csv with the reference's column layout (script.py:223-330), plus
@@ -148,7 +159,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
 
     Studies run with covariance=R (their noise rows' "ensemble" has "covariance") also get noise_covariance.csv
     (covariance_csv_header): one line per noise row, K, R, the noise variance, rho x, rho y, correlation area and high-frequency
-    fraction of the direct and of the registered region (empty without one), then the radial noise power spectrum of the direct one."""
+    fraction of the direct and of the registered region (empty without one), then the radial noise power spectrum of the direct one.
+
+    Studies run with details (rows[0] has "details") also get contrast_detail.csv (DETAIL_CSV_HEADER): one line per cd_ row and radius,
+    the number of details of that radius, the mean, min, max and population std over their positions of contrast, cnr, rose and halo,
+    and the row's outside mse (the same on each of its lines)."""
     os.makedirs(out_dir, exist_ok=True)
     having = lambda key: [(raw_name, rows) for raw_name, rows in studies if rows and key in rows[0]]   # noqa: E731
     toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
@@ -177,6 +192,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     for name, header, covered, cells in tables:
         if covered is not None:
             _write_csv(out_dir, name, header, _lines(covered, cells))
+    if having("details"):
+        _write_csv(out_dir, "contrast_detail.csv", DETAIL_CSV_HEADER, _detail_lines(having("details")))
     ovds = [[raw_name] + _cells(_ovd(rows), SIM_CSV_KEYS) for raw_name, rows in studies if _ovd(rows) is not None]
     if ovds:
         _write_csv(out_dir, "ref_similarities.csv", REF_CSV_HEADER, ovds)
