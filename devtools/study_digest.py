@@ -8,7 +8,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
   * the six dst / src slot operations at N = 151, a symmetry with a transpose, a blur of radius 8, a zoom of 32 / 31 and a veil of radius
     127 (wider than the slot) among them; and the same veil of the source plane into image 0 of the input buffer;
   * the contrast-detail pair at N = 151: nine details of radius 1 .. 8 inserted into image 0 (a disc across a tile corner among them),
-    and the sums of the same details, shifted into the output plane, of image 1's output against slot 0.
+    and the sums of the same details, shifted into the output plane, of image 1's output against slot 0;
+  * the edge-response pair at N = 151: four slanted-edge plates of half-side 8 and 9, one per orientation (a plate across a tile corner
+    and one flush with the plane's corner among them), inserted into image 0, and the tables of the same edges, shifted into the output
+    plane, of image 1's output against slot 0.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -102,5 +105,9 @@ details = [(30 + 40 * j - (7 if i == j else 0), 30 + 40 * i - (7 if i == j else 
 p.alter_details(details)
 note("musica_alter_details", p.input_pixels()[0])
 note("musica_sim_details", p.sim_details([(x - mp.OUT_MARGIN, y - mp.OUT_MARGIN, r, c) for x, y, r, c in details], 0, image_index=1))
+edges = [(63, 63, 8, 1, 8, 0, -512), (113, 46, 9, 5, 13, 1, 8), (46, 113, 9, 15, 16, 2, 128), (N - 27, N - 27, 8, 1, 4, 3, 512)]
+p.alter_edges(edges)
+note("musica_alter_edges", p.input_pixels()[0])
+note("musica_sim_edges", p.sim_edges([(e[0] - mp.OUT_MARGIN, e[1] - mp.OUT_MARGIN) + e[2:] for e in edges], 0, image_index=1))
 p.cleanup()
 print(json.dumps(digests))

@@ -764,6 +764,71 @@ int musica_alter_details(musica_ctx* ctx, uint32_t image_index, uint32_t count, 
 int musica_sim_details(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t count, const musica_detail* details,
                        musica_sim_detail_result* results);
 
+/* ---- edge response: slanted edges, the edge-spread function binned where they lie (new, not in the reference) ----
+ * How does the processor render an edge: the edge-spread function, its overshoot and undershoot (the rebound halo of multi-scale
+ * amplifiers), the 10-90 % rise and the edge MTF, and do they depend on the edge's contrast, position, orientation and polarity? The
+ * ISO 12233 / IEC 62220 slanted edge with a rational slope of our choosing. harness.insert_edges, harness.edge_statistics and
+ * harness.edge_summary are the contract; everything the device computes is integer and bit-identical to them, from call to call as
+ * well (integer LDS atomics and one reduction order).
+ * An edge is (x, y, half, p, q, orientation, contrast): an integer pixel centre, MUSICA_EDGE_MIN_HALF <= half <= MUSICA_EDGE_MAX_HALF,
+ * the slope p / q with 1 <= p < q, MUSICA_EDGE_MIN_Q <= q <= MUSICA_EDGE_MAX_Q and gcd(p, q) = 1, orientation 0 .. 3 and
+ * 1 <= |contrast| <= MUSICA_EDGE_MAX_CONTRAST in 1 / 1024 of the pixel's value. With dx = px - x, dy = py - y the profile coordinate u
+ * and the along-edge coordinate v are (dx, dy), (dy, dx), (-dx, dy), (-dy, dx) for orientation 0, 1, 2, 3, and the signed numerator is
+ * s = q u - p v. Zones:
+ *   plate    |dx|, |dy| <= 2 half     (side 4 half + 1): what gets inserted
+ *   region   |dx|, |dy| <= half       (side 2 half + 1): what gets measured
+ * A list for a plane of side n holds 1 .. MUSICA_EDGE_MAX edges whose plates lie inside [0, n)^2 and are pairwise disjoint
+ * (|xi - xj| > 2 (hi + hj) or |yi - yj| > 2 (hi + hj)): a pixel belongs to at most one plate, so nothing depends on the list's
+ * order. Both entry points refuse every other list before any device work.
+ *   insertion   inside a plate, with m = clamp(2s + q, 0, 2q): out = min((v * (2048 q - contrast * m) + 1024 q) div (2048 q), 65535),
+ *               every other pixel copied. m / 2q is the part of the pixel's one-pixel box aperture along the profile axis that the
+ *               absorber covers; ONE rounding, halves up; m = 0 gives v, m = 2q the detail's min((v * (1024 - contrast) + 512) >> 10,
+ *               65535); the largest intermediate is 65535 * (2048 * 16 + 512 * 32) + 16384 < 2^32.
+ *   statistics  per edge a table of 2B + 1 bins, B = ceil(4 (q + p) half / q) (musica_edge_bins; at most 2047): every pixel of the
+ *               region falls in bin k = floor(4 s / q), stored at index k + B, and each bin holds the exact n, sum_a, sum_b and
+ *               sum_aa of its pixels (at most 2 half + 1 of them: every sum fits uint32); and over the region the sum of (a - b)^2
+ *               and its pixel count. `contrast` is not looked at.
+ * As for the details there is no musica_sim_..._reference sibling. */
+#define MUSICA_EDGE_MIN_HALF 8
+#define MUSICA_EDGE_MAX_HALF 128
+#define MUSICA_EDGE_MIN_Q 4
+#define MUSICA_EDGE_MAX_Q 16
+#define MUSICA_EDGE_MAX_CONTRAST 512
+#define MUSICA_EDGE_MAX 256
+#define MUSICA_EDGE_BINS_MAX 2048
+typedef struct musica_edge {
+    int32_t x, y;                   /* the centre, in pixels of the plane the call names */
+    uint32_t half;                  /* MUSICA_EDGE_MIN_HALF .. MUSICA_EDGE_MAX_HALF */
+    uint32_t p, q;                  /* the slope p / q: 1 <= p < q, MUSICA_EDGE_MIN_Q <= q <= MUSICA_EDGE_MAX_Q, lowest terms */
+    uint32_t orientation;           /* 0 .. 3 */
+    int32_t contrast;               /* 1 <= |contrast| <= MUSICA_EDGE_MAX_CONTRAST, in 1 / 1024 of the pixel's value */
+} musica_edge;
+typedef struct musica_sim_edge_result {
+    uint64_t roi_ssd;               /* sum over the region of (a - b)^2 */
+    uint64_t roi_pixels;            /* (2 half + 1)^2 */
+    uint64_t table_offset;          /* where the edge's table starts in `tables`, in words: 4 times the bins of the edges before it */
+    uint64_t bins;                  /* 2B + 1 */
+} musica_sim_edge_result;
+/* The bins 2B + 1 of the table of an edge of this half-side and slope, or 0 for an inadmissible triple. No context, no device. */
+uint32_t musica_edge_bins(uint32_t half, uint32_t p, uint32_t q);
+/* insert_edges(source plane, edges) into image `image_index` of the input buffer: the edges are in the N x N plane's coordinates. The
+ * kernel is enqueued on the ctx stream (the list is copied to the device first, which waits for what the stream holds), with
+ * musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step and no reference slot. One
+ * launch, 2 bytes read and 2 written per pixel (kernels_edges.hip). Refused before any device work: a NULL context or list, no source,
+ * image_index >= batch, a count outside 1 .. MUSICA_EDGE_MAX, a half-side, slope, orientation or contrast outside its limits, a plate
+ * that leaves the plane, two plates that are not disjoint. */
+int musica_alter_edges(musica_ctx* ctx, uint32_t image_index, uint32_t count, const musica_edge* edges);
+/* edge_statistics of side a, the 8-bit output of batch image `image_index` (quantised while read, exactly as musica_sim_compare reads
+ * it), against side b, reference slot `slot`: results[i] for edges[i], in the coordinates of the (N - 20)^2 output plane. `tables` is
+ * flat: edge i starts at the sum over j < i of 4 * bins_j words (results[i].table_offset) and is laid out [4][bins_i]: n, sum_a, sum_b,
+ * sum_aa; table_words, the words `tables` has room for, must be at least the total. Synchronous. roi_ssd equals musica_sim_compare's
+ * sq_diff_sum over the same (2 half + 1)^2 region. Refused before any device work: a NULL context, list, results or tables, a count
+ * outside 1 .. MUSICA_EDGE_MAX, an image too small for the margin, a slot out of range or never written, image_index >= batch, a
+ * half-side, slope or orientation outside its limits, a plate that leaves the plane, two plates that are not disjoint, table_words
+ * too small. */
+int musica_sim_edges(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t count, const musica_edge* edges,
+                     musica_sim_edge_result* results, uint32_t* tables, uint64_t table_words);
+
 /* ---- device-resident output and stream ordering (new, not in the reference) ---- */
 
 /* What musica_export_out writes per image. */

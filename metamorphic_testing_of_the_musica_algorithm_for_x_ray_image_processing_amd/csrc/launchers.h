@@ -338,6 +338,30 @@ void launch_alter_details(hipStream_t st, const uint16_t* src, uint16_t* out, in
 // plane, pitches in elements, the details in the cropped output plane's coordinates; out: count x kDetailWords u64, all written
 void launch_sim_details(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedDetail* d_details, int count,
                         unsigned long long* out);
+// kernels_edges.hip: the edge-response relation. An edge (x, y, h, p, q, o, c) of a list that the caller has checked (limits, plates
+// inside the plane and pairwise disjoint), packed: a plane side is at most 16384.
+constexpr int kEdgeMinHalf = 8;         // MUSICA_EDGE_MIN_HALF
+constexpr int kEdgeMaxHalf = 128;       // MUSICA_EDGE_MAX_HALF
+constexpr int kEdgeMinQ = 4;            // MUSICA_EDGE_MIN_Q
+constexpr int kEdgeMaxQ = 16;           // MUSICA_EDGE_MAX_Q
+constexpr int kEdgeMaxContrast = 512;   // MUSICA_EDGE_MAX_CONTRAST
+constexpr int kEdgeMax = 256;           // MUSICA_EDGE_MAX
+constexpr int kEdgeBinsMax = 2048;      // MUSICA_EDGE_BINS_MAX
+constexpr int kEdgeWords = 4;           // u64 of a musica_sim_edge_result
+struct PackedEdge {
+    uint32_t xy;      // x | y << 16
+    uint32_t hpqo;    // h | p << 8 | q << 16 | o << 24
+    int32_t c;        // the contrast (0 where the call does not look at it)
+    uint32_t table;   // k_sim_edges: where the edge's 4 x bins words start in the flat tables
+};
+// harness.insert_edges(src, edges) of a dense n x n plane into another (the planes must not overlap); any n >= 1, `count` edges at
+// d_edges (device)
+void launch_alter_edges(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const PackedEdge* d_edges, int count);
+// harness.edge_statistics: one workgroup per edge. a_plane: the graded f32 plane at output pixel (0, 0), b_plane: the slot's u8 plane,
+// pitches in elements, the edges in the cropped output plane's coordinates; results: count x kEdgeWords u64, tables: every edge's
+// 4 x bins u32 from its PackedEdge::table on, all written
+void launch_sim_edges(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedEdge* d_edges, int count,
+                      unsigned long long* results, uint32_t* tables);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

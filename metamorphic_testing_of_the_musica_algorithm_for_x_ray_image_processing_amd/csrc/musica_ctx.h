@@ -139,6 +139,10 @@ struct StudyState {
     // musica_alter_details / musica_sim_details: the device copy of the call's detail list and the details' sums
     PackedDetail* d_details = nullptr;             // [MUSICA_DETAIL_MAX], allocated by the first call of either
     unsigned long long* d_detail_out = nullptr;    // [MUSICA_DETAIL_MAX][kDetailWords], allocated by the first musica_sim_details
+    // musica_alter_edges / musica_sim_edges: the device copy of the call's edge list, the edges' results and their flat tables
+    PackedEdge* d_edges = nullptr;                 // [MUSICA_EDGE_MAX], allocated by the first call of either
+    unsigned long long* d_edge_out = nullptr;      // [MUSICA_EDGE_MAX][kEdgeWords], allocated by the first musica_sim_edges
+    uint32_t* d_edge_tables = nullptr;             // [MUSICA_EDGE_MAX][4][MUSICA_EDGE_BINS_MAX] (8 MiB), allocated by the first musica_sim_edges
 };
 
 struct musica_ctx : DeviceBuffers {

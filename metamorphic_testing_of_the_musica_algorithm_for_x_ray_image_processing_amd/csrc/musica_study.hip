@@ -1,7 +1,7 @@
-// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the five query calls
-// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_details.hip), the ensemble accumulators
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the six query calls
+// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_details.hip, kernels_edges.hip), the ensemble accumulators
 // (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_details.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
+// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_details.hip, kernels_edges.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
@@ -132,6 +132,58 @@ static int details_check(const char* fn, uint32_t count, const musica_detail* ds
 static int details_upload(musica_ctx* c, const char* fn, const std::vector<PackedDetail>& packed) {
     if (!ensure(c, &c->study.d_details, MUSICA_DETAIL_MAX)) return fail("%s: device allocation of the detail list failed", fn);
     HIP_OK(hipMemcpyAsync(c->study.d_details, packed.data(), packed.size() * sizeof(PackedDetail), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+static_assert(kEdgeMinHalf == MUSICA_EDGE_MIN_HALF && kEdgeMaxHalf == MUSICA_EDGE_MAX_HALF && kEdgeMinQ == MUSICA_EDGE_MIN_Q && kEdgeMaxQ == MUSICA_EDGE_MAX_Q &&
+                  kEdgeMaxContrast == MUSICA_EDGE_MAX_CONTRAST && kEdgeMax == MUSICA_EDGE_MAX && kEdgeBinsMax == MUSICA_EDGE_BINS_MAX,
+              "kernels_edges.hip's tile list, u32 pixel, LDS table and u32 sums hold for the edges of include/musica.h");
+static_assert(sizeof(musica_sim_edge_result) == kEdgeWords * sizeof(uint64_t), "k_sim_edges writes a musica_sim_edge_result as its u64 words");
+
+static uint32_t edge_gcd(uint32_t a, uint32_t b) { return b ? edge_gcd(b, a % b) : a; }
+
+uint32_t musica_edge_bins(uint32_t half, uint32_t p, uint32_t q) {
+    if (half < MUSICA_EDGE_MIN_HALF || half > MUSICA_EDGE_MAX_HALF || q < MUSICA_EDGE_MIN_Q || q > MUSICA_EDGE_MAX_Q || p < 1 || p >= q || edge_gcd(p, q) != 1) return 0;
+    return 2 * ((4 * (q + p) * half + q - 1) / q) + 1;
+}
+
+// What both edge calls refuse about a list for a plane of side n (processing.edge_list): the count, each half-side, slope and
+// orientation (and each contrast when the call looks at it), plates inside the plane, plates pairwise disjoint. Fills `packed` for the
+// device, each edge's table behind the one before it, and `words` with the tables' total. No device work.
+static int edges_check(const char* fn, uint32_t count, const musica_edge* es, int n, bool with_contrast, std::vector<PackedEdge>& packed, uint64_t* words) {
+    if (count == 0 || count > MUSICA_EDGE_MAX) return fail("%s: count %u out of range [1, %d]", fn, count, MUSICA_EDGE_MAX);
+    packed.resize(count);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_edge& e = es[i];
+        if (e.half < MUSICA_EDGE_MIN_HALF || e.half > MUSICA_EDGE_MAX_HALF)
+            return fail("%s: edge %u: half-side %u out of range [%d, %d]", fn, i, e.half, MUSICA_EDGE_MIN_HALF, MUSICA_EDGE_MAX_HALF);
+        const uint32_t bins = musica_edge_bins(e.half, e.p, e.q);
+        if (!bins) return fail("%s: edge %u: slope %u / %u is not 1 <= p < q, %d <= q <= %d in lowest terms", fn, i, e.p, e.q, MUSICA_EDGE_MIN_Q, MUSICA_EDGE_MAX_Q);
+        if (e.orientation > 3) return fail("%s: edge %u: orientation %u out of range [0, 3]", fn, i, e.orientation);
+        if (with_contrast && (e.contrast == 0 || e.contrast < -MUSICA_EDGE_MAX_CONTRAST || e.contrast > MUSICA_EDGE_MAX_CONTRAST))
+            return fail("%s: edge %u: contrast %d is not 1 <= |contrast| <= %d", fn, i, e.contrast, MUSICA_EDGE_MAX_CONTRAST);
+        const int64_t reach = 2 * (int64_t)e.half;
+        if (e.x - reach < 0 || e.y - reach < 0 || e.x + reach >= n || e.y + reach >= n)
+            return fail("%s: edge %u: the plate (%d, %d) +- %d leaves the %d x %d plane", fn, i, e.x, e.y, (int)reach, n, n);
+        packed[i] = {(uint32_t)e.x | ((uint32_t)e.y << 16), e.half | (e.p << 8) | (e.q << 16) | (e.orientation << 24), with_contrast ? e.contrast : 0, (uint32_t)at};
+        at += 4ull * bins;
+    }
+    for (uint32_t i = 0; i < count; i++)
+        for (uint32_t j = i + 1; j < count; j++) {
+            const int64_t reach = 2 * ((int64_t)es[i].half + es[j].half);
+            if (std::abs((int64_t)es[i].x - es[j].x) <= reach && std::abs((int64_t)es[i].y - es[j].y) <= reach)
+                return fail("%s: the plates of edges %u and %u are not disjoint", fn, i, j);
+        }
+    *words = at;
+    return 1;
+}
+
+// The call's list on the device, as details_upload.
+static int edges_upload(musica_ctx* c, const char* fn, const std::vector<PackedEdge>& packed) {
+    if (!ensure(c, &c->study.d_edges, MUSICA_EDGE_MAX)) return fail("%s: device allocation of the edge list failed", fn);
+    HIP_OK(hipMemcpyAsync(c->study.d_edges, packed.data(), packed.size() * sizeof(PackedEdge), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     return 1;
 }
@@ -640,6 +692,36 @@ int musica_sim_details(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t coun
     ABI_CATCH("musica_sim_details")
 }
 
+// ---- the edge-response measurement (musica_sim_edges, include/musica.h; kernels_edges.hip) ---------------------------------------------
+int musica_sim_edges(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count, const musica_edge* edges, musica_sim_edge_result* out, uint32_t* tables,
+                     uint64_t table_words) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_edges: ctx is NULL");
+    if (!edges || !out || !tables) return fail("musica_sim_edges: edges, results or tables is NULL");
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_edges: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_edges: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    if (!c->study.written[slot]) return fail("musica_sim_edges: slot %u was never written", slot);
+    CHECK_IMG(c, idx);
+    std::vector<PackedEdge> packed;
+    uint64_t words = 0;
+    if (!edges_check("musica_sim_edges", count, edges, (int)sim_side(c), false, packed, &words)) return 0;
+    if (table_words < words) return fail("musica_sim_edges: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_edge_out, (size_t)MUSICA_EDGE_MAX * kEdgeWords) && ensure(c, &st.d_edge_tables, (size_t)MUSICA_EDGE_MAX * 4 * MUSICA_EDGE_BINS_MAX)))
+        return fail("musica_sim_edges: device allocation failed");
+    if (!edges_upload(c, "musica_sim_edges", packed)) return 0;
+    const int pitch = c->lv[0].pitch;
+    launch_sim_edges(c->stream, image_slice(c, c->d_graded, idx) + (size_t)MUSICA_OUT_MARGIN * pitch + MUSICA_OUT_MARGIN, pitch, st.slot[slot],
+                     (int)sim_side(c), st.d_edges, (int)count, st.d_edge_out, st.d_edge_tables);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out, st.d_edge_out, (size_t)count * sizeof(musica_sim_edge_result), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(tables, st.d_edge_tables, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+    ABI_CATCH("musica_sim_edges")
+}
+
 // ---- ensemble statistics (musica_sim_ensemble_*, include/musica.h; kernels_ensemble.hip) ------------------------------------------------
 int musica_sim_ensemble_reset(musica_ctx* c) {
     ABI_TRY
@@ -1026,6 +1108,24 @@ int musica_alter_details(musica_ctx* c, uint32_t idx, uint32_t count, const musi
     HIP_OK(hipGetLastError());
     return 1;
     ABI_CATCH("musica_alter_details")
+}
+
+int musica_alter_edges(musica_ctx* c, uint32_t idx, uint32_t count, const musica_edge* edges) {
+    ABI_TRY
+    if (!c) return fail("musica_alter_edges: ctx is NULL");
+    if (!edges) return fail("musica_alter_edges: edges is NULL");
+    if (!c->study.d_alter_src) return fail("musica_alter_edges: no source plane (musica_alter_set_source)");
+    CHECK_IMG(c, idx);
+    std::vector<PackedEdge> packed;
+    uint64_t words = 0;
+    if (!edges_check("musica_alter_edges", count, edges, c->N, true, packed, &words)) return 0;
+    CHECK_CTX(c);
+    if (!edges_upload(c, "musica_alter_edges", packed)) return 0;
+    if (!alter_keep_input(c, "musica_alter_edges")) return 0;
+    launch_alter_edges(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, c->study.d_edges, (int)count);   // kernels_edges.hip
+    HIP_OK(hipGetLastError());
+    return 1;
+    ABI_CATCH("musica_alter_edges")
 }
 
 int musica_alter_draws(musica_ctx* c, const musica_alteration* s, int32_t* dst) {

@@ -98,6 +98,51 @@ def DETAILS(n):
     return tuple(detail_grid(n, c) for c in DETAIL_CONTRASTS)
 
 
+# not in the reference: the edge-response rows (insert_edges), rows edge_<c> of a study run with `edges`: slanted-edge plates of the
+# half-sides EDGE_HALVES, the slopes EDGE_SLOPES and all four orientations on a grid (edge_grid), one row per contrast c / 1024 =
+# 0.8 % .. 12.5 %, the cd_ rows' five strengths. EDGES(n) gives the five grids of the image size.
+EDGE_HALVES = (8, 16, 32, 64)
+# 1/8 (7.1 degrees) and 1/5 (11.3) bracket the 5 .. 10 degrees the standards ask for; 1/12 (4.8) is their lower end and 2/7 (15.9) a
+# steep one with p > 1, whose bins interleave two pixel phases. Every q >= 4: every central bin is filled (edge_statistics).
+EDGE_SLOPES = ((1, 8), (1, 5), (1, 12), (2, 7))
+EDGE_CONTRASTS = (8, 16, 32, 64, 128)
+
+
+def edge_grid(n, contrast, halves=None):
+    """The study's edge phantom for a raw image of side n: G x G plates of one contrast on a square grid inside the output plane's
+    footprint. With B = PROCESSING_MARGIN and m = n - 2B, `halves` defaults to the longest prefix of EDGE_HALVES of length k with
+    m // (4 h_last + 1) >= k; G = min(m // (4 h_max + 1), 16) // k * k (ValueError if 0; at most 256 = EDGE_MAX plates), the cell
+    C = m // G, and edge (i, j), i, j < G, row i first, t = i G + j, is (B + j C + C // 2, B + i C + C // 2, halves[(i + j) % k],
+    *EDGE_SLOPES[(t // 4) % 4], t % 4, contrast): the diagonal assignment puts every half-side G / k times in every row and every
+    column of the grid, the orientations cycle fastest and the slopes behind them. A plate has side 4h + 1 <= C, so the plates are
+    disjoint and lie inside [B, n - B)^2: shifted by -B (output_edges) the list is valid for the output plane."""
+    n, b = int(n), PROCESSING_MARGIN
+    m = n - 2 * b
+    if halves is None:
+        k = 0
+        while k < len(EDGE_HALVES) and m // (4 * EDGE_HALVES[k] + 1) >= k + 1:
+            k += 1
+        halves = EDGE_HALVES[:k]
+    halves = tuple(int(h) for h in halves)
+    k = len(halves)
+    g = min(m // (4 * max(halves) + 1), 16) // k * k if k else 0
+    if g <= 0:
+        raise ValueError("a side of %d pixels holds no grid of the half-sides %r" % (n, halves))
+    c = m // g
+    return mp.edge_list([(b + j * c + c // 2, b + i * c + c // 2, halves[(i + j) % k]) + EDGE_SLOPES[((i * g + j) // 4) % len(EDGE_SLOPES)] +
+                         ((i * g + j) % 4, contrast) for i in range(g) for j in range(g)], n)
+
+
+def output_edges(edges):
+    """A raw plane's edges in the coordinates of the output plane (the frame cropped by PROCESSING_MARGIN on every side)."""
+    return tuple((e[0] - PROCESSING_MARGIN, e[1] - PROCESSING_MARGIN) + tuple(e[2:]) for e in edges)
+
+
+def EDGES(n):
+    """The five grids of the edge_ rows of a side-n image: edge_grid(n, c) for c in EDGE_CONTRASTS."""
+    return tuple(edge_grid(n, c) for c in EDGE_CONTRASTS)
+
+
 def scaled(values, image_size):
     """The reference's pixel-valued grids scaled from 3072 to `image_size`."""
     return [max(1, int(round(v * image_size / REF_IMAGE_SIZE))) for v in values]
@@ -525,7 +570,7 @@ VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
-                  detail_tables=False):
+                  detail_tables=False, edges=None, edge_tables=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -565,31 +610,37 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         details = [mp.detail_list(g, n) for g in details]
         for g in details:
             mp.detail_list(output_details(g), n - 2 * PROCESSING_MARGIN)
+    if edges is not None:     # likewise
+        edges = [mp.edge_list(g, n) for g in edges]
+        for g in edges:
+            mp.edge_list(output_edges(g), n - 2 * PROCESSING_MARGIN)
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
-           (("ensemble",) if ensemble else ()) + (("details",) if details is not None else ())
+           (("ensemble",) if ensemble else ()) + (("details",) if details is not None else ()) + \
+           (("edges",) if edges is not None else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, details=details or [], detail_tables=bool(detail_tables),
-        keys=keys, device_alterations=device_alterations)
+        edges=edges or [], edge_tables=bool(edge_tables), keys=keys, device_alterations=device_alterations)
 
 
 # One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
 # region() the region of the registered comparison (None, or no region at all as for the noise rows: no registration); move = (the
 # context's method, the host's function, their parameter), which both move a reference plane as the alteration moves the input: the
 # registered comparison is then against the moved plane; noise = (the row's ordinal, alter(context, stream, image_index)) for the rows
-# that draw, what their ensembles repeat; details = the raw plane's detail list of a cd_ row, measured where the details lie.
-Alteration = collections.namedtuple("Alteration", "name host dev region move noise details", defaults=(None, None, None, None))
+# that draw, what their ensembles repeat; details = the raw plane's detail list of a cd_ row, measured where the details lie; edges = the
+# raw plane's edge list of an edge_ row, likewise.
+Alteration = collections.namedtuple("Alteration", "name host dev region move noise details edges", defaults=(None, None, None, None, None))
 
 
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4, blur, zoom, scatter and cd rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur, zoom, scatter, cd and edge rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -626,6 +677,8 @@ def study_alterations(raw, rng, p, seed, shape, opt):
                          ("sim_scatter_reference", scatter, s))
     for g in opt.details:
         yield Alteration("cd_%d" % g[0][3], lambda: insert_details(raw, g), lambda: p.alter_details(g), details=g)
+    for g in opt.edges:
+        yield Alteration("edge_%d" % g[0][6], lambda: insert_edges(raw, g), lambda: p.alter_edges(g), edges=g)
 
 
 class Scorer:
@@ -676,6 +729,11 @@ class DeviceScorer(Scorer):
         """One musica_sim_details call against the unaltered result; the full frame's integers are the row's direct comparison's."""
         direct = self.compared[0]
         return detail_row(details, self.proc.sim_details(details, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.detail_tables)
+
+    def edges(self, edges):
+        """One musica_sim_edges call against the unaltered result; the full frame's integers are the row's direct comparison's."""
+        direct = self.compared[0]
+        return edge_row(edges, self.proc.sim_edges(edges, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.edge_tables)
 
     def tone(self, comparisons):
         """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
@@ -737,6 +795,10 @@ class HostScorer(Scorer):
         a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
         return detail_row(details, detail_statistics(self.out, self.planes[SLOT_UNALTERED], details), int(((a - b) ** 2).sum()), a.size,
                           self.opt.detail_tables)
+
+    def edges(self, edges):
+        a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
+        return edge_row(edges, edge_statistics(self.out, self.planes[SLOT_UNALTERED], edges), int(((a - b) ** 2).sum()), a.size, self.opt.edge_tables)
 
     def tone(self, comparisons):
         return [tone_similarities(*self.sides(*c)) for c in comparisons]
@@ -802,7 +864,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
-              blurs=None, zooms=None, scatters=None, details=None, detail_tables=False):
+              blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -904,10 +966,25 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     last bit on every path. detail_tables: the dict also carries "per_detail". The rows draw nothing from `rng` and take no ordinal;
     vendor, tone, scales and displacement apply to "direct" as elsewhere. Nothing is asserted about visibility: these are findings.
     Three relations read off a cd_ study: locality (outside_mse near 0), monotonicity (more c, more contrast, at every radius) and
-    position invariance (a small std over the positions); where MUSICA's local gains break the last one is the finding."""
+    position invariance (a small std over the positions); where MUSICA's local gains break the last one is the finding.
+
+    edges: slanted-edge grids, each an edge list (x, y, h, p, q, o, c) for the raw plane (processing.edge_list; EDGES(n) for the five
+    contrasts 0.8 % .. 12.5 % on edge_grid's phantom) that is also valid for the output plane when shifted by the margin
+    (output_edges), else ValueError before any work. None adds nothing. Otherwise rows edge_<c> (c: the grid's first contrast) follow
+    the cd_ rows: the raw image with the grid's plates inserted (insert_edges; on the device: alter_edges), "direct" scored as for
+    every row, "registered" None, and every row of the study gains "edges": None except in the edge_ rows, where it is edge_row's dict
+    of the edges measured where they lie against the unaltered result (edge_statistics; on the device one musica_sim_edges call behind
+    the row's musica_sim_compare, whose exact sq_diff_sum of the full frame gives outside_mse): over all edges, per orientation and
+    per half-side the min, mean, max and count of the step, the 10-90 % rise, the overshoot and undershoot, mtf50 and mtf_peak of
+    the a - b edge-spread function (edge_summary), and outside_mse. Host and device summarise exact integers with one function, so
+    "edges" is equal to the last bit on every path. edge_tables: the dict also carries "per_edge", the three edge-spread functions
+    of every edge included. The rows draw nothing from `rng` and take no ordinal. Nothing is asserted about how an edge is rendered:
+    these are findings. A linear, shift-invariant processor would give the same normalised response at every contrast, position,
+    orientation and polarity; where MUSICA does not is the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
-                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables)
+                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
+                        edges, edge_tables)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -942,6 +1019,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             out.update(zip([key for key, _ in shifted], scorer.shifts([c for _, c in shifted])))
         if alteration is not None and alteration.details:
             out["details"] = scorer.details(output_details(alteration.details))
+        if alteration is not None and alteration.edges:
+            out["edges"] = scorer.edges(output_edges(alteration.edges))
         out["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         if eproc is not None:
             out["ensemble"] = ensemble_of(eproc, alteration.noise, registered[1] if registered else None, full, opt)
@@ -1093,6 +1172,12 @@ def main(argv=None):
                          "contrast_detail.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_details, "
                          "musica_alter_details)")
     ap.add_argument("--detail-tables", action="store_true", help="with --details: keep every detail's numbers in the rows (\"per_detail\")")
+    ap.add_argument("--edges", action="store_true",
+                    help="add the rows edge_<c>: slanted-edge plates in all four orientations inserted on a grid (edge_grid) at the contrasts "
+                         "c / 1024 = 0.8 %% .. 12.5 %%, their edge-spread functions measured where they lie (step, 10-90 %% rise, overshoot, "
+                         "undershoot, edge MTF per orientation), written to edge_response.csv; on the GPU with --device-metrics / "
+                         "--device-alterations (musica_sim_edges, musica_alter_edges)")
+    ap.add_argument("--edge-tables", action="store_true", help="with --edges: keep every edge's numbers and edge-spread functions in the rows (\"per_edge\")")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -1122,6 +1207,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.detail_tables and not args.details:
         ap.error("--detail-tables keeps what --details measures: give --details")
+    if args.edge_tables and not args.edges:
+        ap.error("--edge-tables keeps what --edges measures: give --edges")
     if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
         ap.error("--covariance takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
     if args.covariance and not args.ensemble:
@@ -1179,6 +1266,8 @@ def main(argv=None):
         shift_args["scatters"] = SCATTERS(args.size) if args.scatters is True else args.scatters
     if args.details:
         shift_args.update(details=DETAILS(args.size), detail_tables=args.detail_tables)
+    if args.edges:
+        shift_args.update(edges=EDGES(args.size), edge_tables=args.edge_tables)
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

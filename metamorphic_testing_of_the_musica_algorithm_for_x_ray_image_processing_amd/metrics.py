@@ -706,3 +706,196 @@ def detail_row(details, stats, sq_diff_sum, pixels, tables=False):
     if tables:
         out["per_detail"] = [dict(s, x=d[0], y=d[1], r=d[2], c=d[3]) for d, s in zip(details, summary)]
     return out
+
+
+# ---- edge response: slanted edges, the edge-spread function binned where they lie (not in the reference's script) ---------------------
+# MTF, NPS and contrast-detail are the classic triad; the ensemble gives the NPS, the cd_ rows the contrast-detail curve, and this is the
+# third: how MUSICA renders an edge (ISO 12233 / IEC 62220 slanted edge). An edge is (x, y, h, p, q, o, c): an integer pixel centre, a
+# half-side EDGE_MIN_HALF <= h <= EDGE_MAX_HALF, a rational slope p / q (1 <= p < q, EDGE_MIN_Q <= q <= EDGE_MAX_Q, lowest terms), an
+# orientation o = 0 .. 3 and a contrast 1 <= |c| <= EDGE_MAX_CONTRAST in 1 / 1024 of the pixel's value. With dx = px - x, dy = py - y
+# the profile coordinate u and the along-edge coordinate v are (dx, dy), (dy, dx), (-dx, dy), (-dy, dx) for o = 0, 1, 2, 3 and the
+# signed numerator is s = q u - p v: s / q is the pixel's distance from the edge along the profile axis, in pixels. The plate
+# |dx|, |dy| <= 2h (side 4h + 1) is what gets inserted, the region |dx|, |dy| <= h (side 2h + 1) what gets measured: the region keeps
+# h pixels of the plate around it, so the processor's response to the plate's own border stays out of the profile. The plates of a list
+# lie inside the plane and are pairwise disjoint (processing.edge_list), so nothing depends on the list's order. Everything up to
+# edge_summary is integer: these functions are the contract of musica_alter_edges and musica_sim_edges (include/musica.h), which are
+# bit-identical to them.
+
+def edge_numerators(h, p, q, o, reach):
+    """s = q u - p v of every pixel of the square |dx|, |dy| <= reach about an edge's centre, an int64 array indexed [dy + reach,
+    dx + reach]. `h` is not looked at."""
+    d = np.arange(-int(reach), int(reach) + 1, dtype=np.int64)
+    dy, dx = d[:, None], d[None, :]
+    u, v = ((dx, dy), (dy, dx), (-dx, dy), (-dy, dx))[int(o)]
+    return int(q) * u - int(p) * v + 0 * (dx + dy)
+
+
+def insert_edges(image, edges):
+    """The square 2-D uint16 plane with the plates of `edges` (processing.edge_list for its side, else ValueError before any work)
+    inserted: inside each plate, with m = clamp(2s + q, 0, 2q),
+        out = min((v * (2048 q - c m) + 1024 q) // (2048 q), 65535)
+    and every other pixel copied. m / 2q is the part of the pixel's one-pixel box aperture along the profile axis that the absorber
+    (s > 0) covers, so the edge is an area-sampled ideal step, with ONE rounding, halves up. m = 0 gives exactly v, m = 2q exactly
+    detail_pixel's min((v (1024 - c) + 512) >> 10, 65535); the largest intermediate is 65535 * (2048 * 16 + 512 * 32) + 16384 < 2^32.
+    As for the details a non-zero pixel stays non-zero."""
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype != np.uint16 or not image.size:
+        raise ValueError("insert_edges needs a non-empty square 2-D uint16 plane, got %r %s" % (image.shape, image.dtype))
+    edges = mp.edge_list(edges, image.shape[0])
+    out = image.copy()
+    for x, y, h, p, q, o, c in edges:
+        m = np.clip(2 * edge_numerators(h, p, q, o, 2 * h) + q, 0, 2 * q)
+        plate = out[y - 2 * h:y + 2 * h + 1, x - 2 * h:x + 2 * h + 1]      # a view: the plate is rewritten in place
+        plate[...] = np.minimum((plate.astype(np.int64) * (2048 * q - c * m) + 1024 * q) // (2048 * q), 65535).astype(np.uint16)
+    return out
+
+
+def edge_statistics(a, b, edges):
+    """The exact edge-spread tables of every edge of `edges` (in the planes' coordinates; c is not looked at) over two square uint8
+    planes of equal shape: what musica_sim_edges returns. Every pixel of the region falls in bin k = floor(4 s / q) (a floor division,
+    negative s included): the profile oversampled four times. With B = ceil(4 (q + p) h / q) the table has bins = 2B + 1 entries
+    (processing.edge_bins) and bin k is stored at index k + B. One dict per edge: the ints h, p, q, bins, the uint32 arrays n, sum_a,
+    sum_b, sum_aa (the pixels of each bin, their sums over a and b, the sum of a^2), roi_ssd = the sum over the region of (a - b)^2 and
+    roi_pixels = (2h + 1)^2. A bin receives at most one pixel per line of the region across the profile, so n <= 2h + 1 and every sum
+    fits uint32; every bin -C <= k < C, C = floor(4 (q - p) h / q), is non-empty."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or a.shape != b.shape or a.shape[0] != a.shape[1] or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("edge_statistics needs two square 2-D uint8 planes of equal shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    edges = mp.edge_list(edges, a.shape[0], with_contrast=False)
+    out = []
+    for x, y, h, p, q, o, _ in edges:
+        bins = mp.edge_bins(h, p, q)
+        k = ((4 * edge_numerators(h, p, q, o, h)) // q + bins // 2).ravel()
+        pa = a[y - h:y + h + 1, x - h:x + h + 1].astype(np.int64).ravel()
+        pb = b[y - h:y + h + 1, x - h:x + h + 1].astype(np.int64).ravel()
+        d = {"h": h, "p": p, "q": q, "bins": bins, "roi_ssd": int(((pa - pb) ** 2).sum()), "roi_pixels": int(pa.size)}
+        for key, w in zip(mp.EDGE_SUMS, (np.ones_like(pa), pa, pb, pa * pa)):
+            d[key] = np.bincount(k, weights=w, minlength=bins).astype(np.uint32)   # exact: every sum is below 2^53
+        out.append(d)
+    return out
+
+
+EDGE_SIDES = ("a", "b", "d")                # the three edge-spread functions of an edge: of side a, of side b, of a - b
+EDGE_KEYS = ("low", "high", "step", "rise", "overshoot", "undershoot", "mtf50", "mtf10", "mtf_peak", "mtf_peak_f")   # edge_profile's numbers
+EDGE_FFT = 4096                             # the zero-padded length of the line-spread function's transform: a power of two above EDGE_BINS_MAX
+
+
+def edge_pitch(p, q):
+    """The distance in pixels along the edge's normal between two bins of the four-times oversampled profile: 1/4 q / sqrt(p^2 + q^2)."""
+    return 0.25 * q / math.sqrt(p * p + q * q)
+
+
+def edge_mtf(esf, pitch):
+    """(f, mtf): the edge MTF of an edge-spread function sampled every `pitch` pixels, at the frequencies f_j = j / (EDGE_FFT pitch)
+    <= 0.5 cycles / pixel (up to the pixel grid's Nyquist frequency), or (f, None) when the windowed line-spread function sums to 0.
+    The line-spread function is the difference l_i = e_(i+1) - e_i of the M + 1 samples, windowed with the Hann window
+    w_i = 1/2 - 1/2 cos(2 pi (i + 1/2) / M) (centred on the profile's centre, where the edge lies; no sample is weighted 0),
+    zero-padded to EDGE_FFT and transformed; |L(f)| is divided by |L(0)|, so mtf[0] is exactly 1, and by sinc^2(f pitch)
+    (sinc(x) = sin(pi x) / (pi x)): once for the bin, which averages the profile over a box one pitch wide, and once for the
+    difference, which is the derivative convolved with the same box."""
+    e = np.asarray(esf, dtype=np.float64)
+    f = np.arange(int(math.floor(0.5 * EDGE_FFT * pitch)) + 1, dtype=np.float64) / (EDGE_FFT * pitch)
+    if e.size < 3:
+        return f, None
+    m = e.size - 1
+    lsf = np.diff(e) * (0.5 - 0.5 * np.cos(2.0 * math.pi * (np.arange(m) + 0.5) / m))
+    spectrum = np.abs(np.fft.rfft(lsf, EDGE_FFT))[:f.size]
+    if spectrum[0] == 0.0:
+        return f, None
+    return f, (spectrum / spectrum[0]) / np.sinc(f * pitch) ** 2
+
+
+def _crossing(x, y, level, rising):
+    """The first x, scanning up, at which the piecewise-linear y crosses `level` (upwards if `rising`, else downwards), linearly
+    interpolated between the two samples; None where it does not."""
+    for i in range(1, len(y)):
+        lo, hi = (y[i - 1], y[i]) if rising else (-y[i - 1], -y[i])
+        t = level if rising else -level
+        if lo < t <= hi:
+            return float(x[i - 1] + (x[i] - x[i - 1]) * (t - lo) / (hi - lo))
+    return None
+
+
+def edge_profile(esf, pitch):
+    """The numbers (EDGE_KEYS) of one edge-spread function, the 2C central bins of a table in ascending k, sampled every `pitch` pixels:
+        low, high   the plateau means: of the first and of the last W = max(C // 4, 1) samples (math.fsum / W)
+        step        high - low, signed: which side comes out brighter is the processor's business
+        rise        with e = (esf - low) / step, the distance in pixels along the edge's normal between the first upward crossing of
+                    0.1 and the first upward crossing of 0.9 at or behind it, both interpolated linearly between samples
+        overshoot   max(max e - 1, 0), undershoot max(-min e, 0): fractions of the step, the rebound past the last plateau and
+                    before the first (in the direction of ascending k, whatever the step's sign)
+        mtf50, mtf10   the lowest frequency in cycles / pixel at which edge_mtf falls through 0.5 and 0.1, interpolated linearly
+        mtf_peak, mtf_peak_f   the largest value of edge_mtf up to 0.5 cycles / pixel (an enhancement lifts it above 1) and where
+    rise, overshoot and undershoot are None for a step of 0, the four MTF numbers where edge_mtf has none, a crossing where the
+    curve does not cross."""
+    e = [float(v) for v in esf]
+    w = max(len(e) // 8, 1)
+    low, high = math.fsum(e[:w]) / w, math.fsum(e[-w:]) / w
+    out = dict.fromkeys(EDGE_KEYS)
+    out.update(low=low, high=high, step=high - low)
+    if out["step"] != 0.0:
+        n = [(v - low) / out["step"] for v in e]
+        pos = [i * pitch for i in range(len(n))]
+        x10 = _crossing(pos, n, 0.1, True)
+        first = next((i for i in range(1, len(n)) if x10 is not None and pos[i] >= x10), None)
+        x90 = None if first is None else _crossing([x10] + pos[first:], [0.1] + n[first:], 0.9, True)
+        out.update(rise=None if x90 is None else x90 - x10, overshoot=max(max(n) - 1.0, 0.0), undershoot=max(-min(n), 0.0))
+    f, mtf = edge_mtf(e, pitch)
+    if mtf is not None:
+        peak = int(np.argmax(mtf))
+        out.update(mtf50=_crossing(f, mtf, 0.5, False), mtf10=_crossing(f, mtf, 0.1, False), mtf_peak=float(mtf[peak]), mtf_peak_f=float(f[peak]))
+    return out
+
+
+def edge_central(h, p, q):
+    """C = floor(4 (q - p) h / q): the bins -C <= k < C of an edge's table are non-empty whatever the orientation (>= 2 for h >= 8)."""
+    return (4 * (q - p) * h) // q
+
+
+def edge_summary(stats):
+    """What the study reports of each edge, from edge_statistics' (or musica_sim_edges') exact integers: one function for every study
+    path, so the paths agree to the last bit. Per edge, in f64 and from the central bins -C .. C - 1 only (edge_central): "esf", the
+    three edge-spread functions as lists, a = sum_a / n, b = sum_b / n and d = (sum_a - sum_b) / n (each one correctly rounded division
+    of two integers; d is the response to the edge alone, the anatomy under it removed) with "k0" = -C and "pitch" = edge_pitch(p, q);
+    and under "a", "b" and "d" edge_profile's numbers of each. No threshold is fixed here: these are findings."""
+    out = []
+    for s in stats:
+        c, big = edge_central(s["h"], s["p"], s["q"]), s["bins"] // 2
+        n, sa, sb = ([int(v) for v in s[k][big - c:big + c]] for k in ("n", "sum_a", "sum_b"))
+        esf = {"a": [x / m for x, m in zip(sa, n)], "b": [x / m for x, m in zip(sb, n)], "d": [(x - y) / m for x, y, m in zip(sa, sb, n)]}
+        pitch = edge_pitch(s["p"], s["q"])
+        d = {side: edge_profile(esf[side], pitch) for side in EDGE_SIDES}
+        d["esf"] = dict(esf, k0=-c, pitch=pitch)
+        out.append(d)
+    return out
+
+
+EDGE_ROW_KEYS = ("step", "rise", "overshoot", "undershoot", "mtf50", "mtf_peak")   # what an edge_ row's "edges" gathers, of the d profile
+EDGE_ROW_STATS = ("min", "mean", "max", "count")
+
+
+def _edge_spread(summary):
+    out = {"edges": len(summary)}
+    for k in EDGE_ROW_KEYS:
+        v = [s["d"][k] for s in summary if s["d"][k] is not None]
+        out[k] = {"min": min(v), "mean": math.fsum(v) / len(v), "max": max(v), "count": len(v)} if v else {"min": None, "mean": None, "max": None, "count": 0}
+    return out
+
+
+def edge_row(edges, stats, sq_diff_sum, pixels, tables=False):
+    """An edge_ row's "edges" value from the row's edges, their exact tables and the full frame's exact sum of squared differences over
+    `pixels` pixels: {"all": spread, "orientations": {o: spread}, "halves": {h: spread}, in ascending o and h, "outside_mse":
+    (sq_diff_sum - sum roi_ssd) / (pixels - sum roi_pixels), the change away from every region}. A spread is {"edges": the group's
+    size, and for each of EDGE_ROW_KEYS (of the a - b profile) its min, mean, max over the edges that have the number and their
+    count}. With tables=True also "per_edge": the (x, y, h, p, q, o, c) and edge_summary's dict of every edge, the three
+    edge-spread functions included, in the list's order."""
+    summary = edge_summary(stats)
+    out = {"all": _edge_spread(summary)}
+    for name, at in (("orientations", 5), ("halves", 2)):
+        out[name] = {g: _edge_spread([s for e, s in zip(edges, summary) if e[at] == g]) for g in sorted(set(e[at] for e in edges))}
+    rois, inside = sum(s["roi_ssd"] for s in stats), sum(s["roi_pixels"] for s in stats)
+    outside = int(pixels) - inside
+    out["outside_mse"] = (int(sq_diff_sum) - rois) / outside if outside else 0.0
+    if tables:
+        out["per_edge"] = [dict(s, x=e[0], y=e[1], h=e[2], p=e[3], q=e[4], o=e[5], c=e[6]) for e, s in zip(edges, summary)]
+    return out

@@ -158,6 +158,13 @@ SIM_TILE = 64               # MUSICA_SIM_TILE
 DETAIL_MAX_RADIUS = 64      # MUSICA_DETAIL_MAX_RADIUS
 DETAIL_MAX_CONTRAST = 512   # MUSICA_DETAIL_MAX_CONTRAST
 DETAIL_MAX = 1024           # MUSICA_DETAIL_MAX
+EDGE_MIN_HALF = 8           # MUSICA_EDGE_MIN_HALF
+EDGE_MAX_HALF = 128         # MUSICA_EDGE_MAX_HALF
+EDGE_MIN_Q = 4              # MUSICA_EDGE_MIN_Q
+EDGE_MAX_Q = 16             # MUSICA_EDGE_MAX_Q
+EDGE_MAX_CONTRAST = 512     # MUSICA_EDGE_MAX_CONTRAST
+EDGE_MAX = 256              # MUSICA_EDGE_MAX
+EDGE_BINS_MAX = 2048        # MUSICA_EDGE_BINS_MAX
 
 
 def zoom_ratio(zoom):
@@ -248,6 +255,69 @@ class SimDetailResult(C.Structure):
         d = {zone: {k: int(getattr(self, k)[i]) for k in DETAIL_SUMS} for i, zone in enumerate(DETAIL_ZONES)}
         d.update(box_ssd=int(self.box_ssd), box_pixels=int(self.box_pixels))
         return d
+
+
+def edge_bins(h, p, q):
+    """musica_edge_bins: the bins 2B + 1 of the edge-spread table of an edge of half-side h and slope p / q, B = ceil(4 (q + p) h / q);
+    0 for an inadmissible triple (8 <= h <= EDGE_MAX_HALF, 1 <= p < q, 4 <= q <= EDGE_MAX_Q, gcd(p, q) = 1)."""
+    h, p, q = int(h), int(p), int(q)
+    if not (EDGE_MIN_HALF <= h <= EDGE_MAX_HALF and EDGE_MIN_Q <= q <= EDGE_MAX_Q and 1 <= p < q and math.gcd(p, q) == 1):
+        return 0
+    return 2 * (-((-4 * (q + p) * h) // q)) + 1
+
+
+def edge_list(edges, n, with_contrast=True):
+    """The edges (x, y, h, p, q, o, c) of a slanted-edge list for a plane of side n as harness.insert_edges, harness.edge_statistics and
+    the library take it, a tuple of tuples of ints, else ValueError: 1 .. EDGE_MAX edges of integers, 8 <= h <= EDGE_MAX_HALF, a slope
+    p / q with 1 <= p < q, 4 <= q <= EDGE_MAX_Q in lowest terms, an orientation o of 0 .. 3, 1 <= |c| <= EDGE_MAX_CONTRAST
+    (with_contrast=False: c is not looked at, as the measurement does not), every plate |px - x|, |py - y| <= 2h inside [0, n)^2 and
+    the plates pairwise disjoint."""
+    try:
+        out = []
+        for e in edges:
+            x, y, h, p, q, o, c = e
+            if any(v != int(v) for v in e):
+                raise TypeError
+            out.append(tuple(int(v) for v in e))
+    except (TypeError, ValueError):
+        raise ValueError("an edge list holds septuples of integers (x, y, h, p, q, o, c), got %r" % (edges,))
+    n = int(n)
+    if not 1 <= len(out) <= EDGE_MAX:
+        raise ValueError("an edge list holds 1 .. %d edges, got %d" % (EDGE_MAX, len(out)))
+    for i, (x, y, h, p, q, o, c) in enumerate(out):
+        if not EDGE_MIN_HALF <= h <= EDGE_MAX_HALF:
+            raise ValueError("edge %d: half-side %d is not in %d .. %d" % (i, h, EDGE_MIN_HALF, EDGE_MAX_HALF))
+        if not edge_bins(h, p, q):
+            raise ValueError("edge %d: slope %d / %d is not 1 <= p < q, %d <= q <= %d in lowest terms" % (i, p, q, EDGE_MIN_Q, EDGE_MAX_Q))
+        if not 0 <= o <= 3:
+            raise ValueError("edge %d: orientation %d is not in 0 .. 3" % (i, o))
+        if with_contrast and not 1 <= abs(c) <= EDGE_MAX_CONTRAST:
+            raise ValueError("edge %d: contrast %d is not 1 <= |c| <= %d" % (i, c, EDGE_MAX_CONTRAST))
+        if x - 2 * h < 0 or y - 2 * h < 0 or x + 2 * h >= n or y + 2 * h >= n:
+            raise ValueError("edge %d: the plate (%d, %d) +- %d leaves the %d x %d plane" % (i, x, y, 2 * h, n, n))
+    a = np.array(out, dtype=np.int64)
+    reach = 2 * (a[:, 2][:, None] + a[:, 2][None, :])
+    meet = (np.abs(a[:, 0][:, None] - a[:, 0][None, :]) <= reach) & (np.abs(a[:, 1][:, None] - a[:, 1][None, :]) <= reach)
+    np.fill_diagonal(meet, False)
+    if meet.any():
+        i, j = np.argwhere(meet)[0]
+        raise ValueError("the plates of edges %d and %d are not disjoint" % (i, j))
+    return tuple(out)
+
+
+class Edge(C.Structure):
+    """musica_edge: a slanted edge of slope p / q and orientation o through the integer pixel centre (x, y), measured over
+    |dx|, |dy| <= half and inserted over |dx|, |dy| <= 2 half with `contrast` / 1024."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("half", C.c_uint32), ("p", C.c_uint32), ("q", C.c_uint32), ("orientation", C.c_uint32),
+                ("contrast", C.c_int32)]
+
+
+EDGE_SUMS = ("n", "sum_a", "sum_b", "sum_aa")   # the four rows of an edge's table
+
+
+class SimEdgeResult(C.Structure):
+    """musica_sim_edge_result: the region's exact sum of squared differences and where the edge's table lies in `tables`."""
+    _fields_ = [("roi_ssd", C.c_uint64), ("roi_pixels", C.c_uint64), ("table_offset", C.c_uint64), ("bins", C.c_uint64)]
 
 
 class SimDisplaceResult(C.Structure):
@@ -450,6 +520,9 @@ ABI = {
     "musica_alter_scatter": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_details": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Detail)]),
     "musica_sim_details": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Detail), C.POINTER(SimDetailResult)]),
+    "musica_alter_edges": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Edge)]),
+    "musica_sim_edges": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Edge), C.POINTER(SimEdgeResult), _U32P, C.c_uint64]),
+    "musica_edge_bins": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -857,6 +930,24 @@ class MusicaProcessing:
         self._ok(self._lib.musica_sim_details(self._h, int(image_index), int(slot), len(ds), arr, res), "musica_sim_details")
         return [res[i].as_dict() for i in range(len(ds))]
 
+    def sim_edges(self, edges, slot, image_index=0):
+        """harness.edge_statistics(output of `image_index`, reference slot `slot`, edges) on the device: the edges (x, y, h, p, q, o, c)
+        in the (N - 20)^2 output plane's coordinates (edge_list; c is not looked at). Returns one dict per edge: the Python ints h, p, q,
+        bins, roi_ssd, roi_pixels and the uint32 arrays n, sum_a, sum_b, sum_aa of `bins` entries."""
+        es = edge_list(edges, self.imageSize - 2 * OUT_MARGIN, with_contrast=False)
+        bins = [edge_bins(e[2], e[3], e[4]) for e in es]
+        words = 4 * sum(bins)
+        arr, res, tables = (Edge * len(es))(*[Edge(*e) for e in es]), (SimEdgeResult * len(es))(), np.zeros(words, dtype=np.uint32)
+        self._ok(self._lib.musica_sim_edges(self._h, int(image_index), int(slot), len(es), arr, res, tables.ctypes.data_as(_U32P), words),
+                 "musica_sim_edges")
+        out = []
+        for e, r in zip(es, res):
+            t = tables[int(r.table_offset):int(r.table_offset) + 4 * int(r.bins)].reshape(4, int(r.bins))
+            d = {"h": e[2], "p": e[3], "q": e[4], "bins": int(r.bins), "roi_ssd": int(r.roi_ssd), "roi_pixels": int(r.roi_pixels)}
+            d.update((k, t[i].copy()) for i, k in enumerate(EDGE_SUMS))
+            out.append(d)
+        return out
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -1066,6 +1157,13 @@ class MusicaProcessing:
         ds = detail_list(details, self.imageSize)
         arr = (Detail * len(ds))(*[Detail(*d) for d in ds])
         self._ok(self._lib.musica_alter_details(self._h, int(image_index), len(ds), arr), "musica_alter_details")
+
+    def alter_edges(self, edges, image_index=0):
+        """harness.insert_edges(src, edges): the source with the slanted-edge plates (x, y, h, p, q, o, c) of an edge list (edge_list)
+        inserted."""
+        es = edge_list(edges, self.imageSize)
+        arr = (Edge * len(es))(*[Edge(*e) for e in es])
+        self._ok(self._lib.musica_alter_edges(self._h, int(image_index), len(es), arr), "musica_alter_edges")
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -35,6 +35,8 @@ ENSEMBLE_CSV_HEADER = ['raw file', 'alteration', 'realisations'] + ['%s %s' % (g
 COV_CSV_NAMES = (("noise_var", "noise var"), ("rho_x", "rho x"), ("rho_y", "rho y"), ("corr_area", "correlation area"), ("hf_fraction", "hf fraction"))
 DETAIL_CSV_HEADER = ['raw file', 'alteration', 'radius', 'details'] + ['%s %s' % (k, w) for k in DETAIL_ROW_KEYS for w in DETAIL_ROW_STATS] + \
                     ['outside mse']   # contrast_detail.csv
+EDGE_CSV_HEADER = ['raw file', 'alteration', 'orientation', 'edges'] + ['%s %s' % (k, w) for k in EDGE_ROW_KEYS for w in EDGE_ROW_STATS] + \
+                  ['outside mse']   # edge_response.csv
 
 
 def covariance_csv_header(radius):
@@ -132,6 +134,15 @@ def _detail_lines(studies):
                 yield [raw_name, r["alteration"], radius, g["count"]] + [g[k][w] for k in DETAIL_ROW_KEYS for w in DETAIL_ROW_STATS] + [d["outside_mse"]]
 
 
+def _edge_lines(studies):
+    """edge_response.csv's lines: one per edge_ row and orientation, ascending."""
+    for raw_name, rows in studies:
+        for r in rows:
+            d = r.get("edges")
+            for o, g in (d["orientations"].items() if d else ()):
+                yield [raw_name, r["alteration"], o, g["edges"]] + [g[k][w] for k in EDGE_ROW_KEYS for w in EDGE_ROW_STATS] + [d["outside_mse"]]
+
+
 def write_studies_csvs(studies, out_dir, mean_cnr=True):
     """The reference's output files for several raw images: `studies` is a list of (raw_name, rows) pairs (run_study's rows), written
     in order into one direct_robustness.csv / reg_based_robustness.csv with the reference's column layout (script.py:223-330), plus
@@ -163,7 +174,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
 
     Studies run with details (rows[0] has "details") also get contrast_detail.csv (DETAIL_CSV_HEADER): one line per cd_ row and radius,
     the number of details of that radius, the mean, min, max and population std over their positions of contrast, cnr, rose and halo,
-    and the row's outside mse (the same on each of its lines)."""
+    and the row's outside mse (the same on each of its lines).
+
+    Studies run with edges (rows[0] has "edges") also get edge_response.csv (EDGE_CSV_HEADER): one line per edge_ row and orientation,
+    the number of edges of that orientation, the min, mean, max over them and the count of those that have the number (an empty cell
+    where none has) of step, rise, overshoot, undershoot, mtf50 and mtf_peak, and the row's outside mse."""
     os.makedirs(out_dir, exist_ok=True)
     having = lambda key: [(raw_name, rows) for raw_name, rows in studies if rows and key in rows[0]]   # noqa: E731
     toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
@@ -194,6 +209,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
             _write_csv(out_dir, name, header, _lines(covered, cells))
     if having("details"):
         _write_csv(out_dir, "contrast_detail.csv", DETAIL_CSV_HEADER, _detail_lines(having("details")))
+    if having("edges"):
+        _write_csv(out_dir, "edge_response.csv", EDGE_CSV_HEADER, _edge_lines(having("edges")))
     ovds = [[raw_name] + _cells(_ovd(rows), SIM_CSV_KEYS) for raw_name, rows in studies if _ovd(rows) is not None]
     if ovds:
         _write_csv(out_dir, "ref_similarities.csv", REF_CSV_HEADER, ovds)
