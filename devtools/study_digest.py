@@ -11,7 +11,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     and the sums of the same details, shifted into the output plane, of image 1's output against slot 0;
   * the edge-response pair at N = 151: four slanted-edge plates of half-side 8 and 9, one per orientation (a plate across a tile corner
     and one flush with the plane's corner among them), inserted into image 0, and the tables of the same edges, shifted into the output
-    plane, of image 1's output against slot 0.
+    plane, of image 1's output against slot 0;
+  * the grating pair at N = 151: four grating plates of half-side 8 and 9 (a plate across a tile corner and one flush with the plane's
+    corner among them; wave vectors along both axes and in two octants, periods 2, 5, 8 and 9), inserted into image 0, and the tables
+    of the same gratings, shifted into the output plane, of image 1's output against slot 0.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -109,5 +112,10 @@ edges = [(63, 63, 8, 1, 8, 0, -512), (113, 46, 9, 5, 13, 1, 8), (46, 113, 9, 15,
 p.alter_edges(edges)
 note("musica_alter_edges", p.input_pixels()[0])
 note("musica_sim_edges", p.sim_edges([(e[0] - mp.OUT_MARGIN, e[1] - mp.OUT_MARGIN) + e[2:] for e in edges], 0, image_index=1))
+gratings = [(63, 63, 8, 1, 0, 2, (512, -512)), (113, 46, 9, 0, -1, 9, (100, 77, 17, -50, -94, -94, -50, 17, 77)), (46, 113, 9, -2, 1, 5, (-37, -11, 30, 30, -11)),
+            (N - 27, N - 27, 8, 3, -4, 8, (512, 362, 0, -362, -512, -362, 0, 362))]
+p.alter_gratings(gratings)
+note("musica_alter_gratings", p.input_pixels()[0])
+note("musica_sim_gratings", p.sim_gratings([(g[0] - mp.OUT_MARGIN, g[1] - mp.OUT_MARGIN) + g[2:] for g in gratings], 0, image_index=1))
 p.cleanup()
 print(json.dumps(digests))

@@ -829,6 +829,71 @@ int musica_alter_edges(musica_ctx* ctx, uint32_t image_index, uint32_t count, co
 int musica_sim_edges(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t count, const musica_edge* edges,
                      musica_sim_edge_result* results, uint32_t* tables, uint64_t table_words);
 
+/* ---- grating response: sine patches, the region folded by phase where they lie (new, not in the reference) ----
+ * What defines a multi-scale contrast equaliser: its gain as a function of spatial frequency AND of amplitude, and the harmonic
+ * distortion of a pure tone, the direct signature of the non-linearity. The line-pair / sine grating patch. harness.insert_gratings,
+ * harness.grating_statistics and harness.grating_summary are the contract; everything the device computes is integer and
+ * bit-identical to them, from call to call as well (integer LDS atomics and one reduction order).
+ * A grating is (x, y, half, ux, uy, period) and a wave table: an integer pixel centre, MUSICA_GRATING_MIN_HALF <= half <=
+ * MUSICA_GRATING_MAX_HALF, the wave vector (ux, uy) with |ux|, |uy| <= MUSICA_GRATING_MAX_U, not both 0, gcd(|ux|, |uy|) = 1, and the
+ * period T with 2 <= T <= MUSICA_GRATING_MAX_PERIOD, T <= half, 2 |ux| <= T and 2 |uy| <= T (no aliasing along either axis): |u| / T
+ * cycles per pixel along u. With dx = px - x, dy = py - y the phase of a pixel is k = (ux dx + uy dy) mod T, in 0 .. T - 1. The wave
+ * is T integers in 1 / 1024 of the pixel's value, |w| <= MUSICA_GRATING_MAX_CONTRAST. Zones, as for the edges:
+ *   plate    |dx|, |dy| <= 2 half     (side 4 half + 1): what gets inserted
+ *   region   |dx|, |dy| <= half       (side 2 half + 1): what gets measured
+ * A list for a plane of side n holds 1 .. MUSICA_GRATING_MAX gratings whose plates lie inside [0, n)^2 and are pairwise disjoint
+ * (|xi - xj| > 2 (hi + hj) or |yi - yj| > 2 (hi + hj)): a pixel belongs to at most one plate, so nothing depends on the list's
+ * order. The waves travel in one flat array, grating i's table at the sum of the periods before it. Both entry points refuse every
+ * other list before any device work.
+ *   insertion   inside a plate out = min((v * (1024 - wave[k]) + 512) >> 10, 65535), every other pixel copied. ONE rounding, halves
+ *               up; wave[k] = 0 gives v exactly; the largest intermediate is 65535 * 1536 + 512 < 2^32; a non-zero pixel stays
+ *               non-zero.
+ *   statistics  per grating a table of T bins: every pixel of the region falls in bin k, and each bin holds the exact n, sum_a, sum_b
+ *               and sum_aa of its pixels; and over the region the sum of (a - b)^2 and its pixel count. The wave is not looked at.
+ *               Every bin is non-empty (dx and dy each run over at least T consecutive values and reach the multiples of gcd(ux, T)
+ *               and of gcd(uy, T), together those of gcd(ux, uy, T) = 1). A bin holds at most ceil(S / 2) S pixels, S = 2 half + 1
+ *               <= 257 (one of ux, uy is not 0 mod T, so along that axis a phase repeats at a period of at least 2): 33153 pixels,
+ *               33153 * 255^2 < 2^32, every sum fits uint32.
+ * As for the details and the edges there is no musica_sim_..._reference sibling. */
+#define MUSICA_GRATING_MIN_HALF 8
+#define MUSICA_GRATING_MAX_HALF 128
+#define MUSICA_GRATING_MAX_U 8
+#define MUSICA_GRATING_MAX_PERIOD 64
+#define MUSICA_GRATING_MAX_CONTRAST 512
+#define MUSICA_GRATING_MAX 256
+typedef struct musica_grating {
+    int32_t x, y;                   /* the centre, in pixels of the plane the call names */
+    uint32_t half;                  /* MUSICA_GRATING_MIN_HALF .. MUSICA_GRATING_MAX_HALF */
+    int32_t ux, uy;                 /* the wave vector: |ux|, |uy| <= MUSICA_GRATING_MAX_U, not both 0, coprime */
+    uint32_t period;                /* T: 2 .. MUSICA_GRATING_MAX_PERIOD, T <= half, 2 |ux| <= T, 2 |uy| <= T */
+} musica_grating;
+typedef struct musica_sim_grating_result {
+    uint64_t roi_ssd;               /* sum over the region of (a - b)^2 */
+    uint64_t roi_pixels;            /* (2 half + 1)^2 */
+    uint64_t table_offset;          /* where the grating's table starts in `tables`, in words: 4 times the periods of the gratings before it */
+    uint64_t bins;                  /* T */
+} musica_sim_grating_result;
+/* insert_gratings(source plane, gratings) into image `image_index` of the input buffer: the gratings are in the N x N plane's
+ * coordinates, `waves` holds wave_words int16, grating i's `period` entries at the sum of the periods before it. The kernel is
+ * enqueued on the ctx stream (the list and the waves are copied to the device first, which waits for what the stream holds), with
+ * musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step and no reference slot. One
+ * launch, 2 bytes read and 2 written per pixel (kernels_gratings.hip). Refused before any device work: a NULL context, list or waves,
+ * no source, image_index >= batch, a count outside 1 .. MUSICA_GRATING_MAX, a half-side, wave vector or period outside its limits, a
+ * plate that leaves the plane, two plates that are not disjoint, wave_words less than the periods' sum, a wave entry beyond
+ * +- MUSICA_GRATING_MAX_CONTRAST. */
+int musica_alter_gratings(musica_ctx* ctx, uint32_t image_index, uint32_t count, const musica_grating* gratings, const int16_t* waves,
+                          uint64_t wave_words);
+/* grating_statistics of side a, the 8-bit output of batch image `image_index` (quantised while read, exactly as musica_sim_compare
+ * reads it), against side b, reference slot `slot`: results[i] for gratings[i], in the coordinates of the (N - 20)^2 output plane.
+ * `tables` is flat: grating i starts at 4 times the sum over j < i of period_j words (results[i].table_offset) and is laid out
+ * [4][period_i]: n, sum_a, sum_b, sum_aa; table_words, the words `tables` has room for, must be at least the total. Synchronous.
+ * roi_ssd equals musica_sim_compare's sq_diff_sum over the same (2 half + 1)^2 region. Refused before any device work: a NULL context,
+ * list, results or tables, a count outside 1 .. MUSICA_GRATING_MAX, an image too small for the margin, a slot out of range or never
+ * written, image_index >= batch, a half-side, wave vector or period outside its limits, a plate that leaves the plane, two plates
+ * that are not disjoint, table_words too small. */
+int musica_sim_gratings(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t count, const musica_grating* gratings,
+                        musica_sim_grating_result* results, uint32_t* tables, uint64_t table_words);
+
 /* ---- device-resident output and stream ordering (new, not in the reference) ---- */
 
 /* What musica_export_out writes per image. */

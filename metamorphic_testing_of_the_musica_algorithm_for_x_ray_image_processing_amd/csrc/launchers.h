@@ -362,6 +362,28 @@ void launch_alter_edges(hipStream_t st, const uint16_t* src, uint16_t* out, int 
 // 4 x bins u32 from its PackedEdge::table on, all written
 void launch_sim_edges(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedEdge* d_edges, int count,
                       unsigned long long* results, uint32_t* tables);
+// kernels_gratings.hip: the grating relation. A grating (x, y, h, ux, uy, T) of a list that the caller has checked (limits, plates
+// inside the plane and pairwise disjoint), packed: a plane side is at most 16384.
+constexpr int kGratingMinHalf = 8;         // MUSICA_GRATING_MIN_HALF
+constexpr int kGratingMaxHalf = 128;       // MUSICA_GRATING_MAX_HALF
+constexpr int kGratingMaxU = 8;            // MUSICA_GRATING_MAX_U
+constexpr int kGratingMaxPeriod = 64;      // MUSICA_GRATING_MAX_PERIOD
+constexpr int kGratingMaxContrast = 512;   // MUSICA_GRATING_MAX_CONTRAST
+constexpr int kGratingMax = 256;           // MUSICA_GRATING_MAX
+constexpr int kGratingWords = 4;           // u64 of a musica_sim_grating_result
+struct PackedGrating {
+    uint32_t xy;      // x | y << 16
+    uint32_t htuv;    // h | T << 8 | (ux & 0xFF) << 16 | (uy & 0xFF) << 24: ux, uy as signed bytes
+    uint32_t first;   // the sum of the periods before it: where its wave starts in the flat waves, and a quarter of where its table starts
+};
+// harness.insert_gratings(src, gratings) of a dense n x n plane into another (the planes must not overlap); any n >= 1, `count`
+// gratings at d_gratings and their wave tables at d_waves, grating i's at PackedGrating::first (device)
+void launch_alter_gratings(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const PackedGrating* d_gratings, const int16_t* d_waves, int count);
+// harness.grating_statistics: one workgroup per grating. a_plane: the graded f32 plane at output pixel (0, 0), b_plane: the slot's u8
+// plane, pitches in elements, the gratings in the cropped output plane's coordinates; results: count x kGratingWords u64, tables: every
+// grating's 4 x T u32 from 4 * PackedGrating::first on, all written
+void launch_sim_gratings(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedGrating* d_gratings, int count,
+                         unsigned long long* results, uint32_t* tables);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -143,6 +143,11 @@ struct StudyState {
     PackedEdge* d_edges = nullptr;                 // [MUSICA_EDGE_MAX], allocated by the first call of either
     unsigned long long* d_edge_out = nullptr;      // [MUSICA_EDGE_MAX][kEdgeWords], allocated by the first musica_sim_edges
     uint32_t* d_edge_tables = nullptr;             // [MUSICA_EDGE_MAX][4][MUSICA_EDGE_BINS_MAX] (8 MiB), allocated by the first musica_sim_edges
+    // musica_alter_gratings / musica_sim_gratings: the device copy of the call's grating list, its waves, the results and the flat tables
+    PackedGrating* d_gratings = nullptr;           // [MUSICA_GRATING_MAX], allocated by the first call of either
+    int16_t* d_grating_waves = nullptr;            // [MUSICA_GRATING_MAX][MUSICA_GRATING_MAX_PERIOD], allocated by the first musica_alter_gratings
+    unsigned long long* d_grating_out = nullptr;   // [MUSICA_GRATING_MAX][kGratingWords], allocated by the first musica_sim_gratings
+    uint32_t* d_grating_tables = nullptr;          // [MUSICA_GRATING_MAX][4][MUSICA_GRATING_MAX_PERIOD] (256 KiB), allocated by the first musica_sim_gratings
 };
 
 struct musica_ctx : DeviceBuffers {

@@ -1,7 +1,7 @@
-// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the six query calls
-// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_details.hip, kernels_edges.hip), the ensemble accumulators
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the seven query calls
+// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip), the ensemble accumulators
 // (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_details.hip, kernels_edges.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
+// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
@@ -184,6 +184,51 @@ static int edges_check(const char* fn, uint32_t count, const musica_edge* es, in
 static int edges_upload(musica_ctx* c, const char* fn, const std::vector<PackedEdge>& packed) {
     if (!ensure(c, &c->study.d_edges, MUSICA_EDGE_MAX)) return fail("%s: device allocation of the edge list failed", fn);
     HIP_OK(hipMemcpyAsync(c->study.d_edges, packed.data(), packed.size() * sizeof(PackedEdge), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+static_assert(kGratingMinHalf == MUSICA_GRATING_MIN_HALF && kGratingMaxHalf == MUSICA_GRATING_MAX_HALF && kGratingMaxU == MUSICA_GRATING_MAX_U &&
+                  kGratingMaxPeriod == MUSICA_GRATING_MAX_PERIOD && kGratingMaxContrast == MUSICA_GRATING_MAX_CONTRAST && kGratingMax == MUSICA_GRATING_MAX,
+              "kernels_gratings.hip's tile list, u32 pixel, LDS tables and u32 sums hold for the gratings of include/musica.h");
+static_assert(sizeof(musica_sim_grating_result) == kGratingWords * sizeof(uint64_t), "k_sim_gratings writes a musica_sim_grating_result as its u64 words");
+
+// What both grating calls refuse about a list for a plane of side n (processing.grating_list): the count, each half-side, wave vector
+// and period, plates inside the plane, plates pairwise disjoint. Fills `packed` for the device, each grating's wave (and a quarter of
+// its table's place) behind the one before it, and `periods` with the periods' sum. No device work.
+static int gratings_check(const char* fn, uint32_t count, const musica_grating* gs, int n, std::vector<PackedGrating>& packed, uint64_t* periods) {
+    if (count == 0 || count > MUSICA_GRATING_MAX) return fail("%s: count %u out of range [1, %d]", fn, count, MUSICA_GRATING_MAX);
+    packed.resize(count);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_grating& g = gs[i];
+        if (g.half < MUSICA_GRATING_MIN_HALF || g.half > MUSICA_GRATING_MAX_HALF)
+            return fail("%s: grating %u: half-side %u out of range [%d, %d]", fn, i, g.half, MUSICA_GRATING_MIN_HALF, MUSICA_GRATING_MAX_HALF);
+        if (g.ux < -MUSICA_GRATING_MAX_U || g.ux > MUSICA_GRATING_MAX_U || g.uy < -MUSICA_GRATING_MAX_U || g.uy > MUSICA_GRATING_MAX_U ||
+            edge_gcd((uint32_t)std::abs(g.ux), (uint32_t)std::abs(g.uy)) != 1)
+            return fail("%s: grating %u: wave vector (%d, %d) is not coprime with |ux|, |uy| <= %d", fn, i, g.ux, g.uy, MUSICA_GRATING_MAX_U);
+        if (g.period < 2 || g.period > MUSICA_GRATING_MAX_PERIOD || g.period > g.half || 2 * (uint32_t)std::abs(g.ux) > g.period || 2 * (uint32_t)std::abs(g.uy) > g.period)
+            return fail("%s: grating %u: period %u is not 2 <= T <= min(%d, half) with 2 |ux|, 2 |uy| <= T", fn, i, g.period, MUSICA_GRATING_MAX_PERIOD);
+        const int64_t reach = 2 * (int64_t)g.half;
+        if (g.x - reach < 0 || g.y - reach < 0 || g.x + reach >= n || g.y + reach >= n)
+            return fail("%s: grating %u: the plate (%d, %d) +- %d leaves the %d x %d plane", fn, i, g.x, g.y, (int)reach, n, n);
+        packed[i] = {(uint32_t)g.x | ((uint32_t)g.y << 16), g.half | (g.period << 8) | (((uint32_t)g.ux & 0xFFu) << 16) | (((uint32_t)g.uy & 0xFFu) << 24), (uint32_t)at};
+        at += g.period;
+    }
+    for (uint32_t i = 0; i < count; i++)
+        for (uint32_t j = i + 1; j < count; j++) {
+            const int64_t reach = 2 * ((int64_t)gs[i].half + gs[j].half);
+            if (std::abs((int64_t)gs[i].x - gs[j].x) <= reach && std::abs((int64_t)gs[i].y - gs[j].y) <= reach)
+                return fail("%s: the plates of gratings %u and %u are not disjoint", fn, i, j);
+        }
+    *periods = at;
+    return 1;
+}
+
+// The call's list on the device, as details_upload.
+static int gratings_upload(musica_ctx* c, const char* fn, const std::vector<PackedGrating>& packed) {
+    if (!ensure(c, &c->study.d_gratings, MUSICA_GRATING_MAX)) return fail("%s: device allocation of the grating list failed", fn);
+    HIP_OK(hipMemcpyAsync(c->study.d_gratings, packed.data(), packed.size() * sizeof(PackedGrating), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     return 1;
 }
@@ -722,6 +767,37 @@ int musica_sim_edges(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count,
     ABI_CATCH("musica_sim_edges")
 }
 
+// ---- the grating measurement (musica_sim_gratings, include/musica.h; kernels_gratings.hip) ---------------------------------------------
+int musica_sim_gratings(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count, const musica_grating* gratings, musica_sim_grating_result* out,
+                        uint32_t* tables, uint64_t table_words) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_gratings: ctx is NULL");
+    if (!gratings || !out || !tables) return fail("musica_sim_gratings: gratings, results or tables is NULL");
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_gratings: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_gratings: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
+    if (!c->study.written[slot]) return fail("musica_sim_gratings: slot %u was never written", slot);
+    CHECK_IMG(c, idx);
+    std::vector<PackedGrating> packed;
+    uint64_t periods = 0;
+    if (!gratings_check("musica_sim_gratings", count, gratings, (int)sim_side(c), packed, &periods)) return 0;
+    const uint64_t words = 4 * periods;
+    if (table_words < words) return fail("musica_sim_gratings: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_grating_out, (size_t)MUSICA_GRATING_MAX * kGratingWords) && ensure(c, &st.d_grating_tables, (size_t)MUSICA_GRATING_MAX * 4 * MUSICA_GRATING_MAX_PERIOD)))
+        return fail("musica_sim_gratings: device allocation failed");
+    if (!gratings_upload(c, "musica_sim_gratings", packed)) return 0;
+    const int pitch = c->lv[0].pitch;
+    launch_sim_gratings(c->stream, image_slice(c, c->d_graded, idx) + (size_t)MUSICA_OUT_MARGIN * pitch + MUSICA_OUT_MARGIN, pitch, st.slot[slot],
+                        (int)sim_side(c), st.d_gratings, (int)count, st.d_grating_out, st.d_grating_tables);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out, st.d_grating_out, (size_t)count * sizeof(musica_sim_grating_result), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(tables, st.d_grating_tables, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+    ABI_CATCH("musica_sim_gratings")
+}
+
 // ---- ensemble statistics (musica_sim_ensemble_*, include/musica.h; kernels_ensemble.hip) ------------------------------------------------
 int musica_sim_ensemble_reset(musica_ctx* c) {
     ABI_TRY
@@ -1126,6 +1202,30 @@ int musica_alter_edges(musica_ctx* c, uint32_t idx, uint32_t count, const musica
     HIP_OK(hipGetLastError());
     return 1;
     ABI_CATCH("musica_alter_edges")
+}
+
+int musica_alter_gratings(musica_ctx* c, uint32_t idx, uint32_t count, const musica_grating* gratings, const int16_t* waves, uint64_t wave_words) {
+    ABI_TRY
+    if (!c) return fail("musica_alter_gratings: ctx is NULL");
+    if (!gratings || !waves) return fail("musica_alter_gratings: gratings or waves is NULL");
+    if (!c->study.d_alter_src) return fail("musica_alter_gratings: no source plane (musica_alter_set_source)");
+    CHECK_IMG(c, idx);
+    std::vector<PackedGrating> packed;
+    uint64_t periods = 0;
+    if (!gratings_check("musica_alter_gratings", count, gratings, c->N, packed, &periods)) return 0;
+    if (wave_words < periods) return fail("musica_alter_gratings: wave_words %llu is less than the %llu entries of the waves", (unsigned long long)wave_words, (unsigned long long)periods);
+    for (uint64_t i = 0; i < periods; i++)
+        if (waves[i] < -MUSICA_GRATING_MAX_CONTRAST || waves[i] > MUSICA_GRATING_MAX_CONTRAST)
+            return fail("musica_alter_gratings: wave entry %llu is %d, beyond +-%d", (unsigned long long)i, (int)waves[i], MUSICA_GRATING_MAX_CONTRAST);
+    CHECK_CTX(c);
+    if (!ensure(c, &c->study.d_grating_waves, (size_t)MUSICA_GRATING_MAX * MUSICA_GRATING_MAX_PERIOD)) return fail("musica_alter_gratings: device allocation of the waves failed");
+    HIP_OK(hipMemcpyAsync(c->study.d_grating_waves, waves, (size_t)periods * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    if (!gratings_upload(c, "musica_alter_gratings", packed)) return 0;   // synchronises: the caller's waves have been read
+    if (!alter_keep_input(c, "musica_alter_gratings")) return 0;
+    launch_alter_gratings(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, c->study.d_gratings, c->study.d_grating_waves, (int)count);   // kernels_gratings.hip
+    HIP_OK(hipGetLastError());
+    return 1;
+    ABI_CATCH("musica_alter_gratings")
 }
 
 int musica_alter_draws(musica_ctx* c, const musica_alteration* s, int32_t* dst) {

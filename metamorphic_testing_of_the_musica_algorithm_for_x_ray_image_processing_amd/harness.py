@@ -143,6 +143,64 @@ def EDGES(n):
     return tuple(edge_grid(n, c) for c in EDGE_CONTRASTS)
 
 
+# not in the reference: the grating rows (insert_gratings), rows grating_<c> of a study run with `gratings`: cosine patches of the periods
+# GRATING_PERIODS in the directions GRATING_DIRECTIONS on a grid (grating_grid), one row per contrast c / 1024 = 0.8 % .. 12.5 %, the
+# cd_ and edge_ rows' five strengths. GRATINGS(n) gives the five grids of the image size.
+# 0.5 cycles / pixel (the pixel grid's Nyquist frequency along an axis) down to 1 / 32, two steps an octave from T = 2: the band a
+# multi-scale processor's finer levels divide between them. Along the diagonals the frequency is sqrt(2) / T.
+GRATING_PERIODS = (2, 3, 4, 6, 8, 12, 16, 24, 32)
+GRATING_DIRECTIONS = ((1, 0), (0, 1), (1, 1), (1, -1))
+GRATING_CONTRASTS = (8, 16, 32, 64, 128)
+
+
+def grating_half(period):
+    """The half-side of the phantom's plate of a period: max(8, 2T), so the measured region holds at least four periods."""
+    return max(mp.GRATING_MIN_HALF, 2 * int(period))
+
+
+def grating_grid(n, contrast, periods=None):
+    """The study's grating phantom for a raw image of side n: G x G plates of one contrast on a square grid inside the output plane's
+    footprint, built as edge_grid is. With B = PROCESSING_MARGIN, m = n - 2B and h(T) = grating_half(T), `periods` defaults to the
+    longest prefix of GRATING_PERIODS of length k with m // (4 h(T_last) + 1) >= k; G = min(m // (4 h_max + 1), 16) // k * k
+    (ValueError if 0; at most 256 = GRATING_MAX plates), the cell C = m // G, and grating (i, j), i, j < G, row i first, t = i G + j,
+    is (B + j C + C // 2, B + i C + C // 2, h(T), *GRATING_DIRECTIONS[t % 4], T, grating_wave(T, contrast)) with
+    T = periods[(i + j) % k]: the diagonal assignment puts every period G / k times in every row and every column of the grid, the
+    directions cycle fastest. (Which directions a period meets depends on G mod 4: for G = 9, t = i + j mod 4, so a period meets
+    two neighbouring directions; the "directions" groups and "per_grating" keep them apart.) A plate has side 4h + 1 <= C, so the plates are disjoint and lie inside [B, n - B)^2: shifted by -B
+    (output_gratings) the list is valid for the output plane."""
+    n, b = int(n), PROCESSING_MARGIN
+    m = n - 2 * b
+    if periods is None:
+        k = 0
+        while k < len(GRATING_PERIODS) and m // (4 * grating_half(GRATING_PERIODS[k]) + 1) >= k + 1:
+            k += 1
+        periods = GRATING_PERIODS[:k]
+    periods = tuple(int(t) for t in periods)
+    k = len(periods)
+    g = min(m // (4 * max(grating_half(t) for t in periods) + 1), 16) // k * k if k else 0
+    if g <= 0:
+        raise ValueError("a side of %d pixels holds no grid of the periods %r" % (n, periods))
+    c = m // g
+    return mp.grating_list([(b + j * c + c // 2, b + i * c + c // 2, grating_half(periods[(i + j) % k])) +
+                            GRATING_DIRECTIONS[(i * g + j) % len(GRATING_DIRECTIONS)] + (periods[(i + j) % k], grating_wave(periods[(i + j) % k], contrast))
+                            for i in range(g) for j in range(g)], n)
+
+
+def output_gratings(gratings):
+    """A raw plane's gratings in the coordinates of the output plane (the frame cropped by PROCESSING_MARGIN on every side)."""
+    return tuple((g[0] - PROCESSING_MARGIN, g[1] - PROCESSING_MARGIN) + tuple(g[2:]) for g in gratings)
+
+
+def GRATINGS(n):
+    """The five grids of the grating_ rows of a side-n image: grating_grid(n, c) for c in GRATING_CONTRASTS."""
+    return tuple(grating_grid(n, c) for c in GRATING_CONTRASTS)
+
+
+def grating_contrast(gratings):
+    """The contrast a grating list is named after: the largest |w| of its first grating's wave (grating_wave(T, c): |c|)."""
+    return max(abs(w) for w in gratings[0][6])
+
+
 def scaled(values, image_size):
     """The reference's pixel-valued grids scaled from 3072 to `image_size`."""
     return [max(1, int(round(v * image_size / REF_IMAGE_SIZE))) for v in values]
@@ -570,7 +628,7 @@ VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
-                  detail_tables=False, edges=None, edge_tables=False):
+                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -614,18 +672,22 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         edges = [mp.edge_list(g, n) for g in edges]
         for g in edges:
             mp.edge_list(output_edges(g), n - 2 * PROCESSING_MARGIN)
+    if gratings is not None:  # likewise
+        gratings = [mp.grating_list(g, n) for g in gratings]
+        for g in gratings:
+            mp.grating_list(output_gratings(g), n - 2 * PROCESSING_MARGIN)
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
            (("ensemble",) if ensemble else ()) + (("details",) if details is not None else ()) + \
-           (("edges",) if edges is not None else ())
+           (("edges",) if edges is not None else ()) + (("gratings",) if gratings is not None else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, details=details or [], detail_tables=bool(detail_tables),
-        edges=edges or [], edge_tables=bool(edge_tables), keys=keys, device_alterations=device_alterations)
+        edges=edges or [], edge_tables=bool(edge_tables), gratings=gratings or [], grating_tables=bool(grating_tables), keys=keys, device_alterations=device_alterations)
 
 
 # One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
@@ -633,14 +695,14 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
 # context's method, the host's function, their parameter), which both move a reference plane as the alteration moves the input: the
 # registered comparison is then against the moved plane; noise = (the row's ordinal, alter(context, stream, image_index)) for the rows
 # that draw, what their ensembles repeat; details = the raw plane's detail list of a cd_ row, measured where the details lie; edges = the
-# raw plane's edge list of an edge_ row, likewise.
-Alteration = collections.namedtuple("Alteration", "name host dev region move noise details edges", defaults=(None, None, None, None, None))
+# raw plane's edge list of an edge_ row, gratings = its grating list of a grating_ row, likewise.
+Alteration = collections.namedtuple("Alteration", "name host dev region move noise details edges gratings", defaults=(None, None, None, None, None, None))
 
 
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4, blur, zoom, scatter, cd and edge rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur, zoom, scatter, cd, edge and grating rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -679,6 +741,8 @@ def study_alterations(raw, rng, p, seed, shape, opt):
         yield Alteration("cd_%d" % g[0][3], lambda: insert_details(raw, g), lambda: p.alter_details(g), details=g)
     for g in opt.edges:
         yield Alteration("edge_%d" % g[0][6], lambda: insert_edges(raw, g), lambda: p.alter_edges(g), edges=g)
+    for g in opt.gratings:
+        yield Alteration("grating_%d" % grating_contrast(g), lambda: insert_gratings(raw, g), lambda: p.alter_gratings(g), gratings=g)
 
 
 class Scorer:
@@ -734,6 +798,11 @@ class DeviceScorer(Scorer):
         """One musica_sim_edges call against the unaltered result; the full frame's integers are the row's direct comparison's."""
         direct = self.compared[0]
         return edge_row(edges, self.proc.sim_edges(edges, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.edge_tables)
+
+    def gratings(self, gratings):
+        """One musica_sim_gratings call against the unaltered result; the full frame's integers are the row's direct comparison's."""
+        direct = self.compared[0]
+        return grating_row(gratings, self.proc.sim_gratings(gratings, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.grating_tables)
 
     def tone(self, comparisons):
         """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
@@ -800,6 +869,11 @@ class HostScorer(Scorer):
         a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
         return edge_row(edges, edge_statistics(self.out, self.planes[SLOT_UNALTERED], edges), int(((a - b) ** 2).sum()), a.size, self.opt.edge_tables)
 
+    def gratings(self, gratings):
+        a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
+        return grating_row(gratings, grating_statistics(self.out, self.planes[SLOT_UNALTERED], gratings), int(((a - b) ** 2).sum()), a.size,
+                           self.opt.grating_tables)
+
     def tone(self, comparisons):
         return [tone_similarities(*self.sides(*c)) for c in comparisons]
 
@@ -864,7 +938,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
-              blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False):
+              blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -980,11 +1054,25 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     "edges" is equal to the last bit on every path. edge_tables: the dict also carries "per_edge", the three edge-spread functions
     of every edge included. The rows draw nothing from `rng` and take no ordinal. Nothing is asserted about how an edge is rendered:
     these are findings. A linear, shift-invariant processor would give the same normalised response at every contrast, position,
-    orientation and polarity; where MUSICA does not is the finding."""
+    orientation and polarity; where MUSICA does not is the finding.
+
+    gratings: grating grids, each a grating list (x, y, h, ux, uy, T, wave) for the raw plane (processing.grating_list; GRATINGS(n) for
+    the five contrasts 0.8 % .. 12.5 % on grating_grid's phantom) that is also valid for the output plane when shifted by the margin
+    (output_gratings), else ValueError before any work. None adds nothing. Otherwise rows grating_<c> (c: the largest |w| of the grid's
+    first wave) follow the edge_ rows: the raw image with the grid's plates inserted (insert_gratings; on the device: alter_gratings),
+    "direct" scored as for every row, "registered" None, and every row of the study gains "gratings": None except in the grating_
+    rows, where it is grating_row's dict of the gratings measured where they lie against the unaltered result (grating_statistics; on
+    the device one musica_sim_gratings call behind the row's musica_sim_compare, whose exact sq_diff_sum of the full frame gives
+    outside_mse): over all gratings, per direction and per period the median, min, max and count of the gain, the harmonic distortion
+    and the response of the a - b profile folded over one period (grating_summary), and outside_mse. Host and device summarise exact
+    integers with one function, so "gratings" is equal to the last bit on every path. grating_tables: the dict also carries
+    "per_grating", the folded profiles of every grating included. The rows draw nothing from `rng` and take no ordinal. Nothing is
+    asserted about the gains: these are findings. A linear processor would give the same gain at every contrast and no harmonics;
+    how MUSICA's gain falls with the amplitude and rises with the frequency, and what it adds at 2f and 3f, is the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
-                        edges, edge_tables)
+                        edges, edge_tables, gratings, grating_tables)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -1021,6 +1109,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             out["details"] = scorer.details(output_details(alteration.details))
         if alteration is not None and alteration.edges:
             out["edges"] = scorer.edges(output_edges(alteration.edges))
+        if alteration is not None and alteration.gratings:
+            out["gratings"] = scorer.gratings(output_gratings(alteration.gratings))
         out["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         if eproc is not None:
             out["ensemble"] = ensemble_of(eproc, alteration.noise, registered[1] if registered else None, full, opt)
@@ -1178,6 +1268,12 @@ def main(argv=None):
                          "undershoot, edge MTF per orientation), written to edge_response.csv; on the GPU with --device-metrics / "
                          "--device-alterations (musica_sim_edges, musica_alter_edges)")
     ap.add_argument("--edge-tables", action="store_true", help="with --edges: keep every edge's numbers and edge-spread functions in the rows (\"per_edge\")")
+    ap.add_argument("--gratings", action="store_true",
+                    help="add the rows grating_<c>: cosine patches of the periods 2 .. 32 pixels in four directions inserted on a grid "
+                         "(grating_grid) at the contrasts c / 1024 = 0.8 %% .. 12.5 %%, the output folded by phase where they lie (gain, "
+                         "harmonic distortion and response per period), written to grating_response.csv; on the GPU with --device-metrics / "
+                         "--device-alterations (musica_sim_gratings, musica_alter_gratings)")
+    ap.add_argument("--grating-tables", action="store_true", help="with --gratings: keep every grating's numbers and folded profiles in the rows (\"per_grating\")")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -1209,6 +1305,8 @@ def main(argv=None):
         ap.error("--detail-tables keeps what --details measures: give --details")
     if args.edge_tables and not args.edges:
         ap.error("--edge-tables keeps what --edges measures: give --edges")
+    if args.grating_tables and not args.gratings:
+        ap.error("--grating-tables keeps what --gratings measures: give --gratings")
     if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
         ap.error("--covariance takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
     if args.covariance and not args.ensemble:
@@ -1268,6 +1366,8 @@ def main(argv=None):
         shift_args.update(details=DETAILS(args.size), detail_tables=args.detail_tables)
     if args.edges:
         shift_args.update(edges=EDGES(args.size), edge_tables=args.edge_tables)
+    if args.gratings:
+        shift_args.update(gratings=GRATINGS(args.size), grating_tables=args.grating_tables)
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

@@ -899,3 +899,178 @@ def edge_row(edges, stats, sq_diff_sum, pixels, tables=False):
     if tables:
         out["per_edge"] = [dict(s, x=e[0], y=e[1], h=e[2], p=e[3], q=e[4], o=e[5], c=e[6]) for e, s in zip(edges, summary)]
     return out
+
+
+# ---- grating response: sine patches, the region folded by phase where they lie (not in the reference's script) -------------------------
+# What defines a multi-scale contrast equaliser is its gain as a function of spatial frequency and of amplitude; the edge rows give one
+# broadband MTF per contrast and the discs mix all frequencies of their size. The classical test object is the line-pair / sine grating
+# patch. A grating is (x, y, h, ux, uy, T, wave): an integer pixel centre, a half-side GRATING_MIN_HALF <= h <= GRATING_MAX_HALF, a wave
+# vector (ux, uy) with |ux|, |uy| <= GRATING_MAX_U, not both 0 and coprime, a period 2 <= T <= min(GRATING_MAX_PERIOD, h) with
+# 2 |ux| <= T and 2 |uy| <= T (no aliasing along either axis; |u| / T cycles per pixel along u), and a wave of T integers
+# |w| <= GRATING_MAX_CONTRAST in 1 / 1024 of the pixel's value. With dx = px - x, dy = py - y the phase of a pixel is
+# k = (ux dx + uy dy) mod T, in 0 .. T - 1. The plate |dx|, |dy| <= 2h is what gets inserted, the region |dx|, |dy| <= h what gets
+# measured, as for the edges; the plates of a list lie inside the plane and are pairwise disjoint (processing.grating_list). Everything
+# up to grating_summary is integer: these functions are the contract of musica_alter_gratings and musica_sim_gratings
+# (include/musica.h), which are bit-identical to them. The device contract starts from the integer wave table: the cosine of
+# grating_wave is the study's choice, not the library's.
+
+def grating_phases(ux, uy, period, reach):
+    """k = (ux dx + uy dy) mod T, in 0 .. T - 1, of every pixel of the square |dx|, |dy| <= reach about a grating's centre, an int64
+    array indexed [dy + reach, dx + reach]."""
+    d = np.arange(-int(reach), int(reach) + 1, dtype=np.int64)
+    return (int(ux) * d[None, :] + int(uy) * d[:, None]) % int(period)
+
+
+def grating_wave(period, contrast):
+    """The study's wave table: w[k] = floor(c cos(2 pi k / T) + 1/2) for k = 0 .. T - 1, a cosine of amplitude c / 1024 that attenuates
+    most at phase 0, as a tuple of ints. Where 12 k / T is an integer and the cosine is rational (0, +-1/2, +-1: the even multiples of
+    pi / 6 and the odd multiples of pi / 2) the exact value is substituted and the rounding done in integers, floor((2 c cos + 1) / 2).
+    This makes the table the same on every libm: floor(z + 1/2) depends on the last bits of z = c cos only next to a half-integer z, and
+    a z that IS a half-integer needs a rational cosine, (2j + 1) / (2c); by Niven's theorem the only rational cosines of rational
+    multiples of pi are 0, +-1/2 and +-1, all substituted here. For even c they give the integers 0, +-c/2, +-c, so there are no ties
+    at all; for odd c the tie at +-1/2 is rounded up, exactly. (Everywhere else z stays at least 1e-6 from a half-integer over the
+    whole domain T <= GRATING_MAX_PERIOD, c <= GRATING_MAX_CONTRAST, ten orders above a libm's error: tests/test_grating_restatement.py.)"""
+    t, c = int(period), int(contrast)
+    if not (2 <= t <= mp.GRATING_MAX_PERIOD and abs(c) <= mp.GRATING_MAX_CONTRAST):
+        raise ValueError("grating_wave needs 2 <= T <= %d and |c| <= %d, got %r, %r" % (mp.GRATING_MAX_PERIOD, mp.GRATING_MAX_CONTRAST, period, contrast))
+    twice = {0: 2, 2: 1, 3: 0, 4: -1, 6: -2, 8: -1, 9: 0, 10: 1}     # 2 cos(m pi / 6) where it is rational
+    out = []
+    for k in range(t):
+        m = 12 * k // t if (12 * k) % t == 0 else None
+        out.append((c * twice[m] + 1) // 2 if m in twice else int(math.floor(c * math.cos(2.0 * math.pi * k / t) + 0.5)))
+    return tuple(out)
+
+
+def insert_gratings(image, gratings):
+    """The square 2-D uint16 plane with the plates of `gratings` (processing.grating_list for its side, else ValueError before any
+    work) inserted: inside each plate
+        out = min((v * (1024 - wave[k]) + 512) >> 10, 65535)
+    and every other pixel copied: ONE rounding, halves up. wave[k] = 0 gives exactly v; the largest intermediate is 65535 * 1536 + 512
+    < 2^32; a non-zero pixel stays non-zero (v * 512 + 512 >= 1024 for v >= 1)."""
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype != np.uint16 or not image.size:
+        raise ValueError("insert_gratings needs a non-empty square 2-D uint16 plane, got %r %s" % (image.shape, image.dtype))
+    gratings = mp.grating_list(gratings, image.shape[0])
+    out = image.copy()
+    for x, y, h, ux, uy, t, wave in gratings:
+        w = np.array(wave, dtype=np.int64)[grating_phases(ux, uy, t, 2 * h)]
+        plate = out[y - 2 * h:y + 2 * h + 1, x - 2 * h:x + 2 * h + 1]      # a view: the plate is rewritten in place
+        plate[...] = np.minimum((plate.astype(np.int64) * (1024 - w) + 512) >> 10, 65535).astype(np.uint16)
+    return out
+
+
+def grating_statistics(a, b, gratings):
+    """The exact phase-folded tables of every grating of `gratings` (in the planes' coordinates; the wave is not looked at) over two
+    square uint8 planes of equal shape: what musica_sim_gratings returns. Every pixel of the region falls in bin k, its phase. One dict
+    per grating: the ints h, ux, uy, T, the uint32 arrays n, sum_a, sum_b, sum_aa of T entries (the pixels of each bin, their sums over
+    a and b, the sum of a^2), roi_ssd = the sum over the region of (a - b)^2 and roi_pixels = (2h + 1)^2.
+    Every bin is non-empty: dx and dy each run over S = 2h + 1 >= 2T + 1 consecutive values, so ux dx reaches every multiple of
+    gcd(ux, T) mod T and uy dy every multiple of gcd(uy, T), together every multiple of gcd(ux, uy, T) = 1. A bin holds at most
+    ceil(S / 2) S pixels: one of ux, uy is not 0 mod T (2 |u| <= T and gcd(ux, uy) = 1), so along that axis a phase repeats at a
+    period of at least 2; S <= 257 gives 33153 pixels and 33153 * 255^2 < 2^32, so every sum fits uint32."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or a.shape != b.shape or a.shape[0] != a.shape[1] or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("grating_statistics needs two square 2-D uint8 planes of equal shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    gratings = mp.grating_list(gratings, a.shape[0], with_wave=False)
+    out = []
+    for x, y, h, ux, uy, t, _ in gratings:
+        k = grating_phases(ux, uy, t, h).ravel()
+        pa = a[y - h:y + h + 1, x - h:x + h + 1].astype(np.int64).ravel()
+        pb = b[y - h:y + h + 1, x - h:x + h + 1].astype(np.int64).ravel()
+        d = {"h": h, "ux": ux, "uy": uy, "T": t, "roi_ssd": int(((pa - pb) ** 2).sum()), "roi_pixels": int(pa.size)}
+        for key, w in zip(mp.GRATING_SUMS, (np.ones_like(pa), pa, pb, pa * pa)):
+            d[key] = np.bincount(k, weights=w, minlength=t).astype(np.uint32)   # exact: every sum is below 2^53
+        out.append(d)
+    return out
+
+
+GRATING_SIDES = ("a", "b", "d")     # the three folded profiles of a grating: of side a, of side b, of a - b
+GRATING_HARMONICS = 3               # the harmonics h = 1 .. 3 that grating_summary reports
+
+
+def grating_harmonic(profile, h):
+    """(amplitude, phase) of harmonic h >= 1 of one period m_0 .. m_(T-1) of a profile, or None where 2h > T (the harmonic does not
+    exist): X = sum_k m_k e^(-2 pi i h k / T) (math.fsum of the real and of the imaginary parts, the angle reduced in integers,
+    2 pi ((h k) mod T) / T), the amplitude (2 / T) |X|, or (1 / T) |X| for the Nyquist harmonic 2h = T, the phase atan2(Im X, Re X):
+    m_k = A cos(2 pi h k / T - p) gives (A, -p)."""
+    t = len(profile)
+    if 2 * h > t:
+        return None
+    re = math.fsum(v * math.cos(2.0 * math.pi * ((h * k) % t) / t) for k, v in enumerate(profile))
+    im = -math.fsum(v * math.sin(2.0 * math.pi * ((h * k) % t) / t) for k, v in enumerate(profile))
+    return ((1.0 if 2 * h == t else 2.0) / t) * math.hypot(re, im), math.atan2(im, re)
+
+
+def grating_summary(stats, gratings):
+    """What the study reports of each grating, from grating_statistics' (or musica_sim_gratings') exact integers and the list's waves:
+    one function for every study path, so the paths agree to the last bit. Per grating, in f64:
+        folded      {"a": sum_a / n, "b": sum_b / n, "d": (sum_a - sum_b) / n}: the three mean profiles over one period, as lists (each
+                    one correctly rounded division of two integers; d is the response to the grating alone, the anatomy removed)
+        dc          the mean of d over the period (math.fsum / T)
+        amplitude, harmonic_phase   lists over h = 1, 2, 3 of grating_harmonic(d, h)'s two numbers, None where 2h > T
+        input       the amplitude of the fundamental of wave / 1024: the relative input modulation
+        response    amplitude[0]: the fundamental of d, in gray levels
+        gain        response / input, gray levels per unit of relative input modulation, comparable across contrasts; None for input 0
+        phase       the phase of d's fundamental less the wave's, in (-pi, pi]; None for input 0. The wave ATTENUATES, so an output that
+                    is darker where the wave is largest gives +-pi and a processor that inverts the pattern 0.
+        thd         sqrt(A2^2 + A3^2) / A1 over the harmonics that exist (T >= 4: A2; T >= 6: A3 as well); None where none exists or
+                    A1 = 0
+        texture     the pooled within-phase variance of a, sum_k (sum_aa - sum_a^2 / n) / sum_k n
+        roi_mse     roi_ssd / roi_pixels
+    No threshold is fixed here: these are findings."""
+    out = []
+    for s, g in zip(stats, gratings):
+        n, sa, sb, saa = ([int(v) for v in s[k]] for k in mp.GRATING_SUMS)
+        folded = {"a": [x / m for x, m in zip(sa, n)], "b": [x / m for x, m in zip(sb, n)], "d": [(x - y) / m for x, y, m in zip(sa, sb, n)]}
+        t = len(n)
+        harmonics = [grating_harmonic(folded["d"], h) for h in range(1, GRATING_HARMONICS + 1)]
+        d = {"folded": folded, "dc": math.fsum(folded["d"]) / t, "amplitude": [None if v is None else v[0] for v in harmonics],
+             "harmonic_phase": [None if v is None else v[1] for v in harmonics]}
+        win, wph = grating_harmonic([w / 1024.0 for w in g[6]], 1)
+        response = d["amplitude"][0]
+        turn = None if win == 0.0 else d["harmonic_phase"][0] - wph
+        if turn is not None:
+            turn -= 2.0 * math.pi * math.ceil((turn - math.pi) / (2.0 * math.pi))
+        higher = [v for v in d["amplitude"][1:] if v is not None]
+        d.update(input=win, response=response, gain=None if win == 0.0 else response / win, phase=turn,
+                 thd=math.sqrt(math.fsum(v * v for v in higher)) / response if higher and response != 0.0 else None,
+                 texture=math.fsum(q - x * x / m for q, x, m in zip(saa, sa, n)) / sum(n), roi_mse=s["roi_ssd"] / s["roi_pixels"])
+        out.append(d)
+    return out
+
+
+GRATING_ROW_KEYS = ("gain", "thd", "response")   # what a grating_ row's "gratings" gathers, of the d profile
+GRATING_ROW_STATS = ("median", "min", "max", "count")
+
+
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+
+
+def _grating_spread(summary):
+    out = {"gratings": len(summary)}
+    for k in GRATING_ROW_KEYS:
+        v = [s[k] for s in summary if s[k] is not None]
+        out[k] = {"median": _median(v), "min": min(v), "max": max(v), "count": len(v)} if v else {"median": None, "min": None, "max": None, "count": 0}
+    return out
+
+
+def grating_row(gratings, stats, sq_diff_sum, pixels, tables=False):
+    """A grating_ row's "gratings" value from the row's gratings, their exact tables and the full frame's exact sum of squared
+    differences over `pixels` pixels: {"all": spread, "directions": {"ux,uy": spread}, "periods": {T: spread}, in the order of first
+    appearance and in ascending T, "outside_mse": (sq_diff_sum - sum roi_ssd) / (pixels - sum roi_pixels), the change away from every
+    region}. A spread is {"gratings": the group's size, and for each of GRATING_ROW_KEYS its median, min and max over the gratings that
+    have the number and their count}. With tables=True also "per_grating": the x, y, h, ux, uy, T, wave and grating_summary's dict of
+    every grating, the folded profiles included, in the list's order."""
+    summary = grating_summary(stats, gratings)
+    out = {"all": _grating_spread(summary)}
+    directions = list(dict.fromkeys((g[3], g[4]) for g in gratings))
+    out["directions"] = {"%d,%d" % u: _grating_spread([s for g, s in zip(gratings, summary) if (g[3], g[4]) == u]) for u in directions}
+    out["periods"] = {t: _grating_spread([s for g, s in zip(gratings, summary) if g[5] == t]) for t in sorted(set(g[5] for g in gratings))}
+    rois, inside = sum(s["roi_ssd"] for s in stats), sum(s["roi_pixels"] for s in stats)
+    outside = int(pixels) - inside
+    out["outside_mse"] = (int(sq_diff_sum) - rois) / outside if outside else 0.0
+    if tables:
+        out["per_grating"] = [dict(s, x=g[0], y=g[1], h=g[2], ux=g[3], uy=g[4], T=g[5], wave=list(g[6])) for g, s in zip(gratings, summary)]
+    return out

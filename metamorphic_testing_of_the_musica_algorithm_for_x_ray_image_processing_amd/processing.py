@@ -165,6 +165,12 @@ EDGE_MAX_Q = 16             # MUSICA_EDGE_MAX_Q
 EDGE_MAX_CONTRAST = 512     # MUSICA_EDGE_MAX_CONTRAST
 EDGE_MAX = 256              # MUSICA_EDGE_MAX
 EDGE_BINS_MAX = 2048        # MUSICA_EDGE_BINS_MAX
+GRATING_MIN_HALF = 8        # MUSICA_GRATING_MIN_HALF
+GRATING_MAX_HALF = 128      # MUSICA_GRATING_MAX_HALF
+GRATING_MAX_U = 8           # MUSICA_GRATING_MAX_U
+GRATING_MAX_PERIOD = 64     # MUSICA_GRATING_MAX_PERIOD
+GRATING_MAX_CONTRAST = 512  # MUSICA_GRATING_MAX_CONTRAST
+GRATING_MAX = 256           # MUSICA_GRATING_MAX
 
 
 def zoom_ratio(zoom):
@@ -317,6 +323,71 @@ EDGE_SUMS = ("n", "sum_a", "sum_b", "sum_aa")   # the four rows of an edge's tab
 
 class SimEdgeResult(C.Structure):
     """musica_sim_edge_result: the region's exact sum of squared differences and where the edge's table lies in `tables`."""
+    _fields_ = [("roi_ssd", C.c_uint64), ("roi_pixels", C.c_uint64), ("table_offset", C.c_uint64), ("bins", C.c_uint64)]
+
+
+def grating_admissible(half, ux, uy, period):
+    """Whether (half, ux, uy, T) is a grating's geometry: GRATING_MIN_HALF <= half <= GRATING_MAX_HALF, |ux|, |uy| <= GRATING_MAX_U, not
+    both 0, gcd(|ux|, |uy|) = 1, 2 <= T <= GRATING_MAX_PERIOD, T <= half, 2 |ux| <= T and 2 |uy| <= T."""
+    return (GRATING_MIN_HALF <= half <= GRATING_MAX_HALF and abs(ux) <= GRATING_MAX_U and abs(uy) <= GRATING_MAX_U and math.gcd(abs(ux), abs(uy)) == 1 and
+            2 <= period <= min(GRATING_MAX_PERIOD, half) and 2 * abs(ux) <= period and 2 * abs(uy) <= period)
+
+
+def grating_list(gratings, n, with_wave=True):
+    """The gratings (x, y, h, ux, uy, T, wave) of a grating list for a plane of side n as harness.insert_gratings,
+    harness.grating_statistics and the library take it, a tuple of tuples of ints whose last element is the wave as a tuple of T ints,
+    else ValueError: 1 .. GRATING_MAX gratings of integers, 8 <= h <= GRATING_MAX_HALF, a wave vector (ux, uy) with |ux|, |uy| <=
+    GRATING_MAX_U, not both 0 and coprime, a period 2 <= T <= min(GRATING_MAX_PERIOD, h) with 2 |ux| <= T and 2 |uy| <= T, a wave of
+    exactly T integers |w| <= GRATING_MAX_CONTRAST (with_wave=False: the wave is not looked at, as the measurement does not, and comes
+    back as it was given), every plate |px - x|, |py - y| <= 2h inside [0, n)^2 and the plates pairwise disjoint."""
+    try:
+        out = []
+        for g in gratings:
+            x, y, h, ux, uy, t, wave = g
+            if any(v != int(v) for v in g[:6]):
+                raise TypeError
+            if with_wave:
+                if any(w != int(w) for w in wave):
+                    raise TypeError
+                wave = tuple(int(w) for w in wave)
+            out.append(tuple(int(v) for v in g[:6]) + (wave,))
+    except (TypeError, ValueError):
+        raise ValueError("a grating list holds septuples (x, y, h, ux, uy, T, wave) of six integers and a sequence of integers, got %r" % (gratings,))
+    n = int(n)
+    if not 1 <= len(out) <= GRATING_MAX:
+        raise ValueError("a grating list holds 1 .. %d gratings, got %d" % (GRATING_MAX, len(out)))
+    for i, (x, y, h, ux, uy, t, wave) in enumerate(out):
+        if not GRATING_MIN_HALF <= h <= GRATING_MAX_HALF:
+            raise ValueError("grating %d: half-side %d is not in %d .. %d" % (i, h, GRATING_MIN_HALF, GRATING_MAX_HALF))
+        if not (abs(ux) <= GRATING_MAX_U and abs(uy) <= GRATING_MAX_U and math.gcd(abs(ux), abs(uy)) == 1):
+            raise ValueError("grating %d: wave vector (%d, %d) is not coprime with |ux|, |uy| <= %d" % (i, ux, uy, GRATING_MAX_U))
+        if not grating_admissible(h, ux, uy, t):
+            raise ValueError("grating %d: period %d is not 2 <= T <= min(%d, half) with 2 |ux|, 2 |uy| <= T" % (i, t, GRATING_MAX_PERIOD))
+        if with_wave and (len(wave) != t or any(abs(w) > GRATING_MAX_CONTRAST for w in wave)):
+            raise ValueError("grating %d: the wave is not %d integers |w| <= %d" % (i, t, GRATING_MAX_CONTRAST))
+        if x - 2 * h < 0 or y - 2 * h < 0 or x + 2 * h >= n or y + 2 * h >= n:
+            raise ValueError("grating %d: the plate (%d, %d) +- %d leaves the %d x %d plane" % (i, x, y, 2 * h, n, n))
+    a = np.array([g[:3] for g in out], dtype=np.int64)
+    reach = 2 * (a[:, 2][:, None] + a[:, 2][None, :])
+    meet = (np.abs(a[:, 0][:, None] - a[:, 0][None, :]) <= reach) & (np.abs(a[:, 1][:, None] - a[:, 1][None, :]) <= reach)
+    np.fill_diagonal(meet, False)
+    if meet.any():
+        i, j = np.argwhere(meet)[0]
+        raise ValueError("the plates of gratings %d and %d are not disjoint" % (i, j))
+    return tuple(out)
+
+
+class Grating(C.Structure):
+    """musica_grating: a grating of wave vector (ux, uy) and period T about the integer pixel centre (x, y), measured over
+    |dx|, |dy| <= half and inserted over |dx|, |dy| <= 2 half."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("half", C.c_uint32), ("ux", C.c_int32), ("uy", C.c_int32), ("period", C.c_uint32)]
+
+
+GRATING_SUMS = ("n", "sum_a", "sum_b", "sum_aa")   # the four rows of a grating's table
+
+
+class SimGratingResult(C.Structure):
+    """musica_sim_grating_result: the region's exact sum of squared differences and where the grating's table lies in `tables`."""
     _fields_ = [("roi_ssd", C.c_uint64), ("roi_pixels", C.c_uint64), ("table_offset", C.c_uint64), ("bins", C.c_uint64)]
 
 
@@ -523,6 +594,8 @@ ABI = {
     "musica_alter_edges": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Edge)]),
     "musica_sim_edges": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Edge), C.POINTER(SimEdgeResult), _U32P, C.c_uint64]),
     "musica_edge_bins": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_alter_gratings": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Grating), C.POINTER(C.c_int16), C.c_uint64]),
+    "musica_sim_gratings": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Grating), C.POINTER(SimGratingResult), _U32P, C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -948,6 +1021,23 @@ class MusicaProcessing:
             out.append(d)
         return out
 
+    def sim_gratings(self, gratings, slot, image_index=0):
+        """harness.grating_statistics(output of `image_index`, reference slot `slot`, gratings) on the device: the gratings
+        (x, y, h, ux, uy, T, wave) in the (N - 20)^2 output plane's coordinates (grating_list; the wave is not looked at). Returns one
+        dict per grating: the Python ints h, ux, uy, T, roi_ssd, roi_pixels and the uint32 arrays n, sum_a, sum_b, sum_aa of T entries."""
+        gs = grating_list(gratings, self.imageSize - 2 * OUT_MARGIN, with_wave=False)
+        words = 4 * sum(g[5] for g in gs)
+        arr, res, tables = (Grating * len(gs))(*[Grating(*g[:6]) for g in gs]), (SimGratingResult * len(gs))(), np.zeros(words, dtype=np.uint32)
+        self._ok(self._lib.musica_sim_gratings(self._h, int(image_index), int(slot), len(gs), arr, res, tables.ctypes.data_as(_U32P), words),
+                 "musica_sim_gratings")
+        out = []
+        for g, r in zip(gs, res):
+            t = tables[int(r.table_offset):int(r.table_offset) + 4 * int(r.bins)].reshape(4, int(r.bins))
+            d = {"h": g[2], "ux": g[3], "uy": g[4], "T": int(r.bins), "roi_ssd": int(r.roi_ssd), "roi_pixels": int(r.roi_pixels)}
+            d.update((k, t[i].copy()) for i, k in enumerate(GRATING_SUMS))
+            out.append(d)
+        return out
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -1164,6 +1254,15 @@ class MusicaProcessing:
         es = edge_list(edges, self.imageSize)
         arr = (Edge * len(es))(*[Edge(*e) for e in es])
         self._ok(self._lib.musica_alter_edges(self._h, int(image_index), len(es), arr), "musica_alter_edges")
+
+    def alter_gratings(self, gratings, image_index=0):
+        """harness.insert_gratings(src, gratings): the source with the plates (x, y, h, ux, uy, T, wave) of a grating list
+        (grating_list) inserted."""
+        gs = grating_list(gratings, self.imageSize)
+        arr = (Grating * len(gs))(*[Grating(*g[:6]) for g in gs])
+        waves = np.array([w for g in gs for w in g[6]], dtype=np.int16)
+        self._ok(self._lib.musica_alter_gratings(self._h, int(image_index), len(gs), arr, waves.ctypes.data_as(C.POINTER(C.c_int16)), waves.size),
+                 "musica_alter_gratings")
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRATING_ROW_KEYS, GRATING_ROW_STATS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -37,6 +37,8 @@ DETAIL_CSV_HEADER = ['raw file', 'alteration', 'radius', 'details'] + ['%s %s' %
                     ['outside mse']   # contrast_detail.csv
 EDGE_CSV_HEADER = ['raw file', 'alteration', 'orientation', 'edges'] + ['%s %s' % (k, w) for k in EDGE_ROW_KEYS for w in EDGE_ROW_STATS] + \
                   ['outside mse']   # edge_response.csv
+GRATING_CSV_HEADER = ['raw file', 'alteration', 'period', 'gratings'] + ['%s %s' % (k, w) for k in GRATING_ROW_KEYS for w in GRATING_ROW_STATS] + \
+                     ['outside mse']   # grating_response.csv
 
 
 def covariance_csv_header(radius):
@@ -143,6 +145,15 @@ def _edge_lines(studies):
                 yield [raw_name, r["alteration"], o, g["edges"]] + [g[k][w] for k in EDGE_ROW_KEYS for w in EDGE_ROW_STATS] + [d["outside_mse"]]
 
 
+def _grating_lines(studies):
+    """grating_response.csv's lines: one per grating_ row and period, ascending."""
+    for raw_name, rows in studies:
+        for r in rows:
+            d = r.get("gratings")
+            for t, g in (d["periods"].items() if d else ()):
+                yield [raw_name, r["alteration"], t, g["gratings"]] + [g[k][w] for k in GRATING_ROW_KEYS for w in GRATING_ROW_STATS] + [d["outside_mse"]]
+
+
 def write_studies_csvs(studies, out_dir, mean_cnr=True):
     """The reference's output files for several raw images: `studies` is a list of (raw_name, rows) pairs (run_study's rows), written
     in order into one direct_robustness.csv / reg_based_robustness.csv with the reference's column layout (script.py:223-330), plus
@@ -178,7 +189,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
 
     Studies run with edges (rows[0] has "edges") also get edge_response.csv (EDGE_CSV_HEADER): one line per edge_ row and orientation,
     the number of edges of that orientation, the min, mean, max over them and the count of those that have the number (an empty cell
-    where none has) of step, rise, overshoot, undershoot, mtf50 and mtf_peak, and the row's outside mse."""
+    where none has) of step, rise, overshoot, undershoot, mtf50 and mtf_peak, and the row's outside mse.
+
+    Studies run with gratings (rows[0] has "gratings") also get grating_response.csv (GRATING_CSV_HEADER): one line per grating_ row
+    and period, the number of gratings of that period (one in each direction of the grid that has it), the median, min, max over them
+    and the count of those that have the number (an empty cell where none has) of gain, thd and response, and the row's outside mse."""
     os.makedirs(out_dir, exist_ok=True)
     having = lambda key: [(raw_name, rows) for raw_name, rows in studies if rows and key in rows[0]]   # noqa: E731
     toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
@@ -211,6 +226,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
         _write_csv(out_dir, "contrast_detail.csv", DETAIL_CSV_HEADER, _detail_lines(having("details")))
     if having("edges"):
         _write_csv(out_dir, "edge_response.csv", EDGE_CSV_HEADER, _edge_lines(having("edges")))
+    if having("gratings"):
+        _write_csv(out_dir, "grating_response.csv", GRATING_CSV_HEADER, _grating_lines(having("gratings")))
     ovds = [[raw_name] + _cells(_ovd(rows), SIM_CSV_KEYS) for raw_name, rows in studies if _ovd(rows) is not None]
     if ovds:
         _write_csv(out_dir, "ref_similarities.csv", REF_CSV_HEADER, ovds)
