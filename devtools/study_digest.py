@@ -14,7 +14,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     plane, of image 1's output against slot 0;
   * the grating pair at N = 151: four grating plates of half-side 8 and 9 (a plate across a tile corner and one flush with the plane's
     corner among them; wave vectors along both axes and in two octants, periods 2, 5, 8 and 9), inserted into image 0, and the tables
-    of the same gratings, shifted into the output plane, of image 1's output against slot 0.
+    of the same gratings, shifted into the output plane, of image 1's output against slot 0;
+  * the gain pair at N = 151 (odd: the single-pixel form): a map whose tables run over 0 .. 65535 applied into image 0, and the
+    profiles of image 1's output against slot 0 over the full frame (3 x 3 tiles with a ragged tail), a ragged region from mid-tile
+    with different origins on the two sides, a single column and a single pixel.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -117,5 +120,9 @@ gratings = [(63, 63, 8, 1, 0, 2, (512, -512)), (113, 46, 9, 0, -1, 9, (100, 77, 
 p.alter_gratings(gratings)
 note("musica_alter_gratings", p.input_pixels()[0])
 note("musica_sim_gratings", p.sim_gratings([(g[0] - mp.OUT_MARGIN, g[1] - mp.OUT_MARGIN) + g[2:] for g in gratings], 0, image_index=1))
+ramp = (np.arange(N, dtype=np.int64) * 65535) // (N - 1)
+p.alter_gain(ramp, ramp[::-1] // 9)
+note("musica_alter_gain", p.input_pixels()[0])
+note("musica_sim_profiles", p.sim_profiles([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (1, 0, 64, 0, 64, 0, 1, NW), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)]))
 p.cleanup()
 print(json.dumps(digests))

@@ -894,6 +894,47 @@ int musica_alter_gratings(musica_ctx* ctx, uint32_t image_index, uint32_t count,
 int musica_sim_gratings(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t count, const musica_grating* gratings,
                         musica_sim_grating_result* results, uint32_t* tables, uint64_t table_words);
 
+/* ---- detector gain: a separable gain map, and the row and column profiles of a comparison (new, not in the reference) ----
+ * What varies first from one exposure to the next is the detector's gain: the dose (one constant), the heel effect and vignetting
+ * (smooth multiplicative shading), the gain error of a readout block and the single uncorrected column or row. One separable map
+ * covers them, out(x, y) = v gx[x] gy[y], and one measurement scores them: the exact profiles of a comparison along both axes, where a
+ * line artefact far below the pixel noise shows because a profile integrates along it. harness.apply_gain and
+ * harness.profile_statistics are the contract; everything the device computes is integer and bit-identical to them, from call to call
+ * as well.
+ * A gain map is two tables of N uint16_t for the N x N raw plane, gx per column and gy per row, in units of 1 / MUSICA_GAIN_ONE. Every
+ * value 0 .. 65535 is allowed: 0 is a dead line, 65535 about 16 x.
+ *   g   = gx[x] * gy[y]                          fits uint32: 65535^2 < 2^32
+ *   out = min((v * g + 2^23) >> 24, 65535)       ONE rounding, halves up; the largest intermediate is 65535^3 + 2^23 < 2^48
+ * gx = gy = MUSICA_GAIN_ONE returns v exactly (v * 2^24 + 2^23 >> 24 = v). The clamp at 65535 is the detector's saturation and part of
+ * the contract. There is no musica_sim_gain_reference sibling: what a normalising processor is expected to show is invariance, which the
+ * direct comparison scores. */
+#define MUSICA_GAIN_ONE 4096
+/* apply_gain(source plane, gx, gy) into image `image_index` of the input buffer: gx and gy hold N host values each. The kernel is
+ * enqueued on the ctx stream (the tables are copied to the device first, which waits for what the stream holds), with musica_alter's
+ * guarantees: it changes no other image of the input buffer, no result of the last step and no reference slot. One launch, 2 bytes read
+ * and 2 written per pixel (kernels_gain.hip). An entry point of its own and not a musica_alteration_kind: the kinds are closed at
+ * MUSICA_ALTER_KIND_COUNT. Refused before any device work: a NULL context or table, no source, image_index >= batch. */
+int musica_alter_gain(musica_ctx* ctx, uint32_t image_index, const uint16_t* gx, const uint16_t* gy);
+/* The profiles of `count` (1 .. MUSICA_PROFILE_MAX_QUERIES) comparisons in one launch. A query is musica_sim_compare's: side a the 8-bit
+ * output of batch image `image_index` (quantised while read, exactly as musica_sim_compare reads it), side b reference slot `slot`, the
+ * region (ax, ay) / (bx, by), w x h with w, h >= 1. Query i gets a column table [w][4] followed by a row table [h][4] in the flat
+ * `tables`, from results[i].table_offset (in words: the sum over j < i of 4 (w_j + h_j)) on. A line's four words are the exact
+ *   sum_a, sum_b, sum_dd = sum of (a - b)^2, sum_aa
+ * over the line's pixels inside the region: h pixels for a column, w for a row. A line has at most 16364 pixels (N <= 16384) and
+ * 16364 * 255^2 < 2^32, so everything fits uint32. results[i].ssd is the sum of either table's sum_dd and equals musica_sim_compare's
+ * sq_diff_sum over the same region. table_words, the words `tables` has room for, must be at least the total. Synchronous; integers
+ * only, byte-identical from call to call. Refused before any device work: what musica_sim_compare refuses, except that the smallest
+ * side is 1 and the largest count MUSICA_PROFILE_MAX_QUERIES, a NULL `tables`, and table_words too small. */
+#define MUSICA_PROFILE_MAX_QUERIES 16
+typedef struct musica_sim_profile_result {
+    uint64_t table_offset;          /* where the query's column table starts in `tables`, in words; its row table follows at + 4 cols */
+    uint64_t cols, rows;            /* w, h */
+    uint64_t ssd;                   /* sum over the region of (a - b)^2 */
+    uint64_t pixels;                /* w * h */
+} musica_sim_profile_result;
+int musica_sim_profiles(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_profile_result* results,
+                        uint32_t* tables, uint64_t table_words);
+
 /* ---- device-resident output and stream ordering (new, not in the reference) ---- */
 
 /* What musica_export_out writes per image. */

@@ -384,6 +384,21 @@ void launch_alter_gratings(hipStream_t st, const uint16_t* src, uint16_t* out, i
 // grating's 4 x T u32 from 4 * PackedGrating::first on, all written
 void launch_sim_gratings(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedGrating* d_gratings, int count,
                          unsigned long long* results, uint32_t* tables);
+// kernels_gain.hip: the detector-gain relation. harness.apply_gain(src, gx, gy) of a dense n x n plane into another (the planes must not
+// overlap); any n >= 1. d_gx: the n column gains as they came (u16, a device allocation of its own), d_gy: the n row gains widened to
+// u32 (the kernel fetches them on the scalar side)
+constexpr int kGainOne = 4096;            // MUSICA_GAIN_ONE
+constexpr int kProfileMaxQueries = 16;    // MUSICA_PROFILE_MAX_QUERIES
+void launch_alter_gain(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const uint16_t* d_gx, const uint32_t* d_gy);
+// One comparison of musica_sim_profiles. tiles_x / tiles_y: ceil(w / 64), ceil(h / 64); table: where its tables start in the launch's
+// flat tables, in words: [w][4] then [h][4].
+struct ProfileQueryDev : SimRegion {
+    int tiles_x, tiles_y;
+    unsigned long long table;
+};
+// harness.profile_statistics over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y). tables: every query's words,
+// zeroed by the caller: the tiles add their partials with u32 atomics
+void launch_sim_profiles(hipStream_t st, const ProfileQueryDev* d_qs, int count, int max_tiles, uint32_t* tables);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -148,6 +148,12 @@ struct StudyState {
     int16_t* d_grating_waves = nullptr;            // [MUSICA_GRATING_MAX][MUSICA_GRATING_MAX_PERIOD], allocated by the first musica_alter_gratings
     unsigned long long* d_grating_out = nullptr;   // [MUSICA_GRATING_MAX][kGratingWords], allocated by the first musica_sim_gratings
     uint32_t* d_grating_tables = nullptr;          // [MUSICA_GRATING_MAX][4][MUSICA_GRATING_MAX_PERIOD] (256 KiB), allocated by the first musica_sim_gratings
+    // musica_alter_gain: the device copy of the call's tables; musica_sim_profiles: the queries and the flat tables
+    uint16_t* d_gain_x = nullptr;                  // [N], allocated by the first musica_alter_gain
+    uint32_t* d_gain_y = nullptr;                  // [N]: gy widened to u32, likewise
+    ProfileQueryDev* d_profile_q = nullptr;        // [MUSICA_PROFILE_MAX_QUERIES]
+    uint32_t* d_profile_tables = nullptr;          // the tables of one call: profile_tables_cap u32, regrown when a call needs more
+    size_t profile_tables_cap = 0;
 };
 
 struct musica_ctx : DeviceBuffers {

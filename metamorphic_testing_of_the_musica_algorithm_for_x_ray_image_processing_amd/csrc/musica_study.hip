@@ -1,7 +1,7 @@
-// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the seven query calls
-// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip), the ensemble accumulators
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the eight query calls
+// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip), the ensemble accumulators
 // (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
+// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
@@ -407,10 +407,12 @@ static void sim_finish(const uint32_t* counts /* a 256 | b 256 */, const SimPart
 }
 
 // What musica_sim_compare and musica_sim_joint refuse, in the same words (`what`: the entry point), before any device work.
-static int sim_check_queries(musica_ctx* c, const char* what, uint32_t count, const musica_sim_query* qs, const void* out) {
+// musica_sim_profiles has no window: its smallest side is 1 (min_side) and its largest count max_count.
+static int sim_check_queries(musica_ctx* c, const char* what, uint32_t count, const musica_sim_query* qs, const void* out, uint32_t min_side = 7,
+                             uint32_t max_count = MUSICA_SIM_MAX_QUERIES) {
     if (!c) return fail("%s: ctx is NULL", what);
     if (!qs || !out) return fail("%s: queries or results is NULL", what);
-    if (count == 0 || count > MUSICA_SIM_MAX_QUERIES) return fail("%s: count %u out of range [1, %d]", what, count, MUSICA_SIM_MAX_QUERIES);
+    if (count == 0 || count > max_count) return fail("%s: count %u out of range [1, %u]", what, count, max_count);
     if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("%s: image too small for the %d-pixel margin", what, MUSICA_OUT_MARGIN);
     const uint64_t nw = sim_side(c);
     for (uint32_t i = 0; i < count; i++) {
@@ -418,7 +420,8 @@ static int sim_check_queries(musica_ctx* c, const char* what, uint32_t count, co
         if (q.slot >= MUSICA_SIM_SLOTS) return fail("%s: query %u: slot %u >= %d", what, i, q.slot, MUSICA_SIM_SLOTS);
         if (!c->study.written[q.slot]) return fail("%s: query %u: slot %u was never written", what, i, q.slot);
         if ((int)q.image_index >= c->B) return fail("%s: query %u: image_index %u >= batch %d", what, i, q.image_index, c->B);
-        if (q.w < 7 || q.h < 7) return fail("%s: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", what, i, q.w, q.h);
+        if (min_side == 7 && (q.w < 7 || q.h < 7)) return fail("%s: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", what, i, q.w, q.h);
+        if (q.w < min_side || q.h < min_side) return fail("%s: query %u: region %u x %u has a side below %u", what, i, q.w, q.h, min_side);
         if ((uint64_t)q.ax + q.w > nw || (uint64_t)q.ay + q.h > nw || (uint64_t)q.bx + q.w > nw || (uint64_t)q.by + q.h > nw)
             return fail("%s: query %u: region (%u, %u) / (%u, %u) + %u x %u leaves the %llu x %llu planes", what, i, q.ax, q.ay, q.bx, q.by,
                         q.w, q.h, (unsigned long long)nw, (unsigned long long)nw);
@@ -796,6 +799,49 @@ int musica_sim_gratings(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t cou
     HIP_OK(hipStreamSynchronize(c->stream));
     return 1;
     ABI_CATCH("musica_sim_gratings")
+}
+
+// ---- the profiles of a comparison (musica_sim_profiles, include/musica.h; kernels_gain.hip) ---------------------------------------------
+static_assert(kProfileMaxQueries == MUSICA_PROFILE_MAX_QUERIES && kGainOne == MUSICA_GAIN_ONE, "kernels_gain.hip's limits are include/musica.h's");
+
+int musica_sim_profiles(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_profile_result* out, uint32_t* tables, uint64_t table_words) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_profiles", count, qs, out, 1, MUSICA_PROFILE_MAX_QUERIES)) return 0;
+    if (!tables) return fail("musica_sim_profiles: tables is NULL");
+    std::vector<ProfileQueryDev> hq(count);
+    size_t words = 0;
+    int max_tiles = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        sim_region(c, qs[i], hq[i]);
+        hq[i].tiles_x = tiles_along(qs[i].w);
+        hq[i].tiles_y = tiles_along(qs[i].h);
+        hq[i].table = words;
+        max_tiles = std::max(max_tiles, hq[i].tiles_x * hq[i].tiles_y);
+        words += 4 * ((size_t)qs[i].w + qs[i].h);
+    }
+    if (table_words < words) return fail("musica_sim_profiles: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!ensure(c, &st.d_profile_q, MUSICA_PROFILE_MAX_QUERIES)) return fail("musica_sim_profiles: device allocation failed");
+    if (!grow(c, "musica_sim_profiles", &st.d_profile_tables, &st.profile_tables_cap, words, "table words")) return 0;
+    HIP_OK(hipMemcpyAsync(st.d_profile_q, hq.data(), count * sizeof(ProfileQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_profile_tables, 0, words * sizeof(uint32_t), c->stream));   // the tiles add into them
+    launch_sim_profiles(c->stream, st.d_profile_q, (int)count, max_tiles, st.d_profile_tables);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(tables, st.d_profile_tables, words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        const uint32_t* t = tables + hq[i].table;
+        uint64_t ssd = 0;
+        for (uint32_t x = 0; x < qs[i].w; x++) ssd += t[4 * (size_t)x + 2];   // the column table's sum_dd: every pixel once
+        out[i].table_offset = hq[i].table;
+        out[i].cols = qs[i].w;
+        out[i].rows = qs[i].h;
+        out[i].ssd = ssd;
+        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
+    }
+    return 1;
+    ABI_CATCH("musica_sim_profiles")
 }
 
 // ---- ensemble statistics (musica_sim_ensemble_*, include/musica.h; kernels_ensemble.hip) ------------------------------------------------
@@ -1226,6 +1272,25 @@ int musica_alter_gratings(musica_ctx* c, uint32_t idx, uint32_t count, const mus
     HIP_OK(hipGetLastError());
     return 1;
     ABI_CATCH("musica_alter_gratings")
+}
+
+int musica_alter_gain(musica_ctx* c, uint32_t idx, const uint16_t* gx, const uint16_t* gy) {
+    ABI_TRY
+    if (!c) return fail("musica_alter_gain: ctx is NULL");
+    if (!gx || !gy) return fail("musica_alter_gain: gx or gy is NULL");
+    if (!c->study.d_alter_src) return fail("musica_alter_gain: no source plane (musica_alter_set_source)");
+    CHECK_IMG(c, idx);
+    CHECK_CTX(c);
+    if (!(ensure(c, &c->study.d_gain_x, (size_t)c->N) && ensure(c, &c->study.d_gain_y, (size_t)c->N))) return fail("musica_alter_gain: device allocation of the tables failed");
+    const std::vector<uint32_t> wide(gy, gy + c->N);   // the kernel fetches a row's gain on the scalar side: u32
+    HIP_OK(hipMemcpyAsync(c->study.d_gain_x, gx, (size_t)c->N * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->study.d_gain_y, wide.data(), (size_t)c->N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // the caller's tables and `wide` have been read
+    if (!alter_keep_input(c, "musica_alter_gain")) return 0;
+    launch_alter_gain(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, c->study.d_gain_x, c->study.d_gain_y);   // kernels_gain.hip
+    HIP_OK(hipGetLastError());
+    return 1;
+    ABI_CATCH("musica_alter_gain")
 }
 
 int musica_alter_draws(musica_ctx* c, const musica_alteration* s, int32_t* dst) {

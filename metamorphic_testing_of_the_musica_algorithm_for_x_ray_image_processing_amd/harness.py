@@ -201,6 +201,106 @@ def grating_contrast(gratings):
     return max(abs(w) for w in gratings[0][6])
 
 
+# not in the reference: the detector-gain rows (apply_gain), rows named by the spec of a study run with `gains`: a separable gain map
+# out = v gx[x] gy[y] in units of 1 / 4096 (processing.GAIN_ONE), scored like every row and by the exact row and column profiles of the
+# result against the unaltered result (profile_statistics). A spec is (name, gx, gy); GAINS(n) gives the 25 of the image size: the
+# exposures GAIN_EXPOSURES, and for each strength c of GAIN_CONTRASTS (c / 1024 = 0.8 % .. 12.5 %, the cd_, edge_ and grating_ rows' five)
+# a heel effect, a vignetting, gain bands and defective lines. Every builder works on Python ints.
+GAIN_EXPOSURES = ((1, 4), (1, 2), (3, 4), (3, 2), (2, 1))
+GAIN_CONTRASTS = (8, 16, 32, 64, 128)
+
+
+def _gain_side(n):
+    n = int(n)
+    if n < 2:
+        raise ValueError("a gain map needs a side of at least 2, got %d" % n)
+    return n
+
+
+def gain_exposure(n, num, den):
+    """The dose changed by num / den: gx[i] = 4096, gy[i] = (4096 num + den // 2) // den (the ratio rounded to 1 / 4096, halves up), the
+    same for every i: every pixel is multiplied by one constant."""
+    n, num, den = _gain_side(n), int(num), int(den)
+    g = (mp.GAIN_ONE * num + den // 2) // den
+    if num < 0 or den < 1 or g > 65535:
+        raise ValueError("exposure %d / %d is not a gain of 0 .. 65535 / 4096" % (num, den))
+    return [mp.GAIN_ONE] * n, [g] * n
+
+
+def gain_heel(n, c):
+    """The heel effect, a linear ramp down the rows of c / 1024 peak to peak: with m = n - 1 and t = 2 i - m (-m .. m),
+    gy[i] = 4096 + (4 c t + m) // (2 m) (2 c t / m rounded, halves up: -2c at the top row, +2c at the bottom), gx[i] = 4096."""
+    n, c = _gain_side(n), int(c)
+    m = n - 1
+    return [mp.GAIN_ONE] * n, [mp.GAIN_ONE + (4 * c * (2 * i - m) + m) // (2 * m) for i in range(n)]
+
+
+def gain_vignette(n, c):
+    """Vignetting, a separable parabola that is c / 1024 down at the corners: with m = n - 1 and t = 2 i - m,
+    gx[i] = gy[i] = 4096 - (2 c t^2 + m^2 // 2) // m^2 (2 c (t / m)^2 rounded, halves up: 0 at the centre, 2c down at either end of an
+    axis, so 4c / 4096 = c / 1024 down where both ends meet)."""
+    n, c = _gain_side(n), int(c)
+    m = n - 1
+    g = [mp.GAIN_ONE - (2 * c * (2 * i - m) ** 2 + m * m // 2) // (m * m) for i in range(n)]
+    return g, list(g)
+
+
+def gain_bands(n, c):
+    """Gain bands, readout blocks whose calibration is off: blocks of B = max(16, n // 16) columns alternate between 4096 + 2c (the
+    first) and 4096 - 2c, gx[i] = 4096 + 2c if (i // B) % 2 == 0 else 4096 - 2c, gy[i] = 4096: every block border is a step of
+    4c / 4096 = c / 1024."""
+    n, c = _gain_side(n), int(c)
+    b = max(16, n // 16)
+    return [mp.GAIN_ONE + 2 * c if (i // b) % 2 == 0 else mp.GAIN_ONE - 2 * c for i in range(n)], [mp.GAIN_ONE] * n
+
+
+def gain_line_positions(n):
+    """Where gain_lines puts its nine lines along an axis: PROCESSING_MARGIN + (2 j + 1) (n - 20) // 18 for j = 0 .. 8, the centres of
+    nine equal parts of the output plane's footprint; inside it for n >= 84."""
+    n = _gain_side(n)
+    return [PROCESSING_MARGIN + (2 * j + 1) * (n - 2 * PROCESSING_MARGIN) // 18 for j in range(9)]
+
+
+def gain_lines(n, c):
+    """Defective lines: the nine columns and the nine rows at gain_line_positions(n) have the gain 4096 - 4c (c / 1024 down), every
+    other line 4096. A crossing is down by both."""
+    n, c = _gain_side(n), int(c)
+    at = set(gain_line_positions(n))
+    if not all(0 <= p < n for p in at):
+        raise ValueError("a side of %d pixels does not hold the nine lines" % n)
+    g = [mp.GAIN_ONE - 4 * c if i in at else mp.GAIN_ONE for i in range(n)]
+    return g, list(g)
+
+
+def GAINS(n):
+    """The 25 gain specs (name, gx, gy) of a side-n image: exposure_<num>_<den> for GAIN_EXPOSURES, then heel_<c>, vignette_<c>,
+    band_<c> and line_<c>, each for c in GAIN_CONTRASTS."""
+    out = [("exposure_%d_%d" % e,) + gain_exposure(n, *e) for e in GAIN_EXPOSURES]
+    for name, build in (("heel", gain_heel), ("vignette", gain_vignette), ("band", gain_bands), ("line", gain_lines)):
+        out += [("%s_%d" % (name, c),) + build(n, c) for c in GAIN_CONTRASTS]
+    return tuple(out)
+
+
+def output_gain(spec):
+    """A raw plane's gain spec (name, gx, gy) in the coordinates of the output plane (the frame cropped by PROCESSING_MARGIN on every
+    side): (gx, gy) sliced."""
+    _, gx, gy = spec
+    return tuple(gx[PROCESSING_MARGIN:len(gx) - PROCESSING_MARGIN]), tuple(gy[PROCESSING_MARGIN:len(gy) - PROCESSING_MARGIN])
+
+
+def apply_gain(image, gx, gy):
+    """The square 2-D uint16 plane under the separable gain map (processing.gain_tables for its side, else ValueError before any work):
+        g   = gx[x] * gy[y]                              (fits uint32)
+        out = min((v * g + 2^23) >> 24, 65535)           ONE rounding, halves up, in uint64: the largest intermediate is 65535^3 + 2^23 < 2^48
+    gx = gy = 4096 returns v exactly; the clamp is the detector's saturation."""
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype != np.uint16 or not image.size:
+        raise ValueError("apply_gain needs a non-empty square 2-D uint16 plane, got %r %s" % (image.shape, image.dtype))
+    gx, gy = mp.gain_tables(gx, gy, image.shape[0])
+    g = gx.astype(np.uint64)[None, :] * gy.astype(np.uint64)[:, None]
+    return np.minimum((image.astype(np.uint64) * g + np.uint64(1 << 23)) >> np.uint64(24), np.uint64(65535)).astype(np.uint16)
+
+
 def scaled(values, image_size):
     """The reference's pixel-valued grids scaled from 3072 to `image_size`."""
     return [max(1, int(round(v * image_size / REF_IMAGE_SIZE))) for v in values]
@@ -628,7 +728,7 @@ VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
-                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False):
+                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -676,18 +776,27 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         gratings = [mp.grating_list(g, n) for g in gratings]
         for g in gratings:
             mp.grating_list(output_gratings(g), n - 2 * PROCESSING_MARGIN)
+    if gains is not None:     # every spec's tables are valid for the raw plane; sliced by the margin they are for the output plane
+        try:
+            gains = [(str(name),) + tuple(tuple(int(v) for v in g) for g in mp.gain_tables(gx, gy, n)) for name, gx, gy in gains]
+        except TypeError:
+            raise ValueError("a gain spec is (name, gx, gy), got %r" % (gains,))
+        if n <= 2 * PROCESSING_MARGIN:
+            raise ValueError("a side of %d pixels leaves no output plane to take profiles of" % n)
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
            (("ensemble",) if ensemble else ()) + (("details",) if details is not None else ()) + \
-           (("edges",) if edges is not None else ()) + (("gratings",) if gratings is not None else ())
+           (("edges",) if edges is not None else ()) + (("gratings",) if gratings is not None else ()) + \
+           (("profiles",) if gains is not None else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, details=details or [], detail_tables=bool(detail_tables),
-        edges=edges or [], edge_tables=bool(edge_tables), gratings=gratings or [], grating_tables=bool(grating_tables), keys=keys, device_alterations=device_alterations)
+        edges=edges or [], edge_tables=bool(edge_tables), gratings=gratings or [], grating_tables=bool(grating_tables),
+        gains=gains or [], gain_tables=bool(gain_tables), keys=keys, device_alterations=device_alterations)
 
 
 # One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
@@ -695,14 +804,15 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
 # context's method, the host's function, their parameter), which both move a reference plane as the alteration moves the input: the
 # registered comparison is then against the moved plane; noise = (the row's ordinal, alter(context, stream, image_index)) for the rows
 # that draw, what their ensembles repeat; details = the raw plane's detail list of a cd_ row, measured where the details lie; edges = the
-# raw plane's edge list of an edge_ row, gratings = its grating list of a grating_ row, likewise.
-Alteration = collections.namedtuple("Alteration", "name host dev region move noise details edges gratings", defaults=(None, None, None, None, None, None))
+# raw plane's edge list of an edge_ row, gratings = its grating list of a grating_ row, likewise; gain = the (name, gx, gy) of a gain
+# row, whose profiles are taken over the full output frame.
+Alteration = collections.namedtuple("Alteration", "name host dev region move noise details edges gratings gain", defaults=(None, None, None, None, None, None, None))
 
 
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4, blur, zoom, scatter, cd, edge and grating rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur, zoom, scatter, cd, edge, grating and gain rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -743,6 +853,8 @@ def study_alterations(raw, rng, p, seed, shape, opt):
         yield Alteration("edge_%d" % g[0][6], lambda: insert_edges(raw, g), lambda: p.alter_edges(g), edges=g)
     for g in opt.gratings:
         yield Alteration("grating_%d" % grating_contrast(g), lambda: insert_gratings(raw, g), lambda: p.alter_gratings(g), gratings=g)
+    for g in opt.gains:
+        yield Alteration(g[0], lambda: apply_gain(raw, g[1], g[2]), lambda: p.alter_gain(g[1], g[2]), gain=g)
 
 
 class Scorer:
@@ -803,6 +915,11 @@ class DeviceScorer(Scorer):
         """One musica_sim_gratings call against the unaltered result; the full frame's integers are the row's direct comparison's."""
         direct = self.compared[0]
         return grating_row(gratings, self.proc.sim_gratings(gratings, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.grating_tables)
+
+    def profiles(self, gx_out, gy_out):
+        """One musica_sim_profiles call over the full output frame against the unaltered result."""
+        h, w = self.unalt.shape
+        return profile_row(self.proc.sim_profiles([(0, SLOT_UNALTERED, 0, 0, 0, 0, w, h)])[0], gx_out, gy_out, self.opt.gain_tables)
 
     def tone(self, comparisons):
         """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
@@ -874,6 +991,10 @@ class HostScorer(Scorer):
         return grating_row(gratings, grating_statistics(self.out, self.planes[SLOT_UNALTERED], gratings), int(((a - b) ** 2).sum()), a.size,
                            self.opt.grating_tables)
 
+    def profiles(self, gx_out, gy_out):
+        h, w = self.out.shape
+        return profile_row(profile_statistics(self.out, self.planes[SLOT_UNALTERED], [(0, 0, 0, 0, w, h)])[0], gx_out, gy_out, self.opt.gain_tables)
+
     def tone(self, comparisons):
         return [tone_similarities(*self.sides(*c)) for c in comparisons]
 
@@ -938,7 +1059,8 @@ def ensemble_of(eproc, noise, registered, full, opt):
 
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
-              blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False):
+              blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
+              gains=None, gain_tables=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1068,11 +1190,25 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     integers with one function, so "gratings" is equal to the last bit on every path. grating_tables: the dict also carries
     "per_grating", the folded profiles of every grating included. The rows draw nothing from `rng` and take no ordinal. Nothing is
     asserted about the gains: these are findings. A linear processor would give the same gain at every contrast and no harmonics;
-    how MUSICA's gain falls with the amplitude and rises with the frequency, and what it adds at 2f and 3f, is the finding."""
+    how MUSICA's gain falls with the amplitude and rises with the frequency, and what it adds at 2f and 3f, is the finding.
+
+    gains: gain specs (name, gx, gy), the tables of a separable gain map for the raw plane's columns and rows in 1 / 4096
+    (processing.gain_tables; GAINS(n) for the five exposures and the heel, vignette, band and line maps at the five strengths), else
+    ValueError before any work. None adds nothing. Otherwise rows named by the specs follow the grating_ rows: the raw image under the
+    map (apply_gain; on the device: alter_gain), "direct" scored as for every row, "registered" None (a normalising processor is
+    expected to be invariant, which "direct" scores), and every row of the study gains "profiles": None except in the gain rows, where
+    it is profile_row's dict of the exact column and row profiles of the result against the unaltered result over the full output
+    frame (profile_statistics; on the device one musica_sim_profiles call behind the row's musica_sim_compare) with the map sliced into
+    the output plane (output_gain): per axis the mean shift, the transfer (the slope of the lines' mean change on their relative
+    gain), its correlation and residual, the peak, the line noise, the peak's visibility and the spread (profile_summary). Host and
+    device summarise exact integers with one function, so "profiles" is equal to the last bit on every path. gain_tables: the dict
+    also carries "tables" and "gains", the raw integers. The rows draw nothing from `rng` and take no ordinal. Nothing is asserted:
+    these are findings. A processor that normalises would show no transfer at all; what survives of a line far below the pixel noise,
+    and how far it spreads, is the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
-                        edges, edge_tables, gratings, grating_tables)
+                        edges, edge_tables, gratings, grating_tables, gains, gain_tables)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -1111,6 +1247,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             out["edges"] = scorer.edges(output_edges(alteration.edges))
         if alteration is not None and alteration.gratings:
             out["gratings"] = scorer.gratings(output_gratings(alteration.gratings))
+        if alteration is not None and alteration.gain:
+            out["profiles"] = scorer.profiles(*output_gain(alteration.gain))
         out["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         if eproc is not None:
             out["ensemble"] = ensemble_of(eproc, alteration.noise, registered[1] if registered else None, full, opt)
@@ -1274,6 +1412,12 @@ def main(argv=None):
                          "harmonic distortion and response per period), written to grating_response.csv; on the GPU with --device-metrics / "
                          "--device-alterations (musica_sim_gratings, musica_alter_gratings)")
     ap.add_argument("--grating-tables", action="store_true", help="with --gratings: keep every grating's numbers and folded profiles in the rows (\"per_grating\")")
+    ap.add_argument("--gains", action="store_true",
+                    help="add the detector-gain rows (GAINS): the exposures 1/4 .. 2, and a heel effect, a vignetting, gain bands and defective "
+                         "lines at the strengths c / 1024 = 0.8 %% .. 12.5 %%, each a separable gain map; the exact row and column profiles "
+                         "of the result against the unaltered one (transfer, peak, line noise, visibility, spread per axis), written to "
+                         "gain_response.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_profiles, musica_alter_gain)")
+    ap.add_argument("--gain-tables", action="store_true", help="with --gains: keep the profiles' integers and the gains in the rows (\"tables\", \"gains\")")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -1307,6 +1451,8 @@ def main(argv=None):
         ap.error("--edge-tables keeps what --edges measures: give --edges")
     if args.grating_tables and not args.gratings:
         ap.error("--grating-tables keeps what --gratings measures: give --gratings")
+    if args.gain_tables and not args.gains:
+        ap.error("--gain-tables keeps what --gains measures: give --gains")
     if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
         ap.error("--covariance takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
     if args.covariance and not args.ensemble:
@@ -1368,6 +1514,8 @@ def main(argv=None):
         shift_args.update(edges=EDGES(args.size), edge_tables=args.edge_tables)
     if args.gratings:
         shift_args.update(gratings=GRATINGS(args.size), grating_tables=args.grating_tables)
+    if args.gains:
+        shift_args.update(gains=GAINS(args.size), gain_tables=args.gain_tables)
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

@@ -1074,3 +1074,96 @@ def grating_row(gratings, stats, sq_diff_sum, pixels, tables=False):
     if tables:
         out["per_grating"] = [dict(s, x=g[0], y=g[1], h=g[2], ux=g[3], uy=g[4], T=g[5], wave=list(g[6])) for g, s in zip(gratings, summary)]
     return out
+
+
+# ---- detector gain: the exact row and column profiles of a comparison (not in the reference's script) ---------------------------------
+# Every other metric of the study reduces over areas: a defective column of 0.2 gray levels changes their numbers in the fifth digit.
+# A profile integrates along the line, as the eye does, and shows it at once. profile_statistics is the contract of
+# musica_sim_profiles (include/musica.h), which is bit-identical to it; profile_summary is what the study reports of the integers, one
+# function for every path.
+
+def profile_statistics(a, b, regions):
+    """The exact column and row profiles of every region (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes: what
+    musica_sim_profiles returns. One dict per region: "cols", a (w, 4) uint32 array, and "rows", (h, 4): per line the sums over the
+    line's pixels inside the region of a, of b, of (a - b)^2 and of a^2 (processing.PROFILE_SUMS), h pixels for a column and w for a
+    row; "ssd", the sum over the region of (a - b)^2, which both tables' third columns add up to; "pixels" = w h. A line of up to
+    16364 pixels sums to less than 2^32."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("profile_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    out = []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        pa, pb = a[ay:ay + h, ax:ax + w].astype(np.int64), b[by:by + h, bx:bx + w].astype(np.int64)
+        sums = (pa, pb, (pa - pb) ** 2, pa * pa)
+        out.append({"cols": np.stack([s.sum(axis=0) for s in sums], axis=1).astype(np.uint32),
+                    "rows": np.stack([s.sum(axis=1) for s in sums], axis=1).astype(np.uint32), "ssd": int(sums[2].sum()), "pixels": w * h})
+    return out
+
+
+PROFILE_AXES = ("cols", "rows")     # a profile table's two axes: the lines are columns (gains gx), then rows (gains gy)
+PROFILE_KEYS = ("mean_shift", "transfer", "corr", "residual_rms", "peak", "line_noise", "visibility", "spread")
+
+
+def _profile_axis(table, n, gains):
+    """profile_summary's dict of one axis: table (lines, 4) exact integers, n pixels per line, `gains` the lines' gains in 1 / GAIN_ONE."""
+    lines = len(table)
+    if len(gains) != lines:
+        raise ValueError("a profile of %d lines needs %d gains, got %d" % (lines, lines, len(gains)))
+    diff = [int(r[0]) - int(r[1]) for r in table]
+    D = [d / n for d in diff]
+    L = [int(g) / mp.GAIN_ONE - 1.0 for g in gains]
+    mean_d, mean_l = math.fsum(D) / lines, math.fsum(L) / lines
+    dc, lc = [d - mean_d for d in D], [v - mean_l for v in L]
+    sdd, sll, sld = math.fsum(d * d for d in dc), math.fsum(v * v for v in lc), math.fsum(d * v for d, v in zip(dc, lc))
+    flat = min(gains) == max(gains)             # decided on the integers: L is constant
+    transfer = None if flat else sld / sll
+    fit = [0.0 if flat else transfer * v for v in lc]
+    peak = max(abs(d) for d in dc)
+    # the pooled within-line sample variance of a - b, from exact integers: sum_i (n sum_dd_i - diff_i^2) / (n lines (n - 1))
+    within = sum(n * int(r[2]) - d * d for r, d in zip(table, diff))
+    noise = math.sqrt(within / (n * lines * (n - 1)) / n) if n > 1 else None
+    ranked = sorted(int(g) for g in gains)
+    median = ranked[lines // 2]
+    return {"lines": lines, "mean_shift": mean_d, "transfer": transfer, "corr": sld / math.sqrt(sll * sdd) if not flat and sdd > 0.0 else None,
+            "residual_rms": math.sqrt(math.fsum((d - f) ** 2 for d, f in zip(dc, fit)) / lines), "peak": peak, "line_noise": noise,
+            "visibility": peak / noise if noise else None,
+            "spread": math.fsum(d * d for d, g in zip(dc, gains) if int(g) == median) / sdd if sdd > 0.0 else None}
+
+
+def profile_summary(tables, gx_out, gy_out):
+    """What the study reports of a gain row, from profile_statistics' (or musica_sim_profiles') exact integers of ONE region and the gain
+    tables of its columns and rows (in 1 / GAIN_ONE, w and h entries): one function for every study path and all five families, so the
+    paths agree to the last bit. {"cols": d, "rows": d}; per axis, in f64, with n the pixels of a line (h for a column, w for a row),
+        D[i] = (sum_a - sum_b) / n      the line's mean change, in gray levels (one correctly rounded division of two integers)
+        L[i] = g[i] / GAIN_ONE - 1      the line's relative gain
+    and Dc, Lc the two centred on their means (math.fsum):
+        lines         how many
+        mean_shift    the mean of D: what the whole frame moved by
+        transfer      sum Lc Dc / sum Lc^2, the least-squares slope of D on L: gray levels per unit of relative gain; None where L is
+                      constant (decided on the integer gains)
+        corr          sum Lc Dc / sqrt(sum Lc^2 sum Dc^2); None where L or D is constant
+        residual_rms  sqrt(mean (Dc - transfer Lc)^2): what the fit leaves (of Dc itself where transfer is None)
+        peak          max |Dc|
+        line_noise    the standard error of a line's mean: sqrt(s^2 / n) with the pooled within-line sample variance of a - b,
+                      s^2 = sum_i (n sum_dd[i] - (sum_a[i] - sum_b[i])^2) / (n lines (n - 1)), the numerator an exact integer; None for n = 1
+        visibility    peak / line_noise: how far the largest line stands out of what a line's mean scatters by; None where line_noise
+                      is None or 0
+        spread        the share of sum Dc^2 on the lines whose gain equals the axis's median gain (the upper median, an entry of the
+                      table): how far a line or a step leaks into unaltered neighbours; 1 where every line has the median gain; None
+                      where D is constant
+    No threshold is fixed here: these are findings."""
+    cols, rows = np.asarray(tables["cols"]), np.asarray(tables["rows"])
+    return {"cols": _profile_axis(cols, len(rows), list(gx_out)), "rows": _profile_axis(rows, len(cols), list(gy_out))}
+
+
+def profile_row(tables, gx_out, gy_out, keep=False):
+    """A gain row's "profiles" value: profile_summary's dict, with keep=True also "tables": {"cols", "rows"} as lists of the lines'
+    four integers and "gains": {"cols", "rows"} as lists."""
+    out = profile_summary(tables, gx_out, gy_out)
+    if keep:
+        out["tables"] = {k: [[int(v) for v in r] for r in tables[k]] for k in PROFILE_AXES}
+        out["gains"] = {"cols": [int(g) for g in gx_out], "rows": [int(g) for g in gy_out]}
+    return out

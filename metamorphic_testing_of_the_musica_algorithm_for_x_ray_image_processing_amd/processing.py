@@ -171,6 +171,8 @@ GRATING_MAX_U = 8           # MUSICA_GRATING_MAX_U
 GRATING_MAX_PERIOD = 64     # MUSICA_GRATING_MAX_PERIOD
 GRATING_MAX_CONTRAST = 512  # MUSICA_GRATING_MAX_CONTRAST
 GRATING_MAX = 256           # MUSICA_GRATING_MAX
+GAIN_ONE = 4096             # MUSICA_GAIN_ONE
+PROFILE_MAX_QUERIES = 16    # MUSICA_PROFILE_MAX_QUERIES
 
 
 def zoom_ratio(zoom):
@@ -391,6 +393,26 @@ class SimGratingResult(C.Structure):
     _fields_ = [("roi_ssd", C.c_uint64), ("roi_pixels", C.c_uint64), ("table_offset", C.c_uint64), ("bins", C.c_uint64)]
 
 
+def gain_tables(gx, gy, n):
+    """The two tables of a gain map for a plane of side n as harness.apply_gain and the library take them: (gx, gy), uint16 arrays of n
+    entries (columns, rows) in units of 1 / GAIN_ONE, else ValueError: each a sequence of n integers in 0 .. 65535."""
+    out = []
+    for name, g in (("gx", gx), ("gy", gy)):
+        a = np.asarray(g)
+        if a.ndim != 1 or a.shape[0] != int(n) or a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) > 65535)):
+            raise ValueError("%s is not %d integers in 0 .. 65535, got %r %s" % (name, int(n), a.shape, a.dtype))
+        out.append(np.ascontiguousarray(a, dtype=np.uint16))
+    return tuple(out)
+
+
+PROFILE_SUMS = ("sum_a", "sum_b", "sum_dd", "sum_aa")   # the four words of a line of a profile table
+
+
+class SimProfileResult(C.Structure):
+    """musica_sim_profile_result: where a query's column and row tables lie in `tables`, and the region's exact sum of squared differences."""
+    _fields_ = [("table_offset", C.c_uint64), ("cols", C.c_uint64), ("rows", C.c_uint64), ("ssd", C.c_uint64), ("pixels", C.c_uint64)]
+
+
 class SimDisplaceResult(C.Structure):
     """musica_sim_displace_result: where one comparison's exact block matching puts the output."""
     _fields_ = [("pixels", C.c_uint64), ("ssd_zero", C.c_uint64), ("ssd_min", C.c_uint64), ("dx", C.c_int32), ("dy", C.c_int32),
@@ -596,6 +618,8 @@ ABI = {
     "musica_edge_bins": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_gratings": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Grating), C.POINTER(C.c_int16), C.c_uint64]),
     "musica_sim_gratings": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Grating), C.POINTER(SimGratingResult), _U32P, C.c_uint64]),
+    "musica_alter_gain": (C.c_int, [_VP, C.c_uint32, _U16P, _U16P]),
+    "musica_sim_profiles": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimProfileResult), _U32P, C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -1038,6 +1062,22 @@ class MusicaProcessing:
             out.append(d)
         return out
 
+    def sim_profiles(self, queries):
+        """harness.profile_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 1, at most PROFILE_MAX_QUERIES, all in one launch. Returns one dict per query: "cols", a (w, 4) uint32
+        array, and "rows", (h, 4): per line the exact sum_a, sum_b, sum_dd = sum of (a - b)^2 and sum_aa (PROFILE_SUMS) over the line's
+        pixels inside the region; and the Python ints "ssd" (the sum of either table's sum_dd) and "pixels"."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        words = sum(4 * (int(q.w) + int(q.h)) for q in qs)
+        arr, res, tables = (SimQuery * max(len(qs), 1))(*qs), (SimProfileResult * max(len(qs), 1))(), np.zeros(max(words, 1), dtype=np.uint32)
+        self._ok(self._lib.musica_sim_profiles(self._h, len(qs), arr, res, tables.ctypes.data_as(_U32P), words), "musica_sim_profiles")
+        out = []
+        for r in res[:len(qs)]:
+            at, w, h = int(r.table_offset), int(r.cols), int(r.rows)
+            out.append({"cols": tables[at:at + 4 * w].reshape(w, 4).copy(), "rows": tables[at + 4 * w:at + 4 * (w + h)].reshape(h, 4).copy(),
+                        "ssd": int(r.ssd), "pixels": int(r.pixels)})
+        return out
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -1263,6 +1303,12 @@ class MusicaProcessing:
         waves = np.array([w for g in gs for w in g[6]], dtype=np.int16)
         self._ok(self._lib.musica_alter_gratings(self._h, int(image_index), len(gs), arr, waves.ctypes.data_as(C.POINTER(C.c_int16)), waves.size),
                  "musica_alter_gratings")
+
+    def alter_gain(self, gx, gy, image_index=0):
+        """harness.apply_gain(src, gx, gy): the source under the separable gain map gx[x] gy[y] / GAIN_ONE^2 (gain_tables), one rounding,
+        saturating at 65535."""
+        gx, gy = gain_tables(gx, gy, self.imageSize)
+        self._ok(self._lib.musica_alter_gain(self._h, int(image_index), gx.ctypes.data_as(_U16P), gy.ctypes.data_as(_U16P)), "musica_alter_gain")
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRATING_ROW_KEYS, GRATING_ROW_STATS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRATING_ROW_KEYS, GRATING_ROW_STATS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -39,6 +39,7 @@ EDGE_CSV_HEADER = ['raw file', 'alteration', 'orientation', 'edges'] + ['%s %s' 
                   ['outside mse']   # edge_response.csv
 GRATING_CSV_HEADER = ['raw file', 'alteration', 'period', 'gratings'] + ['%s %s' % (k, w) for k in GRATING_ROW_KEYS for w in GRATING_ROW_STATS] + \
                      ['outside mse']   # grating_response.csv
+GAIN_CSV_HEADER = ['raw file', 'alteration', 'axis', 'lines'] + [k.replace('_', ' ') for k in PROFILE_KEYS]   # gain_response.csv
 
 
 def covariance_csv_header(radius):
@@ -154,6 +155,15 @@ def _grating_lines(studies):
                 yield [raw_name, r["alteration"], t, g["gratings"]] + [g[k][w] for k in GRATING_ROW_KEYS for w in GRATING_ROW_STATS] + [d["outside_mse"]]
 
 
+def _gain_lines(studies):
+    """gain_response.csv's lines: one per gain row and axis, the columns' profile first."""
+    for raw_name, rows in studies:
+        for r in rows:
+            d = r.get("profiles")
+            for axis in (PROFILE_AXES if d else ()):
+                yield [raw_name, r["alteration"], axis, d[axis]["lines"]] + [d[axis][k] for k in PROFILE_KEYS]
+
+
 def write_studies_csvs(studies, out_dir, mean_cnr=True):
     """The reference's output files for several raw images: `studies` is a list of (raw_name, rows) pairs (run_study's rows), written
     in order into one direct_robustness.csv / reg_based_robustness.csv with the reference's column layout (script.py:223-330), plus
@@ -193,7 +203,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
 
     Studies run with gratings (rows[0] has "gratings") also get grating_response.csv (GRATING_CSV_HEADER): one line per grating_ row
     and period, the number of gratings of that period (one in each direction of the grid that has it), the median, min, max over them
-    and the count of those that have the number (an empty cell where none has) of gain, thd and response, and the row's outside mse."""
+    and the count of those that have the number (an empty cell where none has) of gain, thd and response, and the row's outside mse.
+
+    Studies run with gains (rows[0] has "profiles") also get gain_response.csv (GAIN_CSV_HEADER): one line per gain row and axis
+    ("cols": the column profile, scored against gx; "rows": against gy), the number of lines and profile_summary's numbers of the
+    axis (an empty cell where one is None)."""
     os.makedirs(out_dir, exist_ok=True)
     having = lambda key: [(raw_name, rows) for raw_name, rows in studies if rows and key in rows[0]]   # noqa: E731
     toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
@@ -228,6 +242,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
         _write_csv(out_dir, "edge_response.csv", EDGE_CSV_HEADER, _edge_lines(having("edges")))
     if having("gratings"):
         _write_csv(out_dir, "grating_response.csv", GRATING_CSV_HEADER, _grating_lines(having("gratings")))
+    if having("profiles"):
+        _write_csv(out_dir, "gain_response.csv", GAIN_CSV_HEADER, _gain_lines(having("profiles")))
     ovds = [[raw_name] + _cells(_ovd(rows), SIM_CSV_KEYS) for raw_name, rows in studies if _ovd(rows) is not None]
     if ovds:
         _write_csv(out_dir, "ref_similarities.csv", REF_CSV_HEADER, ovds)
