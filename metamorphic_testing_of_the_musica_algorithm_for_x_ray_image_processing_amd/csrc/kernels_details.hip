@@ -6,22 +6,15 @@
 // belongs to at most one disc and to at most one box. A list travels packed, PackedDetail = {x | y << 16, r | (c + 512) << 8}: a plane
 // side is at most 16384 (musica_create), so 8 bytes say everything.
 //
-// k_alter_details<V>: harness.insert_details. ONE launch, 2 B read + 2 B written per pixel: inside a disc
+// k_alter_details<V>: harness.insert_details, the insertion body of study_device.h (insert_patches: bin, stream) with the rule: inside a disc
 //   out = min((v (1024 - c) + 512) >> 10, 65535)          v (1024 - c) + 512 <= 65535 * 1536 + 512 < 2^32: exact u32, ONE rounding
-// and every other pixel is copied. A workgroup of 256 threads owns a 64 x 64 tile of the plane.
-//   bin      the threads stride over the list and append to an LDS list the details whose disc's bounding square (side 2r + 1) meets the
-//            tile, through an LDS counter; the order of the appends does not matter because a pixel meets at most one disc.
-//            CAPACITY. A listed detail has its centre within r of the tile, per axis x in [-r, 63 + r] in tile coordinates. Its box
+// The listed square of a detail is its disc's bounding square (side 2r + 1), and only the chunks that meet one compute d2 per pixel.
+//   CAPACITY A listed detail has its centre within r of the tile, per axis x in [-r, 63 + r] in tile coordinates. Its box
 //            reaches 2r + 2 >= 4 to either side of the centre, so along each axis it covers at least 9 of the 74 positions -5 .. 68
 //            (a centre inside the tile: x - 4 .. x + 4; one left of it: from -5 or further left up to x + 2r + 2 >= r + 2 >= 3; right
 //            likewise). The boxes are disjoint, each holds at least 81 of those 74^2 = 5476 pixels: at most floor(5476 / 81) = 67 are
-//            listed. (r = 1 details at pitch 9 reach 64.) An append past the capacity would be dropped, never written.
-//   stream   a thread moves chunks of V consecutive pixels of a row, V = 8 (16-byte loads and stores) where the side is a multiple of 8
-//            and both planes are 16-byte aligned, else 2 under the same condition for 4 bytes, else single pixels (image 1 of a batch
-//            with odd N^2 starts on a 2-byte boundary only); consecutive lanes take consecutive chunks. All of a thread's loads are
-//            issued before the first is used. A tile with an empty list is a pure copy; elsewhere a chunk is tested against the listed
-//            discs' bounding squares first and only the chunks that meet one compute d2 per pixel.
-// 1.1 KB of LDS. Nothing outside the two planes is read or written; the planes must not overlap.
+//            listed. (r = 1 details at pitch 9 reach 64.)
+// 1.1 KB of LDS.
 //
 // k_sim_details: harness.detail_statistics. One workgroup of 256 threads per detail; side a is the graded f32 plane of a batch image
 // quantised with out_u8 while it is read (exactly what k_sim reads), side b the slot's u8 plane, the detail in the coordinates of the
@@ -45,84 +38,39 @@ constexpr unsigned long long kDetailBoxSide = 4ull * kDetailMaxRadius + 5;
 static_assert(((kDetailBoxSide + kStudyWaves - 1) / kStudyWaves) * ((kDetailBoxSide + 63) / 64) * 255ull * 255ull < (1ull << 32),
               "a lane's partial sums over the largest box fit u32");
 
-struct DetailLds {
-    int x, y, r, c;   // centre in tile coordinates, radius, contrast
-};
-
 __device__ __forceinline__ uint32_t detail_pixel(uint32_t v, int c) { return min((v * (uint32_t)(1024 - c) + 512u) >> 10, 65535u); }
 
-template <int V> struct DetailWord;
-template <> struct DetailWord<8> { typedef uint4 type; };
-template <> struct DetailWord<2> { typedef uint32_t type; };
-template <> struct DetailWord<1> { typedef uint16_t type; };
+struct DetailInsert {
+    typedef PackedDetail Packed;
+    struct Entry {
+        int x, y, r, c;   // centre in tile coordinates, radius, contrast
+    };
+    struct Staged {};
+    struct Row {
+        int r2, dy2;
+    };
+    static constexpr int kTileCap = kDetailTileCap;
+    static __device__ __forceinline__ bool meets(const PackedDetail& p, const TileGeom& t, Entry& e) {
+        e = {(int)(p.xy & 0xFFFFu) - t.x0, (int)(p.xy >> 16) - t.y0, (int)(p.rc & 0xFFu), (int)(p.rc >> 8) - 512};
+        return square_meets(e.x, e.y, e.r, t);
+    }
+    static __device__ __forceinline__ Staged stage(const Entry*, int) { return {}; }
+    static __device__ __forceinline__ Row row(const Entry& d, int, int dy, int, const Staged&) { return {d.r * d.r, dy * dy}; }
+    static __device__ __forceinline__ void pixel(const Entry& d, Row& row, int dx, uint16_t& px) {
+        if (dx * dx + row.dy2 <= row.r2) px = (uint16_t)detail_pixel(px, d.c);
+    }
+};
 
 // n % V == 0 and both planes aligned to 2 V bytes
 template <int V>
 __global__ __launch_bounds__(kDetailThreads) void k_alter_details(const uint16_t* __restrict__ src, uint16_t* __restrict__ out, int n,
                                                                    const PackedDetail* __restrict__ details, int count) {
-    typedef typename DetailWord<V>::type __attribute__((may_alias)) Word;
-    constexpr int ROW = kSimTile / V;                              // chunks per tile row
-    constexpr int TRIPS = kSimTile * ROW / kDetailThreads;         // chunks per thread
-    __shared__ DetailLds list[kDetailTileCap];
-    __shared__ int listed;
-    const int tiles = (n + kSimTile - 1) / kSimTile;
-    const TileGeom t = tile_geom(blockIdx.x, tiles, n, n);
-    if (threadIdx.x == 0) listed = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < count; i += kDetailThreads) {
-        const PackedDetail p = details[i];
-        const int x = (int)(p.xy & 0xFFFFu) - t.x0, y = (int)(p.xy >> 16) - t.y0, r = (int)(p.rc & 0xFFu);
-        if (x + r < 0 || x - r >= t.tw || y + r < 0 || y - r >= t.th) continue;
-        const int slot = atomicAdd(&listed, 1);
-        if (slot < kDetailTileCap) list[slot] = {x, y, r, (int)(p.rc >> 8) - 512};
-    }
-    __syncthreads();
-    const int m = min(listed, kDetailTileCap);
-
-    union Chunk {
-        typename DetailWord<V>::type w;
-        uint16_t px[V];
-    };
-    Chunk staged[TRIPS];
-    // Two passes, unrolled: every load of a thread is in flight before the first is used. A chunk starts inside the plane or lies
-    // outside it entirely (n % V == 0 and the tile's origin is a multiple of 64).
-#pragma unroll
-    for (int k = 0; k < TRIPS; k++) {
-        const int e = k * kDetailThreads + (int)threadIdx.x;
-        const int ty = e / ROW, tx = (e - ty * ROW) * V;
-        if (ty < t.th && tx < t.tw) staged[k].w = *reinterpret_cast<const Word*>(src + (size_t)(t.y0 + ty) * n + (t.x0 + tx));
-    }
-#pragma unroll
-    for (int k = 0; k < TRIPS; k++) {
-        const int e = k * kDetailThreads + (int)threadIdx.x;
-        const int ty = e / ROW, tx = (e - ty * ROW) * V;
-        if (!(ty < t.th && tx < t.tw)) continue;
-        Chunk v = staged[k];
-        for (int j = 0; j < m; j++) {   // m is the same in every lane; 0 in most tiles
-            const DetailLds d = list[j];
-            const int dy = ty - d.y;
-            if (dy < -d.r || dy > d.r || tx + V - 1 < d.x - d.r || tx > d.x + d.r) continue;
-            const int r2 = d.r * d.r, dy2 = dy * dy;
-#pragma unroll
-            for (int q = 0; q < V; q++) {
-                const int dx = tx + q - d.x;
-                if (dx * dx + dy2 <= r2) v.px[q] = (uint16_t)detail_pixel(v.px[q], d.c);
-            }
-        }
-        *reinterpret_cast<Word*>(out + (size_t)(t.y0 + ty) * n + (t.x0 + tx)) = v.w;
-    }
-}
-
-static bool details_aligned(const void* p, const void* q, int n, int v) {
-    return n % v == 0 && reinterpret_cast<uintptr_t>(p) % (2 * v) == 0 && reinterpret_cast<uintptr_t>(q) % (2 * v) == 0;
+    insert_patches<DetailInsert, V>(src, out, n, details, count);
 }
 
 void launch_alter_details(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const PackedDetail* d_details, int count) {
-    const unsigned tiles = (unsigned)((n + kSimTile - 1) / kSimTile);
-    const dim3 grid(tiles * tiles), block(kDetailThreads);
-    if (details_aligned(src, out, n, 8)) hipLaunchKernelGGL((k_alter_details<8>), grid, block, 0, st, src, out, n, d_details, count);
-    else if (details_aligned(src, out, n, 2)) hipLaunchKernelGGL((k_alter_details<2>), grid, block, 0, st, src, out, n, d_details, count);
-    else hipLaunchKernelGGL((k_alter_details<1>), grid, block, 0, st, src, out, n, d_details, count);
+    launch_insert([&](auto v, dim3 grid, dim3 block) { hipLaunchKernelGGL((k_alter_details<decltype(v)::value>), grid, block, 0, st, src, out, n, d_details, count); },
+                  src, out, n);
 }
 
 constexpr int kDetailSums = 13;   // disc n, a, b, aa, bb, ab | ring the same six | box ssd

@@ -8,25 +8,20 @@
 // a list lie inside the plane and are pairwise disjoint (the callers check), so a pixel belongs to at most one plate. A list travels
 // packed, PackedEdge (launchers.h): a plane side is at most 16384.
 //
-// k_alter_edges<V>: harness.insert_edges. ONE launch, 2 B read + 2 B written per pixel: inside a plate, with m = clamp(2s + q, 0, 2q),
+// k_alter_edges<V>: harness.insert_edges, the insertion body of study_device.h (insert_patches: bin, stream) with the rule: inside a
+// plate, with m = clamp(2s + q, 0, 2q),
 //   out = min((v (2048 q - c m) + 1024 q) div (2048 q), 65535)      v (2048 q - c m) + 1024 q <= 65535 * (2048 * 16 + 512 * 32) + 16384
 //                                                                   < 2^32: exact u32, ONE rounding (asserted below on the limits)
-// and every other pixel is copied. m = 0 (s <= -q / 2: the bare side) is v itself and is not computed; m = 2q (the absorber's side) is
+// m = 0 (s <= -q / 2: the bare side) is v itself and is not computed; m = 2q (the absorber's side) is
 // detail_pixel's min((v (1024 - c) + 512) >> 10, 65535), the same number without a division (2q cancels); only the pixels of the
 // transition band 0 < m < 2q divide, as (x >> 11) / q in u32: floor(floor(x / 2048) / q) = floor(x / (2048 q)).
-// A workgroup of 256 threads owns a 64 x 64 tile of the plane, k_alter_details' shape.
-//   bin      the threads stride over the list and append to an LDS list the edges whose plate meets the tile, through an LDS counter;
-//            the order of the appends does not matter because a pixel meets at most one plate.
-//            CAPACITY. A plate has side 4h + 1 >= 33. Along an axis, in tile coordinates, a listed plate is an interval of at least 33
+// The listed square of an edge is its plate, and only the chunks that meet one compute s per pixel.
+//   CAPACITY A plate has side 4h + 1 >= 33. Along an axis, in tile coordinates, a listed plate is an interval of at least 33
 //            positions that meets 0 .. 63, so it covers at least 33 of the 128 positions -32 .. 95: all of itself where it starts at
 //            -32 or later and ends at 95 or sooner, else -32 .. its end >= 0, or its start <= 63 .. 95. The plates are disjoint and
 //            each holds at least 33^2 = 1089 of those 128^2 = 16384 pixels: at most floor(16384 / 1089) = 15 are listed. (h = 8 plates
-//            at pitch 33 reach 9: three to an axis.) An append past the capacity would be dropped, never written.
-//   stream   a thread moves chunks of V consecutive pixels of a row, V = 8 (16-byte loads and stores) where the side is a multiple of 8
-//            and both planes are 16-byte aligned, else 2 under the same condition for 4 bytes, else single pixels; consecutive lanes
-//            take consecutive chunks. All of a thread's loads are issued before the first is used. A tile with an empty list is a pure
-//            copy; elsewhere a chunk is tested against the listed plates first and only the chunks that meet one compute s per pixel.
-// 0.5 KB of LDS. Nothing outside the two planes is read or written; the planes must not overlap.
+//            at pitch 33 reach 9: three to an axis.)
+// 0.5 KB of LDS.
 //
 // k_sim_edges: harness.edge_statistics. One workgroup of 256 threads per edge; side a is the graded f32 plane of a batch image quantised
 // with out_u8 while it is read (exactly what k_sim reads), side b the slot's u8 plane, the edge in the coordinates of the cropped output
@@ -72,91 +67,46 @@ __device__ __forceinline__ EdgeAxes edge_axes(int p, int q, int o) {
     return o == 0 ? EdgeAxes{q, -p} : o == 1 ? EdgeAxes{-p, q} : o == 2 ? EdgeAxes{-q, -p} : EdgeAxes{-p, -q};
 }
 
-struct EdgeLds {
-    int x, y, r, a, b, q, c;   // centre in tile coordinates, the plate's reach 2h, s = a dx + b dy, q, contrast
-};
-
 // 0 < m <= 2q
 __device__ __forceinline__ uint32_t edge_pixel(uint32_t v, int c, int q, int m) {
     if (m == 2 * q) return min((v * (uint32_t)(1024 - c) + 512u) >> 10, 65535u);
     return min(((v * (uint32_t)(2048 * q - c * m) + 1024u * (uint32_t)q) >> 11) / (uint32_t)q, 65535u);
 }
 
-template <int V> struct EdgeWord;
-template <> struct EdgeWord<8> { typedef uint4 type; };
-template <> struct EdgeWord<2> { typedef uint32_t type; };
-template <> struct EdgeWord<1> { typedef uint16_t type; };
+struct EdgeInsert {
+    typedef PackedEdge Packed;
+    struct Entry {
+        int x, y, r, a, b, q, c;   // centre in tile coordinates, the plate's reach 2h, s = a dx + b dy, q, contrast
+    };
+    struct Staged {};
+    typedef int Row;               // b dy
+    static constexpr int kTileCap = kEdgeTileCap;
+    static __device__ __forceinline__ bool meets(const PackedEdge& e, const TileGeom& t, Entry& d) {
+        const int x = (int)(e.xy & 0xFFFFu) - t.x0, y = (int)(e.xy >> 16) - t.y0, r = 2 * (int)(e.hpqo & 0xFFu);
+        if (!square_meets(x, y, r, t)) return false;
+        const int p = (int)((e.hpqo >> 8) & 0xFFu), q = (int)((e.hpqo >> 16) & 0xFFu);
+        const EdgeAxes ax = edge_axes(p, q, (int)(e.hpqo >> 24));
+        d = {x, y, r, ax.a, ax.b, q, e.c};
+        return true;
+    }
+    static __device__ __forceinline__ Staged stage(const Entry*, int) { return {}; }
+    static __device__ __forceinline__ Row row(const Entry& d, int, int dy, int, const Staged&) { return d.b * dy; }
+    static __device__ __forceinline__ void pixel(const Entry& d, Row& row, int dx, uint16_t& px) {
+        const int cover = min(max(2 * (d.a * dx + row) + d.q, 0), 2 * d.q);
+        if (dx >= -d.r && dx <= d.r && cover > 0) px = (uint16_t)edge_pixel(px, d.c, d.q, cover);
+    }
+};
 
 // n % V == 0 and both planes aligned to 2 V bytes
 template <int V>
 __global__ __launch_bounds__(kEdgeThreads) void k_alter_edges(const uint16_t* __restrict__ src, uint16_t* __restrict__ out, int n,
                                                                const PackedEdge* __restrict__ edges, int count) {
-    typedef typename EdgeWord<V>::type __attribute__((may_alias)) Word;
-    constexpr int ROW = kSimTile / V;                            // chunks per tile row
-    constexpr int TRIPS = kSimTile * ROW / kEdgeThreads;         // chunks per thread
-    __shared__ EdgeLds list[kEdgeTileCap];
-    __shared__ int listed;
-    const int tiles = (n + kSimTile - 1) / kSimTile;
-    const TileGeom t = tile_geom(blockIdx.x, tiles, n, n);
-    if (threadIdx.x == 0) listed = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < count; i += kEdgeThreads) {
-        const PackedEdge e = edges[i];
-        const int x = (int)(e.xy & 0xFFFFu) - t.x0, y = (int)(e.xy >> 16) - t.y0, r = 2 * (int)(e.hpqo & 0xFFu);
-        if (x + r < 0 || x - r >= t.tw || y + r < 0 || y - r >= t.th) continue;
-        const int p = (int)((e.hpqo >> 8) & 0xFFu), q = (int)((e.hpqo >> 16) & 0xFFu);
-        const EdgeAxes ax = edge_axes(p, q, (int)(e.hpqo >> 24));
-        const int slot = atomicAdd(&listed, 1);
-        if (slot < kEdgeTileCap) list[slot] = {x, y, r, ax.a, ax.b, q, e.c};
-    }
-    __syncthreads();
-    const int m = min(listed, kEdgeTileCap);
-
-    union Chunk {
-        typename EdgeWord<V>::type w;
-        uint16_t px[V];
-    };
-    Chunk staged[TRIPS];
-    // Two passes, unrolled: every load of a thread is in flight before the first is used. A chunk starts inside the plane or lies
-    // outside it entirely (n % V == 0 and the tile's origin is a multiple of 64).
-#pragma unroll
-    for (int k = 0; k < TRIPS; k++) {
-        const int e = k * kEdgeThreads + (int)threadIdx.x;
-        const int ty = e / ROW, tx = (e - ty * ROW) * V;
-        if (ty < t.th && tx < t.tw) staged[k].w = *reinterpret_cast<const Word*>(src + (size_t)(t.y0 + ty) * n + (t.x0 + tx));
-    }
-#pragma unroll
-    for (int k = 0; k < TRIPS; k++) {
-        const int e = k * kEdgeThreads + (int)threadIdx.x;
-        const int ty = e / ROW, tx = (e - ty * ROW) * V;
-        if (!(ty < t.th && tx < t.tw)) continue;
-        Chunk v = staged[k];
-        for (int j = 0; j < m; j++) {   // m is the same in every lane; 0 in most tiles
-            const EdgeLds d = list[j];
-            const int dy = ty - d.y;
-            if (dy < -d.r || dy > d.r || tx + V - 1 < d.x - d.r || tx > d.x + d.r) continue;
-            const int row = d.b * dy;
-#pragma unroll
-            for (int i = 0; i < V; i++) {
-                const int dx = tx + i - d.x;
-                const int cover = min(max(2 * (d.a * dx + row) + d.q, 0), 2 * d.q);
-                if (dx >= -d.r && dx <= d.r && cover > 0) v.px[i] = (uint16_t)edge_pixel(v.px[i], d.c, d.q, cover);
-            }
-        }
-        *reinterpret_cast<Word*>(out + (size_t)(t.y0 + ty) * n + (t.x0 + tx)) = v.w;
-    }
-}
-
-static bool edges_aligned(const void* p, const void* q, int n, int v) {
-    return n % v == 0 && reinterpret_cast<uintptr_t>(p) % (2 * v) == 0 && reinterpret_cast<uintptr_t>(q) % (2 * v) == 0;
+    insert_patches<EdgeInsert, V>(src, out, n, edges, count);
 }
 
 void launch_alter_edges(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const PackedEdge* d_edges, int count) {
-    const unsigned tiles = (unsigned)((n + kSimTile - 1) / kSimTile);
-    const dim3 grid(tiles * tiles), block(kEdgeThreads);
-    if (edges_aligned(src, out, n, 8)) hipLaunchKernelGGL((k_alter_edges<8>), grid, block, 0, st, src, out, n, d_edges, count);
-    else if (edges_aligned(src, out, n, 2)) hipLaunchKernelGGL((k_alter_edges<2>), grid, block, 0, st, src, out, n, d_edges, count);
-    else hipLaunchKernelGGL((k_alter_edges<1>), grid, block, 0, st, src, out, n, d_edges, count);
+    launch_insert([&](auto v, dim3 grid, dim3 block) { hipLaunchKernelGGL((k_alter_edges<decltype(v)::value>), grid, block, 0, st, src, out, n, d_edges, count); },
+                  src, out, n);
 }
 
 // floor(t / q) for q > 0 and any t

@@ -9,9 +9,8 @@
 //   v g + 2^23 = 2^16 (v gh + 2^7) + v gl, so floor((v g + 2^23) / 2^24) = floor((v gh + 2^7 + floor(v gl / 2^16)) / 2^8):
 //   floor division nests and 2^23 is a multiple of 2^16. v gh <= 65535^2 and floor(v gl / 2^16) + 128 <= 65534 + 128, so the sum stays
 //   below 2^32 (asserted below): two 24-bit multiplies, two shifts and one three-operand add per pixel, no 64-bit multiply.
-// A workgroup of 256 threads is four wavefronts. A lane owns V consecutive columns, V = 8 (16-byte loads and stores) where the side is
-// a multiple of 8 and both planes are 16-byte aligned, else 2 under the same condition for 4 bytes, else single pixels; consecutive lanes
-// take consecutive chunks, so a wavefront moves 1 KiB of one row per access. The lane's V entries of gx are loaded once (one 16-byte load
+// A workgroup of 256 threads is four wavefronts. A lane owns V consecutive columns (study_device.h's pixel words, gx being a third
+// plane of the alignment test); consecutive lanes take consecutive chunks, so a wavefront moves 1 KiB of one row per access. The lane's V entries of gx are loaded once (one 16-byte load
 // for V = 8: the table is a device allocation of its own) and stay in registers while the wavefront goes down kGainRows consecutive rows,
 // whose loads are all issued before the first is used. The row index comes from blockIdx.y and the wavefront's number through
 // readfirstlane, so the compiler knows it is the same in every lane: gy[y] (widened to u32 by the caller, since gfx950 has no 16-bit
@@ -59,20 +58,12 @@ __device__ __forceinline__ uint32_t gain_pixel(uint32_t v, uint32_t g) {
     return min((hi + (lo >> 16) + 128u) >> 8, 65535u);
 }
 
-template <int V> struct GainWord;
-template <> struct GainWord<8> { typedef uint4 type; };
-template <> struct GainWord<2> { typedef uint32_t type; };
-template <> struct GainWord<1> { typedef uint16_t type; };
-
 // n % V == 0 and both planes and gx aligned to 2 V bytes; gy: the row gains widened to u32
 template <int V>
 __global__ __launch_bounds__(kGainThreads) void k_alter_gain(const uint16_t* __restrict__ src, uint16_t* __restrict__ out, int n,
                                                              const uint16_t* __restrict__ gx, const uint32_t* __restrict__ gy) {
-    typedef typename GainWord<V>::type __attribute__((may_alias)) Word;
-    union Chunk {
-        typename GainWord<V>::type w;
-        uint16_t px[V];
-    };
+    typedef typename PixelWord<V>::type __attribute__((may_alias)) Word;
+    typedef PixelChunk<V> Chunk;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: the row arithmetic stays on the scalar unit
     const int y0 = (int)blockIdx.y * kGainBlockRows + wave * kGainRows;
     const int x = ((int)blockIdx.x * 64 + (int)(threadIdx.x & 63)) * V;
@@ -94,21 +85,14 @@ __global__ __launch_bounds__(kGainThreads) void k_alter_gain(const uint16_t* __r
     }
 }
 
-static bool gain_aligned(const void* p, const void* q, const void* t, int n, int v) {
-    return n % v == 0 && reinterpret_cast<uintptr_t>(p) % (2 * v) == 0 && reinterpret_cast<uintptr_t>(q) % (2 * v) == 0 &&
-           reinterpret_cast<uintptr_t>(t) % (2 * v) == 0;
-}
-
-template <int V>
-static void launch_alter_gain_as(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const uint16_t* d_gx, const uint32_t* d_gy) {
-    const dim3 grid((unsigned)((n / V + 63) / 64), (unsigned)((n + kGainBlockRows - 1) / kGainBlockRows));
-    hipLaunchKernelGGL((k_alter_gain<V>), grid, dim3(kGainThreads), 0, st, src, out, n, d_gx, d_gy);
-}
-
 void launch_alter_gain(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const uint16_t* d_gx, const uint32_t* d_gy) {
-    if (gain_aligned(src, out, d_gx, n, 8)) launch_alter_gain_as<8>(st, src, out, n, d_gx, d_gy);
-    else if (gain_aligned(src, out, d_gx, n, 2)) launch_alter_gain_as<2>(st, src, out, n, d_gx, d_gy);
-    else launch_alter_gain_as<1>(st, src, out, n, d_gx, d_gy);
+    launch_by_width(
+        [&](auto v) {
+            constexpr int V = decltype(v)::value;
+            const dim3 grid((unsigned)((n / V + 63) / 64), (unsigned)((n + kGainBlockRows - 1) / kGainBlockRows));
+            hipLaunchKernelGGL((k_alter_gain<V>), grid, dim3(kGainThreads), 0, st, src, out, n, d_gx, d_gy);
+        },
+        n, src, out, d_gx);
 }
 
 // ---- the profiles ----------------------------------------------------------------------------------------------------------------------

@@ -7,25 +7,19 @@
 // S = 2h + 1) measured. The plates of a list lie inside the plane and are pairwise disjoint (the callers check), so a pixel belongs to
 // at most one plate. A list travels packed, PackedGrating (launchers.h): a plane side is at most 16384.
 //
-// k_alter_gratings<V>: harness.insert_gratings. ONE launch, 2 B read + 2 B written per pixel: inside a plate
+// k_alter_gratings<V>: harness.insert_gratings, the insertion body of study_device.h (insert_patches: bin, stage, stream) with the rule:
+// inside a plate
 //   out = min((v (1024 - wave[k]) + 512) >> 10, 65535)      |wave| <= 512: v (1024 - wave) + 512 <= 65535 * 1536 + 512 < 2^32, exact u32,
 //                                                            ONE rounding (asserted below on the limits); wave = 0 gives v
-// and every other pixel is copied. A workgroup of 256 threads owns a 64 x 64 tile of the plane, k_alter_edges' shape.
-//   bin      the threads stride over the list and append to an LDS list the gratings whose plate meets the tile, through an LDS counter;
-//            the order of the appends does not matter because a pixel meets at most one plate.
-//            CAPACITY. k_alter_edges' argument: a plate has side 4h + 1 >= 33, so along an axis a listed plate covers at least 33 of the
+// The listed square of a grating is its plate.
+//   CAPACITY k_alter_edges' argument: a plate has side 4h + 1 >= 33, so along an axis a listed plate covers at least 33 of the
 //            128 positions -32 .. 95 of the tile grown by 32; the plates are disjoint and each holds at least 33^2 = 1089 of those
-//            128^2 = 16384 pixels: at most floor(16384 / 1089) = 15 are listed. An append past the capacity would be dropped.
-//   waves    the listed gratings' wave tables are staged next to the list, T <= 64 int16 each: at most 15 x 64 x 2 B = 1920 B.
-//   stream   a thread moves chunks of V consecutive pixels of a row, V = 8 (16-byte loads and stores) where the side is a multiple of 8
-//            and both planes are 16-byte aligned, else 2 under the same condition for 4 bytes, else single pixels; consecutive lanes
-//            take consecutive chunks. All of a thread's loads are issued before the first is used. A tile with an empty list is a pure
-//            copy; elsewhere a chunk is tested against the listed plates first, and a chunk that meets one takes the phase of its first
-//            pixel with one remainder and carries it along the chunk as k += ux with one wrap (|ux| < T): no division per pixel for
-//            V = 8 and 2. (V = 1, the fallback for odd sides, has one-pixel chunks and so takes the remainder per plate pixel.)
-// 2.3 KB of LDS. Nothing outside the two planes and the list's waves is read, nothing outside `out` written; the planes must not overlap.
-// The word types and the alignment test are k_alter_edges' few lines again, not moved to study_device.h: that would change what
-// kernels_edges.hip is compiled from for five lines.
+//            128^2 = 16384 pixels: at most floor(16384 / 1089) = 15 are listed.
+//   stage    the listed gratings' wave tables are staged next to the list, T <= 64 int16 each: at most 15 x 64 x 2 B = 1920 B.
+//   row      a chunk that meets a plate takes the phase of its first pixel with one remainder and carries it along the chunk as
+//            k += ux with one wrap (|ux| < T): no division per pixel for V = 8 and 2. (V = 1, the fallback for odd sides, has
+//            one-pixel chunks and so takes the remainder per plate pixel.)
+// 2.3 KB of LDS. Beyond the two planes only the list's waves are read.
 //
 // k_sim_gratings: harness.grating_statistics. One workgroup of 256 threads per grating; side a is the graded f32 plane of a batch image
 // quantised with out_u8 while it is read (exactly what k_sim reads), side b the slot's u8 plane, the grating in the coordinates of the
@@ -89,10 +83,6 @@ constexpr unsigned long long grating_lane_pixels() {
 }
 static_assert(grating_lane_pixels() * 255ull * 255ull < (1ull << 32), "a lane's roi_ssd over the largest region fits u32");
 
-struct GratingLds {
-    int x, y, r, ux, uy, t;   // centre in tile coordinates, the plate's reach 2h, the wave vector, the period
-};
-
 __device__ __forceinline__ int grating_ux(uint32_t htuv) { return (int)(int8_t)((htuv >> 16) & 0xFFu); }
 __device__ __forceinline__ int grating_uy(uint32_t htuv) { return (int)(int8_t)(htuv >> 24); }
 
@@ -102,90 +92,55 @@ __device__ __forceinline__ int floor_mod(int t, int q) {
     return m < 0 ? m + q : m;
 }
 
-template <int V> struct GratingWord;
-template <> struct GratingWord<8> { typedef uint4 type; };
-template <> struct GratingWord<2> { typedef uint32_t type; };
-template <> struct GratingWord<1> { typedef uint16_t type; };
+struct GratingInsert {
+    typedef PackedGrating Packed;
+    struct Entry {
+        int x, y, r, ux, uy, t;   // centre in tile coordinates, the plate's reach 2h, the wave vector, the period
+        uint32_t first;           // where its wave begins in the list's waves
+    };
+    typedef int16_t Wave[kGratingMaxPeriod];
+    struct Staged {
+        const Wave* wave;         // the listed gratings' waves, in LDS
+    };
+    struct Row {
+        const int16_t* wave;
+        int phase;                // of the next pixel of the chunk
+    };
+    static constexpr int kTileCap = kGratingTileCap;
+    static __device__ __forceinline__ bool meets(const PackedGrating& g, const TileGeom& t, Entry& e) {
+        e = {(int)(g.xy & 0xFFFFu) - t.x0, (int)(g.xy >> 16) - t.y0, 2 * (int)(g.htuv & 0xFFu), grating_ux(g.htuv), grating_uy(g.htuv),
+             (int)((g.htuv >> 8) & 0xFFu), g.first};
+        return square_meets(e.x, e.y, e.r, t);
+    }
+    static __device__ __forceinline__ Staged stage(const Entry* list, int m, const int16_t* __restrict__ waves) {
+        __shared__ Wave wave[kGratingTileCap];
+        for (int i = threadIdx.x; i < m * kGratingMaxPeriod; i += kGratingThreads) {   // nothing in most tiles
+            const int j = i / kGratingMaxPeriod, k = i - j * kGratingMaxPeriod;
+            if (k < list[j].t) wave[j][k] = waves[list[j].first + k];
+        }
+        __syncthreads();
+        return {wave};
+    }
+    static __device__ __forceinline__ Row row(const Entry& d, int j, int dy, int tx, const Staged& s) {
+        return {s.wave[j], floor_mod(d.ux * (tx - d.x) + d.uy * dy, d.t)};
+    }
+    static __device__ __forceinline__ void pixel(const Entry& d, Row& row, int dx, uint16_t& px) {
+        if (dx >= -d.r && dx <= d.r) px = (uint16_t)min(((uint32_t)px * (uint32_t)(1024 - (int)row.wave[row.phase]) + 512u) >> 10, 65535u);
+        row.phase += d.ux;
+        row.phase = row.phase >= d.t ? row.phase - d.t : row.phase < 0 ? row.phase + d.t : row.phase;
+    }
+};
 
 // n % V == 0 and both planes aligned to 2 V bytes
 template <int V>
 __global__ __launch_bounds__(kGratingThreads) void k_alter_gratings(const uint16_t* __restrict__ src, uint16_t* __restrict__ out, int n,
                                                                      const PackedGrating* __restrict__ gratings, const int16_t* __restrict__ waves, int count) {
-    typedef typename GratingWord<V>::type __attribute__((may_alias)) Word;
-    constexpr int ROW = kSimTile / V;                               // chunks per tile row
-    constexpr int TRIPS = kSimTile * ROW / kGratingThreads;         // chunks per thread
-    __shared__ GratingLds list[kGratingTileCap];
-    __shared__ uint32_t first[kGratingTileCap];
-    __shared__ int16_t wave[kGratingTileCap][kGratingMaxPeriod];
-    __shared__ int listed;
-    const int tiles = (n + kSimTile - 1) / kSimTile;
-    const TileGeom t = tile_geom(blockIdx.x, tiles, n, n);
-    if (threadIdx.x == 0) listed = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < count; i += kGratingThreads) {
-        const PackedGrating g = gratings[i];
-        const int x = (int)(g.xy & 0xFFFFu) - t.x0, y = (int)(g.xy >> 16) - t.y0, r = 2 * (int)(g.htuv & 0xFFu);
-        if (x + r < 0 || x - r >= t.tw || y + r < 0 || y - r >= t.th) continue;
-        const int slot = atomicAdd(&listed, 1);
-        if (slot < kGratingTileCap) {
-            list[slot] = {x, y, r, grating_ux(g.htuv), grating_uy(g.htuv), (int)((g.htuv >> 8) & 0xFFu)};
-            first[slot] = g.first;
-        }
-    }
-    __syncthreads();
-    const int m = min(listed, kGratingTileCap);
-    for (int i = threadIdx.x; i < m * kGratingMaxPeriod; i += kGratingThreads) {   // nothing in most tiles
-        const int j = i / kGratingMaxPeriod, k = i - j * kGratingMaxPeriod;
-        if (k < list[j].t) wave[j][k] = waves[first[j] + k];
-    }
-    __syncthreads();
-
-    union Chunk {
-        typename GratingWord<V>::type w;
-        uint16_t px[V];
-    };
-    Chunk staged[TRIPS];
-    // Two passes, unrolled: every load of a thread is in flight before the first is used. A chunk starts inside the plane or lies
-    // outside it entirely (n % V == 0 and the tile's origin is a multiple of 64).
-#pragma unroll
-    for (int k = 0; k < TRIPS; k++) {
-        const int e = k * kGratingThreads + (int)threadIdx.x;
-        const int ty = e / ROW, tx = (e - ty * ROW) * V;
-        if (ty < t.th && tx < t.tw) staged[k].w = *reinterpret_cast<const Word*>(src + (size_t)(t.y0 + ty) * n + (t.x0 + tx));
-    }
-#pragma unroll
-    for (int k = 0; k < TRIPS; k++) {
-        const int e = k * kGratingThreads + (int)threadIdx.x;
-        const int ty = e / ROW, tx = (e - ty * ROW) * V;
-        if (!(ty < t.th && tx < t.tw)) continue;
-        Chunk v = staged[k];
-        for (int j = 0; j < m; j++) {   // m is the same in every lane; 0 in most tiles
-            const GratingLds d = list[j];
-            const int dy = ty - d.y;
-            if (dy < -d.r || dy > d.r || tx + V - 1 < d.x - d.r || tx > d.x + d.r) continue;
-            int phase = floor_mod(d.ux * (tx - d.x) + d.uy * dy, d.t);
-#pragma unroll
-            for (int i = 0; i < V; i++) {
-                const int dx = tx + i - d.x;
-                if (dx >= -d.r && dx <= d.r) v.px[i] = (uint16_t)min(((uint32_t)v.px[i] * (uint32_t)(1024 - (int)wave[j][phase]) + 512u) >> 10, 65535u);
-                phase += d.ux;
-                phase = phase >= d.t ? phase - d.t : phase < 0 ? phase + d.t : phase;
-            }
-        }
-        *reinterpret_cast<Word*>(out + (size_t)(t.y0 + ty) * n + (t.x0 + tx)) = v.w;
-    }
-}
-
-static bool gratings_aligned(const void* p, const void* q, int n, int v) {
-    return n % v == 0 && reinterpret_cast<uintptr_t>(p) % (2 * v) == 0 && reinterpret_cast<uintptr_t>(q) % (2 * v) == 0;
+    insert_patches<GratingInsert, V>(src, out, n, gratings, count, waves);
 }
 
 void launch_alter_gratings(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const PackedGrating* d_gratings, const int16_t* d_waves, int count) {
-    const unsigned tiles = (unsigned)((n + kSimTile - 1) / kSimTile);
-    const dim3 grid(tiles * tiles), block(kGratingThreads);
-    if (gratings_aligned(src, out, n, 8)) hipLaunchKernelGGL((k_alter_gratings<8>), grid, block, 0, st, src, out, n, d_gratings, d_waves, count);
-    else if (gratings_aligned(src, out, n, 2)) hipLaunchKernelGGL((k_alter_gratings<2>), grid, block, 0, st, src, out, n, d_gratings, d_waves, count);
-    else hipLaunchKernelGGL((k_alter_gratings<1>), grid, block, 0, st, src, out, n, d_gratings, d_waves, count);
+    launch_insert([&](auto v, dim3 grid, dim3 block) { hipLaunchKernelGGL((k_alter_gratings<decltype(v)::value>), grid, block, 0, st, src, out, n, d_gratings, d_waves, count); },
+                  src, out, n);
 }
 
 // a: the graded f32 plane at output pixel (0, 0) (the margin skipped), b: the slot's plane; results: count x kGratingWords u64; tables:

@@ -1,7 +1,9 @@
-// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the eight query calls
-// (musica_sim_*; kernels_similarity.hip, kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip), the ensemble accumulators
-// (musica_sim_ensemble_*; kernels_ensemble.hip, kernels_covariance.hip) and the alterations of the input (musica_alter_*;
-// kernels_alteration.hip, kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip). Their state is musica_ctx::study; the pipeline (musica_ctx.hip, musica_step.hip) knows none of it.
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the eight query calls (musica_sim_*),
+// the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
+// kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
+// kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip and, each with a measurement and an alteration,
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip. Their state is musica_ctx::study; the pipeline
+// (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
 
@@ -65,14 +67,14 @@ static int sim_derive_slot(musica_ctx* c, const char* fn, uint32_t dst_slot, uin
     return 1;
 }
 
+static uint32_t gcd_u32(uint32_t a, uint32_t b) { return b ? gcd_u32(b, a % b) : a; }
+
 static_assert(kZoomMaxP == MUSICA_ZOOM_MAX_P, "kernels_zoom.hip's u32 sums hold for the zooms of include/musica.h");
 
 // What both zoom calls refuse about p / q: harness.zoom's 1 <= q < p <= MUSICA_ZOOM_MAX_P in lowest terms.
 static int zoom_check(const char* fn, uint32_t p, uint32_t q) {
     if (q == 0 || p <= q || p > MUSICA_ZOOM_MAX_P) return fail("%s: zoom %u / %u is not 1 <= q < p <= %d", fn, p, q, MUSICA_ZOOM_MAX_P);
-    uint32_t a = p, b = q;
-    while (b) { const uint32_t r = a % b; a = b; b = r; }
-    if (a != 1) return fail("%s: zoom %u / %u is not in lowest terms (gcd %u)", fn, p, q, a);
+    if (gcd_u32(p, q) != 1) return fail("%s: zoom %u / %u is not in lowest terms (gcd %u)", fn, p, q, gcd_u32(p, q));
     return 1;
 }
 
@@ -85,9 +87,7 @@ static int scatter_check(const char* fn, uint32_t radius, uint32_t num, uint32_t
     if (radius < 1 || radius > MUSICA_SCATTER_MAX_RADIUS) return fail("%s: radius %u out of range [1, %d]", fn, radius, MUSICA_SCATTER_MAX_RADIUS);
     if (num == 0 || num >= den || den > MUSICA_SCATTER_MAX_DEN)
         return fail("%s: scatter fraction %u / %u is not 1 <= num < den <= %d", fn, num, den, MUSICA_SCATTER_MAX_DEN);
-    uint32_t a = den, b = num;
-    while (b) { const uint32_t r = a % b; a = b; b = r; }
-    if (a != 1) return fail("%s: scatter fraction %u / %u is not in lowest terms (gcd %u)", fn, num, den, a);
+    if (gcd_u32(den, num) != 1) return fail("%s: scatter fraction %u / %u is not in lowest terms (gcd %u)", fn, num, den, gcd_u32(den, num));
     return 1;
 }
 
@@ -98,42 +98,54 @@ static int scatter_plane(musica_ctx* c, const char* fn) {
     return 1;
 }
 
-static_assert(kDetailMaxRadius == MUSICA_DETAIL_MAX_RADIUS && kDetailMaxContrast == MUSICA_DETAIL_MAX_CONTRAST && kDetailMax == MUSICA_DETAIL_MAX,
-              "kernels_details.hip's tile list, u32 pixel and u32 partial sums hold for the details of include/musica.h");
-static_assert(sizeof(musica_sim_detail_result) == kDetailWords * sizeof(uint64_t), "k_sim_details writes a musica_sim_detail_result as its u64 words");
+// ---- lists of square patches on a plane (the details' boxes, the edges' and gratings' plates) -----------------------------------------
+// What a refusal calls a relation's patch and its item: "box" / "boxes" of a "detail", "plate" / "plates" of an "edge" or a "grating".
+struct PatchNouns {
+    const char *square, *squares, *item;
+};
+constexpr PatchNouns kDetailNouns{"box", "boxes", "detail"}, kEdgeNouns{"plate", "plates", "edge"}, kGratingNouns{"plate", "plates", "grating"};
 
-// What both detail calls refuse about a list for a plane of side n (processing.detail_list): the count, each radius (and each contrast
-// when the call looks at it), boxes inside the plane, boxes pairwise disjoint. Fills `packed` for the device. No device work.
-static int details_check(const char* fn, uint32_t count, const musica_detail* ds, int n, bool with_contrast, std::vector<PackedDetail>& packed) {
-    if (count == 0 || count > MUSICA_DETAIL_MAX) return fail("%s: count %u out of range [1, %d]", fn, count, MUSICA_DETAIL_MAX);
+// What every list call refuses about `count` items (each with a centre x, y) for a plane of side n, as processing's *_list do: the
+// count; per item what each(i, item, packed) refuses about it (1, or fail(...); it fills the packed item for the device) and a square
+// centre +- reach(item) that leaves the plane; squares that are not pairwise disjoint. No device work.
+template <typename Item, typename Packed, typename Reach, typename Each>
+static int patch_list_check(const char* fn, const PatchNouns& nouns, uint32_t count, uint32_t most, const Item* items, int n, std::vector<Packed>& packed,
+                            Reach reach, Each each) {
+    if (count == 0 || count > most) return fail("%s: count %u out of range [1, %d]", fn, count, (int)most);
     packed.resize(count);
     for (uint32_t i = 0; i < count; i++) {
-        const musica_detail& d = ds[i];
-        if (d.radius < 1 || d.radius > MUSICA_DETAIL_MAX_RADIUS) return fail("%s: detail %u: radius %u out of range [1, %d]", fn, i, d.radius, MUSICA_DETAIL_MAX_RADIUS);
-        if (with_contrast && (d.contrast == 0 || d.contrast < -MUSICA_DETAIL_MAX_CONTRAST || d.contrast > MUSICA_DETAIL_MAX_CONTRAST))
-            return fail("%s: detail %u: contrast %d is not 1 <= |contrast| <= %d", fn, i, d.contrast, MUSICA_DETAIL_MAX_CONTRAST);
-        const int64_t ro = 2 * (int64_t)d.radius + 2;
-        if (d.x - ro < 0 || d.y - ro < 0 || d.x + ro >= n || d.y + ro >= n)
-            return fail("%s: detail %u: the box (%d, %d) +- %d leaves the %d x %d plane", fn, i, d.x, d.y, (int)ro, n, n);
-        const int c = with_contrast ? d.contrast : 0;
-        packed[i] = {(uint32_t)d.x | ((uint32_t)d.y << 16), d.radius | ((uint32_t)(c + 512) << 8)};
+        const Item& t = items[i];
+        if (!each(i, t, packed[i])) return 0;
+        const int64_t r = reach(t);
+        if (t.x - r < 0 || t.y - r < 0 || t.x + r >= n || t.y + r >= n)
+            return fail("%s: %s %u: the %s (%d, %d) +- %d leaves the %d x %d plane", fn, nouns.item, i, nouns.square, t.x, t.y, (int)r, n, n);
     }
     for (uint32_t i = 0; i < count; i++)
         for (uint32_t j = i + 1; j < count; j++) {
-            const int64_t reach = 2 * ((int64_t)ds[i].radius + ds[j].radius) + 4;
-            if (std::abs((int64_t)ds[i].x - ds[j].x) <= reach && std::abs((int64_t)ds[i].y - ds[j].y) <= reach)
-                return fail("%s: the boxes of details %u and %u are not disjoint", fn, i, j);
+            const int64_t both = reach(items[i]) + reach(items[j]);
+            if (std::abs((int64_t)items[i].x - items[j].x) <= both && std::abs((int64_t)items[i].y - items[j].y) <= both)
+                return fail("%s: the %s of %ss %u and %u are not disjoint", fn, nouns.squares, nouns.item, i, j);
         }
     return 1;
 }
 
-// The call's list on the device: copied on the stream, behind the kernels that still read the last call's, and `packed` is free again
-// when this returns.
-static int details_upload(musica_ctx* c, const char* fn, const std::vector<PackedDetail>& packed) {
-    if (!ensure(c, &c->study.d_details, MUSICA_DETAIL_MAX)) return fail("%s: device allocation of the detail list failed", fn);
-    HIP_OK(hipMemcpyAsync(c->study.d_details, packed.data(), packed.size() * sizeof(PackedDetail), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
+static_assert(kDetailMaxRadius == MUSICA_DETAIL_MAX_RADIUS && kDetailMaxContrast == MUSICA_DETAIL_MAX_CONTRAST && kDetailMax == MUSICA_DETAIL_MAX,
+              "kernels_details.hip's tile list, u32 pixel and u32 partial sums hold for the details of include/musica.h");
+static_assert(sizeof(musica_sim_detail_result) == kDetailWords * sizeof(uint64_t), "k_sim_details writes a musica_sim_detail_result as its u64 words");
+
+// What both detail calls refuse about a list for a plane of side n (processing.detail_list): patch_list_check with each radius (and
+// each contrast when the call looks at it) and the boxes' reach 2r + 2.
+static int details_check(const char* fn, uint32_t count, const musica_detail* ds, int n, bool with_contrast, std::vector<PackedDetail>& packed) {
+    return patch_list_check(fn, kDetailNouns, count, MUSICA_DETAIL_MAX, ds, n, packed, [](const musica_detail& d) { return 2 * (int64_t)d.radius + 2; },
+                            [&](uint32_t i, const musica_detail& d, PackedDetail& p) {
+                                if (d.radius < 1 || d.radius > MUSICA_DETAIL_MAX_RADIUS)
+                                    return fail("%s: detail %u: radius %u out of range [1, %d]", fn, i, d.radius, MUSICA_DETAIL_MAX_RADIUS);
+                                if (with_contrast && (d.contrast == 0 || d.contrast < -MUSICA_DETAIL_MAX_CONTRAST || d.contrast > MUSICA_DETAIL_MAX_CONTRAST))
+                                    return fail("%s: detail %u: contrast %d is not 1 <= |contrast| <= %d", fn, i, d.contrast, MUSICA_DETAIL_MAX_CONTRAST);
+                                const int c = with_contrast ? d.contrast : 0;
+                                p = {(uint32_t)d.x | ((uint32_t)d.y << 16), d.radius | ((uint32_t)(c + 512) << 8)};
+                                return 1;
+                            });
 }
 
 static_assert(kEdgeMinHalf == MUSICA_EDGE_MIN_HALF && kEdgeMaxHalf == MUSICA_EDGE_MAX_HALF && kEdgeMinQ == MUSICA_EDGE_MIN_Q && kEdgeMaxQ == MUSICA_EDGE_MAX_Q &&
@@ -141,51 +153,31 @@ static_assert(kEdgeMinHalf == MUSICA_EDGE_MIN_HALF && kEdgeMaxHalf == MUSICA_EDG
               "kernels_edges.hip's tile list, u32 pixel, LDS table and u32 sums hold for the edges of include/musica.h");
 static_assert(sizeof(musica_sim_edge_result) == kEdgeWords * sizeof(uint64_t), "k_sim_edges writes a musica_sim_edge_result as its u64 words");
 
-static uint32_t edge_gcd(uint32_t a, uint32_t b) { return b ? edge_gcd(b, a % b) : a; }
-
 uint32_t musica_edge_bins(uint32_t half, uint32_t p, uint32_t q) {
-    if (half < MUSICA_EDGE_MIN_HALF || half > MUSICA_EDGE_MAX_HALF || q < MUSICA_EDGE_MIN_Q || q > MUSICA_EDGE_MAX_Q || p < 1 || p >= q || edge_gcd(p, q) != 1) return 0;
+    if (half < MUSICA_EDGE_MIN_HALF || half > MUSICA_EDGE_MAX_HALF || q < MUSICA_EDGE_MIN_Q || q > MUSICA_EDGE_MAX_Q || p < 1 || p >= q || gcd_u32(p, q) != 1) return 0;
     return 2 * ((4 * (q + p) * half + q - 1) / q) + 1;
 }
 
-// What both edge calls refuse about a list for a plane of side n (processing.edge_list): the count, each half-side, slope and
-// orientation (and each contrast when the call looks at it), plates inside the plane, plates pairwise disjoint. Fills `packed` for the
-// device, each edge's table behind the one before it, and `words` with the tables' total. No device work.
+// What both edge calls refuse about a list for a plane of side n (processing.edge_list): patch_list_check with each half-side, slope
+// and orientation (and each contrast when the call looks at it) and the plates' reach 2 half. Each edge's table lies behind the one
+// before it; `words` is the tables' total.
 static int edges_check(const char* fn, uint32_t count, const musica_edge* es, int n, bool with_contrast, std::vector<PackedEdge>& packed, uint64_t* words) {
-    if (count == 0 || count > MUSICA_EDGE_MAX) return fail("%s: count %u out of range [1, %d]", fn, count, MUSICA_EDGE_MAX);
-    packed.resize(count);
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < count; i++) {
-        const musica_edge& e = es[i];
-        if (e.half < MUSICA_EDGE_MIN_HALF || e.half > MUSICA_EDGE_MAX_HALF)
-            return fail("%s: edge %u: half-side %u out of range [%d, %d]", fn, i, e.half, MUSICA_EDGE_MIN_HALF, MUSICA_EDGE_MAX_HALF);
-        const uint32_t bins = musica_edge_bins(e.half, e.p, e.q);
-        if (!bins) return fail("%s: edge %u: slope %u / %u is not 1 <= p < q, %d <= q <= %d in lowest terms", fn, i, e.p, e.q, MUSICA_EDGE_MIN_Q, MUSICA_EDGE_MAX_Q);
-        if (e.orientation > 3) return fail("%s: edge %u: orientation %u out of range [0, 3]", fn, i, e.orientation);
-        if (with_contrast && (e.contrast == 0 || e.contrast < -MUSICA_EDGE_MAX_CONTRAST || e.contrast > MUSICA_EDGE_MAX_CONTRAST))
-            return fail("%s: edge %u: contrast %d is not 1 <= |contrast| <= %d", fn, i, e.contrast, MUSICA_EDGE_MAX_CONTRAST);
-        const int64_t reach = 2 * (int64_t)e.half;
-        if (e.x - reach < 0 || e.y - reach < 0 || e.x + reach >= n || e.y + reach >= n)
-            return fail("%s: edge %u: the plate (%d, %d) +- %d leaves the %d x %d plane", fn, i, e.x, e.y, (int)reach, n, n);
-        packed[i] = {(uint32_t)e.x | ((uint32_t)e.y << 16), e.half | (e.p << 8) | (e.q << 16) | (e.orientation << 24), with_contrast ? e.contrast : 0, (uint32_t)at};
-        at += 4ull * bins;
-    }
-    for (uint32_t i = 0; i < count; i++)
-        for (uint32_t j = i + 1; j < count; j++) {
-            const int64_t reach = 2 * ((int64_t)es[i].half + es[j].half);
-            if (std::abs((int64_t)es[i].x - es[j].x) <= reach && std::abs((int64_t)es[i].y - es[j].y) <= reach)
-                return fail("%s: the plates of edges %u and %u are not disjoint", fn, i, j);
-        }
-    *words = at;
-    return 1;
-}
-
-// The call's list on the device, as details_upload.
-static int edges_upload(musica_ctx* c, const char* fn, const std::vector<PackedEdge>& packed) {
-    if (!ensure(c, &c->study.d_edges, MUSICA_EDGE_MAX)) return fail("%s: device allocation of the edge list failed", fn);
-    HIP_OK(hipMemcpyAsync(c->study.d_edges, packed.data(), packed.size() * sizeof(PackedEdge), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
+    *words = 0;
+    return patch_list_check(fn, kEdgeNouns, count, MUSICA_EDGE_MAX, es, n, packed, [](const musica_edge& e) { return 2 * (int64_t)e.half; },
+                            [&](uint32_t i, const musica_edge& e, PackedEdge& p) {
+                                if (e.half < MUSICA_EDGE_MIN_HALF || e.half > MUSICA_EDGE_MAX_HALF)
+                                    return fail("%s: edge %u: half-side %u out of range [%d, %d]", fn, i, e.half, MUSICA_EDGE_MIN_HALF, MUSICA_EDGE_MAX_HALF);
+                                const uint32_t bins = musica_edge_bins(e.half, e.p, e.q);
+                                if (!bins)
+                                    return fail("%s: edge %u: slope %u / %u is not 1 <= p < q, %d <= q <= %d in lowest terms", fn, i, e.p, e.q, MUSICA_EDGE_MIN_Q, MUSICA_EDGE_MAX_Q);
+                                if (e.orientation > 3) return fail("%s: edge %u: orientation %u out of range [0, 3]", fn, i, e.orientation);
+                                if (with_contrast && (e.contrast == 0 || e.contrast < -MUSICA_EDGE_MAX_CONTRAST || e.contrast > MUSICA_EDGE_MAX_CONTRAST))
+                                    return fail("%s: edge %u: contrast %d is not 1 <= |contrast| <= %d", fn, i, e.contrast, MUSICA_EDGE_MAX_CONTRAST);
+                                p = {(uint32_t)e.x | ((uint32_t)e.y << 16), e.half | (e.p << 8) | (e.q << 16) | (e.orientation << 24), with_contrast ? e.contrast : 0,
+                                     (uint32_t)*words};
+                                *words += 4ull * bins;
+                                return 1;
+                            });
 }
 
 static_assert(kGratingMinHalf == MUSICA_GRATING_MIN_HALF && kGratingMaxHalf == MUSICA_GRATING_MAX_HALF && kGratingMaxU == MUSICA_GRATING_MAX_U &&
@@ -193,45 +185,120 @@ static_assert(kGratingMinHalf == MUSICA_GRATING_MIN_HALF && kGratingMaxHalf == M
               "kernels_gratings.hip's tile list, u32 pixel, LDS tables and u32 sums hold for the gratings of include/musica.h");
 static_assert(sizeof(musica_sim_grating_result) == kGratingWords * sizeof(uint64_t), "k_sim_gratings writes a musica_sim_grating_result as its u64 words");
 
-// What both grating calls refuse about a list for a plane of side n (processing.grating_list): the count, each half-side, wave vector
-// and period, plates inside the plane, plates pairwise disjoint. Fills `packed` for the device, each grating's wave (and a quarter of
-// its table's place) behind the one before it, and `periods` with the periods' sum. No device work.
+// What both grating calls refuse about a list for a plane of side n (processing.grating_list): patch_list_check with each half-side,
+// wave vector and period and the plates' reach 2 half. Each grating's wave (and a quarter of its table's place) lies behind the one
+// before it; `periods` is the periods' sum.
 static int gratings_check(const char* fn, uint32_t count, const musica_grating* gs, int n, std::vector<PackedGrating>& packed, uint64_t* periods) {
-    if (count == 0 || count > MUSICA_GRATING_MAX) return fail("%s: count %u out of range [1, %d]", fn, count, MUSICA_GRATING_MAX);
-    packed.resize(count);
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < count; i++) {
-        const musica_grating& g = gs[i];
-        if (g.half < MUSICA_GRATING_MIN_HALF || g.half > MUSICA_GRATING_MAX_HALF)
-            return fail("%s: grating %u: half-side %u out of range [%d, %d]", fn, i, g.half, MUSICA_GRATING_MIN_HALF, MUSICA_GRATING_MAX_HALF);
-        if (g.ux < -MUSICA_GRATING_MAX_U || g.ux > MUSICA_GRATING_MAX_U || g.uy < -MUSICA_GRATING_MAX_U || g.uy > MUSICA_GRATING_MAX_U ||
-            edge_gcd((uint32_t)std::abs(g.ux), (uint32_t)std::abs(g.uy)) != 1)
-            return fail("%s: grating %u: wave vector (%d, %d) is not coprime with |ux|, |uy| <= %d", fn, i, g.ux, g.uy, MUSICA_GRATING_MAX_U);
-        if (g.period < 2 || g.period > MUSICA_GRATING_MAX_PERIOD || g.period > g.half || 2 * (uint32_t)std::abs(g.ux) > g.period || 2 * (uint32_t)std::abs(g.uy) > g.period)
-            return fail("%s: grating %u: period %u is not 2 <= T <= min(%d, half) with 2 |ux|, 2 |uy| <= T", fn, i, g.period, MUSICA_GRATING_MAX_PERIOD);
-        const int64_t reach = 2 * (int64_t)g.half;
-        if (g.x - reach < 0 || g.y - reach < 0 || g.x + reach >= n || g.y + reach >= n)
-            return fail("%s: grating %u: the plate (%d, %d) +- %d leaves the %d x %d plane", fn, i, g.x, g.y, (int)reach, n, n);
-        packed[i] = {(uint32_t)g.x | ((uint32_t)g.y << 16), g.half | (g.period << 8) | (((uint32_t)g.ux & 0xFFu) << 16) | (((uint32_t)g.uy & 0xFFu) << 24), (uint32_t)at};
-        at += g.period;
-    }
-    for (uint32_t i = 0; i < count; i++)
-        for (uint32_t j = i + 1; j < count; j++) {
-            const int64_t reach = 2 * ((int64_t)gs[i].half + gs[j].half);
-            if (std::abs((int64_t)gs[i].x - gs[j].x) <= reach && std::abs((int64_t)gs[i].y - gs[j].y) <= reach)
-                return fail("%s: the plates of gratings %u and %u are not disjoint", fn, i, j);
-        }
-    *periods = at;
-    return 1;
+    *periods = 0;
+    return patch_list_check(fn, kGratingNouns, count, MUSICA_GRATING_MAX, gs, n, packed, [](const musica_grating& g) { return 2 * (int64_t)g.half; },
+                            [&](uint32_t i, const musica_grating& g, PackedGrating& p) {
+                                if (g.half < MUSICA_GRATING_MIN_HALF || g.half > MUSICA_GRATING_MAX_HALF)
+                                    return fail("%s: grating %u: half-side %u out of range [%d, %d]", fn, i, g.half, MUSICA_GRATING_MIN_HALF, MUSICA_GRATING_MAX_HALF);
+                                if (g.ux < -MUSICA_GRATING_MAX_U || g.ux > MUSICA_GRATING_MAX_U || g.uy < -MUSICA_GRATING_MAX_U || g.uy > MUSICA_GRATING_MAX_U ||
+                                    gcd_u32((uint32_t)std::abs(g.ux), (uint32_t)std::abs(g.uy)) != 1)
+                                    return fail("%s: grating %u: wave vector (%d, %d) is not coprime with |ux|, |uy| <= %d", fn, i, g.ux, g.uy, MUSICA_GRATING_MAX_U);
+                                if (g.period < 2 || g.period > MUSICA_GRATING_MAX_PERIOD || g.period > g.half || 2 * (uint32_t)std::abs(g.ux) > g.period ||
+                                    2 * (uint32_t)std::abs(g.uy) > g.period)
+                                    return fail("%s: grating %u: period %u is not 2 <= T <= min(%d, half) with 2 |ux|, 2 |uy| <= T", fn, i, g.period, MUSICA_GRATING_MAX_PERIOD);
+                                p = {(uint32_t)g.x | ((uint32_t)g.y << 16), g.half | (g.period << 8) | (((uint32_t)g.ux & 0xFFu) << 16) | (((uint32_t)g.uy & 0xFFu) << 24),
+                                     (uint32_t)*periods};
+                                *periods += g.period;
+                                return 1;
+                            });
 }
 
-// The call's list on the device, as details_upload.
-static int gratings_upload(musica_ctx* c, const char* fn, const std::vector<PackedGrating>& packed) {
-    if (!ensure(c, &c->study.d_gratings, MUSICA_GRATING_MAX)) return fail("%s: device allocation of the grating list failed", fn);
-    HIP_OK(hipMemcpyAsync(c->study.d_gratings, packed.data(), packed.size() * sizeof(PackedGrating), hipMemcpyHostToDevice, c->stream));
+// Where a relation's list calls keep their device buffers in musica_ctx::study, and how large: the list's `most` items, and for the
+// measurement `out_words` u64 of results per item and `tables_cap` u32 of tables (tables == nullptr: the measurement has none).
+template <typename Packed>
+struct PatchBuffers {
+    const char* item;
+    Packed* StudyState::*list;
+    size_t most;
+    unsigned long long* StudyState::*out;
+    size_t out_words;
+    uint32_t* StudyState::*tables;
+    size_t tables_cap;
+};
+constexpr PatchBuffers<PackedDetail> kDetailBuffers{"detail", &StudyState::d_details, MUSICA_DETAIL_MAX, &StudyState::d_detail_out, kDetailWords, nullptr, 0};
+constexpr PatchBuffers<PackedEdge> kEdgeBuffers{"edge", &StudyState::d_edges, MUSICA_EDGE_MAX, &StudyState::d_edge_out, kEdgeWords, &StudyState::d_edge_tables,
+                                                (size_t)MUSICA_EDGE_MAX * 4 * MUSICA_EDGE_BINS_MAX};
+constexpr PatchBuffers<PackedGrating> kGratingBuffers{"grating", &StudyState::d_gratings, MUSICA_GRATING_MAX, &StudyState::d_grating_out, kGratingWords,
+                                                      &StudyState::d_grating_tables, (size_t)MUSICA_GRATING_MAX * 4 * MUSICA_GRATING_MAX_PERIOD};
+
+// The call's list on the device, in the relation's buffer (allocated on first use): copied on the stream, behind the kernels that
+// still read the last call's, and `packed` is free again when this returns.
+template <typename Packed>
+static int upload_list(musica_ctx* c, const char* fn, const PatchBuffers<Packed>& bufs, const std::vector<Packed>& packed) {
+    if (!ensure(c, &(c->study.*bufs.list), bufs.most)) return fail("%s: device allocation of the %s list failed", fn, bufs.item);
+    HIP_OK(hipMemcpyAsync(c->study.*bufs.list, packed.data(), packed.size() * sizeof(Packed), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     return 1;
 }
+
+// CHECK_IMG and CHECK_CTX for the shared frames below, which name the entry point they serve
+static int check_img(const musica_ctx* c, const char* fn, uint32_t idx) {
+    return (int)idx >= c->B ? fail("%s: image_index %u >= batch %d", fn, (unsigned)idx, c->B) : 1;
+}
+static int check_ctx(const musica_ctx* c, const char* fn) { return hipSetDevice(c->p.device) != hipSuccess ? fail("%s: hipSetDevice failed", fn) : 1; }
+
+// The three list measurements (musica_sim_details / _edges / _gratings), in the manner of sim_derive_slot. `null`: the text of the
+// call's NULL-argument refusal where an argument is NULL, else nullptr. list(side, packed, words): the call's *_check for the output
+// plane (words: what its tables take). launch(a plane, a pitch, b plane, b pitch, list, results, tables). The results come back as
+// `count` Result, the tables' `words` u32 into `tables`.
+template <typename Packed, typename Result, typename List, typename Launch>
+static int sim_patch_list(musica_ctx* c, const char* fn, const char* null, uint32_t idx, uint32_t slot, uint32_t count, const PatchBuffers<Packed>& bufs,
+                          List list, Launch launch, Result* out, uint32_t* tables, uint64_t table_words) {
+    if (!c) return fail("%s: ctx is NULL", fn);
+    if (null) return fail("%s: %s is NULL", fn, null);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("%s: image too small for the %d-pixel margin", fn, MUSICA_OUT_MARGIN);
+    if (slot >= MUSICA_SIM_SLOTS) return fail("%s: slot %u >= %d", fn, slot, MUSICA_SIM_SLOTS);
+    if (!c->study.written[slot]) return fail("%s: slot %u was never written", fn, slot);
+    if (!check_img(c, fn, idx)) return 0;
+    std::vector<Packed> packed;
+    uint64_t words = 0;
+    if (!list((int)sim_side(c), packed, words)) return 0;
+    if (bufs.tables && table_words < words)
+        return fail("%s: table_words %llu is less than the %llu words of the tables", fn, (unsigned long long)table_words, (unsigned long long)words);
+    if (!check_ctx(c, fn)) return 0;
+    StudyState& st = c->study;
+    if (!(ensure(c, &(st.*bufs.out), bufs.most * bufs.out_words) && (!bufs.tables || ensure(c, &(st.*bufs.tables), bufs.tables_cap))))
+        return fail("%s: device allocation failed", fn);
+    if (!upload_list(c, fn, bufs, packed)) return 0;
+    const int pitch = c->lv[0].pitch;
+    uint32_t* d_tables = bufs.tables ? st.*bufs.tables : nullptr;
+    launch(image_slice(c, c->d_graded, idx) + (size_t)MUSICA_OUT_MARGIN * pitch + MUSICA_OUT_MARGIN, pitch, st.slot[slot], (int)sim_side(c), st.*bufs.list,
+           st.*bufs.out, d_tables);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out, st.*bufs.out, (size_t)count * sizeof(Result), hipMemcpyDeviceToHost, c->stream));
+    if (bufs.tables) HIP_OK(hipMemcpyAsync(tables, d_tables, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+// Before an alteration writes into d_input: when the last step read d_input, keep it for the getters that recompute from the input.
+static int alter_keep_input(musica_ctx* c, const char* fn) {
+    if (c->cur_input != c->d_input) return 1;
+    const size_t nn = (size_t)c->N * c->N;
+    if (!ensure(c, &c->d_input_kept, (size_t)c->B * nn)) return fail("%s: device allocation failed", fn);
+    HIP_OK(hipMemcpyAsync(c->d_input_kept, c->d_input, (size_t)c->B * nn * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
+    c->cur_input = c->d_input_kept;
+    return 1;
+}
+
+// The alterations that have an entry point of their own, every one a launch from the source plane into image idx of the input buffer.
+// `null`: the text of the call's NULL-argument refusal where an argument is NULL, else nullptr. check(): what the call refuses about
+// its other arguments (1, or fail(...)), no device work. prepare(): its device buffers and uploads (1, or fail(...)). launch(src, dst).
+template <typename Check, typename Prepare, typename Launch>
+static int alter_into(musica_ctx* c, const char* fn, const char* null, uint32_t idx, Check check, Prepare prepare, Launch launch) {
+    if (!c) return fail("%s: ctx is NULL", fn);
+    if (null) return fail("%s: %s is NULL", fn, null);
+    if (!c->study.d_alter_src) return fail("%s: no source plane (musica_alter_set_source)", fn);
+    if (!check() || !check_img(c, fn, idx) || !check_ctx(c, fn) || !prepare() || !alter_keep_input(c, fn)) return 0;
+    launch(c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+static int nothing() { return 1; }
 
 // harness.ssim_similarity: c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2 (float ** is C pow); cov_norm = npx / (npx - 1)
 static SimConsts sim_consts() {
@@ -715,89 +782,47 @@ int musica_sim_multiscale(musica_ctx* c, uint32_t count, const musica_sim_query*
     ABI_CATCH("musica_sim_multiscale")
 }
 
-// ---- the contrast-detail measurement (musica_sim_details, include/musica.h; kernels_details.hip) ----------------------------------------
+// ---- the list measurements (musica_sim_details / _edges / _gratings, include/musica.h; kernels_details.hip, kernels_edges.hip, kernels_gratings.hip)
 int musica_sim_details(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count, const musica_detail* details, musica_sim_detail_result* out) {
     ABI_TRY
-    if (!c) return fail("musica_sim_details: ctx is NULL");
-    if (!details || !out) return fail("musica_sim_details: details or results is NULL");
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_details: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
-    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_details: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
-    if (!c->study.written[slot]) return fail("musica_sim_details: slot %u was never written", slot);
-    CHECK_IMG(c, idx);
-    std::vector<PackedDetail> packed;
-    if (!details_check("musica_sim_details", count, details, (int)sim_side(c), false, packed)) return 0;
-    CHECK_CTX(c);
-    StudyState& st = c->study;
-    if (!ensure(c, &st.d_detail_out, (size_t)MUSICA_DETAIL_MAX * kDetailWords)) return fail("musica_sim_details: device allocation failed");
-    if (!details_upload(c, "musica_sim_details", packed)) return 0;
-    const int pitch = c->lv[0].pitch;
-    launch_sim_details(c->stream, image_slice(c, c->d_graded, idx) + (size_t)MUSICA_OUT_MARGIN * pitch + MUSICA_OUT_MARGIN, pitch, st.slot[slot],
-                       (int)sim_side(c), st.d_details, (int)count, st.d_detail_out);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(out, st.d_detail_out, (size_t)count * sizeof(musica_sim_detail_result), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
+    return sim_patch_list(
+        c, "musica_sim_details", !details || !out ? "details or results" : nullptr, idx, slot, count, kDetailBuffers,
+        [&](int n, std::vector<PackedDetail>& packed, uint64_t&) { return details_check("musica_sim_details", count, details, n, false, packed); },
+        [&](const float* a, int a_pitch, const uint8_t* b, int b_pitch, const PackedDetail* list, unsigned long long* results, uint32_t*) {
+            launch_sim_details(c->stream, a, a_pitch, b, b_pitch, list, (int)count, results);
+        },
+        out, nullptr, 0);
     ABI_CATCH("musica_sim_details")
 }
 
-// ---- the edge-response measurement (musica_sim_edges, include/musica.h; kernels_edges.hip) ---------------------------------------------
 int musica_sim_edges(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count, const musica_edge* edges, musica_sim_edge_result* out, uint32_t* tables,
                      uint64_t table_words) {
     ABI_TRY
-    if (!c) return fail("musica_sim_edges: ctx is NULL");
-    if (!edges || !out || !tables) return fail("musica_sim_edges: edges, results or tables is NULL");
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_edges: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
-    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_edges: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
-    if (!c->study.written[slot]) return fail("musica_sim_edges: slot %u was never written", slot);
-    CHECK_IMG(c, idx);
-    std::vector<PackedEdge> packed;
-    uint64_t words = 0;
-    if (!edges_check("musica_sim_edges", count, edges, (int)sim_side(c), false, packed, &words)) return 0;
-    if (table_words < words) return fail("musica_sim_edges: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
-    CHECK_CTX(c);
-    StudyState& st = c->study;
-    if (!(ensure(c, &st.d_edge_out, (size_t)MUSICA_EDGE_MAX * kEdgeWords) && ensure(c, &st.d_edge_tables, (size_t)MUSICA_EDGE_MAX * 4 * MUSICA_EDGE_BINS_MAX)))
-        return fail("musica_sim_edges: device allocation failed");
-    if (!edges_upload(c, "musica_sim_edges", packed)) return 0;
-    const int pitch = c->lv[0].pitch;
-    launch_sim_edges(c->stream, image_slice(c, c->d_graded, idx) + (size_t)MUSICA_OUT_MARGIN * pitch + MUSICA_OUT_MARGIN, pitch, st.slot[slot],
-                     (int)sim_side(c), st.d_edges, (int)count, st.d_edge_out, st.d_edge_tables);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(out, st.d_edge_out, (size_t)count * sizeof(musica_sim_edge_result), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(tables, st.d_edge_tables, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
+    return sim_patch_list(
+        c, "musica_sim_edges", !edges || !out || !tables ? "edges, results or tables" : nullptr, idx, slot, count, kEdgeBuffers,
+        [&](int n, std::vector<PackedEdge>& packed, uint64_t& words) { return edges_check("musica_sim_edges", count, edges, n, false, packed, &words); },
+        [&](const float* a, int a_pitch, const uint8_t* b, int b_pitch, const PackedEdge* list, unsigned long long* results, uint32_t* d_tables) {
+            launch_sim_edges(c->stream, a, a_pitch, b, b_pitch, list, (int)count, results, d_tables);
+        },
+        out, tables, table_words);
     ABI_CATCH("musica_sim_edges")
 }
 
-// ---- the grating measurement (musica_sim_gratings, include/musica.h; kernels_gratings.hip) ---------------------------------------------
 int musica_sim_gratings(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count, const musica_grating* gratings, musica_sim_grating_result* out,
                         uint32_t* tables, uint64_t table_words) {
     ABI_TRY
-    if (!c) return fail("musica_sim_gratings: ctx is NULL");
-    if (!gratings || !out || !tables) return fail("musica_sim_gratings: gratings, results or tables is NULL");
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_gratings: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
-    if (slot >= MUSICA_SIM_SLOTS) return fail("musica_sim_gratings: slot %u >= %d", slot, MUSICA_SIM_SLOTS);
-    if (!c->study.written[slot]) return fail("musica_sim_gratings: slot %u was never written", slot);
-    CHECK_IMG(c, idx);
-    std::vector<PackedGrating> packed;
-    uint64_t periods = 0;
-    if (!gratings_check("musica_sim_gratings", count, gratings, (int)sim_side(c), packed, &periods)) return 0;
-    const uint64_t words = 4 * periods;
-    if (table_words < words) return fail("musica_sim_gratings: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
-    CHECK_CTX(c);
-    StudyState& st = c->study;
-    if (!(ensure(c, &st.d_grating_out, (size_t)MUSICA_GRATING_MAX * kGratingWords) && ensure(c, &st.d_grating_tables, (size_t)MUSICA_GRATING_MAX * 4 * MUSICA_GRATING_MAX_PERIOD)))
-        return fail("musica_sim_gratings: device allocation failed");
-    if (!gratings_upload(c, "musica_sim_gratings", packed)) return 0;
-    const int pitch = c->lv[0].pitch;
-    launch_sim_gratings(c->stream, image_slice(c, c->d_graded, idx) + (size_t)MUSICA_OUT_MARGIN * pitch + MUSICA_OUT_MARGIN, pitch, st.slot[slot],
-                        (int)sim_side(c), st.d_gratings, (int)count, st.d_grating_out, st.d_grating_tables);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(out, st.d_grating_out, (size_t)count * sizeof(musica_sim_grating_result), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(tables, st.d_grating_tables, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 1;
+    return sim_patch_list(
+        c, "musica_sim_gratings", !gratings || !out || !tables ? "gratings, results or tables" : nullptr, idx, slot, count, kGratingBuffers,
+        [&](int n, std::vector<PackedGrating>& packed, uint64_t& words) {
+            uint64_t periods = 0;
+            const int ok = gratings_check("musica_sim_gratings", count, gratings, n, packed, &periods);
+            words = 4 * periods;
+            return ok;
+        },
+        [&](const float* a, int a_pitch, const uint8_t* b, int b_pitch, const PackedGrating* list, unsigned long long* results, uint32_t* d_tables) {
+            launch_sim_gratings(c->stream, a, a_pitch, b, b_pitch, list, (int)count, results, d_tables);
+        },
+        out, tables, table_words);
     ABI_CATCH("musica_sim_gratings")
 }
 
@@ -1143,16 +1168,6 @@ static int alter_args(musica_ctx* c, const char* fn, const musica_alteration* s,
     return 1;
 }
 
-// Before an alteration writes into d_input: when the last step read d_input, keep it for the getters that recompute from the input.
-static int alter_keep_input(musica_ctx* c, const char* fn) {
-    if (c->cur_input != c->d_input) return 1;
-    const size_t nn = (size_t)c->N * c->N;
-    if (!ensure(c, &c->d_input_kept, (size_t)c->B * nn)) return fail("%s: device allocation failed", fn);
-    HIP_OK(hipMemcpyAsync(c->d_input_kept, c->d_input, (size_t)c->B * nn * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
-    c->cur_input = c->d_input_kept;
-    return 1;
-}
-
 int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
     if (!c) return fail("musica_alter: ctx is NULL");
     AlterDev a;
@@ -1178,118 +1193,86 @@ int musica_alter(musica_ctx* c, uint32_t idx, const musica_alteration* s) {
 }
 
 int musica_alter_blur(musica_ctx* c, uint32_t idx, uint32_t radius) {
-    if (!c) return fail("musica_alter_blur: ctx is NULL");
-    if (!c->study.d_alter_src) return fail("musica_alter_blur: no source plane (musica_alter_set_source)");
-    if (radius < 1 || radius > MUSICA_BLUR_MAX_RADIUS) return fail("musica_alter_blur: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS);
-    CHECK_IMG(c, idx);
-    CHECK_CTX(c);
-    if (!alter_keep_input(c, "musica_alter_blur")) return 0;
-    launch_blur_u16(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, (int)radius);   // kernels_blur.hip
-    HIP_OK(hipGetLastError());
-    return 1;
+    return alter_into(
+        c, "musica_alter_blur", nullptr, idx,
+        [&] { return radius < 1 || radius > MUSICA_BLUR_MAX_RADIUS ? fail("musica_alter_blur: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS) : 1; },
+        nothing, [&](const uint16_t* src, uint16_t* dst) { launch_blur_u16(c->stream, src, dst, c->N, (int)radius); });   // kernels_blur.hip
 }
 
 int musica_alter_zoom(musica_ctx* c, uint32_t idx, uint32_t p, uint32_t q) {
-    if (!c) return fail("musica_alter_zoom: ctx is NULL");
-    if (!c->study.d_alter_src) return fail("musica_alter_zoom: no source plane (musica_alter_set_source)");
-    if (!zoom_check("musica_alter_zoom", p, q)) return 0;
-    CHECK_IMG(c, idx);
-    CHECK_CTX(c);
-    if (!alter_keep_input(c, "musica_alter_zoom")) return 0;
-    launch_zoom_u16(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, (int)p, (int)q);   // kernels_zoom.hip
-    HIP_OK(hipGetLastError());
-    return 1;
+    return alter_into(c, "musica_alter_zoom", nullptr, idx, [&] { return zoom_check("musica_alter_zoom", p, q); }, nothing,
+                      [&](const uint16_t* src, uint16_t* dst) { launch_zoom_u16(c->stream, src, dst, c->N, (int)p, (int)q); });   // kernels_zoom.hip
 }
 
 int musica_alter_scatter(musica_ctx* c, uint32_t idx, uint32_t radius, uint32_t num, uint32_t den) {
-    if (!c) return fail("musica_alter_scatter: ctx is NULL");
-    if (!c->study.d_alter_src) return fail("musica_alter_scatter: no source plane (musica_alter_set_source)");
-    if (!scatter_check("musica_alter_scatter", radius, num, den)) return 0;
-    CHECK_IMG(c, idx);
-    CHECK_CTX(c);
-    if (!scatter_plane(c, "musica_alter_scatter")) return 0;
-    if (!alter_keep_input(c, "musica_alter_scatter")) return 0;
-    launch_scatter_u16(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->study.d_scatter, c->N, (int)radius, (int)num,
-                       (int)den);   // kernels_scatter.hip
-    HIP_OK(hipGetLastError());
-    return 1;
+    return alter_into(c, "musica_alter_scatter", nullptr, idx, [&] { return scatter_check("musica_alter_scatter", radius, num, den); },
+                      [&] { return scatter_plane(c, "musica_alter_scatter"); }, [&](const uint16_t* src, uint16_t* dst) {
+                          launch_scatter_u16(c->stream, src, dst, c->study.d_scatter, c->N, (int)radius, (int)num, (int)den);   // kernels_scatter.hip
+                      });
 }
 
 int musica_alter_details(musica_ctx* c, uint32_t idx, uint32_t count, const musica_detail* details) {
     ABI_TRY
-    if (!c) return fail("musica_alter_details: ctx is NULL");
-    if (!details) return fail("musica_alter_details: details is NULL");
-    if (!c->study.d_alter_src) return fail("musica_alter_details: no source plane (musica_alter_set_source)");
-    CHECK_IMG(c, idx);
     std::vector<PackedDetail> packed;
-    if (!details_check("musica_alter_details", count, details, c->N, true, packed)) return 0;
-    CHECK_CTX(c);
-    if (!details_upload(c, "musica_alter_details", packed)) return 0;
-    if (!alter_keep_input(c, "musica_alter_details")) return 0;
-    launch_alter_details(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, c->study.d_details, (int)count);   // kernels_details.hip
-    HIP_OK(hipGetLastError());
-    return 1;
+    return alter_into(
+        c, "musica_alter_details", !details ? "details" : nullptr, idx, [&] { return details_check("musica_alter_details", count, details, c->N, true, packed); },
+        [&] { return upload_list(c, "musica_alter_details", kDetailBuffers, packed); },
+        [&](const uint16_t* src, uint16_t* dst) { launch_alter_details(c->stream, src, dst, c->N, c->study.d_details, (int)count); });   // kernels_details.hip
     ABI_CATCH("musica_alter_details")
 }
 
 int musica_alter_edges(musica_ctx* c, uint32_t idx, uint32_t count, const musica_edge* edges) {
     ABI_TRY
-    if (!c) return fail("musica_alter_edges: ctx is NULL");
-    if (!edges) return fail("musica_alter_edges: edges is NULL");
-    if (!c->study.d_alter_src) return fail("musica_alter_edges: no source plane (musica_alter_set_source)");
-    CHECK_IMG(c, idx);
     std::vector<PackedEdge> packed;
     uint64_t words = 0;
-    if (!edges_check("musica_alter_edges", count, edges, c->N, true, packed, &words)) return 0;
-    CHECK_CTX(c);
-    if (!edges_upload(c, "musica_alter_edges", packed)) return 0;
-    if (!alter_keep_input(c, "musica_alter_edges")) return 0;
-    launch_alter_edges(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, c->study.d_edges, (int)count);   // kernels_edges.hip
-    HIP_OK(hipGetLastError());
-    return 1;
+    return alter_into(
+        c, "musica_alter_edges", !edges ? "edges" : nullptr, idx, [&] { return edges_check("musica_alter_edges", count, edges, c->N, true, packed, &words); },
+        [&] { return upload_list(c, "musica_alter_edges", kEdgeBuffers, packed); },
+        [&](const uint16_t* src, uint16_t* dst) { launch_alter_edges(c->stream, src, dst, c->N, c->study.d_edges, (int)count); });   // kernels_edges.hip
     ABI_CATCH("musica_alter_edges")
 }
 
 int musica_alter_gratings(musica_ctx* c, uint32_t idx, uint32_t count, const musica_grating* gratings, const int16_t* waves, uint64_t wave_words) {
     ABI_TRY
-    if (!c) return fail("musica_alter_gratings: ctx is NULL");
-    if (!gratings || !waves) return fail("musica_alter_gratings: gratings or waves is NULL");
-    if (!c->study.d_alter_src) return fail("musica_alter_gratings: no source plane (musica_alter_set_source)");
-    CHECK_IMG(c, idx);
     std::vector<PackedGrating> packed;
     uint64_t periods = 0;
-    if (!gratings_check("musica_alter_gratings", count, gratings, c->N, packed, &periods)) return 0;
-    if (wave_words < periods) return fail("musica_alter_gratings: wave_words %llu is less than the %llu entries of the waves", (unsigned long long)wave_words, (unsigned long long)periods);
-    for (uint64_t i = 0; i < periods; i++)
-        if (waves[i] < -MUSICA_GRATING_MAX_CONTRAST || waves[i] > MUSICA_GRATING_MAX_CONTRAST)
-            return fail("musica_alter_gratings: wave entry %llu is %d, beyond +-%d", (unsigned long long)i, (int)waves[i], MUSICA_GRATING_MAX_CONTRAST);
-    CHECK_CTX(c);
-    if (!ensure(c, &c->study.d_grating_waves, (size_t)MUSICA_GRATING_MAX * MUSICA_GRATING_MAX_PERIOD)) return fail("musica_alter_gratings: device allocation of the waves failed");
-    HIP_OK(hipMemcpyAsync(c->study.d_grating_waves, waves, (size_t)periods * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-    if (!gratings_upload(c, "musica_alter_gratings", packed)) return 0;   // synchronises: the caller's waves have been read
-    if (!alter_keep_input(c, "musica_alter_gratings")) return 0;
-    launch_alter_gratings(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, c->study.d_gratings, c->study.d_grating_waves, (int)count);   // kernels_gratings.hip
-    HIP_OK(hipGetLastError());
-    return 1;
+    return alter_into(
+        c, "musica_alter_gratings", !gratings || !waves ? "gratings or waves" : nullptr, idx,
+        [&] {
+            if (!gratings_check("musica_alter_gratings", count, gratings, c->N, packed, &periods)) return 0;
+            if (wave_words < periods)
+                return fail("musica_alter_gratings: wave_words %llu is less than the %llu entries of the waves", (unsigned long long)wave_words, (unsigned long long)periods);
+            for (uint64_t i = 0; i < periods; i++)
+                if (waves[i] < -MUSICA_GRATING_MAX_CONTRAST || waves[i] > MUSICA_GRATING_MAX_CONTRAST)
+                    return fail("musica_alter_gratings: wave entry %llu is %d, beyond +-%d", (unsigned long long)i, (int)waves[i], MUSICA_GRATING_MAX_CONTRAST);
+            return 1;
+        },
+        [&] {
+            if (!ensure(c, &c->study.d_grating_waves, (size_t)MUSICA_GRATING_MAX * MUSICA_GRATING_MAX_PERIOD))
+                return fail("musica_alter_gratings: device allocation of the waves failed");
+            HIP_OK(hipMemcpyAsync(c->study.d_grating_waves, waves, (size_t)periods * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+            return upload_list(c, "musica_alter_gratings", kGratingBuffers, packed);   // synchronises: the caller's waves have been read
+        },
+        [&](const uint16_t* src, uint16_t* dst) {
+            launch_alter_gratings(c->stream, src, dst, c->N, c->study.d_gratings, c->study.d_grating_waves, (int)count);   // kernels_gratings.hip
+        });
     ABI_CATCH("musica_alter_gratings")
 }
 
 int musica_alter_gain(musica_ctx* c, uint32_t idx, const uint16_t* gx, const uint16_t* gy) {
     ABI_TRY
-    if (!c) return fail("musica_alter_gain: ctx is NULL");
-    if (!gx || !gy) return fail("musica_alter_gain: gx or gy is NULL");
-    if (!c->study.d_alter_src) return fail("musica_alter_gain: no source plane (musica_alter_set_source)");
-    CHECK_IMG(c, idx);
-    CHECK_CTX(c);
-    if (!(ensure(c, &c->study.d_gain_x, (size_t)c->N) && ensure(c, &c->study.d_gain_y, (size_t)c->N))) return fail("musica_alter_gain: device allocation of the tables failed");
-    const std::vector<uint32_t> wide(gy, gy + c->N);   // the kernel fetches a row's gain on the scalar side: u32
-    HIP_OK(hipMemcpyAsync(c->study.d_gain_x, gx, (size_t)c->N * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->study.d_gain_y, wide.data(), (size_t)c->N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));   // the caller's tables and `wide` have been read
-    if (!alter_keep_input(c, "musica_alter_gain")) return 0;
-    launch_alter_gain(c->stream, c->study.d_alter_src, c->d_input + idx * (size_t)c->N * c->N, c->N, c->study.d_gain_x, c->study.d_gain_y);   // kernels_gain.hip
-    HIP_OK(hipGetLastError());
-    return 1;
+    return alter_into(
+        c, "musica_alter_gain", !gx || !gy ? "gx or gy" : nullptr, idx, nothing,
+        [&] {
+            if (!(ensure(c, &c->study.d_gain_x, (size_t)c->N) && ensure(c, &c->study.d_gain_y, (size_t)c->N)))
+                return fail("musica_alter_gain: device allocation of the tables failed");
+            const std::vector<uint32_t> wide(gy, gy + c->N);   // the kernel fetches a row's gain on the scalar side: u32
+            HIP_OK(hipMemcpyAsync(c->study.d_gain_x, gx, (size_t)c->N * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipMemcpyAsync(c->study.d_gain_y, wide.data(), (size_t)c->N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipStreamSynchronize(c->stream));   // the caller's tables and `wide` have been read
+            return 1;
+        },
+        [&](const uint16_t* src, uint16_t* dst) { launch_alter_gain(c->stream, src, dst, c->N, c->study.d_gain_x, c->study.d_gain_y); });   // kernels_gain.hip
     ABI_CATCH("musica_alter_gain")
 }
 

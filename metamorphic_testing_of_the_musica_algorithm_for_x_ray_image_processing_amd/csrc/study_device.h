@@ -1,7 +1,11 @@
 // study_device.h — what the study's kernels share on the device (kernels_similarity.hip, kernels_scales.hip, kernels_joint.hip,
-// kernels_displace.hip, kernels_covariance.hip, kernels_ensemble.hip): the address-space typedefs, the reductions and their ONE order,
-// the 64 x 64 tile of a region, the packed byte windows of k_displace and k_cov_add, and the per-window SSIM terms.
+// kernels_displace.hip, kernels_covariance.hip, kernels_ensemble.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip,
+// kernels_gain.hip): the address-space typedefs, the reductions and their ONE order, the 64 x 64 tile of a region, the pixel words of
+// the kernels that stream a u16 plane and the insertion body of the patch relations (insert_patches), the packed byte windows of
+// k_displace and k_cov_add, and the per-window SSIM terms.
 #pragma once
+
+#include <type_traits>
 
 #include "kernels_common.h"
 #include "launchers.h"
@@ -90,6 +94,113 @@ __device__ __forceinline__ TileGeom tile_geom(int tile, int tiles_x, int w, int 
     const int x0 = tx * kSimTile, y0 = ty * kSimTile;
     return {x0, y0, min(kSimTile, w - x0), min(kSimTile, h - y0)};
 }
+
+// ---- pixel words (k_alter_details, k_alter_edges, k_alter_gratings, k_alter_gain) ---------------------------------------------------
+// A thread of these kernels moves chunks of V consecutive u16 pixels of a row with one load and one store: V = 8 (16 bytes) where the
+// side is a multiple of 8 and every plane is 16-byte aligned, else 2 under the same condition for 4 bytes, else single pixels (image 1
+// of a batch with odd N^2 starts on a 2-byte boundary only). With n % V == 0 a chunk starts inside the plane or lies outside it entirely.
+template <int V> struct PixelWord;
+template <> struct PixelWord<8> { typedef uint4 type; };
+template <> struct PixelWord<2> { typedef uint32_t type; };
+template <> struct PixelWord<1> { typedef uint16_t type; };
+template <int V>
+union PixelChunk {
+    typename PixelWord<V>::type w;
+    uint16_t px[V];
+};
+
+// n % v == 0 and every plane (or table read a chunk at a time) aligned to 2 v bytes
+template <typename... P>
+inline bool pixels_aligned(int n, int v, const P*... planes) {
+    return n % v == 0 && ((reinterpret_cast<uintptr_t>(planes) % (2 * v) == 0) && ...);
+}
+
+// launch(std::integral_constant<int, V>) for the widest V the side and the planes allow
+template <typename Launch, typename... P>
+inline void launch_by_width(Launch&& launch, int n, const P*... planes) {
+    if (pixels_aligned(n, 8, planes...)) launch(std::integral_constant<int, 8>());
+    else if (pixels_aligned(n, 2, planes...)) launch(std::integral_constant<int, 2>());
+    else launch(std::integral_constant<int, 1>());
+}
+
+// ---- the insertion body of the patch relations (k_alter_details, k_alter_edges, k_alter_gratings) ---------------------------------
+// ONE launch, 2 B read + 2 B written per pixel: a pixel inside a listed patch is changed by the relation's rule, every other pixel is
+// copied. The patches of a list (discs in their boxes, plates) lie inside the plane and are pairwise disjoint (the callers check), so a
+// pixel belongs to at most one. A workgroup of kStudyThreads threads owns a 64 x 64 tile of the plane (tile_geom).
+//   bin      the threads stride over the packed list and append to an LDS list the patches whose square (centre +- Entry::r) meets the
+//            tile, through an LDS counter; the order of the appends does not matter because a pixel meets at most one patch. The
+//            relation's file argues and asserts the CAPACITY R::kTileCap of a tile's list; an append past it would be dropped, never
+//            written.
+//   stage    a relation may stage more behind the list, in LDS of its own (R::stage: the gratings' waves).
+//   stream   a thread moves chunks of V consecutive pixels of a row (pixel words above); consecutive lanes take consecutive chunks.
+//            Two passes, unrolled: every load of a thread is in flight before the first is used. A tile with an empty list is a pure
+//            copy; elsewhere a chunk is tested against the listed patches' squares first and only the chunks that meet one set up the
+//            relation's row state (R::row) and apply its rule to their V pixels (R::pixel).
+// Nothing outside the two planes (and what R::stage reads) is read, nothing outside `out` written; the planes must not overlap.
+// A relation R supplies: Packed, the list's item as it travels; Entry, its LDS form, which begins with int x, y, r (the centre in tile
+// coordinates and the reach of the square); kTileCap; meets(packed, tile, entry&): whether the item meets the tile, and if so its entry;
+// stage(list, m, extra...) -> Staged (empty where there is nothing to stage); Row and row(entry, j, dy, tx, staged): the state of a
+// chunk at tile column tx of the row dy below the centre of patch j; pixel(entry, row&, dx, px&): pixel dx right of the centre.
+template <typename R, int V, typename... Extra>
+__device__ __forceinline__ void insert_patches(const uint16_t* __restrict__ src, uint16_t* __restrict__ out, int n,
+                                               const typename R::Packed* __restrict__ items, int count, Extra... extra) {
+    typedef typename PixelWord<V>::type __attribute__((may_alias)) Word;
+    typedef typename R::Entry Entry;
+    constexpr int ROW = kSimTile / V;                            // chunks per tile row
+    constexpr int TRIPS = kSimTile * ROW / kStudyThreads;        // chunks per thread
+    __shared__ Entry list[R::kTileCap];
+    __shared__ int listed;
+    const int tiles = (n + kSimTile - 1) / kSimTile;
+    const TileGeom t = tile_geom(blockIdx.x, tiles, n, n);
+    if (threadIdx.x == 0) listed = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < count; i += kStudyThreads) {
+        // The item whole, before the test: a field fetched behind the test is a second load that is still pending where the test fails,
+        // and the wait for it then lands behind the first chunk's store (0.45 us of k_alter_edges<8> at 3072^2).
+        const typename R::Packed p = items[i];
+        Entry e;
+        if (!R::meets(p, t, e)) continue;
+        const int slot = atomicAdd(&listed, 1);
+        if (slot < R::kTileCap) list[slot] = e;
+    }
+    __syncthreads();
+    const int m = min(listed, R::kTileCap);
+    const typename R::Staged staged = R::stage(list, m, extra...);
+
+    PixelChunk<V> loaded[TRIPS];
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+        const int e = k * kStudyThreads + (int)threadIdx.x;
+        const int ty = e / ROW, tx = (e - ty * ROW) * V;
+        if (ty < t.th && tx < t.tw) loaded[k].w = *reinterpret_cast<const Word*>(src + (size_t)(t.y0 + ty) * n + (t.x0 + tx));
+    }
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+        const int e = k * kStudyThreads + (int)threadIdx.x;
+        const int ty = e / ROW, tx = (e - ty * ROW) * V;
+        if (!(ty < t.th && tx < t.tw)) continue;
+        PixelChunk<V> v = loaded[k];
+        for (int j = 0; j < m; j++) {   // m is the same in every lane; 0 in most tiles
+            const Entry d = list[j];
+            const int dy = ty - d.y;
+            if (dy < -d.r || dy > d.r || tx + V - 1 < d.x - d.r || tx > d.x + d.r) continue;
+            typename R::Row row = R::row(d, j, dy, tx, staged);
+#pragma unroll
+            for (int q = 0; q < V; q++) R::pixel(d, row, tx + q - d.x, v.px[q]);
+        }
+        *reinterpret_cast<Word*>(out + (size_t)(t.y0 + ty) * n + (t.x0 + tx)) = v.w;
+    }
+}
+
+// What the launchers of the three kernels share: one workgroup per tile, the widest V
+template <typename Launch>
+inline void launch_insert(Launch&& launch, const uint16_t* src, uint16_t* out, int n) {
+    const unsigned tiles = (unsigned)((n + kSimTile - 1) / kSimTile);
+    launch_by_width([&](auto v) { launch(v, dim3(tiles * tiles), dim3(kStudyThreads)); }, n, src, out);
+}
+
+// Whether the square centre (x, y) +- r, in tile coordinates, meets the tile
+__device__ __forceinline__ bool square_meets(int x, int y, int r, const TileGeom& t) { return !(x + r < 0 || x - r >= t.tw || y + r < 0 || y - r >= t.th); }
 
 // ---- packed byte windows (k_displace, k_cov_add) -------------------------------------------------------------------------------------
 // Both kernels hold a tile as packed bytes, 16 words per row at a 16-byte aligned pitch, and the window their candidates / lags reach

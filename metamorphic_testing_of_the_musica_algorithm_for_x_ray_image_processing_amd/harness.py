@@ -58,6 +58,35 @@ def SCATTERS(n):
     return tuple((r, a, b) for a, b in SCATTER_FRACTIONS)
 
 
+def _patch_grid(n, sizes, defaults, side, cap, what, item):
+    """The grid detail_grid, edge_grid and grating_grid share, for a raw image of side n: G x G square patches on a square grid inside
+    the output plane's footprint. With B = PROCESSING_MARGIN and m = n - 2B, `sizes` defaults to the longest prefix of `defaults` of
+    length k with m // side(its last) >= k; G = min(m // (the largest side), cap) // k * k (ValueError if 0, naming the sizes as
+    `what`), the cell C = m // G, and patch (i, j), i, j < G, row i first, is item(B + j C + C // 2, B + i C + C // 2,
+    sizes[(i + j) % k], i G + j): the diagonal assignment puts every size G / k times in every row and every column of the grid, so
+    in every band of the frame. A patch has side(size) <= C, so the patches are disjoint and lie inside [B, n - B)^2: shifted by -B
+    (_output_patches) the list is valid for the output plane."""
+    n, b = int(n), PROCESSING_MARGIN
+    m = n - 2 * b
+    if sizes is None:
+        k = 0
+        while k < len(defaults) and m // side(defaults[k]) >= k + 1:
+            k += 1
+        sizes = defaults[:k]
+    sizes = tuple(int(v) for v in sizes)
+    k = len(sizes)
+    g = min(m // max(side(v) for v in sizes), cap) // k * k if k else 0
+    if g <= 0:
+        raise ValueError("a side of %d pixels holds no grid of the %s %r" % (n, what, sizes))
+    c = m // g
+    return [item(b + j * c + c // 2, b + i * c + c // 2, sizes[(i + j) % k], i * g + j) for i in range(g) for j in range(g)]
+
+
+def _output_patches(items):
+    """A raw plane's patches (x, y, ...) in the coordinates of the output plane (the frame cropped by PROCESSING_MARGIN on every side)."""
+    return tuple((t[0] - PROCESSING_MARGIN, t[1] - PROCESSING_MARGIN) + tuple(t[2:]) for t in items)
+
+
 # not in the reference: the contrast-detail rows (insert_details), rows cd_<c> of a study run with `details`: discs of the radii
 # DETAIL_RADII on a grid (detail_grid), one row per contrast c / 1024 = 0.8 % .. 12.5 %, five strengths as every alteration of the
 # reference's script has. DETAILS(n) gives the five grids of the image size.
@@ -66,31 +95,15 @@ DETAIL_CONTRASTS = (8, 16, 32, 64, 128)
 
 
 def detail_grid(n, contrast, radii=None):
-    """The study's contrast-detail phantom for a raw image of side n: G x G details of one contrast on a square grid inside the output
-    plane's footprint. With B = PROCESSING_MARGIN and m = n - 2B, `radii` defaults to the longest prefix of DETAIL_RADII of length k
-    with m // (4 r_last + 5) >= k; G = min(m // (4 r_max + 5), 32) // k * k (ValueError if 0), the cell C = m // G, and detail (i, j),
-    i, j < G, row i first, is (B + j C + C // 2, B + i C + C // 2, radii[(i + j) % k], contrast): the diagonal assignment puts every
-    radius G / k times in every row and every column of the grid, so in every band of the frame. A box has side 4r + 5 <= C, so the
-    boxes are disjoint and lie inside [B, n - B)^2: shifted by -B (output_details) the list is valid for the output plane."""
-    n, b = int(n), PROCESSING_MARGIN
-    m = n - 2 * b
-    if radii is None:
-        k = 0
-        while k < len(DETAIL_RADII) and m // (4 * DETAIL_RADII[k] + 5) >= k + 1:
-            k += 1
-        radii = DETAIL_RADII[:k]
-    radii = tuple(int(r) for r in radii)
-    k = len(radii)
-    g = min(m // (4 * max(radii) + 5), 32) // k * k if k else 0
-    if g <= 0:
-        raise ValueError("a side of %d pixels holds no grid of the radii %r" % (n, radii))
-    c = m // g
-    return mp.detail_list([(b + j * c + c // 2, b + i * c + c // 2, radii[(i + j) % k], contrast) for i in range(g) for j in range(g)], n)
+    """The study's contrast-detail phantom for a raw image of side n: _patch_grid's G x G details of one contrast, their sizes the
+    radii (default: a prefix of DETAIL_RADII), a box's side 4r + 5, G at most 32: detail (i, j) is (x, y, radii[(i + j) % k], contrast),
+    so every radius lies G / k times in every row and every column of the grid."""
+    return mp.detail_list(_patch_grid(n, radii, DETAIL_RADII, lambda r: 4 * r + 5, 32, "radii", lambda x, y, r, t: (x, y, r, contrast)), n)
 
 
 def output_details(details):
-    """A raw plane's details in the coordinates of the output plane (the frame cropped by PROCESSING_MARGIN on every side)."""
-    return tuple((x - PROCESSING_MARGIN, y - PROCESSING_MARGIN, r, c) for x, y, r, c in details)
+    """A raw plane's details in the coordinates of the output plane (_output_patches)."""
+    return _output_patches(details)
 
 
 def DETAILS(n):
@@ -109,33 +122,17 @@ EDGE_CONTRASTS = (8, 16, 32, 64, 128)
 
 
 def edge_grid(n, contrast, halves=None):
-    """The study's edge phantom for a raw image of side n: G x G plates of one contrast on a square grid inside the output plane's
-    footprint. With B = PROCESSING_MARGIN and m = n - 2B, `halves` defaults to the longest prefix of EDGE_HALVES of length k with
-    m // (4 h_last + 1) >= k; G = min(m // (4 h_max + 1), 16) // k * k (ValueError if 0; at most 256 = EDGE_MAX plates), the cell
-    C = m // G, and edge (i, j), i, j < G, row i first, t = i G + j, is (B + j C + C // 2, B + i C + C // 2, halves[(i + j) % k],
-    *EDGE_SLOPES[(t // 4) % 4], t % 4, contrast): the diagonal assignment puts every half-side G / k times in every row and every
-    column of the grid, the orientations cycle fastest and the slopes behind them. A plate has side 4h + 1 <= C, so the plates are
-    disjoint and lie inside [B, n - B)^2: shifted by -B (output_edges) the list is valid for the output plane."""
-    n, b = int(n), PROCESSING_MARGIN
-    m = n - 2 * b
-    if halves is None:
-        k = 0
-        while k < len(EDGE_HALVES) and m // (4 * EDGE_HALVES[k] + 1) >= k + 1:
-            k += 1
-        halves = EDGE_HALVES[:k]
-    halves = tuple(int(h) for h in halves)
-    k = len(halves)
-    g = min(m // (4 * max(halves) + 1), 16) // k * k if k else 0
-    if g <= 0:
-        raise ValueError("a side of %d pixels holds no grid of the half-sides %r" % (n, halves))
-    c = m // g
-    return mp.edge_list([(b + j * c + c // 2, b + i * c + c // 2, halves[(i + j) % k]) + EDGE_SLOPES[((i * g + j) // 4) % len(EDGE_SLOPES)] +
-                         ((i * g + j) % 4, contrast) for i in range(g) for j in range(g)], n)
+    """The study's edge phantom for a raw image of side n: _patch_grid's G x G plates of one contrast, their sizes the half-sides
+    (default: a prefix of EDGE_HALVES), a plate's side 4h + 1, G at most 16 (256 = EDGE_MAX plates): edge t = i G + j is (x, y,
+    halves[(i + j) % k], *EDGE_SLOPES[(t // 4) % 4], t % 4, contrast), so every half-side lies G / k times in every row and every
+    column of the grid, the orientations cycle fastest and the slopes behind them."""
+    return mp.edge_list(_patch_grid(n, halves, EDGE_HALVES, lambda h: 4 * h + 1, 16, "half-sides",
+                                    lambda x, y, h, t: (x, y, h) + EDGE_SLOPES[(t // 4) % len(EDGE_SLOPES)] + (t % 4, contrast)), n)
 
 
 def output_edges(edges):
-    """A raw plane's edges in the coordinates of the output plane (the frame cropped by PROCESSING_MARGIN on every side)."""
-    return tuple((e[0] - PROCESSING_MARGIN, e[1] - PROCESSING_MARGIN) + tuple(e[2:]) for e in edges)
+    """A raw plane's edges in the coordinates of the output plane (_output_patches)."""
+    return _output_patches(edges)
 
 
 def EDGES(n):
@@ -159,36 +156,19 @@ def grating_half(period):
 
 
 def grating_grid(n, contrast, periods=None):
-    """The study's grating phantom for a raw image of side n: G x G plates of one contrast on a square grid inside the output plane's
-    footprint, built as edge_grid is. With B = PROCESSING_MARGIN, m = n - 2B and h(T) = grating_half(T), `periods` defaults to the
-    longest prefix of GRATING_PERIODS of length k with m // (4 h(T_last) + 1) >= k; G = min(m // (4 h_max + 1), 16) // k * k
-    (ValueError if 0; at most 256 = GRATING_MAX plates), the cell C = m // G, and grating (i, j), i, j < G, row i first, t = i G + j,
-    is (B + j C + C // 2, B + i C + C // 2, h(T), *GRATING_DIRECTIONS[t % 4], T, grating_wave(T, contrast)) with
-    T = periods[(i + j) % k]: the diagonal assignment puts every period G / k times in every row and every column of the grid, the
-    directions cycle fastest. (Which directions a period meets depends on G mod 4: for G = 9, t = i + j mod 4, so a period meets
-    two neighbouring directions; the "directions" groups and "per_grating" keep them apart.) A plate has side 4h + 1 <= C, so the plates are disjoint and lie inside [B, n - B)^2: shifted by -B
-    (output_gratings) the list is valid for the output plane."""
-    n, b = int(n), PROCESSING_MARGIN
-    m = n - 2 * b
-    if periods is None:
-        k = 0
-        while k < len(GRATING_PERIODS) and m // (4 * grating_half(GRATING_PERIODS[k]) + 1) >= k + 1:
-            k += 1
-        periods = GRATING_PERIODS[:k]
-    periods = tuple(int(t) for t in periods)
-    k = len(periods)
-    g = min(m // (4 * max(grating_half(t) for t in periods) + 1), 16) // k * k if k else 0
-    if g <= 0:
-        raise ValueError("a side of %d pixels holds no grid of the periods %r" % (n, periods))
-    c = m // g
-    return mp.grating_list([(b + j * c + c // 2, b + i * c + c // 2, grating_half(periods[(i + j) % k])) +
-                            GRATING_DIRECTIONS[(i * g + j) % len(GRATING_DIRECTIONS)] + (periods[(i + j) % k], grating_wave(periods[(i + j) % k], contrast))
-                            for i in range(g) for j in range(g)], n)
+    """The study's grating phantom for a raw image of side n: _patch_grid's G x G plates of one contrast, their sizes the periods
+    (default: a prefix of GRATING_PERIODS), a plate's side 4 h(T) + 1 with h(T) = grating_half(T), G at most 16 (256 = GRATING_MAX
+    plates): grating t = i G + j is (x, y, h(T), *GRATING_DIRECTIONS[t % 4], T, grating_wave(T, contrast)) with T = periods[(i + j) % k],
+    so every period lies G / k times in every row and every column of the grid, the directions cycle fastest. (Which directions a
+    period meets depends on G mod 4: for G = 9, t = i + j mod 4, so a period meets two neighbouring directions; the "directions"
+    groups and "per_grating" keep them apart.)"""
+    return mp.grating_list(_patch_grid(n, periods, GRATING_PERIODS, lambda t: 4 * grating_half(t) + 1, 16, "periods",
+                                       lambda x, y, p, t: (x, y, grating_half(p)) + GRATING_DIRECTIONS[t % len(GRATING_DIRECTIONS)] + (p, grating_wave(p, contrast))), n)
 
 
 def output_gratings(gratings):
-    """A raw plane's gratings in the coordinates of the output plane (the frame cropped by PROCESSING_MARGIN on every side)."""
-    return tuple((g[0] - PROCESSING_MARGIN, g[1] - PROCESSING_MARGIN) + tuple(g[2:]) for g in gratings)
+    """A raw plane's gratings in the coordinates of the output plane (_output_patches)."""
+    return _output_patches(gratings)
 
 
 def GRATINGS(n):
@@ -726,6 +706,58 @@ TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "referenc
 VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
 
 
+# The four patch relations of the study, each one row of this table. key: the row key of its measurement; option / tables: run_study's
+# argument with its payloads (a grid, a gain spec) and the flag that keeps the raw tables; check(payloads, n): the payloads checked for a
+# raw plane of side n and, as output() maps them, for the output plane (ValueError), normalised; name(payload): the row's name;
+# insert(raw, payload): the host's altered raw image; alter(proc, payload): the same on the device; output(payload): the payload in the
+# coordinates of the output plane, what is measured; host(out, reference, measured) and device(proc, measured, shape): the exact
+# integers of the output against the unaltered result; frame: whether summarise also takes the full frame's sq_diff_sum and pixels;
+# summarise(measured, statistics, [sq_diff_sum, pixels,] tables): the row's value.
+Relation = collections.namedtuple("Relation", "key option tables check name insert alter output host device frame summarise")
+
+
+def _checked_grids(list_of):
+    """Relation.check of a list relation: each grid is valid for the raw plane and, shifted, for the output plane."""
+    def check(grids, n):
+        grids = [list_of(g, n) for g in grids]
+        for g in grids:
+            list_of(_output_patches(g), n - 2 * PROCESSING_MARGIN)
+        return grids
+    return check
+
+
+def _checked_gains(gains, n):
+    """Relation.check of the gain relation: every spec's tables are valid for the raw plane; sliced by the margin they are for the output plane."""
+    try:
+        gains = [(str(name),) + tuple(tuple(int(v) for v in g) for g in mp.gain_tables(gx, gy, n)) for name, gx, gy in gains]
+    except TypeError:
+        raise ValueError("a gain spec is (name, gx, gy), got %r" % (gains,))
+    if n <= 2 * PROCESSING_MARGIN:
+        raise ValueError("a side of %d pixels leaves no output plane to take profiles of" % n)
+    return gains
+
+
+def _frame(shape):
+    return (0, 0, 0, 0, shape[1], shape[0])
+
+
+RELATIONS = (
+    Relation("details", "details", "detail_tables", _checked_grids(mp.detail_list), lambda g: "cd_%d" % g[0][3], insert_details,
+             lambda p, g: p.alter_details(g), _output_patches, detail_statistics,
+             lambda p, m, shape: p.sim_details(m, SLOT_UNALTERED), True, detail_row),
+    Relation("edges", "edges", "edge_tables", _checked_grids(mp.edge_list), lambda g: "edge_%d" % g[0][6], insert_edges,
+             lambda p, g: p.alter_edges(g), _output_patches, edge_statistics,
+             lambda p, m, shape: p.sim_edges(m, SLOT_UNALTERED), True, edge_row),
+    Relation("gratings", "gratings", "grating_tables", _checked_grids(mp.grating_list), lambda g: "grating_%d" % grating_contrast(g),
+             insert_gratings, lambda p, g: p.alter_gratings(g), _output_patches, grating_statistics,
+             lambda p, m, shape: p.sim_gratings(m, SLOT_UNALTERED), True, grating_row),
+    # the profiles are taken over the full output frame; measured: (gx, gy) sliced into it
+    Relation("profiles", "gains", "gain_tables", _checked_gains, lambda g: g[0], lambda raw, g: apply_gain(raw, g[1], g[2]), lambda p, g: p.alter_gain(g[1], g[2]),
+             output_gain, lambda out, ref, m: profile_statistics(out, ref, [_frame(out.shape)])[0],
+             lambda p, m, shape: p.sim_profiles([(0, SLOT_UNALTERED) + _frame(shape)])[0], False, lambda m, stats, tables: profile_row(stats, m[0], m[1], tables)),
+)
+
+
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False):
@@ -764,49 +796,31 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
             raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
     zooms = [mp.zoom_ratio(z) for z in (zooms or ())]
     scatters = [mp.scatter_spec(s) for s in (scatters or ())]
-    if details is not None:   # each grid is valid for the raw plane and, shifted, for the output plane
-        details = [mp.detail_list(g, n) for g in details]
-        for g in details:
-            mp.detail_list(output_details(g), n - 2 * PROCESSING_MARGIN)
-    if edges is not None:     # likewise
-        edges = [mp.edge_list(g, n) for g in edges]
-        for g in edges:
-            mp.edge_list(output_edges(g), n - 2 * PROCESSING_MARGIN)
-    if gratings is not None:  # likewise
-        gratings = [mp.grating_list(g, n) for g in gratings]
-        for g in gratings:
-            mp.grating_list(output_gratings(g), n - 2 * PROCESSING_MARGIN)
-    if gains is not None:     # every spec's tables are valid for the raw plane; sliced by the margin they are for the output plane
-        try:
-            gains = [(str(name),) + tuple(tuple(int(v) for v in g) for g in mp.gain_tables(gx, gy, n)) for name, gx, gy in gains]
-        except TypeError:
-            raise ValueError("a gain spec is (name, gx, gy), got %r" % (gains,))
-        if n <= 2 * PROCESSING_MARGIN:
-            raise ValueError("a side of %d pixels leaves no output plane to take profiles of" % n)
+    given = dict(details=details, edges=edges, gratings=gratings, gains=gains)
+    for rel in RELATIONS:
+        if given[rel.option] is not None:
+            given[rel.option] = rel.check(given[rel.option], n)
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
-           (("ensemble",) if ensemble else ()) + (("details",) if details is not None else ()) + \
-           (("edges",) if edges is not None else ()) + (("gratings",) if gratings is not None else ()) + \
-           (("profiles",) if gains is not None else ())
+           (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None)
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
-        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, details=details or [], detail_tables=bool(detail_tables),
-        edges=edges or [], edge_tables=bool(edge_tables), gratings=gratings or [], grating_tables=bool(grating_tables),
-        gains=gains or [], gain_tables=bool(gain_tables), keys=keys, device_alterations=device_alterations)
+        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
+        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), keys=keys, device_alterations=device_alterations,
+        **{option: payloads or [] for option, payloads in given.items()})
 
 
 # One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
 # region() the region of the registered comparison (None, or no region at all as for the noise rows: no registration); move = (the
 # context's method, the host's function, their parameter), which both move a reference plane as the alteration moves the input: the
 # registered comparison is then against the moved plane; noise = (the row's ordinal, alter(context, stream, image_index)) for the rows
-# that draw, what their ensembles repeat; details = the raw plane's detail list of a cd_ row, measured where the details lie; edges = the
-# raw plane's edge list of an edge_ row, gratings = its grating list of a grating_ row, likewise; gain = the (name, gx, gy) of a gain
-# row, whose profiles are taken over the full output frame.
-Alteration = collections.namedtuple("Alteration", "name host dev region move noise details edges gratings gain", defaults=(None, None, None, None, None, None, None))
+# that draw, what their ensembles repeat; measure = (relation, payload) for the rows of a patch relation (RELATIONS): what the row
+# measures beyond its comparisons, the raw plane's grid or gain spec.
+Alteration = collections.namedtuple("Alteration", "name host dev region move noise measure", defaults=(None, None, None, None))
 
 
 def study_alterations(raw, rng, p, seed, shape, opt):
@@ -847,20 +861,15 @@ def study_alterations(raw, rng, p, seed, shape, opt):
     for s in opt.scatters:
         yield Alteration("scatter_%d_%d_%d" % s, lambda: scatter(raw, s), lambda: p.alter_scatter(s), lambda: roi_scatter(shape, s),
                          ("sim_scatter_reference", scatter, s))
-    for g in opt.details:
-        yield Alteration("cd_%d" % g[0][3], lambda: insert_details(raw, g), lambda: p.alter_details(g), details=g)
-    for g in opt.edges:
-        yield Alteration("edge_%d" % g[0][6], lambda: insert_edges(raw, g), lambda: p.alter_edges(g), edges=g)
-    for g in opt.gratings:
-        yield Alteration("grating_%d" % grating_contrast(g), lambda: insert_gratings(raw, g), lambda: p.alter_gratings(g), gratings=g)
-    for g in opt.gains:
-        yield Alteration(g[0], lambda: apply_gain(raw, g[1], g[2]), lambda: p.alter_gain(g[1], g[2]), gain=g)
+    for rel in RELATIONS:
+        for g in getattr(opt, rel.option):
+            yield Alteration(rel.name(g), lambda: rel.insert(raw, g), lambda: rel.alter(p, g), measure=(rel, g))
 
 
 class Scorer:
     """How run_study scores a row, on the host or on the device. produce(alteration) makes the altered output the one that is scored
     (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
-    SLOT_ROTATED and SLOT_VENDOR_ROTATED; similarities, tone, scales and shifts take the row's comparisons, (reference key, region)
+    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key; similarities, tone, scales and shifts take the row's comparisons, (reference key, region)
     pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset)."""
 
     def __init__(self, runner, opt, unalt):
@@ -898,28 +907,14 @@ class DeviceScorer(Scorer):
             getattr(self.proc, method)(SLOT_VENDOR_ROTATED, SLOT_VENDOR, parameter)
 
     def similarities(self, comparisons):
-        self.compared = self.proc.sim_compare([(0, slot) + region for slot, region in comparisons])   # details() reads the direct one's integers
+        self.compared = self.proc.sim_compare([(0, slot) + region for slot, region in comparisons])   # measure() reads the direct one's integers
         return [{k: r[k] for k in mp.SIM_METRICS} for r in self.compared]
 
-    def details(self, details):
-        """One musica_sim_details call against the unaltered result; the full frame's integers are the row's direct comparison's."""
+    def measure(self, relation, measured):
+        """One call of the relation's musica_sim_* against the unaltered result; the full frame's integers are the row's direct comparison's."""
         direct = self.compared[0]
-        return detail_row(details, self.proc.sim_details(details, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.detail_tables)
-
-    def edges(self, edges):
-        """One musica_sim_edges call against the unaltered result; the full frame's integers are the row's direct comparison's."""
-        direct = self.compared[0]
-        return edge_row(edges, self.proc.sim_edges(edges, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.edge_tables)
-
-    def gratings(self, gratings):
-        """One musica_sim_gratings call against the unaltered result; the full frame's integers are the row's direct comparison's."""
-        direct = self.compared[0]
-        return grating_row(gratings, self.proc.sim_gratings(gratings, SLOT_UNALTERED), direct["sq_diff_sum"], direct["pixels"], self.opt.grating_tables)
-
-    def profiles(self, gx_out, gy_out):
-        """One musica_sim_profiles call over the full output frame against the unaltered result."""
-        h, w = self.unalt.shape
-        return profile_row(self.proc.sim_profiles([(0, SLOT_UNALTERED, 0, 0, 0, 0, w, h)])[0], gx_out, gy_out, self.opt.gain_tables)
+        frame = (direct["sq_diff_sum"], direct["pixels"]) if relation.frame else ()
+        return relation.summarise(measured, relation.device(self.proc, measured, self.unalt.shape), *frame, getattr(self.opt, relation.tables))
 
     def tone(self, comparisons):
         """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
@@ -977,23 +972,12 @@ class HostScorer(Scorer):
     def similarities(self, comparisons):
         return [similarities(*self.sides(*c)) for c in comparisons]
 
-    def details(self, details):
-        a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
-        return detail_row(details, detail_statistics(self.out, self.planes[SLOT_UNALTERED], details), int(((a - b) ** 2).sum()), a.size,
-                          self.opt.detail_tables)
-
-    def edges(self, edges):
-        a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
-        return edge_row(edges, edge_statistics(self.out, self.planes[SLOT_UNALTERED], edges), int(((a - b) ** 2).sum()), a.size, self.opt.edge_tables)
-
-    def gratings(self, gratings):
-        a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
-        return grating_row(gratings, grating_statistics(self.out, self.planes[SLOT_UNALTERED], gratings), int(((a - b) ** 2).sum()), a.size,
-                           self.opt.grating_tables)
-
-    def profiles(self, gx_out, gy_out):
-        h, w = self.out.shape
-        return profile_row(profile_statistics(self.out, self.planes[SLOT_UNALTERED], [(0, 0, 0, 0, w, h)])[0], gx_out, gy_out, self.opt.gain_tables)
+    def measure(self, relation, measured):
+        frame = ()
+        if relation.frame:
+            a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
+            frame = (int(((a - b) ** 2).sum()), a.size)
+        return relation.summarise(measured, relation.host(self.out, self.planes[SLOT_UNALTERED], measured), *frame, getattr(self.opt, relation.tables))
 
     def tone(self, comparisons):
         return [tone_similarities(*self.sides(*c)) for c in comparisons]
@@ -1241,14 +1225,9 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
             shifted = [(key + "_shift", (slot, _inset(region, opt.displacement))) for key, (slot, region) in own]
             shifted = [(key, c) for key, c in shifted if c[1] is not None]
             out.update(zip([key for key, _ in shifted], scorer.shifts([c for _, c in shifted])))
-        if alteration is not None and alteration.details:
-            out["details"] = scorer.details(output_details(alteration.details))
-        if alteration is not None and alteration.edges:
-            out["edges"] = scorer.edges(output_edges(alteration.edges))
-        if alteration is not None and alteration.gratings:
-            out["gratings"] = scorer.gratings(output_gratings(alteration.gratings))
-        if alteration is not None and alteration.gain:
-            out["profiles"] = scorer.profiles(*output_gain(alteration.gain))
+        if alteration is not None and alteration.measure:
+            relation, payload = alteration.measure
+            out[relation.key] = scorer.measure(relation, relation.output(payload))
         out["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         if eproc is not None:
             out["ensemble"] = ensemble_of(eproc, alteration.noise, registered[1] if registered else None, full, opt)

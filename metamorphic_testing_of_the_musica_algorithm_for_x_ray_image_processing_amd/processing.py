@@ -211,39 +211,58 @@ def scatter_spec(spec):
     return r, a, b
 
 
+def _ints(t, k):
+    """The k integers of an item as a tuple of ints; TypeError or ValueError otherwise."""
+    t = tuple(t)
+    out = tuple(map(int, t))
+    if len(out) != k or out != t:   # elementwise ==: 3.0 is 3, 3.5 is not
+        raise TypeError
+    return out
+
+
+def _patch_list(items, n, name, holds, most, parse, check, square):
+    """What detail_list, edge_list and grating_list share: a list of square patches for a plane of side n as a tuple of parse(item),
+    else ValueError. name = (article, noun) and square = (singular, plural) word the refusals, `holds` says what an item is. In this
+    order: every item parses (TypeError or ValueError from parse: the whole list is refused); 1 .. most items; per item check(i, item)
+    raises what is specific to the relation and returns the item's reach r, then the square centre +- r lies inside [0, n)^2; the
+    squares are pairwise disjoint."""
+    article, noun = name
+    try:
+        out = [parse(t) for t in items]
+    except (TypeError, ValueError):
+        raise ValueError("%s %s list holds %s, got %r" % (article, noun, holds, items))
+    n = int(n)
+    if not 1 <= len(out) <= most:
+        raise ValueError("%s %s list holds 1 .. %d %ss, got %d" % (article, noun, most, noun, len(out)))
+    squares = []
+    for i, t in enumerate(out):
+        x, y, r = t[0], t[1], check(i, t)
+        if x - r < 0 or y - r < 0 or x + r >= n or y + r >= n:
+            raise ValueError("%s %d: the %s (%d, %d) +- %d leaves the %d x %d plane" % (noun, i, square[0], x, y, r, n, n))
+        squares.append((x, y, r))
+    a = np.array(squares, dtype=np.int64)
+    both = a[:, 2][:, None] + a[:, 2][None, :]
+    meet = (np.abs(a[:, 0][:, None] - a[:, 0][None, :]) <= both) & (np.abs(a[:, 1][:, None] - a[:, 1][None, :]) <= both)
+    np.fill_diagonal(meet, False)
+    if meet.any():
+        i, j = np.argwhere(meet)[0]
+        raise ValueError("the %s of %ss %d and %d are not disjoint" % (square[1], noun, i, j))
+    return tuple(out)
+
+
 def detail_list(details, n, with_contrast=True):
     """The details (x, y, r, c) of a contrast-detail list for a plane of side n as harness.insert_details, harness.detail_statistics and
     the library take it, a tuple of tuples of ints, else ValueError: 1 .. DETAIL_MAX details of integers, 1 <= r <= DETAIL_MAX_RADIUS,
     1 <= |c| <= DETAIL_MAX_CONTRAST (with_contrast=False: c is not looked at, as the measurement does not), every box |px - x|,
     |py - y| <= 2r + 2 inside [0, n)^2 and the boxes pairwise disjoint."""
-    try:
-        out = []
-        for d in details:
-            x, y, r, c = d
-            if x != int(x) or y != int(y) or r != int(r) or c != int(c):
-                raise TypeError
-            out.append((int(x), int(y), int(r), int(c)))
-    except (TypeError, ValueError):
-        raise ValueError("a detail list holds quadruples of integers (x, y, r, c), got %r" % (details,))
-    n = int(n)
-    if not 1 <= len(out) <= DETAIL_MAX:
-        raise ValueError("a detail list holds 1 .. %d details, got %d" % (DETAIL_MAX, len(out)))
-    for i, (x, y, r, c) in enumerate(out):
+    def check(i, d):
+        x, y, r, c = d
         if not 1 <= r <= DETAIL_MAX_RADIUS:
             raise ValueError("detail %d: radius %d is not in 1 .. %d" % (i, r, DETAIL_MAX_RADIUS))
         if with_contrast and not 1 <= abs(c) <= DETAIL_MAX_CONTRAST:
             raise ValueError("detail %d: contrast %d is not 1 <= |c| <= %d" % (i, c, DETAIL_MAX_CONTRAST))
-        ro = 2 * r + 2
-        if x - ro < 0 or y - ro < 0 or x + ro >= n or y + ro >= n:
-            raise ValueError("detail %d: the box (%d, %d) +- %d leaves the %d x %d plane" % (i, x, y, ro, n, n))
-    a = np.array(out, dtype=np.int64)
-    reach = (2 * a[:, 2] + 2)[:, None] + (2 * a[:, 2] + 2)[None, :]
-    meet = (np.abs(a[:, 0][:, None] - a[:, 0][None, :]) <= reach) & (np.abs(a[:, 1][:, None] - a[:, 1][None, :]) <= reach)
-    np.fill_diagonal(meet, False)
-    if meet.any():
-        i, j = np.argwhere(meet)[0]
-        raise ValueError("the boxes of details %d and %d are not disjoint" % (i, j))
-    return tuple(out)
+        return 2 * r + 2
+    return _patch_list(details, n, ("a", "detail"), "quadruples of integers (x, y, r, c)", DETAIL_MAX, lambda d: _ints(d, 4), check, ("box", "boxes"))
 
 
 class Detail(C.Structure):
@@ -280,19 +299,8 @@ def edge_list(edges, n, with_contrast=True):
     p / q with 1 <= p < q, 4 <= q <= EDGE_MAX_Q in lowest terms, an orientation o of 0 .. 3, 1 <= |c| <= EDGE_MAX_CONTRAST
     (with_contrast=False: c is not looked at, as the measurement does not), every plate |px - x|, |py - y| <= 2h inside [0, n)^2 and
     the plates pairwise disjoint."""
-    try:
-        out = []
-        for e in edges:
-            x, y, h, p, q, o, c = e
-            if any(v != int(v) for v in e):
-                raise TypeError
-            out.append(tuple(int(v) for v in e))
-    except (TypeError, ValueError):
-        raise ValueError("an edge list holds septuples of integers (x, y, h, p, q, o, c), got %r" % (edges,))
-    n = int(n)
-    if not 1 <= len(out) <= EDGE_MAX:
-        raise ValueError("an edge list holds 1 .. %d edges, got %d" % (EDGE_MAX, len(out)))
-    for i, (x, y, h, p, q, o, c) in enumerate(out):
+    def check(i, e):
+        x, y, h, p, q, o, c = e
         if not EDGE_MIN_HALF <= h <= EDGE_MAX_HALF:
             raise ValueError("edge %d: half-side %d is not in %d .. %d" % (i, h, EDGE_MIN_HALF, EDGE_MAX_HALF))
         if not edge_bins(h, p, q):
@@ -301,16 +309,8 @@ def edge_list(edges, n, with_contrast=True):
             raise ValueError("edge %d: orientation %d is not in 0 .. 3" % (i, o))
         if with_contrast and not 1 <= abs(c) <= EDGE_MAX_CONTRAST:
             raise ValueError("edge %d: contrast %d is not 1 <= |c| <= %d" % (i, c, EDGE_MAX_CONTRAST))
-        if x - 2 * h < 0 or y - 2 * h < 0 or x + 2 * h >= n or y + 2 * h >= n:
-            raise ValueError("edge %d: the plate (%d, %d) +- %d leaves the %d x %d plane" % (i, x, y, 2 * h, n, n))
-    a = np.array(out, dtype=np.int64)
-    reach = 2 * (a[:, 2][:, None] + a[:, 2][None, :])
-    meet = (np.abs(a[:, 0][:, None] - a[:, 0][None, :]) <= reach) & (np.abs(a[:, 1][:, None] - a[:, 1][None, :]) <= reach)
-    np.fill_diagonal(meet, False)
-    if meet.any():
-        i, j = np.argwhere(meet)[0]
-        raise ValueError("the plates of edges %d and %d are not disjoint" % (i, j))
-    return tuple(out)
+        return 2 * h
+    return _patch_list(edges, n, ("an", "edge"), "septuples of integers (x, y, h, p, q, o, c)", EDGE_MAX, lambda e: _ints(e, 7), check, ("plate", "plates"))
 
 
 class Edge(C.Structure):
@@ -342,23 +342,14 @@ def grating_list(gratings, n, with_wave=True):
     GRATING_MAX_U, not both 0 and coprime, a period 2 <= T <= min(GRATING_MAX_PERIOD, h) with 2 |ux| <= T and 2 |uy| <= T, a wave of
     exactly T integers |w| <= GRATING_MAX_CONTRAST (with_wave=False: the wave is not looked at, as the measurement does not, and comes
     back as it was given), every plate |px - x|, |py - y| <= 2h inside [0, n)^2 and the plates pairwise disjoint."""
-    try:
-        out = []
-        for g in gratings:
-            x, y, h, ux, uy, t, wave = g
-            if any(v != int(v) for v in g[:6]):
-                raise TypeError
-            if with_wave:
-                if any(w != int(w) for w in wave):
-                    raise TypeError
-                wave = tuple(int(w) for w in wave)
-            out.append(tuple(int(v) for v in g[:6]) + (wave,))
-    except (TypeError, ValueError):
-        raise ValueError("a grating list holds septuples (x, y, h, ux, uy, T, wave) of six integers and a sequence of integers, got %r" % (gratings,))
-    n = int(n)
-    if not 1 <= len(out) <= GRATING_MAX:
-        raise ValueError("a grating list holds 1 .. %d gratings, got %d" % (GRATING_MAX, len(out)))
-    for i, (x, y, h, ux, uy, t, wave) in enumerate(out):
+    def parse(g):
+        g = tuple(g)
+        if len(g) != 7:
+            raise TypeError
+        return _ints(g[:6], 6) + (_ints(g[6], len(g[6])) if with_wave else g[6],)
+
+    def check(i, g):
+        x, y, h, ux, uy, t, wave = g
         if not GRATING_MIN_HALF <= h <= GRATING_MAX_HALF:
             raise ValueError("grating %d: half-side %d is not in %d .. %d" % (i, h, GRATING_MIN_HALF, GRATING_MAX_HALF))
         if not (abs(ux) <= GRATING_MAX_U and abs(uy) <= GRATING_MAX_U and math.gcd(abs(ux), abs(uy)) == 1):
@@ -367,16 +358,9 @@ def grating_list(gratings, n, with_wave=True):
             raise ValueError("grating %d: period %d is not 2 <= T <= min(%d, half) with 2 |ux|, 2 |uy| <= T" % (i, t, GRATING_MAX_PERIOD))
         if with_wave and (len(wave) != t or any(abs(w) > GRATING_MAX_CONTRAST for w in wave)):
             raise ValueError("grating %d: the wave is not %d integers |w| <= %d" % (i, t, GRATING_MAX_CONTRAST))
-        if x - 2 * h < 0 or y - 2 * h < 0 or x + 2 * h >= n or y + 2 * h >= n:
-            raise ValueError("grating %d: the plate (%d, %d) +- %d leaves the %d x %d plane" % (i, x, y, 2 * h, n, n))
-    a = np.array([g[:3] for g in out], dtype=np.int64)
-    reach = 2 * (a[:, 2][:, None] + a[:, 2][None, :])
-    meet = (np.abs(a[:, 0][:, None] - a[:, 0][None, :]) <= reach) & (np.abs(a[:, 1][:, None] - a[:, 1][None, :]) <= reach)
-    np.fill_diagonal(meet, False)
-    if meet.any():
-        i, j = np.argwhere(meet)[0]
-        raise ValueError("the plates of gratings %d and %d are not disjoint" % (i, j))
-    return tuple(out)
+        return 2 * h
+    return _patch_list(gratings, n, ("a", "grating"), "septuples (x, y, h, ux, uy, T, wave) of six integers and a sequence of integers", GRATING_MAX,
+                       parse, check, ("plate", "plates"))
 
 
 class Grating(C.Structure):
@@ -391,6 +375,19 @@ GRATING_SUMS = ("n", "sum_a", "sum_b", "sum_aa")   # the four rows of a grating'
 class SimGratingResult(C.Structure):
     """musica_sim_grating_result: the region's exact sum of squared differences and where the grating's table lies in `tables`."""
     _fields_ = [("roi_ssd", C.c_uint64), ("roi_pixels", C.c_uint64), ("table_offset", C.c_uint64), ("bins", C.c_uint64)]
+
+
+def _unpack_tables(results, tables, sums):
+    """Per musica_sim_edge_result / musica_sim_grating_result: (its bins, {roi_ssd, roi_pixels and the uint32 arrays `sums`, the rows
+    of its [len(sums)][bins] table in the flat `tables`})."""
+    out = []
+    for r in results:
+        at, bins = int(r.table_offset), int(r.bins)
+        t = tables[at:at + len(sums) * bins].reshape(len(sums), bins)
+        d = {"roi_ssd": int(r.roi_ssd), "roi_pixels": int(r.roi_pixels)}
+        d.update((k, t[i].copy()) for i, k in enumerate(sums))
+        out.append((bins, d))
+    return out
 
 
 def gain_tables(gx, gy, n):
@@ -1037,13 +1034,7 @@ class MusicaProcessing:
         arr, res, tables = (Edge * len(es))(*[Edge(*e) for e in es]), (SimEdgeResult * len(es))(), np.zeros(words, dtype=np.uint32)
         self._ok(self._lib.musica_sim_edges(self._h, int(image_index), int(slot), len(es), arr, res, tables.ctypes.data_as(_U32P), words),
                  "musica_sim_edges")
-        out = []
-        for e, r in zip(es, res):
-            t = tables[int(r.table_offset):int(r.table_offset) + 4 * int(r.bins)].reshape(4, int(r.bins))
-            d = {"h": e[2], "p": e[3], "q": e[4], "bins": int(r.bins), "roi_ssd": int(r.roi_ssd), "roi_pixels": int(r.roi_pixels)}
-            d.update((k, t[i].copy()) for i, k in enumerate(EDGE_SUMS))
-            out.append(d)
-        return out
+        return [dict({"h": e[2], "p": e[3], "q": e[4], "bins": bins}, **d) for e, (bins, d) in zip(es, _unpack_tables(res, tables, EDGE_SUMS))]
 
     def sim_gratings(self, gratings, slot, image_index=0):
         """harness.grating_statistics(output of `image_index`, reference slot `slot`, gratings) on the device: the gratings
@@ -1054,13 +1045,7 @@ class MusicaProcessing:
         arr, res, tables = (Grating * len(gs))(*[Grating(*g[:6]) for g in gs]), (SimGratingResult * len(gs))(), np.zeros(words, dtype=np.uint32)
         self._ok(self._lib.musica_sim_gratings(self._h, int(image_index), int(slot), len(gs), arr, res, tables.ctypes.data_as(_U32P), words),
                  "musica_sim_gratings")
-        out = []
-        for g, r in zip(gs, res):
-            t = tables[int(r.table_offset):int(r.table_offset) + 4 * int(r.bins)].reshape(4, int(r.bins))
-            d = {"h": g[2], "ux": g[3], "uy": g[4], "T": int(r.bins), "roi_ssd": int(r.roi_ssd), "roi_pixels": int(r.roi_pixels)}
-            d.update((k, t[i].copy()) for i, k in enumerate(GRATING_SUMS))
-            out.append(d)
-        return out
+        return [dict({"h": g[2], "ux": g[3], "uy": g[4], "T": bins}, **d) for g, (bins, d) in zip(gs, _unpack_tables(res, tables, GRATING_SUMS))]
 
     def sim_profiles(self, queries):
         """harness.profile_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or

@@ -128,40 +128,29 @@ def _covariance_cells(e, radius):
            list(cov["direct"]["nps_radial"])
 
 
-def _detail_lines(studies):
-    """contrast_detail.csv's lines: one per cd_ row and radius, ascending."""
+def _group_lines(studies, key, groups, cells):
+    """A patch relation's CSV lines: one per row that has `key` and per (label, group) of groups(the row's value), in their order: the
+    raw file, the alteration, the label, then cells(the value, the group)."""
     for raw_name, rows in studies:
         for r in rows:
-            d = r.get("details")
-            for radius, g in (d["radii"].items() if d else ()):
-                yield [raw_name, r["alteration"], radius, g["count"]] + [g[k][w] for k in DETAIL_ROW_KEYS for w in DETAIL_ROW_STATS] + [d["outside_mse"]]
+            d = r.get(key)
+            for label, g in (groups(d) if d else ()):
+                yield [raw_name, r["alteration"], label] + cells(d, g)
 
 
-def _edge_lines(studies):
-    """edge_response.csv's lines: one per edge_ row and orientation, ascending."""
-    for raw_name, rows in studies:
-        for r in rows:
-            d = r.get("edges")
-            for o, g in (d["orientations"].items() if d else ()):
-                yield [raw_name, r["alteration"], o, g["edges"]] + [g[k][w] for k in EDGE_ROW_KEYS for w in EDGE_ROW_STATS] + [d["outside_mse"]]
+def _spread_cells(count, keys, stats):
+    return lambda d, g: [g[count]] + [g[k][w] for k in keys for w in stats] + [d["outside_mse"]]
 
 
-def _grating_lines(studies):
-    """grating_response.csv's lines: one per grating_ row and period, ascending."""
-    for raw_name, rows in studies:
-        for r in rows:
-            d = r.get("gratings")
-            for t, g in (d["periods"].items() if d else ()):
-                yield [raw_name, r["alteration"], t, g["gratings"]] + [g[k][w] for k in GRATING_ROW_KEYS for w in GRATING_ROW_STATS] + [d["outside_mse"]]
-
-
-def _gain_lines(studies):
-    """gain_response.csv's lines: one per gain row and axis, the columns' profile first."""
-    for raw_name, rows in studies:
-        for r in rows:
-            d = r.get("profiles")
-            for axis in (PROFILE_AXES if d else ()):
-                yield [raw_name, r["alteration"], axis, d[axis]["lines"]] + [d[axis][k] for k in PROFILE_KEYS]
+# file name, header, row key, groups, cells of _group_lines: contrast_detail.csv has one line per cd_ row and radius, ascending;
+# edge_response.csv one per edge_ row and orientation; grating_response.csv one per grating_ row and period; gain_response.csv one per
+# gain row and axis, the columns' profile first
+RELATION_CSVS = (
+    ("contrast_detail.csv", DETAIL_CSV_HEADER, "details", lambda d: d["radii"].items(), _spread_cells("count", DETAIL_ROW_KEYS, DETAIL_ROW_STATS)),
+    ("edge_response.csv", EDGE_CSV_HEADER, "edges", lambda d: d["orientations"].items(), _spread_cells("edges", EDGE_ROW_KEYS, EDGE_ROW_STATS)),
+    ("grating_response.csv", GRATING_CSV_HEADER, "gratings", lambda d: d["periods"].items(), _spread_cells("gratings", GRATING_ROW_KEYS, GRATING_ROW_STATS)),
+    ("gain_response.csv", GAIN_CSV_HEADER, "profiles", lambda d: [(axis, d[axis]) for axis in PROFILE_AXES], lambda d, g: [g["lines"]] + [g[k] for k in PROFILE_KEYS]),
+)
 
 
 def write_studies_csvs(studies, out_dir, mean_cnr=True):
@@ -236,14 +225,9 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     for name, header, covered, cells in tables:
         if covered is not None:
             _write_csv(out_dir, name, header, _lines(covered, cells))
-    if having("details"):
-        _write_csv(out_dir, "contrast_detail.csv", DETAIL_CSV_HEADER, _detail_lines(having("details")))
-    if having("edges"):
-        _write_csv(out_dir, "edge_response.csv", EDGE_CSV_HEADER, _edge_lines(having("edges")))
-    if having("gratings"):
-        _write_csv(out_dir, "grating_response.csv", GRATING_CSV_HEADER, _grating_lines(having("gratings")))
-    if having("profiles"):
-        _write_csv(out_dir, "gain_response.csv", GAIN_CSV_HEADER, _gain_lines(having("profiles")))
+    for name, header, key, groups, cells in RELATION_CSVS:
+        if having(key):
+            _write_csv(out_dir, name, header, _group_lines(having(key), key, groups, cells))
     ovds = [[raw_name] + _cells(_ovd(rows), SIM_CSV_KEYS) for raw_name, rows in studies if _ovd(rows) is not None]
     if ovds:
         _write_csv(out_dir, "ref_similarities.csv", REF_CSV_HEADER, ovds)

@@ -69,7 +69,7 @@ def _check(p, raw, edges, image_index=0):
     return got
 
 
-@pytest.mark.parametrize("n", [84, 137])    # 84: two tiles a side, the second ragged, rows of whole 16-byte words; 137: odd, single pixels
+@pytest.mark.parametrize("n", [84, 88, 137])    # two tiles a side, the second ragged. 84 % 8 = 4: 4-byte words; 88: rows of whole 16-byte words, a chunk ends at the plane's edge; 137: odd, single pixels
 def test_alter_edges_is_bit_identical(n):
     raw = _full_range_u16(n, n)
     p = _ctx(n)
@@ -307,6 +307,7 @@ def test_refusals_leave_the_context_usable():
     refused(lib.musica_sim_edges(p._h, 0, 0, 2, _array(ok), res, tp, need - 1), "table_words")
     refused(lib.musica_sim_edges(p._h, 0, 0, 2, _array(ok), res, tp, 0), "table_words")
     refused(lib.musica_alter_edges(p._h, 1, 2, _array(ok)), "image_index")        # image_index == batch
+    refused(lib.musica_alter_edges(p._h, 1, 1, _array(((130, 130, 0, 1, 8, 0, 8),))), "half-side")   # a bad list AND a bad index: every alteration names its own arguments first
     refused(lib.musica_sim_edges(p._h, 1, 0, 2, _array(ok), res, tp, words), "image_index")
     refused(lib.musica_sim_edges(p._h, 0, 5, 2, _array(ok), res, tp, words), "never written")
     refused(lib.musica_sim_edges(p._h, 0, mp.SIM_SLOTS, 2, _array(ok), res, tp, words), "slot")

@@ -95,7 +95,7 @@ def test_the_lists_wrap_the_phase_both_ways():
     assert {(np.sign(ux), np.sign(uy)) for ux, uy, _ in SMALL + WIDE} == {(a, b) for a in (-1, 0, 1) for b in (-1, 0, 1)} - {(0, 0)}
 
 
-@pytest.mark.parametrize("n", [84, 137])    # 84: two tiles a side, the second ragged, rows of whole 16-byte words; 137: odd, single pixels
+@pytest.mark.parametrize("n", [84, 88, 137])    # two tiles a side, the second ragged. 84 % 8 = 4: 4-byte words; 88: rows of whole 16-byte words, a chunk ends at the plane's edge; 137: odd, single pixels
 def test_alter_gratings_is_bit_identical(n):
     raw = _full_range_u16(n, n)
     p = _ctx(n)
@@ -373,6 +373,7 @@ def test_refusals_leave_the_context_usable():
     refused(lib.musica_sim_gratings(p._h, 0, 0, 2, _array(ok), res, tp, need - 1), "table_words")
     refused(lib.musica_sim_gratings(p._h, 0, 0, 2, _array(ok), res, tp, 0), "table_words")
     refused(lib.musica_alter_gratings(p._h, 1, 2, _array(ok), wp, w.size), "image_index")        # image_index == batch
+    refused(lib.musica_alter_gratings(p._h, 1, 1, _array(((130, 130, 0, 1, 0, 8, None),)), zp, zeros.size), "half-side")   # a bad list AND a bad index: every alteration names its own arguments first
     refused(lib.musica_sim_gratings(p._h, 1, 0, 2, _array(ok), res, tp, words), "image_index")
     refused(lib.musica_sim_gratings(p._h, 0, 5, 2, _array(ok), res, tp, words), "never written")
     refused(lib.musica_sim_gratings(p._h, 0, mp.SIM_SLOTS, 2, _array(ok), res, tp, words), "slot")

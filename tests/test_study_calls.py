@@ -1,12 +1,16 @@
 """The device branch of harness.run_study, on a CPU: a recording stand-in for runner.proc and for the ensemble context logs every
 sim_* / alter_* / execute* call (arrays reduced to shape and dtype) and answers with canned results of the right shape, each number
 different from every other, so the rows also say which result went under which key. Three studies at side 84 (a 64 x 64 output), one
-value per grid, are compared with tests/golden/study_calls.json.
+value per grid, are compared with tests/golden/study_calls.json; a fourth, "relations", with one grid or spec of each of the four patch
+relations (details, edges, gratings, gains), with tests/golden/study_calls_relations.json.
 
 The golden file was recorded with record() below driving the harness.py of the commit BEFORE run_study was split into a row routine
 and two scorers (never the code under test), with one edit by hand: in row 0 the sim_displace call was moved behind the
-sim_multiscale calls, the order every other row already had."""
+sim_multiscale calls, the order every other row already had. study_calls_relations.json was recorded the same way with the harness.py of the commit BEFORE the
+four relations were put into one table. Its rows hold what the *_row summarisers make of the canned sums, some of it through an FFT and
+cosines: those floats are compared to 1e-9 relative, everything else of it exactly, as the three older studies are throughout."""
 import json
+import math
 import os
 
 import numpy as np
@@ -16,6 +20,7 @@ from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd 
 from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import processing as mp
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "study_calls.json")
+GOLDEN_RELATIONS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "study_calls_relations.json")
 SIDE = 84
 OUT = SIDE - 2 * H.PROCESSING_MARGIN
 ENSEMBLE_INPUTS = ("sq_bias_sum", "var_sum", "sq_err_sum", "bias_sum", "abs_bias_max", "var_max", "realisations")
@@ -43,6 +48,7 @@ class RecordingProc:
     def __init__(self, log, name, batch=1):
         self.log, self.name, self.batch = log, name, batch
         self.plane = np.random.default_rng(5).integers(0, 256, size=(OUT, OUT)).astype(np.uint8)
+        self.measured = np.random.default_rng(6).integers(0, 256, size=(OUT, OUT)).astype(np.uint8)   # what the patch relations' calls measure against `plane`
         self.counts = {}      # per kind of call, the source of the canned numbers: they do not depend on the order of unlike calls
         self.tracked = 0      # regions of the last sim_ensemble_track
 
@@ -77,7 +83,20 @@ class RecordingProc:
         return self.plane.copy()
 
     def _sim_compare(self, queries):
-        return [dict({k: self.number("compare") for k in mp.SIM_METRICS}, pixels=q[6] * q[7]) for q in queries]
+        return [dict({k: self.number("compare") for k in mp.SIM_METRICS}, pixels=q[6] * q[7], sq_diff_sum=1000 + self.ordinal("sq_diff_sum")) for q in queries]
+
+    # The patch relations: the host's exact statistics of two fixed planes, which have the calls' shapes and which every *_row accepts.
+    def _sim_details(self, details, slot, image_index=0):
+        return H.detail_statistics(self.measured, self.plane, details)
+
+    def _sim_edges(self, edges, slot, image_index=0):
+        return H.edge_statistics(self.measured, self.plane, edges)
+
+    def _sim_gratings(self, gratings, slot, image_index=0):
+        return H.grating_statistics(self.measured, self.plane, gratings)
+
+    def _sim_profiles(self, queries):
+        return [H.profile_statistics(self.measured, self.plane, [tuple(q[2:])])[0] for q in queries]
 
     def _sim_joint(self, queries, tables=False):
         return [dict({k: self.number("joint") for k in mp.JOINT_METRICS if k != "tone_ssim"}, tone_lut=np.arange(256, dtype=np.uint8)) for _ in queries]
@@ -135,6 +154,9 @@ STUDIES = {
                               ensemble=3, ensemble_tiles=True, covariance=2, covariance_tiles=True)),
     "device_metrics": (False, dict(GRIDS, vendor=True, symmetries=[4], blurs=[1])),
     "no_region": (True, dict(GRIDS, translations=[60], vendor=True, tone=True, scales=2, displacement=2)),   # 60 > 64 - 8: nothing to register
+    # one grid or spec of each patch relation, tables off
+    "relations": (True, dict(GRIDS, details=[H.detail_grid(SIDE, 8)], edges=[H.edge_grid(SIDE, 8)], gratings=[H.grating_grid(SIDE, 8)],
+                             gains=[H.GAINS(SIDE)[0]] + [g for g in H.GAINS(SIDE) if g[0] == "line_8"])),
 }
 
 
@@ -152,8 +174,21 @@ def record(name, harness=H):
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(GOLDEN) as f:
-        return json.load(f)
+    with open(GOLDEN) as f, open(GOLDEN_RELATIONS) as g:
+        return dict(json.load(f), **json.load(g))
+
+
+def _same(got, want, tolerant):
+    """Equal as JSON; with `tolerant`, a float against a float to 1e-9 relative."""
+    if tolerant and isinstance(got, float) and isinstance(want, float):
+        return math.isclose(got, want, rel_tol=1e-9, abs_tol=1e-12)
+    if type(got) is not type(want):
+        return False
+    if isinstance(got, dict):
+        return list(got) == list(want) and all(_same(got[k], want[k], tolerant) for k in got)
+    if isinstance(got, list):
+        return len(got) == len(want) and all(_same(g, w, tolerant) for g, w in zip(got, want))
+    return got == want
 
 
 @pytest.mark.parametrize("name", sorted(STUDIES))
@@ -163,7 +198,9 @@ def test_the_device_study_makes_the_recorded_calls(name, golden):
         assert g == w, "call %d of %s" % (i, name)
     assert len(got["calls"]) == len(want["calls"])
     assert [[k for k, _ in row] for row in got["rows"]] == [[k for k, _ in row] for row in want["rows"]]   # the keys and their order
-    assert got["rows"] == want["rows"]
+    for g, w in zip(got["rows"], want["rows"]):
+        assert _same(g, w, tolerant=name == "relations"), dict(g)["alteration"]
+    assert len(got["rows"]) == len(want["rows"])
 
 
 def test_the_studies_cover_what_they_are_meant_to(golden):
@@ -184,3 +221,14 @@ def test_the_studies_cover_what_they_are_meant_to(golden):
     assert all(v is None for k, v in t_x if k.startswith("registered"))
     queries = [len(c[2][0]) for c in golden["no_region"]["calls"] if c[1] == "sim_compare"]
     assert queries[2] == 4 and queries[4] == 2                                # t_x_60: direct and vendor only; c_sh_8: all four
+
+
+def test_the_relations_study_covers_the_four_relations(golden):
+    calls = [(c[0], c[1]) for c in golden["relations"]["calls"]]
+    for call in ("alter_details", "alter_edges", "alter_gratings", "alter_gain", "sim_details", "sim_edges", "sim_gratings", "sim_profiles"):
+        assert ("proc", call) in calls, call
+    assert calls.count(("proc", "alter_gain")) == 2 and calls.count(("proc", "sim_profiles")) == 2   # the exposure and the lines
+    rows = [dict(row) for row in golden["relations"]["rows"]]
+    for key, names in (("details", ["cd_8"]), ("edges", ["edge_8"]), ("gratings", ["grating_8"]), ("profiles", ["exposure_1_4", "line_8"])):
+        assert [r["alteration"] for r in rows if r[key] is not None] == names
+    assert len(rows[[r["alteration"] for r in rows].index("cd_8")]["details"]["radii"]) >= 1
