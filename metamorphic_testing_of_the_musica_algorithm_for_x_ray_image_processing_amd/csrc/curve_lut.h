@@ -125,5 +125,28 @@ MUSICA_HD float musica_lut_eval(const F4* bucket, const F4* seg, int base, float
     const float r = g.z * (sf - g.x) + g.y;
     return sf < 0.0f ? 0.0f : r;
 }
+// musica_lut_eval for an argument whose sign bit is clear unless it is a NaN: +0, a positive number, +inf, or any NaN. That is what
+// musica_rms25_8 (exact_math.h) leaves, the sdev the expand launches compute in registers: its sums are sums of squares, each +0, positive,
+// +inf or NaN, so a sum is never negative and never -0; musica_sqrt_core of +0 is +0 and of a positive number is sqrtf's positive value
+// (checked over all patterns on the GPU); sqrtf(x / 25.0f) of such a sum is +0, positive, +inf or NaN. A stored sdev image can hold what
+// a caller injected, so the launches that read one keep musica_lut_eval. With such an argument, bit for bit the same value in fewer
+// instructions:
+//   * non-negative floats order like their patterns taken as unsigned integers, 2.0f is 0x40000000, and every NaN pattern (either sign)
+//     is above 0x7F800000: musica_lut_clamp(s) is the pattern's unsigned minimum with 0x40000000 — one instruction, no NaN quieting;
+//   * the key is then 0 .. kLutKeyTop, and base >= 0 wherever a table exists (musica_lut_entries): max(key, base) - base is key - base
+//     saturating at 0, an index 0 .. kLutKeyTop - base = n - 1 as before;
+//   * sf >= +0, so the `sf < 0 ? 0 : r` select never takes its first arm.
+MUSICA_HD uint32_t musica_usub_sat(uint32_t a, uint32_t b) { return a > b ? a - b : 0u; }   // one v_sub_u32 with the clamp bit
+template <class F4>
+MUSICA_HD float musica_lut_eval_nonneg(const F4* bucket, const F4* seg, int base, float s) {
+    const uint32_t u = (uint32_t)musica_float_bits(s);
+    const uint32_t uf = u < 0x40000000u ? u : 0x40000000u;
+    const float sf = musica_bits_float((int32_t)uf);
+    const uint32_t idx = musica_usub_sat(uf >> kLutShift, (uint32_t)base);
+    const F4 e = *reinterpret_cast<const F4*>(reinterpret_cast<const char*>(bucket) + idx * 16u);
+    const int joff = musica_float_bits(e.x) + (e.y < sf ? 16 : 0) + (e.z < sf ? 16 : 0);
+    const F4 g = *reinterpret_cast<const F4*>(reinterpret_cast<const char*>(seg) + joff);
+    return g.z * (sf - g.x) + g.y;
+}
 
 }  // namespace musica

@@ -781,9 +781,11 @@ struct LutLds {
 // LUTOK is wave-uniform and decided once per wavefront (k_expand_fast picks the instantiation of the whole march): a per-texel
 // `if (!ok) slow()` put a divergent branch and a call sequence around each of the 16 lookups of a trip. `base` is lut.base in a
 // scalar register.
-template <bool LUTOK>
+// NONNEG: s comes out of musica_rms25_8 (the SD march), never out of a stored image: musica_lut_eval_nonneg has the proof.
+template <bool LUTOK, bool NONNEG = false>
 __device__ __forceinline__ float curve_eval_lut(const CurveLds& t, const LutLds& lut, int base, float s) {
     if (!LUTOK) return curve_eval(t, s);
+    if (NONNEG) return musica_lut_eval_nonneg(lut.bucket, lut.seg, base, s);
     return musica_lut_eval(lut.bucket, lut.seg, base, s);
 }
 
@@ -835,6 +837,9 @@ __device__ __forceinline__ void sdev_from_band(const BRow& r0, const BRow& r1, c
     s[7] = sum5(q[5], q[6], q[7], b0, b1);
     musica_rms25_8(s);
 }
+// Bits 0 .. 3 of x as the low bits of bytes 0 .. 3: the product moves bit i to i, i + 7, i + 14 and i + 21 — sixteen different places,
+// so nothing carries — and bit 8k is reached from i = k alone.
+__device__ __forceinline__ uint32_t spread4(uint32_t x) { return ((x & 15u) * 0x204081u) & 0x01010101u; }   // 4 x 22 bits: a 24-bit multiply
 template <int GAIN, bool NR, bool GH, bool LUTOK, bool CNR48, bool CH = false, bool SD = false>
 __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds& tab, const LutLds& lut, uint32_t* lh, int img, uint32_t* lc = nullptr,
                                              uint32_t tx0 = 0u, uint32_t ty0 = 0u) {
@@ -870,6 +875,8 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
         for (int j = 0; j < 8; j++)
             if (g.active && (uint32_t)(g.c + j) > border && (uint32_t)(g.c + j) < lim) colin |= 1u << j;
     }
+    // the border bits as bytes of 0 / 1, four columns per word: the low half of row_phase's byte selectors, the same for every row of the lane
+    const uint32_t colsp[2] = {spread4(colin & 15u), spread4(colin >> 4)};
     uint32_t* lhc = lh + (GH ? 1 + (lane & (kGhCopies - 1)) * kGhStride : 0);   // bin 0 of the lane's copy; the word below it is a spare one too
     // CLAHE tile column of each of the lane's 8 columns, relative to the workgroup's first one (clahe_histogram.comp:34)
     const float fS = (float)S;
@@ -884,11 +891,11 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
     // `src` is the band row, `b` the registers the reconstructed row is left in (the same array, or — SD — the lowpass row's: the band row stays
     // in the window)
     auto row_phase = [&](const int ph, float* b, const float* src, const float* sd, const float* low, const float* f, const uint32_t le_t,
-                         const int kk, const uint32_t w_cnr, const uint32_t w_dark_or_ramp, const bool one_ramp, const bool one_dark) __attribute__((always_inline)) {
+                         const int kk, const uint32_t wpair, const bool one_ramp, const bool one_dark) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             // contrast_curve_apply.comp:61
-            float p = src[j] * (GAIN == GAIN_CURVE ? curve_eval_lut<LUTOK>(tab, lut, lut_base, sd[j]) : gain_of<GAIN>(GAIN != GAIN_CONST ? sd[j] : 0.0f, a.high, tab));
+            float p = src[j] * (GAIN == GAIN_CURVE ? curve_eval_lut<LUTOK, SD>(tab, lut, lut_base, sd[j]) : gain_of<GAIN>(GAIN != GAIN_CONST ? sd[j] : 0.0f, a.high, tab));
             if (NR) p = p * f[j];   // noise_reduction.comp:57
             b[j] = low[j] + p;      // img_addition.comp:15
         }
@@ -896,7 +903,15 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
         if (GH) {
             const uint32_t dark = le_t >> (8 * ph);
             const uint32_t y = (uint32_t)(2 * kk + ph);
-            const uint32_t m = (y > border && y < lim) ? colin : 0u;   // inside-the-border bits of the lane's 8 columns in this row
+            const bool rowin = y > border && y < lim;                  // wave-uniform
+            const uint32_t m = rowin ? colin : 0u;   // inside-the-border bits of the lane's 8 columns in this row (CH)
+            // :28-30 uint(relevant * 100) of the row's 8 texels, once per row: 0 outside the border, w_cnr for a bright pixel inside it,
+            // w_dark_or_ramp for a dark one — a byte each (all <= 100), picked out of wrow = {0, w_cnr, 0, w_dark_or_ramp} by the byte
+            // selector (inside-the-border bit) + 2 * (`<= 0.9` bit); outside the border rows wrow is 0 altogether.
+            const uint32_t wrow = rowin ? wpair : 0u;
+            uint32_t wq[2];
+#pragma unroll
+            for (int h = 0; h < 2; h++) wq[h] = __builtin_amdgcn_perm(wrow, wrow, (spread4((le_t >> (8 * ph + 4 * h)) & 15u) << 1) | colsp[h]);
             const uint32_t chy = CH ? min(f2u((float)y / fS * (float)MUSICA_CLAHE_TILES) - ty0, 1u) : 0u;   // clahe_histogram.comp:35 (wave-uniform)
 #pragma unroll
             for (int j = 0; j < 8; j++) {
@@ -906,9 +921,9 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
                 // the clamp: max(NaN, -1) = -1 and every scaled <= -1 land on the spare word below bin 0, everything >= 1024 on the spare
                 // word above bin 1023 (neither is flushed); (-1, 0) truncates to bin 0 like the shader's int(). The clamped value indexes directly.
                 const int bin = (int)fminf(fmaxf(cur * (float)MUSICA_GRAD_BINS, -1.0f), (float)MUSICA_GRAD_BINS);
-                // :28-30 uint(relevant * 100): 0 outside the border; adding 0 leaves the histogram as it is
-                const bool le090 = ((dark >> j) & 1u) != 0u;
-                const uint32_t w = ((m >> j) & 1u) * (le090 ? w_dark_or_ramp : w_cnr);
+                // adding 0 leaves the histogram as it is
+                const bool le090 = CH && ((dark >> j) & 1u) != 0u;
+                const uint32_t w = (wq[j >> 2] >> (8 * (j & 3))) & 0xFFu;
                 atomicAdd(&lhc[bin], w);
                 if (CH) {
                     const float scaled = cur * (float)(MUSICA_CLAHE_BINS - 1) + 0.5f;                 // clahe_histogram.comp:20
@@ -980,19 +995,20 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
             }
             const CnrClass kc = classify_cnr(cnr_pair);
             const uint32_t w_cnr = kc.ramp ? kc.w_ramp : 0u, w_dark_or_ramp = kc.ramp ? kc.w_ramp : (kc.high ? 100u : 0u);
+            const uint32_t wpair = (w_cnr << 8) | (w_dark_or_ramp << 24);   // row_phase's byte table
             const float r6 = cnr_pair / 6.0f;
             const bool one_ramp = CH && kc.ramp && (((r6 * r6) * (r6 * r6)) * r6 == 1.0f);
             const bool one_dark = CH && !kc.ramp && kc.high;
             {   // even row 2k: window rows 2k - 2 .. 2k + 2, its band values are the centre row's
                 float sd[8];
                 sdev_from_band(r0, r1, r2, r3, r4, sd);
-                row_phase(0, lowE, r2.v, sd, lowE, fe, le, k, w_cnr, w_dark_or_ramp, one_ramp, one_dark);
+                row_phase(0, lowE, r2.v, sd, lowE, fe, le, k, wpair, one_ramp, one_dark);
             }
             load_brow(r0, 2 * k + 4, more);   // the slot of row 2k - 2 takes row 2k + 4 (the next trip's; nothing if there is none)
             {   // odd row 2k + 1: rows 2k - 1 .. 2k + 3
                 float sd[8];
                 sdev_from_band(r1, r2, r3, r4, r5, sd);
-                row_phase(1, lowO, r3.v, sd, lowO, fo, le, k, w_cnr, w_dark_or_ramp, one_ramp, one_dark);
+                row_phase(1, lowO, r3.v, sd, lowO, fo, le, k, wpair, one_ramp, one_dark);
             }
             load_brow(r1, 2 * k + 5, more);
             le = le_n;
@@ -1071,6 +1087,7 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
         // img_relevant.comp:44-63 for the cnr texel above the row pair (rows 2k, 2k+1 and columns c..c+7 share it)
         const CnrClass kc = classify_cnr(cnr_pair);
         const uint32_t w_cnr = kc.ramp ? kc.w_ramp : 0u, w_dark_or_ramp = kc.ramp ? kc.w_ramp : (kc.high ? 100u : 0u);   // bright / dark pixel under this texel
+        const uint32_t wpair = (w_cnr << 8) | (w_dark_or_ramp << 24);   // row_phase's byte table
         // relevant == 1.0 (CH): the ramp value itself, else 1.0 for a dark pixel under a high-cnr texel (relevant_of)
         const float r6 = cnr_pair / 6.0f;
         const bool one_ramp = CH && kc.ramp && (((r6 * r6) * (r6 * r6)) * r6 == 1.0f);
@@ -1079,11 +1096,11 @@ __device__ __forceinline__ bool expand_march(const ExpandArgs& a, const CurveLds
         // lookup — up into the even row's phase, and the wait for the odd row with them. __builtin_amdgcn_sched_barrier(0) in front of
         // either phase keeps them apart, and costs more than it saves: 153 registers, i.e. 84 bytes of scratch at 4 wavefronts per SIMD
         // (116 us) or 3 wavefronts per SIMD (85.9 us, the same as this form: 85.2 - 87.2 against 89.4 - 89.7 us before the pipeline).)
-        row_phase(0, be, be, se, lowE, fe, le, k, w_cnr, w_dark_or_ramp, one_ramp, one_dark);
+        row_phase(0, be, be, se, lowE, fe, le, k, wpair, one_ramp, one_dark);
         // the even row of the next trip into the registers the even row has just left
         load8(be, bb, goff_n + (uint32_t)(2 * kn) * rb);
         if (GAIN != GAIN_CONST) load8(se, sb, goff_n + (uint32_t)(2 * kn) * rb);
-        row_phase(1, bo, bo, so, lowO, fo, le, k, w_cnr, w_dark_or_ramp, one_ramp, one_dark);
+        row_phase(1, bo, bo, so, lowO, fo, le, k, wpair, one_ramp, one_dark);
         le = le_n;
     }
     }
