@@ -95,6 +95,12 @@ __global__ __launch_bounds__(kBlockThreads, OCC) void k_reduce_up(const float* _
 __device__ __forceinline__ void dma16nt(const Buf& b, uint32_t voff, uint32_t lds_byte) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen nt lds" ::"s"(lds_byte), "v"(voff), "s"(b.r) : "memory", "m0");
 }
+// dma16() of kernels_pyramid.hip for one dword per lane (lane l lands at M0 + 4 l): the production kernel gathers its halo columns 16 bytes at a time since round 4
+__device__ __forceinline__ void dma4(const Buf& b, uint32_t voff, uint32_t lds_byte) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dword %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "s"(lds_byte), "v"(voff), "s"(b.r) : "memory");
+}
 
 // RT output rows per workgroup of W wavefronts; NTS: non-temporal stores; NTL: non-temporal DMA loads;
 // SPLIT: the first half of the wavefronts starts computing when the upper half of the rows has landed.

@@ -3,10 +3,11 @@
     python -m metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd.build
 
 -ffp-contract=off keeps every f32 multiply and add separately rounded (the parity contract with
-oracle/musica_oracle.c); IEEE division and sqrt are hipcc's default for HIP. -fno-slp-vectorize for kernels_analysis.hip
-only (NO_SLP below): on gfx950 a packed f32 multiply or add costs what two plain ones cost and the pairs the SLP vectoriser
-builds cost v_mov on top (profiles/r04_rb0_experiments.txt) — the sdev + noise-histogram march gains 5 % at 8 x 2048^2
-(59.4 -> 56.6 us); the pyramid kernels are equal at 2048^2 and 5 % slower at 8192^2 without SLP, so they keep it.
+oracle/musica_oracle.c); IEEE division and sqrt are hipcc's default for HIP. -fno-slp-vectorize for the two files that keep a
+window of squares in registers (NO_SLP below): on gfx950 a packed f32 multiply or add costs what two plain ones cost and the
+pairs the SLP vectoriser builds cost v_mov on top (profiles/r04_rb0_experiments.txt) — the sdev + noise-histogram march gains
+5 % at 8 x 2048^2 (59.4 -> 56.6 us); the other pyramid kernels are equal at 2048^2 and 5 % slower at 8192^2 without SLP, so
+they keep it.
 """
 import os
 import subprocess
@@ -19,8 +20,8 @@ CLI = os.path.join(HERE, "musica-standalone")
 HIP_SOURCES = ["kernels_pyramid.hip", "kernels_expand_sd.hip", "kernels_analysis.hip", "kernels_gradation.hip", "kernels_clahe.hip", "kernels_bench.hip",
                "kernels_similarity.hip", "kernels_joint.hip", "kernels_displace.hip", "kernels_scales.hip", "kernels_ensemble.hip", "kernels_covariance.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_blur.hip", "kernels_zoom.hip", "kernels_scatter.hip", "kernels_details.hip", "kernels_edges.hip", "kernels_gratings.hip", "kernels_gain.hip", "kernels_export.hip", "musica_ctx.hip", "musica_step.hip", "musica_pipeline.hip", "musica_study.hip"]
 CPP_SOURCES = ["musica_io.cpp"]
-HEADERS = ["musica_device.h", "kernels_common.h", "exact_math.h", "curve_lut.h", "sdev_parts.h", "grad_parts.h", "launchers.h", "study_device.h", "musica_ctx.h", os.path.join("..", "..", "include", "musica.h")]
-NO_SLP = {"kernels_analysis.hip", "kernels_expand_sd.hip"}   # kernels_expand_sd.hip: kernels_pyramid.hip's expand march again, for the launches that compute sdev in registers
+HEADERS = ["musica_device.h", "kernels_common.h", "exact_math.h", "curve_lut.h", "sdev_parts.h", "grad_parts.h", "launchers.h", "pyramid_march.h", "study_device.h", "musica_ctx.h", os.path.join("..", "..", "include", "musica.h")]
+NO_SLP = {"kernels_analysis.hip", "kernels_expand_sd.hip"}   # kernels_expand_sd.hip: the pyramid launches that keep a window of squares in registers (SD expand, level 0's histogram march, the paired launch)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 
@@ -49,8 +50,7 @@ def build(force=False, verbose=False):
         sp = os.path.join(CSRC, src)
         obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         objs.append(obj)
-        deps = [sp] + headers + ([os.path.join(CSRC, "kernels_pyramid.hip")] if src == "kernels_expand_sd.hip" else [])
-        if force or _stale(obj, deps):
+        if force or _stale(obj, [sp] + headers):
             cmd = [hipcc] + FLAGS + (["-fno-slp-vectorize"] if src in NO_SLP else []) + (["-x", "hip"] if src.endswith(".hip") else []) + ["-c", sp, "-o", obj]
             if verbose:
                 print(" ".join(cmd))
@@ -75,36 +75,49 @@ def build(force=False, verbose=False):
     return LIB
 
 
-def _kernel_body(obj_name, wanted):
-    """The disassembly lines of the kernels of build/<obj_name>.o's gfx950 code object whose label line `wanted` accepts
-    (llvm-objdump --offloading, then -d). Raises RuntimeError when the tool, the object or the code object is missing."""
+def _code_object_text(obj, *commands):
+    """What each of `commands` (an llvm tool's name and its arguments, e.g. ("llvm-objdump", "-d")) prints about the gfx950 code object
+    inside `obj` (llvm-objdump --offloading takes it out first): one string per command. `obj` is a path to an object file, or a bare
+    name such as "kernels_analysis" for build/<name>.o. Raises RuntimeError when the tool, the object or the code object is missing."""
     import glob
     import shutil
     import tempfile
-    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+    llvm = "/opt/rocm/lib/llvm/bin"
+    objdump = os.path.join(llvm, "llvm-objdump")
     if not os.path.exists(objdump):
-        raise RuntimeError("llvm-objdump not found under /opt/rocm/lib/llvm/bin")
-    obj = os.path.join(HERE, "build", obj_name + ".o")
+        raise RuntimeError("llvm-objdump not found under %s" % llvm)
+    if not obj.endswith(".o"):
+        obj = os.path.join(HERE, "build", obj + ".o")
     if not os.path.exists(obj):
         raise RuntimeError("%s is not built" % obj)
     td = tempfile.mkdtemp(prefix="musica_isa_")
     try:
-        copy = os.path.join(td, obj_name + ".o")
+        copy = os.path.join(td, os.path.basename(obj))
         shutil.copy(obj, copy)
         subprocess.run([objdump, "--offloading", copy], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=td)   # writes <copy>.0.hipv4-...gfx950
         outs = glob.glob(copy + ".*gfx950")
         if not outs:
             raise RuntimeError("no gfx950 code object inside %s" % obj)
-        text = subprocess.run([objdump, "-d", outs[0]], check=True, stdout=subprocess.PIPE, text=True).stdout
+        return [subprocess.run([os.path.join(llvm, c[0])] + list(c[1:]) + [outs[0]], check=True, stdout=subprocess.PIPE, text=True).stdout for c in commands]
     finally:
         shutil.rmtree(td, ignore_errors=True)
-    body, inside = [], False
+
+
+def _kernel_bodies(text):
+    """`llvm-objdump -d` output as {label line: the disassembly lines below it}, in the listing's order."""
+    bodies, body = {}, None
     for line in text.splitlines():
         if line.endswith(">:"):
-            inside = wanted(line)
-        elif inside:
+            body = bodies.setdefault(line, [])
+        elif body is not None:
             body.append(line)
-    return body
+    return bodies
+
+
+def _kernel_body(obj, wanted):
+    """The disassembly lines of the kernels of `obj`'s gfx950 code object whose label line `wanted` accepts (`obj` as _code_object_text takes it)."""
+    text, = _code_object_text(obj, ("llvm-objdump", "-d"))
+    return [line for label, body in _kernel_bodies(text).items() if wanted(label) for line in body]
 
 
 def check_isa():

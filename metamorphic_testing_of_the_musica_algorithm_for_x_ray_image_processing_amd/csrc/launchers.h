@@ -73,9 +73,13 @@ void launch_reduce_band_u16(hipStream_t st, const uint16_t* px, float* down, flo
 void launch_reduce_band(hipStream_t st, const float* fine, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch, int rows_per_wave,
                         int swz);
 void launch_lowpass(hipStream_t st, const float* coarse, float* low, const LevelDesc& lf, const LevelDesc& lc, int batch, int ref = 0);
-void launch_expand(hipStream_t st, const ExpandArgs& a, int gain_mode, bool nr, int batch, bool force_generic);
+void launch_expand(hipStream_t st, const ExpandArgs& a, int gain_mode, bool nr, int batch, bool force_generic);   // a.sdev == nullptr (GAIN_CURVE): hands over to launch_expand_sd
+// reduce + band of the levels in `a`, then their expand slots, one workgroup per image (levels of side <= kTailSide)
+void launch_tiny_tail(hipStream_t st, const TailArgs& a, int batch);
+void launch_exp_band(hipStream_t st, const ExpandArgs& a, int gain_mode, bool nr, int batch);
+// kernels_expand_sd.hip (the pyramid launches that keep a window of squares in registers)
 // reduce + band of level i + 1 AND the sdev + noise-histogram pass of level i in one launch (both read what the reduce + band launch of level i wrote
-// and nothing of each other; kernels_expand_sd.hip). Workgroups 0 .. of grid.x take the sdev pass (sl.first = 0), the rest the reduce + band launch.
+// and nothing of each other). Workgroups 0 .. of grid.x take the sdev pass (sl.first = 0), the rest the reduce + band launch.
 struct RbSdevArgs {
     const float* fine; float* down; float* band;   // reduce + band of level i + 1: its fine image, coarse image, band image
     int S, pitch; size_t plane; int Sc, cpitch; size_t cplane; int rows_rb;
@@ -86,17 +90,14 @@ struct RbSdevArgs {
     int seam_items;                                // filled in by launch_rb_sdev
 };
 void launch_rb_sdev(hipStream_t st, RbSdevArgs a, const LevelDesc& ls, int batch);
-// launch_reduce_band_u16 that also counts level 0's noise histogram (k_reduce_band_hist, kernels_expand_sd.hip) except for the two columns
+// launch_reduce_band_u16 that also counts level 0's noise histogram (k_reduce_band_hist) except for the two columns
 // either side of every interior strip boundary: launch_hist_seam, or the sdev role of launch_rb_sdev with sl.rows < 0, counts those from
 // the stored band image. rows_per_wave % 8 == 0. hist: image 0's level-0 histogram.
 void launch_reduce_band_u16_hist(hipStream_t st, const uint16_t* px, float* down, float* band, const LevelDesc& lf, const LevelDesc& lc, int batch,
                                  int rows_per_wave, const uint32_t* minmax, int min_chain_exact, uint16_t* le090, int swz, uint32_t* hist,
                                  size_t hist_stride, int cov);
 void launch_hist_seam(hipStream_t st, const float* band, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov, int batch);
-void launch_expand_sd(hipStream_t st, const ExpandArgs& a, bool nr, int batch);   // a.sdev == nullptr: sdev computed by the launch (kernels_expand_sd.hip)
-// reduce + band of the levels in `a`, then their expand slots, one workgroup per image (levels of side <= kTailSide)
-void launch_tiny_tail(hipStream_t st, const TailArgs& a, int batch);
-void launch_exp_band(hipStream_t st, const ExpandArgs& a, int gain_mode, bool nr, int batch);
+void launch_expand_sd(hipStream_t st, const ExpandArgs& a, bool nr, int batch);   // a.sdev == nullptr: sdev computed by the launch
 // kernels_analysis.hip
 void launch_clear(hipStream_t st, uint32_t* minmax, uint32_t* noise_hist, uint32_t* grad_hist, uint32_t* clahe_hist, int batch, uint32_t* grad_hist_b = nullptr, uint32_t* gzero = nullptr);
 // min / max of the raw pixels (slots: [batch][kMinMaxSlots] words, ticket: [batch] words, zero at first use) and, where the pointers are

@@ -1,5 +1,6 @@
 // sdev_parts.h — the per-row pieces of the fused 5x5 RMS + noise-histogram march (img_sdev.comp + noise_hist.comp),
-// shared by k_sdev_hist* (kernels_analysis.hip) and the band+sdev kernel (kernels_pyramid.hip).
+// shared by k_sdev_hist* (kernels_analysis.hip), the level-0 reduce + band march that counts its own histogram (pyramid_march.h) and
+// the paired reduce + band / sdev launch (kernels_expand_sd.hip).
 #pragma once
 
 #include "kernels_common.h"
