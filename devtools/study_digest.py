@@ -17,7 +17,9 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     of the same gratings, shifted into the output plane, of image 1's output against slot 0;
   * the gain pair at N = 151 (odd: the single-pixel form): a map whose tables run over 0 .. 65535 applied into image 0, and the
     profiles of image 1's output against slot 0 over the full frame (3 x 3 tiles with a ragged tail), a ragged region from mid-tile
-    with different origins on the two sides, a single column and a single pixel.
+    with different origins on the two sides, a single column and a single pixel;
+  * the tone-table pair at N = 151: a permutation of the 65536 levels applied into image 0, and the levels of image 1's output against
+    slot 0 over the same four regions, the classes the source plane >> 4 (4096 classes) and >> 9 (128).
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -124,5 +126,9 @@ ramp = (np.arange(N, dtype=np.int64) * 65535) // (N - 1)
 p.alter_gain(ramp, ramp[::-1] // 9)
 note("musica_alter_gain", p.input_pixels()[0])
 note("musica_sim_profiles", p.sim_profiles([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (1, 0, 64, 0, 64, 0, 1, NW), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)]))
+p.alter_lut((np.arange(65536, dtype=np.int64) * 40503 + 77) % 65536)   # a permutation of the levels
+note("musica_alter_lut", p.input_pixels()[0])
+for shift in (4, 9):
+    note("musica_sim_levels_s%d" % shift, p.sim_levels([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (1, 0, 64, 0, 64, 0, 1, NW), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)], shift))
 p.cleanup()
 print(json.dumps(digests))

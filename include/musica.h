@@ -935,6 +935,50 @@ typedef struct musica_sim_profile_result {
 int musica_sim_profiles(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_profile_result* results,
                         uint32_t* tables, uint64_t table_words);
 
+/* ---- tone tables: a point-wise map of the input's gray levels, and the output per input level (new, not in the reference) ----
+ * Every other alteration moves, blurs, shades or adds to the input; none changes its gray levels point-wise: a dark-current pedestal,
+ * a non-linear detector characteristic, a coarser ADC, saturation, a negative. That is the axis on which MUSICA promises most (sqrt,
+ * min, max and normalise in front, a tone curve built from the image's own histogram behind). One table covers them, out = lut[v], and
+ * one measurement scores them: the exact sums of a comparison kept apart by the level of the INPUT pixel, which give the chain's
+ * characteristic curve (mean output per input level) before and after, and split the change of the output into a part that is a
+ * function of the input level alone and a remainder. harness.apply_lut and harness.level_statistics are the contract; everything the
+ * device computes is integer and bit-identical to them, from call to call as well.
+ * A table holds MUSICA_LUT_ENTRIES uint16_t, one for every value a raw pixel can take; every table is allowed. The identity copies. */
+#define MUSICA_LUT_ENTRIES 65536
+/* apply_lut(source plane, lut) into image `image_index` of the input buffer: lut holds MUSICA_LUT_ENTRIES host values. The kernel is
+ * enqueued on the ctx stream (the table is copied to a context-owned 128 KiB device buffer first, allocated on first use, which waits
+ * for what the stream holds), with musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step
+ * and no reference slot. One launch, 2 bytes read and 2 written per pixel, the table staged in LDS (kernels_levels.hip). An
+ * entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT. Refused before any device
+ * work: a NULL context or table, no source, image_index >= batch. */
+int musica_alter_lut(musica_ctx* ctx, uint32_t image_index, const uint16_t* lut);
+/* The levels of `count` (1 .. MUSICA_LEVEL_MAX_QUERIES) comparisons in one launch. A query is musica_sim_compare's: side a the 8-bit
+ * output of batch image `image_index` (quantised while read, exactly as musica_sim_compare reads it), side b reference slot `slot`, the
+ * region (ax, ay) / (bx, by), w x h with w, h >= 1. The class of a-side pixel (x, y) of the output plane is
+ *   source[(y + MUSICA_OUT_MARGIN) * N + x + MUSICA_OUT_MARGIN] >> shift
+ * with the alteration source plane (musica_alter_set_source) and shift in MUSICA_LEVEL_MIN_SHIFT .. MUSICA_LEVEL_MAX_SHIFT, so there
+ * are C = (65535 >> shift) + 1 <= 4096 classes: the level of the unaltered input under the pixel, whatever origin side b has. Query i
+ * gets a table [C][MUSICA_LEVEL_WORDS] of uint64_t in the flat `tables`, from results[i].table_offset (in words: i * C *
+ * MUSICA_LEVEL_WORDS) on. A class's six words are the exact
+ *   n, sum_a, sum_b, sum_dd = sum of (a - b)^2, sum_aa, sum_bb
+ * over the region's pixels of that class. The n of a table add up to w * h and results[i].ssd, the sum of its sum_dd, equals
+ * musica_sim_compare's sq_diff_sum over the same region. table_words, the words `tables` has room for, must be at least count * C *
+ * MUSICA_LEVEL_WORDS. Synchronous; integers only, byte-identical from call to call. Refused before any device work: what
+ * musica_sim_compare refuses, except that the smallest side is 1 and the largest count MUSICA_LEVEL_MAX_QUERIES, then no source plane,
+ * a shift out of range, a NULL `tables`, and table_words too small. After a refusal the context stays usable. */
+#define MUSICA_LEVEL_MAX_QUERIES 4
+#define MUSICA_LEVEL_MIN_SHIFT 4
+#define MUSICA_LEVEL_MAX_SHIFT 15
+#define MUSICA_LEVEL_WORDS 6
+typedef struct musica_sim_level_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t classes;               /* C */
+    uint64_t ssd;                   /* sum over the region of (a - b)^2 */
+    uint64_t pixels;                /* w * h */
+} musica_sim_level_result;
+int musica_sim_levels(musica_ctx* ctx, uint32_t shift, uint32_t count, const musica_sim_query* queries, musica_sim_level_result* results,
+                      uint64_t* tables, uint64_t table_words);
+
 /* ---- device-resident output and stream ordering (new, not in the reference) ---- */
 
 /* What musica_export_out writes per image. */

@@ -118,17 +118,6 @@ __device__ __forceinline__ void row_sum(T&... v) {
     ((v += row_up<1>(v)), ...);
 }
 
-// n >= 1 consecutive bytes at p as one word, byte k in bits 8k: the first four when n >= 4 (one load), else the n of a ragged tail
-__device__ __forceinline__ uint32_t load_bytes4(const GlobalU8* p, int n) {
-    uint32_t word = 0u;
-    if (n >= 4) {
-        __builtin_memcpy(&word, p, 4);   // 1-byte aligned
-        return word;
-    }
-    for (int k = 0; k < n; k++) word |= (uint32_t)p[k] << (8 * k);
-    return word;
-}
-
 __global__ __launch_bounds__(kStudyThreads) void k_sim_profiles(const ProfileQueryDev* __restrict__ qs, uint32_t* __restrict__ tables) {
     __shared__ uint4 col_part[kStudyWaves][kSimTile];
     __shared__ uint4 row_part[kSimTile];

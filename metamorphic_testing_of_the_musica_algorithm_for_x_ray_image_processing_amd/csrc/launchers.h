@@ -400,6 +400,27 @@ struct ProfileQueryDev : SimRegion {
 // harness.profile_statistics over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y). tables: every query's words,
 // zeroed by the caller: the tiles add their partials with u32 atomics
 void launch_sim_profiles(hipStream_t st, const ProfileQueryDev* d_qs, int count, int max_tiles, uint32_t* tables);
+// kernels_levels.hip: the tone-table relation. harness.apply_lut(src, lut) of a dense n x n plane into another (the planes must not
+// overlap); any n >= 1. d_lut: the table's kLutEntries u16 on the device
+constexpr int kLutEntries = 65536;        // a value for every u16
+constexpr int kLevelMaxQueries = 4;       // MUSICA_LEVEL_MAX_QUERIES
+constexpr int kLevelMinShift = 4;         // MUSICA_LEVEL_MIN_SHIFT
+constexpr int kLevelMaxShift = 15;        // MUSICA_LEVEL_MAX_SHIFT
+constexpr int kLevelMaxClasses = 4096;    // (65535 >> kLevelMinShift) + 1
+constexpr int kLevelWords = 6;            // u64 of a class: n, sum a, sum b, sum (a - b)^2, sum a^2, sum b^2
+void launch_alter_lut(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const uint16_t* d_lut);
+// One comparison of musica_sim_levels. s: the source plane at side a's pixel (0, 0), s_pitch in elements; chunk_rows / chunks: launch
+// geometry (level_geometry); table: where its [classes][kLevelWords] u64 start in the launch's flat tables, in words.
+struct LevelQueryDev : SimRegion {
+    const uint16_t* s;
+    int s_pitch;
+    int chunk_rows, chunks;
+    unsigned long long table;
+};
+void level_geometry(LevelQueryDev& q, int count);   // count: the queries of the launch
+// harness.level_statistics over `count` queries with the classes source >> shift (grid.x = min(max_chunks, 128 / count)). tables: every
+// query's words, zeroed by the caller: the workgroups add into them with u64 atomics
+void launch_sim_levels(hipStream_t st, const LevelQueryDev* d_qs, int count, int max_chunks, int shift, unsigned long long* tables);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -154,6 +154,10 @@ struct StudyState {
     ProfileQueryDev* d_profile_q = nullptr;        // [MUSICA_PROFILE_MAX_QUERIES]
     uint32_t* d_profile_tables = nullptr;          // the tables of one call: profile_tables_cap u32, regrown when a call needs more
     size_t profile_tables_cap = 0;
+    // musica_alter_lut: the device copy of the call's table; musica_sim_levels: the queries and the flat tables
+    uint16_t* d_lut = nullptr;                     // [kLutEntries] (128 KiB), allocated by the first musica_alter_lut
+    LevelQueryDev* d_level_q = nullptr;            // [MUSICA_LEVEL_MAX_QUERIES]
+    unsigned long long* d_level_tables = nullptr;  // [MUSICA_LEVEL_MAX_QUERIES][kLevelMaxClasses][kLevelWords] (768 KiB), allocated by the first musica_sim_levels
 };
 
 struct musica_ctx : DeviceBuffers {

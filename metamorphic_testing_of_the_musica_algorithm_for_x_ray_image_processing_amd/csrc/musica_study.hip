@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip, kernels_levels.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
@@ -869,6 +869,53 @@ int musica_sim_profiles(musica_ctx* c, uint32_t count, const musica_sim_query* q
     ABI_CATCH("musica_sim_profiles")
 }
 
+// ---- the levels of a comparison (musica_sim_levels, include/musica.h; kernels_levels.hip) -----------------------------------------------
+static_assert(kLevelMaxQueries == MUSICA_LEVEL_MAX_QUERIES && kLevelMinShift == MUSICA_LEVEL_MIN_SHIFT && kLevelMaxShift == MUSICA_LEVEL_MAX_SHIFT &&
+                  kLutEntries == MUSICA_LUT_ENTRIES && kLevelWords == MUSICA_LEVEL_WORDS,
+              "kernels_levels.hip's limits are include/musica.h's");
+
+int musica_sim_levels(musica_ctx* c, uint32_t shift, uint32_t count, const musica_sim_query* qs, musica_sim_level_result* out, uint64_t* tables, uint64_t table_words) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_levels", count, qs, out, 1, MUSICA_LEVEL_MAX_QUERIES)) return 0;
+    if (!c->study.d_alter_src) return fail("musica_sim_levels: no source plane (musica_alter_set_source)");
+    if (shift < MUSICA_LEVEL_MIN_SHIFT || shift > MUSICA_LEVEL_MAX_SHIFT)
+        return fail("musica_sim_levels: shift %u out of range [%d, %d]", shift, MUSICA_LEVEL_MIN_SHIFT, MUSICA_LEVEL_MAX_SHIFT);
+    if (!tables) return fail("musica_sim_levels: tables is NULL");
+    const size_t classes = (65535u >> shift) + 1, per_query = classes * kLevelWords, words = count * per_query;
+    if (table_words < words) return fail("musica_sim_levels: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_level_q, MUSICA_LEVEL_MAX_QUERIES) && ensure(c, &st.d_level_tables, (size_t)MUSICA_LEVEL_MAX_QUERIES * kLevelMaxClasses * kLevelWords)))
+        return fail("musica_sim_levels: device allocation failed");
+    std::vector<LevelQueryDev> hq(count);
+    int max_chunks = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        sim_region(c, qs[i], hq[i]);
+        hq[i].s = st.d_alter_src + (size_t)(qs[i].ay + MUSICA_OUT_MARGIN) * c->N + qs[i].ax + MUSICA_OUT_MARGIN;   // the class is taken at side a's coordinates
+        hq[i].s_pitch = c->N;
+        hq[i].table = i * per_query;
+        level_geometry(hq[i], (int)count);
+        max_chunks = std::max(max_chunks, hq[i].chunks);
+    }
+    HIP_OK(hipMemcpyAsync(st.d_level_q, hq.data(), count * sizeof(LevelQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_level_tables, 0, words * sizeof(uint64_t), c->stream));   // the workgroups add into them
+    launch_sim_levels(c->stream, st.d_level_q, (int)count, max_chunks, (int)shift, st.d_level_tables);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(tables, st.d_level_tables, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        const uint64_t* t = tables + hq[i].table;
+        uint64_t ssd = 0;
+        for (size_t k = 0; k < classes; k++) ssd += t[k * kLevelWords + 3];
+        out[i].table_offset = hq[i].table;
+        out[i].classes = classes;
+        out[i].ssd = ssd;
+        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
+    }
+    return 1;
+    ABI_CATCH("musica_sim_levels")
+}
+
 // ---- ensemble statistics (musica_sim_ensemble_*, include/musica.h; kernels_ensemble.hip) ------------------------------------------------
 int musica_sim_ensemble_reset(musica_ctx* c) {
     ABI_TRY
@@ -1274,6 +1321,20 @@ int musica_alter_gain(musica_ctx* c, uint32_t idx, const uint16_t* gx, const uin
         },
         [&](const uint16_t* src, uint16_t* dst) { launch_alter_gain(c->stream, src, dst, c->N, c->study.d_gain_x, c->study.d_gain_y); });   // kernels_gain.hip
     ABI_CATCH("musica_alter_gain")
+}
+
+int musica_alter_lut(musica_ctx* c, uint32_t idx, const uint16_t* lut) {
+    ABI_TRY
+    return alter_into(
+        c, "musica_alter_lut", !lut ? "lut" : nullptr, idx, nothing,
+        [&] {
+            if (!ensure(c, &c->study.d_lut, (size_t)MUSICA_LUT_ENTRIES)) return fail("musica_alter_lut: device allocation of the table failed");
+            HIP_OK(hipMemcpyAsync(c->study.d_lut, lut, (size_t)MUSICA_LUT_ENTRIES * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipStreamSynchronize(c->stream));   // the caller's table has been read
+            return 1;
+        },
+        [&](const uint16_t* src, uint16_t* dst) { launch_alter_lut(c->stream, src, dst, c->N, c->study.d_lut); });   // kernels_levels.hip
+    ABI_CATCH("musica_alter_lut")
 }
 
 int musica_alter_draws(musica_ctx* c, const musica_alteration* s, int32_t* dst) {

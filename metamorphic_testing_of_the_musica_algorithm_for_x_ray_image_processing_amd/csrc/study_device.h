@@ -1,6 +1,6 @@
 // study_device.h — what the study's kernels share on the device (kernels_similarity.hip, kernels_scales.hip, kernels_joint.hip,
 // kernels_displace.hip, kernels_covariance.hip, kernels_ensemble.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip,
-// kernels_gain.hip): the address-space typedefs, the reductions and their ONE order, the 64 x 64 tile of a region, the pixel words of
+// kernels_gain.hip, kernels_levels.hip): the address-space typedefs, the reductions and their ONE order, the 64 x 64 tile of a region, the pixel words of
 // the kernels that stream a u16 plane and the insertion body of the patch relations (insert_patches), the packed byte windows of
 // k_displace and k_cov_add, and the per-window SSIM terms.
 #pragma once
@@ -224,6 +224,17 @@ __device__ __forceinline__ uint32_t load_quant4(const GlobalF32* p, int n) {
     }
     uint32_t word = 0u;
     for (int k = 0; k < n; k++) word |= out_u8(p[k]) << (8 * k);
+    return word;
+}
+
+// n >= 1 consecutive bytes at p as one word, byte k in bits 8k: the first four when n >= 4 (one load), else the n of a ragged tail
+__device__ __forceinline__ uint32_t load_bytes4(const GlobalU8* p, int n) {
+    uint32_t word = 0u;
+    if (n >= 4) {
+        __builtin_memcpy(&word, p, 4);   // 1-byte aligned
+        return word;
+    }
+    for (int k = 0; k < n; k++) word |= (uint32_t)p[k] << (8 * k);
     return word;
 }
 

@@ -281,6 +281,70 @@ def apply_gain(image, gx, gy):
     return np.minimum((image.astype(np.uint64) * g + np.uint64(1 << 23)) >> np.uint64(24), np.uint64(65535)).astype(np.uint16)
 
 
+# not in the reference: the tone-table rows (apply_lut), rows named by the spec of a study run with `luts`: the raw image mapped point-wise
+# through a 65536-entry table, out = lut[v], scored like every row and by the exact sums of the result against the unaltered result per
+# level of the unaltered INPUT (level_statistics): the chain's characteristic curve before and after. A spec is (name, lut); LUTS(raw)
+# gives the 21 of a raw plane, built from its own range: a pedestal, saturation, a coarser ADC, a non-linear characteristic, a negative.
+LUT_CONTRASTS = (8, 16, 32, 64, 128)
+LUT_BITS = (12, 10, 8, 7, 6)
+LUT_GAMMAS = ((3, 4), (9, 10), (11, 10), (5, 4), (3, 2))
+
+
+def LUTS(raw):
+    """The 21 tone-table specs (name, lut) of a raw plane, each lut a uint16 array of 65536 entries, from the plane's own range lo =
+    min, hi = max, span = hi - lo (ValueError if span < 1024); v runs over 0 .. 65535 and c over LUT_CONTRASTS:
+        offset_<c>          min(v + ((c span + 512) >> 10), 65535): a dark-current pedestal of c / 1024 of the span
+        clip_<c>            min(v, hi - ((c span) >> 10)): saturation of the top c / 1024 of the span
+        bits_<b>            v & ~((1 << s) - 1) with s = max(0, span.bit_length() - b), b in LUT_BITS: an ADC that leaves about b bits
+                            of the span
+        gamma_<num>_<den>   lo + rint(span ((v - lo) / span)^(num / den)) on lo <= v <= hi, v outside, (num, den) in LUT_GAMMAS: a
+                            non-linear characteristic that keeps both ends of the range (f64 pow, here, once: the table is the payload)
+        negative            lo + hi - v on lo <= v <= hi, v outside
+    Every table but `negative` is non-decreasing."""
+    raw = np.asarray(raw)
+    if raw.dtype != np.uint16 or not raw.size:
+        raise ValueError("LUTS needs a non-empty uint16 plane, got %r %s" % (raw.shape, raw.dtype))
+    lo, hi = int(raw.min()), int(raw.max())
+    span = hi - lo
+    if span < 1024:
+        raise ValueError("the plane's range %d .. %d spans less than 1024 levels" % (lo, hi))
+    v = np.arange(mp.LUT_ENTRIES, dtype=np.int64)
+    inside = (v >= lo) & (v <= hi)
+    out = [("offset_%d" % c, np.minimum(v + ((c * span + 512) >> 10), 65535)) for c in LUT_CONTRASTS]
+    out += [("clip_%d" % c, np.minimum(v, hi - ((c * span) >> 10))) for c in LUT_CONTRASTS]
+    out += [("bits_%d" % b, v & ~((1 << max(0, span.bit_length() - b)) - 1)) for b in LUT_BITS]
+    unit = np.clip((v - lo) / span, 0.0, 1.0)
+    out += [("gamma_%d_%d" % (num, den), np.where(inside, lo + np.rint(span * np.power(unit, num / den)).astype(np.int64), v)) for num, den in LUT_GAMMAS]
+    out.append(("negative", np.where(inside, lo + hi - v, v)))
+    return tuple((name, lut.astype(np.uint16)) for name, lut in out)
+
+
+def apply_lut(image, lut):
+    """The square 2-D uint16 plane mapped point-wise through the tone table (processing.lut_table: 65536 integers in 0 .. 65535, else
+    ValueError before any work): lut[image]. lut = arange(65536) copies the image. This is the contract of musica_alter_lut
+    (include/musica.h), which is bit-identical to it."""
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype != np.uint16 or not image.size:
+        raise ValueError("apply_lut needs a non-empty square 2-D uint16 plane, got %r %s" % (image.shape, image.dtype))
+    return mp.lut_table(lut)[image]
+
+
+def level_shift(raw):
+    """The shift of a study's classes: the smallest that puts raw.max() below 4096 classes, and never less than LEVEL_MIN_SHIFT = 4."""
+    return max(mp.LEVEL_MIN_SHIFT, int(np.asarray(raw).max()).bit_length() - 12)
+
+
+def level_classes(raw, shift):
+    """The class plane of the output of a square 2-D uint16 raw plane: raw[M:-M, M:-M] >> shift with M = PROCESSING_MARGIN, the level of
+    the unaltered input under every output pixel; shift an integer 4 .. 15 (processing.level_count: (65535 >> shift) + 1 <= 4096
+    classes), else ValueError."""
+    mp.level_count(shift)
+    raw = np.asarray(raw)
+    if raw.ndim != 2 or raw.shape[0] != raw.shape[1] or raw.dtype != np.uint16 or raw.shape[0] <= 2 * PROCESSING_MARGIN:
+        raise ValueError("level_classes needs a square 2-D uint16 plane of a side above %d, got %r %s" % (2 * PROCESSING_MARGIN, raw.shape, raw.dtype))
+    return raw[PROCESSING_MARGIN:-PROCESSING_MARGIN, PROCESSING_MARGIN:-PROCESSING_MARGIN] >> np.uint16(shift)
+
+
 def scaled(values, image_size):
     """The reference's pixel-valued grids scaled from 3072 to `image_size`."""
     return [max(1, int(round(v * image_size / REF_IMAGE_SIZE))) for v in values]
@@ -706,14 +770,15 @@ TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "referenc
 VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
 
 
-# The four patch relations of the study, each one row of this table. key: the row key of its measurement; option / tables: run_study's
+# The five relations of the study that measure beyond a row's comparisons, each one row of this table. key: the row key of its measurement; option / tables: run_study's
 # argument with its payloads (a grid, a gain spec) and the flag that keeps the raw tables; check(payloads, n): the payloads checked for a
 # raw plane of side n and, as output() maps them, for the output plane (ValueError), normalised; name(payload): the row's name;
 # insert(raw, payload): the host's altered raw image; alter(proc, payload): the same on the device; output(payload): the payload in the
 # coordinates of the output plane, what is measured; host(out, reference, measured) and device(proc, measured, shape): the exact
 # integers of the output against the unaltered result; frame: whether summarise also takes the full frame's sq_diff_sum and pixels;
-# summarise(measured, statistics, [sq_diff_sum, pixels,] tables): the row's value.
-Relation = collections.namedtuple("Relation", "key option tables check name insert alter output host device frame summarise")
+# summarise(measured, statistics, [sq_diff_sum, pixels,] tables): the row's value; source(raw): what the measurement takes from the raw
+# plane itself, once per study, appended to every payload of the relation's rows (None: nothing).
+Relation = collections.namedtuple("Relation", "key option tables check name insert alter output host device frame summarise source", defaults=(None,))
 
 
 def _checked_grids(list_of):
@@ -737,6 +802,17 @@ def _checked_gains(gains, n):
     return gains
 
 
+def _checked_luts(luts, n):
+    """Relation.check of the tone-table relation: every spec is a name and a table of 65536 values in u16."""
+    try:
+        luts = [(str(name), mp.lut_table(lut)) for name, lut in luts]
+    except TypeError:
+        raise ValueError("a lut spec is (name, lut), got %r" % (luts,))
+    if n <= 2 * PROCESSING_MARGIN:
+        raise ValueError("a side of %d pixels leaves no output plane to take levels of" % n)
+    return luts
+
+
 def _frame(shape):
     return (0, 0, 0, 0, shape[1], shape[0])
 
@@ -755,12 +831,18 @@ RELATIONS = (
     Relation("profiles", "gains", "gain_tables", _checked_gains, lambda g: g[0], lambda raw, g: apply_gain(raw, g[1], g[2]), lambda p, g: p.alter_gain(g[1], g[2]),
              output_gain, lambda out, ref, m: profile_statistics(out, ref, [_frame(out.shape)])[0],
              lambda p, m, shape: p.sim_profiles([(0, SLOT_UNALTERED) + _frame(shape)])[0], False, lambda m, stats, tables: profile_row(stats, m[0], m[1], tables)),
+    # the levels are taken over the full output frame; a payload: (name, lut, (shift, the class plane)), measured: the pair the study's raw plane gave
+    Relation("levels", "luts", "lut_tables", _checked_luts, lambda s: s[0], lambda raw, s: apply_lut(raw, s[1]), lambda p, s: p.alter_lut(s[1]),
+             lambda s: s[2], lambda out, ref, m: level_statistics(out, ref, m[1], [_frame(out.shape)], mp.level_count(m[0]))[0],
+             lambda p, m, shape: p.sim_levels([(0, SLOT_UNALTERED) + _frame(shape)], m[0])[0]["table"], True,
+             lambda m, table, sq_diff_sum, pixels, tables: level_row(table, sq_diff_sum, pixels, tables),
+             lambda raw: (level_shift(raw), level_classes(raw, level_shift(raw)))),
 )
 
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
-                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False):
+                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -796,7 +878,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
             raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
     zooms = [mp.zoom_ratio(z) for z in (zooms or ())]
     scatters = [mp.scatter_spec(s) for s in (scatters or ())]
-    given = dict(details=details, edges=edges, gratings=gratings, gains=gains)
+    given = dict(details=details, edges=edges, gratings=gratings, gains=gains, luts=luts)
     for rel in RELATIONS:
         if given[rel.option] is not None:
             given[rel.option] = rel.check(given[rel.option], n)
@@ -810,7 +892,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
-        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), keys=keys, device_alterations=device_alterations,
+        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
 
 
@@ -818,15 +900,15 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
 # region() the region of the registered comparison (None, or no region at all as for the noise rows: no registration); move = (the
 # context's method, the host's function, their parameter), which both move a reference plane as the alteration moves the input: the
 # registered comparison is then against the moved plane; noise = (the row's ordinal, alter(context, stream, image_index)) for the rows
-# that draw, what their ensembles repeat; measure = (relation, payload) for the rows of a patch relation (RELATIONS): what the row
-# measures beyond its comparisons, the raw plane's grid or gain spec.
+# that draw, what their ensembles repeat; measure = (relation, payload) for the rows of a relation (RELATIONS): what the row
+# measures beyond its comparisons, the raw plane's grid, gain spec or lut spec (with what Relation.source took from the raw plane).
 Alteration = collections.namedtuple("Alteration", "name host dev region move noise measure", defaults=(None, None, None, None))
 
 
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4, blur, zoom, scatter, cd, edge, grating and gain rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur, zoom, scatter, cd, edge, grating, gain and lut rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -862,7 +944,9 @@ def study_alterations(raw, rng, p, seed, shape, opt):
         yield Alteration("scatter_%d_%d_%d" % s, lambda: scatter(raw, s), lambda: p.alter_scatter(s), lambda: roi_scatter(shape, s),
                          ("sim_scatter_reference", scatter, s))
     for rel in RELATIONS:
-        for g in getattr(opt, rel.option):
+        payloads = getattr(opt, rel.option)
+        carried = (rel.source(raw),) if rel.source and payloads else ()
+        for g in (tuple(g) + carried if carried else g for g in payloads):
             yield Alteration(rel.name(g), lambda: rel.insert(raw, g), lambda: rel.alter(p, g), measure=(rel, g))
 
 
@@ -1044,7 +1128,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
-              gains=None, gain_tables=False):
+              gains=None, gain_tables=False, luts=None, lut_tables=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1188,11 +1272,27 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     device summarise exact integers with one function, so "profiles" is equal to the last bit on every path. gain_tables: the dict
     also carries "tables" and "gains", the raw integers. The rows draw nothing from `rng` and take no ordinal. Nothing is asserted:
     these are findings. A processor that normalises would show no transfer at all; what survives of a line far below the pixel noise,
-    and how far it spreads, is the finding."""
+    and how far it spreads, is the finding.
+
+    luts: tone-table specs (name, lut), each lut 65536 integers in 0 .. 65535 (processing.lut_table; LUTS(raw) for the 21 pedestals,
+    saturations, coarser ADCs, gammas and the negative of the plane's own range), else ValueError before any work. None adds nothing.
+    Otherwise rows named by the specs follow the gain rows: the raw image mapped point-wise through the table (apply_lut; on the device:
+    alter_lut), "direct" scored as for every row, "registered" None (a processor that normalises and builds its tone curve from the
+    histogram is expected to absorb a monotone table, which "direct" scores), and every row of the study gains "levels": None except
+    in the lut rows, where it is level_row's dict of the exact sums of the result against the unaltered result over the full output
+    frame per class of the unaltered input, raw >> level_shift(raw) under the output pixel (level_statistics with level_classes; on the
+    device one musica_sim_levels call behind the row's musica_sim_compare, whose sq_diff_sum and pixels the table must add up to; with
+    device_metrics alone the raw plane is made resident once for it): how many classes are occupied, the rms and largest shift of the
+    characteristic curve, the slope and correlation of the new curve on the old, the share of the change that is a function of the
+    input level alone, the within-class remainder, the ratio of the within-class scatters and the reversals (level_summary). Host and
+    device summarise exact integers with one function, so "levels" is equal to the last bit on every path. lut_tables: the dict also
+    carries "levels", "curve_a" and "curve_b", the two curves. The rows draw nothing from `rng` and take no ordinal. Nothing is asserted:
+    these are findings. A processor that fully normalises would show no curve shift for any monotone table; what it makes of a coarser
+    ADC, of saturation and of a negative is the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
-                        edges, edge_tables, gratings, grating_tables, gains, gain_tables)
+                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -1238,6 +1338,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     if opt.device_alterations:
         runner.proc.alter_set_source(raw)
         seed = int(rng.integers(0, 2 ** 63))
+    elif opt.luts and getattr(runner, "device_metrics", False):
+        runner.proc.alter_set_source(raw)   # musica_sim_levels takes its classes from the resident source plane
     if opt.ensemble:
         eproc = runner.ensemble_context(opt.ensemble)
         eproc.alter_set_source(raw)
@@ -1276,7 +1378,7 @@ def read_manifest(path):
 def run_studies(entries, runner, **study_args):
     """run_study over several raw images through one runner: `entries` as read_manifest returns them (raw paths of the runner's size;
     a reference: the vendor DICOM, read with dicom.read_dicom_gray). Every image gets a fresh np.random.default_rng(0), so its rows are
-    those of a study of that image alone. Returns [(raw as written, rows)], for write_studies_csvs."""
+    those of a study of that image alone; luts=True stands for LUTS of each image. Returns [(raw as written, rows)], for write_studies_csvs."""
     from .dicom import read_dicom_gray
     from .processing import read_raw
     studies = []
@@ -1285,7 +1387,8 @@ def run_studies(entries, runner, **study_args):
         if raw is None:
             raise ValueError("%s: not a raw file of %d x %d pixels (256-byte header + N*N uint16)" % (raw_path, runner.n, runner.n))
         vendor = read_dicom_gray(ref_path) if ref_path else None
-        studies.append((name, run_study(raw, runner, rng=np.random.default_rng(0), vendor=vendor, **study_args)))
+        per_image = dict(study_args, luts=LUTS(raw)) if study_args.get("luts") is True else study_args   # the tables follow each plane's own range
+        studies.append((name, run_study(raw, runner, rng=np.random.default_rng(0), vendor=vendor, **per_image)))
     return studies
 
 
@@ -1397,6 +1500,12 @@ def main(argv=None):
                          "of the result against the unaltered one (transfer, peak, line noise, visibility, spread per axis), written to "
                          "gain_response.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_profiles, musica_alter_gain)")
     ap.add_argument("--gain-tables", action="store_true", help="with --gains: keep the profiles' integers and the gains in the rows (\"tables\", \"gains\")")
+    ap.add_argument("--luts", action="store_true",
+                    help="add the tone-table rows (LUTS): pedestals, saturations, coarser ADCs, gammas and the negative of the image's own range, "
+                         "each a point-wise map of the raw gray levels; the exact sums of the result against the unaltered one per level of the "
+                         "input (curve shift, slope, global fraction, within-class remainder, spread ratio, reversals), written to "
+                         "level_response.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_levels, musica_alter_lut)")
+    ap.add_argument("--lut-tables", action="store_true", help="with --luts: keep the two characteristic curves in the rows (\"levels\", \"curve_a\", \"curve_b\")")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -1432,6 +1541,8 @@ def main(argv=None):
         ap.error("--grating-tables keeps what --gratings measures: give --gratings")
     if args.gain_tables and not args.gains:
         ap.error("--gain-tables keeps what --gains measures: give --gains")
+    if args.lut_tables and not args.luts:
+        ap.error("--lut-tables keeps what --luts measures: give --luts")
     if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
         ap.error("--covariance takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
     if args.covariance and not args.ensemble:
@@ -1495,6 +1606,8 @@ def main(argv=None):
         shift_args.update(gratings=GRATINGS(args.size), grating_tables=args.grating_tables)
     if args.gains:
         shift_args.update(gains=GAINS(args.size), gain_tables=args.gain_tables)
+    if args.luts:
+        shift_args.update(luts=True if args.manifest else LUTS(raw), lut_tables=args.lut_tables)
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

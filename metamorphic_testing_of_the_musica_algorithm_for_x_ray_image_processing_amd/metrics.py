@@ -1167,3 +1167,109 @@ def profile_row(tables, gx_out, gy_out, keep=False):
         out["tables"] = {k: [[int(v) for v in r] for r in tables[k]] for k in PROFILE_AXES}
         out["gains"] = {"cols": [int(g) for g in gx_out], "rows": [int(g) for g in gy_out]}
     return out
+
+
+# ---- tone tables: the output per level of the input (not in the reference's script) --------------------------------------------------
+# Every other metric of the study compares the output with a reference plane; none conditions on the input. The sums of a comparison
+# kept apart by the class of the INPUT pixel (its raw value >> shift) give the characteristic curve of the chain, the mean output per
+# input level, before and after an alteration, and split the change into a part that is a function of the input level alone (a change
+# of the global tone curve) and a remainder. level_statistics is the contract of musica_sim_levels (include/musica.h), which is
+# bit-identical to it; level_summary is what the study reports of the integers, one function for every path.
+
+def level_statistics(a, b, classes, regions, count):
+    """The exact sums per class of every region (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes: what musica_sim_levels
+    returns. `classes` is an integer plane of a's shape with values below `count` (1 .. 4096; harness.level_classes): the class of a
+    pixel is taken at side a's coordinates, whatever origin side b has. One (count, 6) uint64 table per region: per class the sums over
+    the region's pixels of that class of 1, a, b, (a - b)^2, a^2 and b^2 (processing.LEVEL_SUMS). The first column adds up to w h, the
+    fourth to the region's sum of squared differences (musica_sim_compare's sq_diff_sum). Integers throughout: every sum is a
+    histogram of (class, value) pairs times the values."""
+    a, b, classes, count = np.asarray(a), np.asarray(b), np.asarray(classes), int(count)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("level_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    if not 1 <= count <= 4096:
+        raise ValueError("count %d is not in 1 .. 4096" % count)
+    if classes.shape != a.shape or classes.dtype.kind not in "iu" or (classes.size and (int(classes.min()) < 0 or int(classes.max()) >= count)):
+        raise ValueError("the classes are not a %r plane of integers below %d, got %r %s" % (a.shape, count, classes.shape, classes.dtype))
+    values, diffs = np.arange(256, dtype=np.int64), np.arange(-255, 256, dtype=np.int64)
+    out = []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        k = classes[ay:ay + h, ax:ax + w].astype(np.int64).ravel()
+        pa, pb = a[ay:ay + h, ax:ax + w].astype(np.int64).ravel(), b[by:by + h, bx:bx + w].astype(np.int64).ravel()
+        ha = np.bincount(k * 256 + pa, minlength=count * 256).reshape(count, 256)              # how often class k meets the value a
+        hb = np.bincount(k * 256 + pb, minlength=count * 256).reshape(count, 256)
+        hd = np.bincount(k * 511 + (pa - pb + 255), minlength=count * 511).reshape(count, 511)   # ... and the difference a - b
+        out.append(np.stack([ha.sum(axis=1), ha @ values, hb @ values, hd @ (diffs * diffs), ha @ (values * values), hb @ (values * values)],
+                            axis=1).astype(np.uint64))
+    return out
+
+
+LEVEL_KEYS = ("classes", "curve_shift_rms", "curve_shift_max", "slope", "correlation", "global_fraction", "within_rms", "spread_ratio", "reversals")
+
+
+def level_summary(table, curves=False):
+    """What the study reports of a lut row, from level_statistics' (or musica_sim_levels') exact integers of ONE region: one function
+    for every study path, so the paths agree to the last bit. With k running over the OCCUPIED classes (n_k > 0) in ascending order,
+    N = sum n_k, ssd = sum sum_dd, d_k = sum_a - sum_b (an integer), and in f64 (one correctly rounded division of two integers
+    each, sums by math.fsum)
+        a_k = sum_a / n_k, b_k = sum_b / n_k      the two characteristic curves: the mean output of class k after and before
+    the dict holds
+        classes          how many classes are occupied
+        curve_shift_rms  sqrt(sum n_k (a_k - b_k)^2 / N), the terms taken as d_k^2 / n_k
+        curve_shift_max  max |a_k - b_k|, taken as |d_k| / n_k
+        slope            the n-weighted least-squares slope of a_k on b_k across the classes, sum n (a - ma)(b - mb) / sum n (b - mb)^2
+                         with the n-weighted means ma, mb; None where b_k is constant
+        correlation      sum n (a - ma)(b - mb) / sqrt(sum n (a - ma)^2 sum n (b - mb)^2); None where a_k or b_k is constant
+        global_fraction  sum_k d_k^2 / n_k / ssd: the share of the change that is a function of the input level alone, hence a pure
+                         change of the global tone curve; None where nothing changed (ssd = 0)
+        within_rms       sqrt(sum_k (n_k sum_dd - d_k^2) / n_k / N), every numerator an exact non-negative integer: the within-class
+                         remainder, so that global_fraction ssd + within_rms^2 N = ssd to rounding
+        spread_ratio     sqrt(Wa / Wb) with W = sum_k (n_k sum_xx - sum_x^2) / n_k, the pooled within-class scatter of a over that of b:
+                         whether local contrast at a given input level changed; None where Wb = 0
+        reversals        how many neighbouring occupied classes have an a step and a b step of opposite non-zero signs, decided on the
+                         integers (the sign of sum_x' n - sum_x n')
+    and with curves=True also "levels" (the occupied classes), "curve_a" and "curve_b" (a_k and b_k) as lists. No threshold is fixed
+    here: these are findings."""
+    t = [[int(v) for v in row] for row in np.asarray(table)]
+    if not t or any(len(row) != 6 for row in t):
+        raise ValueError("a level table is (classes, 6), got %r" % (np.asarray(table).shape,))
+    rows = [(k, row) for k, row in enumerate(t) if row[0] > 0]
+    if not rows:
+        raise ValueError("the level table holds no pixel")
+    n = [r[0] for _, r in rows]
+    total, ssd = sum(n), sum(r[3] for _, r in rows)
+    d = [r[1] - r[2] for _, r in rows]
+    a, b = [r[1] / r[0] for _, r in rows], [r[2] / r[0] for _, r in rows]
+    between = math.fsum(v * v / m for v, m in zip(d, n))
+    within = math.fsum((m * r[3] - v * v) / m for (_, r), v, m in zip(rows, d, n))
+    ma, mb = sum(r[1] for _, r in rows) / total, sum(r[2] for _, r in rows) / total
+    saa = math.fsum(m * (x - ma) ** 2 for m, x in zip(n, a))
+    sbb = math.fsum(m * (y - mb) ** 2 for m, y in zip(n, b))
+    sab = math.fsum(m * (x - ma) * (y - mb) for m, x, y in zip(n, a, b))
+    flat_a, flat_b = (all(r[i] * n[0] == rows[0][1][i] * m for (_, r), m in zip(rows, n)) for i in (1, 2))   # decided on the integers
+    wa = math.fsum((m * r[4] - r[1] * r[1]) / m for (_, r), m in zip(rows, n))
+    wb = math.fsum((m * r[5] - r[2] * r[2]) / m for (_, r), m in zip(rows, n))
+    reversals = 0
+    for ((_, p), (_, q)) in zip(rows, rows[1:]):
+        step_a, step_b = q[1] * p[0] - p[1] * q[0], q[2] * p[0] - p[2] * q[0]
+        reversals += (step_a > 0 and step_b < 0) or (step_a < 0 and step_b > 0)
+    out = {"classes": len(rows), "curve_shift_rms": math.sqrt(between / total), "curve_shift_max": max(abs(v) / m for v, m in zip(d, n)),
+           "slope": None if flat_b else sab / sbb, "correlation": None if flat_a or flat_b else sab / math.sqrt(saa * sbb),
+           "global_fraction": between / ssd if ssd else None, "within_rms": math.sqrt(within / total),
+           "spread_ratio": math.sqrt(wa / wb) if wb > 0.0 else None, "reversals": int(reversals)}
+    if curves:
+        out.update(levels=[k for k, _ in rows], curve_a=a, curve_b=b)
+    return out
+
+
+def level_row(table, sq_diff_sum, pixels, keep=False):
+    """A lut row's "levels" value: level_summary's dict of the full frame's table, with keep=True the two curves as well. The table
+    must account for the frame (ValueError otherwise): its n add up to `pixels` and its sum_dd to `sq_diff_sum`, the integers of the
+    row's direct comparison."""
+    t = np.asarray(table)
+    if int(t[:, 0].sum()) != int(pixels) or int(t[:, 3].sum()) != int(sq_diff_sum):
+        raise ValueError("the level table holds %d pixels and a squared difference of %d, the frame %d and %d"
+                         % (int(t[:, 0].sum()), int(t[:, 3].sum()), int(pixels), int(sq_diff_sum)))
+    return level_summary(t, curves=keep)

@@ -173,6 +173,10 @@ GRATING_MAX_CONTRAST = 512  # MUSICA_GRATING_MAX_CONTRAST
 GRATING_MAX = 256           # MUSICA_GRATING_MAX
 GAIN_ONE = 4096             # MUSICA_GAIN_ONE
 PROFILE_MAX_QUERIES = 16    # MUSICA_PROFILE_MAX_QUERIES
+LUT_ENTRIES = 65536         # MUSICA_LUT_ENTRIES
+LEVEL_MAX_QUERIES = 4       # MUSICA_LEVEL_MAX_QUERIES
+LEVEL_MIN_SHIFT = 4         # MUSICA_LEVEL_MIN_SHIFT
+LEVEL_MAX_SHIFT = 15        # MUSICA_LEVEL_MAX_SHIFT
 
 
 def zoom_ratio(zoom):
@@ -410,6 +414,31 @@ class SimProfileResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("cols", C.c_uint64), ("rows", C.c_uint64), ("ssd", C.c_uint64), ("pixels", C.c_uint64)]
 
 
+def lut_table(lut):
+    """A tone table as harness.apply_lut and the library take it: a uint16 array of LUT_ENTRIES entries, else ValueError: a sequence of
+    LUT_ENTRIES integers in 0 .. 65535."""
+    a = np.asarray(lut)
+    if a.ndim != 1 or a.shape[0] != LUT_ENTRIES or a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 65535:
+        raise ValueError("lut is not %d integers in 0 .. 65535, got %r %s" % (LUT_ENTRIES, a.shape, a.dtype))
+    return np.ascontiguousarray(a, dtype=np.uint16)
+
+
+def level_count(shift):
+    """How many classes source >> shift has, (65535 >> shift) + 1 <= 4096, for an integer shift in LEVEL_MIN_SHIFT .. LEVEL_MAX_SHIFT,
+    else ValueError."""
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not LEVEL_MIN_SHIFT <= shift <= LEVEL_MAX_SHIFT:
+        raise ValueError("shift %r is not an integer in %d .. %d" % (shift, LEVEL_MIN_SHIFT, LEVEL_MAX_SHIFT))
+    return (65535 >> int(shift)) + 1
+
+
+LEVEL_SUMS = ("n", "sum_a", "sum_b", "sum_dd", "sum_aa", "sum_bb")   # the six words of a class of a level table
+
+
+class SimLevelResult(C.Structure):
+    """musica_sim_level_result: where a query's table lies in `tables`, and the region's exact sum of squared differences."""
+    _fields_ = [("table_offset", C.c_uint64), ("classes", C.c_uint64), ("ssd", C.c_uint64), ("pixels", C.c_uint64)]
+
+
 class SimDisplaceResult(C.Structure):
     """musica_sim_displace_result: where one comparison's exact block matching puts the output."""
     _fields_ = [("pixels", C.c_uint64), ("ssd_zero", C.c_uint64), ("ssd_min", C.c_uint64), ("dx", C.c_int32), ("dy", C.c_int32),
@@ -617,6 +646,8 @@ ABI = {
     "musica_sim_gratings": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Grating), C.POINTER(SimGratingResult), _U32P, C.c_uint64]),
     "musica_alter_gain": (C.c_int, [_VP, C.c_uint32, _U16P, _U16P]),
     "musica_sim_profiles": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimProfileResult), _U32P, C.c_uint64]),
+    "musica_alter_lut": (C.c_int, [_VP, C.c_uint32, _U16P]),
+    "musica_sim_levels": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimLevelResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -1063,6 +1094,25 @@ class MusicaProcessing:
                         "ssd": int(r.ssd), "pixels": int(r.pixels)})
         return out
 
+    def sim_levels(self, queries, shift):
+        """harness.level_statistics on the device, the classes being the alteration source (alter_set_source) under side a's pixels
+        >> shift: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or SimQuery) with w, h >= 1, 1 ..
+        LEVEL_MAX_QUERIES of them, all in one launch; shift an integer in LEVEL_MIN_SHIFT .. LEVEL_MAX_SHIFT (ValueError before any call).
+        Returns one dict per query: "table", a (classes, 6) uint64 array of the exact n, sum_a, sum_b, sum_dd = sum of (a - b)^2, sum_aa
+        and sum_bb (LEVEL_SUMS) per class, and the Python ints "classes", "ssd" (the sum of sum_dd) and "pixels"."""
+        classes = level_count(shift)
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        if not 1 <= len(qs) <= LEVEL_MAX_QUERIES:
+            raise ValueError("sim_levels takes 1 .. %d queries, got %d" % (LEVEL_MAX_QUERIES, len(qs)))
+        words = len(qs) * classes * len(LEVEL_SUMS)
+        arr, res, tables = (SimQuery * len(qs))(*qs), (SimLevelResult * len(qs))(), np.zeros(words, dtype=np.uint64)
+        self._ok(self._lib.musica_sim_levels(self._h, int(shift), len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), words), "musica_sim_levels")
+        out = []
+        for r in res:
+            at, c = int(r.table_offset), int(r.classes)
+            out.append({"table": tables[at:at + c * len(LEVEL_SUMS)].reshape(c, len(LEVEL_SUMS)).copy(), "classes": c, "ssd": int(r.ssd), "pixels": int(r.pixels)})
+        return out
+
     def sim_get_reference(self, slot):
         """Reference slot `slot` as an (N - 20, N - 20) uint8 array."""
         n = self.imageSize - 2 * OUT_MARGIN
@@ -1294,6 +1344,11 @@ class MusicaProcessing:
         saturating at 65535."""
         gx, gy = gain_tables(gx, gy, self.imageSize)
         self._ok(self._lib.musica_alter_gain(self._h, int(image_index), gx.ctypes.data_as(_U16P), gy.ctypes.data_as(_U16P)), "musica_alter_gain")
+
+    def alter_lut(self, lut, image_index=0):
+        """harness.apply_lut(src, lut): the source mapped point-wise through the tone table (lut_table), lut[v] for every pixel v."""
+        lut = lut_table(lut)
+        self._ok(self._lib.musica_alter_lut(self._h, int(image_index), lut.ctypes.data_as(_U16P)), "musica_alter_lut")
 
     def alter_collimator(self, shutter_h, shutter_v, seed=0, stream=0, image_index=0):
         """harness.apply_collimator(src, shutter_h, shutter_v)."""

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRATING_ROW_KEYS, GRATING_ROW_STATS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -40,6 +40,7 @@ EDGE_CSV_HEADER = ['raw file', 'alteration', 'orientation', 'edges'] + ['%s %s' 
 GRATING_CSV_HEADER = ['raw file', 'alteration', 'period', 'gratings'] + ['%s %s' % (k, w) for k in GRATING_ROW_KEYS for w in GRATING_ROW_STATS] + \
                      ['outside mse']   # grating_response.csv
 GAIN_CSV_HEADER = ['raw file', 'alteration', 'axis', 'lines'] + [k.replace('_', ' ') for k in PROFILE_KEYS]   # gain_response.csv
+LEVEL_CSV_HEADER = ['raw file', 'alteration'] + [k.replace('_', ' ') for k in LEVEL_KEYS]   # level_response.csv
 
 
 def covariance_csv_header(radius):
@@ -144,12 +145,13 @@ def _spread_cells(count, keys, stats):
 
 # file name, header, row key, groups, cells of _group_lines: contrast_detail.csv has one line per cd_ row and radius, ascending;
 # edge_response.csv one per edge_ row and orientation; grating_response.csv one per grating_ row and period; gain_response.csv one per
-# gain row and axis, the columns' profile first
+# gain row and axis, the columns' profile first; level_response.csv one per lut row, the number of occupied classes in the label's place
 RELATION_CSVS = (
     ("contrast_detail.csv", DETAIL_CSV_HEADER, "details", lambda d: d["radii"].items(), _spread_cells("count", DETAIL_ROW_KEYS, DETAIL_ROW_STATS)),
     ("edge_response.csv", EDGE_CSV_HEADER, "edges", lambda d: d["orientations"].items(), _spread_cells("edges", EDGE_ROW_KEYS, EDGE_ROW_STATS)),
     ("grating_response.csv", GRATING_CSV_HEADER, "gratings", lambda d: d["periods"].items(), _spread_cells("gratings", GRATING_ROW_KEYS, GRATING_ROW_STATS)),
     ("gain_response.csv", GAIN_CSV_HEADER, "profiles", lambda d: [(axis, d[axis]) for axis in PROFILE_AXES], lambda d, g: [g["lines"]] + [g[k] for k in PROFILE_KEYS]),
+    ("level_response.csv", LEVEL_CSV_HEADER, "levels", lambda d: [(d[LEVEL_KEYS[0]], d)], lambda d, g: [g[k] for k in LEVEL_KEYS[1:]]),
 )
 
 
@@ -196,7 +198,10 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
 
     Studies run with gains (rows[0] has "profiles") also get gain_response.csv (GAIN_CSV_HEADER): one line per gain row and axis
     ("cols": the column profile, scored against gx; "rows": against gy), the number of lines and profile_summary's numbers of the
-    axis (an empty cell where one is None)."""
+    axis (an empty cell where one is None).
+
+    Studies run with luts (rows[0] has "levels") also get level_response.csv (LEVEL_CSV_HEADER): one line per lut row, level_summary's
+    numbers of the full frame (an empty cell where one is None)."""
     os.makedirs(out_dir, exist_ok=True)
     having = lambda key: [(raw_name, rows) for raw_name, rows in studies if rows and key in rows[0]]   # noqa: E731
     toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
