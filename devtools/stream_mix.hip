@@ -1,7 +1,7 @@
 // Dev tool (round 4): what plain streaming kernels reach from HBM for the READ : WRITE mixes of the level-0 kernels of a C4 step
 // (8 x 2048^2) — the ceilings the marching kernels are measured against. One thread = 8 pixels of a row; no stencil, no halo.
 //   rb0   : read 2 B/px (uint16), write 4 B/px (band) + 1 B/px (coarse)          = k_reduce_band<true>   (7 B/px)
-//   sdev  : read 4 B/px, write 4 B/px                                            = k_sdev_hist_pf        (8 B/px)
+//   sdev  : read 4 B/px, write 4 B/px                                            = k_sdev_hist, a march (8 B/px)
 //   exp0  : read 4 + 4 B/px (band, sdev) + 1 B/px (coarse), write 4 B/px          = k_expand_fast<GH>     (13 B/px)
 //   apply : read 4, write 4 (the 1:1 stream of devtools/stream11.hip)
 //   rd / wr : read-only (sum into a dummy) / write-only

@@ -5,9 +5,9 @@
 //   k_minmax_u16    : img_sqrt.comp + img_max_reduce.comp chain + min_reduce.comp chain   (K1 + K2 + K3)
 //   k_normalize     : img_sqrt.comp + img_normalize.comp                                    (K1 + K4)
 //   k_sdev_hist     : img_sdev.comp + noise_hist.comp fused                                 (K10 + K11)
-//   k_noise_curves  : img_histogram_max.comp + contrast_curve_generate.comp                 (K12 + K13)
-//   k_cnr           : img_cnr.comp                                                          (K15)
+//   k_curves_cnr    : img_histogram_max.comp + contrast_curve_generate.comp, img_cnr.comp   (K12 + K13, K15)
 //   k_sqrt          : img_sqrt.comp alone (debug image)
+#include <assert.h>
 #include <stdlib.h>
 #include <algorithm>
 #include "kernels_common.h"
@@ -276,18 +276,9 @@ __global__ void k_sqrt(const uint16_t* __restrict__ px, float* __restrict__ out,
 // Software-pipelined form: one row per trip; the raw row of trip y+1 is requested before trip y is
 // computed and squared only when it enters the window (so the request never blocks the arithmetic).
 // (sdev_march_block — one workgroup of the march — lives in sdev_parts.h: the paired reduce + band / sdev launch of kernels_expand_sd.hip uses it too)
-template <bool HIST, bool A8>
-__global__ __launch_bounds__(kBlockThreads) void k_sdev_hist_pf(const float* __restrict__ band, float* __restrict__ sdev, int S, int pitch,
-                                                                size_t plane, uint32_t* __restrict__ hist, size_t hist_stride, int cov,
-                                                                int rows_per_wave, int swz) {
-    __shared__ uint32_t lh[kHistLdsWords];
-    const size_t img = blockIdx.z;
-    sdev_march_block<HIST, A8>(band + img * plane, sdev ? sdev + img * plane : nullptr, S, pitch, plane, HIST ? hist + img * hist_stride : nullptr, cov, rows_per_wave,
-                               xcd_tile(swz), lh);
-}
-
+//
 // ---- K10 + K11, one 16-row histogram run per workgroup ------------------------------------------------------
-// The march above gives a wavefront a whole 16-row run (the `break` of noise_hist.comp:29-39 makes a run an ordered scan), i.e.
+// The march gives a wavefront a whole 16-row run (the `break` of noise_hist.comp:29-39 makes a run an ordered scan), i.e.
 // 20 dependent row trips: 16 - 17 us per launch however small the level, and 16 rows x ~290 vector instructions would cost a
 // lone wavefront ~9 us even with every load in flight. Here the four wavefronts of a workgroup share ONE run of 512 columns:
 // each takes 4 of its rows, requests its 8 input rows at once (one round of latency), computes its 4 sdev rows and the
@@ -296,66 +287,28 @@ __global__ __launch_bounds__(kBlockThreads) void k_sdev_hist_pf(const float* __r
 // their texels to the workgroup's LDS histogram. Same expressions (sdev_values, musica_noise_bin) as the march: same bits.
 // Input rows are read twice (8 per 4 instead of 20 per 16), from the XCD's L2 the second time.
 // (sdev_run_block lives in sdev_parts.h, like sdev_march_block)
-template <bool A8>
-__global__ __launch_bounds__(kBlockThreads) void k_sdev_hist_run(const float* __restrict__ band, float* __restrict__ sdev, int S, int pitch,
-                                                                 size_t plane, uint32_t* __restrict__ hist, size_t hist_stride, int cov, int swz) {
-    __shared__ uint32_t lh[kHistLdsWords];
-    __shared__ unsigned long long nzw[kWavesPerBlock][8];
-    const size_t img = blockIdx.z;
-    sdev_run_block<A8>(band + img * plane, sdev ? sdev + img * plane : nullptr, S, pitch, plane, hist + img * hist_stride, cov, xcd_tile(swz), lh, nzw);
-}
-
-// The runs of SEVERAL levels in one launch (levels whose launch of their own would be a few dozen workgroups: a context
-// that runs alone pays ~5 us of fixed cost per launch and the four sdev launches of a step depend on nothing but their
-// own band image). Workgroups first .. first + strips * blocks - 1 of grid.x belong to level k; the finest level first.
-template <bool A8>
-__global__ __launch_bounds__(kBlockThreads) void k_sdev_hist_runs(const SdevRunLevels a, size_t hist_stride, int cov) {
-    __shared__ uint32_t lh[kHistLdsWords];
-    __shared__ unsigned long long nzw[kWavesPerBlock][8];
-    int k = 0;
-    for (int j = 1; j < a.n; j++) k = (int)blockIdx.x >= a.l[j].first ? j : k;   // block-uniform
-    const SdevRunLevel& l = a.l[k];
-    const int local = (int)blockIdx.x - l.first;
-    Tile tile;
-    tile.strip = local % l.strips;
-    tile.segblock = local / l.strips;
-    const size_t img = blockIdx.z;
-    sdev_run_block<A8>(l.band + img * l.plane, l.sdev ? l.sdev + img * l.plane : nullptr, l.S, l.pitch, l.plane, l.hist + img * hist_stride, cov, tile, lh, nzw);
-}
-
-// EVERY level's sdev + noise-histogram pass in one launch, each level in the form its launch of its own would take (a march of l.rows rows per
-// wavefront, or one 16-row run per workgroup where l.rows == 0). The four passes of a step depend on nothing but their own band image, and
-// alone on the chip the marches of levels 0 and 1 are 2 and 1 wavefronts per SIMD of dependent arithmetic (8 x 2048^2: 45 + 23 us, and 14 us
-// for the runs of levels 2 + 3): side by side they fill each other's issue slots.
-template <bool A8>
-__global__ __launch_bounds__(kBlockThreads) void k_sdev_hist_levels(const SdevRunLevels a, size_t hist_stride, int cov) {
+//
+// ---- the launch: the passes of 1 .. kSdevRunLevelsMax levels, each level in its own form ----------------------------
+// Workgroups l.first .. of grid.x belong to level k, the finest level first; a level starts at a multiple of 8 workgroups and the grid
+// is a multiple of 8 wide (the launcher pads), so the XCD-aware mapping holds inside a level (sdev_level_block, role_tile). One level is
+// the launch of its own; several in one launch because the passes of a step depend on nothing but their own band image: a context that
+// runs alone pays ~5 us of fixed cost per launch of a few dozen workgroups (the levels that take the run form), and alone on the chip
+// the marches of levels 0 and 1 are 2 and 1 wavefronts per SIMD of dependent arithmetic (8 x 2048^2: 45 + 23 us, and 14 us for the runs
+// of levels 2 + 3): side by side they fill each other's issue slots.
+// RUNS = false: every level marches; the run form and its `nzw` are compiled out (80 registers instead of 110). HIST = false: the sdev
+// image alone (ensure_sdev).
+template <bool HIST, bool A8, bool RUNS>
+__global__ __launch_bounds__(kBlockThreads) void k_sdev_hist(const SdevRunLevels a, size_t hist_stride, int cov) {
     __shared__ uint32_t lh[kHistLdsWords];
     __shared__ unsigned long long nzw[kWavesPerBlock][8];
     int k = 0;
     for (int j = 1; j < a.n; j++) k = (int)blockIdx.x >= a.l[j].first ? j : k;   // block-uniform
     const SdevRunLevel& l = a.l[k];
-    const int local = (int)blockIdx.x - l.first;
-    // a level starts at a multiple of 8 workgroups and the grid is a multiple of 8 wide (the launcher pads), so workgroup `local` of a level
-    // runs on XCD local % 8: the mapping of xcd_tile() — XCD x takes the x-th eighth of the level's blocks, strip by strip — where the blocks
-    // divide by 8, the plain one elsewhere
-    const int blocks = l.blocks;
     Tile tile;
-    if (a.swz && (blocks & 7) == 0) {
-        const int xcd = local & 7, j = local >> 3;
-        tile.strip = j % l.strips;
-        tile.segblock = xcd * (blocks >> 3) + j / l.strips;
-    } else {
-        tile.strip = local % l.strips;
-        tile.segblock = local / l.strips;
-    }
-    if (tile.segblock >= blocks) return;   // padding (block-uniform)
-    const size_t img = blockIdx.z;
-    float* sd = l.sdev ? l.sdev + img * l.plane : nullptr;
-    if (l.rows > 0) sdev_march_block<true, A8>(l.band + img * l.plane, sd, l.S, l.pitch, l.plane, l.hist + img * hist_stride, cov, l.rows, tile, lh);
-    else sdev_run_block<A8>(l.band + img * l.plane, sd, l.S, l.pitch, l.plane, l.hist + img * hist_stride, cov, tile, lh, nzw);
+    if (!role_tile((int)blockIdx.x - l.first, l.strips, l.blocks, a.swz, tile)) return;   // padding (block-uniform)
+    sdev_level_block<HIST, A8, RUNS>(l, tile, blockIdx.z, hist_stride, cov, lh, nzw);
 }
 
-// histogram only (kernel-level parity tests feed a foreign sdev image): same scan, no stencil.
 // img_sdev.comp:10-35 literally: sum += pixel * pixel over m (x) outer, n (y) inner, out-of-image taps 0 (Q1), sqrt(sum / 25).
 __global__ void k_sdev_literal(const float* __restrict__ band, float* __restrict__ sdev, int S, int pitch, size_t plane) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -376,6 +329,7 @@ __global__ void k_sdev_literal(const float* __restrict__ band, float* __restrict
     sdev[(size_t)y * pitch + x] = sqrtf(sum / 25.0f);   // :30
 }
 
+// histogram only (kernel-level parity tests feed a foreign sdev image): same scan, no stencil.
 __global__ __launch_bounds__(kBlockThreads) void k_noise_hist_only(const float* __restrict__ sdev, int S, int pitch, size_t plane,
                                                                    uint32_t* __restrict__ hist, size_t hist_stride, int cov) {
     __shared__ uint32_t lh[MUSICA_NOISE_BINS];
@@ -508,14 +462,6 @@ __device__ __forceinline__ void noise_curves_block(int level, int img, const uin
     }
 }
 
-__global__ __launch_bounds__(256) void k_noise_curves(const uint32_t* __restrict__ hist, size_t hist_stride,
-                                                      musica_hist_max_point* __restrict__ maxpts, DevCurve* __restrict__ curves,
-                                                      const musica_contrast_params* __restrict__ cparams, int levels,
-                                                      DevCurveLut* __restrict__ luts, const uint32_t* __restrict__ minmax, int min_chain_exact,
-                                                      int* __restrict__ thr090, int lev0) {
-    noise_curves_block(lev0 + (int)blockIdx.x, blockIdx.y, hist, hist_stride, maxpts, curves, cparams, levels, luts, minmax, min_chain_exact, thr090);
-}
-
 // K12 + K13 and K15 in one launch: workgroups 0 .. levels-1 of an image build that level's curve, the others each
 // normalise one 32 x 8 tile of the level-3 sdev image. img_cnr.comp only needs the level-3 noise mode, so a tile
 // workgroup takes the argmax of that histogram itself (2048 bins, the same first-maximum key as K12) instead of
@@ -546,21 +492,6 @@ __global__ __launch_bounds__(256) void k_curves_cnr(const uint32_t* __restrict__
     if (ref == 0.0f) ref = (1.0f / (float)MUSICA_NOISE_BINS) * kMaxNoiseValue;                  // :25
     const int t = (int)blockIdx.x - nlev;
     const int x = (t % tiles_x) * 32 + (int)(threadIdx.x & 31), y = (t / tiles_x) * 8 + (int)(threadIdx.x >> 5);
-    if (x >= S || y >= S) return;
-    const size_t o = (size_t)img * plane + (size_t)y * pitch + x;
-    const float v = sdev[o] / ref;                                                              // :31
-    cnr[o] = v / kMaxCnrValue;                                                                  // :43
-}
-
-// ---- K15 ------------------------------------------------------------------------------
-__global__ void k_cnr(const float* __restrict__ sdev, float* __restrict__ cnr, int S, int pitch, size_t plane,
-                      const musica_hist_max_point* __restrict__ maxpts, int levels) {
-    const int img = blockIdx.z;
-    const musica_hist_max_point mp = maxpts[(size_t)img * levels + MUSICA_CNR_LEVEL];
-    float ref = (float)mp.maxBin * (1.0f / (float)MUSICA_NOISE_BINS) * kMaxNoiseValue;          // img_cnr.comp:22
-    if (ref == 0.0f) ref = (1.0f / (float)MUSICA_NOISE_BINS) * kMaxNoiseValue;                  // :25
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= S || y >= S) return;
     const size_t o = (size_t)img * plane + (size_t)y * pitch + x;
     const float v = sdev[o] / ref;                                                              // :31
@@ -676,71 +607,41 @@ void launch_sqrt(hipStream_t st, const uint16_t* px, float* out, const LevelDesc
     hipLaunchKernelGGL(k_sqrt, dim3(1024, 1, batch), dim3(256), 0, st, px, out, l0.S, l0.pitch, l0.plane);
 }
 
-void launch_sdev_hist(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov,
-                      int batch, int rows_per_wave, int swz) {
-    const int strips = (l.S + kStripCols - 1) / kStripCols;
-    if (rows_per_wave <= 0) {   // one 16-row run per workgroup (k_sdev_hist_run)
-        const dim3 grid(strips, (l.S + kHistArea - 1) / kHistArea, batch);
-        if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_run<true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, swz);
-        else hipLaunchKernelGGL((k_sdev_hist_run<false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, swz);
-        return;
-    }
-    const int segs = (l.S + rows_per_wave - 1) / rows_per_wave;
-    const dim3 grid(strips, (segs + kWavesPerBlock - 1) / kWavesPerBlock, batch);
-    if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_pf<true, true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, rows_per_wave, swz);
-    else hipLaunchKernelGGL((k_sdev_hist_pf<true, false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov, rows_per_wave, swz);
-}
-
-void launch_sdev_hist_runs(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
-                           size_t hist_stride, int cov, int batch) {
+// The sdev + noise-histogram passes of n <= kSdevRunLevelsMax levels in ONE launch (k_sdev_hist), each level in its own form: rows[k] > 0 the march
+// with that many rows per wavefront, 0 one 16-row run per workgroup. sdev[k] == nullptr: histogram only; hist[k]: image 0's histogram of
+// level k; hist == nullptr: the sdev images alone (every level marches, every side a multiple of 8).
+void launch_sdev_hist(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
+                      const int* rows, size_t hist_stride, int cov, int batch, int swz) {
     SdevRunLevels a;
     a.n = n;
+    a.swz = swz;
     int first = 0;
-    bool a8 = true;
+    bool a8 = true, marches = true;
     for (int k = 0; k < n; k++) {
         const LevelDesc& l = lv[k];
-        const int strips = (l.S + kStripCols - 1) / kStripCols;
-        a.l[k] = SdevRunLevel{band[k], sdev[k], hist[k], l.plane, l.S, l.pitch, strips, first, 0, 0};
-        first += strips * ((l.S + kHistArea - 1) / kHistArea);
-        a8 = a8 && (l.S & 7) == 0;
-    }
-    for (int k = n; k < kSdevRunLevelsMax; k++) a.l[k] = a.l[0];
-    a.swz = 0;
-    const dim3 grid(first, 1, batch);
-    if (a8) hipLaunchKernelGGL((k_sdev_hist_runs<true>), grid, dim3(kBlockThreads), 0, st, a, hist_stride, cov);
-    else hipLaunchKernelGGL((k_sdev_hist_runs<false>), grid, dim3(kBlockThreads), 0, st, a, hist_stride, cov);
-}
-
-void launch_sdev_hist_levels(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
-                             const int* rows, size_t hist_stride, int cov, int batch, int swz) {
-    SdevRunLevels a;
-    a.n = n;
-    int first = 0;
-    bool a8 = true;
-    for (int k = 0; k < n; k++) {
-        const LevelDesc& l = lv[k];
-        const int strips = (l.S + kStripCols - 1) / kStripCols;
-        int blocks;   // workgroups per strip
-        if (rows[k] > 0) { const int segs = (l.S + rows[k] - 1) / rows[k]; blocks = (segs + kWavesPerBlock - 1) / kWavesPerBlock; }
-        else blocks = (l.S + kHistArea - 1) / kHistArea;
-        a.l[k] = SdevRunLevel{band[k], sdev[k], hist[k], l.plane, l.S, l.pitch, strips, first, rows[k] > 0 ? rows[k] : 0, blocks};
+        const int strips = (l.S + kStripCols - 1) / kStripCols, r = rows[k] > 0 ? rows[k] : 0, blocks = sdev_blocks_per_strip(l.S, r);
+        a.l[k] = SdevRunLevel{band[k], sdev[k], hist ? hist[k] : nullptr, l.plane, l.S, l.pitch, strips, first, r, blocks};
         first += (strips * blocks + 7) & ~7;   // every level starts on XCD 0
         a8 = a8 && (l.S & 7) == 0;
+        marches = marches && r > 0;
     }
     for (int k = n; k < kSdevRunLevelsMax; k++) a.l[k] = a.l[0];
-    a.swz = swz;
-    const dim3 grid(first, 1, batch);
-    if (a8) hipLaunchKernelGGL((k_sdev_hist_levels<true>), grid, dim3(kBlockThreads), 0, st, a, hist_stride, cov);
-    else hipLaunchKernelGGL((k_sdev_hist_levels<false>), grid, dim3(kBlockThreads), 0, st, a, hist_stride, cov);
-}
-
-// sdev alone (no histogram): the stored image of a level whose hot path does not store it, for getters / dumps / the stage entry points
-void launch_sdev_only(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch, int swz) {
-    const int strips = (l.S + kStripCols - 1) / kStripCols, rows = 16;
-    const int segs = (l.S + rows - 1) / rows;
-    const dim3 grid(strips, (segs + kWavesPerBlock - 1) / kWavesPerBlock, batch);
-    if ((l.S & 7) == 0) hipLaunchKernelGGL((k_sdev_hist_pf<false, true>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, (uint32_t*)nullptr, (size_t)0, 0, rows, swz);
-    else hipLaunchKernelGGL((k_sdev_hist_pf<false, false>), grid, dim3(kBlockThreads), 0, st, band, sdev, l.S, l.pitch, l.plane, (uint32_t*)nullptr, (size_t)0, 0, rows, swz);
+    const dim3 grid(first, 1, batch), block(kBlockThreads);
+    // Which instantiation a launch takes follows from the launch alone, and leaves it on the registers and LDS it has had as a kernel of its
+    // own: the code without the run form (80 registers, not 110) for ONE marching level, the code with it for every launch of several levels
+    // or of a level in the run form. A launch of several levels that all march thus runs the 110-register code, as it always has: whether
+    // it would prefer the 80-register code is a measured change for another day.
+    const bool runs = !(n == 1 && marches);
+    if (!hist) {
+        assert(a8 && !runs);   // ensure_sdev: 16-row marches of levels whose side is a multiple of 8
+        hipLaunchKernelGGL((k_sdev_hist<false, true, false>), grid, block, 0, st, a, hist_stride, cov);
+    } else if (runs) {
+        if (a8) hipLaunchKernelGGL((k_sdev_hist<true, true, true>), grid, block, 0, st, a, hist_stride, cov);
+        else hipLaunchKernelGGL((k_sdev_hist<true, false, true>), grid, block, 0, st, a, hist_stride, cov);
+    } else {
+        if (a8) hipLaunchKernelGGL((k_sdev_hist<true, true, false>), grid, block, 0, st, a, hist_stride, cov);
+        else hipLaunchKernelGGL((k_sdev_hist<true, false, false>), grid, block, 0, st, a, hist_stride, cov);
+    }
 }
 
 void launch_sdev_literal(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch) {
@@ -752,25 +653,12 @@ void launch_noise_hist_only(hipStream_t st, const float* sdev, const LevelDesc& 
                        dim3(kBlockThreads), 0, st, sdev, l.S, l.pitch, l.plane, hist, hist_stride, cov);
 }
 
-void launch_noise_curves(hipStream_t st, const uint32_t* hist, size_t hist_stride, musica_hist_max_point* maxpts, DevCurve* curves,
-                         const musica_contrast_params* cparams, int levels, int batch, DevCurveLut* luts, const uint32_t* minmax, int min_chain_exact,
-                         int* thr090, int lev0, int nlev) {
-    hipLaunchKernelGGL(k_noise_curves, dim3(nlev > 0 ? nlev : levels - lev0, batch), dim3(256), 0, st, hist, hist_stride, maxpts, curves, cparams, levels, luts,
-                       minmax, min_chain_exact, thr090, lev0);
-}
-
 void launch_curves_cnr(hipStream_t st, const uint32_t* hist, size_t hist_stride, musica_hist_max_point* maxpts, DevCurve* curves,
                        const musica_contrast_params* cparams, int levels, int batch, DevCurveLut* luts, const float* sdev, float* cnr,
                        const LevelDesc& l3, const uint32_t* minmax, int min_chain_exact, int* thr090, int lev0) {
     const int tiles_x = (l3.S + 31) / 32, tiles_y = (l3.S + 7) / 8;
     hipLaunchKernelGGL(k_curves_cnr, dim3(levels - lev0 + tiles_x * tiles_y, batch), dim3(256), 0, st, hist, hist_stride, maxpts, curves, cparams, levels,
                        luts, sdev, cnr, l3.S, l3.pitch, l3.plane, tiles_x, minmax, min_chain_exact, thr090, lev0);
-}
-
-void launch_cnr(hipStream_t st, const float* sdev, float* cnr, const LevelDesc& l3, const musica_hist_max_point* maxpts, int levels,
-                int batch) {
-    hipLaunchKernelGGL(k_cnr, dim3((l3.S + 31) / 32, (l3.S + 7) / 8, batch), dim3(32, 8), 0, st, sdev, cnr, l3.S, l3.pitch, l3.plane,
-                       maxpts, levels);
 }
 
 void launch_selftest_exact_math(hipStream_t st, unsigned long long* d_bad4) {

@@ -124,6 +124,20 @@ __device__ __forceinline__ Tile xcd_tile(int swz) {
     }
     return t;
 }
+// The same mapping for a role: a contiguous range of a 1-D grid's workgroups that starts at a multiple of 8 (the launcher pads), so that
+// workgroup `local` of the role runs on XCD local % 8. strips x blocks tiles; the swizzled mapping where the blocks divide by 8, the plain
+// one elsewhere: for the same linear workgroup id, the tile xcd_tile() gives on a (strips, blocks) grid. false: a padding workgroup.
+__device__ __forceinline__ bool role_tile(int local, int strips, int blocks, int swz, Tile& t) {
+    if (swz && (blocks & 7) == 0) {
+        const int xcd = local & 7, j = local >> 3;
+        t.strip = j % strips;
+        t.segblock = xcd * (blocks >> 3) + j / strips;
+    } else {
+        t.strip = local % strips;
+        t.segblock = local / strips;
+    }
+    return t.segblock < blocks;   // false: padding
+}
 
 // ---- arithmetic in the oracle's MUSICA_ORDER_FAST order ----
 // ((((w0*a + w1*b) + w2*c) + w3*d) + w4*e), products and sums rounded separately.

@@ -19,18 +19,7 @@ namespace musica {
 // level i + 1 both wait for reduce + band of level i only. Alone on the chip each is 1 - 2 wavefronts per SIMD of dependent arithmetic (8 x 2048^2:
 // 45 us and 20 us at i = 0); as the two roles of one grid they fill each other's issue slots, and the pyramid's dependent chain RB1 -> RB2 -> RB3 -> RB4
 // runs in the shadow of the sdev passes instead of in front of them. A role is a contiguous range of workgroups starting at a multiple of 8 (the XCD a
-// workgroup runs on is its index % 8: the tile mapping of xcd_tile() holds inside a role).
-__device__ __forceinline__ bool role_tile(int local, int strips, int blocks, int swz, Tile& t) {
-    if (swz && (blocks & 7) == 0) {
-        const int xcd = local & 7, j = local >> 3;
-        t.strip = j % strips;
-        t.segblock = xcd * (blocks >> 3) + j / strips;
-    } else {
-        t.strip = local % strips;
-        t.segblock = local / strips;
-    }
-    return t.segblock < blocks;   // false: padding
-}
+// workgroup runs on is its index % 8: the tile mapping of xcd_tile() holds inside a role, kernels_common.h role_tile).
 // The seam of the level-0 march that counts its own noise histogram (reduce_band_block<true, true>): the two columns either side of every
 // interior strip boundary, which that march leaves uncounted, from the stored band image. noise_hist.comp scans every (column, 16-row run)
 // on its own (:20-47, m outer), so these runs are the shader's whatever launch counts them. One thread per column and run: 20 band rows x 5
@@ -133,9 +122,7 @@ __global__ __launch_bounds__(kBlockThreads, 4) void k_rb_sdev(const RbSdevArgs a
         return;
     }
     if (!role_tile((int)blockIdx.x, l.strips, l.blocks, a.swz, tile)) return;
-    float* sd = l.sdev ? l.sdev + (size_t)img * l.plane : nullptr;
-    if (l.rows > 0) sdev_march_block<true, true>(l.band + (size_t)img * l.plane, sd, l.S, l.pitch, l.plane, l.hist + (size_t)img * a.hist_stride, a.cov, l.rows, tile, lh);
-    else sdev_run_block<true>(l.band + (size_t)img * l.plane, sd, l.S, l.pitch, l.plane, l.hist + (size_t)img * a.hist_stride, a.cov, tile, lh, nzw);
+    sdev_level_block<true, true, true>(l, tile, (size_t)img, a.hist_stride, a.cov, lh, nzw);
 }
 // `a`: the pointers, geometry of the reduce + band role and sl.{band, sdev, hist, rows} filled in by the caller; ls: the sdev level
 void launch_rb_sdev(hipStream_t st, RbSdevArgs a, const LevelDesc& ls, int batch) {
@@ -143,8 +130,7 @@ void launch_rb_sdev(hipStream_t st, RbSdevArgs a, const LevelDesc& ls, int batch
     int s_blocks;
     a.seam_items = 0;
     if (a.sl.rows < 0) { a.seam_items = seam_items(ls.S, a.cov); s_strips = 1; s_blocks = (a.seam_items + kBlockThreads - 1) / kBlockThreads; }
-    else if (a.sl.rows > 0) { const int segs = (ls.S + a.sl.rows - 1) / a.sl.rows; s_blocks = (segs + kWavesPerBlock - 1) / kWavesPerBlock; }
-    else s_blocks = (ls.S + kHistArea - 1) / kHistArea;
+    else s_blocks = sdev_blocks_per_strip(ls.S, a.sl.rows);
     a.sl.plane = ls.plane; a.sl.S = ls.S; a.sl.pitch = ls.pitch; a.sl.strips = s_strips; a.sl.blocks = s_blocks; a.sl.first = 0;
     a.rb_first = (s_strips * s_blocks + 7) & ~7;
     a.rb_strips = (a.S + kStripCols - 1) / kStripCols;

@@ -148,30 +148,6 @@ __global__ __launch_bounds__(kBlockThreads) void k_grad_hist(GradArgs a) {
     grad_hist_body<SHARED8, RAW>(a, img, lh, s_thr);
 }
 
-// histogram from a stored relevant image (kernel-level parity tests, one thread per 16x16 area like the reference)
-__global__ void k_grad_hist_ref(const float* __restrict__ img, const float* __restrict__ relevant, int N, int pitch, size_t plane,
-                                uint32_t* __restrict__ hist) {
-    const int gx = blockIdx.x * blockDim.x + threadIdx.x, gy = blockIdx.y * blockDim.y + threadIdx.y;
-    const int bx = gx * kHistArea, by = gy * kHistArea;
-    if (bx >= N || by >= N) return;
-    img += (size_t)blockIdx.z * plane;
-    relevant += (size_t)blockIdx.z * plane;
-    uint32_t* gh = hist + (size_t)blockIdx.z * MUSICA_GRAD_BINS;
-    for (int m = 0; m < kHistArea; m++)
-        for (int n = 0; n < kHistArea; n++) {
-            const int x = bx + m, y = by + n;
-            const float cur = (x < N && y < N) ? img[(size_t)y * pitch + x] : 0.0f;
-            if (cur == 0.0f) return;
-            if (cur != cur) continue;
-            const float scaled = cur * (float)MUSICA_GRAD_BINS;
-            if (!(scaled > -2147483648.0f && scaled < 2147483648.0f)) continue;
-            const int bin = (int)scaled;
-            if (bin < 0 || bin >= MUSICA_GRAD_BINS) continue;
-            const uint32_t w = f2u(relevant[(size_t)y * pitch + x] * 100.0f);
-            if (w) atomicAdd(&gh[bin], w);
-        }
-}
-
 __global__ void k_relevant(const float* __restrict__ normalized, const float* __restrict__ cnr, float* __restrict__ out, int N, int pitch,
                            size_t plane, int cnrS, int cnrPitch, size_t cnrPlane, int cnrScale) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -535,12 +511,6 @@ void launch_grad_hist(hipStream_t st, const GradArgs& a, int batch) {
         if (raw) hipLaunchKernelGGL((k_grad_hist<false, true>), grid, dim3(kBlockThreads), 0, st, a);
         else hipLaunchKernelGGL((k_grad_hist<false, false>), grid, dim3(kBlockThreads), 0, st, a);
     }
-}
-
-void launch_grad_hist_ref(hipStream_t st, const float* img, const float* relevant, const LevelDesc& l0, uint32_t* hist, int batch) {
-    const int areas = (l0.S + kHistArea - 1) / kHistArea;
-    hipLaunchKernelGGL(k_grad_hist_ref, dim3((areas + 15) / 16, (areas + 15) / 16, batch), dim3(16, 16), 0, st, img, relevant, l0.S, l0.pitch,
-                       l0.plane, hist);
 }
 
 void launch_relevant(hipStream_t st, const float* normalized, const float* cnr, float* out, const LevelDesc& l0, const LevelDesc& l3,

@@ -108,23 +108,17 @@ void launch_minmax(hipStream_t st, const uint16_t* px, int N, uint32_t* minmax, 
                    uint32_t* clahe_hist = nullptr);
 void launch_normalize(hipStream_t st, const uint16_t* px, float* out, const LevelDesc& l0, const uint32_t* minmax, int min_chain_exact, int batch);
 void launch_sqrt(hipStream_t st, const uint16_t* px, float* out, const LevelDesc& l0, int batch);
-void launch_sdev_hist(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov, int batch, int rows_per_wave, int swz);
-// the 16-row-run form of launch_sdev_hist for n <= kSdevRunLevelsMax levels in ONE launch (hist[k]: image 0's histogram of level k)
-void launch_sdev_hist_runs(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
-                           size_t hist_stride, int cov, int batch);
-// every level's sdev + noise-histogram pass in ONE launch, each level in its own form (rows[k] > 0: the march with that many rows per
-// wavefront, 0: one 16-row run per workgroup); sdev[k] == nullptr: histogram only
-void launch_sdev_hist_levels(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
-                             const int* rows, size_t hist_stride, int cov, int batch, int swz);
+// the sdev + noise-histogram passes (fast order) of n <= kSdevRunLevelsMax levels in ONE launch of k_sdev_hist, each level in its own form
+// (rows[k] > 0: the march with that many rows per wavefront, 0: one 16-row run per workgroup); sdev[k] == nullptr: histogram only; hist[k]:
+// image 0's histogram of level k; hist == nullptr: the sdev images alone (marches only, sides that are multiples of 8)
+void launch_sdev_hist(hipStream_t st, int n, const float* const* band, float* const* sdev, const LevelDesc* lv, uint32_t* const* hist,
+                      const int* rows, size_t hist_stride, int cov, int batch, int swz);
 void launch_noise_hist_only(hipStream_t st, const float* sdev, const LevelDesc& l, uint32_t* hist, size_t hist_stride, int cov, int batch);
 // img_sdev.comp:10-35 with the 25 squares accumulated in the shader's order (one thread per texel; MUSICA_FLAG_REFERENCE_ORDER)
 void launch_sdev_literal(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch);
-void launch_sdev_only(hipStream_t st, const float* band, float* sdev, const LevelDesc& l, int batch, int swz);   // the fast order's sdev image alone (no histogram)
-void launch_noise_curves(hipStream_t st, const uint32_t* hist, size_t hist_stride, musica_hist_max_point* maxpts, DevCurve* curves, const musica_contrast_params* cparams, int levels, int batch, DevCurveLut* luts, const uint32_t* minmax, int min_chain_exact, int* thr090, int lev0 = 0, int nlev = 0);
 void launch_curves_cnr(hipStream_t st, const uint32_t* hist, size_t hist_stride, musica_hist_max_point* maxpts, DevCurve* curves,
                        const musica_contrast_params* cparams, int levels, int batch, DevCurveLut* luts, const float* sdev, float* cnr,
                        const LevelDesc& l3, const uint32_t* minmax, int min_chain_exact, int* thr090, int lev0 = 0);
-void launch_cnr(hipStream_t st, const float* sdev, float* cnr, const LevelDesc& l3, const musica_hist_max_point* maxpts, int levels, int batch);
 void launch_selftest_exact_math(hipStream_t st, unsigned long long* d_bad4);
 // the RGBA plots of RENDER_HISTS (kernels_gradation.hip): out = MUSICA_HIST_RENDER_WIDTH x MUSICA_HIST_RENDER_HEIGHT packed texels
 void launch_render_noise_hist(hipStream_t st, const uint32_t* hist, const musica_hist_max_point* maxpt, uint32_t* out);
@@ -135,7 +129,6 @@ void launch_stats(hipStream_t st, const float* cnr, const LevelDesc& l3, const u
                   musica_stats* out, uint32_t image_id_base, uint32_t image_id_stride, int batch, double* partial);
 // kernels_gradation.hip
 void launch_grad_hist(hipStream_t st, const GradArgs& a, int batch);
-void launch_grad_hist_ref(hipStream_t st, const float* img, const float* relevant, const LevelDesc& l0, uint32_t* hist, int batch);
 void launch_relevant(hipStream_t st, const float* normalized, const float* cnr, float* out, const LevelDesc& l0, const LevelDesc& l3,
                      int cnrScale, int batch, const uint16_t* raw = nullptr, const int* thr090 = nullptr);
 // recount (images whose a.only_if word is set, into a.hist) + tone curve in one launch; ticket: [batch][kGradTicketStride] words, zero

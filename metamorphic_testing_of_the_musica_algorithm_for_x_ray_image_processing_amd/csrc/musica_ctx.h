@@ -201,7 +201,7 @@ struct musica_ctx : DeviceBuffers {
     // (StepForm::sd_levels); the stage entry points, getters and dumps want the stored images: ensure_sdev() writes them on demand.
     bool sd_fused, sdev_stored = true;
     bool pair_rb_sdev;         // the one-stream script pairs the sdev pass of level i with reduce + band of level i + 1 in one launch (k_rb_sdev); MUSICA_PAIR_RB_SDEV
-    bool sdev_one_launch;      // the sdev + noise-histogram passes of levels 0 .. 3 as ONE launch (k_sdev_hist_levels); MUSICA_SDEV_ONE_LAUNCH=0: one launch per marching level + one for the runs
+    bool sdev_one_launch;      // the sdev + noise-histogram passes of levels 0 .. 3 as ONE launch of k_sdev_hist; MUSICA_SDEV_ONE_LAUNCH=0: one launch per marching level + one for the runs
     int rows_rb[MUSICA_MAX_LEVELS];   // its coarse rows per wavefront
     // Level 0's reduce + band launch of a whole-step script counts the level's noise histogram itself (k_reduce_band_hist) and the level-0
     // sdev pass shrinks to the seam columns (StepForm::hist_rows). MUSICA_HIST_IN_RB: 0 never, 1 wherever the form exists, unset (-1):

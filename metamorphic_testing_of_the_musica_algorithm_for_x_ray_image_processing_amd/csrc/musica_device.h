@@ -79,21 +79,22 @@ struct LevelDesc {
     size_t plane;   // floats per image plane = pitch * S
 };
 
-// the levels of one k_sdev_hist_runs launch (kernels_analysis.hip): workgroups first .. of grid.x take level k's runs
+// the levels of one k_sdev_hist launch (kernels_analysis.hip): workgroups first .. of grid.x take level k's pass (sdev_parts.h
+// sdev_level_block); the sdev role of k_rb_sdev (kernels_expand_sd.hip) is one such level
 constexpr int kSdevRunLevelsMax = 4;
 struct SdevRunLevel {
     const float* band;
-    float* sdev;
-    uint32_t* hist;   // image 0's histogram of this level
+    float* sdev;      // nullptr: histogram only
+    uint32_t* hist;   // image 0's histogram of this level (not read by a launch without histogram)
     size_t plane;
     int S, pitch, strips, first;
-    int rows;         // k_sdev_hist_levels: rows per wavefront of a level that marches, 0 for a level that takes one 16-row run per workgroup
-    int blocks;       // k_sdev_hist_levels: workgroups per strip
+    int rows;         // rows per wavefront of a level that marches, 0 for a level that takes one 16-row run per workgroup
+    int blocks;       // workgroups per strip
 };
 struct SdevRunLevels {
     SdevRunLevel l[kSdevRunLevelsMax];
     int n;
-    int swz;          // k_sdev_hist_levels: XCD-aware workgroup -> tile mapping inside a level
+    int swz;          // XCD-aware workgroup -> tile mapping inside a level (kernels_common.h role_tile)
 };
 
 // the levels of one k_tiny_tail launch (kernels_pyramid.hip): level T + k reads `fine`, writes its reduced image `down`, its

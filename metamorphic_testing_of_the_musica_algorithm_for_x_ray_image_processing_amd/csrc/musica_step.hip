@@ -25,7 +25,7 @@ static int pick_rows(int dflt, int min_rows, int S, int rows_total, int batch, i
     }
     return rpw < min_rows ? min_rows : rpw;
 }
-// Rows per wavefront of the sdev + noise-histogram launch of level i; 0 = one 16-row run per workgroup (k_sdev_hist_run), the
+// Rows per wavefront of the sdev + noise-histogram launch of level i; 0 = one 16-row run per workgroup (sdev_run_block), the
 // form for every launch that cannot fill the chip with 16-row marches (MUSICA_SDEV_RUN=0 / 1: never / always).
 static int sdev_rows_default(const musica_ctx* c, int i, int batch) {
     const int mode = env_int("MUSICA_SDEV_RUN", -1);
@@ -205,38 +205,37 @@ static void enqueue_reduce(musica_ctx* c, const StepForm& f, int first, int end)
 }
 
 // stage "anly" (src/vk_processing.cpp:2284-2357)
-static void run_sdev_level(musica_ctx* c, const StepForm& f, int i, int rows) {
-    if (c->ref_order) {   // img_sdev.comp literally, then noise_hist.comp on the stored image
-        launch_sdev_literal(c->cur, c->d_band[i], c->d_sdev[i], c->lv[i], c->B);
-        launch_noise_hist_only(c->cur, c->d_sdev[i], c->lv[i], noise_hist_of(c, i), kNoiseHistStride, c->hist_cov, c->B);
-        return;
-    }
-    launch_sdev_hist(c->cur, c->d_band[i], f.sd(i) ? nullptr : c->d_sdev[i], c->lv[i], noise_hist_of(c, i), kNoiseHistStride, c->hist_cov, c->B, rows, c->xcd_swizzle);
-}
+// the fast order's sdev images of the levels whose hot path does not store them (no histogram), for getters / dumps / the stage entry points
 void ensure_sdev(musica_ctx* c) {
     if (c->sdev_stored) return;
+    const int rows = 16;
     for (int i = 0; i < MUSICA_CNR_LEVEL && i < c->L; i++)
-        if (rb_level(c, i)) launch_sdev_only(c->stream, c->d_band[i], c->d_sdev[i], c->lv[i], c->B, c->xcd_swizzle);
+        if (rb_level(c, i)) launch_sdev_hist(c->stream, 1, &c->d_band[i], &c->d_sdev[i], &c->lv[i], nullptr, &rows, 0, 0, c->B, c->xcd_swizzle);
     c->sdev_stored = true;
 }
-// Levels first .. MUSICA_CNR_LEVEL of sdev + noise histogram as one launch (their launches depend on nothing but their own band image):
-// every level in its own form (k_sdev_hist_levels), or, when every one of them is the 16-row-run form, a few dozen workgroups per small
-// level (k_sdev_hist_runs)
-static void run_sdev_levels(musica_ctx* c, const StepForm& f, int first, bool runs_only) {
-    const float* band[kSdevRunLevelsMax];
+// The sdev + noise-histogram passes of levels first .. last as ONE launch (k_sdev_hist: they depend on nothing but their own band image), every
+// level in the form rows_sdev gives it, or all of them in the form of `rows` where that is >= 0 (autotune's candidates). Under
+// MUSICA_FLAG_REFERENCE_ORDER a level at a time: img_sdev.comp literally, then noise_hist.comp on the stored image.
+static void run_sdev_levels(musica_ctx* c, const StepForm& f, int first, int last, int rows = -1) {
+    if (c->ref_order) {
+        for (int i = first; i <= last; i++) {
+            Span sp(c, MUSICA_KERNEL_SDEV_HIST);
+            launch_sdev_literal(c->cur, c->d_band[i], c->d_sdev[i], c->lv[i], c->B);
+            launch_noise_hist_only(c->cur, c->d_sdev[i], c->lv[i], noise_hist_of(c, i), kNoiseHistStride, c->hist_cov, c->B);
+        }
+        return;
+    }
     float* sdev[kSdevRunLevelsMax];
     uint32_t* hist[kSdevRunLevelsMax];
-    LevelDesc lv[kSdevRunLevelsMax];
-    int rows[kSdevRunLevelsMax];
-    int n = 0;
-    for (int i = first; i <= MUSICA_CNR_LEVEL; i++, n++) {
-        band[n] = c->d_band[i]; sdev[n] = f.sd(i) ? nullptr : c->d_sdev[i]; lv[n] = c->lv[i];
-        hist[n] = noise_hist_of(c, i);
-        rows[n] = c->rows_sdev[i] > 0 ? c->rows_sdev[i] : 0;
+    int rws[kSdevRunLevelsMax];
+    const int n = last - first + 1;
+    for (int k = 0; k < n; k++) {
+        sdev[k] = f.sd(first + k) ? nullptr : c->d_sdev[first + k];
+        hist[k] = noise_hist_of(c, first + k);
+        rws[k] = rows >= 0 ? rows : c->rows_sdev[first + k];
     }
     Span sp(c, MUSICA_KERNEL_SDEV_HIST);
-    if (runs_only) launch_sdev_hist_runs(c->cur, n, band, sdev, lv, hist, kNoiseHistStride, c->hist_cov, c->B);
-    else launch_sdev_hist_levels(c->cur, n, band, sdev, lv, hist, rows, kNoiseHistStride, c->hist_cov, c->B, c->xcd_swizzle);
+    launch_sdev_hist(c->cur, n, &c->d_band[first], sdev, &c->lv[first], hist, rws, kNoiseHistStride, c->hist_cov, c->B, c->xcd_swizzle);
 }
 // The sdev + noise-histogram passes still to run from level i on. Where level 0's histogram came out of its reduce + band launch, the seam
 // columns are what is left of its pass (a launch of its own here; a pair runs it in the sdev role). Then one launch, or one per marching
@@ -248,12 +247,9 @@ static void enqueue_sdev_from(musica_ctx* c, const StepForm& f, int i) {
         i = 1;
     }
     if (i > MUSICA_CNR_LEVEL) return;
-    if (f.sdev_one) { run_sdev_levels(c, f, i, false); return; }
-    for (; i < f.merged; i++) {
-        Span sp(c, MUSICA_KERNEL_SDEV_HIST);
-        run_sdev_level(c, f, i, c->rows_sdev[i]);
-    }
-    if (i <= MUSICA_CNR_LEVEL) run_sdev_levels(c, f, i, true);
+    if (f.sdev_one) { run_sdev_levels(c, f, i, MUSICA_CNR_LEVEL); return; }
+    for (; i < f.merged; i++) run_sdev_levels(c, f, i, i);
+    if (i <= MUSICA_CNR_LEVEL) run_sdev_levels(c, f, i, MUSICA_CNR_LEVEL);   // the levels from f.merged on all take the run form
 }
 // curves of every level + cnr of level 3 in one launch (kernels_analysis.hip k_curves_cnr)
 static void run_curves_cnr(musica_ctx* c) {
@@ -536,7 +532,7 @@ void autotune(musica_ctx* c) {
         struct { int* slot; const int* cand; int ncand; void (*fn)(musica_ctx*, const StepForm&, int, int); bool use; } jobs[3] = {
             {&c->rows_rb[i], cand_rb, 5, run_reduce_band, rb_level(c, i)},
             {&c->rows_expand[i], cand_pair, 4, [](musica_ctx* x, const StepForm& g, int l, int r) { run_expand_level(x, g, l, r, true); }, true},
-            {i <= MUSICA_CNR_LEVEL ? &c->rows_sdev[i] : nullptr, cand_sdev, 4, run_sdev_level, i <= MUSICA_CNR_LEVEL},
+            {i <= MUSICA_CNR_LEVEL ? &c->rows_sdev[i] : nullptr, cand_sdev, 4, [](musica_ctx* x, const StepForm& g, int l, int r) { run_sdev_levels(x, g, l, l, r > 0 ? r : 0); }, i <= MUSICA_CNR_LEVEL},
         };
         for (auto& j : jobs) {
             if (!j.use) continue;

@@ -489,7 +489,7 @@ constexpr int kChSlots = 4, kChCopies = 2;
 // take what is out of range (word 0 of the array is the first copy's lower one)
 constexpr int kGhCopies = 4, kGhStride = MUSICA_GRAD_BINS + 8;
 // SD (levels 0 .. 2 of a context that does not store their sdev images): the launch computes the 5 x 5 RMS of the band image itself, from a
-// window of six band rows it keeps in registers — the bits k_sdev_hist* would have stored (the same sum5 / musica_rms25_8 on the same
+// window of six band rows it keeps in registers — the bits k_sdev_hist would have stored (the same sum5 / musica_rms25_8 on the same
 // squares, sdev_parts.h) — instead of reading them: 4 B per texel less to read here and 4 B less for the sdev launch to write.
 struct BRow {
     float v[8];     // band columns c .. c+7

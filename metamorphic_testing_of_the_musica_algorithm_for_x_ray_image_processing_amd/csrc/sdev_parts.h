@@ -1,5 +1,5 @@
 // sdev_parts.h — the per-row pieces of the fused 5x5 RMS + noise-histogram march (img_sdev.comp + noise_hist.comp),
-// shared by k_sdev_hist* (kernels_analysis.hip), the level-0 reduce + band march that counts its own histogram (pyramid_march.h) and
+// shared by k_sdev_hist (kernels_analysis.hip), the level-0 reduce + band march that counts its own histogram (pyramid_march.h) and
 // the paired reduce + band / sdev launch (kernels_expand_sd.hip).
 #pragma once
 
@@ -309,6 +309,24 @@ __device__ __forceinline__ void sdev_run_block(const float* __restrict__ band, f
     }
     __syncthreads();
     hist_lds_flush(lh, hist);
+}
+
+// ---- one workgroup of a level's pass, whichever launch it rides in (k_sdev_hist, the sdev role of k_rb_sdev) ----
+// `tile` of the level's l.strips x l.blocks tiles (role_tile: the launcher pads a level to a multiple of 8 workgroups), image `img`: the
+// image's planes and histogram, then the march of l.rows rows per wavefront or, where l.rows == 0, one run.
+// RUNS = false compiles the run form out (every level of the launch marches); HIST = false: the sdev image alone, l.hist is not read.
+template <bool HIST, bool A8, bool RUNS>
+__device__ __forceinline__ void sdev_level_block(const SdevRunLevel& l, const Tile tile, size_t img, size_t hist_stride, int cov, uint32_t* lh,
+                                                 unsigned long long (*nzw)[8]) {
+    static_assert(HIST || !RUNS, "the run form always counts the histogram");
+    float* sd = l.sdev ? l.sdev + img * l.plane : nullptr;
+    if (!RUNS || l.rows > 0) sdev_march_block<HIST, A8>(l.band + img * l.plane, sd, l.S, l.pitch, l.plane, HIST ? l.hist + img * hist_stride : nullptr, cov, l.rows, tile, lh);
+    else sdev_run_block<A8>(l.band + img * l.plane, sd, l.S, l.pitch, l.plane, l.hist + img * hist_stride, cov, tile, lh, nzw);
+}
+// Workgroups per strip of a level of side S in its form: four wavefronts of `rows` rows each, or (rows == 0) one 16-row run
+static inline int sdev_blocks_per_strip(int S, int rows) {
+    const int per_block = rows > 0 ? rows * kWavesPerBlock : kHistArea;
+    return (S + per_block - 1) / per_block;
 }
 
 

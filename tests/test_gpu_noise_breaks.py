@@ -48,9 +48,9 @@ def _assert_hist(got, want_oracle, want_scan, sdev_oracle, n, what):
 #   504 / L4   cov = 0: every histogram stays empty whatever the band holds, and the curves come from empty histograms
 _SIDES = [(1032, 6), (1000, 6), (1536, 6), (520, 4), (504, 4)]
 _FIXED = {"MUSICA_AUTOTUNE": "0"}
-# name -> (environment, context flags, oracle order). With a batch the analysis stage is one launch for all levels (k_sdev_hist_levels), each
-# level in the form MUSICA_SDEV_RUN / MUSICA_SDEV_ROWS give it; MUSICA_SDEV_ONE_LAUNCH=0 takes the per-level launches k_sdev_hist /
-# k_sdev_hist_run and the merged run launch of the small levels (k_sdev_hist_runs).
+# name -> (environment, context flags, oracle order). With a batch the analysis stage is one launch of k_sdev_hist for all levels, each
+# level in the form MUSICA_SDEV_RUN / MUSICA_SDEV_ROWS give it; MUSICA_SDEV_ONE_LAUNCH=0 takes the per-level launches (one marching level:
+# k_sdev_hist<.., RUNS = false>) and the merged run launch of the small levels.
 _FORMS = {
     "march16": (dict(_FIXED, MUSICA_SDEV_RUN="0", MUSICA_SDEV_ROWS="16"), 0, "fast"),
     "march32": (dict(_FIXED, MUSICA_SDEV_RUN="0", MUSICA_SDEV_ROWS="32"), 0, "fast"),
@@ -189,7 +189,7 @@ def _step_case(ob, n, levels, env, flags, names, monkeypatch, executes=2):
 @pytest.mark.parametrize("one_launch", ["1", "0"])
 @pytest.mark.parametrize("n,levels", [(1032, 6), (1536, 6)], ids=["1032_L6", "1536_L6"])
 def test_lone_context_steps(ob, n, levels, one_launch, monkeypatch):
-    """All levels in one launch (k_sdev_hist_levels) and the per-level launches with the merged run launch of the small levels."""
+    """All levels in one launch of k_sdev_hist and the per-level launches with the merged run launch of the small levels."""
     p = _step_case(ob, n, levels, {"MUSICA_SDEV_ONE_LAUNCH": one_launch}, 0, (0,), monkeypatch)
     _compare_step(p, ob, n, levels, (0,), "one launch %s: " % one_launch)
     p.cleanup()
