@@ -7,6 +7,8 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     3 x 3 tiles with a 3-pixel ragged tail (a masked last chunk), and one region narrower than 16 pixels (a tile of the ragged chunk only);
   * the six dst / src slot operations at N = 151, a symmetry with a transpose, a blur of radius 8, a zoom of 32 / 31 and a veil of radius
     127 (wider than the slot) among them; and the same veil of the source plane into image 0 of the input buffer;
+  * the warp pair at N = 151: a random field over the whole +-16 pixels on 4 x 4 nodes (the widest windows, every border tile clamps)
+    of slot 0 at the margin's origin, where tiles and cells do not align, and of the source plane into image 0 at origin 0;
   * the contrast-detail pair at N = 151: nine details of radius 1 .. 8 inserted into image 0 (a disc across a tile corner among them),
     and the sums of the same details, shifted into the output plane, of image 1's output against slot 0;
   * the edge-response pair at N = 151: four slanted-edge plates of half-side 8 and 9, one per orientation (a plate across a tile corner
@@ -106,9 +108,14 @@ p.sim_zoom_reference(5, 0, (32, 31))
 p.sim_scatter_reference(6, 0, (127, 2, 3))
 for name, slot in (("rotate", 1), ("transform", 2), ("blur", 3), ("remap", 4), ("zoom", 5), ("scatter", 6)):
     note("musica_sim_%s_reference" % name, p.sim_get_reference(slot))
+field = np.random.default_rng(4).integers(-mp.WARP_MAX_SHIFT, mp.WARP_MAX_SHIFT + 1, (mp.warp_nodes(N),) * 2 + (2,))
+p.sim_warp_reference(7, 0, field)
+note("musica_sim_warp_reference", p.sim_get_reference(7))
 p.alter_set_source(phantom(N, 3, noise=4.0))
 p.alter_scatter((127, 2, 3))
 note("musica_alter_scatter", p.input_pixels()[0])
+p.alter_warp(field)
+note("musica_alter_warp", p.input_pixels()[0])
 details = [(30 + 40 * j - (7 if i == j else 0), 30 + 40 * i - (7 if i == j else 0), (1, 2, 4, 8, 1, 2, 4, 8, 1)[3 * i + j], (-512, 8, 128)[j]) for i in range(3) for j in range(3)]
 p.alter_details(details)
 note("musica_alter_details", p.input_pixels()[0])

@@ -445,6 +445,46 @@ int musica_sim_zoom_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_s
  * MUSICA_SCATTER_MAX_DEN, gcd(num, den) != 1, a slot out of range, dst_slot == src_slot, a source slot never written, an image too
  * small for the margin, a failed allocation of the row plane. Marks dst_slot written; changes no other slot. */
 int musica_sim_scatter_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t radius, uint32_t num, uint32_t den);
+/* ---- local deformation: the exact grid warp (new, not in the reference) ----
+ * Every other geometric alteration moves the whole frame rigidly or affinely; patient motion, breathing and positioning differences do
+ * not. harness.warp(image, field, origin) is the contract: a square 2-D uint16 or uint8 plane of side n under a backward warp
+ * out[x] = in[x + d(x)] (no holes, no folds), d given on a control grid of spacing G = MUSICA_WARP_GRID pixels. The field is M x M x 2
+ * integers: field[j][i] = (dx, dy), the displacement at node (row j, column i) in units of 1 / MUSICA_WARP_UNIT pixel, every component
+ * within +-MUSICA_WARP_MAX_SHIFT (16 pixels). With the origin (ox, oy), 0 <= ox, oy < G, pixel (x, y) of the plane sits at grid
+ * coordinate (x + ox, y + oy); M >= ((n - 1 + max(ox, oy)) >> 6) + 2 and nodes beyond that count are ignored, so one node array serves
+ * the raw plane (origin 0) and the output plane cropped by the margin (origin MUSICA_OUT_MARGIN). In integers, `>>` the arithmetic
+ * shift (a floor), for output pixel (x, y):
+ *   X = x + ox,  cx = X >> 6,  fx = X & 63                                       (Y, cy, fy likewise from y + oy)
+ *   per component c (0: dx, 1: dy), d = field[.., .., c]:
+ *     S_c = (64 - fy) ((64 - fx) d[cy, cx]     + fx d[cy, cx + 1])
+ *         +       fy  ((64 - fx) d[cy + 1, cx] + fx d[cy + 1, cx + 1])           |S_c| <= 2^24
+ *     s_c = (S_c + 2048) >> 12                                                   1 / 256 pixel; |s_c| <= max |d|
+ *   ix = x + (s_0 >> 8),  wx = s_0 & 255                                         (iy, wy likewise from s_1)
+ *   x0 = clamp(ix), x1 = clamp(ix + 1), y0 = clamp(iy), y1 = clamp(iy + 1)       clamp to 0 .. n - 1: edge replicated, no fill value
+ *   out[y, x] = ((256 - wy) ((256 - wx) in[y0, x0] + wx in[y0, x1]) + wy ((256 - wx) in[y1, x0] + wx in[y1, x1]) + 32768) >> 16
+ * ONE rounding of the field and ONE of the image sum, halves up; nothing is rounded between the two image passes. The sum is at most
+ * 65535 * 65536 + 32768 < 2^32, so every intermediate fits i32 or u32. The result has the input's type. The sign agrees with
+ * musica_sim_displace: an output that follows the input has its best shift at +d.
+ *   - the zero field is the identity;
+ *   - a constant field of whole pixels (256 kx, 256 ky) is in[clamp(y + ky), clamp(x + kx)] exactly, and a constant field survives the
+ *     interpolation unchanged: (4096 d + 2048) >> 12 = d;
+ *   - a constant plane is preserved for every field: the weights are convex, nothing saturates;
+ *   - reach: r(field) = (max |d| + 255) div 256 + 1, and a pixel reads only within r of itself;
+ *   - cropping commutes inside the reach: warp(P, F)[10:-10, 10:-10] and warp(P[10:-10, 10:-10], F, origin (10, 10)) agree everywhere
+ *     except within r(F) of the border, where the cropped plane clamps: a registered comparison is inset by r;
+ *   - no commutation with the symmetries of the square is claimed: the floors are not mirror-symmetric.
+ * The device results are bit-identical to that statement and repeat from call to call (kernels_warp.hip). The
+ * entry points take one origin for both axes and keep the nodes a call needs in a device buffer of the context, grown on first use. */
+#define MUSICA_WARP_GRID 64
+#define MUSICA_WARP_UNIT 256
+#define MUSICA_WARP_MAX_SHIFT 4096
+#define MUSICA_WARP_MAX_NODES 258   /* what N = 16384 needs at any origin */
+/* warp(reference slot `src_slot`, field, (origin, origin)) of the (N - 20)^2 u8 plane into `dst_slot` (device to device, on the ctx
+ * stream). `field`: nodes x nodes x 2 host int16, row-major, (dx, dy) per node, borrowed for the call. Refused before any device work:
+ * a NULL context or field, a slot out of range, dst_slot == src_slot, a source slot never written, origin > 63, `nodes` below
+ * ((N - 21 + origin) >> 6) + 2 or above MUSICA_WARP_MAX_NODES, a node component outside +-MUSICA_WARP_MAX_SHIFT (the refusal names the
+ * node), an image too small for the margin. Marks dst_slot written; changes no other slot. */
+int musica_sim_warp_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, const int16_t* field, uint32_t nodes, uint32_t origin);
 /* (N - 20)^2 bytes of reference slot `slot` to the host (synchronous); the slot must have been written. */
 int musica_sim_get_reference(musica_ctx* ctx, uint32_t slot, uint8_t* dst);
 
@@ -707,6 +747,13 @@ int musica_alter_zoom(musica_ctx* ctx, uint32_t image_index, uint32_t p, uint32_
  * Refused before any device work: a NULL context, no source, a radius outside 1 .. MUSICA_SCATTER_MAX_RADIUS, num = 0, num >= den,
  * den > MUSICA_SCATTER_MAX_DEN, gcd(num, den) != 1, image_index >= batch, a failed allocation of the row plane. */
 int musica_alter_scatter(musica_ctx* ctx, uint32_t image_index, uint32_t radius, uint32_t num, uint32_t den);
+/* warp(source plane, field, origin (0, 0)) (above, at musica_sim_warp_reference) into image `image_index` of the input buffer, enqueued
+ * on the ctx stream, with musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step and no
+ * reference slot. An entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT. `field`:
+ * nodes x nodes x 2 host int16, row-major, (dx, dy) per node, borrowed for the call. Refused before any device work: a NULL context or
+ * field, no source, `nodes` below ((N - 1) >> 6) + 2 or above MUSICA_WARP_MAX_NODES, a node component outside +-MUSICA_WARP_MAX_SHIFT
+ * (the refusal names the node), image_index >= batch. */
+int musica_alter_warp(musica_ctx* ctx, uint32_t image_index, const int16_t* field, uint32_t nodes);
 /* Test hook: the N x N integer draws of a noise alteration (k of COLLIMATOR / POISSON, for every pixel; the truncated noise of GAUSSIAN),
  * the same numbers musica_alter uses. Synchronous. */
 int musica_alter_draws(musica_ctx* ctx, const musica_alteration* spec, int32_t* dst);

@@ -315,6 +315,15 @@ constexpr int kScatterMaxRadius = 127;   // MUSICA_SCATTER_MAX_RADIUS
 constexpr int kScatterMaxDen = 64;       // MUSICA_SCATTER_MAX_DEN
 void launch_scatter_u16(hipStream_t st, const uint16_t* src, uint16_t* out, uint32_t* plane32, int n, int radius, int num, int den);
 void launch_scatter_u8(hipStream_t st, const uint8_t* src, uint8_t* out, uint32_t* plane32, int n, int radius, int num, int den);
+// kernels_warp.hip: harness.warp(plane, field, (origin, origin)), the exact backward warp by a displacement field on a control grid of
+// spacing kWarpGrid in units of 1 / kWarpUnit pixel, of a dense n x n plane into another (the planes must not overlap); any n >= 1,
+// 0 <= origin < kWarpGrid. nodes: m x m nodes on the device, row-major, one u32 each (dx in the low half, dy in the high one, both i16
+// within +-kWarpMaxShift), m >= ((n - 1 + origin) >> 6) + 2
+constexpr int kWarpGrid = 64;          // MUSICA_WARP_GRID
+constexpr int kWarpUnit = 256;         // MUSICA_WARP_UNIT
+constexpr int kWarpMaxShift = 4096;    // MUSICA_WARP_MAX_SHIFT
+void launch_warp_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const uint32_t* nodes, int m, int origin);
+void launch_warp_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, const uint32_t* nodes, int m, int origin);
 // kernels_details.hip: the contrast-detail relation. A detail (x, y, r, c) of a list that the caller has checked (limits, boxes inside
 // the plane and pairwise disjoint), packed: a plane side is at most 16384.
 constexpr int kDetailMaxRadius = 64;      // MUSICA_DETAIL_MAX_RADIUS

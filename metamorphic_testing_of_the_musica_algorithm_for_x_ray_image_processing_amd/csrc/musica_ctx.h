@@ -136,6 +136,9 @@ struct StudyState {
     int32_t* d_alter_draws = nullptr;    // [N * N], musica_alter_draws only
     // musica_alter_scatter / musica_sim_scatter_reference: the row passes' plane between the two launches
     uint32_t* d_scatter = nullptr;       // [N * N] (a slot's (N - 20)^2 use its start), allocated by the first scatter call
+    // musica_alter_warp / musica_sim_warp_reference: the device copy of the call's nodes, one u32 each
+    uint32_t* d_warp_nodes = nullptr;    // warp_nodes_cap nodes, regrown when a call needs more
+    size_t warp_nodes_cap = 0;
     // musica_alter_details / musica_sim_details: the device copy of the call's detail list and the details' sums
     PackedDetail* d_details = nullptr;             // [MUSICA_DETAIL_MAX], allocated by the first call of either
     unsigned long long* d_detail_out = nullptr;    // [MUSICA_DETAIL_MAX][kDetailWords], allocated by the first musica_sim_details

@@ -1,7 +1,7 @@
 // musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the eight query calls (musica_sim_*),
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
-// kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip and, each with a measurement and an alteration,
+// kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
 // kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip, kernels_levels.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
@@ -88,6 +88,43 @@ static int scatter_check(const char* fn, uint32_t radius, uint32_t num, uint32_t
     if (num == 0 || num >= den || den > MUSICA_SCATTER_MAX_DEN)
         return fail("%s: scatter fraction %u / %u is not 1 <= num < den <= %d", fn, num, den, MUSICA_SCATTER_MAX_DEN);
     if (gcd_u32(den, num) != 1) return fail("%s: scatter fraction %u / %u is not in lowest terms (gcd %u)", fn, num, den, gcd_u32(den, num));
+    return 1;
+}
+
+static_assert(kWarpGrid == MUSICA_WARP_GRID && kWarpUnit == MUSICA_WARP_UNIT && kWarpMaxShift == MUSICA_WARP_MAX_SHIFT,
+              "kernels_warp.hip's cells, window and i32 sums hold for the fields of include/musica.h");
+static_assert(MUSICA_WARP_MAX_NODES == ((16384 - 2 * MUSICA_OUT_MARGIN - 1 + MUSICA_WARP_GRID - 1) >> 6) + 2, "the nodes of the largest plane at the largest origin");
+
+// What both warp calls refuse about a field of nodes x nodes nodes for a plane of side n at `origin`, as processing.warp_field does; then
+// the m x m nodes the plane needs, packed for the device (dx in the low half of a u32, dy in the high one). No device work.
+static int warp_check(const char* fn, const int16_t* field, uint32_t nodes, uint32_t origin, size_t n, std::vector<uint32_t>& packed, int* m) {
+    if (origin >= MUSICA_WARP_GRID) return fail("%s: origin %u is not in 0 .. %d", fn, origin, MUSICA_WARP_GRID - 1);
+    const uint32_t need = (uint32_t)((n - 1 + origin) >> 6) + 2;
+    if (nodes < need) return fail("%s: %u nodes a side are fewer than the %u that a plane of %zu pixels at origin %u needs", fn, nodes, need, n, origin);
+    if (nodes > MUSICA_WARP_MAX_NODES) return fail("%s: %u nodes a side are more than %d", fn, nodes, MUSICA_WARP_MAX_NODES);
+    for (uint32_t j = 0; j < nodes; j++)
+        for (uint32_t i = 0; i < nodes; i++)
+            for (int k = 0; k < 2; k++) {
+                const int v = field[((size_t)j * nodes + i) * 2 + k];
+                if (v < -MUSICA_WARP_MAX_SHIFT || v > MUSICA_WARP_MAX_SHIFT)
+                    return fail("%s: node (row %u, column %u) has the component %d, beyond +-%d", fn, j, i, v, MUSICA_WARP_MAX_SHIFT);
+            }
+    packed.resize((size_t)need * need);
+    for (uint32_t j = 0; j < need; j++)
+        for (uint32_t i = 0; i < need; i++) {
+            const int16_t* d = field + ((size_t)j * nodes + i) * 2;
+            packed[(size_t)j * need + i] = (uint32_t)(uint16_t)d[0] | (uint32_t)(uint16_t)d[1] << 16;
+        }
+    *m = (int)need;
+    return 1;
+}
+
+// The call's nodes on the device, in the context's buffer (grown when a call needs more than the largest so far): copied on the
+// stream, behind the kernel that still reads the last call's, and `packed` is free again when this returns.
+static int warp_upload(musica_ctx* c, const char* fn, const std::vector<uint32_t>& packed) {
+    if (!grow(c, fn, &c->study.d_warp_nodes, &c->study.warp_nodes_cap, packed.size(), "nodes")) return 0;
+    HIP_OK(hipMemcpyAsync(c->study.d_warp_nodes, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
     return 1;
 }
 
@@ -420,6 +457,23 @@ int musica_sim_scatter_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_
         [&](const uint8_t* src, uint8_t* dst) {
             launch_scatter_u8(c->stream, src, dst, c->study.d_scatter, (int)sim_side(c), (int)radius, (int)num, (int)den);
         });
+}
+
+int musica_sim_warp_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const int16_t* field, uint32_t nodes, uint32_t origin) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_warp_reference: ctx is NULL");
+    if (!field) return fail("musica_sim_warp_reference: field is NULL");
+    std::vector<uint32_t> packed;
+    int m = 0;
+    return sim_derive_slot(
+        c, "musica_sim_warp_reference", dst_slot, src_slot,
+        [&] {   // behind the slot rules: a written source implies a plane
+            if (!warp_check("musica_sim_warp_reference", field, nodes, origin, sim_side(c), packed, &m)) return 0;
+            if (hipSetDevice(c->p.device) != hipSuccess) return fail("musica_sim_warp_reference: hipSetDevice failed");
+            return warp_upload(c, "musica_sim_warp_reference", packed);
+        },
+        [&](const uint8_t* src, uint8_t* dst) { launch_warp_u8(c->stream, src, dst, (int)sim_side(c), c->study.d_warp_nodes, m, (int)origin); });   // kernels_warp.hip
+    ABI_CATCH("musica_sim_warp_reference")
 }
 
 int musica_sim_remap_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint8_t lut[256]) {
@@ -1256,6 +1310,17 @@ int musica_alter_scatter(musica_ctx* c, uint32_t idx, uint32_t radius, uint32_t 
                       [&] { return scatter_plane(c, "musica_alter_scatter"); }, [&](const uint16_t* src, uint16_t* dst) {
                           launch_scatter_u16(c->stream, src, dst, c->study.d_scatter, c->N, (int)radius, (int)num, (int)den);   // kernels_scatter.hip
                       });
+}
+
+int musica_alter_warp(musica_ctx* c, uint32_t idx, const int16_t* field, uint32_t nodes) {
+    ABI_TRY
+    std::vector<uint32_t> packed;
+    int m = 0;
+    return alter_into(
+        c, "musica_alter_warp", !field ? "field" : nullptr, idx, [&] { return warp_check("musica_alter_warp", field, nodes, 0, (size_t)c->N, packed, &m); },
+        [&] { return warp_upload(c, "musica_alter_warp", packed); },
+        [&](const uint16_t* src, uint16_t* dst) { launch_warp_u16(c->stream, src, dst, c->N, c->study.d_warp_nodes, m, 0); });   // kernels_warp.hip
+    ABI_CATCH("musica_alter_warp")
 }
 
 int musica_alter_details(musica_ctx* c, uint32_t idx, uint32_t count, const musica_detail* details) {

@@ -58,6 +58,43 @@ def SCATTERS(n):
     return tuple((r, a, b) for a, b in SCATTER_FRACTIONS)
 
 
+# not in the reference: the amplitudes, in 1 / 256 pixel, of the local-deformation rows (warp), rows <family>_<a> of a study run with
+# `warps`: 0.25, 1, 4, 8 and 16 pixels, five strengths as every alteration of the reference's script has. WARPS(n) gives the 25 fields.
+WARP_AMPLITUDES = (64, 256, 1024, 2048, 4096)
+
+
+def _div_nearest(a, b):
+    """a / b for integers, b > 0, to nearest, ties away from zero."""
+    q = (2 * abs(a) + b) // (2 * b)
+    return q if a >= 0 else -q
+
+
+def WARPS(n):
+    """The 25 specs (name, field) of the warp rows of a side-n image, built in integers only, so that a name fixes the field on every
+    machine. With M = processing.warp_nodes(n) nodes a side (enough for the raw plane at origin 0 and for the output plane at the
+    margin), L = M - 1, u = 2i - L, v = 2j - L for node (row j, column i), w = (L^2 - u^2)(L^2 - v^2) (0 on the border), division to
+    nearest with ties away from zero, and a in WARP_AMPLITUDES, the fields (dx, dy) are
+        shift_<a>     (a, a)                         the sub-pixel and whole-pixel translation without a fill region
+        stretch_<a>   (0, a v / L)                   a uniform stretch along y (breathing)
+        shear_<a>     (a v / L, 0)                   a shear
+        bulge_<a>     (a u w / L^5, a v w / L^5)     a local magnification that vanishes at the border; the peak is about 0.385 a
+        twist_<a>     (-a v w / L^5, a u w / L^5)    a local rotation that vanishes at the border
+    each an int16 (M, M, 2) array with every component within +-a."""
+    m = mp.warp_nodes(n)
+    el = m - 1
+    families = (("shift", lambda a, u, v, w: (a, a)),
+                ("stretch", lambda a, u, v, w: (0, _div_nearest(a * v, el))),
+                ("shear", lambda a, u, v, w: (_div_nearest(a * v, el), 0)),
+                ("bulge", lambda a, u, v, w: (_div_nearest(a * u * w, el ** 5), _div_nearest(a * v * w, el ** 5))),
+                ("twist", lambda a, u, v, w: (_div_nearest(-a * v * w, el ** 5), _div_nearest(a * u * w, el ** 5))))
+    specs = []
+    for family, node in families:
+        for a in WARP_AMPLITUDES:
+            field = [[node(a, 2 * i - el, 2 * j - el, (el * el - (2 * i - el) ** 2) * (el * el - (2 * j - el) ** 2)) for i in range(m)] for j in range(m)]
+            specs.append(("%s_%d" % (family, a), np.array(field, dtype=np.int16).reshape(m, m, 2)))
+    return tuple(specs)
+
+
 def _patch_grid(n, sizes, defaults, side, cap, what, item):
     """The grid detail_grid, edge_grid and grating_grid share, for a raw image of side n: G x G square patches on a square grid inside
     the output plane's footprint. With B = PROCESSING_MARGIN and m = n - 2B, `sizes` defaults to the longest prefix of `defaults` of
@@ -473,6 +510,62 @@ def zoom(image, ratio):
     return ((g[:, None] * top + f[:, None] * bottom + np.uint64(d * d // 2)) // np.uint64(d * d)).astype(image.dtype)
 
 
+def warp(image, field, origin=(0, 0)):
+    """The exact grid warp of a square 2-D uint16 or uint8 plane of side n (not in the reference's script): a local deformation, the
+    backward warp out[x] = in[x + d(x)] (no holes, no folds) by a displacement field on a control grid of spacing G = 64 pixels. field
+    is an (M, M, 2) array of integers, field[j, i] = (dx, dy) at node (row j, column i) in units of 1 / 256 pixel, every component within
+    +-WARP_MAX_SHIFT = 4096 (16 pixels). origin = (ox, oy), 0 <= ox, oy < 64: pixel (x, y) of this plane sits at grid coordinate
+    (x + ox, y + oy); M >= ((n - 1 + max(ox, oy)) >> 6) + 2 and nodes beyond that count are ignored, so one node array serves the raw
+    plane (origin 0) and the output plane cropped by PROCESSING_MARGIN (origin 10). ValueError before any work otherwise
+    (processing.warp_field). Everything is integer arithmetic, `>>` the arithmetic shift (a floor). For output pixel (x, y):
+        X = x + ox,  cx = X >> 6,  fx = X & 63                                     (Y, cy, fy likewise from y + oy)
+        per component c (0: dx, 1: dy), d = field[.., .., c]:
+          S_c = (64 - fy) ((64 - fx) d[cy, cx]     + fx d[cy, cx + 1])
+              +       fy  ((64 - fx) d[cy + 1, cx] + fx d[cy + 1, cx + 1])         |S_c| <= 2^24
+          s_c = (S_c + 2048) >> 12                                                 1 / 256 px; |s_c| <= max |d| (convex weights, one rounding)
+        ix = x + (s_0 >> 8),  wx = s_0 & 255                                       (iy, wy likewise from s_1)
+        x0 = clamp(ix), x1 = clamp(ix + 1), y0 = clamp(iy), y1 = clamp(iy + 1)     clamp to 0 .. n - 1: edge replicated, no fill value
+        out[y, x] = ((256 - wy) ((256 - wx) in[y0, x0] + wx in[y0, x1]) + wy ((256 - wx) in[y1, x0] + wx in[y1, x1]) + 32768) >> 16
+    ONE rounding of the field and ONE of the image sum, halves up; nothing is rounded between the two image passes. The sum is at most
+    65535 * 65536 + 32768 < 2^32: every intermediate fits i32 or u32. The result has the input's dtype. The sign agrees with
+    displacement_table: an output that follows the input has its best shift at +d.
+      * The zero field is the identity.
+      * A constant field of whole pixels (256 kx, 256 ky) is in[clamp(y + ky), clamp(x + kx)] exactly; a constant field survives the
+        interpolation unchanged because (4096 d + 2048) >> 12 = d.
+      * A constant plane is preserved for every field: the weights are convex, nothing saturates.
+      * Reach: warp_reach(field) = (max |d| + 255) // 256 + 1, and a pixel reads only within the reach of itself.
+      * Cropping commutes inside the reach: warp(P, F)[10:-10, 10:-10] and warp(P[10:-10, 10:-10], F, origin=(10, 10)) agree
+        everywhere except within warp_reach(F) of the border, where they do differ because the cropped plane clamps: the registered
+        region is inset by the reach (register_warp, roi_warp).
+      * No commutation with the apply_symmetry elements is claimed: the floors are not mirror-symmetric.
+    This is the contract of musica_alter_warp and musica_sim_warp_reference (include/musica.h), which take one origin for both axes and
+    are bit-identical to it."""
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype not in (np.uint16, np.uint8) or not image.size:
+        raise ValueError("warp needs a non-empty square 2-D uint16 or uint8 plane, got %r %s" % (image.shape, image.dtype))
+    try:
+        ox, oy = origin
+    except (TypeError, ValueError):
+        raise ValueError("an origin is a pair (ox, oy), got %r" % (origin,))
+    n = image.shape[0]
+    for o in (ox, oy):
+        field = mp.warp_field(field, n, o)
+    s0, s1 = warp_shifts(field, np.arange(n) + int(ox), np.arange(n) + int(oy))
+    ix, iy = np.arange(n)[None, :] + (s0 >> 8), np.arange(n)[:, None] + (s1 >> 8)
+    wx, wy = (s0 & 255).astype(np.uint64), (s1 & 255).astype(np.uint64)
+    x0, x1, y0, y1 = (np.clip(v, 0, n - 1) for v in (ix, ix + 1, iy, iy + 1))
+    a, one = image.astype(np.uint64), np.uint64(256)
+    top = (one - wx) * a[y0, x0] + wx * a[y0, x1]
+    bottom = (one - wx) * a[y1, x0] + wx * a[y1, x1]
+    return (((one - wy) * top + wy * bottom + np.uint64(32768)) >> np.uint64(16)).astype(image.dtype)
+
+
+def warp_reach(field):
+    """(max |d| + 255) // 256 + 1: how far, in pixels, warp reads from an output pixel at most (the whole pixels of the largest
+    displacement, rounded up, and the bilinear neighbour)."""
+    return (int(np.abs(np.asarray(field).astype(np.int64)).max()) + 255) // 256 + 1
+
+
 def _box(acc, radius, axis):
     """sum_{k = -R .. R} acc[clamp(i + k)] along `axis` of a uint64 array: np.pad(mode="edge"), then the (2R + 1)-window sum as the
     difference of two entries of the padded array's cumulative sum."""
@@ -672,6 +765,20 @@ def roi_scatter(shape, spec):
     return _inset((0, 0, 0, 0, shape[1], shape[0]), 2 * mp.scatter_spec(spec)[0])
 
 
+def register_warp(alt, unalt, field):
+    """The altered result against the unaltered result warped like the alteration (the raw plane's field at the origin of the output
+    plane, the margin), both inset by the field's reach: within it the warped reference is built from clamped neighbours, while the
+    altered output there came from real neighbours in the processing margin (warp)."""
+    r = warp_reach(field)
+    h, w = alt.shape
+    return alt[r:max(h - r, r), r:max(w - r, r)], warp(unalt, field, origin=(PROCESSING_MARGIN,) * 2)[r:max(h - r, r), r:max(w - r, r)]
+
+
+def roi_warp(shape, field):
+    """The full frame inset by the field's reach, as the region of a device-side comparison; None when a side falls under 7."""
+    return _inset((0, 0, 0, 0, shape[1], shape[0]), warp_reach(field))
+
+
 # ---- running the pipeline -------------------------------------------------------------------------
 
 class Runner:
@@ -842,7 +949,7 @@ RELATIONS = (
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
-                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False):
+                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -878,6 +985,14 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
             raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
     zooms = [mp.zoom_ratio(z) for z in (zooms or ())]
     scatters = [mp.scatter_spec(s) for s in (scatters or ())]
+    try:
+        warps = [(str(name), mp.warp_field(field, n)) for name, field in (warps or ())]
+    except TypeError:
+        raise ValueError("a warp spec is (name, field), got %r" % (warps,))
+    for _, field in warps:   # the same nodes at the origin of the output plane
+        if n <= 2 * PROCESSING_MARGIN:
+            raise ValueError("a side of %d pixels leaves no output plane to warp" % n)
+        mp.warp_field(field, n - 2 * PROCESSING_MARGIN, PROCESSING_MARGIN)
     given = dict(details=details, edges=edges, gratings=gratings, gains=gains, luts=luts)
     for rel in RELATIONS:
         if given[rel.option] is not None:
@@ -885,13 +1000,13 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
-           (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None)
+           (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("warp",) if warps else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
-        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
+        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
         grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
 
@@ -901,14 +1016,15 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
 # context's method, the host's function, their parameter), which both move a reference plane as the alteration moves the input: the
 # registered comparison is then against the moved plane; noise = (the row's ordinal, alter(context, stream, image_index)) for the rows
 # that draw, what their ensembles repeat; measure = (relation, payload) for the rows of a relation (RELATIONS): what the row
-# measures beyond its comparisons, the raw plane's grid, gain spec or lut spec (with what Relation.source took from the raw plane).
-Alteration = collections.namedtuple("Alteration", "name host dev region move noise measure", defaults=(None, None, None, None))
+# measures beyond its comparisons, the raw plane's grid, gain spec or lut spec (with what Relation.source took from the raw plane); warp:
+# the field of a warp row, what its "warp" key reports and tracks.
+Alteration = collections.namedtuple("Alteration", "name host dev region move noise measure warp", defaults=(None, None, None, None, None))
 
 
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4, blur, zoom, scatter, cd, edge, grating, gain and lut rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur, zoom, scatter, warp, cd, edge, grating, gain and lut rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -943,6 +1059,9 @@ def study_alterations(raw, rng, p, seed, shape, opt):
     for s in opt.scatters:
         yield Alteration("scatter_%d_%d_%d" % s, lambda: scatter(raw, s), lambda: p.alter_scatter(s), lambda: roi_scatter(shape, s),
                          ("sim_scatter_reference", scatter, s))
+    for name, f in opt.warps:
+        yield Alteration(name, lambda: warp(raw, f), lambda: p.alter_warp(f), lambda: roi_warp(shape, f),
+                         ("sim_warp_reference", lambda plane, f: warp(plane, f, origin=(PROCESSING_MARGIN,) * 2), f), warp=f)
     for rel in RELATIONS:
         payloads = getattr(opt, rel.option)
         carried = (rel.source(raw),) if rel.source and payloads else ()
@@ -954,14 +1073,15 @@ class Scorer:
     """How run_study scores a row, on the host or on the device. produce(alteration) makes the altered output the one that is scored
     (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
     SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key; similarities, tone, scales and shifts take the row's comparisons, (reference key, region)
-    pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset)."""
+    pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset; keep: the dicts carry their
+    tile tables whatever displacement_tiles says, for a warp row's tracking)."""
 
     def __init__(self, runner, opt, unalt):
         self.runner, self.proc, self.opt, self.unalt = runner, runner.proc, opt, unalt
 
-    def shift_summary(self, table, region, tiles, tiles_off, tile_tables):
+    def shift_summary(self, table, region, tiles, tiles_off, tile_tables, keep=False):
         out = displacement_summary(table, region[4] * region[5], tiles, tiles_off)
-        if self.opt.displacement_tiles:
+        if self.opt.displacement_tiles or keep:
             out["tile_tables"], out["size"] = tile_tables, (region[4], region[5])
         return out
 
@@ -1021,11 +1141,11 @@ class DeviceScorer(Scorer):
                 out[i] = {k: r[k] for k in SCALES_KEYS}
         return out
 
-    def shifts(self, comparisons):
+    def shifts(self, comparisons, keep=False):
         """One musica_sim_displace call, none without a comparison."""
         res = self.proc.sim_displace([(0, slot) + region for slot, region in comparisons], self.opt.displacement, tables=True,
-                                     tiles=self.opt.displacement_tiles) if comparisons else []
-        return [self.shift_summary(r["table"], region, r["tiles_x"] * r["tiles_y"], r["tiles_off"], r.get("tile_tables"))
+                                     tiles=self.opt.displacement_tiles or keep) if comparisons else []
+        return [self.shift_summary(r["table"], region, r["tiles_x"] * r["tiles_y"], r["tiles_off"], r.get("tile_tables"), keep)
                 for (_, region), r in zip(comparisons, res)]
 
 
@@ -1070,9 +1190,9 @@ class HostScorer(Scorer):
         res = [multiscale_similarities(*self.sides(slot, region), min(self.opt.scales, max_scales(region[4], region[5]))) for slot, region in comparisons]
         return [{k: r[k] for k in SCALES_KEYS} for r in res]
 
-    def shifts(self, comparisons):
+    def shifts(self, comparisons, keep=False):
         tables = [(region, displacement_tile_tables(self.out, self.planes[slot], region, self.opt.displacement)) for slot, region in comparisons]
-        return [self.shift_summary(tt.astype(np.int64).sum(axis=(0, 1)), region, tt.shape[0] * tt.shape[1], displacement_tiles_off(tt), tt)
+        return [self.shift_summary(tt.astype(np.int64).sum(axis=(0, 1)), region, tt.shape[0] * tt.shape[1], displacement_tiles_off(tt), tt, keep)
                 for region, tt in tables]
 
 
@@ -1128,7 +1248,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
-              gains=None, gain_tables=False, luts=None, lut_tables=False):
+              gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1221,8 +1341,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     details: contrast-detail grids, each a detail list (x, y, r, c) for the raw plane (processing.detail_list; DETAILS(n) for the five
     contrasts 0.8 % .. 12.5 % on detail_grid's phantom) that is also valid for the output plane when shifted by the margin
     (output_details), else ValueError before any work. None adds nothing. Otherwise rows cd_<c> (c: the grid's first contrast) follow
-    the scatter_* rows: the raw image with the grid's discs inserted (insert_details; on the device: alter_details), "direct" scored
-    as for every row, "registered" None (nothing moved, as for the noise rows), and every row of the study gains "details": None
+    the scatter_* and warp rows: the raw image with the grid's discs inserted (insert_details; on the device: alter_details),
+    "direct" scored as for every row, "registered" None (nothing moved, as for the noise rows), and every row of the study gains "details": None
     except in the cd_ rows, where it is detail_row's dict of the details measured where they lie against the unaltered result
     (detail_statistics; on the device one musica_sim_details call behind the row's musica_sim_compare, whose exact sq_diff_sum of the
     full frame gives outside_mse): per radius the count and the mean, min, max and population std over the positions of contrast,
@@ -1288,11 +1408,27 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     device summarise exact integers with one function, so "levels" is equal to the last bit on every path. lut_tables: the dict also
     carries "levels", "curve_a" and "curve_b", the two curves. The rows draw nothing from `rng` and take no ordinal. Nothing is asserted:
     these are findings. A processor that fully normalises would show no curve shift for any monotone table; what it makes of a coarser
-    ADC, of saturation and of a negative is the finding."""
+    ADC, of saturation and of a negative is the finding.
+
+    warps: local-deformation specs (name, field), each field an (M, M, 2) array of node displacements in 1 / 256 pixel on the 64-pixel
+    control grid of the raw plane (warp; processing.warp_field; WARPS(n) for shifts, stretches, shears, bulges and twists of 0.25 to
+    16 pixels), valid for the raw plane at origin 0 and for the output plane at the margin, else ValueError before any work. None or
+    empty adds nothing. Otherwise rows named by the specs follow the scatter_* rows: the raw image warped by the field (on the device:
+    alter_warp). "direct" against the unaltered result says how much of the deformation reaches the output; "registered", over the
+    frame inset by the field's reach (roi_warp; None when the inset frame has a side under 8) against the unaltered result warped by
+    the same field at the output plane's origin, says what a processor that commutes with the deformation would not show. On the
+    device that reference goes into slot 1 and the warped vendor image into slot 3 (musica_sim_warp_reference). The rows draw nothing
+    from `rng` and take no ordinal; vendor, tone, scales and displacement apply to them as to a zoom row. Every row of such a study
+    gains "warp": None except in the warp rows, where it is {"reach": warp_reach(field), "peak": the largest |d| in pixels,
+    "tracking"}; "tracking" is None without a displacement radius (or where the inset frame is too small) and else warp_tracking's
+    dict from the tile tables of the row's DIRECT displacement comparison: how many 64 x 64 tiles there are, how many of their
+    expected shifts the radius reaches, how many of those the block matching found, and the rms distance between measured and
+    expected shift. Host and device tables are equal integers, so the dict is equal on every path. Nothing is asserted about the
+    values: whether MUSICA's local gains let the output follow a deformation tile by tile is the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
-                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables)
+                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -1324,7 +1460,17 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         if opt.displacement:   # a *_shift stays None without its comparison, or where the inset leaves a side under 7
             shifted = [(key + "_shift", (slot, _inset(region, opt.displacement))) for key, (slot, region) in own]
             shifted = [(key, c) for key, c in shifted if c[1] is not None]
-            out.update(zip([key for key, _ in shifted], scorer.shifts([c for _, c in shifted])))
+            tracked = alteration is not None and alteration.warp is not None   # a warp row reads its direct comparison's tile tables
+            out.update(zip([key for key, _ in shifted], scorer.shifts([c for _, c in shifted], keep=tracked)))
+        if alteration is not None and alteration.warp is not None:
+            direct = out.get("direct_shift")
+            out["warp"] = {"reach": warp_reach(alteration.warp), "peak": int(np.abs(alteration.warp.astype(np.int64)).max()) / mp.WARP_UNIT,
+                           "tracking": warp_tracking(alteration.warp, (PROCESSING_MARGIN,) * 2, _inset(full, opt.displacement), direct["tile_tables"])
+                           if direct else None}
+            if not opt.displacement_tiles:
+                for key in ("direct_shift", "registered_shift"):
+                    if out.get(key):
+                        del out[key]["tile_tables"], out[key]["size"]
         if alteration is not None and alteration.measure:
             relation, payload = alteration.measure
             out[relation.key] = scorer.measure(relation, relation.output(payload))
@@ -1444,6 +1590,16 @@ def scatter_list(text):
                                          % (mp.SCATTER_MAX_RADIUS, mp.SCATTER_MAX_DEN, text, ": %s" % e if str(e) else ""))
 
 
+def warp_list(text):
+    """--warps' comma list of names of WARPS: <family>_<amplitude>."""
+    import argparse
+    names = tuple(text.split(","))
+    known = ["%s_%d" % (f, a) for f in ("shift", "stretch", "shear", "bulge", "twist") for a in WARP_AMPLITUDES]
+    if not names or any(t not in known for t in names):
+        raise argparse.ArgumentTypeError("expected a comma-separated list of warps out of %s, got %r" % (",".join(known), text))
+    return names
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Metamorphic study of raw images (or a seeded phantom) on the HIP MUSICA path")
@@ -1476,6 +1632,12 @@ def main(argv=None):
                          "in lowest terms) and box radius R (1 .. 127; the tent x tent veil has sigma = sqrt(2R(R+1)/3) pixels), compared "
                          "directly and, inset by 2R, with the unaltered result veiled alike; without a list, 1/10,1/4,1/2,2/3,4/5 at "
                          "R = round(127 * size / 3072)")
+    ap.add_argument("--warps", nargs="?", const=True, default=None, type=warp_list, metavar="NAME,NAME,...",
+                    help="add the local-deformation rows (WARPS): shift, stretch, shear, bulge and twist fields on a 64-pixel control grid at "
+                         "the amplitudes 64, 256, 1024, 2048, 4096 / 256 pixels, the raw image warped exactly (integer bilinear), compared "
+                         "directly and, inset by the field's reach, with the unaltered result warped alike; with --displacement the tiles' "
+                         "best shifts are scored against the field's, written to warp_response.csv; on the GPU with --device-alterations "
+                         "(musica_alter_warp, musica_sim_warp_reference); without a list, all 25")
     ap.add_argument("--details", action="store_true",
                     help="add the rows cd_<c>: discs of radius 1 .. 32 inserted on a grid (detail_grid) at the contrasts c / 1024 = 0.8 %% .. "
                          "12.5 %%, measured where they lie (contrast, cnr, halo per radius; the change away from them), written to "
@@ -1598,6 +1760,8 @@ def main(argv=None):
         shift_args["zooms"] = args.zooms
     if args.scatters:
         shift_args["scatters"] = SCATTERS(args.size) if args.scatters is True else args.scatters
+    if args.warps:
+        shift_args["warps"] = [w for w in WARPS(args.size) if args.warps is True or w[0] in args.warps]
     if args.details:
         shift_args.update(details=DETAILS(args.size), detail_tables=args.detail_tables)
     if args.edges:

@@ -246,6 +246,65 @@ def displacement_maps(tile_tables, w, h):
     return rmse, mag
 
 
+def warp_shifts(field, xs, ys):
+    """harness.warp's interpolated displacements (s_0, s_1), two (len(ys), len(xs)) int64 arrays in 1 / 256 pixel, at the GRID coordinates
+    xs (columns) and ys (rows), origin included: with cx = X >> 6, fx = X & 63 and likewise in y, per component
+    s = ((64 - fy) ((64 - fx) d[cy, cx] + fx d[cy, cx + 1]) + fy ((64 - fx) d[cy + 1, cx] + fx d[cy + 1, cx + 1]) + 2048) >> 12.
+    The field must hold the nodes cy + 1, cx + 1 of every coordinate (processing.warp_field checks a plane's)."""
+    f = np.asarray(field).astype(np.int64)
+    xs, ys = np.asarray(xs, dtype=np.int64), np.asarray(ys, dtype=np.int64)
+    cx, fx, cy, fy = xs >> 6, (xs & 63)[None, :], ys >> 6, (ys & 63)[:, None]
+    out = []
+    for c in (0, 1):
+        d = f[:, :, c]
+        top = (64 - fx) * d[cy][:, cx] + fx * d[cy][:, cx + 1]
+        bottom = (64 - fx) * d[cy + 1][:, cx] + fx * d[cy + 1][:, cx + 1]
+        out.append(((64 - fy) * top + fy * bottom + 2048) >> 12)
+    return tuple(out)
+
+
+WARP_TRACKING_KEYS = ("tiles", "in_reach", "tracked", "err_rms")
+
+
+def warp_tracking(field, origin, region, tile_tables):
+    """Whether the output followed a deformation of the input tile by tile: a warp row's "tracking" dict (WARP_TRACKING_KEYS) from the
+    tile tables (tiles_y, tiles_x, S, S) of its DIRECT displacement comparison over `region` = (ax, ay, bx, by, w, h) of the output
+    plane, whose pixel (x, y) sits at grid coordinate (x + ox, y + oy), origin = (ox, oy). Per 64 x 64 tile of the region (the last
+    ones ragged) the expected shift is the exact mean over the tile's pixels of (s_0, s_1) / 256 (warp_shifts; an integer sum over
+    256 * pixels) and the measured shift the tile's argmin by the tables' tie rule (_displacement_argmin). A tile is in reach when its
+    expected shift, rounded half away from zero, lies within the tables' radius on both axes. "tiles": their number; "in_reach": those
+    in reach; "tracked": those in reach whose measured shift equals the rounded expected one on both axes; "err_rms": the rms over
+    the tiles in reach of the distance between the measured and the expected shift, in pixels (None without a tile in reach). Exact
+    integers in, one function on every path: the dict is equal wherever the tables are."""
+    ax, ay, _, _, w, h = (int(v) for v in region)
+    ox, oy = (int(v) for v in origin)
+    tt = np.asarray(tile_tables)
+    t, radius = mp.SIM_TILE, tt.shape[2] // 2
+    if tt.ndim != 4 or tt.shape[:2] != ((h + t - 1) // t, (w + t - 1) // t) or tt.shape[2] != tt.shape[3] or tt.shape[2] % 2 != 1:
+        raise ValueError("expected the (tiles_y, tiles_x, S, S) tile tables of a %d x %d region, got %r" % (w, h, tt.shape))
+    s = warp_shifts(field, ax + ox + np.arange(w), ay + oy + np.arange(h))
+
+    def nearest(num, den):   # num / den rounded half away from zero
+        q = (2 * abs(num) + den) // (2 * den)
+        return q if num >= 0 else -q
+
+    in_reach = tracked = 0
+    sq = 0.0
+    for ty in range(tt.shape[0]):
+        for tx in range(tt.shape[1]):
+            tile = [c[ty * t:ty * t + t, tx * t:tx * t + t] for c in s]
+            den = mp.WARP_UNIT * tile[0].size
+            sx, sy = int(tile[0].sum()), int(tile[1].sum())
+            ex, ey = nearest(sx, den), nearest(sy, den)
+            if max(abs(ex), abs(ey)) > radius:
+                continue
+            in_reach += 1
+            y, x = _displacement_argmin(tt[ty, tx])
+            tracked += (x - radius, y - radius) == (ex, ey)
+            sq += (x - radius - sx / den) ** 2 + (y - radius - sy / den) ** 2
+    return {"tiles": tt.shape[0] * tt.shape[1], "in_reach": in_reach, "tracked": tracked, "err_rms": math.sqrt(sq / in_reach) if in_reach else None}
+
+
 def _inset(region, r):
     """The region (ax, ay, bx, by, w, h) inset by r on every side, or None when a side falls under 7."""
     ax, ay, bx, by, w, h = region

@@ -154,6 +154,10 @@ BLUR_MAX_RADIUS = 8         # MUSICA_BLUR_MAX_RADIUS
 ZOOM_MAX_P = 32             # MUSICA_ZOOM_MAX_P
 SCATTER_MAX_RADIUS = 127    # MUSICA_SCATTER_MAX_RADIUS
 SCATTER_MAX_DEN = 64        # MUSICA_SCATTER_MAX_DEN
+WARP_GRID = 64              # MUSICA_WARP_GRID
+WARP_UNIT = 256             # MUSICA_WARP_UNIT
+WARP_MAX_SHIFT = 4096       # MUSICA_WARP_MAX_SHIFT
+WARP_MAX_NODES = 258        # MUSICA_WARP_MAX_NODES
 SIM_TILE = 64               # MUSICA_SIM_TILE
 DETAIL_MAX_RADIUS = 64      # MUSICA_DETAIL_MAX_RADIUS
 DETAIL_MAX_CONTRAST = 512   # MUSICA_DETAIL_MAX_CONTRAST
@@ -213,6 +217,32 @@ def scatter_spec(spec):
     if math.gcd(a, b) != 1:
         raise ValueError("scatter fraction %d / %d is not in lowest terms" % (a, b))
     return r, a, b
+
+
+def warp_nodes(n, origin=0):
+    """How many nodes a side the field of a plane of side n at `origin` needs: ((n - 1 + origin) >> 6) + 2."""
+    return ((int(n) - 1 + int(origin)) >> 6) + 2
+
+
+def warp_field(field, n, origin=0):
+    """A displacement field as harness.warp and the library take it for a plane of side n at `origin` (one integer for both axes): a
+    contiguous int16 array (M, M, 2), field[j, i] = (dx, dy) of node (row j, column i) in units of 1 / WARP_UNIT pixel, else ValueError:
+    an origin outside 0 .. WARP_GRID - 1, an array of integers that is not (M, M, 2), M below warp_nodes(n, origin) or above
+    WARP_MAX_NODES, a component beyond +-WARP_MAX_SHIFT. The same check as the C side's."""
+    if isinstance(origin, bool) or not isinstance(origin, (int, np.integer)) or not 0 <= origin < WARP_GRID:
+        raise ValueError("origin %r is not an integer in 0 .. %d" % (origin, WARP_GRID - 1))
+    a = np.asarray(field)
+    if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 2 or a.dtype.kind not in "iu":
+        raise ValueError("a field is an (M, M, 2) array of integers, got %r %s" % (a.shape, a.dtype))
+    need = warp_nodes(n, origin)
+    if a.shape[0] < need:
+        raise ValueError("%d nodes a side are fewer than the %d that a plane of %d pixels at origin %d needs" % (a.shape[0], need, int(n), origin))
+    if a.shape[0] > WARP_MAX_NODES:
+        raise ValueError("%d nodes a side are more than %d" % (a.shape[0], WARP_MAX_NODES))
+    if int(a.min()) < -WARP_MAX_SHIFT or int(a.max()) > WARP_MAX_SHIFT:
+        j, i, k = (int(v[0]) for v in np.nonzero(abs(a.astype(np.int64)) > WARP_MAX_SHIFT))
+        raise ValueError("node (row %d, column %d) has the component %d, beyond +-%d" % (j, i, int(a[j, i, k]), WARP_MAX_SHIFT))
+    return np.ascontiguousarray(a, dtype=np.int16)
 
 
 def _ints(t, k):
@@ -637,6 +667,8 @@ ABI = {
     "musica_alter_zoom": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_scatter_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_scatter": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "musica_sim_warp_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.c_int16), C.c_uint32, C.c_uint32]),
+    "musica_alter_warp": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_int16), C.c_uint32]),
     "musica_alter_details": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Detail)]),
     "musica_sim_details": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Detail), C.POINTER(SimDetailResult)]),
     "musica_alter_edges": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Edge)]),
@@ -1046,6 +1078,13 @@ class MusicaProcessing:
         r, a, b = scatter_spec(spec)
         self._ok(self._lib.musica_sim_scatter_reference(self._h, int(dst_slot), int(src_slot), r, a, b), "musica_sim_scatter_reference")
 
+    def sim_warp_reference(self, dst_slot, src_slot, field, origin=OUT_MARGIN):
+        """Reference slot `src_slot` as harness.warp(slot, field, (origin, origin)) (field: warp_field) into `dst_slot`, on the device.
+        The default origin is the margin: the field of the raw plane, applied to the output plane."""
+        f = warp_field(field, self.imageSize - 2 * OUT_MARGIN, origin)
+        self._ok(self._lib.musica_sim_warp_reference(self._h, int(dst_slot), int(src_slot), f.ctypes.data_as(C.POINTER(C.c_int16)), f.shape[0], int(origin)),
+                 "musica_sim_warp_reference")
+
     def sim_details(self, details, slot, image_index=0):
         """harness.detail_statistics(output of `image_index`, reference slot `slot`, details) on the device: the details (x, y, r, c) in
         the (N - 20)^2 output plane's coordinates (detail_list; c is not looked at). Returns one dict per detail: "disc" and "ring", each
@@ -1338,6 +1377,11 @@ class MusicaProcessing:
         waves = np.array([w for g in gs for w in g[6]], dtype=np.int16)
         self._ok(self._lib.musica_alter_gratings(self._h, int(image_index), len(gs), arr, waves.ctypes.data_as(C.POINTER(C.c_int16)), waves.size),
                  "musica_alter_gratings")
+
+    def alter_warp(self, field, image_index=0):
+        """harness.warp(src, field): the exact backward warp by the displacement field on the 64-pixel control grid (warp_field)."""
+        f = warp_field(field, self.imageSize)
+        self._ok(self._lib.musica_alter_warp(self._h, int(image_index), f.ctypes.data_as(C.POINTER(C.c_int16)), f.shape[0]), "musica_alter_warp")
 
     def alter_gain(self, gx, gy, image_index=0):
         """harness.apply_gain(src, gx, gy): the source under the separable gain map gx[x] gy[y] / GAIN_ONE^2 (gain_tables), one rounding,

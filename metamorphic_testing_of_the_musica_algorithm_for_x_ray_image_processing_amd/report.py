@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -41,6 +41,8 @@ GRATING_CSV_HEADER = ['raw file', 'alteration', 'period', 'gratings'] + ['%s %s'
                      ['outside mse']   # grating_response.csv
 GAIN_CSV_HEADER = ['raw file', 'alteration', 'axis', 'lines'] + [k.replace('_', ' ') for k in PROFILE_KEYS]   # gain_response.csv
 LEVEL_CSV_HEADER = ['raw file', 'alteration'] + [k.replace('_', ' ') for k in LEVEL_KEYS]   # level_response.csv
+
+WARP_CSV_HEADER = ['raw file', 'alteration', 'reach', 'peak'] + [k.replace('_', ' ') for k in WARP_TRACKING_KEYS] + ['registered mse', 'registered ssim']   # warp_response.csv
 
 
 def covariance_csv_header(radius):
@@ -201,7 +203,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     axis (an empty cell where one is None).
 
     Studies run with luts (rows[0] has "levels") also get level_response.csv (LEVEL_CSV_HEADER): one line per lut row, level_summary's
-    numbers of the full frame (an empty cell where one is None)."""
+    numbers of the full frame (an empty cell where one is None).
+
+    Studies run with warps (rows[0] has "warp") also get warp_response.csv (WARP_CSV_HEADER): one line per warp row, the field's reach
+    and peak displacement in pixels, the four tracking numbers of metrics.warp_tracking (empty without a displacement radius) and the
+    registered mse and ssim (empty where the row has no registered comparison)."""
     os.makedirs(out_dir, exist_ok=True)
     having = lambda key: [(raw_name, rows) for raw_name, rows in studies if rows and key in rows[0]]   # noqa: E731
     toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
@@ -226,6 +232,9 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
          lambda r, ovd: [c for key, _ in scale_groups for c in _scale_csv_cells(r.get(key))]),
         ("ensemble.csv", ENSEMBLE_CSV_HEADER, ensembles or None, lambda r, ovd: _ensemble_cells(r["ensemble"])),
         ("noise_covariance.csv", covariance_csv_header(radius), covs or None, lambda r, ovd: _covariance_cells(r["ensemble"], radius)),
+        ("warp_response.csv", WARP_CSV_HEADER, having("warp") or None,
+         lambda r, ovd: None if r["warp"] is None else [r["warp"]["reach"], r["warp"]["peak"]] + _cells(r["warp"]["tracking"], WARP_TRACKING_KEYS) +
+         _cells(r["registered"], ("mse", "ssim"))),
     ]
     for name, header, covered, cells in tables:
         if covered is not None:
