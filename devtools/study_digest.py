@@ -21,7 +21,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     profiles of image 1's output against slot 0 over the full frame (3 x 3 tiles with a ragged tail), a ragged region from mid-tile
     with different origins on the two sides, a single column and a single pixel;
   * the tone-table pair at N = 151: a permutation of the 65536 levels applied into image 0, and the levels of image 1's output against
-    slot 0 over the same four regions, the classes the source plane >> 4 (4096 classes) and >> 9 (128).
+    slot 0 over the same four regions, the classes the source plane >> 4 (4096 classes) and >> 9 (128);
+  * the gradients at N = 151 of other images' outputs against slot 0: the full frame (129 x 129 interior pixels: 3 x 3 tiles with a
+    one-pixel ragged tail), a ragged region from mid-tile with different origins on the two sides, a 7-wide column and a 7 x 7 corner;
+    gsim is the one f64 of the call summed on the device.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -137,5 +140,7 @@ p.alter_lut((np.arange(65536, dtype=np.int64) * 40503 + 77) % 65536)   # a permu
 note("musica_alter_lut", p.input_pixels()[0])
 for shift in (4, 9):
     note("musica_sim_levels_s%d" % shift, p.sim_levels([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (1, 0, 64, 0, 64, 0, 1, NW), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)], shift))
+if hasattr(p, "sim_gradients"):   # a --tree from before the gradient metrics has none: its other digests compare as they are
+    note("musica_sim_gradients", p.sim_gradients([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 7, NW - 1), (1, 0, NW - 7, NW - 7, 0, 0, 7, 7)]))
 p.cleanup()
 print(json.dumps(digests))

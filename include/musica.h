@@ -1026,6 +1026,42 @@ typedef struct musica_sim_level_result {
 int musica_sim_levels(musica_ctx* ctx, uint32_t shift, uint32_t count, const musica_sim_query* queries, musica_sim_level_result* results,
                       uint64_t* tables, uint64_t table_words);
 
+/* ---- gradient metrics: the Sobel gradients of a comparison, by the edge strength of the reference (new, not in the reference) ----
+ * MUSICA amplifies weak gradients more than strong ones; every other measurement compares gray levels, windows, scales, positions, lines
+ * or planted patches. This one compares the edges of the image itself. metrics.gradient_statistics is the contract; every word of the
+ * tables is an exact integer equal to it and byte-identical from call to call.
+ * A query is musica_sim_compare's (side a the 8-bit output of batch image `image_index`, quantised while read exactly as
+ * musica_sim_compare reads it; side b reference slot `slot`; w, h >= 7). Over the INTERIOR of the region, the (w - 2) x (h - 2) pixels
+ * whose 3 x 3 neighbourhood lies inside the region (no pixel outside a region is read), both sides get the integer Sobel gradient
+ *   gx = (p[y-1][x+1] + 2 p[y][x+1] + p[y+1][x+1]) - (the same at x - 1)
+ *   gy = (p[y+1][x-1] + 2 p[y+1][x] + p[y+1][x+1]) - (the same at y - 1)
+ * both in -1020 .. 1020, and per pixel the terms
+ *   A = gxa^2 + gya^2, B = gxb^2 + gyb^2, dot = gxa gxb + gya gyb, cross = gxa gyb - gya gxb
+ * each of magnitude <= 1 300 500 (attained by A and B at the neighbourhood [[0,0,255],[0,.,255],[0,255,255]]). A pixel's class is the
+ * bit length of B, 0 .. 21: class 0 is a reference pixel without gradient, class 21 starts at 2^20 (a diagonal step, gx = gy = 765).
+ * Query i gets a table [MUSICA_GRADIENT_CLASSES][MUSICA_GRADIENT_WORDS] of uint64_t in the flat `tables`, from
+ * results[i].table_offset (in words: i * MUSICA_GRADIENT_CLASSES * MUSICA_GRADIENT_WORDS) on. A class's six words are
+ *   n, sum A, sum B, sum dot, sum cross, neg = the number of its pixels with dot < 0
+ * sum dot and sum cross signed, in two's complement. The n of a table add up to results[i].pixels = (w - 2) (h - 2).
+ * results[i].gsim is the mean over the interior of q = (2 dot + C) / (A + B + C), C = MUSICA_GRADIENT_C = 2720 (the 170 of GMSD, Xue et
+ * al. 2014, stated for Prewitt / 3, carried to Sobel's squared scale: x 16): numerator and denominator exact integers below 2^53, one
+ * correctly rounded f64 division per pixel, the sum in the device's own FIXED order (per-workgroup partials folded by a second launch,
+ * no f64 atomics), so it repeats bit for bit and agrees with the host's math.fsum within rounding; identical sides give exactly 1.0.
+ * Every word of the count tables is written and nothing behind them. Synchronous, on the context's stream after whatever was enqueued
+ * there; changes no slot, no result of a step and no input image; scratch is allocated on first use. Refused before any device work:
+ * what musica_sim_compare refuses, then a NULL `tables` and table_words < count * MUSICA_GRADIENT_CLASSES * MUSICA_GRADIENT_WORDS.
+ * After a refusal the context stays usable. */
+#define MUSICA_GRADIENT_CLASSES 22
+#define MUSICA_GRADIENT_WORDS 6
+#define MUSICA_GRADIENT_C 2720
+typedef struct musica_sim_gradient_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t pixels;                /* (w - 2) * (h - 2) */
+    double gsim;                    /* mean of q over the interior */
+} musica_sim_gradient_result;
+int musica_sim_gradients(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_gradient_result* results,
+                         uint64_t* tables, uint64_t table_words);
+
 /* ---- device-resident output and stream ordering (new, not in the reference) ---- */
 
 /* What musica_export_out writes per image. */

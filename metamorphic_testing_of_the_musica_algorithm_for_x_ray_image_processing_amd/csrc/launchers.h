@@ -423,6 +423,21 @@ void level_geometry(LevelQueryDev& q, int count);   // count: the queries of the
 // harness.level_statistics over `count` queries with the classes source >> shift (grid.x = min(max_chunks, 128 / count)). tables: every
 // query's words, zeroed by the caller: the workgroups add into them with u64 atomics
 void launch_sim_levels(hipStream_t st, const LevelQueryDev* d_qs, int count, int max_chunks, int shift, unsigned long long* tables);
+// kernels_gradients.hip: the gradient metrics. One comparison of musica_sim_gradients: w, h >= 7 are the REGION's; the kernel tiles its
+// interior, (w - 2) x (h - 2). tiles_x / tiles_y: ceil((w - 2) / 64), ceil((h - 2) / 64); tile_base: where the query's tile partials
+// start in the launch's partials, in doubles; table: where its [kGradClasses][kGradWords] u64 start in the launch's flat tables, in words.
+constexpr int kGradClasses = 22;          // MUSICA_GRADIENT_CLASSES: the bit lengths of B <= 1 300 500
+constexpr int kGradWords = 6;             // MUSICA_GRADIENT_WORDS: n, sum A, sum B, sum dot, sum cross, neg
+constexpr int kGradC = 2720;              // MUSICA_GRADIENT_C: the stabiliser of q
+struct GradQueryDev : SimRegion {
+    int tiles_x, tiles_y;
+    unsigned long long tile_base;
+    unsigned long long table;
+};
+// metrics.gradient_statistics over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y), then k_gradients_fold. tables:
+// every query's words, zeroed by the caller: the tiles add into them with u64 atomics; part: a double per tile (all written); out[i]: the
+// sum of q over query i's interior
+void launch_sim_gradients(hipStream_t st, const GradQueryDev* d_qs, int count, int max_tiles, unsigned long long* tables, double* part, double* out);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

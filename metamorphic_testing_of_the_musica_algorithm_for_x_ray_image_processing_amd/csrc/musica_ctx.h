@@ -161,6 +161,12 @@ struct StudyState {
     uint16_t* d_lut = nullptr;                     // [kLutEntries] (128 KiB), allocated by the first musica_alter_lut
     LevelQueryDev* d_level_q = nullptr;            // [MUSICA_LEVEL_MAX_QUERIES]
     unsigned long long* d_level_tables = nullptr;  // [MUSICA_LEVEL_MAX_QUERIES][kLevelMaxClasses][kLevelWords] (768 KiB), allocated by the first musica_sim_levels
+    // musica_sim_gradients: the queries, the flat tables, the sums of q and the tiles' partials
+    GradQueryDev* d_grad_q = nullptr;              // [MUSICA_SIM_MAX_QUERIES]
+    unsigned long long* d_grad_tables = nullptr;   // [MUSICA_SIM_MAX_QUERIES][kGradClasses][kGradWords], allocated by the first musica_sim_gradients
+    double* d_grad_out = nullptr;                  // [MUSICA_SIM_MAX_QUERIES]
+    double* d_grad_part = nullptr;                 // the tiles' partials of one call: grad_part_cap doubles, regrown when a call needs more
+    size_t grad_part_cap = 0;
 };
 
 struct musica_ctx : DeviceBuffers {

@@ -1,8 +1,8 @@
-// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the eight query calls (musica_sim_*),
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the nine query calls (musica_sim_*),
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip, kernels_levels.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip, kernels_levels.hip, and kernels_gradients.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
@@ -968,6 +968,51 @@ int musica_sim_levels(musica_ctx* c, uint32_t shift, uint32_t count, const music
     }
     return 1;
     ABI_CATCH("musica_sim_levels")
+}
+
+// ---- the gradients of a comparison (musica_sim_gradients, include/musica.h; kernels_gradients.hip) --------------------------------------
+static_assert(kGradClasses == MUSICA_GRADIENT_CLASSES && kGradWords == MUSICA_GRADIENT_WORDS && kGradC == MUSICA_GRADIENT_C,
+              "kernels_gradients.hip's constants are include/musica.h's");
+
+int musica_sim_gradients(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_gradient_result* out, uint64_t* tables, uint64_t table_words) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_gradients", count, qs, out)) return 0;
+    if (!tables) return fail("musica_sim_gradients: tables is NULL");
+    const size_t per_query = (size_t)kGradClasses * kGradWords, words = count * per_query;
+    if (table_words < words) return fail("musica_sim_gradients: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
+    std::vector<GradQueryDev> hq(count);
+    size_t tiles = 0;
+    int max_tiles = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        sim_region(c, qs[i], hq[i]);
+        hq[i].tiles_x = tiles_along(qs[i].w - 2);   // of the interior
+        hq[i].tiles_y = tiles_along(qs[i].h - 2);
+        hq[i].tile_base = tiles;
+        hq[i].table = i * per_query;
+        tiles += (size_t)hq[i].tiles_x * hq[i].tiles_y;
+        max_tiles = std::max(max_tiles, hq[i].tiles_x * hq[i].tiles_y);
+    }
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_grad_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_grad_tables, (size_t)MUSICA_SIM_MAX_QUERIES * per_query) &&
+          ensure(c, &st.d_grad_out, MUSICA_SIM_MAX_QUERIES)))
+        return fail("musica_sim_gradients: device allocation failed");
+    if (!grow(c, "musica_sim_gradients", &st.d_grad_part, &st.grad_part_cap, tiles, "tile partials")) return 0;
+    HIP_OK(hipMemcpyAsync(st.d_grad_q, hq.data(), count * sizeof(GradQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_grad_tables, 0, words * sizeof(uint64_t), c->stream));   // the tiles add into them
+    launch_sim_gradients(c->stream, st.d_grad_q, (int)count, max_tiles, st.d_grad_tables, st.d_grad_part, st.d_grad_out);
+    HIP_OK(hipGetLastError());
+    std::vector<double> sums(count);
+    HIP_OK(hipMemcpyAsync(tables, st.d_grad_tables, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(sums.data(), st.d_grad_out, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq, the tables and the sums are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        out[i].table_offset = hq[i].table;
+        out[i].pixels = (uint64_t)(qs[i].w - 2) * (qs[i].h - 2);
+        out[i].gsim = sums[i] / (double)out[i].pixels;
+    }
+    return 1;
+    ABI_CATCH("musica_sim_gradients")
 }
 
 // ---- ensemble statistics (musica_sim_ensemble_*, include/musica.h; kernels_ensemble.hip) ------------------------------------------------

@@ -1,8 +1,9 @@
 // study_device.h — what the study's kernels share on the device (kernels_similarity.hip, kernels_scales.hip, kernels_joint.hip,
 // kernels_displace.hip, kernels_covariance.hip, kernels_ensemble.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip,
-// kernels_gain.hip, kernels_levels.hip): the address-space typedefs, the reductions and their ONE order, the 64 x 64 tile of a region, the pixel words of
-// the kernels that stream a u16 plane and the insertion body of the patch relations (insert_patches), the packed byte windows of
-// k_displace and k_cov_add, and the per-window SSIM terms.
+// kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip): the address-space typedefs, the reductions and their ONE order, the
+// 64 x 64 tile of a region, the pixel words of the kernels that stream a u16 plane and the insertion body of the patch relations
+// (insert_patches), the packed byte windows of k_displace and k_cov_add, the staged windows of k_gradients (stage_windows), and the
+// per-window SSIM terms.
 #pragma once
 
 #include <type_traits>
@@ -51,6 +52,27 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
 }
 
 __device__ __forceinline__ bool wave_leader() { return (threadIdx.x & 63) == 0; }
+
+// INTEGER sums only, where any order gives the same bits: every 32-bit argument summed over its wavefront by DPP adds, in place. The
+// wavefront's LAST lane (wave_last) ends with the sum; the other lanes hold partial sums. All 64 lanes must be active. The six steps
+// are the scan of the compiler's own wavefront reductions on gfx9: row_shr 1, 2, 4, 8 inside the rows of 16 lanes (a lane without a
+// source adds 0), then row_bcast15 into rows 1 and 3 and row_bcast31 into rows 2 and 3: adds with a DPP operand, no LDS traffic,
+// where the __shfl_down tree of wave_sum is six dependent ds_bpermute_b32 a value.
+template <int CTRL, int ROWS, typename T>
+__device__ __forceinline__ void wave_isum_step(T& v) {
+    static_assert(sizeof(T) == 4 && std::is_integral<T>::value, "32-bit integers");
+    v = (T)((uint32_t)v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xF, false));
+}
+template <typename... T>
+__device__ __forceinline__ void wave_isum(T&... v) {
+    (wave_isum_step<0x111, 0xF>(v), ...);   // row_shr:1
+    (wave_isum_step<0x112, 0xF>(v), ...);   // row_shr:2
+    (wave_isum_step<0x114, 0xF>(v), ...);   // row_shr:4
+    (wave_isum_step<0x118, 0xF>(v), ...);   // row_shr:8
+    (wave_isum_step<0x142, 0xA>(v), ...);   // row_bcast15 into rows 1 and 3
+    (wave_isum_step<0x143, 0xC>(v), ...);   // row_bcast31 into rows 2 and 3
+}
+__device__ __forceinline__ bool wave_last() { return (threadIdx.x & 63) == 63; }
 
 // The wavefronts' values of N reduced quantities of one type, in LDS. The caller reduces ALL its values over the wavefront first, then
 // stores them in ONE `if (wave_leader())` block with put() (one predicated region, stores that merge), places ONE __syncthreads() behind
@@ -236,6 +258,24 @@ __device__ __forceinline__ uint32_t load_bytes4(const GlobalU8* p, int n) {
     }
     for (int k = 0; k < n; k++) word |= (uint32_t)p[k] << (8 * k);
     return word;
+}
+
+// A cols x rows window of both sides of a comparison as packed bytes in LDS, `pitch` words a row, `words` >= ceil(cols / 4) of them
+// written in each of `lds_rows` rows: pixel x of a row in byte x & 3 of word x >> 2, every byte beyond the window 0. pa / pb: the
+// window's first pixel. Side a is quantised on the way (load_quant4). Nothing outside the cols x rows pixels is read. The caller's
+// barrier stands behind it.
+__device__ __forceinline__ void stage_windows(const GlobalF32* __restrict__ pa, int a_pitch, const GlobalU8* __restrict__ pb, int b_pitch, int cols, int rows,
+                                              uint32_t* __restrict__ wa, uint32_t* __restrict__ wb, int pitch, int words, int lds_rows) {
+    for (int i = threadIdx.x; i < lds_rows * words; i += kStudyThreads) {
+        const int r = i / words, wd = i - r * words, x = wd << 2;
+        uint32_t a = 0u, b = 0u;
+        if (r < rows && x < cols) {
+            a = load_quant4(pa + (ptrdiff_t)r * a_pitch + x, cols - x);
+            b = load_bytes4(pb + (ptrdiff_t)r * b_pitch + x, cols - x);
+        }
+        wa[r * pitch + wd] = a;
+        wb[r * pitch + wd] = b;
+    }
 }
 
 // The four words of 16 window pixels shifted by sh bytes (v_alignbyte_b32): lo is the word before b1 .. b4, sh = (dx + R) & 3 with the

@@ -872,6 +872,8 @@ SCALE_ROW_KEYS = {"direct": "direct_scales", "registered": "registered_scales", 
                   "registered_reference": "registered_reference_scales"}
 TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "reference": "reference_tone",
              "registered_reference": "registered_reference_tone"}
+GRADIENT_ROW_KEYS = {"direct": "direct_gradient", "registered": "registered_gradient", "reference": "reference_gradient",
+                     "registered_reference": "registered_reference_gradient"}
 
 
 VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
@@ -949,7 +951,8 @@ RELATIONS = (
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
-                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None):
+                  detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
+                  gradients=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -964,6 +967,8 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     scales = int(scales)
     if scales and not 1 <= scales <= mp.SIM_MAX_SCALES:
         raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
+    if not isinstance(gradients, (bool, np.bool_)):
+        raise ValueError("gradients is a flag, got %r" % (gradients,))
     ensemble = int(ensemble)
     device_alterations = getattr(runner, "device_alterations", False)
     if ensemble and not 1 <= ensemble <= mp.SIM_ENSEMBLE_MAX:
@@ -1000,12 +1005,13 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
+           (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + \
            (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("warp",) if warps else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
-        displacement_tiles=displacement_tiles, scales=scales, ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
+        displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
         grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
@@ -1072,7 +1078,7 @@ def study_alterations(raw, rng, p, seed, shape, opt):
 class Scorer:
     """How run_study scores a row, on the host or on the device. produce(alteration) makes the altered output the one that is scored
     (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
-    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key; similarities, tone, scales and shifts take the row's comparisons, (reference key, region)
+    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key; similarities, tone, scales, gradients and shifts take the row's comparisons, (reference key, region)
     pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset; keep: the dicts carry their
     tile tables whatever displacement_tiles says, for a warp row's tracking)."""
 
@@ -1141,6 +1147,11 @@ class DeviceScorer(Scorer):
                 out[i] = {k: r[k] for k in SCALES_KEYS}
         return out
 
+    def gradients(self, comparisons):
+        """One musica_sim_gradients call over the row's comparisons."""
+        res = self.proc.sim_gradients([(0, slot) + region for slot, region in comparisons])
+        return [gradient_row(r["table"], r["gsim"]) for r in res]
+
     def shifts(self, comparisons, keep=False):
         """One musica_sim_displace call, none without a comparison."""
         res = self.proc.sim_displace([(0, slot) + region for slot, region in comparisons], self.opt.displacement, tables=True,
@@ -1189,6 +1200,9 @@ class HostScorer(Scorer):
     def scales(self, comparisons):
         res = [multiscale_similarities(*self.sides(slot, region), min(self.opt.scales, max_scales(region[4], region[5]))) for slot, region in comparisons]
         return [{k: r[k] for k in SCALES_KEYS} for r in res]
+
+    def gradients(self, comparisons):
+        return [gradient_row(*gradient_statistics(self.out, self.planes[slot], [region])[0]) for slot, region in comparisons]
 
     def shifts(self, comparisons, keep=False):
         tables = [(region, displacement_tile_tables(self.out, self.planes[slot], region, self.opt.displacement)) for slot, region in comparisons]
@@ -1248,7 +1262,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
-              gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None):
+              gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1293,6 +1307,15 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     ms_ssim, scales and the lists ssim, cs, lum, mse of length `scales`, a comparison using min(S, max_scales of its region). On the
     device the row's queries go through one musica_sim_multiscale call per distinct scale count; on the host the restatement scores
     the same crops. With scales=0 the rows and the launches are exactly as before.
+
+    gradients: True compares what MUSICA amplifies, the edges of the image itself (gradient_statistics). Every comparison dict of a
+    row gains a sibling: direct_gradient, registered_gradient and, with a vendor image, reference_gradient and
+    registered_reference_gradient; present exactly where the original is and None exactly where it is None. Each is gradient_row's
+    dict: the GRADIENT_KEYS gsim, gc, gain, turn, reversed, rmse and compression, gain_by_class (22 entries, None for an empty class)
+    and "table", the exact 22 x 6 integers of the comparison's interior by the edge strength of its reference side. On the device the
+    row's queries go through one musica_sim_gradients call behind the scales'; on the host the restatement scores the same crops.
+    The integers are equal on every path and summarised by one function; gsim agrees to rounding (the device sums in its own fixed
+    order). Anything but a bool is a ValueError; with gradients=False the rows and the launches are exactly as before.
 
     ensemble: K > 0 (at most SIM_ENSEMBLE_MAX; needs runner.device_alterations, else ValueError) repeats every noise alteration K times and
     splits the change of the output into bias and noise (ensemble_statistics). Every row gains "ensemble": None for rows without noise,
@@ -1428,17 +1451,18 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
-                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps)
+                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
     scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
-    metrics = [("", scorer.similarities)] + ([("_tone", scorer.tone)] if opt.tone else []) + ([("_scales", scorer.scales)] if opt.scales else [])
+    metrics = [("", scorer.similarities)] + ([("_tone", scorer.tone)] if opt.tone else []) + ([("_scales", scorer.scales)] if opt.scales else []) + \
+              ([("_gradient", scorer.gradients)] if opt.gradients else [])
     rows = []
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -1682,6 +1706,11 @@ def main(argv=None):
                     help="say at which spatial scale the output changed: SSIM, its contrast-structure factor and mse at S (1 .. 5) scales of "
                          "2 x 2 pooling and their MS-SSIM product, per comparison, written to scale_robustness.csv; on the GPU with "
                          "--device-metrics / --device-alterations (musica_sim_multiscale)")
+    ap.add_argument("--gradients", action="store_true",
+                    help="compare what MUSICA amplifies, the edges of the image itself: the exact Sobel gradient sums of every comparison by "
+                         "the edge strength of its reference side (gradient similarity and correlation, gain, turn, reversed share, rmse, "
+                         "gain per class and its compression slope), written to gradient_robustness.csv; on the GPU with --device-metrics / "
+                         "--device-alterations (musica_sim_gradients)")
     ap.add_argument("--ensemble", type=int, default=0, metavar="K",
                     help="with --device-alterations: repeat every noise alteration K (1 .. 1024) times and split the change of the output into "
                          "bias against the unaltered result and noise, per pixel, written to ensemble.csv (musica_sim_ensemble_*)")
@@ -1750,6 +1779,8 @@ def main(argv=None):
                  {"displacement": args.displacement} if args.displacement else {}
     if args.scales:
         shift_args["scales"] = args.scales
+    if args.gradients:
+        shift_args["gradients"] = True
     if args.ensemble:
         shift_args.update(ensemble=args.ensemble, ensemble_tiles=bool(args.ensemble_maps))
     if args.covariance:

@@ -1332,3 +1332,105 @@ def level_row(table, sq_diff_sum, pixels, keep=False):
         raise ValueError("the level table holds %d pixels and a squared difference of %d, the frame %d and %d"
                          % (int(t[:, 0].sum()), int(t[:, 3].sum()), int(pixels), int(sq_diff_sum)))
     return level_summary(t, curves=keep)
+
+
+# ---- gradient metrics: the edges of a comparison, by the edge strength of the reference (not in the reference's script) ---------------
+# MUSICA raises weak gradients more than strong ones. Every other metric compares gray levels, windows, scales, positions, lines or
+# planted patches; this one compares the integer Sobel gradients of both sides of a comparison over the interior of its region, their
+# exact sums kept apart by the bit length of the reference side's squared gradient. gradient_statistics is the contract of
+# musica_sim_gradients (include/musica.h), whose tables are bit-identical to it; gradient_summary is what the study reports of the
+# integers, one function for every path.
+
+def sobel_gradients(p):
+    """The integer Sobel gradients (gx, gy), int64, of a 2-D plane over its interior, (h - 2, w - 2):
+    gx = (p[y-1][x+1] + 2 p[y][x+1] + p[y+1][x+1]) - (the same at x - 1), gy = (p[y+1][x-1] + 2 p[y+1][x] + p[y+1][x+1]) - (the same
+    at y - 1); for a uint8 plane both lie in -1020 .. 1020."""
+    p = np.asarray(p).astype(np.int64)
+    col = p[:-2, :] + 2 * p[1:-1, :] + p[2:, :]     # t + 2 m + b of every column
+    row = p[:, :-2] + 2 * p[:, 1:-1] + p[:, 2:]
+    return col[:, 2:] - col[:, :-2], row[2:, :] - row[:-2, :]
+
+
+def gradient_statistics(out, ref, regions):
+    """What musica_sim_gradients returns for every region (ax, ay, bx, by, w, h), w, h >= 7, of two 2-D uint8 planes (side a: `out`,
+    side b: `ref`): a list of (table, gsim). Over the interior of the region, the (w - 2) x (h - 2) pixels whose 3 x 3 neighbourhood
+    lies inside it, with the gradients of sobel_gradients and per pixel
+        A = gxa^2 + gya^2, B = gxb^2 + gyb^2, dot = gxa gxb + gya gyb, cross = gxa gyb - gya gxb      (each |.| <= 1 300 500)
+    a pixel's class is the bit length of B, 0 .. 21 (processing.GRADIENT_CLASSES = 22): 0 where the reference has no gradient. The
+    table is (22, 6) uint64, per class n, sum A, sum B, sum dot, sum cross (both signed, stored in two's complement as the device
+    stores them: table.view(np.int64) reads them) and neg, the number of its pixels with dot < 0 (processing.GRADIENT_FIELDS); exact
+    integers, the n adding up to (w - 2)(h - 2). gsim is the mean over the interior of q = (2 dot + C) / (A + B + C), C =
+    processing.GRADIENT_C = 2720 (the 170 of GMSD, Xue et al. 2014, for Prewitt / 3, carried to Sobel's squared scale: x 16): one
+    correctly rounded f64 division of two exact integers per pixel, summed by math.fsum; identical sides give exactly 1.0."""
+    a, b = np.asarray(out), np.asarray(ref)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("gradient_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    res = []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 7 or h < 7 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is smaller than 7 x 7 or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        gxa, gya = sobel_gradients(a[ay:ay + h, ax:ax + w])
+        gxb, gyb = sobel_gradients(b[by:by + h, bx:bx + w])
+        A, B = gxa * gxa + gya * gya, gxb * gxb + gyb * gyb
+        dot, cross = gxa * gxb + gya * gyb, gxa * gyb - gya * gxb
+        cls = np.frexp(B.astype(np.float64))[1]      # the bit length of an integer below 2^53: frexp's exponent, 0 for 0
+        table = np.zeros((mp.GRADIENT_CLASSES, len(mp.GRADIENT_FIELDS)), dtype=np.int64)
+        for k in np.unique(cls):
+            m = cls == k
+            table[k] = [int(m.sum()), int(A[m].sum()), int(B[m].sum()), int(dot[m].sum()), int(cross[m].sum()), int((dot[m] < 0).sum())]
+        q = (2 * dot + mp.GRADIENT_C).astype(np.float64) / (A + B + mp.GRADIENT_C).astype(np.float64)
+        res.append((table.view(np.uint64), math.fsum(q.ravel().tolist()) / q.size))
+    return res
+
+
+GRADIENT_KEYS = ("gsim", "gc", "gain", "turn", "reversed", "rmse", "compression")   # gradient_summary's numbers, before gain_by_class
+
+
+def _signed_table(table):
+    t = np.asarray(table)
+    if t.shape != (mp.GRADIENT_CLASSES, len(mp.GRADIENT_FIELDS)) or t.dtype.kind not in "iu":
+        raise ValueError("a gradient table is (%d, %d) integers, got %r %s" % (mp.GRADIENT_CLASSES, len(mp.GRADIENT_FIELDS), t.shape, t.dtype))
+    t = t.astype(np.uint64).view(np.int64) if t.dtype.kind == "u" else t
+    return [[int(v) for v in row] for row in t]
+
+
+def gradient_summary(table, gsim):
+    """What the study reports of a comparison's gradients, from gradient_statistics' (or musica_sim_gradients') exact integers of ONE
+    region: one function for every study path. With the sums over all classes N, SA, SB, SD (dot), SC (cross), exact integers:
+        gsim           as given
+        gc             SD / sqrt(SA SB), the gradient correlation; 1.0 where both sides are flat (SA = SB = 0), 0.0 where one is
+        gain           sqrt(SA / SB); 1.0 where both sides are flat, None where only the reference is (SB = 0 < SA)
+        turn           atan2(SC, SD) in degrees, the mean rotation of the gradients from b to a; 0.0 where SC = SD = 0
+        reversed       the share of the pixels of classes >= 1 with dot < 0; 0.0 where there is none (a flat reference)
+        rmse           sqrt((SA + SB - 2 SD) / N), the rms length of the gradient difference (the numerator is sum |ga - gb|^2 >= 0)
+        gain_by_class  22 entries, sqrt(sum A / sum B) of the class; None where the class is empty or its sum B is 0 (class 0)
+        compression    the n-weighted least-squares slope of log2(gain_by_class) on the class index over the classes >= 1 that have a
+                       positive gain; 0.0 with fewer than two such classes. Negative where weak edges are amplified more than strong
+                       ones, MUSICA's signature.
+    Every float is one correctly rounded operation on exact integers, or math.fsum of such. ValueError for a table without a pixel."""
+    t = _signed_table(table)
+    n, sa, sb, sd, sc = (sum(row[i] for row in t) for i in range(5))
+    if n <= 0:
+        raise ValueError("the gradient table holds no pixel")
+    edged, neg = sum(row[0] for row in t[1:]), sum(row[5] for row in t[1:])
+    gains = [math.sqrt(row[1] / row[2]) if row[0] > 0 and row[2] > 0 else None for row in t]
+    fit = [(k, t[k][0], math.log2(g)) for k, g in enumerate(gains) if k >= 1 and g is not None and g > 0.0]
+    compression = 0.0
+    if len(fit) >= 2:
+        weight = sum(m for _, m, _ in fit)
+        mk, my = sum(m * k for k, m, _ in fit) / weight, math.fsum(m * y for _, m, y in fit) / weight
+        compression = math.fsum(m * (k - mk) * (y - my) for k, m, y in fit) / math.fsum(m * (k - mk) ** 2 for k, m, _ in fit)
+    return {"gsim": float(gsim),
+            "gc": sd / math.sqrt(sa * sb) if sa and sb else 1.0 if sa == sb else 0.0,
+            "gain": math.sqrt(sa / sb) if sb else 1.0 if sa == 0 else None,
+            "turn": math.degrees(math.atan2(sc, sd)),
+            "reversed": neg / edged if edged else 0.0,
+            "rmse": math.sqrt((sa + sb - 2 * sd) / n),
+            "compression": compression,
+            "gain_by_class": gains}
+
+
+def gradient_row(table, gsim):
+    """A row's *_gradient value: gradient_summary's dict and "table", the 22 x 6 exact integers (dot and cross signed) as lists."""
+    return dict(gradient_summary(table, gsim), table=_signed_table(table))

@@ -181,6 +181,8 @@ LUT_ENTRIES = 65536         # MUSICA_LUT_ENTRIES
 LEVEL_MAX_QUERIES = 4       # MUSICA_LEVEL_MAX_QUERIES
 LEVEL_MIN_SHIFT = 4         # MUSICA_LEVEL_MIN_SHIFT
 LEVEL_MAX_SHIFT = 15        # MUSICA_LEVEL_MAX_SHIFT
+GRADIENT_CLASSES = 22       # MUSICA_GRADIENT_CLASSES: the bit lengths of B <= 1 300 500
+GRADIENT_C = 2720           # MUSICA_GRADIENT_C
 
 
 def zoom_ratio(zoom):
@@ -469,6 +471,14 @@ class SimLevelResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("classes", C.c_uint64), ("ssd", C.c_uint64), ("pixels", C.c_uint64)]
 
 
+GRADIENT_FIELDS = ("n", "sum_A", "sum_B", "sum_dot", "sum_cross", "neg")   # the six words of a class of a gradient table
+
+
+class SimGradientResult(C.Structure):
+    """musica_sim_gradient_result: where a query's table lies in `tables`, the interior's pixel count and the mean of q."""
+    _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64), ("gsim", C.c_double)]
+
+
 class SimDisplaceResult(C.Structure):
     """musica_sim_displace_result: where one comparison's exact block matching puts the output."""
     _fields_ = [("pixels", C.c_uint64), ("ssd_zero", C.c_uint64), ("ssd_min", C.c_uint64), ("dx", C.c_int32), ("dy", C.c_int32),
@@ -680,6 +690,7 @@ ABI = {
     "musica_sim_profiles": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimProfileResult), _U32P, C.c_uint64]),
     "musica_alter_lut": (C.c_int, [_VP, C.c_uint32, _U16P]),
     "musica_sim_levels": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimLevelResult), C.POINTER(C.c_uint64), C.c_uint64]),
+    "musica_sim_gradients": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimGradientResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -1150,6 +1161,28 @@ class MusicaProcessing:
         for r in res:
             at, c = int(r.table_offset), int(r.classes)
             out.append({"table": tables[at:at + c * len(LEVEL_SUMS)].reshape(c, len(LEVEL_SUMS)).copy(), "classes": c, "ssd": int(r.ssd), "pixels": int(r.pixels)})
+        return out
+
+    def sim_gradients(self, queries):
+        """metrics.gradient_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 7, 1 .. SIM_MAX_QUERIES of them, all in one launch (ValueError before any call for a count or a side out
+        of range). Returns one dict per query: "table", a (GRADIENT_CLASSES, 6) uint64 array of the exact n, sum_A, sum_B, sum_dot,
+        sum_cross (both signed, two's complement) and neg (GRADIENT_FIELDS) per class of the reference side's edge strength, "gsim", the
+        mean of q over the interior, and the Python int "pixels" = (w - 2) (h - 2)."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        if not 1 <= len(qs) <= SIM_MAX_QUERIES:
+            raise ValueError("sim_gradients takes 1 .. %d queries, got %d" % (SIM_MAX_QUERIES, len(qs)))
+        for i, q in enumerate(qs):
+            if q.w < 7 or q.h < 7:
+                raise ValueError("sim_gradients: query %d: region %d x %d is smaller than 7 x 7" % (i, q.w, q.h))
+        per = GRADIENT_CLASSES * len(GRADIENT_FIELDS)
+        words = len(qs) * per
+        arr, res, tables = (SimQuery * len(qs))(*qs), (SimGradientResult * len(qs))(), np.zeros(words, dtype=np.uint64)
+        self._ok(self._lib.musica_sim_gradients(self._h, len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), words), "musica_sim_gradients")
+        out = []
+        for r in res:
+            at = int(r.table_offset)
+            out.append({"table": tables[at:at + per].reshape(GRADIENT_CLASSES, len(GRADIENT_FIELDS)).copy(), "gsim": float(r.gsim), "pixels": int(r.pixels)})
         return out
 
     def sim_get_reference(self, slot):

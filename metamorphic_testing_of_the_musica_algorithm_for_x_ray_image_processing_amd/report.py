@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -26,6 +26,9 @@ SHIFT_CSV_HEADER = ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in SH
 SCALE_CSV_GROUPS = (('direct_scales', 'altered vs unaltered'), ('registered_scales', 'registered vs unaltered'),
                     ('reference_scales', 'altered vs reference'), ('registered_reference_scales', 'registered vs reference'))
 SCALE_CSV_METRICS = ("ssim", "cs", "mse")   # per scale 0 .. 4, behind ms_ssim and scales
+
+GRADIENT_CSV_GROUPS = (('direct_gradient', 'altered vs unaltered'), ('registered_gradient', 'registered vs unaltered'),
+                       ('reference_gradient', 'altered vs reference'), ('registered_reference_gradient', 'registered vs reference'))
 
 ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
 ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
@@ -63,6 +66,20 @@ def _scale_csv_cells(t):
     if t is None:
         return [""] * (2 + len(SCALE_CSV_METRICS) * mp.SIM_MAX_SCALES)
     return [t["ms_ssim"], t["scales"]] + [t[m][s] if s < t["scales"] else "" for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)]
+
+
+def gradient_csv_header(with_reference):
+    """gradient_robustness.csv's columns: per group the GRADIENT_KEYS gsim, gc, gain, turn, reversed, rmse and compression, then gain_0
+    .. gain_21, the gain of every class of the reference side's edge strength; the two vendor groups only for studies that have a
+    vendor image."""
+    return ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in GRADIENT_CSV_GROUPS[:4 if with_reference else 2]
+                                         for m in GRADIENT_KEYS + tuple('gain_%d' % k for k in range(mp.GRADIENT_CLASSES))]
+
+
+def _gradient_csv_cells(t):
+    if t is None:
+        return [""] * (len(GRADIENT_KEYS) + mp.GRADIENT_CLASSES)
+    return ["" if v is None else v for v in [t[k] for k in GRADIENT_KEYS] + list(t["gain_by_class"])]
 
 
 def tone_csv_header(with_reference):
@@ -178,6 +195,9 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     Studies run with scales (rows[0] has "direct_scales") also get scale_robustness.csv (scale_csv_header): one line per row, the
     unaltered one included; cells without a comparison, and of scales beyond a comparison's count, are empty.
 
+    Studies run with gradients (rows[0] has "direct_gradient") also get gradient_robustness.csv (gradient_csv_header): one line per
+    row, the unaltered one included; cells without a comparison, of a gain that has no value and of an empty class are empty.
+
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
     and standard deviation over the realisations of the five similarity metrics.
@@ -213,6 +233,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
     tone_groups = TONE_CSV_GROUPS[:4 if any("reference_tone" in rows[0] for _, rows in toned) else 2]
     scale_groups = SCALE_CSV_GROUPS[:4 if any("reference_scales" in rows[0] for _, rows in scored) else 2]
+    graded = having("direct_gradient")
+    gradient_groups = GRADIENT_CSV_GROUPS[:4 if any("reference_gradient" in rows[0] for _, rows in graded) else 2]
     covs = [(raw_name, [r for r in rows if r.get("ensemble") and "covariance" in r["ensemble"]]) for raw_name, rows in ensembles]
     covs = [(raw_name, rows) for raw_name, rows in covs if rows]
     radius = covs[0][1][0]["ensemble"]["covariance"]["direct"]["radius"] if covs else 0
@@ -230,6 +252,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
          lambda r, ovd: [c for key, _ in SHIFT_CSV_GROUPS for c in _cells(r.get(key), SHIFT_KEYS)]),
         ("scale_robustness.csv", scale_csv_header(len(scale_groups) == 4), scored or None,
          lambda r, ovd: [c for key, _ in scale_groups for c in _scale_csv_cells(r.get(key))]),
+        ("gradient_robustness.csv", gradient_csv_header(len(gradient_groups) == 4), graded or None,
+         lambda r, ovd: [c for key, _ in gradient_groups for c in _gradient_csv_cells(r.get(key))]),
         ("ensemble.csv", ENSEMBLE_CSV_HEADER, ensembles or None, lambda r, ovd: _ensemble_cells(r["ensemble"])),
         ("noise_covariance.csv", covariance_csv_header(radius), covs or None, lambda r, ovd: _covariance_cells(r["ensemble"], radius)),
         ("warp_response.csv", WARP_CSV_HEADER, having("warp") or None,
