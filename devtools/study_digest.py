@@ -24,7 +24,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     slot 0 over the same four regions, the classes the source plane >> 4 (4096 classes) and >> 9 (128);
   * the gradients at N = 151 of other images' outputs against slot 0: the full frame (129 x 129 interior pixels: 3 x 3 tiles with a
     one-pixel ragged tail), a ragged region from mid-tile with different origins on the two sides, a 7-wide column and a 7 x 7 corner;
-    gsim is the one f64 of the call summed on the device.
+    gsim is the one f64 of the call summed on the device;
+  * the point-response pair at N = 151: five points of half-side 5 in groups 0, 1 and 3 (group 2 stays empty; a 2 x 2 cluster across a
+    tile corner and a window flush with the output plane's corner among them; a dead, a hot, a half, a faint and a brightened one)
+    inserted into image 0, and the sums and stacks of the same points, shifted into the output plane, of image 1's output against slot 0.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -142,5 +145,10 @@ for shift in (4, 9):
     note("musica_sim_levels_s%d" % shift, p.sim_levels([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (1, 0, 64, 0, 64, 0, 1, NW), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)], shift))
 if hasattr(p, "sim_gradients"):   # a --tree from before the gradient metrics has none: its other digests compare as they are
     note("musica_sim_gradients", p.sim_gradients([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 7, NW - 1), (1, 0, NW - 7, NW - 7, 0, 0, 7, 7)]))
+if hasattr(p, "sim_points"):      # likewise a --tree from before the point response
+    points = [(63, 63, 5, 2, 1024, 0), (113, 46, 5, 3, -64512, 1), (46, 113, 5, 1, 512, 3), (N - 16, N - 16, 5, 3, -1, 1), (80, 90, 5, 2, 64, 0)]
+    p.alter_points(points)
+    note("musica_alter_points", p.input_pixels()[0])
+    note("musica_sim_points", p.sim_points([(q[0] - mp.OUT_MARGIN, q[1] - mp.OUT_MARGIN) + q[2:] for q in points], 0, image_index=1))
 p.cleanup()
 print(json.dumps(digests))

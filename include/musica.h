@@ -1062,6 +1062,71 @@ typedef struct musica_sim_gradient_result {
 int musica_sim_gradients(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_gradient_result* results,
                          uint64_t* tables, uint64_t table_words);
 
+/* ---- point response: defect pixels and clusters, the response stacked where they lie (new, not in the reference) ----
+ * The impulse of the classical measurements: a single detector element or a small cluster is altered and the two-dimensional response
+ * around it is read back, stacked over many positions. A multi-scale amplifier answers with a narrow core, a wide skirt and a rebound
+ * ring of the opposite sign, differently for dead, faint and hot impulses and for different backgrounds. harness.insert_points,
+ * harness.point_statistics and harness.point_summary are the contract; everything the device computes is integer and bit-identical to
+ * them, from call to call as well (integer atomics and integer reductions: exact in any order).
+ * A point is (x, y, radius, size, contrast, group): an integer pixel centre; MUSICA_POINT_MIN_RADIUS <= radius R <= MUSICA_POINT_MAX_RADIUS,
+ * the half-side of its window; 1 <= size s <= MUSICA_POINT_MAX_SIZE; MUSICA_POINT_MIN_CONTRAST <= contrast <= MUSICA_POINT_MAX_CONTRAST
+ * and not 0, in 1 / 1024 of the pixel's value; group < groups <= MUSICA_POINT_MAX_GROUPS. (The struct is musica_defect: musica_point is
+ * the curves' (x, y).) Zones:
+ *   window   |dx|, |dy| <= R            (side S = 2R + 1, at most 65: at most 4225 offsets). Every point of a list has the same R.
+ *   cluster  along each axis the offsets -((s - 1) div 2) .. s div 2: s = 1 one pixel, s = 2 x .. x + 1, s = 3 x - 1 .. x + 1
+ *   core     |dx|, |dy| <= 1            (holds every cluster)
+ * A list for a plane of side n holds 1 .. MUSICA_POINT_MAX points whose windows lie inside [0, n)^2 and are pairwise disjoint
+ * (|xi - xj| > 2R or |yi - yj| > 2R), so nothing depends on the list's order. Both entry points refuse every other list before any
+ * device work.
+ *   insertion   inside a cluster out = min((v * (1024 - contrast) + 512) >> 10, 65535), every other pixel copied. ONE rounding, halves
+ *               up; contrast 1024 is a dead element (0), contrast -64512 multiplies by 64 and saturates everything above 1023 counts (a
+ *               hot element); the largest intermediate is 65535 * 65536 + 512 < 2^32. UNLIKE the other patch relations an insertion
+ *               with contrast > 512 CAN CREATE ZEROS (v = 1, contrast = 513 gives 0), which the noise and gradation histograms treat
+ *               specially: that is what a dead element does to them, and part of what the rows measure.
+ *   statistics  per point the sums of a and b over the 3 x 3 core and over the window, the window's sum of (a - b)^2 and its pixel
+ *               count S^2; per group the stack, a uint32 table [3][S^2]: for every offset o = (dy + R) S + (dx + R), over all the
+ *               group's points p, sum a(p + o), sum b(p + o) and sum (a - b)^2(p + o). Every window lies inside the plane, so every
+ *               offset is hit by every point of the group: the count is the group's point count. A group without points is all zero.
+ *               MUSICA_POINT_MAX * 255^2 = 266 342 400 < 2^32. `contrast` is not looked at, and `size` only checked.
+ * For every group the stack's three sums over all offsets equal the sums of win_sum_a, win_sum_b and win_ssd over its points. As for the
+ * details there is no musica_sim_..._reference sibling. */
+#define MUSICA_POINT_MIN_RADIUS 4
+#define MUSICA_POINT_MAX_RADIUS 32
+#define MUSICA_POINT_MAX_SIZE 3
+#define MUSICA_POINT_MIN_CONTRAST (-64512)
+#define MUSICA_POINT_MAX_CONTRAST 1024
+#define MUSICA_POINT_MAX_GROUPS 16
+#define MUSICA_POINT_MAX 4096
+typedef struct musica_defect {
+    int32_t x, y;                   /* the centre, in pixels of the plane the call names */
+    uint32_t radius;                /* MUSICA_POINT_MIN_RADIUS .. MUSICA_POINT_MAX_RADIUS, the same for every point of a list */
+    uint32_t size;                  /* 1 .. MUSICA_POINT_MAX_SIZE */
+    int32_t contrast;               /* MUSICA_POINT_MIN_CONTRAST .. MUSICA_POINT_MAX_CONTRAST, not 0, in 1 / 1024 of the pixel's value */
+    uint32_t group;                 /* 0 .. groups - 1 */
+} musica_defect;
+typedef struct musica_sim_point_result {
+    uint64_t core_sum_a, core_sum_b;   /* sums over the 3 x 3 core of side a (the output) and side b (the slot) */
+    uint64_t win_sum_a, win_sum_b;     /* sums over the window */
+    uint64_t win_ssd;                  /* sum over the window of (a - b)^2 */
+    uint64_t win_pixels;               /* (2 radius + 1)^2 */
+} musica_sim_point_result;
+/* insert_points(source plane, points) into image `image_index` of the input buffer: the points are in the N x N plane's coordinates.
+ * The kernel is enqueued on the ctx stream (the list is copied to the device first, which waits for what the stream holds), with
+ * musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step and no reference slot. One
+ * launch, 2 bytes read and 2 written per pixel (kernels_points.hip). Refused before any device work: a NULL context or list, no source,
+ * image_index >= batch, a count outside 1 .. MUSICA_POINT_MAX, a radius, size, contrast or group outside its limits, radii that differ,
+ * a window that leaves the plane, two windows that are not disjoint. */
+int musica_alter_points(musica_ctx* ctx, uint32_t image_index, uint32_t count, const musica_defect* points);
+/* point_statistics of side a, the 8-bit output of batch image `image_index` (quantised while read, exactly as musica_sim_compare reads
+ * it), against side b, reference slot `slot`: results[i] for points[i], in the coordinates of the (N - 20)^2 output plane, and the
+ * groups' stacks, flat [groups][3][S^2], into `tables`, which holds table_words >= groups * 3 * S^2 words. Synchronous. win_ssd equals
+ * musica_sim_compare's sq_diff_sum over the same S^2 region. Refused before any device work: a NULL context, list, results or tables, a
+ * count outside 1 .. MUSICA_POINT_MAX, groups outside 1 .. MUSICA_POINT_MAX_GROUPS, an image too small for the margin, a slot out of
+ * range or never written, image_index >= batch, a radius, size or group outside its limits, radii that differ, a window that leaves the plane,
+ * two windows that are not disjoint, table_words too small. */
+int musica_sim_points(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t count, const musica_defect* points, uint32_t groups,
+                      musica_sim_point_result* results, uint32_t* tables, uint64_t table_words);
+
 /* ---- device-resident output and stream ordering (new, not in the reference) ---- */
 
 /* What musica_export_out writes per image. */

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <stdlib.h>
+#include <vector>
 #include "musica_device.h"
 
 namespace musica {
@@ -438,6 +439,38 @@ struct GradQueryDev : SimRegion {
 // every query's words, zeroed by the caller: the tiles add into them with u64 atomics; part: a double per tile (all written); out[i]: the
 // sum of q over query i's interior
 void launch_sim_gradients(hipStream_t st, const GradQueryDev* d_qs, int count, int max_tiles, unsigned long long* tables, double* part, double* out);
+// kernels_points.hip: the point-response relation. A point (x, y, R, s, c, group) of a list that the caller has checked (limits, one R,
+// windows inside the plane and pairwise disjoint), packed: a plane side is at most 16384.
+constexpr int kPointMinRadius = 4;           // MUSICA_POINT_MIN_RADIUS
+constexpr int kPointMaxRadius = 32;          // MUSICA_POINT_MAX_RADIUS
+constexpr int kPointMaxSize = 3;             // MUSICA_POINT_MAX_SIZE
+constexpr int kPointMinContrast = -64512;    // MUSICA_POINT_MIN_CONTRAST
+constexpr int kPointMaxContrast = 1024;      // MUSICA_POINT_MAX_CONTRAST
+constexpr int kPointMaxGroups = 16;          // MUSICA_POINT_MAX_GROUPS
+constexpr int kPointMax = 4096;              // MUSICA_POINT_MAX
+constexpr int kPointWords = 6;               // u64 of a musica_sim_point_result
+constexpr int kPointChunk = 64;              // points of one workgroup of k_sim_points
+constexpr int kPointMaxChunks = kPointMax / kPointChunk + kPointMaxGroups;   // every group may end on a ragged chunk
+constexpr int kPointTableWords = kPointMaxGroups * 3 * (2 * kPointMaxRadius + 1) * (2 * kPointMaxRadius + 1);   // the largest tables
+constexpr int kPointPlanWords = kPointMax + 3 * kPointMaxChunks;                                                  // the largest plan
+struct PackedPoint {
+    uint32_t xy;     // x | y << 16
+    uint32_t rsgc;   // R | s << 6 | group << 8 | (c - kPointMinContrast) << 12
+};
+constexpr int kPointTileRows = 16384 / 64;   // the tile rows of the largest plane (musica_create): point_rows' entries behind a list
+// Orders a packed list by y and appends one {first, count} entry per tile row of a plane of side n: what launch_alter_points takes
+void point_rows(std::vector<PackedPoint>& packed, int n);
+// harness.insert_points(src, points) of a dense n x n plane into another (the planes must not overlap); any n >= 1, `count` points at
+// d_points (device) as point_rows left them, the tile rows' entries behind them
+void launch_alter_points(hipStream_t st, const uint16_t* src, uint16_t* out, int n, const PackedPoint* d_points, int count);
+// How launch_sim_points walks a list (host): the indices ordered by group, then the chunks; returns the chunks (kernels_points.hip)
+int point_plan(const PackedPoint* points, int count, std::vector<uint32_t>& plan);
+// harness.point_statistics: one workgroup per chunk of `plan` (point_plan's words on the host, copied to d_plan, kPointPlanWords u32 on
+// the device, on the stream: `plan` must live until the stream has been waited for). a_plane: the graded f32 plane at output pixel
+// (0, 0), b_plane: the slot's u8 plane, pitches in elements, the points in the cropped output plane's coordinates, all of half-side
+// `radius`; results: count x kPointWords u64, all written; tables: [groups][3][(2 radius + 1)^2] u32, zeroed here on the stream
+void launch_sim_points(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedPoint* d_points, int count, int radius,
+                       int groups, const uint32_t* plan, int chunks, uint32_t* d_plan, unsigned long long* results, uint32_t* tables);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -167,6 +167,10 @@ struct StudyState {
     double* d_grad_out = nullptr;                  // [MUSICA_SIM_MAX_QUERIES]
     double* d_grad_part = nullptr;                 // the tiles' partials of one call: grad_part_cap doubles, regrown when a call needs more
     size_t grad_part_cap = 0;
+    // musica_alter_points / musica_sim_points: the device copy of the call's point list, the points' results, the stacks and the launch plan
+    PackedPoint* d_points = nullptr;               // [MUSICA_POINT_MAX + kPointTileRows] (point_rows' entries behind an insertion's list), allocated by the first call of either
+    unsigned long long* d_point_out = nullptr;     // [MUSICA_POINT_MAX][kPointWords], allocated by the first musica_sim_points
+    uint32_t* d_point_tables = nullptr;            // [kPointTableWords] stacks (792 KiB), then [kPointPlanWords] of point_plan, allocated likewise
 };
 
 struct musica_ctx : DeviceBuffers {

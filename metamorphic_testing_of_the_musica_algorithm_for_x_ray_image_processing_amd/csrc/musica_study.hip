@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_gain.hip, kernels_levels.hip, and kernels_gradients.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, and kernels_gradients.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
@@ -140,7 +140,8 @@ static int scatter_plane(musica_ctx* c, const char* fn) {
 struct PatchNouns {
     const char *square, *squares, *item;
 };
-constexpr PatchNouns kDetailNouns{"box", "boxes", "detail"}, kEdgeNouns{"plate", "plates", "edge"}, kGratingNouns{"plate", "plates", "grating"};
+constexpr PatchNouns kDetailNouns{"box", "boxes", "detail"}, kEdgeNouns{"plate", "plates", "edge"}, kGratingNouns{"plate", "plates", "grating"},
+    kPointNouns{"window", "windows", "point"};
 
 // What every list call refuses about `count` items (each with a centre x, y) for a plane of side n, as processing's *_list do: the
 // count; per item what each(i, item, packed) refuses about it (1, or fail(...); it fills the packed item for the device) and a square
@@ -244,6 +245,33 @@ static int gratings_check(const char* fn, uint32_t count, const musica_grating* 
                             });
 }
 
+static_assert(kPointMinRadius == MUSICA_POINT_MIN_RADIUS && kPointMaxRadius == MUSICA_POINT_MAX_RADIUS && kPointMaxSize == MUSICA_POINT_MAX_SIZE &&
+                  kPointMinContrast == MUSICA_POINT_MIN_CONTRAST && kPointMaxContrast == MUSICA_POINT_MAX_CONTRAST && kPointMaxGroups == MUSICA_POINT_MAX_GROUPS &&
+                  kPointMax == MUSICA_POINT_MAX,
+              "kernels_points.hip's tile list, u32 pixel and u32 sums hold for the points of include/musica.h");
+static_assert(sizeof(musica_sim_point_result) == kPointWords * sizeof(uint64_t), "k_sim_points writes a musica_sim_point_result as its u64 words");
+
+// What both point calls refuse about a list for a plane of side n (processing.point_list): `groups` itself, then patch_list_check with
+// each radius (one for the whole list), size, contrast (when the call looks at it) and group, and the windows' reach R.
+static int points_check(const char* fn, uint32_t count, const musica_defect* ps, int n, bool with_contrast, uint32_t groups, std::vector<PackedPoint>& packed) {
+    if (groups < 1 || groups > MUSICA_POINT_MAX_GROUPS) return fail("%s: groups %u out of range [1, %d]", fn, groups, MUSICA_POINT_MAX_GROUPS);
+    return patch_list_check(fn, kPointNouns, count, MUSICA_POINT_MAX, ps, n, packed, [](const musica_defect& d) { return (int64_t)d.radius; },
+                            [&](uint32_t i, const musica_defect& d, PackedPoint& p) {
+                                if (d.radius < MUSICA_POINT_MIN_RADIUS || d.radius > MUSICA_POINT_MAX_RADIUS)
+                                    return fail("%s: point %u: radius %u out of range [%d, %d]", fn, i, d.radius, MUSICA_POINT_MIN_RADIUS, MUSICA_POINT_MAX_RADIUS);
+                                if (d.radius != ps[0].radius)
+                                    return fail("%s: point %u: radius %u differs from the list's radius %u", fn, i, d.radius, ps[0].radius);
+                                if (d.size < 1 || d.size > MUSICA_POINT_MAX_SIZE) return fail("%s: point %u: size %u out of range [1, %d]", fn, i, d.size, MUSICA_POINT_MAX_SIZE);
+                                if (with_contrast && (d.contrast == 0 || d.contrast < MUSICA_POINT_MIN_CONTRAST || d.contrast > MUSICA_POINT_MAX_CONTRAST))
+                                    return fail("%s: point %u: contrast %d is not in [%d, %d] without 0", fn, i, d.contrast, MUSICA_POINT_MIN_CONTRAST,
+                                                MUSICA_POINT_MAX_CONTRAST);
+                                if (d.group >= groups) return fail("%s: point %u: group %u is not below %u", fn, i, d.group, groups);
+                                const int c = with_contrast ? d.contrast : 0;
+                                p = {(uint32_t)d.x | ((uint32_t)d.y << 16), d.radius | (d.size << 6) | (d.group << 8) | ((uint32_t)(c - MUSICA_POINT_MIN_CONTRAST) << 12)};
+                                return 1;
+                            });
+}
+
 // Where a relation's list calls keep their device buffers in musica_ctx::study, and how large: the list's `most` items, and for the
 // measurement `out_words` u64 of results per item and `tables_cap` u32 of tables (tables == nullptr: the measurement has none).
 template <typename Packed>
@@ -261,6 +289,10 @@ constexpr PatchBuffers<PackedEdge> kEdgeBuffers{"edge", &StudyState::d_edges, MU
                                                 (size_t)MUSICA_EDGE_MAX * 4 * MUSICA_EDGE_BINS_MAX};
 constexpr PatchBuffers<PackedGrating> kGratingBuffers{"grating", &StudyState::d_gratings, MUSICA_GRATING_MAX, &StudyState::d_grating_out, kGratingWords,
                                                       &StudyState::d_grating_tables, (size_t)MUSICA_GRATING_MAX * 4 * MUSICA_GRATING_MAX_PERIOD};
+// the stacks' buffer also holds the launch plan of k_sim_points, behind the largest tables
+// ... and the list's the tile rows' ranges of k_alter_points, behind the points
+constexpr PatchBuffers<PackedPoint> kPointBuffers{"point", &StudyState::d_points, MUSICA_POINT_MAX + kPointTileRows, &StudyState::d_point_out, kPointWords, &StudyState::d_point_tables,
+                                                  (size_t)kPointTableWords + kPointPlanWords};
 
 // The call's list on the device, in the relation's buffer (allocated on first use): copied on the stream, behind the kernels that
 // still read the last call's, and `packed` is free again when this returns.
@@ -836,7 +868,7 @@ int musica_sim_multiscale(musica_ctx* c, uint32_t count, const musica_sim_query*
     ABI_CATCH("musica_sim_multiscale")
 }
 
-// ---- the list measurements (musica_sim_details / _edges / _gratings, include/musica.h; kernels_details.hip, kernels_edges.hip, kernels_gratings.hip)
+// ---- the list measurements (musica_sim_details / _edges / _gratings / _points, include/musica.h; kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip)
 int musica_sim_details(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count, const musica_detail* details, musica_sim_detail_result* out) {
     ABI_TRY
     return sim_patch_list(
@@ -878,6 +910,28 @@ int musica_sim_gratings(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t cou
         },
         out, tables, table_words);
     ABI_CATCH("musica_sim_gratings")
+}
+
+int musica_sim_points(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count, const musica_defect* points, uint32_t groups, musica_sim_point_result* out,
+                      uint32_t* tables, uint64_t table_words) {
+    ABI_TRY
+    std::vector<uint32_t> plan;   // lives until sim_patch_list has waited for the stream
+    int chunks = 0;
+    return sim_patch_list(
+        c, "musica_sim_points", !points || !out || !tables ? "points, results or tables" : nullptr, idx, slot, count, kPointBuffers,
+        [&](int n, std::vector<PackedPoint>& packed, uint64_t& words) {
+            if (!points_check("musica_sim_points", count, points, n, false, groups, packed)) return 0;
+            const uint64_t side = 2ull * points[0].radius + 1;
+            words = groups * 3ull * side * side;
+            chunks = point_plan(packed.data(), (int)count, plan);
+            return 1;
+        },
+        [&](const float* a, int a_pitch, const uint8_t* b, int b_pitch, const PackedPoint* list, unsigned long long* results, uint32_t* d_tables) {
+            launch_sim_points(c->stream, a, a_pitch, b, b_pitch, list, (int)count, (int)points[0].radius, (int)groups, plan.data(), chunks,
+                              d_tables + kPointTableWords, results, d_tables);
+        },
+        out, tables, table_words);
+    ABI_CATCH("musica_sim_points")
 }
 
 // ---- the profiles of a comparison (musica_sim_profiles, include/musica.h; kernels_gain.hip) ---------------------------------------------
@@ -1414,6 +1468,20 @@ int musica_alter_gratings(musica_ctx* c, uint32_t idx, uint32_t count, const mus
             launch_alter_gratings(c->stream, src, dst, c->N, c->study.d_gratings, c->study.d_grating_waves, (int)count);   // kernels_gratings.hip
         });
     ABI_CATCH("musica_alter_gratings")
+}
+
+int musica_alter_points(musica_ctx* c, uint32_t idx, uint32_t count, const musica_defect* points) {
+    ABI_TRY
+    std::vector<PackedPoint> packed;
+    return alter_into(
+        c, "musica_alter_points", !points ? "points" : nullptr, idx,
+        [&] { return points_check("musica_alter_points", count, points, c->N, true, MUSICA_POINT_MAX_GROUPS, packed); },
+        [&] {
+            point_rows(packed, c->N);   // ordered by y, each tile row's range behind the points
+            return upload_list(c, "musica_alter_points", kPointBuffers, packed);
+        },
+        [&](const uint16_t* src, uint16_t* dst) { launch_alter_points(c->stream, src, dst, c->N, c->study.d_points, (int)count); });   // kernels_points.hip
+    ABI_CATCH("musica_alter_points")
 }
 
 int musica_alter_gain(musica_ctx* c, uint32_t idx, const uint16_t* gx, const uint16_t* gy) {

@@ -1,6 +1,6 @@
 // study_device.h — what the study's kernels share on the device (kernels_similarity.hip, kernels_scales.hip, kernels_joint.hip,
 // kernels_displace.hip, kernels_covariance.hip, kernels_ensemble.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip,
-// kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip): the address-space typedefs, the reductions and their ONE order, the
+// kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip): the address-space typedefs, the reductions and their ONE order, the
 // 64 x 64 tile of a region, the pixel words of the kernels that stream a u16 plane and the insertion body of the patch relations
 // (insert_patches), the packed byte windows of k_displace and k_cov_add, the staged windows of k_gradients (stage_windows), and the
 // per-window SSIM terms.
@@ -145,7 +145,7 @@ inline void launch_by_width(Launch&& launch, int n, const P*... planes) {
     else launch(std::integral_constant<int, 1>());
 }
 
-// ---- the insertion body of the patch relations (k_alter_details, k_alter_edges, k_alter_gratings) ---------------------------------
+// ---- the insertion body of the patch relations (k_alter_details, k_alter_edges, k_alter_gratings, k_alter_points) ---------------------------------
 // ONE launch, 2 B read + 2 B written per pixel: a pixel inside a listed patch is changed by the relation's rule, every other pixel is
 // copied. The patches of a list (discs in their boxes, plates) lie inside the plane and are pairwise disjoint (the callers check), so a
 // pixel belongs to at most one. A workgroup of kStudyThreads threads owns a 64 x 64 tile of the plane (tile_geom).

@@ -218,6 +218,34 @@ def grating_contrast(gratings):
     return max(abs(w) for w in gratings[0][6])
 
 
+# not in the reference: the point-response rows (insert_points), rows point_<c> of a study run with `points`: defect pixels and 2 x 2
+# and 3 x 3 clusters on a grid (point_grid), each with a window of half-side POINT_RADIUS around it, one row per contrast c / 1024: a
+# dead element, a half-dead and a faint one, a doubled and a hot one. POINTS(n) gives the five grids of the image size.
+POINT_RADIUS = 16
+POINT_SIZES = (1, 2, 3)
+POINT_CONTRASTS = (1024, 512, 64, -1024, -64512)
+
+
+def point_grid(n, contrast, sizes=None, radius=POINT_RADIUS):
+    """The study's point phantom for a raw image of side n: _patch_grid's G x G points of one contrast and one window half-side, their
+    sizes the cluster sizes (default: a prefix of POINT_SIZES), a window's side 2 radius + 1, G at most 64 (63 x 63 = 3969 <= POINT_MAX
+    points at n = 3072): point (i, j) is (x, y, radius, sizes[(i + j) % k], contrast, (i + j) % k), so every size lies G / k times in
+    every row and every column of the grid and the group is the index of the size."""
+    order = POINT_SIZES if sizes is None else tuple(int(v) for v in sizes)
+    return mp.point_list(_patch_grid(n, sizes, POINT_SIZES, lambda s: 2 * int(radius) + 1, 64, "cluster sizes",
+                                     lambda x, y, s, t: (x, y, int(radius), s, contrast, order.index(s))), n)
+
+
+def output_points(points):
+    """A raw plane's points in the coordinates of the output plane (_output_patches)."""
+    return _output_patches(points)
+
+
+def POINTS(n):
+    """The five grids of the point_ rows of a side-n image: point_grid(n, c) for c in POINT_CONTRASTS."""
+    return tuple(point_grid(n, c) for c in POINT_CONTRASTS)
+
+
 # not in the reference: the detector-gain rows (apply_gain), rows named by the spec of a study run with `gains`: a separable gain map
 # out = v gx[x] gy[y] in units of 1 / 4096 (processing.GAIN_ONE), scored like every row and by the exact row and column profiles of the
 # result against the unaltered result (profile_statistics). A spec is (name, gx, gy); GAINS(n) gives the 25 of the image size: the
@@ -879,7 +907,7 @@ GRADIENT_ROW_KEYS = {"direct": "direct_gradient", "registered": "registered_grad
 VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
 
 
-# The five relations of the study that measure beyond a row's comparisons, each one row of this table. key: the row key of its measurement; option / tables: run_study's
+# The six relations of the study that measure beyond a row's comparisons, each one row of this table. key: the row key of its measurement; option / tables: run_study's
 # argument with its payloads (a grid, a gain spec) and the flag that keeps the raw tables; check(payloads, n): the payloads checked for a
 # raw plane of side n and, as output() maps them, for the output plane (ValueError), normalised; name(payload): the row's name;
 # insert(raw, payload): the host's altered raw image; alter(proc, payload): the same on the device; output(payload): the payload in the
@@ -946,13 +974,17 @@ RELATIONS = (
              lambda p, m, shape: p.sim_levels([(0, SLOT_UNALTERED) + _frame(shape)], m[0])[0]["table"], True,
              lambda m, table, sq_diff_sum, pixels, tables: level_row(table, sq_diff_sum, pixels, tables),
              lambda raw: (level_shift(raw), level_classes(raw, level_shift(raw)))),
+    # the fourth list relation, behind the others so that its rows come last; a row is named after its grid's first contrast
+    Relation("points", "points", "point_tables", _checked_grids(mp.point_list), lambda g: "point_%d" % g[0][4], insert_points,
+             lambda p, g: p.alter_points(g), _output_patches, point_statistics,
+             lambda p, m, shape: p.sim_points(m, SLOT_UNALTERED), True, point_row),
 )
 
 
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
-                  gradients=False):
+                  gradients=False, points=None, point_tables=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -998,7 +1030,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         if n <= 2 * PROCESSING_MARGIN:
             raise ValueError("a side of %d pixels leaves no output plane to warp" % n)
         mp.warp_field(field, n - 2 * PROCESSING_MARGIN, PROCESSING_MARGIN)
-    given = dict(details=details, edges=edges, gratings=gratings, gains=gains, luts=luts)
+    given = dict(details=details, edges=edges, gratings=gratings, gains=gains, luts=luts, points=points)
     for rel in RELATIONS:
         if given[rel.option] is not None:
             given[rel.option] = rel.check(given[rel.option], n)
@@ -1013,7 +1045,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
-        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), keys=keys, device_alterations=device_alterations,
+        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
 
 
@@ -1262,7 +1294,7 @@ def ensemble_of(eproc, noise, registered, full, opt):
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
-              gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False):
+              gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1447,11 +1479,25 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     dict from the tile tables of the row's DIRECT displacement comparison: how many 64 x 64 tiles there are, how many of their
     expected shifts the radius reaches, how many of those the block matching found, and the rms distance between measured and
     expected shift. Host and device tables are equal integers, so the dict is equal on every path. Nothing is asserted about the
-    values: whether MUSICA's local gains let the output follow a deformation tile by tile is the finding."""
+    values: whether MUSICA's local gains let the output follow a deformation tile by tile is the finding.
+
+    points: point-response grids, each a point list (x, y, R, s, c, group) for the raw plane (processing.point_list; POINTS(n) for a
+    dead, a half-dead, a faint, a doubled and a hot element on point_grid's phantom) that is also valid for the output plane when
+    shifted by the margin (output_points), else ValueError before any work. None adds nothing. Otherwise rows point_<c> (c: the grid's
+    first contrast) follow every other row: the raw image with the grid's clusters altered (insert_points; on the device:
+    alter_points; a dead element writes zeros into the input, which the noise and gradation histograms treat specially), "direct"
+    scored as for every row, "registered" None, and every row of the study gains "points": None except in the point_ rows, where it is
+    point_row's dict of the response stacked around the points against the unaltered result (point_statistics; on the device one
+    musica_sim_points call behind the row's musica_sim_compare, whose exact sq_diff_sum of the full frame gives outside_mse): per
+    group (cluster size) and over all points the peak, gain, volume, radial profile, fwhm, rebound, reach, anisotropy, spread and the
+    dependence on the local background (point_summary), and outside_mse. Host and device summarise exact integers with one function,
+    so "points" is equal to the last bit on every path. point_tables: the dict also carries "per_point" and "stacks". The rows draw
+    nothing from `rng` and take no ordinal. Nothing is asserted: the narrow core, the wide skirt and the rebound ring of a multi-scale
+    amplifier, and how they differ between a dead, a faint and a hot element, are the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
-                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients)
+                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients, points, point_tables)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -1692,6 +1738,12 @@ def main(argv=None):
                          "input (curve shift, slope, global fraction, within-class remainder, spread ratio, reversals), written to "
                          "level_response.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_levels, musica_alter_lut)")
     ap.add_argument("--lut-tables", action="store_true", help="with --luts: keep the two characteristic curves in the rows (\"levels\", \"curve_a\", \"curve_b\")")
+    ap.add_argument("--points", action="store_true",
+                    help="add the rows point_<c>: defect pixels and 2 x 2 and 3 x 3 clusters on a grid (point_grid), dead, half-dead, faint, "
+                         "doubled and hot (c / 1024 = 1, 0.5, 0.0625, -1, -63), the two-dimensional response stacked around them (peak, gain, "
+                         "fwhm, rebound, reach, anisotropy, spread; the change beyond the windows), written to point_response.csv; on the GPU "
+                         "with --device-metrics / --device-alterations (musica_sim_points, musica_alter_points)")
+    ap.add_argument("--point-tables", action="store_true", help="with --points: keep every point's sums and the stacks in the rows (\"per_point\", \"stacks\")")
     ap.add_argument("--tone", action="store_true",
                     help="add the joint-histogram tone metrics of every comparison (mutual information, correlation ratio, tone-matched mse and "
                          "ssim) and write them to tone_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_joint)")
@@ -1734,6 +1786,8 @@ def main(argv=None):
         ap.error("--gain-tables keeps what --gains measures: give --gains")
     if args.lut_tables and not args.luts:
         ap.error("--lut-tables keeps what --luts measures: give --luts")
+    if args.point_tables and not args.points:
+        ap.error("--point-tables keeps what --points measures: give --points")
     if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
         ap.error("--covariance takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
     if args.covariance and not args.ensemble:
@@ -1803,6 +1857,8 @@ def main(argv=None):
         shift_args.update(gains=GAINS(args.size), gain_tables=args.gain_tables)
     if args.luts:
         shift_args.update(luts=True if args.manifest else LUTS(raw), lut_tables=args.lut_tables)
+    if args.points:
+        shift_args.update(points=POINTS(args.size), point_tables=args.point_tables)
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)

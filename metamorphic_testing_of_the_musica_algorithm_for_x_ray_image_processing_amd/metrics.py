@@ -767,6 +767,170 @@ def detail_row(details, stats, sq_diff_sum, pixels, tables=False):
     return out
 
 
+# ---- point response: defect pixels and clusters, the response stacked where they lie (not in the reference's script) ------------------
+# The impulse of the classical measurements. A point is (x, y, R, s, c, group): an integer pixel centre, the half-side POINT_MIN_RADIUS
+# <= R <= POINT_MAX_RADIUS of its window |dx|, |dy| <= R (side S = 2R + 1; one R for the whole list), the cluster size 1 <= s <=
+# POINT_MAX_SIZE (along each axis the offsets -((s - 1) // 2) .. s // 2: one pixel, x .. x + 1, x - 1 .. x + 1, all inside the core
+# |dx|, |dy| <= 1), the contrast POINT_MIN_CONTRAST <= c <= POINT_MAX_CONTRAST, c != 0, in 1 / 1024 of the pixel's value, and a group
+# below POINT_MAX_GROUPS. The windows of a list lie inside the plane and are pairwise disjoint (processing.point_list), so nothing
+# depends on the list's order. Everything up to point_summary is integer: these functions are the contract of musica_alter_points and
+# musica_sim_points (include/musica.h), which are bit-identical to them.
+
+def point_cluster(s):
+    """(lo, hi): the first and last offset, along each axis, of a cluster of size s: (0, 0), (0, 1), (-1, 1) for s = 1, 2, 3."""
+    s = int(s)
+    return -((s - 1) // 2), s // 2
+
+
+def insert_points(image, points):
+    """The square 2-D uint16 plane with the clusters of `points` (processing.point_list for its side, else ValueError before any work)
+    altered: inside each cluster
+        out = min((v * (1024 - c) + 512) >> 10, 65535)
+    and every other pixel copied. ONE rounding, halves up; c = 1024 is a dead element (0), c = -64512 multiplies by 64 and saturates
+    everything above 1023 counts (a hot element); the largest intermediate is 65535 * 65536 + 512 < 2^32. UNLIKE insert_details an
+    insertion with c > 512 can create zeros (v = 1, c = 513 gives 0), which trigger the early exits of the noise and gradation
+    histograms: that is what a dead element does to them, and part of what the rows measure. The windows are disjoint, so a pixel
+    belongs to at most one cluster and the result does not depend on the list's order."""
+    image = np.asarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.dtype != np.uint16 or not image.size:
+        raise ValueError("insert_points needs a non-empty square 2-D uint16 plane, got %r %s" % (image.shape, image.dtype))
+    points = mp.point_list(points, image.shape[0])
+    out = image.copy()
+    for x, y, _, s, c, _ in points:
+        lo, hi = point_cluster(s)
+        v = out[y + lo:y + hi + 1, x + lo:x + hi + 1].astype(np.uint64)
+        out[y + lo:y + hi + 1, x + lo:x + hi + 1] = np.minimum((v * np.uint64(1024 - c) + np.uint64(512)) >> np.uint64(10), np.uint64(65535)).astype(np.uint16)
+    return out
+
+
+def point_statistics(a, b, points, groups=None):
+    """The exact sums of the points of `points` (in the planes' coordinates; c is not looked at) over two square uint8 planes of equal
+    shape, what musica_sim_points returns: {"points": per point a dict of the Python ints core_sum_a, core_sum_b (over the 3 x 3 core),
+    win_sum_a, win_sum_b, win_ssd = sum of (a - b)^2 (over the window) and win_pixels = S^2; "groups": per group 0 .. groups - 1
+    (processing.point_groups: by default 1 + the largest group) a dict of "count", the group's points, and the stack, the (S, S) int64
+    arrays sum_a, sum_b and ssd indexed [dy + R, dx + R]: over the group's points p the sums of a(p + o), b(p + o) and (a - b)^2(p + o).
+    A group without points is all zero."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or a.shape != b.shape or a.shape[0] != a.shape[1] or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("point_statistics needs two square 2-D uint8 planes of equal shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    points = mp.point_list(points, a.shape[0], with_contrast=False)
+    groups = mp.point_groups(points, groups)
+    r = points[0][2]
+    side = 2 * r + 1
+    stacks = [dict({"count": 0}, **{k: np.zeros((side, side), dtype=np.int64) for k in mp.POINT_STACKS}) for _ in range(groups)]
+    per_point = []
+    for x, y, _, _, _, g in points:
+        pa = a[y - r:y + r + 1, x - r:x + r + 1].astype(np.int64)
+        pb = b[y - r:y + r + 1, x - r:x + r + 1].astype(np.int64)
+        dd = (pa - pb) ** 2
+        per_point.append({"core_sum_a": int(pa[r - 1:r + 2, r - 1:r + 2].sum()), "core_sum_b": int(pb[r - 1:r + 2, r - 1:r + 2].sum()),
+                          "win_sum_a": int(pa.sum()), "win_sum_b": int(pb.sum()), "win_ssd": int(dd.sum()), "win_pixels": side * side})
+        stack = stacks[g]
+        stack["count"] += 1
+        stack["sum_a"] += pa
+        stack["sum_b"] += pb
+        stack["ssd"] += dd
+    return {"points": per_point, "groups": stacks}
+
+
+POINT_KEYS = ("count", "peak", "gain", "volume", "fwhm", "rebound", "rebound_radius", "reach", "anisotropy", "spread", "level_slope", "level_r")   # point_summary's scalars; "radial" beside them
+POINT_CSV_HEADER = ['raw file', 'alteration', 'group'] + [k.replace('_', ' ') for k in POINT_KEYS] + ['outside mse']   # point_response.csv
+
+
+def _point_response(count, sum_a, sum_b, ssd, cores, contrast):
+    """point_summary's numbers of one stack of `count` points: the (S, S) int64 arrays, the points' (core_sum_a, core_sum_b) and the
+    contrast the gain is taken against."""
+    out = dict.fromkeys(POINT_KEYS)
+    out["count"], out["radial"] = int(count), None
+    if not count:
+        return out
+    side = sum_a.shape[0]
+    r = side // 2
+    h = (sum_a - sum_b).astype(np.float64) / float(count)
+    d = np.arange(-r, r + 1, dtype=np.int64)
+    dy, dx = d[:, None] + 0 * d[None, :], 0 * d[:, None] + d[None, :]
+    d2 = dx * dx + dy * dy
+    inside = d2 <= r * r
+    rho = np.array([[math.isqrt(int(v)) for v in row] for row in d2], dtype=np.int64)
+    peak = float(h[r, r])
+    radial = [math.fsum(h[inside & (rho == k)].tolist()) / int((inside & (rho == k)).sum()) for k in range(r + 1)]
+    h2 = h * h
+    energy = [math.fsum(h2[inside & (rho == k)].tolist()) for k in range(r + 1)]
+    total = math.fsum(energy)
+    reach = next(k for k in range(r + 1) if math.fsum(energy[:k + 1]) >= 0.9 * total)
+    all2 = math.fsum(h2.ravel().tolist())
+    moment = math.fsum((h2 * d2).ravel().tolist())
+    out.update(peak=peak, gain=peak * 1024.0 / contrast if contrast else None, volume=math.fsum(h.ravel().tolist()), radial=radial, reach=reach,
+               anisotropy=(math.fsum((h2 * (dx * dx)).ravel().tolist()) - math.fsum((h2 * (dy * dy)).ravel().tolist())) / moment if moment else 0.0,
+               spread=math.sqrt(max(math.fsum((ssd.astype(np.float64) / float(count) - h2).ravel().tolist()), 0.0) / all2) if all2 else None)
+    if peak != 0.0:
+        rel = [v / peak for v in radial]
+        k = next((k for k in range(1, r + 1) if rel[k] < 0.5), None)
+        if k is not None:
+            out["fwhm"] = 2.0 * ((k - 1) + (rel[k - 1] - 0.5) / (rel[k - 1] - rel[k]))
+        k = min(range(r + 1), key=lambda k: rel[k])
+        out["rebound"], out["rebound_radius"] = (rel[k], k) if rel[k] < 0.0 else (0.0, None)
+    if len(cores) >= 2:
+        x = [cb / 9.0 for _, cb in cores]
+        y = [float(ca - cb) for ca, cb in cores]
+        mx, my = math.fsum(x) / len(x), math.fsum(y) / len(y)
+        sxx = math.fsum((u - mx) * (u - mx) for u in x)
+        syy = math.fsum((v - my) * (v - my) for v in y)
+        sxy = math.fsum((u - mx) * (v - my) for u, v in zip(x, y))
+        if sxx > 0.0:
+            out["level_slope"] = sxy / sxx
+            if syy > 0.0:
+                out["level_r"] = sxy / math.sqrt(sxx * syy)
+    return out
+
+
+def point_summary(stats, points):
+    """What the study reports of a point list, from point_statistics' (or musica_sim_points') exact integers: one function for every
+    study path, so the paths agree to the last bit. {"groups": [one dict per group], "all": the same over all the points (the groups'
+    stacks added)}. With h(o) = (sum_a - sum_b)(o) / count, the mean response at offset o = (dx, dy), in f64 (sums by math.fsum):
+        count           the points
+        peak            h(0, 0)
+        gain            peak * 1024 / c, signed: c is the contrast of the first point of the group (of the list, for "all")
+        volume          sum of h over the window
+        radial          the mean of h per class rho = floor(sqrt(dx^2 + dy^2)), rho = 0 .. R, over dx^2 + dy^2 <= R^2
+        fwhm            twice the radius at which radial / peak first falls below 1 / 2, interpolated linearly between the two classes;
+                        None if the peak is 0 or it never does
+        rebound         the extreme of radial of the sign opposite to the peak, divided by the peak (so negative; 0.0 where there is none,
+                        None if the peak is 0), and rebound_radius, the class where it lies (None where there is none)
+        reach           the smallest rho whose classes 0 .. rho hold 90 % of the sum of h^2 within d^2 <= R^2
+        anisotropy      (sum h^2 dx^2 - sum h^2 dy^2) / sum h^2 (dx^2 + dy^2) over the window; 0.0 where that is 0 / 0
+        spread          sqrt(sum_o (ssd(o) / count - h(o)^2) / sum_o h(o)^2): how much the response differs from position to position;
+                        None where h is 0 everywhere
+        level_slope, level_r   the points' core responses core_sum_a - core_sum_b regressed on their backgrounds core_sum_b / 9: the
+                        slope and Pearson's r; None with fewer than two points or without variance
+    A group without points has its count 0 and None everywhere else. None of these is asserted anywhere: they are findings."""
+    groups = stats["groups"]
+    out = []
+    for g, stack in enumerate(groups):
+        mine = [i for i, p in enumerate(points) if p[5] == g]
+        cores = [(stats["points"][i]["core_sum_a"], stats["points"][i]["core_sum_b"]) for i in mine]
+        out.append(_point_response(stack["count"], stack["sum_a"], stack["sum_b"], stack["ssd"], cores, points[mine[0]][4] if mine else 0))
+    cores = [(s["core_sum_a"], s["core_sum_b"]) for s in stats["points"]]
+    whole = _point_response(sum(s["count"] for s in groups), *[sum(np.asarray(s[k], dtype=np.int64) for s in groups) for k in mp.POINT_STACKS], cores, points[0][4])
+    return {"groups": out, "all": whole}
+
+
+def point_row(points, stats, sq_diff_sum, pixels, tables=False):
+    """A point_ row's "points" value from the row's points, their exact sums and stacks and the full frame's exact sum of squared
+    differences over `pixels` pixels: point_summary's {"groups", "all"} and "outside_mse": (sq_diff_sum - sum win_ssd) / (pixels - sum
+    win_pixels), how far beyond R the change reaches (0.0 when the windows are the whole frame); with tables=True also "per_point": the
+    (x, y, R, s, c, group) and the exact sums of every point, in the list's order, and "stacks": per group its count and the three
+    planes as nested lists of Python ints."""
+    out = point_summary(stats, points)
+    inside_ssd, inside = sum(s["win_ssd"] for s in stats["points"]), sum(s["win_pixels"] for s in stats["points"])
+    outside = int(pixels) - inside
+    out["outside_mse"] = (int(sq_diff_sum) - inside_ssd) / outside if outside else 0.0
+    if tables:
+        out["per_point"] = [dict(s, x=p[0], y=p[1], R=p[2], s=p[3], c=p[4], group=p[5]) for p, s in zip(points, stats["points"])]
+        out["stacks"] = [dict({"count": int(g["count"])}, **{k: np.asarray(g[k]).astype(np.int64).tolist() for k in mp.POINT_STACKS}) for g in stats["groups"]]
+    return out
+
+
 # ---- edge response: slanted edges, the edge-spread function binned where they lie (not in the reference's script) ---------------------
 # MTF, NPS and contrast-detail are the classic triad; the ensemble gives the NPS, the cd_ rows the contrast-detail curve, and this is the
 # third: how MUSICA renders an edge (ISO 12233 / IEC 62220 slanted edge). An edge is (x, y, h, p, q, o, c): an integer pixel centre, a

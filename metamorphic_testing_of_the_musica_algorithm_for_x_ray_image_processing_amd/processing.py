@@ -175,6 +175,13 @@ GRATING_MAX_U = 8           # MUSICA_GRATING_MAX_U
 GRATING_MAX_PERIOD = 64     # MUSICA_GRATING_MAX_PERIOD
 GRATING_MAX_CONTRAST = 512  # MUSICA_GRATING_MAX_CONTRAST
 GRATING_MAX = 256           # MUSICA_GRATING_MAX
+POINT_MIN_RADIUS = 4        # MUSICA_POINT_MIN_RADIUS
+POINT_MAX_RADIUS = 32       # MUSICA_POINT_MAX_RADIUS
+POINT_MAX_SIZE = 3          # MUSICA_POINT_MAX_SIZE
+POINT_MIN_CONTRAST = -64512  # MUSICA_POINT_MIN_CONTRAST
+POINT_MAX_CONTRAST = 1024   # MUSICA_POINT_MAX_CONTRAST
+POINT_MAX_GROUPS = 16       # MUSICA_POINT_MAX_GROUPS
+POINT_MAX = 4096            # MUSICA_POINT_MAX
 GAIN_ONE = 4096             # MUSICA_GAIN_ONE
 PROFILE_MAX_QUERIES = 16    # MUSICA_PROFILE_MAX_QUERIES
 LUT_ENTRIES = 65536         # MUSICA_LUT_ENTRIES
@@ -411,6 +418,62 @@ GRATING_SUMS = ("n", "sum_a", "sum_b", "sum_aa")   # the four rows of a grating'
 class SimGratingResult(C.Structure):
     """musica_sim_grating_result: the region's exact sum of squared differences and where the grating's table lies in `tables`."""
     _fields_ = [("roi_ssd", C.c_uint64), ("roi_pixels", C.c_uint64), ("table_offset", C.c_uint64), ("bins", C.c_uint64)]
+
+
+def point_list(points, n, with_contrast=True):
+    """The points (x, y, R, s, c, group) of a point-response list for a plane of side n as harness.insert_points,
+    harness.point_statistics and the library take it, a tuple of tuples of ints, else ValueError: 1 .. POINT_MAX points of integers,
+    POINT_MIN_RADIUS <= R <= POINT_MAX_RADIUS and the same R for every point, a cluster size 1 <= s <= POINT_MAX_SIZE,
+    POINT_MIN_CONTRAST <= c <= POINT_MAX_CONTRAST and c != 0 (with_contrast=False: c is not looked at, as the measurement does not), a
+    group in 0 .. POINT_MAX_GROUPS - 1, every window |px - x|, |py - y| <= R inside [0, n)^2 and the windows pairwise disjoint."""
+    first = []
+
+    def check(i, p):
+        x, y, r, s, c, g = p
+        if not POINT_MIN_RADIUS <= r <= POINT_MAX_RADIUS:
+            raise ValueError("point %d: radius %d is not in %d .. %d" % (i, r, POINT_MIN_RADIUS, POINT_MAX_RADIUS))
+        first.append(r)
+        if r != first[0]:
+            raise ValueError("point %d: radius %d differs from the list's radius %d" % (i, r, first[0]))
+        if not 1 <= s <= POINT_MAX_SIZE:
+            raise ValueError("point %d: size %d is not in 1 .. %d" % (i, s, POINT_MAX_SIZE))
+        if with_contrast and (c == 0 or not POINT_MIN_CONTRAST <= c <= POINT_MAX_CONTRAST):
+            raise ValueError("point %d: contrast %d is not in %d .. %d without 0" % (i, c, POINT_MIN_CONTRAST, POINT_MAX_CONTRAST))
+        if not 0 <= g < POINT_MAX_GROUPS:
+            raise ValueError("point %d: group %d is not in 0 .. %d" % (i, g, POINT_MAX_GROUPS - 1))
+        return r
+    return _patch_list(points, n, ("a", "point"), "sextuples of integers (x, y, R, s, c, group)", POINT_MAX, lambda p: _ints(p, 6), check, ("window", "windows"))
+
+
+def point_groups(points, groups=None):
+    """How many stacks the measurement of a checked point list keeps: `groups`, by default 1 + the largest group of the list; an integer
+    in 1 .. POINT_MAX_GROUPS above every point's group, else ValueError."""
+    most = max(p[5] for p in points)
+    if groups is None:
+        return most + 1
+    if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)) or not 1 <= groups <= POINT_MAX_GROUPS:
+        raise ValueError("groups %r is not an integer in 1 .. %d" % (groups, POINT_MAX_GROUPS))
+    if most >= groups:
+        raise ValueError("a point's group %d is not below groups %d" % (most, groups))
+    return int(groups)
+
+
+class Defect(C.Structure):
+    """musica_defect: a cluster of `size` x `size` pixels at the integer pixel centre (x, y) altered by `contrast` / 1024, measured over
+    the window |dx|, |dy| <= `radius` and stacked with the other points of its `group`. (Point is the curves' (x, y).)"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("radius", C.c_uint32), ("size", C.c_uint32), ("contrast", C.c_int32), ("group", C.c_uint32)]
+
+
+POINT_SUMS = ("core_sum_a", "core_sum_b", "win_sum_a", "win_sum_b", "win_ssd", "win_pixels")   # a musica_sim_point_result's words
+POINT_STACKS = ("sum_a", "sum_b", "ssd")                                                       # the three planes of a group's stack
+
+
+class SimPointResult(C.Structure):
+    """musica_sim_point_result: the exact sums of one point's core and window."""
+    _fields_ = [(k, C.c_uint64) for k in POINT_SUMS]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in POINT_SUMS}
 
 
 def _unpack_tables(results, tables, sums):
@@ -686,6 +749,8 @@ ABI = {
     "musica_edge_bins": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_gratings": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Grating), C.POINTER(C.c_int16), C.c_uint64]),
     "musica_sim_gratings": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Grating), C.POINTER(SimGratingResult), _U32P, C.c_uint64]),
+    "musica_alter_points": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Defect)]),
+    "musica_sim_points": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Defect), C.c_uint32, C.POINTER(SimPointResult), _U32P, C.c_uint64]),
     "musica_alter_gain": (C.c_int, [_VP, C.c_uint32, _U16P, _U16P]),
     "musica_sim_profiles": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimProfileResult), _U32P, C.c_uint64]),
     "musica_alter_lut": (C.c_int, [_VP, C.c_uint32, _U16P]),
@@ -1128,6 +1193,22 @@ class MusicaProcessing:
                  "musica_sim_gratings")
         return [dict({"h": g[2], "ux": g[3], "uy": g[4], "T": bins}, **d) for g, (bins, d) in zip(gs, _unpack_tables(res, tables, GRATING_SUMS))]
 
+    def sim_points(self, points, slot, groups=None, image_index=0):
+        """harness.point_statistics(output of `image_index`, reference slot `slot`, points, groups) on the device: the points
+        (x, y, R, s, c, group) in the (N - 20)^2 output plane's coordinates (point_list; c is not looked at), `groups` (default: 1 + the
+        largest group) in 1 .. POINT_MAX_GROUPS. Returns {"points": one dict of the Python ints POINT_SUMS per point, "groups": one dict
+        per group: "count" and the (S, S) int64 arrays sum_a, sum_b and ssd (POINT_STACKS), indexed [dy + R, dx + R]}."""
+        ps = point_list(points, self.imageSize - 2 * OUT_MARGIN, with_contrast=False)
+        groups = point_groups(ps, groups)
+        side = 2 * ps[0][2] + 1
+        words = groups * 3 * side * side
+        arr, res, tables = (Defect * len(ps))(*[Defect(*p) for p in ps]), (SimPointResult * len(ps))(), np.zeros(words, dtype=np.uint32)
+        self._ok(self._lib.musica_sim_points(self._h, int(image_index), int(slot), len(ps), arr, groups, res, tables.ctypes.data_as(_U32P), words),
+                 "musica_sim_points")
+        stacks = tables.reshape(groups, 3, side, side).astype(np.int64)
+        return {"points": [r.as_dict() for r in res],
+                "groups": [dict({"count": sum(1 for p in ps if p[5] == g)}, **{k: stacks[g, i] for i, k in enumerate(POINT_STACKS)}) for g in range(groups)]}
+
     def sim_profiles(self, queries):
         """harness.profile_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
         SimQuery) with w, h >= 1, at most PROFILE_MAX_QUERIES, all in one launch. Returns one dict per query: "cols", a (w, 4) uint32
@@ -1410,6 +1491,12 @@ class MusicaProcessing:
         waves = np.array([w for g in gs for w in g[6]], dtype=np.int16)
         self._ok(self._lib.musica_alter_gratings(self._h, int(image_index), len(gs), arr, waves.ctypes.data_as(C.POINTER(C.c_int16)), waves.size),
                  "musica_alter_gratings")
+
+    def alter_points(self, points, image_index=0):
+        """harness.insert_points(src, points): the source with the clusters (x, y, R, s, c, group) of a point list (point_list) altered."""
+        ps = point_list(points, self.imageSize)
+        arr = (Defect * len(ps))(*[Defect(*p) for p in ps])
+        self._ok(self._lib.musica_alter_points(self._h, int(image_index), len(ps), arr), "musica_alter_points")
 
     def alter_warp(self, field, image_index=0):
         """harness.warp(src, field): the exact backward warp by the displacement field on the 64-pixel control grid (warp_field)."""

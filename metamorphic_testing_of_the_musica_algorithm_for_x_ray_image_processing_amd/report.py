@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -171,6 +171,9 @@ RELATION_CSVS = (
     ("grating_response.csv", GRATING_CSV_HEADER, "gratings", lambda d: d["periods"].items(), _spread_cells("gratings", GRATING_ROW_KEYS, GRATING_ROW_STATS)),
     ("gain_response.csv", GAIN_CSV_HEADER, "profiles", lambda d: [(axis, d[axis]) for axis in PROFILE_AXES], lambda d, g: [g["lines"]] + [g[k] for k in PROFILE_KEYS]),
     ("level_response.csv", LEVEL_CSV_HEADER, "levels", lambda d: [(d[LEVEL_KEYS[0]], d)], lambda d, g: [g[k] for k in LEVEL_KEYS[1:]]),
+    # point_response.csv: one line per point_ row and group, in the groups' order, then "all"
+    ("point_response.csv", POINT_CSV_HEADER, "points", lambda d: list(enumerate(d["groups"])) + [("all", d["all"])],
+     lambda d, g: [g[k] for k in POINT_KEYS] + [d["outside_mse"]]),
 )
 
 
@@ -224,6 +227,10 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
 
     Studies run with luts (rows[0] has "levels") also get level_response.csv (LEVEL_CSV_HEADER): one line per lut row, level_summary's
     numbers of the full frame (an empty cell where one is None).
+
+    Studies run with points (rows[0] has "points") also get point_response.csv (POINT_CSV_HEADER): one line per point_ row and group
+    (the index of the cluster size), then one for all the row's points ("all"): point_summary's scalars (an empty cell where one is
+    None) and the row's outside mse.
 
     Studies run with warps (rows[0] has "warp") also get warp_response.csv (WARP_CSV_HEADER): one line per warp row, the field's reach
     and peak displacement in pixels, the four tracking numbers of metrics.warp_tracking (empty without a displacement radius) and the
