@@ -27,7 +27,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     gsim is the one f64 of the call summed on the device;
   * the point-response pair at N = 151: five points of half-side 5 in groups 0, 1 and 3 (group 2 stays empty; a 2 x 2 cluster across a
     tile corner and a window flush with the output plane's corner among them; a dead, a hot, a half, a faint and a brightened one)
-    inserted into image 0, and the sums and stacks of the same points, shifted into the output plane, of image 1's output against slot 0.
+    inserted into image 0, and the sums and stacks of the same points, shifted into the output plane, of image 1's output against slot 0;
+  * the reach pair at N = 151 (odd: the single-pixel form of the row launch): the tables of image 1's output against slot 0 over the
+    same four regions as the levels, and the class plane, for fifteen radii up to 128, the seeds being where the input of image 1's
+    step differs from the source plane.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -150,5 +153,9 @@ if hasattr(p, "sim_points"):      # likewise a --tree from before the point resp
     p.alter_points(points)
     note("musica_alter_points", p.input_pixels()[0])
     note("musica_sim_points", p.sim_points([(q[0] - mp.OUT_MARGIN, q[1] - mp.OUT_MARGIN) + q[2:] for q in points], 0, image_index=1))
+if hasattr(p, "sim_reach"):       # likewise a --tree from before the reach metric
+    radii = [0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128]
+    note("musica_sim_reach", [p.sim_reach([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (1, 0, 64, 0, 64, 0, 1, NW), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)], radii),
+                              p.sim_reach_classes(radii, image_index=1)])
 p.cleanup()
 print(json.dumps(digests))

@@ -1062,6 +1062,59 @@ typedef struct musica_sim_gradient_result {
 int musica_sim_gradients(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_gradient_result* results,
                          uint64_t* tables, uint64_t table_words);
 
+/* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
+ * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change
+ * outwards: the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global
+ * stages (min / max, the two histograms, the tone curve: the same small shift everywhere, however far). Every other measurement scores
+ * the place of the change, or the whole frame; this one keeps the exact sums of a comparison apart by the distance of the pixel from
+ * the nearest CHANGED input pixel. metrics.reach_classes and metrics.reach_statistics are the contract; everything the device computes
+ * is integer and bit-identical to them, from call to call as well.
+ * The planes: "source" is the alteration source plane (musica_alter_set_source), "altered" the input plane that image `image_index`'s
+ * current output was computed from (the plane the on-demand getters recompute from, also after a later alteration has overwritten
+ * the input buffer), so input and output are always a coherent pair. seed = source != altered, over the whole N x N plane: seeds in
+ * the MUSICA_OUT_MARGIN-pixel margin count, and distances are taken in the N x N plane.
+ * The distance is Chebyshev's (L-infinity: the footprints of separable filters are squares). With K = radii_count radii, radii[0] = 0,
+ * strictly ascending, each <= MUSICA_REACH_MAX_RADIUS, the class of input pixel (x, y) is the smallest k for which the box
+ * [x - radii[k], x + radii[k]] x [y - radii[k], y + radii[k]], clipped to the plane, holds a seed, and K where the box of radii[K - 1]
+ * holds none: class 0 is a changed pixel itself, class K "farther than the last radius, or nothing changed"; K + 1 classes.
+ * A query is musica_sim_compare's (side a the 8-bit output of batch image `image_index`, quantised while read exactly as
+ * musica_sim_compare reads it; side b reference slot `slot`; w, h >= 1). The class of a-side pixel (x, y) of the output plane is that
+ * of input pixel (x + MUSICA_OUT_MARGIN, y + MUSICA_OUT_MARGIN), whatever origin side b has. Query i gets a table
+ * [K + 1][MUSICA_REACH_WORDS] of uint64_t in the flat `tables`, from results[i].table_offset (in words: i * (K + 1) *
+ * MUSICA_REACH_WORDS) on. A class's six words are the exact
+ *   n, changed = the number of its pixels with a != b, sum_a, sum_b, sum_dd = sum of (a - b)^2, max_d = max |a - b| (0 for an empty class)
+ * over the region's pixels of that class. INVARIANTS: the n of a table add up to w * h; results[i].ssd, the sum of its sum_dd, equals
+ * musica_sim_compare's sq_diff_sum over the same region; changed <= n; max_d^2 * changed >= sum_dd >= changed. results[i].seeds is the
+ * number of changed pixels of the N x N input plane, the same for every query of a call. Every word of the tables is written and
+ * nothing behind them.
+ * Both entry points are synchronous, on the context's stream after whatever was enqueued there; they change no slot, no input image
+ * and no result of a step; scratch is grown on first use and freed with the context (the summed-area table of the seeds shares the
+ * scatter calls' N x N u32 plane: no call needs both at once). Three launches: the seeds' prefix counts along the rows, running sums
+ * down the columns, then the classes by bisection over the radii (four loads of the table a step) and the sums (kernels_reach.hip).
+ * All queries of a call name the same image_index. Refused before any device work, musica_last_error naming the entry point: what
+ * musica_sim_levels refuses about a context and its queries (sides from 1) with the largest count MUSICA_REACH_MAX_QUERIES; no source
+ * plane; a last step whose input was not a plane of the context's (musica_execute_device); NULL radii; radii_count outside 1 ..
+ * MUSICA_REACH_MAX_RADII; radii[0] != 0, radii that do not strictly ascend, a radius above MUSICA_REACH_MAX_RADIUS; queries that name
+ * different images; a NULL `tables`; table_words < count * (K + 1) * MUSICA_REACH_WORDS. After a refusal the context stays usable. */
+#define MUSICA_REACH_MAX_RADII 32
+#define MUSICA_REACH_MAX_RADIUS 16383
+#define MUSICA_REACH_MAX_QUERIES 16
+#define MUSICA_REACH_WORDS 6
+typedef struct musica_sim_reach_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t classes;               /* K + 1 */
+    uint64_t ssd;                   /* sum over the region of (a - b)^2 */
+    uint64_t pixels;                /* w * h */
+    uint64_t seeds;                 /* changed pixels of the N x N input plane; the same for every query of a call */
+} musica_sim_reach_result;
+int musica_sim_reach(musica_ctx* ctx, uint32_t radii_count, const uint32_t* radii, uint32_t count, const musica_sim_query* queries,
+                     musica_sim_reach_result* results, uint64_t* tables, uint64_t table_words);
+/* The class plane itself: the (N - 20)^2 classes of the output plane's pixels as host bytes, row-major (metrics.reach_classes cropped
+ * by MUSICA_OUT_MARGIN), for maps and for tests. The first two launches, then one that classifies and stores. Refused before any device
+ * work: a NULL context or dst, an image too small for the margin, image_index >= batch, then what musica_sim_reach refuses about the
+ * source, the last step's input and the radii. */
+int musica_sim_reach_classes(musica_ctx* ctx, uint32_t image_index, uint32_t radii_count, const uint32_t* radii, uint8_t* dst);
+
 /* ---- point response: defect pixels and clusters, the response stacked where they lie (new, not in the reference) ----
  * The impulse of the classical measurements: a single detector element or a small cluster is altered and the two-dimensional response
  * around it is read back, stacked over many positions. A multi-scale amplifier answers with a narrow core, a wide skirt and a rebound

@@ -45,23 +45,6 @@ constexpr int kScatterCols = 64;       // its columns: one wavefront
 static_assert(kScatterThreads << 6 >= 16384, "SH = 6 holds the largest side a context accepts");
 static_assert(2 * ((kScatterThreads << 6) + kScatterThreads) * 4 + kScatterThreads * 8 + 64 <= 160 * 1024, "the LDS of a row workgroup at SH = 6");
 
-// The exclusive prefix of v over the workgroup's threads (thread order); wave_tot: one word a wavefront, free again on return.
-template <typename U>
-__device__ __forceinline__ U scatter_block_scan(U v, U* wave_tot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    U inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const U o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) wave_tot[wave] = inc;
-    __syncthreads();
-    U before = 0;
-    for (int w = 0; w < wave; w++) before += wave_tot[w];
-    __syncthreads();
-    return before + inc - v;
-}
-
 template <typename T, int SH>
 __global__ __launch_bounds__(kScatterThreads) void k_scatter_rows(const T* __restrict__ src, uint32_t* __restrict__ plane, int n, int R) {
     constexpr int kSeg = 1 << SH, kWords = (kScatterThreads << SH) + kScatterThreads;
@@ -80,7 +63,7 @@ __global__ __launch_bounds__(kScatterThreads) void k_scatter_rows(const T* __res
     uint32_t run = 0;
     for (int k = 0; k < kSeg; k++)
         if (s0 + k < n) { run += p1[at(s0 + k)]; p1[at(s0 + k)] = run; }
-    const uint32_t off1 = scatter_block_scan(run, tot32);
+    const uint32_t off1 = block_scan_exclusive(run, tot32);
     for (int k = 0; k < kSeg; k++)
         if (s0 + k < n) p1[at(s0 + k)] += off1;
     __syncthreads();
@@ -97,7 +80,7 @@ __global__ __launch_bounds__(kScatterThreads) void k_scatter_rows(const T* __res
     run = 0;
     for (int k = 0; k < kSeg; k++)
         if (s0 + k < n) { run += p2[at(s0 + k)]; p2[at(s0 + k)] = run; }
-    base[tid] = scatter_block_scan((unsigned long long)run, tot64);
+    base[tid] = block_scan_exclusive((unsigned long long)run, tot64);
     __syncthreads();
 
     for (int i = tid; i < n; i += kScatterThreads) {

@@ -439,6 +439,29 @@ struct GradQueryDev : SimRegion {
 // every query's words, zeroed by the caller: the tiles add into them with u64 atomics; part: a double per tile (all written); out[i]: the
 // sum of q over query i's interior
 void launch_sim_gradients(hipStream_t st, const GradQueryDev* d_qs, int count, int max_tiles, unsigned long long* tables, double* part, double* out);
+// kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
+// Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
+constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII
+constexpr int kReachMaxRadius = 16383;    // MUSICA_REACH_MAX_RADIUS
+constexpr int kReachMaxQueries = 16;      // MUSICA_REACH_MAX_QUERIES
+constexpr int kReachWords = 6;            // MUSICA_REACH_WORDS: n, changed, sum a, sum b, sum (a - b)^2, max |a - b|
+// The summed-area table of source != altered (two dense n x n u16 planes, any alignment of 2 bytes, any n in 1 .. 16384) into `sat`,
+// n x n u32: sat[y * n + x] = the changed pixels of rows 0 .. y, columns 0 .. x; sat[n * n - 1] is their number. Two launches: the
+// rows' inclusive prefix counts, then the running sums down the columns, in place.
+void launch_reach_table(hipStream_t st, const uint16_t* source, const uint16_t* altered, uint32_t* sat, int n);
+// One comparison of musica_sim_reach. sx, sy: where a-side pixel (0, 0) lies in the n x n input plane (the margin added by the caller);
+// tiles_x / tiles_y: ceil(w / 64), ceil(h / 64); table: where its [radii + 1][kReachWords] u64 start in the launch's flat tables, in words.
+struct ReachQueryDev : SimRegion {
+    int sx, sy;
+    int tiles_x, tiles_y;
+    unsigned long long table;
+};
+// metrics.reach_statistics over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y) with the classes of the K radii at
+// d_radii (device, ascending from 0). tables: every query's words, zeroed by the caller: the tiles add into them with u64 atomics
+void launch_sim_reach(hipStream_t st, const ReachQueryDev* d_qs, int count, int max_tiles, const uint32_t* sat, int n, const uint32_t* d_radii, int K,
+                      unsigned long long* tables);
+// metrics.reach_classes cropped by `margin`: the (n - 2 margin)^2 classes as bytes into dst (device), nothing else written
+void launch_reach_classes(hipStream_t st, const uint32_t* sat, int n, int margin, const uint32_t* d_radii, int K, uint8_t* dst);
 // kernels_points.hip: the point-response relation. A point (x, y, R, s, c, group) of a list that the caller has checked (limits, one R,
 // windows inside the plane and pairwise disjoint), packed: a plane side is at most 16384.
 constexpr int kPointMinRadius = 4;           // MUSICA_POINT_MIN_RADIUS

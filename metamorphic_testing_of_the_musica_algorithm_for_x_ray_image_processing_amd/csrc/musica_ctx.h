@@ -167,6 +167,12 @@ struct StudyState {
     double* d_grad_out = nullptr;                  // [MUSICA_SIM_MAX_QUERIES]
     double* d_grad_part = nullptr;                 // the tiles' partials of one call: grad_part_cap doubles, regrown when a call needs more
     size_t grad_part_cap = 0;
+    // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
+    // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
+    uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either
+    ReachQueryDev* d_reach_q = nullptr;            // [MUSICA_REACH_MAX_QUERIES]
+    unsigned long long* d_reach_tables = nullptr;  // [MUSICA_REACH_MAX_QUERIES][MUSICA_REACH_MAX_RADII + 1][kReachWords]
+    uint8_t* d_reach_classes = nullptr;            // [(N - 20)^2], allocated by the first musica_sim_reach_classes
     // musica_alter_points / musica_sim_points: the device copy of the call's point list, the points' results, the stacks and the launch plan
     PackedPoint* d_points = nullptr;               // [MUSICA_POINT_MAX + kPointTileRows] (point_rows' entries behind an insertion's list), allocated by the first call of either
     unsigned long long* d_point_out = nullptr;     // [MUSICA_POINT_MAX][kPointWords], allocated by the first musica_sim_points

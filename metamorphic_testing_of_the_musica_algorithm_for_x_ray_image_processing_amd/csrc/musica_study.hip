@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, and kernels_gradients.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip and kernels_reach.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
@@ -1067,6 +1067,108 @@ int musica_sim_gradients(musica_ctx* c, uint32_t count, const musica_sim_query* 
     }
     return 1;
     ABI_CATCH("musica_sim_gradients")
+}
+
+// ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------
+static_assert(kReachMaxRadii == MUSICA_REACH_MAX_RADII && kReachMaxRadius == MUSICA_REACH_MAX_RADIUS && kReachMaxQueries == MUSICA_REACH_MAX_QUERIES &&
+                  kReachWords == MUSICA_REACH_WORDS,
+              "kernels_reach.hip's limits are include/musica.h's");
+
+// What both reach calls refuse behind their own arguments, in the same words: no source plane, a last step whose input is not a plane
+// of the context's (the pair of input and output would not be coherent), and a list of radii that is not 0 < r1 < .. <= the maximum.
+static int reach_check(const musica_ctx* c, const char* fn, uint32_t radii_count, const uint32_t* radii) {
+    if (!c->study.d_alter_src) return fail("%s: no source plane (musica_alter_set_source)", fn);
+    if (c->cur_input != c->d_input && !(c->d_input_kept && c->cur_input == c->d_input_kept) && !(c->d_input2 && c->cur_input == c->d_input2))
+        return fail("%s: the last step's input is not a plane of the context's (musica_execute_device)", fn);
+    if (!radii) return fail("%s: radii is NULL", fn);
+    if (radii_count < 1 || radii_count > MUSICA_REACH_MAX_RADII) return fail("%s: radii_count %u out of range [1, %d]", fn, radii_count, MUSICA_REACH_MAX_RADII);
+    if (radii[0] != 0) return fail("%s: radii[0] is %u, not 0", fn, radii[0]);
+    for (uint32_t k = 0; k < radii_count; k++) {
+        if (k && radii[k] <= radii[k - 1]) return fail("%s: radii[%u] = %u does not ascend from radii[%u] = %u", fn, k, radii[k], k - 1, radii[k - 1]);
+        if (radii[k] > MUSICA_REACH_MAX_RADIUS) return fail("%s: radii[%u] = %u is above %d", fn, k, radii[k], MUSICA_REACH_MAX_RADIUS);
+    }
+    return 1;
+}
+
+// The radii on the device and the summed-area table of source != the input of image idx's current output, enqueued on the stream.
+static int reach_table(musica_ctx* c, const char* fn, uint32_t idx, uint32_t radii_count, const uint32_t* radii) {
+    StudyState& st = c->study;
+    if (!ensure(c, &st.d_reach_radii, MUSICA_REACH_MAX_RADII)) return fail("%s: device allocation failed", fn);
+    if (!scatter_plane(c, fn)) return 0;
+    HIP_OK(hipMemcpyAsync(st.d_reach_radii, radii, radii_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    launch_reach_table(c->stream, st.d_alter_src, c->cur_input + idx * (size_t)c->N * c->N, st.d_scatter, c->N);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+int musica_sim_reach(musica_ctx* c, uint32_t radii_count, const uint32_t* radii, uint32_t count, const musica_sim_query* qs, musica_sim_reach_result* out,
+                     uint64_t* tables, uint64_t table_words) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_reach", count, qs, out, 1, MUSICA_REACH_MAX_QUERIES)) return 0;
+    if (!reach_check(c, "musica_sim_reach", radii_count, radii)) return 0;
+    for (uint32_t i = 1; i < count; i++)
+        if (qs[i].image_index != qs[0].image_index)
+            return fail("musica_sim_reach: query %u names image %u, query 0 image %u: one call, one input plane", i, qs[i].image_index, qs[0].image_index);
+    if (!tables) return fail("musica_sim_reach: tables is NULL");
+    const size_t classes = (size_t)radii_count + 1, per_query = classes * kReachWords, words = count * per_query;
+    if (table_words < words) return fail("musica_sim_reach: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_reach_q, MUSICA_REACH_MAX_QUERIES) &&
+          ensure(c, &st.d_reach_tables, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords)))
+        return fail("musica_sim_reach: device allocation failed");
+    std::vector<ReachQueryDev> hq(count);
+    int max_tiles = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        sim_region(c, qs[i], hq[i]);
+        hq[i].sx = (int)qs[i].ax + MUSICA_OUT_MARGIN;   // the class is taken at side a's coordinates
+        hq[i].sy = (int)qs[i].ay + MUSICA_OUT_MARGIN;
+        hq[i].tiles_x = tiles_along(qs[i].w);
+        hq[i].tiles_y = tiles_along(qs[i].h);
+        hq[i].table = i * per_query;
+        max_tiles = std::max(max_tiles, hq[i].tiles_x * hq[i].tiles_y);
+    }
+    if (!reach_table(c, "musica_sim_reach", qs[0].image_index, radii_count, radii)) return 0;
+    HIP_OK(hipMemcpyAsync(st.d_reach_q, hq.data(), count * sizeof(ReachQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_reach_tables, 0, words * sizeof(uint64_t), c->stream));   // the tiles add into them
+    launch_sim_reach(c->stream, st.d_reach_q, (int)count, max_tiles, st.d_scatter, c->N, st.d_reach_radii, (int)radii_count, st.d_reach_tables);
+    HIP_OK(hipGetLastError());
+    uint32_t seeds = 0;
+    HIP_OK(hipMemcpyAsync(tables, st.d_reach_tables, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(&seeds, st.d_scatter + (size_t)c->N * c->N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));   // the table's last entry
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq, radii, the tables and the seeds are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        const uint64_t* t = tables + hq[i].table;
+        uint64_t ssd = 0;
+        for (size_t k = 0; k < classes; k++) ssd += t[k * kReachWords + 4];
+        out[i].table_offset = hq[i].table;
+        out[i].classes = classes;
+        out[i].ssd = ssd;
+        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
+        out[i].seeds = seeds;
+    }
+    return 1;
+    ABI_CATCH("musica_sim_reach")
+}
+
+int musica_sim_reach_classes(musica_ctx* c, uint32_t idx, uint32_t radii_count, const uint32_t* radii, uint8_t* dst) {
+    ABI_TRY
+    if (!c) return fail("musica_sim_reach_classes: ctx is NULL");
+    if (!dst) return fail("musica_sim_reach_classes: dst is NULL");
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("musica_sim_reach_classes: image too small for the %d-pixel margin", MUSICA_OUT_MARGIN);
+    if (!check_img(c, "musica_sim_reach_classes", idx)) return 0;
+    if (!reach_check(c, "musica_sim_reach_classes", radii_count, radii)) return 0;
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    const size_t px = sim_side(c) * sim_side(c);
+    if (!ensure(c, &st.d_reach_classes, px)) return fail("musica_sim_reach_classes: device allocation failed");
+    if (!reach_table(c, "musica_sim_reach_classes", idx, radii_count, radii)) return 0;
+    launch_reach_classes(c->stream, st.d_scatter, c->N, MUSICA_OUT_MARGIN, st.d_reach_radii, (int)radii_count, st.d_reach_classes);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(dst, st.d_reach_classes, px, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // radii and dst are the caller's again
+    return 1;
+    ABI_CATCH("musica_sim_reach_classes")
 }
 
 // ---- ensemble statistics (musica_sim_ensemble_*, include/musica.h; kernels_ensemble.hip) ------------------------------------------------

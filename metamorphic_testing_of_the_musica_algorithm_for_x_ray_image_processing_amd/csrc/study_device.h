@@ -1,6 +1,7 @@
 // study_device.h — what the study's kernels share on the device (kernels_similarity.hip, kernels_scales.hip, kernels_joint.hip,
 // kernels_displace.hip, kernels_covariance.hip, kernels_ensemble.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip,
-// kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip): the address-space typedefs, the reductions and their ONE order, the
+// kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_scatter.hip, kernels_reach.hip): the address-space typedefs, the
+// reductions and their ONE order, the workgroup's prefix sum, the
 // 64 x 64 tile of a region, the pixel words of the kernels that stream a u16 plane and the insertion body of the patch relations
 // (insert_patches), the packed byte windows of k_displace and k_cov_add, the staged windows of k_gradients (stage_windows), and the
 // per-window SSIM terms.
@@ -22,6 +23,7 @@ constexpr int kStudyWaves = kStudyThreads / 64;
 typedef __attribute__((address_space(1))) float GlobalF32;
 typedef __attribute__((address_space(1))) uint8_t GlobalU8;
 typedef __attribute__((address_space(1))) unsigned long long GlobalU64;
+typedef __attribute__((address_space(1))) uint32_t GlobalU32;
 
 __device__ __forceinline__ uint32_t dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
 
@@ -73,6 +75,44 @@ __device__ __forceinline__ void wave_isum(T&... v) {
     (wave_isum_step<0x143, 0xC>(v), ...);   // row_bcast31 into rows 2 and 3
 }
 __device__ __forceinline__ bool wave_last() { return (threadIdx.x & 63) == 63; }
+// The same six steps with an UNSIGNED maximum in place of the add (a lane without a source takes max(v, 0) = v): the wavefront's last
+// lane ends with the largest argument. All 64 lanes must be active.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ void wave_umax_step(uint32_t& v) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xF, false);
+    v = o > v ? o : v;
+}
+__device__ __forceinline__ void wave_umax(uint32_t& v) {
+    wave_umax_step<0x111, 0xF>(v);
+    wave_umax_step<0x112, 0xF>(v);
+    wave_umax_step<0x114, 0xF>(v);
+    wave_umax_step<0x118, 0xF>(v);
+    wave_umax_step<0x142, 0xA>(v);
+    wave_umax_step<0x143, 0xC>(v);
+}
+
+// The exclusive prefix of v over the workgroup's threads (thread order; k_scatter_rows, k_reach_rows); wave_tot: one word a wavefront,
+// free again on return. total: where given, every thread also gets the sum over the whole workgroup.
+template <typename U>
+__device__ __forceinline__ U block_scan_exclusive(U v, U* wave_tot, U* total = nullptr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    U inc = v;
+    for (int off = 1; off < 64; off <<= 1) {
+        const U o = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += o;
+    }
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    U before = 0;
+    for (int w = 0; w < wave; w++) before += wave_tot[w];
+    if (total) {
+        U all = before;
+        for (int w = wave; w < (int)(blockDim.x >> 6); w++) all += wave_tot[w];
+        *total = all;
+    }
+    __syncthreads();
+    return before + inc - v;
+}
 
 // The wavefronts' values of N reduced quantities of one type, in LDS. The caller reduces ALL its values over the wavefront first, then
 // stores them in ONE `if (wave_leader())` block with put() (one predicated region, stores that merge), places ONE __syncthreads() behind

@@ -410,6 +410,18 @@ def level_classes(raw, shift):
     return raw[PROCESSING_MARGIN:-PROCESSING_MARGIN, PROCESSING_MARGIN:-PROCESSING_MARGIN] >> np.uint16(shift)
 
 
+def REACH_RADII(n):
+    """The default radii of a study's reach classes for a raw plane of side n: 0, then the half-octaves 1, 2, 3, 4, 6, 8, 12, 16, 24, ..
+    (2^k and 3 * 2^(k - 1)) up to the largest below n; at most REACH_MAX_RADII = 32 entries (28 at the largest side, 16384)."""
+    radii, k = [0], 0
+    while True:
+        for r in ((1 << k),) + ((3 << (k - 1),) if k >= 1 else ()):
+            if r >= n or len(radii) == mp.REACH_MAX_RADII:
+                return radii
+            radii.append(r)
+        k += 1
+
+
 def scaled(values, image_size):
     """The reference's pixel-valued grids scaled from 3072 to `image_size`."""
     return [max(1, int(round(v * image_size / REF_IMAGE_SIZE))) for v in values]
@@ -984,7 +996,7 @@ RELATIONS = (
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
-                  gradients=False, points=None, point_tables=False):
+                  gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1001,6 +1013,10 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
     if not isinstance(gradients, (bool, np.bool_)):
         raise ValueError("gradients is a flag, got %r" % (gradients,))
+    if reach is None or reach is False:
+        reach = None
+    else:
+        reach = [int(r) for r in mp.reach_radii(REACH_RADII(n) if reach is True else reach)]
     ensemble = int(ensemble)
     device_alterations = getattr(runner, "device_alterations", False)
     if ensemble and not 1 <= ensemble <= mp.SIM_ENSEMBLE_MAX:
@@ -1037,7 +1053,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
-           (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + \
+           (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + (("direct_reach",) if reach is not None else ()) + \
            (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("warp",) if warps else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
@@ -1045,7 +1061,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
-        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), keys=keys, device_alterations=device_alterations,
+        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), reach=reach, reach_tables=bool(reach_tables), reach_maps=bool(reach_maps), keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
 
 
@@ -1112,7 +1128,8 @@ class Scorer:
     (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
     SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key; similarities, tone, scales, gradients and shifts take the row's comparisons, (reference key, region)
     pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset; keep: the dicts carry their
-    tile tables whatever displacement_tiles says, for a warp row's tracking)."""
+    tile tables whatever displacement_tiles says, for a warp row's tracking); reach takes the row's direct comparison, behind
+    similarities, and looks at the change of the input from `source`, the study's raw plane."""
 
     def __init__(self, runner, opt, unalt):
         self.runner, self.proc, self.opt, self.unalt = runner, runner.proc, opt, unalt
@@ -1121,6 +1138,16 @@ class Scorer:
         out = displacement_summary(table, region[4] * region[5], tiles, tiles_off)
         if self.opt.displacement_tiles or keep:
             out["tile_tables"], out["size"] = tile_tables, (region[4], region[5])
+        return out
+
+    def reach_value(self, table, seeds, sq_diff_sum, pixels, class_plane=None):
+        """A row's direct_reach from a full-frame reach table: None where the alteration changed no input pixel, or every one. With
+        reach_maps the output's class plane rides along."""
+        if not 0 < seeds < self.source.size:
+            return None
+        out = reach_row(table, self.opt.reach, seeds, sq_diff_sum, pixels, self.opt.reach_tables)
+        if self.opt.reach_maps and class_plane is not None:
+            out["class_plane"] = np.asarray(class_plane)
         return out
 
 
@@ -1184,6 +1211,12 @@ class DeviceScorer(Scorer):
         res = self.proc.sim_gradients([(0, slot) + region for slot, region in comparisons])
         return [gradient_row(r["table"], r["gsim"]) for r in res]
 
+    def reach(self, comparisons):
+        """One musica_sim_reach call over the row's direct comparison (the first that similarities() scored)."""
+        res = self.proc.sim_reach([(0, slot) + region for slot, region in comparisons], self.opt.reach)
+        plane = self.proc.sim_reach_classes(self.opt.reach) if self.opt.reach_maps else None
+        return [self.reach_value(r["table"], r["seeds"], self.compared[i]["sq_diff_sum"], self.compared[i]["pixels"], plane) for i, r in enumerate(res)]
+
     def shifts(self, comparisons, keep=False):
         """One musica_sim_displace call, none without a comparison."""
         res = self.proc.sim_displace([(0, slot) + region for slot, region in comparisons], self.opt.displacement, tables=True,
@@ -1205,7 +1238,8 @@ class HostScorer(Scorer):
             self.planes[SLOT_VENDOR] = vendor_to_u8(opt.vendor)
 
     def produce(self, alteration):
-        self.out = self.runner.run(alteration.host())
+        self.altered = alteration.host()
+        self.out = self.runner.run(self.altered)
 
     def move(self, method, function, parameter):
         for slot, moved in ((SLOT_UNALTERED, SLOT_ROTATED), (SLOT_VENDOR, SLOT_VENDOR_ROTATED)):
@@ -1235,6 +1269,16 @@ class HostScorer(Scorer):
 
     def gradients(self, comparisons):
         return [gradient_row(*gradient_statistics(self.out, self.planes[slot], [region])[0]) for slot, region in comparisons]
+
+    def reach(self, comparisons):
+        """The restatement on the altered input that produce() kept."""
+        classes = reach_classes(self.source, self.altered, self.opt.reach)
+        seeds, out = int(np.count_nonzero(self.source != self.altered)), []
+        for slot, region in comparisons:
+            table, = reach_statistics(self.out, self.planes[slot], classes, [region], len(self.opt.reach) + 1)
+            a, b = (p.astype(np.int64) for p in self.sides(slot, region))
+            out.append(self.reach_value(table, seeds, int(((a - b) ** 2).sum()), a.size, classes[PROCESSING_MARGIN:-PROCESSING_MARGIN, PROCESSING_MARGIN:-PROCESSING_MARGIN]))
+        return out
 
     def shifts(self, comparisons, keep=False):
         tables = [(region, displacement_tile_tables(self.out, self.planes[slot], region, self.opt.displacement)) for slot, region in comparisons]
@@ -1294,7 +1338,8 @@ def ensemble_of(eproc, noise, registered, full, opt):
 def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations=None, sigmas=None, factors=None, vendor=None, symmetries=None,
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
-              gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False):
+              gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
+              reach_tables=False, reach_maps=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1493,15 +1538,30 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     dependence on the local background (point_summary), and outside_mse. Host and device summarise exact integers with one function,
     so "points" is equal to the last bit on every path. point_tables: the dict also carries "per_point" and "stacks". The rows draw
     nothing from `rng` and take no ordinal. Nothing is asserted: the narrow core, the wide skirt and the rebound ring of a multi-scale
-    amplifier, and how they differ between a dead, a faint and a hot element, are the finding."""
+    amplifier, and how they differ between a dead, a faint and a hot element, are the finding.
+
+    reach: None (the default: the rows and the calls are exactly as without it), True for REACH_RADII(n), or a list of radii
+    (processing.reach_radii: from 0, strictly ascending, at most 32 of at most 16383), else ValueError before any work. Every row gains
+    "direct_reach" behind its gradient keys: None in the unaltered row and in a row whose alteration changed no pixel of the input or
+    every one, else reach_row's dict of the row's DIRECT comparison over the full output frame, its exact sums kept apart by the
+    Chebyshev distance of the pixel from the nearest changed input pixel (reach_classes, reach_statistics; on the device one
+    musica_sim_reach call behind the row's musica_sim_compare, whose sq_diff_sum and pixels the table must add up to; with
+    device_metrics alone the raw plane is made resident once for it): per class rmse, changed share, mean shift and max, and the
+    extent beyond which nothing changed, the floor that no distance removes (the global stages), the spill out of the altered set,
+    the radius of half the spill and the decay slope (reach_summary). Host and device summarise exact integers with one function, so
+    the dict is equal to the last bit on every path. reach_tables: the dict also carries "table". reach_maps: it also carries "class_plane",
+    the (N - 20)^2 classes of the output's pixels (on the device one musica_sim_reach_classes call more), what write_reach_maps draws. Nothing is asserted: how far the
+    pyramid carries a local change, and how much of it the global stages spread over the whole frame, are the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
-                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients, points, point_tables)
+                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients, points, point_tables, reach,
+                        reach_tables, reach_maps)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
     scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
+    scorer.source = raw   # what reach() takes the input's change against
     metrics = [("", scorer.similarities)] + ([("_tone", scorer.tone)] if opt.tone else []) + ([("_scales", scorer.scales)] if opt.scales else []) + \
               ([("_gradient", scorer.gradients)] if opt.gradients else [])
     rows = []
@@ -1527,6 +1587,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         out["alteration"] = alteration.name if alteration is not None else "unaltered"
         for suffix, score in metrics:
             out.update(zip([key + suffix for key, _ in compared], score([c for _, c in compared])))
+        if opt.reach is not None and alteration is not None:   # behind the row's comparisons: the direct one's integers are checked against
+            out["direct_reach"], = scorer.reach([(SLOT_UNALTERED, full)])
         if opt.displacement:   # a *_shift stays None without its comparison, or where the inset leaves a side under 7
             shifted = [(key + "_shift", (slot, _inset(region, opt.displacement))) for key, (slot, region) in own]
             shifted = [(key, c) for key, c in shifted if c[1] is not None]
@@ -1554,8 +1616,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     if opt.device_alterations:
         runner.proc.alter_set_source(raw)
         seed = int(rng.integers(0, 2 ** 63))
-    elif opt.luts and getattr(runner, "device_metrics", False):
-        runner.proc.alter_set_source(raw)   # musica_sim_levels takes its classes from the resident source plane
+    elif (opt.luts or opt.reach is not None) and getattr(runner, "device_metrics", False):
+        runner.proc.alter_set_source(raw)   # musica_sim_levels takes its classes from the resident source plane, musica_sim_reach the unchanged input
     if opt.ensemble:
         eproc = runner.ensemble_context(opt.ensemble)
         eproc.alter_set_source(raw)
@@ -1670,6 +1732,15 @@ def warp_list(text):
     return names
 
 
+def reach_list(text):
+    """--reach R0,R1,...: radii from 0, strictly ascending (processing.reach_radii)."""
+    import argparse
+    try:
+        return [int(v) for v in mp.reach_radii([int(t) for t in text.split(",")])]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Metamorphic study of raw images (or a seeded phantom) on the HIP MUSICA path")
@@ -1763,6 +1834,14 @@ def main(argv=None):
                          "the edge strength of its reference side (gradient similarity and correlation, gain, turn, reversed share, rmse, "
                          "gain per class and its compression slope), written to gradient_robustness.csv; on the GPU with --device-metrics / "
                          "--device-alterations (musica_sim_gradients)")
+    ap.add_argument("--reach", nargs="?", const=True, default=None, type=reach_list, metavar="R0,R1,...",
+                    help="keep every row's direct comparison apart by the Chebyshev distance from the nearest changed input pixel: rmse, changed "
+                         "share, shift and max per distance class, the extent beyond which nothing changed, the global floor, the spill, its half "
+                         "radius and decay, written to reach.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_reach); "
+                         "without a list, 0 and the half-octaves 1, 2, 3, 4, 6, 8, .. below the image side")
+    ap.add_argument("--reach-tables", action="store_true", help="with --reach: keep the exact integers per class in the rows (\"table\")")
+    ap.add_argument("--reach-maps", metavar="DIR",
+                    help="with --reach: two 8-bit BMPs per row that has a reach into DIR: the class plane and the per-class rmse as bars")
     ap.add_argument("--ensemble", type=int, default=0, metavar="K",
                     help="with --device-alterations: repeat every noise alteration K (1 .. 1024) times and split the change of the output into "
                          "bias against the unaltered result and noise, per pixel, written to ensemble.csv (musica_sim_ensemble_*)")
@@ -1788,6 +1867,8 @@ def main(argv=None):
         ap.error("--lut-tables keeps what --luts measures: give --luts")
     if args.point_tables and not args.points:
         ap.error("--point-tables keeps what --points measures: give --points")
+    if (args.reach_tables or args.reach_maps) and args.reach is None:
+        ap.error("--reach-tables and --reach-maps keep and draw what --reach measures: give --reach")
     if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
         ap.error("--covariance takes a radius of 1 .. %d pixels" % mp.SIM_MAX_RADIUS)
     if args.covariance and not args.ensemble:
@@ -1859,6 +1940,8 @@ def main(argv=None):
         shift_args.update(luts=True if args.manifest else LUTS(raw), lut_tables=args.lut_tables)
     if args.points:
         shift_args.update(points=POINTS(args.size), point_tables=args.point_tables)
+    if args.reach is not None:
+        shift_args.update(reach=args.reach, reach_tables=args.reach_tables, reach_maps=bool(args.reach_maps))
     try:
         if args.manifest:
             studies = run_studies(entries, runner, symmetries=args.symmetries, tone=args.tone, **shift_args)
@@ -1874,6 +1957,8 @@ def main(argv=None):
         write_ensemble_maps(studies, args.ensemble_maps)
     if args.covariance_maps:
         write_covariance_maps(studies, args.covariance_maps)
+    if args.reach_maps:
+        write_reach_maps(studies, args.reach_maps)
     print("wrote %d alterations to %s" % (sum(len(rows) - 1 for _, rows in studies), args.out))
     return 0
 

@@ -1598,3 +1598,157 @@ def gradient_summary(table, gsim):
 def gradient_row(table, gsim):
     """A row's *_gradient value: gradient_summary's dict and "table", the 22 x 6 exact integers (dot and cross signed) as lists."""
     return dict(gradient_summary(table, gsim), table=_signed_table(table))
+
+
+# ---- reach: the change of the output by the distance from the changed input (not in the reference's script) ---------------------------
+# The locality relation: a change of the input inside a set changes the output only near it. Two effects carry a local change outwards:
+# the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global stages (min / max,
+# the histograms, the tone curve: the same small shift everywhere). The sums of a comparison kept apart by the Chebyshev distance of the
+# pixel from the nearest changed input pixel tell them apart. reach_classes and reach_statistics are the contract of musica_sim_reach
+# and musica_sim_reach_classes (include/musica.h), which are bit-identical to them; reach_summary is what the study reports of the
+# integers, one function for every path.
+
+def reach_classes(source, altered, radii):
+    """The reach class of every pixel of two 2-D uint16 planes of one shape, a uint8 plane: with seed = source != altered and the K radii
+    (processing.reach_radii: radii[0] = 0, strictly ascending, at most 32 of at most 16383), the class of pixel (x, y) is the smallest k
+    for which the box [x - radii[k], x + radii[k]] x [y - radii[k], y + radii[k]], clipped to the plane, holds a seed, and K where the
+    box of radii[K - 1] holds none (also where nothing changed at all). Class 0 is a changed pixel itself. A box of radius r holds a seed
+    exactly where the Chebyshev distance to the nearest seed is at most r, so this is the chessboard distance transform of the seeds
+    (scipy.ndimage.distance_transform_cdt), looked up in the radii: no summed-area table, unlike the device."""
+    s, a = np.asarray(source), np.asarray(altered)
+    if s.ndim != 2 or s.shape != a.shape or s.dtype != np.uint16 or a.dtype != np.uint16:
+        raise ValueError("reach_classes needs two 2-D uint16 planes of one shape, got %r %s and %r %s" % (s.shape, s.dtype, a.shape, a.dtype))
+    r = mp.reach_radii(radii)
+    seed = s != a
+    if not seed.any():
+        return np.full(s.shape, len(r), dtype=np.uint8)
+    dist = ndimage.distance_transform_cdt(~seed, metric="chessboard")    # 0 on a seed, else the L-infinity distance to the nearest one
+    return np.searchsorted(r.astype(np.int64), dist.astype(np.int64), side="left").astype(np.uint8)
+
+
+def reach_statistics(out, ref, classes, regions, count):
+    """The exact sums per reach class of every region (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes (side a: `out`, side b:
+    `ref`): what musica_sim_reach returns. `classes` is reach_classes' plane of the INPUT, 2 * OUT_MARGIN larger than `out` along both
+    axes, with values below `count` = K + 1: the class of a-side pixel (x, y) is classes[y + OUT_MARGIN, x + OUT_MARGIN], whatever
+    origin side b has. One (count, 6) uint64 table per region: per class n, changed (the pixels with a != b), sum_a, sum_b, sum_dd = the
+    sum of (a - b)^2 and max_d = max |a - b|, 0 for an empty class (processing.REACH_FIELDS). The n add up to w h, the sum_dd to the
+    region's sum of squared differences (musica_sim_compare's sq_diff_sum); changed <= n and max_d^2 changed >= sum_dd >= changed."""
+    a, b, classes, count = np.asarray(out), np.asarray(ref), np.asarray(classes), int(count)
+    m = mp.OUT_MARGIN
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("reach_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    if not 2 <= count <= mp.REACH_MAX_RADII + 1:
+        raise ValueError("count %d is not in 2 .. %d" % (count, mp.REACH_MAX_RADII + 1))
+    if classes.shape != (a.shape[0] + 2 * m, a.shape[1] + 2 * m) or classes.dtype.kind not in "iu" or int(classes.min()) < 0 or int(classes.max()) >= count:
+        raise ValueError("the classes are not a %r plane of integers below %d, got %r %s" % ((a.shape[0] + 2 * m, a.shape[1] + 2 * m), count, classes.shape, classes.dtype))
+    values, tables = np.arange(256, dtype=np.int64), []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        k = classes[ay + m:ay + m + h, ax + m:ax + m + w].astype(np.int64).ravel()
+        pa, pb = a[ay:ay + h, ax:ax + w].astype(np.int64).ravel(), b[by:by + h, bx:bx + w].astype(np.int64).ravel()
+        ha = np.bincount(k * 256 + pa, minlength=count * 256).reshape(count, 256)                # how often class k meets the value a
+        hb = np.bincount(k * 256 + pb, minlength=count * 256).reshape(count, 256)
+        hd = np.bincount(k * 256 + np.abs(pa - pb), minlength=count * 256).reshape(count, 256)   # ... and the difference |a - b|
+        n = hd.sum(axis=1)
+        max_d = np.where(hd > 0, values, 0).max(axis=1)
+        tables.append(np.stack([n, n - hd[:, 0], ha @ values, hb @ values, hd @ (values * values), max_d], axis=1).astype(np.uint64))
+    return tables
+
+
+REACH_KEYS = ("seeds", "classes", "last_class", "extent", "floor", "spill", "half_reach", "decay")   # reach_summary's numbers over the table
+
+
+def reach_summary(table, radii):
+    """What the study reports of a comparison's reach, from reach_statistics' (or musica_sim_reach's) exact integers of ONE region: one
+    function for every study path, so the paths agree to the last bit. The table has K + 1 rows for the K radii; class 0 is distance 0,
+    class k in 1 .. K - 1 the distances radii[k - 1] + 1 .. radii[k], class K everything beyond radii[K - 1]. Every float is one
+    correctly rounded operation on exact integers, or math.fsum of such in ascending class order. Per class, as lists of K + 1 entries
+    (None where the class is empty, n = 0):
+        n             the class's pixels (0 for an empty class)
+        rmse          sqrt(sum_dd / n)
+        changed       changed / n, the share of its pixels whose output changed
+        shift         (sum_a - sum_b) / n, the mean signed change
+        max           max_d
+        outer         radii[k], the class's outer radius; None for the open class K
+    and over the table
+        classes       how many classes are occupied
+        last_class    the largest class with changed > 0; None where no pixel changed
+        extent        the outer radius of last_class: beyond it NOTHING changed, exactly; None where last_class is None or the open
+                      class K (the change reaches past the last radius)
+        floor         the rmse of the outermost occupied class: the global component, which no distance removes
+        spill         sum of sum_dd over the classes >= 1 / sum over all: the share of the change that left the altered set; None where
+                      nothing changed (sum_dd = 0 everywhere)
+        half_reach    the radius within which half of the spill lies. With T = the spill's sum_dd, C_k = sum_dd of classes 1 .. k
+                      (C_0 = 0) and k the smallest class >= 1 with 2 C_k >= T (decided on the integers): linear in the radius across
+                      class k, radii[k - 1] + (radii[k] - radii[k - 1]) (T - 2 C_{k-1}) / (2 sum_dd_k); None where T = 0 or k is the
+                      open class K
+        decay         the unweighted least-squares slope of log2(rmse_k^2 - floor^2) on log2(mid_k), mid_k = (radii[k - 1] + 1 +
+                      radii[k]) / 2 the class's mean distance, over the occupied classes k in 1 .. K - 1 whose rmse^2 exceeds floor^2
+                      (decided on the integers: sum_dd_k n_f > sum_dd_f n_k, f the floor's class; the difference is taken as
+                      (sum_dd_k n_f - sum_dd_f n_k) / (n_k n_f)); None with fewer than three such classes. -2 is a 1 / r fall of the
+                      amplitude.
+    No threshold is fixed here: these are findings."""
+    r = [int(v) for v in mp.reach_radii(radii)]
+    t = [[int(v) for v in row] for row in np.asarray(table)]
+    K = len(r)
+    if len(t) != K + 1 or any(len(row) != 6 for row in t):
+        raise ValueError("a reach table of %d radii is (%d, 6), got %r" % (K, K + 1, np.asarray(table).shape))
+    occupied = [k for k in range(K + 1) if t[k][0] > 0]
+    if not occupied:
+        raise ValueError("the reach table holds no pixel")
+    per = lambda f: [f(t[k]) if t[k][0] > 0 else None for k in range(K + 1)]
+    touched = [k for k in occupied if t[k][1] > 0]
+    last = touched[-1] if touched else None
+    f = occupied[-1]
+    nf, df = t[f][0], t[f][4]
+    total, spilled = sum(row[4] for row in t), sum(row[4] for row in t[1:])
+    half = None
+    if spilled > 0:
+        before = 0
+        for k in range(1, K + 1):
+            if 2 * (before + t[k][4]) >= spilled:
+                if k < K:
+                    half = r[k - 1] + (r[k] - r[k - 1]) * ((spilled - 2 * before) / (2 * t[k][4]))
+                break
+            before += t[k][4]
+    fit = [(math.log2((r[k - 1] + 1 + r[k]) / 2), math.log2((t[k][4] * nf - df * t[k][0]) / (t[k][0] * nf)))
+           for k in occupied if 1 <= k < K and t[k][4] * nf > df * t[k][0]]
+    decay = None
+    if len(fit) >= 3:
+        mx, my = math.fsum(x for x, _ in fit) / len(fit), math.fsum(y for _, y in fit) / len(fit)
+        decay = math.fsum((x - mx) * (y - my) for x, y in fit) / math.fsum((x - mx) ** 2 for x, _ in fit)
+    return {"classes": len(occupied), "last_class": last, "extent": r[last] if last is not None and last < K else None,
+            "floor": math.sqrt(df / nf), "spill": spilled / total if total else None, "half_reach": half, "decay": decay,
+            "n": [row[0] for row in t], "rmse": per(lambda row: math.sqrt(row[4] / row[0])), "changed": per(lambda row: row[1] / row[0]),
+            "shift": per(lambda row: (row[2] - row[3]) / row[0]), "max": per(lambda row: row[5]), "outer": r + [None]}
+
+
+def reach_maps(class_plane, rmse):
+    """Two uint8 images of a row's reach: the class plane, class 0 white and the last class black in equal steps, and the per-class rmse
+    as bars, 8 pixels wide and up to 64 high, the tallest the largest rmse (an empty class and an rmse of 0 have no bar)."""
+    plane = np.asarray(class_plane)
+    last = len(rmse) - 1
+    shade = (255 - (plane.astype(np.int64) * 255) // max(last, 1)).astype(np.uint8)
+    top = max([v for v in rmse if v] or [1.0])
+    bars = np.zeros((64, 8 * len(rmse)), np.uint8)
+    for k, v in enumerate(rmse):
+        h = int(round(64 * v / top)) if v else 0
+        if h:
+            bars[64 - h:, 8 * k:8 * k + 7] = 255
+    return shade, bars
+
+
+def reach_row(table, radii, seeds, sq_diff_sum, pixels, keep=False):
+    """A row's direct_reach value: reach_summary's dict of the full frame's table, "seeds" (the changed pixels of the input plane) and
+    "radii", with keep=True "table" as well, the (K + 1) x 6 exact integers as lists. The table must account for the frame (ValueError
+    otherwise): its n add up to `pixels` and its sum_dd to `sq_diff_sum`, the integers of the row's direct comparison."""
+    t = np.asarray(table)
+    if int(t[:, 0].sum()) != int(pixels) or int(t[:, 4].sum()) != int(sq_diff_sum):
+        raise ValueError("the reach table holds %d pixels and a squared difference of %d, the frame %d and %d"
+                         % (int(t[:, 0].sum()), int(t[:, 4].sum()), int(pixels), int(sq_diff_sum)))
+    out = dict(reach_summary(t, radii), seeds=int(seeds), radii=[int(v) for v in radii])
+    if keep:
+        out["table"] = [[int(v) for v in row] for row in t]
+    return out

@@ -190,6 +190,9 @@ LEVEL_MIN_SHIFT = 4         # MUSICA_LEVEL_MIN_SHIFT
 LEVEL_MAX_SHIFT = 15        # MUSICA_LEVEL_MAX_SHIFT
 GRADIENT_CLASSES = 22       # MUSICA_GRADIENT_CLASSES: the bit lengths of B <= 1 300 500
 GRADIENT_C = 2720           # MUSICA_GRADIENT_C
+REACH_MAX_RADII = 32        # MUSICA_REACH_MAX_RADII
+REACH_MAX_RADIUS = 16383    # MUSICA_REACH_MAX_RADIUS
+REACH_MAX_QUERIES = 16      # MUSICA_REACH_MAX_QUERIES
 
 
 def zoom_ratio(zoom):
@@ -542,6 +545,27 @@ class SimGradientResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64), ("gsim", C.c_double)]
 
 
+REACH_FIELDS = ("n", "changed", "sum_a", "sum_b", "sum_dd", "max_d")   # the six words of a class of a reach table
+
+
+class SimReachResult(C.Structure):
+    """musica_sim_reach_result: where a query's table lies in `tables`, the region's exact sum of squared differences and the number
+    of changed pixels of the whole input plane."""
+    _fields_ = [("table_offset", C.c_uint64), ("classes", C.c_uint64), ("ssd", C.c_uint64), ("pixels", C.c_uint64), ("seeds", C.c_uint64)]
+
+
+def reach_radii(radii):
+    """A list of reach radii as metrics.reach_classes and the library take it: a uint32 array of 1 .. REACH_MAX_RADII integers, the first
+    0, strictly ascending, each at most REACH_MAX_RADIUS, else ValueError."""
+    r = [v for v in radii]
+    if not 1 <= len(r) <= REACH_MAX_RADII or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
+        raise ValueError("radii are not 1 .. %d integers, got %r" % (REACH_MAX_RADII, r))
+    r = [int(v) for v in r]
+    if r[0] != 0 or any(b <= a for a, b in zip(r, r[1:])) or r[-1] > REACH_MAX_RADIUS:
+        raise ValueError("radii do not ascend strictly from 0 to at most %d: %r" % (REACH_MAX_RADIUS, r))
+    return np.array(r, dtype=np.uint32)
+
+
 class SimDisplaceResult(C.Structure):
     """musica_sim_displace_result: where one comparison's exact block matching puts the output."""
     _fields_ = [("pixels", C.c_uint64), ("ssd_zero", C.c_uint64), ("ssd_min", C.c_uint64), ("dx", C.c_int32), ("dy", C.c_int32),
@@ -756,6 +780,8 @@ ABI = {
     "musica_alter_lut": (C.c_int, [_VP, C.c_uint32, _U16P]),
     "musica_sim_levels": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimLevelResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_gradients": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimGradientResult), C.POINTER(C.c_uint64), C.c_uint64]),
+    "musica_sim_reach": (C.c_int, [_VP, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimReachResult), C.POINTER(C.c_uint64), C.c_uint64]),
+    "musica_sim_reach_classes": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, _U8P]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -1264,6 +1290,38 @@ class MusicaProcessing:
         for r in res:
             at = int(r.table_offset)
             out.append({"table": tables[at:at + per].reshape(GRADIENT_CLASSES, len(GRADIENT_FIELDS)).copy(), "gsim": float(r.gsim), "pixels": int(r.pixels)})
+        return out
+
+    def sim_reach(self, queries, radii):
+        """metrics.reach_statistics on the device, the classes being metrics.reach_classes(source plane, the input the image's current
+        output was computed from, radii): queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or SimQuery) with
+        w, h >= 1, 1 .. REACH_MAX_QUERIES of them, all of one image_index, all in one call; radii as reach_radii takes them (ValueError
+        before any call). Returns one dict per query: "table", a (len(radii) + 1, 6) uint64 array of the exact n, changed, sum_a, sum_b,
+        sum_dd = sum of (a - b)^2 and max_d = max |a - b| (REACH_FIELDS) per class, and the Python ints "classes", "ssd" (the sum of
+        sum_dd), "pixels" and "seeds" (the changed pixels of the whole N x N input plane)."""
+        r = reach_radii(radii)
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        if not 1 <= len(qs) <= REACH_MAX_QUERIES:
+            raise ValueError("sim_reach takes 1 .. %d queries, got %d" % (REACH_MAX_QUERIES, len(qs)))
+        per = (len(r) + 1) * len(REACH_FIELDS)
+        words = len(qs) * per
+        arr, res, tables = (SimQuery * len(qs))(*qs), (SimReachResult * len(qs))(), np.zeros(words, dtype=np.uint64)
+        self._ok(self._lib.musica_sim_reach(self._h, len(r), r.ctypes.data_as(_U32P), len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), words),
+                 "musica_sim_reach")
+        out = []
+        for q in res:
+            at, c = int(q.table_offset), int(q.classes)
+            out.append({"table": tables[at:at + c * len(REACH_FIELDS)].reshape(c, len(REACH_FIELDS)).copy(), "classes": c, "ssd": int(q.ssd),
+                        "pixels": int(q.pixels), "seeds": int(q.seeds)})
+        return out
+
+    def sim_reach_classes(self, radii, image_index=0):
+        """metrics.reach_classes(source plane, the input image_index's current output was computed from, radii) cropped by the margin:
+        an (N - 20, N - 20) uint8 array."""
+        r = reach_radii(radii)
+        n = self.imageSize - 2 * OUT_MARGIN
+        out = np.empty((n, n), dtype=np.uint8)
+        self._ok(self._lib.musica_sim_reach_classes(self._h, int(image_index), len(r), r.ctypes.data_as(_U32P), out.ctypes.data_as(_U8P)), "musica_sim_reach_classes")
         return out
 
     def sim_get_reference(self, slot):

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -45,6 +45,9 @@ GRATING_CSV_HEADER = ['raw file', 'alteration', 'period', 'gratings'] + ['%s %s'
 GAIN_CSV_HEADER = ['raw file', 'alteration', 'axis', 'lines'] + [k.replace('_', ' ') for k in PROFILE_KEYS]   # gain_response.csv
 LEVEL_CSV_HEADER = ['raw file', 'alteration'] + [k.replace('_', ' ') for k in LEVEL_KEYS]   # level_response.csv
 
+REACH_CSV_CLASS = ("outer", "n", "rmse", "changed", "shift", "max")   # reach_summary's per-class lists, in reach.csv's order
+REACH_CSV_HEADER = ['raw file', 'alteration', 'class', 'outer radius', 'pixels', 'rmse', 'changed share', 'shift', 'max'] + \
+                   [k.replace('_', ' ') for k in REACH_KEYS]   # reach.csv
 WARP_CSV_HEADER = ['raw file', 'alteration', 'reach', 'peak'] + [k.replace('_', ' ') for k in WARP_TRACKING_KEYS] + ['registered mse', 'registered ssim']   # warp_response.csv
 
 
@@ -171,6 +174,9 @@ RELATION_CSVS = (
     ("grating_response.csv", GRATING_CSV_HEADER, "gratings", lambda d: d["periods"].items(), _spread_cells("gratings", GRATING_ROW_KEYS, GRATING_ROW_STATS)),
     ("gain_response.csv", GAIN_CSV_HEADER, "profiles", lambda d: [(axis, d[axis]) for axis in PROFILE_AXES], lambda d, g: [g["lines"]] + [g[k] for k in PROFILE_KEYS]),
     ("level_response.csv", LEVEL_CSV_HEADER, "levels", lambda d: [(d[LEVEL_KEYS[0]], d)], lambda d, g: [g[k] for k in LEVEL_KEYS[1:]]),
+    # reach.csv: one line per row that has a reach and per class, ascending, the summary's numbers the same on each of its lines
+    ("reach.csv", REACH_CSV_HEADER, "direct_reach", lambda d: [(k, k) for k in range(len(d["n"]))],
+     lambda d, k: ["" if d[c][k] is None else d[c][k] for c in REACH_CSV_CLASS] + ["" if d[c] is None else d[c] for c in REACH_KEYS]),
     # point_response.csv: one line per point_ row and group, in the groups' order, then "all"
     ("point_response.csv", POINT_CSV_HEADER, "points", lambda d: list(enumerate(d["groups"])) + [("all", d["all"])],
      lambda d, g: [g[k] for k in POINT_KEYS] + [d["outside_mse"]]),
@@ -231,6 +237,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     Studies run with points (rows[0] has "points") also get point_response.csv (POINT_CSV_HEADER): one line per point_ row and group
     (the index of the cluster size), then one for all the row's points ("all"): point_summary's scalars (an empty cell where one is
     None) and the row's outside mse.
+
+    Studies run with reach (rows[0] has "direct_reach") also get reach.csv (REACH_CSV_HEADER): one line per row whose alteration
+    changed some but not all input pixels and per distance class, ascending: the class, its outer radius (empty for the open last
+    class), its pixels, rmse, changed share, mean shift and max (empty for an empty class), then reach_summary's numbers of the row
+    (seeds, classes, last class, extent, floor, spill, half reach, decay; an empty cell where one is None), the same on each line.
 
     Studies run with warps (rows[0] has "warp") also get warp_response.csv (WARP_CSV_HEADER): one line per warp row, the field's reach
     and peak displacement in pixels, the four tracking numbers of metrics.warp_tracking (empty without a displacement radius) and the
@@ -310,6 +321,18 @@ def _covariance_images(r):
 def _displacement_images(r):
     t = r.get("registered_shift")
     return () if t is None or "tile_tables" not in t else zip(("rmse", "shift"), displacement_maps(t["tile_tables"], *t["size"]))
+
+
+def _reach_images(r):
+    d = r.get("direct_reach")
+    return () if d is None or "class_plane" not in d else zip(("reach_classes", "reach_rmse"), reach_maps(d["class_plane"], d["rmse"]))
+
+
+def write_reach_maps(studies, out_dir):
+    """Two 8-bit BMPs per row of studies run with reach_maps that has a reach: <raw>_<alteration>_reach_classes.bmp, the class of every
+    output pixel (class 0 white, the last class black), and <raw>_<alteration>_reach_rmse.bmp, the per-class rmse as bars. Returns the
+    paths written."""
+    return _write_maps(studies, out_dir, _reach_images)
 
 
 def write_ensemble_maps(studies, out_dir):
