@@ -30,7 +30,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     inserted into image 0, and the sums and stacks of the same points, shifted into the output plane, of image 1's output against slot 0;
   * the reach pair at N = 151 (odd: the single-pixel form of the row launch): the tables of image 1's output against slot 0 over the
     same four regions as the levels, and the class plane, for fifteen radii up to 128, the seeds being where the input of image 1's
-    step differs from the source plane.
+    step differs from the source plane;
+  * the local order at N = 151 of other images' outputs against slot 0: the full frame (125 x 125 interior pixels: 2 x 2 tiles with a
+    ragged tail), a 70 x 75 region from mid-tile with different origins on the two sides (one tile across, two down), a 7-wide column
+    and a 7 x 7 corner; integers only.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -157,5 +160,7 @@ if hasattr(p, "sim_reach"):       # likewise a --tree from before the reach metr
     radii = [0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128]
     note("musica_sim_reach", [p.sim_reach([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (1, 0, 64, 0, 64, 0, 1, NW), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)], radii),
                               p.sim_reach_classes(radii, image_index=1)])
+if hasattr(p, "sim_order"):       # likewise a --tree from before the local-order metric
+    note("musica_sim_order", p.sim_order([(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 7, NW - 1), (1, 0, NW - 7, NW - 7, 0, 0, 7, 7)]))
 p.cleanup()
 print(json.dumps(digests))

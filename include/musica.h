@@ -1062,6 +1062,43 @@ typedef struct musica_sim_gradient_result {
 int musica_sim_gradients(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_gradient_result* results,
                          uint64_t* tables, uint64_t table_words);
 
+/* ---- local order: the census signs of a comparison (new, not in the reference) ----
+ * MUSICA ends in a monotone tone curve, and most alterations move gray levels without changing the scene. Every other measurement
+ * charges the values that moved; this one asks whether the same pixel is still the darker one of a neighbouring pair (the census
+ * transform, Zabih & Woodfill 1994). metrics.order_statistics is the contract; every word of the tables is an exact integer equal to it
+ * and byte-identical from call to call. There is no float on the device: every derived number is the host's (metrics.order_summary).
+ * A query is musica_sim_compare's (side a the 8-bit output of batch image `image_index`, quantised while read exactly as
+ * musica_sim_compare reads it; side b reference slot `slot`; w, h >= 7). Over the INTERIOR of the region, the (w - 6) x (h - 6) pixels
+ * whose 7 x 7 neighbourhood lies inside the region (no pixel outside a region is read), a pixel c and each of its 48 neighbours n give
+ * one sign per side, s = sign(p[n] - p[c]) in {-1, 0, +1}, in the ring max(|dx|, |dy|) = 1, 2, 3 of 8, 16 and 24 neighbours. A (pixel,
+ * neighbour) pair is
+ *   same       sa = sb != 0      the order is kept
+ *   reversed   sa = -sb != 0     the order is reversed
+ *   flattened  sa = 0, sb != 0   the output ties where the reference orders
+ *   split      sa != 0, sb = 0   the output orders where the reference ties
+ * or tied on both sides. The census distance of a pixel is d = sum |sa - sb| over its 48 neighbours = 2 reversed + flattened + split,
+ * 0 .. 96. Query i gets MUSICA_ORDER_TABLE_WORDS uint64_t in the flat `tables`, from results[i].table_offset (in words: i *
+ * MUSICA_ORDER_TABLE_WORDS) on: first [MUSICA_ORDER_RINGS][MUSICA_ORDER_WORDS], per ring
+ *   pairs (results[i].pixels x 8, 16, 24), same, reversed, flattened, split          (the pairs tied on both sides are the remainder)
+ * then [MUSICA_ORDER_BINS], the number of interior pixels at each d; they add up to results[i].pixels = (w - 6) (h - 6), and
+ * sum d hist[d] equals the rings' sum of 2 reversed + flattened + split. Only ring sums are shown, so the order of the neighbours
+ * inside a ring is the implementation's own. Identical sides give reversed = flattened = split = 0 and hist[0] = pixels; swapping the
+ * sides swaps flattened and split; b -> 255 - b swaps same and reversed; a strictly increasing map of either side changes no word.
+ * Every word of the tables is written and nothing behind them. Synchronous, on the context's stream after whatever was enqueued there;
+ * changes no slot, no result of a step and no input image; scratch is allocated on first use. Refused before any device work: what
+ * musica_sim_compare refuses, then a NULL `tables` and table_words < count * MUSICA_ORDER_TABLE_WORDS. After a refusal the context
+ * stays usable. */
+#define MUSICA_ORDER_RINGS 3
+#define MUSICA_ORDER_WORDS 5
+#define MUSICA_ORDER_BINS 97
+#define MUSICA_ORDER_TABLE_WORDS 112
+typedef struct musica_sim_order_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t pixels;                /* (w - 6) * (h - 6) */
+} musica_sim_order_result;
+int musica_sim_order(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_order_result* results,
+                     uint64_t* tables, uint64_t table_words);
+
 /* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
  * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change
  * outwards: the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global

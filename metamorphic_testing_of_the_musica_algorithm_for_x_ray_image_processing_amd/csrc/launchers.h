@@ -439,6 +439,20 @@ struct GradQueryDev : SimRegion {
 // every query's words, zeroed by the caller: the tiles add into them with u64 atomics; part: a double per tile (all written); out[i]: the
 // sum of q over query i's interior
 void launch_sim_gradients(hipStream_t st, const GradQueryDev* d_qs, int count, int max_tiles, unsigned long long* tables, double* part, double* out);
+// kernels_order.hip: the local-order metric. One comparison of musica_sim_order: w, h >= 7 are the REGION's; the kernel tiles its
+// interior, (w - 6) x (h - 6). tiles_x / tiles_y: ceil((w - 6) / 64), ceil((h - 6) / 64); table: where its kOrderTableWords u64 start in
+// the launch's flat tables, in words.
+constexpr int kOrderRings = 3;            // MUSICA_ORDER_RINGS: max(|dx|, |dy|) = 1, 2, 3 with 8, 16 and 24 neighbours
+constexpr int kOrderWords = 5;            // MUSICA_ORDER_WORDS: pairs, same, reversed, flattened, split
+constexpr int kOrderBins = 97;            // MUSICA_ORDER_BINS: the census distance d = 0 .. 96
+constexpr int kOrderTableWords = 112;     // MUSICA_ORDER_TABLE_WORDS: [kOrderRings][kOrderWords], then [kOrderBins]
+struct OrderQueryDev : SimRegion {
+    int tiles_x, tiles_y;
+    unsigned long long table;
+};
+// metrics.order_statistics over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y). tables: every query's words,
+// zeroed by the caller: the tiles add into them with u64 atomics
+void launch_sim_order(hipStream_t st, const OrderQueryDev* d_qs, int count, int max_tiles, unsigned long long* tables);
 // kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
 // Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
 constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII

@@ -167,6 +167,9 @@ struct StudyState {
     double* d_grad_out = nullptr;                  // [MUSICA_SIM_MAX_QUERIES]
     double* d_grad_part = nullptr;                 // the tiles' partials of one call: grad_part_cap doubles, regrown when a call needs more
     size_t grad_part_cap = 0;
+    // musica_sim_order: the queries and the flat tables
+    OrderQueryDev* d_order_q = nullptr;            // [MUSICA_SIM_MAX_QUERIES]
+    unsigned long long* d_order_tables = nullptr;  // [MUSICA_SIM_MAX_QUERIES][kOrderTableWords], allocated by the first musica_sim_order
     // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
     // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
     uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either

@@ -1,8 +1,8 @@
-// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the nine query calls (musica_sim_*),
+// musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the query calls (musica_sim_*),
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip and kernels_reach.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip and kernels_reach.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it.
 #include <math.h>
 #include <string.h>
@@ -1067,6 +1067,44 @@ int musica_sim_gradients(musica_ctx* c, uint32_t count, const musica_sim_query* 
     }
     return 1;
     ABI_CATCH("musica_sim_gradients")
+}
+
+// ---- the local order of a comparison (musica_sim_order, include/musica.h; kernels_order.hip) --------------------------------------------
+static_assert(kOrderRings == MUSICA_ORDER_RINGS && kOrderWords == MUSICA_ORDER_WORDS && kOrderBins == MUSICA_ORDER_BINS &&
+                  kOrderTableWords == MUSICA_ORDER_TABLE_WORDS,
+              "kernels_order.hip's constants are include/musica.h's");
+
+int musica_sim_order(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_order_result* out, uint64_t* tables, uint64_t table_words) {
+    ABI_TRY
+    if (!sim_check_queries(c, "musica_sim_order", count, qs, out)) return 0;
+    if (!tables) return fail("musica_sim_order: tables is NULL");
+    const size_t per_query = (size_t)kOrderTableWords, words = count * per_query;
+    if (table_words < words) return fail("musica_sim_order: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
+    std::vector<OrderQueryDev> hq(count);
+    int max_tiles = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        sim_region(c, qs[i], hq[i]);
+        hq[i].tiles_x = tiles_along(qs[i].w - 6);   // of the interior
+        hq[i].tiles_y = tiles_along(qs[i].h - 6);
+        hq[i].table = i * per_query;
+        max_tiles = std::max(max_tiles, hq[i].tiles_x * hq[i].tiles_y);
+    }
+    CHECK_CTX(c);
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_order_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_order_tables, (size_t)MUSICA_SIM_MAX_QUERIES * per_query)))
+        return fail("musica_sim_order: device allocation failed");
+    HIP_OK(hipMemcpyAsync(st.d_order_q, hq.data(), count * sizeof(OrderQueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.d_order_tables, 0, words * sizeof(uint64_t), c->stream));   // the tiles add into them
+    launch_sim_order(c->stream, st.d_order_q, (int)count, max_tiles, st.d_order_tables);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(tables, st.d_order_tables, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        out[i].table_offset = hq[i].table;
+        out[i].pixels = (uint64_t)(qs[i].w - 6) * (qs[i].h - 6);
+    }
+    return 1;
+    ABI_CATCH("musica_sim_order")
 }
 
 // ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------

@@ -914,6 +914,8 @@ TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "referenc
              "registered_reference": "registered_reference_tone"}
 GRADIENT_ROW_KEYS = {"direct": "direct_gradient", "registered": "registered_gradient", "reference": "reference_gradient",
                      "registered_reference": "registered_reference_gradient"}
+ORDER_ROW_KEYS = {"direct": "direct_order", "registered": "registered_order", "reference": "reference_order",
+                  "registered_reference": "registered_reference_order"}
 
 
 VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
@@ -996,7 +998,7 @@ RELATIONS = (
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
-                  gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False):
+                  gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1013,6 +1015,8 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
     if not isinstance(gradients, (bool, np.bool_)):
         raise ValueError("gradients is a flag, got %r" % (gradients,))
+    if not isinstance(order, (bool, np.bool_)):
+        raise ValueError("order is a flag, got %r" % (order,))
     if reach is None or reach is False:
         reach = None
     else:
@@ -1053,13 +1057,13 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
-           (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + (("direct_reach",) if reach is not None else ()) + \
+           (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + (tuple(ORDER_ROW_KEYS[k] for k in compared) if order else ()) + (("direct_reach",) if reach is not None else ()) + \
            (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("warp",) if warps else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
-        displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
+        displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), order=bool(order), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
         grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), reach=reach, reach_tables=bool(reach_tables), reach_maps=bool(reach_maps), keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
@@ -1126,7 +1130,7 @@ def study_alterations(raw, rng, p, seed, shape, opt):
 class Scorer:
     """How run_study scores a row, on the host or on the device. produce(alteration) makes the altered output the one that is scored
     (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
-    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key; similarities, tone, scales, gradients and shifts take the row's comparisons, (reference key, region)
+    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key; similarities, tone, scales, gradients, order and shifts take the row's comparisons, (reference key, region)
     pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset; keep: the dicts carry their
     tile tables whatever displacement_tiles says, for a warp row's tracking); reach takes the row's direct comparison, behind
     similarities, and looks at the change of the input from `source`, the study's raw plane."""
@@ -1211,6 +1215,11 @@ class DeviceScorer(Scorer):
         res = self.proc.sim_gradients([(0, slot) + region for slot, region in comparisons])
         return [gradient_row(r["table"], r["gsim"]) for r in res]
 
+    def order(self, comparisons):
+        """One musica_sim_order call over the row's comparisons."""
+        res = self.proc.sim_order([(0, slot) + region for slot, region in comparisons])
+        return [order_row(np.concatenate([r["rings"].ravel(), r["histogram"]])) for r in res]
+
     def reach(self, comparisons):
         """One musica_sim_reach call over the row's direct comparison (the first that similarities() scored)."""
         res = self.proc.sim_reach([(0, slot) + region for slot, region in comparisons], self.opt.reach)
@@ -1269,6 +1278,9 @@ class HostScorer(Scorer):
 
     def gradients(self, comparisons):
         return [gradient_row(*gradient_statistics(self.out, self.planes[slot], [region])[0]) for slot, region in comparisons]
+
+    def order(self, comparisons):
+        return [order_row(order_statistics(self.out, self.planes[slot], [region])[0]) for slot, region in comparisons]
 
     def reach(self, comparisons):
         """The restatement on the altered input that produce() kept."""
@@ -1339,7 +1351,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False):
+              reach_tables=False, reach_maps=False, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1393,6 +1405,18 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     row's queries go through one musica_sim_gradients call behind the scales'; on the host the restatement scores the same crops.
     The integers are equal on every path and summarised by one function; gsim agrees to rounding (the device sums in its own fixed
     order). Anything but a bool is a ValueError; with gradients=False the rows and the launches are exactly as before.
+
+    order: True asks whether the local order of the gray levels survived: is the same pixel still the darker one of a neighbouring
+    pair (order_statistics: the census signs of both sides over the 7 x 7 neighbourhood). A monotone change of the gray levels, even a
+    spatially varying one that stays locally monotone, scores as nothing; rebound rings, halos, reversed weak edges and flattened
+    texture break orders. Every comparison dict of a row gains a sibling behind the gradient keys and before direct_reach: direct_order,
+    registered_order and, with a vendor image, reference_order and registered_reference_order; present exactly where the original is
+    and None exactly where it is None. Each is order_row's dict: the ORDER_KEYS tau, tau_by_ring (three entries), reversed, flattened,
+    split, intact, distance, median and p95, "rings", the exact 3 x 5 integers per ring (pairs, same, reversed, flattened, split), and
+    "histogram", the 97 numbers of interior pixels per census distance. On the device the row's queries go through one
+    musica_sim_order call behind the gradients'; on the host the restatement scores the same crops. There is no float on the device:
+    the integers are equal on every path and summarised by one function, so the rows are identical. Anything but a bool is a
+    ValueError; with order=False the rows and the launches are exactly as before.
 
     ensemble: K > 0 (at most SIM_ENSEMBLE_MAX; needs runner.device_alterations, else ValueError) repeats every noise alteration K times and
     splits the change of the output into bias and noise (ensemble_statistics). Every row gains "ensemble": None for rows without noise,
@@ -1556,19 +1580,19 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
                         edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients, points, point_tables, reach,
-                        reach_tables, reach_maps)
+                        reach_tables, reach_maps, order)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
     scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
     scorer.source = raw   # what reach() takes the input's change against
     metrics = [("", scorer.similarities)] + ([("_tone", scorer.tone)] if opt.tone else []) + ([("_scales", scorer.scales)] if opt.scales else []) + \
-              ([("_gradient", scorer.gradients)] if opt.gradients else [])
+              ([("_gradient", scorer.gradients)] if opt.gradients else []) + ([("_order", scorer.order)] if opt.order else [])
     rows = []
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, gradients, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, order, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -1834,6 +1858,11 @@ def main(argv=None):
                          "the edge strength of its reference side (gradient similarity and correlation, gain, turn, reversed share, rmse, "
                          "gain per class and its compression slope), written to gradient_robustness.csv; on the GPU with --device-metrics / "
                          "--device-alterations (musica_sim_gradients)")
+    ap.add_argument("--order", action="store_true",
+                    help="ask whether the local order of the gray levels survived: the census signs of every comparison over the 7 x 7 "
+                         "neighbourhood (Kendall's tau of centre-neighbour pairs, overall and per ring, the reversed, flattened and split "
+                         "shares, the intact share and the census distance), written to order_robustness.csv; on the GPU with "
+                         "--device-metrics / --device-alterations (musica_sim_order)")
     ap.add_argument("--reach", nargs="?", const=True, default=None, type=reach_list, metavar="R0,R1,...",
                     help="keep every row's direct comparison apart by the Chebyshev distance from the nearest changed input pixel: rmse, changed "
                          "share, shift and max per distance class, the extent beyond which nothing changed, the global floor, the spill, its half "
@@ -1916,6 +1945,8 @@ def main(argv=None):
         shift_args["scales"] = args.scales
     if args.gradients:
         shift_args["gradients"] = True
+    if args.order:
+        shift_args["order"] = True
     if args.ensemble:
         shift_args.update(ensemble=args.ensemble, ensemble_tiles=bool(args.ensemble_maps))
     if args.covariance:

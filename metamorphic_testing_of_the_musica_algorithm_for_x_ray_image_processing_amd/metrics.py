@@ -1600,6 +1600,122 @@ def gradient_row(table, gsim):
     return dict(gradient_summary(table, gsim), table=_signed_table(table))
 
 
+# ---- local order: the census signs of a comparison (not in the reference's script) -----------------------------------------------------
+# MUSICA ends in a monotone tone curve and most alterations move gray levels without changing the scene. Every other metric charges the
+# values that moved; this one asks whether the same pixel is still the darker one of a neighbouring pair (the census transform, Zabih &
+# Woodfill 1994): a spatially varying but locally monotone change keeps every local order and scores as "nothing happened", while
+# rebound rings, halos, reversed weak edges and flattened texture break orders. order_statistics is the contract of musica_sim_order
+# (include/musica.h), whose tables are bit-identical to it; order_summary is what the study reports of the integers, one function for
+# every path. Integers throughout: every double is computed here from exact integers.
+
+ORDER_RADIUS = 3   # the 7 x 7 neighbourhood: rings max(|dx|, |dy|) = 1, 2, 3 with 8, 16 and 24 neighbours
+
+
+def order_statistics(out, ref, regions):
+    """What musica_sim_order returns for every region (ax, ay, bx, by, w, h), w, h >= 7, of two 2-D uint8 planes (side a: `out`, side
+    b: `ref`): a list of flat tables of processing.ORDER_TABLE_WORDS = 112 uint64. Over the interior of the region, the (w - 6) x
+    (h - 6) pixels whose 7 x 7 neighbourhood lies inside it, a pixel c and each of its 48 neighbours n give per side the sign
+    s = sign(p[n] - p[c]); the pair is `same` (sa = sb != 0), `reversed` (sa = -sb != 0), `flattened` (sa = 0, sb != 0: the output ties
+    where the reference orders), `split` (sa != 0, sb = 0) or tied on both sides. The table holds first (3, 5), per ring max(|dx|, |dy|)
+    = 1, 2, 3 the pairs (pixels x 8, 16, 24), same, reversed, flattened and split (processing.ORDER_FIELDS), then the (97,) histogram
+    of the per-pixel census distance d = sum |sa - sb| = 2 reversed + flattened + split, 0 .. 96 (order_parts splits a table)."""
+    a, b = np.asarray(out), np.asarray(ref)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("order_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    R = ORDER_RADIUS
+    res = []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 7 or h < 7 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is smaller than 7 x 7 or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        pa, pb = a[ay:ay + h, ax:ax + w].astype(np.int16), b[by:by + h, bx:bx + w].astype(np.int16)
+        ca, cb = pa[R:h - R, R:w - R], pb[R:h - R, R:w - R]
+        rings = np.zeros((mp.ORDER_RINGS, len(mp.ORDER_FIELDS)), dtype=np.int64)
+        d = np.zeros(ca.shape, dtype=np.int64)
+        for dy in range(-R, R + 1):
+            for dx in range(-R, R + 1):
+                ring = max(abs(dx), abs(dy))
+                if ring == 0:
+                    continue
+                sa = np.sign(pa[R + dy:h - R + dy, R + dx:w - R + dx] - ca)
+                sb = np.sign(pb[R + dy:h - R + dy, R + dx:w - R + dx] - cb)
+                rings[ring - 1] += [ca.size, int(((sa == sb) & (sa != 0)).sum()), int(((sa == -sb) & (sa != 0)).sum()),
+                                    int(((sa == 0) & (sb != 0)).sum()), int(((sa != 0) & (sb == 0)).sum())]
+                d += np.abs(sa - sb)
+        res.append(np.concatenate([rings.ravel(), np.bincount(d.ravel(), minlength=mp.ORDER_BINS)]).astype(np.uint64))
+    return res
+
+
+ORDER_KEYS = ("tau", "tau_by_ring", "reversed", "flattened", "split", "intact", "distance", "median", "p95")   # order_summary's numbers
+
+
+def order_parts(table):
+    """A flat order table as (rings, histogram): lists of Python ints, 3 x 5 and 97. ValueError for anything but 112 integers."""
+    t = np.asarray(table)
+    if t.shape != (mp.ORDER_TABLE_WORDS,) or t.dtype.kind not in "iu":
+        raise ValueError("an order table is %d integers, got %r %s" % (mp.ORDER_TABLE_WORDS, t.shape, t.dtype))
+    v = [int(x) for x in t]
+    head = mp.ORDER_RINGS * len(mp.ORDER_FIELDS)
+    return [v[r * len(mp.ORDER_FIELDS):(r + 1) * len(mp.ORDER_FIELDS)] for r in range(mp.ORDER_RINGS)], v[head:]
+
+
+def _order_tau(same, rev, flat, split):
+    strict_a, strict_b = same + rev + split, same + rev + flat
+    if strict_a == 0 or strict_b == 0:
+        return 1.0 if strict_a == strict_b else 0.0
+    return (same - rev) / math.sqrt(strict_a * strict_b)
+
+
+def _order_rank(hist, num, den):
+    """The smallest d whose cumulative count reaches num / den of the pixels (nearest rank, integers only)."""
+    total, cum = sum(hist), 0
+    for d, n in enumerate(hist):
+        cum += n
+        if n and cum * den >= total * num:
+            return d
+    return 0
+
+
+def order_summary(table):
+    """What the study reports of a comparison's local order, from order_statistics' (or musica_sim_order's) exact integers of ONE
+    region: one function for every study path. With the sums over the rings N (pairs), S (same), R (reversed), F (flattened), P (split):
+        tau          (S - R) / sqrt((S + R + P)(S + R + F)): Kendall's tau-b restricted to centre-neighbour pairs (the factors are the
+                     pairs strict in a and strict in b); 1.0 where both sides tie everywhere, 0.0 where exactly one does
+        tau_by_ring  the same of each ring alone, three entries
+        reversed     R / (S + R), the share of the pairs ordered on both sides whose order is reversed; 0.0 without such a pair
+        flattened    F / (S + R + F), the share of the pairs strict in b that a ties; 0.0 where b ties everywhere
+        split        P / (N - (S + R + F)), the share of the pairs tied in b that a orders; 0.0 where b ties nowhere
+        intact       hist[0] / pixels, the share of the pixels whose 48 signs all agree
+        distance     the mean census distance / 96
+        median, p95  of d, nearest rank: the smallest d whose cumulative count reaches 1 / 2 and 95 / 100 of the pixels (ints)
+    Every float is one or two correctly rounded operations on exact integers. ValueError for a table without a pixel, or whose
+    histogram and rings disagree (sum hist = pairs / 8, 16, 24; sum d hist[d] = sum 2 R + F + P)."""
+    rings, hist = order_parts(table)
+    pixels = sum(hist)
+    n, s, r, f, p = (sum(row[i] for row in rings) for i in range(5))
+    if pixels <= 0:
+        raise ValueError("the order table holds no pixel")
+    if [row[0] for row in rings] != [pixels * 8 * (k + 1) for k in range(mp.ORDER_RINGS)] or sum(d * v for d, v in enumerate(hist)) != 2 * r + f + p:
+        raise ValueError("the order table's histogram holds %d pixels at a distance sum of %d, its rings %r pairs and %d"
+                         % (pixels, sum(d * v for d, v in enumerate(hist)), [row[0] for row in rings], 2 * r + f + p))
+    strict_b = s + r + f
+    return {"tau": _order_tau(s, r, f, p),
+            "tau_by_ring": [_order_tau(*row[1:]) for row in rings],
+            "reversed": r / (s + r) if s + r else 0.0,
+            "flattened": f / strict_b if strict_b else 0.0,
+            "split": p / (n - strict_b) if n - strict_b else 0.0,
+            "intact": hist[0] / pixels,
+            "distance": (2 * r + f + p) / (96 * pixels),
+            "median": _order_rank(hist, 1, 2),
+            "p95": _order_rank(hist, 95, 100)}
+
+
+def order_row(table):
+    """A row's *_order value: order_summary's dict, "rings", the 3 x 5 exact integers, and "histogram", the 97, as lists."""
+    rings, hist = order_parts(table)
+    return dict(order_summary(table), rings=rings, histogram=hist)
+
+
 # ---- reach: the change of the output by the distance from the changed input (not in the reference's script) ---------------------------
 # The locality relation: a change of the input inside a set changes the output only near it. Two effects carry a local change outwards:
 # the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global stages (min / max,

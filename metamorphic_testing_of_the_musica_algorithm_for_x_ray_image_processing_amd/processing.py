@@ -190,6 +190,8 @@ LEVEL_MIN_SHIFT = 4         # MUSICA_LEVEL_MIN_SHIFT
 LEVEL_MAX_SHIFT = 15        # MUSICA_LEVEL_MAX_SHIFT
 GRADIENT_CLASSES = 22       # MUSICA_GRADIENT_CLASSES: the bit lengths of B <= 1 300 500
 GRADIENT_C = 2720           # MUSICA_GRADIENT_C
+ORDER_RINGS = 3             # MUSICA_ORDER_RINGS: max(|dx|, |dy|) = 1, 2, 3 with 8, 16 and 24 neighbours
+ORDER_BINS = 97             # MUSICA_ORDER_BINS: the census distance d = 0 .. 96
 REACH_MAX_RADII = 32        # MUSICA_REACH_MAX_RADII
 REACH_MAX_RADIUS = 16383    # MUSICA_REACH_MAX_RADIUS
 REACH_MAX_QUERIES = 16      # MUSICA_REACH_MAX_QUERIES
@@ -566,6 +568,15 @@ def reach_radii(radii):
     return np.array(r, dtype=np.uint32)
 
 
+ORDER_FIELDS = ("pairs", "same", "reversed", "flattened", "split")   # the five words of a ring of an order table (MUSICA_ORDER_WORDS)
+ORDER_TABLE_WORDS = ORDER_RINGS * len(ORDER_FIELDS) + ORDER_BINS      # MUSICA_ORDER_TABLE_WORDS = 112
+
+
+class SimOrderResult(C.Structure):
+    """musica_sim_order_result: where a query's table lies in `tables` and the interior's pixel count."""
+    _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64)]
+
+
 class SimDisplaceResult(C.Structure):
     """musica_sim_displace_result: where one comparison's exact block matching puts the output."""
     _fields_ = [("pixels", C.c_uint64), ("ssd_zero", C.c_uint64), ("ssd_min", C.c_uint64), ("dx", C.c_int32), ("dy", C.c_int32),
@@ -782,6 +793,7 @@ ABI = {
     "musica_sim_gradients": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimGradientResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_reach": (C.c_int, [_VP, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimReachResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_reach_classes": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, _U8P]),
+    "musica_sim_order": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimOrderResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -1290,6 +1302,29 @@ class MusicaProcessing:
         for r in res:
             at = int(r.table_offset)
             out.append({"table": tables[at:at + per].reshape(GRADIENT_CLASSES, len(GRADIENT_FIELDS)).copy(), "gsim": float(r.gsim), "pixels": int(r.pixels)})
+        return out
+
+    def sim_order(self, queries):
+        """metrics.order_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 7, 1 .. SIM_MAX_QUERIES of them, all in one launch (ValueError before any call for a count or a side out
+        of range). Returns one dict per query: "rings", a (ORDER_RINGS, 5) uint64 array of the exact pairs, same, reversed, flattened
+        and split (ORDER_FIELDS) per ring of the 7 x 7 neighbourhood, "histogram", the (ORDER_BINS,) uint64 numbers of interior pixels
+        at each census distance 0 .. 96, and the Python int "pixels" = (w - 6) (h - 6)."""
+        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        if not 1 <= len(qs) <= SIM_MAX_QUERIES:
+            raise ValueError("sim_order takes 1 .. %d queries, got %d" % (SIM_MAX_QUERIES, len(qs)))
+        for i, q in enumerate(qs):
+            if q.w < 7 or q.h < 7:
+                raise ValueError("sim_order: query %d: region %d x %d is smaller than 7 x 7" % (i, q.w, q.h))
+        head = ORDER_RINGS * len(ORDER_FIELDS)
+        words = len(qs) * ORDER_TABLE_WORDS
+        arr, res, tables = (SimQuery * len(qs))(*qs), (SimOrderResult * len(qs))(), np.zeros(words, dtype=np.uint64)
+        self._ok(self._lib.musica_sim_order(self._h, len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), words), "musica_sim_order")
+        out = []
+        for r in res:
+            at = int(r.table_offset)
+            out.append({"rings": tables[at:at + head].reshape(ORDER_RINGS, len(ORDER_FIELDS)).copy(),
+                        "histogram": tables[at + head:at + ORDER_TABLE_WORDS].copy(), "pixels": int(r.pixels)})
         return out
 
     def sim_reach(self, queries, radii):

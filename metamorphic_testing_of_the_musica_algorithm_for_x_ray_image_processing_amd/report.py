@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, reach_maps
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -29,6 +29,11 @@ SCALE_CSV_METRICS = ("ssim", "cs", "mse")   # per scale 0 .. 4, behind ms_ssim a
 
 GRADIENT_CSV_GROUPS = (('direct_gradient', 'altered vs unaltered'), ('registered_gradient', 'registered vs unaltered'),
                        ('reference_gradient', 'altered vs reference'), ('registered_reference_gradient', 'registered vs reference'))
+
+# order_robustness.csv: one line per row and comparison the row has, in this order; tau_by_ring spread over three columns
+ORDER_CSV_GROUPS = (('direct_order', 'altered vs unaltered'), ('registered_order', 'registered vs unaltered'),
+                    ('reference_order', 'altered vs reference'), ('registered_reference_order', 'registered vs reference'))
+ORDER_CSV_HEADER = ['raw file', 'alteration', 'comparison'] + [c for k in ORDER_KEYS for c in (['tau ring %d' % (i + 1) for i in range(mp.ORDER_RINGS)] if k == "tau_by_ring" else [k])]
 
 ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
 ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
@@ -161,6 +166,17 @@ def _group_lines(studies, key, groups, cells):
                 yield [raw_name, r["alteration"], label] + cells(d, g)
 
 
+def _order_lines(studies):
+    """order_robustness.csv's lines: one per row and comparison that the row has (ORDER_CSV_GROUPS' order), the unaltered row included:
+    the raw file, the alteration, the comparison, then the ORDER_KEYS with tau_by_ring's three entries in a column each."""
+    for raw_name, rows in studies:
+        for r in rows:
+            for key, label in ORDER_CSV_GROUPS:
+                t = r.get(key)
+                if t is not None:
+                    yield [raw_name, r["alteration"], label] + [c for k in ORDER_KEYS for c in (list(t[k]) if k == "tau_by_ring" else [t[k]])]
+
+
 def _spread_cells(count, keys, stats):
     return lambda d, g: [g[count]] + [g[k][w] for k in keys for w in stats] + [d["outside_mse"]]
 
@@ -206,6 +222,10 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
 
     Studies run with gradients (rows[0] has "direct_gradient") also get gradient_robustness.csv (gradient_csv_header): one line per
     row, the unaltered one included; cells without a comparison, of a gain that has no value and of an empty class are empty.
+
+    Studies run with order (rows[0] has "direct_order") also get order_robustness.csv (ORDER_CSV_HEADER): one line per row, the
+    unaltered one included, and comparison that the row has (none for a comparison that is None): the comparison's name, then
+    order_summary's ORDER_KEYS, tau_by_ring in three columns.
 
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
@@ -281,6 +301,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     for name, header, covered, cells in tables:
         if covered is not None:
             _write_csv(out_dir, name, header, _lines(covered, cells))
+    if having("direct_order"):
+        _write_csv(out_dir, "order_robustness.csv", ORDER_CSV_HEADER, _order_lines(having("direct_order")))
     for name, header, key, groups, cells in RELATION_CSVS:
         if having(key):
             _write_csv(out_dir, name, header, _group_lines(having(key), key, groups, cells))
