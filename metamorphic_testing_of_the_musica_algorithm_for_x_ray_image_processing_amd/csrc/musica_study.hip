@@ -3,7 +3,8 @@
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
 // kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip and kernels_reach.hip. Their state is musica_ctx::study; the pipeline
-// (musica_ctx.hip, musica_step.hip) knows none of it.
+// (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
+// sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
 #include <string.h>
 
@@ -369,6 +370,120 @@ static int alter_into(musica_ctx* c, const char* fn, const char* null, uint32_t 
 }
 static int nothing() { return 1; }
 
+// What musica_sim_compare and musica_sim_joint refuse, in the same words (`what`: the entry point), before any device work.
+// musica_sim_profiles has no window: its smallest side is 1 (min_side) and its largest count max_count.
+static int sim_check_queries(musica_ctx* c, const char* what, uint32_t count, const musica_sim_query* qs, const void* out, uint32_t min_side = 7,
+                             uint32_t max_count = MUSICA_SIM_MAX_QUERIES) {
+    if (!c) return fail("%s: ctx is NULL", what);
+    if (!qs || !out) return fail("%s: queries or results is NULL", what);
+    if (count == 0 || count > max_count) return fail("%s: count %u out of range [1, %u]", what, count, max_count);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("%s: image too small for the %d-pixel margin", what, MUSICA_OUT_MARGIN);
+    const uint64_t nw = sim_side(c);
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_sim_query& q = qs[i];
+        if (q.slot >= MUSICA_SIM_SLOTS) return fail("%s: query %u: slot %u >= %d", what, i, q.slot, MUSICA_SIM_SLOTS);
+        if (!c->study.written[q.slot]) return fail("%s: query %u: slot %u was never written", what, i, q.slot);
+        if ((int)q.image_index >= c->B) return fail("%s: query %u: image_index %u >= batch %d", what, i, q.image_index, c->B);
+        if (min_side == 7 && (q.w < 7 || q.h < 7)) return fail("%s: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", what, i, q.w, q.h);
+        if (q.w < min_side || q.h < min_side) return fail("%s: query %u: region %u x %u has a side below %u", what, i, q.w, q.h, min_side);
+        if ((uint64_t)q.ax + q.w > nw || (uint64_t)q.ay + q.h > nw || (uint64_t)q.bx + q.w > nw || (uint64_t)q.by + q.h > nw)
+            return fail("%s: query %u: region (%u, %u) / (%u, %u) + %u x %u leaves the %llu x %llu planes", what, i, q.ax, q.ay, q.bx, q.by,
+                        q.w, q.h, (unsigned long long)nw, (unsigned long long)nw);
+    }
+    return 1;
+}
+
+// Where a query's two regions lie: a in the graded plane of its image (margin included), b in its slot's plane.
+static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion& d) {
+    d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
+    d.b = c->study.slot[q.slot] + (size_t)q.by * sim_side(c) + q.bx;
+    d.a_pitch = c->lv[0].pitch;
+    d.b_pitch = (int)sim_side(c);
+    d.w = (int)q.w;
+    d.h = (int)q.h;
+}
+
+// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _reach) -----------------------------------------------
+// Where a table call keeps its queries and its flat tables in musica_ctx::study, and what it takes: at most `most` queries with sides
+// of at least `min_side`. The tables' buffer holds `tables_cap` words from the first call on; where `grown` names its capacity it
+// holds the words of the largest call so far instead.
+template <typename QueryDev, typename Word>
+struct TableBuffers {
+    QueryDev* StudyState::*queries;
+    Word* StudyState::*tables;
+    uint32_t most, min_side;
+    size_t tables_cap;
+    size_t StudyState::*grown = nullptr;
+};
+constexpr TableBuffers<ProfileQueryDev, uint32_t> kProfileBuffers{&StudyState::d_profile_q, &StudyState::d_profile_tables, MUSICA_PROFILE_MAX_QUERIES, 1, 0, &StudyState::profile_tables_cap};
+constexpr TableBuffers<LevelQueryDev, unsigned long long> kLevelBuffers{&StudyState::d_level_q, &StudyState::d_level_tables, MUSICA_LEVEL_MAX_QUERIES, 1, (size_t)MUSICA_LEVEL_MAX_QUERIES * kLevelMaxClasses * kLevelWords};
+constexpr TableBuffers<GradQueryDev, unsigned long long> kGradBuffers{&StudyState::d_grad_q, &StudyState::d_grad_tables, MUSICA_SIM_MAX_QUERIES, 7, (size_t)MUSICA_SIM_MAX_QUERIES * kGradClasses * kGradWords};
+constexpr TableBuffers<OrderQueryDev, unsigned long long> kOrderBuffers{&StudyState::d_order_q, &StudyState::d_order_tables, MUSICA_SIM_MAX_QUERIES, 7, (size_t)MUSICA_SIM_MAX_QUERIES * kOrderTableWords};
+constexpr TableBuffers<ReachQueryDev, unsigned long long> kReachBuffers{&StudyState::d_reach_q, &StudyState::d_reach_tables, MUSICA_REACH_MAX_QUERIES, 1, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords};
+
+// What a call's place() says of one query: its tiles or chunks (the launch's grid.x is the largest) and the words of its table.
+struct TablePlace {
+    int units;
+    size_t words;
+};
+
+// The query's grid of MUSICA_SIM_TILE^2 tiles over w x h pixels (its region, or the interior that the kernel tiles), and their number.
+template <typename D>
+static int tile_grid(D& d, uint32_t w, uint32_t h) {
+    d.tiles_x = tiles_along(w);
+    d.tiles_y = tiles_along(h);
+    return d.tiles_x * d.tiles_y;
+}
+
+// The sum of column `col` of a table of `rows` rows of `stride` words: the ssd of a query from its table's sum_dd.
+template <typename Word>
+static uint64_t column_sum(const Word* t, size_t rows, size_t stride, size_t col) {
+    uint64_t sum = 0;
+    for (size_t k = 0; k < rows; k++) sum += t[k * stride + col];
+    return sum;
+}
+
+// The five table calls, in the manner of sim_patch_list: sim_check_queries, then check() (the call's refusals about its other arguments:
+// 1, or fail(...)), then the tables' refusals; no device work so far. place(q, d) fills what query q's device form d holds beyond its
+// regions and its table's place (the tables lie one behind the other). prepare(): the call's other device buffers and what it enqueues
+// before its launch; launch(queries, the largest units, tables) into zeroed tables; fetch(): what it copies back beside the tables (both
+// 1, or fail(...)). One wait for the stream, then finish(i, q, t) fills out[i] behind its table_offset from query i's table t in `tables`.
+template <typename QueryDev, typename Word, typename HostWord, typename Result, typename Check, typename Place, typename Prepare, typename Launch, typename Fetch, typename Finish>
+static int sim_query_tables(musica_ctx* c, const char* fn, const TableBuffers<QueryDev, Word>& bufs, uint32_t count, const musica_sim_query* qs, Result* out,
+                            HostWord* tables, uint64_t table_words, Check check, Place place, Prepare prepare, Launch launch, Fetch fetch, Finish finish) {
+    static_assert(sizeof(HostWord) == sizeof(Word), "the tables come back as the device's words");
+    if (!sim_check_queries(c, fn, count, qs, out, bufs.min_side, bufs.most) || !check()) return 0;
+    if (!tables) return fail("%s: tables is NULL", fn);
+    std::vector<QueryDev> hq(count);
+    size_t words = 0;
+    int max_units = 1;
+    for (uint32_t i = 0; i < count; i++) {
+        sim_region(c, qs[i], hq[i]);
+        hq[i].table = words;
+        const TablePlace at = place(qs[i], hq[i]);
+        max_units = std::max(max_units, at.units);
+        words += at.words;
+    }
+    if (table_words < words) return fail("%s: table_words %llu is less than the %llu words of the tables", fn, (unsigned long long)table_words, (unsigned long long)words);
+    if (!check_ctx(c, fn)) return 0;
+    StudyState& st = c->study;
+    if (!(ensure(c, &(st.*bufs.queries), bufs.most) && (bufs.grown || ensure(c, &(st.*bufs.tables), bufs.tables_cap)))) return fail("%s: device allocation failed", fn);
+    if (bufs.grown && !grow(c, fn, &(st.*bufs.tables), &(st.*bufs.grown), words, "table words")) return 0;
+    if (!prepare()) return 0;
+    HIP_OK(hipMemcpyAsync(st.*bufs.queries, hq.data(), count * sizeof(QueryDev), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(st.*bufs.tables, 0, words * sizeof(Word), c->stream));   // the workgroups add into them
+    launch(st.*bufs.queries, max_units, st.*bufs.tables);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(tables, st.*bufs.tables, words * sizeof(Word), hipMemcpyDeviceToHost, c->stream));
+    if (!fetch()) return 0;
+    HIP_OK(hipStreamSynchronize(c->stream));   // hq, the tables and what fetch() copies are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        out[i].table_offset = hq[i].table;
+        finish(i, qs[i], tables + hq[i].table);
+    }
+    return 1;
+}
+
 // harness.ssim_similarity: c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2 (float ** is C pow); cov_norm = npx / (npx - 1)
 static SimConsts sim_consts() {
     const double k1 = 0.01 * 255, k2 = 0.03 * 255;
@@ -557,39 +672,6 @@ static void sim_finish(const uint32_t* counts /* a 256 | b 256 */, const SimPart
     o->hist_intersection = (double)inter / (double)n;
     o->hist_distance = sqrt(e2) / sqrt(2.0);
     o->hist_bhattacharyya = bc;
-}
-
-// What musica_sim_compare and musica_sim_joint refuse, in the same words (`what`: the entry point), before any device work.
-// musica_sim_profiles has no window: its smallest side is 1 (min_side) and its largest count max_count.
-static int sim_check_queries(musica_ctx* c, const char* what, uint32_t count, const musica_sim_query* qs, const void* out, uint32_t min_side = 7,
-                             uint32_t max_count = MUSICA_SIM_MAX_QUERIES) {
-    if (!c) return fail("%s: ctx is NULL", what);
-    if (!qs || !out) return fail("%s: queries or results is NULL", what);
-    if (count == 0 || count > max_count) return fail("%s: count %u out of range [1, %u]", what, count, max_count);
-    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("%s: image too small for the %d-pixel margin", what, MUSICA_OUT_MARGIN);
-    const uint64_t nw = sim_side(c);
-    for (uint32_t i = 0; i < count; i++) {
-        const musica_sim_query& q = qs[i];
-        if (q.slot >= MUSICA_SIM_SLOTS) return fail("%s: query %u: slot %u >= %d", what, i, q.slot, MUSICA_SIM_SLOTS);
-        if (!c->study.written[q.slot]) return fail("%s: query %u: slot %u was never written", what, i, q.slot);
-        if ((int)q.image_index >= c->B) return fail("%s: query %u: image_index %u >= batch %d", what, i, q.image_index, c->B);
-        if (min_side == 7 && (q.w < 7 || q.h < 7)) return fail("%s: query %u: region %u x %u is smaller than the 7 x 7 SSIM window", what, i, q.w, q.h);
-        if (q.w < min_side || q.h < min_side) return fail("%s: query %u: region %u x %u has a side below %u", what, i, q.w, q.h, min_side);
-        if ((uint64_t)q.ax + q.w > nw || (uint64_t)q.ay + q.h > nw || (uint64_t)q.bx + q.w > nw || (uint64_t)q.by + q.h > nw)
-            return fail("%s: query %u: region (%u, %u) / (%u, %u) + %u x %u leaves the %llu x %llu planes", what, i, q.ax, q.ay, q.bx, q.by,
-                        q.w, q.h, (unsigned long long)nw, (unsigned long long)nw);
-    }
-    return 1;
-}
-
-// Where a query's two regions lie: a in the graded plane of its image (margin included), b in its slot's plane.
-static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion& d) {
-    d.a = image_slice(c, c->d_graded, q.image_index) + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->lv[0].pitch + q.ax + MUSICA_OUT_MARGIN;
-    d.b = c->study.slot[q.slot] + (size_t)q.by * sim_side(c) + q.bx;
-    d.a_pitch = c->lv[0].pitch;
-    d.b_pitch = (int)sim_side(c);
-    d.w = (int)q.w;
-    d.h = (int)q.h;
 }
 
 int musica_sim_compare(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_result* out) {
@@ -939,41 +1021,16 @@ static_assert(kProfileMaxQueries == MUSICA_PROFILE_MAX_QUERIES && kGainOne == MU
 
 int musica_sim_profiles(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_profile_result* out, uint32_t* tables, uint64_t table_words) {
     ABI_TRY
-    if (!sim_check_queries(c, "musica_sim_profiles", count, qs, out, 1, MUSICA_PROFILE_MAX_QUERIES)) return 0;
-    if (!tables) return fail("musica_sim_profiles: tables is NULL");
-    std::vector<ProfileQueryDev> hq(count);
-    size_t words = 0;
-    int max_tiles = 1;
-    for (uint32_t i = 0; i < count; i++) {
-        sim_region(c, qs[i], hq[i]);
-        hq[i].tiles_x = tiles_along(qs[i].w);
-        hq[i].tiles_y = tiles_along(qs[i].h);
-        hq[i].table = words;
-        max_tiles = std::max(max_tiles, hq[i].tiles_x * hq[i].tiles_y);
-        words += 4 * ((size_t)qs[i].w + qs[i].h);
-    }
-    if (table_words < words) return fail("musica_sim_profiles: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
-    CHECK_CTX(c);
-    StudyState& st = c->study;
-    if (!ensure(c, &st.d_profile_q, MUSICA_PROFILE_MAX_QUERIES)) return fail("musica_sim_profiles: device allocation failed");
-    if (!grow(c, "musica_sim_profiles", &st.d_profile_tables, &st.profile_tables_cap, words, "table words")) return 0;
-    HIP_OK(hipMemcpyAsync(st.d_profile_q, hq.data(), count * sizeof(ProfileQueryDev), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemsetAsync(st.d_profile_tables, 0, words * sizeof(uint32_t), c->stream));   // the tiles add into them
-    launch_sim_profiles(c->stream, st.d_profile_q, (int)count, max_tiles, st.d_profile_tables);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(tables, st.d_profile_tables, words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
-    for (uint32_t i = 0; i < count; i++) {
-        const uint32_t* t = tables + hq[i].table;
-        uint64_t ssd = 0;
-        for (uint32_t x = 0; x < qs[i].w; x++) ssd += t[4 * (size_t)x + 2];   // the column table's sum_dd: every pixel once
-        out[i].table_offset = hq[i].table;
-        out[i].cols = qs[i].w;
-        out[i].rows = qs[i].h;
-        out[i].ssd = ssd;
-        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
-    }
-    return 1;
+    return sim_query_tables(
+        c, "musica_sim_profiles", kProfileBuffers, count, qs, out, tables, table_words, nothing,
+        [](const musica_sim_query& q, ProfileQueryDev& d) { return TablePlace{tile_grid(d, q.w, q.h), 4 * ((size_t)q.w + q.h)}; }, nothing,
+        [&](const ProfileQueryDev* d_qs, int max_tiles, uint32_t* d_tables) { launch_sim_profiles(c->stream, d_qs, (int)count, max_tiles, d_tables); }, nothing,
+        [&](uint32_t i, const musica_sim_query& q, const uint32_t* t) {
+            out[i].cols = q.w;
+            out[i].rows = q.h;
+            out[i].ssd = column_sum(t, q.w, 4, 2);   // the column table's sum_dd: every pixel once
+            out[i].pixels = (uint64_t)q.w * q.h;
+        });
     ABI_CATCH("musica_sim_profiles")
 }
 
@@ -984,43 +1041,30 @@ static_assert(kLevelMaxQueries == MUSICA_LEVEL_MAX_QUERIES && kLevelMinShift == 
 
 int musica_sim_levels(musica_ctx* c, uint32_t shift, uint32_t count, const musica_sim_query* qs, musica_sim_level_result* out, uint64_t* tables, uint64_t table_words) {
     ABI_TRY
-    if (!sim_check_queries(c, "musica_sim_levels", count, qs, out, 1, MUSICA_LEVEL_MAX_QUERIES)) return 0;
-    if (!c->study.d_alter_src) return fail("musica_sim_levels: no source plane (musica_alter_set_source)");
-    if (shift < MUSICA_LEVEL_MIN_SHIFT || shift > MUSICA_LEVEL_MAX_SHIFT)
-        return fail("musica_sim_levels: shift %u out of range [%d, %d]", shift, MUSICA_LEVEL_MIN_SHIFT, MUSICA_LEVEL_MAX_SHIFT);
-    if (!tables) return fail("musica_sim_levels: tables is NULL");
-    const size_t classes = (65535u >> shift) + 1, per_query = classes * kLevelWords, words = count * per_query;
-    if (table_words < words) return fail("musica_sim_levels: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
-    CHECK_CTX(c);
-    StudyState& st = c->study;
-    if (!(ensure(c, &st.d_level_q, MUSICA_LEVEL_MAX_QUERIES) && ensure(c, &st.d_level_tables, (size_t)MUSICA_LEVEL_MAX_QUERIES * kLevelMaxClasses * kLevelWords)))
-        return fail("musica_sim_levels: device allocation failed");
-    std::vector<LevelQueryDev> hq(count);
-    int max_chunks = 1;
-    for (uint32_t i = 0; i < count; i++) {
-        sim_region(c, qs[i], hq[i]);
-        hq[i].s = st.d_alter_src + (size_t)(qs[i].ay + MUSICA_OUT_MARGIN) * c->N + qs[i].ax + MUSICA_OUT_MARGIN;   // the class is taken at side a's coordinates
-        hq[i].s_pitch = c->N;
-        hq[i].table = i * per_query;
-        level_geometry(hq[i], (int)count);
-        max_chunks = std::max(max_chunks, hq[i].chunks);
-    }
-    HIP_OK(hipMemcpyAsync(st.d_level_q, hq.data(), count * sizeof(LevelQueryDev), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemsetAsync(st.d_level_tables, 0, words * sizeof(uint64_t), c->stream));   // the workgroups add into them
-    launch_sim_levels(c->stream, st.d_level_q, (int)count, max_chunks, (int)shift, st.d_level_tables);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(tables, st.d_level_tables, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
-    for (uint32_t i = 0; i < count; i++) {
-        const uint64_t* t = tables + hq[i].table;
-        uint64_t ssd = 0;
-        for (size_t k = 0; k < classes; k++) ssd += t[k * kLevelWords + 3];
-        out[i].table_offset = hq[i].table;
-        out[i].classes = classes;
-        out[i].ssd = ssd;
-        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
-    }
-    return 1;
+    size_t classes = 0;   // of a shift that check() has let through
+    return sim_query_tables(
+        c, "musica_sim_levels", kLevelBuffers, count, qs, out, tables, table_words,
+        [&] {
+            if (!c->study.d_alter_src) return fail("musica_sim_levels: no source plane (musica_alter_set_source)");
+            if (shift < MUSICA_LEVEL_MIN_SHIFT || shift > MUSICA_LEVEL_MAX_SHIFT)
+                return fail("musica_sim_levels: shift %u out of range [%d, %d]", shift, MUSICA_LEVEL_MIN_SHIFT, MUSICA_LEVEL_MAX_SHIFT);
+            classes = (65535u >> shift) + 1;
+            return 1;
+        },
+        [&](const musica_sim_query& q, LevelQueryDev& d) {
+            d.s = c->study.d_alter_src + (size_t)(q.ay + MUSICA_OUT_MARGIN) * c->N + q.ax + MUSICA_OUT_MARGIN;   // the class is taken at side a's coordinates
+            d.s_pitch = c->N;
+            level_geometry(d, (int)count);
+            return TablePlace{d.chunks, classes * kLevelWords};
+        },
+        nothing,
+        [&](const LevelQueryDev* d_qs, int max_chunks, unsigned long long* d_tables) { launch_sim_levels(c->stream, d_qs, (int)count, max_chunks, (int)shift, d_tables); },
+        nothing,
+        [&](uint32_t i, const musica_sim_query& q, const uint64_t* t) {
+            out[i].classes = classes;
+            out[i].ssd = column_sum(t, classes, kLevelWords, 3);
+            out[i].pixels = (uint64_t)q.w * q.h;
+        });
     ABI_CATCH("musica_sim_levels")
 }
 
@@ -1030,42 +1074,29 @@ static_assert(kGradClasses == MUSICA_GRADIENT_CLASSES && kGradWords == MUSICA_GR
 
 int musica_sim_gradients(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_gradient_result* out, uint64_t* tables, uint64_t table_words) {
     ABI_TRY
-    if (!sim_check_queries(c, "musica_sim_gradients", count, qs, out)) return 0;
-    if (!tables) return fail("musica_sim_gradients: tables is NULL");
-    const size_t per_query = (size_t)kGradClasses * kGradWords, words = count * per_query;
-    if (table_words < words) return fail("musica_sim_gradients: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
-    std::vector<GradQueryDev> hq(count);
     size_t tiles = 0;
-    int max_tiles = 1;
-    for (uint32_t i = 0; i < count; i++) {
-        sim_region(c, qs[i], hq[i]);
-        hq[i].tiles_x = tiles_along(qs[i].w - 2);   // of the interior
-        hq[i].tiles_y = tiles_along(qs[i].h - 2);
-        hq[i].tile_base = tiles;
-        hq[i].table = i * per_query;
-        tiles += (size_t)hq[i].tiles_x * hq[i].tiles_y;
-        max_tiles = std::max(max_tiles, hq[i].tiles_x * hq[i].tiles_y);
-    }
-    CHECK_CTX(c);
-    StudyState& st = c->study;
-    if (!(ensure(c, &st.d_grad_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_grad_tables, (size_t)MUSICA_SIM_MAX_QUERIES * per_query) &&
-          ensure(c, &st.d_grad_out, MUSICA_SIM_MAX_QUERIES)))
-        return fail("musica_sim_gradients: device allocation failed");
-    if (!grow(c, "musica_sim_gradients", &st.d_grad_part, &st.grad_part_cap, tiles, "tile partials")) return 0;
-    HIP_OK(hipMemcpyAsync(st.d_grad_q, hq.data(), count * sizeof(GradQueryDev), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemsetAsync(st.d_grad_tables, 0, words * sizeof(uint64_t), c->stream));   // the tiles add into them
-    launch_sim_gradients(c->stream, st.d_grad_q, (int)count, max_tiles, st.d_grad_tables, st.d_grad_part, st.d_grad_out);
-    HIP_OK(hipGetLastError());
-    std::vector<double> sums(count);
-    HIP_OK(hipMemcpyAsync(tables, st.d_grad_tables, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(sums.data(), st.d_grad_out, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));   // hq, the tables and the sums are read by then
-    for (uint32_t i = 0; i < count; i++) {
-        out[i].table_offset = hq[i].table;
-        out[i].pixels = (uint64_t)(qs[i].w - 2) * (qs[i].h - 2);
-        out[i].gsim = sums[i] / (double)out[i].pixels;
-    }
-    return 1;
+    std::vector<double> sums;   // lives until sim_query_tables has waited for the stream
+    return sim_query_tables(
+        c, "musica_sim_gradients", kGradBuffers, count, qs, out, tables, table_words, nothing,
+        [&](const musica_sim_query& q, GradQueryDev& d) {
+            d.tile_base = tiles;
+            tiles += (size_t)tile_grid(d, q.w - 2, q.h - 2);   // of the interior
+            return TablePlace{d.tiles_x * d.tiles_y, (size_t)kGradClasses * kGradWords};
+        },
+        [&] {
+            if (!ensure(c, &c->study.d_grad_out, MUSICA_SIM_MAX_QUERIES)) return fail("musica_sim_gradients: device allocation failed");
+            return grow(c, "musica_sim_gradients", &c->study.d_grad_part, &c->study.grad_part_cap, tiles, "tile partials");
+        },
+        [&](const GradQueryDev* d_qs, int max_tiles, unsigned long long* d_tables) { launch_sim_gradients(c->stream, d_qs, (int)count, max_tiles, d_tables, c->study.d_grad_part, c->study.d_grad_out); },
+        [&] {
+            sums.resize(count);
+            HIP_OK(hipMemcpyAsync(sums.data(), c->study.d_grad_out, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            return 1;
+        },
+        [&](uint32_t i, const musica_sim_query& q, const uint64_t*) {
+            out[i].pixels = (uint64_t)(q.w - 2) * (q.h - 2);
+            out[i].gsim = sums[i] / (double)out[i].pixels;
+        });
     ABI_CATCH("musica_sim_gradients")
 }
 
@@ -1076,34 +1107,14 @@ static_assert(kOrderRings == MUSICA_ORDER_RINGS && kOrderWords == MUSICA_ORDER_W
 
 int musica_sim_order(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_order_result* out, uint64_t* tables, uint64_t table_words) {
     ABI_TRY
-    if (!sim_check_queries(c, "musica_sim_order", count, qs, out)) return 0;
-    if (!tables) return fail("musica_sim_order: tables is NULL");
-    const size_t per_query = (size_t)kOrderTableWords, words = count * per_query;
-    if (table_words < words) return fail("musica_sim_order: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
-    std::vector<OrderQueryDev> hq(count);
-    int max_tiles = 1;
-    for (uint32_t i = 0; i < count; i++) {
-        sim_region(c, qs[i], hq[i]);
-        hq[i].tiles_x = tiles_along(qs[i].w - 6);   // of the interior
-        hq[i].tiles_y = tiles_along(qs[i].h - 6);
-        hq[i].table = i * per_query;
-        max_tiles = std::max(max_tiles, hq[i].tiles_x * hq[i].tiles_y);
-    }
-    CHECK_CTX(c);
-    StudyState& st = c->study;
-    if (!(ensure(c, &st.d_order_q, MUSICA_SIM_MAX_QUERIES) && ensure(c, &st.d_order_tables, (size_t)MUSICA_SIM_MAX_QUERIES * per_query)))
-        return fail("musica_sim_order: device allocation failed");
-    HIP_OK(hipMemcpyAsync(st.d_order_q, hq.data(), count * sizeof(OrderQueryDev), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemsetAsync(st.d_order_tables, 0, words * sizeof(uint64_t), c->stream));   // the tiles add into them
-    launch_sim_order(c->stream, st.d_order_q, (int)count, max_tiles, st.d_order_tables);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(tables, st.d_order_tables, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));   // hq and the tables are read by then
-    for (uint32_t i = 0; i < count; i++) {
-        out[i].table_offset = hq[i].table;
-        out[i].pixels = (uint64_t)(qs[i].w - 6) * (qs[i].h - 6);
-    }
-    return 1;
+    return sim_query_tables(
+        c, "musica_sim_order", kOrderBuffers, count, qs, out, tables, table_words, nothing,
+        [](const musica_sim_query& q, OrderQueryDev& d) { return TablePlace{tile_grid(d, q.w - 6, q.h - 6), (size_t)kOrderTableWords}; },   // of the interior
+        nothing, [&](const OrderQueryDev* d_qs, int max_tiles, unsigned long long* d_tables) { launch_sim_order(c->stream, d_qs, (int)count, max_tiles, d_tables); },
+        nothing,
+        [&](uint32_t i, const musica_sim_query& q, const uint64_t*) {
+            out[i].pixels = (uint64_t)(q.w - 6) * (q.h - 6);
+        });
     ABI_CATCH("musica_sim_order")
 }
 
@@ -1142,50 +1153,36 @@ static int reach_table(musica_ctx* c, const char* fn, uint32_t idx, uint32_t rad
 int musica_sim_reach(musica_ctx* c, uint32_t radii_count, const uint32_t* radii, uint32_t count, const musica_sim_query* qs, musica_sim_reach_result* out,
                      uint64_t* tables, uint64_t table_words) {
     ABI_TRY
-    if (!sim_check_queries(c, "musica_sim_reach", count, qs, out, 1, MUSICA_REACH_MAX_QUERIES)) return 0;
-    if (!reach_check(c, "musica_sim_reach", radii_count, radii)) return 0;
-    for (uint32_t i = 1; i < count; i++)
-        if (qs[i].image_index != qs[0].image_index)
-            return fail("musica_sim_reach: query %u names image %u, query 0 image %u: one call, one input plane", i, qs[i].image_index, qs[0].image_index);
-    if (!tables) return fail("musica_sim_reach: tables is NULL");
-    const size_t classes = (size_t)radii_count + 1, per_query = classes * kReachWords, words = count * per_query;
-    if (table_words < words) return fail("musica_sim_reach: table_words %llu is less than the %llu words of the tables", (unsigned long long)table_words, (unsigned long long)words);
-    CHECK_CTX(c);
-    StudyState& st = c->study;
-    if (!(ensure(c, &st.d_reach_q, MUSICA_REACH_MAX_QUERIES) &&
-          ensure(c, &st.d_reach_tables, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords)))
-        return fail("musica_sim_reach: device allocation failed");
-    std::vector<ReachQueryDev> hq(count);
-    int max_tiles = 1;
-    for (uint32_t i = 0; i < count; i++) {
-        sim_region(c, qs[i], hq[i]);
-        hq[i].sx = (int)qs[i].ax + MUSICA_OUT_MARGIN;   // the class is taken at side a's coordinates
-        hq[i].sy = (int)qs[i].ay + MUSICA_OUT_MARGIN;
-        hq[i].tiles_x = tiles_along(qs[i].w);
-        hq[i].tiles_y = tiles_along(qs[i].h);
-        hq[i].table = i * per_query;
-        max_tiles = std::max(max_tiles, hq[i].tiles_x * hq[i].tiles_y);
-    }
-    if (!reach_table(c, "musica_sim_reach", qs[0].image_index, radii_count, radii)) return 0;
-    HIP_OK(hipMemcpyAsync(st.d_reach_q, hq.data(), count * sizeof(ReachQueryDev), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemsetAsync(st.d_reach_tables, 0, words * sizeof(uint64_t), c->stream));   // the tiles add into them
-    launch_sim_reach(c->stream, st.d_reach_q, (int)count, max_tiles, st.d_scatter, c->N, st.d_reach_radii, (int)radii_count, st.d_reach_tables);
-    HIP_OK(hipGetLastError());
+    const size_t classes = (size_t)radii_count + 1;
     uint32_t seeds = 0;
-    HIP_OK(hipMemcpyAsync(tables, st.d_reach_tables, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(&seeds, st.d_scatter + (size_t)c->N * c->N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));   // the table's last entry
-    HIP_OK(hipStreamSynchronize(c->stream));   // hq, radii, the tables and the seeds are read by then
-    for (uint32_t i = 0; i < count; i++) {
-        const uint64_t* t = tables + hq[i].table;
-        uint64_t ssd = 0;
-        for (size_t k = 0; k < classes; k++) ssd += t[k * kReachWords + 4];
-        out[i].table_offset = hq[i].table;
-        out[i].classes = classes;
-        out[i].ssd = ssd;
-        out[i].pixels = (uint64_t)qs[i].w * qs[i].h;
-        out[i].seeds = seeds;
-    }
-    return 1;
+    return sim_query_tables(
+        c, "musica_sim_reach", kReachBuffers, count, qs, out, tables, table_words,
+        [&] {
+            if (!reach_check(c, "musica_sim_reach", radii_count, radii)) return 0;
+            for (uint32_t i = 1; i < count; i++)
+                if (qs[i].image_index != qs[0].image_index)
+                    return fail("musica_sim_reach: query %u names image %u, query 0 image %u: one call, one input plane", i, qs[i].image_index, qs[0].image_index);
+            return 1;
+        },
+        [&](const musica_sim_query& q, ReachQueryDev& d) {
+            d.sx = (int)q.ax + MUSICA_OUT_MARGIN;   // the class is taken at side a's coordinates
+            d.sy = (int)q.ay + MUSICA_OUT_MARGIN;
+            return TablePlace{tile_grid(d, q.w, q.h), classes * kReachWords};
+        },
+        [&] { return reach_table(c, "musica_sim_reach", qs[0].image_index, radii_count, radii); },
+        [&](const ReachQueryDev* d_qs, int max_tiles, unsigned long long* d_tables) {
+            launch_sim_reach(c->stream, d_qs, (int)count, max_tiles, c->study.d_scatter, c->N, c->study.d_reach_radii, (int)radii_count, d_tables);
+        },
+        [&] {   // the summed-area table's last entry
+            HIP_OK(hipMemcpyAsync(&seeds, c->study.d_scatter + (size_t)c->N * c->N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            return 1;
+        },
+        [&](uint32_t i, const musica_sim_query& q, const uint64_t* t) {
+            out[i].classes = classes;
+            out[i].ssd = column_sum(t, classes, kReachWords, 4);
+            out[i].pixels = (uint64_t)q.w * q.h;
+            out[i].seeds = seeds;
+        });
     ABI_CATCH("musica_sim_reach")
 }
 

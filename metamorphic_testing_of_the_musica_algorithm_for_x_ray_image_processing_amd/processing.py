@@ -844,6 +844,11 @@ def _f32p(a):
     return a.ctypes.data_as(_F32P)
 
 
+def _queries(queries):
+    """The queries of a call as SimQuery: one passes through, any other sequence of its eight fields goes through int() field by field."""
+    return [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+
+
 class MusicaProcessing:
     """Drop-in for the reference's VulkanProcessing (one HIP stream on one device per object)."""
 
@@ -1158,7 +1163,7 @@ class MusicaProcessing:
         """queries: (image_index, slot, ax, ay, bx, by, w, h) tuples (or SimQuery), all in one launch. Returns one dict per query:
         harness.similarities()' five numbers plus the exact sq_diff_sum, pixels, bins_a / bins_b (== np.histogram(..., bins=256)[0])
         and the min / max of each side."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        qs = _queries(queries)
         arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimResult * max(len(qs), 1))()
         self._ok(self._lib.musica_sim_compare(self._h, len(qs), arr, res), "musica_sim_compare")
         return [res[i].as_dict() for i in range(len(qs))]
@@ -1247,15 +1252,27 @@ class MusicaProcessing:
         return {"points": [r.as_dict() for r in res],
                 "groups": [dict({"count": sum(1 for p in ps if p[5] == g)}, **{k: stacks[g, i] for i, k in enumerate(POINT_STACKS)}) for g in range(groups)]}
 
+    def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False):
+        """What sim_profiles / _levels / _gradients / _order / _reach share: the refusals of sim_<name> before any call (most: 1 .. most
+        queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead` in front of
+        the count. Returns the results and the flat tables, `words` zeroed words of `dtype`."""
+        if most is not None and not 1 <= len(qs) <= most:
+            raise ValueError("sim_%s takes 1 .. %d queries, got %d" % (name, most, len(qs)))
+        for i, q in enumerate(qs if window else ()):
+            if q.w < 7 or q.h < 7:
+                raise ValueError("sim_%s: query %d: region %d x %d is smaller than 7 x 7" % (name, i, q.w, q.h))
+        arr, res, tables = (SimQuery * max(len(qs), 1))(*qs), (result_type * max(len(qs), 1))(), np.zeros(max(words, 1), dtype=dtype)
+        call = getattr(self._lib, "musica_sim_" + name)
+        self._ok(call(self._h, *lead, len(qs), arr, res, tables.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), words), "musica_sim_" + name)
+        return res, tables
+
     def sim_profiles(self, queries):
         """harness.profile_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
         SimQuery) with w, h >= 1, at most PROFILE_MAX_QUERIES, all in one launch. Returns one dict per query: "cols", a (w, 4) uint32
         array, and "rows", (h, 4): per line the exact sum_a, sum_b, sum_dd = sum of (a - b)^2 and sum_aa (PROFILE_SUMS) over the line's
         pixels inside the region; and the Python ints "ssd" (the sum of either table's sum_dd) and "pixels"."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
-        words = sum(4 * (int(q.w) + int(q.h)) for q in qs)
-        arr, res, tables = (SimQuery * max(len(qs), 1))(*qs), (SimProfileResult * max(len(qs), 1))(), np.zeros(max(words, 1), dtype=np.uint32)
-        self._ok(self._lib.musica_sim_profiles(self._h, len(qs), arr, res, tables.ctypes.data_as(_U32P), words), "musica_sim_profiles")
+        qs = _queries(queries)
+        res, tables = self._sim_tables("profiles", qs, SimProfileResult, np.uint32, sum(4 * (int(q.w) + int(q.h)) for q in qs))
         out = []
         for r in res[:len(qs)]:
             at, w, h = int(r.table_offset), int(r.cols), int(r.rows)
@@ -1270,12 +1287,8 @@ class MusicaProcessing:
         Returns one dict per query: "table", a (classes, 6) uint64 array of the exact n, sum_a, sum_b, sum_dd = sum of (a - b)^2, sum_aa
         and sum_bb (LEVEL_SUMS) per class, and the Python ints "classes", "ssd" (the sum of sum_dd) and "pixels"."""
         classes = level_count(shift)
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
-        if not 1 <= len(qs) <= LEVEL_MAX_QUERIES:
-            raise ValueError("sim_levels takes 1 .. %d queries, got %d" % (LEVEL_MAX_QUERIES, len(qs)))
-        words = len(qs) * classes * len(LEVEL_SUMS)
-        arr, res, tables = (SimQuery * len(qs))(*qs), (SimLevelResult * len(qs))(), np.zeros(words, dtype=np.uint64)
-        self._ok(self._lib.musica_sim_levels(self._h, int(shift), len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), words), "musica_sim_levels")
+        qs = _queries(queries)
+        res, tables = self._sim_tables("levels", qs, SimLevelResult, np.uint64, len(qs) * classes * len(LEVEL_SUMS), int(shift), most=LEVEL_MAX_QUERIES)
         out = []
         for r in res:
             at, c = int(r.table_offset), int(r.classes)
@@ -1288,16 +1301,9 @@ class MusicaProcessing:
         of range). Returns one dict per query: "table", a (GRADIENT_CLASSES, 6) uint64 array of the exact n, sum_A, sum_B, sum_dot,
         sum_cross (both signed, two's complement) and neg (GRADIENT_FIELDS) per class of the reference side's edge strength, "gsim", the
         mean of q over the interior, and the Python int "pixels" = (w - 2) (h - 2)."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
-        if not 1 <= len(qs) <= SIM_MAX_QUERIES:
-            raise ValueError("sim_gradients takes 1 .. %d queries, got %d" % (SIM_MAX_QUERIES, len(qs)))
-        for i, q in enumerate(qs):
-            if q.w < 7 or q.h < 7:
-                raise ValueError("sim_gradients: query %d: region %d x %d is smaller than 7 x 7" % (i, q.w, q.h))
+        qs = _queries(queries)
         per = GRADIENT_CLASSES * len(GRADIENT_FIELDS)
-        words = len(qs) * per
-        arr, res, tables = (SimQuery * len(qs))(*qs), (SimGradientResult * len(qs))(), np.zeros(words, dtype=np.uint64)
-        self._ok(self._lib.musica_sim_gradients(self._h, len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), words), "musica_sim_gradients")
+        res, tables = self._sim_tables("gradients", qs, SimGradientResult, np.uint64, len(qs) * per, most=SIM_MAX_QUERIES, window=True)
         out = []
         for r in res:
             at = int(r.table_offset)
@@ -1310,16 +1316,9 @@ class MusicaProcessing:
         of range). Returns one dict per query: "rings", a (ORDER_RINGS, 5) uint64 array of the exact pairs, same, reversed, flattened
         and split (ORDER_FIELDS) per ring of the 7 x 7 neighbourhood, "histogram", the (ORDER_BINS,) uint64 numbers of interior pixels
         at each census distance 0 .. 96, and the Python int "pixels" = (w - 6) (h - 6)."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
-        if not 1 <= len(qs) <= SIM_MAX_QUERIES:
-            raise ValueError("sim_order takes 1 .. %d queries, got %d" % (SIM_MAX_QUERIES, len(qs)))
-        for i, q in enumerate(qs):
-            if q.w < 7 or q.h < 7:
-                raise ValueError("sim_order: query %d: region %d x %d is smaller than 7 x 7" % (i, q.w, q.h))
+        qs = _queries(queries)
         head = ORDER_RINGS * len(ORDER_FIELDS)
-        words = len(qs) * ORDER_TABLE_WORDS
-        arr, res, tables = (SimQuery * len(qs))(*qs), (SimOrderResult * len(qs))(), np.zeros(words, dtype=np.uint64)
-        self._ok(self._lib.musica_sim_order(self._h, len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), words), "musica_sim_order")
+        res, tables = self._sim_tables("order", qs, SimOrderResult, np.uint64, len(qs) * ORDER_TABLE_WORDS, most=SIM_MAX_QUERIES, window=True)
         out = []
         for r in res:
             at = int(r.table_offset)
@@ -1335,14 +1334,9 @@ class MusicaProcessing:
         sum_dd = sum of (a - b)^2 and max_d = max |a - b| (REACH_FIELDS) per class, and the Python ints "classes", "ssd" (the sum of
         sum_dd), "pixels" and "seeds" (the changed pixels of the whole N x N input plane)."""
         r = reach_radii(radii)
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
-        if not 1 <= len(qs) <= REACH_MAX_QUERIES:
-            raise ValueError("sim_reach takes 1 .. %d queries, got %d" % (REACH_MAX_QUERIES, len(qs)))
-        per = (len(r) + 1) * len(REACH_FIELDS)
-        words = len(qs) * per
-        arr, res, tables = (SimQuery * len(qs))(*qs), (SimReachResult * len(qs))(), np.zeros(words, dtype=np.uint64)
-        self._ok(self._lib.musica_sim_reach(self._h, len(r), r.ctypes.data_as(_U32P), len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), words),
-                 "musica_sim_reach")
+        qs = _queries(queries)
+        words = len(qs) * (len(r) + 1) * len(REACH_FIELDS)
+        res, tables = self._sim_tables("reach", qs, SimReachResult, np.uint64, words, len(r), r.ctypes.data_as(_U32P), most=REACH_MAX_QUERIES)
         out = []
         for q in res:
             at, c = int(q.table_offset), int(q.classes)
@@ -1371,7 +1365,7 @@ class MusicaProcessing:
         numbers but tone_ssim), the entropies h_a, h_b, h_ab, the exact pixels and sq_diff_sum, tone_lut ((256,) uint8: the least-squares
         remap of the slot's gray levels onto the image's) and, with tables=True, "joint": the (256, 256) uint32 counts, row a, column b
         (== harness.joint_histogram)."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        qs = _queries(queries)
         arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimJointResult * max(len(qs), 1))()
         joint = np.empty((max(len(qs), 1), 256, 256), dtype=np.uint32) if tables else None
         self._ok(self._lib.musica_sim_joint(self._h, len(qs), arr, res, joint.ctypes.data_as(_U32P) if tables else None), "musica_sim_joint")
@@ -1388,7 +1382,7 @@ class MusicaProcessing:
         then smallest dx), tiles_x, tiles_y and tiles_off (the 64 x 64 tiles whose own best shift is not (0, 0)); with tables=True "table":
         the (S, S) uint64 sums, row dy, column dx, S = 2 radius + 1; with tiles=True "tile_tables": the (tiles_y, tiles_x, S, S) uint32 sums
         of the tiles. The slot's window grown by `radius` must lie inside the plane."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        qs = _queries(queries)
         if not 0 <= int(radius) < 2 ** 32:
             raise ValueError("radius %r is not in 1 .. %d" % (radius, SIM_MAX_RADIUS))
         s = 2 * min(int(radius), SIM_MAX_RADIUS) + 1   # a radius beyond the range is refused by the call: the arrays only have to exist
@@ -1416,7 +1410,7 @@ class MusicaProcessing:
         block sums of both sides, == harness.multiscale_similarities. Returns one dict per query: ms_ssim, scales, pixels, the lists
         ssim, cs, lum, mse (SCALE_METRICS), ssd (exact), plane_w, plane_h of length `scales`, and "raw": those arrays at their full
         length (zero beyond `scales`). min(w, h) >> (scales - 1) must be at least 7."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        qs = _queries(queries)
         if not 0 <= int(scales) < 2 ** 32:
             raise ValueError("scales %r is not in 1 .. %d" % (scales, SIM_MAX_SCALES))
         arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimScalesResult * max(len(qs), 1))()
@@ -1446,7 +1440,7 @@ class MusicaProcessing:
         """queries as sim_compare's (image_index is checked and not used: side a is the ensemble), all in one launch. Returns one dict per
         query: the doubles ENSEMBLE_METRICS and the exact ENSEMBLE_INTEGERS (== harness.ensemble_statistics); with tiles=True
         "tile_tables": the (tiles_y, tiles_x, 2) uint64 pairs (sum D^2, sum V) of the 64 x 64 tiles."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in queries]
+        qs = _queries(queries)
         arr, res = (SimQuery * max(len(qs), 1))(*qs), (SimEnsembleResult * max(len(qs), 1))()
         tile = None
         if tiles:
@@ -1476,7 +1470,7 @@ class MusicaProcessing:
         the ensemble now starting, after sim_ensemble_reset and before the first add: every later sim_ensemble_add also accumulates the
         lag products of those regions for the lags dy = 0 .. radius, dx = -radius .. radius. A region grown by `radius` to the left, to
         the right and downwards must lie inside the plane. sim_ensemble_reset drops the tracking."""
-        qs = [q if isinstance(q, SimQuery) else SimQuery(*[int(v) for v in q]) for q in regions]
+        qs = _queries(regions)
         if not 0 <= int(radius) < 2 ** 32:
             raise ValueError("radius %r is not in 1 .. %d" % (radius, SIM_MAX_RADIUS))
         arr = (SimQuery * max(len(qs), 1))(*qs)
