@@ -1217,6 +1217,52 @@ int musica_alter_points(musica_ctx* ctx, uint32_t image_index, uint32_t count, c
 int musica_sim_points(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t count, const musica_defect* points, uint32_t groups,
                       musica_sim_point_result* results, uint32_t* tables, uint64_t table_words);
 
+/* ---- model observer: the channel responses of patches (new, not in the reference) ----
+ * Task-based assessment puts a model observer on top of MTF, noise power and contrast-detail: it looks at a patch through a few
+ * smooth channels and reports how well a signal is told from its absence against the background the processor produced (a
+ * channelized Hotelling observer with Laguerre-Gauss channels: metrics.laguerre_gauss_bank, metrics.observer_summary). The device
+ * does the expensive part, the inner products of many windows with a bank of templates; metrics.channel_responses is the contract,
+ * and everything the device computes is integer and bit-identical to it, from call to call as well (no float, no atomics).
+ * A bank is {half, channels, weights}: 1 <= half <= MUSICA_OBSERVER_MAX_HALF, the window |dx|, |dy| <= half of side S = 2 half + 1;
+ * 1 <= channels C <= MUSICA_OBSERVER_MAX_CHANNELS; weights[C][S][S], row-major ([j][dy + half][dx + half]), the full int8 range. A
+ * view is (x, y, bank): an integer centre in the (N - 20)^2 output plane and the index of its bank. A call holds 1 ..
+ * MUSICA_OBSERVER_MAX_BANKS banks and 1 .. MUSICA_OBSERVER_MAX_VIEWS views whose windows lie inside the plane; they MAY overlap and
+ * views may repeat (the call only reads). Side a is the 8-bit output of batch image `image_index`, quantised while read exactly as
+ * musica_sim_compare reads it; side b is reference slot `slot`. View i gets 2 C int32_t in the flat `tables`, from
+ * results[i].table_offset (in words; the tables lie one behind the other in view order) on: first the side-a responses
+ *   R_a[j] = sum over dy, dx of weights[j][dy + half][dx + half] * a(x + dx, y + dy),   j = 0 .. C - 1,
+ * then R_b[j] likewise; results[i].sum_a and sum_b are the window's plain sums. |R| <= 255 * 128 * 133^2 = 577 368 960 < 2^31 (asserted
+ * below), so int32_t is exact. Every word of the tables is written and nothing behind them. Synchronous, on the context's stream
+ * after whatever was enqueued there; changes no slot, no result of a step and no input image; scratch is allocated on first use.
+ * One launch, one workgroup per view and block of 8 channels (kernels_observer.hip). Refused before any device work: a NULL context,
+ * banks, views, results or tables; an image too small for the margin; a slot out of range or never written; image_index >= batch;
+ * bank_count outside 1 .. MUSICA_OBSERVER_MAX_BANKS; a bank with NULL weights, or a half or channel count outside its limits; count
+ * outside 1 .. MUSICA_OBSERVER_MAX_VIEWS; a view whose bank is not below bank_count or whose window leaves the plane; table_words
+ * below the tables' total. After a refusal the context stays usable. */
+#define MUSICA_OBSERVER_MAX_VIEWS 1024
+#define MUSICA_OBSERVER_MAX_BANKS 8
+#define MUSICA_OBSERVER_MAX_CHANNELS 16
+#define MUSICA_OBSERVER_MAX_HALF 66          /* 2 * 32 + 2: the box of a radius-32 detail */
+#ifdef __cplusplus
+static_assert(255ll * 128 * (2 * MUSICA_OBSERVER_MAX_HALF + 1) * (2 * MUSICA_OBSERVER_MAX_HALF + 1) < (1ll << 31), "a channel response is an exact int32_t");
+#endif
+typedef struct musica_channel_bank {
+    uint32_t half;                  /* 1 .. MUSICA_OBSERVER_MAX_HALF: the window |dx|, |dy| <= half, side S = 2 half + 1 */
+    uint32_t channels;              /* 1 .. MUSICA_OBSERVER_MAX_CHANNELS */
+    const int8_t* weights;          /* [channels][S][S], row-major, the full int8 range */
+} musica_channel_bank;
+typedef struct musica_view {
+    int32_t x, y;                   /* the centre, in pixels of the output plane */
+    uint32_t bank;                  /* 0 .. bank_count - 1 */
+} musica_view;
+typedef struct musica_sim_observer_result {
+    uint64_t table_offset;          /* where the view's 2 x channels int32_t start in `tables`, in words */
+    uint32_t pixels;                /* S^2 */
+    uint32_t sum_a, sum_b;          /* the window's plain sums (<= 255 * 17689) */
+} musica_sim_observer_result;
+int musica_sim_observer(musica_ctx* ctx, uint32_t image_index, uint32_t slot, uint32_t bank_count, const musica_channel_bank* banks,
+                        uint32_t count, const musica_view* views, musica_sim_observer_result* results, int32_t* tables, uint64_t table_words);
+
 /* ---- device-resident output and stream ordering (new, not in the reference) ---- */
 
 /* What musica_export_out writes per image. */

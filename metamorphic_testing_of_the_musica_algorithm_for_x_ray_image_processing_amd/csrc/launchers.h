@@ -508,6 +508,29 @@ int point_plan(const PackedPoint* points, int count, std::vector<uint32_t>& plan
 // `radius`; results: count x kPointWords u64, all written; tables: [groups][3][(2 radius + 1)^2] u32, zeroed here on the stream
 void launch_sim_points(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedPoint* d_points, int count, int radius,
                        int groups, const uint32_t* plan, int chunks, uint32_t* d_plan, unsigned long long* results, uint32_t* tables);
+// kernels_observer.hip: the model-observer relation. A view (x, y, bank) of a list that the caller has checked (limits, windows inside
+// the plane; they may overlap), with what the kernel needs of its bank.
+constexpr int kObserverMaxViews = 1024;      // MUSICA_OBSERVER_MAX_VIEWS
+constexpr int kObserverMaxBanks = 8;         // MUSICA_OBSERVER_MAX_BANKS
+constexpr int kObserverMaxChannels = 16;     // MUSICA_OBSERVER_MAX_CHANNELS
+constexpr int kObserverMaxHalf = 66;         // MUSICA_OBSERVER_MAX_HALF
+constexpr int kObserverBlock = 8;            // channels of one workgroup of k_observer
+struct PackedView {
+    int32_t x, y;        // the centre
+    uint32_t half;       // of its bank
+    uint32_t channels;   // of its bank
+    uint32_t weights;    // where its bank's words start in the call's packed weights
+    uint32_t table;      // where its 2 x channels int32 start in the flat tables, in words
+};
+// Appends a bank's weights[channels][S][S] (S = 2 half + 1) to `words` as k_observer reads them (host): [channels][S][ceil(S / 4)]
+// words of four weights each, biased to u8 (w + 128), the pad bytes of a row's last word 0
+void observer_pack(const int8_t* weights, int half, int channels, std::vector<uint32_t>& words);
+// metrics.channel_responses: one workgroup per view and block of kObserverBlock channels (max_channels: the largest count of the
+// call's banks). a_plane: the graded f32 plane at output pixel (0, 0), b_plane: the slot's u8 plane, pitches in elements, the views in
+// the cropped output plane's coordinates; tables: every view's 2 x channels int32 from its PackedView::table on, sums: count x 2 u32
+// (the window's plain sums of a and b), all written
+void launch_sim_observer(hipStream_t st, const float* a_plane, int a_pitch, const uint8_t* b_plane, int b_pitch, const PackedView* d_views, int count,
+                         int max_channels, const uint32_t* d_weights, int32_t* tables, uint32_t* sums);
 // kernels_bench.hip (measurement aid)
 void launch_copy41(hipStream_t st, const float* in, float* out, int side);
 // kernels_clahe.hip

@@ -180,6 +180,12 @@ struct StudyState {
     PackedPoint* d_points = nullptr;               // [MUSICA_POINT_MAX + kPointTileRows] (point_rows' entries behind an insertion's list), allocated by the first call of either
     unsigned long long* d_point_out = nullptr;     // [MUSICA_POINT_MAX][kPointWords], allocated by the first musica_sim_points
     uint32_t* d_point_tables = nullptr;            // [kPointTableWords] stacks (792 KiB), then [kPointPlanWords] of point_plan, allocated likewise
+    // musica_sim_observer: the device copy of the call's views, its banks' packed weights, the flat tables and the windows' plain sums
+    PackedView* d_obs_views = nullptr;             // [MUSICA_OBSERVER_MAX_VIEWS], allocated by the first call
+    uint32_t* d_obs_weights = nullptr;             // observer_pack's words of one call: obs_weights_cap u32, regrown when a call needs more
+    size_t obs_weights_cap = 0;
+    int32_t* d_obs_tables = nullptr;               // [MUSICA_OBSERVER_MAX_VIEWS][2][MUSICA_OBSERVER_MAX_CHANNELS] (128 KiB), allocated by the first call
+    uint32_t* d_obs_sums = nullptr;                // [MUSICA_OBSERVER_MAX_VIEWS][2], likewise
 };
 
 struct musica_ctx : DeviceBuffers {

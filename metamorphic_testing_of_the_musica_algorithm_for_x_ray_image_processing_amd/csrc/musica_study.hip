@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip and kernels_reach.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
 // sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
@@ -1014,6 +1014,81 @@ int musica_sim_points(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t count
         },
         out, tables, table_words);
     ABI_CATCH("musica_sim_points")
+}
+
+// ---- the channel responses of patches (musica_sim_observer, include/musica.h; kernels_observer.hip) ---------------------------------------
+static_assert(kObserverMaxViews == MUSICA_OBSERVER_MAX_VIEWS && kObserverMaxBanks == MUSICA_OBSERVER_MAX_BANKS && kObserverMaxChannels == MUSICA_OBSERVER_MAX_CHANNELS &&
+                  kObserverMaxHalf == MUSICA_OBSERVER_MAX_HALF,
+              "kernels_observer.hip's u32 partials and int32 responses hold for the banks of include/musica.h");
+
+// A plain body in sim_patch_list's order and words: that frame refuses windows that overlap, which views may, and carries one list.
+int musica_sim_observer(musica_ctx* c, uint32_t idx, uint32_t slot, uint32_t bank_count, const musica_channel_bank* banks, uint32_t count, const musica_view* views,
+                        musica_sim_observer_result* out, int32_t* tables, uint64_t table_words) {
+    ABI_TRY
+    const char* fn = "musica_sim_observer";
+    if (!c) return fail("%s: ctx is NULL", fn);
+    if (!banks || !views || !out || !tables) return fail("%s: banks, views, results or tables is NULL", fn);
+    if (c->N <= 2 * MUSICA_OUT_MARGIN) return fail("%s: image too small for the %d-pixel margin", fn, MUSICA_OUT_MARGIN);
+    if (slot >= MUSICA_SIM_SLOTS) return fail("%s: slot %u >= %d", fn, slot, MUSICA_SIM_SLOTS);
+    if (!c->study.written[slot]) return fail("%s: slot %u was never written", fn, slot);
+    if (!check_img(c, fn, idx)) return 0;
+    if (bank_count == 0 || bank_count > MUSICA_OBSERVER_MAX_BANKS) return fail("%s: bank_count %u out of range [1, %d]", fn, bank_count, MUSICA_OBSERVER_MAX_BANKS);
+    uint32_t max_channels = 0;
+    for (uint32_t k = 0; k < bank_count; k++) {
+        const musica_channel_bank& b = banks[k];
+        if (!b.weights) return fail("%s: bank %u: weights is NULL", fn, k);
+        if (b.half < 1 || b.half > MUSICA_OBSERVER_MAX_HALF) return fail("%s: bank %u: half %u out of range [1, %d]", fn, k, b.half, MUSICA_OBSERVER_MAX_HALF);
+        if (b.channels < 1 || b.channels > MUSICA_OBSERVER_MAX_CHANNELS)
+            return fail("%s: bank %u: channels %u out of range [1, %d]", fn, k, b.channels, MUSICA_OBSERVER_MAX_CHANNELS);
+        max_channels = std::max(max_channels, b.channels);
+    }
+    if (count == 0 || count > MUSICA_OBSERVER_MAX_VIEWS) return fail("%s: count %u out of range [1, %d]", fn, count, MUSICA_OBSERVER_MAX_VIEWS);
+    const int n = (int)sim_side(c);
+    std::vector<PackedView> packed(count);
+    uint64_t words = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        const musica_view& v = views[i];
+        if (v.bank >= bank_count) return fail("%s: view %u: bank %u is not below %u", fn, i, v.bank, bank_count);
+        const int64_t r = banks[v.bank].half;
+        if (v.x - r < 0 || v.y - r < 0 || v.x + r >= n || v.y + r >= n)
+            return fail("%s: view %u: the window (%d, %d) +- %d leaves the %d x %d plane", fn, i, v.x, v.y, (int)r, n, n);
+        packed[i] = {v.x, v.y, banks[v.bank].half, banks[v.bank].channels, 0u, (uint32_t)words};
+        words += 2ull * banks[v.bank].channels;
+    }
+    if (table_words < words)
+        return fail("%s: table_words %llu is less than the %llu words of the tables", fn, (unsigned long long)table_words, (unsigned long long)words);
+    // the banks as the kernel reads them, one behind the other, once per call
+    std::vector<uint32_t> weights;
+    std::vector<uint32_t> bank_at(bank_count);
+    for (uint32_t k = 0; k < bank_count; k++) {
+        bank_at[k] = (uint32_t)weights.size();
+        observer_pack(banks[k].weights, (int)banks[k].half, (int)banks[k].channels, weights);
+    }
+    for (uint32_t i = 0; i < count; i++) packed[i].weights = bank_at[views[i].bank];
+    if (!check_ctx(c, fn)) return 0;
+    StudyState& st = c->study;
+    if (!(ensure(c, &st.d_obs_views, (size_t)MUSICA_OBSERVER_MAX_VIEWS) &&
+          ensure(c, &st.d_obs_tables, (size_t)MUSICA_OBSERVER_MAX_VIEWS * 2 * MUSICA_OBSERVER_MAX_CHANNELS) &&
+          ensure(c, &st.d_obs_sums, (size_t)MUSICA_OBSERVER_MAX_VIEWS * 2)))
+        return fail("%s: device allocation failed", fn);
+    if (!grow(c, fn, &st.d_obs_weights, &st.obs_weights_cap, weights.size(), "weight words")) return 0;
+    // on the stream, behind the kernel that still reads the last call's
+    HIP_OK(hipMemcpyAsync(st.d_obs_views, packed.data(), count * sizeof(PackedView), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(st.d_obs_weights, weights.data(), weights.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const int pitch = c->lv[0].pitch;
+    launch_sim_observer(c->stream, image_slice(c, c->d_graded, idx) + (size_t)MUSICA_OUT_MARGIN * pitch + MUSICA_OUT_MARGIN, pitch, st.slot[slot], n, st.d_obs_views,
+                        (int)count, (int)max_channels, st.d_obs_weights, st.d_obs_tables, st.d_obs_sums);
+    HIP_OK(hipGetLastError());
+    std::vector<uint32_t> sums(2 * (size_t)count);
+    HIP_OK(hipMemcpyAsync(tables, st.d_obs_tables, (size_t)words * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(sums.data(), st.d_obs_sums, sums.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // packed, weights, the tables and the sums are read by then
+    for (uint32_t i = 0; i < count; i++) {
+        const uint32_t side = 2 * packed[i].half + 1;
+        out[i] = {packed[i].table, side * side, sums[2 * i], sums[2 * i + 1]};
+    }
+    return 1;
+    ABI_CATCH("musica_sim_observer")
 }
 
 // ---- the profiles of a comparison (musica_sim_profiles, include/musica.h; kernels_gain.hip) ---------------------------------------------

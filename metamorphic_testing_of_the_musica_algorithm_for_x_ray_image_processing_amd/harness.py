@@ -998,7 +998,7 @@ RELATIONS = (
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
-                  gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, order=False):
+                  gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1017,6 +1017,10 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         raise ValueError("gradients is a flag, got %r" % (gradients,))
     if not isinstance(order, (bool, np.bool_)):
         raise ValueError("order is a flag, got %r" % (order,))
+    if not isinstance(observer, (bool, np.bool_)):
+        raise ValueError("observer is a flag, got %r" % (observer,))
+    if observer and details is None:
+        raise ValueError("the observer looks at the details of the cd_ rows: give details")
     if reach is None or reach is False:
         reach = None
     else:
@@ -1054,16 +1058,18 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     for rel in RELATIONS:
         if given[rel.option] is not None:
             given[rel.option] = rel.check(given[rel.option], n)
+    for g in (given["details"] if observer else ()):   # the views and banks of every grid, as the measurement will take them
+        mp.view_list(*observer_views(output_details(g)), n - 2 * PROCESSING_MARGIN)
     compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
            (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + (tuple(ORDER_ROW_KEYS[k] for k in compared) if order else ()) + (("direct_reach",) if reach is not None else ()) + \
-           (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("warp",) if warps else ())
+           (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("observer",) if observer else ()) + (("warp",) if warps else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
-        displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), order=bool(order), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
+        displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), order=bool(order), observer=bool(observer), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
         grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), reach=reach, reach_tables=bool(reach_tables), reach_maps=bool(reach_maps), keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
@@ -1130,7 +1136,7 @@ def study_alterations(raw, rng, p, seed, shape, opt):
 class Scorer:
     """How run_study scores a row, on the host or on the device. produce(alteration) makes the altered output the one that is scored
     (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
-    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key; similarities, tone, scales, gradients, order and shifts take the row's comparisons, (reference key, region)
+    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key and observer(details) a cd_ row's "observer"; similarities, tone, scales, gradients, order and shifts take the row's comparisons, (reference key, region)
     pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset; keep: the dicts carry their
     tile tables whatever displacement_tiles says, for a warp row's tracking); reach takes the row's direct comparison, behind
     similarities, and looks at the change of the input from `source`, the study's raw plane."""
@@ -1188,6 +1194,11 @@ class DeviceScorer(Scorer):
         direct = self.compared[0]
         frame = (direct["sq_diff_sum"], direct["pixels"]) if relation.frame else ()
         return relation.summarise(measured, relation.device(self.proc, measured, self.unalt.shape), *frame, getattr(self.opt, relation.tables))
+
+    def observer(self, details):
+        """One musica_sim_observer call behind the row's musica_sim_details: the details' views against the unaltered result."""
+        views, banks = observer_views(details)
+        return observer_row(details, self.proc.sim_observer(views, banks, SLOT_UNALTERED))
 
     def tone(self, comparisons):
         """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
@@ -1268,6 +1279,10 @@ class HostScorer(Scorer):
             a, b = self.out.astype(np.int64), self.planes[SLOT_UNALTERED].astype(np.int64)
             frame = (int(((a - b) ** 2).sum()), a.size)
         return relation.summarise(measured, relation.host(self.out, self.planes[SLOT_UNALTERED], measured), *frame, getattr(self.opt, relation.tables))
+
+    def observer(self, details):
+        views, banks = observer_views(details)
+        return observer_row(details, channel_responses(self.out, self.planes[SLOT_UNALTERED], views, banks))
 
     def tone(self, comparisons):
         return [tone_similarities(*self.sides(*c)) for c in comparisons]
@@ -1351,7 +1366,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False, order=False):
+              reach_tables=False, reach_maps=False, observer=False, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1575,12 +1590,23 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     the radius of half the spill and the decay slope (reach_summary). Host and device summarise exact integers with one function, so
     the dict is equal to the last bit on every path. reach_tables: the dict also carries "table". reach_maps: it also carries "class_plane",
     the (N - 20)^2 classes of the output's pixels (on the device one musica_sim_reach_classes call more), what write_reach_maps draws. Nothing is asserted: how far the
-    pyramid carries a local change, and how much of it the global stages spread over the whole frame, are the finding."""
+    pyramid carries a local change, and how much of it the global stages spread over the whole frame, are the finding.
+
+    observer: True (needs details, else ValueError; anything but a bool is one too) puts a model observer on the cd_ rows: a channelized
+    Hotelling observer with Laguerre-Gauss channels (laguerre_gauss_bank, observer_summary). Every row of the study gains "observer"
+    behind the relations' keys: None except in the cd_ rows, where it is observer_row's dict of the details' windows against the
+    unaltered result at the details' output positions, one bank per distinct radius (observer_views; channel_responses, on the device
+    one musica_sim_observer call behind the row's musica_sim_details): per radius the count, the detectability cho with its auc, the
+    non-prewhitening npw on the disc channel, the spread of the Hotelling scores over the positions and the channels' snr. Every grid's
+    radii must give banks the call takes (r <= 32, at most OBSERVER_MAX_BANKS distinct), else ValueError before any work. Host and
+    device summarise exact integers with one function, so "observer" is equal to the last bit on every path; observer_curve reads the
+    threshold contrast per radius off the cd_ rows. Nothing is asserted: these are findings. With observer=False the rows, keys and
+    launches are exactly as before."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
                         edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients, points, point_tables, reach,
-                        reach_tables, reach_maps, order)
+                        reach_tables, reach_maps, observer=observer, order=order)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -1630,6 +1656,8 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
         if alteration is not None and alteration.measure:
             relation, payload = alteration.measure
             out[relation.key] = scorer.measure(relation, relation.output(payload))
+            if opt.observer and relation.key == "details":
+                out["observer"] = scorer.observer(relation.output(payload))
         out["mean_cnr"] = runner.mean_cnr() if runner.proc else None
         if eproc is not None:
             out["ensemble"] = ensemble_of(eproc, alteration.noise, registered[1] if registered else None, full, opt)
@@ -1863,6 +1891,11 @@ def main(argv=None):
                          "neighbourhood (Kendall's tau of centre-neighbour pairs, overall and per ring, the reversed, flattened and split "
                          "shares, the intact share and the census distance), written to order_robustness.csv; on the GPU with "
                          "--device-metrics / --device-alterations (musica_sim_order)")
+    ap.add_argument("--observer", action="store_true",
+                    help="with --details: a model observer on the cd_ rows, a channelized Hotelling observer with six Laguerre-Gauss channels "
+                         "and the disc as a non-prewhitening template (detectability, auc, position spread and channel snr per radius, and "
+                         "the threshold contrast against radius), written to observer.csv; on the GPU with --device-metrics / "
+                         "--device-alterations (musica_sim_observer)")
     ap.add_argument("--reach", nargs="?", const=True, default=None, type=reach_list, metavar="R0,R1,...",
                     help="keep every row's direct comparison apart by the Chebyshev distance from the nearest changed input pixel: rmse, changed "
                          "share, shift and max per distance class, the extent beyond which nothing changed, the global floor, the spill, its half "
@@ -1894,6 +1927,8 @@ def main(argv=None):
         ap.error("--gain-tables keeps what --gains measures: give --gains")
     if args.lut_tables and not args.luts:
         ap.error("--lut-tables keeps what --luts measures: give --luts")
+    if args.observer and not args.details:
+        ap.error("--observer looks at the details of the cd_ rows: give --details")
     if args.point_tables and not args.points:
         ap.error("--point-tables keeps what --points measures: give --points")
     if (args.reach_tables or args.reach_maps) and args.reach is None:
@@ -1947,6 +1982,8 @@ def main(argv=None):
         shift_args["gradients"] = True
     if args.order:
         shift_args["order"] = True
+    if args.observer:
+        shift_args["observer"] = True
     if args.ensemble:
         shift_args.update(ensemble=args.ensemble, ensemble_tiles=bool(args.ensemble_maps))
     if args.covariance:

@@ -1868,3 +1868,161 @@ def reach_row(table, radii, seeds, sq_diff_sum, pixels, keep=False):
     if keep:
         out["table"] = [[int(v) for v in row] for row in t]
     return out
+
+
+# ---- model observer: the channel responses of patches (not in the reference's script) ---------------------------------------------------
+# Task-based assessment puts a model observer on top of MTF, noise power and contrast-detail: it looks at a patch through a few smooth
+# channels and reports how well a disc is told from its absence against the background the processor produced, a detectability d'.
+# detail_summary's cnr and rose are a one-number observer: they see neither the shape of the response (a halo or rebound ring) nor the
+# correlation of the background. A channelized Hotelling observer with Laguerre-Gauss channels (Barrett & Myers, Foundations of Image
+# Science, ch. 14; Gallas & Barrett 2003) is the standard answer. A view is (x, y, bank): an integer centre and the index of a bank, an
+# int8 array (C, S, S) of C templates over the window |dx|, |dy| <= half, S = 2 half + 1; windows may overlap and views may repeat
+# (processing.view_list). channel_responses is integer and the contract of musica_sim_observer (include/musica.h), which is
+# bit-identical to it; observer_summary is the one f64 function every study path shares.
+
+def channel_responses(a, b, views, banks):
+    """The responses of every view of `views` (processing.view_list for the planes' side, else ValueError before any work) over two
+    square uint8 planes of equal shape: a list of dicts, "a" and "b" the int32 arrays of the bank's C inner products
+        R[j] = sum over dy, dx of bank[j, dy + half, dx + half] * plane[y + dy, x + dx]
+    on either side (|R| <= 255 * 128 * 133^2 < 2^31; summed in int64), and the Python ints "pixels" = S^2, "sum_a" and "sum_b", the
+    window's plain sums: what musica_sim_observer returns."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or a.shape != b.shape or a.shape[0] != a.shape[1] or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("channel_responses needs two square 2-D uint8 planes of equal shape, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    views, banks = mp.view_list(views, banks, a.shape[0])
+    wide = [k.astype(np.int64) for k in banks]
+    out = []
+    for x, y, k in views:
+        half = banks[k].shape[1] // 2
+        pa = a[y - half:y + half + 1, x - half:x + half + 1].astype(np.int64)
+        pb = b[y - half:y + half + 1, x - half:x + half + 1].astype(np.int64)
+        out.append({"a": (wide[k] * pa[None]).sum(axis=(1, 2)).astype(np.int32), "b": (wide[k] * pb[None]).sum(axis=(1, 2)).astype(np.int32),
+                    "pixels": int(pa.size), "sum_a": int(pa.sum()), "sum_b": int(pb.sum())})
+    return out
+
+
+OBSERVER_CHANNELS = 6   # the Laguerre-Gauss channels of the study's banks; the disc indicator follows them
+
+
+def laguerre_gauss_bank(r, channels=OBSERVER_CHANNELS):
+    """The study's bank for a radius-r detail: an int8 array (channels + 1, S, S) over the detail's box, half = 2r + 2, S = 2 half + 1.
+    With rho2 = dx^2 + dy^2 and the width a = half, channel j < channels is the Laguerre-Gauss function
+        u_j = exp(-pi rho2 / a^2) L_j(2 pi rho2 / a^2)                      (numpy.polynomial.laguerre)
+    quantised as rint(127 u_j / max |u_j|): rotationally symmetric, so invariant under the square's eight symmetries, channel 0 a
+    Gaussian with 127 at the centre (its only 127 up to r = 8; from r = 16 on the nearest neighbours round to 127 as well). The last
+    channel is the disc indicator rho2 <= r^2 with weight 1: its response is detail_statistics' disc sum_a / sum_b, a cross-check
+    between two entry points, and the non-prewhitening observer's template."""
+    r, channels = int(r), int(channels)
+    if r < 1 or not 1 <= channels < mp.OBSERVER_MAX_CHANNELS:
+        raise ValueError("laguerre_gauss_bank needs r >= 1 and 1 .. %d channels, got r = %d and %d" % (mp.OBSERVER_MAX_CHANNELS - 1, r, channels))
+    half = 2 * r + 2
+    d = np.arange(-half, half + 1, dtype=np.int64)
+    rho2 = d[:, None] ** 2 + d[None, :] ** 2
+    t = np.pi * rho2.astype(np.float64) / float(half * half)
+    bank = np.empty((channels + 1,) + rho2.shape, dtype=np.int8)
+    for j in range(channels):
+        u = np.exp(-t) * np.polynomial.laguerre.lagval(2.0 * t, [0.0] * j + [1.0])
+        bank[j] = np.rint(127.0 * u / np.abs(u).max()).astype(np.int8)
+    bank[channels] = rho2 <= r * r
+    return bank
+
+
+_OBSERVER_BANKS = {}
+
+
+def observer_views(details):
+    """(views, banks) of a detail list for channel_responses / sim_observer: one view per detail, in the list's order, at the detail's
+    centre with the bank of its radius; the banks laguerre_gauss_bank(r) of the distinct radii in ascending order (each built once)."""
+    radii = sorted(set(int(d[2]) for d in details))
+    for r in radii:
+        if r not in _OBSERVER_BANKS:
+            _OBSERVER_BANKS[r] = laguerre_gauss_bank(r)
+    return [(int(d[0]), int(d[1]), radii.index(int(d[2]))) for d in details], [_OBSERVER_BANKS[r] for r in radii]
+
+
+OBSERVER_KEYS = ("count", "cho", "auc", "npw", "spread", "channel_snr")   # observer_summary's entries of one radius
+OBSERVER_MAX_COND = 1e10                                                  # a covariance worse conditioned than this is not inverted
+
+
+def _quotient(num, den):
+    return num / den if den else None
+
+
+def observer_summary(radii, responses):
+    """What the study reports of the views of a cd_ row, from channel_responses' (or musica_sim_observer's) exact integers: one function
+    for every study path, so the paths agree to the last bit. radii: the radius of each view's detail; responses: their dicts, the
+    last channel of each the disc indicator, the others the LG channels. Per radius, over its m positions, with va_i and vb_i the LG
+    responses on either side and D_i = va_i - vb_i, in f64:
+        mean D      the mean signal in channel space
+        K           (cov(va) + cov(vb)) / 2 with ddof = 1: the background's channel covariance
+        cho         sqrt(max(mean D^T K^-1 mean D, 0)) by np.linalg.solve: the channelized Hotelling observer's detectability d'
+        auc         (1 + erf(cho / 2)) / 2: the area under its ROC curve
+        channel_snr mean D_j / sqrt(K_jj) per LG channel
+        npw         the same quotient on the disc channel: the non-prewhitening observer with the disc as its template
+        spread      std / |mean| (population std) of the Hotelling scores (K^-1 mean D)^T D_i over the positions: position invariance
+    cho, auc and spread are None where m < 2 channels + 2 or cond(K) > OBSERVER_MAX_COND (a singular K among them); a quotient with a
+    zero denominator is None, and with m < 2 there is no covariance at all. Returns {r: dict of OBSERVER_KEYS} in ascending r. No
+    threshold is fixed here: these are findings."""
+    out = {}
+    for r in sorted(set(int(v) for v in radii)):
+        group = [s for v, s in zip(radii, responses) if int(v) == r]
+        va = np.array([[int(x) for x in s["a"]] for s in group], dtype=np.float64)
+        vb = np.array([[int(x) for x in s["b"]] for s in group], dtype=np.float64)
+        m, channels = va.shape[0], va.shape[1] - 1
+        delta = va - vb
+        mean = delta.mean(axis=0)
+        entry = {"count": m, "cho": None, "auc": None, "npw": None, "spread": None, "channel_snr": [None] * channels}
+        out[r] = entry
+        if m < 2:
+            continue
+        full = 0.5 * (np.cov(va, rowvar=False, ddof=1) + np.cov(vb, rowvar=False, ddof=1)).reshape(channels + 1, channels + 1)
+        snr = [_quotient(float(mean[j]), math.sqrt(max(float(full[j, j]), 0.0))) for j in range(channels + 1)]
+        entry["channel_snr"], entry["npw"] = snr[:channels], snr[channels]
+        k = full[:channels, :channels]
+        if m < 2 * channels + 2 or not np.all(np.isfinite(k)) or not np.linalg.cond(k) <= OBSERVER_MAX_COND:
+            continue
+        w = np.linalg.solve(k, mean[:channels])
+        cho = math.sqrt(max(float(mean[:channels] @ w), 0.0))
+        scores = delta[:, :channels] @ w
+        entry["cho"], entry["auc"] = cho, 0.5 * (1.0 + math.erf(cho / 2.0))
+        entry["spread"] = _quotient(float(scores.std()), abs(float(scores.mean())))
+    return out
+
+
+def observer_row(details, responses):
+    """A cd_ row's "observer" value from the row's details (their radii) and the responses of observer_views' views:
+    {"radii": observer_summary's dict}."""
+    return {"radii": observer_summary([d[2] for d in details], responses)}
+
+
+def observer_curve(rows, level=1.0):
+    """The contrast-detail curve of a study by its model observer: {r: the contrast (in 1 / 1024, a float) at which the cd_ rows' cho of
+    radius r crosses `level`}, by linear interpolation in log-log between the first two neighbouring contrasts (ascending) whose cho lie
+    on either side of it; None where it never crosses (a cho that is None or not positive is left out). The level is the caller's
+    convention, not a finding."""
+    if not level > 0:
+        raise ValueError("observer_curve needs a positive level, got %r" % (level,))
+    points = {}
+    for row in rows:
+        if row["alteration"].startswith("cd_") and row.get("observer"):
+            for r, entry in row["observer"]["radii"].items():
+                if entry["cho"] is not None and entry["cho"] > 0:
+                    points.setdefault(r, []).append((int(row["alteration"][3:]), entry["cho"]))
+    curve = {}
+    for r in sorted(points):
+        curve[r] = None
+        pts = sorted(points[r])
+        for (c1, h1), (c2, h2) in zip(pts, pts[1:]):
+            if h1 == level:
+                curve[r] = float(c1)
+            elif h2 == level:
+                curve[r] = float(c2)
+            elif (h1 < level) != (h2 < level):
+                t = (math.log(level) - math.log(h1)) / (math.log(h2) - math.log(h1))
+                curve[r] = math.exp(math.log(c1) + t * (math.log(c2) - math.log(c1)))
+            else:
+                continue
+            break
+        if curve[r] is None and len(pts) == 1 and pts[0][1] == level:
+            curve[r] = float(pts[0][0])
+    return curve

@@ -195,6 +195,10 @@ ORDER_BINS = 97             # MUSICA_ORDER_BINS: the census distance d = 0 .. 96
 REACH_MAX_RADII = 32        # MUSICA_REACH_MAX_RADII
 REACH_MAX_RADIUS = 16383    # MUSICA_REACH_MAX_RADIUS
 REACH_MAX_QUERIES = 16      # MUSICA_REACH_MAX_QUERIES
+OBSERVER_MAX_VIEWS = 1024   # MUSICA_OBSERVER_MAX_VIEWS
+OBSERVER_MAX_BANKS = 8      # MUSICA_OBSERVER_MAX_BANKS
+OBSERVER_MAX_CHANNELS = 16  # MUSICA_OBSERVER_MAX_CHANNELS
+OBSERVER_MAX_HALF = 66      # MUSICA_OBSERVER_MAX_HALF: 2 * 32 + 2, the box of a radius-32 detail
 
 
 def zoom_ratio(zoom):
@@ -479,6 +483,60 @@ class SimPointResult(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k in POINT_SUMS}
+
+
+def view_list(views, banks, n):
+    """The views (x, y, bank) and the template banks of a model-observer call for a plane of side n as metrics.channel_responses and the
+    library take them: (a tuple of tuples of ints, a tuple of contiguous int8 arrays (C, S, S)), else ValueError, checked as the C side
+    checks: 1 .. OBSERVER_MAX_BANKS banks, each an array of integers within int8 of shape (C, S, S) with 1 <= C <= OBSERVER_MAX_CHANNELS
+    and S = 2 half + 1, 1 <= half <= OBSERVER_MAX_HALF; 1 .. OBSERVER_MAX_VIEWS views of integers, each naming a bank of the call and
+    with its window |px - x|, |py - y| <= half inside [0, n)^2. The windows may overlap and views may repeat."""
+    try:
+        arrays = [np.asarray(b) for b in banks]
+    except (TypeError, ValueError):
+        raise ValueError("the banks are a sequence of integer arrays (C, S, S), got %r" % (banks,))
+    if not 1 <= len(arrays) <= OBSERVER_MAX_BANKS:
+        raise ValueError("an observer call holds 1 .. %d banks, got %d" % (OBSERVER_MAX_BANKS, len(arrays)))
+    out_banks = []
+    for k, a in enumerate(arrays):
+        if a.ndim != 3 or a.shape[1] != a.shape[2] or a.dtype.kind not in "iu" or not a.size:
+            raise ValueError("bank %d: not a (C, S, S) array of integers, got %r %s" % (k, a.shape, a.dtype))
+        if a.shape[1] % 2 != 1 or not 1 <= a.shape[1] // 2 <= OBSERVER_MAX_HALF:
+            raise ValueError("bank %d: side %d is not 2 half + 1 with half in 1 .. %d" % (k, a.shape[1], OBSERVER_MAX_HALF))
+        if not 1 <= a.shape[0] <= OBSERVER_MAX_CHANNELS:
+            raise ValueError("bank %d: %d channels are not in 1 .. %d" % (k, a.shape[0], OBSERVER_MAX_CHANNELS))
+        if int(a.min()) < -128 or int(a.max()) > 127:
+            raise ValueError("bank %d: a weight is beyond int8" % k)
+        out_banks.append(np.ascontiguousarray(a, dtype=np.int8))
+    try:
+        out = [_ints(v, 3) for v in views]
+    except (TypeError, ValueError):
+        raise ValueError("a view list holds triples of integers (x, y, bank), got %r" % (views,))
+    n = int(n)
+    if not 1 <= len(out) <= OBSERVER_MAX_VIEWS:
+        raise ValueError("a view list holds 1 .. %d views, got %d" % (OBSERVER_MAX_VIEWS, len(out)))
+    for i, (x, y, k) in enumerate(out):
+        if not 0 <= k < len(out_banks):
+            raise ValueError("view %d: bank %d is not in 0 .. %d" % (i, k, len(out_banks) - 1))
+        r = out_banks[k].shape[1] // 2
+        if x - r < 0 or y - r < 0 or x + r >= n or y + r >= n:
+            raise ValueError("view %d: the window (%d, %d) +- %d leaves the %d x %d plane" % (i, x, y, r, n, n))
+    return tuple(out), tuple(out_banks)
+
+
+class ChannelBank(C.Structure):
+    """musica_channel_bank: `channels` int8 templates over the window |dx|, |dy| <= half, weights[channels][S][S]."""
+    _fields_ = [("half", C.c_uint32), ("channels", C.c_uint32), ("weights", C.POINTER(C.c_int8))]
+
+
+class View(C.Structure):
+    """musica_view: a window of bank `bank` about the integer pixel centre (x, y)."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("bank", C.c_uint32)]
+
+
+class SimObserverResult(C.Structure):
+    """musica_sim_observer_result: where a view's responses lie in `tables`, its window's pixel count and plain sums."""
+    _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint32), ("sum_a", C.c_uint32), ("sum_b", C.c_uint32)]
 
 
 def _unpack_tables(results, tables, sums):
@@ -786,6 +844,8 @@ ABI = {
     "musica_sim_gratings": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Grating), C.POINTER(SimGratingResult), _U32P, C.c_uint64]),
     "musica_alter_points": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(Defect)]),
     "musica_sim_points": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Defect), C.c_uint32, C.POINTER(SimPointResult), _U32P, C.c_uint64]),
+    "musica_sim_observer": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ChannelBank), C.c_uint32, C.POINTER(View), C.POINTER(SimObserverResult),
+                                      C.POINTER(C.c_int32), C.c_uint64]),
     "musica_alter_gain": (C.c_int, [_VP, C.c_uint32, _U16P, _U16P]),
     "musica_sim_profiles": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimProfileResult), _U32P, C.c_uint64]),
     "musica_alter_lut": (C.c_int, [_VP, C.c_uint32, _U16P]),
@@ -1251,6 +1311,23 @@ class MusicaProcessing:
         stacks = tables.reshape(groups, 3, side, side).astype(np.int64)
         return {"points": [r.as_dict() for r in res],
                 "groups": [dict({"count": sum(1 for p in ps if p[5] == g)}, **{k: stacks[g, i] for i, k in enumerate(POINT_STACKS)}) for g in range(groups)]}
+
+    def sim_observer(self, views, banks, slot, image_index=0):
+        """metrics.channel_responses(output of `image_index`, reference slot `slot`, views, banks) on the device: the views (x, y, bank)
+        in the (N - 20)^2 output plane's coordinates and the int8 banks (C, S, S) (view_list: ValueError before any call). Returns one
+        dict per view: "a" and "b", the int32 arrays of its bank's C channel responses on either side, and the Python ints "pixels"
+        (S^2), "sum_a" and "sum_b" (the window's plain sums)."""
+        vs, bs = view_list(views, banks, self.imageSize - 2 * OUT_MARGIN)
+        words = sum(2 * bs[k].shape[0] for _, _, k in vs)
+        barr = (ChannelBank * len(bs))(*[ChannelBank(b.shape[1] // 2, b.shape[0], b.ctypes.data_as(C.POINTER(C.c_int8))) for b in bs])
+        arr, res, tables = (View * len(vs))(*[View(*v) for v in vs]), (SimObserverResult * len(vs))(), np.zeros(words, dtype=np.int32)
+        self._ok(self._lib.musica_sim_observer(self._h, int(image_index), int(slot), len(bs), barr, len(vs), arr, res,
+                                               tables.ctypes.data_as(C.POINTER(C.c_int32)), words), "musica_sim_observer")
+        out = []
+        for (_, _, k), r in zip(vs, res):
+            at, c = int(r.table_offset), bs[k].shape[0]
+            out.append({"a": tables[at:at + c].copy(), "b": tables[at + c:at + 2 * c].copy(), "pixels": int(r.pixels), "sum_a": int(r.sum_a), "sum_b": int(r.sum_b)})
+        return out
 
     def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False):
         """What sim_profiles / _levels / _gradients / _order / _reach share: the refusals of sim_<name> before any call (most: 1 .. most

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, reach_maps
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -53,6 +53,9 @@ LEVEL_CSV_HEADER = ['raw file', 'alteration'] + [k.replace('_', ' ') for k in LE
 REACH_CSV_CLASS = ("outer", "n", "rmse", "changed", "shift", "max")   # reach_summary's per-class lists, in reach.csv's order
 REACH_CSV_HEADER = ['raw file', 'alteration', 'class', 'outer radius', 'pixels', 'rmse', 'changed share', 'shift', 'max'] + \
                    [k.replace('_', ' ') for k in REACH_KEYS]   # reach.csv
+OBSERVER_CSV_KEYS = ("cho", "auc", "npw", "spread")   # observer_summary's scalars, in observer.csv's order; the channels' snr follow
+OBSERVER_CSV_HEADER = ['raw file', 'alteration', 'radius', 'details'] + list(OBSERVER_CSV_KEYS) + ['snr channel %d' % j for j in range(OBSERVER_CHANNELS)]   # observer.csv
+OBSERVER_CURVE_CSV_HEADER = ['raw file', 'radius', 'level', 'threshold contrast']   # observer_curve.csv
 WARP_CSV_HEADER = ['raw file', 'alteration', 'reach', 'peak'] + [k.replace('_', ' ') for k in WARP_TRACKING_KEYS] + ['registered mse', 'registered ssim']   # warp_response.csv
 
 
@@ -196,6 +199,9 @@ RELATION_CSVS = (
     # point_response.csv: one line per point_ row and group, in the groups' order, then "all"
     ("point_response.csv", POINT_CSV_HEADER, "points", lambda d: list(enumerate(d["groups"])) + [("all", d["all"])],
      lambda d, g: [g[k] for k in POINT_KEYS] + [d["outside_mse"]]),
+    # observer.csv: one line per cd_ row and radius, ascending
+    ("observer.csv", OBSERVER_CSV_HEADER, "observer", lambda d: d["radii"].items(),
+     lambda d, g: [g["count"]] + ["" if v is None else v for v in [g[k] for k in OBSERVER_CSV_KEYS] + list(g["channel_snr"])]),
 )
 
 
@@ -263,6 +269,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     class), its pixels, rmse, changed share, mean shift and max (empty for an empty class), then reach_summary's numbers of the row
     (seeds, classes, last class, extent, floor, spill, half reach, decay; an empty cell where one is None), the same on each line.
 
+    Studies run with observer (rows[0] has "observer") also get observer.csv (OBSERVER_CSV_HEADER): one line per cd_ row and radius,
+    ascending: the number of details of that radius, the model observer's cho, auc, npw and spread and the snr of its Laguerre-Gauss
+    channels (an empty cell where one is None); and observer_curve.csv (OBSERVER_CURVE_CSV_HEADER): one line per study and radius, the
+    contrast at which cho crosses the level 1 (observer_curve; the level is a convention, not a finding), empty where it never does.
+
     Studies run with warps (rows[0] has "warp") also get warp_response.csv (WARP_CSV_HEADER): one line per warp row, the field's reach
     and peak displacement in pixels, the four tracking numbers of metrics.warp_tracking (empty without a displacement radius) and the
     registered mse and ssim (empty where the row has no registered comparison)."""
@@ -306,6 +317,9 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     for name, header, key, groups, cells in RELATION_CSVS:
         if having(key):
             _write_csv(out_dir, name, header, _group_lines(having(key), key, groups, cells))
+    if having("observer"):
+        _write_csv(out_dir, "observer_curve.csv", OBSERVER_CURVE_CSV_HEADER,
+                   [[raw_name, radius, 1.0, "" if c is None else c] for raw_name, rows in having("observer") for radius, c in observer_curve(rows, 1.0).items()])
     ovds = [[raw_name] + _cells(_ovd(rows), SIM_CSV_KEYS) for raw_name, rows in studies if _ovd(rows) is not None]
     if ovds:
         _write_csv(out_dir, "ref_similarities.csv", REF_CSV_HEADER, ovds)
