@@ -35,7 +35,12 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     ragged tail), a 70 x 75 region from mid-tile with different origins on the two sides (one tile across, two down), a 7-wide column
     and a 7 x 7 corner; integers only;
   * the model observer at N = 151 of image 1's output against slot 0: six overlapping views of the Laguerre-Gauss banks of the radii
-    1, 2, 4, 8 and 16 (windows of side 9 .. 69, one flush with the output plane's corner, one view twice); integers only.
+    1, 2, 4, 8 and 16 (windows of side 9 .. 69, one flush with the output plane's corner, one view twice); integers only;
+  * the codec pair at N = 151 (odd: the unaligned path, a partial last block): the source plane through the study's table of DC step
+    1024 into image 0, and slot 0 through its 8-bit table at the margin's origin 2 into slot 1; integers only;
+  * the lattice sums at N = 151 of other images' outputs against slot 0, at period 8 (origin 2) and period 32 (origin 10): the full
+    frame (130 x 130 counted pixels: 3 x 3 tiles with a two-pixel ragged tail), a ragged region from mid-tile with different origins on
+    the two sides, a 2-wide column and a 2 x 2 corner; integers only.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -168,5 +173,13 @@ if hasattr(p, "sim_observer"):    # likewise a --tree from before the model obse
     from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import metrics
     views, banks = metrics.observer_views([(30, 30, 1, 0), (63, 64, 2, 0), (65, 66, 4, 0), (NW - 19, NW - 19, 8, 0), (66, 64, 16, 0), (63, 64, 2, 0)])
     note("musica_sim_observer", [[r["a"], r["b"], r["pixels"], r["sum_a"], r["sum_b"]] for r in p.sim_observer(views, banks, 0, image_index=1)])
+if hasattr(p, "alter_codec"):     # likewise a --tree from before the block codec
+    from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd import metrics
+    p.alter_codec(metrics.codec_table(1024))
+    p.sim_codec_reference(1, 0, metrics.codec_table8(metrics.codec_table(1024)))
+    note("musica_codec", [p.input_pixels()[0], p.sim_get_reference(1)])
+if hasattr(p, "sim_lattice"):     # likewise a --tree from before the lattice sums
+    qs = [(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 2, NW - 1), (1, 0, NW - 2, NW - 2, 0, 0, 2, 2)]
+    note("musica_sim_lattice", [p.sim_lattice(qs, 8, 2), p.sim_lattice(qs, 32, 10)])
 p.cleanup()
 print(json.dumps(digests))

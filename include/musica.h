@@ -401,6 +401,27 @@ int musica_sim_transform_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t 
  * Refused before any device work: a NULL context, a slot out of range, dst_slot == src_slot, a source slot never written, a radius outside
  * 1 .. MUSICA_BLUR_MAX_RADIUS, an image too small for the margin. Marks dst_slot written; changes no other slot. */
 int musica_sim_blur_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, uint32_t radius);
+/* ---- lossy compression: the exact 8 x 8 block codec (new, not in the reference) ----
+ * metrics.block_codec(plane, table, origin) is the contract: of a square 2-D uint16 (bits = 16) or uint8 (bits = 8) plane, with a table
+ * of 64 quantiser steps Q[v][u] in 1 .. 65535 (v the vertical frequency) and an origin (oy, ox), each 0 .. 7: the plane lies on a grid of
+ * 8 x 8 blocks that start at x = -ox and y = -oy (mod 8); a block that sticks out of the plane is completed by edge replication, as
+ * JPEG does, and only in-plane pixels are written. Per block, in int32 throughout, rs(t, s) = (t + 2^(s - 1)) >> s (arithmetic shift),
+ * M[0][x] = 512, M[u][x] = rint(512 sqrt 2 cos((2x + 1) u pi / 16)) (the 64 literals stand in kernels_codec.hip and metrics.CODEC_M):
+ *   X  = v - 2^(bits - 1)
+ *   A  = rs(X M^T, 10)                          rows        |X M^T| <= 2^27
+ *   F  = rs(M A, 11)                            columns     |M A| <= 2^29, |F| <= 2^18  (the orthonormal DCT, DC = 8 mean exactly)
+ *   q  = sign(F) ((|F| + (Q >> 1)) div Q)       halves away from zero
+ *   F' = q Q                                    |F'| <= 2^18 + 32767
+ *   A' = clamp(rs(M^T F', 10), -2^18, 2^18 - 1) |M^T F'| <= 3825 (2^18 + 32767) < 2^31; the clamp is part of the contract
+ *   X' = rs(A' M, 11)                           |A' M| <= 2^30
+ *   out = clamp(X' + 2^(bits - 1), 0, 2^bits - 1)
+ * A constant block comes back exactly whenever Q[0][0] divides 8 X. The device results are bit-identical to that statement and repeat
+ * from call to call (kernels_codec.hip). */
+/* block_codec(reference slot `src_slot`, table, (origin, origin)) of the (N - 20)^2 u8 plane into `dst_slot` (device to device, on the
+ * ctx stream); the study passes origin = MUSICA_OUT_MARGIN % 8, so the blocks lie where the raw plane's lay. Refused before any device
+ * work: a NULL context, a NULL table, a slot out of range, dst_slot == src_slot, a source slot never written, a table entry of 0,
+ * origin > 7, an image too small for the margin. Marks dst_slot written; changes no other slot. */
+int musica_sim_codec_reference(musica_ctx* ctx, uint32_t dst_slot, uint32_t src_slot, const uint16_t table[64], uint32_t origin);
 /* ---- magnification: the exact rational zoom (new, not in the reference) ----
  * harness.zoom(image, (p, q)) is the contract: a square 2-D uint16 or uint8 plane of side n magnified by p / q about its centre,
  * bilinearly, in integers, with 1 <= q < p <= MUSICA_ZOOM_MAX_P and gcd(p, q) = 1. With D = 2p, for an output index x
@@ -736,6 +757,10 @@ int musica_alter(musica_ctx* ctx, uint32_t image_index, const musica_alteration*
  * slot. An entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT. Refused before any
  * device work: no source, image_index >= batch, a radius outside 1 .. MUSICA_BLUR_MAX_RADIUS. */
 int musica_alter_blur(musica_ctx* ctx, uint32_t image_index, uint32_t radius);
+/* block_codec(source plane, table, (0, 0)) (above, at musica_sim_codec_reference) into image `image_index` of the input buffer, enqueued
+ * on the ctx stream, with musica_alter's guarantees. Refused before any device work: a NULL context, a NULL table, no source,
+ * a table entry of 0, image_index >= batch. */
+int musica_alter_codec(musica_ctx* ctx, uint32_t image_index, const uint16_t table[64]);
 /* zoom(source plane, (p, q)) (above, at musica_sim_zoom_reference) into image `image_index` of the input buffer, enqueued on the ctx
  * stream, with musica_alter's guarantees: it changes no other image of the input buffer, no result of the last step and no reference
  * slot. An entry point of its own and not a musica_alteration_kind: the kinds are closed at MUSICA_ALTER_KIND_COUNT. Refused before any
@@ -1098,6 +1123,31 @@ typedef struct musica_sim_order_result {
 } musica_sim_order_result;
 int musica_sim_order(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_order_result* results,
                      uint64_t* tables, uint64_t table_words);
+
+/* ---- lattice sums: a comparison folded by the position modulo a period (new, not in the reference) ----
+ * Blocking is a lattice artefact, and so is the shift variance of a decimated pyramid, with periods 2, 4 .. 32 on the raw grid.
+ * metrics.lattice_statistics is the contract. Queries are musica_sim_compare's with w, h >= 2, at most MUSICA_LATTICE_MAX_QUERIES;
+ * `period` P is one of 2, 4, 8, 16, 32 and `origin` o is 0 .. P - 1. The sums run over the query's pixels (i, j) with i < w - 1 and
+ * j < h - 1, so that every counted pixel has a right and a lower neighbour inside the region. The class of a pixel is
+ * [(ay + j + o) mod P][(ax + i + o) mod P]: side a's position on the raw grid when o is the margin mod P. Query i gets
+ * P * P * MUSICA_LATTICE_WORDS uint64_t in the flat `tables`, from results[i].table_offset (in words) on, [row phase][column phase]:
+ *   n, sum a, sum b, sum (a - b)^2, sum (a[i + 1] - a[i])^2, the same of b, sum (a[j + 1] - a[j])^2, the same of b
+ * The n add up to results[i].pixels = (w - 1) (h - 1); sum (a - b)^2 adds up to musica_sim_compare's sq_diff_sum of the query shrunk by
+ * one column and one row; the table folded by phase mod P / 2 is the table of period P / 2 with origin o mod P / 2. Everything is an
+ * integer: the tables equal the restatement word for word and repeat from call to call. Every word of the tables is written and nothing
+ * behind them. Synchronous, on the context's stream after whatever was enqueued there; changes no slot, no result of a step and no input
+ * image; scratch is allocated on first use. Refused before any device work: what musica_sim_compare refuses (with the smallest side 2),
+ * then a period that is not one of the five, origin >= period, a NULL `tables` and table_words below the tables' words. After a
+ * refusal the context stays usable. */
+#define MUSICA_LATTICE_WORDS 8
+#define MUSICA_LATTICE_MAX_PERIOD 32
+#define MUSICA_LATTICE_MAX_QUERIES 16
+typedef struct musica_sim_lattice_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t pixels;                /* (w - 1) * (h - 1) */
+} musica_sim_lattice_result;
+int musica_sim_lattice(musica_ctx* ctx, uint32_t period, uint32_t origin, uint32_t count, const musica_sim_query* queries,
+                       musica_sim_lattice_result* results, uint64_t* tables, uint64_t table_words);
 
 /* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
  * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change

@@ -303,6 +303,14 @@ void launch_symmetry_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n,
 constexpr int kBlurMaxRadius = 8;   // MUSICA_BLUR_MAX_RADIUS
 void launch_blur_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, int radius);
 void launch_blur_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int radius);
+// kernels_codec.hip: metrics.block_codec(plane, table, (origin, origin)), the exact 8 x 8 integer block codec, of a dense n x n plane into
+// another (the planes must not overlap); any n >= 1, origin 0 .. 7, every table entry 1 .. 65535 (q[v * 8 + u], v the vertical
+// frequency).
+struct CodecTable {
+    uint16_t q[64];
+};
+void launch_codec_u16(hipStream_t st, const uint16_t* src, uint16_t* out, int n, int origin, const CodecTable& table);
+void launch_codec_u8(hipStream_t st, const uint8_t* src, uint8_t* out, int n, int origin, const CodecTable& table);
 // kernels_zoom.hip: harness.zoom(plane, (p, q)), the exact bilinear magnification by p / q about the centre, of a dense n x n plane into
 // another (the planes must not overlap); any n >= 1, 1 <= q < p <= kZoomMaxP with gcd(p, q) = 1
 constexpr int kZoomMaxP = 32;   // MUSICA_ZOOM_MAX_P
@@ -453,6 +461,32 @@ struct OrderQueryDev : SimRegion {
 // metrics.order_statistics over `count` queries (grid.x = max_tiles, the largest tiles_x * tiles_y). tables: every query's words,
 // zeroed by the caller: the tiles add into them with u64 atomics
 void launch_sim_order(hipStream_t st, const OrderQueryDev* d_qs, int count, int max_tiles, unsigned long long* tables);
+// kernels_lattice.hip: the lattice sums. One comparison of musica_sim_lattice: w, h >= 2 are the REGION's; the kernel tiles its counted
+// pixels, (w - 1) x (h - 1). tiles_x / tiles_y: ceil((w - 1) / 64), ceil((h - 1) / 64); groups: the persistent workgroups that share
+// the tiles (lattice_groups); phase_x / phase_y: (ax + origin) mod P, (ay + origin) mod P, the class of the region's first pixel;
+// table: where its P * P * kLatticeWords u64 start in the launch's flat tables, in words; part: where its `groups` partial tables of
+// P * P * kLatticeWords u32 start in the launch's partials, in words.
+constexpr int kLatticeWords = 8;          // MUSICA_LATTICE_WORDS: n, a, b, dd, the squared steps right of a and b, down of a and b
+constexpr int kLatticeMaxPeriod = 32;     // MUSICA_LATTICE_MAX_PERIOD
+constexpr int kLatticeMaxQueries = 16;    // MUSICA_LATTICE_MAX_QUERIES
+constexpr int kLatticeGroupTiles = 64;    // the most tiles of a workgroup: its u32 sums hold (kernels_lattice.hip, THE 32-BIT RULE)
+struct LatticeQueryDev : SimRegion {
+    int tiles_x, tiles_y, groups;
+    int phase_x, phase_y;
+    unsigned long long table, part;
+};
+// The workgroups of a query of `tiles` tiles at period P: every workgroup stores a partial table of 8 P^2 words (32 KiB at P = 32), so
+// the larger periods take fewer workgroups with more tiles each; never more than kLatticeGroupTiles tiles each. most > 0 (the tuning
+// variable MUSICA_LATTICE_GROUPS, read at every call) lowers the number: the tables do not depend on it.
+inline int lattice_groups(int tiles, int period, int most = 0) {
+    const int by_period = period >= 32 ? 512 : period >= 16 ? 1024 : 4096;
+    const int want = most > 0 && most < by_period ? most : by_period;
+    const int least = (tiles + kLatticeGroupTiles - 1) / kLatticeGroupTiles;
+    return tiles < want ? tiles : (least > want ? least : want);
+}
+// metrics.lattice_statistics over `count` queries (grid.x = max_groups, the largest `groups`). part: room for every query's partial
+// tables; tables: every query's words, zeroed by the caller: the fold launch adds into them with u64 atomics
+void launch_sim_lattice(hipStream_t st, const LatticeQueryDev* d_qs, int count, int max_groups, int period, uint32_t* part, unsigned long long* tables);
 // kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
 // Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
 constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII

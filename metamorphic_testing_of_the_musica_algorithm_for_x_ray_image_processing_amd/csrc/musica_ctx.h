@@ -170,6 +170,11 @@ struct StudyState {
     // musica_sim_order: the queries and the flat tables
     OrderQueryDev* d_order_q = nullptr;            // [MUSICA_SIM_MAX_QUERIES]
     unsigned long long* d_order_tables = nullptr;  // [MUSICA_SIM_MAX_QUERIES][kOrderTableWords], allocated by the first musica_sim_order
+    // musica_sim_lattice: the queries and the flat tables
+    LatticeQueryDev* d_lattice_q = nullptr;          // [MUSICA_LATTICE_MAX_QUERIES]
+    unsigned long long* d_lattice_tables = nullptr;  // [MUSICA_LATTICE_MAX_QUERIES][kLatticeMaxPeriod^2][kLatticeWords], allocated by the first musica_sim_lattice
+    uint32_t* d_lattice_part = nullptr;              // the workgroups' partial tables of one call: lattice_part_cap words, regrown when a call needs more
+    size_t lattice_part_cap = 0;
     // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
     // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
     uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either

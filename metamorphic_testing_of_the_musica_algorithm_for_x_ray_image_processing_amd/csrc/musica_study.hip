@@ -1,8 +1,8 @@
 // musica_study.hip — the metamorphic study's entry points of include/musica.h: the reference slots and the query calls (musica_sim_*),
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
-// kernels_symmetry.hip, kernels_blur.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
+// kernels_symmetry.hip, kernels_blur.hip, kernels_codec.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
 // sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
@@ -79,6 +79,16 @@ static int zoom_check(const char* fn, uint32_t p, uint32_t q) {
     return 1;
 }
 
+// What both codec calls refuse about a table that is not NULL and an origin, as processing.codec_table_words does; then the table as the
+// kernel takes it. No device work.
+static int codec_check(const char* fn, const uint16_t* table, uint32_t origin, CodecTable& t) {
+    if (origin > 7) return fail("%s: origin %u is not in 0 .. 7", fn, origin);
+    for (int k = 0; k < 64; k++) {
+        if (table[k] == 0) return fail("%s: table entry %d (v = %d, u = %d) is 0: the steps are 1 .. 65535", fn, k, k / 8, k % 8);
+        t.q[k] = table[k];
+    }
+    return 1;
+}
 static_assert(kScatterMaxRadius == MUSICA_SCATTER_MAX_RADIUS && kScatterMaxDen == MUSICA_SCATTER_MAX_DEN,
               "kernels_scatter.hip's u32 row plane and u64 numerator hold for the scatters of include/musica.h");
 
@@ -419,6 +429,7 @@ constexpr TableBuffers<ProfileQueryDev, uint32_t> kProfileBuffers{&StudyState::d
 constexpr TableBuffers<LevelQueryDev, unsigned long long> kLevelBuffers{&StudyState::d_level_q, &StudyState::d_level_tables, MUSICA_LEVEL_MAX_QUERIES, 1, (size_t)MUSICA_LEVEL_MAX_QUERIES * kLevelMaxClasses * kLevelWords};
 constexpr TableBuffers<GradQueryDev, unsigned long long> kGradBuffers{&StudyState::d_grad_q, &StudyState::d_grad_tables, MUSICA_SIM_MAX_QUERIES, 7, (size_t)MUSICA_SIM_MAX_QUERIES * kGradClasses * kGradWords};
 constexpr TableBuffers<OrderQueryDev, unsigned long long> kOrderBuffers{&StudyState::d_order_q, &StudyState::d_order_tables, MUSICA_SIM_MAX_QUERIES, 7, (size_t)MUSICA_SIM_MAX_QUERIES * kOrderTableWords};
+constexpr TableBuffers<LatticeQueryDev, unsigned long long> kLatticeBuffers{&StudyState::d_lattice_q, &StudyState::d_lattice_tables, MUSICA_LATTICE_MAX_QUERIES, 2, (size_t)MUSICA_LATTICE_MAX_QUERIES * kLatticeMaxPeriod * kLatticeMaxPeriod * kLatticeWords};
 constexpr TableBuffers<ReachQueryDev, unsigned long long> kReachBuffers{&StudyState::d_reach_q, &StudyState::d_reach_tables, MUSICA_REACH_MAX_QUERIES, 1, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords};
 
 // What a call's place() says of one query: its tiles or chunks (the launch's grid.x is the largest) and the words of its table.
@@ -585,6 +596,15 @@ int musica_sim_blur_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slo
         c, "musica_sim_blur_reference", dst_slot, src_slot,
         [&] { return radius >= 1 && radius <= MUSICA_BLUR_MAX_RADIUS ? 1 : fail("musica_sim_blur_reference: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS); },
         [&](const uint8_t* src, uint8_t* dst) { launch_blur_u8(c->stream, src, dst, (int)sim_side(c), (int)radius); });
+}
+
+int musica_sim_codec_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, const uint16_t table[64], uint32_t origin) {
+    if (!c) return fail("musica_sim_codec_reference: ctx is NULL");
+    if (!table) return fail("musica_sim_codec_reference: table is NULL");
+    CodecTable t;
+    return sim_derive_slot(
+        c, "musica_sim_codec_reference", dst_slot, src_slot, [&] { return codec_check("musica_sim_codec_reference", table, origin, t); },
+        [&](const uint8_t* src, uint8_t* dst) { launch_codec_u8(c->stream, src, dst, (int)sim_side(c), (int)origin, t); });
 }
 
 int musica_sim_zoom_reference(musica_ctx* c, uint32_t dst_slot, uint32_t src_slot, uint32_t p, uint32_t q) {
@@ -1193,6 +1213,39 @@ int musica_sim_order(musica_ctx* c, uint32_t count, const musica_sim_query* qs, 
     ABI_CATCH("musica_sim_order")
 }
 
+// ---- the lattice sums of a comparison (musica_sim_lattice, include/musica.h; kernels_lattice.hip) --------------------------------------
+static_assert(kLatticeWords == MUSICA_LATTICE_WORDS && kLatticeMaxPeriod == MUSICA_LATTICE_MAX_PERIOD && kLatticeMaxQueries == MUSICA_LATTICE_MAX_QUERIES, "kernels_lattice.hip's constants are include/musica.h's");
+
+int musica_sim_lattice(musica_ctx* c, uint32_t period, uint32_t origin, uint32_t count, const musica_sim_query* qs, musica_sim_lattice_result* out, uint64_t* tables,
+                       uint64_t table_words) {
+    ABI_TRY
+    size_t partials = 0;   // words of every query's partial tables
+    return sim_query_tables(
+        c, "musica_sim_lattice", kLatticeBuffers, count, qs, out, tables, table_words,
+        [&] {
+            if (period != 2 && period != 4 && period != 8 && period != 16 && period != 32) return fail("musica_sim_lattice: period %u is not one of 2, 4, 8, 16, 32", period);
+            if (origin >= period) return fail("musica_sim_lattice: origin %u is not below the period %u", origin, period);
+            return 1;
+        },
+        [&](const musica_sim_query& q, LatticeQueryDev& d) {   // of the counted pixels
+            d.groups = lattice_groups(tile_grid(d, q.w - 1, q.h - 1), (int)period, env_int("MUSICA_LATTICE_GROUPS", 0));
+            d.phase_x = (int)((q.ax + origin) % period);
+            d.phase_y = (int)((q.ay + origin) % period);
+            d.part = partials;
+            partials += (size_t)d.groups * period * period * kLatticeWords;
+            return TablePlace{d.groups, (size_t)period * period * kLatticeWords};
+        },
+        [&] { return grow(c, "musica_sim_lattice", &c->study.d_lattice_part, &c->study.lattice_part_cap, partials, "partial words"); },
+        [&](const LatticeQueryDev* d_qs, int max_groups, unsigned long long* d_tables) {
+            launch_sim_lattice(c->stream, d_qs, (int)count, max_groups, (int)period, c->study.d_lattice_part, d_tables);
+        },
+        nothing,
+        [&](uint32_t i, const musica_sim_query& q, const uint64_t*) {
+            out[i].pixels = (uint64_t)(q.w - 1) * (q.h - 1);
+        });
+    ABI_CATCH("musica_sim_lattice")
+}
+
 // ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------
 static_assert(kReachMaxRadii == MUSICA_REACH_MAX_RADII && kReachMaxRadius == MUSICA_REACH_MAX_RADIUS && kReachMaxQueries == MUSICA_REACH_MAX_QUERIES &&
                   kReachWords == MUSICA_REACH_WORDS,
@@ -1609,6 +1662,13 @@ int musica_alter_blur(musica_ctx* c, uint32_t idx, uint32_t radius) {
         c, "musica_alter_blur", nullptr, idx,
         [&] { return radius < 1 || radius > MUSICA_BLUR_MAX_RADIUS ? fail("musica_alter_blur: radius %u out of range [1, %d]", radius, MUSICA_BLUR_MAX_RADIUS) : 1; },
         nothing, [&](const uint16_t* src, uint16_t* dst) { launch_blur_u16(c->stream, src, dst, c->N, (int)radius); });   // kernels_blur.hip
+}
+
+int musica_alter_codec(musica_ctx* c, uint32_t idx, const uint16_t table[64]) {
+    CodecTable t;
+    return alter_into(
+        c, "musica_alter_codec", table ? nullptr : "table", idx, [&] { return codec_check("musica_alter_codec", table, 0, t); }, nothing,
+        [&](const uint16_t* src, uint16_t* dst) { launch_codec_u16(c->stream, src, dst, c->N, 0, t); });   // kernels_codec.hip
 }
 
 int musica_alter_zoom(musica_ctx* c, uint32_t idx, uint32_t p, uint32_t q) {

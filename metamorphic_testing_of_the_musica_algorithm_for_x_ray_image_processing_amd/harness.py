@@ -916,6 +916,8 @@ GRADIENT_ROW_KEYS = {"direct": "direct_gradient", "registered": "registered_grad
                      "registered_reference": "registered_reference_gradient"}
 ORDER_ROW_KEYS = {"direct": "direct_order", "registered": "registered_order", "reference": "reference_order",
                   "registered_reference": "registered_reference_order"}
+LATTICE_ROW_KEYS = {"direct": "direct_lattice", "registered": "registered_lattice", "reference": "reference_lattice",
+                    "registered_reference": "registered_reference_lattice"}
 
 
 VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
@@ -998,7 +1000,8 @@ RELATIONS = (
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
-                  gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, order=False):
+                  gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, codecs=None,
+                  lattice=0, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1054,6 +1057,19 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         if n <= 2 * PROCESSING_MARGIN:
             raise ValueError("a side of %d pixels leaves no output plane to warp" % n)
         mp.warp_field(field, n - 2 * PROCESSING_MARGIN, PROCESSING_MARGIN)
+    try:
+        codecs = [int(s) for s in (codecs or ())]
+    except (TypeError, ValueError):
+        raise ValueError("codecs is a list of DC steps, got %r" % (codecs,))
+    for s in codecs:
+        codec_table(s)
+    if codecs and n <= 2 * PROCESSING_MARGIN:
+        raise ValueError("a side of %d pixels leaves no output plane to compress" % n)
+    if isinstance(lattice, (bool, np.bool_, str)) or not isinstance(lattice, (int, float, np.integer, np.floating)) or lattice != int(lattice):
+        raise ValueError("lattice is a period, one of %r, or 0, got %r" % (LATTICE_PERIODS, lattice))
+    lattice = int(lattice)
+    if lattice:
+        mp.lattice_period(lattice, PROCESSING_MARGIN % lattice)
     given = dict(details=details, edges=edges, gratings=gratings, gains=gains, luts=luts, points=points)
     for rel in RELATIONS:
         if given[rel.option] is not None:
@@ -1064,14 +1080,15 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
            (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + (tuple(ORDER_ROW_KEYS[k] for k in compared) if order else ()) + (("direct_reach",) if reach is not None else ()) + \
-           (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("observer",) if observer else ()) + (("warp",) if warps else ())
+           (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("observer",) if observer else ()) + (("warp",) if warps else ()) + \
+           (tuple(LATTICE_ROW_KEYS[k] for k in compared) if lattice else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), order=bool(order), observer=bool(observer), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
-        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), reach=reach, reach_tables=bool(reach_tables), reach_maps=bool(reach_maps), keys=keys, device_alterations=device_alterations,
+        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), reach=reach, reach_tables=bool(reach_tables), reach_maps=bool(reach_maps), codecs=codecs, lattice=lattice, keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
 
 
@@ -1088,7 +1105,7 @@ Alteration = collections.namedtuple("Alteration", "name host dev region move noi
 def study_alterations(raw, rng, p, seed, shape, opt):
     """Every Alteration of the study once, in the rows' order. run_study makes a row's calls before the next one is built: the rows'
     order is the order of the `rng` draws. The device's noise draws (context p, the study's seed) take the row's ordinal in the study
-    as their stream; the d4, blur, zoom, scatter, warp, cd, edge, grating, gain and lut rows draw nothing and take no ordinal."""
+    as their stream; the d4, blur, zoom, scatter, warp, codec, cd, edge, grating, gain and lut rows draw nothing and take no ordinal."""
     ordinal = itertools.count(1)
     for s in opt.shutters:
         k = next(ordinal)
@@ -1126,6 +1143,9 @@ def study_alterations(raw, rng, p, seed, shape, opt):
     for name, f in opt.warps:
         yield Alteration(name, lambda: warp(raw, f), lambda: p.alter_warp(f), lambda: roi_warp(shape, f),
                          ("sim_warp_reference", lambda plane, f: warp(plane, f, origin=(PROCESSING_MARGIN,) * 2), f), warp=f)
+    for s in opt.codecs:   # the output plane's blocks lie where the raw plane's lay: its origin is the margin mod 8
+        yield Alteration("codec_%d" % s, lambda: block_codec(raw, codec_table(s)), lambda: p.alter_codec(codec_table(s)), lambda: _frame(shape),
+                         ("sim_codec_reference", lambda plane, t: block_codec(plane, t, (PROCESSING_MARGIN % 8,) * 2), codec_table8(codec_table(s))))
     for rel in RELATIONS:
         payloads = getattr(opt, rel.option)
         carried = (rel.source(raw),) if rel.source and payloads else ()
@@ -1231,6 +1251,11 @@ class DeviceScorer(Scorer):
         res = self.proc.sim_order([(0, slot) + region for slot, region in comparisons])
         return [order_row(np.concatenate([r["rings"].ravel(), r["histogram"]])) for r in res]
 
+    def lattice(self, comparisons):
+        """One musica_sim_lattice call over the row's comparisons."""
+        res = self.proc.sim_lattice([(0, slot) + region for slot, region in comparisons], self.opt.lattice, PROCESSING_MARGIN % self.opt.lattice)
+        return [lattice_row(r["table"]) for r in res]
+
     def reach(self, comparisons):
         """One musica_sim_reach call over the row's direct comparison (the first that similarities() scored)."""
         res = self.proc.sim_reach([(0, slot) + region for slot, region in comparisons], self.opt.reach)
@@ -1296,6 +1321,10 @@ class HostScorer(Scorer):
 
     def order(self, comparisons):
         return [order_row(order_statistics(self.out, self.planes[slot], [region])[0]) for slot, region in comparisons]
+
+    def lattice(self, comparisons):
+        P = self.opt.lattice
+        return [lattice_row(lattice_statistics(self.out, self.planes[slot], [region], P, PROCESSING_MARGIN % P)[0]) for slot, region in comparisons]
 
     def reach(self, comparisons):
         """The restatement on the altered input that produce() kept."""
@@ -1366,7 +1395,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False, observer=False, order=False):
+              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1601,24 +1630,44 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     radii must give banks the call takes (r <= 32, at most OBSERVER_MAX_BANKS distinct), else ValueError before any work. Host and
     device summarise exact integers with one function, so "observer" is equal to the last bit on every path; observer_curve reads the
     threshold contrast per radius off the cd_ rows. Nothing is asserted: these are findings. With observer=False the rows, keys and
-    launches are exactly as before."""
+    launches are exactly as before.
+
+    codecs: DC steps of the lossy-compression rows (block_codec with codec_table(s); CODECS for 16, 64, 256, 1024, 4096), each in
+    1 .. 65535, else ValueError before any work. None or empty adds nothing. Otherwise rows codec_<s> follow the warp rows: the raw image
+    through the exact 8 x 8 block codec (on the device: alter_codec), "direct" against the unaltered result (how much of the codec's loss
+    reaches the output), "registered" over the whole output frame against the unaltered result compressed alike: the 8-bit plane through
+    block_codec with codec_table8 of the same table at the origin PROCESSING_MARGIN % 8, so its blocks lie where the raw plane's lay
+    (on the device: musica_sim_codec_reference into slot 1, the vendor image into slot 3). That is compress-before against
+    compress-after. Like the blur rows they draw nothing from `rng` and take no ordinal; every metric of the study applies to them.
+
+    lattice: a period P in LATTICE_PERIODS asks how much of every change sits on a lattice of the raw grid (lattice_statistics: a
+    comparison's sums folded by the position modulo P, at the origin PROCESSING_MARGIN % P, the raw plane's lattice seen from the output
+    plane): the 8 x 8 blocks of a codec row, and the decimated pyramid's own periods 2 .. 32 in the t_x_, shift_ and zoom_ rows. Every
+    comparison dict of a row gains a sibling behind all other keys: direct_lattice, registered_lattice and, with a vendor image,
+    reference_lattice and registered_reference_lattice; present exactly where the original is and None exactly where it is None. Each
+    is lattice_row's dict: per axis "x" and "y" the LATTICE_AXIS_KEYS step_a, step_b, amplified and phase_mse, then "periodic" and the
+    exact "table" (lattice_summary). On the device one musica_sim_lattice call behind the order's; on the host the restatement scores
+    the same crops. There is no float on the device and one summary function: the values are equal to the last bit on every path.
+    Anything but 0 or one of the five periods is a ValueError; with lattice=0 the rows and the launches are exactly as before. Nothing
+    asserts how much the pipeline amplifies blocking: that is the finding."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
                         edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients, points, point_tables, reach,
-                        reach_tables, reach_maps, observer=observer, order=order)
+                        reach_tables, reach_maps, observer=observer, order=order, codecs=codecs, lattice=lattice)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
     scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
     scorer.source = raw   # what reach() takes the input's change against
     metrics = [("", scorer.similarities)] + ([("_tone", scorer.tone)] if opt.tone else []) + ([("_scales", scorer.scales)] if opt.scales else []) + \
-              ([("_gradient", scorer.gradients)] if opt.gradients else []) + ([("_order", scorer.order)] if opt.order else [])
+              ([("_gradient", scorer.gradients)] if opt.gradients else []) + ([("_order", scorer.order)] if opt.order else []) + \
+              ([("_lattice", scorer.lattice)] if opt.lattice else [])
     rows = []
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, gradients, order, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, order, lattice, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -1793,6 +1842,18 @@ def reach_list(text):
         raise argparse.ArgumentTypeError(str(e))
 
 
+def codec_list(text):
+    """--codecs' comma list of DC steps 1 .. 65535."""
+    import argparse
+    try:
+        steps = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a comma-separated list of DC steps 1 .. 65535, got %r" % (text,))
+    if not steps or any(not 1 <= s <= 65535 for s in steps):
+        raise argparse.ArgumentTypeError("codec DC steps are 1 .. 65535, got %r" % (text,))
+    return steps
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Metamorphic study of raw images (or a seeded phantom) on the HIP MUSICA path")
@@ -1886,6 +1947,14 @@ def main(argv=None):
                          "the edge strength of its reference side (gradient similarity and correlation, gain, turn, reversed share, rmse, "
                          "gain per class and its compression slope), written to gradient_robustness.csv; on the GPU with --device-metrics / "
                          "--device-alterations (musica_sim_gradients)")
+    ap.add_argument("--codecs", nargs="?", const=CODECS, default=None, type=codec_list, metavar="S,S,...",
+                    help="add the rows codec_<s>: the raw image through the exact 8 x 8 integer block codec with the JPEG luminance table "
+                         "scaled to the DC step s (1 .. 65535), compared directly and with the unaltered result compressed alike "
+                         "(compress-before against compress-after); without a list, 16,64,256,1024,4096")
+    ap.add_argument("--lattice", type=int, default=0, choices=(0,) + LATTICE_PERIODS, metavar="P",
+                    help="fold every comparison's sums by the position modulo P on the raw grid (2, 4, 8, 16 or 32): the steps across the "
+                         "lattice lines, their amplification and the periodic share of the change, written to lattice_robustness.csv; on "
+                         "the GPU with --device-metrics / --device-alterations (musica_sim_lattice)")
     ap.add_argument("--order", action="store_true",
                     help="ask whether the local order of the gray levels survived: the census signs of every comparison over the 7 x 7 "
                          "neighbourhood (Kendall's tau of centre-neighbour pairs, overall and per ring, the reversed, flattened and split "
@@ -1990,6 +2059,10 @@ def main(argv=None):
         shift_args.update(covariance=args.covariance, covariance_tiles=bool(args.covariance_maps))
     if args.blurs:
         shift_args["blurs"] = args.blurs
+    if args.codecs:
+        shift_args["codecs"] = args.codecs
+    if args.lattice:
+        shift_args["lattice"] = args.lattice
     if args.zooms:
         shift_args["zooms"] = args.zooms
     if args.scatters:

@@ -1,6 +1,7 @@
 """The host restatements of the study's metrics: numpy statements of what the musica_sim_* kernels compute (include/musica.h), which the
 host study scores with and the GPU tests compare the kernels against. harness re-exports every name."""
 import math
+from fractions import Fraction
 
 import numpy as np
 from scipy import ndimage
@@ -2026,3 +2027,208 @@ def observer_curve(rows, level=1.0):
         if curve[r] is None and len(pts) == 1 and pts[0][1] == level:
             curve[r] = float(pts[0][0])
     return curve
+
+
+# ---- lossy compression: the exact 8 x 8 block codec (not in the reference's script) --------------------------------------------------
+# An input that went through a lossy block-transform codec (teleradiology, archive migration, detector firmware that compresses before
+# processing) is a perturbation every deployed processor meets, and a multi-scale contrast amplifier is the kind of processor that turns
+# invisible 8 x 8 blocking into visible structure. block_codec is an integer DCT codec stated so that a device can reproduce it bit for
+# bit: it is the contract of musica_alter_codec and musica_sim_codec_reference (include/musica.h).
+
+# M[0][x] = 512, M[u][x] = rint(512 sqrt 2 cos((2x + 1) u pi / 16)): 1024 sqrt 2 (about 1448) times the orthonormal 8-point DCT-II, rounded,
+# as literals; a forward and a backward pass together are scaled by 2^21, which the shifts of 10 and 11 bits take out
+CODEC_M = np.array([[512, 512, 512, 512, 512, 512, 512, 512],
+                    [710, 602, 402, 141, -141, -402, -602, -710],
+                    [669, 277, -277, -669, -669, -277, 277, 669],
+                    [602, -141, -710, -402, 402, 710, 141, -602],
+                    [512, -512, -512, 512, 512, -512, -512, 512],
+                    [402, -710, 141, 602, -602, -141, 710, -402],
+                    [277, -669, 669, -277, -277, 669, -669, 277],
+                    [141, -402, 602, -710, 710, -602, 402, -141]], dtype=np.int64)
+# The luminance quantisation table of ITU-T T.81 (JPEG), Annex K, table K.1, indexed [v][u]
+CODEC_K = np.array([[16, 11, 10, 16, 24, 40, 51, 61],
+                    [12, 12, 14, 19, 26, 58, 60, 55],
+                    [14, 13, 16, 24, 40, 57, 69, 56],
+                    [14, 17, 22, 29, 51, 87, 80, 62],
+                    [18, 22, 37, 56, 68, 109, 103, 77],
+                    [24, 35, 55, 64, 81, 104, 113, 92],
+                    [49, 64, 78, 87, 103, 121, 120, 101],
+                    [72, 92, 95, 98, 112, 100, 103, 99]], dtype=np.int64)
+CODECS = (16, 64, 256, 1024, 4096)   # the study's DC steps: 4096 is the 8-bit quality-50 table at 16-bit scale
+
+
+def codec_table(s):
+    """The study's quantiser table of DC step s: clip((K s + 8) >> 4, 1, 65535) with K the Annex K luminance table, so Q[0][0] = s exactly
+    (s in 1 .. 65535, else ValueError). An (8, 8) uint16 array indexed [v][u]."""
+    s = int(s)
+    if not 1 <= s <= 65535:
+        raise ValueError("codec step %d is not in 1 .. 65535" % s)
+    return np.clip((CODEC_K * s + 8) >> 4, 1, 65535).astype(np.uint16)
+
+
+def codec_table8(table):
+    """The table of a processed 8-bit plane that goes with a 16-bit table: max(1, (table + 128) >> 8)."""
+    return np.maximum(1, (mp.codec_table_words(table).astype(np.int64) + 128) >> 8).astype(np.uint16)
+
+
+def _codec_rs(t, s):
+    return (t + (1 << (s - 1))) >> s   # numpy's >> of a signed integer is arithmetic
+
+
+def codec_blocks(X, Q):
+    """block_codec's arithmetic on blocks X[..., y, x] of level-shifted int64 pixels with the table Q[v][u]: the stages A, F, F', A' and
+    X' (before the level shift back and the last clamp) and the raw products X M^T, M A, M^T F' and A' M, whose bounds are the int32
+    contract. A dict of int64 arrays."""
+    M = CODEC_M
+    p1 = X @ M.T                                       # [y][u]
+    A = _codec_rs(p1, 10)
+    p2 = M @ A                                         # [v][u]
+    F = _codec_rs(p2, 11)
+    Fq = np.sign(F) * ((np.abs(F) + (Q >> 1)) // Q) * Q
+    p3 = M.T @ Fq                                      # [y][u]
+    A2 = np.clip(_codec_rs(p3, 10), -(1 << 18), (1 << 18) - 1)
+    p4 = A2 @ M                                        # [y][x]
+    return {"XMt": p1, "A": A, "MA": p2, "F": F, "Fq": Fq, "MtF": p3, "A2": A2, "A2M": p4, "X2": _codec_rs(p4, 11)}
+
+
+def block_codec(plane, table, origin=(0, 0)):
+    """The exact 8 x 8 integer block codec of a square 2-D uint16 (bits = 16) or uint8 (bits = 8) plane of side n. table: 8 x 8 integers
+    1 .. 65535, the quantiser step per coefficient, indexed [v][u] with v the vertical frequency. origin = (oy, ox), each 0 .. 7, places
+    the plane on a larger grid: blocks start at x = -ox and y = -oy (mod 8). A block that sticks out of the plane is completed by edge
+    replication, as JPEG does; only in-plane pixels are returned. Per block everything is int32-sized integers, with
+    rs(t, s) = (t + 2^(s - 1)) >> s (arithmetic shift) and M = CODEC_M:
+        X  = v - 2^(bits - 1)
+        A  = rs(X M^T, 10)                           rows        |X M^T| <= 2^27
+        F  = rs(M A, 11)                             columns     |M A| <= 2^29, |F| <= 2^18 (the orthonormal DCT, DC = 8 mean exactly)
+        q  = sign(F) ((|F| + (Q >> 1)) div Q)        halves away from zero
+        F' = q Q                                     |F'| <= 2^18 + 32767
+        A' = clamp(rs(M^T F', 10), -2^18, 2^18 - 1)  |M^T F'| <= 3825 (2^18 + 32767) < 2^31; the clamp is part of the contract
+        X' = rs(A' M, 11)                            |A' M| <= 2^30
+        out = clamp(X' + 2^(bits - 1), 0, 2^bits - 1)
+    A constant block comes back exactly whenever Q[0][0] divides 8 X; M departs from orthogonality by 0.06 %, so Q = 1 is not lossless.
+    The result has the input's dtype. ValueError for anything else."""
+    plane = np.asarray(plane)
+    if plane.ndim != 2 or plane.shape[0] != plane.shape[1] or plane.dtype not in (np.uint16, np.uint8) or not plane.size:
+        raise ValueError("block_codec needs a non-empty square 2-D uint16 or uint8 plane, got %r %s" % (plane.shape, plane.dtype))
+    Q = mp.codec_table_words(table).astype(np.int64)
+    try:
+        oy, ox = (int(v) for v in origin)
+    except (TypeError, ValueError):
+        raise ValueError("a codec origin is (oy, ox), got %r" % (origin,))
+    if not (0 <= oy <= 7 and 0 <= ox <= 7):
+        raise ValueError("codec origin %r is not in 0 .. 7" % (origin,))
+    n = plane.shape[0]
+    bits = 8 * plane.dtype.itemsize
+    half = 1 << (bits - 1)
+    by, bx = (n + oy + 7) // 8, (n + ox + 7) // 8
+    grid = np.pad(plane.astype(np.int64), ((oy, 8 * by - n - oy), (ox, 8 * bx - n - ox)), mode="edge")
+    X = grid.reshape(by, 8, bx, 8).transpose(0, 2, 1, 3) - half
+    out = codec_blocks(X, Q)["X2"].transpose(0, 2, 1, 3).reshape(8 * by, 8 * bx) + half
+    return np.clip(out, 0, (1 << bits) - 1)[oy:oy + n, ox:ox + n].astype(plane.dtype)
+
+
+# ---- lattice sums: a comparison folded by the position modulo a period (not in the reference's script) --------------------------------
+# Blocking is a lattice artefact, and so is the shift variance of the decimated pyramid, with periods 2, 4 .. 32 on the raw grid. No other
+# metric conditions on a pixel's position modulo a period. lattice_statistics is the contract of musica_sim_lattice (include/musica.h),
+# whose tables are bit-identical to it; lattice_summary is what the study reports of the integers, one function for every path.
+
+LATTICE_PERIODS = (2, 4, 8, 16, 32)
+
+
+def lattice_statistics(a, b, queries, period, origin):
+    """What musica_sim_lattice returns for every query (ax, ay, bx, by, w, h), w, h >= 2, of two 2-D uint8 planes (side a, side b): a
+    list of (P, P, 8) uint64 tables, P = period in LATTICE_PERIODS, origin o in 0 .. P - 1. The sums run over the query's pixels (i, j)
+    with i < w - 1 and j < h - 1, so that every counted pixel has a right and a lower neighbour inside the region; the class of a pixel
+    is [(ay + j + o) mod P][(ax + i + o) mod P], side a's position on the raw grid. Per class (processing.LATTICE_FIELDS): n, sum a,
+    sum b, sum (a - b)^2, sum (a[i + 1] - a[i])^2, the same of b, sum (a[j + 1] - a[j])^2, the same of b."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("lattice_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    P, o = mp.lattice_period(period, origin)
+    res = []
+    for region in queries:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 2 or h < 2 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is smaller than 2 x 2 or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        pa, pb = a[ay:ay + h, ax:ax + w].astype(np.int64), b[by:by + h, bx:bx + w].astype(np.int64)
+        ca, cb = pa[:-1, :-1], pb[:-1, :-1]
+        fields = [np.ones_like(ca), ca, cb, (ca - cb) ** 2, (pa[:-1, 1:] - ca) ** 2, (pb[:-1, 1:] - cb) ** 2, (pa[1:, :-1] - ca) ** 2, (pb[1:, :-1] - cb) ** 2]
+        cls = (((ay + o + np.arange(h - 1)) % P)[:, None] * P + ((ax + o + np.arange(w - 1)) % P)[None, :]).ravel()
+        table = np.stack([_int_bincount(cls, f.ravel(), P * P) for f in fields], axis=1)
+        res.append(table.reshape(P, P, len(fields)).astype(np.uint64))
+    return res
+
+
+def _int_bincount(classes, values, count):
+    """sum of the int64 `values` per class, exactly (np.bincount's weights are doubles)."""
+    out = np.zeros(count, dtype=np.int64)
+    np.add.at(out, classes, values)
+    return out
+
+
+def lattice_fold(table, period):
+    """A (P, P, 8) lattice table folded by phase mod `period` (a divisor of P): the table of that period with the origin o mod period."""
+    t = np.asarray(table)
+    P = t.shape[0]
+    if t.ndim != 3 or t.shape[1] != P or P % int(period):
+        raise ValueError("a lattice table is (P, P, 8) and folds to a divisor of P, got %r to %r" % (t.shape, period))
+    p = int(period)
+    return t.reshape(P // p, p, P // p, p, t.shape[2]).sum(axis=(0, 2), dtype=t.dtype)
+
+
+LATTICE_AXIS_KEYS = ("step_a", "step_b", "amplified", "phase_mse")   # lattice_summary's numbers per axis; "periodic" beside the axes
+
+
+def lattice_summary(table):
+    """What the study reports of a comparison's lattice sums, from lattice_statistics' (or musica_sim_lattice's) exact integers of ONE
+    query: one function for every study path. With the table summed over the other axis' phases, per axis ("x": the column phase and
+    the horizontal steps, "y": the row phase and the vertical steps):
+        step_a, step_b  the mean squared step across the lattice line (phase P - 1 -> 0) over the mean squared step at the other phases
+        amplified       step_a / step_b
+        phase_mse       {p: the largest over the mean of the p per-phase mse} for every period p | P, p >= 2, the table folded to p
+    and "periodic": the share of sum (d - mean d)^2, d = a - b, carried by the class means of d over the P^2 classes. A quotient with
+    a zero denominator is None. Every float is one division of exact integers (the phase_mse mean: of exact fractions). No threshold is
+    fixed here: these are findings."""
+    t = np.asarray(table)
+    if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[0] not in LATTICE_PERIODS or t.shape[2] != len(mp.LATTICE_FIELDS) or t.dtype.kind not in "iu":
+        raise ValueError("a lattice table is (P, P, %d) integers with P in %r, got %r %s" % (len(mp.LATTICE_FIELDS), LATTICE_PERIODS, t.shape, t.dtype))
+    P = t.shape[0]
+    v = [[[int(x) for x in cell] for cell in row] for row in t]
+    out = {}
+    for axis, name, fa, fb in ((1, "x", 4, 5), (0, "y", 6, 7)):
+        # per phase along the axis: every field summed over the other axis
+        line = [[sum((v[k][p] if axis == 1 else v[p][k])[f] for k in range(P)) for f in range(len(mp.LATTICE_FIELDS))] for p in range(P)]
+        steps = {}
+        for key, f in (("step_a", fa), ("step_b", fb)):
+            across = (line[P - 1][f], line[P - 1][0])
+            others = (sum(line[p][f] for p in range(P - 1)), sum(line[p][0] for p in range(P - 1)))
+            steps[key] = (across[0] * others[1], across[1] * others[0])   # the quotient of the two means as one fraction
+        entry = {k: (n / d if d else None) for k, (n, d) in steps.items()}
+        (na, da), (nb, db) = steps["step_a"], steps["step_b"]
+        entry["amplified"] = (na * db) / (da * nb) if da and db and nb else None
+        entry["phase_mse"] = {}
+        p = 2
+        while p <= P:
+            folded = [(sum(line[k][3] for k in range(P) if k % p == ph), sum(line[k][0] for k in range(P) if k % p == ph)) for ph in range(p)]
+            if any(n == 0 for _, n in folded):
+                entry["phase_mse"][p] = None
+            else:
+                mses = [Fraction(s, n) for s, n in folded]
+                mean = sum(mses) / p
+                entry["phase_mse"][p] = float(max(mses) / mean) if mean else None
+            p *= 2
+        out[name] = entry
+    cells = [c for row in v for c in row]
+    n = sum(c[0] for c in cells)
+    sd = sum(c[1] - c[2] for c in cells)
+    sdd = sum(c[3] for c in cells)
+    # n times the sums of squares, so that everything stays an integer: total = n sum d^2 - (sum d)^2
+    total = n * sdd - sd * sd
+    between = sum((Fraction((c[1] - c[2]) ** 2, c[0]) for c in cells if c[0]), Fraction(0)) * n - sd * sd
+    out["periodic"] = float(between / total) if total else None
+    return out
+
+
+def lattice_row(table):
+    """A row's *_lattice value: lattice_summary's dict and "table", the (P, P, 8) exact integers as nested lists."""
+    return dict(lattice_summary(table), table=np.asarray(table).astype(np.uint64).tolist())

@@ -199,6 +199,8 @@ OBSERVER_MAX_VIEWS = 1024   # MUSICA_OBSERVER_MAX_VIEWS
 OBSERVER_MAX_BANKS = 8      # MUSICA_OBSERVER_MAX_BANKS
 OBSERVER_MAX_CHANNELS = 16  # MUSICA_OBSERVER_MAX_CHANNELS
 OBSERVER_MAX_HALF = 66      # MUSICA_OBSERVER_MAX_HALF: 2 * 32 + 2, the box of a radius-32 detail
+LATTICE_MAX_PERIOD = 32     # MUSICA_LATTICE_MAX_PERIOD
+LATTICE_MAX_QUERIES = 16    # MUSICA_LATTICE_MAX_QUERIES
 
 
 def zoom_ratio(zoom):
@@ -216,6 +218,36 @@ def zoom_ratio(zoom):
     if math.gcd(p, q) != 1:
         raise ValueError("zoom %d / %d is not in lowest terms" % (p, q))
     return p, q
+
+
+def codec_table_words(table):
+    """A quantiser table as metrics.block_codec and the library take it: 8 x 8 integers 1 .. 65535, indexed [v][u], as a C-contiguous
+    (8, 8) uint16 array; else ValueError."""
+    try:
+        t = np.asarray(table)
+        if t.shape != (8, 8) or t.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("a codec table is 8 x 8 integers, got %r" % (table,))
+    if int(t.min()) < 1 or int(t.max()) > 65535:
+        raise ValueError("codec table entries are 1 .. 65535, got %d .. %d" % (int(t.min()), int(t.max())))
+    return np.ascontiguousarray(t, dtype=np.uint16)
+
+
+def lattice_period(period, origin):
+    """(P, o) of a lattice as metrics.lattice_statistics and the library take it: P one of 2, 4, 8, 16, 32 and the origin 0 <= o < P,
+    integers, else ValueError."""
+    try:
+        if period != int(period) or origin != int(origin):
+            raise TypeError
+        P, o = int(period), int(origin)
+    except (TypeError, ValueError):
+        raise ValueError("a lattice is a period and an origin, integers, got %r, %r" % (period, origin))
+    if P not in (2, 4, 8, 16, 32):
+        raise ValueError("lattice period %d is not one of 2, 4, 8, 16, 32" % P)
+    if not 0 <= o < P:
+        raise ValueError("lattice origin %d is not in 0 .. %d" % (o, P - 1))
+    return P, o
 
 
 def scatter_spec(spec):
@@ -635,6 +667,14 @@ class SimOrderResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64)]
 
 
+LATTICE_FIELDS = ("n", "sum_a", "sum_b", "sum_dd", "step_x_a", "step_x_b", "step_y_a", "step_y_b")   # the eight words of a class of a lattice table (MUSICA_LATTICE_WORDS)
+
+
+class SimLatticeResult(C.Structure):
+    """musica_sim_lattice_result: where a query's table lies in `tables` and the number of counted pixels."""
+    _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64)]
+
+
 class SimDisplaceResult(C.Structure):
     """musica_sim_displace_result: where one comparison's exact block matching puts the output."""
     _fields_ = [("pixels", C.c_uint64), ("ssd_zero", C.c_uint64), ("ssd_min", C.c_uint64), ("dx", C.c_int32), ("dy", C.c_int32),
@@ -829,6 +869,8 @@ ABI = {
     "musica_sim_transform_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_blur_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_blur": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
+    "musica_sim_codec_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32]),
+    "musica_alter_codec": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_uint16)]),
     "musica_sim_zoom_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_alter_zoom": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "musica_sim_scatter_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -854,6 +896,7 @@ ABI = {
     "musica_sim_reach": (C.c_int, [_VP, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimReachResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_reach_classes": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, _U8P]),
     "musica_sim_order": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimOrderResult), C.POINTER(C.c_uint64), C.c_uint64]),
+    "musica_sim_lattice": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimLatticeResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -1247,6 +1290,15 @@ class MusicaProcessing:
             raise ValueError("blur radius %d is not in 1 .. %d" % (radius, BLUR_MAX_RADIUS))
         self._ok(self._lib.musica_sim_blur_reference(self._h, int(dst_slot), int(src_slot), int(radius)), "musica_sim_blur_reference")
 
+    def sim_codec_reference(self, dst_slot, src_slot, table, origin=OUT_MARGIN % 8):
+        """Reference slot `src_slot` as metrics.block_codec(slot, table, (origin, origin)) (table: codec_table_words; origin 0 .. 7) into
+        `dst_slot`, on the device. The default origin is the margin mod 8: the blocks of the raw plane, seen from the output plane."""
+        t = codec_table_words(table)
+        if not 0 <= int(origin) <= 7:
+            raise ValueError("codec origin %d is not in 0 .. 7" % origin)
+        self._ok(self._lib.musica_sim_codec_reference(self._h, int(dst_slot), int(src_slot), t.ctypes.data_as(C.POINTER(C.c_uint16)), int(origin)),
+                 "musica_sim_codec_reference")
+
     def sim_zoom_reference(self, dst_slot, src_slot, zoom):
         """Reference slot `src_slot` as harness.zoom(slot, zoom) (zoom = (p, q): zoom_ratio) into `dst_slot`, on the device."""
         p, q = zoom_ratio(zoom)
@@ -1330,7 +1382,7 @@ class MusicaProcessing:
         return out
 
     def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False):
-        """What sim_profiles / _levels / _gradients / _order / _reach share: the refusals of sim_<name> before any call (most: 1 .. most
+        """What sim_profiles / _levels / _gradients / _order / _lattice / _reach share: the refusals of sim_<name> before any call (most: 1 .. most
         queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead` in front of
         the count. Returns the results and the flat tables, `words` zeroed words of `dtype`."""
         if most is not None and not 1 <= len(qs) <= most:
@@ -1401,6 +1453,24 @@ class MusicaProcessing:
             at = int(r.table_offset)
             out.append({"rings": tables[at:at + head].reshape(ORDER_RINGS, len(ORDER_FIELDS)).copy(),
                         "histogram": tables[at + head:at + ORDER_TABLE_WORDS].copy(), "pixels": int(r.pixels)})
+        return out
+
+    def sim_lattice(self, queries, period, origin=0):
+        """metrics.lattice_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 2, 1 .. LATTICE_MAX_QUERIES of them, all in one launch; period one of 2, 4, 8, 16, 32 and origin below it
+        (lattice_period: ValueError before any call, as for a count or a side out of range). Returns one dict per query: "table", a
+        (P, P, 8) uint64 array of the exact LATTICE_FIELDS per [row phase][column phase], and the Python int "pixels" = (w - 1) (h - 1)."""
+        P, o = lattice_period(period, origin)
+        qs = _queries(queries)
+        for i, q in enumerate(qs):
+            if q.w < 2 or q.h < 2:
+                raise ValueError("sim_lattice: query %d: region %d x %d is smaller than 2 x 2" % (i, q.w, q.h))
+        per = P * P * len(LATTICE_FIELDS)
+        res, tables = self._sim_tables("lattice", qs, SimLatticeResult, np.uint64, len(qs) * per, P, o, most=LATTICE_MAX_QUERIES)
+        out = []
+        for r in res:
+            at = int(r.table_offset)
+            out.append({"table": tables[at:at + per].reshape(P, P, len(LATTICE_FIELDS)).copy(), "pixels": int(r.pixels)})
         return out
 
     def sim_reach(self, queries, radii):
@@ -1622,6 +1692,11 @@ class MusicaProcessing:
         if int(radius) < 0:
             raise ValueError("blur radius %d is not in 1 .. %d" % (radius, BLUR_MAX_RADIUS))
         self._ok(self._lib.musica_alter_blur(self._h, int(image_index), int(radius)), "musica_alter_blur")
+
+    def alter_codec(self, table, image_index=0):
+        """metrics.block_codec(src, table): the exact 8 x 8 integer block codec with the quantiser table `table` (codec_table_words)."""
+        t = codec_table_words(table)
+        self._ok(self._lib.musica_alter_codec(self._h, int(image_index), t.ctypes.data_as(C.POINTER(C.c_uint16))), "musica_alter_codec")
 
     def alter_zoom(self, zoom, image_index=0):
         """harness.zoom(src, zoom): the exact bilinear magnification by p / q about the centre, zoom = (p, q) (zoom_ratio)."""

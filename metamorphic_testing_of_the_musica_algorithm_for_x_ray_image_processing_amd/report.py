@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
+from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -34,6 +34,13 @@ GRADIENT_CSV_GROUPS = (('direct_gradient', 'altered vs unaltered'), ('registered
 ORDER_CSV_GROUPS = (('direct_order', 'altered vs unaltered'), ('registered_order', 'registered vs unaltered'),
                     ('reference_order', 'altered vs reference'), ('registered_reference_order', 'registered vs reference'))
 ORDER_CSV_HEADER = ['raw file', 'alteration', 'comparison'] + [c for k in ORDER_KEYS for c in (['tau ring %d' % (i + 1) for i in range(mp.ORDER_RINGS)] if k == "tau_by_ring" else [k])]
+
+# lattice_robustness.csv: one line per row and comparison the row has, in this order; per axis the steps, then phase_mse per period
+LATTICE_CSV_GROUPS = (('direct_lattice', 'altered vs unaltered'), ('registered_lattice', 'registered vs unaltered'),
+                      ('reference_lattice', 'altered vs reference'), ('registered_reference_lattice', 'registered vs reference'))
+LATTICE_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'period', 'periodic'] + \
+                     ['%s %s' % (axis, c) for axis in ("x", "y") for k in LATTICE_AXIS_KEYS
+                      for c in (['phase mse %d' % p for p in LATTICE_PERIODS] if k == "phase_mse" else [k.replace('_', ' ')])]
 
 ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
 ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
@@ -180,6 +187,21 @@ def _order_lines(studies):
                     yield [raw_name, r["alteration"], label] + [c for k in ORDER_KEYS for c in (list(t[k]) if k == "tau_by_ring" else [t[k]])]
 
 
+def _lattice_lines(studies):
+    """lattice_robustness.csv's lines: one per row and comparison that the row has (LATTICE_CSV_GROUPS' order), the unaltered row
+    included: the raw file, the alteration, the comparison, the period, the periodic share, then per axis the LATTICE_AXIS_KEYS with
+    phase_mse in a column per period of LATTICE_PERIODS (empty beyond the study's period, as every value that is None)."""
+    blank = lambda v: "" if v is None else v
+    for raw_name, rows in studies:
+        for r in rows:
+            for key, label in LATTICE_CSV_GROUPS:
+                t = r.get(key)
+                if t is not None:
+                    yield [raw_name, r["alteration"], label, len(t["table"]), blank(t["periodic"])] + \
+                          [c for axis in ("x", "y") for k in LATTICE_AXIS_KEYS
+                           for c in ([blank(t[axis][k].get(p)) for p in LATTICE_PERIODS] if k == "phase_mse" else [blank(t[axis][k])])]
+
+
 def _spread_cells(count, keys, stats):
     return lambda d, g: [g[count]] + [g[k][w] for k in keys for w in stats] + [d["outside_mse"]]
 
@@ -232,6 +254,10 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     Studies run with order (rows[0] has "direct_order") also get order_robustness.csv (ORDER_CSV_HEADER): one line per row, the
     unaltered one included, and comparison that the row has (none for a comparison that is None): the comparison's name, then
     order_summary's ORDER_KEYS, tau_by_ring in three columns.
+
+    Studies run with lattice=P (rows[0] has "direct_lattice") also get lattice_robustness.csv (LATTICE_CSV_HEADER): one line per row,
+    the unaltered one included, and comparison that the row has: the comparison's name, the period, the periodic share, then per axis
+    step a, step b, amplified and the largest-over-mean per-phase mse of every period up to P.
 
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
@@ -314,6 +340,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
             _write_csv(out_dir, name, header, _lines(covered, cells))
     if having("direct_order"):
         _write_csv(out_dir, "order_robustness.csv", ORDER_CSV_HEADER, _order_lines(having("direct_order")))
+    if having("direct_lattice"):
+        _write_csv(out_dir, "lattice_robustness.csv", LATTICE_CSV_HEADER, _lattice_lines(having("direct_lattice")))
     for name, header, key, groups, cells in RELATION_CSVS:
         if having(key):
             _write_csv(out_dir, name, header, _group_lines(having(key), key, groups, cells))
