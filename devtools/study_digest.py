@@ -40,7 +40,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     1024 into image 0, and slot 0 through its 8-bit table at the margin's origin 2 into slot 1; integers only;
   * the lattice sums at N = 151 of other images' outputs against slot 0, at period 8 (origin 2) and period 32 (origin 10): the full
     frame (130 x 130 counted pixels: 3 x 3 tiles with a two-pixel ragged tail), a ragged region from mid-tile with different origins on
-    the two sides, a 2-wide column and a 2 x 2 corner; integers only.
+    the two sides, a 2-wide column and a 2 x 2 corner; integers only;
+  * the connected components at N = 151 of other images' outputs against slot 0 (noise against noise: a dense mask at threshold 0, a
+    sparse one at 3), 4- and 8-connected, label planes included: the full frame (131 x 131: 3 x 3 tiles with a three-pixel ragged
+    tail), a ragged region from mid-tile with different origins on the two sides, a one-pixel column and a single pixel; integers only.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -181,5 +184,8 @@ if hasattr(p, "alter_codec"):     # likewise a --tree from before the block code
 if hasattr(p, "sim_lattice"):     # likewise a --tree from before the lattice sums
     qs = [(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 2, NW - 1), (1, 0, NW - 2, NW - 2, 0, 0, 2, 2)]
     note("musica_sim_lattice", [p.sim_lattice(qs, 8, 2), p.sim_lattice(qs, 32, 10)])
+if hasattr(p, "sim_blobs"):       # likewise a --tree from before the cluster metric
+    qs = [(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 1, NW - 1), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)]
+    note("musica_sim_blobs", [p.sim_blobs(qs, t, c, labels=True) for t in (0, 3) for c in (4, 8)])
 p.cleanup()
 print(json.dumps(digests))

@@ -1149,6 +1149,44 @@ typedef struct musica_sim_lattice_result {
 int musica_sim_lattice(musica_ctx* ctx, uint32_t period, uint32_t origin, uint32_t count, const musica_sim_query* queries,
                        musica_sim_lattice_result* results, uint64_t* tables, uint64_t table_words);
 
+/* ---- blobs: the connected components of a comparison's change mask (new, not in the reference) ----
+ * Every other measurement sums a comparison over a set chosen before the pixels are looked at; this one asks whether the changed pixels
+ * form objects: scattered single-pixel flips against halos, seams, rings and blocks. metrics.blob_statistics is the contract. Queries
+ * are musica_sim_compare's with w, h >= 1, at most MUSICA_BLOBS_MAX_QUERIES (a row's direct, registered and two vendor comparisons).
+ * The mask of a query is |a - b| > threshold (0 .. 254) over its w x h pixels; two mask pixels are connected when they are neighbours
+ * (connectivity 4: in a row or a column; 8: diagonally too), through pixels of the region only. The label of a component is 1 + the
+ * row-major index y w + x, within the region, of its first pixel; 0 off the mask. Query i gets MUSICA_BLOB_CLASSES * MUSICA_BLOB_WORDS
+ * uint64_t in the flat `tables`, from results[i].table_offset (in words) on; the class of a component of n pixels is
+ * bit_length(n) - 1 (class 0: single pixels, class 1: 2 .. 3, ..), and per class
+ *   components, pixels, sum |a - b|, sum (a - b)^2, the sum of the bounding boxes' areas, components with a pixel on the region's outline
+ * The classes' pixels add up to `changed`, their components to `components`; at threshold 0 their sum (a - b)^2 adds up to
+ * musica_sim_compare's sq_diff_sum. Of components of equal size the one with the smaller first pixel is the largest; where nothing
+ * changed every largest_* is 0. `labels` may be NULL; else query i's plane of w h uint32_t labels, dense, starts at
+ * results[i].label_offset (in words; the planes lie one behind the other). Everything is an integer and the partition is unique: the
+ * results equal the restatement word for word and repeat from call to call. Every word of the tables and of the label planes is written
+ * and nothing behind them. Synchronous, on the context's stream after whatever was enqueued there; changes no slot, no result of a step
+ * and no input image; scratch is allocated on first use and regrown when a call needs more. Refused before any device work: what
+ * musica_sim_compare refuses (with the smallest side 1), then threshold > 254, a connectivity that is neither 4 nor 8, label_words below
+ * the planes' words where `labels` is given, a NULL `tables` and table_words below the tables' words. A labelling loop that reached its
+ * cap (more steps than the region has pixels: a defect, never the data) is reported as "musica_sim_blobs: internal: ..." after the call
+ * has run. After a refusal the context stays usable. */
+#define MUSICA_BLOB_CLASSES 32
+#define MUSICA_BLOB_WORDS 6
+#define MUSICA_BLOBS_MAX_QUERIES 4
+typedef struct musica_sim_blobs_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t label_offset;          /* where its label plane starts in `labels`, in words (whether or not labels are asked for) */
+    uint64_t pixels;                /* w * h */
+    uint64_t changed;               /* the mask's pixels */
+    uint64_t components;
+    uint64_t largest_sum_dd;        /* the largest component's sum (a - b)^2 */
+    uint32_t largest_n;             /* ... its pixels */
+    uint32_t largest_first;         /* ... its first pixel's row-major index in the region */
+    uint32_t largest_x0, largest_y0, largest_x1, largest_y1;   /* ... its bounding box, inclusive, in the region */
+} musica_sim_blobs_result;
+int musica_sim_blobs(musica_ctx* ctx, uint32_t threshold, uint32_t connectivity, uint32_t count, const musica_sim_query* queries,
+                     musica_sim_blobs_result* results, uint64_t* tables, uint64_t table_words, uint32_t* labels, uint64_t label_words);
+
 /* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
  * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change
  * outwards: the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global

@@ -487,6 +487,44 @@ inline int lattice_groups(int tiles, int period, int most = 0) {
 // metrics.lattice_statistics over `count` queries (grid.x = max_groups, the largest `groups`). part: room for every query's partial
 // tables; tables: every query's words, zeroed by the caller: the fold launch adds into them with u64 atomics
 void launch_sim_lattice(hipStream_t st, const LatticeQueryDev* d_qs, int count, int max_groups, int period, uint32_t* part, unsigned long long* tables);
+// kernels_blobs.hip: the cluster metric. One comparison of musica_sim_blobs: tiles_x / tiles_y: ceil(w / 64), ceil(h / 64); table: where
+// its kBlobClasses * kBlobWords u64 start in the launch's flat tables, in words; plane: where its w * h words start in each of the
+// launch's u32 planes (parent, slots, labels); tile0: the launch's tiles before its own (a tile owns kBlobTileRecords records and one
+// count); cap: more than w * h, the most steps of any data-dependent loop.
+constexpr int kBlobClasses = 32;          // MUSICA_BLOB_CLASSES: bit_length(n) - 1 of a component of n < 2^32 pixels
+constexpr int kBlobWords = 6;             // MUSICA_BLOB_WORDS: components, pixels, sum |d|, sum d^2, box area, border
+constexpr int kBlobMaxQueries = 4;        // MUSICA_BLOBS_MAX_QUERIES
+constexpr int kBlobTileSlots = 256;       // records of a tile's components that touch one of its sides (at most 252)
+constexpr int kBlobTileRecords = kBlobTileSlots + 1;   // ... and its largest component that touches none
+constexpr int kBlobSeamThreads = 128;     // k_blobs_seam: a tile's last column and last row
+struct BlobRecord {
+    uint32_t first, root;       // the first pixel of the tile-local component; its component's first pixel (== first: a root)
+    uint32_t n, x0, y0, x1, y1, pad;
+    unsigned long long sd, sdd;
+};
+struct BlobBest {               // the largest component of a query; zeros where nothing changed
+    uint32_t n, first, x0, y0, x1, y1;
+    unsigned long long sdd;
+};
+struct BlobQueryDev : SimRegion {
+    int tiles_x, tiles_y;
+    unsigned long long table, plane, tile0;
+    uint32_t cap, pad;
+};
+struct BlobScratch {
+    uint32_t* parent;           // the union-find plane, every query's w * h words
+    uint32_t* slots;            // at a record's first pixel: its index in recs; written there only
+    uint32_t* labels;           // the label planes, or nullptr where none are asked for
+    BlobRecord* recs;           // [tiles of the launch][kBlobTileRecords]
+    uint32_t* counts;           // [tiles of the launch]: the records of a tile that are in use
+    unsigned long long* best;   // [kBlobMaxQueries]: the largest key, zeroed by the caller
+    BlobBest* largest;          // [kBlobMaxQueries], zeroed by the caller
+    uint32_t* err;              // one word, zeroed by the caller: not zero after the launch where a loop hit its cap
+};
+// metrics.blob_statistics over `count` queries (grid.x = max_tiles; max_pixels: the largest w * h; records: the launch's records).
+// tables: every query's words, zeroed by the caller
+void launch_sim_blobs(hipStream_t st, const BlobQueryDev* d_qs, int count, int max_tiles, unsigned long long max_pixels, unsigned long long records, uint32_t threshold,
+                      int connectivity, const BlobScratch& s, unsigned long long* tables);
 // kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
 // Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
 constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII

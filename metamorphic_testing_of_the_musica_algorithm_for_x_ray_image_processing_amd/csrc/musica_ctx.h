@@ -175,6 +175,20 @@ struct StudyState {
     unsigned long long* d_lattice_tables = nullptr;  // [MUSICA_LATTICE_MAX_QUERIES][kLatticeMaxPeriod^2][kLatticeWords], allocated by the first musica_sim_lattice
     uint32_t* d_lattice_part = nullptr;              // the workgroups' partial tables of one call: lattice_part_cap words, regrown when a call needs more
     size_t lattice_part_cap = 0;
+    // musica_sim_blobs: the queries, the flat tables and the scratch of one call (kernels_blobs.hip: BlobScratch), each regrown when a
+    // call needs more
+    BlobQueryDev* d_blob_q = nullptr;               // [MUSICA_BLOBS_MAX_QUERIES]
+    unsigned long long* d_blob_tables = nullptr;    // [MUSICA_BLOBS_MAX_QUERIES][kBlobClasses][kBlobWords], allocated by the first musica_sim_blobs
+    uint32_t* d_blob_parent = nullptr;              // blob_plane_cap words, and as many in d_blob_slots
+    uint32_t* d_blob_slots = nullptr;
+    size_t blob_plane_cap = 0;
+    uint32_t* d_blob_labels = nullptr;              // blob_label_cap words: only calls that ask for label planes
+    size_t blob_label_cap = 0;
+    BlobRecord* d_blob_recs = nullptr;              // blob_tile_cap tiles of kBlobTileRecords records, and as many words in d_blob_counts
+    uint32_t* d_blob_counts = nullptr;
+    size_t blob_tile_cap = 0, blob_count_cap = 0;
+    unsigned long long* d_blob_best = nullptr;      // [kBlobMaxQueries] keys, then one word of errors (as u64)
+    BlobBest* d_blob_largest = nullptr;             // [kBlobMaxQueries]
     // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
     // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
     uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either

@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_codec.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
 // sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
@@ -413,7 +413,7 @@ static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion
     d.h = (int)q.h;
 }
 
-// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _reach) -----------------------------------------------
+// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _reach) -----------------------------------------------
 // Where a table call keeps its queries and its flat tables in musica_ctx::study, and what it takes: at most `most` queries with sides
 // of at least `min_side`. The tables' buffer holds `tables_cap` words from the first call on; where `grown` names its capacity it
 // holds the words of the largest call so far instead.
@@ -430,6 +430,7 @@ constexpr TableBuffers<LevelQueryDev, unsigned long long> kLevelBuffers{&StudySt
 constexpr TableBuffers<GradQueryDev, unsigned long long> kGradBuffers{&StudyState::d_grad_q, &StudyState::d_grad_tables, MUSICA_SIM_MAX_QUERIES, 7, (size_t)MUSICA_SIM_MAX_QUERIES * kGradClasses * kGradWords};
 constexpr TableBuffers<OrderQueryDev, unsigned long long> kOrderBuffers{&StudyState::d_order_q, &StudyState::d_order_tables, MUSICA_SIM_MAX_QUERIES, 7, (size_t)MUSICA_SIM_MAX_QUERIES * kOrderTableWords};
 constexpr TableBuffers<LatticeQueryDev, unsigned long long> kLatticeBuffers{&StudyState::d_lattice_q, &StudyState::d_lattice_tables, MUSICA_LATTICE_MAX_QUERIES, 2, (size_t)MUSICA_LATTICE_MAX_QUERIES * kLatticeMaxPeriod * kLatticeMaxPeriod * kLatticeWords};
+constexpr TableBuffers<BlobQueryDev, unsigned long long> kBlobBuffers{&StudyState::d_blob_q, &StudyState::d_blob_tables, MUSICA_BLOBS_MAX_QUERIES, 1, (size_t)MUSICA_BLOBS_MAX_QUERIES * kBlobClasses * kBlobWords};
 constexpr TableBuffers<ReachQueryDev, unsigned long long> kReachBuffers{&StudyState::d_reach_q, &StudyState::d_reach_tables, MUSICA_REACH_MAX_QUERIES, 1, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords};
 
 // What a call's place() says of one query: its tiles or chunks (the launch's grid.x is the largest) and the words of its table.
@@ -1244,6 +1245,89 @@ int musica_sim_lattice(musica_ctx* c, uint32_t period, uint32_t origin, uint32_t
             out[i].pixels = (uint64_t)(q.w - 1) * (q.h - 1);
         });
     ABI_CATCH("musica_sim_lattice")
+}
+
+// ---- the connected components of a comparison's change mask (musica_sim_blobs, include/musica.h; kernels_blobs.hip) --------------------
+static_assert(kBlobClasses == MUSICA_BLOB_CLASSES && kBlobWords == MUSICA_BLOB_WORDS && kBlobMaxQueries == MUSICA_BLOBS_MAX_QUERIES, "kernels_blobs.hip's constants are include/musica.h's");
+
+int musica_sim_blobs(musica_ctx* c, uint32_t threshold, uint32_t connectivity, uint32_t count, const musica_sim_query* qs, musica_sim_blobs_result* out, uint64_t* tables,
+                     uint64_t table_words, uint32_t* labels, uint64_t label_words) {
+    ABI_TRY
+    size_t pixels = 0, max_pixels = 0, tiles = 0;   // of the whole call: every query's w * h, the largest, every query's tiles
+    BlobBest largest[kBlobMaxQueries];
+    unsigned long long keys_err[kBlobMaxQueries + 1] = {};   // the keys, then the error word
+    BlobScratch s = {};
+    const int ok = sim_query_tables(
+        c, "musica_sim_blobs", kBlobBuffers, count, qs, out, tables, table_words,
+        [&] {
+            if (threshold > 254) return fail("musica_sim_blobs: threshold %u is not in 0 .. 254", threshold);
+            if (connectivity != 4 && connectivity != 8) return fail("musica_sim_blobs: connectivity %u is neither 4 nor 8", connectivity);
+            uint64_t words = 0;
+            for (uint32_t i = 0; i < count; i++) words += (uint64_t)qs[i].w * qs[i].h;
+            if (labels && label_words < words)
+                return fail("musica_sim_blobs: label_words %llu is less than the %llu words of the label planes", (unsigned long long)label_words, (unsigned long long)words);
+            return 1;
+        },
+        [&](const musica_sim_query& q, BlobQueryDev& d) {
+            const size_t n = (size_t)q.w * q.h;
+            d.plane = pixels;
+            d.tile0 = tiles;
+            d.cap = (uint32_t)std::min<size_t>(n + 64, 0xFFFFFFFEu);
+            d.pad = 0;
+            pixels += n;
+            max_pixels = std::max(max_pixels, n);
+            const int own = tile_grid(d, q.w, q.h);
+            tiles += (size_t)own;
+            return TablePlace{own, (size_t)kBlobClasses * kBlobWords};
+        },
+        [&] {
+            StudyState& st = c->study;
+            if (!grow(c, "musica_sim_blobs", &st.d_blob_parent, &st.blob_plane_cap, pixels, "plane words", 1, &st.d_blob_slots) ||
+                (labels && !grow(c, "musica_sim_blobs", &st.d_blob_labels, &st.blob_label_cap, pixels, "label words")) ||
+                !grow(c, "musica_sim_blobs", &st.d_blob_recs, &st.blob_tile_cap, tiles, "tiles of records", kBlobTileRecords) ||
+                !grow(c, "musica_sim_blobs", &st.d_blob_counts, &st.blob_count_cap, tiles, "tile counts"))
+                return 0;
+            if (!(ensure(c, &st.d_blob_best, (size_t)kBlobMaxQueries + 1) && ensure(c, &st.d_blob_largest, (size_t)kBlobMaxQueries)))
+                return fail("musica_sim_blobs: device allocation failed");
+            HIP_OK(hipMemsetAsync(st.d_blob_best, 0, sizeof(keys_err), c->stream));
+            HIP_OK(hipMemsetAsync(st.d_blob_largest, 0, sizeof(largest), c->stream));
+            s = BlobScratch{st.d_blob_parent, st.d_blob_slots, labels ? st.d_blob_labels : nullptr, st.d_blob_recs, st.d_blob_counts, st.d_blob_best, st.d_blob_largest,
+                            reinterpret_cast<uint32_t*>(st.d_blob_best + kBlobMaxQueries)};
+            return 1;
+        },
+        [&](const BlobQueryDev* d_qs, int max_tiles, unsigned long long* d_tables) {
+            launch_sim_blobs(c->stream, d_qs, (int)count, max_tiles, max_pixels, (unsigned long long)tiles * kBlobTileRecords, threshold, (int)connectivity, s, d_tables);
+        },
+        [&] {
+            HIP_OK(hipMemcpyAsync(keys_err, c->study.d_blob_best, sizeof(keys_err), hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipMemcpyAsync(largest, c->study.d_blob_largest, sizeof(largest), hipMemcpyDeviceToHost, c->stream));
+            if (labels) HIP_OK(hipMemcpyAsync(labels, c->study.d_blob_labels, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            return 1;
+        },
+        [&](uint32_t i, const musica_sim_query& q, const uint64_t* t) {
+            musica_sim_blobs_result& r = out[i];
+            const BlobBest& b = largest[i];
+            r.pixels = (uint64_t)q.w * q.h;
+            r.changed = column_sum(t, kBlobClasses, kBlobWords, 1);
+            r.components = column_sum(t, kBlobClasses, kBlobWords, 0);
+            r.largest_n = b.n;
+            r.largest_first = b.first;
+            r.largest_x0 = b.x0;
+            r.largest_y0 = b.y0;
+            r.largest_x1 = b.x1;
+            r.largest_y1 = b.y1;
+            r.largest_sum_dd = b.sdd;
+        });
+    if (!ok) return 0;
+    uint64_t at = 0;   // the label planes lie one behind the other, whether or not they were asked for
+    for (uint32_t i = 0; i < count; i++) {
+        out[i].label_offset = at;
+        at += out[i].pixels;
+    }
+    if ((uint32_t)keys_err[kBlobMaxQueries])
+        return fail("musica_sim_blobs: internal: a labelling loop hit its cap or a link did not descend (error word %u)", (uint32_t)keys_err[kBlobMaxQueries]);
+    return 1;
+    ABI_CATCH("musica_sim_blobs")
 }
 
 // ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------

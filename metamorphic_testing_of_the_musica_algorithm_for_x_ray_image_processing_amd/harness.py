@@ -918,6 +918,8 @@ ORDER_ROW_KEYS = {"direct": "direct_order", "registered": "registered_order", "r
                   "registered_reference": "registered_reference_order"}
 LATTICE_ROW_KEYS = {"direct": "direct_lattice", "registered": "registered_lattice", "reference": "reference_lattice",
                     "registered_reference": "registered_reference_lattice"}
+BLOB_ROW_KEYS = {"direct": "direct_blobs", "registered": "registered_blobs", "reference": "reference_blobs",
+                 "registered_reference": "registered_reference_blobs"}
 
 
 VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
@@ -1001,7 +1003,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
                   gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, codecs=None,
-                  lattice=0, order=False):
+                  lattice=0, blobs=None, blob_connectivity=8, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1070,6 +1072,10 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     lattice = int(lattice)
     if lattice:
         mp.lattice_period(lattice, PROCESSING_MARGIN % lattice)
+    if blobs is not None:
+        blobs = mp.blob_threshold(blobs)
+    if blob_connectivity not in (4, 8) or isinstance(blob_connectivity, (bool, np.bool_)):
+        raise ValueError("blob_connectivity is 4 or 8, got %r" % (blob_connectivity,))
     given = dict(details=details, edges=edges, gratings=gratings, gains=gains, luts=luts, points=points)
     for rel in RELATIONS:
         if given[rel.option] is not None:
@@ -1081,14 +1087,14 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
            (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
            (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + (tuple(ORDER_ROW_KEYS[k] for k in compared) if order else ()) + (("direct_reach",) if reach is not None else ()) + \
            (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("observer",) if observer else ()) + (("warp",) if warps else ()) + \
-           (tuple(LATTICE_ROW_KEYS[k] for k in compared) if lattice else ())
+           (tuple(LATTICE_ROW_KEYS[k] for k in compared) if lattice else ()) + (tuple(BLOB_ROW_KEYS[k] for k in compared) if blobs is not None else ())
     return types.SimpleNamespace(
         shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
         rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
         factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
         displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), order=bool(order), observer=bool(observer), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
         covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
-        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), reach=reach, reach_tables=bool(reach_tables), reach_maps=bool(reach_maps), codecs=codecs, lattice=lattice, keys=keys, device_alterations=device_alterations,
+        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), reach=reach, reach_tables=bool(reach_tables), reach_maps=bool(reach_maps), codecs=codecs, lattice=lattice, blobs=blobs, blob_connectivity=int(blob_connectivity), keys=keys, device_alterations=device_alterations,
         **{option: payloads or [] for option, payloads in given.items()})
 
 
@@ -1156,7 +1162,7 @@ def study_alterations(raw, rng, p, seed, shape, opt):
 class Scorer:
     """How run_study scores a row, on the host or on the device. produce(alteration) makes the altered output the one that is scored
     (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
-    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key and observer(details) a cd_ row's "observer"; similarities, tone, scales, gradients, order and shifts take the row's comparisons, (reference key, region)
+    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key and observer(details) a cd_ row's "observer"; similarities, tone, scales, gradients, order, lattice, blobs and shifts take the row's comparisons, (reference key, region)
     pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset; keep: the dicts carry their
     tile tables whatever displacement_tiles says, for a warp row's tracking); reach takes the row's direct comparison, behind
     similarities, and looks at the change of the input from `source`, the study's raw plane."""
@@ -1256,6 +1262,10 @@ class DeviceScorer(Scorer):
         res = self.proc.sim_lattice([(0, slot) + region for slot, region in comparisons], self.opt.lattice, PROCESSING_MARGIN % self.opt.lattice)
         return [lattice_row(r["table"]) for r in res]
 
+    def blobs(self, comparisons):
+        """One musica_sim_blobs call over the row's comparisons (at most four: BLOBS_MAX_QUERIES)."""
+        return [blob_row(r) for r in self.proc.sim_blobs([(0, slot) + region for slot, region in comparisons], self.opt.blobs, self.opt.blob_connectivity)]
+
     def reach(self, comparisons):
         """One musica_sim_reach call over the row's direct comparison (the first that similarities() scored)."""
         res = self.proc.sim_reach([(0, slot) + region for slot, region in comparisons], self.opt.reach)
@@ -1326,6 +1336,9 @@ class HostScorer(Scorer):
         P = self.opt.lattice
         return [lattice_row(lattice_statistics(self.out, self.planes[slot], [region], P, PROCESSING_MARGIN % P)[0]) for slot, region in comparisons]
 
+    def blobs(self, comparisons):
+        return [blob_row(blob_statistics(self.out, self.planes[slot], [region], self.opt.blobs, self.opt.blob_connectivity)[0]) for slot, region in comparisons]
+
     def reach(self, comparisons):
         """The restatement on the altered input that produce() kept."""
         classes = reach_classes(self.source, self.altered, self.opt.reach)
@@ -1395,7 +1408,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, order=False):
+              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1649,12 +1662,22 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     exact "table" (lattice_summary). On the device one musica_sim_lattice call behind the order's; on the host the restatement scores
     the same crops. There is no float on the device and one summary function: the values are equal to the last bit on every path.
     Anything but 0 or one of the five periods is a ValueError; with lattice=0 the rows and the launches are exactly as before. Nothing
-    asserts how much the pipeline amplifies blocking: that is the finding."""
+    asserts how much the pipeline amplifies blocking: that is the finding.
+
+    blobs: a threshold T in 0 .. 254 (processing.blob_threshold; None: off) asks whether the changed pixels of every comparison form
+    objects: the connected components (blob_connectivity: 4 or 8) of the mask |a - b| > T (blob_statistics). Every comparison dict of a
+    row gains a sibling behind all other keys, the lattice's included: direct_blobs, registered_blobs and, with a vendor image,
+    reference_blobs and registered_reference_blobs; present exactly where the original is and None exactly where it is None. Each is
+    blob_row's dict: blob_summary's BLOB_KEYS (the components, the changed, isolated, clustered and largest shares, the mean size, the
+    fill and the border share), "largest_box", the per-class "class_components" and "class_pixels" and the exact "table". On the device
+    one musica_sim_blobs call behind the lattice's; on the host the restatement labels the same crops. Everything is an integer and
+    there is one summary function: the values are equal to the last bit on every path. With blobs=None the rows and the launches are
+    exactly as before. Label maps are not written."""
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
                         displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
                         edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients, points, point_tables, reach,
-                        reach_tables, reach_maps, observer=observer, order=order, codecs=codecs, lattice=lattice)
+                        reach_tables, reach_maps, observer=observer, order=order, codecs=codecs, lattice=lattice, blobs=blobs, blob_connectivity=blob_connectivity)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
@@ -1662,12 +1685,12 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     scorer.source = raw   # what reach() takes the input's change against
     metrics = [("", scorer.similarities)] + ([("_tone", scorer.tone)] if opt.tone else []) + ([("_scales", scorer.scales)] if opt.scales else []) + \
               ([("_gradient", scorer.gradients)] if opt.gradients else []) + ([("_order", scorer.order)] if opt.order else []) + \
-              ([("_lattice", scorer.lattice)] if opt.lattice else [])
+              ([("_lattice", scorer.lattice)] if opt.lattice else []) + ([("_blobs", scorer.blobs)] if opt.blobs is not None else [])
     rows = []
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, gradients, order, lattice, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -1955,6 +1978,12 @@ def main(argv=None):
                     help="fold every comparison's sums by the position modulo P on the raw grid (2, 4, 8, 16 or 32): the steps across the "
                          "lattice lines, their amplification and the periodic share of the change, written to lattice_robustness.csv; on "
                          "the GPU with --device-metrics / --device-alterations (musica_sim_lattice)")
+    ap.add_argument("--blobs", type=int, default=None, choices=range(255), metavar="T",
+                    help="label the connected components of every comparison's change mask |a - b| > T (0 .. 254): how many there are, how "
+                         "much of the change is isolated pixels and how much sits in components of 16 pixels or more, the largest one's "
+                         "share and box, written to blob_robustness.csv; on the GPU with --device-metrics / --device-alterations "
+                         "(musica_sim_blobs)")
+    ap.add_argument("--blob-connectivity", type=int, default=8, choices=(4, 8), help="the neighbourhood of --blobs (default 8)")
     ap.add_argument("--order", action="store_true",
                     help="ask whether the local order of the gray levels survived: the census signs of every comparison over the 7 x 7 "
                          "neighbourhood (Kendall's tau of centre-neighbour pairs, overall and per ring, the reversed, flattened and split "
@@ -2063,6 +2092,9 @@ def main(argv=None):
         shift_args["codecs"] = args.codecs
     if args.lattice:
         shift_args["lattice"] = args.lattice
+    if args.blobs is not None:
+        shift_args["blobs"] = args.blobs
+        shift_args["blob_connectivity"] = args.blob_connectivity
     if args.zooms:
         shift_args["zooms"] = args.zooms
     if args.scatters:

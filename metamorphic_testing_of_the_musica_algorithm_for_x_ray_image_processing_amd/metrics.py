@@ -2232,3 +2232,102 @@ def lattice_summary(table):
 def lattice_row(table):
     """A row's *_lattice value: lattice_summary's dict and "table", the (P, P, 8) exact integers as nested lists."""
     return dict(lattice_summary(table), table=np.asarray(table).astype(np.uint64).tolist())
+
+
+# ---- blobs: the connected components of a comparison's change mask (not in the reference's script) ------------------------------------
+# Every other metric sums a comparison over a set chosen before the pixels are looked at; 300 isolated flips and one 300-pixel streak of
+# the same |a - b| are the same to all of them. blob_statistics labels the mask |a - b| > threshold and is the contract of
+# musica_sim_blobs (include/musica.h), whose tables, largest component and label planes are bit-identical to it; blob_summary is what the
+# study reports of the integers, one function for every path.
+
+BLOB_STRUCTURES = {4: np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]], dtype=bool), 8: np.ones((3, 3), dtype=bool)}
+BLOB_CLUSTERED_CLASS = 4   # components of 16 pixels at least: blob_summary's "clustered"
+
+
+def blob_statistics(a, b, queries, threshold, connectivity=8):
+    """What musica_sim_blobs returns for every query (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes (side a, side b): a list
+    of dicts. The mask of a query is |a - b| > threshold (processing.blob_threshold: 0 .. 254) over its pixels; connectivity 4 or 8; a
+    pixel of the region connects only to pixels of the region (scipy.ndimage.label with the matching structure, then integers only).
+    The canonical label of a component is 1 + the row-major index y w + x, within the region, of its first pixel, 0 off the mask:
+    nothing depends on scipy's numbering. Per query:
+      "table"       (BLOB_CLASSES, 6) uint64, the class of a component of n pixels being n.bit_length() - 1; per class the
+                    processing.BLOB_FIELDS components, pixels, sum_d = sum |a - b|, sum_dd = sum (a - b)^2, box_area = the sum of the
+                    bounding boxes' areas, border = the components with a pixel on the region's outline
+      "pixels"      w h;  "changed": the mask's pixels;  "components"      (Python ints)
+      "largest"     the dict n, first, x0, y0, x1, y1, sum_dd of the largest component (first: its first pixel's row-major index; the
+                    box inclusive; of equal sizes the smaller first wins); all 0 where nothing changed
+      "labels"      the (h, w) uint32 plane of the canonical labels."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("blob_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    t = mp.blob_threshold(threshold)
+    if connectivity not in BLOB_STRUCTURES:
+        raise ValueError("connectivity %r is neither 4 nor 8" % (connectivity,))
+    res = []
+    for region in queries:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        d = np.abs(a[ay:ay + h, ax:ax + w].astype(np.int64) - b[by:by + h, bx:bx + w].astype(np.int64))
+        mask = d > t
+        numbered, count = ndimage.label(mask, structure=BLOB_STRUCTURES[connectivity])
+        table = np.zeros((mp.BLOB_CLASSES, len(mp.BLOB_FIELDS)), dtype=np.uint64)
+        largest = dict.fromkeys(("n", "first", "x0", "y0", "x1", "y1", "sum_dd"), 0)
+        labels = np.zeros((h, w), dtype=np.uint32)
+        if count:
+            at = np.flatnonzero(mask)                     # ascending: the row-major order
+            of = numbered.ravel()[at] - 1                 # scipy's number of every mask pixel, from 0
+            _, where = np.unique(of, return_index=True)
+            first = at[where]                             # per component: its first pixel
+            y, x, dm = at // w, at % w, d.ravel()[at]
+            n, sd, sdd = (_int_bincount(of, v, count) for v in (np.ones_like(at), dm, dm * dm))
+            x0, y0 = np.full(count, w, dtype=np.int64), np.full(count, h, dtype=np.int64)
+            x1, y1 = np.zeros(count, dtype=np.int64), np.zeros(count, dtype=np.int64)
+            np.minimum.at(x0, of, x)
+            np.minimum.at(y0, of, y)
+            np.maximum.at(x1, of, x)
+            np.maximum.at(y1, of, y)
+            border = ((x0 == 0) | (y0 == 0) | (x1 == w - 1) | (y1 == h - 1)).astype(np.int64)
+            cls = np.array([int(v).bit_length() - 1 for v in n])
+            fields = (np.ones_like(n), n, sd, sdd, (x1 - x0 + 1) * (y1 - y0 + 1), border)
+            table = np.stack([_int_bincount(cls, f, mp.BLOB_CLASSES) for f in fields], axis=1).astype(np.uint64)
+            k = min(range(count), key=lambda i: (-int(n[i]), int(first[i])))
+            largest = {"n": int(n[k]), "first": int(first[k]), "x0": int(x0[k]), "y0": int(y0[k]), "x1": int(x1[k]), "y1": int(y1[k]), "sum_dd": int(sdd[k])}
+            labels.ravel()[at] = (first[of] + 1).astype(np.uint32)
+        res.append({"table": table, "pixels": w * h, "changed": int(mask.sum()), "components": int(count), "largest": largest, "labels": labels})
+    return res
+
+
+BLOB_KEYS = ("components", "changed", "isolated", "clustered", "largest", "largest_dd", "mean_size", "fill", "border")   # blob_summary's numbers; "largest_box", "class_components" and "class_pixels" beside them
+
+
+def blob_summary(stats):
+    """What the study reports of a comparison's components, from ONE dict of blob_statistics (or sim_blobs): one function for every
+    study path. "components": their number; then the shares, each one division of exact integers and None where nothing changed:
+        changed      the mask's pixels over the region's (0.0 where nothing changed, None only for an empty region)
+        isolated     the pixels of single-pixel components over the changed ones
+        clustered    the pixels of components of 16 pixels at least over the changed ones
+        largest      the largest component's pixels over the changed ones;  largest_dd: its sum (a - b)^2 over the mask's
+        mean_size    the changed pixels over the components
+        fill         the changed pixels over the sum of the components' box areas
+        border       the components with a pixel on the region's outline over the components
+    and "largest_box" [x0, y0, x1, y1] (None where nothing changed), "class_components" and "class_pixels", BLOB_CLASSES ints each."""
+    t = np.asarray(stats["table"])
+    if t.shape != (mp.BLOB_CLASSES, len(mp.BLOB_FIELDS)) or t.dtype.kind not in "iu":
+        raise ValueError("a blob table is (%d, %d) integers, got %r %s" % (mp.BLOB_CLASSES, len(mp.BLOB_FIELDS), t.shape, t.dtype))
+    v = [[int(x) for x in row] for row in t]
+    comps, px, sdd, area, border = (sum(row[f] for row in v) for f in (0, 1, 3, 4, 5))
+    big = stats["largest"]
+    if px != int(stats["changed"]) or comps != int(stats["components"]):
+        raise ValueError("the table's classes add up to %d pixels in %d components, the statistics say %d in %d" % (px, comps, stats["changed"], stats["components"]))
+    share = lambda n, d: n / d if d else None
+    return {"components": comps, "changed": share(px, int(stats["pixels"])), "isolated": share(v[0][1], px),
+            "clustered": share(sum(row[1] for row in v[BLOB_CLUSTERED_CLASS:]), px), "largest": share(int(big["n"]), px),
+            "largest_dd": share(int(big["sum_dd"]), sdd), "mean_size": share(px, comps), "fill": share(px, area), "border": share(border, comps),
+            "largest_box": [int(big[k]) for k in ("x0", "y0", "x1", "y1")] if px else None,
+            "class_components": [row[0] for row in v], "class_pixels": [row[1] for row in v]}
+
+
+def blob_row(stats):
+    """A row's *_blobs value: blob_summary's dict and "table", the (BLOB_CLASSES, 6) exact integers as nested lists."""
+    return dict(blob_summary(stats), table=np.asarray(stats["table"]).astype(np.uint64).tolist())

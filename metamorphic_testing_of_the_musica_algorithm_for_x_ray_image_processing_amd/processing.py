@@ -201,6 +201,8 @@ OBSERVER_MAX_CHANNELS = 16  # MUSICA_OBSERVER_MAX_CHANNELS
 OBSERVER_MAX_HALF = 66      # MUSICA_OBSERVER_MAX_HALF: 2 * 32 + 2, the box of a radius-32 detail
 LATTICE_MAX_PERIOD = 32     # MUSICA_LATTICE_MAX_PERIOD
 LATTICE_MAX_QUERIES = 16    # MUSICA_LATTICE_MAX_QUERIES
+BLOBS_MAX_QUERIES = 4       # MUSICA_BLOBS_MAX_QUERIES
+BLOB_CLASSES = 32           # MUSICA_BLOB_CLASSES
 
 
 def zoom_ratio(zoom):
@@ -248,6 +250,20 @@ def lattice_period(period, origin):
     if not 0 <= o < P:
         raise ValueError("lattice origin %d is not in 0 .. %d" % (o, P - 1))
     return P, o
+
+
+def blob_threshold(threshold):
+    """The threshold t of a change mask |a - b| > t as metrics.blob_statistics and the library take it: an integer 0 .. 254, else
+    ValueError."""
+    try:
+        if isinstance(threshold, (bool, np.bool_, str)) or threshold != int(threshold):
+            raise TypeError
+        t = int(threshold)
+    except (TypeError, ValueError):
+        raise ValueError("a blob threshold is an integer 0 .. 254, got %r" % (threshold,))
+    if not 0 <= t <= 254:
+        raise ValueError("blob threshold %d is not in 0 .. 254" % t)
+    return t
 
 
 def scatter_spec(spec):
@@ -675,6 +691,16 @@ class SimLatticeResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64)]
 
 
+BLOB_FIELDS = ("components", "pixels", "sum_d", "sum_dd", "box_area", "border")   # the six words of a class of a blob table (MUSICA_BLOB_WORDS)
+
+
+class SimBlobsResult(C.Structure):
+    """musica_sim_blobs_result: where a query's table and label plane lie, its counts and its largest component."""
+    _fields_ = [("table_offset", C.c_uint64), ("label_offset", C.c_uint64), ("pixels", C.c_uint64), ("changed", C.c_uint64), ("components", C.c_uint64),
+                ("largest_sum_dd", C.c_uint64), ("largest_n", C.c_uint32), ("largest_first", C.c_uint32), ("largest_x0", C.c_uint32), ("largest_y0", C.c_uint32),
+                ("largest_x1", C.c_uint32), ("largest_y1", C.c_uint32)]
+
+
 class SimDisplaceResult(C.Structure):
     """musica_sim_displace_result: where one comparison's exact block matching puts the output."""
     _fields_ = [("pixels", C.c_uint64), ("ssd_zero", C.c_uint64), ("ssd_min", C.c_uint64), ("dx", C.c_int32), ("dy", C.c_int32),
@@ -897,6 +923,7 @@ ABI = {
     "musica_sim_reach_classes": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, _U8P]),
     "musica_sim_order": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimOrderResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_lattice": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimLatticeResult), C.POINTER(C.c_uint64), C.c_uint64]),
+    "musica_sim_blobs": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimBlobsResult), C.POINTER(C.c_uint64), C.c_uint64, _U32P, C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
     "musica_sim_remap_reference": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U8P]),
@@ -1471,6 +1498,36 @@ class MusicaProcessing:
         for r in res:
             at = int(r.table_offset)
             out.append({"table": tables[at:at + per].reshape(P, P, len(LATTICE_FIELDS)).copy(), "pixels": int(r.pixels)})
+        return out
+
+    def sim_blobs(self, queries, threshold, connectivity=8, labels=False):
+        """metrics.blob_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or SimQuery)
+        with w, h >= 1, 1 .. BLOBS_MAX_QUERIES of them, all in one call; threshold 0 .. 254 (blob_threshold) and connectivity 4 or 8
+        (ValueError before any call, as for a count out of range). Returns one dict per query, the same as blob_statistics': "table", a
+        (BLOB_CLASSES, 6) uint64 array of the exact BLOB_FIELDS per class, the Python ints "pixels", "changed" and "components", the dict
+        "largest" (n, first, x0, y0, x1, y1, sum_dd) and, with labels=True, "labels", the (h, w) uint32 plane of the canonical labels."""
+        t = blob_threshold(threshold)
+        if connectivity not in (4, 8):
+            raise ValueError("connectivity %r is neither 4 nor 8" % (connectivity,))
+        qs = _queries(queries)
+        if not 1 <= len(qs) <= BLOBS_MAX_QUERIES:
+            raise ValueError("sim_blobs takes 1 .. %d queries, got %d" % (BLOBS_MAX_QUERIES, len(qs)))
+        per = BLOB_CLASSES * len(BLOB_FIELDS)
+        arr, res, tables = (SimQuery * len(qs))(*qs), (SimBlobsResult * len(qs))(), np.zeros(len(qs) * per, dtype=np.uint64)
+        planes = np.zeros(sum(int(q.w) * int(q.h) for q in qs), dtype=np.uint32) if labels else None
+        self._ok(self._lib.musica_sim_blobs(self._h, t, int(connectivity), len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), len(tables),
+                                            planes.ctypes.data_as(_U32P) if labels else None, len(planes) if labels else 0), "musica_sim_blobs")
+        out = []
+        for q, r in zip(qs, res):
+            at = int(r.table_offset)
+            d = {"table": tables[at:at + per].reshape(BLOB_CLASSES, len(BLOB_FIELDS)).copy(), "pixels": int(r.pixels), "changed": int(r.changed),
+                 "components": int(r.components),
+                 "largest": {"n": int(r.largest_n), "first": int(r.largest_first), "x0": int(r.largest_x0), "y0": int(r.largest_y0), "x1": int(r.largest_x1),
+                             "y1": int(r.largest_y1), "sum_dd": int(r.largest_sum_dd)}}
+            if labels:
+                lo = int(r.label_offset)
+                d["labels"] = planes[lo:lo + int(q.w) * int(q.h)].reshape(int(q.h), int(q.w)).copy()
+            out.append(d)
         return out
 
     def sim_reach(self, queries, radii):

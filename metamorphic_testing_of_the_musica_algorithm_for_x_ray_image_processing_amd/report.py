@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
+from .metrics import BLOB_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -41,6 +41,13 @@ LATTICE_CSV_GROUPS = (('direct_lattice', 'altered vs unaltered'), ('registered_l
 LATTICE_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'period', 'periodic'] + \
                      ['%s %s' % (axis, c) for axis in ("x", "y") for k in LATTICE_AXIS_KEYS
                       for c in (['phase mse %d' % p for p in LATTICE_PERIODS] if k == "phase_mse" else [k.replace('_', ' ')])]
+
+# blob_robustness.csv: one line per row and comparison the row has, in this order; blob_summary's numbers, the largest component's box,
+# then the components and the pixels of every class
+BLOB_CSV_GROUPS = (('direct_blobs', 'altered vs unaltered'), ('registered_blobs', 'registered vs unaltered'),
+                   ('reference_blobs', 'altered vs reference'), ('registered_reference_blobs', 'registered vs reference'))
+BLOB_CSV_HEADER = ['raw file', 'alteration', 'comparison'] + [k.replace('_', ' ') for k in BLOB_KEYS] + ['largest x0', 'largest y0', 'largest x1', 'largest y1'] + \
+                  ['%s class %d' % (what, c) for what in ('components', 'pixels') for c in range(mp.BLOB_CLASSES)]
 
 ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
 ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
@@ -202,6 +209,20 @@ def _lattice_lines(studies):
                            for c in ([blank(t[axis][k].get(p)) for p in LATTICE_PERIODS] if k == "phase_mse" else [blank(t[axis][k])])]
 
 
+def _blob_lines(studies):
+    """blob_robustness.csv's lines: one per row and comparison that the row has (BLOB_CSV_GROUPS' order), the unaltered row included:
+    the raw file, the alteration, the comparison, blob_summary's BLOB_KEYS, the largest component's box (empty where nothing changed,
+    as every value that is None), then the components and the pixels per class."""
+    blank = lambda v: "" if v is None else v
+    for raw_name, rows in studies:
+        for r in rows:
+            for key, label in BLOB_CSV_GROUPS:
+                t = r.get(key)
+                if t is not None:
+                    yield [raw_name, r["alteration"], label] + [blank(t[k]) for k in BLOB_KEYS] + list(t["largest_box"] or [""] * 4) + \
+                          list(t["class_components"]) + list(t["class_pixels"])
+
+
 def _spread_cells(count, keys, stats):
     return lambda d, g: [g[count]] + [g[k][w] for k in keys for w in stats] + [d["outside_mse"]]
 
@@ -258,6 +279,10 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     Studies run with lattice=P (rows[0] has "direct_lattice") also get lattice_robustness.csv (LATTICE_CSV_HEADER): one line per row,
     the unaltered one included, and comparison that the row has: the comparison's name, the period, the periodic share, then per axis
     step a, step b, amplified and the largest-over-mean per-phase mse of every period up to P.
+
+    Studies run with blobs=T (rows[0] has "direct_blobs") also get blob_robustness.csv (BLOB_CSV_HEADER): one line per row, the
+    unaltered one included, and comparison that the row has: the comparison's name, blob_summary's numbers, the largest component's
+    box, then the components and the pixels of every size class.
 
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
@@ -342,6 +367,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
         _write_csv(out_dir, "order_robustness.csv", ORDER_CSV_HEADER, _order_lines(having("direct_order")))
     if having("direct_lattice"):
         _write_csv(out_dir, "lattice_robustness.csv", LATTICE_CSV_HEADER, _lattice_lines(having("direct_lattice")))
+    if having("direct_blobs"):
+        _write_csv(out_dir, "blob_robustness.csv", BLOB_CSV_HEADER, _blob_lines(having("direct_blobs")))
     for name, header, key, groups, cells in RELATION_CSVS:
         if having(key):
             _write_csv(out_dir, name, header, _group_lines(having(key), key, groups, cells))
