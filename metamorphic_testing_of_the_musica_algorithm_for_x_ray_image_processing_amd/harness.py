@@ -15,6 +15,7 @@ The host restatements of the metrics live in metrics.py, the CSV and BMP writers
 harness.<name> reaches every one of them, and keeps the grids and generators, the registration, Runner, run_study and the command line.
 """
 import collections
+import functools
 import itertools
 import math
 import os
@@ -908,20 +909,7 @@ def read_bmp_gray(path):
 SLOT_UNALTERED, SLOT_ROTATED, SLOT_VENDOR, SLOT_VENDOR_ROTATED = 0, 1, 2, 3
 VENDOR_SLOT = {SLOT_UNALTERED: SLOT_VENDOR, SLOT_ROTATED: SLOT_VENDOR_ROTATED}
 SLOT_TONE = 4   # tone=True: slots 4 .. 7 hold the slots of a row's (at most four) comparisons remapped with their tone_lut (musica_sim_remap_reference)
-SCALE_ROW_KEYS = {"direct": "direct_scales", "registered": "registered_scales", "reference": "reference_scales",
-                  "registered_reference": "registered_reference_scales"}
-TONE_KEYS = {"direct": "direct_tone", "registered": "registered_tone", "reference": "reference_tone",
-             "registered_reference": "registered_reference_tone"}
-GRADIENT_ROW_KEYS = {"direct": "direct_gradient", "registered": "registered_gradient", "reference": "reference_gradient",
-                     "registered_reference": "registered_reference_gradient"}
-ORDER_ROW_KEYS = {"direct": "direct_order", "registered": "registered_order", "reference": "reference_order",
-                  "registered_reference": "registered_reference_order"}
-LATTICE_ROW_KEYS = {"direct": "direct_lattice", "registered": "registered_lattice", "reference": "reference_lattice",
-                    "registered_reference": "registered_reference_lattice"}
-BLOB_ROW_KEYS = {"direct": "direct_blobs", "registered": "registered_blobs", "reference": "reference_blobs",
-                 "registered_reference": "registered_reference_blobs"}
-
-
+COMPARED = ("direct", "registered", "reference", "registered_reference")   # a row's comparisons: its own two, then the same against the vendor image
 VENDOR_KEY = {"direct": "reference", "registered": "registered_reference"}   # a row's comparison -> the same against the vendor image
 
 
@@ -999,6 +987,158 @@ RELATIONS = (
 )
 
 
+def _sides(out, plane, region):
+    """The two crops of a comparison: the output by the region's a side, the reference plane by its b side."""
+    ax, ay, bx, by, w, h = region
+    return out[ay:ay + h, ax:ax + w], plane[by:by + h, bx:bx + w]
+
+
+def _checked_flag(name):
+    def check(value):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError("%s is a flag, got %r" % (name, value))
+        return bool(value)
+    return check
+
+
+def _checked_scales(scales):
+    scales = int(scales)
+    if scales and not 1 <= scales <= mp.SIM_MAX_SCALES:
+        raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
+    return scales
+
+
+def _checked_lattice(lattice):
+    if isinstance(lattice, (bool, np.bool_, str)) or not isinstance(lattice, (int, float, np.integer, np.floating)) or lattice != int(lattice):
+        raise ValueError("lattice is a period, one of %r, or 0, got %r" % (LATTICE_PERIODS, lattice))
+    if int(lattice):
+        mp.lattice_period(int(lattice), PROCESSING_MARGIN % int(lattice))
+    return int(lattice)
+
+
+def _host_scales(opt, out, plane, region):
+    r = multiscale_similarities(*_sides(out, plane, region), min(opt.scales, max_scales(region[4], region[5])))
+    return {k: r[k] for k in SCALES_KEYS}
+
+
+def _device_tone(proc, queries, opt):
+    """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
+    has at most four), then one musica_sim_compare call over the same regions for tone_ssim."""
+    res = proc.sim_joint(queries)
+    for i, (q, r) in enumerate(zip(queries, res)):
+        proc.sim_remap_reference(SLOT_TONE + i, q[1], r["tone_lut"])
+    scored = proc.sim_compare([(0, SLOT_TONE + i) + q[2:] for i, q in enumerate(queries)])
+    for r, c in zip(res, scored):
+        r["tone_ssim"] = c["ssim"]
+    return [{k: r[k] for k in mp.JOINT_METRICS} for r in res]
+
+
+def _device_scales(proc, queries, opt):
+    """One musica_sim_multiscale call per distinct scale count, ascending; the results in the comparisons' order."""
+    counts = [min(opt.scales, max_scales(q[6], q[7])) for q in queries]
+    out = [None] * len(queries)
+    for n in sorted(set(counts)):
+        idx = [i for i, c in enumerate(counts) if c == n]
+        for i, r in zip(idx, proc.sim_multiscale([queries[i] for i in idx], n)):
+            out[i] = {k: r[k] for k in SCALES_KEYS}
+    return out
+
+
+# The six metrics that score every comparison of a row, each one entry of this table, in SCORING order: the order of a row's calls.
+# option: run_study's argument; suffix: comparison <c> of a row (COMPARED) gets the sibling key <c>_<suffix>; on(value): whether the
+# normalised option asks for the metric; check(value): the option checked (ValueError) and normalised; host(opt, out, plane, region):
+# one comparison's value, the restatement on the output and the reference plane; device(proc, queries, opt): the values of a row's
+# comparisons, given as musica_sim_compare's queries, from one musica_sim_* call (at most four: BLOBS_MAX_QUERIES; tone and scales make
+# a few calls and keep a function each); csv: its file (report.METRIC_CSVS). Host and device summarise with one *_row function.
+ComparisonMetric = collections.namedtuple("ComparisonMetric", "option suffix on check host device csv")
+COMPARISON_METRICS = (
+    ComparisonMetric("tone", "tone", bool, lambda v: v, lambda opt, out, plane, region: tone_similarities(*_sides(out, plane, region)),
+                     _device_tone, METRIC_CSVS["tone"]),
+    ComparisonMetric("scales", "scales", bool, _checked_scales, _host_scales, _device_scales, METRIC_CSVS["scales"]),
+    ComparisonMetric("gradients", "gradient", bool, _checked_flag("gradients"),
+                     lambda opt, out, plane, region: gradient_row(*gradient_statistics(out, plane, [region])[0]),
+                     lambda proc, queries, opt: [gradient_row(r["table"], r["gsim"]) for r in proc.sim_gradients(queries)], METRIC_CSVS["gradient"]),
+    ComparisonMetric("order", "order", bool, _checked_flag("order"),
+                     lambda opt, out, plane, region: order_row(order_statistics(out, plane, [region])[0]),
+                     lambda proc, queries, opt: [order_row(np.concatenate([r["rings"].ravel(), r["histogram"]])) for r in proc.sim_order(queries)],
+                     METRIC_CSVS["order"]),
+    ComparisonMetric("lattice", "lattice", bool, _checked_lattice,
+                     lambda opt, out, plane, region: lattice_row(lattice_statistics(out, plane, [region], opt.lattice, PROCESSING_MARGIN % opt.lattice)[0]),
+                     lambda proc, queries, opt: [lattice_row(r["table"]) for r in proc.sim_lattice(queries, opt.lattice, PROCESSING_MARGIN % opt.lattice)],
+                     METRIC_CSVS["lattice"]),
+    ComparisonMetric("blobs", "blobs", lambda v: v is not None, lambda v: None if v is None else mp.blob_threshold(v),
+                     lambda opt, out, plane, region: blob_row(blob_statistics(out, plane, [region], opt.blobs, opt.blob_connectivity)[0]),
+                     lambda proc, queries, opt: [blob_row(r) for r in proc.sim_blobs(queries, opt.blobs, opt.blob_connectivity)], METRIC_CSVS["blobs"]),
+)
+TONE_KEYS, SCALE_ROW_KEYS, GRADIENT_ROW_KEYS, ORDER_ROW_KEYS, LATTICE_ROW_KEYS, BLOB_ROW_KEYS = \
+    ({c: "%s_%s" % (c, m.suffix) for c in COMPARED} for m in COMPARISON_METRICS[:6])   # comparison -> its sibling key, of the metrics that tests ask by name
+# The order of the refusals and of a row's keys is history, not the scoring order. These metrics are checked before the moved rows'
+# options, every other one behind them; the key groups stand in this order, a metric that is not named behind them all.
+CHECKED_EARLY = ("scales", "gradients", "order")
+KEY_GROUPS = ("tone", "shift", "scales", "gradient", "order", "reach", "ensemble", "relations", "observer", "warp", "lattice", "blobs")
+
+
+def _checked_ints(what, lo, hi):
+    """Moved.check of a list of integers lo .. hi: all converted, then each checked."""
+    def check(values, n):
+        values = [int(v) for v in values]
+        for v in values:
+            if not lo <= v <= hi:
+                raise ValueError("%s %d is not in %d .. %d" % (what, v, lo, hi))
+        return values
+    return check
+
+
+def _checked_warps(warps, n):
+    try:
+        warps = [(str(name), mp.warp_field(field, n)) for name, field in warps]
+    except TypeError:
+        raise ValueError("a warp spec is (name, field), got %r" % (warps,))
+    for _, field in warps:   # the same nodes at the origin of the output plane
+        if n <= 2 * PROCESSING_MARGIN:
+            raise ValueError("a side of %d pixels leaves no output plane to warp" % n)
+        mp.warp_field(field, n - 2 * PROCESSING_MARGIN, PROCESSING_MARGIN)
+    return warps
+
+
+def _checked_codecs(codecs, n):
+    try:
+        codecs = [int(s) for s in codecs]
+    except (TypeError, ValueError):
+        raise ValueError("codecs is a list of DC steps, got %r" % (codecs,))
+    for s in codecs:
+        codec_table(s)
+    if codecs and n <= 2 * PROCESSING_MARGIN:
+        raise ValueError("a side of %d pixels leaves no output plane to compress" % n)
+    return codecs
+
+
+# The six alterations that move a reference plane the way they move the input, each one entry of this table, in the rows' order (and
+# the refusals'). option: run_study's argument, a list of values; name(v): the row's name; check(values, n): the list checked for a raw
+# plane of side n (ValueError) and normalised; host(raw, v): the altered raw image; alter(proc, v): the same on the device;
+# region(shape, v): the region of the registered comparison; move(v): Alteration.move, (the context's sim_*_reference method, the
+# host's function of the output plane, their parameter); field(v): Alteration.warp; cli(v, n): --<option>'s value as run_study's.
+Moved = collections.namedtuple("Moved", "option name check host alter region move field cli", defaults=(None, None))
+MOVED = (
+    Moved("symmetries", lambda e: "d4_%d" % e, _checked_ints("symmetry element", 0, 7), apply_symmetry, lambda p, e: p.alter_symmetry(e),
+          lambda shape, e: roi_symmetry(shape), lambda e: ("sim_transform_reference", apply_symmetry, e)),
+    Moved("blurs", lambda r: "blur_%d" % r, _checked_ints("blur radius", 1, mp.BLUR_MAX_RADIUS), binomial_blur, lambda p, r: p.alter_blur(r), roi_blur,
+          lambda r: ("sim_blur_reference", binomial_blur, r)),
+    Moved("zooms", lambda z: "zoom_%d_%d" % z, lambda zooms, n: [mp.zoom_ratio(z) for z in zooms], zoom, lambda p, z: p.alter_zoom(z),
+          lambda shape, z: roi_zoom(shape), lambda z: ("sim_zoom_reference", zoom, z)),
+    Moved("scatters", lambda s: "scatter_%d_%d_%d" % s, lambda scatters, n: [mp.scatter_spec(s) for s in scatters], scatter, lambda p, s: p.alter_scatter(s), roi_scatter,
+          lambda s: ("sim_scatter_reference", scatter, s), cli=lambda v, n: SCATTERS(n) if v is True else v),
+    # a value: the spec (name, field); the output plane's origin on the control grid is the margin
+    Moved("warps", lambda w: w[0], _checked_warps, lambda raw, w: warp(raw, w[1]), lambda p, w: p.alter_warp(w[1]), lambda shape, w: roi_warp(shape, w[1]),
+          lambda w: ("sim_warp_reference", lambda plane, f: warp(plane, f, origin=(PROCESSING_MARGIN,) * 2), w[1]), lambda w: w[1],
+          lambda v, n: [w for w in WARPS(n) if v is True or w[0] in v]),
+    # a value: the DC step; the output plane's blocks lie where the raw plane's lay, its origin is the margin mod 8, its table the 8-bit one
+    Moved("codecs", lambda s: "codec_%d" % s, _checked_codecs, lambda raw, s: block_codec(raw, codec_table(s)), lambda p, s: p.alter_codec(codec_table(s)),
+          lambda shape, s: _frame(shape),
+          lambda s: ("sim_codec_reference", lambda plane, t: block_codec(plane, t, (PROCESSING_MARGIN % 8,) * 2), codec_table8(codec_table(s)))),
+)
+
+
 def study_options(n, runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement, displacement_tiles,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
@@ -1007,95 +1147,61 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
+    o = {k: v for k, v in locals().items() if k not in ("n", "runner")}   # every option by its name: checked and normalised in place, the namespace in the end
     if vendor is not None:
-        vendor = np.asarray(vendor)
+        o["vendor"] = vendor = np.asarray(vendor)
         want = (n - 2 * PROCESSING_MARGIN,) * 2
         if vendor.shape != want or vendor.dtype not in (np.uint8, np.uint16):
             raise ValueError("vendor image must be a %d x %d uint8 or uint16 array, got %r %s" % (want + (vendor.shape, vendor.dtype)))
-    displacement = int(displacement)
+    o["displacement"] = displacement = int(displacement)
     if displacement and not 1 <= displacement <= mp.SIM_MAX_RADIUS:
         raise ValueError("displacement radius %d is not in 1 .. %d" % (displacement, mp.SIM_MAX_RADIUS))
-    scales = int(scales)
-    if scales and not 1 <= scales <= mp.SIM_MAX_SCALES:
-        raise ValueError("scales %d is not in 1 .. %d" % (scales, mp.SIM_MAX_SCALES))
-    if not isinstance(gradients, (bool, np.bool_)):
-        raise ValueError("gradients is a flag, got %r" % (gradients,))
-    if not isinstance(order, (bool, np.bool_)):
-        raise ValueError("order is a flag, got %r" % (order,))
-    if not isinstance(observer, (bool, np.bool_)):
-        raise ValueError("observer is a flag, got %r" % (observer,))
+    for m in COMPARISON_METRICS:
+        if m.option in CHECKED_EARLY:
+            o[m.option] = m.check(o[m.option])
+    o["observer"] = _checked_flag("observer")(observer)
     if observer and details is None:
         raise ValueError("the observer looks at the details of the cd_ rows: give details")
-    if reach is None or reach is False:
-        reach = None
-    else:
-        reach = [int(r) for r in mp.reach_radii(REACH_RADII(n) if reach is True else reach)]
-    ensemble = int(ensemble)
+    o["reach"] = None if reach is None or reach is False else [int(r) for r in mp.reach_radii(REACH_RADII(n) if reach is True else reach)]
+    o["ensemble"] = ensemble = int(ensemble)
     device_alterations = getattr(runner, "device_alterations", False)
     if ensemble and not 1 <= ensemble <= mp.SIM_ENSEMBLE_MAX:
         raise ValueError("ensemble %d is not in 1 .. %d" % (ensemble, mp.SIM_ENSEMBLE_MAX))
     if ensemble and not device_alterations:
         raise ValueError("an ensemble repeats the device's noise alterations: it needs a runner with device_alterations")
-    covariance = int(covariance)
+    o["covariance"] = covariance = int(covariance)
     if covariance and not 1 <= covariance <= mp.SIM_MAX_RADIUS:
         raise ValueError("covariance radius %d is not in 1 .. %d" % (covariance, mp.SIM_MAX_RADIUS))
     if covariance and not ensemble:
         raise ValueError("covariance is taken over the realisations of an ensemble: give ensemble > 0")
-    symmetries = [int(e) for e in (symmetries or ())]
-    for e in symmetries:
-        if not 0 <= e <= 7:
-            raise ValueError("symmetry element %d is not in 0 .. 7" % e)
-    blurs = [int(r) for r in (blurs or ())]
-    for r in blurs:
-        if not 1 <= r <= mp.BLUR_MAX_RADIUS:
-            raise ValueError("blur radius %d is not in 1 .. %d" % (r, mp.BLUR_MAX_RADIUS))
-    zooms = [mp.zoom_ratio(z) for z in (zooms or ())]
-    scatters = [mp.scatter_spec(s) for s in (scatters or ())]
-    try:
-        warps = [(str(name), mp.warp_field(field, n)) for name, field in (warps or ())]
-    except TypeError:
-        raise ValueError("a warp spec is (name, field), got %r" % (warps,))
-    for _, field in warps:   # the same nodes at the origin of the output plane
-        if n <= 2 * PROCESSING_MARGIN:
-            raise ValueError("a side of %d pixels leaves no output plane to warp" % n)
-        mp.warp_field(field, n - 2 * PROCESSING_MARGIN, PROCESSING_MARGIN)
-    try:
-        codecs = [int(s) for s in (codecs or ())]
-    except (TypeError, ValueError):
-        raise ValueError("codecs is a list of DC steps, got %r" % (codecs,))
-    for s in codecs:
-        codec_table(s)
-    if codecs and n <= 2 * PROCESSING_MARGIN:
-        raise ValueError("a side of %d pixels leaves no output plane to compress" % n)
-    if isinstance(lattice, (bool, np.bool_, str)) or not isinstance(lattice, (int, float, np.integer, np.floating)) or lattice != int(lattice):
-        raise ValueError("lattice is a period, one of %r, or 0, got %r" % (LATTICE_PERIODS, lattice))
-    lattice = int(lattice)
-    if lattice:
-        mp.lattice_period(lattice, PROCESSING_MARGIN % lattice)
-    if blobs is not None:
-        blobs = mp.blob_threshold(blobs)
+    for m in MOVED:
+        o[m.option] = m.check(o[m.option] or (), n)
+    for m in COMPARISON_METRICS:
+        if m.option not in CHECKED_EARLY:
+            o[m.option] = m.check(o[m.option])
     if blob_connectivity not in (4, 8) or isinstance(blob_connectivity, (bool, np.bool_)):
         raise ValueError("blob_connectivity is 4 or 8, got %r" % (blob_connectivity,))
-    given = dict(details=details, edges=edges, gratings=gratings, gains=gains, luts=luts, points=points)
+    o["blob_connectivity"] = int(blob_connectivity)
     for rel in RELATIONS:
-        if given[rel.option] is not None:
-            given[rel.option] = rel.check(given[rel.option], n)
-    for g in (given["details"] if observer else ()):   # the views and banks of every grid, as the measurement will take them
+        if o[rel.option] is not None:
+            o[rel.option] = rel.check(o[rel.option], n)
+    for g in (o["details"] if observer else ()):   # the views and banks of every grid, as the measurement will take them
         mp.view_list(*observer_views(output_details(g)), n - 2 * PROCESSING_MARGIN)
-    compared = ("direct", "registered") + (() if vendor is None else ("reference", "registered_reference"))
-    keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + (tuple(TONE_KEYS[k] for k in compared) if tone else ()) + \
-           (("direct_shift", "registered_shift") if displacement else ()) + (tuple(SCALE_ROW_KEYS[k] for k in compared) if scales else ()) + \
-           (tuple(GRADIENT_ROW_KEYS[k] for k in compared) if gradients else ()) + (tuple(ORDER_ROW_KEYS[k] for k in compared) if order else ()) + (("direct_reach",) if reach is not None else ()) + \
-           (("ensemble",) if ensemble else ()) + tuple(rel.key for rel in RELATIONS if given[rel.option] is not None) + (("observer",) if observer else ()) + (("warp",) if warps else ()) + \
-           (tuple(LATTICE_ROW_KEYS[k] for k in compared) if lattice else ()) + (tuple(BLOB_ROW_KEYS[k] for k in compared) if blobs is not None else ())
-    return types.SimpleNamespace(
-        shutters=scaled(SHUTTERS, n) if shutters is None else shutters, translations=scaled(TRANSLATIONS, n) if translations is None else translations,
-        rotations=ROTATIONS if rotations is None else rotations, sigmas=GAUSS_SIGMAS if sigmas is None else sigmas,
-        factors=POISSON_FACTORS if factors is None else factors, vendor=vendor, symmetries=symmetries, tone=tone, displacement=displacement,
-        displacement_tiles=displacement_tiles, scales=scales, gradients=bool(gradients), order=bool(order), observer=bool(observer), ensemble=ensemble, ensemble_tiles=ensemble_tiles, covariance=covariance,
-        covariance_tiles=covariance_tiles, blurs=blurs, zooms=zooms, scatters=scatters, warps=warps, detail_tables=bool(detail_tables), edge_tables=bool(edge_tables),
-        grating_tables=bool(grating_tables), gain_tables=bool(gain_tables), lut_tables=bool(lut_tables), point_tables=bool(point_tables), reach=reach, reach_tables=bool(reach_tables), reach_maps=bool(reach_maps), codecs=codecs, lattice=lattice, blobs=blobs, blob_connectivity=int(blob_connectivity), keys=keys, device_alterations=device_alterations,
-        **{option: payloads or [] for option, payloads in given.items()})
+    compared = COMPARED[:2 if vendor is None else 4]
+    groups = {m.suffix: tuple("%s_%s" % (c, m.suffix) for c in compared) if m.on(o[m.option]) else () for m in COMPARISON_METRICS}
+    groups.update(shift=("direct_shift", "registered_shift") if displacement else (), reach=("direct_reach",) if o["reach"] is not None else (),
+                  ensemble=("ensemble",) if ensemble else (), relations=tuple(rel.key for rel in RELATIONS if o[rel.option] is not None),
+                  observer=("observer",) if observer else (), warp=("warp",) if o["warps"] else ())
+    keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + \
+           tuple(k for g in KEY_GROUPS + tuple(m.suffix for m in COMPARISON_METRICS if m.suffix not in KEY_GROUPS) for k in groups[g])
+    for grid, default in (("shutters", scaled(SHUTTERS, n)), ("translations", scaled(TRANSLATIONS, n)), ("rotations", ROTATIONS),
+                          ("sigmas", GAUSS_SIGMAS), ("factors", POISSON_FACTORS)):
+        if o[grid] is None:
+            o[grid] = default
+    for rel in RELATIONS:
+        o[rel.option], o[rel.tables] = o[rel.option] or [], bool(o[rel.tables])
+    o["reach_tables"], o["reach_maps"] = bool(reach_tables), bool(reach_maps)
+    return types.SimpleNamespace(keys=keys, device_alterations=device_alterations, **o)
 
 
 # One alteration of the study: its row's name; host() the altered raw image; dev() the call that writes it into the resident input buffer;
@@ -1134,24 +1240,10 @@ def study_alterations(raw, rng, p, seed, shape, opt):
         k = next(ordinal)
         yield Alteration("pn_%s" % f, lambda: apply_quantum_noise(raw, f, rng), lambda k=k: p.alter_poisson(f, seed, k),
                          noise=(k, lambda q, stream, i: q.alter_poisson(f, seed, stream, i)))
-    for e in opt.symmetries:
-        yield Alteration("d4_%d" % e, lambda: apply_symmetry(raw, e), lambda: p.alter_symmetry(e), lambda: roi_symmetry(shape),
-                         ("sim_transform_reference", apply_symmetry, e))
-    for r in opt.blurs:
-        yield Alteration("blur_%d" % r, lambda: binomial_blur(raw, r), lambda: p.alter_blur(r), lambda: roi_blur(shape, r),
-                         ("sim_blur_reference", binomial_blur, r))
-    for z in opt.zooms:
-        yield Alteration("zoom_%d_%d" % z, lambda: zoom(raw, z), lambda: p.alter_zoom(z), lambda: roi_zoom(shape),
-                         ("sim_zoom_reference", zoom, z))
-    for s in opt.scatters:
-        yield Alteration("scatter_%d_%d_%d" % s, lambda: scatter(raw, s), lambda: p.alter_scatter(s), lambda: roi_scatter(shape, s),
-                         ("sim_scatter_reference", scatter, s))
-    for name, f in opt.warps:
-        yield Alteration(name, lambda: warp(raw, f), lambda: p.alter_warp(f), lambda: roi_warp(shape, f),
-                         ("sim_warp_reference", lambda plane, f: warp(plane, f, origin=(PROCESSING_MARGIN,) * 2), f), warp=f)
-    for s in opt.codecs:   # the output plane's blocks lie where the raw plane's lay: its origin is the margin mod 8
-        yield Alteration("codec_%d" % s, lambda: block_codec(raw, codec_table(s)), lambda: p.alter_codec(codec_table(s)), lambda: _frame(shape),
-                         ("sim_codec_reference", lambda plane, t: block_codec(plane, t, (PROCESSING_MARGIN % 8,) * 2), codec_table8(codec_table(s))))
+    for m in MOVED:
+        for v in getattr(opt, m.option):
+            yield Alteration(m.name(v), lambda: m.host(raw, v), lambda: m.alter(p, v), lambda: m.region(shape, v), m.move(v),
+                             warp=m.field(v) if m.field else None)
     for rel in RELATIONS:
         payloads = getattr(opt, rel.option)
         carried = (rel.source(raw),) if rel.source and payloads else ()
@@ -1162,10 +1254,12 @@ def study_alterations(raw, rng, p, seed, shape, opt):
 class Scorer:
     """How run_study scores a row, on the host or on the device. produce(alteration) makes the altered output the one that is scored
     (until then it is the unaltered result); move(method, function, parameter) moves the unaltered result, and the vendor image, into
-    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key and observer(details) a cd_ row's "observer"; similarities, tone, scales, gradients, order, lattice, blobs and shifts take the row's comparisons, (reference key, region)
-    pairs with a SLOT_* number as the key, and return one result each (shifts: the regions already inset; keep: the dicts carry their
-    tile tables whatever displacement_tiles says, for a warp row's tracking); reach takes the row's direct comparison, behind
-    similarities, and looks at the change of the input from `source`, the study's raw plane."""
+    SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key and
+    observer(details) a cd_ row's "observer". similarities, score and shifts take the row's comparisons, (reference key, region) pairs
+    with a SLOT_* number as the key, and return one result each: similarities the five SIM_METRICS, score(metric, comparisons) the
+    sibling values of one entry of COMPARISON_METRICS, by the entry's host or device form, and shifts the displacement (the regions
+    already inset; keep: the dicts carry their tile tables whatever displacement_tiles says, for a warp row's tracking). reach takes
+    the row's direct comparison, behind similarities, and looks at the change of the input from `source`, the study's raw plane."""
 
     def __init__(self, runner, opt, unalt):
         self.runner, self.proc, self.opt, self.unalt = runner, runner.proc, opt, unalt
@@ -1226,45 +1320,9 @@ class DeviceScorer(Scorer):
         views, banks = observer_views(details)
         return observer_row(details, self.proc.sim_observer(views, banks, SLOT_UNALTERED))
 
-    def tone(self, comparisons):
-        """One musica_sim_joint call, every comparison's slot remapped with its tone_lut into a slot of its own from SLOT_TONE on (a row
-        has at most four), then one musica_sim_compare call over the same regions for tone_ssim."""
-        res = self.proc.sim_joint([(0, slot) + region for slot, region in comparisons])
-        for i, ((slot, _), r) in enumerate(zip(comparisons, res)):
-            self.proc.sim_remap_reference(SLOT_TONE + i, slot, r["tone_lut"])
-        scored = self.proc.sim_compare([(0, SLOT_TONE + i) + region for i, (_, region) in enumerate(comparisons)])
-        for r, c in zip(res, scored):
-            r["tone_ssim"] = c["ssim"]
-        return [{k: r[k] for k in mp.JOINT_METRICS} for r in res]
-
-    def scales(self, comparisons):
-        """One musica_sim_multiscale call per distinct scale count, ascending; the results in the comparisons' order."""
-        counts = [min(self.opt.scales, max_scales(region[4], region[5])) for _, region in comparisons]
-        out = [None] * len(comparisons)
-        for n in sorted(set(counts)):
-            idx = [i for i, c in enumerate(counts) if c == n]
-            for i, r in zip(idx, self.proc.sim_multiscale([(0, comparisons[i][0]) + comparisons[i][1] for i in idx], n)):
-                out[i] = {k: r[k] for k in SCALES_KEYS}
-        return out
-
-    def gradients(self, comparisons):
-        """One musica_sim_gradients call over the row's comparisons."""
-        res = self.proc.sim_gradients([(0, slot) + region for slot, region in comparisons])
-        return [gradient_row(r["table"], r["gsim"]) for r in res]
-
-    def order(self, comparisons):
-        """One musica_sim_order call over the row's comparisons."""
-        res = self.proc.sim_order([(0, slot) + region for slot, region in comparisons])
-        return [order_row(np.concatenate([r["rings"].ravel(), r["histogram"]])) for r in res]
-
-    def lattice(self, comparisons):
-        """One musica_sim_lattice call over the row's comparisons."""
-        res = self.proc.sim_lattice([(0, slot) + region for slot, region in comparisons], self.opt.lattice, PROCESSING_MARGIN % self.opt.lattice)
-        return [lattice_row(r["table"]) for r in res]
-
-    def blobs(self, comparisons):
-        """One musica_sim_blobs call over the row's comparisons (at most four: BLOBS_MAX_QUERIES)."""
-        return [blob_row(r) for r in self.proc.sim_blobs([(0, slot) + region for slot, region in comparisons], self.opt.blobs, self.opt.blob_connectivity)]
+    def score(self, metric, comparisons):
+        """The metric's musica_sim_* call, or calls, over the row's comparisons as musica_sim_compare's queries."""
+        return metric.device(self.proc, [(0, slot) + region for slot, region in comparisons], self.opt)
 
     def reach(self, comparisons):
         """One musica_sim_reach call over the row's direct comparison (the first that similarities() scored)."""
@@ -1301,12 +1359,8 @@ class HostScorer(Scorer):
             if slot in self.planes:
                 self.planes[moved] = function(self.planes[slot], parameter)
 
-    def sides(self, slot, region):
-        ax, ay, bx, by, w, h = region
-        return self.out[ay:ay + h, ax:ax + w], self.planes[slot][by:by + h, bx:bx + w]
-
     def similarities(self, comparisons):
-        return [similarities(*self.sides(*c)) for c in comparisons]
+        return [similarities(*_sides(self.out, self.planes[slot], region)) for slot, region in comparisons]
 
     def measure(self, relation, measured):
         frame = ()
@@ -1319,25 +1373,8 @@ class HostScorer(Scorer):
         views, banks = observer_views(details)
         return observer_row(details, channel_responses(self.out, self.planes[SLOT_UNALTERED], views, banks))
 
-    def tone(self, comparisons):
-        return [tone_similarities(*self.sides(*c)) for c in comparisons]
-
-    def scales(self, comparisons):
-        res = [multiscale_similarities(*self.sides(slot, region), min(self.opt.scales, max_scales(region[4], region[5]))) for slot, region in comparisons]
-        return [{k: r[k] for k in SCALES_KEYS} for r in res]
-
-    def gradients(self, comparisons):
-        return [gradient_row(*gradient_statistics(self.out, self.planes[slot], [region])[0]) for slot, region in comparisons]
-
-    def order(self, comparisons):
-        return [order_row(order_statistics(self.out, self.planes[slot], [region])[0]) for slot, region in comparisons]
-
-    def lattice(self, comparisons):
-        P = self.opt.lattice
-        return [lattice_row(lattice_statistics(self.out, self.planes[slot], [region], P, PROCESSING_MARGIN % P)[0]) for slot, region in comparisons]
-
-    def blobs(self, comparisons):
-        return [blob_row(blob_statistics(self.out, self.planes[slot], [region], self.opt.blobs, self.opt.blob_connectivity)[0]) for slot, region in comparisons]
+    def score(self, metric, comparisons):
+        return [metric.host(self.opt, self.out, self.planes[slot], region) for slot, region in comparisons]
 
     def reach(self, comparisons):
         """The restatement on the altered input that produce() kept."""
@@ -1345,7 +1382,7 @@ class HostScorer(Scorer):
         seeds, out = int(np.count_nonzero(self.source != self.altered)), []
         for slot, region in comparisons:
             table, = reach_statistics(self.out, self.planes[slot], classes, [region], len(self.opt.reach) + 1)
-            a, b = (p.astype(np.int64) for p in self.sides(slot, region))
+            a, b = (p.astype(np.int64) for p in _sides(self.out, self.planes[slot], region))
             out.append(self.reach_value(table, seeds, int(((a - b) ** 2).sum()), a.size, classes[PROCESSING_MARGIN:-PROCESSING_MARGIN, PROCESSING_MARGIN:-PROCESSING_MARGIN]))
         return out
 
@@ -1673,19 +1710,15 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     one musica_sim_blobs call behind the lattice's; on the host the restatement labels the same crops. Everything is an integer and
     there is one summary function: the values are equal to the last bit on every path. With blobs=None the rows and the launches are
     exactly as before. Label maps are not written."""
+    options = {k: v for k, v in locals().items() if k not in ("raw", "runner", "rng")}   # every option by its name, as study_options takes them
     rng = rng or np.random.default_rng(0)
-    opt = study_options(raw.shape[0], runner, shutters, translations, rotations, sigmas, factors, vendor, symmetries, tone, displacement,
-                        displacement_tiles, scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms, scatters, details, detail_tables,
-                        edges, edge_tables, gratings, grating_tables, gains, gain_tables, luts, lut_tables, warps, gradients, points, point_tables, reach,
-                        reach_tables, reach_maps, observer=observer, order=order, codecs=codecs, lattice=lattice, blobs=blobs, blob_connectivity=blob_connectivity)
+    opt = study_options(raw.shape[0], runner, **options)
     unalt = runner.run(raw)
     shape = unalt.shape
     full = (0, 0, 0, 0, shape[1], shape[0])
     scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
     scorer.source = raw   # what reach() takes the input's change against
-    metrics = [("", scorer.similarities)] + ([("_tone", scorer.tone)] if opt.tone else []) + ([("_scales", scorer.scales)] if opt.scales else []) + \
-              ([("_gradient", scorer.gradients)] if opt.gradients else []) + ([("_order", scorer.order)] if opt.order else []) + \
-              ([("_lattice", scorer.lattice)] if opt.lattice else []) + ([("_blobs", scorer.blobs)] if opt.blobs is not None else [])
+    metrics = [("", scorer.similarities)] + [("_" + m.suffix, functools.partial(scorer.score, m)) for m in COMPARISON_METRICS if m.on(getattr(opt, m.option))]
     rows = []
 
     def row(alteration=None, eproc=None):
@@ -1794,66 +1827,62 @@ def run_studies(entries, runner, **study_args):
     return studies
 
 
-def symmetry_list(text):
-    """--symmetries' comma list of elements 0 .. 7."""
+def _comma_list(text, parse, expected, detail=False, valid=None, refused=None):
+    """What the comma-list flags share: parse(the parts) gives the values; ArgumentTypeError(expected) where it raises ValueError
+    (detail: followed by the error's own text), ArgumentTypeError(refused) where a value is not valid()."""
     import argparse
     try:
-        elements = tuple(int(t) for t in text.split(","))
-    except ValueError:
-        raise argparse.ArgumentTypeError("expected a comma-separated list of elements 0 .. 7, got %r" % text)
-    if not elements or any(not 0 <= e <= 7 for e in elements):
-        raise argparse.ArgumentTypeError("symmetry elements are 0 .. 7, got %r" % text)
-    return elements
+        values = tuple(parse(text.split(",")))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(expected + (": %s" % e if detail and str(e) else ""))
+    if valid is not None and (not values or any(not valid(v) for v in values)):
+        raise argparse.ArgumentTypeError(refused)
+    return values
+
+
+def _ints(parts):
+    return [int(t) for t in parts]
+
+
+def symmetry_list(text):
+    """--symmetries' comma list of elements 0 .. 7."""
+    return _comma_list(text, _ints, "expected a comma-separated list of elements 0 .. 7, got %r" % text,
+                       valid=lambda e: 0 <= e <= 7, refused="symmetry elements are 0 .. 7, got %r" % text)
 
 
 def blur_list(text):
     """--blurs' comma list of radii 1 .. BLUR_MAX_RADIUS."""
-    import argparse
-    try:
-        radii = tuple(int(t) for t in text.split(","))
-    except ValueError:
-        raise argparse.ArgumentTypeError("expected a comma-separated list of radii 1 .. %d, got %r" % (mp.BLUR_MAX_RADIUS, text))
-    if not radii or any(not 1 <= r <= mp.BLUR_MAX_RADIUS for r in radii):
-        raise argparse.ArgumentTypeError("blur radii are 1 .. %d, got %r" % (mp.BLUR_MAX_RADIUS, text))
-    return radii
+    return _comma_list(text, _ints, "expected a comma-separated list of radii 1 .. %d, got %r" % (mp.BLUR_MAX_RADIUS, text),
+                       valid=lambda r: 1 <= r <= mp.BLUR_MAX_RADIUS, refused="blur radii are 1 .. %d, got %r" % (mp.BLUR_MAX_RADIUS, text))
 
 
 def zoom_list(text):
     """--zooms' comma list of magnifications P/Q: 1 <= Q < P <= ZOOM_MAX_P in lowest terms."""
-    import argparse
-    try:
-        zooms = tuple(tuple(int(v) for v in t.split("/")) for t in text.split(","))
-        if not zooms or any(len(z) != 2 for z in zooms):
+    def ratios(parts):
+        zooms = [tuple(int(v) for v in t.split("/")) for t in parts]
+        if any(len(z) != 2 for z in zooms):
             raise ValueError
-        return tuple(mp.zoom_ratio(z) for z in zooms)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError("expected a comma-separated list of magnifications P/Q (1 <= Q < P <= %d, lowest terms), got %r%s"
-                                         % (mp.ZOOM_MAX_P, text, ": %s" % e if str(e) else ""))
+        return [mp.zoom_ratio(z) for z in zooms]
+    return _comma_list(text, ratios, "expected a comma-separated list of magnifications P/Q (1 <= Q < P <= %d, lowest terms), got %r"
+                       % (mp.ZOOM_MAX_P, text), detail=True)
 
 
 def scatter_list(text):
     """--scatters' comma list of veils R:A/B: 1 <= R <= SCATTER_MAX_RADIUS, 1 <= A < B <= SCATTER_MAX_DEN in lowest terms."""
-    import argparse
-    try:
-        specs = []
-        for t in text.split(","):
+    def veils(parts):
+        for t in parts:
             radius, fraction = t.split(":")
             a, b = fraction.split("/")
-            specs.append(mp.scatter_spec((int(radius), int(a), int(b))))
-        return tuple(specs)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError("expected a comma-separated list of veils R:A/B (1 <= R <= %d, 1 <= A < B <= %d, lowest terms), got %r%s"
-                                         % (mp.SCATTER_MAX_RADIUS, mp.SCATTER_MAX_DEN, text, ": %s" % e if str(e) else ""))
+            yield mp.scatter_spec((int(radius), int(a), int(b)))
+    return _comma_list(text, veils, "expected a comma-separated list of veils R:A/B (1 <= R <= %d, 1 <= A < B <= %d, lowest terms), got %r"
+                       % (mp.SCATTER_MAX_RADIUS, mp.SCATTER_MAX_DEN, text), detail=True)
 
 
 def warp_list(text):
     """--warps' comma list of names of WARPS: <family>_<amplitude>."""
-    import argparse
-    names = tuple(text.split(","))
     known = ["%s_%d" % (f, a) for f in ("shift", "stretch", "shear", "bulge", "twist") for a in WARP_AMPLITUDES]
-    if not names or any(t not in known for t in names):
-        raise argparse.ArgumentTypeError("expected a comma-separated list of warps out of %s, got %r" % (",".join(known), text))
-    return names
+    return _comma_list(text, tuple, None, valid=known.__contains__,
+                       refused="expected a comma-separated list of warps out of %s, got %r" % (",".join(known), text))
 
 
 def reach_list(text):
@@ -1867,14 +1896,8 @@ def reach_list(text):
 
 def codec_list(text):
     """--codecs' comma list of DC steps 1 .. 65535."""
-    import argparse
-    try:
-        steps = tuple(int(t) for t in text.split(","))
-    except ValueError:
-        raise argparse.ArgumentTypeError("expected a comma-separated list of DC steps 1 .. 65535, got %r" % (text,))
-    if not steps or any(not 1 <= s <= 65535 for s in steps):
-        raise argparse.ArgumentTypeError("codec DC steps are 1 .. 65535, got %r" % (text,))
-    return steps
+    return _comma_list(text, _ints, "expected a comma-separated list of DC steps 1 .. 65535, got %r" % (text,),
+                       valid=lambda s: 1 <= s <= 65535, refused="codec DC steps are 1 .. 65535, got %r" % (text,))
 
 
 def main(argv=None):
@@ -2015,20 +2038,11 @@ def main(argv=None):
     ap.add_argument("--covariance-maps", metavar="DIR",
                     help="with --covariance: one 8-bit BMP per noise row into DIR: the centred noise power spectrum, log-scaled")
     args = ap.parse_args(argv)
-    if args.detail_tables and not args.details:
-        ap.error("--detail-tables keeps what --details measures: give --details")
-    if args.edge_tables and not args.edges:
-        ap.error("--edge-tables keeps what --edges measures: give --edges")
-    if args.grating_tables and not args.gratings:
-        ap.error("--grating-tables keeps what --gratings measures: give --gratings")
-    if args.gain_tables and not args.gains:
-        ap.error("--gain-tables keeps what --gains measures: give --gains")
-    if args.lut_tables and not args.luts:
-        ap.error("--lut-tables keeps what --luts measures: give --luts")
-    if args.observer and not args.details:
-        ap.error("--observer looks at the details of the cd_ rows: give --details")
-    if args.point_tables and not args.points:
-        ap.error("--point-tables keeps what --points measures: give --points")
+    needs = [(rel.tables, rel.option, "--%s keeps what --%s measures: give --%s" % (rel.tables.replace("_", "-"), rel.option, rel.option)) for rel in RELATIONS]
+    needs.insert(5, ("observer", "details", "--observer looks at the details of the cd_ rows: give --details"))   # refused before --point-tables
+    for flag, needed, text in needs:
+        if getattr(args, flag) and not getattr(args, needed):
+            ap.error(text)
     if (args.reach_tables or args.reach_maps) and args.reach is None:
         ap.error("--reach-tables and --reach-maps keep and draw what --reach measures: give --reach")
     if args.covariance and not 1 <= args.covariance <= mp.SIM_MAX_RADIUS:
@@ -2074,45 +2088,25 @@ def main(argv=None):
                     **({"ensemble_batch": args.ensemble_batch} if args.ensemble else {}))
     shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
                  {"displacement": args.displacement} if args.displacement else {}
-    if args.scales:
-        shift_args["scales"] = args.scales
-    if args.gradients:
-        shift_args["gradients"] = True
-    if args.order:
-        shift_args["order"] = True
+    for m in COMPARISON_METRICS[1:]:   # --scales .. --blobs, under their options' names (--tone and --symmetries are passed whatever they say)
+        if m.on(getattr(args, m.option)):
+            shift_args[m.option] = getattr(args, m.option)
+    if args.blobs is not None:
+        shift_args["blob_connectivity"] = args.blob_connectivity
+    for m in MOVED[1:]:                # --blurs .. --codecs: the lists as given, a flag without a list as the entry's defaults for the size
+        if getattr(args, m.option):
+            shift_args[m.option] = m.cli(getattr(args, m.option), args.size) if m.cli else getattr(args, m.option)
     if args.observer:
         shift_args["observer"] = True
     if args.ensemble:
         shift_args.update(ensemble=args.ensemble, ensemble_tiles=bool(args.ensemble_maps))
     if args.covariance:
         shift_args.update(covariance=args.covariance, covariance_tiles=bool(args.covariance_maps))
-    if args.blurs:
-        shift_args["blurs"] = args.blurs
-    if args.codecs:
-        shift_args["codecs"] = args.codecs
-    if args.lattice:
-        shift_args["lattice"] = args.lattice
-    if args.blobs is not None:
-        shift_args["blobs"] = args.blobs
-        shift_args["blob_connectivity"] = args.blob_connectivity
-    if args.zooms:
-        shift_args["zooms"] = args.zooms
-    if args.scatters:
-        shift_args["scatters"] = SCATTERS(args.size) if args.scatters is True else args.scatters
-    if args.warps:
-        shift_args["warps"] = [w for w in WARPS(args.size) if args.warps is True or w[0] in args.warps]
-    if args.details:
-        shift_args.update(details=DETAILS(args.size), detail_tables=args.detail_tables)
-    if args.edges:
-        shift_args.update(edges=EDGES(args.size), edge_tables=args.edge_tables)
-    if args.gratings:
-        shift_args.update(gratings=GRATINGS(args.size), grating_tables=args.grating_tables)
-    if args.gains:
-        shift_args.update(gains=GAINS(args.size), gain_tables=args.gain_tables)
-    if args.luts:
-        shift_args.update(luts=True if args.manifest else LUTS(raw), lut_tables=args.lut_tables)
-    if args.points:
-        shift_args.update(points=POINTS(args.size), point_tables=args.point_tables)
+    grids = dict(details=DETAILS, edges=EDGES, gratings=GRATINGS, gains=GAINS, points=POINTS)
+    for rel in RELATIONS:          # --details .. --points: the defaults for the size, the luts of the image itself (a manifest: of each image)
+        if getattr(args, rel.option):
+            payloads = (True if args.manifest else LUTS(raw)) if rel.option == "luts" else grids[rel.option](args.size)
+            shift_args.update({rel.option: payloads, rel.tables: getattr(args, rel.tables)})
     if args.reach is not None:
         shift_args.update(reach=args.reach, reach_tables=args.reach_tables, reach_maps=bool(args.reach_maps))
     try:

@@ -1408,10 +1408,11 @@ class MusicaProcessing:
             out.append({"a": tables[at:at + c].copy(), "b": tables[at + c:at + 2 * c].copy(), "pixels": int(r.pixels), "sum_a": int(r.sum_a), "sum_b": int(r.sum_b)})
         return out
 
-    def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False):
-        """What sim_profiles / _levels / _gradients / _order / _lattice / _reach share: the refusals of sim_<name> before any call (most: 1 .. most
-        queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead` in front of
-        the count. Returns the results and the flat tables, `words` zeroed words of `dtype`."""
+    def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False, trail=()):
+        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _reach share: the refusals of sim_<name> before any call
+        (most: 1 .. most queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead`
+        in front of the count and `trail` (blobs: the label plane and its length) behind the tables' length. Returns the results and the
+        flat tables, `words` zeroed words of `dtype`."""
         if most is not None and not 1 <= len(qs) <= most:
             raise ValueError("sim_%s takes 1 .. %d queries, got %d" % (name, most, len(qs)))
         for i, q in enumerate(qs if window else ()):
@@ -1419,7 +1420,7 @@ class MusicaProcessing:
                 raise ValueError("sim_%s: query %d: region %d x %d is smaller than 7 x 7" % (name, i, q.w, q.h))
         arr, res, tables = (SimQuery * max(len(qs), 1))(*qs), (result_type * max(len(qs), 1))(), np.zeros(max(words, 1), dtype=dtype)
         call = getattr(self._lib, "musica_sim_" + name)
-        self._ok(call(self._h, *lead, len(qs), arr, res, tables.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), words), "musica_sim_" + name)
+        self._ok(call(self._h, *lead, len(qs), arr, res, tables.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), words, *trail), "musica_sim_" + name)
         return res, tables
 
     def sim_profiles(self, queries):
@@ -1510,13 +1511,10 @@ class MusicaProcessing:
         if connectivity not in (4, 8):
             raise ValueError("connectivity %r is neither 4 nor 8" % (connectivity,))
         qs = _queries(queries)
-        if not 1 <= len(qs) <= BLOBS_MAX_QUERIES:
-            raise ValueError("sim_blobs takes 1 .. %d queries, got %d" % (BLOBS_MAX_QUERIES, len(qs)))
         per = BLOB_CLASSES * len(BLOB_FIELDS)
-        arr, res, tables = (SimQuery * len(qs))(*qs), (SimBlobsResult * len(qs))(), np.zeros(len(qs) * per, dtype=np.uint64)
         planes = np.zeros(sum(int(q.w) * int(q.h) for q in qs), dtype=np.uint32) if labels else None
-        self._ok(self._lib.musica_sim_blobs(self._h, t, int(connectivity), len(qs), arr, res, tables.ctypes.data_as(C.POINTER(C.c_uint64)), len(tables),
-                                            planes.ctypes.data_as(_U32P) if labels else None, len(planes) if labels else 0), "musica_sim_blobs")
+        res, tables = self._sim_tables("blobs", qs, SimBlobsResult, np.uint64, len(qs) * per, t, int(connectivity), most=BLOBS_MAX_QUERIES,
+                                       trail=(planes.ctypes.data_as(_U32P), len(planes)) if labels else (None, 0))
         out = []
         for q, r in zip(qs, res):
             at = int(r.table_offset)

@@ -1,5 +1,6 @@
 """What a study leaves on disk: the reference's CSV files (script.py:223-330) and the files of the study's later options, one table
 entry each, and the 8-bit BMP maps of the tile tables. harness re-exports every name."""
+import collections
 import csv
 import os
 
@@ -16,36 +17,36 @@ CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs 
 
 REF_CSV_HEADER = ['raw file', 'mse similarity', 'ssim similarity', 'histogram distance']   # ref_similarities.csv (script.py:285-290)
 TONE_CSV_NAMES = ('mutual information', 'normalized mutual information', 'correlation ratio', 'tone-matched mse', 'tone-matched ssim')   # JOINT_METRICS' order
-TONE_CSV_GROUPS = (('direct_tone', 'altered vs unaltered'), ('registered_tone', 'registered vs unaltered'),
-                   ('reference_tone', 'altered vs reference'), ('registered_reference_tone', 'registered vs reference'))
+
+# A row's comparisons, each the stem of its row keys and its label in the files: a comparison metric's files (METRIC_CSVS) take the key
+# <stem>_<suffix>; the two vendor groups stand last, the per-row files have them only for studies that have a vendor image
+COMPARISON_CSV_GROUPS = (('direct', 'altered vs unaltered'), ('registered', 'registered vs unaltered'),
+                         ('reference', 'altered vs reference'), ('registered_reference', 'registered vs reference'))
+
+
+def _csv_groups(suffix):
+    return tuple(('%s_%s' % (stem, suffix), label) for stem, label in COMPARISON_CSV_GROUPS)
+
+
+TONE_CSV_GROUPS, SCALE_CSV_GROUPS, GRADIENT_CSV_GROUPS, ORDER_CSV_GROUPS, LATTICE_CSV_GROUPS, BLOB_CSV_GROUPS = \
+    (_csv_groups(suffix) for suffix in ('tone', 'scales', 'gradient', 'order', 'lattice', 'blobs'))
 
 SHIFT_CSV_NAMES = ('dx', 'dy', 'sub dx', 'sub dy', 'mse at zero', 'mse at best', 'tiles', 'tiles off')   # SHIFT_KEYS' order
 SHIFT_CSV_GROUPS = (('direct_shift', 'direct'), ('registered_shift', 'registered'))
 SHIFT_CSV_HEADER = ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in SHIFT_CSV_GROUPS for m in SHIFT_CSV_NAMES]   # displacement.csv
 
-SCALE_CSV_GROUPS = (('direct_scales', 'altered vs unaltered'), ('registered_scales', 'registered vs unaltered'),
-                    ('reference_scales', 'altered vs reference'), ('registered_reference_scales', 'registered vs reference'))
 SCALE_CSV_METRICS = ("ssim", "cs", "mse")   # per scale 0 .. 4, behind ms_ssim and scales
 
-GRADIENT_CSV_GROUPS = (('direct_gradient', 'altered vs unaltered'), ('registered_gradient', 'registered vs unaltered'),
-                       ('reference_gradient', 'altered vs reference'), ('registered_reference_gradient', 'registered vs reference'))
-
-# order_robustness.csv: one line per row and comparison the row has, in this order; tau_by_ring spread over three columns
-ORDER_CSV_GROUPS = (('direct_order', 'altered vs unaltered'), ('registered_order', 'registered vs unaltered'),
-                    ('reference_order', 'altered vs reference'), ('registered_reference_order', 'registered vs reference'))
+# order_robustness.csv: one line per row and comparison the row has, in COMPARISON_CSV_GROUPS' order; tau_by_ring spread over three columns
 ORDER_CSV_HEADER = ['raw file', 'alteration', 'comparison'] + [c for k in ORDER_KEYS for c in (['tau ring %d' % (i + 1) for i in range(mp.ORDER_RINGS)] if k == "tau_by_ring" else [k])]
 
 # lattice_robustness.csv: one line per row and comparison the row has, in this order; per axis the steps, then phase_mse per period
-LATTICE_CSV_GROUPS = (('direct_lattice', 'altered vs unaltered'), ('registered_lattice', 'registered vs unaltered'),
-                      ('reference_lattice', 'altered vs reference'), ('registered_reference_lattice', 'registered vs reference'))
 LATTICE_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'period', 'periodic'] + \
                      ['%s %s' % (axis, c) for axis in ("x", "y") for k in LATTICE_AXIS_KEYS
                       for c in (['phase mse %d' % p for p in LATTICE_PERIODS] if k == "phase_mse" else [k.replace('_', ' ')])]
 
 # blob_robustness.csv: one line per row and comparison the row has, in this order; blob_summary's numbers, the largest component's box,
 # then the components and the pixels of every class
-BLOB_CSV_GROUPS = (('direct_blobs', 'altered vs unaltered'), ('registered_blobs', 'registered vs unaltered'),
-                   ('reference_blobs', 'altered vs reference'), ('registered_reference_blobs', 'registered vs reference'))
 BLOB_CSV_HEADER = ['raw file', 'alteration', 'comparison'] + [k.replace('_', ' ') for k in BLOB_KEYS] + ['largest x0', 'largest y0', 'largest x1', 'largest y1'] + \
                   ['%s class %d' % (what, c) for what in ('components', 'pixels') for c in range(mp.BLOB_CLASSES)]
 
@@ -79,12 +80,16 @@ def covariance_csv_header(radius):
            ['direct nps radius %d' % i for i in range(int(radius) + 1)]
 
 
+def _row_csv_header(columns, with_reference):
+    """The columns of a comparison metric's per-row file: the raw file, the alteration, then `columns` per group of
+    COMPARISON_CSV_GROUPS, the two vendor groups only for studies that have a vendor image."""
+    return ['raw file', 'alteration'] + ['%s %s' % (g, c) for _, g in COMPARISON_CSV_GROUPS[:4 if with_reference else 2] for c in columns]
+
+
 def scale_csv_header(with_reference):
     """scale_robustness.csv's columns: per group ms_ssim, scales, then ssim, cs and mse of scales 0 .. 4; the two vendor groups only for
     studies that have a vendor image."""
-    return ['raw file', 'alteration'] + [c for _, g in SCALE_CSV_GROUPS[:4 if with_reference else 2] for c in
-                                         ['%s ms-ssim' % g, '%s scales' % g] +
-                                         ['%s %s scale %d' % (g, m, s) for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)]]
+    return _row_csv_header(['ms-ssim', 'scales'] + ['%s scale %d' % (m, s) for m in SCALE_CSV_METRICS for s in range(mp.SIM_MAX_SCALES)], with_reference)
 
 
 def _scale_csv_cells(t):
@@ -97,8 +102,7 @@ def gradient_csv_header(with_reference):
     """gradient_robustness.csv's columns: per group the GRADIENT_KEYS gsim, gc, gain, turn, reversed, rmse and compression, then gain_0
     .. gain_21, the gain of every class of the reference side's edge strength; the two vendor groups only for studies that have a
     vendor image."""
-    return ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in GRADIENT_CSV_GROUPS[:4 if with_reference else 2]
-                                         for m in GRADIENT_KEYS + tuple('gain_%d' % k for k in range(mp.GRADIENT_CLASSES))]
+    return _row_csv_header(GRADIENT_KEYS + tuple('gain_%d' % k for k in range(mp.GRADIENT_CLASSES)), with_reference)
 
 
 def _gradient_csv_cells(t):
@@ -109,7 +113,7 @@ def _gradient_csv_cells(t):
 
 def tone_csv_header(with_reference):
     """tone_robustness.csv's columns: the five JOINT_METRICS per group, the two vendor groups only for studies that have a vendor image."""
-    return ['raw file', 'alteration'] + ['%s %s' % (g, m) for _, g in TONE_CSV_GROUPS[:4 if with_reference else 2] for m in TONE_CSV_NAMES]
+    return _row_csv_header(TONE_CSV_NAMES, with_reference)
 
 
 def normalized_vs_reference(ref, ovd):
@@ -183,44 +187,52 @@ def _group_lines(studies, key, groups, cells):
                 yield [raw_name, r["alteration"], label] + cells(d, g)
 
 
-def _order_lines(studies):
-    """order_robustness.csv's lines: one per row and comparison that the row has (ORDER_CSV_GROUPS' order), the unaltered row included:
-    the raw file, the alteration, the comparison, then the ORDER_KEYS with tau_by_ring's three entries in a column each."""
+def _comparison_lines(studies, groups, cells):
+    """The lines of a comparison metric's per-comparison file: one per row, the unaltered one included, and comparison that the row
+    has, in the groups' order: the raw file, the alteration, the comparison's label, then cells(its value)."""
     for raw_name, rows in studies:
         for r in rows:
-            for key, label in ORDER_CSV_GROUPS:
+            for key, label in groups:
                 t = r.get(key)
                 if t is not None:
-                    yield [raw_name, r["alteration"], label] + [c for k in ORDER_KEYS for c in (list(t[k]) if k == "tau_by_ring" else [t[k]])]
+                    yield [raw_name, r["alteration"], label] + cells(t)
 
 
-def _lattice_lines(studies):
-    """lattice_robustness.csv's lines: one per row and comparison that the row has (LATTICE_CSV_GROUPS' order), the unaltered row
-    included: the raw file, the alteration, the comparison, the period, the periodic share, then per axis the LATTICE_AXIS_KEYS with
-    phase_mse in a column per period of LATTICE_PERIODS (empty beyond the study's period, as every value that is None)."""
-    blank = lambda v: "" if v is None else v
-    for raw_name, rows in studies:
-        for r in rows:
-            for key, label in LATTICE_CSV_GROUPS:
-                t = r.get(key)
-                if t is not None:
-                    yield [raw_name, r["alteration"], label, len(t["table"]), blank(t["periodic"])] + \
-                          [c for axis in ("x", "y") for k in LATTICE_AXIS_KEYS
-                           for c in ([blank(t[axis][k].get(p)) for p in LATTICE_PERIODS] if k == "phase_mse" else [blank(t[axis][k])])]
+def _blank(v):
+    return "" if v is None else v
 
 
-def _blob_lines(studies):
-    """blob_robustness.csv's lines: one per row and comparison that the row has (BLOB_CSV_GROUPS' order), the unaltered row included:
-    the raw file, the alteration, the comparison, blob_summary's BLOB_KEYS, the largest component's box (empty where nothing changed,
-    as every value that is None), then the components and the pixels per class."""
-    blank = lambda v: "" if v is None else v
-    for raw_name, rows in studies:
-        for r in rows:
-            for key, label in BLOB_CSV_GROUPS:
-                t = r.get(key)
-                if t is not None:
-                    yield [raw_name, r["alteration"], label] + [blank(t[k]) for k in BLOB_KEYS] + list(t["largest_box"] or [""] * 4) + \
-                          list(t["class_components"]) + list(t["class_pixels"])
+def _order_cells(t):
+    """The ORDER_KEYS with tau_by_ring's three entries in a column each."""
+    return [c for k in ORDER_KEYS for c in (list(t[k]) if k == "tau_by_ring" else [t[k]])]
+
+
+def _lattice_cells(t):
+    """The period, the periodic share, then per axis the LATTICE_AXIS_KEYS with phase_mse in a column per period of LATTICE_PERIODS
+    (empty beyond the study's period, as every value that is None)."""
+    return [len(t["table"]), _blank(t["periodic"])] + \
+           [c for axis in ("x", "y") for k in LATTICE_AXIS_KEYS
+            for c in ([_blank(t[axis][k].get(p)) for p in LATTICE_PERIODS] if k == "phase_mse" else [_blank(t[axis][k])])]
+
+
+def _blob_cells(t):
+    """blob_summary's BLOB_KEYS, the largest component's box (empty where nothing changed, as every value that is None), then the
+    components and the pixels per class."""
+    return [_blank(t[k]) for k in BLOB_KEYS] + list(t["largest_box"] or [""] * 4) + list(t["class_components"]) + list(t["class_pixels"])
+
+
+# The files of the comparison metrics (harness.COMPARISON_METRICS), by key suffix: a study that has direct_<suffix> gets the file.
+# per "row": one line per row, header(with_reference), then cells(a group's value or None) for every group; per "comparison": one line
+# per row and comparison that the row has, the header as it stands, then cells(the value).
+MetricCsv = collections.namedtuple("MetricCsv", "file per header cells")
+METRIC_CSVS = {
+    "tone": MetricCsv("tone_robustness.csv", "row", tone_csv_header, lambda t: _cells(t, mp.JOINT_METRICS)),
+    "scales": MetricCsv("scale_robustness.csv", "row", scale_csv_header, _scale_csv_cells),
+    "gradient": MetricCsv("gradient_robustness.csv", "row", gradient_csv_header, _gradient_csv_cells),
+    "order": MetricCsv("order_robustness.csv", "comparison", ORDER_CSV_HEADER, _order_cells),
+    "lattice": MetricCsv("lattice_robustness.csv", "comparison", LATTICE_CSV_HEADER, _lattice_cells),
+    "blobs": MetricCsv("blob_robustness.csv", "comparison", BLOB_CSV_HEADER, _blob_cells),
+}
 
 
 def _spread_cells(count, keys, stats):
@@ -330,11 +342,7 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     registered mse and ssim (empty where the row has no registered comparison)."""
     os.makedirs(out_dir, exist_ok=True)
     having = lambda key: [(raw_name, rows) for raw_name, rows in studies if rows and key in rows[0]]   # noqa: E731
-    toned, scored, ensembles = having("direct_tone"), having("direct_scales"), having("ensemble")
-    tone_groups = TONE_CSV_GROUPS[:4 if any("reference_tone" in rows[0] for _, rows in toned) else 2]
-    scale_groups = SCALE_CSV_GROUPS[:4 if any("reference_scales" in rows[0] for _, rows in scored) else 2]
-    graded = having("direct_gradient")
-    gradient_groups = GRADIENT_CSV_GROUPS[:4 if any("reference_gradient" in rows[0] for _, rows in graded) else 2]
+    ensembles = having("ensemble")
     covs = [(raw_name, [r for r in rows if r.get("ensemble") and "covariance" in r["ensemble"]]) for raw_name, rows in ensembles]
     covs = [(raw_name, rows) for raw_name, rows in covs if rows]
     radius = covs[0][1][0]["ensemble"]["covariance"]["direct"]["radius"] if covs else 0
@@ -346,14 +354,8 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
          lambda r, ovd: None if _unaltered(r) or r["registered"] is None else
          _cells(r["registered"], SIM_CSV_KEYS) + _ref_columns(r.get("registered_reference"), ovd)),
         ("mean_cnr.csv", ["raw file", "alteration", "mean cnr"], studies if mean_cnr else None, lambda r, ovd: [r["mean_cnr"]]),
-        ("tone_robustness.csv", tone_csv_header(len(tone_groups) == 4), toned or None,
-         lambda r, ovd: [c for key, _ in tone_groups for c in _cells(r.get(key), mp.JOINT_METRICS)]),
         ("displacement.csv", SHIFT_CSV_HEADER, having("direct_shift") or None,
          lambda r, ovd: [c for key, _ in SHIFT_CSV_GROUPS for c in _cells(r.get(key), SHIFT_KEYS)]),
-        ("scale_robustness.csv", scale_csv_header(len(scale_groups) == 4), scored or None,
-         lambda r, ovd: [c for key, _ in scale_groups for c in _scale_csv_cells(r.get(key))]),
-        ("gradient_robustness.csv", gradient_csv_header(len(gradient_groups) == 4), graded or None,
-         lambda r, ovd: [c for key, _ in gradient_groups for c in _gradient_csv_cells(r.get(key))]),
         ("ensemble.csv", ENSEMBLE_CSV_HEADER, ensembles or None, lambda r, ovd: _ensemble_cells(r["ensemble"])),
         ("noise_covariance.csv", covariance_csv_header(radius), covs or None, lambda r, ovd: _covariance_cells(r["ensemble"], radius)),
         ("warp_response.csv", WARP_CSV_HEADER, having("warp") or None,
@@ -363,12 +365,14 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     for name, header, covered, cells in tables:
         if covered is not None:
             _write_csv(out_dir, name, header, _lines(covered, cells))
-    if having("direct_order"):
-        _write_csv(out_dir, "order_robustness.csv", ORDER_CSV_HEADER, _order_lines(having("direct_order")))
-    if having("direct_lattice"):
-        _write_csv(out_dir, "lattice_robustness.csv", LATTICE_CSV_HEADER, _lattice_lines(having("direct_lattice")))
-    if having("direct_blobs"):
-        _write_csv(out_dir, "blob_robustness.csv", BLOB_CSV_HEADER, _blob_lines(having("direct_blobs")))
+    for suffix, metric in METRIC_CSVS.items():
+        covered, groups = having("direct_" + suffix), _csv_groups(suffix)
+        if covered and metric.per == "row":
+            groups = groups[:4 if any(groups[2][0] in rows[0] for _, rows in covered) else 2]
+            _write_csv(out_dir, metric.file, metric.header(len(groups) == 4),
+                       _lines(covered, lambda r, ovd: [c for key, _ in groups for c in metric.cells(r.get(key))]))
+        elif covered:
+            _write_csv(out_dir, metric.file, metric.header, _comparison_lines(covered, groups, metric.cells))
     for name, header, key, groups, cells in RELATION_CSVS:
         if having(key):
             _write_csv(out_dir, name, header, _group_lines(having(key), key, groups, cells))
@@ -444,7 +448,6 @@ def write_displacement_maps(studies, out_dir):
     <raw>_<alteration>_rmse.bmp, the tile RMSE at the zero shift, and <raw>_<alteration>_shift.bmp, the length of the tile's best shift.
     Returns the paths written."""
     return _write_maps(studies, out_dir, _displacement_images)
-
 
 
 def write_study_csvs(rows, out_dir, raw_name, mean_cnr=True):

@@ -8,7 +8,16 @@ The golden file was recorded with record() below driving the harness.py of the c
 and two scorers (never the code under test), with one edit by hand: in row 0 the sim_displace call was moved behind the
 sim_multiscale calls, the order every other row already had. study_calls_relations.json was recorded the same way with the harness.py of the commit BEFORE the
 four relations were put into one table. Its rows hold what the *_row summarisers make of the canned sums, some of it through an FFT and
-cosines: those floats are compared to 1e-9 relative, everything else of it exactly, as the three older studies are throughout."""
+cosines: those floats are compared to 1e-9 relative, everything else of it exactly, as the three older studies are throughout.
+
+A fifth study, "later", holds every option that came after those: zoom, scatter, warp and codec rows, a lut, a point grid, a detail grid
+under the observer, gradients, order, lattice, blobs and reach with its maps, compared with tests/golden/study_calls_later.json. That
+file was recorded the same way with the harness.py of the commit BEFORE the comparison metrics and the moved rows were put into tables
+("Add a cluster metric: connected components of a comparison on the GPU"). Its level and reach rows check their tables against the
+integers of the row's direct comparison, so in this study sim_compare's sq_diff_sum is the two fixed planes' own; the long integer
+tables and the arrays of its rows are kept as their size and sha256; its floats are compared to 1e-9 relative like the relations'."""
+import hashlib
+import inspect
 import json
 import math
 import os
@@ -21,6 +30,7 @@ from metamorphic_testing_of_the_musica_algorithm_for_x_ray_image_processing_amd 
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "study_calls.json")
 GOLDEN_RELATIONS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "study_calls_relations.json")
+GOLDEN_LATER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "study_calls_later.json")
 SIDE = 84
 OUT = SIDE - 2 * H.PROCESSING_MARGIN
 ENSEMBLE_INPUTS = ("sq_bias_sum", "var_sum", "sq_err_sum", "bias_sum", "abs_bias_max", "var_max", "realisations")
@@ -39,16 +49,42 @@ def _plain(v):
     return v
 
 
+def _leaves(v):
+    """The integers of a nested list of integers, None for anything else."""
+    if isinstance(v, list):
+        parts = [_leaves(x) for x in v]
+        return None if None in parts else sum(parts)
+    return 1 if isinstance(v, int) and not isinstance(v, bool) else None
+
+
+def _compact(v):
+    """A row's value with its bulk reduced: an array to shape, dtype and sha256 of its bytes, a nested list of more than 32 integers to
+    their number and the sha256 of its JSON text. Floats stay as they are, for the tolerance."""
+    if isinstance(v, np.ndarray):
+        return {"shape": list(v.shape), "dtype": str(v.dtype), "sha256": hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()}
+    if isinstance(v, dict):
+        return {k: _compact(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        plain = json.loads(json.dumps(_plain(v)))
+        if (_leaves(plain) or 0) > 32:
+            return {"integers": _leaves(plain), "sha256": hashlib.sha256(json.dumps(plain).encode()).hexdigest()}
+        return [_compact(x) for x in v]
+    return v
+
+
 KINDS = ("stats", "compare", "joint", "multiscale")
 
 
 class RecordingProc:
     """Stands in for a MusicaProcessing context: `name` tells the runner's context ("proc") from the ensemble's ("eproc") in the log."""
 
-    def __init__(self, log, name, batch=1):
-        self.log, self.name, self.batch = log, name, batch
+    def __init__(self, log, name, batch=1, exact=False):
+        self.log, self.name, self.batch, self.exact = log, name, batch, exact   # exact: sim_compare's sq_diff_sum is the fixed planes' own
         self.plane = np.random.default_rng(5).integers(0, 256, size=(OUT, OUT)).astype(np.uint8)
         self.measured = np.random.default_rng(6).integers(0, 256, size=(OUT, OUT)).astype(np.uint8)   # what the patch relations' calls measure against `plane`
+        self.source = np.random.default_rng(7).integers(0, 65536, size=(SIDE, SIDE)).astype(np.uint16)   # what sim_levels and sim_reach take from the resident source plane
+        self.changed = self.source.copy()
+        self.changed[30:34, 40:44] ^= 1                                                                  # and the input of the step: sixteen seeds
         self.counts = {}      # per kind of call, the source of the canned numbers: they do not depend on the order of unlike calls
         self.tracked = 0      # regions of the last sim_ensemble_track
 
@@ -82,8 +118,17 @@ class RecordingProc:
     def _sim_get_reference(self, slot):
         return self.plane.copy()
 
+    def reference(self, slot):
+        """What the comparison metrics' calls measure `measured` against: `plane` for slot 0, another plane for every other slot."""
+        return np.roll(self.plane, slot, axis=0)
+
     def _sim_compare(self, queries):
-        return [dict({k: self.number("compare") for k in mp.SIM_METRICS}, pixels=q[6] * q[7], sq_diff_sum=1000 + self.ordinal("sq_diff_sum")) for q in queries]
+        out = [dict({k: self.number("compare") for k in mp.SIM_METRICS}, pixels=q[6] * q[7], sq_diff_sum=1000 + self.ordinal("sq_diff_sum")) for q in queries]
+        for q, r in zip(queries, out if self.exact else ()):
+            ax, ay, bx, by, w, h = q[2:]
+            d = self.measured[ay:ay + h, ax:ax + w].astype(np.int64) - self.reference(q[1])[by:by + h, bx:bx + w]
+            r["sq_diff_sum"] = int((d * d).sum())
+        return out
 
     # The patch relations: the host's exact statistics of two fixed planes, which have the calls' shapes and which every *_row accepts.
     def _sim_details(self, details, slot, image_index=0):
@@ -97,6 +142,41 @@ class RecordingProc:
 
     def _sim_profiles(self, queries):
         return [H.profile_statistics(self.measured, self.plane, [tuple(q[2:])])[0] for q in queries]
+
+    def _sim_levels(self, queries, shift):
+        classes = H.level_classes(self.source, shift)
+        tables = [H.level_statistics(self.measured, self.reference(q[1]), classes, [tuple(q[2:])], mp.level_count(shift))[0] for q in queries]
+        return [{"table": t, "classes": len(t), "ssd": int(t[:, 3].sum()), "pixels": int(t[:, 0].sum())} for t in tables]
+
+    def _sim_points(self, points, slot, groups=None, image_index=0):
+        return H.point_statistics(self.measured, self.plane, points, groups)
+
+    def _sim_observer(self, views, banks, slot, image_index=0):
+        return H.channel_responses(self.measured, self.plane, views, banks)
+
+    # The comparison metrics: the host's exact statistics of `measured` against the slot's plane over the query's region, as the sim_* wrappers shape them.
+    def _sim_gradients(self, queries):
+        res = [H.gradient_statistics(self.measured, self.reference(q[1]), [tuple(q[2:])])[0] for q in queries]
+        return [{"table": t, "gsim": g, "pixels": (q[6] - 2) * (q[7] - 2)} for q, (t, g) in zip(queries, res)]
+
+    def _sim_order(self, queries):
+        head = mp.ORDER_RINGS * len(mp.ORDER_FIELDS)
+        res = [H.order_statistics(self.measured, self.reference(q[1]), [tuple(q[2:])])[0] for q in queries]
+        return [{"rings": t[:head].reshape(mp.ORDER_RINGS, len(mp.ORDER_FIELDS)), "histogram": t[head:], "pixels": (q[6] - 6) * (q[7] - 6)} for q, t in zip(queries, res)]
+
+    def _sim_lattice(self, queries, period, origin=0):
+        return [{"table": H.lattice_statistics(self.measured, self.reference(q[1]), [tuple(q[2:])], period, origin)[0], "pixels": (q[6] - 1) * (q[7] - 1)} for q in queries]
+
+    def _sim_blobs(self, queries, threshold, connectivity=8, labels=False):
+        return [H.blob_statistics(self.measured, self.reference(q[1]), [tuple(q[2:])], threshold, connectivity)[0] for q in queries]
+
+    def _sim_reach(self, queries, radii):
+        classes = H.reach_classes(self.source, self.changed, radii)
+        tables = [H.reach_statistics(self.measured, self.reference(q[1]), classes, [tuple(q[2:])], len(radii) + 1)[0] for q in queries]
+        return [{"table": t, "classes": len(t), "ssd": int(t[:, 4].sum()), "pixels": int(t[:, 0].sum()), "seeds": int(np.count_nonzero(self.source != self.changed))} for t in tables]
+
+    def _sim_reach_classes(self, radii, image_index=0):
+        return H.reach_classes(self.source, self.changed, radii)[H.PROCESSING_MARGIN:-H.PROCESSING_MARGIN, H.PROCESSING_MARGIN:-H.PROCESSING_MARGIN]
 
     def _sim_joint(self, queries, tables=False):
         return [dict({k: self.number("joint") for k in mp.JOINT_METRICS if k != "tone_ssim"}, tone_lut=np.arange(256, dtype=np.uint8)) for _ in queries]
@@ -139,12 +219,12 @@ class RecordingProc:
         return out
 
 
-def _runner(log, device_alterations, batch=2):
+def _runner(log, device_alterations, batch=2, exact=False):
     """A harness.Runner around two recording contexts: its own methods run, nothing of the library is loaded."""
     r = H.Runner.__new__(H.Runner)
     r.n, r.levels, r.device, r.use_cli = SIDE, 0, 0, False
     r.device_alterations, r.device_metrics, r.ensemble_batch = device_alterations, True, batch
-    r.proc, r.ensemble_proc = RecordingProc(log, "proc"), RecordingProc(log, "eproc", batch)
+    r.proc, r.ensemble_proc = RecordingProc(log, "proc", exact=exact), RecordingProc(log, "eproc", batch)
     return r
 
 
@@ -157,7 +237,12 @@ STUDIES = {
     # one grid or spec of each patch relation, tables off
     "relations": (True, dict(GRIDS, details=[H.detail_grid(SIDE, 8)], edges=[H.edge_grid(SIDE, 8)], gratings=[H.grating_grid(SIDE, 8)],
                              gains=[H.GAINS(SIDE)[0]] + [g for g in H.GAINS(SIDE) if g[0] == "line_8"])),
+    # every option that came after those; displacement: the warp row's tracking reads its tile tables; luts=True: LUTS of the study's raw plane
+    "later": (True, dict(GRIDS, zooms=[(5, 4)], scatters=[H.SCATTERS(SIDE)[0]], warps=H.WARPS(SIDE)[:1], codecs=[64], luts=True,
+                         points=[H.point_grid(SIDE, 64)], details=[H.detail_grid(SIDE, 8)], observer=True, gradients=True, order=True, lattice=8,
+                         blobs=3, reach=True, reach_maps=True, displacement=2, vendor=True, tone=True, scales=2)),
 }
+COMPACT = ("later",)   # the studies whose rows are kept with their bulk reduced (_compact)
 
 
 def record(name, harness=H):
@@ -167,15 +252,27 @@ def record(name, harness=H):
     raw = rng.integers(0, 4096, size=(SIDE, SIDE)).astype(np.uint16)
     if args.get("vendor"):
         args = dict(args, vendor=rng.integers(0, 65536, size=(OUT, OUT)).astype(np.uint16))
+    if args.get("luts") is True:
+        args = dict(args, luts=harness.LUTS(raw)[:1])
     log = []
-    rows = harness.run_study(raw, _runner(log, device_alterations), rng=np.random.default_rng(0), **args)
-    return json.loads(json.dumps({"calls": log, "rows": [[[k, _plain(v)] for k, v in row.items()] for row in rows]}))
+    exact = bool(args.get("luts") or args.get("reach"))   # their rows hold the tables to the direct comparison's integers
+    rows = harness.run_study(raw, _runner(log, device_alterations, exact=exact), rng=np.random.default_rng(0), **args)
+    reduce = _compact if name in COMPACT else (lambda v: v)
+    rows = json.loads(json.dumps([[[k, _plain(reduce(v))] for k, v in row.items()] for row in rows]))
+    first = {}   # COMPACT: a long value that an earlier (row, key) had already (the stand-in's answers do not depend on the row) names that one
+    for row in rows if name in COMPACT else ():
+        for item in row:
+            text = json.dumps(item[1])
+            if len(text) > 200:
+                item[1] = {"as": first[text]} if text in first else item[1]
+                first.setdefault(text, [row[0][1], item[0]])
+    return {"calls": json.loads(json.dumps(log)), "rows": rows}
 
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(GOLDEN) as f, open(GOLDEN_RELATIONS) as g:
-        return dict(json.load(f), **json.load(g))
+    with open(GOLDEN) as f, open(GOLDEN_RELATIONS) as g, open(GOLDEN_LATER) as h:
+        return dict(json.load(f), **json.load(g), **json.load(h))
 
 
 def _same(got, want, tolerant):
@@ -199,7 +296,7 @@ def test_the_device_study_makes_the_recorded_calls(name, golden):
     assert len(got["calls"]) == len(want["calls"])
     assert [[k for k, _ in row] for row in got["rows"]] == [[k for k, _ in row] for row in want["rows"]]   # the keys and their order
     for g, w in zip(got["rows"], want["rows"]):
-        assert _same(g, w, tolerant=name == "relations"), dict(g)["alteration"]
+        assert _same(g, w, tolerant=name in ("relations", "later")), dict(g)["alteration"]
     assert len(got["rows"]) == len(want["rows"])
 
 
@@ -232,3 +329,41 @@ def test_the_relations_study_covers_the_four_relations(golden):
     for key, names in (("details", ["cd_8"]), ("edges", ["edge_8"]), ("gratings", ["grating_8"]), ("profiles", ["exposure_1_4", "line_8"])):
         assert [r["alteration"] for r in rows if r[key] is not None] == names
     assert len(rows[[r["alteration"] for r in rows].index("cd_8")]["details"]["radii"]) >= 1
+
+
+LATER_ORDER = ("sim_compare", "sim_joint", "sim_multiscale", "sim_gradients", "sim_order", "sim_lattice", "sim_blobs", "sim_reach", "sim_displace")
+LATER_RELATIONS = ("sim_details", "sim_levels", "sim_points")
+
+
+def test_the_later_study_covers_the_later_options(golden):
+    calls = [(c[0], c[1]) for c in golden["later"]["calls"]]
+    for call in ("sim_gradients", "sim_order", "sim_lattice", "sim_blobs", "sim_reach", "sim_reach_classes", "sim_levels", "sim_points", "sim_observer",
+                 "sim_zoom_reference", "sim_scatter_reference", "sim_warp_reference", "sim_codec_reference", "alter_zoom", "alter_scatter", "alter_warp",
+                 "alter_codec", "alter_lut", "alter_points", "alter_details", "sim_details", "sim_joint", "sim_multiscale", "sim_displace"):
+        assert ("proc", call) in calls, call
+    # per row (a row of this study begins with its alter_* call) the calls come in the scoring order, then the relation's, then the observer's
+    starts = [i for i, (_, c) in enumerate(calls) if c.startswith("alter_") and c != "alter_set_source"] + [len(calls)]
+    rows = [[c for _, c in calls[a:b]] for a, b in zip(starts, starts[1:])]
+    assert len(rows) == len(golden["later"]["rows"]) - 1
+    for row in rows:
+        for call in LATER_ORDER:
+            assert call in row, (row[0], call)
+        relation = [c for c in LATER_RELATIONS if c in row]
+        assert len(relation) <= 1
+        first = [row.index(c) for c in LATER_ORDER + tuple(relation) + (("sim_observer",) if "sim_observer" in row else ())]
+        assert first == sorted(first), row
+        assert ("sim_reach_classes" in row) and row.index("sim_reach_classes") == row.index("sim_reach") + 1
+    assert [r[0] for r in rows if "sim_observer" in r] == ["alter_details"] and [r[0] for r in rows if "sim_levels" in r] == ["alter_lut"]
+    assert [r[0] for r in rows if "sim_points" in r] == ["alter_points"]
+    # the rows' keys come in the order of study_options(...).keys
+    defaults = {k: p.default for k, p in inspect.signature(H.run_study).parameters.items() if k not in ("raw", "runner", "rng")}
+    args = dict(defaults, **STUDIES["later"][1])
+    args.update(vendor=np.zeros((OUT, OUT), dtype=np.uint16), luts=[("identity", np.arange(65536, dtype=np.uint16))])
+    keys = list(H.study_options(SIDE, _runner([], True), **args).keys)
+    assert len(keys) == len(set(keys)) and {"direct_blobs", "registered_reference_lattice", "direct_reach", "observer", "warp", "levels", "points"} <= set(keys)
+    for row in golden["later"]["rows"][1:]:
+        assert [k for k, _ in row] == keys
+    assert [k for k, _ in golden["later"]["rows"][0]] == [k for k in keys if not k.startswith("registered_reference")]
+    named = [dict(row)["alteration"] for row in golden["later"]["rows"]]
+    for name in ("zoom_5_4", "scatter_%d_%d_%d" % H.SCATTERS(SIDE)[0], H.WARPS(SIDE)[0][0], "codec_64", "cd_8", "point_64"):
+        assert name in named, name
