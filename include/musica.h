@@ -1187,6 +1187,40 @@ typedef struct musica_sim_blobs_result {
 int musica_sim_blobs(musica_ctx* ctx, uint32_t threshold, uint32_t connectivity, uint32_t count, const musica_sim_query* queries,
                      musica_sim_blobs_result* results, uint64_t* tables, uint64_t table_words, uint32_t* labels, uint64_t label_words);
 
+/* ---- spectrum: the exact Walsh transforms of a comparison (new, not in the reference) ----
+ * MUSICA amplifies bands, so its transfer function is a gain per band; this measurement takes it from the image itself: which spatial
+ * frequency band and orientation was changed, and by what gain. A Fourier transform cannot be exact; the Walsh-Hadamard transform can,
+ * and its octave bands are the Haar subbands. metrics.spectrum_statistics is the contract. Queries are musica_sim_compare's with
+ * w, h >= 1, at most MUSICA_SPECTRUM_MAX_QUERIES (a row's direct, registered and two vendor comparisons); `tile` T is one of 8, 16, 32,
+ * 64. A region holds (w / T) x (h / T) whole tiles of T x T pixels, anchored at its first pixel on either side; the remainder columns
+ * and rows are not counted. W is the T x T Walsh matrix in sequency order: row s is the row of the Sylvester Hadamard matrix with exactly
+ * s sign changes. Per tile A = W a W^T and B = W b W^T in integers, |A|, |B| <= 255 T^2 < 2^20. Query i gets
+ * T * T * MUSICA_SPECTRUM_WORDS int64_t in the flat `tables`, from results[i].table_offset (in words) on, indexed [sv][su] with the row
+ * sequency first, and per coefficient, over the region's tiles,
+ *   sum A^2, sum B^2, sum A B (signed)
+ * results[i].tiles = (w / T) (h / T) may be 0; the table is then all zeros. Three identities tie the table to the pixels:
+ *   1. Parseval: the sum A^2 of the whole table is T^2 sum a^2 over the tiled area, and the table's sum of (A^2 + B^2 - 2 A B) is T^2
+ *      times musica_sim_compare's sq_diff_sum of the region cut to (w / T) T x (h / T) T.
+ *   2. DC: entry [0][0] holds the sum of (a tile's pixel sum)^2.
+ *   3. Haar: 2 sum A^2 over sv, su >= T / 2 is T^2 sum (a[y][2 i] - a[y][2 i + 1])^2 over the tiled area, whatever T; and the sum A^2
+ *      of column su = 1 is T times the sum, over the rows of every tile, of (left half's sum - right half's sum)^2.
+ * A tile adds at most 2^40 to a word; a side is at most 16364, which gives at most 2^16 tiles at T = 64 and at most 2^22 tiles of at
+ * most 2^28 at T = 8: every word stays below 2^63. Everything is an integer: the tables equal the restatement word for word and
+ * repeat from call to call. Every word of the tables is written and nothing behind them. Synchronous, on the context's stream after
+ * whatever was enqueued there; changes no slot, no result of a step and no input image; scratch is allocated on first use and regrown
+ * when a call needs more. Refused before any device work: what musica_sim_compare refuses (with the smallest side 1 and at most
+ * MUSICA_SPECTRUM_MAX_QUERIES queries, none included), then a tile that is not one of the four, a NULL `tables` and table_words below
+ * the tables' words. After a refusal the context stays usable. */
+#define MUSICA_SPECTRUM_WORDS 3
+#define MUSICA_SPECTRUM_MAX_TILE 64
+#define MUSICA_SPECTRUM_MAX_QUERIES 4
+typedef struct musica_sim_spectrum_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t tiles;                 /* (w / T) * (h / T) */
+} musica_sim_spectrum_result;
+int musica_sim_spectrum(musica_ctx* ctx, uint32_t tile, uint32_t count, const musica_sim_query* queries,
+                        musica_sim_spectrum_result* results, int64_t* tables, uint64_t table_words);
+
 /* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
  * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change
  * outwards: the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global

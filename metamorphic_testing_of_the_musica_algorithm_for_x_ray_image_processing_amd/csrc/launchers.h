@@ -525,6 +525,31 @@ struct BlobScratch {
 // tables: every query's words, zeroed by the caller
 void launch_sim_blobs(hipStream_t st, const BlobQueryDev* d_qs, int count, int max_tiles, unsigned long long max_pixels, unsigned long long records, uint32_t threshold,
                       int connectivity, const BlobScratch& s, unsigned long long* tables);
+// kernels_spectrum.hip: the spectrum metric. One comparison of musica_sim_spectrum at tile T: tiled_w / tiled_h: (w / T) T, (h / T) T,
+// the region cut to whole tiles (0 where it holds none); tiles_x / tiles_y: ceil(tiled_w / 64), ceil(tiled_h / 64), the 64 x 64 BLOCKS
+// the kernel walks; groups: the persistent workgroups that share the blocks (spectrum_groups; 0 where there is no block); table: where
+// its T * T * kSpectrumWords words start in the launch's flat tables, in words; part: where its `groups` partial tables of as many
+// words start in the launch's partials, in words.
+constexpr int kSpectrumWords = 3;         // MUSICA_SPECTRUM_WORDS: sum A^2, sum B^2, sum A B
+constexpr int kSpectrumMaxTile = 64;      // MUSICA_SPECTRUM_MAX_TILE
+constexpr int kSpectrumMaxQueries = 4;    // MUSICA_SPECTRUM_MAX_QUERIES
+struct SpectrumQueryDev : SimRegion {
+    int tiles_x, tiles_y, groups;
+    int tiled_w, tiled_h;
+    unsigned long long table, part;
+};
+// The workgroups of a query of `blocks` blocks: min(blocks, want), where want is kSpectrumGroups, or `most` where 0 < most < want (the
+// tuning variable MUSICA_SPECTRUM_GROUPS, read at every call): the tables do not depend on it. A workgroup's 64-bit sums hold for any
+// number of blocks (kernels_spectrum.hip, THE 64-BIT RULE); the number is three workgroups of 44.6 KiB LDS a compute unit on 256 of them,
+// and at T = 64, where a partial table is 96 KiB, 72 MiB of partials in all; 256 and 512 measured slower at every T.
+constexpr int kSpectrumGroups = 768;
+inline int spectrum_groups(int blocks, int most = 0) {
+    const int want = most > 0 && most < kSpectrumGroups ? most : kSpectrumGroups;
+    return blocks < want ? blocks : want;
+}
+// metrics.spectrum_statistics over `count` queries (grid.x = max_groups, the largest `groups`, at least 1). part: room for every query's
+// partial tables; tables: every query's words, zeroed by the caller: the fold launch adds into them with u64 atomics
+void launch_sim_spectrum(hipStream_t st, const SpectrumQueryDev* d_qs, int count, int max_groups, int tile, unsigned long long* part, unsigned long long* tables);
 // kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
 // Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
 constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII

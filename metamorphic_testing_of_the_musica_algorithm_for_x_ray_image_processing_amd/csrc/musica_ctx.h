@@ -189,6 +189,11 @@ struct StudyState {
     size_t blob_tile_cap = 0, blob_count_cap = 0;
     unsigned long long* d_blob_best = nullptr;      // [kBlobMaxQueries] keys, then one word of errors (as u64)
     BlobBest* d_blob_largest = nullptr;             // [kBlobMaxQueries]
+    // musica_sim_spectrum: the queries and the flat tables
+    SpectrumQueryDev* d_spectrum_q = nullptr;         // [MUSICA_SPECTRUM_MAX_QUERIES]
+    unsigned long long* d_spectrum_tables = nullptr;  // [MUSICA_SPECTRUM_MAX_QUERIES][kSpectrumMaxTile^2][kSpectrumWords], allocated by the first musica_sim_spectrum
+    unsigned long long* d_spectrum_part = nullptr;    // the workgroups' partial tables of one call: spectrum_part_cap words, regrown when a call needs more
+    size_t spectrum_part_cap = 0;
     // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
     // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
     uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either

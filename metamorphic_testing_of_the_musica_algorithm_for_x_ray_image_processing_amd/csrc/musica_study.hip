@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_codec.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
 // sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
@@ -413,7 +413,7 @@ static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion
     d.h = (int)q.h;
 }
 
-// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _reach) -----------------------------------------------
+// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _reach) -----------------------------------------------
 // Where a table call keeps its queries and its flat tables in musica_ctx::study, and what it takes: at most `most` queries with sides
 // of at least `min_side`. The tables' buffer holds `tables_cap` words from the first call on; where `grown` names its capacity it
 // holds the words of the largest call so far instead.
@@ -431,6 +431,7 @@ constexpr TableBuffers<GradQueryDev, unsigned long long> kGradBuffers{&StudyStat
 constexpr TableBuffers<OrderQueryDev, unsigned long long> kOrderBuffers{&StudyState::d_order_q, &StudyState::d_order_tables, MUSICA_SIM_MAX_QUERIES, 7, (size_t)MUSICA_SIM_MAX_QUERIES * kOrderTableWords};
 constexpr TableBuffers<LatticeQueryDev, unsigned long long> kLatticeBuffers{&StudyState::d_lattice_q, &StudyState::d_lattice_tables, MUSICA_LATTICE_MAX_QUERIES, 2, (size_t)MUSICA_LATTICE_MAX_QUERIES * kLatticeMaxPeriod * kLatticeMaxPeriod * kLatticeWords};
 constexpr TableBuffers<BlobQueryDev, unsigned long long> kBlobBuffers{&StudyState::d_blob_q, &StudyState::d_blob_tables, MUSICA_BLOBS_MAX_QUERIES, 1, (size_t)MUSICA_BLOBS_MAX_QUERIES * kBlobClasses * kBlobWords};
+constexpr TableBuffers<SpectrumQueryDev, unsigned long long> kSpectrumBuffers{&StudyState::d_spectrum_q, &StudyState::d_spectrum_tables, MUSICA_SPECTRUM_MAX_QUERIES, 1, (size_t)MUSICA_SPECTRUM_MAX_QUERIES * kSpectrumMaxTile * kSpectrumMaxTile * kSpectrumWords};
 constexpr TableBuffers<ReachQueryDev, unsigned long long> kReachBuffers{&StudyState::d_reach_q, &StudyState::d_reach_tables, MUSICA_REACH_MAX_QUERIES, 1, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords};
 
 // What a call's place() says of one query: its tiles or chunks (the launch's grid.x is the largest) and the words of its table.
@@ -1328,6 +1329,38 @@ int musica_sim_blobs(musica_ctx* c, uint32_t threshold, uint32_t connectivity, u
         return fail("musica_sim_blobs: internal: a labelling loop hit its cap or a link did not descend (error word %u)", (uint32_t)keys_err[kBlobMaxQueries]);
     return 1;
     ABI_CATCH("musica_sim_blobs")
+}
+
+// ---- the Walsh spectrum of a comparison (musica_sim_spectrum, include/musica.h; kernels_spectrum.hip) ----------------------------------
+static_assert(kSpectrumWords == MUSICA_SPECTRUM_WORDS && kSpectrumMaxTile == MUSICA_SPECTRUM_MAX_TILE && kSpectrumMaxQueries == MUSICA_SPECTRUM_MAX_QUERIES, "kernels_spectrum.hip's constants are include/musica.h's");
+
+int musica_sim_spectrum(musica_ctx* c, uint32_t tile, uint32_t count, const musica_sim_query* qs, musica_sim_spectrum_result* out, int64_t* tables, uint64_t table_words) {
+    ABI_TRY
+    size_t partials = 0;   // words of every query's partial tables
+    return sim_query_tables(
+        c, "musica_sim_spectrum", kSpectrumBuffers, count, qs, out, tables, table_words,
+        [&] {
+            if (tile != 8 && tile != 16 && tile != 32 && tile != 64) return fail("musica_sim_spectrum: tile %u is not one of 8, 16, 32, 64", tile);
+            return 1;
+        },
+        [&](const musica_sim_query& q, SpectrumQueryDev& d) {   // of the whole tiles
+            d.tiled_w = (int)(q.w / tile * tile);
+            d.tiled_h = (int)(q.h / tile * tile);
+            const int blocks = tile_grid(d, (uint32_t)d.tiled_w, (uint32_t)d.tiled_h);   // 0 where either side holds no tile
+            d.groups = spectrum_groups(blocks, env_int("MUSICA_SPECTRUM_GROUPS", 0));
+            d.part = partials;
+            partials += (size_t)d.groups * tile * tile * kSpectrumWords;
+            return TablePlace{d.groups, (size_t)tile * tile * kSpectrumWords};
+        },
+        [&] { return grow(c, "musica_sim_spectrum", &c->study.d_spectrum_part, &c->study.spectrum_part_cap, partials, "partial words"); },
+        [&](const SpectrumQueryDev* d_qs, int max_groups, unsigned long long* d_tables) {
+            launch_sim_spectrum(c->stream, d_qs, (int)count, max_groups, (int)tile, c->study.d_spectrum_part, d_tables);
+        },
+        nothing,
+        [&](uint32_t i, const musica_sim_query& q, const int64_t*) {
+            out[i].tiles = (uint64_t)(q.w / tile) * (q.h / tile);
+        });
+    ABI_CATCH("musica_sim_spectrum")
 }
 
 // ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------

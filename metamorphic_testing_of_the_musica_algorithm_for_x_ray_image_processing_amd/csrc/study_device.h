@@ -1,6 +1,6 @@
 // study_device.h — what the study's kernels share on the device (kernels_similarity.hip, kernels_scales.hip, kernels_joint.hip,
 // kernels_displace.hip, kernels_covariance.hip, kernels_ensemble.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip,
-// kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_scatter.hip, kernels_reach.hip, kernels_observer.hip, kernels_blobs.hip): the address-space typedefs, the
+// kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_scatter.hip, kernels_reach.hip, kernels_observer.hip, kernels_blobs.hip, kernels_spectrum.hip): the address-space typedefs, the
 // reductions and their ONE order, the workgroup's prefix sum, the
 // 64 x 64 tile of a region, the pixel words of the kernels that stream a u16 plane and the insertion body of the patch relations
 // (insert_patches), the packed byte windows of k_displace and k_cov_add, the staged windows of k_gradients and k_order (stage_windows), and the

@@ -1044,7 +1044,7 @@ def _device_scales(proc, queries, opt):
     return out
 
 
-# The six metrics that score every comparison of a row, each one entry of this table, in SCORING order: the order of a row's calls.
+# The seven metrics that score every comparison of a row, each one entry of this table, in SCORING order: the order of a row's calls.
 # option: run_study's argument; suffix: comparison <c> of a row (COMPARED) gets the sibling key <c>_<suffix>; on(value): whether the
 # normalised option asks for the metric; check(value): the option checked (ValueError) and normalised; host(opt, out, plane, region):
 # one comparison's value, the restatement on the output and the reference plane; device(proc, queries, opt): the values of a row's
@@ -1069,6 +1069,9 @@ COMPARISON_METRICS = (
     ComparisonMetric("blobs", "blobs", lambda v: v is not None, lambda v: None if v is None else mp.blob_threshold(v),
                      lambda opt, out, plane, region: blob_row(blob_statistics(out, plane, [region], opt.blobs, opt.blob_connectivity)[0]),
                      lambda proc, queries, opt: [blob_row(r) for r in proc.sim_blobs(queries, opt.blobs, opt.blob_connectivity)], METRIC_CSVS["blobs"]),
+    ComparisonMetric("spectrum", "spectrum", lambda v: v is not None, lambda v: None if v is None else mp.spectrum_tile(v),
+                     lambda opt, out, plane, region: spectrum_row(spectrum_statistics(out, plane, [region], opt.spectrum)[0], opt.spectrum),
+                     lambda proc, queries, opt: [spectrum_row(r, opt.spectrum) for r in proc.sim_spectrum(queries, opt.spectrum)], METRIC_CSVS["spectrum"]),
 )
 TONE_KEYS, SCALE_ROW_KEYS, GRADIENT_ROW_KEYS, ORDER_ROW_KEYS, LATTICE_ROW_KEYS, BLOB_ROW_KEYS = \
     ({c: "%s_%s" % (c, m.suffix) for c in COMPARED} for m in COMPARISON_METRICS[:6])   # comparison -> its sibling key, of the metrics that tests ask by name
@@ -1143,7 +1146,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
                   gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, codecs=None,
-                  lattice=0, blobs=None, blob_connectivity=8, order=False):
+                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1445,7 +1448,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, order=False):
+              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1709,7 +1712,19 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     fill and the border share), "largest_box", the per-class "class_components" and "class_pixels" and the exact "table". On the device
     one musica_sim_blobs call behind the lattice's; on the host the restatement labels the same crops. Everything is an integer and
     there is one summary function: the values are equal to the last bit on every path. With blobs=None the rows and the launches are
-    exactly as before. Label maps are not written."""
+    exactly as before. Label maps are not written.
+
+    spectrum: a tile side T, one of 8, 16, 32, 64 (processing.spectrum_tile; None: off), asks which spatial frequency band and
+    orientation of the image itself every comparison changed, and by what gain: the exact Walsh-Hadamard transforms of the whole T x T
+    tiles of both sides (spectrum_statistics; the Walsh octaves are the Haar subbands). Every comparison dict of a row gains a sibling
+    behind all other keys, the blobs' included: direct_spectrum, registered_spectrum and, with a vendor image, reference_spectrum and
+    registered_reference_spectrum; present exactly where the original is, None where it is None or where its region holds no whole
+    tile. Each is spectrum_row's dict: spectrum_summary's "bands" and "radial" (gain, coherence and error share per band pair and per
+    radial band), the SPECTRUM_KEYS (slope, the horizontal, vertical, diagonal and dc error shares, ac_gain, ac_coherence), "tile",
+    "tiles" and the exact "table". On the device one musica_sim_spectrum call behind the blobs'; on the host the restatement
+    transforms the same crops. Everything is an integer and there is one summary function: the values are equal to the last bit on
+    every path. Anything but None or one of the four sides is a ValueError; with spectrum=None the rows and the launches are exactly as
+    before. Nothing asserts what the gains are: that is the finding."""
     options = {k: v for k, v in locals().items() if k not in ("raw", "runner", "rng")}   # every option by its name, as study_options takes them
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, **options)
@@ -1723,7 +1738,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -2006,6 +2021,10 @@ def main(argv=None):
                          "much of the change is isolated pixels and how much sits in components of 16 pixels or more, the largest one's "
                          "share and box, written to blob_robustness.csv; on the GPU with --device-metrics / --device-alterations "
                          "(musica_sim_blobs)")
+    ap.add_argument("--spectrum", type=int, default=None, choices=mp.SPECTRUM_TILES, metavar="T",
+                    help="add the exact Walsh spectrum of every comparison over its whole T x T tiles, T one of 8, 16, 32, 64: gain, coherence "
+                         "and error share per octave band and orientation, written to spectrum_robustness.csv; on the GPU with "
+                         "--device-metrics / --device-alterations (musica_sim_spectrum)")
     ap.add_argument("--blob-connectivity", type=int, default=8, choices=(4, 8), help="the neighbourhood of --blobs (default 8)")
     ap.add_argument("--order", action="store_true",
                     help="ask whether the local order of the gray levels survived: the census signs of every comparison over the 7 x 7 "
@@ -2088,7 +2107,7 @@ def main(argv=None):
                     **({"ensemble_batch": args.ensemble_batch} if args.ensemble else {}))
     shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
                  {"displacement": args.displacement} if args.displacement else {}
-    for m in COMPARISON_METRICS[1:]:   # --scales .. --blobs, under their options' names (--tone and --symmetries are passed whatever they say)
+    for m in COMPARISON_METRICS[1:]:   # --scales .. --spectrum, under their options' names (--tone and --symmetries are passed whatever they say)
         if m.on(getattr(args, m.option)):
             shift_args[m.option] = getattr(args, m.option)
     if args.blobs is not None:

@@ -2331,3 +2331,136 @@ def blob_summary(stats):
 def blob_row(stats):
     """A row's *_blobs value: blob_summary's dict and "table", the (BLOB_CLASSES, 6) exact integers as nested lists."""
     return dict(blob_summary(stats), table=np.asarray(stats["table"]).astype(np.uint64).tolist())
+
+
+# ---- spectrum: the exact Walsh transforms of a comparison (not in the reference's script) ---------------------------------------------
+# MUSICA amplifies bands, so its transfer function is a gain per band. The grating rows measure it on inserted sine patches, the scales on
+# low-pass pooled planes without orientation; the transform-domain sums of a comparison give, for the image itself, the gain, the coherence
+# and the share of the error per band and orientation. A Fourier transform cannot be exact integers; the Walsh-Hadamard transform can, and
+# its octave bands are the Haar subbands. spectrum_statistics is the contract of musica_sim_spectrum (include/musica.h), whose tables are
+# bit-identical to it; spectrum_summary is what the study reports of the integers, one function for every path.
+
+_WALSH = {}
+
+
+def walsh_matrix(tile):
+    """The T x T Walsh matrix in sequency order, int64: row s is the row of the Sylvester Hadamard matrix (scipy.linalg.hadamard) with
+    exactly s sign changes. T as processing.spectrum_tile takes it."""
+    T = mp.spectrum_tile(tile)
+    if T not in _WALSH:
+        from scipy.linalg import hadamard
+        H = hadamard(T).astype(np.int64)
+        changes = (H[:, 1:] != H[:, :-1]).sum(axis=1)
+        if sorted(changes.tolist()) != list(range(T)):
+            raise AssertionError("the sign changes of the Sylvester rows of order %d are not 0 .. %d" % (T, T - 1))
+        _WALSH[T] = (H[np.argsort(changes)], np.argsort(changes))
+    return _WALSH[T][0]
+
+
+def _hadamard_axis(x, axis):
+    """The butterflies of the Sylvester Hadamard transform along `axis` (a power of two long) of an int64 array: natural order."""
+    x = np.moveaxis(x, axis, -1)
+    shape, T = x.shape, x.shape[-1]
+    h = 1
+    while h < T:
+        y = x.reshape(shape[:-1] + (T // (2 * h), 2, h))
+        x = np.stack([y[..., 0, :] + y[..., 1, :], y[..., 0, :] - y[..., 1, :]], axis=-2).reshape(shape)
+        h *= 2
+    return np.moveaxis(x, -1, axis)
+
+
+def spectrum_statistics(a, b, queries, tile):
+    """What musica_sim_spectrum returns for every query (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes (side a, side b): a
+    list of dicts. A region holds tx = w // T by ty = h // T whole tiles of T x T pixels, T = tile in 8, 16, 32, 64, anchored at its
+    first pixel on either side; the remainder columns and rows are not counted. Per tile A = W a W^T and B = W b W^T in integers
+    (W = walsh_matrix(T)); "table" is the (T, T, 3) int64 array, indexed [row sequency][column sequency], of the sums over the tiles
+    of A^2, B^2 and A B (processing.SPECTRUM_FIELDS), all zeros where "tiles" = tx ty is 0. The butterflies here are a fast form of the
+    two matrix products; tests/test_spectrum_restatement.py holds them to the literal ones."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("spectrum_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    T = mp.spectrum_tile(tile)
+    walsh_matrix(T)
+    order = _WALSH[T][1]   # the natural index of every sequency
+    res = []
+    for region in queries:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        tx, ty = w // T, h // T
+        table = np.zeros((T, T, len(mp.SPECTRUM_FIELDS)), dtype=np.int64)
+        if tx and ty:
+            coeff = []
+            for plane, x0, y0 in ((a, ax, ay), (b, bx, by)):
+                tiles = plane[y0:y0 + ty * T, x0:x0 + tx * T].astype(np.int64).reshape(ty, T, tx, T)
+                coeff.append(_hadamard_axis(_hadamard_axis(tiles, 1), 3)[:, order][:, :, :, order])
+            A, B = coeff
+            table[:, :, 0], table[:, :, 1], table[:, :, 2] = (A * A).sum(axis=(0, 2)), (B * B).sum(axis=(0, 2)), (A * B).sum(axis=(0, 2))
+        res.append({"table": table, "tiles": tx * ty})
+    return res
+
+
+SPECTRUM_BAND_KEYS = ("gain", "coherence", "error")   # spectrum_summary's numbers of a band pair and of a radial band
+SPECTRUM_KEYS = ("slope", "horizontal", "vertical", "diagonal", "dc", "ac_gain", "ac_coherence")   # ... and of the whole table; "bands" and "radial" beside them
+
+
+def _spectrum_band(aa, bb, ab, total):
+    """gain = sqrt(sum A^2 / sum B^2), coherence = sum A B / sqrt(sum A^2 sum B^2), error = the share of sum (A - B)^2 in `total`."""
+    return {"gain": math.sqrt(aa / bb) if bb else None, "coherence": ab / math.sqrt(aa * bb) if aa and bb else None,
+            "error": (aa + bb - 2 * ab) / total if total else 0.0}
+
+
+def spectrum_summary(table, tiles, tile):
+    """What the study reports of a comparison's Walsh sums, from spectrum_statistics' (or musica_sim_spectrum's) exact integers of ONE
+    query: one function for every study path; None where `tiles` is 0. The band of a sequency s is s.bit_length(): 0 (DC), 1 .. log2 T
+    per axis, the octaves of the Haar subbands. With the three sums added up over a set of coefficients,
+        gain        sqrt(sum A^2 / sum B^2): what side a has of the band over what side b has; None where sum B^2 is 0
+        coherence   sum A B / sqrt(sum A^2 sum B^2): 1 where a's band is b's times a positive number; None where either sum is 0
+        error       the set's share of sum (A - B)^2 over the whole table (by Parseval T^2 times the sum of squared differences of the
+                    tiled area); 0.0 everywhere where the sides are equal
+    "bands"[cy][cx] has the three for the band pair (row band cy, column band cx), "radial"[r] for the pairs with max(cy, cx) = r.
+    "slope": the least-squares slope of log2 gain on r over the AC radial bands r >= 1 that have a gain above 0 (None with fewer than
+    two): the octave-to-octave tilt of the transfer function. "horizontal", "vertical", "diagonal", "dc": the error shares of the pairs
+    with cx > cy (finer along a row than down a column), cx < cy, cx = cy > 0, and of the DC coefficient. "ac_gain", "ac_coherence":
+    gain and coherence over every coefficient but DC. Every share and quotient is one division of exact integers."""
+    T = mp.spectrum_tile(tile)
+    t = np.asarray(table)
+    if t.shape != (T, T, len(mp.SPECTRUM_FIELDS)) or t.dtype.kind not in "iu":
+        raise ValueError("a spectrum table of tile %d is (%d, %d, %d) integers, got %r %s" % (T, T, T, len(mp.SPECTRUM_FIELDS), t.shape, t.dtype))
+    if not int(tiles):
+        return None
+    bands = T.bit_length()   # 0 .. log2 T
+    v = t.astype(np.int64)   # sum A B is signed: a uint64 table holds it in two's complement
+    sums = [[[0, 0, 0] for _ in range(bands)] for _ in range(bands)]
+    for sv in range(T):
+        for su in range(T):
+            cell = sums[sv.bit_length()][su.bit_length()]
+            for f in range(3):
+                cell[f] += int(v[sv, su, f])
+    pairs = [(cy, cx) for cy in range(bands) for cx in range(bands)]
+    over = lambda keep: tuple(sum(sums[cy][cx][f] for cy, cx in pairs if keep(cy, cx)) for f in range(3))   # noqa: E731
+    err = lambda s: s[0] + s[1] - 2 * s[2]   # noqa: E731
+    total = err(over(lambda cy, cx: True))
+    share = lambda keep: err(over(keep)) / total if total else 0.0   # noqa: E731
+    out = {"bands": [[_spectrum_band(*sums[cy][cx], total) for cx in range(bands)] for cy in range(bands)],
+           "radial": [_spectrum_band(*over(lambda cy, cx, r=r: max(cy, cx) == r), total) for r in range(bands)]}
+    points = [(r, math.log2(band["gain"])) for r, band in enumerate(out["radial"]) if r >= 1 and band["gain"]]
+    if len(points) >= 2:
+        mx, my = sum(x for x, _ in points) / len(points), sum(y for _, y in points) / len(points)
+        out["slope"] = sum((x - mx) * (y - my) for x, y in points) / sum((x - mx) ** 2 for x, _ in points)
+    else:
+        out["slope"] = None
+    out["horizontal"], out["vertical"] = share(lambda cy, cx: cx > cy), share(lambda cy, cx: cx < cy)
+    out["diagonal"], out["dc"] = share(lambda cy, cx: cx == cy and cx > 0), share(lambda cy, cx: cx == 0 and cy == 0)
+    ac = _spectrum_band(*over(lambda cy, cx: cx > 0 or cy > 0), total)
+    out["ac_gain"], out["ac_coherence"] = ac["gain"], ac["coherence"]
+    return out
+
+
+def spectrum_row(stats, tile):
+    """A row's *_spectrum value from ONE dict of spectrum_statistics (or sim_spectrum): spectrum_summary's dict, "tile", "tiles" and
+    "table", the (T, T, 3) exact integers as nested lists; None where the region holds no tile."""
+    summary = spectrum_summary(stats["table"], stats["tiles"], tile)
+    if summary is None:
+        return None
+    return dict(summary, tile=int(tile), tiles=int(stats["tiles"]), table=np.asarray(stats["table"]).astype(np.int64).tolist())

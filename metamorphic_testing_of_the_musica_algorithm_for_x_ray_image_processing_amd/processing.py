@@ -203,6 +203,9 @@ LATTICE_MAX_PERIOD = 32     # MUSICA_LATTICE_MAX_PERIOD
 LATTICE_MAX_QUERIES = 16    # MUSICA_LATTICE_MAX_QUERIES
 BLOBS_MAX_QUERIES = 4       # MUSICA_BLOBS_MAX_QUERIES
 BLOB_CLASSES = 32           # MUSICA_BLOB_CLASSES
+SPECTRUM_MAX_TILE = 64      # MUSICA_SPECTRUM_MAX_TILE
+SPECTRUM_MAX_QUERIES = 4    # MUSICA_SPECTRUM_MAX_QUERIES
+SPECTRUM_TILES = (8, 16, 32, 64)
 
 
 def zoom_ratio(zoom):
@@ -250,6 +253,20 @@ def lattice_period(period, origin):
     if not 0 <= o < P:
         raise ValueError("lattice origin %d is not in 0 .. %d" % (o, P - 1))
     return P, o
+
+
+def spectrum_tile(tile):
+    """The tile side T of a Walsh spectrum as metrics.spectrum_statistics and the library take it: one of 8, 16, 32, 64, an integer, else
+    ValueError."""
+    try:
+        if isinstance(tile, (bool, np.bool_, str)) or tile != int(tile):
+            raise TypeError
+        T = int(tile)
+    except (TypeError, ValueError):
+        raise ValueError("a spectrum tile is one of 8, 16, 32, 64, got %r" % (tile,))
+    if T not in SPECTRUM_TILES:
+        raise ValueError("spectrum tile %d is not one of 8, 16, 32, 64" % T)
+    return T
 
 
 def blob_threshold(threshold):
@@ -694,6 +711,14 @@ class SimLatticeResult(C.Structure):
 BLOB_FIELDS = ("components", "pixels", "sum_d", "sum_dd", "box_area", "border")   # the six words of a class of a blob table (MUSICA_BLOB_WORDS)
 
 
+SPECTRUM_FIELDS = ("sum_aa", "sum_bb", "sum_ab")   # the three words of a coefficient of a spectrum table (MUSICA_SPECTRUM_WORDS)
+
+
+class SimSpectrumResult(C.Structure):
+    """musica_sim_spectrum_result: where a query's table lies in `tables` and the number of whole tiles."""
+    _fields_ = [("table_offset", C.c_uint64), ("tiles", C.c_uint64)]
+
+
 class SimBlobsResult(C.Structure):
     """musica_sim_blobs_result: where a query's table and label plane lie, its counts and its largest component."""
     _fields_ = [("table_offset", C.c_uint64), ("label_offset", C.c_uint64), ("pixels", C.c_uint64), ("changed", C.c_uint64), ("components", C.c_uint64),
@@ -923,6 +948,7 @@ ABI = {
     "musica_sim_reach_classes": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, _U8P]),
     "musica_sim_order": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimOrderResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_lattice": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimLatticeResult), C.POINTER(C.c_uint64), C.c_uint64]),
+    "musica_sim_spectrum": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimSpectrumResult), C.POINTER(C.c_int64), C.c_uint64]),
     "musica_sim_blobs": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimBlobsResult), C.POINTER(C.c_uint64), C.c_uint64, _U32P, C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
@@ -1409,7 +1435,7 @@ class MusicaProcessing:
         return out
 
     def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False, trail=()):
-        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _reach share: the refusals of sim_<name> before any call
+        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _reach share: the refusals of sim_<name> before any call
         (most: 1 .. most queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead`
         in front of the count and `trail` (blobs: the label plane and its length) behind the tables' length. Returns the results and the
         flat tables, `words` zeroed words of `dtype`."""
@@ -1526,6 +1552,21 @@ class MusicaProcessing:
                 lo = int(r.label_offset)
                 d["labels"] = planes[lo:lo + int(q.w) * int(q.h)].reshape(int(q.h), int(q.w)).copy()
             out.append(d)
+        return out
+
+    def sim_spectrum(self, queries, tile):
+        """metrics.spectrum_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 1, 1 .. SPECTRUM_MAX_QUERIES of them, all in one launch; tile one of 8, 16, 32, 64 (spectrum_tile:
+        ValueError before any call, as for a count out of range). Returns one dict per query: "table", a (T, T, 3) int64 array of the
+        exact SPECTRUM_FIELDS per [row sequency][column sequency], and the Python int "tiles" = (w // T) (h // T)."""
+        T = spectrum_tile(tile)
+        qs = _queries(queries)
+        per = T * T * len(SPECTRUM_FIELDS)
+        res, tables = self._sim_tables("spectrum", qs, SimSpectrumResult, np.int64, len(qs) * per, T, most=SPECTRUM_MAX_QUERIES)
+        out = []
+        for r in res:
+            at = int(r.table_offset)
+            out.append({"table": tables[at:at + per].reshape(T, T, len(SPECTRUM_FIELDS)).copy(), "tiles": int(r.tiles)})
         return out
 
     def sim_reach(self, queries, radii):

@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import BLOB_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
+from .metrics import BLOB_KEYS, SPECTRUM_BAND_KEYS, SPECTRUM_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -49,6 +49,10 @@ LATTICE_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'period', 'periodi
 # then the components and the pixels of every class
 BLOB_CSV_HEADER = ['raw file', 'alteration', 'comparison'] + [k.replace('_', ' ') for k in BLOB_KEYS] + ['largest x0', 'largest y0', 'largest x1', 'largest y1'] + \
                   ['%s class %d' % (what, c) for what in ('components', 'pixels') for c in range(mp.BLOB_CLASSES)]
+
+# spectrum_robustness.csv: one line per row, comparison the row has and radial band, ascending; the band's numbers, then the totals of
+# the comparison, the same on each of its lines
+SPECTRUM_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'tile', 'tiles', 'band'] + list(SPECTRUM_BAND_KEYS) + [k.replace('_', ' ') for k in SPECTRUM_KEYS]
 
 ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
 ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
@@ -187,15 +191,17 @@ def _group_lines(studies, key, groups, cells):
                 yield [raw_name, r["alteration"], label] + cells(d, g)
 
 
-def _comparison_lines(studies, groups, cells):
+def _comparison_lines(studies, groups, cells, several=False):
     """The lines of a comparison metric's per-comparison file: one per row, the unaltered one included, and comparison that the row
-    has, in the groups' order: the raw file, the alteration, the comparison's label, then cells(its value)."""
+    has, in the groups' order: the raw file, the alteration, the comparison's label, then cells(its value); several: cells(its value)
+    is a list of lines' cells, a line each."""
     for raw_name, rows in studies:
         for r in rows:
             for key, label in groups:
                 t = r.get(key)
                 if t is not None:
-                    yield [raw_name, r["alteration"], label] + cells(t)
+                    for line in (cells(t) if several else [cells(t)]):
+                        yield [raw_name, r["alteration"], label] + line
 
 
 def _blank(v):
@@ -221,9 +227,17 @@ def _blob_cells(t):
     return [_blank(t[k]) for k in BLOB_KEYS] + list(t["largest_box"] or [""] * 4) + list(t["class_components"]) + list(t["class_pixels"])
 
 
+def _spectrum_lines(t):
+    """A line per radial band: the tile, the tiles, the band and its SPECTRUM_BAND_KEYS, then the comparison's SPECTRUM_KEYS (an empty
+    cell where one is None)."""
+    totals = [_blank(t[k]) for k in SPECTRUM_KEYS]
+    return [[t["tile"], t["tiles"], r] + [_blank(band[k]) for k in SPECTRUM_BAND_KEYS] + totals for r, band in enumerate(t["radial"])]
+
+
 # The files of the comparison metrics (harness.COMPARISON_METRICS), by key suffix: a study that has direct_<suffix> gets the file.
 # per "row": one line per row, header(with_reference), then cells(a group's value or None) for every group; per "comparison": one line
-# per row and comparison that the row has, the header as it stands, then cells(the value).
+# per row and comparison that the row has, the header as it stands, then cells(the value); per "band": the same with a line for each
+# entry of cells(the value).
 MetricCsv = collections.namedtuple("MetricCsv", "file per header cells")
 METRIC_CSVS = {
     "tone": MetricCsv("tone_robustness.csv", "row", tone_csv_header, lambda t: _cells(t, mp.JOINT_METRICS)),
@@ -232,6 +246,7 @@ METRIC_CSVS = {
     "order": MetricCsv("order_robustness.csv", "comparison", ORDER_CSV_HEADER, _order_cells),
     "lattice": MetricCsv("lattice_robustness.csv", "comparison", LATTICE_CSV_HEADER, _lattice_cells),
     "blobs": MetricCsv("blob_robustness.csv", "comparison", BLOB_CSV_HEADER, _blob_cells),
+    "spectrum": MetricCsv("spectrum_robustness.csv", "band", SPECTRUM_CSV_HEADER, _spectrum_lines),
 }
 
 
@@ -295,6 +310,11 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     Studies run with blobs=T (rows[0] has "direct_blobs") also get blob_robustness.csv (BLOB_CSV_HEADER): one line per row, the
     unaltered one included, and comparison that the row has: the comparison's name, blob_summary's numbers, the largest component's
     box, then the components and the pixels of every size class.
+
+    Studies run with spectrum=T (rows[0] has "direct_spectrum") also get spectrum_robustness.csv (SPECTRUM_CSV_HEADER): one line per
+    row, the unaltered one included, comparison that the row has (none where its region holds no whole tile) and radial band 0 .. log2 T:
+    the comparison's name, T, the tiles, the band, its gain, coherence and error share, then spectrum_summary's totals of the
+    comparison, the same on each of its lines.
 
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
@@ -372,7 +392,7 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
             _write_csv(out_dir, metric.file, metric.header(len(groups) == 4),
                        _lines(covered, lambda r, ovd: [c for key, _ in groups for c in metric.cells(r.get(key))]))
         elif covered:
-            _write_csv(out_dir, metric.file, metric.header, _comparison_lines(covered, groups, metric.cells))
+            _write_csv(out_dir, metric.file, metric.header, _comparison_lines(covered, groups, metric.cells, metric.per == "band"))
     for name, header, key, groups, cells in RELATION_CSVS:
         if having(key):
             _write_csv(out_dir, name, header, _group_lines(having(key), key, groups, cells))
