@@ -46,7 +46,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     tail), a ragged region from mid-tile with different origins on the two sides, a one-pixel column and a single pixel; integers only;
   * the Walsh spectrum at N = 151 of other images' outputs against slot 0, at tile 8 and tile 64: the full frame (16 x 16 tiles of 8
     in 3 x 3 blocks with a ragged last one; 2 x 2 tiles of 64), a ragged region from mid-block with different origins on the two
-    sides, a column that holds no tile and a single tile of 8; integers only.
+    sides, a column that holds no tile and a single tile of 8; integers only;
+  * the co-occurrence tables at N = 151 of other images' outputs against slot 0, at 8 levels with the distances 1, 2, 4, 8 and at 64
+    levels with 3 and 16: the full frame (131 x 131: 3 x 3 tiles with a three-pixel ragged tail), a ragged region from mid-tile with
+    different origins on the two sides, a one-pixel column (no horizontal pair) and a single pixel (no pair); integers only.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -193,5 +196,8 @@ if hasattr(p, "sim_blobs"):       # likewise a --tree from before the cluster me
 if hasattr(p, "sim_spectrum"):    # likewise a --tree from before the spectrum metric
     qs = [(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 7, NW - 1), (1, 0, NW - 8, NW - 8, 0, 0, 8, 8)]
     note("musica_sim_spectrum", [p.sim_spectrum(qs, 8), p.sim_spectrum(qs, 64)])
+if hasattr(p, "sim_cooccurrence"):   # likewise a --tree from before the texture metric
+    qs = [(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 1, NW - 1), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)]
+    note("musica_sim_cooccurrence", [p.sim_cooccurrence(qs, 8, (1, 2, 4, 8)), p.sim_cooccurrence(qs, 64, (3, 16))])
 p.cleanup()
 print(json.dumps(digests))

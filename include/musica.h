@@ -1221,6 +1221,39 @@ typedef struct musica_sim_spectrum_result {
 int musica_sim_spectrum(musica_ctx* ctx, uint32_t tile, uint32_t count, const musica_sim_query* queries,
                         musica_sim_spectrum_result* results, int64_t* tables, uint64_t table_words);
 
+/* ---- texture: the gray-level co-occurrence matrices of a comparison (new, not in the reference) ----
+ * Did the texture of the image survive? The second-order gray-level statistics of Haralick (1973), the terms in which radiomics
+ * reports the stability of features under processing. metrics.cooccurrence_statistics is the contract. Queries are
+ * musica_sim_compare's with w, h >= 1, at most MUSICA_COOCCURRENCE_MAX_QUERIES (a row's direct, registered and two vendor
+ * comparisons). `levels` G is one of 8, 16, 32, 64: the level of an 8-bit pixel v is v >> (8 - log2 G). `distances` holds
+ * distance_count = 1 .. MUSICA_COOCCURRENCE_MAX_DISTANCES distinct ascending d, each 1 .. MUSICA_COOCCURRENCE_MAX_DISTANCE. The four
+ * directions of a distance d have the offsets (dx, dy), y running down: 0 degrees (d, 0), 45 (d, d), 90 (0, d), 135 (-d, d). Side a is
+ * the graded plane of the query's image quantised as musica_sim_compare quantises it, side b the query's reference slot. A pair
+ * (p, p + offset) counts on a side where BOTH pixels lie inside the region on that side, once, in T[level(p)][level(p + offset)]:
+ * nothing is symmetrised. Query i gets distance_count * 4 * 2 * G * G uint32_t in the flat `tables`, from results[i].table_offset (in
+ * words) on, indexed [distance][direction][side a = 0, b = 1][first level][second level]; results[i].pairs[k][direction] =
+ * max(w - |dx|, 0) * max(h - dy, 0) for the distances given, 0 for the others. A region too small for an offset has no pair there and
+ * an all-zero table: that is not a refusal. Identities: every [k][direction][side] table sums to pairs[k][direction]; its row and column
+ * sums are the level histograms of the sub-rectangles that the first and the second pixels run over; the table at G / 2 is the 2 x 2
+ * fold of the table at G. A side is at most 16364, so a table entry stays below 2^28 and uint32_t is exact. Everything is an integer:
+ * the tables equal the restatement word for word and repeat from call to call, whatever MUSICA_COOCCURRENCE_GROUPS (the workgroups
+ * of a query's distance and side, read at every call) says. Every word of the tables is written and nothing behind them. Synchronous,
+ * on the context's stream after whatever was enqueued there; changes no slot, no result of a step and no input image; scratch is
+ * allocated on first use. Refused before any device work: what musica_sim_compare refuses (with the smallest side 1 and at most
+ * MUSICA_COOCCURRENCE_MAX_QUERIES queries, none included), then levels that are not one of the four, a NULL or empty or too long
+ * distance list, a distance out of range or not above the one before it, a NULL `tables` and table_words below the tables' words.
+ * After a refusal the context stays usable. */
+#define MUSICA_COOCCURRENCE_MAX_DISTANCES 4
+#define MUSICA_COOCCURRENCE_MAX_DISTANCE 16
+#define MUSICA_COOCCURRENCE_MAX_LEVELS 64
+#define MUSICA_COOCCURRENCE_MAX_QUERIES 4
+typedef struct musica_sim_cooccurrence_result {
+    uint64_t table_offset;          /* where the query's tables start in `tables`, in words */
+    uint64_t pairs[MUSICA_COOCCURRENCE_MAX_DISTANCES][4];   /* [distance][direction]: the pairs that each of its two tables holds */
+} musica_sim_cooccurrence_result;
+int musica_sim_cooccurrence(musica_ctx* ctx, uint32_t levels, uint32_t distance_count, const uint32_t* distances, uint32_t count,
+                            const musica_sim_query* queries, musica_sim_cooccurrence_result* results, uint32_t* tables, uint64_t table_words);
+
 /* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
  * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change
  * outwards: the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global

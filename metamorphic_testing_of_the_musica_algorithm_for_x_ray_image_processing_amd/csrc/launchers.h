@@ -550,6 +550,33 @@ inline int spectrum_groups(int blocks, int most = 0) {
 // metrics.spectrum_statistics over `count` queries (grid.x = max_groups, the largest `groups`, at least 1). part: room for every query's
 // partial tables; tables: every query's words, zeroed by the caller: the fold launch adds into them with u64 atomics
 void launch_sim_spectrum(hipStream_t st, const SpectrumQueryDev* d_qs, int count, int max_groups, int tile, unsigned long long* part, unsigned long long* tables);
+// kernels_cooccurrence.hip: the texture metric. One comparison of musica_sim_cooccurrence: tiles_x / tiles_y: its region's 64 x 64
+// tiles; groups: the persistent workgroups that share the tiles of ONE distance and side (cooccurrence_groups); table: where its
+// distance_count * 4 * 2 * G * G words start in the launch's flat tables, in words.
+constexpr int kCooccurrenceMaxDistances = 4;   // MUSICA_COOCCURRENCE_MAX_DISTANCES
+constexpr int kCooccurrenceMaxDistance = 16;   // MUSICA_COOCCURRENCE_MAX_DISTANCE
+constexpr int kCooccurrenceMaxLevels = 64;     // MUSICA_COOCCURRENCE_MAX_LEVELS
+constexpr int kCooccurrenceMaxQueries = 4;     // MUSICA_COOCCURRENCE_MAX_QUERIES
+struct CooccurrenceQueryDev : SimRegion {
+    int tiles_x, tiles_y, groups;
+    unsigned long long table;
+};
+struct CooccurrenceDistances {
+    int count;
+    int d[kCooccurrenceMaxDistances];
+};
+// The workgroups that one distance and side of a query of `tiles` tiles get: min(tiles, want), where want is kCooccurrenceGroups, or
+// `most` where 0 < most < want (the tuning variable MUSICA_COOCCURRENCE_GROUPS, read at every call): the tables do not depend on it,
+// a workgroup's u32 counters hold any number of tiles (kernels_cooccurrence.hip, THE WIDTH RULE). A launch has 2 * distance_count
+// times as many workgroups a query; the number is a measurement.
+constexpr int kCooccurrenceGroups = 256;
+inline int cooccurrence_groups(int tiles, int most = 0) {
+    const int want = most > 0 && most < kCooccurrenceGroups ? most : kCooccurrenceGroups;
+    return tiles < want ? tiles : want;
+}
+// metrics.cooccurrence_statistics over `count` queries at `levels` gray levels (grid.x = max_groups, the largest `groups`, at least 1;
+// grid.y = 2 * dist.count). tables: every query's words, zeroed by the caller: the workgroups add into them with u32 atomics
+void launch_sim_cooccurrence(hipStream_t st, const CooccurrenceQueryDev* d_qs, int count, int max_groups, int levels, const CooccurrenceDistances& dist, uint32_t* tables);
 // kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
 // Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
 constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII

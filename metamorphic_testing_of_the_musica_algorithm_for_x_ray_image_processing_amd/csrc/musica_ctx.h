@@ -194,6 +194,9 @@ struct StudyState {
     unsigned long long* d_spectrum_tables = nullptr;  // [MUSICA_SPECTRUM_MAX_QUERIES][kSpectrumMaxTile^2][kSpectrumWords], allocated by the first musica_sim_spectrum
     unsigned long long* d_spectrum_part = nullptr;    // the workgroups' partial tables of one call: spectrum_part_cap words, regrown when a call needs more
     size_t spectrum_part_cap = 0;
+    // musica_sim_cooccurrence: the queries and the flat tables
+    CooccurrenceQueryDev* d_cooccurrence_q = nullptr;   // [MUSICA_COOCCURRENCE_MAX_QUERIES]
+    uint32_t* d_cooccurrence_tables = nullptr;          // [MUSICA_COOCCURRENCE_MAX_QUERIES][MAX_DISTANCES][4][2][MAX_LEVELS^2], allocated by the first musica_sim_cooccurrence
     // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
     // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
     uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either

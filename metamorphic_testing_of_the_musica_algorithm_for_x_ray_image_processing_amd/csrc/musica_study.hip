@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_codec.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
 // sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
@@ -413,7 +413,7 @@ static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion
     d.h = (int)q.h;
 }
 
-// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _reach) -----------------------------------------------
+// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _reach) -----------------------------------------------
 // Where a table call keeps its queries and its flat tables in musica_ctx::study, and what it takes: at most `most` queries with sides
 // of at least `min_side`. The tables' buffer holds `tables_cap` words from the first call on; where `grown` names its capacity it
 // holds the words of the largest call so far instead.
@@ -432,6 +432,7 @@ constexpr TableBuffers<OrderQueryDev, unsigned long long> kOrderBuffers{&StudySt
 constexpr TableBuffers<LatticeQueryDev, unsigned long long> kLatticeBuffers{&StudyState::d_lattice_q, &StudyState::d_lattice_tables, MUSICA_LATTICE_MAX_QUERIES, 2, (size_t)MUSICA_LATTICE_MAX_QUERIES * kLatticeMaxPeriod * kLatticeMaxPeriod * kLatticeWords};
 constexpr TableBuffers<BlobQueryDev, unsigned long long> kBlobBuffers{&StudyState::d_blob_q, &StudyState::d_blob_tables, MUSICA_BLOBS_MAX_QUERIES, 1, (size_t)MUSICA_BLOBS_MAX_QUERIES * kBlobClasses * kBlobWords};
 constexpr TableBuffers<SpectrumQueryDev, unsigned long long> kSpectrumBuffers{&StudyState::d_spectrum_q, &StudyState::d_spectrum_tables, MUSICA_SPECTRUM_MAX_QUERIES, 1, (size_t)MUSICA_SPECTRUM_MAX_QUERIES * kSpectrumMaxTile * kSpectrumMaxTile * kSpectrumWords};
+constexpr TableBuffers<CooccurrenceQueryDev, uint32_t> kCooccurrenceBuffers{&StudyState::d_cooccurrence_q, &StudyState::d_cooccurrence_tables, MUSICA_COOCCURRENCE_MAX_QUERIES, 1, (size_t)MUSICA_COOCCURRENCE_MAX_QUERIES * MUSICA_COOCCURRENCE_MAX_DISTANCES * 4 * 2 * kCooccurrenceMaxLevels * kCooccurrenceMaxLevels};
 constexpr TableBuffers<ReachQueryDev, unsigned long long> kReachBuffers{&StudyState::d_reach_q, &StudyState::d_reach_tables, MUSICA_REACH_MAX_QUERIES, 1, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords};
 
 // What a call's place() says of one query: its tiles or chunks (the launch's grid.x is the largest) and the words of its table.
@@ -1361,6 +1362,54 @@ int musica_sim_spectrum(musica_ctx* c, uint32_t tile, uint32_t count, const musi
             out[i].tiles = (uint64_t)(q.w / tile) * (q.h / tile);
         });
     ABI_CATCH("musica_sim_spectrum")
+}
+
+// ---- the co-occurrence matrices of a comparison (musica_sim_cooccurrence, include/musica.h; kernels_cooccurrence.hip) ------------------
+static_assert(kCooccurrenceMaxDistances == MUSICA_COOCCURRENCE_MAX_DISTANCES && kCooccurrenceMaxDistance == MUSICA_COOCCURRENCE_MAX_DISTANCE &&
+                  kCooccurrenceMaxLevels == MUSICA_COOCCURRENCE_MAX_LEVELS && kCooccurrenceMaxQueries == MUSICA_COOCCURRENCE_MAX_QUERIES,
+              "kernels_cooccurrence.hip's constants are include/musica.h's");
+
+int musica_sim_cooccurrence(musica_ctx* c, uint32_t levels, uint32_t distance_count, const uint32_t* distances, uint32_t count, const musica_sim_query* qs,
+                            musica_sim_cooccurrence_result* out, uint32_t* tables, uint64_t table_words) {
+    ABI_TRY
+    CooccurrenceDistances dist{};
+    return sim_query_tables(
+        c, "musica_sim_cooccurrence", kCooccurrenceBuffers, count, qs, out, tables, table_words,
+        [&] {
+            if (levels != 8 && levels != 16 && levels != 32 && levels != 64) return fail("musica_sim_cooccurrence: levels %u are not one of 8, 16, 32, 64", levels);
+            if (!distances) return fail("musica_sim_cooccurrence: distances is NULL");
+            if (distance_count == 0 || distance_count > MUSICA_COOCCURRENCE_MAX_DISTANCES)
+                return fail("musica_sim_cooccurrence: distance_count %u out of range [1, %d]", distance_count, MUSICA_COOCCURRENCE_MAX_DISTANCES);
+            for (uint32_t k = 0; k < distance_count; k++) {
+                if (distances[k] < 1 || distances[k] > MUSICA_COOCCURRENCE_MAX_DISTANCE)
+                    return fail("musica_sim_cooccurrence: distance %u: %u is not in 1 .. %d", k, distances[k], MUSICA_COOCCURRENCE_MAX_DISTANCE);
+                if (k && distances[k] <= distances[k - 1])
+                    return fail("musica_sim_cooccurrence: distance %u: %u is not above distance %u: %u", k, distances[k], k - 1, distances[k - 1]);
+                dist.d[k] = (int)distances[k];
+            }
+            dist.count = (int)distance_count;
+            return 1;
+        },
+        [&](const musica_sim_query& q, CooccurrenceQueryDev& d) {
+            d.groups = cooccurrence_groups(tile_grid(d, q.w, q.h), env_int("MUSICA_COOCCURRENCE_GROUPS", 0));
+            return TablePlace{d.groups, (size_t)distance_count * 4 * 2 * levels * levels};
+        },
+        nothing,
+        [&](const CooccurrenceQueryDev* d_qs, int max_groups, uint32_t* d_tables) {
+            launch_sim_cooccurrence(c->stream, d_qs, (int)count, max_groups, (int)levels, dist, d_tables);
+        },
+        nothing,
+        [&](uint32_t i, const musica_sim_query& q, const uint32_t*) {
+            memset(out[i].pairs, 0, sizeof(out[i].pairs));
+            for (uint32_t k = 0; k < distance_count; k++) {
+                const uint64_t d = distances[k], cols = q.w > d ? q.w - d : 0, rows = q.h > d ? q.h - d : 0;
+                out[i].pairs[k][0] = cols * q.h;    // (d, 0)
+                out[i].pairs[k][1] = cols * rows;   // (d, d)
+                out[i].pairs[k][2] = q.w * rows;    // (0, d)
+                out[i].pairs[k][3] = cols * rows;   // (-d, d)
+            }
+        });
+    ABI_CATCH("musica_sim_cooccurrence")
 }
 
 // ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------

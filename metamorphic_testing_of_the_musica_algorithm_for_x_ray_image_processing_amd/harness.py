@@ -1044,7 +1044,7 @@ def _device_scales(proc, queries, opt):
     return out
 
 
-# The seven metrics that score every comparison of a row, each one entry of this table, in SCORING order: the order of a row's calls.
+# The metrics that score every comparison of a row, each one entry of a table, in SCORING order: the order of a row's calls.
 # option: run_study's argument; suffix: comparison <c> of a row (COMPARED) gets the sibling key <c>_<suffix>; on(value): whether the
 # normalised option asks for the metric; check(value): the option checked (ValueError) and normalised; host(opt, out, plane, region):
 # one comparison's value, the restatement on the output and the reference plane; device(proc, queries, opt): the values of a row's
@@ -1072,6 +1072,14 @@ COMPARISON_METRICS = (
     ComparisonMetric("spectrum", "spectrum", lambda v: v is not None, lambda v: None if v is None else mp.spectrum_tile(v),
                      lambda opt, out, plane, region: spectrum_row(spectrum_statistics(out, plane, [region], opt.spectrum)[0], opt.spectrum),
                      lambda proc, queries, opt: [spectrum_row(r, opt.spectrum) for r in proc.sim_spectrum(queries, opt.spectrum)], METRIC_CSVS["spectrum"]),
+)
+# COMPARISON_METRICS is the seven entries above and ends with the spectrum: tests/test_spectrum_restatement.py holds it to that. The
+# study walks STUDY_METRICS, the same table with the metrics added since appended, in scoring order.
+STUDY_METRICS = COMPARISON_METRICS + (
+    ComparisonMetric("texture", "texture", lambda v: v is not None, lambda v: None if v is None else mp.cooccurrence_levels(v),
+                     lambda opt, out, plane, region: texture_row(cooccurrence_statistics(out, plane, [region], opt.texture, opt.texture_distances)[0], opt.texture, opt.texture_distances),
+                     lambda proc, queries, opt: [texture_row(r, opt.texture, opt.texture_distances) for r in proc.sim_cooccurrence(queries, opt.texture, opt.texture_distances)],
+                     METRIC_CSVS["texture"]),
 )
 TONE_KEYS, SCALE_ROW_KEYS, GRADIENT_ROW_KEYS, ORDER_ROW_KEYS, LATTICE_ROW_KEYS, BLOB_ROW_KEYS = \
     ({c: "%s_%s" % (c, m.suffix) for c in COMPARED} for m in COMPARISON_METRICS[:6])   # comparison -> its sibling key, of the metrics that tests ask by name
@@ -1146,7 +1154,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
                   gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, codecs=None,
-                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, order=False):
+                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1159,7 +1167,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     o["displacement"] = displacement = int(displacement)
     if displacement and not 1 <= displacement <= mp.SIM_MAX_RADIUS:
         raise ValueError("displacement radius %d is not in 1 .. %d" % (displacement, mp.SIM_MAX_RADIUS))
-    for m in COMPARISON_METRICS:
+    for m in STUDY_METRICS:
         if m.option in CHECKED_EARLY:
             o[m.option] = m.check(o[m.option])
     o["observer"] = _checked_flag("observer")(observer)
@@ -1179,24 +1187,25 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         raise ValueError("covariance is taken over the realisations of an ensemble: give ensemble > 0")
     for m in MOVED:
         o[m.option] = m.check(o[m.option] or (), n)
-    for m in COMPARISON_METRICS:
+    for m in STUDY_METRICS:
         if m.option not in CHECKED_EARLY:
             o[m.option] = m.check(o[m.option])
     if blob_connectivity not in (4, 8) or isinstance(blob_connectivity, (bool, np.bool_)):
         raise ValueError("blob_connectivity is 4 or 8, got %r" % (blob_connectivity,))
     o["blob_connectivity"] = int(blob_connectivity)
+    o["texture_distances"] = mp.cooccurrence_distances(texture_distances)
     for rel in RELATIONS:
         if o[rel.option] is not None:
             o[rel.option] = rel.check(o[rel.option], n)
     for g in (o["details"] if observer else ()):   # the views and banks of every grid, as the measurement will take them
         mp.view_list(*observer_views(output_details(g)), n - 2 * PROCESSING_MARGIN)
     compared = COMPARED[:2 if vendor is None else 4]
-    groups = {m.suffix: tuple("%s_%s" % (c, m.suffix) for c in compared) if m.on(o[m.option]) else () for m in COMPARISON_METRICS}
+    groups = {m.suffix: tuple("%s_%s" % (c, m.suffix) for c in compared) if m.on(o[m.option]) else () for m in STUDY_METRICS}
     groups.update(shift=("direct_shift", "registered_shift") if displacement else (), reach=("direct_reach",) if o["reach"] is not None else (),
                   ensemble=("ensemble",) if ensemble else (), relations=tuple(rel.key for rel in RELATIONS if o[rel.option] is not None),
                   observer=("observer",) if observer else (), warp=("warp",) if o["warps"] else ())
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + \
-           tuple(k for g in KEY_GROUPS + tuple(m.suffix for m in COMPARISON_METRICS if m.suffix not in KEY_GROUPS) for k in groups[g])
+           tuple(k for g in KEY_GROUPS + tuple(m.suffix for m in STUDY_METRICS if m.suffix not in KEY_GROUPS) for k in groups[g])
     for grid, default in (("shutters", scaled(SHUTTERS, n)), ("translations", scaled(TRANSLATIONS, n)), ("rotations", ROTATIONS),
                           ("sigmas", GAUSS_SIGMAS), ("factors", POISSON_FACTORS)):
         if o[grid] is None:
@@ -1260,7 +1269,7 @@ class Scorer:
     SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key and
     observer(details) a cd_ row's "observer". similarities, score and shifts take the row's comparisons, (reference key, region) pairs
     with a SLOT_* number as the key, and return one result each: similarities the five SIM_METRICS, score(metric, comparisons) the
-    sibling values of one entry of COMPARISON_METRICS, by the entry's host or device form, and shifts the displacement (the regions
+    sibling values of one entry of STUDY_METRICS, by the entry's host or device form, and shifts the displacement (the regions
     already inset; keep: the dicts carry their tile tables whatever displacement_tiles says, for a warp row's tracking). reach takes
     the row's direct comparison, behind similarities, and looks at the change of the input from `source`, the study's raw plane."""
 
@@ -1448,7 +1457,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, order=False):
+              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1724,7 +1733,20 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     "tiles" and the exact "table". On the device one musica_sim_spectrum call behind the blobs'; on the host the restatement
     transforms the same crops. Everything is an integer and there is one summary function: the values are equal to the last bit on
     every path. Anything but None or one of the four sides is a ValueError; with spectrum=None the rows and the launches are exactly as
-    before. Nothing asserts what the gains are: that is the finding."""
+    before. Nothing asserts what the gains are: that is the finding.
+
+    texture: the gray levels G, one of 8, 16, 32, 64 (processing.cooccurrence_levels; None: off), asks whether the texture of the image
+    survived: the gray-level co-occurrence matrices (Haralick 1973) of both sides of every comparison at texture_distances (1 .. 4
+    distinct ascending distances 1 .. 16, processing.cooccurrence_distances; checked like blob_connectivity, whether texture is given
+    or not) in the directions 0, 45, 90, 135 degrees (cooccurrence_statistics). Every comparison dict of a row gains a sibling behind
+    all other keys, the spectrum's included: direct_texture, registered_texture and, with a vendor image, reference_texture and
+    registered_reference_texture; present exactly where the original is, None where it is None or where its region has no pair at any
+    distance. Each is texture_row's dict: cooccurrence_summary's "distances" (per distance contrast, dissimilarity, homogeneity,
+    energy, entropy, correlation and anisotropy of either side, their differences and the Jensen-Shannon divergence; None for a
+    distance without a pair) and the largest "divergence", "levels", "distance_list" and the exact "pairs". On the device one
+    musica_sim_cooccurrence call behind the spectrum's; on the host the restatement counts the same crops. The tables are integers
+    and there is one summary function: the values are equal to the last bit on every path. With texture=None the rows and the launches
+    are exactly as before."""
     options = {k: v for k, v in locals().items() if k not in ("raw", "runner", "rng")}   # every option by its name, as study_options takes them
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, **options)
@@ -1733,12 +1755,12 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     full = (0, 0, 0, 0, shape[1], shape[0])
     scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
     scorer.source = raw   # what reach() takes the input's change against
-    metrics = [("", scorer.similarities)] + [("_" + m.suffix, functools.partial(scorer.score, m)) for m in COMPARISON_METRICS if m.on(getattr(opt, m.option))]
+    metrics = [("", scorer.similarities)] + [("_" + m.suffix, functools.partial(scorer.score, m)) for m in STUDY_METRICS if m.on(getattr(opt, m.option))]
     rows = []
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, texture, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -2025,6 +2047,13 @@ def main(argv=None):
                     help="add the exact Walsh spectrum of every comparison over its whole T x T tiles, T one of 8, 16, 32, 64: gain, coherence "
                          "and error share per octave band and orientation, written to spectrum_robustness.csv; on the GPU with "
                          "--device-metrics / --device-alterations (musica_sim_spectrum)")
+    ap.add_argument("--texture", type=int, default=None, choices=mp.COOCCURRENCE_LEVELS, metavar="G",
+                    help="add the texture of every comparison: the gray-level co-occurrence matrices of both sides at G levels, G one of 8, 16, "
+                         "32, 64, and Haralick's contrast, dissimilarity, homogeneity, energy, entropy and correlation, the anisotropy and the "
+                         "Jensen-Shannon divergence of the two sides per distance, written to texture_robustness.csv; on the GPU with "
+                         "--device-metrics / --device-alterations (musica_sim_cooccurrence)")
+    ap.add_argument("--texture-distances", type=lambda v: tuple(int(d) for d in v.split(",")), default=mp.COOCCURRENCE_DISTANCES, metavar="d0,d1,..",
+                    help="the distances of --texture: 1 .. 4 distinct ascending integers 1 .. 16 (default 1,2,4,8)")
     ap.add_argument("--blob-connectivity", type=int, default=8, choices=(4, 8), help="the neighbourhood of --blobs (default 8)")
     ap.add_argument("--order", action="store_true",
                     help="ask whether the local order of the gray levels survived: the census signs of every comparison over the 7 x 7 "
@@ -2107,11 +2136,13 @@ def main(argv=None):
                     **({"ensemble_batch": args.ensemble_batch} if args.ensemble else {}))
     shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
                  {"displacement": args.displacement} if args.displacement else {}
-    for m in COMPARISON_METRICS[1:]:   # --scales .. --spectrum, under their options' names (--tone and --symmetries are passed whatever they say)
+    for m in STUDY_METRICS[1:]:   # --scales .. --texture, under their options' names (--tone and --symmetries are passed whatever they say)
         if m.on(getattr(args, m.option)):
             shift_args[m.option] = getattr(args, m.option)
     if args.blobs is not None:
         shift_args["blob_connectivity"] = args.blob_connectivity
+    if args.texture is not None:
+        shift_args["texture_distances"] = args.texture_distances
     for m in MOVED[1:]:                # --blurs .. --codecs: the lists as given, a flag without a list as the entry's defaults for the size
         if getattr(args, m.option):
             shift_args[m.option] = m.cli(getattr(args, m.option), args.size) if m.cli else getattr(args, m.option)

@@ -2464,3 +2464,145 @@ def spectrum_row(stats, tile):
     if summary is None:
         return None
     return dict(summary, tile=int(tile), tiles=int(stats["tiles"]), table=np.asarray(stats["table"]).astype(np.int64).tolist())
+
+
+# ---- the texture of a comparison: gray-level co-occurrence matrices ------------------------------------------------------------------
+# Did the texture of the image survive? The second-order gray-level statistics of Haralick, Shanmugam and Dinstein (1973), the terms
+# in which radiomics reports the stability of features under processing. cooccurrence_statistics is the contract of
+# musica_sim_cooccurrence (include/musica.h), whose tables are bit-identical to it; cooccurrence_summary is what the study reports of
+# the integers, one function for every path.
+
+COOCCURRENCE_DIRECTIONS = (0, 45, 90, 135)   # degrees; the offset of direction i at distance d is cooccurrence_offsets(d)[i]
+
+
+def cooccurrence_offsets(d):
+    """The offsets (dx, dy) of the four directions at distance d: 0 (d, 0), 45 (d, d), 90 (0, d), 135 (-d, d); y runs down."""
+    return ((d, 0), (d, d), (0, d), (-d, d))
+
+
+def cooccurrence_statistics(a, b, regions, levels, distances):
+    """What musica_sim_cooccurrence returns for every region (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes (side a, side
+    b): a list of dicts. The level of a pixel v is v >> (8 - log2 G), G = levels in 8, 16, 32, 64 (processing.cooccurrence_levels);
+    distances: 1 .. 4 distinct ascending d in 1 .. 16 (processing.cooccurrence_distances). A pair (p, p + offset) counts on a side
+    where both pixels lie inside the region on that side, once, in T[level(p)][level(p + offset)]: nothing is symmetrised.
+    "table": the (D, 4, 2, G, G) uint32 array [distance][direction][side a = 0, b = 1] (a region has fewer than 2^32 pairs);
+    "pairs": the (D, 4) uint64 array (w - |dx|) (h - dy), 0 where the region is too small for the offset: its tables are then zero."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("cooccurrence_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    G, ds = mp.cooccurrence_levels(levels), mp.cooccurrence_distances(distances)
+    shift = 8 - (G.bit_length() - 1)
+    res = []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        sides = ((a[ay:ay + h, ax:ax + w] >> shift).astype(np.int64), (b[by:by + h, bx:bx + w] >> shift).astype(np.int64))
+        table = np.zeros((len(ds), 4, 2, G, G), dtype=np.uint32)
+        pairs = np.zeros((len(ds), 4), dtype=np.uint64)
+        for k, d in enumerate(ds):
+            for i, (dx, dy) in enumerate(cooccurrence_offsets(d)):
+                cols, rows = w - abs(dx), h - dy
+                if cols <= 0 or rows <= 0:
+                    continue
+                pairs[k, i] = cols * rows
+                x0 = max(0, -dx)   # the first pixels' first column
+                for s, lv in enumerate(sides):
+                    first, second = lv[:rows, x0:x0 + cols], lv[dy:dy + rows, x0 + dx:x0 + dx + cols]
+                    table[k, i, s] = np.bincount((first * G + second).ravel(), minlength=G * G).reshape(G, G)
+        res.append({"table": table, "pairs": pairs})
+    return res
+
+
+COOCCURRENCE_FEATURES = ("contrast", "dissimilarity", "homogeneity", "energy", "entropy", "correlation")   # cooccurrence_features' numbers
+
+
+def cooccurrence_features(C):
+    """Haralick's features of ONE symmetric G x G matrix C of non-negative integers with a positive sum N, P = C / N:
+        contrast sum (i - j)^2 P, dissimilarity sum |i - j| P, homogeneity sum P / (1 + (i - j)^2), energy sum P^2,
+        entropy -sum P log2 P (bits), correlation sum (i - mu)(j - mu) P / var, 1.0 where the side is flat (var = 0: skimage's convention).
+    The sums over |i - j| = k, sum C^2, sum i j C and the marginal's moments are exact integers and every sum of quotients is
+    math.fsum's correctly rounded one, so a value does not depend on the order of the cells: the negative and the transposed matrix
+    give the same bits."""
+    G = len(C)
+    C = [[int(v) for v in row] for row in C]
+    N = sum(map(sum, C))
+    by_k = [0] * G
+    squares = moment = 0
+    for i in range(G):
+        for j in range(G):
+            by_k[abs(i - j)] += C[i][j]
+            squares += C[i][j] * C[i][j]
+            moment += i * j * C[i][j]
+    s1 = sum(i * sum(C[i]) for i in range(G))
+    s2 = sum(i * i * sum(C[i]) for i in range(G))
+    var = N * s2 - s1 * s1
+    return {"contrast": sum(k * k * n for k, n in enumerate(by_k)) / N, "dissimilarity": sum(k * n for k, n in enumerate(by_k)) / N,
+            "homogeneity": math.fsum(n / (1 + k * k) for k, n in enumerate(by_k)) / N, "energy": squares / (N * N),
+            "entropy": math.fsum(c / N * math.log2(N / c) for row in C for c in row if c),
+            "correlation": (N * moment - s1 * s1) / var if var else 1.0}
+
+
+def _cooccurrence_divergence(Ca, Cb):
+    """The Jensen-Shannon divergence in bits of Pa = Ca / N and Pb = Cb / N (the two sides of a region have the same pairs, so one N):
+    (sum Ca log2(2 Ca / (Ca + Cb)) + sum Cb log2(2 Cb / (Ca + Cb))) / 2 N, exactly 0.0 where the matrices are equal."""
+    N = sum(int(v) for row in Ca for v in row)
+    terms = []
+    for ra, rb in zip(Ca, Cb):
+        for x, y in zip(ra, rb):
+            x, y = int(x), int(y)
+            if x != y:
+                terms.extend(c * math.log2(2 * c / (x + y)) for c in (x, y) if c)
+    return max(0.0, math.fsum(terms) / (2 * N))
+
+
+def cooccurrence_summary(table, pairs, levels, distances):
+    """What the study reports of a comparison's co-occurrence tables, from cooccurrence_statistics' (or musica_sim_cooccurrence's)
+    exact integers of ONE region: one function for every study path; None where no distance has a pair. Per side and distance the
+    symmetric, direction-summed matrix C = sum over the directions of (T + T^T), P = C / sum C. "distances"[k] is None where distance
+    k has no pair in any direction, else
+        "distance", "pairs"   d and the pairs of its four directions together
+        "a", "b"              cooccurrence_features of the side's C, and "anisotropy": (max - min) / mean of the contrast of
+                              T + T^T over the directions that have pairs, 0.0 where the mean is 0 (a flat side)
+        "difference"          a's feature minus b's, per feature, and of the anisotropy
+        "divergence"          the Jensen-Shannon divergence of P_a and P_b, in bits (0 .. 1)
+    "divergence": the largest over the distances."""
+    G, ds = mp.cooccurrence_levels(levels), mp.cooccurrence_distances(distances)
+    t, n = np.asarray(table), np.asarray(pairs)
+    if t.shape != (len(ds), 4, 2, G, G) or t.dtype.kind not in "iu" or n.shape != (len(ds), 4):
+        raise ValueError("the co-occurrence tables of %d levels and %d distances are (%d, 4, 2, %d, %d) integers with (%d, 4) pairs, got %r %s and %r"
+                         % (G, len(ds), len(ds), G, G, len(ds), t.shape, t.dtype, n.shape))
+    t = t.astype(np.int64)
+    out = []
+    for k, d in enumerate(ds):
+        have = [i for i in range(4) if int(n[k, i])]
+        if not have:
+            out.append(None)
+            continue
+        entry = {"distance": d, "pairs": sum(int(n[k, i]) for i in have)}
+        matrices = []
+        for s, side in enumerate("ab"):
+            sym = [t[k, i, s] + t[k, i, s].T for i in range(4)]
+            C = sum(sym[i] for i in have).tolist()
+            matrices.append(C)
+            entry[side] = cooccurrence_features(C)
+            contrasts = [cooccurrence_features(sym[i].tolist())["contrast"] for i in have]
+            mean = math.fsum(contrasts) / len(contrasts)
+            entry[side]["anisotropy"] = (max(contrasts) - min(contrasts)) / mean if mean else 0.0
+        entry["difference"] = {f: entry["a"][f] - entry["b"][f] for f in COOCCURRENCE_FEATURES + ("anisotropy",)}
+        entry["divergence"] = _cooccurrence_divergence(*matrices)
+        out.append(entry)
+    if all(e is None for e in out):
+        return None
+    return {"distances": out, "divergence": max(e["divergence"] for e in out if e is not None)}
+
+
+def texture_row(stats, levels, distances):
+    """A row's *_texture value from ONE dict of cooccurrence_statistics (or sim_cooccurrence): cooccurrence_summary's dict, "levels",
+    "distance_list" and "pairs", the (D, 4) exact counts as nested lists; None where no distance has a pair. The tables themselves, up to
+    131072 words a comparison, are not kept in the row."""
+    summary = cooccurrence_summary(stats["table"], stats["pairs"], levels, distances)
+    if summary is None:
+        return None
+    return dict(summary, levels=int(levels), distance_list=[int(d) for d in mp.cooccurrence_distances(distances)],
+                pairs=[[int(v) for v in row] for row in np.asarray(stats["pairs"])])

@@ -206,6 +206,12 @@ BLOB_CLASSES = 32           # MUSICA_BLOB_CLASSES
 SPECTRUM_MAX_TILE = 64      # MUSICA_SPECTRUM_MAX_TILE
 SPECTRUM_MAX_QUERIES = 4    # MUSICA_SPECTRUM_MAX_QUERIES
 SPECTRUM_TILES = (8, 16, 32, 64)
+COOCCURRENCE_MAX_DISTANCES = 4   # MUSICA_COOCCURRENCE_MAX_DISTANCES
+COOCCURRENCE_MAX_DISTANCE = 16   # MUSICA_COOCCURRENCE_MAX_DISTANCE
+COOCCURRENCE_MAX_LEVELS = 64     # MUSICA_COOCCURRENCE_MAX_LEVELS
+COOCCURRENCE_MAX_QUERIES = 4     # MUSICA_COOCCURRENCE_MAX_QUERIES
+COOCCURRENCE_LEVELS = (8, 16, 32, 64)
+COOCCURRENCE_DISTANCES = (1, 2, 4, 8)   # the study's default distance list
 
 
 def zoom_ratio(zoom):
@@ -267,6 +273,42 @@ def spectrum_tile(tile):
     if T not in SPECTRUM_TILES:
         raise ValueError("spectrum tile %d is not one of 8, 16, 32, 64" % T)
     return T
+
+
+def cooccurrence_levels(levels):
+    """The gray levels G of a co-occurrence table as metrics.cooccurrence_statistics and the library take them: one of 8, 16, 32, 64, an
+    integer, else ValueError."""
+    try:
+        if isinstance(levels, (bool, np.bool_, str)) or levels != int(levels):
+            raise TypeError
+        G = int(levels)
+    except (TypeError, ValueError):
+        raise ValueError("co-occurrence levels are one of 8, 16, 32, 64, got %r" % (levels,))
+    if G not in COOCCURRENCE_LEVELS:
+        raise ValueError("co-occurrence levels %d are not one of 8, 16, 32, 64" % G)
+    return G
+
+
+def cooccurrence_distances(distances):
+    """The distance list of a co-occurrence table as metrics.cooccurrence_statistics and the library take it: a tuple of 1 ..
+    COOCCURRENCE_MAX_DISTANCES distinct ascending integers, each 1 .. COOCCURRENCE_MAX_DISTANCE, else ValueError."""
+    try:
+        if isinstance(distances, (str, bytes)):
+            raise TypeError
+        given = list(distances)
+        if any(isinstance(d, (bool, np.bool_, str)) or d != int(d) for d in given):
+            raise TypeError
+        ds = tuple(int(d) for d in given)
+    except (TypeError, ValueError):
+        raise ValueError("co-occurrence distances are a list of integers, got %r" % (distances,))
+    if not 1 <= len(ds) <= COOCCURRENCE_MAX_DISTANCES:
+        raise ValueError("co-occurrence takes 1 .. %d distances, got %d" % (COOCCURRENCE_MAX_DISTANCES, len(ds)))
+    for d in ds:
+        if not 1 <= d <= COOCCURRENCE_MAX_DISTANCE:
+            raise ValueError("co-occurrence distance %d is not in 1 .. %d" % (d, COOCCURRENCE_MAX_DISTANCE))
+    if any(y <= x for x, y in zip(ds, ds[1:])):
+        raise ValueError("co-occurrence distances are distinct and ascending, got %r" % (ds,))
+    return ds
 
 
 def blob_threshold(threshold):
@@ -719,6 +761,11 @@ class SimSpectrumResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("tiles", C.c_uint64)]
 
 
+class SimCooccurrenceResult(C.Structure):
+    """musica_sim_cooccurrence_result: where a query's tables lie in `tables` and the pairs of every [distance][direction]."""
+    _fields_ = [("table_offset", C.c_uint64), ("pairs", (C.c_uint64 * 4) * COOCCURRENCE_MAX_DISTANCES)]
+
+
 class SimBlobsResult(C.Structure):
     """musica_sim_blobs_result: where a query's table and label plane lie, its counts and its largest component."""
     _fields_ = [("table_offset", C.c_uint64), ("label_offset", C.c_uint64), ("pixels", C.c_uint64), ("changed", C.c_uint64), ("components", C.c_uint64),
@@ -949,6 +996,7 @@ ABI = {
     "musica_sim_order": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimOrderResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_lattice": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimLatticeResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_spectrum": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimSpectrumResult), C.POINTER(C.c_int64), C.c_uint64]),
+    "musica_sim_cooccurrence": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimCooccurrenceResult), _U32P, C.c_uint64]),
     "musica_sim_blobs": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimBlobsResult), C.POINTER(C.c_uint64), C.c_uint64, _U32P, C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
@@ -1435,7 +1483,7 @@ class MusicaProcessing:
         return out
 
     def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False, trail=()):
-        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _reach share: the refusals of sim_<name> before any call
+        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _reach share: the refusals of sim_<name> before any call
         (most: 1 .. most queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead`
         in front of the count and `trail` (blobs: the label plane and its length) behind the tables' length. Returns the results and the
         flat tables, `words` zeroed words of `dtype`."""
@@ -1567,6 +1615,25 @@ class MusicaProcessing:
         for r in res:
             at = int(r.table_offset)
             out.append({"table": tables[at:at + per].reshape(T, T, len(SPECTRUM_FIELDS)).copy(), "tiles": int(r.tiles)})
+        return out
+
+    def sim_cooccurrence(self, queries, levels, distances):
+        """metrics.cooccurrence_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 1, 1 .. COOCCURRENCE_MAX_QUERIES of them, all in one launch; levels one of 8, 16, 32, 64
+        (cooccurrence_levels) and distances 1 .. 4 distinct ascending integers 1 .. 16 (cooccurrence_distances): ValueError before any
+        call, as for a count out of range. Returns one dict per query: "table", a (D, 4, 2, G, G) uint32 array
+        [distance][direction 0, 45, 90, 135][side a = 0, b = 1][level of the first pixel][level of the second], and "pairs", the
+        (D, 4) uint64 array of the pairs of every distance and direction."""
+        G, ds = cooccurrence_levels(levels), cooccurrence_distances(distances)
+        qs = _queries(queries)
+        per = len(ds) * 4 * 2 * G * G
+        res, tables = self._sim_tables("cooccurrence", qs, SimCooccurrenceResult, np.uint32, len(qs) * per, G, len(ds), (C.c_uint32 * len(ds))(*ds),
+                                       most=COOCCURRENCE_MAX_QUERIES)
+        out = []
+        for r in res:
+            at = int(r.table_offset)
+            out.append({"table": tables[at:at + per].reshape(len(ds), 4, 2, G, G).copy(),
+                        "pairs": np.array([[int(r.pairs[k][i]) for i in range(4)] for k in range(len(ds))], dtype=np.uint64)})
         return out
 
     def sim_reach(self, queries, radii):

@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import BLOB_KEYS, SPECTRUM_BAND_KEYS, SPECTRUM_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
+from .metrics import BLOB_KEYS, COOCCURRENCE_FEATURES, SPECTRUM_BAND_KEYS, SPECTRUM_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -53,6 +53,11 @@ BLOB_CSV_HEADER = ['raw file', 'alteration', 'comparison'] + [k.replace('_', ' '
 # spectrum_robustness.csv: one line per row, comparison the row has and radial band, ascending; the band's numbers, then the totals of
 # the comparison, the same on each of its lines
 SPECTRUM_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'tile', 'tiles', 'band'] + list(SPECTRUM_BAND_KEYS) + [k.replace('_', ' ') for k in SPECTRUM_KEYS]
+
+# texture_robustness.csv: one line per row, comparison the row has and distance that has a pair, ascending; the distance's numbers, then
+# the comparison's largest divergence, the same on each of its lines
+TEXTURE_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'levels', 'distance', 'pairs'] + \
+                     ['%s %s' % (f, what) for f in COOCCURRENCE_FEATURES + ('anisotropy',) for what in ('a', 'b', 'difference')] + ['divergence', 'largest divergence']
 
 ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
 ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
@@ -234,7 +239,14 @@ def _spectrum_lines(t):
     return [[t["tile"], t["tiles"], r] + [_blank(band[k]) for k in SPECTRUM_BAND_KEYS] + totals for r, band in enumerate(t["radial"])]
 
 
-# The files of the comparison metrics (harness.COMPARISON_METRICS), by key suffix: a study that has direct_<suffix> gets the file.
+def _texture_lines(t):
+    """A line per distance that has a pair: the levels, the distance, its pairs, every feature and the anisotropy of side a, of side b
+    and their difference, the distance's divergence, then the comparison's largest."""
+    return [[t["levels"], e["distance"], e["pairs"]] + [v for f in COOCCURRENCE_FEATURES + ("anisotropy",) for v in (e["a"][f], e["b"][f], e["difference"][f])] +
+            [e["divergence"], t["divergence"]] for e in t["distances"] if e is not None]
+
+
+# The files of the comparison metrics (harness.STUDY_METRICS), by key suffix: a study that has direct_<suffix> gets the file.
 # per "row": one line per row, header(with_reference), then cells(a group's value or None) for every group; per "comparison": one line
 # per row and comparison that the row has, the header as it stands, then cells(the value); per "band": the same with a line for each
 # entry of cells(the value).
@@ -247,6 +259,7 @@ METRIC_CSVS = {
     "lattice": MetricCsv("lattice_robustness.csv", "comparison", LATTICE_CSV_HEADER, _lattice_cells),
     "blobs": MetricCsv("blob_robustness.csv", "comparison", BLOB_CSV_HEADER, _blob_cells),
     "spectrum": MetricCsv("spectrum_robustness.csv", "band", SPECTRUM_CSV_HEADER, _spectrum_lines),
+    "texture": MetricCsv("texture_robustness.csv", "band", TEXTURE_CSV_HEADER, _texture_lines),
 }
 
 
@@ -315,6 +328,12 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     row, the unaltered one included, comparison that the row has (none where its region holds no whole tile) and radial band 0 .. log2 T:
     the comparison's name, T, the tiles, the band, its gain, coherence and error share, then spectrum_summary's totals of the
     comparison, the same on each of its lines.
+
+    Studies run with texture=G (rows[0] has "direct_texture") also get texture_robustness.csv (TEXTURE_CSV_HEADER): one line per row,
+    the unaltered one included, comparison that the row has (none where its region has no pair) and distance that has a pair: the
+    comparison's name, G, the distance, its pairs, contrast, dissimilarity, homogeneity, energy, entropy, correlation and anisotropy
+    of side a, of side b and their difference, the distance's Jensen-Shannon divergence, then the comparison's largest divergence, the
+    same on each of its lines.
 
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
