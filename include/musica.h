@@ -1254,6 +1254,45 @@ typedef struct musica_sim_cooccurrence_result {
 int musica_sim_cooccurrence(musica_ctx* ctx, uint32_t levels, uint32_t distance_count, const uint32_t* distances, uint32_t count,
                             const musica_sim_query* queries, musica_sim_cooccurrence_result* results, uint32_t* tables, uint64_t table_words);
 
+/* ---- size: the granulometry of a comparison (new, not in the reference) ----
+ * Which object sizes became brighter or darker, and by how much? The granulometry of mathematical morphology (Matheron 1975; the
+ * pattern spectrum of Maragos 1989): the openings and closings of an image by a growing element sieve its bright and its dark
+ * structures by size, without inserting anything. metrics.granulometry_statistics is the contract. Queries are musica_sim_compare's
+ * with w, h >= 1, at most MUSICA_GRANULOMETRY_MAX_QUERIES (a row's direct, registered and two vendor comparisons). Side a is the
+ * graded plane of the query's image quantised as musica_sim_compare quantises it, side b the query's reference slot. The region is its
+ * own domain: for r >= 1 the element of a pixel p is the (2 r + 1)^2 square around p CLIPPED to the region; the erosion is the minimum
+ * over it, the dilation the maximum, the opening g_r the dilation of the erosion, the closing f_r the erosion of the dilation,
+ * g_0 = f_0 = identity (scipy's minimum_filter with mode="constant", cval=255 and maximum_filter with cval=0 on the region's
+ * sub-array). Nothing outside the region is read. So an interior bright square of side s survives g_r iff 2 r + 1 <= s, but a square
+ * flush in the region's corner meets the clipped element and survives iff r + 1 <= s: a 3 x 3 square in the corner survives r = 2, one
+ * in the interior is gone at r = 2. `radii` holds radius_count = 1 .. MUSICA_GRANULOMETRY_MAX_RADII distinct ascending
+ * r_1 < .. < r_K, each 1 .. MUSICA_GRANULOMETRY_MAX_RADIUS, r_0 = 0. Query i gets (K + 1) * 2 * MUSICA_GRANULOMETRY_WORDS uint64_t in
+ * the flat `tables`, from results[i].table_offset (in words) on, indexed [class][polarity bright = 0, dark = 1][word]. Class k < K:
+ * bright A = g_{r_k}(a) - g_{r_k+1}(a), the bright structure that passes the sieve r_k and not r_k+1; dark
+ * A = f_{r_k+1}(a) - f_{r_k}(a); class K, the residue: bright A = g_{r_K}(a), dark A = 255 - f_{r_K}(a); B likewise from b. Words:
+ * sum A, sum B, sum A^2, sum B^2, sum A B over the region's pixels. Every A, B is 0 .. 255 and a side is at most 16364, so a word
+ * stays below 2^45. results[i].pixels = w * h. Identities: the bright sums of A over the classes add up to sum a, the dark ones to
+ * sum (255 - a) (B: b); complementing both sides swaps the polarities; swapping the sides swaps words 0 <-> 1 and 2 <-> 3; the table
+ * is unchanged by the square's eight symmetries applied to both sides of the region; the sums of A and B of a coarser radii list are
+ * the sums over the finer list's classes that a class spans. Everything is an integer: the tables equal the restatement word for word
+ * and repeat from call to call, whatever MUSICA_GRANULOMETRY_GROUPS (the workgroups of a query's polarity, read at every call;
+ * 0: the launch's own choice) says. Every word of the tables is written and nothing behind them. Synchronous, on the context's stream
+ * after whatever was enqueued there; changes no slot, no result of a step and no input image; scratch is allocated on first use.
+ * Refused before any device work: what musica_sim_compare refuses (with the smallest side 1 and at most
+ * MUSICA_GRANULOMETRY_MAX_QUERIES queries, none included), then a NULL `radii`, a radius_count outside 1 ..
+ * MUSICA_GRANULOMETRY_MAX_RADII, a radius out of range, a radius not above the one before it, a NULL `tables` and table_words below
+ * the tables' words. After a refusal the context stays usable. */
+#define MUSICA_GRANULOMETRY_MAX_RADII 8
+#define MUSICA_GRANULOMETRY_MAX_RADIUS 16
+#define MUSICA_GRANULOMETRY_MAX_QUERIES 4
+#define MUSICA_GRANULOMETRY_WORDS 5
+typedef struct musica_sim_granulometry_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t pixels;                /* w * h */
+} musica_sim_granulometry_result;
+int musica_sim_granulometry(musica_ctx* ctx, uint32_t radius_count, const uint32_t* radii, uint32_t count, const musica_sim_query* queries,
+                            musica_sim_granulometry_result* results, uint64_t* tables, uint64_t table_words);
+
 /* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
  * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change
  * outwards: the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global

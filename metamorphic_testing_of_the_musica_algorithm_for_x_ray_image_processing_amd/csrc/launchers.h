@@ -577,6 +577,32 @@ inline int cooccurrence_groups(int tiles, int most = 0) {
 // metrics.cooccurrence_statistics over `count` queries at `levels` gray levels (grid.x = max_groups, the largest `groups`, at least 1;
 // grid.y = 2 * dist.count). tables: every query's words, zeroed by the caller: the workgroups add into them with u32 atomics
 void launch_sim_cooccurrence(hipStream_t st, const CooccurrenceQueryDev* d_qs, int count, int max_groups, int levels, const CooccurrenceDistances& dist, uint32_t* tables);
+// kernels_granulometry.hip: the size metric. One comparison of musica_sim_granulometry: tiles_x / tiles_y: its region's 64 x 64 tiles;
+// groups: the persistent workgroups that share the tiles of ONE polarity (granulometry_groups); table: where its
+// (radius_count + 1) * 2 * kGranulometryWords words start in the launch's flat tables, in words.
+constexpr int kGranulometryMaxRadii = 8;      // MUSICA_GRANULOMETRY_MAX_RADII
+constexpr int kGranulometryMaxRadius = 16;    // MUSICA_GRANULOMETRY_MAX_RADIUS
+constexpr int kGranulometryMaxQueries = 4;    // MUSICA_GRANULOMETRY_MAX_QUERIES
+constexpr int kGranulometryWords = 5;         // MUSICA_GRANULOMETRY_WORDS
+struct GranulometryQueryDev : SimRegion {
+    int tiles_x, tiles_y, groups;
+    unsigned long long table;
+};
+struct GranulometryRadii {
+    int count;
+    int r[kGranulometryMaxRadii];
+};
+// The workgroups that one polarity of a query of `tiles` tiles gets: min(tiles, want), where want is kGranulometryGroups, or `most`
+// where 0 < most < want (the tuning variable MUSICA_GRANULOMETRY_GROUPS, read at every call): the tables do not depend on it, a
+// workgroup's u64 table holds any number of tiles. A launch has twice as many workgroups a query; two fit a compute unit (LDS).
+constexpr int kGranulometryGroups = 256;
+inline int granulometry_groups(int tiles, int most = 0) {
+    const int want = most > 0 && most < kGranulometryGroups ? most : kGranulometryGroups;
+    return tiles < want ? tiles : want;
+}
+// metrics.granulometry_statistics over `count` queries (grid.x = max_groups, the largest `groups`, at least 1; grid.y = the two
+// polarities). tables: every query's words, zeroed by the caller: the workgroups add into them with u64 atomics
+void launch_sim_granulometry(hipStream_t st, const GranulometryQueryDev* d_qs, int count, int max_groups, const GranulometryRadii& radii, unsigned long long* tables);
 // kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
 // Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
 constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII

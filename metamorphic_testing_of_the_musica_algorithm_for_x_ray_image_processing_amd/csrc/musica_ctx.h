@@ -197,6 +197,9 @@ struct StudyState {
     // musica_sim_cooccurrence: the queries and the flat tables
     CooccurrenceQueryDev* d_cooccurrence_q = nullptr;   // [MUSICA_COOCCURRENCE_MAX_QUERIES]
     uint32_t* d_cooccurrence_tables = nullptr;          // [MUSICA_COOCCURRENCE_MAX_QUERIES][MAX_DISTANCES][4][2][MAX_LEVELS^2], allocated by the first musica_sim_cooccurrence
+    // musica_sim_granulometry: the queries and the flat tables
+    GranulometryQueryDev* d_granulometry_q = nullptr;         // [MUSICA_GRANULOMETRY_MAX_QUERIES]
+    unsigned long long* d_granulometry_tables = nullptr;      // [MUSICA_GRANULOMETRY_MAX_QUERIES][MAX_RADII + 1][2][MUSICA_GRANULOMETRY_WORDS], allocated by the first musica_sim_granulometry
     // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
     // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
     uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either

@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_codec.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip, kernels_granulometry.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
 // sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
@@ -413,7 +413,7 @@ static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion
     d.h = (int)q.h;
 }
 
-// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _reach) -----------------------------------------------
+// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _reach) -----------------------------------------------
 // Where a table call keeps its queries and its flat tables in musica_ctx::study, and what it takes: at most `most` queries with sides
 // of at least `min_side`. The tables' buffer holds `tables_cap` words from the first call on; where `grown` names its capacity it
 // holds the words of the largest call so far instead.
@@ -433,6 +433,7 @@ constexpr TableBuffers<LatticeQueryDev, unsigned long long> kLatticeBuffers{&Stu
 constexpr TableBuffers<BlobQueryDev, unsigned long long> kBlobBuffers{&StudyState::d_blob_q, &StudyState::d_blob_tables, MUSICA_BLOBS_MAX_QUERIES, 1, (size_t)MUSICA_BLOBS_MAX_QUERIES * kBlobClasses * kBlobWords};
 constexpr TableBuffers<SpectrumQueryDev, unsigned long long> kSpectrumBuffers{&StudyState::d_spectrum_q, &StudyState::d_spectrum_tables, MUSICA_SPECTRUM_MAX_QUERIES, 1, (size_t)MUSICA_SPECTRUM_MAX_QUERIES * kSpectrumMaxTile * kSpectrumMaxTile * kSpectrumWords};
 constexpr TableBuffers<CooccurrenceQueryDev, uint32_t> kCooccurrenceBuffers{&StudyState::d_cooccurrence_q, &StudyState::d_cooccurrence_tables, MUSICA_COOCCURRENCE_MAX_QUERIES, 1, (size_t)MUSICA_COOCCURRENCE_MAX_QUERIES * MUSICA_COOCCURRENCE_MAX_DISTANCES * 4 * 2 * kCooccurrenceMaxLevels * kCooccurrenceMaxLevels};
+constexpr TableBuffers<GranulometryQueryDev, unsigned long long> kGranulometryBuffers{&StudyState::d_granulometry_q, &StudyState::d_granulometry_tables, MUSICA_GRANULOMETRY_MAX_QUERIES, 1, (size_t)MUSICA_GRANULOMETRY_MAX_QUERIES * (MUSICA_GRANULOMETRY_MAX_RADII + 1) * 2 * kGranulometryWords};
 constexpr TableBuffers<ReachQueryDev, unsigned long long> kReachBuffers{&StudyState::d_reach_q, &StudyState::d_reach_tables, MUSICA_REACH_MAX_QUERIES, 1, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords};
 
 // What a call's place() says of one query: its tiles or chunks (the launch's grid.x is the largest) and the words of its table.
@@ -1410,6 +1411,43 @@ int musica_sim_cooccurrence(musica_ctx* c, uint32_t levels, uint32_t distance_co
             }
         });
     ABI_CATCH("musica_sim_cooccurrence")
+}
+
+// ---- the granulometry of a comparison (musica_sim_granulometry, include/musica.h; kernels_granulometry.hip) -----------------------------
+static_assert(kGranulometryMaxRadii == MUSICA_GRANULOMETRY_MAX_RADII && kGranulometryMaxRadius == MUSICA_GRANULOMETRY_MAX_RADIUS &&
+                  kGranulometryMaxQueries == MUSICA_GRANULOMETRY_MAX_QUERIES && kGranulometryWords == MUSICA_GRANULOMETRY_WORDS,
+              "kernels_granulometry.hip's constants are include/musica.h's");
+
+int musica_sim_granulometry(musica_ctx* c, uint32_t radius_count, const uint32_t* radii, uint32_t count, const musica_sim_query* qs,
+                            musica_sim_granulometry_result* out, uint64_t* tables, uint64_t table_words) {
+    ABI_TRY
+    GranulometryRadii list{};
+    return sim_query_tables(
+        c, "musica_sim_granulometry", kGranulometryBuffers, count, qs, out, tables, table_words,
+        [&] {
+            if (!radii) return fail("musica_sim_granulometry: radii is NULL");
+            if (radius_count == 0 || radius_count > MUSICA_GRANULOMETRY_MAX_RADII)
+                return fail("musica_sim_granulometry: radius_count %u out of range [1, %d]", radius_count, MUSICA_GRANULOMETRY_MAX_RADII);
+            for (uint32_t k = 0; k < radius_count; k++)
+                if (radii[k] < 1 || radii[k] > MUSICA_GRANULOMETRY_MAX_RADIUS)
+                    return fail("musica_sim_granulometry: radius %u: %u is not in 1 .. %d", k, radii[k], MUSICA_GRANULOMETRY_MAX_RADIUS);
+            for (uint32_t k = 1; k < radius_count; k++)
+                if (radii[k] <= radii[k - 1])
+                    return fail("musica_sim_granulometry: radius %u: %u is not above radius %u: %u", k, radii[k], k - 1, radii[k - 1]);
+            for (uint32_t k = 0; k < radius_count; k++) list.r[k] = (int)radii[k];
+            list.count = (int)radius_count;
+            return 1;
+        },
+        [&](const musica_sim_query& q, GranulometryQueryDev& d) {
+            d.groups = granulometry_groups(tile_grid(d, q.w, q.h), env_int("MUSICA_GRANULOMETRY_GROUPS", 0));
+            return TablePlace{d.groups, ((size_t)radius_count + 1) * 2 * kGranulometryWords};
+        },
+        nothing,
+        [&](const GranulometryQueryDev* d_qs, int max_groups, unsigned long long* d_tables) {
+            launch_sim_granulometry(c->stream, d_qs, (int)count, max_groups, list, d_tables);
+        },
+        nothing, [&](uint32_t i, const musica_sim_query& q, const uint64_t*) { out[i].pixels = (uint64_t)q.w * q.h; });
+    ABI_CATCH("musica_sim_granulometry")
 }
 
 // ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------

@@ -1081,6 +1081,14 @@ STUDY_METRICS = COMPARISON_METRICS + (
                      lambda proc, queries, opt: [texture_row(r, opt.texture, opt.texture_distances) for r in proc.sim_cooccurrence(queries, opt.texture, opt.texture_distances)],
                      METRIC_CSVS["texture"]),
 )
+# STUDY_METRICS is the eight entries above and ends with the texture: tests/test_cooccurrence_restatement.py holds it to that. The
+# study, its checks, its key groups, the command line and the report walk ROW_METRICS, to which the next metric is appended.
+ROW_METRICS = STUDY_METRICS + (
+    ComparisonMetric("granulometry", "granulometry", lambda v: v is not None, lambda v: None if v is None else mp.granulometry_radii(v),
+                     lambda opt, out, plane, region: granulometry_row(granulometry_statistics(out, plane, [region], opt.granulometry)[0], opt.granulometry),
+                     lambda proc, queries, opt: [granulometry_row(r, opt.granulometry) for r in proc.sim_granulometry(queries, opt.granulometry)],
+                     METRIC_CSVS["granulometry"]),
+)
 TONE_KEYS, SCALE_ROW_KEYS, GRADIENT_ROW_KEYS, ORDER_ROW_KEYS, LATTICE_ROW_KEYS, BLOB_ROW_KEYS = \
     ({c: "%s_%s" % (c, m.suffix) for c in COMPARED} for m in COMPARISON_METRICS[:6])   # comparison -> its sibling key, of the metrics that tests ask by name
 # The order of the refusals and of a row's keys is history, not the scoring order. These metrics are checked before the moved rows'
@@ -1154,7 +1162,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
                   gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, codecs=None,
-                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, order=False):
+                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1167,7 +1175,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     o["displacement"] = displacement = int(displacement)
     if displacement and not 1 <= displacement <= mp.SIM_MAX_RADIUS:
         raise ValueError("displacement radius %d is not in 1 .. %d" % (displacement, mp.SIM_MAX_RADIUS))
-    for m in STUDY_METRICS:
+    for m in ROW_METRICS:
         if m.option in CHECKED_EARLY:
             o[m.option] = m.check(o[m.option])
     o["observer"] = _checked_flag("observer")(observer)
@@ -1187,7 +1195,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         raise ValueError("covariance is taken over the realisations of an ensemble: give ensemble > 0")
     for m in MOVED:
         o[m.option] = m.check(o[m.option] or (), n)
-    for m in STUDY_METRICS:
+    for m in ROW_METRICS:
         if m.option not in CHECKED_EARLY:
             o[m.option] = m.check(o[m.option])
     if blob_connectivity not in (4, 8) or isinstance(blob_connectivity, (bool, np.bool_)):
@@ -1200,12 +1208,12 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     for g in (o["details"] if observer else ()):   # the views and banks of every grid, as the measurement will take them
         mp.view_list(*observer_views(output_details(g)), n - 2 * PROCESSING_MARGIN)
     compared = COMPARED[:2 if vendor is None else 4]
-    groups = {m.suffix: tuple("%s_%s" % (c, m.suffix) for c in compared) if m.on(o[m.option]) else () for m in STUDY_METRICS}
+    groups = {m.suffix: tuple("%s_%s" % (c, m.suffix) for c in compared) if m.on(o[m.option]) else () for m in ROW_METRICS}
     groups.update(shift=("direct_shift", "registered_shift") if displacement else (), reach=("direct_reach",) if o["reach"] is not None else (),
                   ensemble=("ensemble",) if ensemble else (), relations=tuple(rel.key for rel in RELATIONS if o[rel.option] is not None),
                   observer=("observer",) if observer else (), warp=("warp",) if o["warps"] else ())
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + \
-           tuple(k for g in KEY_GROUPS + tuple(m.suffix for m in STUDY_METRICS if m.suffix not in KEY_GROUPS) for k in groups[g])
+           tuple(k for g in KEY_GROUPS + tuple(m.suffix for m in ROW_METRICS if m.suffix not in KEY_GROUPS) for k in groups[g])
     for grid, default in (("shutters", scaled(SHUTTERS, n)), ("translations", scaled(TRANSLATIONS, n)), ("rotations", ROTATIONS),
                           ("sigmas", GAUSS_SIGMAS), ("factors", POISSON_FACTORS)):
         if o[grid] is None:
@@ -1269,7 +1277,7 @@ class Scorer:
     SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key and
     observer(details) a cd_ row's "observer". similarities, score and shifts take the row's comparisons, (reference key, region) pairs
     with a SLOT_* number as the key, and return one result each: similarities the five SIM_METRICS, score(metric, comparisons) the
-    sibling values of one entry of STUDY_METRICS, by the entry's host or device form, and shifts the displacement (the regions
+    sibling values of one entry of ROW_METRICS, by the entry's host or device form, and shifts the displacement (the regions
     already inset; keep: the dicts carry their tile tables whatever displacement_tiles says, for a warp row's tracking). reach takes
     the row's direct comparison, behind similarities, and looks at the change of the input from `source`, the study's raw plane."""
 
@@ -1457,7 +1465,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, order=False):
+              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1746,7 +1754,18 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     distance without a pair) and the largest "divergence", "levels", "distance_list" and the exact "pairs". On the device one
     musica_sim_cooccurrence call behind the spectrum's; on the host the restatement counts the same crops. The tables are integers
     and there is one summary function: the values are equal to the last bit on every path. With texture=None the rows and the launches
-    are exactly as before."""
+    are exactly as before.
+
+    granulometry: a radii list, 1 .. 8 distinct ascending integers 1 .. 16 (processing.granulometry_radii; None: off), asks which object
+    sizes became brighter or darker: the openings and closings of both sides of every comparison by the growing (2 r + 1)^2 square,
+    clipped to the region (granulometry_statistics). Every comparison dict of a row gains a sibling behind all other keys, the
+    texture's included: direct_granulometry, registered_granulometry and, with a vendor image, reference_granulometry and
+    registered_reference_granulometry; present exactly where the original is, None where it is None. Each is granulometry_row's dict:
+    granulometry_summary's "bright" and "dark" (per class the pattern-spectrum shares of either side, gain, coherence and mse; the mean
+    element sides and their shift, the slope of log gain on log side, the residue's shift), "radii", "pixels" and the exact "table". On
+    the device one musica_sim_granulometry call behind the texture's; on the host the restatement sieves the same crops. The tables
+    are integers and there is one summary function: the values are equal to the last bit on every path. With granulometry=None the
+    rows and the launches are exactly as before."""
     options = {k: v for k, v in locals().items() if k not in ("raw", "runner", "rng")}   # every option by its name, as study_options takes them
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, **options)
@@ -1755,12 +1774,12 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     full = (0, 0, 0, 0, shape[1], shape[0])
     scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
     scorer.source = raw   # what reach() takes the input's change against
-    metrics = [("", scorer.similarities)] + [("_" + m.suffix, functools.partial(scorer.score, m)) for m in STUDY_METRICS if m.on(getattr(opt, m.option))]
+    metrics = [("", scorer.similarities)] + [("_" + m.suffix, functools.partial(scorer.score, m)) for m in ROW_METRICS if m.on(getattr(opt, m.option))]
     rows = []
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, texture, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, texture, granulometry, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -1922,6 +1941,15 @@ def warp_list(text):
                        refused="expected a comma-separated list of warps out of %s, got %r" % (",".join(known), text))
 
 
+def granulometry_list(text):
+    """--granulometry r1,r2,...: radii 1 .. 16, distinct and ascending (processing.granulometry_radii)."""
+    import argparse
+    try:
+        return mp.granulometry_radii([int(t) for t in text.split(",")])
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def reach_list(text):
     """--reach R0,R1,...: radii from 0, strictly ascending (processing.reach_radii)."""
     import argparse
@@ -2054,6 +2082,12 @@ def main(argv=None):
                          "--device-metrics / --device-alterations (musica_sim_cooccurrence)")
     ap.add_argument("--texture-distances", type=lambda v: tuple(int(d) for d in v.split(",")), default=mp.COOCCURRENCE_DISTANCES, metavar="d0,d1,..",
                     help="the distances of --texture: 1 .. 4 distinct ascending integers 1 .. 16 (default 1,2,4,8)")
+    ap.add_argument("--granulometry", nargs="?", const=mp.GRANULOMETRY_RADII, default=None, type=granulometry_list, metavar="r1,r2,..",
+                    help="add the sizes of every comparison: the granulometry of both sides, openings and closings by the growing (2 r + 1)^2 "
+                         "square at 1 .. 8 distinct ascending radii 1 .. 16 (without a list 1,2,4,8,16): per polarity and size class the "
+                         "pattern-spectrum shares, gain, coherence and mse, the mean element side and the slope of log gain on log side, "
+                         "written to granulometry_robustness.csv; on the GPU with --device-metrics / --device-alterations "
+                         "(musica_sim_granulometry)")
     ap.add_argument("--blob-connectivity", type=int, default=8, choices=(4, 8), help="the neighbourhood of --blobs (default 8)")
     ap.add_argument("--order", action="store_true",
                     help="ask whether the local order of the gray levels survived: the census signs of every comparison over the 7 x 7 "
@@ -2136,7 +2170,7 @@ def main(argv=None):
                     **({"ensemble_batch": args.ensemble_batch} if args.ensemble else {}))
     shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
                  {"displacement": args.displacement} if args.displacement else {}
-    for m in STUDY_METRICS[1:]:   # --scales .. --texture, under their options' names (--tone and --symmetries are passed whatever they say)
+    for m in ROW_METRICS[1:]:   # --scales .. --granulometry, under their options' names (--tone and --symmetries are passed whatever they say)
         if m.on(getattr(args, m.option)):
             shift_args[m.option] = getattr(args, m.option)
     if args.blobs is not None:

@@ -2606,3 +2606,113 @@ def texture_row(stats, levels, distances):
         return None
     return dict(summary, levels=int(levels), distance_list=[int(d) for d in mp.cooccurrence_distances(distances)],
                 pairs=[[int(v) for v in row] for row in np.asarray(stats["pairs"])])
+
+
+# ---- the sizes of a comparison: the granulometry -----------------------------------------------------------------------------------------
+# Which object sizes became brighter or darker, and by how much? The granulometry of mathematical morphology (Matheron 1975; the pattern
+# spectrum of Maragos 1989): openings and closings by a growing square sieve the bright and the dark structures by size.
+# granulometry_statistics is the contract of musica_sim_granulometry (include/musica.h), whose tables are bit-identical to it;
+# granulometry_summary is what the study reports of the integers, one function for every path.
+
+GRANULOMETRY_POLARITIES = ("bright", "dark")
+GRANULOMETRY_FIELDS = ("sum_a", "sum_b", "sum_aa", "sum_bb", "sum_ab")   # a table's words
+GRANULOMETRY_CLASS_KEYS = ("share_a", "share_b", "gain", "coherence", "mse")
+GRANULOMETRY_KEYS = ("mean_side_a", "mean_side_b", "mean_side_shift", "slope", "residue_shift")
+
+
+def granulometry_opening(f, r):
+    """The opening of a 2-D uint8 plane by the (2 r + 1)^2 square clipped to the plane (the plane is its own domain): the erosion is the
+    minimum over the clipped square (cval=255), the dilation the maximum (cval=0); r = 0 is the identity."""
+    if r == 0:
+        return f
+    eroded = ndimage.minimum_filter(f, size=2 * r + 1, mode="constant", cval=255)
+    return ndimage.maximum_filter(eroded, size=2 * r + 1, mode="constant", cval=0)
+
+
+def granulometry_closing(f, r):
+    """The closing by the same element: the erosion of the dilation; 255 - closing(f) = opening(255 - f)."""
+    if r == 0:
+        return f
+    dilated = ndimage.maximum_filter(f, size=2 * r + 1, mode="constant", cval=0)
+    return ndimage.minimum_filter(dilated, size=2 * r + 1, mode="constant", cval=255)
+
+
+def granulometry_statistics(a, b, regions, radii):
+    """What musica_sim_granulometry returns for every region (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes (side a, side
+    b): a list of dicts. radii: K = 1 .. 8 distinct ascending r_1 < .. < r_K in 1 .. 16 (processing.granulometry_radii), r_0 = 0. The
+    region's sub-array is its own domain: nothing outside it is read. "table": the (K + 1, 2, 5) uint64 array
+    [class][polarity bright = 0, dark = 1][sum A, sum B, sum A^2, sum B^2, sum A B] over the region's pixels, where for class k < K
+    A = opening_{r_k}(a) - opening_{r_k+1}(a) (bright) or closing_{r_k+1}(a) - closing_{r_k}(a) (dark) and for the residue, class K,
+    A = opening_{r_K}(a) or 255 - closing_{r_K}(a); B likewise from b. "pixels": w * h."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("granulometry_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    rs = (0,) + mp.granulometry_radii(radii)
+    K = len(rs) - 1
+    res = []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        sides = (np.ascontiguousarray(a[ay:ay + h, ax:ax + w]), np.ascontiguousarray(b[by:by + h, bx:bx + w]))
+        table = np.zeros((K + 1, 2, len(GRANULOMETRY_FIELDS)), dtype=np.uint64)
+        for p, sieve in enumerate((granulometry_opening, granulometry_closing)):
+            planes = [[sieve(f, r).astype(np.int64) for r in rs] for f in sides]
+            for k in range(K + 1):
+                if k < K:
+                    A, B = ((g[k] - g[k + 1]) if p == 0 else (g[k + 1] - g[k]) for g in planes)
+                else:
+                    A, B = (g[K] if p == 0 else 255 - g[K] for g in planes)
+                table[k, p] = [int(A.sum()), int(B.sum()), int((A * A).sum()), int((B * B).sum()), int((A * B).sum())]
+        res.append({"table": table, "pixels": w * h})
+    return res
+
+
+def granulometry_summary(table, radii, pixels):
+    """What the study reports of a comparison's granulometry, in f64 from granulometry_statistics' (or musica_sim_granulometry's) exact
+    integers of ONE region only: one function for every study path. A dict with "bright" and "dark", each
+        "classes"          per class k < K a dict: "radius" r_k+1 and "side" 2 r_k+1 + 1, the element that removes the class;
+                           "share_a", "share_b": the pattern spectrum, sum A / the sum of sum A over the classes k < K (None where that is 0);
+                           "gain" sum A B / sum B^2 (None where sum B^2 is 0); "coherence" sum A B / sqrt(sum A^2 sum B^2) (None where
+                           either is 0); "mse" (sum A^2 + sum B^2 - 2 sum A B) / pixels, the band's mean squared difference
+        "mean_side_a", "mean_side_b"   the share-weighted mean element side (None without shares), "mean_side_shift" a's minus b's
+        "slope"            the least-squares slope of log gain on log side over the classes that have a positive gain, None with fewer
+                           than two: negative where small structures gain more
+        "residue_shift"    (sum A - sum B) / pixels of the residue class."""
+    rs = mp.granulometry_radii(radii)
+    K = len(rs)
+    t = np.asarray(table)
+    if t.shape != (K + 1, 2, len(GRANULOMETRY_FIELDS)) or t.dtype.kind not in "iu":
+        raise ValueError("the granulometry table of %d radii is (%d, 2, %d) integers, got %r %s" % (K, K + 1, len(GRANULOMETRY_FIELDS), t.shape, t.dtype))
+    pixels = int(pixels)
+    if pixels < 1:
+        raise ValueError("a granulometry has at least one pixel, got %d" % pixels)
+    out = {}
+    for p, polarity in enumerate(GRANULOMETRY_POLARITIES):
+        words = [[int(v) for v in t[k, p]] for k in range(K + 1)]
+        total_a, total_b = sum(w[0] for w in words[:K]), sum(w[1] for w in words[:K])
+        classes = []
+        for k in range(K):
+            sa, sb, saa, sbb, sab = words[k]
+            classes.append({"radius": rs[k], "side": 2 * rs[k] + 1,
+                            "share_a": sa / total_a if total_a else None, "share_b": sb / total_b if total_b else None,
+                            "gain": sab / sbb if sbb else None, "coherence": sab / math.sqrt(saa * sbb) if saa and sbb else None,
+                            "mse": (saa + sbb - 2 * sab) / pixels})
+        mean_a = math.fsum(c["side"] * c["share_a"] for c in classes) if total_a else None
+        mean_b = math.fsum(c["side"] * c["share_b"] for c in classes) if total_b else None
+        points = [(math.log(c["side"]), math.log(c["gain"])) for c in classes if c["gain"] is not None and c["gain"] > 0]
+        slope = None
+        if len(points) >= 2:
+            mx, my = math.fsum(x for x, _ in points) / len(points), math.fsum(y for _, y in points) / len(points)
+            slope = math.fsum((x - mx) * (y - my) for x, y in points) / math.fsum((x - mx) * (x - mx) for x, _ in points)
+        out[polarity] = {"classes": classes, "mean_side_a": mean_a, "mean_side_b": mean_b,
+                         "mean_side_shift": mean_a - mean_b if mean_a is not None and mean_b is not None else None, "slope": slope,
+                         "residue_shift": (words[K][0] - words[K][1]) / pixels}
+    return out
+
+
+def granulometry_row(stats, radii):
+    """A row's *_granulometry value from ONE dict of granulometry_statistics (or sim_granulometry): granulometry_summary's dict, "radii",
+    "pixels" and the exact "table" as nested lists."""
+    return dict(granulometry_summary(stats["table"], radii, stats["pixels"]), radii=[int(r) for r in mp.granulometry_radii(radii)],
+                pixels=int(stats["pixels"]), table=np.asarray(stats["table"]).astype(np.uint64).tolist())

@@ -212,6 +212,11 @@ COOCCURRENCE_MAX_LEVELS = 64     # MUSICA_COOCCURRENCE_MAX_LEVELS
 COOCCURRENCE_MAX_QUERIES = 4     # MUSICA_COOCCURRENCE_MAX_QUERIES
 COOCCURRENCE_LEVELS = (8, 16, 32, 64)
 COOCCURRENCE_DISTANCES = (1, 2, 4, 8)   # the study's default distance list
+GRANULOMETRY_MAX_RADII = 8       # MUSICA_GRANULOMETRY_MAX_RADII
+GRANULOMETRY_MAX_RADIUS = 16     # MUSICA_GRANULOMETRY_MAX_RADIUS
+GRANULOMETRY_MAX_QUERIES = 4     # MUSICA_GRANULOMETRY_MAX_QUERIES
+GRANULOMETRY_WORDS = 5           # MUSICA_GRANULOMETRY_WORDS
+GRANULOMETRY_RADII = (1, 2, 4, 8, 16)   # the study's default radii list
 
 
 def zoom_ratio(zoom):
@@ -309,6 +314,28 @@ def cooccurrence_distances(distances):
     if any(y <= x for x, y in zip(ds, ds[1:])):
         raise ValueError("co-occurrence distances are distinct and ascending, got %r" % (ds,))
     return ds
+
+
+def granulometry_radii(radii):
+    """The radii list of a granulometry as metrics.granulometry_statistics and the library take it: a tuple of 1 ..
+    GRANULOMETRY_MAX_RADII distinct ascending integers, each 1 .. GRANULOMETRY_MAX_RADIUS, else ValueError."""
+    try:
+        if isinstance(radii, (str, bytes)):
+            raise TypeError
+        given = list(radii)
+        if any(isinstance(r, (bool, np.bool_, str)) or r != int(r) for r in given):
+            raise TypeError
+        rs = tuple(int(r) for r in given)
+    except (TypeError, ValueError):
+        raise ValueError("granulometry radii are a list of integers, got %r" % (radii,))
+    if not 1 <= len(rs) <= GRANULOMETRY_MAX_RADII:
+        raise ValueError("granulometry takes 1 .. %d radii, got %d" % (GRANULOMETRY_MAX_RADII, len(rs)))
+    for r in rs:
+        if not 1 <= r <= GRANULOMETRY_MAX_RADIUS:
+            raise ValueError("granulometry radius %d is not in 1 .. %d" % (r, GRANULOMETRY_MAX_RADIUS))
+    if any(y <= x for x, y in zip(rs, rs[1:])):
+        raise ValueError("granulometry radii are distinct and ascending, got %r" % (rs,))
+    return rs
 
 
 def blob_threshold(threshold):
@@ -766,6 +793,11 @@ class SimCooccurrenceResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("pairs", (C.c_uint64 * 4) * COOCCURRENCE_MAX_DISTANCES)]
 
 
+class SimGranulometryResult(C.Structure):
+    """musica_sim_granulometry_result: where a query's table lies in `tables` and the pixels of its region."""
+    _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64)]
+
+
 class SimBlobsResult(C.Structure):
     """musica_sim_blobs_result: where a query's table and label plane lie, its counts and its largest component."""
     _fields_ = [("table_offset", C.c_uint64), ("label_offset", C.c_uint64), ("pixels", C.c_uint64), ("changed", C.c_uint64), ("components", C.c_uint64),
@@ -997,6 +1029,7 @@ ABI = {
     "musica_sim_lattice": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimLatticeResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_spectrum": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimSpectrumResult), C.POINTER(C.c_int64), C.c_uint64]),
     "musica_sim_cooccurrence": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimCooccurrenceResult), _U32P, C.c_uint64]),
+    "musica_sim_granulometry": (C.c_int, [_VP, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimGranulometryResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_blobs": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimBlobsResult), C.POINTER(C.c_uint64), C.c_uint64, _U32P, C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
@@ -1483,7 +1516,7 @@ class MusicaProcessing:
         return out
 
     def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False, trail=()):
-        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _reach share: the refusals of sim_<name> before any call
+        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _reach share: the refusals of sim_<name> before any call
         (most: 1 .. most queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead`
         in front of the count and `trail` (blobs: the label plane and its length) behind the tables' length. Returns the results and the
         flat tables, `words` zeroed words of `dtype`."""
@@ -1634,6 +1667,23 @@ class MusicaProcessing:
             at = int(r.table_offset)
             out.append({"table": tables[at:at + per].reshape(len(ds), 4, 2, G, G).copy(),
                         "pairs": np.array([[int(r.pairs[k][i]) for i in range(4)] for k in range(len(ds))], dtype=np.uint64)})
+        return out
+
+    def sim_granulometry(self, queries, radii):
+        """metrics.granulometry_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 1, 1 .. GRANULOMETRY_MAX_QUERIES of them, all in one launch; radii 1 .. 8 distinct ascending integers
+        1 .. 16 (granulometry_radii): ValueError before any call, as for a count out of range. Returns one dict per query: "table", a
+        (K + 1, 2, 5) uint64 array [class, the residue last][polarity bright = 0, dark = 1][sum A, sum B, sum A^2, sum B^2, sum A B],
+        and "pixels", w * h."""
+        rs = granulometry_radii(radii)
+        qs = _queries(queries)
+        per = (len(rs) + 1) * 2 * GRANULOMETRY_WORDS
+        res, tables = self._sim_tables("granulometry", qs, SimGranulometryResult, np.uint64, len(qs) * per, len(rs), (C.c_uint32 * len(rs))(*rs),
+                                       most=GRANULOMETRY_MAX_QUERIES)
+        out = []
+        for r in res[:len(qs)]:
+            at = int(r.table_offset)
+            out.append({"table": tables[at:at + per].reshape(len(rs) + 1, 2, GRANULOMETRY_WORDS).copy(), "pixels": int(r.pixels)})
         return out
 
     def sim_reach(self, queries, radii):

@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import BLOB_KEYS, COOCCURRENCE_FEATURES, SPECTRUM_BAND_KEYS, SPECTRUM_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
+from .metrics import BLOB_KEYS, COOCCURRENCE_FEATURES, GRANULOMETRY_CLASS_KEYS, GRANULOMETRY_KEYS, GRANULOMETRY_POLARITIES, SPECTRUM_BAND_KEYS, SPECTRUM_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -58,6 +58,11 @@ SPECTRUM_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'tile', 'tiles', 
 # the comparison's largest divergence, the same on each of its lines
 TEXTURE_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'levels', 'distance', 'pairs'] + \
                      ['%s %s' % (f, what) for f in COOCCURRENCE_FEATURES + ('anisotropy',) for what in ('a', 'b', 'difference')] + ['divergence', 'largest divergence']
+
+# granulometry_robustness.csv: one line per row, comparison the row has, polarity and class, the residue (the class behind the last
+# radius, without an element) last; the class's numbers, then the polarity's, the same on each of its lines
+GRANULOMETRY_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'pixels', 'polarity', 'class', 'radius', 'side', 'sum a', 'sum b'] + \
+                          [k.replace('_', ' ') for k in GRANULOMETRY_CLASS_KEYS + GRANULOMETRY_KEYS]
 
 ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
 ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
@@ -246,7 +251,22 @@ def _texture_lines(t):
             [e["divergence"], t["divergence"]] for e in t["distances"] if e is not None]
 
 
-# The files of the comparison metrics (harness.STUDY_METRICS), by key suffix: a study that has direct_<suffix> gets the file.
+def _granulometry_lines(t):
+    """A line per polarity and class, the residue last (no radius, side or class numbers): the pixels, the polarity, the class, the
+    radius and side of the element that removes it, its exact sums of A and B, share, gain, coherence and mse, then the polarity's mean
+    sides, their shift, the slope and the residue's shift."""
+    lines = []
+    for p, polarity in enumerate(GRANULOMETRY_POLARITIES):
+        s = t[polarity]
+        totals = [_blank(s[k]) for k in GRANULOMETRY_KEYS]
+        for k, words in enumerate(t["table"]):
+            c = s["classes"][k] if k < len(s["classes"]) else None
+            lines.append([t["pixels"], polarity, k, c["radius"] if c else "", c["side"] if c else "", words[p][0], words[p][1]] +
+                         [_blank(c[key]) if c else "" for key in GRANULOMETRY_CLASS_KEYS] + totals)
+    return lines
+
+
+# The files of the comparison metrics (harness.ROW_METRICS), by key suffix: a study that has direct_<suffix> gets the file.
 # per "row": one line per row, header(with_reference), then cells(a group's value or None) for every group; per "comparison": one line
 # per row and comparison that the row has, the header as it stands, then cells(the value); per "band": the same with a line for each
 # entry of cells(the value).
@@ -260,6 +280,7 @@ METRIC_CSVS = {
     "blobs": MetricCsv("blob_robustness.csv", "comparison", BLOB_CSV_HEADER, _blob_cells),
     "spectrum": MetricCsv("spectrum_robustness.csv", "band", SPECTRUM_CSV_HEADER, _spectrum_lines),
     "texture": MetricCsv("texture_robustness.csv", "band", TEXTURE_CSV_HEADER, _texture_lines),
+    "granulometry": MetricCsv("granulometry_robustness.csv", "band", GRANULOMETRY_CSV_HEADER, _granulometry_lines),
 }
 
 
@@ -334,6 +355,13 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     comparison's name, G, the distance, its pairs, contrast, dissimilarity, homogeneity, energy, entropy, correlation and anisotropy
     of side a, of side b and their difference, the distance's Jensen-Shannon divergence, then the comparison's largest divergence, the
     same on each of its lines.
+
+    Studies run with granulometry=radii (rows[0] has "direct_granulometry") also get granulometry_robustness.csv
+    (GRANULOMETRY_CSV_HEADER): one line per row, the unaltered one included, comparison that the row has, polarity (bright, dark) and
+    class, the residue last: the comparison's name, its pixels, the polarity, the class, the radius and side of the element that removes
+    it, the exact sums of A and B, the pattern-spectrum shares of either side, gain, coherence and mse (empty for the residue), then
+    the polarity's mean element sides, their shift, the slope of log gain on log side and the residue's shift, the same on each of its
+    lines.
 
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
