@@ -1293,6 +1293,48 @@ typedef struct musica_sim_granulometry_result {
 int musica_sim_granulometry(musica_ctx* ctx, uint32_t radius_count, const uint32_t* radii, uint32_t count, const musica_sim_query* queries,
                             musica_sim_granulometry_result* results, uint64_t* tables, uint64_t table_words);
 
+/* ---- contours: the distances between the edge sets of a comparison (new, not in the reference) ----
+ * Are the contours of the output where the contours of the reference are, how far did they move, how many are new (halo rims, rebound
+ * rings, noise lifted over the edge threshold) and how many are gone? musica_sim_gradients compares gradients at the same pixel; this
+ * call compares the two edge SETS, as Pratt's figure of merit, the chamfer distances and the Hausdorff distance do, all of which come
+ * from its table. metrics.contour_statistics is the contract. Queries are musica_sim_compare's with w, h >= 1, at most
+ * MUSICA_CONTOURS_MAX_QUERIES (a row's direct, registered and two vendor comparisons). Side a is the graded plane of the query's image
+ * quantised as musica_sim_compare quantises it, side b the query's reference slot. The region is its own domain; nothing outside it is
+ * read. The contour E of a side: the strength M = gx^2 + gy^2 of the integer Sobel gradients (musica_sim_gradients') at
+ * 1 <= x <= w - 2, 1 <= y <= h - 2 and 0 everywhere else (a region with a side below 3 has no contour); a pixel is horizontal where
+ * |gx| >= |gy|, else vertical; before / after are M(x - 1, y) / M(x + 1, y) of a horizontal pixel, M(x, y - 1) / M(x, y + 1) of a
+ * vertical one; E = M >= threshold and M > before and M >= after (on a plateau of equal strengths the left or upper pixel), threshold
+ * 1 .. MUSICA_CONTOURS_MAX_THRESHOLD, the largest M there is. For a source set S and a target set T every pixel s of S gets
+ * d2(s) = min over t in T of dx^2 + dy^2, exact; its bin is d2 where d2 <= radius^2 and radius^2 + 1 ("far") otherwise, radius
+ * 1 .. MUSICA_CONTOURS_MAX_RADIUS; an empty T puts all of S into "far". Query i gets 2 * (radius^2 + 2) uint64_t in the flat `tables`,
+ * from results[i].table_offset (in words) on, indexed [direction][bin]: direction 0 with S = E_a, T = E_b (where the output's contours
+ * lie with respect to the reference's), direction 1 with S = E_b, T = E_a. A bin whose index is no sum of two squares is written as 0.
+ * results[i].contour_a / contour_b = |E_a|, |E_b|, counted where the contours are made, not from the table; pixels = w * h. With
+ * `planes` not NULL query i also gets w * h bytes, row-major, from results[i].plane_offset (in bytes; set whether or not planes were
+ * asked for) on: bit 0 = E_a, bit 1 = E_b. Identities: row 0 sums to contour_a and row 1 to contour_b; table[0][0] == table[1][0] ==
+ * |E_a and E_b|; swapping the sides swaps the rows; identical sides put everything into bin 0; the table at a smaller radius r is this
+ * one with the bins r^2 + 1 .. radius^2 + 1 folded into its far bin; complementing either side (255 - v) changes nothing; the same
+ * content at another origin gives the same table. Everything is an integer: tables and planes equal the restatement word for word
+ * and repeat from call to call, whatever MUSICA_CONTOURS_GROUPS (the workgroups of a query's direction, read at every call; 0: the
+ * launch's own choice) says. Every word of the tables is written and nothing behind them; with `planes` every byte of the planes and
+ * nothing behind them. Synchronous, on the context's stream after whatever was enqueued there; changes no slot, no result of a step
+ * and no input image; scratch is allocated on first use. Refused: what musica_sim_compare refuses (with the smallest side 1 and at
+ * most MUSICA_CONTOURS_MAX_QUERIES queries, none included), then a threshold out of range, a radius out of range, a NULL `tables`,
+ * table_words below the tables' words, and plane_bytes below the planes' bytes where `planes` is given; all before any launch or
+ * copy. After a refusal the context stays usable. */
+#define MUSICA_CONTOURS_MAX_RADIUS 32
+#define MUSICA_CONTOURS_MAX_QUERIES 4
+#define MUSICA_CONTOURS_MAX_THRESHOLD 1300500u
+typedef struct musica_sim_contours_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t contour_a;             /* |E_a| */
+    uint64_t contour_b;             /* |E_b| */
+    uint64_t pixels;                /* w * h */
+    uint64_t plane_offset;          /* where the query's byte plane starts in `planes`, in bytes */
+} musica_sim_contours_result;
+int musica_sim_contours(musica_ctx* ctx, uint32_t threshold, uint32_t radius, uint32_t count, const musica_sim_query* queries,
+                        musica_sim_contours_result* results, uint64_t* tables, uint64_t table_words, uint8_t* planes, uint64_t plane_bytes);
+
 /* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
  * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change
  * outwards: the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global

@@ -603,6 +603,30 @@ inline int granulometry_groups(int tiles, int most = 0) {
 // metrics.granulometry_statistics over `count` queries (grid.x = max_groups, the largest `groups`, at least 1; grid.y = the two
 // polarities). tables: every query's words, zeroed by the caller: the workgroups add into them with u64 atomics
 void launch_sim_granulometry(hipStream_t st, const GranulometryQueryDev* d_qs, int count, int max_groups, const GranulometryRadii& radii, unsigned long long* tables);
+// kernels_contours.hip: the contour metric. One comparison of musica_sim_contours: tiles_x / tiles_y: its region's 64 x 64 tiles;
+// groups: the persistent workgroups that share the tiles of ONE direction (contours_groups); table: where its 2 * (radius^2 + 2) words
+// start in the launch's flat tables, in words; bits: where its two bit planes (side a, then side b: h rows of row_words u64, bit x & 63
+// of word x >> 6 = pixel x) start in the scratch, in words; plane: where its byte plane starts, in bytes.
+constexpr int kContoursMaxRadius = 32;             // MUSICA_CONTOURS_MAX_RADIUS
+constexpr int kContoursMaxQueries = 4;             // MUSICA_CONTOURS_MAX_QUERIES
+constexpr uint32_t kContoursMaxThreshold = 1300500u;   // MUSICA_CONTOURS_MAX_THRESHOLD: kernels_gradients.hip's kGradMaxTerm
+struct ContourQueryDev : SimRegion {
+    int tiles_x, tiles_y, groups, row_words;
+    unsigned long long table, bits, plane;
+};
+// The workgroups that one direction of a query of `tiles` tiles gets: min(tiles, want), where want is kContoursGroups, or `most`
+// where 0 < most < want (the tuning variable MUSICA_CONTOURS_GROUPS, read at every call): the tables do not depend on it.
+constexpr int kContoursGroups = 1024;
+inline int contours_groups(int tiles, int most = 0) {
+    const int want = most > 0 && most < kContoursGroups ? most : kContoursGroups;
+    return tiles < want ? tiles : want;
+}
+// metrics.contour_statistics over `count` queries: k_contour_mask (grid.x = max_tiles, the most tiles of a query; grid.z the queries)
+// writes every word of the bit planes, the byte planes where `planes` is not null, and adds the set sizes to counts[query][side]
+// (zeroed by the caller); k_contour_distance (grid.x = max_groups, grid.y = the two directions) adds into the tables, zeroed by the
+// caller, with u64 atomics
+void launch_sim_contours(hipStream_t st, const ContourQueryDev* d_qs, int count, int max_tiles, int max_groups, uint32_t threshold, int radius,
+                         unsigned long long* bits, unsigned long long* counts, uint8_t* planes, unsigned long long* tables);
 // kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
 // Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
 constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII

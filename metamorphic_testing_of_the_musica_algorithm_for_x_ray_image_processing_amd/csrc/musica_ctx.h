@@ -200,6 +200,14 @@ struct StudyState {
     // musica_sim_granulometry: the queries and the flat tables
     GranulometryQueryDev* d_granulometry_q = nullptr;         // [MUSICA_GRANULOMETRY_MAX_QUERIES]
     unsigned long long* d_granulometry_tables = nullptr;      // [MUSICA_GRANULOMETRY_MAX_QUERIES][MAX_RADII + 1][2][MUSICA_GRANULOMETRY_WORDS], allocated by the first musica_sim_granulometry
+    // musica_sim_contours: the queries, the flat tables, the set sizes and the scratch planes
+    ContourQueryDev* d_contour_q = nullptr;                   // [MUSICA_CONTOURS_MAX_QUERIES]
+    unsigned long long* d_contour_tables = nullptr;           // [MUSICA_CONTOURS_MAX_QUERIES][2][MAX_RADIUS^2 + 2], allocated by the first musica_sim_contours
+    unsigned long long* d_contour_counts = nullptr;           // [MUSICA_CONTOURS_MAX_QUERIES][2]: |E_a|, |E_b|
+    unsigned long long* d_contour_bits = nullptr;             // contour_bits_cap words: per query the two sides' bit planes, h rows of ceil(w / 64) words
+    size_t contour_bits_cap = 0;
+    uint8_t* d_contour_planes = nullptr;                      // contour_plane_cap bytes: only calls that ask for the byte planes
+    size_t contour_plane_cap = 0;
     // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
     // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
     uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either

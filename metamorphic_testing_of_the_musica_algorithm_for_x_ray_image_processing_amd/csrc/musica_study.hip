@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_codec.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip, kernels_granulometry.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip, kernels_granulometry.hip, kernels_contours.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
 // sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
@@ -413,7 +413,7 @@ static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion
     d.h = (int)q.h;
 }
 
-// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _reach) -----------------------------------------------
+// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _contours / _reach) -----------------------------------------------
 // Where a table call keeps its queries and its flat tables in musica_ctx::study, and what it takes: at most `most` queries with sides
 // of at least `min_side`. The tables' buffer holds `tables_cap` words from the first call on; where `grown` names its capacity it
 // holds the words of the largest call so far instead.
@@ -434,6 +434,7 @@ constexpr TableBuffers<BlobQueryDev, unsigned long long> kBlobBuffers{&StudyStat
 constexpr TableBuffers<SpectrumQueryDev, unsigned long long> kSpectrumBuffers{&StudyState::d_spectrum_q, &StudyState::d_spectrum_tables, MUSICA_SPECTRUM_MAX_QUERIES, 1, (size_t)MUSICA_SPECTRUM_MAX_QUERIES * kSpectrumMaxTile * kSpectrumMaxTile * kSpectrumWords};
 constexpr TableBuffers<CooccurrenceQueryDev, uint32_t> kCooccurrenceBuffers{&StudyState::d_cooccurrence_q, &StudyState::d_cooccurrence_tables, MUSICA_COOCCURRENCE_MAX_QUERIES, 1, (size_t)MUSICA_COOCCURRENCE_MAX_QUERIES * MUSICA_COOCCURRENCE_MAX_DISTANCES * 4 * 2 * kCooccurrenceMaxLevels * kCooccurrenceMaxLevels};
 constexpr TableBuffers<GranulometryQueryDev, unsigned long long> kGranulometryBuffers{&StudyState::d_granulometry_q, &StudyState::d_granulometry_tables, MUSICA_GRANULOMETRY_MAX_QUERIES, 1, (size_t)MUSICA_GRANULOMETRY_MAX_QUERIES * (MUSICA_GRANULOMETRY_MAX_RADII + 1) * 2 * kGranulometryWords};
+constexpr TableBuffers<ContourQueryDev, unsigned long long> kContourBuffers{&StudyState::d_contour_q, &StudyState::d_contour_tables, MUSICA_CONTOURS_MAX_QUERIES, 1, (size_t)MUSICA_CONTOURS_MAX_QUERIES * 2 * (MUSICA_CONTOURS_MAX_RADIUS * MUSICA_CONTOURS_MAX_RADIUS + 2)};
 constexpr TableBuffers<ReachQueryDev, unsigned long long> kReachBuffers{&StudyState::d_reach_q, &StudyState::d_reach_tables, MUSICA_REACH_MAX_QUERIES, 1, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords};
 
 // What a call's place() says of one query: its tiles or chunks (the launch's grid.x is the largest) and the words of its table.
@@ -1448,6 +1449,71 @@ int musica_sim_granulometry(musica_ctx* c, uint32_t radius_count, const uint32_t
         },
         nothing, [&](uint32_t i, const musica_sim_query& q, const uint64_t*) { out[i].pixels = (uint64_t)q.w * q.h; });
     ABI_CATCH("musica_sim_granulometry")
+}
+
+// ---- the contours of a comparison (musica_sim_contours, include/musica.h; kernels_contours.hip) ------------------------------------------
+static_assert(kContoursMaxRadius == MUSICA_CONTOURS_MAX_RADIUS && kContoursMaxQueries == MUSICA_CONTOURS_MAX_QUERIES && kContoursMaxThreshold == MUSICA_CONTOURS_MAX_THRESHOLD,
+              "kernels_contours.hip's constants are include/musica.h's");
+
+int musica_sim_contours(musica_ctx* c, uint32_t threshold, uint32_t radius, uint32_t count, const musica_sim_query* qs, musica_sim_contours_result* out, uint64_t* tables,
+                        uint64_t table_words, uint8_t* planes, uint64_t plane_bytes) {
+    ABI_TRY
+    size_t pixels = 0, bit_words = 0;   // of the whole call: every query's w * h, every query's two bit planes
+    int max_tiles = 1;
+    unsigned long long counts[kContoursMaxQueries][2] = {};
+    const int ok = sim_query_tables(
+        c, "musica_sim_contours", kContourBuffers, count, qs, out, tables, table_words,
+        [&] {
+            if (threshold < 1 || threshold > MUSICA_CONTOURS_MAX_THRESHOLD)
+                return fail("musica_sim_contours: threshold %u is not in 1 .. %u", threshold, MUSICA_CONTOURS_MAX_THRESHOLD);
+            if (radius < 1 || radius > MUSICA_CONTOURS_MAX_RADIUS) return fail("musica_sim_contours: radius %u is not in 1 .. %d", radius, MUSICA_CONTOURS_MAX_RADIUS);
+            return 1;
+        },
+        [&](const musica_sim_query& q, ContourQueryDev& d) {
+            const int tiles = tile_grid(d, q.w, q.h);
+            max_tiles = std::max(max_tiles, tiles);
+            d.groups = contours_groups(tiles, env_int("MUSICA_CONTOURS_GROUPS", 0));
+            d.row_words = d.tiles_x;   // a tile column is one u64 of a bit row
+            d.bits = bit_words;
+            d.plane = pixels;
+            bit_words += 2 * (size_t)q.h * d.row_words;
+            pixels += (size_t)q.w * q.h;
+            return TablePlace{d.groups, 2 * ((size_t)radius * radius + 2)};
+        },
+        [&] {   // behind the tables' refusals, in front of every launch and copy
+            if (planes && plane_bytes < pixels)
+                return fail("musica_sim_contours: plane_bytes %llu is less than the %llu bytes of the planes", (unsigned long long)plane_bytes, (unsigned long long)pixels);
+            StudyState& st = c->study;
+            if (!grow(c, "musica_sim_contours", &st.d_contour_bits, &st.contour_bits_cap, bit_words, "bit-plane words") ||
+                (planes && !grow(c, "musica_sim_contours", &st.d_contour_planes, &st.contour_plane_cap, pixels, "plane bytes")))
+                return 0;
+            if (!ensure(c, &st.d_contour_counts, (size_t)kContoursMaxQueries * 2)) return fail("musica_sim_contours: device allocation failed");
+            HIP_OK(hipMemsetAsync(st.d_contour_counts, 0, sizeof(counts), c->stream));
+            return 1;
+        },
+        [&](const ContourQueryDev* d_qs, int max_groups, unsigned long long* d_tables) {
+            StudyState& st = c->study;
+            launch_sim_contours(c->stream, d_qs, (int)count, max_tiles, max_groups, threshold, (int)radius, st.d_contour_bits, st.d_contour_counts,
+                                planes ? st.d_contour_planes : nullptr, d_tables);
+        },
+        [&] {
+            HIP_OK(hipMemcpyAsync(counts, c->study.d_contour_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
+            if (planes) HIP_OK(hipMemcpyAsync(planes, c->study.d_contour_planes, pixels, hipMemcpyDeviceToHost, c->stream));
+            return 1;
+        },
+        [&](uint32_t i, const musica_sim_query& q, const uint64_t*) {
+            out[i].contour_a = counts[i][0];
+            out[i].contour_b = counts[i][1];
+            out[i].pixels = (uint64_t)q.w * q.h;
+        });
+    if (!ok) return 0;
+    uint64_t at = 0;   // the byte planes lie one behind the other, whether or not they were asked for
+    for (uint32_t i = 0; i < count; i++) {
+        out[i].plane_offset = at;
+        at += out[i].pixels;
+    }
+    return 1;
+    ABI_CATCH("musica_sim_contours")
 }
 
 // ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------

@@ -1,9 +1,9 @@
 // study_device.h — what the study's kernels share on the device (kernels_similarity.hip, kernels_scales.hip, kernels_joint.hip,
 // kernels_displace.hip, kernels_covariance.hip, kernels_ensemble.hip, kernels_details.hip, kernels_edges.hip, kernels_gratings.hip,
-// kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_scatter.hip, kernels_reach.hip, kernels_observer.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip, kernels_granulometry.hip): the address-space typedefs, the
+// kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_scatter.hip, kernels_reach.hip, kernels_observer.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip, kernels_granulometry.hip, kernels_contours.hip): the address-space typedefs, the
 // reductions and their ONE order, the workgroup's prefix sum, the
 // 64 x 64 tile of a region, the pixel words of the kernels that stream a u16 plane and the insertion body of the patch relations
-// (insert_patches), the packed byte windows of k_displace and k_cov_add, the staged windows of k_gradients and k_order (stage_windows), the one-sided window with a clipped halo of k_cooccurrence and k_granulometry (stage_halo_window), and the
+// (insert_patches), the packed byte windows of k_displace and k_cov_add, the staged windows of k_gradients and k_order (stage_windows), the one-sided window with a clipped halo of k_cooccurrence, k_granulometry and k_contour_mask (stage_halo_window), and the
 // per-window SSIM terms.
 #pragma once
 
@@ -326,7 +326,7 @@ __device__ __forceinline__ uint32_t load_pixels4(const GlobalU8* p, int n) { ret
 // the pixels that may be read: window pixel (c, r) is region pixel (ox + c, oy + r), `p` the REGION's first pixel, and only the region
 // pixels x_lo <= x < x_hi, y_lo <= y < y_hi (the caller's tile and its halo, clipped to the region) are read; every other byte of the
 // staged words is 0. ox may be negative. map(word): what is stored of a word of four pixels (k_cooccurrence: their levels;
-// k_granulometry: the bytes or their complements). `outside`, where not 0: the word whose bytes stand behind map() for the pixels that
+// k_granulometry: the bytes or their complements; k_contour_mask: the bytes). `outside`, where not 0: the word whose bytes stand behind map() for the pixels that
 // were not read (k_granulometry: 255, the neutral value of an erosion). The caller's barrier stands behind it.
 template <typename Px, typename Map>
 __device__ __forceinline__ void stage_halo_window(const Px* __restrict__ p, int pitch_px, int ox, int oy, int x_lo, int x_hi, int y_lo, int y_hi,

@@ -1088,6 +1088,12 @@ ROW_METRICS = STUDY_METRICS + (
                      lambda opt, out, plane, region: granulometry_row(granulometry_statistics(out, plane, [region], opt.granulometry)[0], opt.granulometry),
                      lambda proc, queries, opt: [granulometry_row(r, opt.granulometry) for r in proc.sim_granulometry(queries, opt.granulometry)],
                      METRIC_CSVS["granulometry"]),
+    ComparisonMetric("contours", "contours", lambda v: v is not None, lambda v: None if v is None else mp.contour_threshold(v),
+                     lambda opt, out, plane, region: contour_row(contour_statistics(out, plane, [region], opt.contours, opt.contour_radius, planes=opt.contour_maps)[0],
+                                                                 opt.contours, opt.contour_radius),
+                     lambda proc, queries, opt: [contour_row(r, opt.contours, opt.contour_radius)
+                                                 for r in proc.sim_contours(queries, opt.contours, opt.contour_radius, planes=opt.contour_maps)],
+                     METRIC_CSVS["contours"]),
 )
 TONE_KEYS, SCALE_ROW_KEYS, GRADIENT_ROW_KEYS, ORDER_ROW_KEYS, LATTICE_ROW_KEYS, BLOB_ROW_KEYS = \
     ({c: "%s_%s" % (c, m.suffix) for c in COMPARED} for m in COMPARISON_METRICS[:6])   # comparison -> its sibling key, of the metrics that tests ask by name
@@ -1162,7 +1168,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
                   gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, codecs=None,
-                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, order=False):
+                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, contours=None, contour_radius=mp.CONTOURS_RADIUS, contour_maps=False, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1202,6 +1208,8 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         raise ValueError("blob_connectivity is 4 or 8, got %r" % (blob_connectivity,))
     o["blob_connectivity"] = int(blob_connectivity)
     o["texture_distances"] = mp.cooccurrence_distances(texture_distances)
+    o["contour_radius"] = mp.contour_radius(contour_radius)
+    o["contour_maps"] = _checked_flag("contour_maps")(contour_maps)
     for rel in RELATIONS:
         if o[rel.option] is not None:
             o[rel.option] = rel.check(o[rel.option], n)
@@ -1465,7 +1473,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, order=False):
+              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, contours=None, contour_radius=mp.CONTOURS_RADIUS, contour_maps=False, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1765,7 +1773,21 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     element sides and their shift, the slope of log gain on log side, the residue's shift), "radii", "pixels" and the exact "table". On
     the device one musica_sim_granulometry call behind the texture's; on the host the restatement sieves the same crops. The tables
     are integers and there is one summary function: the values are equal to the last bit on every path. With granulometry=None the
-    rows and the launches are exactly as before."""
+    rows and the launches are exactly as before.
+
+    contours: a threshold tau on the squared Sobel gradient, an integer 1 .. 1 300 500 (processing.contour_threshold; None: off), asks
+    whether the contours of the output are where the contours of the reference are: both sides' thinned edge sets and, per contour pixel
+    of one side, the exact squared distance to the nearest contour pixel of the other, resolved up to contour_radius, 1 .. 32
+    (processing.contour_radius; contour_statistics). Every comparison dict of a row gains a sibling behind all other keys, the
+    granulometry's included: direct_contours, registered_contours and, with a vendor image, reference_contours and
+    registered_reference_contours; present exactly where the original is, None where it is None. Each is contour_row's dict:
+    contour_summary's sizes, densities and ratio of the two sets, Pratt's figure of merit "fom", the "kept", "moved" and "lost" shares
+    of the reference's contour, the "spurious" share of the output's, per direction the mean, median and 95th percentile of the
+    distance, the "hausdorff" distance, then "threshold", "radius", "pixels" and the exact "table"; with contour_maps also "planes",
+    the byte plane (bit 0: the output's contour, bit 1: the reference's) that report.write_contour_maps draws. On the device one
+    musica_sim_contours call behind the granulometry's; on the host the restatement takes the same crops. The tables are integers and
+    there is one summary function: the values are equal to the last bit on every path. With contours=None the rows and the launches
+    are exactly as before."""
     options = {k: v for k, v in locals().items() if k not in ("raw", "runner", "rng")}   # every option by its name, as study_options takes them
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, **options)
@@ -1779,7 +1801,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, texture, granulometry, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, texture, granulometry, contours, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -1950,6 +1972,24 @@ def granulometry_list(text):
         raise argparse.ArgumentTypeError(str(e))
 
 
+def contour_tau(text):
+    """--contours TAU: the threshold on the squared Sobel gradient, 1 .. 1 300 500 (processing.contour_threshold)."""
+    import argparse
+    try:
+        return mp.contour_threshold(int(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def contour_reach(text):
+    """--contour-radius R: 1 .. 32 (processing.contour_radius)."""
+    import argparse
+    try:
+        return mp.contour_radius(int(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def reach_list(text):
     """--reach R0,R1,...: radii from 0, strictly ascending (processing.reach_radii)."""
     import argparse
@@ -2088,6 +2128,16 @@ def main(argv=None):
                          "pattern-spectrum shares, gain, coherence and mse, the mean element side and the slope of log gain on log side, "
                          "written to granulometry_robustness.csv; on the GPU with --device-metrics / --device-alterations "
                          "(musica_sim_granulometry)")
+    ap.add_argument("--contours", nargs="?", const=mp.CONTOURS_THRESHOLD, default=None, type=contour_tau, metavar="TAU",
+                    help="add the contours of every comparison: the thinned Sobel edge sets of both sides (squared gradient >= TAU, 1 .. 1300500; "
+                         "without a value 4096: |g| >= 64, a straight step of 16 of 255 gray levels) and the exact distances between them: "
+                         "Pratt's figure of merit, the kept, moved, lost and spurious shares, mean, median and 95th percentile of the distance "
+                         "and the Hausdorff distance, written to contour_robustness.csv; on the GPU with --device-metrics / "
+                         "--device-alterations (musica_sim_contours)")
+    ap.add_argument("--contour-radius", type=contour_reach, default=mp.CONTOURS_RADIUS, metavar="R",
+                    help="the radius up to which --contours resolves a distance, 1 .. 32 (default 16): a contour pixel without a partner within R is lost or spurious")
+    ap.add_argument("--contour-maps", metavar="DIR", default=None,
+                    help="with --contours: draw the two contours of every registered row (the output's alone 85, the reference's alone 170, both 255) as BMPs into DIR")
     ap.add_argument("--blob-connectivity", type=int, default=8, choices=(4, 8), help="the neighbourhood of --blobs (default 8)")
     ap.add_argument("--order", action="store_true",
                     help="ask whether the local order of the gray levels survived: the census signs of every comparison over the 7 x 7 "
@@ -2170,13 +2220,15 @@ def main(argv=None):
                     **({"ensemble_batch": args.ensemble_batch} if args.ensemble else {}))
     shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
                  {"displacement": args.displacement} if args.displacement else {}
-    for m in ROW_METRICS[1:]:   # --scales .. --granulometry, under their options' names (--tone and --symmetries are passed whatever they say)
+    for m in ROW_METRICS[1:]:   # --scales .. --contours, under their options' names (--tone and --symmetries are passed whatever they say)
         if m.on(getattr(args, m.option)):
             shift_args[m.option] = getattr(args, m.option)
     if args.blobs is not None:
         shift_args["blob_connectivity"] = args.blob_connectivity
     if args.texture is not None:
         shift_args["texture_distances"] = args.texture_distances
+    if args.contours is not None:
+        shift_args.update(contour_radius=args.contour_radius, contour_maps=bool(args.contour_maps))
     for m in MOVED[1:]:                # --blurs .. --codecs: the lists as given, a flag without a list as the entry's defaults for the size
         if getattr(args, m.option):
             shift_args[m.option] = m.cli(getattr(args, m.option), args.size) if m.cli else getattr(args, m.option)
@@ -2210,6 +2262,8 @@ def main(argv=None):
         write_covariance_maps(studies, args.covariance_maps)
     if args.reach_maps:
         write_reach_maps(studies, args.reach_maps)
+    if args.contour_maps and args.contours is not None:
+        write_contour_maps(studies, args.contour_maps)
     print("wrote %d alterations to %s" % (sum(len(rows) - 1 for _, rows in studies), args.out))
     return 0
 

@@ -2716,3 +2716,154 @@ def granulometry_row(stats, radii):
     "pixels" and the exact "table" as nested lists."""
     return dict(granulometry_summary(stats["table"], radii, stats["pixels"]), radii=[int(r) for r in mp.granulometry_radii(radii)],
                 pixels=int(stats["pixels"]), table=np.asarray(stats["table"]).astype(np.uint64).tolist())
+
+
+# ---- the contours of a comparison: the distances between the two edge sets -----------------------------------------------------------------
+# Are the contours of the output where the contours of the reference are, how far did they move, how many are new and how many are gone?
+# gsim, gc and turn compare gradients at the same pixel: a contour that moved by two pixels and one that vanished while another appeared
+# elsewhere look alike to them. The edge-detection literature's answer is the distance between the two edge sets (Pratt's figure of merit,
+# the chamfer distances, the Hausdorff distance), all from one table: per contour pixel of one side the exact squared Euclidean distance
+# to the nearest contour pixel of the other. contour_statistics is the contract of musica_sim_contours (include/musica.h), whose tables
+# and planes are bit-identical to it; contour_summary is what the study reports of the integers, one function for every path.
+
+CONTOUR_DIRECTIONS = ("a_to_b", "b_to_a")   # the table's rows: S = E_a, T = E_b (where a's contours lie with respect to b's), then S = E_b, T = E_a
+CONTOUR_KEYS = ("contour_a", "contour_b", "density_a", "density_b", "ratio", "fom", "kept", "moved", "lost", "spurious", "hausdorff")
+CONTOUR_DIRECTION_KEYS = ("found", "far", "mean", "median", "p95")
+CONTOUR_FOM_SCALE = 9        # Pratt's figure of merit: 1 / (1 + d^2 / 9), Pratt's alpha = 1 / 9
+CONTOUR_KEPT_D2 = 2          # a contour pixel is "kept" where the other side has one among its eight neighbours or at its place
+
+
+def contour_mask(p, threshold):
+    """The contour E of a 2-D uint8 plane, which is its own domain, as a bool plane: the strength M = gx^2 + gy^2 of sobel_gradients
+    over the interior 1 <= x <= w - 2, 1 <= y <= h - 2 and 0 everywhere else (a plane with a side below 3 has no contour); a pixel is
+    horizontal where |gx| >= |gy|, else vertical; `before` / `after` are M(x - 1, y) / M(x + 1, y) of a horizontal pixel and
+    M(x, y - 1) / M(x, y + 1) of a vertical one; E = M >= threshold and M > before and M >= after: non-maximum suppression along the
+    axis, on a plateau of equal strengths the left or upper pixel is the contour."""
+    tau = mp.contour_threshold(threshold)
+    p = np.asarray(p)
+    h, w = p.shape
+    M = np.zeros((h + 2, w + 2), dtype=np.int64)   # M with a frame of zeros: pixel (x, y) at [y + 1][x + 1]
+    horizontal = np.ones((h, w), dtype=bool)
+    if w >= 3 and h >= 3:
+        gx, gy = sobel_gradients(p)
+        M[2:h, 2:w] = gx * gx + gy * gy
+        horizontal[1:h - 1, 1:w - 1] = np.abs(gx) >= np.abs(gy)
+    m = M[1:h + 1, 1:w + 1]
+    before = np.where(horizontal, M[1:h + 1, 0:w], M[0:h, 1:w + 1])
+    after = np.where(horizontal, M[1:h + 1, 2:w + 2], M[2:h + 2, 1:w + 1])
+    return (m >= tau) & (m > before) & (m >= after)
+
+
+def _contour_distances(S, T, R):
+    """Row of the table: the R^2 + 2 counts of the pixels of S by the exact squared distance to the nearest pixel of T."""
+    row = np.zeros(R * R + 2, dtype=np.uint64)
+    ys, xs = np.nonzero(S)
+    if len(ys) == 0:
+        return row
+    if not T.any():
+        row[R * R + 1] = len(ys)
+        return row
+    iy, ix = ndimage.distance_transform_edt(~T, return_distances=False, return_indices=True)   # the nearest pixel of T, by index
+    dy, dx = iy[ys, xs].astype(np.int64) - ys, ix[ys, xs].astype(np.int64) - xs
+    d2 = dy * dy + dx * dx                                                                      # integers, never the float distance
+    row[:] = np.bincount(np.where(d2 <= R * R, d2, R * R + 1), minlength=R * R + 2).astype(np.uint64)
+    return row
+
+
+def contour_statistics(a, b, regions, threshold, radius, planes=False):
+    """What musica_sim_contours returns for every region (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes (side a, side b): a
+    list of dicts. The region's sub-array is its own domain: nothing outside it is read. E_a and E_b are contour_mask of the two
+    sub-arrays at `threshold` tau, 1 .. 1 300 500 (processing.contour_threshold). For a source set S and a target set T every pixel
+    s of S gets d^2(s) = the minimum over t in T of dx^2 + dy^2; its bin is d^2 where d^2 <= R^2 and R^2 + 1 ("far") otherwise, R the
+    `radius`, 1 .. 32 (processing.contour_radius); an empty T puts every pixel of S into "far". "table": the (2, R^2 + 2) uint64 array
+    of the bins' counts, direction 0 with S = E_a, T = E_b (where a's contours lie with respect to b's), direction 1 with S = E_b,
+    T = E_a; a bin whose index is no sum of two squares stays 0. "contour_a", "contour_b": |E_a|, |E_b|. "pixels": w * h. With
+    planes=True "planes": the (h, w) uint8 plane with bit 0 = E_a and bit 1 = E_b.
+    Identities: row 0 sums to contour_a and row 1 to contour_b; table[0][0] == table[1][0] == |E_a and E_b|; swapping the sides swaps
+    the rows; identical sides put everything into bin 0; the table at R' < R is the table at R with the bins R'^2 + 1 .. R^2 + 1
+    folded into its far bin; complementing either side (255 - v) changes nothing; the same content at another origin gives the same
+    table. The distances come from scipy's exact Euclidean distance transform, taken by the INDEX of the nearest target pixel and
+    squared as integers."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("contour_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    tau, R = mp.contour_threshold(threshold), mp.contour_radius(radius)
+    res = []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        Ea, Eb = contour_mask(a[ay:ay + h, ax:ax + w], tau), contour_mask(b[by:by + h, bx:bx + w], tau)
+        d = {"table": np.stack([_contour_distances(Ea, Eb, R), _contour_distances(Eb, Ea, R)]), "contour_a": int(Ea.sum()), "contour_b": int(Eb.sum()),
+             "pixels": w * h}
+        if planes:
+            d["planes"] = (Ea.astype(np.uint8) | (Eb.astype(np.uint8) << 1))
+        res.append(d)
+    return res
+
+
+def _contour_quantile(counts, d2s, total, q):
+    """The distance d of the ceil(q * total)-th found pixel in ascending order of d (total >= 1): the lower empirical quantile."""
+    want = max(1, math.ceil(q * total - 1e-12))
+    seen = 0
+    for n, d2 in zip(counts, d2s):
+        seen += n
+        if seen >= want:
+            return math.sqrt(d2)
+    return math.sqrt(d2s[-1])
+
+
+def contour_summary(table, radius, pixels):
+    """What the study reports of a comparison's contours, in f64 from contour_statistics' (or musica_sim_contours') exact integers of ONE
+    region only: one function for every study path. Row 0 of the table is a's contour pixels by their distance to b's, row 1 b's by
+    their distance to a's (b the reference); "found" are the pixels of a row in the bins d^2 <= R^2. A dict:
+        "contour_a", "contour_b"   the rows' sums; "density_a", "density_b": over the pixels; "ratio": contour_a / contour_b, None
+                                   where b has no contour
+        "fom"        Pratt's figure of merit: the sum over row 0's found pixels of 1 / (1 + d^2 / 9), divided by
+                     max(contour_a, contour_b); None without contours
+        "kept", "moved", "lost"    the shares of row 1 with d^2 <= 2, with 2 < d^2 <= R^2 and far; None where b has no contour
+        "spurious"   row 0's far share; None where a has no contour
+        "a_to_b", "b_to_a"         per direction "found", "far" and the "mean", "median" (the lower one) and "p95" of d over the found
+                                   pixels, None without any
+        "hausdorff"  the largest found d over both directions; None where any pixel is far or nothing was found."""
+    R = mp.contour_radius(radius)
+    t = np.asarray(table)
+    if t.shape != (2, R * R + 2) or t.dtype.kind not in "iu":
+        raise ValueError("the contour table of radius %d is (2, %d) integers, got %r %s" % (R, R * R + 2, t.shape, t.dtype))
+    pixels = int(pixels)
+    if pixels < 1:
+        raise ValueError("a contour comparison has at least one pixel, got %d" % pixels)
+    rows = [[int(v) for v in t[d]] for d in range(2)]
+    na, nb = sum(rows[0]), sum(rows[1])
+    out = {"contour_a": na, "contour_b": nb, "density_a": na / pixels, "density_b": nb / pixels, "ratio": na / nb if nb else None}
+    out["fom"] = math.fsum(n / (1.0 + d2 / CONTOUR_FOM_SCALE) for d2, n in enumerate(rows[0][:R * R + 1]) if n) / max(na, nb) if max(na, nb) else None
+    near = sum(rows[1][:min(CONTOUR_KEPT_D2, R * R) + 1])   # at R = 1 bin 2 is the far one: a diagonal neighbour is not resolved
+    far_b, far_a = rows[1][R * R + 1], rows[0][R * R + 1]
+    out["kept"] = near / nb if nb else None
+    out["moved"] = (nb - near - far_b) / nb if nb else None
+    out["lost"] = far_b / nb if nb else None
+    out["spurious"] = far_a / na if na else None
+    largest = None
+    for name, row in zip(CONTOUR_DIRECTIONS, rows):
+        hit = [(d2, n) for d2, n in enumerate(row[:R * R + 1]) if n]
+        found = sum(n for _, n in hit)
+        s = {"found": found, "far": row[R * R + 1], "mean": None, "median": None, "p95": None}
+        if found:
+            d2s, counts = [d2 for d2, _ in hit], [n for _, n in hit]
+            s["mean"] = math.fsum(n * math.sqrt(d2) for d2, n in hit) / found
+            s["median"] = _contour_quantile(counts, d2s, found, 0.5)
+            s["p95"] = _contour_quantile(counts, d2s, found, 0.95)
+            largest = max(largest or 0.0, math.sqrt(d2s[-1]))
+        out[name] = s
+    out["hausdorff"] = largest if (far_a == 0 and far_b == 0) else None
+    return out
+
+
+def contour_row(stats, threshold, radius):
+    """A row's *_contours value from ONE dict of contour_statistics (or sim_contours): contour_summary's dict, "threshold", "radius",
+    "pixels" and the exact "table" as nested lists; "planes" where the dict has them."""
+    row = dict(contour_summary(stats["table"], radius, stats["pixels"]), threshold=mp.contour_threshold(threshold), radius=mp.contour_radius(radius),
+               pixels=int(stats["pixels"]), table=np.asarray(stats["table"]).astype(np.uint64).tolist())
+    if "planes" in stats:
+        row["planes"] = np.asarray(stats["planes"], dtype=np.uint8)
+    return row

@@ -217,6 +217,11 @@ GRANULOMETRY_MAX_RADIUS = 16     # MUSICA_GRANULOMETRY_MAX_RADIUS
 GRANULOMETRY_MAX_QUERIES = 4     # MUSICA_GRANULOMETRY_MAX_QUERIES
 GRANULOMETRY_WORDS = 5           # MUSICA_GRANULOMETRY_WORDS
 GRANULOMETRY_RADII = (1, 2, 4, 8, 16)   # the study's default radii list
+CONTOURS_MAX_RADIUS = 32         # MUSICA_CONTOURS_MAX_RADIUS
+CONTOURS_MAX_QUERIES = 4         # MUSICA_CONTOURS_MAX_QUERIES
+CONTOURS_MAX_THRESHOLD = 1300500 # MUSICA_CONTOURS_MAX_THRESHOLD: 1020^2 + 510^2, the largest squared Sobel gradient of a uint8 plane
+CONTOURS_THRESHOLD = 4096        # the command line's default: |g| >= 64, a straight step of 16 of 255 gray levels
+CONTOURS_RADIUS = 16             # the study's default radius
 
 
 def zoom_ratio(zoom):
@@ -336,6 +341,30 @@ def granulometry_radii(radii):
     if any(y <= x for x, y in zip(rs, rs[1:])):
         raise ValueError("granulometry radii are distinct and ascending, got %r" % (rs,))
     return rs
+
+
+def _contour_integer(value, what, lo, hi):
+    try:
+        if isinstance(value, (bool, np.bool_, str, bytes, float, np.floating)) or value != int(value):
+            raise TypeError
+        v = int(value)
+    except (TypeError, ValueError):
+        raise ValueError("contours: %s is an integer %d .. %d, got %r" % (what, lo, hi, value))
+    if not lo <= v <= hi:
+        raise ValueError("contours: %s %d is not in %d .. %d" % (what, v, lo, hi))
+    return v
+
+
+def contour_threshold(threshold):
+    """The threshold tau on the squared Sobel gradient gx^2 + gy^2 of a contour pixel, as metrics.contour_statistics and the library
+    take it: an integer 1 .. CONTOURS_MAX_THRESHOLD, else ValueError (a bool, a float and a string are refused whatever they hold)."""
+    return _contour_integer(threshold, "the threshold", 1, CONTOURS_MAX_THRESHOLD)
+
+
+def contour_radius(radius):
+    """The radius R up to which the distance between two contour sets is resolved, as metrics.contour_statistics and the library take
+    it: an integer 1 .. CONTOURS_MAX_RADIUS, else ValueError (a bool, a float and a string are refused whatever they hold)."""
+    return _contour_integer(radius, "the radius", 1, CONTOURS_MAX_RADIUS)
 
 
 def blob_threshold(threshold):
@@ -798,6 +827,11 @@ class SimGranulometryResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64)]
 
 
+class SimContoursResult(C.Structure):
+    """musica_sim_contours_result: where a query's table and byte plane lie, the sizes of its two contour sets and its pixels."""
+    _fields_ = [("table_offset", C.c_uint64), ("contour_a", C.c_uint64), ("contour_b", C.c_uint64), ("pixels", C.c_uint64), ("plane_offset", C.c_uint64)]
+
+
 class SimBlobsResult(C.Structure):
     """musica_sim_blobs_result: where a query's table and label plane lie, its counts and its largest component."""
     _fields_ = [("table_offset", C.c_uint64), ("label_offset", C.c_uint64), ("pixels", C.c_uint64), ("changed", C.c_uint64), ("components", C.c_uint64),
@@ -1030,6 +1064,7 @@ ABI = {
     "musica_sim_spectrum": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimSpectrumResult), C.POINTER(C.c_int64), C.c_uint64]),
     "musica_sim_cooccurrence": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimCooccurrenceResult), _U32P, C.c_uint64]),
     "musica_sim_granulometry": (C.c_int, [_VP, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimGranulometryResult), C.POINTER(C.c_uint64), C.c_uint64]),
+    "musica_sim_contours": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimContoursResult), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64]),
     "musica_sim_blobs": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimBlobsResult), C.POINTER(C.c_uint64), C.c_uint64, _U32P, C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
@@ -1516,7 +1551,7 @@ class MusicaProcessing:
         return out
 
     def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False, trail=()):
-        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _reach share: the refusals of sim_<name> before any call
+        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _contours / _reach share: the refusals of sim_<name> before any call
         (most: 1 .. most queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead`
         in front of the count and `trail` (blobs: the label plane and its length) behind the tables' length. Returns the results and the
         flat tables, `words` zeroed words of `dtype`."""
@@ -1684,6 +1719,29 @@ class MusicaProcessing:
         for r in res[:len(qs)]:
             at = int(r.table_offset)
             out.append({"table": tables[at:at + per].reshape(len(rs) + 1, 2, GRANULOMETRY_WORDS).copy(), "pixels": int(r.pixels)})
+        return out
+
+    def sim_contours(self, queries, threshold, radius, planes=False):
+        """metrics.contour_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 1, 1 .. CONTOURS_MAX_QUERIES of them, all in one call; threshold 1 .. 1 300 500 (contour_threshold) and
+        radius 1 .. 32 (contour_radius): ValueError before any call, as for a count out of range. Returns one dict per query, the same
+        as contour_statistics': "table", a (2, R^2 + 2) uint64 array [direction a -> b = 0, b -> a = 1][d^2, "far" last], the Python
+        ints "contour_a", "contour_b" and "pixels" and, with planes=True, "planes", the (h, w) uint8 plane with bit 0 = a's contour
+        and bit 1 = b's."""
+        tau, R = contour_threshold(threshold), contour_radius(radius)
+        qs = _queries(queries)
+        per = 2 * (R * R + 2)
+        plane = np.zeros(max(sum(int(q.w) * int(q.h) for q in qs), 1), dtype=np.uint8) if planes else None
+        res, tables = self._sim_tables("contours", qs, SimContoursResult, np.uint64, len(qs) * per, tau, R, most=CONTOURS_MAX_QUERIES,
+                                       trail=(plane.ctypes.data_as(C.POINTER(C.c_uint8)), len(plane)) if planes else (None, 0))
+        out = []
+        for q, r in zip(qs, res):
+            at = int(r.table_offset)
+            d = {"table": tables[at:at + per].reshape(2, R * R + 2).copy(), "contour_a": int(r.contour_a), "contour_b": int(r.contour_b), "pixels": int(r.pixels)}
+            if planes:
+                lo = int(r.plane_offset)
+                d["planes"] = plane[lo:lo + int(q.w) * int(q.h)].reshape(int(q.h), int(q.w)).copy()
+            out.append(d)
         return out
 
     def sim_reach(self, queries, radii):

@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from . import processing as mp
-from .metrics import BLOB_KEYS, COOCCURRENCE_FEATURES, GRANULOMETRY_CLASS_KEYS, GRANULOMETRY_KEYS, GRANULOMETRY_POLARITIES, SPECTRUM_BAND_KEYS, SPECTRUM_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
+from .metrics import BLOB_KEYS, CONTOUR_DIRECTIONS, CONTOUR_DIRECTION_KEYS, CONTOUR_KEYS, COOCCURRENCE_FEATURES, GRANULOMETRY_CLASS_KEYS, GRANULOMETRY_KEYS, GRANULOMETRY_POLARITIES, SPECTRUM_BAND_KEYS, SPECTRUM_KEYS, DETAIL_ROW_KEYS, DETAIL_ROW_STATS, EDGE_ROW_KEYS, EDGE_ROW_STATS, GRADIENT_KEYS, GRATING_ROW_KEYS, GRATING_ROW_STATS, LATTICE_AXIS_KEYS, LATTICE_PERIODS, LEVEL_KEYS, OBSERVER_CHANNELS, ORDER_KEYS, POINT_CSV_HEADER, POINT_KEYS, PROFILE_AXES, PROFILE_KEYS, REACH_KEYS, SHIFT_KEYS, WARP_TRACKING_KEYS, displacement_maps, ensemble_maps, nps_map, observer_curve, reach_maps
 
 # ---- the CSV files' headers ---------------------------------------------------------------------
 CSV_HEADER = ['raw file', 'alteration', 'altered vs unaltered mse', 'altered vs unaltered ssim', 'altered vs unaltered histogram distance',
@@ -63,6 +63,12 @@ TEXTURE_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'levels', 'distanc
 # radius, without an element) last; the class's numbers, then the polarity's, the same on each of its lines
 GRANULOMETRY_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'pixels', 'polarity', 'class', 'radius', 'side', 'sum a', 'sum b'] + \
                           [k.replace('_', ' ') for k in GRANULOMETRY_CLASS_KEYS + GRANULOMETRY_KEYS]
+
+# contour_robustness.csv: one line per row, comparison the row has and direction (a_to_b: the output's contour pixels by their distance
+# to the reference's; b_to_a: the reference's by their distance to the output's); the direction's numbers, then the comparison's, the
+# same on both of its lines
+CONTOUR_CSV_HEADER = ['raw file', 'alteration', 'comparison', 'pixels', 'threshold', 'radius', 'direction'] + \
+                     [k.replace('_', ' ') for k in CONTOUR_DIRECTION_KEYS + CONTOUR_KEYS]
 
 ENSEMBLE_CSV_NAMES = (("mean_shift", "mean shift"), ("bias_rms", "bias rms"), ("noise_rms", "noise rms"), ("bias_fraction", "bias fraction"), ("mse", "mse"))
 ENSEMBLE_CSV_METRICS = ("mse", "ssim", "histogram intersection", "histogram distance", "histogram bhattacharyya")   # SIM_METRICS' order
@@ -266,6 +272,14 @@ def _granulometry_lines(t):
     return lines
 
 
+def _contour_lines(t):
+    """A line per direction: the pixels, the threshold, the radius, the direction, its found and far pixels and the mean, median and
+    95th percentile of the distance over the found ones, then the comparison's sizes, densities, ratio, figure of merit, kept, moved,
+    lost and spurious shares and Hausdorff distance."""
+    totals = [_blank(t[k]) for k in CONTOUR_KEYS]
+    return [[t["pixels"], t["threshold"], t["radius"], d] + [_blank(t[d][k]) for k in CONTOUR_DIRECTION_KEYS] + totals for d in CONTOUR_DIRECTIONS]
+
+
 # The files of the comparison metrics (harness.ROW_METRICS), by key suffix: a study that has direct_<suffix> gets the file.
 # per "row": one line per row, header(with_reference), then cells(a group's value or None) for every group; per "comparison": one line
 # per row and comparison that the row has, the header as it stands, then cells(the value); per "band": the same with a line for each
@@ -281,6 +295,7 @@ METRIC_CSVS = {
     "spectrum": MetricCsv("spectrum_robustness.csv", "band", SPECTRUM_CSV_HEADER, _spectrum_lines),
     "texture": MetricCsv("texture_robustness.csv", "band", TEXTURE_CSV_HEADER, _texture_lines),
     "granulometry": MetricCsv("granulometry_robustness.csv", "band", GRANULOMETRY_CSV_HEADER, _granulometry_lines),
+    "contours": MetricCsv("contour_robustness.csv", "band", CONTOUR_CSV_HEADER, _contour_lines),
 }
 
 
@@ -362,6 +377,13 @@ def write_studies_csvs(studies, out_dir, mean_cnr=True):
     it, the exact sums of A and B, the pattern-spectrum shares of either side, gain, coherence and mse (empty for the residue), then
     the polarity's mean element sides, their shift, the slope of log gain on log side and the residue's shift, the same on each of its
     lines.
+
+    Studies run with contours=tau (rows[0] has "direct_contours") also get contour_robustness.csv (CONTOUR_CSV_HEADER): one line per
+    row, the unaltered one included, comparison that the row has and direction (a_to_b: the output's contour pixels by their distance
+    to the reference's, b_to_a the other way round): the comparison's name, its pixels, the threshold, the radius, the direction, its
+    found and far pixels, the mean, median and 95th percentile of the distance over the found ones, then the sizes, densities and ratio
+    of the two contours, Pratt's figure of merit, the kept, moved and lost shares of the reference's contour, the spurious share of the
+    output's and the Hausdorff distance, the same on both of its lines.
 
     Studies run with ensemble=K (rows[0] has "ensemble") also get ensemble.csv (ENSEMBLE_CSV_HEADER): one line per noise row, K, the
     mean shift, bias rms, noise rms, bias fraction and mse of the direct and of the registered ensemble (empty without one), then the mean
@@ -495,6 +517,18 @@ def write_reach_maps(studies, out_dir):
     output pixel (class 0 white, the last class black), and <raw>_<alteration>_reach_rmse.bmp, the per-class rmse as bars. Returns the
     paths written."""
     return _write_maps(studies, out_dir, _reach_images)
+
+
+def _contour_images(r):
+    d = r.get("registered_contours")
+    return () if d is None or "planes" not in d else (("contours", (np.asarray(d["planes"], dtype=np.uint8) & 3) * 85),)
+
+
+def write_contour_maps(studies, out_dir):
+    """One 8-bit BMP per registered row of studies run with contour_maps: <raw>_<alteration>_contours.bmp, the two contours of the
+    registered comparison: 85 where only the output has a contour pixel, 170 where only the reference has one, 255 where both have.
+    Returns the paths written."""
+    return _write_maps(studies, out_dir, _contour_images)
 
 
 def write_ensemble_maps(studies, out_dir):
