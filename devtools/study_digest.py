@@ -55,7 +55,10 @@ seeded phantoms; the shapes are the smallest at which the kernels can still go w
     one-pixel column and a single pixel; integers only;
   * the contours at N = 151 of other images' outputs against slot 0, at the threshold 4096 with the radius 16 and at 1 with 32, tables,
     set sizes and byte planes: the full frame (131 x 131: 3 x 3 tiles with a three-pixel ragged tail), a ragged region from mid-tile
-    with different origins on the two sides, a one-pixel column (no contour) and a single pixel; integers only.
+    with different origins on the two sides, a one-pixel column (no contour) and a single pixel; integers only;
+  * the Minkowski cell histograms at N = 151 of other images' outputs against slot 0: the full frame (131 x 131: 3 x 3 tiles with a
+    three-pixel ragged tail), a ragged region from mid-tile with different origins on the two sides, a one-pixel column (no horizontal
+    interior edge) and a single pixel (three empty kinds); integers only.
 Prints one JSON line {entry point: sha256}. Run it on two trees and compare the lines; the digests pin nothing from version to version
 (the ABI does not promise f64 bits), so they are not committed as goldens.
   python devtools/study_digest.py [--tree DIR]      # DIR: the checkout whose package is imported (default: this one)"""
@@ -211,5 +214,8 @@ if hasattr(p, "sim_granulometry"):   # likewise a --tree from before the size me
 if hasattr(p, "sim_contours"):   # likewise a --tree from before the contour metric
     qs = [(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 1, NW - 1), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)]
     note("musica_sim_contours", [p.sim_contours(qs, 4096, 16, planes=True), p.sim_contours(qs, 1, 32, planes=True)])
+if hasattr(p, "sim_minkowski"):   # likewise a --tree from before the shape metric
+    qs = [(1, 0, 0, 0, 0, 0, NW, NW), (1, 0, 40, 33, 38, 29, 70, 75), (2, 0, 64, 0, 63, 1, 1, NW - 1), (1, 0, NW - 1, NW - 1, 0, 0, 1, 1)]
+    note("musica_sim_minkowski", [p.sim_minkowski(qs)])
 p.cleanup()
 print(json.dumps(digests))

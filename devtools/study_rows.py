@@ -6,11 +6,11 @@ two trees bit for bit: what a change of harness.py or report.py must leave alone
   * alterations   harness.Runner with device_alterations at N = 151, with ensemble=3 and covariance=2 and their tile tables.
 Every study has one value per grid of the reference's alterations, a d4, blur, zoom, scatter, warp and codec row, one grid or spec of
 every patch relation with its *_tables flag on and the observer, a vendor image, tone, scales=2, gradients, order, lattice=8, blobs=3,
-spectrum=8, texture=8 (distances 1, 3), granulometry=(1, 3), contours=900 (radius 5), reach with its tables and maps, and displacement=2 with its tile tables. An option that the tree's run_study does not have
+spectrum=8, texture=8 (distances 1, 3), granulometry=(1, 3), contours=900 (radius 5), minkowski with its curves, reach with its tables and maps, and displacement=2 with its tile tables. An option that the tree's run_study does not have
 yet is left out, and --off leaves options out by name: what remains compares with a tree from before them.
 Prints one JSON line {path: {"rows": {alteration: {key: sha256}}, "keys": the rows' keys in order, "csv": {file: sha256}}}. Run it on two trees on one machine and
 compare the lines; the digests pin nothing from version to version (the ABI does not promise f64 bits), so they are not committed.
-  python devtools/study_rows.py [--tree DIR] [--paths host,metrics,alterations] [--off spectrum,texture,texture_distances,granulometry,contours,contour_radius]   # DIR: the checkout whose package is imported"""
+  python devtools/study_rows.py [--tree DIR] [--paths host,metrics,alterations] [--off spectrum,texture,texture_distances,granulometry,contours,contour_radius,minkowski,minkowski_curves]   # DIR: the checkout whose package is imported"""
 import argparse
 import hashlib
 import inspect
@@ -88,7 +88,7 @@ def study(path):
         scatters=[H.SCATTERS(n)[0]], warps=H.WARPS(n)[:1], codecs=[64], details=[H.detail_grid(n, 8)], detail_tables=True, observer=True,
         edges=[H.edge_grid(n, 8)], edge_tables=True, gratings=[H.grating_grid(n, 8)], grating_tables=True, gains=H.GAINS(n)[:1], gain_tables=True,
         luts=H.LUTS(image)[:1], lut_tables=True, points=[H.point_grid(n, 64)], point_tables=True, tone=True, scales=2, gradients=True, order=True,
-        lattice=8, blobs=3, spectrum=8, texture=8, texture_distances=(1, 3), granulometry=(1, 3), contours=900, contour_radius=5, reach=True, reach_tables=True, reach_maps=True, displacement=2, displacement_tiles=True)
+        lattice=8, blobs=3, spectrum=8, texture=8, texture_distances=(1, 3), granulometry=(1, 3), contours=900, contour_radius=5, minkowski=True, minkowski_curves=True, reach=True, reach_tables=True, reach_maps=True, displacement=2, displacement_tiles=True)
     for name in list(options):
         if name not in inspect.signature(H.run_study).parameters or name in args.off.split(","):
             del options[name]

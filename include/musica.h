@@ -1335,6 +1335,53 @@ typedef struct musica_sim_contours_result {
 int musica_sim_contours(musica_ctx* ctx, uint32_t threshold, uint32_t radius, uint32_t count, const musica_sim_query* queries,
                         musica_sim_contours_result* results, uint64_t* tables, uint64_t table_words, uint8_t* planes, uint64_t plane_bytes);
 
+/* ---- minkowski: the Minkowski functionals of the level sets of a comparison (new, not in the reference) ----
+ * What does the gray-level landscape of the output look like as a shape: did the processing break one bright structure into islands,
+ * punch holes into solid ones, lengthen the iso-contours? The answer is the three Minkowski functionals of every threshold set
+ * {v >= t}: area, perimeter and Euler characteristic (components minus holes); by Hadwiger's theorem there is no fourth additive,
+ * motion-invariant, continuous measure of a planar set. All of them, at all 255 thresholds, follow from the cell histograms that this
+ * call returns. metrics.minkowski_statistics is the contract. Queries are musica_sim_compare's with w, h >= 1, at most
+ * MUSICA_MINKOWSKI_MAX_QUERIES (a row's direct, registered and two vendor comparisons). The region is its own domain: pixels outside
+ * it do not exist and nothing outside it is read. A side is a uint8 plane over the region: side 0 the graded plane of the query's image
+ * quantised as musica_sim_compare quantises it, side 1 the query's reference slot, side 2 their pixel-wise minimum, whose upper sets
+ * are the intersections of the two sides' upper sets. Query i gets MUSICA_MINKOWSKI_SIDES * MUSICA_MINKOWSKI_KINDS * 256 uint32_t
+ * in the flat `tables`, from results[i].table_offset (in words) on, indexed [side][kind][v]: the number of cells of that kind whose
+ * value is v. The kinds, their cells, their number and a cell's value:
+ *   0 face     the pixels                                                   w h                the pixel
+ *   1 any_h    the edges between horizontal neighbours, the two outline     h (w + 1)          the maximum of the 1 or 2 incident
+ *              columns included                                                                pixels that exist
+ *   2 any_v    the edges between vertical neighbours, the two outline       (h + 1) w          likewise
+ *              rows included
+ *   3 any_x    all pixel corners                                            (h + 1) (w + 1)    the maximum of the 1, 2 or 4 incident
+ *                                                                                              pixels that exist
+ *   4 all_h    the interior edges between horizontal neighbours             h (w - 1)          the minimum of the two
+ *   5 all_v    the interior edges between vertical neighbours               (h - 1) w          the minimum of the two
+ *   6 all_x    the interior corners                                         (h - 1) (w - 1)    the minimum of the four
+ *   7 outline  the region's outline edges                                   2 w + 2 h          their one pixel (a corner pixel counts
+ *                                                                                              twice, a 1 x 1 region's pixel four times)
+ * Nothing is cumulated. On the closed cubical complex a cell belongs to the set at t iff the maximum of its incident pixels is >= t,
+ * on the open complex iff their minimum is, so with N_k(t) the sum of row k over v >= t: area = N0; perimeter = N1 + N2 - N7 - N4 - N5,
+ * the interior edges with exactly one side in the set (the crop is not charged); the Euler characteristic with 8-connected components
+ * and 4-connected holes = N3 - N1 - N2 + N0, the one with 4-connected components and 8-connected holes = N0 - N4 - N5 + N6; the
+ * outline edges that the set touches = N7 (metrics.minkowski_curves). results[i].pixels = w * h. Identities: every [side][kind] row
+ * sums to the number of its cells above (a 1 x 1 region has three empty kinds); the sum over t >= 1 of the area is the sum of the
+ * pixels, of the perimeter the sum of |differences| of horizontal and vertical neighbours; side 2's face row is the histogram of
+ * min(a, b). Everything is an integer: the tables equal the restatement word for word and repeat from call to call, whatever
+ * MUSICA_MINKOWSKI_GROUPS (the workgroups of a query's side, read at every call; 0: the launch's own choice) says. Every word of the
+ * tables is written and nothing behind them. Synchronous, on the context's stream after whatever was enqueued there; changes no
+ * slot, no result of a step and no input image; scratch is allocated on first use. Refused: what musica_sim_compare refuses (with
+ * the smallest side 1 and at most MUSICA_MINKOWSKI_MAX_QUERIES queries, none included), then a NULL `tables` and table_words below
+ * the tables' words; all before any launch or copy, `tables` untouched. After a refusal the context stays usable. */
+#define MUSICA_MINKOWSKI_MAX_QUERIES 4
+#define MUSICA_MINKOWSKI_KINDS 8
+#define MUSICA_MINKOWSKI_SIDES 3
+typedef struct musica_sim_minkowski_result {
+    uint64_t table_offset;          /* where the query's table starts in `tables`, in words */
+    uint64_t pixels;                /* w * h */
+} musica_sim_minkowski_result;
+int musica_sim_minkowski(musica_ctx* ctx, uint32_t count, const musica_sim_query* queries, musica_sim_minkowski_result* results,
+                         uint32_t* tables, uint64_t table_words);
+
 /* ---- reach: the change of the output by the distance from the changed input (new, not in the reference) ----
  * The locality relation: a change of the input inside a set changes the output only near that set. Two effects carry a local change
  * outwards: the pyramid's footprints (a level-i band reaches about 2^(i + 2) pixels and dies off with distance) and the global

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmusica_hip.so")
 CLI = os.path.join(HERE, "musica-standalone")
 HIP_SOURCES = ["kernels_pyramid.hip", "kernels_expand_sd.hip", "kernels_analysis.hip", "kernels_gradation.hip", "kernels_clahe.hip", "kernels_bench.hip",
-               "kernels_similarity.hip", "kernels_joint.hip", "kernels_displace.hip", "kernels_scales.hip", "kernels_ensemble.hip", "kernels_covariance.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_blur.hip", "kernels_codec.hip", "kernels_zoom.hip", "kernels_scatter.hip", "kernels_warp.hip", "kernels_details.hip", "kernels_edges.hip", "kernels_gratings.hip", "kernels_points.hip", "kernels_gain.hip", "kernels_levels.hip", "kernels_gradients.hip", "kernels_order.hip", "kernels_lattice.hip", "kernels_blobs.hip", "kernels_spectrum.hip", "kernels_cooccurrence.hip", "kernels_granulometry.hip", "kernels_contours.hip", "kernels_reach.hip", "kernels_observer.hip", "kernels_export.hip", "musica_ctx.hip", "musica_step.hip", "musica_pipeline.hip", "musica_study.hip"]
+               "kernels_similarity.hip", "kernels_joint.hip", "kernels_displace.hip", "kernels_scales.hip", "kernels_ensemble.hip", "kernels_covariance.hip", "kernels_alteration.hip", "kernels_symmetry.hip", "kernels_blur.hip", "kernels_codec.hip", "kernels_zoom.hip", "kernels_scatter.hip", "kernels_warp.hip", "kernels_details.hip", "kernels_edges.hip", "kernels_gratings.hip", "kernels_points.hip", "kernels_gain.hip", "kernels_levels.hip", "kernels_gradients.hip", "kernels_order.hip", "kernels_lattice.hip", "kernels_blobs.hip", "kernels_spectrum.hip", "kernels_cooccurrence.hip", "kernels_granulometry.hip", "kernels_contours.hip", "kernels_minkowski.hip", "kernels_reach.hip", "kernels_observer.hip", "kernels_export.hip", "musica_ctx.hip", "musica_step.hip", "musica_pipeline.hip", "musica_study.hip"]
 CPP_SOURCES = ["musica_io.cpp"]
 HEADERS = ["musica_device.h", "kernels_common.h", "exact_math.h", "curve_lut.h", "sdev_parts.h", "grad_parts.h", "launchers.h", "pyramid_march.h", "study_device.h", "musica_ctx.h", os.path.join("..", "..", "include", "musica.h")]
 NO_SLP = {"kernels_analysis.hip", "kernels_expand_sd.hip"}   # kernels_expand_sd.hip: the pyramid launches that keep a window of squares in registers (SD expand, level 0's histogram march, the paired launch)

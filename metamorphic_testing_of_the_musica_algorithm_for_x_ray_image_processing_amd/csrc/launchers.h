@@ -627,6 +627,27 @@ inline int contours_groups(int tiles, int most = 0) {
 // caller, with u64 atomics
 void launch_sim_contours(hipStream_t st, const ContourQueryDev* d_qs, int count, int max_tiles, int max_groups, uint32_t threshold, int radius,
                          unsigned long long* bits, unsigned long long* counts, uint8_t* planes, unsigned long long* tables);
+// kernels_minkowski.hip: the shape metric. One comparison of musica_sim_minkowski: tiles_x / tiles_y: its region's 64 x 64 tiles;
+// groups: the persistent workgroups that share the tiles of ONE side (minkowski_groups); table: where its
+// kMinkowskiSides * kMinkowskiKinds * 256 words start in the launch's flat tables, in words.
+constexpr int kMinkowskiMaxQueries = 4;   // MUSICA_MINKOWSKI_MAX_QUERIES
+constexpr int kMinkowskiKinds = 8;        // MUSICA_MINKOWSKI_KINDS
+constexpr int kMinkowskiSides = 3;        // MUSICA_MINKOWSKI_SIDES
+struct MinkowskiQueryDev : SimRegion {
+    int tiles_x, tiles_y, groups;
+    unsigned long long table;
+};
+// The workgroups that one side of a query of `tiles` tiles gets: min(tiles, want), where want is kMinkowskiGroups, or `most` where
+// 0 < most < want (the tuning variable MUSICA_MINKOWSKI_GROUPS, read at every call): the tables do not depend on it, a workgroup's
+// u32 counters hold any number of tiles (kernels_minkowski.hip, THE WIDTH RULE). A launch has three times as many workgroups a query.
+constexpr int kMinkowskiGroups = 256;
+inline int minkowski_groups(int tiles, int most = 0) {
+    const int want = most > 0 && most < kMinkowskiGroups ? most : kMinkowskiGroups;
+    return tiles < want ? tiles : want;
+}
+// metrics.minkowski_statistics over `count` queries (grid.x = max_groups, the largest `groups`, at least 1; grid.y = the three sides).
+// tables: every query's words, zeroed by the caller: the workgroups add into them with u32 atomics
+void launch_sim_minkowski(hipStream_t st, const MinkowskiQueryDev* d_qs, int count, int max_groups, uint32_t* tables);
 // kernels_reach.hip: the reach metric. The class of a pixel of the n x n input plane is the first radius of an ascending list whose
 // Chebyshev box around the pixel holds a changed input pixel (metrics.reach_classes); a comparison's exact sums are kept apart by it.
 constexpr int kReachMaxRadii = 32;        // MUSICA_REACH_MAX_RADII

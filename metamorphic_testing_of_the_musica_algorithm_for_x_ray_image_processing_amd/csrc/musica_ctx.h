@@ -208,6 +208,9 @@ struct StudyState {
     size_t contour_bits_cap = 0;
     uint8_t* d_contour_planes = nullptr;                      // contour_plane_cap bytes: only calls that ask for the byte planes
     size_t contour_plane_cap = 0;
+    // musica_sim_minkowski: the queries and the flat tables
+    MinkowskiQueryDev* d_minkowski_q = nullptr;               // [MUSICA_MINKOWSKI_MAX_QUERIES]
+    uint32_t* d_minkowski_tables = nullptr;                   // [MUSICA_MINKOWSKI_MAX_QUERIES][SIDES][KINDS][256], allocated by the first musica_sim_minkowski
     // musica_sim_reach / musica_sim_reach_classes: the radii, the queries, the flat tables and the class plane. The summed-area table
     // of the change mask lives in d_scatter: every call that uses that plane fills it itself and is done with it when it returns.
     uint32_t* d_reach_radii = nullptr;             // [MUSICA_REACH_MAX_RADII], allocated by the first call of either

@@ -2,7 +2,7 @@
 // the ensemble accumulators (musica_sim_ensemble_*) and the alterations of the input (musica_alter_*). Their kernels: kernels_similarity.hip,
 // kernels_joint.hip, kernels_displace.hip, kernels_scales.hip, kernels_ensemble.hip, kernels_covariance.hip, kernels_alteration.hip,
 // kernels_symmetry.hip, kernels_blur.hip, kernels_codec.hip, kernels_zoom.hip, kernels_scatter.hip, kernels_warp.hip and, each with a measurement and an alteration,
-// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip, kernels_granulometry.hip, kernels_contours.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
+// kernels_details.hip, kernels_edges.hip, kernels_gratings.hip, kernels_points.hip, kernels_gain.hip, kernels_levels.hip, kernels_gradients.hip, kernels_order.hip, kernels_lattice.hip, kernels_blobs.hip, kernels_spectrum.hip, kernels_cooccurrence.hip, kernels_granulometry.hip, kernels_contours.hip, kernels_minkowski.hip and kernels_reach.hip, and the measurement of kernels_observer.hip. Their state is musica_ctx::study; the pipeline
 // (musica_ctx.hip, musica_step.hip) knows none of it. Calls of one kind share a host frame: sim_derive_slot (a slot made from a slot),
 // sim_patch_list (the list measurements), sim_query_tables (the table comparisons) and alter_into (the alterations with an entry point).
 #include <math.h>
@@ -413,7 +413,7 @@ static void sim_region(const musica_ctx* c, const musica_sim_query& q, SimRegion
     d.h = (int)q.h;
 }
 
-// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _contours / _reach) -----------------------------------------------
+// ---- the table comparisons (musica_sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _contours / _minkowski / _reach) -----------------------------------------------
 // Where a table call keeps its queries and its flat tables in musica_ctx::study, and what it takes: at most `most` queries with sides
 // of at least `min_side`. The tables' buffer holds `tables_cap` words from the first call on; where `grown` names its capacity it
 // holds the words of the largest call so far instead.
@@ -435,6 +435,7 @@ constexpr TableBuffers<SpectrumQueryDev, unsigned long long> kSpectrumBuffers{&S
 constexpr TableBuffers<CooccurrenceQueryDev, uint32_t> kCooccurrenceBuffers{&StudyState::d_cooccurrence_q, &StudyState::d_cooccurrence_tables, MUSICA_COOCCURRENCE_MAX_QUERIES, 1, (size_t)MUSICA_COOCCURRENCE_MAX_QUERIES * MUSICA_COOCCURRENCE_MAX_DISTANCES * 4 * 2 * kCooccurrenceMaxLevels * kCooccurrenceMaxLevels};
 constexpr TableBuffers<GranulometryQueryDev, unsigned long long> kGranulometryBuffers{&StudyState::d_granulometry_q, &StudyState::d_granulometry_tables, MUSICA_GRANULOMETRY_MAX_QUERIES, 1, (size_t)MUSICA_GRANULOMETRY_MAX_QUERIES * (MUSICA_GRANULOMETRY_MAX_RADII + 1) * 2 * kGranulometryWords};
 constexpr TableBuffers<ContourQueryDev, unsigned long long> kContourBuffers{&StudyState::d_contour_q, &StudyState::d_contour_tables, MUSICA_CONTOURS_MAX_QUERIES, 1, (size_t)MUSICA_CONTOURS_MAX_QUERIES * 2 * (MUSICA_CONTOURS_MAX_RADIUS * MUSICA_CONTOURS_MAX_RADIUS + 2)};
+constexpr TableBuffers<MinkowskiQueryDev, uint32_t> kMinkowskiBuffers{&StudyState::d_minkowski_q, &StudyState::d_minkowski_tables, MUSICA_MINKOWSKI_MAX_QUERIES, 1, (size_t)MUSICA_MINKOWSKI_MAX_QUERIES * MUSICA_MINKOWSKI_SIDES * MUSICA_MINKOWSKI_KINDS * 256};
 constexpr TableBuffers<ReachQueryDev, unsigned long long> kReachBuffers{&StudyState::d_reach_q, &StudyState::d_reach_tables, MUSICA_REACH_MAX_QUERIES, 1, (size_t)MUSICA_REACH_MAX_QUERIES * (MUSICA_REACH_MAX_RADII + 1) * kReachWords};
 
 // What a call's place() says of one query: its tiles or chunks (the launch's grid.x is the largest) and the words of its table.
@@ -1514,6 +1515,24 @@ int musica_sim_contours(musica_ctx* c, uint32_t threshold, uint32_t radius, uint
     }
     return 1;
     ABI_CATCH("musica_sim_contours")
+}
+
+// ---- the level sets of a comparison (musica_sim_minkowski, include/musica.h; kernels_minkowski.hip) --------------------------------------
+static_assert(kMinkowskiMaxQueries == MUSICA_MINKOWSKI_MAX_QUERIES && kMinkowskiKinds == MUSICA_MINKOWSKI_KINDS && kMinkowskiSides == MUSICA_MINKOWSKI_SIDES,
+              "kernels_minkowski.hip's constants are include/musica.h's");
+
+int musica_sim_minkowski(musica_ctx* c, uint32_t count, const musica_sim_query* qs, musica_sim_minkowski_result* out, uint32_t* tables, uint64_t table_words) {
+    ABI_TRY
+    return sim_query_tables(
+        c, "musica_sim_minkowski", kMinkowskiBuffers, count, qs, out, tables, table_words, nothing,
+        [&](const musica_sim_query& q, MinkowskiQueryDev& d) {
+            d.groups = minkowski_groups(tile_grid(d, q.w, q.h), env_int("MUSICA_MINKOWSKI_GROUPS", 0));
+            return TablePlace{d.groups, (size_t)kMinkowskiSides * kMinkowskiKinds * 256};
+        },
+        nothing,
+        [&](const MinkowskiQueryDev* d_qs, int max_groups, uint32_t* d_tables) { launch_sim_minkowski(c->stream, d_qs, (int)count, max_groups, d_tables); },
+        nothing, [&](uint32_t i, const musica_sim_query& q, const uint32_t*) { out[i].pixels = (uint64_t)q.w * q.h; });
+    ABI_CATCH("musica_sim_minkowski")
 }
 
 // ---- the reach of a change of the input (musica_sim_reach / musica_sim_reach_classes, include/musica.h; kernels_reach.hip) --------------

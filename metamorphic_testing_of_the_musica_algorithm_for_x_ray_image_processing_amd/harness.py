@@ -1082,7 +1082,7 @@ STUDY_METRICS = COMPARISON_METRICS + (
                      METRIC_CSVS["texture"]),
 )
 # STUDY_METRICS is the eight entries above and ends with the texture: tests/test_cooccurrence_restatement.py holds it to that. The
-# study, its checks, its key groups, the command line and the report walk ROW_METRICS, to which the next metric is appended.
+# granulometry and the contours are appended in ROW_METRICS, which tests/test_contours_restatement.py holds to end with the contours.
 ROW_METRICS = STUDY_METRICS + (
     ComparisonMetric("granulometry", "granulometry", lambda v: v is not None, lambda v: None if v is None else mp.granulometry_radii(v),
                      lambda opt, out, plane, region: granulometry_row(granulometry_statistics(out, plane, [region], opt.granulometry)[0], opt.granulometry),
@@ -1094,6 +1094,16 @@ ROW_METRICS = STUDY_METRICS + (
                      lambda proc, queries, opt: [contour_row(r, opt.contours, opt.contour_radius)
                                                  for r in proc.sim_contours(queries, opt.contours, opt.contour_radius, planes=opt.contour_maps)],
                      METRIC_CSVS["contours"]),
+)
+# ROW_METRICS is the ten entries above and ends with the contours: tests/test_contours_restatement.py holds it to that. The study, its
+# checks, its key groups, the command line and the report walk SCORED_METRICS (and report.SCORED_CSVS), the same table with the metrics
+# added since appended, in scoring order. The tests of a new metric hold this table by MEMBERSHIP AND PREFIX (ROW_METRICS is its prefix;
+# exactly one entry has the metric's option), never by its last element: the next metric is appended HERE and nothing is renamed again.
+SCORED_METRICS = ROW_METRICS + (
+    ComparisonMetric("minkowski", "minkowski", bool, _checked_flag("minkowski"),
+                     lambda opt, out, plane, region: minkowski_row(minkowski_statistics(out, plane, [region])[0], opt.minkowski_curves),
+                     lambda proc, queries, opt: [minkowski_row(r, opt.minkowski_curves) for r in proc.sim_minkowski(queries)],
+                     SCORED_CSVS["minkowski"]),
 )
 TONE_KEYS, SCALE_ROW_KEYS, GRADIENT_ROW_KEYS, ORDER_ROW_KEYS, LATTICE_ROW_KEYS, BLOB_ROW_KEYS = \
     ({c: "%s_%s" % (c, m.suffix) for c in COMPARED} for m in COMPARISON_METRICS[:6])   # comparison -> its sibling key, of the metrics that tests ask by name
@@ -1168,7 +1178,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
                   scales, ensemble, ensemble_tiles, covariance, covariance_tiles, blurs, zooms=None, scatters=None, details=None,
                   detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False, gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None,
                   gradients=False, points=None, point_tables=False, reach=None, reach_tables=False, reach_maps=False, observer=False, codecs=None,
-                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, contours=None, contour_radius=mp.CONTOURS_RADIUS, contour_maps=False, order=False):
+                  lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, contours=None, contour_radius=mp.CONTOURS_RADIUS, contour_maps=False, minkowski=False, minkowski_curves=False, order=False):
     """run_study's arguments for a raw image of side n, checked in this order before any work (ValueError; the runner is only asked for
     its device_alterations) and normalised: a namespace of them, the grids' defaults filled in, plus `keys` (the keys of a row, in
     order) and `device_alterations`."""
@@ -1181,7 +1191,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     o["displacement"] = displacement = int(displacement)
     if displacement and not 1 <= displacement <= mp.SIM_MAX_RADIUS:
         raise ValueError("displacement radius %d is not in 1 .. %d" % (displacement, mp.SIM_MAX_RADIUS))
-    for m in ROW_METRICS:
+    for m in SCORED_METRICS:
         if m.option in CHECKED_EARLY:
             o[m.option] = m.check(o[m.option])
     o["observer"] = _checked_flag("observer")(observer)
@@ -1201,7 +1211,7 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
         raise ValueError("covariance is taken over the realisations of an ensemble: give ensemble > 0")
     for m in MOVED:
         o[m.option] = m.check(o[m.option] or (), n)
-    for m in ROW_METRICS:
+    for m in SCORED_METRICS:
         if m.option not in CHECKED_EARLY:
             o[m.option] = m.check(o[m.option])
     if blob_connectivity not in (4, 8) or isinstance(blob_connectivity, (bool, np.bool_)):
@@ -1210,18 +1220,19 @@ def study_options(n, runner, shutters, translations, rotations, sigmas, factors,
     o["texture_distances"] = mp.cooccurrence_distances(texture_distances)
     o["contour_radius"] = mp.contour_radius(contour_radius)
     o["contour_maps"] = _checked_flag("contour_maps")(contour_maps)
+    o["minkowski_curves"] = _checked_flag("minkowski_curves")(minkowski_curves)
     for rel in RELATIONS:
         if o[rel.option] is not None:
             o[rel.option] = rel.check(o[rel.option], n)
     for g in (o["details"] if observer else ()):   # the views and banks of every grid, as the measurement will take them
         mp.view_list(*observer_views(output_details(g)), n - 2 * PROCESSING_MARGIN)
     compared = COMPARED[:2 if vendor is None else 4]
-    groups = {m.suffix: tuple("%s_%s" % (c, m.suffix) for c in compared) if m.on(o[m.option]) else () for m in ROW_METRICS}
+    groups = {m.suffix: tuple("%s_%s" % (c, m.suffix) for c in compared) if m.on(o[m.option]) else () for m in SCORED_METRICS}
     groups.update(shift=("direct_shift", "registered_shift") if displacement else (), reach=("direct_reach",) if o["reach"] is not None else (),
                   ensemble=("ensemble",) if ensemble else (), relations=tuple(rel.key for rel in RELATIONS if o[rel.option] is not None),
                   observer=("observer",) if observer else (), warp=("warp",) if o["warps"] else ())
     keys = ("alteration", "direct", "registered", "mean_cnr") + compared[2:] + \
-           tuple(k for g in KEY_GROUPS + tuple(m.suffix for m in ROW_METRICS if m.suffix not in KEY_GROUPS) for k in groups[g])
+           tuple(k for g in KEY_GROUPS + tuple(m.suffix for m in SCORED_METRICS if m.suffix not in KEY_GROUPS) for k in groups[g])
     for grid, default in (("shutters", scaled(SHUTTERS, n)), ("translations", scaled(TRANSLATIONS, n)), ("rotations", ROTATIONS),
                           ("sigmas", GAUSS_SIGMAS), ("factors", POISSON_FACTORS)):
         if o[grid] is None:
@@ -1285,7 +1296,7 @@ class Scorer:
     SLOT_ROTATED and SLOT_VENDOR_ROTATED; measure(relation, measured) gives the value of a patch relation's row key and
     observer(details) a cd_ row's "observer". similarities, score and shifts take the row's comparisons, (reference key, region) pairs
     with a SLOT_* number as the key, and return one result each: similarities the five SIM_METRICS, score(metric, comparisons) the
-    sibling values of one entry of ROW_METRICS, by the entry's host or device form, and shifts the displacement (the regions
+    sibling values of one entry of SCORED_METRICS, by the entry's host or device form, and shifts the displacement (the regions
     already inset; keep: the dicts carry their tile tables whatever displacement_tiles says, for a warp row's tracking). reach takes
     the row's direct comparison, behind similarities, and looks at the change of the input from `source`, the study's raw plane."""
 
@@ -1473,7 +1484,7 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
               tone=False, displacement=0, displacement_tiles=False, scales=0, ensemble=0, ensemble_tiles=False, covariance=0, covariance_tiles=False,
               blurs=None, zooms=None, scatters=None, details=None, detail_tables=False, edges=None, edge_tables=False, gratings=None, grating_tables=False,
               gains=None, gain_tables=False, luts=None, lut_tables=False, warps=None, gradients=False, points=None, point_tables=False, reach=None,
-              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, contours=None, contour_radius=mp.CONTOURS_RADIUS, contour_maps=False, order=False):
+              reach_tables=False, reach_maps=False, observer=False, codecs=None, lattice=0, blobs=None, blob_connectivity=8, spectrum=None, texture=None, texture_distances=mp.COOCCURRENCE_DISTANCES, granulometry=None, contours=None, contour_radius=mp.CONTOURS_RADIUS, contour_maps=False, minkowski=False, minkowski_curves=False, order=False):
     """The reference's per-image loop (script.py:383-657): returns a list of rows
     {alteration, direct: {...}, registered: {...} or None, mean_cnr}. With runner.device_metrics the similarities are computed
     on the device against the unaltered result kept in reference slot 0 (rotations: the rotated unaltered result in slot 1).
@@ -1787,7 +1798,20 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     the byte plane (bit 0: the output's contour, bit 1: the reference's) that report.write_contour_maps draws. On the device one
     musica_sim_contours call behind the granulometry's; on the host the restatement takes the same crops. The tables are integers and
     there is one summary function: the values are equal to the last bit on every path. With contours=None the rows and the launches
-    are exactly as before."""
+    are exactly as before.
+
+    minkowski: a flag (anything but a bool is refused) asks what the gray-level landscape of the output looks like as a shape: the three
+    Minkowski functionals, area, perimeter and Euler characteristic, of every threshold set {v >= t} of the output, of the reference
+    and of their pixel-wise minimum, from eight exact cell histograms a side (minkowski_statistics). Every comparison dict of a row
+    gains a sibling behind all other keys, the contours' included: direct_minkowski, registered_minkowski and, with a vendor image,
+    reference_minkowski and registered_reference_minkowski; present exactly where the original is, None where it is None. Each is
+    minkowski_row's dict: minkowski_summary's "pixels", per side the mean, the total variation "tv", the most "islands" and "holes"
+    with their levels and the outline "contact", "tv_gain", the normalised L1 distances of the four curves, the "overlap" of the upper
+    sets with its smallest level, the tone-free "matched" read-out at the area fractions 1 / 8 .. 7 / 8 with its two distances, which
+    no increasing tone curve changes, and the exact "table"; with minkowski_curves (a flag) also "curves", the (3, 5, 256) array that
+    report.write_minkowski_curves writes. On the device one musica_sim_minkowski call behind the contours'; on the host the
+    restatement takes the same crops. The tables are integers and there is one summary function: the values are equal to the last bit
+    on every path. With minkowski=False the rows and the launches are exactly as before."""
     options = {k: v for k, v in locals().items() if k not in ("raw", "runner", "rng")}   # every option by its name, as study_options takes them
     rng = rng or np.random.default_rng(0)
     opt = study_options(raw.shape[0], runner, **options)
@@ -1796,12 +1820,12 @@ def run_study(raw, runner, rng=None, shutters=None, translations=None, rotations
     full = (0, 0, 0, 0, shape[1], shape[0])
     scorer = (DeviceScorer if getattr(runner, "device_metrics", False) else HostScorer)(runner, opt, unalt)   # the one place that asks
     scorer.source = raw   # what reach() takes the input's change against
-    metrics = [("", scorer.similarities)] + [("_" + m.suffix, functools.partial(scorer.score, m)) for m in ROW_METRICS if m.on(getattr(opt, m.option))]
+    metrics = [("", scorer.similarities)] + [("_" + m.suffix, functools.partial(scorer.score, m)) for m in SCORED_METRICS if m.on(getattr(opt, m.option))]
     rows = []
 
     def row(alteration=None, eproc=None):
         """One row, the unaltered one without an alteration: the output produced, every comparison it has scored with every metric of
-        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, texture, granulometry, contours, displacement; then, with the ensemble's context, the row's ensemble."""
+        the study, in the order compare, tone, scales, gradients, order, lattice, blobs, spectrum, texture, granulometry, contours, minkowski, displacement; then, with the ensemble's context, the row's ensemble."""
         registered = None   # (reference key, region) of the registered comparison
         if alteration is not None:
             scorer.produce(alteration)
@@ -2138,6 +2162,13 @@ def main(argv=None):
                     help="the radius up to which --contours resolves a distance, 1 .. 32 (default 16): a contour pixel without a partner within R is lost or spurious")
     ap.add_argument("--contour-maps", metavar="DIR", default=None,
                     help="with --contours: draw the two contours of every registered row (the output's alone 85, the reference's alone 170, both 255) as BMPs into DIR")
+    ap.add_argument("--minkowski", action="store_true",
+                    help="add the shape of every comparison's level sets: the Minkowski functionals (area, perimeter, Euler characteristic) of every "
+                         "threshold set of the output, of the reference and of their minimum, exact for all 255 levels: total variation, islands, "
+                         "holes, the overlap of the upper sets and a read-out at matched area fractions that no increasing tone curve changes, "
+                         "written to minkowski_robustness.csv; on the GPU with --device-metrics / --device-alterations (musica_sim_minkowski)")
+    ap.add_argument("--minkowski-curves", metavar="DIR", default=None,
+                    help="with --minkowski: write the five curves of every row, comparison and side at the levels 1 .. 255 as one CSV a raw file into DIR")
     ap.add_argument("--blob-connectivity", type=int, default=8, choices=(4, 8), help="the neighbourhood of --blobs (default 8)")
     ap.add_argument("--order", action="store_true",
                     help="ask whether the local order of the gray levels survived: the census signs of every comparison over the 7 x 7 "
@@ -2220,7 +2251,7 @@ def main(argv=None):
                     **({"ensemble_batch": args.ensemble_batch} if args.ensemble else {}))
     shift_args = {"displacement": args.displacement, "displacement_tiles": True} if args.displacement_maps else \
                  {"displacement": args.displacement} if args.displacement else {}
-    for m in ROW_METRICS[1:]:   # --scales .. --contours, under their options' names (--tone and --symmetries are passed whatever they say)
+    for m in SCORED_METRICS[1:]:   # --scales .. --minkowski, under their options' names (--tone and --symmetries are passed whatever they say)
         if m.on(getattr(args, m.option)):
             shift_args[m.option] = getattr(args, m.option)
     if args.blobs is not None:
@@ -2229,6 +2260,8 @@ def main(argv=None):
         shift_args["texture_distances"] = args.texture_distances
     if args.contours is not None:
         shift_args.update(contour_radius=args.contour_radius, contour_maps=bool(args.contour_maps))
+    if args.minkowski and args.minkowski_curves:
+        shift_args["minkowski_curves"] = True
     for m in MOVED[1:]:                # --blurs .. --codecs: the lists as given, a flag without a list as the entry's defaults for the size
         if getattr(args, m.option):
             shift_args[m.option] = m.cli(getattr(args, m.option), args.size) if m.cli else getattr(args, m.option)
@@ -2264,6 +2297,8 @@ def main(argv=None):
         write_reach_maps(studies, args.reach_maps)
     if args.contour_maps and args.contours is not None:
         write_contour_maps(studies, args.contour_maps)
+    if args.minkowski_curves and args.minkowski:
+        write_minkowski_curves(studies, args.minkowski_curves)
     print("wrote %d alterations to %s" % (sum(len(rows) - 1 for _, rows in studies), args.out))
     return 0
 

@@ -2867,3 +2867,137 @@ def contour_row(stats, threshold, radius):
     if "planes" in stats:
         row["planes"] = np.asarray(stats["planes"], dtype=np.uint8)
     return row
+
+
+# ---- the shape of a comparison: the Minkowski functionals of the level sets ----------------------------------------------------------------
+# What does the gray-level landscape of the output look like as a shape: did the processing break one bright structure into islands, punch
+# holes into solid ones, lengthen the iso-contours? The three Minkowski functionals of every threshold set {v >= t}, area, perimeter and
+# Euler characteristic (components minus holes), are by Hadwiger's theorem all there is of additive, motion-invariant, continuous measures
+# of a planar set. They are exact in integers and for all thresholds at once: on the closed cubical complex a cell (pixel, pixel edge,
+# pixel corner) belongs to the set at t iff the MAXIMUM of its incident pixels is >= t, on the open complex iff their MINIMUM is, so eight
+# 256-bin histograms of cell values a side give every curve and V - E + F the Euler characteristics: no labelling, no float.
+# minkowski_statistics is the contract of musica_sim_minkowski (include/musica.h), whose tables are bit-identical to it;
+# minkowski_summary is what the study reports of the integers, one function for every path.
+
+MINKOWSKI_SIDES = ("a", "b", "min")    # the table's sides: the output, the reference, their pixel-wise minimum (the intersections of the upper sets)
+MINKOWSKI_KINDS = ("face", "any_h", "any_v", "any_x", "all_h", "all_v", "all_x", "outline")   # the table's rows
+MINKOWSKI_CURVES = ("area", "perimeter", "euler8", "euler4", "contact")                      # minkowski_curves' rows
+MINKOWSKI_FRACTIONS = 7                # the matched read-out: the area fractions k / 8, k = 1 .. 7
+MINKOWSKI_SIDE_KEYS = ("mean", "tv", "islands", "islands_level", "holes", "holes_level", "contact")   # each with _a and _b
+MINKOWSKI_KEYS = tuple("%s_%s" % (k, s) for s in "ab" for k in MINKOWSKI_SIDE_KEYS) + \
+    ("tv_gain", "area_l1", "perimeter_l1", "euler8_l1", "euler4_l1", "overlap", "overlap_min", "overlap_min_level", "matched_perimeter_l1", "matched_euler8_l1")
+MINKOWSKI_MATCHED_KEYS = ("fraction", "level_a", "level_b", "perimeter_a", "perimeter_b", "euler8_a", "euler8_b", "euler4_a", "euler4_b")
+
+
+def minkowski_cells(p):
+    """The eight cell-value histograms of ONE 2-D uint8 plane, which is its own domain: the (8, 256) uint32 array [kind][value] of
+    MINKOWSKI_KINDS. A pixel that does not exist takes no part in a maximum (any_*); a cell that would need one is no cell of all_*."""
+    p = np.asarray(p, dtype=np.uint8)
+    z = np.pad(p, 1)   # a frame of zeros: the maximum over the pixels that exist
+    cells = (p,
+             np.maximum(z[1:-1, :-1], z[1:-1, 1:]),                                                    # h x (w + 1)
+             np.maximum(z[:-1, 1:-1], z[1:, 1:-1]),                                                    # (h + 1) x w
+             np.maximum(np.maximum(z[:-1, :-1], z[:-1, 1:]), np.maximum(z[1:, :-1], z[1:, 1:])),      # (h + 1) x (w + 1)
+             np.minimum(p[:, :-1], p[:, 1:]),                                                          # h x (w - 1)
+             np.minimum(p[:-1, :], p[1:, :]),                                                          # (h - 1) x w
+             np.minimum(np.minimum(p[:-1, :-1], p[:-1, 1:]), np.minimum(p[1:, :-1], p[1:, 1:])),      # (h - 1) x (w - 1)
+             np.concatenate([p[0, :], p[-1, :], p[:, 0], p[:, -1]]))                                   # 2 w + 2 h
+    return np.stack([np.bincount(c.ravel(), minlength=256) for c in cells]).astype(np.uint32)
+
+
+def minkowski_statistics(a, b, regions):
+    """What musica_sim_minkowski returns for every region (ax, ay, bx, by, w, h), w, h >= 1, of two 2-D uint8 planes (side a, side b): a
+    list of dicts. The region's sub-array is its own domain: nothing outside it is read. "table": the (3, 8, 256) uint32 array
+    [side a = 0, b = 1, min(a, b) = 2][kind][value] of minkowski_cells: the number of cells of a kind (MINKOWSKI_KINDS: the pixels; the
+    pixel edges between horizontal and between vertical neighbours and the pixel corners by the maximum of their pixels that exist, the
+    outline's included; the interior edges and corners by the minimum of theirs; the 2 w + 2 h outline edges by their one pixel) whose
+    value is v. Nothing is cumulated. "pixels": w * h. Every row sums to its number of cells: w h, h (w + 1), (h + 1) w,
+    (h + 1) (w + 1), h (w - 1), (h - 1) w, (h - 1) (w - 1), 2 w + 2 h."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 2 or b.ndim != 2 or a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError("minkowski_statistics needs two 2-D uint8 planes, got %r %s and %r %s" % (a.shape, a.dtype, b.shape, b.dtype))
+    res = []
+    for region in regions:
+        ax, ay, bx, by, w, h = (int(v) for v in region)
+        if min(ax, ay, bx, by) < 0 or w < 1 or h < 1 or ax + w > a.shape[1] or ay + h > a.shape[0] or bx + w > b.shape[1] or by + h > b.shape[0]:
+            raise ValueError("region %r is empty or leaves the %r / %r planes" % (tuple(region), a.shape, b.shape))
+        sa, sb = a[ay:ay + h, ax:ax + w], b[by:by + h, bx:bx + w]
+        res.append({"table": np.stack([minkowski_cells(sa), minkowski_cells(sb), minkowski_cells(np.minimum(sa, sb))]), "pixels": w * h})
+    return res
+
+
+def minkowski_curves(table):
+    """The Minkowski functionals of the threshold sets {v >= t}, t = 0 .. 255, from a (3, 8, 256) table of minkowski_statistics: the
+    (3, 5, 256) int64 array [side][MINKOWSKI_CURVES][t]. With N_k(t) the cells of kind k whose value is at least t: area = N0;
+    perimeter = N1 + N2 - N7 - N4 - N5, the interior pixel edges with exactly one side in the set (the region's outline is not charged);
+    euler8 = N3 - N1 - N2 + N0, the 8-connected components minus the 4-connected holes (the closed complex); euler4 = N0 - N4 - N5 + N6,
+    the 4-connected components minus the 8-connected holes (the open complex); contact = N7, the outline edges that the set touches."""
+    t = np.asarray(table)
+    if t.shape != (len(MINKOWSKI_SIDES), len(MINKOWSKI_KINDS), 256) or t.dtype.kind not in "iu":
+        raise ValueError("a Minkowski table is (3, 8, 256) integers, got %r %s" % (t.shape, t.dtype))
+    N = np.cumsum(t.astype(np.int64)[:, :, ::-1], axis=2)[:, :, ::-1]
+    return np.stack([N[:, 0], N[:, 1] + N[:, 2] - N[:, 7] - N[:, 4] - N[:, 5], N[:, 3] - N[:, 1] - N[:, 2] + N[:, 0],
+                     N[:, 0] - N[:, 4] - N[:, 5] + N[:, 6], N[:, 7]], axis=1)
+
+
+def _minkowski_l1(fa, fb):
+    """sum |fa - fb| / sum (|fa| + |fb|) of two lists of integers, None where the denominator is 0."""
+    den = sum(abs(x) + abs(y) for x, y in zip(fa, fb))
+    return sum(abs(x - y) for x, y in zip(fa, fb)) / den if den else None
+
+
+def minkowski_summary(table, pixels):
+    """What the study reports of a comparison's level sets, in f64 from minkowski_statistics' (or musica_sim_minkowski's) exact integers
+    of ONE region only: one function for every study path. All sums run over the levels t = 1 .. 255; a quotient whose denominator is 0
+    is None. A dict: "pixels"; per side s in a, b "mean_s" = sum area / pixels (the mean gray level), "tv_s" = sum perimeter / pixels
+    (the anisotropic total variation a pixel, by the co-area formula), "islands_s" the maximum of euler8 and "islands_level_s" the lowest
+    level that reaches it, "holes_s" minus the minimum of euler8, floored at 0, and "holes_level_s" the lowest level of that minimum,
+    "contact_s" = sum contact / (255 * the outline's edges); "tv_gain" = tv_a / tv_b; "area_l1", "perimeter_l1", "euler8_l1",
+    "euler4_l1" = sum |f_a - f_b| / sum (|f_a| + |f_b|); "overlap" = sum area_min / sum (area_a + area_b - area_min), the Ruzicka
+    similarity sum min / sum max; "overlap_min" the smallest Jaccard index of a level whose union is not empty, "overlap_min_level" the
+    lowest such level; "matched", the tone-free read-out: for k = 1 .. 7 a dict of "fraction" k / 8, "level_a" and "level_b", on either
+    side the largest t in 0 .. 255 with 8 area(t) >= k pixels, and "perimeter", "euler8" and "euler4" of either side at its own level;
+    "matched_perimeter_l1" and "matched_euler8_l1", the same normalised L1 over the seven. Where a is a strictly increasing function of
+    b the two sides have the same family of upper sets, so the seven pairs are equal and the two distances 0.0."""
+    c = minkowski_curves(table)
+    pixels = int(pixels)
+    if pixels < 1 or int(c[0, 0, 0]) != pixels:
+        raise ValueError("the Minkowski table holds %d pixels, got pixels = %d" % (int(c[0, 0, 0]), pixels))
+    area, perimeter, euler8, euler4, contact = ([[int(v) for v in c[s, k]] for s in range(3)] for k in range(len(MINKOWSKI_CURVES)))
+    outline = int(c[0, 4, 0])   # 2 w + 2 h
+    out = {"pixels": pixels}
+    for s, name in enumerate("ab"):
+        e = euler8[s][1:]
+        top, low = max(e), min(e)
+        out.update({"mean_" + name: sum(area[s][1:]) / pixels, "tv_" + name: sum(perimeter[s][1:]) / pixels,
+                    "islands_" + name: top, "islands_level_" + name: 1 + e.index(top),
+                    "holes_" + name: max(0, -low), "holes_level_" + name: 1 + e.index(low),
+                    "contact_" + name: sum(contact[s][1:]) / (255 * outline)})
+    out = {k: out[k] for k in ("pixels",) + MINKOWSKI_KEYS[:2 * len(MINKOWSKI_SIDE_KEYS)]}
+    out["tv_gain"] = out["tv_a"] / out["tv_b"] if out["tv_b"] else None
+    for k, f in (("area", area), ("perimeter", perimeter), ("euler8", euler8), ("euler4", euler4)):
+        out[k + "_l1"] = _minkowski_l1(f[0][1:], f[1][1:])
+    union = [x + y - z for x, y, z in zip(area[0], area[1], area[2])]
+    out["overlap"] = sum(area[2][1:]) / sum(union[1:]) if sum(union[1:]) else None
+    out["overlap_min"], out["overlap_min_level"] = None, None
+    for t in range(1, 256):
+        if union[t] and (out["overlap_min"] is None or area[2][t] / union[t] < out["overlap_min"]):
+            out["overlap_min"], out["overlap_min_level"] = area[2][t] / union[t], t
+    matched = []
+    for k in range(1, MINKOWSKI_FRACTIONS + 1):
+        ta, tb = (max(t for t in range(256) if 8 * area[s][t] >= k * pixels) for s in range(2))   # t = 0 always qualifies
+        matched.append({"fraction": k / 8, "level_a": ta, "level_b": tb, "perimeter_a": perimeter[0][ta], "perimeter_b": perimeter[1][tb],
+                        "euler8_a": euler8[0][ta], "euler8_b": euler8[1][tb], "euler4_a": euler4[0][ta], "euler4_b": euler4[1][tb]})
+    out["matched_perimeter_l1"] = _minkowski_l1([m["perimeter_a"] for m in matched], [m["perimeter_b"] for m in matched])
+    out["matched_euler8_l1"] = _minkowski_l1([m["euler8_a"] for m in matched], [m["euler8_b"] for m in matched])
+    out["matched"] = matched
+    return out
+
+
+def minkowski_row(stats, curves=False):
+    """A row's *_minkowski value from ONE dict of minkowski_statistics (or sim_minkowski): minkowski_summary's dict and the exact
+    "table" as nested lists; with curves=True also "curves", minkowski_curves' (3, 5, 256) int64 array."""
+    row = dict(minkowski_summary(stats["table"], stats["pixels"]), table=np.asarray(stats["table"]).astype(np.uint32).tolist())
+    if curves:
+        row["curves"] = minkowski_curves(stats["table"])
+    return row

@@ -222,6 +222,9 @@ CONTOURS_MAX_QUERIES = 4         # MUSICA_CONTOURS_MAX_QUERIES
 CONTOURS_MAX_THRESHOLD = 1300500 # MUSICA_CONTOURS_MAX_THRESHOLD: 1020^2 + 510^2, the largest squared Sobel gradient of a uint8 plane
 CONTOURS_THRESHOLD = 4096        # the command line's default: |g| >= 64, a straight step of 16 of 255 gray levels
 CONTOURS_RADIUS = 16             # the study's default radius
+MINKOWSKI_MAX_QUERIES = 4        # MUSICA_MINKOWSKI_MAX_QUERIES
+MINKOWSKI_KINDS = 8              # MUSICA_MINKOWSKI_KINDS: face, any_h, any_v, any_x, all_h, all_v, all_x, outline
+MINKOWSKI_SIDES = 3              # MUSICA_MINKOWSKI_SIDES: a, b, min(a, b)
 
 
 def zoom_ratio(zoom):
@@ -832,6 +835,11 @@ class SimContoursResult(C.Structure):
     _fields_ = [("table_offset", C.c_uint64), ("contour_a", C.c_uint64), ("contour_b", C.c_uint64), ("pixels", C.c_uint64), ("plane_offset", C.c_uint64)]
 
 
+class SimMinkowskiResult(C.Structure):
+    """musica_sim_minkowski_result: where a query's table lies and its pixels."""
+    _fields_ = [("table_offset", C.c_uint64), ("pixels", C.c_uint64)]
+
+
 class SimBlobsResult(C.Structure):
     """musica_sim_blobs_result: where a query's table and label plane lie, its counts and its largest component."""
     _fields_ = [("table_offset", C.c_uint64), ("label_offset", C.c_uint64), ("pixels", C.c_uint64), ("changed", C.c_uint64), ("components", C.c_uint64),
@@ -1065,6 +1073,7 @@ ABI = {
     "musica_sim_cooccurrence": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimCooccurrenceResult), _U32P, C.c_uint64]),
     "musica_sim_granulometry": (C.c_int, [_VP, C.c_uint32, _U32P, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimGranulometryResult), C.POINTER(C.c_uint64), C.c_uint64]),
     "musica_sim_contours": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimContoursResult), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64]),
+    "musica_sim_minkowski": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimMinkowskiResult), _U32P, C.c_uint64]),
     "musica_sim_blobs": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimBlobsResult), C.POINTER(C.c_uint64), C.c_uint64, _U32P, C.c_uint64]),
     "musica_sim_joint": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.POINTER(SimJointResult), _U32P]),
     "musica_sim_displace": (C.c_int, [_VP, C.c_uint32, C.POINTER(SimQuery), C.c_uint32, C.POINTER(SimDisplaceResult), C.POINTER(C.c_uint64), _U32P]),
@@ -1551,7 +1560,7 @@ class MusicaProcessing:
         return out
 
     def _sim_tables(self, name, qs, result_type, dtype, words, *lead, most=None, window=False, trail=()):
-        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _contours / _reach share: the refusals of sim_<name> before any call
+        """What sim_profiles / _levels / _gradients / _order / _lattice / _blobs / _spectrum / _cooccurrence / _granulometry / _contours / _minkowski / _reach share: the refusals of sim_<name> before any call
         (most: 1 .. most queries, None: any number; window: sides of 7 at least), its arrays and the call of musica_sim_<name> with `lead`
         in front of the count and `trail` (blobs: the label plane and its length) behind the tables' length. Returns the results and the
         flat tables, `words` zeroed words of `dtype`."""
@@ -1742,6 +1751,21 @@ class MusicaProcessing:
                 lo = int(r.plane_offset)
                 d["planes"] = plane[lo:lo + int(q.w) * int(q.h)].reshape(int(q.h), int(q.w)).copy()
             out.append(d)
+        return out
+
+    def sim_minkowski(self, queries):
+        """metrics.minkowski_statistics on the device: queries as sim_compare's, (image_index, slot, ax, ay, bx, by, w, h) tuples (or
+        SimQuery) with w, h >= 1, 1 .. MINKOWSKI_MAX_QUERIES of them, all in one call: ValueError before any call for a count out of
+        range. Returns one dict per query, the same as minkowski_statistics': "table", a (3, 8, 256) uint32 array
+        [side a = 0, b = 1, min(a, b) = 2][kind][value], the number of cells of a kind (the pixels; the pixel edges and corners by the
+        maximum of their pixels; the interior ones by the minimum; the outline edges) whose value is v, and the Python int "pixels"."""
+        qs = _queries(queries)
+        per = MINKOWSKI_SIDES * MINKOWSKI_KINDS * 256
+        res, tables = self._sim_tables("minkowski", qs, SimMinkowskiResult, np.uint32, len(qs) * per, most=MINKOWSKI_MAX_QUERIES)
+        out = []
+        for r in res:
+            at = int(r.table_offset)
+            out.append({"table": tables[at:at + per].reshape(MINKOWSKI_SIDES, MINKOWSKI_KINDS, 256).copy(), "pixels": int(r.pixels)})
         return out
 
     def sim_reach(self, queries, radii):
